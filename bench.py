@@ -9,19 +9,22 @@ config 5's per-GPU share at P = 64) into the batch; same-kind launches of differ
 N > 1 project p of the job lives on rank p mod N (no data-path collective) and the ranks exchange only the
 per-project peak table with ONE RCCL all-reduce(max) inside the timed region.
 
-    python bench.py --gpus N --steps K --warmup W [--projects-per-gpu P]
+    python bench.py --gpus N --steps K --warmup W [--projects-per-gpu P] [--dump-outputs DIR] [--full] [--long]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0.  Besides the contract fields:
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps, writes its outputs (--dump-outputs)
+and prints the contract fields with what the timed region itself shows (ranks, kernel marks, host phases, peak table).
+--full measures the rest after the timed region, each figure in runs of its own:
   roofline      the dominant kernel (by HIP-event time measured live on the engine's stream during the timed steps)
                 against a ceiling MEASURED in this process on this device (tools/ubench/ceilings.hip)
   rooflines     the same for every kernel family of the timed region
   cpu_baseline  the CPU oracle (oracle/, a C++ restatement of the reference's block-serial algorithm -- NOT the
                 Rust reference, which cannot be built here) single-threaded on the same project
-  config5       (default run) 64 projects per GPU through the same batch path, aggregate Msamples/s
+  config5       (P != 64) 64 projects per GPU through the same batch path, aggregate Msamples/s
   scanned       (N = 1) the reference's normalize-then-render workflow on the same project
   configs       (N = 1) BASELINE configs 1, 3, 4: ms per render, dominant kernel, its bound and fraction
+--long prints every note string and per-kernel breakdown instead of the compact line.
 """
 import argparse
 import ctypes
@@ -329,6 +332,28 @@ def time_batch(batch, cs, steps, warmup, barrier, exchange):
         (fam, (_, per_step)), = fam0.items()
         ktimes = {fam: (marked, steps * per_step)}
     return dt, ktimes, peaks, every, marked
+
+
+DUMP_PCM_BYTES = 60 << 20   # --dump-outputs: the PCM (and its frame indices) of the 64 MB the dump may take
+
+
+def dump_outputs(d, batch, cs, peaks):
+    """What the timed path's last step handed its caller, for comparing two builds output for output: pcm.npy, every project's
+    int16 PCM as float32 (exact), shape (projects, frames, 2), and peak_table.npy, the exchanged per-project peaks.  PCM larger
+    than DUMP_PCM_BYTES is a fixed seeded sample of frames, the same frames for every project, their indices in pcm_frames.npy."""
+    os.makedirs(d, exist_ok=True)
+    n = len(batch.projects)
+    frames = cs * batch.projects[0][2].bl
+    idx = None
+    if n * frames * 2 * 4 > DUMP_PCM_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(frames, DUMP_PCM_BYTES // (n * 2 * 4 + 8), replace=False))
+        np.save(os.path.join(d, "pcm_frames.npy"), idx.astype(np.float64))
+    pcm = np.empty((n, frames if idx is None else idx.size, 2), np.float32)
+    for i in range(n):
+        p = batch.read_pcm(i, cs)
+        pcm[i] = p if idx is None else p[idx]
+    np.save(os.path.join(d, "pcm.npy"), pcm)
+    np.save(os.path.join(d, "peak_table.npy"), np.asarray(peaks, np.float32))
 
 
 def time_project(p, api, opts, reps):
@@ -738,11 +763,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--projects-per-gpu", type=int, default=1, help="projects in this GPU's batch (config 5: 64)")
     ap.add_argument("--seconds", type=float, default=SECONDS, help=argparse.SUPPRESS)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline only: no config5 / scanned / configs / ceilings of other kernels")
+    ap.add_argument("--full", action="store_true", help="after the timed region also measure everything beside the headline: the roofline "
+                                                        "with its ceilings, config5 / e2e / scanned / configs, the CPU baselines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: headline only: no config5 / scanned / configs / ceilings of other kernels")
     ap.add_argument("--no-fuse", action="store_true", help="edge-buffer model: one HBM buffer per source vertex (no source inlining)")
     ap.add_argument("--no-pack", action="store_true", help="inlined sources gather the f32 sample form (8 B/frame) instead of the packed 16-bit one")
-    ap.add_argument("--full", action="store_true", help="print the long form of the line (every note string and per-kernel breakdown) instead of the compact one")
+    ap.add_argument("--long", action="store_true", help="print the long form of the line (every note string and per-kernel breakdown) instead of the compact one")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed for rank 0's projects to DIR: pcm.npy (float32; a fixed "
+                         "sample of frames beyond 60 MB, their indices in pcm_frames.npy) and peak_table.npy")
     args = ap.parse_args()
     if args.cpu_worker is not None:
         cpu_worker(args.cpu_worker, args.seconds)
@@ -833,10 +863,12 @@ def main():
     dt = reduce_max(dt)
     device_bytes = sum(g.device_bytes() for _, _, g in batch.projects)
     host = batch.host_times()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, batch, cs, peaks)
 
     # ---- config 5 proper beside it: 64 projects per GPU through the same path (skipped when the main region already is that) ----
     c5 = None
-    want_c5 = not args.no_extras and P != 64 and not args.no_fuse and not args.no_pack
+    want_c5 = args.full and not args.no_extras and P != 64 and not args.no_fuse and not args.no_pack
     if want_c5:
         # every rank must take the same branch (the section holds collectives): 64 resident projects need ~6.5 GB
         ok = torch.tensor([1 if torch.cuda.mem_get_info()[0] > (10 << 30) else 0], dtype=torch.int32,
@@ -881,176 +913,177 @@ def main():
             # k_norm_fix check launch for grids that are not resident at once; mode 5, the resident grid, is this ONE launch)
             abf["k_sum"] = (4.0 if packed else 8.0) * N_SRC + 4.0
         survey_abf = algorithmic_bytes_per_frame(N_SRC, False, False)   # SURVEY 8(d) edge-buffer figure
-        ub = None
-        try:
-            ub = ubench()
-        except Exception as e:   # noqa: BLE001
-            sys.stderr.write("bench.py: no ubench library (%s): ceilings omitted\n" % e)
-
-        # the HBM denominator measured on this box (1 GiB each way: beyond the Infinity Cache) -- the repo's own
-        # float4 copy kernel (tools/ubench/ceilings.hip k_stream: 16 B per lane in, 16 B out) and, beside it, torch's copy_
-        own_copy_gbs = None
-        if ub is not None:
+        ub, copy_gbs, kernels, roofline = None, None, [], None
+        if args.full:   # (the ceilings are runs of their own: the plain line carries the timed region only)
             try:
-                fr = (1 << 30) // 8
-                ms_c = float(ub.td_ubench_stream(fr, 1, 1, 10))
-                if ms_c > 0:
-                    own_copy_gbs = 2.0 * fr * 8 / (ms_c * 1e-3) / 1e9
-            except Exception:   # noqa: BLE001
-                own_copy_gbs = None
-        copy_gbs = HBM_COPY_GBS
-        try:
-            n = 256 << 20
-            src = torch.empty(n, dtype=torch.float32, device="cuda").normal_()
-            dst = torch.empty_like(src)
-            for _ in range(3):
-                dst.copy_(src)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(10):
-                dst.copy_(src)
-            e1.record()
-            torch.cuda.synchronize()
-            copy_gbs = 10 * 2 * n * 4 / (e0.elapsed_time(e1) * 1e-3) / 1e9   # read + write bytes
-            del src, dst
-        except Exception:   # noqa: BLE001
+                ub = ubench()
+            except Exception as e:   # noqa: BLE001
+                sys.stderr.write("bench.py: no ubench library (%s): ceilings omitted\n" % e)
+
+            # the HBM denominator measured on this box (1 GiB each way: beyond the Infinity Cache) -- the repo's own
+            # float4 copy kernel (tools/ubench/ceilings.hip k_stream: 16 B per lane in, 16 B out) and, beside it, torch's copy_
+            own_copy_gbs = None
+            if ub is not None:
+                try:
+                    fr = (1 << 30) // 8
+                    ms_c = float(ub.td_ubench_stream(fr, 1, 1, 10))
+                    if ms_c > 0:
+                        own_copy_gbs = 2.0 * fr * 8 / (ms_c * 1e-3) / 1e9
+                except Exception:   # noqa: BLE001
+                    own_copy_gbs = None
             copy_gbs = HBM_COPY_GBS
-        torch_copy_gbs = copy_gbs
-        if own_copy_gbs and own_copy_gbs > copy_gbs:
-            copy_gbs = own_copy_gbs      # the denominator is the faster of the two copies this box shows
+            try:
+                n = 256 << 20
+                src = torch.empty(n, dtype=torch.float32, device="cuda").normal_()
+                dst = torch.empty_like(src)
+                for _ in range(3):
+                    dst.copy_(src)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(10):
+                    dst.copy_(src)
+                e1.record()
+                torch.cuda.synchronize()
+                copy_gbs = 10 * 2 * n * 4 / (e0.elapsed_time(e1) * 1e-3) / 1e9   # read + write bytes
+                del src, dst
+            except Exception:   # noqa: BLE001
+                copy_gbs = HBM_COPY_GBS
+            torch_copy_gbs = copy_gbs
+            if own_copy_gbs and own_copy_gbs > copy_gbs:
+                copy_gbs = own_copy_gbs      # the denominator is the faster of the two copies this box shows
 
-        # ---- measured ceilings for the kernels of the timed region ----
-        lens = np.array([project.assets["s%02d" % k].pcm.shape[0] for k in range(N_SRC)], dtype=np.uint32)
-        nq = 4 if frames >= 2600 * 1024 else (2 if frames >= 1800 * 1024 else 1)
-        gather_ms = gather_l2_ms = stream_ms = None
-        if ub is not None and fused and packed:
-            lp = lens.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))
-            gx = (frames + 1024 * nq - 1) // (1024 * nq)
-            per = max(1, (256 * 4) // gx)                     # the engine's batch slicing (launch_sum, kernels.hip)
-            it = 20 if P == 1 else 5
-            gather_ms = min(float(ub.td_ubench_gather(lp, N_SRC, frames, nq, it, P, per)), float(ub.td_ubench_gather(lp, N_SRC, frames, nq, it, P, 0)))
-            small = np.full(N_SRC, 1021, dtype=np.uint32)     # 64 x 4 KB: resident in every XCD's L2 (and mostly in L1)
-            sp = small.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))
-            gather_l2_ms = min(float(ub.td_ubench_gather(sp, N_SRC, frames, nq, it, P, per)), float(ub.td_ubench_gather(sp, N_SRC, frames, nq, it, P, 0)))
-        if ub is not None:
-            stream_ms = float(ub.td_ubench_stream(frames, 1, 1, 20))
-        tp, tp_tag = profiled("pmc_summary", with_tag=True)
-        tp = tp or {}
-        mode_key = "nofuse" if args.no_fuse else ("fused_f32" if args.no_pack else "fused")
+            # ---- measured ceilings for the kernels of the timed region ----
+            lens = np.array([project.assets["s%02d" % k].pcm.shape[0] for k in range(N_SRC)], dtype=np.uint32)
+            nq = 4 if frames >= 2600 * 1024 else (2 if frames >= 1800 * 1024 else 1)
+            gather_ms = gather_l2_ms = stream_ms = None
+            if ub is not None and fused and packed:
+                lp = lens.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))
+                gx = (frames + 1024 * nq - 1) // (1024 * nq)
+                per = max(1, (256 * 4) // gx)                     # the engine's batch slicing (launch_sum, kernels.hip)
+                it = 20 if P == 1 else 5
+                gather_ms = min(float(ub.td_ubench_gather(lp, N_SRC, frames, nq, it, P, per)), float(ub.td_ubench_gather(lp, N_SRC, frames, nq, it, P, 0)))
+                small = np.full(N_SRC, 1021, dtype=np.uint32)     # 64 x 4 KB: resident in every XCD's L2 (and mostly in L1)
+                sp = small.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))
+                gather_l2_ms = min(float(ub.td_ubench_gather(sp, N_SRC, frames, nq, it, P, per)), float(ub.td_ubench_gather(sp, N_SRC, frames, nq, it, P, 0)))
+            if ub is not None:
+                stream_ms = float(ub.td_ubench_stream(frames, 1, 1, 20))
+            tp, tp_tag = profiled("pmc_summary", with_tag=True)
+            tp = tp or {}
+            mode_key = "nofuse" if args.no_fuse else ("fused_f32" if args.no_pack else "fused")
 
-        kernels = []
-        for name, (ms, launches) in sorted(ktimes.items(), key=lambda kv: -kv[1][0]):
-            avg_ms = ms / max(launches, 1)                    # one launch covers the P projects of the batch
-            bytes_per_launch = abf.get(name, 0.0) * frames * P
-            gbs = bytes_per_launch / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
-            prof = (tp.get(mode_key) or {}).get(name) or {}
-            row = {"kernel": name, "avg_ms": round(avg_ms, 5), "launches": int(launches), "projects_per_launch": P,
-                   "algorithmic_bytes_per_launch": int(bytes_per_launch), "achieved": round(gbs, 1), "unit": "GB/s",
-                   # fabric-side (L2-miss) bytes per launch from the committed rocprofv3 --pmc passes of this command -- the counters
-                   # cannot be read from inside a process that is being timed; `traffic_profiled` says which file and how it was made
-                   "traffic": prof.get("hbm_side_bytes_per_launch"),
-                   "traffic_profiled": None if "hbm_side_bytes_per_launch" not in prof else {
-                       "bytes_per_launch": prof["hbm_side_bytes_per_launch"], "l2_hit_rate": prof.get("l2_hit_rate"),
-                       "avg_us_rocprof": prof.get("avg_us"),
-                       "profile": "profiles/%s_pmc_summary.json" % tp_tag,
-                       "note": "separate rocprofv3 --pmc passes of this command (FETCH_SIZE x 2 per the gfx950 half-count rule + "
-                               "WRITE_SIZE); fabric-side bytes: Infinity-Cache hits are included, so HBM bytes are at most this"}}
-            if name == "k_sum" and fused and packed and gather_ms and gather_ms > 0:
-                ceil_gbs = bytes_per_launch / (gather_ms * 1e-3) / 1e9
-                compulsory = (int(lens.sum()) * 4 + (4 if single_pass else 8) * frames) * P
-                row.update({"bound": "cache-gather ceiling (measured)", "peak": round(ceil_gbs, 1), "frac": round(gbs / ceil_gbs, 4),
-                            "ceiling_ms": round(gather_ms, 5),
-                            "ceiling_l2_resident_GBs": None if not gather_l2_ms else round(bytes_per_launch / (gather_l2_ms * 1e-3) / 1e9, 1),
-                            "frac_of_l2_resident_ceiling": None if not gather_l2_ms else round(gather_l2_ms / avg_ms, 4),
-                            "hbm_compulsory_bytes": compulsory,
-                            "hbm_compulsory_frac": round(compulsory / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                            "bytes_per_frame": abf[name],
-                            "note": k_sum_roofline_note(single_pass, lens.sum() * 4 / 1e6, frames, P)})
-            else:
-                row.update({"bound": "hbm", "peak": HBM_PEAK_GBS, "frac": round(gbs / HBM_PEAK_GBS, 4),
-                            "frac_of_measured_copy": round(gbs / copy_gbs, 4), "bytes_per_frame": abf.get(name)})
-                if name == "k_scale" and stream_ms and stream_ms > 0:
-                    row["stream_ceiling_ms"] = round(stream_ms, 5)
-                    row["note"] = ("Normalize pass B: 8 B raw sum in + 4 B PCM out per frame; stream_ceiling_ms = a bare 8 B in / 8 B out "
-                                   "float4 stream over the same %d frames (tools/ubench/ceilings.hip), i.e. launch ramp + tail included" % frames)
-            kernels.append(row)
-        dom = kernels[0] if kernels else None
-        rocprof_kernel = None
-        if dom:
-            if dom["kernel"] == "k_sum":
-                rocprof_kernel = (("tdk::k_sum16w<4, true>" if nq == 4 else "tdk::k_sum16w<2, true>" if nq == 2 else "tdk::k_sum<3>") if packed
-                                  else ("tdk::k_sum16w<2, false>" if frames >= 1800 * 1024 else "tdk::k_sum<2>")) if fused else "tdk::k_sum<1>"
-            else:
-                rocprof_kernel = "tdk::" + dom["kernel"]
-        roofline = None
-        if dom:
-            roofline = {k: dom.get(k) for k in ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "traffic_profiled",
-                                                 "bytes_per_frame", "ceiling_ms", "ceiling_l2_resident_GBs", "frac_of_l2_resident_ceiling",
-                                                 "hbm_compulsory_bytes", "hbm_compulsory_frac", "frac_of_measured_copy", "note") if k in dom}
-            roofline["avg_ms"] = dom["avg_ms"]
-            roofline["rocprof_kernel"] = rocprof_kernel   # the engine times launch FAMILIES; this instantiation is the rocprofv3 name
-            if "hbm_compulsory_bytes" in dom:
-                # the same launch against the HBM roofline in its plain form: the bytes that must cross HBM once per launch
-                # (every sample table once + the output write) over the launch time, against 8 TB/s
-                hb = dom["hbm_compulsory_bytes"] / (dom["avg_ms"] * 1e-3) / 1e9
-                roofline["hbm_form"] = {"bound": "hbm", "achieved": round(hb, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                        "frac": round(hb / HBM_PEAK_GBS, 4), "bytes": dom["hbm_compulsory_bytes"],
-                                        "note": "compulsory HBM bytes only: the launch is bound by its cache-served gathers (`bound` above), not by HBM"}
-            roofline["measured_copy_GBs"] = round(copy_gbs, 1)
-            roofline["copy_GBs"] = {"own_float4_kernel": None if not own_copy_gbs else round(own_copy_gbs, 1), "torch_copy_": round(torch_copy_gbs, 1),
-                                    "guide_float4": HBM_COPY_GBS, "bytes_each_way": 1 << 30}
-            vp = ((profiled("valu") or {}).get("config2") or {}).get(dom["kernel"])
-            if vp:
-                roofline["valu_profiled"] = dict(vp, profile="profiles/%s_valu.json" % PROFILE_TAG)
-                if fused and packed and dom["kernel"] == "k_sum" and vp.get("SQ_INSTS_VALU"):
-                    # what the launch costs in VALU issue alone: wave-level instructions (profiled) x the measured issue time of
-                    # their class -- SDWA conversions and packed f32, 1.75 ns per wave and SIMD (tools/ubench/issue_rate.hip) --
-                    # over the chip's 1 024 SIMDs: the second thing the launch is limited by, beside the cache hierarchy
-                    roofline["valu_issue_ms"] = round(vp["SQ_INSTS_VALU"] * 1.75e-9 / 1024.0 * 1e3, 5)
-                    roofline["frac_valu_issue"] = round(roofline["valu_issue_ms"] / dom["avg_ms"], 4)
-            if dom.get("traffic") and dom.get("hbm_compulsory_bytes"):
-                roofline["wasted_vs_compulsory"] = round(dom["traffic"] / dom["hbm_compulsory_bytes"], 2)
-                roofline["traffic_source"] = "profiles/%s_pmc_summary.json" % tp_tag   # (rocprofv3 --pmc FETCH_SIZE x 2 [gfx950 half-count] + WRITE_SIZE, per launch: NOTES.md#roofline)
-            if fused and packed and dom["kernel"] == "k_sum":
-                # two hardware-denominated readings beside the measured ceiling (guide figures only, no ubench):
-                #  frac_of_l2_peak: the gathered + written bytes against the aggregate L2 bandwidth;
-                #  l2_mall_split: the bytes split by the PROFILED L2 hit rate -- hits at the guide's L2 gather rate, the rest at
-                #  its Infinity-Cache gather rate, one after the other -- as a time floor for this launch
-                gathered = dom["algorithmic_bytes_per_launch"]
-                roofline["frac_of_l2_peak"] = round(dom["achieved"] / L2_PEAK_GBS, 4)
-                roofline["l2_peak_GBs"] = L2_PEAK_GBS
-                hit = ((dom.get("traffic_profiled") or {}).get("l2_hit_rate"))
-                if hit is not None:
-                    floor_ms = (gathered * hit / (L2_GATHER_GBS * 1e9) + gathered * (1.0 - hit) / (MALL_GATHER_GBS * 1e9)) * 1e3
-                    roofline["l2_mall_split"] = {"l2_hit_rate_profiled": hit, "l2_gather_GBs": L2_GATHER_GBS, "mall_gather_GBs": MALL_GATHER_GBS,
-                                                 "floor_ms": round(floor_ms, 5), "frac": round(floor_ms / dom["avg_ms"], 4),
-                                                 "note": "bytes x hit rate / 17.8 TB/s + bytes x (1 - hit rate) / 8.6 TB/s (MI355X_MICROARCH.md, "
-                                                         "'Indexed rows: gather'), hit rate from profiles/%s_pmc_summary.json" % tp_tag}
-                    # Two guide-priced floors for THIS launch's split, both printed, the HARDER one as `frac` (round-5 review: the
-                    # gathers are contiguous 64 B per lane -- a wave reads 4 KB in a row -- so the hits are priced at the L2's STREAM
-                    # rate, 34.5 TB/s, not at the rate of random 1 152-byte rows; the misses at the Infinity-Cache rate either way):
-                    #   frac_l2_stream   = (bytes x hit / 34.5 TB/s + bytes x (1 - hit) / 8.6 TB/s) / measured
-                    #   frac_gather_rows = (bytes x hit / 17.8 TB/s + bytes x (1 - hit) / 8.6 TB/s) / measured   (round 5's `frac`)
-                    # No dependency on this repo's own ceiling kernel, which stays beside them (frac_of_ubench_ceiling).
-                    stream_floor_ms = (gathered * hit / (L2_PEAK_GBS * 1e9) + gathered * (1.0 - hit) / (MALL_GATHER_GBS * 1e9)) * 1e3
-                    roofline["frac_of_ubench_ceiling"] = roofline.get("frac")
-                    roofline["ubench_ceiling_GBs"] = roofline.get("peak")
-                    roofline["frac_gather_rows"] = round(floor_ms / dom["avg_ms"], 4)
-                    roofline["peak_gather_rows_GBs"] = round(gathered / (floor_ms * 1e-3) / 1e9, 1)
-                    roofline["frac_l2_stream"] = round(stream_floor_ms / dom["avg_ms"], 4)
-                    roofline["peak_l2_stream_GBs"] = round(gathered / (stream_floor_ms * 1e-3) / 1e9, 1)
-                    roofline["l2_hit_profiled"] = hit
-                    roofline["bound"] = "l2 stream + infinity cache"   # (hits at 34.5 TB/s, misses at 8.6 TB/s: NOTES.md#roofline)
-                    roofline["peak"] = roofline["peak_l2_stream_GBs"]
-                    roofline["frac"] = roofline["frac_l2_stream"]
+            kernels = []
+            for name, (ms, launches) in sorted(ktimes.items(), key=lambda kv: -kv[1][0]):
+                avg_ms = ms / max(launches, 1)                    # one launch covers the P projects of the batch
+                bytes_per_launch = abf.get(name, 0.0) * frames * P
+                gbs = bytes_per_launch / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
+                prof = (tp.get(mode_key) or {}).get(name) or {}
+                row = {"kernel": name, "avg_ms": round(avg_ms, 5), "launches": int(launches), "projects_per_launch": P,
+                       "algorithmic_bytes_per_launch": int(bytes_per_launch), "achieved": round(gbs, 1), "unit": "GB/s",
+                       # fabric-side (L2-miss) bytes per launch from the committed rocprofv3 --pmc passes of this command -- the counters
+                       # cannot be read from inside a process that is being timed; `traffic_profiled` says which file and how it was made
+                       "traffic": prof.get("hbm_side_bytes_per_launch"),
+                       "traffic_profiled": None if "hbm_side_bytes_per_launch" not in prof else {
+                           "bytes_per_launch": prof["hbm_side_bytes_per_launch"], "l2_hit_rate": prof.get("l2_hit_rate"),
+                           "avg_us_rocprof": prof.get("avg_us"),
+                           "profile": "profiles/%s_pmc_summary.json" % tp_tag,
+                           "note": "separate rocprofv3 --pmc passes of this command (FETCH_SIZE x 2 per the gfx950 half-count rule + "
+                                   "WRITE_SIZE); fabric-side bytes: Infinity-Cache hits are included, so HBM bytes are at most this"}}
+                if name == "k_sum" and fused and packed and gather_ms and gather_ms > 0:
+                    ceil_gbs = bytes_per_launch / (gather_ms * 1e-3) / 1e9
+                    compulsory = (int(lens.sum()) * 4 + (4 if single_pass else 8) * frames) * P
+                    row.update({"bound": "cache-gather ceiling (measured)", "peak": round(ceil_gbs, 1), "frac": round(gbs / ceil_gbs, 4),
+                                "ceiling_ms": round(gather_ms, 5),
+                                "ceiling_l2_resident_GBs": None if not gather_l2_ms else round(bytes_per_launch / (gather_l2_ms * 1e-3) / 1e9, 1),
+                                "frac_of_l2_resident_ceiling": None if not gather_l2_ms else round(gather_l2_ms / avg_ms, 4),
+                                "hbm_compulsory_bytes": compulsory,
+                                "hbm_compulsory_frac": round(compulsory / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                                "bytes_per_frame": abf[name],
+                                "note": k_sum_roofline_note(single_pass, lens.sum() * 4 / 1e6, frames, P)})
                 else:
-                    roofline["bound"] = "l2+infinity-cache gather (ceiling measured in-process: tools/ubench)"
-            if fused and dom["kernel"] == "k_sum":
-                roofline["survey_model"] = {
-                    "bytes_per_frame": survey_abf["k_sum"],
-                    "note": "SURVEY 8(d)'s edge-buffer figure (8k+8) for the same launch time -- not a bandwidth: the k source edge "
-                            "buffers do not exist in this mode (--no-fuse runs that model, where the kernel is HBM-bound)",
-                    "equivalent_GBs": round(survey_abf["k_sum"] * frames * P / (dom["avg_ms"] * 1e-3) / 1e9, 1)}
+                    row.update({"bound": "hbm", "peak": HBM_PEAK_GBS, "frac": round(gbs / HBM_PEAK_GBS, 4),
+                                "frac_of_measured_copy": round(gbs / copy_gbs, 4), "bytes_per_frame": abf.get(name)})
+                    if name == "k_scale" and stream_ms and stream_ms > 0:
+                        row["stream_ceiling_ms"] = round(stream_ms, 5)
+                        row["note"] = ("Normalize pass B: 8 B raw sum in + 4 B PCM out per frame; stream_ceiling_ms = a bare 8 B in / 8 B out "
+                                       "float4 stream over the same %d frames (tools/ubench/ceilings.hip), i.e. launch ramp + tail included" % frames)
+                kernels.append(row)
+            dom = kernels[0] if kernels else None
+            rocprof_kernel = None
+            if dom:
+                if dom["kernel"] == "k_sum":
+                    rocprof_kernel = (("tdk::k_sum16w<4, true>" if nq == 4 else "tdk::k_sum16w<2, true>" if nq == 2 else "tdk::k_sum<3>") if packed
+                                      else ("tdk::k_sum16w<2, false>" if frames >= 1800 * 1024 else "tdk::k_sum<2>")) if fused else "tdk::k_sum<1>"
+                else:
+                    rocprof_kernel = "tdk::" + dom["kernel"]
+            roofline = None
+            if dom:
+                roofline = {k: dom.get(k) for k in ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "traffic_profiled",
+                                                     "bytes_per_frame", "ceiling_ms", "ceiling_l2_resident_GBs", "frac_of_l2_resident_ceiling",
+                                                     "hbm_compulsory_bytes", "hbm_compulsory_frac", "frac_of_measured_copy", "note") if k in dom}
+                roofline["avg_ms"] = dom["avg_ms"]
+                roofline["rocprof_kernel"] = rocprof_kernel   # the engine times launch FAMILIES; this instantiation is the rocprofv3 name
+                if "hbm_compulsory_bytes" in dom:
+                    # the same launch against the HBM roofline in its plain form: the bytes that must cross HBM once per launch
+                    # (every sample table once + the output write) over the launch time, against 8 TB/s
+                    hb = dom["hbm_compulsory_bytes"] / (dom["avg_ms"] * 1e-3) / 1e9
+                    roofline["hbm_form"] = {"bound": "hbm", "achieved": round(hb, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                            "frac": round(hb / HBM_PEAK_GBS, 4), "bytes": dom["hbm_compulsory_bytes"],
+                                            "note": "compulsory HBM bytes only: the launch is bound by its cache-served gathers (`bound` above), not by HBM"}
+                roofline["measured_copy_GBs"] = round(copy_gbs, 1)
+                roofline["copy_GBs"] = {"own_float4_kernel": None if not own_copy_gbs else round(own_copy_gbs, 1), "torch_copy_": round(torch_copy_gbs, 1),
+                                        "guide_float4": HBM_COPY_GBS, "bytes_each_way": 1 << 30}
+                vp = ((profiled("valu") or {}).get("config2") or {}).get(dom["kernel"])
+                if vp:
+                    roofline["valu_profiled"] = dict(vp, profile="profiles/%s_valu.json" % PROFILE_TAG)
+                    if fused and packed and dom["kernel"] == "k_sum" and vp.get("SQ_INSTS_VALU"):
+                        # what the launch costs in VALU issue alone: wave-level instructions (profiled) x the measured issue time of
+                        # their class -- SDWA conversions and packed f32, 1.75 ns per wave and SIMD (tools/ubench/issue_rate.hip) --
+                        # over the chip's 1 024 SIMDs: the second thing the launch is limited by, beside the cache hierarchy
+                        roofline["valu_issue_ms"] = round(vp["SQ_INSTS_VALU"] * 1.75e-9 / 1024.0 * 1e3, 5)
+                        roofline["frac_valu_issue"] = round(roofline["valu_issue_ms"] / dom["avg_ms"], 4)
+                if dom.get("traffic") and dom.get("hbm_compulsory_bytes"):
+                    roofline["wasted_vs_compulsory"] = round(dom["traffic"] / dom["hbm_compulsory_bytes"], 2)
+                    roofline["traffic_source"] = "profiles/%s_pmc_summary.json" % tp_tag   # (rocprofv3 --pmc FETCH_SIZE x 2 [gfx950 half-count] + WRITE_SIZE, per launch: NOTES.md#roofline)
+                if fused and packed and dom["kernel"] == "k_sum":
+                    # two hardware-denominated readings beside the measured ceiling (guide figures only, no ubench):
+                    #  frac_of_l2_peak: the gathered + written bytes against the aggregate L2 bandwidth;
+                    #  l2_mall_split: the bytes split by the PROFILED L2 hit rate -- hits at the guide's L2 gather rate, the rest at
+                    #  its Infinity-Cache gather rate, one after the other -- as a time floor for this launch
+                    gathered = dom["algorithmic_bytes_per_launch"]
+                    roofline["frac_of_l2_peak"] = round(dom["achieved"] / L2_PEAK_GBS, 4)
+                    roofline["l2_peak_GBs"] = L2_PEAK_GBS
+                    hit = ((dom.get("traffic_profiled") or {}).get("l2_hit_rate"))
+                    if hit is not None:
+                        floor_ms = (gathered * hit / (L2_GATHER_GBS * 1e9) + gathered * (1.0 - hit) / (MALL_GATHER_GBS * 1e9)) * 1e3
+                        roofline["l2_mall_split"] = {"l2_hit_rate_profiled": hit, "l2_gather_GBs": L2_GATHER_GBS, "mall_gather_GBs": MALL_GATHER_GBS,
+                                                     "floor_ms": round(floor_ms, 5), "frac": round(floor_ms / dom["avg_ms"], 4),
+                                                     "note": "bytes x hit rate / 17.8 TB/s + bytes x (1 - hit rate) / 8.6 TB/s (MI355X_MICROARCH.md, "
+                                                             "'Indexed rows: gather'), hit rate from profiles/%s_pmc_summary.json" % tp_tag}
+                        # Two guide-priced floors for THIS launch's split, both printed, the HARDER one as `frac` (round-5 review: the
+                        # gathers are contiguous 64 B per lane -- a wave reads 4 KB in a row -- so the hits are priced at the L2's STREAM
+                        # rate, 34.5 TB/s, not at the rate of random 1 152-byte rows; the misses at the Infinity-Cache rate either way):
+                        #   frac_l2_stream   = (bytes x hit / 34.5 TB/s + bytes x (1 - hit) / 8.6 TB/s) / measured
+                        #   frac_gather_rows = (bytes x hit / 17.8 TB/s + bytes x (1 - hit) / 8.6 TB/s) / measured   (round 5's `frac`)
+                        # No dependency on this repo's own ceiling kernel, which stays beside them (frac_of_ubench_ceiling).
+                        stream_floor_ms = (gathered * hit / (L2_PEAK_GBS * 1e9) + gathered * (1.0 - hit) / (MALL_GATHER_GBS * 1e9)) * 1e3
+                        roofline["frac_of_ubench_ceiling"] = roofline.get("frac")
+                        roofline["ubench_ceiling_GBs"] = roofline.get("peak")
+                        roofline["frac_gather_rows"] = round(floor_ms / dom["avg_ms"], 4)
+                        roofline["peak_gather_rows_GBs"] = round(gathered / (floor_ms * 1e-3) / 1e9, 1)
+                        roofline["frac_l2_stream"] = round(stream_floor_ms / dom["avg_ms"], 4)
+                        roofline["peak_l2_stream_GBs"] = round(gathered / (stream_floor_ms * 1e-3) / 1e9, 1)
+                        roofline["l2_hit_profiled"] = hit
+                        roofline["bound"] = "l2 stream + infinity cache"   # (hits at 34.5 TB/s, misses at 8.6 TB/s: NOTES.md#roofline)
+                        roofline["peak"] = roofline["peak_l2_stream_GBs"]
+                        roofline["frac"] = roofline["frac_l2_stream"]
+                    else:
+                        roofline["bound"] = "l2+infinity-cache gather (ceiling measured in-process: tools/ubench)"
+                if fused and dom["kernel"] == "k_sum":
+                    roofline["survey_model"] = {
+                        "bytes_per_frame": survey_abf["k_sum"],
+                        "note": "SURVEY 8(d)'s edge-buffer figure (8k+8) for the same launch time -- not a bandwidth: the k source edge "
+                                "buffers do not exist in this mode (--no-fuse runs that model, where the kernel is HBM-bound)",
+                        "equivalent_GBs": round(survey_abf["k_sum"] * frames * P / (dom["avg_ms"] * 1e-3) / 1e9, 1)}
         out = {
             "metric": "offline render Msamples/sec (stereo 48 kHz) + % HBM roofline, 64-vertex graph",
             "value": round(value, 2),
@@ -1097,7 +1130,7 @@ def main():
             out["config5"] = c5
             if e2e:
                 out["e2e"] = e2e
-        if world == 1 and not args.no_extras:
+        if world == 1 and args.full and not args.no_extras:
             sb0, fb0, g0 = batch.projects[0]
             # the reference's recommended workflow: `normalize` (scan_exact, state.rs:473) then `render`; the scan is paid
             # once per project edit, the render each time -- both are reported
@@ -1171,7 +1204,7 @@ def main():
                 out["configs"] = other_configs(api, workloads, ub, chain_ns)
             except Exception as e:   # noqa: BLE001
                 out["configs"] = {"error": str(e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(project, frames)
             out["gpu_over_cpu_1thread"] = round(out["value"] / out["cpu_baseline"]["value"], 1)
             if not args.no_extras:
@@ -1183,7 +1216,7 @@ def main():
                 if allc:
                     out["cpu_baseline_all_cores"] = allc
                     out["gpu_over_cpu_all_cores"] = round(out["value"] / allc["value"], 1)
-        result_line = json.dumps(out if args.full else compact(out))
+        result_line = json.dumps(out if args.long else compact(out))
     if use_dist:
         dist.barrier()
         dist.destroy_process_group()

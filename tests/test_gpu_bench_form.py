@@ -174,6 +174,34 @@ def test_bench_one_rank_over_rccl():
     assert out["ranks"]["n"] == 1 and out["ranks"]["exchange_ms"] >= 0.0 and out["ranks"]["start_skew_us"] == 0.0
 
 
+def test_bench_plain_run_dumps_the_last_steps_outputs(oracle, tmp_path):
+    """A plain `bench.py --gpus 1` times exactly --steps steps and carries the timed region only (no roofline, configs or CPU
+    baseline: those are --full's); --dump-outputs writes the last step's PCM and peak table -- the oracle's; --full adds the
+    roofline."""
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        env.pop(k, None)
+    d = tmp_path / "out"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--seconds", "6"]
+    r = subprocess.run(cmd + ["--dump-outputs", str(d)], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = json.loads([l for l in r.stdout.splitlines() if l.strip()][-1])
+    assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["value"] > 0 and out["unit"] == "Msamples/s" and out["dtype"] == "f32"
+    for k in ("roofline", "configs", "config5", "scanned", "cpu_baseline", "edge_buffer_mode"):
+        assert k not in out, k
+    p = W.config2(seconds=6.0)
+    osb, ofb, og = p.build(oracle)
+    ref, _ = og.render_all(osb, ofb, p.cs, 16, want_f32=False)
+    pcm = np.load(d / "pcm.npy")
+    assert pcm.dtype == np.float32 and pcm.shape == (1,) + ref.shape and np.array_equal(pcm[0], ref.astype(np.float32))
+    assert np.load(d / "peak_table.npy").tolist() == [np.float32(og.get_normalization_value("sum"))]
+    r = subprocess.run(cmd + ["--full", "--no-extras", "--no-cpu-baseline"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                       text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = json.loads([l for l in r.stdout.splitlines() if l.strip()][-1])
+    assert out["roofline"]["kernel"] and out["roofline"]["frac"] > 0
+
+
 def test_bench_says_so_when_the_librarys_communicator_cannot_be_made():
     """Without RCCL behind the library (TD_RCCL_DISABLE: what a missing or broken librccl looks like) the ranks agree that
     td_comm_init failed and run the reduction through torch.distributed on the engine's table -- and the line says so, loudly."""

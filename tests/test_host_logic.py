@@ -164,15 +164,13 @@ def test_refresh_takes_output_settings(api):
 
 
 def test_reference_example_scripts_parse(api):
-    """The reference's own example scripts run through the front-end up to the first missing asset file
-    (their /home/cody/... paths do not exist anywhere but the author's machine)."""
-    ref = "/root/reference"
-    if not os.path.isdir(ref):
-        pytest.skip("reference tree not present on this box")
-    for f in ("project.lua", "examples/neg-adsr-env-example.lua", "examples/sample-project.lua",
-              "examples/sample-synth-adsr-lv2fx-example.lua", "examples/stream.lua"):
+    """Scripts shaped like the reference's example projects (tests/golden/scripts: its whole vocabulary -- LV2 plug-ins and
+    parameters, resources, streams, comments, table variables, booleans, a missing semicolon) run through the front-end up to
+    the first missing asset file (their paths do not exist)."""
+    d = os.path.join(ROOT, "tests", "golden", "scripts")
+    for f in ("full_graph.lua", "looped_envelope.lua", "synth_chain.lua", "streamed.lua"):
         s = api.State("", 48000, 1024)
-        assert not s.refresh(open(os.path.join(ref, f)).read())
+        assert not s.refresh(open(os.path.join(d, f)).read())
         assert "could not open file" in api.last_error()
         assert "set_output(" in s.dump_calls() and "connect(" in s.dump_calls()
 
@@ -209,6 +207,40 @@ def test_bench_helpers_format_in_both_normalize_forms():
         assert ("(4k+4)" in note) == single and "20 MB" in note
     assert mod.algorithmic_bytes_per_frame(64, True, True)["k_sum"] == 4.0 * 64 + 8.0
     assert mod.algorithmic_bytes_per_frame(64, False, False)["k_sum"] == 8.0 * 64 + 8.0
+
+
+def test_bench_dump_outputs_is_exact_and_bounded(tmp_path):
+    """bench.py --dump-outputs: every project's PCM as float32 (exact), the peak table; a batch whose PCM exceeds the budget is
+    dumped as the same seeded sample of frames every time, under 64 MB in all."""
+    import bench
+
+    class G:
+        bl = 1024
+
+    class FakeBatch:
+        def __init__(self, n, cs):
+            self.projects = [(None, None, G()) for _ in range(n)]
+            self.pcm = [np.random.default_rng(i).integers(-32768, 32768, (cs * 1024, 2)).astype(np.int16) for i in range(n)]
+
+        def read_pcm(self, i, cs):
+            return self.pcm[i]
+
+    small = FakeBatch(2, 3)
+    bench.dump_outputs(str(tmp_path / "a"), small, 3, np.array([0.5, 0.25], np.float32))
+    pcm = np.load(tmp_path / "a" / "pcm.npy")
+    assert pcm.dtype == np.float32 and pcm.shape == (2, 3 * 1024, 2) and np.array_equal(pcm, np.stack(small.pcm).astype(np.float32))
+    assert np.load(tmp_path / "a" / "peak_table.npy").tolist() == [0.5, 0.25]
+    assert not (tmp_path / "a" / "pcm_frames.npy").exists()
+    big = FakeBatch(3, 2813)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), big, 2813, np.ones(3, np.float32))
+    total = sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b"))
+    assert total <= 64 << 20, total
+    idx = np.load(tmp_path / "b" / "pcm_frames.npy")
+    pcm = np.load(tmp_path / "b" / "pcm.npy")
+    assert idx.dtype == np.float64 and pcm.shape == (3, idx.size, 2) and np.all(np.diff(idx) > 0)
+    assert np.array_equal(pcm[2], big.pcm[2][idx.astype(np.int64)].astype(np.float32))
+    assert np.array_equal(idx, np.load(tmp_path / "c" / "pcm_frames.npy")) and np.array_equal(pcm, np.load(tmp_path / "c" / "pcm.npy"))
 
 
 def test_bench_line_compact_form_fits_the_drivers_tail():
