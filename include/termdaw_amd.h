@@ -160,6 +160,23 @@ int td_graph_read_f32(const td_graph* g, float* out, size_t n_floats);
 /* Per-block absolute peak of the last render's un-quantised output (n_blocks floats) reduced on the
  * device to one float: used for the per-project peak table of the multi-GPU batch. */
 float td_graph_output_peak(const td_graph* g);
+/* Stems: vertices rendered to PCM of their own beside the output, in the same render.  Stem X of a render is what the render
+ * would give with set_output(X) (graph.rs:141-148): X and everything upstream of it are computed, reaching the output or not,
+ * exactly as that render would compute them.  The renders td_graph_render_all, _async and _resampled write every stem at the
+ * output's bit depth, frame count and (resampled) rate; td_graph_render_block ignores the stems (block pulls compute the
+ * output's plan alone: with stems set, every pull re-plans twice -- to the output's plan and back -- and settles a guarded
+ * verdict still out first), and a td_batch render fails while a member graph has stems set.  A stem may sit downstream of
+ * the output: the output's f32 frames are then kept whatever "output_f32" says.  Under the guarded modes ("band_mode"
+ * 2, "sine_mode" 2) everything upstream of a stem other than the output takes the exact kernels.
+ * td_graph_set_stems replaces the list (n = 0 clears it; td_graph_reset clears it too); an unknown or repeated name -> 0 and
+ * the list unchanged.  A stem may name the output vertex: its bytes are then the output's. */
+int td_graph_set_stems(td_graph* g, const char* const* names, size_t n);
+size_t td_graph_stem_count(const td_graph* g);
+/* Stem i of the last render: interleaved, the same words as td_graph_output_pcm_device (NULL: not rendered). */
+const void* td_graph_stem_pcm_device(const td_graph* g, size_t i);
+int td_graph_read_stem_pcm(const td_graph* g, size_t i, void* out, size_t bytes);
+/* max |x| over the frames of stem i quantised in the last render (a NaN frame: NaN). */
+float td_graph_stem_peak(const td_graph* g, size_t i);
 /* Timing hook for bench.py: enqueue one full render on the graph's stream without the final host
  * synchronisation (td_graph_sync waits).  Same work as td_graph_render_all. */
 size_t td_graph_render_all_async(td_graph* g, const td_samplebank* sb, td_flowwbank* fb, size_t n_blocks, int bits);
@@ -378,6 +395,11 @@ int td_state_scan_exact(td_state* s);                                     /* sta
 /* State::render state.rs:477-577: renders cs blocks and writes the integer WAV to output_file
  * (relative to the process working directory, like hound::WavWriter::create at state.rs:514). path_override may be NULL. */
 int td_state_render(td_state* s, const char* path_override);
+/* Stems of the State's renders (td_graph_set_stems): the names are resolved at each render -- an unknown one fails the render
+ * before any file is written.  td_state_render then writes stem X next to the output as "<path minus .wav>.<X>.wav", same
+ * header; characters of X outside [A-Za-z0-9._-] become '_', and two stems that map to one file name are an error.
+ * n = 0 clears the list. */
+int td_state_set_stems(td_state* s, const char* const* names, size_t n);
 /* Same render, PCM left in memory: copies frames*2 words to out (may be NULL to query the size). */
 size_t td_state_render_to_memory(td_state* s, void* out, size_t bytes);
 /* The same render, returned as a view of the library's own page-locked read-back buffer (interleaved PCM,

@@ -1,9 +1,11 @@
-"""Headless render driver:  python -m termdaw_amd <project_dir> [--scan] [-o out.wav]
+"""Headless render driver:  python -m termdaw_amd <project_dir> [--scan] [-o out.wav] [--stem NAME ...]
                         python -m termdaw_amd <project_dir> --stream [--realtime] [-o out.wav] < events
 
 The reference renders only from its TUI (`render` / `normalize` commands, ui_workflow.rs:120-133); the first form is
 the same sequence -- State::refresh, optionally State::scan_exact, State::render -- without the TUI.
 <project_dir> holds project.toml ([settings] main, buffer_length, project_samplerate) and the project script.
+--stem NAME (repeatable) renders vertex NAME in the same pass as well, to "<output minus .wav>.NAME.wav" -- what the
+render would write with set_output(NAME) -- and prints one line per stem: its path and peak ("clips" above 1.0).
 
 --stream is the reference's stream workflow (stream_workflow.rs:41-105) without the audio device: events for the
 streams the script declared (declare_stream) arrive on stdin, blocks are pulled one at a time at the playhead.
@@ -15,6 +17,7 @@ and stops.  --realtime paces the pulls like the reference (half a second ahead o
 stream is rendered as fast as the events arrive.  The pulled blocks are written as a 16-bit WAV.
 """
 import argparse
+import re
 import sys
 import time
 
@@ -33,6 +36,8 @@ def main(argv=None):
     ap.add_argument("--exact-sine", action="store_true",
                     help="debug_sine / synth vertices evaluate glibc's sinf bit for bit (default: the tolerance-class device sine, <= 1e-6 RMS; "
                          "config 3's oscillators take 0.32 instead of 0.09 ms)")
+    ap.add_argument("--stem", action="append", default=[], metavar="NAME",
+                    help="also render vertex NAME to <output minus .wav>.NAME.wav in the same pass (repeatable)")
     ap.add_argument("--stream", action="store_true", help="stream workflow: events from stdin, block pulls at the playhead")
     ap.add_argument("--realtime", action="store_true", help="with --stream: pace the pulls against the wall clock")
     args = ap.parse_args(argv)
@@ -49,13 +54,30 @@ def main(argv=None):
         print("TermDaw: refresh failed: %s" % api.last_error(), file=sys.stderr)
         return 1
     t1 = time.perf_counter()
-    if args.scan:
-        s.scan_exact()
-    s.render(args.output)
+    try:
+        if args.stem:
+            s.set_stems(args.stem)
+        if args.scan:
+            s.scan_exact()
+        s.render(args.output)
+    except api.TermdawError as e:
+        print("TermDaw: render failed: %s" % e, file=sys.stderr)
+        return 1
     t2 = time.perf_counter()
+    out = args.output or s.output_file
     print("Ok: rendered %d blocks to %s (%d-bit, %d Hz): load %.1f ms, render+write %.1f ms"
-          % (s.cs, args.output or s.output_file, s.bd, s.render_sr, (t1 - t0) * 1e3, (t2 - t1) * 1e3))
+          % (s.cs, out, s.bd, s.render_sr, (t1 - t0) * 1e3, (t2 - t1) * 1e3))
+    g = s.g
+    for i, name in enumerate(args.stem):
+        peak = g.stem_peak(i)
+        print("stem %s: %s peak %.6g%s" % (name, stem_path(out, name), peak, " clips" if not peak <= 1.0 else ""))
     return 0
+
+
+def stem_path(master, vertex):
+    """Where td_state_render writes stem `vertex` of a render to `master` (include/termdaw_amd.h td_state_set_stems)."""
+    base = master[:-4] if master.endswith(".wav") else master
+    return "%s.%s.wav" % (base, re.sub(r"[^A-Za-z0-9._-]", "_", vertex))
 
 
 def stream(s, args, lines=None):

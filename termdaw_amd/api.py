@@ -83,6 +83,11 @@ SIGNATURES = {
     "td_graph_read_pcm": (_i32, [_vp, _vp, _sz]),
     "td_graph_read_f32": (_i32, [_vp, _fp, _sz]),
     "td_graph_output_peak": (_f32, [_vp]),
+    "td_graph_set_stems": (_i32, [_vp, C.POINTER(_cp), _sz]),
+    "td_graph_stem_count": (_sz, [_vp]),
+    "td_graph_stem_pcm_device": (_vp, [_vp, _sz]),
+    "td_graph_read_stem_pcm": (_i32, [_vp, _sz, _vp, _sz]),
+    "td_graph_stem_peak": (_f32, [_vp, _sz]),
     "td_graph_render_all_async": (_sz, [_vp, _vp, _vp, _sz, _i32]),
     "td_graph_sync": (_i32, [_vp]),
     "td_graph_norm_fix_runs": (_sz, [_vp]),
@@ -133,6 +138,7 @@ SIGNATURES = {
     "td_state_refresh": (_i32, [_vp]),
     "td_state_scan_exact": (_i32, [_vp]),
     "td_state_render": (_i32, [_vp, _cp]),
+    "td_state_set_stems": (_i32, [_vp, C.POINTER(_cp), _sz]),
     "td_state_render_to_memory": (_sz, [_vp, _vp, _sz]),
     "td_state_render_view": (_vp, [_vp, C.POINTER(_sz)]),
     "td_state_chunk_count": (_sz, [_vp]),
@@ -209,6 +215,11 @@ def _check(ok):
 def _fa(a):
     a = np.ascontiguousarray(a, dtype=np.float32)
     return a, a.ctypes.data_as(_fp)
+
+
+def _names(names):
+    names = [n.encode() for n in names]
+    return (_cp * max(1, len(names)))(*names), len(names)
 
 
 def device_count():
@@ -396,6 +407,7 @@ class Graph:
         if cs and not n:
             raise TermdawError(last_error())
         frames = cs * self.bl
+        self._pcm_shape = (frames, np.int32 if bd > 16 else np.int16)
         pcm = f = None
         if want_pcm:
             pcm = np.zeros((frames, 2), np.int32 if bd > 16 else np.int16)
@@ -412,6 +424,7 @@ class Graph:
         n = lib().td_graph_render_all_resampled(self.h, sb.h, fb.h, cs, bd, psr, render_sr)
         if cs and not n:
             raise TermdawError(last_error())
+        self._pcm_shape = (n, np.int32 if bd > 16 else np.int16)
         pcm = np.zeros((n, 2), np.int32 if bd > 16 else np.int16)
         f = np.zeros((n, 2), np.float32)
         if n:
@@ -424,7 +437,34 @@ class Graph:
         n = lib().td_graph_render_all_async(self.h, sb.h, fb.h, cs, bd)
         if cs and not n:
             raise TermdawError(last_error())
+        self._pcm_shape = (n, np.int32 if bd > 16 else np.int16)
         return n
+
+    # -- stems: named vertices rendered to PCM of their own by the same render (include/termdaw_amd.h) --
+    def set_stems(self, names):
+        """Replaces the stem list (an empty list clears it); an unknown or repeated name raises and leaves the list as it was."""
+        arr, n = _names(names)
+        _check(lib().td_graph_set_stems(self.h, arr, n))
+
+    def stem_count(self):
+        return lib().td_graph_stem_count(self.h)
+
+    def read_stem_pcm(self, i):
+        """Stem i of this Graph object's last render_all / render_all_resampled / render_all_async: (frames, 2) of the output's dtype."""
+        frames, dt = getattr(self, "_pcm_shape", (None, None))
+        if frames is None:
+            raise TermdawError("read_stem_pcm: nothing rendered through this Graph object")
+        pcm = np.zeros((frames, 2), dt)
+        if frames:
+            _check(lib().td_graph_read_stem_pcm(self.h, i, pcm.ctypes.data_as(_vp), pcm.nbytes))
+        return pcm
+
+    def stem_peak(self, i):
+        """max |x| of the frames of stem i quantised in the last render (NaN when a frame was NaN)."""
+        v = lib().td_graph_stem_peak(self.h, i)
+        if v == 0.0 and not lib().td_graph_stem_pcm_device(self.h, i):   # (0.0 is also what the call returns for a stem not rendered)
+            raise TermdawError(last_error())
+        return float(v)
 
     def sync(self):
         _check(lib().td_graph_sync(self.h))
@@ -676,7 +716,13 @@ class State:
         _check(lib().td_state_scan_exact(self.h))
 
     def render(self, path=None):
+        """State::render; with stems set, each stem X also goes to "<path minus .wav>.<X>.wav"."""
         _check(lib().td_state_render(self.h, path.encode() if path else None))
+
+    def set_stems(self, names):
+        """Stems of the following renders, resolved at each render (an unknown name fails it before any file is written)."""
+        arr, n = _names(names)
+        _check(lib().td_state_set_stems(self.h, arr, n))
 
     def render_to_memory(self):
         nbytes = lib().td_state_render_to_memory(self.h, None, 0)

@@ -20,7 +20,7 @@ namespace tde {
 
 const char* const kFamilyName[F_COUNT] = {"k_sample_loop", "k_sample_multi", "k_sample_lerp", "k_debug_sine",
                                            "k_synth",       "k_sampsyn", "k_adsr_env", "k_sine_probe", "k_sum",          "k_scale",       "k_norm_fix",
-                                           "k_adsr",        "k_band_pass",    "k_band_spec", "k_band_fix", "k_band_fill", "k_band_scan", "k_quantise", "k_band_audit", "k_sources"};
+                                           "k_adsr",        "k_band_pass",    "k_band_spec", "k_band_fix", "k_band_fill", "k_band_scan", "k_quantise", "k_band_audit", "k_stems", "k_sources"};
 
 
 // ------------------------------------------------------------------------------------------------
@@ -651,19 +651,25 @@ static void table_key(const Vertex& v, const td_flowwbank* fb, const std::vector
 }
 // ------------------------------------------------------------------------------------------------
 // plan: reachable set, topological levels (graph.rs:98-108 visits exactly the vertices that reach the
-// output; others never run and never advance -- quirk Q12)
+// output; others never run and never advance -- quirk Q12).  The stems (td_graph_set_stems) are roots of the same walk: a
+// stem is computed with everything upstream of it, as the reference would with set_output(stem); what reaches neither the
+// output nor a stem stays unvisited.
 // ------------------------------------------------------------------------------------------------
 void build_plan(td_graph* g) {
     const size_t n = g->vertices.size();
     g->level.assign(n, -1);
     g->order.clear();
     g->n_levels = 0;
-    if (g->output_vertex >= 0) {
-        // iterative post-order DFS over reverse edges
-        std::vector<char> seen(n, 0);
-        std::vector<std::pair<size_t, size_t>> stack;
-        stack.push_back({(size_t)g->output_vertex, 0});
-        seen[(size_t)g->output_vertex] = 1;
+    std::vector<size_t> roots;
+    if (g->output_vertex >= 0) roots.push_back((size_t)g->output_vertex);
+    for (size_t s : g->stems) roots.push_back(s);
+    // iterative post-order DFS over reverse edges, root after root
+    std::vector<char> seen(n, 0);
+    std::vector<std::pair<size_t, size_t>> stack;
+    for (size_t root : roots) {
+        if (seen[root]) continue;
+        stack.push_back({root, 0});
+        seen[root] = 1;
         while (!stack.empty()) {
             auto& top = stack.back();
             const size_t v = top.first;
@@ -822,6 +828,32 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
     std::vector<std::vector<size_t>> cons(nv);
     for (size_t vi : g->order)
         for (size_t u : g->edges[vi]) cons[u].push_back(vi);
+    // ---- tapped vertices: the output and the stems (td_graph_set_stems).  Their frames must exist in full, pan and gain
+    // applied, when the render's last launches read them: no read-through, no chain membership, no pre-sum folding, no fused
+    // Normalize behind them, no buffer release.  (The exception: a stem on a sample_loop source stays inlined -- the stem
+    // launch gathers the loop itself.)
+    std::vector<char> tapped(nv, 0);
+    tapped[(size_t)g->output_vertex] = 1;
+    for (size_t sv : g->stems) tapped[sv] = 1;
+    // Something else in the render reads the output's frames -- the output is a stem itself, or a stem sits downstream of it:
+    // then its f32 frames are kept whatever "output_f32" says, and its k_norm_fix is not deferred behind the submission.
+    bool out_read = !cons[(size_t)g->output_vertex].empty();
+    for (size_t sv : g->stems) out_read = out_read || (long)sv == g->output_vertex;
+    const bool out_f32 = g->output_f32 || out_read;
+    // (engine option "debug.stem_taps", read-only) which fusions the stems of this graph have switched off since its stem list
+    // was last set -- bit 0: a stem on an inlined loop source (kept inlined), 1: a gain / pan stage, 2: an Adsr vertex its
+    // consumer would evaluate, 3: a band-pass vertex inside a chain launch, 4: a Sum folded into a chain's input phase, 5: a
+    // stem the output does not reach
+    auto stem_only = [&](size_t v) { return tapped[v] && (long)v != g->output_vertex; };
+    if (!g->stems.empty()) {
+        std::vector<char> reach(nv, 0);
+        reach[(size_t)g->output_vertex] = 1;
+        for (size_t k = g->order.size(); k-- > 0;)
+            if (reach[g->order[k]])
+                for (size_t u : g->edges[g->order[k]]) reach[u] = 1;
+        for (size_t sv : g->stems)
+            if (!reach[sv]) g->stem_taps |= 32u;
+    }
     const bool scan_on = g->band_mode >= 1;
     // ---- the guard (band_mode 2, engine.h tde::Guard): a band-pass vertex takes the scan only where the launch's own estimate
     // of its deviation can be carried to the graph's output -- `down[u]`: the static gain from vertex u's output to the
@@ -857,7 +889,15 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
         }
         for (size_t k = g->order.size(); k-- > 0;) {   // consumers first
             const size_t u = g->order[k];
-            if ((long)u == g->output_vertex) { down[u] = PathGain{1.0, -1}; continue; }
+            // a stem: the guard carries nothing to it -- everything upstream takes the exact kernels; the output
+            // too, when a stem sits downstream of it (it then has consumers in the plan, and they lead to stems only)
+            if (stem_only(u)) { down[u] = PathGain{0.0, -2}; continue; }
+            if ((long)u == g->output_vertex) {
+                down[u] = PathGain{1.0, -1};
+                for (size_t w : cons[u])
+                    if (down[w].norm == -2) down[u] = PathGain{0.0, -2};
+                continue;
+            }
             double sum = 0.0;
             long nz = -1;
             bool first = true;
@@ -994,15 +1034,17 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
     // (all of them sum their inputs through the same term loop), so its edge buffer is never materialised
     std::vector<char> inlined(nv, 0);
     if (g->fuse_sources)
-        for (size_t vi : g->order)
+        for (size_t vi : g->order) {
             inlined[vi] = g->vertices[vi].kind == K_SAMPLE_LOOP && (long)vi != g->output_vertex;
+            if (inlined[vi] && stem_only(vi)) g->stem_taps |= 1u;
+        }
     // ... and so is a Sum vertex with exactly one (materialised) input -- a gain / pan stage: its consumers read
     // the input's buffer and apply `0.0 + x`, pan, gain themselves (term kind 4); one launch and one buffer less
     // ... and an Adsr vertex with one materialised input and ONE consumer whose kernel is of the summing family (a Sum, a
     // Normalize, a band-pass -- directly or through one gain / pan stage): that consumer evaluates the envelope itself,
     // as its only term or among others (term kind 5); inlined 3 = such an Adsr vertex, 4 = the stage behind one
     auto is_stage = [&](size_t vi) {   // a single-input Sum that is not the output
-        return g->vertices[vi].kind == K_SUM && (long)vi != g->output_vertex && g->edges[vi].size() == 1;
+        return g->vertices[vi].kind == K_SUM && !tapped[vi] && g->edges[vi].size() == 1;
     };
     auto takes_adsr_terms = [&](size_t c) {   // consumer kernels that take a kind-5 term (the k_sum family, k_band_pass)
         const Vertex& w = g->vertices[c];
@@ -1018,18 +1060,22 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
     if (g->fuse_sources)
         for (size_t vi : g->order) {   // topological order: the input's own flag is final here
             const Vertex& v = g->vertices[vi];
-            if (v.kind == K_ADSR && g->inline_adsr && !(v.wet < 0.0001f) && (long)vi != g->output_vertex &&
+            if (v.kind == K_ADSR && g->inline_adsr && !(v.wet < 0.0001f) &&
                 g->edges[vi].size() == 1 && inlined[g->edges[vi][0]] < 3 && cons[vi].size() == 1) {
                 // (its input: an edge buffer, an inlined loop source or a gain / pan stage -- anything but another envelope)
                 const size_t c = cons[vi][0];
                 const bool direct = takes_adsr_terms(c);
                 const bool staged = is_stage(c) && cons[c].size() == 1 && takes_adsr_terms(cons[c][0]);
-                if (direct || staged) {
+                if ((direct || staged) && tapped[vi]) {
+                    if (stem_only(vi)) g->stem_taps |= 4u;
+                } else if (direct || staged) {
                     inlined[vi] = 3;
                     outlive(g->edges[vi][0], last_use[vi]);
                 }
                 continue;
             }
+            if (stem_only(vi) && v.kind == K_SUM && g->edges[vi].size() == 1 && (!inlined[g->edges[vi][0]] || inlined[g->edges[vi][0]] == 3))
+                g->stem_taps |= 2u;
             if (!is_stage(vi)) continue;
             const size_t u = g->edges[vi][0];
             if (inlined[u] == 3) {
@@ -1091,9 +1137,13 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                     links.insert(links.begin(), ChainLink{u, inlined[u] == 3});
                     u = g->edges[u][0];
                 }
-                if (!ok || inlined[u] || !scan_plan.count(u) || cons[u].size() != 1 || (long)u == g->output_vertex) continue;
+                if (!ok || inlined[u] || !scan_plan.count(u) || cons[u].size() != 1) continue;
                 // (k_band_chain runs `pass` vertices -- whose right-channel smoothers reach no output -- at 16 frames per lane)
                 if (!g->vertices[b].pass || !g->vertices[u].pass || !kv.second.Kw || !scan_plan[u].Kw) continue;
+                if (tapped[u]) {
+                    if (stem_only(u)) g->stem_taps |= 8u;
+                    continue;
+                }
                 prev_of[b] = u;
                 next_of[u] = b;
                 links_before[b] = links;
@@ -1141,7 +1191,7 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
         bl == (size_t)kTileFrames && M < ((size_t)1 << 31)) {
         for (auto& kv : scan_plan) {
             const size_t L = kv.first;
-            if (inlined[L] == 5 || (long)L == g->output_vertex || cons[L].size() != 1) continue;   // (only a launch's last vertex)
+            if (inlined[L] == 5 || tapped[L] || cons[L].size() != 1) continue;   // (only a launch's last vertex)
             const std::vector<size_t> piece = chain_of.count(L) ? chain_of[L] : std::vector<size_t>{L};
             bool ok = true;
             for (size_t b : piece) ok = ok && g->vertices[b].pass && scan_plan[b].Kw != 0u;
@@ -1149,7 +1199,7 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
             std::vector<ChainLink> links;
             size_t u = cons[L][0];
             while (links.size() < 3 && (inlined[u] == 2 || inlined[u] == 3 || inlined[u] == 4) && cons[u].size() == 1 &&
-                   (long)u != g->output_vertex) {
+                   !tapped[u]) {
                 links.push_back(ChainLink{u, inlined[u] == 3});
                 u = cons[u][0];
             }
@@ -1178,10 +1228,14 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                 u = g->edges[u][0];
             }
             const Vertex& uv = g->vertices[u];
-            if (inlined[u] || uv.kind != K_SUM || g->edges[u].size() < 2 || cons[u].size() != 1 || (long)u == g->output_vertex) continue;
+            if (inlined[u] || uv.kind != K_SUM || g->edges[u].size() < 2 || cons[u].size() != 1) continue;
             bool ok = true;
             for (size_t w : g->edges[u]) ok = ok && inlined[w] < 3;   // (edge buffers, loop sources, gain / pan stages: kinds 0 .. 4)
             if (!ok) continue;
+            if (tapped[u]) {
+                if (stem_only(u)) g->stem_taps |= 16u;
+                continue;
+            }
             presum_of[first] = u;
             inlined[u] = 7;
             for (size_t w : g->edges[u]) {   // its inputs are read at the LAST vertex' level
@@ -1305,6 +1359,26 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
     const uint32_t probe_stride = 1u << probe_lg, probe_n = (uint32_t)((M + probe_stride - 1) / probe_stride), probe_groups = (probe_n + 15u) / 16u;
     std::vector<std::pair<size_t, size_t>> probe_src;   // (vertex, scratch offset of its ProbeDesc::noise)
     std::vector<size_t> probe_desc_off;                 // ... and where its ProbeDesc stands in the arena
+    // an inlined sample_loop source as an input term (kinds 1 .. 3): what its consumers -- and a stem launch -- gather
+    auto loop_term = [&](size_t u) {
+        InTerm t{};
+        const Vertex& src = g->vertices[u];
+        const SampleEntry& s = sb->samples[src.sample_index];
+        t.p = s.d;
+        t.len = s.len;
+        t.t0 = vt[u].t0;
+        t.pg = make_pg(src.gain, src.angle);
+        const bool fits32 = s.len <= 0xFFFFFFFFull && t.t0 + M + kTileFrames <= 0xFFFFFFFFull;
+        t.kind = fits32 ? 1u : 2u;
+        t.magic = fits32 ? (s.len >= 2 ? (uint32_t)(0x100000000ull / s.len) : 0xFFFFFFFFu) : 0u;
+        if (fits32 && s.d16 && g->packed_samples) {   // half the gather bytes, same values
+            t.kind = 3u;
+            t.p = reinterpret_cast<const float2*>(s.d16);
+            t.scale_l = s.scale_l;
+            t.scale_r = s.scale_r;
+        }
+        return t;
+    };
     for (int lv = 0; lv < g->n_levels; ++lv) {
         std::vector<size_t> fam_v[F_COUNT];
         std::vector<float2*> level_tmp;            // scratch edge buffers that live for this level only
@@ -1374,21 +1448,7 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                     t.kind = 4u;
                     t.pg = make_pg(g->vertices[u].gain, g->vertices[u].angle);
                 } else if (inlined[u]) {
-                    const Vertex& src = g->vertices[u];
-                    const SampleEntry& s = sb->samples[src.sample_index];
-                    t.p = s.d;
-                    t.len = s.len;
-                    t.t0 = vt[u].t0;
-                    t.pg = make_pg(src.gain, src.angle);
-                    const bool fits32 = s.len <= 0xFFFFFFFFull && t.t0 + M + kTileFrames <= 0xFFFFFFFFull;
-                    t.kind = fits32 ? 1u : 2u;
-                    t.magic = fits32 ? (s.len >= 2 ? (uint32_t)(0x100000000ull / s.len) : 0xFFFFFFFFu) : 0u;
-                    if (fits32 && s.d16 && g->packed_samples) {   // half the gather bytes, same values
-                        t.kind = 3u;
-                        t.p = reinterpret_cast<const float2*>(s.d16);
-                        t.scale_l = s.scale_l;
-                        t.scale_r = s.scale_r;
-                    }
+                    t = loop_term(u);
                 } else {
                     t.p = g->vbuf[u];
                 }
@@ -1474,7 +1534,8 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
             }
             norm_mode[vi] = mode;
             // (modes 3 / 4 / 5 all have k_norm_fix behind them; for 4 / 5 on the output vertex of a one-chunk render it is not
-            // enqueued but kept for settle(): nothing in the submission reads the vertex' frames or its carried max)
+            // enqueued but kept for settle(): nothing in the submission reads the vertex' frames or its carried max -- unless a stem
+            // is the output or sits downstream of it, `out_read`)
             fam_v[mode == 1u ? F_SCALE : F_NORMFIX].push_back(vi);
         }
         std::map<size_t, std::pair<size_t, size_t>> norm_scratch;   // vi -> (peaks, init snapshot)
@@ -1665,7 +1726,7 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                             x.pcm = pcm_dst;
                             x.amplitude = amplitude;
                             x.qmode = (uint32_t)qmode;
-                            if (!g->output_f32) x.out = nullptr;
+                            if (!out_f32) x.out = nullptr;
                         }
                         x.term_mode = term_mode[vi];
                         x.debug = (uint32_t)g->norm_debug;
@@ -1727,7 +1788,7 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                         x.amplitude = amplitude;
                         x.qmode = is_out ? (uint32_t)qmode : 0u;
                         x.pg = make_pg(v.gain, v.angle);
-                        x.pcm_only = (is_out && !g->output_f32) ? 1u : 0u;
+                        x.pcm_only = (is_out && !out_f32) ? 1u : 0u;
                         d.push_back(x);
                     }
                     off = st.put(d);
@@ -1738,7 +1799,7 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                 } break;
                 case F_NORMFIX: {   // the same descriptors the speculative k_sum launch got
                     // deferred (kept for settle(), not launched): a mode 4 / 5 output vertex of a one-chunk render -- last in `vs`
-                    auto deferred = [&](size_t vi) { return g->defer_fix && norm_mode[vi] >= 4u && (long)vi == g->output_vertex; };
+                    auto deferred = [&](size_t vi) { return g->defer_fix && norm_mode[vi] >= 4u && (long)vi == g->output_vertex && !out_read; };
                     std::stable_sort(vs.begin(), vs.end(), [&](size_t a, size_t b) { return deferred(a) < deferred(b); });
                     std::vector<SumDesc> d;
                     for (size_t vi : vs) d.push_back(sum_desc_of[vi]);
@@ -2046,7 +2107,7 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                                 y.pcm = pcm_dst;
                                 y.amplitude = amplitude;
                                 y.qmode = (uint32_t)qmode;
-                                if (!g->output_f32) y.out = nullptr;
+                                if (!out_f32) y.out = nullptr;
                             }
                             y.pg = make_pg(nv.gain, nv.angle);
                             y.state = &g->dstate[nv.state_slot].norm;
@@ -2123,7 +2184,7 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
         for (float2* t : level_tmp) g->free_bufs.push_back(t);
         // release buffers whose last consumer sits at this level
         for (size_t vi : g->order)
-            if (g->vbuf[vi] && last_use[vi] == lv && (long)vi != g->output_vertex) {
+            if (g->vbuf[vi] && last_use[vi] == lv && !tapped[vi]) {
                 g->free_bufs.push_back(g->vbuf[vi]);
                 // keep vbuf[vi] for descriptor bookkeeping of this level only
                 last_use[vi] = -2;
@@ -2135,6 +2196,30 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
     if (pcm_dst && qmode && outv.kind != K_NORMALIZE) {
         std::vector<QuantDesc> d{{g->vbuf[(size_t)g->output_vertex], pcm_dst, amplitude, (uint32_t)qmode}};
         add_launch(F_QUANT, st.put(d), 1, 0u, g->n_levels);
+    }
+    // the stems: ONE launch for all of them (k_stems), behind everything that computes their frames
+    const bool stem_pcm = pcm_dst && qmode;
+    if (!g->stems.empty() && !is_scan && (stem_pcm || g->stem_f32_wanted)) {
+        const size_t qbytes = qmode == 1 ? 4 : 8;   // PCM bytes per frame
+        std::vector<StemDesc> d;
+        for (size_t k = 0; k < g->stems.size(); ++k) {
+            const size_t sv = g->stems[k];
+            StemDesc x{};
+            if (inlined[sv] == 1) {
+                x.src = loop_term(sv);
+            } else {
+                if (inlined[sv] || !g->vbuf[sv]) return fail("termdaw_amd: internal: a stem vertex was not materialised");
+                x.src.p = g->vbuf[sv];
+                x.src.kind = 0u;
+            }
+            x.pcm = stem_pcm ? g->d_stem_pcm + k * g->stem_stride + g->chunk_frame0 * qbytes : nullptr;
+            x.f32 = g->stem_f32_wanted ? g->d_stem_f32 + k * g->stem_f32_stride + g->chunk_frame0 : nullptr;
+            x.peak = g->d_stem_peak + k;
+            x.amplitude = amplitude;
+            x.qmode = stem_pcm ? (uint32_t)qmode : 0u;
+            d.push_back(x);
+        }
+        add_launch(F_STEMS, st.put(d), (int)d.size(), 0u, g->n_levels);
     }
     // the guard's verdict on this chunk: one workgroup adds up what the guarded scan launches estimated (k_band_audit)
     const double guard_thr = (double)g->band_guard_ppb * 1e-9;
@@ -2249,6 +2334,7 @@ size_t desc_size(int fam) {
         case F_BAND_SCAN: return sizeof(BandScanDesc);
         case F_QUANT: return sizeof(QuantDesc);
         case F_AUDIT: return sizeof(AuditHead);
+        case F_STEMS: return sizeof(StemDesc);
         default: return 0;
     }
 }

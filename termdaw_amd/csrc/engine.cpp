@@ -881,6 +881,7 @@ static int submit_chunk(Arena& ar, ChunkBuild& cb, hipStream_t stream, ProfCtx& 
                     break;
                 case F_QUANT: launch_quantise((const QuantDesc*)d, L.n, L.M, s); break;
                 case F_AUDIT: launch_band_audit((const AuditHead*)d, L.n, s); break;
+                case F_STEMS: launch_stems((const StemDesc*)d, L.n, L.M, s); break;   // (prepare_render has checked it exists)
             }
         }
         li = lj;
@@ -902,6 +903,59 @@ struct RenderPlan {
     float amplitude = 0.f;
     size_t word = 0;
 };
+// The stems' device side for a render of `frames` frames: PCM of `word`-byte samples (0: none), the peaks, the f32 copies of a
+// resampled render.  Nothing in flight reads them: the caller has drained what used them before growing anything.
+static int prepare_stems(td_graph* g, size_t frames, size_t word) {
+    if (!launch_stems) return fail("termdaw_amd: this build has no k_stems kernel: stems cannot be rendered");
+    const size_t n = g->stems.size();
+    if (word) {
+        const size_t stride = (frames * 2 * word + 64 + 255) & ~(size_t)255;
+        if (n * stride > g->stem_pcm_cap) {
+            if (!drain(g)) return 0;
+            if (g->d_stem_pcm) { (void)hipFree(g->d_stem_pcm); g->device_bytes -= g->stem_pcm_cap; }
+            g->d_stem_pcm = nullptr;
+            g->stem_pcm_cap = 0;
+            TD_HIP(hipMalloc(&g->d_stem_pcm, n * stride));
+            g->stem_pcm_cap = n * stride;
+            g->device_bytes += n * stride;
+        }
+        g->stem_stride = stride;
+        g->stem_pcm_bytes = frames * 2 * word;
+    }
+    if (n > g->stem_peak_cap) {
+        if (!drain(g)) return 0;
+        if (g->d_stem_peak) { (void)hipFree(g->d_stem_peak); g->device_bytes -= g->stem_peak_cap * 4; }
+        g->d_stem_peak = nullptr;
+        g->stem_peak_cap = 0;
+        TD_HIP(hipMalloc(&g->d_stem_peak, n * 4));
+        g->stem_peak_cap = n;
+        g->device_bytes += n * 4;
+    }
+    if (g->stem_f32_wanted) {
+        const size_t stride = frames + 2;   // (float2 frames)
+        if (n * stride * sizeof(float2) > g->stem_f32_cap) {
+            if (!drain(g)) return 0;
+            if (g->d_stem_f32) { (void)hipFree(g->d_stem_f32); g->device_bytes -= g->stem_f32_cap; }
+            g->d_stem_f32 = nullptr;
+            g->stem_f32_cap = 0;
+            TD_HIP(hipMalloc(&g->d_stem_f32, n * stride * sizeof(float2)));
+            g->stem_f32_cap = n * stride * sizeof(float2);
+            g->device_bytes += g->stem_f32_cap;
+        }
+        g->stem_f32_stride = stride;
+    }
+    return 1;
+}
+// Does anything else in the render read the output's frames -- the output is a stem, or a stem sits downstream of it?  (Then
+// compile_chunk keeps them in f32 whatever "output_f32" says: compile.cpp `out_read`.)
+static bool output_read(const td_graph* g) {
+    for (size_t sv : g->stems)
+        if ((long)sv == g->output_vertex) return true;
+    for (size_t vi : g->order)
+        for (size_t u : g->edges[vi])
+            if ((long)u == g->output_vertex) return true;
+    return false;
+}
 static int prepare_render(td_graph* g, size_t n_blocks, int bits, bool want_pcm, RenderPlan* rp) {
     if (!ensure_graph_device(g)) return 0;
     if (g->output_vertex < 0) return fail("TermDaw: error: output vertex not found.");
@@ -935,6 +989,7 @@ static int prepare_render(td_graph* g, size_t n_blocks, int bits, bool want_pcm,
         }
         g->pcm_bytes = rp->total * 2 * rp->word;
     }
+    if (!g->stems.empty() && (want_pcm || g->stem_f32_wanted) && !prepare_stems(g, rp->total, rp->word)) return 0;
     if (rp->multi) {
         const size_t need = (rp->total + 2) * sizeof(float2);
         if (need > g->out_f32_cap) {
@@ -965,6 +1020,7 @@ static int compile_next_chunk(td_graph* g, const td_samplebank* sb, td_flowwbank
         fb->set_time_to_next_block();
     }
     const uint64_t t0 = advance_graph_time ? g->t : scan_t0 + done * bl;
+    g->chunk_frame0 = done * bl;
     void* pcm_dst = rp.want_pcm ? (uint8_t*)g->d_pcm + done * bl * 2 * rp.word : nullptr;
     return compile_chunk(g, sb, fb, cur, t0, is_scan, pcm_dst, rp.qmode, rp.amplitude, cb);
 }
@@ -979,7 +1035,7 @@ static int finish_chunk(td_graph* g, const RenderPlan& rp, size_t done, size_t n
 }
 static void finish_render(td_graph* g, const RenderPlan& rp) {
     g->last_out_f32 = rp.multi ? g->d_out_f32 : (rp.n_blocks ? g->vbuf[(size_t)g->output_vertex] : nullptr);
-    if (!g->output_f32 && rp.want_pcm && g->vertices[(size_t)g->output_vertex].kind == K_NORMALIZE)
+    if (!g->output_f32 && !output_read(g) && rp.want_pcm && g->vertices[(size_t)g->output_vertex].kind == K_NORMALIZE)
         g->last_out_f32 = nullptr;   // (the f32 frames of the output were never written)
     g->last_frames = rp.total;
     g->last_bits = rp.bits;
@@ -1138,6 +1194,10 @@ int graph_render_chunks(td_graph* g, const td_samplebank* sb, td_flowwbank* fb, 
     g->batch_projects = 1;
     const bool guarded = may_be_audited(g);
     if (guarded && !guard_begin(g, sb, fb, n_blocks, is_scan, bits, advance_graph_time, scan_t0, want_pcm)) return 0;
+    if (!g->stems.empty() && !is_scan && (want_pcm || g->stem_f32_wanted)) {   // (the stems' peaks accumulate over the render's chunks)
+        TD_HIP(hipMemsetAsync(g->d_stem_peak, 0, g->stems.size() * 4, g->stream));
+        g->stems_rendered = g->stems.size();
+    }
     bool audited = false;
     ChunkBuild& cb = g->build;
     cb.st = &g->staging;
@@ -1200,6 +1260,8 @@ static int graph_set_time_impl(td_graph* g, size_t time) {   // graph.rs:123-128
 static int batch_render_range(td_batch* b, size_t lo, size_t hi, size_t n_blocks, bool is_scan, int bits, bool advance_graph_time,
                               bool want_pcm, bool allow_defer) {
     if (hi <= lo) return 1;
+    for (size_t i = lo; i < hi; ++i)
+        if (!b->graphs[i]->stems.empty()) return fail("td_batch: project " + std::to_string(i) + " has stems set: batches do not render stems");
     if (!ensure_device(b->device)) return 0;
     const size_t P = hi - lo;
     std::vector<RenderPlan> rp(P);
@@ -1435,7 +1497,7 @@ void td_graph_free(td_graph* g) {
             }
     }
     const bool has_device_state = g->stream || !g->pool.empty() || !g->wavetables.empty() || g->dstate || g->arena.d || g->d_pcm ||
-                                  g->d_out_f32 || g->d_resampled || g->d_scalar;
+                                  g->d_out_f32 || g->d_resampled || g->d_scalar || g->d_stem_pcm || g->d_stem_peak || g->d_stem_f32;
     if (has_device_state && hipSetDevice(g->device) == hipSuccess) {
         if (g->stream) (void)hipStreamSynchronize(g->stream);
         else (void)hipDeviceSynchronize();   // (a graph whose stream could not be re-made after td_batch_free)
@@ -1447,6 +1509,9 @@ void td_graph_free(td_graph* g) {
         if (g->d_pcm && !g->pcm_borrowed) (void)hipFree(g->d_pcm);
         if (g->d_out_f32) (void)hipFree(g->d_out_f32);
         if (g->d_resampled) (void)hipFree(g->d_resampled);
+        if (g->d_stem_pcm) (void)hipFree(g->d_stem_pcm);
+        if (g->d_stem_peak) (void)hipFree(g->d_stem_peak);
+        if (g->d_stem_f32) (void)hipFree(g->d_stem_f32);
         if (g->d_scalar) (void)hipFree(g->d_scalar);
         if (g->guard.d_backup) (void)hipFree(g->guard.d_backup);
         if (g->guard.h_word) (void)hipHostFree(g->guard.h_word);
@@ -1468,6 +1533,9 @@ void td_graph_reset(td_graph* g) {
     g->edges.clear();
     g->name_map.clear();
     g->output_vertex = -1;
+    g->stems.clear();
+    g->stems_rendered = 0;
+    g->stem_taps = 0;
     g->t = 0;
     g->hstate.clear();
     g->state_host_dirty = true;
@@ -1712,6 +1780,13 @@ int td_graph_render_block(td_graph* g, const td_samplebank* sb, td_flowwbank* fb
     // Graph::render leaves the FlowwBank alone: run one block on a cursor snapshot
     const size_t frame = fb->frame;
     const std::vector<size_t> starts = fb->start_indices;
+    // (block pulls ignore the stems: the plan of the output alone, as the reference's Graph::render walks it)
+    struct Unstem {
+        td_graph* g;
+        std::vector<size_t> kept;
+        explicit Unstem(td_graph* x) : g(x) { if (!g->stems.empty()) { settle_guard_before_edit(g); kept.swap(g->stems); g->plan_dirty = true; } }
+        ~Unstem() { if (!kept.empty()) { (void)drain(g); kept.swap(g->stems); g->plan_dirty = true; } }
+    } unstem(g);
     const int ok = graph_render_chunks(g, sb, fb, 1, false, 16, true, 0, false);
     fb->frame = frame;
     fb->start_indices = starts;
@@ -1776,6 +1851,38 @@ size_t td_graph_render_all(td_graph* g, const td_samplebank* sb, td_flowwbank* f
     if (!td_graph_sync(g)) return 0;
     return n;
 }
+// The stems of a resampled render: every stem's whole-timeline f32 frames (d_stem_f32, written by the render's k_stems
+// launches) through the same resampler as the output's, then ONE k_stems launch quantises all of them -- and takes their
+// peaks over the resampled frames.  Not the hot path: a stream synchronisation per stem.
+static int resample_stems(td_graph* g, size_t total, size_t psr, size_t render_sr, size_t nout, float amplitude, int qmode) {
+    const size_t n = g->stems.size(), word = qmode == 1 ? 2 : 4;
+    if (!prepare_stems(g, nout, word)) return 0;
+    std::vector<float2*> rs(n, nullptr);
+    std::vector<StemDesc> d(n);
+    StemDesc* dd = nullptr;
+    int ok = 1;
+    for (size_t k = 0; k < n && ok; ++k) {
+        size_t nk = 0;
+        ok = resample_device(g->d_stem_f32 + k * g->stem_f32_stride, total, psr, render_sr, &rs[k], &nk, g->stream);
+        if (ok && nk != nout) ok = fail("termdaw_amd: internal: a stem resampled to another length than the output");
+        d[k] = StemDesc{};
+        d[k].src.p = rs[k];
+        d[k].pcm = g->d_stem_pcm + k * g->stem_stride;
+        d[k].peak = g->d_stem_peak + k;
+        d[k].amplitude = amplitude;
+        d[k].qmode = (uint32_t)qmode;
+    }
+    if (ok && hipMalloc(&dd, n * sizeof(StemDesc)) != hipSuccess) ok = fail("termdaw_amd: out of device memory for the stem descriptors");
+    if (ok && (hipMemsetAsync(g->d_stem_peak, 0, n * 4, g->stream) != hipSuccess ||
+               hipMemcpyAsync(dd, d.data(), n * sizeof(StemDesc), hipMemcpyHostToDevice, g->stream) != hipSuccess))
+        ok = fail("HIP error: stem descriptors");
+    if (ok) launch_stems(dd, (int)n, (uint32_t)nout, g->stream);
+    if (hipStreamSynchronize(g->stream) != hipSuccess && ok) ok = fail("HIP error: the stems' quantise");
+    for (float2* p : rs) if (p) (void)hipFree(p);
+    if (dd) (void)hipFree(dd);
+    g->stems_rendered = ok ? n : 0;
+    return ok;
+}
 // State::render's `psr > render_sr` arm (state.rs:533-561): render, then resample the whole timeline with
 // the build-defined resampler (the reference streams rubato block by block -- parity unpinned), quantise.
 size_t td_graph_render_all_resampled(td_graph* g, const td_samplebank* sb, td_flowwbank* fb, size_t n_blocks, int bits,
@@ -1784,9 +1891,11 @@ size_t td_graph_render_all_resampled(td_graph* g, const td_samplebank* sb, td_fl
         fail("Bitdepth not supported: choose bitdepth in {8, 16, 24, 32}.");
         return 0;
     }
-    if (!graph_render_chunks(g, sb, fb, n_blocks, false, bits, true, 0, false)) return 0;
-    if (!graph_set_time_impl(g, 0)) return 0;
-    if (!drain(g)) return 0;   // (the resampler reads the output vertex' frames)
+    g->stem_f32_wanted = !g->stems.empty();   // (the stems' whole-timeline frames are resampled like the output's)
+    int rendered = graph_render_chunks(g, sb, fb, n_blocks, false, bits, true, 0, false);
+    rendered = rendered && graph_set_time_impl(g, 0) && drain(g);   // (the resampler reads the output vertex' frames)
+    g->stem_f32_wanted = false;
+    if (!rendered) return 0;
     const size_t total = n_blocks * g->bl;
     float2* rs = nullptr;
     size_t nout = 0;
@@ -1816,9 +1925,48 @@ size_t td_graph_render_all_resampled(td_graph* g, const td_samplebank* sb, td_fl
     g->last_out_f32 = rs;
     g->last_frames = nout;
     g->last_bits = bits;
+    if (!g->stems.empty() && !resample_stems(g, total, psr, render_sr, nout, amplitude, qmode)) return 0;
     return nout;
 }
 const void* td_graph_output_pcm_device(const td_graph* g) { return g->d_pcm; }
+
+// ---- stems (include/termdaw_amd.h; the semantics of set_output, graph.rs:141-148, for every named vertex) ----
+int td_graph_set_stems(td_graph* g, const char* const* names, size_t n) {
+    std::vector<size_t> v;
+    for (size_t i = 0; i < n; ++i) {
+        auto it = names && names[i] ? g->name_map.find(names[i]) : g->name_map.end();
+        if (it == g->name_map.end()) return fail(std::string("set_stems: vertex not found: ") + (names && names[i] ? names[i] : "(null)"));
+        if (std::find(v.begin(), v.end(), it->second) != v.end()) return fail(std::string("set_stems: vertex named twice: ") + names[i]);
+        v.push_back(it->second);
+    }
+    settle_guard_before_edit(g);
+    g->stems = v;
+    g->stems_rendered = 0;
+    g->stem_taps = 0;
+    g->plan_dirty = true;
+    return 1;
+}
+size_t td_graph_stem_count(const td_graph* g) { return g->stems.size(); }
+const void* td_graph_stem_pcm_device(const td_graph* g, size_t i) {
+    if (i >= g->stems_rendered || !g->d_stem_pcm) return nullptr;
+    return g->d_stem_pcm + i * g->stem_stride;
+}
+int td_graph_read_stem_pcm(const td_graph* g, size_t i, void* out, size_t bytes) {
+    if (i >= g->stems_rendered || !g->d_stem_pcm || bytes > g->stem_pcm_bytes) return fail("read_stem_pcm: no such stem rendered / size too large");
+    if (!drain(const_cast<td_graph*>(g))) return 0;
+    TD_HIP(hipMemcpy(out, g->d_stem_pcm + i * g->stem_stride, bytes, hipMemcpyDeviceToHost));
+    return 1;
+}
+float td_graph_stem_peak(const td_graph* gc, size_t i) {
+    td_graph* g = const_cast<td_graph*>(gc);
+    if (i >= g->stems_rendered || !g->d_stem_peak) { fail("stem_peak: no such stem rendered"); return 0.0f; }
+    if (!drain(g)) return 0.0f;
+    uint32_t bits = 0;
+    if (hipMemcpy(&bits, g->d_stem_peak + i, 4, hipMemcpyDeviceToHost) != hipSuccess) { fail("HIP error: stem peak read-back"); return 0.0f; }
+    float v;
+    memcpy(&v, &bits, 4);
+    return v;
+}
 const float* td_graph_output_f32_device(const td_graph* g) { return (const float*)g->last_out_f32; }
 int td_graph_read_pcm(const td_graph* g, void* out, size_t bytes) {
     if (!g->d_pcm || bytes > g->pcm_bytes) return fail("read_pcm: nothing rendered / size too large");
@@ -1953,11 +2101,13 @@ static std::vector<OptionRef> option_table(td_graph* g) {
         {"debug.table_cache", 0, &g->table_cache}, {"debug.band_serial", 0, &g->band_serial}, {"debug.band_chain", 0, &g->band_chain}, {"debug.band_scan_nf", 1, &g->band_scan_nf},
         {"debug.band_quick", 2, &g->band_quick}, {"debug.band_short", 2, &g->band_short}, {"debug.band_medium", 2, &g->band_medium},
         {"debug.band_warmup", 2, &g->band_warmup}, {"debug.band_depth", 2, &g->band_depth},
+        {"debug.stem_taps", 2, &g->stem_taps},
     };
 }
 int td_graph_set_option(td_graph* g, const char* key, long value) {
     const std::string k = key ? key : "";
     // (keys with a rule of their own first)
+    if (k == "debug.stem_taps") return fail("td_graph_set_option: debug.stem_taps is read-only");
     if (k == "band_mode") {   // 0: exact (default, the parity mode), 1: blocked affine scan (tolerance class), 2: the scan under the guard
         if (value != 0 && value != 1 && value != 2) return fail("band_mode must be 0 (exact), 1 (scan) or 2 (guarded scan)");
         if (g->guard.armed && !drain(g)) return 0;   // (a verdict still out belongs to the mode it was rendered in)
@@ -2127,6 +2277,8 @@ int td_batch_render_to_files(td_batch* b, size_t n_blocks, int bits, size_t rend
     if (!P) return 1;
     if (!ensure_device(b->device)) return 0;
     if (!(bits == 8 || bits == 16 || bits == 24 || bits == 32)) return fail("Bitdepth not supported: choose bitdepth in {8, 16, 24, 32}.");
+    for (size_t i = 0; i < P; ++i)
+        if (!b->graphs[i]->stems.empty()) return fail("td_batch: project " + std::to_string(i) + " has stems set: batches do not render stems");
     const size_t G = group > 0 ? (size_t)group : 8;
     const size_t n_groups = (P + G - 1) / G;
     const auto w0 = std::chrono::steady_clock::now();
@@ -2301,6 +2453,8 @@ const void* td_batch_host_pcm(const td_batch* b, size_t i, size_t* bytes) {
     return b->host_pcm + b->host_pcm_off[i];
 }
 int td_batch_normalize_scan(td_batch* b, size_t chunks) {   // State::scan_exact (state.rs:473-475) for every project
+    for (size_t i = 0; i < b->graphs.size(); ++i)
+        if (!b->graphs[i]->stems.empty()) return fail("td_batch: project " + std::to_string(i) + " has stems set: batches do not render stems");
     for (size_t i = 0; i < b->graphs.size(); ++i) {
         if (b->graphs[i]->output_vertex < 0) return fail("TermDaw: error: output vertex not found.");
         if (!scan_begin(b->graphs[i], b->fbs[i])) return 0;

@@ -375,6 +375,18 @@ struct td_graph {
     int last_bits = 16;
     float* d_scalar = nullptr;
     float2* d_resampled = nullptr;            // output of the last td_graph_render_all_resampled
+    // stems (td_graph_set_stems): vertices rendered to PCM of their own beside the output, by ONE k_stems launch per chunk
+    std::vector<size_t> stems;                // in the order they were named
+    uint8_t* d_stem_pcm = nullptr;            // stem k's PCM at k * stem_stride (same words and frame count as the output's)
+    size_t stem_pcm_cap = 0, stem_stride = 0, stem_pcm_bytes = 0;
+    uint32_t* d_stem_peak = nullptr;          // per stem: max |x| of the frames quantised (f32 bits), reset at render start
+    size_t stem_peak_cap = 0;
+    float2* d_stem_f32 = nullptr;             // resampled renders only: every stem's whole-timeline f32 frames, stem k at k * stem_f32_stride
+    size_t stem_f32_cap = 0, stem_f32_stride = 0;
+    bool stem_f32_wanted = false;             // (set per render) the stem launch copies the frames into d_stem_f32
+    size_t stems_rendered = 0;                // stems the last render wrote (0: none, or the list changed since)
+    size_t chunk_frame0 = 0;                  // (set per chunk) frames of the render in front of the chunk being compiled
+    unsigned stem_taps = 0;                   // (diagnostic, "debug.stem_taps") the fusions the stems switched off since the list was set: compile_chunk
     size_t device_bytes = 0;
     bool fuse_sources = true;                  // inline sample_loop sources into their consumers
     bool packed_samples = true;                // inlined sources read the packed 16-bit sample form when it exists

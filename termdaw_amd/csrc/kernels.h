@@ -135,7 +135,8 @@ struct ScaleDesc {
     float amplitude;
     uint32_t qmode;         // 0 none, 1 int16, 2 int32
     PanGain pg;
-    uint32_t pcm_only;      // the scaled f32 frames are not written back (nobody reads them: engine option "output_f32" 0)
+    uint32_t pcm_only;      // the scaled f32 frames are not written back (engine option "output_f32" 0, set only where nothing in the
+                            // render reads them: not when a stem is the output or sits downstream of it)
     uint32_t pad[3];
 };
 
@@ -144,6 +145,20 @@ struct QuantDesc {
     void* pcm;
     float amplitude;
     uint32_t qmode;
+};
+
+// One stem of a chunk (k_stems, engine family F_STEMS): a vertex' frames quantised into a PCM stream of their own, beside the
+// output's.  `src` is an input term of kind 0 -- the vertex' materialised edge buffer, pan / gain already applied -- or of kind
+// 1 / 2 / 3: an inlined sample_loop source, which k_stems gathers itself through the same device code its consumers use
+// (term_pair: the Barrett modulo, the packed 16-bit table, the epilogue), so its edge buffer still never exists.  Every stem
+// reduces max |x| over the frames it quantises into `peak` (f32 bits; unsigned order, so a NaN frame wins).
+struct StemDesc {
+    InTerm src;
+    void* pcm;          // this chunk's slice of the stem's PCM (same words as the output's), or nullptr
+    float2* f32;        // a copy of the frames (resampled renders: the whole timeline is resampled afterwards), or nullptr
+    uint32_t* peak;     // the stem's running peak over the render
+    float amplitude;
+    uint32_t qmode;     // 0 none, 1 int16, 2 int32
 };
 
 // sample_loop_gen (extensions.rs:331-341): out[m] = sample[(t0 + m) % len]
@@ -567,6 +582,9 @@ void launch_scale(const ScaleDesc* d, int n_desc, uint32_t frames, uint32_t bl, 
 // second half of the speculative single-pass normalize: a no-op unless a block peak exceeded the carried max
 void launch_norm_fix(const SumDesc* d, int n_desc, uint32_t frames, uint32_t bl, hipStream_t s);
 void launch_quantise(const QuantDesc* d, int n_desc, uint32_t frames, hipStream_t s);
+// Weak: the host engine calls it only when stems are set, and a host-only build of the engine (tests/mock_hip.cpp) has no
+// definition -- the engine then refuses stems with an error instead of failing to link.
+__attribute__((weak)) void launch_stems(const StemDesc* d, int n_desc, uint32_t frames, hipStream_t s);
 void launch_sinf(const float* in, float* out, uint32_t n, int exact, hipStream_t s);   // out[i] = sin_glibc(in[i]) (exact) or sin_any(in[i])
 void launch_debug_verify(const uint32_t* p, uint32_t n_words, const uint32_t* seg_sums, uint32_t* report, hipStream_t s);   // (TD_DEBUG_SYNC & 16)
 void launch_sample_loop(const LoopDesc* d, int n_desc, uint32_t frames, hipStream_t s);

@@ -1133,6 +1133,51 @@ __global__ __launch_bounds__(kThreads) void k_quantise(const QuantDesc* __restri
 }
 
 // ------------------------------------------------------------------------------------------------
+// k_stems: every stem of a chunk in ONE grid -- blockIdx.y the stem, blockIdx.x a tile of kStemTileFrames frames.  A
+// thread loads its kStemPairs frame pairs first (a materialised buffer, or the loop gathered by term_pair exactly as the
+// source's consumers gather it), then quantises them out of registers with the shared store_quant_pair; the frames'
+// max |x| goes through the wave (unsigned max of the f32 bits: a NaN frame wins), across the four waves in LDS, and
+// leaves the workgroup as ONE atomic per stem and tile.
+// ------------------------------------------------------------------------------------------------
+constexpr uint32_t kStemPairs = 4;
+constexpr uint32_t kStemTileFrames = kThreads * 2u * kStemPairs;   // 2 048
+TD_DEV uint32_t abs_bits(float x) { return __float_as_uint(x) & 0x7FFFFFFFu; }
+__global__ __launch_bounds__(kThreads) void k_stems(const StemDesc* __restrict__ descs, uint32_t M) {
+    const StemDesc& d = descs[blockIdx.y];
+    const TermTab src = term_tab(&d.src);
+    const uint32_t base = blockIdx.x * kStemTileFrames + 2u * threadIdx.x;
+    float4 v[kStemPairs];
+#pragma unroll
+    for (uint32_t q = 0; q < kStemPairs; ++q) {
+        const uint32_t m = base + q * 2u * kThreads;
+        v[q] = m < M ? term_pair(src, 0u, m, M) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    uint32_t pk = 0u;
+#pragma unroll
+    for (uint32_t q = 0; q < kStemPairs; ++q) {
+        const uint32_t m = base + q * 2u * kThreads;
+        if (m >= M) continue;
+        if (d.qmode) store_quant_pair(d.pcm, d.qmode, m, M, v[q], d.amplitude);
+        if (d.f32) {
+            if (m + 1 < M) gstore4(d.f32 + m, v[q]);
+            else d.f32[m] = make_float2(v[q].x, v[q].y);
+        }
+        pk = max(pk, max(abs_bits(v[q].x), abs_bits(v[q].y)));
+        if (m + 1 < M) pk = max(pk, max(abs_bits(v[q].z), abs_bits(v[q].w)));
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) pk = max(pk, (uint32_t)__shfl_xor((int)pk, off, 64));
+    __shared__ uint32_t wave_pk[kThreads / 64];
+    if ((threadIdx.x & 63u) == 0u) wave_pk[threadIdx.x / 64u] = pk;
+    __syncthreads();
+    if (threadIdx.x == 0u) {
+        uint32_t all = wave_pk[0];
+        for (uint32_t w = 1; w < kThreads / 64u; ++w) all = max(all, wave_pk[w]);
+        if (all) atomicMax(d.peak, all);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // k_sample_loop: out[m] = sample[(t0 + m) % len]   (extensions.rs:331-341)
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kThreads) void k_sample_loop(const LoopDesc* __restrict__ descs, uint32_t M) {
@@ -4593,6 +4638,10 @@ void launch_debug_verify(const uint32_t* p, uint32_t n_words, const uint32_t* se
 void launch_quantise(const QuantDesc* d, int n, uint32_t frames, hipStream_t s) {
     if (!n || !frames) return;
     TD_BATCHED(k_quantise, tiles(frames), kThreads, d, n, frames);
+}
+void launch_stems(const StemDesc* d, int n, uint32_t frames, hipStream_t s) {
+    if (!n || !frames) return;
+    TD_BATCHED(k_stems, (frames + kStemTileFrames - 1) / kStemTileFrames, kThreads, d, n, frames);
 }
 void launch_sample_loop(const LoopDesc* d, int n, uint32_t frames, hipStream_t s) {
     if (!n || !frames) return;

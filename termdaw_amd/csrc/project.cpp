@@ -5,6 +5,7 @@
 // with vertices grouped by type in the fixed order of state.rs:341-457, connect edges in call order,
 // set the output, check the graph and reset the normalize vertices.  State::render (state.rs:477-577)
 // drives the whole-timeline GPU render and writes the integer WAV.
+#include <ctype.h>
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
@@ -139,6 +140,9 @@ struct td_state {
         ~Pinned() { if (p) (void)hipHostFree(p); }
     } host_pcm;
     size_t out_frames = 0;
+    // td_state_set_stems: vertex names, resolved on the graph at every render (a refresh rebuilds the graph)
+    std::vector<std::string> stems;
+    bool stems_set = false;
 };
 
 namespace {
@@ -551,6 +555,20 @@ void td_state_free(td_state* s) {
 
 int td_state_set_option(td_state* s, const char* key, long value) { return td_graph_set_option(s->g, key, value); }
 
+int td_state_set_stems(td_state* s, const char* const* names, size_t n) {
+    std::vector<std::string> v;
+    for (size_t i = 0; i < n; ++i) {
+        if (!names || !names[i]) return fail("set_stems: null name");
+        for (const std::string& w : v)
+            if (w == names[i]) return fail(std::string("set_stems: vertex named twice: ") + names[i]);
+        v.push_back(names[i]);
+    }
+    s->stems = v;
+    s->stems_set = !v.empty();
+    if (!s->stems_set && !s->g->stems.empty() && !td_graph_set_stems(s->g, nullptr, 0)) return 0;
+    return 1;
+}
+
 int td_state_refresh_source(td_state* s, const char* lua_source) { return do_refresh(s, lua_source ? lua_source : ""); }
 
 int td_state_refresh(td_state* s) {
@@ -564,13 +582,40 @@ int td_state_refresh(td_state* s) {
     return do_refresh(s, ss.str());
 }
 
+static int apply_stems(td_state* s);
 int td_state_scan_exact(td_state* s) {
     if (!s->loaded) return fail("State not loaded!");   // check_loaded! ui_workflow.rs:101-109
+    if (!apply_stems(s)) return 0;   // (the scan walks the stems' plan too: a Normalize vertex only a stem reaches is scanned)
     return td_graph_normalize_scan(s->g, s->sb, s->fb, s->cs);
+}
+
+// The State's stems onto its graph (td_graph_set_stems), when they differ from what the graph holds.
+static int apply_stems(td_state* s) {
+    if (!s->stems_set) return 1;
+    std::vector<size_t> want;
+    for (const std::string& n : s->stems) {
+        auto it = s->g->name_map.find(n);
+        if (it == s->g->name_map.end()) return fail("stem vertex not found: " + n);
+        want.push_back(it->second);
+    }
+    if (want == s->g->stems) return 1;
+    std::vector<const char*> names;
+    for (const std::string& n : s->stems) names.push_back(n.c_str());
+    return td_graph_set_stems(s->g, names.data(), names.size());
+}
+// "<master minus .wav>.<vertex>.wav", characters outside [A-Za-z0-9._-] as '_'
+static std::string stem_path(const std::string& master, const std::string& vertex) {
+    std::string base = master;
+    if (base.size() >= 4 && base.compare(base.size() - 4, 4, ".wav") == 0) base.resize(base.size() - 4);
+    std::string v = vertex;
+    for (char& c : v)
+        if (!(isalnum((unsigned char)c) || c == '.' || c == '_' || c == '-')) c = '_';
+    return base + "." + v + ".wav";
 }
 
 static int state_render_device(td_state* s) {
     if (!s->loaded) return fail("State not loaded!");
+    if (!apply_stems(s)) return 0;
     if (!(s->bd == 8 || s->bd == 16 || s->bd == 24 || s->bd == 32))
         return fail("Bitdepth of " + std::to_string(s->bd) + " not supported: choose bitdepth in {8, 16, 24, 32}.");
     if (s->cs == 0) {
@@ -597,10 +642,32 @@ static int state_render_device(td_state* s) {
     return td_graph_read_pcm(s->g, s->host_pcm.data(), s->host_pcm.size());
 }
 
+// The stems of the render just done, one file each, with the output's header.
+static int write_stems(td_state* s, const std::vector<std::string>& paths) {
+    if (paths.empty() || !s->out_frames) return 1;
+    const size_t word = s->bd > 16 ? 4 : 2;
+    std::vector<uint8_t> pcm(s->out_frames * 2 * word);
+    std::string err;
+    for (size_t i = 0; i < paths.size(); ++i) {
+        if (!td_graph_read_stem_pcm(s->g, i, pcm.data(), pcm.size())) return 0;
+        if (!tdw::write_wav_int(paths[i].c_str(), pcm.data(), s->out_frames, 2, s->render_sr, (int)s->bd, &err)) return fail(err);
+    }
+    return 1;
+}
+
 int td_state_render(td_state* s, const char* path_override) {
-    if (!state_render_device(s)) return 0;
     std::string err;
     const std::string path = path_override ? path_override : s->output_file;
+    std::vector<std::string> stem_paths;
+    if (s->stems_set)
+        for (const std::string& n : s->stems) {
+            stem_paths.push_back(stem_path(path, n));
+            for (size_t j = 0; j + 1 < stem_paths.size(); ++j)
+                if (stem_paths[j] == stem_paths.back())
+                    return fail("stems \"" + s->stems[j] + "\" and \"" + n + "\" would both be written to " + stem_paths.back());
+        }
+    if (!state_render_device(s)) return 0;
+    if (!write_stems(s, stem_paths)) return 0;
     // A 60 s render is 11.5 MB of words that ARE the file's bytes (16- / 32-bit): one thread copying them into the page cache
     // took 2.0 of td_state_render's 2.3 ms.  Slices written side by side (pwrite at their own offsets, wav.cpp) make the same file.
     const size_t data_bytes = s->host_pcm.size();
