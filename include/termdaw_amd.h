@@ -177,6 +177,27 @@ const void* td_graph_stem_pcm_device(const td_graph* g, size_t i);
 int td_graph_read_stem_pcm(const td_graph* g, size_t i, void* out, size_t bytes);
 /* max |x| over the frames of stem i quantised in the last render (a NaN frame: NaN). */
 float td_graph_stem_peak(const td_graph* g, size_t i);
+/* Loudness of the last whole render (td_graph_render_all, _async, _resampled): ITU-R BS.1770-4 with the gating of EBU Tech 3341
+ * and the loudness range of EBU Tech 3342.  The reference has no counterpart (its README lists a LUFS mastering tool under
+ * "Goals for later").  What is measured is the PCM td_graph_read_pcm returns -- at the render's rate and bit depth, each word
+ * scaled by 1 / 2^(bits-1) as a WAV reader scales it -- so the figures are a file meter's on the WAV td_state_render writes; the
+ * graph is settled first as the read functions settle it (the deferred Normalize check, a guarded verdict).  Channels L and R,
+ * weight 1.0 each; K-weighting from zero state at frame 0; hops of round(rate / 10) frames, whole hops only.  Eight doubles per
+ * signal: [0] integrated LUFS, [1] momentary max LUFS, [2] short-term max LUFS, [3] loudness range LU, [4] true peak dBTP,
+ * [5] sample peak dBFS, [6] frames measured, [7] sample rate.  Silence: -inf loudness and peaks, LRA 0; fewer than 4 hops:
+ * integrated and momentary -inf; a NaN frame: [0]..[5] NaN.  DESIGN.md §3k gives the definitions, the filters and the kernel.
+ * td_graph_loudness: n signals -- 0 the output, 1 + i stem i of the same render -- in ONE k_loudness launch; fails when there is
+ * no whole render or n > 1 + the stems the render wrote.  The figures are bitwise reproducible. */
+int td_graph_loudness(td_graph* g, double* out, size_t n);
+/* The 400 ms block series (LUFS, one block per hop from hop 3 on) of signal `which` of the last td_graph_loudness: copies up to
+ * cap values (out may be NULL) and returns the count; 0 and td_last_error when there is no such signal. */
+size_t td_graph_momentary(const td_graph* g, size_t which, double* out, size_t cap);
+/* The same meter over interleaved host frames (f32, L R), measured on the device: frames * 2 floats at rate sr. */
+int td_loudness_f32(const float* lr, size_t frames, size_t sr, double out[8]);
+/* Host only, no GPU: the meter's filters at rate sr -- kw: the K-weighting shelf b0 b1 b2 a1 a2 then high-pass b0 b1 b2 a1 a2
+ * (a0 = 1); fir: the true-peak interpolator, *phases x *taps floats phase-major (phase 0 the unit impulse; 4 phases below 96 kHz,
+ * 2 below 192 kHz, else 1).  fir may be NULL to ask for the sizes; a fir of capacity cap too small fails. */
+int td_loudness_filters(size_t sr, double kw[10], float* fir, size_t cap, size_t* phases, size_t* taps);
 /* Timing hook for bench.py: enqueue one full render on the graph's stream without the final host
  * synchronisation (td_graph_sync waits).  Same work as td_graph_render_all. */
 size_t td_graph_render_all_async(td_graph* g, const td_samplebank* sb, td_flowwbank* fb, size_t n_blocks, int bits);
@@ -334,6 +355,10 @@ const void* td_batch_host_pcm(const td_batch* b, size_t i, size_t* bytes);
  * goes to entry first + i * stride, all other entries are zeroed. */
 int td_batch_peaks(td_batch* b, float* out);
 int td_batch_peak_table_device(td_batch* b, float* d_table, size_t n_total, size_t first, size_t stride);
+/* Loudness of every project's last render (td_graph_loudness's eight doubles per project, td_batch_add order), all in ONE
+ * k_loudness launch; BS.1770-4 / EBU Tech 3341 / 3342, no reference counterpart.  A project's figures are bitwise those of
+ * td_graph_loudness on its own graph. */
+int td_batch_loudness(td_batch* b, double* out);
 /* ---- the job's one collective, behind the C ABI (round 6).  BASELINE config 5: 512 independent projects over the 8 GPUs of a
  * node, one process per GPU, "RCCL over xGMI only for the final peak all-reduce".  The reference renders one project per process
  * (State::render's loop, state.rs:563-575); a batch driver running that loop on every GPU ends with this exchange.

@@ -1,4 +1,4 @@
-"""Headless render driver:  python -m termdaw_amd <project_dir> [--scan] [-o out.wav] [--stem NAME ...]
+"""Headless render driver:  python -m termdaw_amd <project_dir> [--scan] [-o out.wav] [--stem NAME ...] [--loudness]
                         python -m termdaw_amd <project_dir> --stream [--realtime] [-o out.wav] < events
 
 The reference renders only from its TUI (`render` / `normalize` commands, ui_workflow.rs:120-133); the first form is
@@ -6,6 +6,9 @@ the same sequence -- State::refresh, optionally State::scan_exact, State::render
 <project_dir> holds project.toml ([settings] main, buffer_length, project_samplerate) and the project script.
 --stem NAME (repeatable) renders vertex NAME in the same pass as well, to "<output minus .wav>.NAME.wav" -- what the
 render would write with set_output(NAME) -- and prints one line per stem: its path and peak ("clips" above 1.0).
+--loudness prints, after the render, one line per written file (the output, then each stem): its ITU-R BS.1770-4 / EBU R128
+integrated loudness, loudness range, momentary and short-term maxima, true peak and sample peak, measured on the device in
+one launch from the PCM the file holds.
 
 --stream is the reference's stream workflow (stream_workflow.rs:41-105) without the audio device: events for the
 streams the script declared (declare_stream) arrive on stdin, blocks are pulled one at a time at the playhead.
@@ -38,6 +41,8 @@ def main(argv=None):
                          "config 3's oscillators take 0.32 instead of 0.09 ms)")
     ap.add_argument("--stem", action="append", default=[], metavar="NAME",
                     help="also render vertex NAME to <output minus .wav>.NAME.wav in the same pass (repeatable)")
+    ap.add_argument("--loudness", action="store_true",
+                    help="after the render, print each written file's loudness (BS.1770-4 / EBU R128: I, LRA, M max, S max, dBTP, dBFS)")
     ap.add_argument("--stream", action="store_true", help="stream workflow: events from stdin, block pulls at the playhead")
     ap.add_argument("--realtime", action="store_true", help="with --stream: pace the pulls against the wall clock")
     args = ap.parse_args(argv)
@@ -71,7 +76,21 @@ def main(argv=None):
     for i, name in enumerate(args.stem):
         peak = g.stem_peak(i)
         print("stem %s: %s peak %.6g%s" % (name, stem_path(out, name), peak, " clips" if not peak <= 1.0 else ""))
+    if args.loudness:
+        try:
+            rows = g.loudness(stems=bool(args.stem))
+        except api.TermdawError as e:
+            print("TermDaw: loudness failed: %s" % e, file=sys.stderr)
+            return 1
+        for path, r in zip([out] + [stem_path(out, n) for n in args.stem], rows):
+            print(loudness_line(path, r))
     return 0
+
+
+def loudness_line(path, r):
+    """One --loudness line: integrated, loudness range, momentary / short-term maxima, true peak, sample peak."""
+    return ("loudness %s: I %.1f LUFS  LRA %.1f LU  M max %.1f LUFS  S max %.1f LUFS  %.1f dBTP  %.1f dBFS"
+            % (path, r["integrated"], r["lra"], r["momentary_max"], r["short_term_max"], r["true_peak"], r["sample_peak"]))
 
 
 def stem_path(master, vertex):

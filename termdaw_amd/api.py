@@ -88,6 +88,10 @@ SIGNATURES = {
     "td_graph_stem_pcm_device": (_vp, [_vp, _sz]),
     "td_graph_read_stem_pcm": (_i32, [_vp, _sz, _vp, _sz]),
     "td_graph_stem_peak": (_f32, [_vp, _sz]),
+    "td_graph_loudness": (_i32, [_vp, C.POINTER(C.c_double), _sz]),
+    "td_graph_momentary": (_sz, [_vp, _sz, C.POINTER(C.c_double), _sz]),
+    "td_loudness_f32": (_i32, [_fp, _sz, _sz, C.POINTER(C.c_double)]),
+    "td_loudness_filters": (_i32, [_sz, C.POINTER(C.c_double), _fp, _sz, C.POINTER(_sz), C.POINTER(_sz)]),
     "td_graph_render_all_async": (_sz, [_vp, _vp, _vp, _sz, _i32]),
     "td_graph_sync": (_i32, [_vp]),
     "td_graph_norm_fix_runs": (_sz, [_vp]),
@@ -116,6 +120,7 @@ SIGNATURES = {
     "td_batch_host_pcm": (_vp, [_vp, _sz, C.POINTER(_sz)]),
     "td_batch_peaks": (_i32, [_vp, _fp]),
     "td_batch_peak_table_device": (_i32, [_vp, _vp, _sz, _sz, _sz]),
+    "td_batch_loudness": (_i32, [_vp, C.POINTER(C.c_double)]),
     "td_comm_unique_id": (_i32, [_vp, _sz]),
     "td_comm_init": (_vp, [_vp, _sz, _i32, _i32]),
     "td_comm_init_host": (_vp, [_vp, _vp, _i32, _i32]),
@@ -220,6 +225,43 @@ def _fa(a):
 def _names(names):
     names = [n.encode() for n in names]
     return (_cp * max(1, len(names)))(*names), len(names)
+
+
+# -- loudness (ITU-R BS.1770-4 / EBU Tech 3341 / 3342; include/termdaw_amd.h td_graph_loudness) --
+LOUDNESS_FIELDS = ("integrated", "momentary_max", "short_term_max", "lra", "true_peak", "sample_peak", "frames", "sr")
+
+
+def _loudness_dicts(out, n):
+    rows = []
+    for i in range(n):
+        v = [float(x) for x in out[8 * i:8 * i + 8]]
+        d = dict(zip(LOUDNESS_FIELDS, v))
+        d["frames"], d["sr"] = int(v[6]), int(v[7])
+        rows.append(d)
+    return rows
+
+
+def loudness_f32(frames, sr):
+    """The meter over host frames: a (N, 2) float32 array (L, R) at rate sr, measured on the device -> one dict of
+    LOUDNESS_FIELDS (integrated / momentary_max / short_term_max in LUFS, lra in LU, true_peak in dBTP, sample_peak in dBFS)."""
+    a = np.ascontiguousarray(frames, dtype=np.float32).reshape(-1, 2)
+    out = (C.c_double * 8)()
+    _check(lib().td_loudness_f32(a.ctypes.data_as(_fp), a.shape[0], int(sr), out))
+    return _loudness_dicts(out, 1)[0]
+
+
+def loudness_filters(sr):
+    """The meter's filters at rate sr (host only): (shelf (b, a), high-pass (b, a)) as float64 arrays with a[0] = 1, and the
+    true-peak FIR as a (phases, taps) float32 array (phase 0 the unit impulse)."""
+    kw = (C.c_double * 10)()
+    ph, taps = _sz(0), _sz(0)
+    _check(lib().td_loudness_filters(int(sr), kw, None, 0, C.byref(ph), C.byref(taps)))
+    fir = np.zeros((ph.value, taps.value), np.float32)
+    _check(lib().td_loudness_filters(int(sr), kw, fir.ctypes.data_as(_fp), fir.size, C.byref(ph), C.byref(taps)))
+    k = np.array(kw[:], np.float64)
+    shelf = (k[0:3].copy(), np.array([1.0, k[3], k[4]]))
+    hp = (k[5:8].copy(), np.array([1.0, k[8], k[9]]))
+    return shelf, hp, fir
 
 
 def device_count():
@@ -501,6 +543,27 @@ class Graph:
         _check(lib().td_graph_band_stats(self.h, out))
         return {"mismatched": out[0], "recomputed": out[1], "parked": out[2]}
 
+    def loudness(self, stems=True):
+        """Loudness of the last whole render (render_all / render_all_async / render_all_resampled): the output, then with
+        stems=True every stem it wrote, in ONE launch -> a list of dicts of LOUDNESS_FIELDS."""
+        n = 1 + (int(lib().td_graph_stem_count(self.h)) if stems else 0)
+        if stems and n > 1 and not lib().td_graph_stem_pcm_device(self.h, n - 2):
+            n = 1   # (stems set since the render: it wrote none)
+        out = (C.c_double * (8 * n))()
+        _check(lib().td_graph_loudness(self.h, out, n))
+        self._loud_n = n
+        return _loudness_dicts(out, n)
+
+    def momentary(self, which=0):
+        """The 400 ms block series (LUFS) of signal `which` (0 the output, 1 + i stem i) of the last loudness() call."""
+        if not 0 <= which < getattr(self, "_loud_n", 0):
+            raise TermdawError("momentary: signal %d was not measured by this Graph object's last loudness()" % which)
+        n = lib().td_graph_momentary(self.h, which, None, 0)
+        out = np.zeros(n, np.float64)
+        if n:
+            lib().td_graph_momentary(self.h, which, out.ctypes.data_as(C.POINTER(C.c_double)), n)
+        return out
+
     def band_guard_stats(self):
         """band_mode 2: renders audited, renders done again with the exact kernels, last / largest estimated RMS deviation."""
         out = (C.c_double * 4)()
@@ -633,6 +696,12 @@ class Batch:
 
     def normalize_scan(self, chunks):
         _check(lib().td_batch_normalize_scan(self.h, chunks))
+
+    def loudness(self):
+        """Loudness of every project's last render in ONE launch (Graph.loudness's dict per project, td_batch_add order)."""
+        out = (C.c_double * (8 * max(len(self), 1)))()
+        _check(lib().td_batch_loudness(self.h, out))
+        return _loudness_dicts(out, len(self))
 
     def peaks(self):
         out = np.zeros(max(len(self), 1), np.float32)

@@ -27,6 +27,7 @@
 #include <thread>
 #include <limits>
 
+#include "loudness.h"
 #include "wav.h"
 
 using namespace tdk;
@@ -970,6 +971,7 @@ static int prepare_render(td_graph* g, size_t n_blocks, int bits, bool want_pcm,
     rp->multi = n_blocks > rp->chunk_blocks;
     rp->want_pcm = want_pcm;
     rp->bits = bits;
+    if (want_pcm) g->loud_frames = 0;   // (d_pcm is about to be overwritten: measurable again when the render has finished)
     if (want_pcm) {
         if (!(bits == 8 || bits == 16 || bits == 24 || bits == 32))   // state.rs:495-501
             return fail("Bitdepth not supported: choose bitdepth in {8, 16, 24, 32}.");
@@ -1039,6 +1041,7 @@ static void finish_render(td_graph* g, const RenderPlan& rp) {
         g->last_out_f32 = nullptr;   // (the f32 frames of the output were never written)
     g->last_frames = rp.total;
     g->last_bits = rp.bits;
+    if (rp.want_pcm) { g->loud_frames = rp.total; g->loud_bits = rp.bits; g->loud_sr = g->sr; }
 }
 
 // Everything queued for the graph has completed AND a deferred k_norm_fix has run if one was called for (settle_arena): the
@@ -1497,7 +1500,8 @@ void td_graph_free(td_graph* g) {
             }
     }
     const bool has_device_state = g->stream || !g->pool.empty() || !g->wavetables.empty() || g->dstate || g->arena.d || g->d_pcm ||
-                                  g->d_out_f32 || g->d_resampled || g->d_scalar || g->d_stem_pcm || g->d_stem_peak || g->d_stem_f32;
+                                  g->d_out_f32 || g->d_resampled || g->d_scalar || g->d_stem_pcm || g->d_stem_peak || g->d_stem_f32 ||
+                                  g->d_loud;
     if (has_device_state && hipSetDevice(g->device) == hipSuccess) {
         if (g->stream) (void)hipStreamSynchronize(g->stream);
         else (void)hipDeviceSynchronize();   // (a graph whose stream could not be re-made after td_batch_free)
@@ -1512,6 +1516,7 @@ void td_graph_free(td_graph* g) {
         if (g->d_stem_pcm) (void)hipFree(g->d_stem_pcm);
         if (g->d_stem_peak) (void)hipFree(g->d_stem_peak);
         if (g->d_stem_f32) (void)hipFree(g->d_stem_f32);
+        if (g->d_loud) (void)hipFree(g->d_loud);
         if (g->d_scalar) (void)hipFree(g->d_scalar);
         if (g->guard.d_backup) (void)hipFree(g->guard.d_backup);
         if (g->guard.h_word) (void)hipHostFree(g->guard.h_word);
@@ -1536,6 +1541,8 @@ void td_graph_reset(td_graph* g) {
     g->stems.clear();
     g->stems_rendered = 0;
     g->stem_taps = 0;
+    g->loud_frames = 0;
+    g->momentary.clear();
     g->t = 0;
     g->hstate.clear();
     g->state_host_dirty = true;
@@ -1891,6 +1898,7 @@ size_t td_graph_render_all_resampled(td_graph* g, const td_samplebank* sb, td_fl
         fail("Bitdepth not supported: choose bitdepth in {8, 16, 24, 32}.");
         return 0;
     }
+    g->loud_frames = 0;
     g->stem_f32_wanted = !g->stems.empty();   // (the stems' whole-timeline frames are resampled like the output's)
     int rendered = graph_render_chunks(g, sb, fb, n_blocks, false, bits, true, 0, false);
     rendered = rendered && graph_set_time_impl(g, 0) && drain(g);   // (the resampler reads the output vertex' frames)
@@ -1926,6 +1934,9 @@ size_t td_graph_render_all_resampled(td_graph* g, const td_samplebank* sb, td_fl
     g->last_frames = nout;
     g->last_bits = bits;
     if (!g->stems.empty() && !resample_stems(g, total, psr, render_sr, nout, amplitude, qmode)) return 0;
+    g->loud_frames = nout;
+    g->loud_bits = bits;
+    g->loud_sr = render_sr;
     return nout;
 }
 const void* td_graph_output_pcm_device(const td_graph* g) { return g->d_pcm; }
@@ -1966,6 +1977,134 @@ float td_graph_stem_peak(const td_graph* gc, size_t i) {
     float v;
     memcpy(&v, &bits, 4);
     return v;
+}
+// ---- loudness (include/termdaw_amd.h td_graph_loudness): ONE k_loudness launch over every signal asked for,
+// the hop energies and peak words back, the figures in double on the host ----
+static int measure_loudness(hipStream_t stream, uint8_t** d_work, size_t* cap, ProfCtx* prof, const std::vector<loud::Signal>& sig,
+                            double* out, std::vector<std::vector<double>>* mom) {
+    if (!launch_loudness) return fail("termdaw_amd: this build has no k_loudness kernel: loudness cannot be measured");
+    const size_t n = sig.size();
+    std::vector<LoudDesc> d(n);
+    std::vector<size_t> e_off(n);
+    size_t hops_total = 0;
+    uint32_t max_tiles = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const char* why = "";
+        if (!loud::describe(sig[i], d[i], &why)) return fail(why);
+        e_off[i] = hops_total;
+        hops_total += loud::hops(d[i]);
+        max_tiles = std::max(max_tiles, d[i].n_tiles);
+    }
+    const size_t desc_b = n * sizeof(LoudDesc), peak_b = (n * 8 + 7) & ~(size_t)7, need = desc_b + peak_b + hops_total * 16;
+    if (need > *cap) {
+        TD_HIP(hipStreamSynchronize(stream));
+        if (*d_work) (void)hipFree(*d_work);
+        *d_work = nullptr;
+        *cap = 0;
+        TD_HIP(hipMalloc(d_work, need));
+        *cap = need;
+    }
+    uint32_t* d_peak = (uint32_t*)(*d_work + desc_b);
+    double* d_energy = (double*)(*d_work + desc_b + peak_b);
+    for (size_t i = 0; i < n; ++i) {
+        d[i].pcm = sig[i].pcm;
+        d[i].peak = d_peak + 2 * i;
+        d[i].energy = d_energy + 2 * e_off[i];
+    }
+    TD_HIP(hipMemcpyAsync(*d_work, d.data(), desc_b, hipMemcpyHostToDevice, stream));
+    TD_HIP(hipMemsetAsync(d_peak, 0, peak_b, stream));
+    {
+        ProfCtx none;
+        ProfCtx& pc = prof ? *prof : none;
+        pc.now = pc.every != 0;   // (every measurement is timed while profiling is on)
+        Prof pr(pc, F_LOUD, stream);
+        launch_loudness((const LoudDesc*)*d_work, (int)n, max_tiles, stream);
+    }
+    TD_HIP(hipGetLastError());
+    std::vector<uint8_t> back(peak_b + hops_total * 16);
+    TD_HIP(hipMemcpyAsync(back.data(), d_peak, back.size(), hipMemcpyDeviceToHost, stream));
+    TD_HIP(hipStreamSynchronize(stream));
+    const uint32_t* peak = (const uint32_t*)back.data();
+    const double* energy = (const double*)(back.data() + peak_b);
+    if (mom) mom->assign(n, {});
+    std::vector<double> scratch;
+    for (size_t i = 0; i < n; ++i)
+        loud::figures(energy + 2 * e_off[i], loud::hops(d[i]), d[i].hop, peak + 2 * i, sig[i].frames, sig[i].sr, out + 8 * i,
+                      mom ? &(*mom)[i] : &scratch);
+    return 1;
+}
+// The output (0) or stem i - 1 of the last whole render, as a WAV reader would see it
+static loud::Signal render_signal(const td_graph* g, size_t which) {
+    loud::Signal s;
+    s.pcm = which ? (const void*)(g->d_stem_pcm + (which - 1) * g->stem_stride) : (const void*)g->d_pcm;
+    s.kind = g->loud_bits > 16 ? 1u : 0u;
+    s.scale = loud::word_scale(g->loud_bits);
+    s.frames = g->loud_frames;
+    s.sr = g->loud_sr;
+    return s;
+}
+int td_graph_loudness(td_graph* g, double* out, size_t n) {
+    if (!g->loud_frames || !g->d_pcm) return fail("loudness: no whole render to measure (td_graph_render_all / _async / _resampled)");
+    if (n > 1 + g->stems_rendered)
+        return fail("loudness: " + std::to_string(n) + " signals asked for, the last render has the output and " +
+                    std::to_string(g->stems_rendered) + " stems");
+    if (!drain(g)) return 0;   // (the deferred Normalize check and a guarded verdict settle first: the final bytes are measured)
+    if (!g->loud_frames || !g->d_pcm) return fail("loudness: no whole render to measure");
+    if (!n) return 1;
+    std::vector<loud::Signal> sig;
+    for (size_t i = 0; i < n; ++i) sig.push_back(render_signal(g, i));
+    return measure_loudness(g->stream, &g->d_loud, &g->loud_cap, &g->prof, sig, out, &g->momentary);
+}
+size_t td_graph_momentary(const td_graph* g, size_t which, double* out, size_t cap) {
+    if (which >= g->momentary.size()) { fail("momentary: no such signal in the last td_graph_loudness"); return 0; }
+    const std::vector<double>& m = g->momentary[which];
+    if (out) std::copy(m.begin(), m.begin() + (long)std::min(cap, m.size()), out);
+    return m.size();
+}
+int td_batch_loudness(td_batch* b, double* out) {
+    if (b->graphs.empty()) return 1;
+    for (size_t i = 0; i < b->graphs.size(); ++i)
+        if (!b->graphs[i]->loud_frames || !b->graphs[i]->d_pcm)
+            return fail("loudness: project " + std::to_string(i) + " has no whole render to measure");
+    if (!ensure_device(b->device)) return 0;
+    for (td_graph* g : b->graphs)
+        if (!drain(g)) return 0;
+    std::vector<loud::Signal> sig;
+    for (td_graph* g : b->graphs) sig.push_back(render_signal(g, 0));
+    hipStream_t st = b->stream ? b->stream : b->graphs[0]->stream;
+    return measure_loudness(st, &b->d_loud, &b->loud_cap, &b->prof, sig, out, nullptr);
+}
+int td_loudness_f32(const float* lr, size_t frames, size_t sr, double out[8]) {
+    if (!ensure_device(cur_device())) return 0;
+    if (frames && !lr) return fail("loudness_f32: null frames");
+    loud::Signal s;
+    s.kind = 2;
+    s.frames = frames;
+    s.sr = sr;
+    void* d_in = nullptr;
+    uint8_t* d_work = nullptr;
+    size_t cap = 0;
+    int ok = hipMalloc(&d_in, frames * 8 + 8) == hipSuccess ? 1 : fail("loudness_f32: out of device memory");
+    if (ok && frames && hipMemcpy(d_in, lr, frames * 8, hipMemcpyHostToDevice) != hipSuccess) ok = fail("HIP error: loudness_f32 upload");
+    s.pcm = d_in;
+    if (ok) ok = measure_loudness(nullptr, &d_work, &cap, nullptr, {s}, out, nullptr);
+    if (d_work) (void)hipFree(d_work);
+    if (d_in) (void)hipFree(d_in);
+    return ok;
+}
+int td_loudness_filters(size_t sr, double kw[10], float* fir, size_t cap, size_t* phases, size_t* taps) {
+    if (!sr) return fail("loudness_filters: the sample rate must be positive");
+    if (kw) loud::kweight((double)sr, kw);
+    const size_t P = loud::phases(sr);
+    if (phases) *phases = P;
+    if (taps) *taps = kLoudTaps;
+    if (fir) {
+        if (cap < P * kLoudTaps) return fail("loudness_filters: the FIR needs " + std::to_string(P * kLoudTaps) + " floats");
+        float f[4][kLoudTaps];
+        loud::fir(sr, f);
+        memcpy(fir, f, P * kLoudTaps * sizeof(float));
+    }
+    return 1;
 }
 const float* td_graph_output_f32_device(const td_graph* g) { return (const float*)g->last_out_f32; }
 int td_graph_read_pcm(const td_graph* g, void* out, size_t bytes) {
@@ -2192,7 +2331,7 @@ void td_batch_free(td_batch* b) {
         g->owns_stream = true;
         g->band_stats_base = nullptr;   // (it pointed into the batch arena's scratch, freed below)
         g->band_stats_off.clear();
-        if (g->pcm_borrowed) { g->d_pcm = nullptr; g->pcm_cap = 0; g->pcm_bytes = 0; g->pcm_borrowed = false; }   // (a slice of the batch's PCM arena)
+        if (g->pcm_borrowed) { g->d_pcm = nullptr; g->pcm_cap = 0; g->pcm_bytes = 0; g->pcm_borrowed = false; g->loud_frames = 0; }   // (a slice of the batch's PCM arena)
         if (dev_ok && hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) != hipSuccess) g->stream = nullptr;
     }
     if (dev_ok) {
@@ -2203,6 +2342,7 @@ void td_batch_free(td_batch* b) {
         if (b->h_table) (void)hipHostFree(b->h_table);
         if (b->copy_stream) { (void)hipStreamSynchronize(b->copy_stream); (void)hipStreamDestroy(b->copy_stream); }
         if (b->d_pcm_arena) (void)hipFree(b->d_pcm_arena);
+        if (b->d_loud) (void)hipFree(b->d_loud);
         for (hipEvent_t e : b->ev_pool) (void)hipEventDestroy(e);
         for (hipEvent_t e : b->ev_mark) if (e) (void)hipEventDestroy(e);
         if (b->host_pcm) (void)hipHostFree(b->host_pcm);
@@ -2320,7 +2460,7 @@ int td_batch_render_to_files(td_batch* b, size_t n_blocks, int bits, size_t rend
         if (!settle_arena(b->arena, b->stream)) return 0;   // (nothing queued may still write an old PCM buffer)
         if (need > b->d_pcm_arena_cap) {
             for (td_graph* g : b->graphs)
-                if (g->pcm_borrowed) { g->d_pcm = nullptr; g->pcm_cap = 0; g->pcm_bytes = 0; g->pcm_borrowed = false; }
+                if (g->pcm_borrowed) { g->d_pcm = nullptr; g->pcm_cap = 0; g->pcm_bytes = 0; g->pcm_borrowed = false; g->loud_frames = 0; }
             if (b->d_pcm_arena) (void)hipFree(b->d_pcm_arena);
             b->d_pcm_arena = nullptr;
             b->d_pcm_arena_cap = 0;

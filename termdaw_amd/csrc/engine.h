@@ -387,6 +387,13 @@ struct td_graph {
     size_t stems_rendered = 0;                // stems the last render wrote (0: none, or the list changed since)
     size_t chunk_frame0 = 0;                  // (set per chunk) frames of the render in front of the chunk being compiled
     unsigned stem_taps = 0;                   // (diagnostic, "debug.stem_taps") the fusions the stems switched off since the list was set: compile_chunk
+    // loudness (td_graph_loudness): what the last whole render left in d_pcm -- frames (0: nothing measurable), bit depth, rate
+    // (the render rate after td_graph_render_all_resampled) -- the meter's device workspace, and its block series per signal
+    size_t loud_frames = 0, loud_sr = 0;
+    int loud_bits = 16;
+    uint8_t* d_loud = nullptr;
+    size_t loud_cap = 0;
+    std::vector<std::vector<double>> momentary;
     size_t device_bytes = 0;
     bool fuse_sources = true;                  // inline sample_loop sources into their consumers
     bool packed_samples = true;                // inlined sources read the packed 16-bit sample form when it exists
@@ -462,6 +469,8 @@ struct td_batch {
     std::vector<hipEvent_t> ev_pool;
     hipEvent_t ev_mark[2] = {nullptr, nullptr};   // td_batch_mark
     bool mark_set[2] = {false, false};
+    uint8_t* d_loud = nullptr;           // td_batch_loudness: the meter's device workspace
+    size_t loud_cap = 0;
 };
 
 namespace tde {

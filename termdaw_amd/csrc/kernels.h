@@ -161,6 +161,32 @@ struct StemDesc {
     uint32_t qmode;     // 0 none, 1 int16, 2 int32
 };
 
+// One signal of a loudness measurement (k_loudness; ITU-R BS.1770-4 / EBU Tech 3341 / 3342): interleaved
+// stereo words, scaled by `scale` as a WAV reader scales them.  The signal is cut into tiles of `tile` frames (a whole
+// number of hops); the workgroup of a tile first runs the K-weighting cascade over the `kThreads * run - tile` frames in
+// front of it from zero state (the warm-up: the host sizes it so that the largest pole radius r gives r^warm <= 1e-12),
+// with each lane walking `run` frames and the lanes joined by a scan of the cascade's 4-dimensional state through `pw`.
+// It stores the sum of squares of the K-weighted channels over every whole hop it owns (energy[hop * 2 + c], plain
+// stores) and raises the signal's true / sample peak words (max |x| as f32 bits, atomicMax: order-independent).
+struct LoudDesc {
+    const void* pcm;
+    double* energy;         // [frames / hop][2]
+    uint32_t* peak;         // [0] true peak, [1] sample peak (the host zeroes them)
+    uint32_t kind;          // 0 int16, 1 int32, 2 f32
+    uint32_t frames;
+    uint32_t hop;
+    uint32_t tile;          // <= 128 hops
+    uint32_t run;           // <= hop
+    uint32_t n_tiles;
+    uint32_t phases;        // true-peak oversampling: 1, 2 or 4
+    uint32_t pad;
+    double scale;
+    double kw[10];          // shelf b0 b1 b2 a1 a2, then high-pass b0 b1 b2 a1 a2 (a0 = 1)
+    double pw[8][16];       // A^(run * 2^k), k = 0..7, row-major: A maps the cascade state (s1, s2, t1, t2) one frame on, input 0
+    float fir[4][12];       // phase p, tap i: the weight of x[m - 5 + i] in the point at m + p / phases (phase 0: the unit impulse)
+};
+constexpr uint32_t kLoudTaps = 12;
+
 // sample_loop_gen (extensions.rs:331-341): out[m] = sample[(t0 + m) % len]
 struct LoopDesc {
     const float2* sample;
@@ -585,6 +611,8 @@ void launch_quantise(const QuantDesc* d, int n_desc, uint32_t frames, hipStream_
 // Weak: the host engine calls it only when stems are set, and a host-only build of the engine (tests/mock_hip.cpp) has no
 // definition -- the engine then refuses stems with an error instead of failing to link.
 __attribute__((weak)) void launch_stems(const StemDesc* d, int n_desc, uint32_t frames, hipStream_t s);
+// Weak for the same reason: every signal of a loudness measurement in ONE launch (grid.x: the largest tile count).
+__attribute__((weak)) void launch_loudness(const LoudDesc* d, int n_desc, uint32_t max_tiles, hipStream_t s);
 void launch_sinf(const float* in, float* out, uint32_t n, int exact, hipStream_t s);   // out[i] = sin_glibc(in[i]) (exact) or sin_any(in[i])
 void launch_debug_verify(const uint32_t* p, uint32_t n_words, const uint32_t* seg_sums, uint32_t* report, hipStream_t s);   // (TD_DEBUG_SYNC & 16)
 void launch_sample_loop(const LoopDesc* d, int n_desc, uint32_t frames, hipStream_t s);

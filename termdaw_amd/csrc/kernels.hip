@@ -1178,6 +1178,211 @@ __global__ __launch_bounds__(kThreads) void k_stems(const StemDesc* __restrict__
 }
 
 // ------------------------------------------------------------------------------------------------
+// k_loudness: every signal of a loudness measurement in ONE grid -- blockIdx.y the signal, blockIdx.x a tile of d.tile frames
+// (a whole number of hops), the body instantiated per word kind.  The K-weighting cascade (two biquads per channel, transposed direct form II, f64)
+// is a linear recurrence with a 4-dimensional state per channel, so the workgroup runs it in parallel over the warm-up in
+// front of its tile and the tile itself: each lane walks `run` consecutive frames from zero state (pass 1), a 256-lane
+// Hillis-Steele scan in LDS joins the lanes' end states through the host's powers A^(run 2^k), and each lane walks its frames
+// again from the state it now knows (pass 2), summing y^2 of the tile's frames per hop.  The hop sums leave through LDS in
+// lane order (a fixed order: bitwise reproducible) as plain f64 stores.  The true peak is a 12-tap polyphase FIR over the
+// tile's frames (a window in registers, rotated by a 12-way unroll); the peaks leave as ONE atomicMax per word and tile.
+// Nothing here depends on how many signals share the launch.
+// ------------------------------------------------------------------------------------------------
+// Frame m, scaled; K is the word kind (the caller branches on it once, per workgroup).
+template <uint32_t K>
+TD_DEV double2 loud_word(const LoudDesc& d, int64_t m) {
+    double l, r;
+    if (K == 0u) {
+        const uint32_t w = reinterpret_cast<const uint32_t*>(d.pcm)[m];
+        l = (double)(int16_t)(w & 0xFFFFu);
+        r = (double)(int16_t)(w >> 16);
+    } else if (K == 1u) {
+        const int2 w = reinterpret_cast<const int2*>(d.pcm)[m];
+        l = (double)w.x;
+        r = (double)w.y;
+    } else {
+        const float2 w = reinterpret_cast<const float2*>(d.pcm)[m];
+        l = (double)w.x;
+        r = (double)w.y;
+    }
+    return make_double2(l * d.scale, r * d.scale);
+}
+// Frames m .. m + N - 1, zero outside [0, frames).  A block wholly inside (every lane but those at the signal's ends) loads
+// without a branch per frame, so its N loads are in flight together.
+template <uint32_t K, uint32_t N>
+TD_DEV void loud_block(const LoudDesc& d, int64_t m, double2 (&xs)[N]) {
+    if (m >= 0 && m + (int64_t)N <= (int64_t)d.frames) {
+#pragma unroll
+        for (uint32_t k = 0; k < N; ++k) xs[k] = loud_word<K>(d, m + k);
+    } else {
+#pragma unroll
+        for (uint32_t k = 0; k < N; ++k)
+            xs[k] = m + k >= 0 && m + k < (int64_t)d.frames ? loud_word<K>(d, m + k) : make_double2(0.0, 0.0);
+    }
+}
+// One frame of one channel through the cascade; s = (s1, s2) of the shelf, (t1, t2) of the high-pass.
+TD_DEV double kweight(const double* __restrict__ c, double* s, double x) {
+    const double u = fma(c[0], x, s[0]);
+    s[0] = fma(c[1], x, fma(-c[3], u, s[1]));
+    s[1] = fma(c[2], x, -c[4] * u);
+    const double v = fma(c[5], u, s[2]);
+    s[2] = fma(c[6], u, fma(-c[8], v, s[3]));
+    s[3] = fma(c[7], u, -c[9] * v);
+    return v;
+}
+constexpr uint32_t kLoudLoads = 8;   // frames a lane loads ahead of the recurrence
+template <uint32_t K>
+TD_DEV void loudness_tile(const LoudDesc& d, double (*sv)[8], int32_t* hop_of, uint32_t (*wave_pk)[kThreads / 64]) {
+    const uint32_t tid = threadIdx.x, run = d.run, hop = d.hop;
+    double c[10];
+#pragma unroll
+    for (int i = 0; i < 10; ++i) c[i] = d.kw[i];
+    const int64_t t0 = (int64_t)blockIdx.x * d.tile;
+    const int64_t q0 = (int64_t)tid * run - (int64_t)(kThreads * run - d.tile);   // the lane's first frame, relative to t0
+    const int64_t r0 = t0 + q0;
+    // pass 1: the lane's frames from zero state -> its end state
+    double st[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (uint32_t i0 = 0; i0 < run; i0 += kLoudLoads) {
+        double2 xs[kLoudLoads];
+        loud_block<K>(d, r0 + i0, xs);
+#pragma unroll
+        for (uint32_t k = 0; k < kLoudLoads; ++k)
+            if (i0 + k < run) {
+                (void)kweight(c, st, xs[k].x);
+                (void)kweight(c, st + 4, xs[k].y);
+            }
+    }
+    // the scan: after step k, lane j holds sum_{i in (j - 2^(k+1), j]} A^(run (j - i)) e_i of the lanes' zero-state end states e_i
+#pragma unroll 1
+    for (uint32_t k = 0; k < 8; ++k) {
+        const uint32_t off = 1u << k;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) sv[tid][i] = st[i];
+        __syncthreads();
+        if (tid >= off) {
+            const double* P = d.pw[k];
+#pragma unroll
+            for (int ch = 0; ch < 2; ++ch) {
+                double o[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) o[i] = sv[tid - off][ch * 4 + i];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    double a = st[ch * 4 + r];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) a = fma(P[r * 4 + i], o[i], a);
+                    st[ch * 4 + r] = a;
+                }
+            }
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) sv[tid][i] = st[i];
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 8; ++i) st[i] = tid ? sv[tid - 1][i] : 0.0;   // the lane's true start state
+    __syncthreads();
+    // pass 2: the same frames from that state; y^2 of the tile's whole-hop frames, per (hop slot, channel)
+    const int64_t whole = (int64_t)(d.frames / hop) * hop;
+    const int64_t lim = whole - t0 < (int64_t)d.tile ? whole - t0 : (int64_t)d.tile;   // tile frames [0, lim) count
+    const int32_t ha = q0 < 0 ? 0 : (int32_t)(q0 / hop);                                // (run <= hop: at most two hops)
+    double e[4] = {0.0, 0.0, 0.0, 0.0};
+    for (uint32_t i0 = 0; i0 < run; i0 += kLoudLoads) {
+        double2 xs[kLoudLoads];
+        loud_block<K>(d, r0 + i0, xs);
+#pragma unroll
+        for (uint32_t k = 0; k < kLoudLoads; ++k)
+            if (i0 + k < run) {
+                const double yl = kweight(c, st, xs[k].x);
+                const double yr = kweight(c, st + 4, xs[k].y);
+                const int64_t q = q0 + i0 + k;
+                if (q >= 0 && q < lim) {
+                    const bool second = (int32_t)(q / hop) != ha;
+                    e[second ? 2 : 0] = fma(yl, yl, e[second ? 2 : 0]);
+                    e[second ? 3 : 1] = fma(yr, yr, e[second ? 3 : 1]);
+                }
+            }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) sv[tid][i] = e[i];
+    hop_of[tid] = ha;
+    // the true peak: frames [t0 + tid * R, ...) of the tile, each the centre of a 12-frame window
+    const uint32_t R = (d.tile + kThreads - 1) / kThreads;
+    const int64_t m0 = t0 + (int64_t)tid * R;
+    int64_t m_end = t0 + (int64_t)d.tile < (int64_t)d.frames ? t0 + (int64_t)d.tile : (int64_t)d.frames;
+    if (m0 + R < m_end) m_end = m0 + R;
+    const int64_t cnt = m_end - m0;
+    uint32_t sp = 0u, tp = 0u;
+    if (cnt > 0) {
+        f2v w[kLoudTaps];
+        double2 xb[kLoudTaps];
+        loud_block<K>(d, m0 - 5, xb);
+#pragma unroll
+        for (uint32_t j = 0; j + 1 < kLoudTaps; ++j) w[j] = f2v{(float)xb[j].x, (float)xb[j].y};
+        for (int64_t b = 0; b < cnt; b += kLoudTaps) {
+            loud_block<K>(d, m0 + b + 6, xb);   // (the block's loads first, all in flight at once)
+#pragma unroll
+            for (uint32_t k = 0; k < kLoudTaps; ++k) {
+                if (b + k >= cnt) break;
+                w[(k + 11) % kLoudTaps] = f2v{(float)xb[k].x, (float)xb[k].y};
+                const f2v cur = w[(k + 5) % kLoudTaps];
+                sp = max(sp, max(abs_bits(cur.x), abs_bits(cur.y)));
+#pragma unroll
+                for (uint32_t p = 1; p < 4; ++p) {
+                    if (p >= d.phases) break;
+                    f2v a = {0.f, 0.f};
+#pragma unroll
+                    for (uint32_t j = 0; j < kLoudTaps; ++j) {
+                        const float h = d.fir[p][j];
+                        a = __builtin_elementwise_fma(f2v{h, h}, w[(k + j) % kLoudTaps], a);
+                    }
+                    tp = max(tp, max(abs_bits(a.x), abs_bits(a.y)));
+                }
+            }
+        }
+    }
+    tp = max(tp, sp);   // (phase 0 is the unit impulse: the samples themselves)
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        sp = max(sp, (uint32_t)__shfl_xor((int)sp, off, 64));
+        tp = max(tp, (uint32_t)__shfl_xor((int)tp, off, 64));
+    }
+    if ((tid & 63u) == 0u) { wave_pk[0][tid / 64u] = tp; wave_pk[1][tid / 64u] = sp; }
+    __syncthreads();
+    const uint32_t n_hops = d.tile / hop;
+    if (tid < 2u * n_hops) {   // hop h, channel ch: the lanes' partial sums in lane order
+        const int32_t h = (int32_t)(tid >> 1);
+        const uint32_t ch = tid & 1u;
+        double acc = 0.0;
+        for (uint32_t j = 0; j < kThreads; ++j) {
+            const int32_t hj = hop_of[j];
+            if (hj == h) acc += sv[j][ch];
+            else if (hj + 1 == h) acc += sv[j][2 + ch];
+        }
+        const uint64_t hg = (uint64_t)(t0 / hop) + (uint64_t)h;
+        if ((int64_t)hg * hop < whole) d.energy[hg * 2 + ch] = acc;
+    }
+    if (tid == 0u) {
+        uint32_t a = wave_pk[0][0], b = wave_pk[1][0];
+        for (uint32_t w = 1; w < kThreads / 64u; ++w) { a = max(a, wave_pk[0][w]); b = max(b, wave_pk[1][w]); }
+        if (a) atomicMax(d.peak, a);
+        if (b) atomicMax(d.peak + 1, b);
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void k_loudness(const LoudDesc* __restrict__ descs) {
+    const LoudDesc& d = descs[blockIdx.y];
+    if (blockIdx.x >= d.n_tiles) return;
+    __shared__ double sv[kThreads][8];
+    __shared__ int32_t hop_of[kThreads];
+    __shared__ uint32_t wave_pk[2][kThreads / 64];
+    if (d.kind == 0u) loudness_tile<0>(d, sv, hop_of, wave_pk);
+    else if (d.kind == 1u) loudness_tile<1>(d, sv, hop_of, wave_pk);
+    else loudness_tile<2>(d, sv, hop_of, wave_pk);
+}
+
+// ------------------------------------------------------------------------------------------------
 // k_sample_loop: out[m] = sample[(t0 + m) % len]   (extensions.rs:331-341)
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kThreads) void k_sample_loop(const LoopDesc* __restrict__ descs, uint32_t M) {
@@ -4642,6 +4847,10 @@ void launch_quantise(const QuantDesc* d, int n, uint32_t frames, hipStream_t s) 
 void launch_stems(const StemDesc* d, int n, uint32_t frames, hipStream_t s) {
     if (!n || !frames) return;
     TD_BATCHED(k_stems, (frames + kStemTileFrames - 1) / kStemTileFrames, kThreads, d, n, frames);
+}
+void launch_loudness(const LoudDesc* d, int n, uint32_t max_tiles, hipStream_t s) {
+    for (int o = 0; o < n && max_tiles; o += kMaxGridY)
+        hipLaunchKernelGGL(k_loudness, dim3(max_tiles, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
 }
 void launch_sample_loop(const LoopDesc* d, int n, uint32_t frames, hipStream_t s) {
     if (!n || !frames) return;
