@@ -198,6 +198,39 @@ int td_loudness_f32(const float* lr, size_t frames, size_t sr, double out[8]);
  * (a0 = 1); fir: the true-peak interpolator, *phases x *taps floats phase-major (phase 0 the unit impulse; 4 phases below 96 kHz,
  * 2 below 192 kHz, else 1).  fir may be NULL to ask for the sizes; a fir of capacity cap too small fails. */
 int td_loudness_filters(size_t sr, double kw[10], float* fir, size_t cap, size_t* phases, size_t* taps);
+/* Loudness mastering of the last whole render to a target integrated loudness T (LUFS, [-60, 0]) under a true-peak ceiling
+ * C (dBTP, [-30, 0]; c = 10^(C/20)): gain plus a lookahead brickwall limiter.  No reference counterpart (its README lists a
+ * "Lufs mastering tool" under "Goals for later"); DESIGN.md §3l.  Input x[n][c]: td_graph_loudness's signal -- the render's
+ * words scaled by 1 / 2^(bits-1) at its rate fs (after _resampled) -- or the caller's f32 frames (td_master_f32).
+ * Lookahead (ms, [0.1, 100], default 5): W = max(1, round(lookahead fs / 1000)) frames, half away from zero.  Release (ms,
+ * [1, 10000], default 100): a = exp(-1 / (release fs / 1000)).  One pass at gain g under the internal ceiling c':
+ *   1. p[n] = max over both channels of |x[n]| and of the meter's interpolated points at m + k/P (k = 1 .. P-1; the f32 FMA
+ *      chain over the 12 taps of its FIR in tap order, x = 0 outside [0, N)) for m = n and m = n - 1: bitwise the meter's points.
+ *   2. q[n] = max of p over [n, n + W - 1] (j < N).       3. h[n] = min(1, c' / (g q[n])); h = 1 where q = 0.
+ *   4. e[n] = min(h[n], 1 - a (1 - e[n-1])), e[-1] = 1 (u = 1 - e: u[n] = max(1 - h[n], a u[n-1]), a parallel scan), in f64.
+ *   5. G[n] = (1/W) sum of e[k] over k = n-W+1 .. n, in f64, with e[k < 0] = e[0] (the limiter settled on the opening peak):
+ *      every e in the window of frame n is at most c' / (g p[n]), so every sample point stays under c'.
+ *   6. words: saturate(trunc(w g G[n])) in f64 on the integer word w, to [-2^(bits-1), 2^(bits-1) - 1] (unity gain: the
+ *      identity); f32: (float)(x g G[n]).
+ * The pass loop (double, from the meter's figures): measure the input, L_in (-inf or NaN: "master: nothing to master");
+ * g1 = 10^((T - L_in)/20), c'1 = c.  After pass k: done when |I_k - T| <= 0.1 LU and TP_k <= C; else g *= 10^((T - I_k)/20)
+ * and, when TP_k > C, c' *= 10^((C - TP_k - 0.01)/20).  At most 4 passes aim at both; if pass 4 is still over C one more pass
+ * runs with g held and c' corrected, and if that is still over C the call fails and the rendered words are put back.  Missing
+ * the loudness target is not an error: report [14] says so.
+ * Report, TD_MASTER_FIELDS doubles per signal: [0..7] the meter's figures of the mastered signal (bitwise what
+ * td_graph_loudness returns right after), [8] input integrated LUFS, [9] input true peak dBTP, [10] the last pass' g,
+ * [11] its c' (linear), [12] min over n of G (as f32; 1.0 when the limiter never engaged), [13] passes run, [14] 1 when both
+ * targets were met.
+ * td_graph_master masters in place: the first call after a render keeps the output's words (device to device) and every call
+ * until the next render or td_graph_reset masters from that copy, so calls never compound.  Afterwards td_graph_read_pcm,
+ * td_graph_output_pcm_device, td_graph_loudness and the State's file see the mastered words; the stems, the f32 output and
+ * td_graph_output_peak stay as rendered.  The graph is settled first (as td_graph_loudness); no whole render fails. */
+#define TD_MASTER_FIELDS 15
+int td_graph_master(td_graph* g, double target_lufs, double ceiling_dbtp, double lookahead_ms, double release_ms, double* out);
+/* The same interleaved f32 frames (L R) from the host, measured and mastered on the device: out_lr gets frames * 2 floats,
+ * untouched when the call fails. */
+int td_master_f32(const float* lr, size_t frames, size_t sr, double target_lufs, double ceiling_dbtp, double lookahead_ms,
+                  double release_ms, float* out_lr, double* out);
 /* Timing hook for bench.py: enqueue one full render on the graph's stream without the final host
  * synchronisation (td_graph_sync waits).  Same work as td_graph_render_all. */
 size_t td_graph_render_all_async(td_graph* g, const td_samplebank* sb, td_flowwbank* fb, size_t n_blocks, int bits);
@@ -359,6 +392,10 @@ int td_batch_peak_table_device(td_batch* b, float* d_table, size_t n_total, size
  * k_loudness launch; BS.1770-4 / EBU Tech 3341 / 3342, no reference counterpart.  A project's figures are bitwise those of
  * td_graph_loudness on its own graph. */
 int td_batch_loudness(td_batch* b, double* out);
+/* td_graph_master on every project's last render (TD_MASTER_FIELDS doubles per project, td_batch_add order): pass k of every
+ * project in ONE launch per kernel, projects that are done drop out of later passes.  A project's words and report are bitwise
+ * those of td_graph_master on its own graph.  td_batch_render_to_files writes unmastered files (out of scope). */
+int td_batch_master(td_batch* b, double target_lufs, double ceiling_dbtp, double lookahead_ms, double release_ms, double* out);
 /* ---- the job's one collective, behind the C ABI (round 6).  BASELINE config 5: 512 independent projects over the 8 GPUs of a
  * node, one process per GPU, "RCCL over xGMI only for the final peak all-reduce".  The reference renders one project per process
  * (State::render's loop, state.rs:563-575); a batch driver running that loop on every GPU ends with this exchange.
@@ -425,6 +462,12 @@ int td_state_render(td_state* s, const char* path_override);
  * header; characters of X outside [A-Za-z0-9._-] become '_', and two stems that map to one file name are an error.
  * n = 0 clears the list. */
 int td_state_set_stems(td_state* s, const char* const* names, size_t n);
+/* Master every later render of the State (on = 1; 0: off, the default) to target_lufs under ceiling_dbtp with the default
+ * lookahead (5 ms) and release (100 ms): td_graph_master after the render, before the read-back, so td_state_render,
+ * _render_to_memory and _render_view return mastered words.  Stems are written unmastered. */
+int td_state_set_master(td_state* s, int on, double target_lufs, double ceiling_dbtp);
+/* The report (TD_MASTER_FIELDS doubles) of the State's last render; 0 when that render was not mastered. */
+int td_state_master_report(const td_state* s, double* out);
 /* Same render, PCM left in memory: copies frames*2 words to out (may be NULL to query the size). */
 size_t td_state_render_to_memory(td_state* s, void* out, size_t bytes);
 /* The same render, returned as a view of the library's own page-locked read-back buffer (interleaved PCM,

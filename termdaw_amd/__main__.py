@@ -1,4 +1,5 @@
 """Headless render driver:  python -m termdaw_amd <project_dir> [--scan] [-o out.wav] [--stem NAME ...] [--loudness]
+                                                 [--master LUFS[:DBTP]]
                         python -m termdaw_amd <project_dir> --stream [--realtime] [-o out.wav] < events
 
 The reference renders only from its TUI (`render` / `normalize` commands, ui_workflow.rs:120-133); the first form is
@@ -9,6 +10,10 @@ render would write with set_output(NAME) -- and prints one line per stem: its pa
 --loudness prints, after the render, one line per written file (the output, then each stem): its ITU-R BS.1770-4 / EBU R128
 integrated loudness, loudness range, momentary and short-term maxima, true peak and sample peak, measured on the device in
 one launch from the PCM the file holds.
+--master LUFS[:DBTP] masters the output before it is written: gain and a lookahead brickwall limiter to LUFS integrated
+loudness under a true-peak ceiling of DBTP (default -1), and prints one line: the input and output loudness, the gain, the
+largest limiter reduction, the true peak and the passes taken.  Stems are written unmastered; with --loudness the output's
+line describes the mastered file.
 
 --stream is the reference's stream workflow (stream_workflow.rs:41-105) without the audio device: events for the
 streams the script declared (declare_stream) arrive on stdin, blocks are pulled one at a time at the playhead.
@@ -20,6 +25,7 @@ and stops.  --realtime paces the pulls like the reference (half a second ahead o
 stream is rendered as fast as the events arrive.  The pulled blocks are written as a 16-bit WAV.
 """
 import argparse
+import math
 import re
 import sys
 import time
@@ -43,9 +49,11 @@ def main(argv=None):
                     help="also render vertex NAME to <output minus .wav>.NAME.wav in the same pass (repeatable)")
     ap.add_argument("--loudness", action="store_true",
                     help="after the render, print each written file's loudness (BS.1770-4 / EBU R128: I, LRA, M max, S max, dBTP, dBFS)")
+    ap.add_argument("--master", default=None, metavar="LUFS[:DBTP]",
+                    help="master the output to LUFS integrated loudness under a DBTP true-peak ceiling (default -1) before writing it")
     ap.add_argument("--stream", action="store_true", help="stream workflow: events from stdin, block pulls at the playhead")
     ap.add_argument("--realtime", action="store_true", help="with --stream: pace the pulls against the wall clock")
-    args = ap.parse_args(argv)
+    args = ap.parse_args(join_master_value(sys.argv[1:] if argv is None else list(argv)))
     api.set_device(args.device)
     s = api.State(open_dir=args.project_dir)
     if args.exact_bandpass:
@@ -62,6 +70,8 @@ def main(argv=None):
     try:
         if args.stem:
             s.set_stems(args.stem)
+        if args.master is not None:
+            s.set_master(*parse_master(args.master))
         if args.scan:
             s.scan_exact()
         s.render(args.output)
@@ -76,6 +86,8 @@ def main(argv=None):
     for i, name in enumerate(args.stem):
         peak = g.stem_peak(i)
         print("stem %s: %s peak %.6g%s" % (name, stem_path(out, name), peak, " clips" if not peak <= 1.0 else ""))
+    if args.master is not None:
+        print(master_line(out, s.master_report()))
     if args.loudness:
         try:
             rows = g.loudness(stems=bool(args.stem))
@@ -91,6 +103,39 @@ def loudness_line(path, r):
     """One --loudness line: integrated, loudness range, momentary / short-term maxima, true peak, sample peak."""
     return ("loudness %s: I %.1f LUFS  LRA %.1f LU  M max %.1f LUFS  S max %.1f LUFS  %.1f dBTP  %.1f dBFS"
             % (path, r["integrated"], r["lra"], r["momentary_max"], r["short_term_max"], r["true_peak"], r["sample_peak"]))
+
+
+def join_master_value(argv):
+    """`--master -14:-1` -> `--master=-14:-1`: argparse takes a value that starts with '-' and is not a plain negative number
+    for an option, so a target with a ceiling could otherwise only be given in the `=` form."""
+    out = []
+    i = 0
+    while i < len(argv):
+        if argv[i] == "--master" and i + 1 < len(argv):
+            out.append("--master=" + argv[i + 1])
+            i += 2
+        else:
+            out.append(argv[i])
+            i += 1
+    return out
+
+
+def parse_master(text):
+    """--master LUFS[:DBTP] -> (target LUFS, ceiling dBTP)."""
+    parts = text.split(":")
+    try:
+        if len(parts) > 2:
+            raise ValueError
+        return float(parts[0]), float(parts[1]) if len(parts) == 2 else -1.0
+    except ValueError:
+        raise api.TermdawError("--master: expected LUFS or LUFS:DBTP, got %r" % text)
+
+
+def master_line(path, r):
+    """One --master line: loudness in and out, the gain, the largest limiter reduction, the true peak, the passes."""
+    return ("master %s: I %.1f -> %.1f LUFS, gain %.2f dB, max reduction %.2f dB, %.1f dBTP, %d passes%s"
+            % (path, r["input_integrated"], r["integrated"], 20.0 * math.log10(r["gain"]), -20.0 * math.log10(max(r["min_gain"], 1e-300)),
+               r["true_peak"], r["passes"], "" if r["met"] else ", target not met"))
 
 
 def stem_path(master, vertex):

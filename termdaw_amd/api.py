@@ -92,6 +92,8 @@ SIGNATURES = {
     "td_graph_momentary": (_sz, [_vp, _sz, C.POINTER(C.c_double), _sz]),
     "td_loudness_f32": (_i32, [_fp, _sz, _sz, C.POINTER(C.c_double)]),
     "td_loudness_filters": (_i32, [_sz, C.POINTER(C.c_double), _fp, _sz, C.POINTER(_sz), C.POINTER(_sz)]),
+    "td_graph_master": (_i32, [_vp, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double)]),
+    "td_master_f32": (_i32, [_fp, _sz, _sz, C.c_double, C.c_double, C.c_double, C.c_double, _fp, C.POINTER(C.c_double)]),
     "td_graph_render_all_async": (_sz, [_vp, _vp, _vp, _sz, _i32]),
     "td_graph_sync": (_i32, [_vp]),
     "td_graph_norm_fix_runs": (_sz, [_vp]),
@@ -121,6 +123,7 @@ SIGNATURES = {
     "td_batch_peaks": (_i32, [_vp, _fp]),
     "td_batch_peak_table_device": (_i32, [_vp, _vp, _sz, _sz, _sz]),
     "td_batch_loudness": (_i32, [_vp, C.POINTER(C.c_double)]),
+    "td_batch_master": (_i32, [_vp, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double)]),
     "td_comm_unique_id": (_i32, [_vp, _sz]),
     "td_comm_init": (_vp, [_vp, _sz, _i32, _i32]),
     "td_comm_init_host": (_vp, [_vp, _vp, _i32, _i32]),
@@ -144,6 +147,8 @@ SIGNATURES = {
     "td_state_scan_exact": (_i32, [_vp]),
     "td_state_render": (_i32, [_vp, _cp]),
     "td_state_set_stems": (_i32, [_vp, C.POINTER(_cp), _sz]),
+    "td_state_set_master": (_i32, [_vp, _i32, C.c_double, C.c_double]),
+    "td_state_master_report": (_i32, [_vp, C.POINTER(C.c_double)]),
     "td_state_render_to_memory": (_sz, [_vp, _vp, _sz]),
     "td_state_render_view": (_vp, [_vp, C.POINTER(_sz)]),
     "td_state_chunk_count": (_sz, [_vp]),
@@ -262,6 +267,32 @@ def loudness_filters(sr):
     shelf = (k[0:3].copy(), np.array([1.0, k[3], k[4]]))
     hp = (k[5:8].copy(), np.array([1.0, k[8], k[9]]))
     return shelf, hp, fir
+
+
+# -- mastering (include/termdaw_amd.h td_graph_master): TD_MASTER_FIELDS doubles per signal --
+MASTER_FIELDS = LOUDNESS_FIELDS + ("input_integrated", "input_true_peak", "gain", "ceiling", "min_gain", "passes", "met")
+
+
+def _master_dicts(out, n):
+    rows = []
+    for i in range(n):
+        v = [float(x) for x in out[15 * i:15 * i + 15]]
+        d = dict(zip(MASTER_FIELDS, v))
+        d["frames"], d["sr"], d["passes"], d["met"] = int(v[6]), int(v[7]), int(v[13]), bool(v[14])
+        rows.append(d)
+    return rows
+
+
+def master_f32(frames, sr, target_lufs, ceiling_dbtp=-1.0, lookahead_ms=5.0, release_ms=100.0):
+    """Master host frames ((N, 2) float32, L R, at rate sr) on the device -> (mastered (N, 2) float32 frames, a dict of
+    MASTER_FIELDS): the meter's figures of the result, the input's integrated loudness and true peak, the last pass' linear
+    gain and internal ceiling, the smallest limiter gain, the passes run and whether both targets were met."""
+    a = np.ascontiguousarray(frames, dtype=np.float32).reshape(-1, 2)
+    res = np.zeros_like(a)
+    out = (C.c_double * 15)()
+    _check(lib().td_master_f32(a.ctypes.data_as(_fp), a.shape[0], int(sr), float(target_lufs), float(ceiling_dbtp),
+                               float(lookahead_ms), float(release_ms), res.ctypes.data_as(_fp), out))
+    return res, _master_dicts(out, 1)[0]
 
 
 def device_count():
@@ -554,6 +585,25 @@ class Graph:
         self._loud_n = n
         return _loudness_dicts(out, n)
 
+    def read_pcm(self, frames=None, bd=None):
+        """The output's words of the last whole render as they are now (after master(): mastered), frames x 2; frames and bd
+        default to those of this object's last render_all / render_all_resampled."""
+        if frames is None or bd is None:
+            f, dt = self._pcm_shape
+            frames = f if frames is None else frames
+            bd = (32 if dt == np.int32 else 16) if bd is None else bd
+        out = np.zeros((frames, 2), np.int32 if bd > 16 else np.int16)
+        if frames:
+            _check(lib().td_graph_read_pcm(self.h, out.ctypes.data_as(_vp), out.nbytes))
+        return out
+
+    def master(self, target_lufs, ceiling_dbtp=-1.0, lookahead_ms=5.0, release_ms=100.0):
+        """Master the last whole render in place to target_lufs under ceiling_dbtp (from the rendered words every time: calls
+        never compound) -> a dict of MASTER_FIELDS.  read_pcm / loudness() see the mastered words; stems and f32 frames do not."""
+        out = (C.c_double * 15)()
+        _check(lib().td_graph_master(self.h, float(target_lufs), float(ceiling_dbtp), float(lookahead_ms), float(release_ms), out))
+        return _master_dicts(out, 1)[0]
+
     def momentary(self, which=0):
         """The 400 ms block series (LUFS) of signal `which` (0 the output, 1 + i stem i) of the last loudness() call."""
         if not 0 <= which < getattr(self, "_loud_n", 0):
@@ -703,6 +753,12 @@ class Batch:
         _check(lib().td_batch_loudness(self.h, out))
         return _loudness_dicts(out, len(self))
 
+    def master(self, target_lufs, ceiling_dbtp=-1.0, lookahead_ms=5.0, release_ms=100.0):
+        """Graph.master on every project's last render, each pass of all projects in one launch per kernel -> a list of dicts."""
+        out = (C.c_double * (15 * max(len(self), 1)))()
+        _check(lib().td_batch_master(self.h, float(target_lufs), float(ceiling_dbtp), float(lookahead_ms), float(release_ms), out))
+        return _master_dicts(out, len(self))
+
     def peaks(self):
         out = np.zeros(max(len(self), 1), np.float32)
         _check(lib().td_batch_peaks(self.h, out.ctypes.data_as(_fp)))
@@ -792,6 +848,16 @@ class State:
         """Stems of the following renders, resolved at each render (an unknown name fails it before any file is written)."""
         arr, n = _names(names)
         _check(lib().td_state_set_stems(self.h, arr, n))
+
+    def set_master(self, target_lufs=None, ceiling_dbtp=-1.0):
+        """Master every following render to target_lufs under ceiling_dbtp (default lookahead and release); None: off."""
+        on = target_lufs is not None
+        _check(lib().td_state_set_master(self.h, int(on), float(target_lufs) if on else 0.0, float(ceiling_dbtp)))
+
+    def master_report(self):
+        """The MASTER_FIELDS dict of the last render, or None when it was not mastered."""
+        out = (C.c_double * 15)()
+        return _master_dicts(out, 1)[0] if lib().td_state_master_report(self.h, out) else None
 
     def render_to_memory(self):
         nbytes = lib().td_state_render_to_memory(self.h, None, 0)

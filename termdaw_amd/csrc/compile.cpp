@@ -20,7 +20,8 @@ namespace tde {
 
 const char* const kFamilyName[F_COUNT] = {"k_sample_loop", "k_sample_multi", "k_sample_lerp", "k_debug_sine",
                                            "k_synth",       "k_sampsyn", "k_adsr_env", "k_sine_probe", "k_sum",          "k_scale",       "k_norm_fix",
-                                           "k_adsr",        "k_band_pass",    "k_band_spec", "k_band_fix", "k_band_fill", "k_band_scan", "k_quantise", "k_band_audit", "k_stems", "k_sources", "k_loudness"};
+                                           "k_adsr",        "k_band_pass",    "k_band_spec", "k_band_fix", "k_band_fill", "k_band_scan", "k_quantise", "k_band_audit", "k_stems", "k_sources", "k_loudness",
+                                           "k_master_detect", "k_master_scan", "k_master_carry", "k_master_apply"};
 
 
 // ------------------------------------------------------------------------------------------------

@@ -11,7 +11,9 @@ namespace tde {
 enum Family { F_LOOP, F_MULTI, F_LERP, F_SINE, F_SYNTH, F_SAMPSYN, F_ENV, F_PROBE /* k_sine_probe: behind the sine kinds' launches of its level */, F_SUM, F_SCALE, F_NORMFIX, F_ADSR, F_BAND, F_BAND_SPEC, F_BAND_FIX, F_BAND_FILL, F_BAND_SCAN, F_QUANT, F_AUDIT,
               F_STEMS /* k_stems: the chunk's stems, behind everything else */,
               F_SOURCES /* (no descriptors of its own: several of the families above as ONE grid, submit_chunk) */,
-              F_LOUD /* k_loudness: td_graph_loudness / td_batch_loudness, launched outside the render (never compiled) */, F_COUNT };
+              F_LOUD /* k_loudness: td_graph_loudness / td_batch_loudness, launched outside the render (never compiled) */,
+              F_MASTER_DETECT, F_MASTER_SCAN, F_MASTER_CARRY, F_MASTER_APPLY /* k_master_*: td_graph_master / td_batch_master (never compiled) */,
+              F_COUNT };
 extern const char* const kFamilyName[F_COUNT];
 
 // ---- compile.cpp ----

@@ -28,6 +28,7 @@
 #include <limits>
 
 #include "loudness.h"
+#include "master.h"
 #include "wav.h"
 
 using namespace tdk;
@@ -971,7 +972,7 @@ static int prepare_render(td_graph* g, size_t n_blocks, int bits, bool want_pcm,
     rp->multi = n_blocks > rp->chunk_blocks;
     rp->want_pcm = want_pcm;
     rp->bits = bits;
-    if (want_pcm) g->loud_frames = 0;   // (d_pcm is about to be overwritten: measurable again when the render has finished)
+    if (want_pcm) { g->loud_frames = 0; g->master_kept = false; }   // (d_pcm is about to be overwritten: measurable again when the render has finished)
     if (want_pcm) {
         if (!(bits == 8 || bits == 16 || bits == 24 || bits == 32))   // state.rs:495-501
             return fail("Bitdepth not supported: choose bitdepth in {8, 16, 24, 32}.");
@@ -1501,7 +1502,7 @@ void td_graph_free(td_graph* g) {
     }
     const bool has_device_state = g->stream || !g->pool.empty() || !g->wavetables.empty() || g->dstate || g->arena.d || g->d_pcm ||
                                   g->d_out_f32 || g->d_resampled || g->d_scalar || g->d_stem_pcm || g->d_stem_peak || g->d_stem_f32 ||
-                                  g->d_loud;
+                                  g->d_loud || g->d_master_src || g->d_master;
     if (has_device_state && hipSetDevice(g->device) == hipSuccess) {
         if (g->stream) (void)hipStreamSynchronize(g->stream);
         else (void)hipDeviceSynchronize();   // (a graph whose stream could not be re-made after td_batch_free)
@@ -1517,6 +1518,8 @@ void td_graph_free(td_graph* g) {
         if (g->d_stem_peak) (void)hipFree(g->d_stem_peak);
         if (g->d_stem_f32) (void)hipFree(g->d_stem_f32);
         if (g->d_loud) (void)hipFree(g->d_loud);
+        if (g->d_master_src) (void)hipFree(g->d_master_src);
+        if (g->d_master) (void)hipFree(g->d_master);
         if (g->d_scalar) (void)hipFree(g->d_scalar);
         if (g->guard.d_backup) (void)hipFree(g->guard.d_backup);
         if (g->guard.h_word) (void)hipHostFree(g->guard.h_word);
@@ -1542,6 +1545,7 @@ void td_graph_reset(td_graph* g) {
     g->stems_rendered = 0;
     g->stem_taps = 0;
     g->loud_frames = 0;
+    g->master_kept = false;
     g->momentary.clear();
     g->t = 0;
     g->hstate.clear();
@@ -1899,6 +1903,7 @@ size_t td_graph_render_all_resampled(td_graph* g, const td_samplebank* sb, td_fl
         return 0;
     }
     g->loud_frames = 0;
+    g->master_kept = false;
     g->stem_f32_wanted = !g->stems.empty();   // (the stems' whole-timeline frames are resampled like the output's)
     int rendered = graph_render_chunks(g, sb, fb, n_blocks, false, bits, true, 0, false);
     rendered = rendered && graph_set_time_impl(g, 0) && drain(g);   // (the resampler reads the output vertex' frames)
@@ -2105,6 +2110,246 @@ int td_loudness_filters(size_t sr, double kw[10], float* fir, size_t cap, size_t
         memcpy(fir, f, P * kLoudTaps * sizeof(float));
     }
     return 1;
+}
+// ---- mastering (include/termdaw_amd.h td_graph_master): k_master_detect once, then per pass k_master_scan,
+// k_master_carry, k_master_apply and ONE k_loudness launch over the signals still running; the decisions in double on the host ----
+static int grow_device(hipStream_t stream, uint8_t** d, size_t* cap, size_t need) {
+    if (need <= *cap) return 1;
+    TD_HIP(hipStreamSynchronize(stream));
+    if (*d) (void)hipFree(*d);
+    *d = nullptr;
+    *cap = 0;
+    TD_HIP(hipMalloc(d, need));
+    *cap = need;
+    return 1;
+}
+static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+static loud::Signal meter_view(const void* pcm, const mst::Signal& s) {
+    loud::Signal m;
+    m.pcm = pcm;
+    m.kind = s.kind;
+    m.scale = s.kind == 2u ? 1.0 : loud::word_scale(s.bits);
+    m.frames = s.frames;
+    m.sr = s.sr;
+    return m;
+}
+static int have_master_kernels() {
+    if (!launch_master_detect || !launch_master_scan || !launch_master_carry || !launch_master_apply)
+        return fail("termdaw_amd: this build has no k_master kernels: mastering is not available");
+    return 1;
+}
+// Every dst back to its src (best effort: an error already set stays the call's error); 0 when a copy failed.
+static int restore_words(const std::vector<mst::Signal>& sig, hipStream_t stream) {
+    bool ok = true;
+    for (const mst::Signal& s : sig) {
+        const size_t bytes = s.frames * (s.kind == 0u ? 4 : 8);
+        if (bytes) ok &= hipMemcpyAsync(s.dst, s.src, bytes, hipMemcpyDeviceToDevice, stream) == hipSuccess;
+    }
+    ok &= hipStreamSynchronize(stream) == hipSuccess;
+    return ok ? 1 : 0;
+}
+// Masters every signal (src -> dst) and leaves mst::kFields doubles per signal in out.  `label(i)` names signal i in errors.
+// On any failure once the passes have begun (the ceiling not held, a HIP error, the meter failing) every dst holds its src again.
+static int master_signals(hipStream_t stream, uint8_t** d_work, size_t* cap, uint8_t** d_loud, size_t* loud_cap, ProfCtx* prof,
+                          const std::vector<mst::Signal>& sig, double T, double C, double lookahead_ms, double release_ms,
+                          double* out, std::string (*label)(size_t)) {
+    const size_t n = sig.size();
+    if (!n) return 1;
+    std::vector<double> fin(8 * n), fig(8 * n);
+    {
+        std::vector<loud::Signal> ms;
+        for (const mst::Signal& s : sig) ms.push_back(meter_view(s.src, s));
+        if (!measure_loudness(stream, d_loud, loud_cap, prof, ms, fin.data(), nullptr)) return 0;
+    }
+    for (size_t i = 0; i < n; ++i)
+        if (!std::isfinite(fin[8 * i]))
+            return fail("master: nothing to master (" + label(i) + "integrated loudness " + std::to_string(fin[8 * i]) +
+                        ": silence, fewer than 4 hops or everything gated)");
+    // the workspace: descriptors, min-G words, then per signal q, agg, carry
+    std::vector<MasterDesc> d(n);
+    std::vector<mst::Loop> lp(n);
+    const size_t desc_b = align256(n * sizeof(MasterDesc)), gmin_b = align256(n * 4);
+    size_t need = desc_b + gmin_b;
+    std::vector<size_t> q_off(n), a_off(n), c_off(n);
+    uint32_t max_tiles = 0;
+    for (size_t i = 0; i < n; ++i) {
+        mst::describe(sig[i], mst::window(lookahead_ms, sig[i].sr), mst::release_coef(release_ms, sig[i].sr), d[i]);
+        lp[i].start(T, C, fin[8 * i]);
+        q_off[i] = need;
+        need += align256(sig[i].frames * 4);
+        a_off[i] = need;
+        need += align256((size_t)d[i].n_tiles * 8);
+        c_off[i] = need;
+        need += align256((size_t)d[i].n_tiles * 8);
+        max_tiles = std::max(max_tiles, d[i].n_tiles);
+    }
+    if (!grow_device(stream, d_work, cap, need)) return 0;
+    uint8_t* w = *d_work;
+    uint32_t* d_gmin = (uint32_t*)(w + desc_b);
+    for (size_t i = 0; i < n; ++i) {
+        d[i].src = sig[i].src;
+        d[i].dst = sig[i].dst;
+        d[i].q = (float*)(w + q_off[i]);
+        d[i].agg = (double*)(w + a_off[i]);
+        d[i].carry = (double*)(w + c_off[i]);
+        d[i].gmin = d_gmin + i;
+        d[i].g = lp[i].g;
+        d[i].cp = lp[i].cp;
+    }
+    ProfCtx none;
+    ProfCtx& pc = prof ? *prof : none;
+    pc.now = pc.every != 0;   // (every call is timed while profiling is on)
+    TD_HIP(hipMemcpyAsync(w, d.data(), n * sizeof(MasterDesc), hipMemcpyHostToDevice, stream));
+    {
+        Prof pr(pc, F_MASTER_DETECT, stream);
+        launch_master_detect((const MasterDesc*)w, (int)n, max_tiles, stream);
+    }
+    TD_HIP(hipGetLastError());
+    std::vector<float> gmin(n, 1.0f);
+    bool failed = false;
+    auto run_passes = [&]() -> int {
+        for (;;) {
+            std::vector<size_t> act;
+            for (size_t i = 0; i < n; ++i)
+                if (!lp[i].done) act.push_back(i);
+            if (act.empty()) break;
+            std::vector<MasterDesc> ad;
+            uint32_t at = 0;
+            for (size_t i : act) {
+                d[i].g = lp[i].g;
+                d[i].cp = lp[i].cp;
+                d[i].gmin = d_gmin + ad.size();
+                ad.push_back(d[i]);
+                at = std::max(at, d[i].n_tiles);
+            }
+            const int na = (int)ad.size();
+            const std::vector<uint32_t> inf(act.size(), 0x7F800000u);
+            TD_HIP(hipMemcpyAsync(w, ad.data(), ad.size() * sizeof(MasterDesc), hipMemcpyHostToDevice, stream));
+            TD_HIP(hipMemcpyAsync(d_gmin, inf.data(), inf.size() * 4, hipMemcpyHostToDevice, stream));
+            pc.now = pc.every != 0;
+            { Prof pr(pc, F_MASTER_SCAN, stream); launch_master_scan((const MasterDesc*)w, na, at, stream); }
+            { Prof pr(pc, F_MASTER_CARRY, stream); launch_master_carry((const MasterDesc*)w, na, stream); }
+            { Prof pr(pc, F_MASTER_APPLY, stream); launch_master_apply((const MasterDesc*)w, na, at, stream); }
+            TD_HIP(hipGetLastError());
+            std::vector<uint32_t> words(act.size());
+            TD_HIP(hipMemcpyAsync(words.data(), d_gmin, words.size() * 4, hipMemcpyDeviceToHost, stream));
+            std::vector<loud::Signal> ms;
+            for (size_t i : act) ms.push_back(meter_view(sig[i].dst, sig[i]));
+            std::vector<double> f(8 * act.size());
+            if (!measure_loudness(stream, d_loud, loud_cap, prof, ms, f.data(), nullptr)) return 0;   // (synchronises the stream)
+            for (size_t k = 0; k < act.size(); ++k) {
+                const size_t i = act[k];
+                memcpy(&gmin[i], &words[k], 4);
+                std::copy(f.begin() + (long)(8 * k), f.begin() + (long)(8 * k + 8), fig.begin() + (long)(8 * i));
+                lp[i].after(f[8 * k], f[8 * k + 4]);
+                failed |= lp[i].failed;
+            }
+        }
+        return 1;
+    };
+    if (!run_passes()) {
+        (void)restore_words(sig, stream);
+        return 0;
+    }
+    if (failed) {
+        std::string who;
+        for (size_t i = 0; i < n && who.empty(); ++i)
+            if (lp[i].failed) who = label(i) + "true peak " + std::to_string(fig[8 * i + 4]) + " dBTP";
+        const bool back = restore_words(sig, stream);
+        return fail("master: the ceiling could not be held (" + who + " after " + std::to_string(mst::kAimedPasses + 1) +
+                    " passes): " + (back ? "the rendered words are back" : "HIP error while putting the rendered words back"));
+    }
+    for (size_t i = 0; i < n; ++i) {
+        double* o = out + (size_t)mst::kFields * i;
+        std::copy(fig.begin() + (long)(8 * i), fig.begin() + (long)(8 * i + 8), o);
+        o[8] = fin[8 * i];
+        o[9] = fin[8 * i + 4];
+        o[10] = lp[i].g;
+        o[11] = lp[i].cp;
+        o[12] = (double)gmin[i];
+        o[13] = (double)lp[i].passes;
+        o[14] = lp[i].met ? 1.0 : 0.0;
+    }
+    return 1;
+}
+// The output of g's last whole render as a signal to master from the kept copy (made here when there is none).
+static int master_view(td_graph* g, hipStream_t stream, mst::Signal* s) {
+    const size_t bytes = g->loud_frames * (g->loud_bits > 16 ? 8 : 4);
+    if (!g->master_kept) {
+        if (!grow_device(stream, &g->d_master_src, &g->master_src_cap, bytes)) return 0;
+        TD_HIP(hipMemcpyAsync(g->d_master_src, g->d_pcm, bytes, hipMemcpyDeviceToDevice, stream));
+        g->master_kept = true;
+    }
+    s->src = g->d_master_src;
+    s->dst = g->d_pcm;
+    s->kind = g->loud_bits > 16 ? 1u : 0u;
+    s->bits = g->loud_bits;
+    s->frames = g->loud_frames;
+    s->sr = g->loud_sr;
+    return 1;
+}
+int td_graph_master(td_graph* g, double target_lufs, double ceiling_dbtp, double lookahead_ms, double release_ms, double* out) {
+    const std::string bad = mst::check(target_lufs, ceiling_dbtp, lookahead_ms, release_ms);
+    if (!bad.empty()) return fail(bad);
+    if (!g->loud_frames || !g->d_pcm) return fail("master: no whole render to master (td_graph_render_all / _async / _resampled)");
+    if (!drain(g)) return 0;   // (the deferred Normalize check and a guarded verdict settle first, as for td_graph_loudness)
+    if (!g->loud_frames || !g->d_pcm) return fail("master: no whole render to master");
+    if (!have_master_kernels()) return 0;
+    if (!out) return fail("master: null report");
+    mst::Signal s;
+    if (!master_view(g, g->stream, &s)) return 0;
+    return master_signals(g->stream, &g->d_master, &g->master_cap, &g->d_loud, &g->loud_cap, &g->prof, {s}, target_lufs,
+                          ceiling_dbtp, lookahead_ms, release_ms, out, [](size_t) { return std::string(); });
+}
+int td_batch_master(td_batch* b, double target_lufs, double ceiling_dbtp, double lookahead_ms, double release_ms, double* out) {
+    const std::string bad = mst::check(target_lufs, ceiling_dbtp, lookahead_ms, release_ms);
+    if (!bad.empty()) return fail(bad);
+    if (b->graphs.empty()) return 1;
+    for (size_t i = 0; i < b->graphs.size(); ++i)
+        if (!b->graphs[i]->loud_frames || !b->graphs[i]->d_pcm)
+            return fail("master: project " + std::to_string(i) + " has no whole render to master");
+    if (!ensure_device(b->device)) return 0;
+    for (td_graph* g : b->graphs)
+        if (!drain(g)) return 0;
+    if (!have_master_kernels()) return 0;
+    if (!out) return fail("master: null report");
+    hipStream_t st = b->stream ? b->stream : b->graphs[0]->stream;
+    std::vector<mst::Signal> sig(b->graphs.size());
+    for (size_t i = 0; i < b->graphs.size(); ++i)
+        if (!master_view(b->graphs[i], st, &sig[i])) return 0;
+    return master_signals(st, &b->d_master, &b->master_cap, &b->d_loud, &b->loud_cap, &b->prof, sig, target_lufs, ceiling_dbtp,
+                          lookahead_ms, release_ms, out, [](size_t i) { return "project " + std::to_string(i) + ": "; });
+}
+int td_master_f32(const float* lr, size_t frames, size_t sr, double target_lufs, double ceiling_dbtp, double lookahead_ms,
+                  double release_ms, float* out_lr, double* out) {
+    const std::string bad = mst::check(target_lufs, ceiling_dbtp, lookahead_ms, release_ms);
+    if (!bad.empty()) return fail(bad);
+    if (!ensure_device(cur_device())) return 0;
+    if (frames && (!lr || !out_lr)) return fail("master_f32: null frames");
+    if (!out) return fail("master_f32: null report");
+    if (!have_master_kernels()) return 0;
+    mst::Signal s;
+    s.kind = 2;
+    s.frames = frames;
+    s.sr = sr;
+    void* d_in = nullptr;
+    void* d_out = nullptr;
+    uint8_t *d_work = nullptr, *d_loud = nullptr;
+    size_t cap = 0, loud_cap = 0;
+    int ok = hipMalloc(&d_in, frames * 8 + 16) == hipSuccess && hipMalloc(&d_out, frames * 8 + 16) == hipSuccess
+                 ? 1 : fail("master_f32: out of device memory");
+    if (ok && frames && hipMemcpy(d_in, lr, frames * 8, hipMemcpyHostToDevice) != hipSuccess) ok = fail("HIP error: master_f32 upload");
+    s.src = d_in;
+    s.dst = d_out;
+    if (ok)
+        ok = master_signals(nullptr, &d_work, &cap, &d_loud, &loud_cap, nullptr, {s}, target_lufs, ceiling_dbtp, lookahead_ms,
+                            release_ms, out, [](size_t) { return std::string(); });
+    if (ok && frames && hipMemcpy(out_lr, d_out, frames * 8, hipMemcpyDeviceToHost) != hipSuccess) ok = fail("HIP error: master_f32 download");
+    if (d_work) (void)hipFree(d_work);
+    if (d_loud) (void)hipFree(d_loud);
+    if (d_out) (void)hipFree(d_out);
+    if (d_in) (void)hipFree(d_in);
+    return ok;
 }
 const float* td_graph_output_f32_device(const td_graph* g) { return (const float*)g->last_out_f32; }
 int td_graph_read_pcm(const td_graph* g, void* out, size_t bytes) {
@@ -2331,7 +2576,7 @@ void td_batch_free(td_batch* b) {
         g->owns_stream = true;
         g->band_stats_base = nullptr;   // (it pointed into the batch arena's scratch, freed below)
         g->band_stats_off.clear();
-        if (g->pcm_borrowed) { g->d_pcm = nullptr; g->pcm_cap = 0; g->pcm_bytes = 0; g->pcm_borrowed = false; g->loud_frames = 0; }   // (a slice of the batch's PCM arena)
+        if (g->pcm_borrowed) { g->d_pcm = nullptr; g->pcm_cap = 0; g->pcm_bytes = 0; g->pcm_borrowed = false; g->loud_frames = 0; g->master_kept = false; }   // (a slice of the batch's PCM arena)
         if (dev_ok && hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) != hipSuccess) g->stream = nullptr;
     }
     if (dev_ok) {
@@ -2343,6 +2588,7 @@ void td_batch_free(td_batch* b) {
         if (b->copy_stream) { (void)hipStreamSynchronize(b->copy_stream); (void)hipStreamDestroy(b->copy_stream); }
         if (b->d_pcm_arena) (void)hipFree(b->d_pcm_arena);
         if (b->d_loud) (void)hipFree(b->d_loud);
+        if (b->d_master) (void)hipFree(b->d_master);
         for (hipEvent_t e : b->ev_pool) (void)hipEventDestroy(e);
         for (hipEvent_t e : b->ev_mark) if (e) (void)hipEventDestroy(e);
         if (b->host_pcm) (void)hipHostFree(b->host_pcm);
@@ -2460,7 +2706,7 @@ int td_batch_render_to_files(td_batch* b, size_t n_blocks, int bits, size_t rend
         if (!settle_arena(b->arena, b->stream)) return 0;   // (nothing queued may still write an old PCM buffer)
         if (need > b->d_pcm_arena_cap) {
             for (td_graph* g : b->graphs)
-                if (g->pcm_borrowed) { g->d_pcm = nullptr; g->pcm_cap = 0; g->pcm_bytes = 0; g->pcm_borrowed = false; g->loud_frames = 0; }
+                if (g->pcm_borrowed) { g->d_pcm = nullptr; g->pcm_cap = 0; g->pcm_bytes = 0; g->pcm_borrowed = false; g->loud_frames = 0; g->master_kept = false; }
             if (b->d_pcm_arena) (void)hipFree(b->d_pcm_arena);
             b->d_pcm_arena = nullptr;
             b->d_pcm_arena_cap = 0;

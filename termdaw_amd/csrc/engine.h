@@ -394,6 +394,13 @@ struct td_graph {
     uint8_t* d_loud = nullptr;
     size_t loud_cap = 0;
     std::vector<std::vector<double>> momentary;
+    // mastering (td_graph_master): the rendered words of the output, kept by the first call after a render (d_pcm is mastered
+    // in place; every call masters from this copy), and the passes' device workspace
+    bool master_kept = false;
+    uint8_t* d_master_src = nullptr;
+    size_t master_src_cap = 0;
+    uint8_t* d_master = nullptr;
+    size_t master_cap = 0;
     size_t device_bytes = 0;
     bool fuse_sources = true;                  // inline sample_loop sources into their consumers
     bool packed_samples = true;                // inlined sources read the packed 16-bit sample form when it exists
@@ -471,6 +478,8 @@ struct td_batch {
     bool mark_set[2] = {false, false};
     uint8_t* d_loud = nullptr;           // td_batch_loudness: the meter's device workspace
     size_t loud_cap = 0;
+    uint8_t* d_master = nullptr;         // td_batch_master: the passes' device workspace
+    size_t master_cap = 0;
 };
 
 namespace tde {

@@ -187,6 +187,39 @@ struct LoudDesc {
 };
 constexpr uint32_t kLoudTaps = 12;
 
+// One signal of a mastering pass (k_master_detect / k_master_scan / k_master_carry / k_master_apply): a
+// lookahead brickwall limiter at gain g under the internal ceiling cp over interleaved stereo words scaled by `scale`.  The
+// signal is cut into tiles of kMasterTile frames; a lane owns kMasterRun consecutive frames of a tile.  k_master_detect leaves
+// q[n] = max of the detector p over [n, n + W - 1] (p: |x| and the meter's interpolated points next to frame n, as f32);
+// the release u[n] = max(1 - h[n], a u[n - 1]) (h = min(1, cp / (g q))) is a (max, x) recurrence: k_master_scan leaves
+// each tile's zero-start end value in agg[], k_master_carry the value entering each tile in carry[], and k_master_apply
+// rebuilds e = 1 - u from there, forms G as the mean of e over the W frames ending at n (e[0] before frame 0) and writes
+// saturate(trunc(w g G)) (f32: (float)(x g G)) to dst, and the smallest G as f32 bits to *gmin (atomicMin).
+constexpr uint32_t kMasterRun = 8;                       // frames per lane
+constexpr uint32_t kMasterTile = kMasterRun * kThreads;  // frames per workgroup
+struct MasterDesc {
+    const void* src;        // the words as rendered (never written)
+    void* dst;              // the mastered words
+    float* q;               // [frames]
+    double* agg;            // [n_tiles]
+    double* carry;          // [n_tiles]
+    uint32_t* gmin;         // the host sets +inf bits
+    uint32_t kind;          // 0 int16, 1 int32, 2 f32
+    uint32_t frames;
+    uint32_t n_tiles;
+    uint32_t W;             // lookahead window, frames (1 .. 2^20)
+    uint32_t chunk;         // tiles per lane in k_master_carry
+    uint32_t phases;        // the meter's true-peak oversampling: 1, 2 or 4
+    int32_t lo, hi;         // the bit depth's word range (saturation)
+    double scale;
+    double g, cp;           // this pass' gain and internal ceiling (linear)
+    double pw[8];           // a^(kMasterRun * 2^k)
+    double pwc[8];          // a^(kMasterTile * chunk * 2^k)
+    double a_tile;          // a^kMasterTile
+    double a;               // the release coefficient
+    float fir[4][12];       // the meter's FIR (LoudDesc::fir)
+};
+
 // sample_loop_gen (extensions.rs:331-341): out[m] = sample[(t0 + m) % len]
 struct LoopDesc {
     const float2* sample;
@@ -613,6 +646,12 @@ void launch_quantise(const QuantDesc* d, int n_desc, uint32_t frames, hipStream_
 __attribute__((weak)) void launch_stems(const StemDesc* d, int n_desc, uint32_t frames, hipStream_t s);
 // Weak for the same reason: every signal of a loudness measurement in ONE launch (grid.x: the largest tile count).
 __attribute__((weak)) void launch_loudness(const LoudDesc* d, int n_desc, uint32_t max_tiles, hipStream_t s);
+// Weak for the same reason: the mastering launches, every signal of a pass in ONE grid each (grid.x: the largest tile count;
+// launch_master_carry: one workgroup per signal).
+__attribute__((weak)) void launch_master_detect(const MasterDesc* d, int n_desc, uint32_t max_tiles, hipStream_t s);
+__attribute__((weak)) void launch_master_scan(const MasterDesc* d, int n_desc, uint32_t max_tiles, hipStream_t s);
+__attribute__((weak)) void launch_master_carry(const MasterDesc* d, int n_desc, hipStream_t s);
+__attribute__((weak)) void launch_master_apply(const MasterDesc* d, int n_desc, uint32_t max_tiles, hipStream_t s);
 void launch_sinf(const float* in, float* out, uint32_t n, int exact, hipStream_t s);   // out[i] = sin_glibc(in[i]) (exact) or sin_any(in[i])
 void launch_debug_verify(const uint32_t* p, uint32_t n_words, const uint32_t* seg_sums, uint32_t* report, hipStream_t s);   // (TD_DEBUG_SYNC & 16)
 void launch_sample_loop(const LoopDesc* d, int n_desc, uint32_t frames, hipStream_t s);

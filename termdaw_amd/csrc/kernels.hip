@@ -1383,6 +1383,406 @@ __global__ __launch_bounds__(kThreads) void k_loudness(const LoudDesc* __restric
 }
 
 // ------------------------------------------------------------------------------------------------
+// k_master_*: loudness mastering (td_graph_master) -- a lookahead brickwall limiter at gain g under the
+// internal ceiling cp, every signal of a pass in ONE grid per kernel (blockIdx.y the signal), each signal's tiling its own.
+//   k_master_detect (once per call): q[n] = max over [n, n + W - 1] of p, p[n] = max(|x[n]|, the meter's interpolated
+//     points at n + k/P and n - 1 + k/P) -- the same f32 FMA chain as k_loudness, so the limiter sees the meter's points.
+//   k_master_scan: each tile's release u from 0 at its start (lanes' runs joined by an LDS scan of (max, x)) -> agg[tile].
+//   k_master_carry: one workgroup per signal scans agg[] -> carry[tile], the u entering each tile.
+//   k_master_apply: e = 1 - u from the carries, G = mean of e over the W frames ending at n (e[0] before frame 0), the
+//     words at g G.
+// No workgroup waits for another: the scan is three launches.
+// ------------------------------------------------------------------------------------------------
+// Frame m as the meter's true-peak window holds it (f32 of the scaled word); 0 outside [0, frames).
+template <uint32_t K>
+TD_DEV float2 mst_frame(const MasterDesc& d, int64_t m) {
+    if (m < 0 || m >= (int64_t)d.frames) return make_float2(0.f, 0.f);
+    double l, r;
+    if (K == 0u) {
+        const uint32_t w = reinterpret_cast<const uint32_t*>(d.src)[m];
+        l = (double)(int16_t)(w & 0xFFFFu);
+        r = (double)(int16_t)(w >> 16);
+    } else if (K == 1u) {
+        const int2 w = reinterpret_cast<const int2*>(d.src)[m];
+        l = (double)w.x;
+        r = (double)w.y;
+    } else {
+        const float2 w = reinterpret_cast<const float2*>(d.src)[m];
+        l = (double)w.x;
+        r = (double)w.y;
+    }
+    return make_float2((float)(l * d.scale), (float)(r * d.scale));
+}
+// max |point| over phases 1 .. P - 1 and both channels of the frame at the centre (xw[5]) of a 12-frame window
+TD_DEV float mst_points(const MasterDesc& d, const float2 (&xw)[kLoudTaps]) {
+    float mx = 0.f;
+#pragma unroll
+    for (uint32_t p = 1; p < 4; ++p) {
+        if (p >= d.phases) break;
+        float al = 0.f, ar = 0.f;
+#pragma unroll
+        for (uint32_t j = 0; j < kLoudTaps; ++j) {
+            const float h = d.fir[p][j];
+            al = fmaf(h, xw[j].x, al);
+            ar = fmaf(h, xw[j].y, ar);
+        }
+        mx = fmaxf(mx, fmaxf(fabsf(al), fabsf(ar)));
+    }
+    return mx;
+}
+// p over frames [m0, m0 + cnt) (m0 >= 0; p = 0 from `frames` on): into lds[m - m0] when lds is set; returns their max.
+template <uint32_t K>
+TD_DEV float mst_detect_run(const MasterDesc& d, int64_t m0, int64_t cnt, float* lds) {
+    float red = 0.f;
+    if (cnt <= 0) return red;
+    const int64_t N = d.frames;
+    float2 xw[kLoudTaps];
+#pragma unroll
+    for (uint32_t j = 0; j < kLoudTaps; ++j) xw[j] = mst_frame<K>(d, m0 - 6 + (int64_t)j);   // the window of frame m0 - 1
+    float prev = m0 >= 1 && m0 - 1 < N ? mst_points(d, xw) : 0.f;
+    for (int64_t i = 0; i < cnt; ++i) {
+        const int64_t m = m0 + i;
+#pragma unroll
+        for (uint32_t j = 0; j + 1 < kLoudTaps; ++j) xw[j] = xw[j + 1];
+        xw[kLoudTaps - 1] = mst_frame<K>(d, m + 6);
+        float p = 0.f;
+        if (m < N) {
+            const float cur = mst_points(d, xw);
+            p = fmaxf(fmaxf(fabsf(xw[5].x), fabsf(xw[5].y)), fmaxf(cur, prev));
+            prev = cur;
+        }
+        if (lds) lds[i] = p;
+        red = fmaxf(red, p);
+    }
+    return red;
+}
+// Frames [m0, m0 + L) split into contiguous runs, one per lane: p into lds[0 .. L) (or only the max, lds null).
+template <uint32_t K>
+TD_DEV float mst_detect_range(const MasterDesc& d, int64_t m0, int64_t L, float* lds) {
+    const int64_t per = (L + kThreads - 1) / kThreads, b = (int64_t)threadIdx.x * per;
+    const int64_t cnt = b < L ? (L - b < per ? L - b : per) : 0;
+    return mst_detect_run<K>(d, m0 + b, cnt, lds ? lds + b : nullptr);
+}
+// In-place running max over v[0 .. kMasterTile) in LDS, forward (prefix) or backward (suffix); lanes own kMasterRun elements.
+TD_DEV void mst_scan_max(float* v, float* lane, bool backward) {
+    const uint32_t tid = threadIdx.x;
+    const uint32_t lo = (backward ? kThreads - 1u - tid : tid) * kMasterRun;
+    float a = 0.f;
+#pragma unroll
+    for (uint32_t k = 0; k < kMasterRun; ++k) {
+        const uint32_t i = backward ? lo + kMasterRun - 1u - k : lo + k;
+        a = fmaxf(a, v[i]);
+        v[i] = a;
+    }
+    lane[tid] = a;
+    __syncthreads();
+    for (uint32_t off = 1; off < kThreads; off <<= 1) {   // inclusive scan of the lanes' totals, in walking order
+        const float o = tid >= off ? lane[tid - off] : 0.f;
+        __syncthreads();
+        lane[tid] = fmaxf(lane[tid], o);
+        __syncthreads();
+    }
+    const float in = tid ? lane[tid - 1] : 0.f;
+#pragma unroll
+    for (uint32_t k = 0; k < kMasterRun; ++k) v[lo + k] = fmaxf(v[lo + k], in);
+    __syncthreads();
+}
+template <uint32_t K>
+TD_DEV void master_detect_tile(const MasterDesc& d, float* sp, float* lane) {
+    const uint32_t tid = threadIdx.x, W = d.W;
+    const int64_t t0 = (int64_t)blockIdx.x * kMasterTile, N = d.frames;
+    float* qo = d.q;
+    if (W <= kMasterTile + 1u) {
+        // p over [t0, t0 + T + W - 1) in LDS; r_k[i] = max p[i .. i + 2^k - 1] by doubling; q = max(r_K[i], r_K[i + W - 2^K])
+        const uint32_t L = kMasterTile + W - 1u;
+        (void)mst_detect_range<K>(d, t0, L, sp);
+        __syncthreads();
+        uint32_t k2 = 0;
+        while ((2u << k2) <= W) ++k2;
+        for (uint32_t j = 0; j < k2; ++j) {
+            const uint32_t s = 1u << j;
+            float r[2 * kMasterRun];
+#pragma unroll
+            for (uint32_t k = 0; k < 2 * kMasterRun; ++k) {
+                const uint32_t i = tid + k * kThreads;
+                r[k] = i + s < L ? fmaxf(sp[i], sp[i + s]) : (i < L ? sp[i] : 0.f);
+            }
+            __syncthreads();
+#pragma unroll
+            for (uint32_t k = 0; k < 2 * kMasterRun; ++k) {
+                const uint32_t i = tid + k * kThreads;
+                if (i < L) sp[i] = r[k];
+            }
+            __syncthreads();
+        }
+        const uint32_t sh = W - (1u << k2);
+#pragma unroll
+        for (uint32_t k = 0; k < kMasterRun; ++k) {
+            const uint32_t i = tid + k * kThreads;
+            if (t0 + i < N) qo[t0 + i] = fmaxf(sp[i], sp[i + sh]);
+        }
+    } else {
+        // the window [n, n + W - 1] of tile frame n = t0 + i: the tile's suffix from i, everything between the tile and
+        // t0 + W - 1, and the prefix to i of the T frames from t0 + W - 1
+        float* A = sp;
+        float* B = sp + kMasterTile;
+        (void)mst_detect_range<K>(d, t0, kMasterTile, A);
+        (void)mst_detect_range<K>(d, t0 + W - 1, kMasterTile, B);
+        float mid = mst_detect_range<K>(d, t0 + kMasterTile, (int64_t)W - 1 - kMasterTile, nullptr);
+        __syncthreads();
+        mst_scan_max(A, lane, true);
+        mst_scan_max(B, lane, false);
+        lane[tid] = mid;
+        __syncthreads();
+        for (uint32_t off = kThreads / 2; off; off >>= 1) {
+            if (tid < off) lane[tid] = fmaxf(lane[tid], lane[tid + off]);
+            __syncthreads();
+        }
+        mid = lane[0];
+#pragma unroll
+        for (uint32_t k = 0; k < kMasterRun; ++k) {
+            const uint32_t i = tid + k * kThreads;
+            if (t0 + i < N) qo[t0 + i] = fmaxf(fmaxf(A[i], mid), B[i]);
+        }
+    }
+}
+__global__ __launch_bounds__(kThreads) void k_master_detect(const MasterDesc* __restrict__ descs) {
+    const MasterDesc& d = descs[blockIdx.y];
+    if (blockIdx.x >= d.n_tiles) return;
+    __shared__ float sp[2 * kMasterTile];
+    __shared__ float lane[kThreads];
+    if (d.kind == 0u) master_detect_tile<0>(d, sp, lane);
+    else if (d.kind == 1u) master_detect_tile<1>(d, sp, lane);
+    else master_detect_tile<2>(d, sp, lane);
+}
+
+TD_DEV double mst_omh(const MasterDesc& d, float qf) {   // 1 - h for one held detector value
+    const double q = (double)qf;
+    return q > 0.0 ? 1.0 - fmin(1.0, d.cp / (d.g * q)) : 0.0;
+}
+// 1 - h of the lane's kMasterRun frames of the tile at t0 (h = 1 from `frames` on)
+TD_DEV void mst_one_minus_h(const MasterDesc& d, int64_t t0, double (&omh)[kMasterRun]) {
+    const int64_t f0 = t0 + (int64_t)threadIdx.x * kMasterRun;
+    float qv[kMasterRun];
+    if (f0 + (int64_t)kMasterRun <= (int64_t)d.frames) {
+        const float4 a = gload4(d.q + f0), b = gload4(d.q + f0 + 4);
+        qv[0] = a.x; qv[1] = a.y; qv[2] = a.z; qv[3] = a.w; qv[4] = b.x; qv[5] = b.y; qv[6] = b.z; qv[7] = b.w;
+    } else {
+#pragma unroll
+        for (uint32_t k = 0; k < kMasterRun; ++k) qv[k] = f0 + k < (int64_t)d.frames ? d.q[f0 + k] : 0.f;
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < kMasterRun; ++k) omh[k] = mst_omh(d, qv[k]);
+}
+// The release over the tile at t0 entering at u_in: returns the u entering the lane's run; *last (lane 255's end) the tile's end.
+TD_DEV double mst_release(const MasterDesc& d, const double (&omh)[kMasterRun], double u_in, double* sv, double* last) {
+    const uint32_t tid = threadIdx.x;
+    const double a = d.a;
+    double u = tid ? 0.0 : u_in;
+#pragma unroll
+    for (uint32_t k = 0; k < kMasterRun; ++k) u = fmax(omh[k], a * u);
+#pragma unroll 1
+    for (uint32_t k = 0; k < 8; ++k) {   // inclusive scan over the lanes: (m, s) o x = max(m, s x), s = a^(run 2^k)
+        const uint32_t off = 1u << k;
+        sv[tid] = u;
+        __syncthreads();
+        if (tid >= off) u = fmax(u, d.pw[k] * sv[tid - off]);
+        __syncthreads();
+    }
+    sv[tid] = u;
+    __syncthreads();
+    const double in = tid ? sv[tid - 1] : u_in;
+    *last = sv[kThreads - 1];
+    __syncthreads();
+    return in;
+}
+__global__ __launch_bounds__(kThreads) void k_master_scan(const MasterDesc* __restrict__ descs) {
+    const MasterDesc& d = descs[blockIdx.y];
+    if (blockIdx.x >= d.n_tiles) return;
+    __shared__ double sv[kThreads];
+    double omh[kMasterRun], last;
+    mst_one_minus_h(d, (int64_t)blockIdx.x * kMasterTile, omh);
+    (void)mst_release(d, omh, 0.0, sv, &last);
+    if (threadIdx.x == 0) d.agg[blockIdx.x] = last;
+}
+__global__ __launch_bounds__(kThreads) void k_master_carry(const MasterDesc* __restrict__ descs) {
+    const MasterDesc& d = descs[blockIdx.x];
+    __shared__ double sv[kThreads];
+    const uint32_t tid = threadIdx.x, n = d.n_tiles, c = d.chunk;
+    const uint32_t b = tid * c, e = b + c < n ? b + c : n;
+    double u = 0.0;
+    for (uint32_t r = b; r < e; ++r) u = fmax(d.agg[r], d.a_tile * u);
+#pragma unroll 1
+    for (uint32_t k = 0; k < 8; ++k) {
+        const uint32_t off = 1u << k;
+        sv[tid] = u;
+        __syncthreads();
+        if (tid >= off) u = fmax(u, d.pwc[k] * sv[tid - off]);
+        __syncthreads();
+    }
+    sv[tid] = u;
+    __syncthreads();
+    u = tid ? sv[tid - 1] : 0.0;
+    for (uint32_t r = b; r < e; ++r) {
+        d.carry[r] = u;
+        u = fmax(d.agg[r], d.a_tile * u);
+    }
+}
+
+// One frame's word(s) at gain v = g G: saturate(trunc(w v)) on the integer word, (float)(x v) on f32
+TD_DEV int32_t mst_word(int32_t w, double g, double G, const MasterDesc& d) {
+    const double y = trunc((double)w * g * G);
+    return (int32_t)fmin(fmax(y, (double)d.lo), (double)d.hi);
+}
+template <uint32_t K>
+TD_DEV void mst_apply_frames(const MasterDesc& d, int64_t f0, uint32_t cnt, const double (&G)[kMasterRun]) {
+    const double g = d.g;
+    const bool vec = cnt == kMasterRun && ((((uintptr_t)d.src) | ((uintptr_t)d.dst)) & 15u) == 0u;
+    if (K == 0u) {
+        const uint32_t* s = reinterpret_cast<const uint32_t*>(d.src) + f0;
+        uint32_t* o = reinterpret_cast<uint32_t*>(d.dst) + f0;
+        uint32_t w[kMasterRun];
+        if (vec) {
+            const i4v a = *reinterpret_cast<const i4v TD_GLOBAL*>((const TD_GLOBAL char*)s);
+            const i4v b = *reinterpret_cast<const i4v TD_GLOBAL*>((const TD_GLOBAL char*)(s + 4));
+            w[0] = (uint32_t)a.x; w[1] = (uint32_t)a.y; w[2] = (uint32_t)a.z; w[3] = (uint32_t)a.w;
+            w[4] = (uint32_t)b.x; w[5] = (uint32_t)b.y; w[6] = (uint32_t)b.z; w[7] = (uint32_t)b.w;
+        } else {
+            for (uint32_t k = 0; k < cnt; ++k) w[k] = s[k];
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < kMasterRun; ++k) {
+            const int32_t l = mst_word((int16_t)(w[k] & 0xFFFFu), g, G[k], d), r = mst_word((int16_t)(w[k] >> 16), g, G[k], d);
+            w[k] = ((uint32_t)l & 0xFFFFu) | ((uint32_t)r << 16);
+        }
+        if (vec) {
+            const i4v a = {(int)w[0], (int)w[1], (int)w[2], (int)w[3]}, b = {(int)w[4], (int)w[5], (int)w[6], (int)w[7]};
+            *reinterpret_cast<i4v TD_GLOBAL*>((TD_GLOBAL char*)o) = a;
+            *reinterpret_cast<i4v TD_GLOBAL*>((TD_GLOBAL char*)(o + 4)) = b;
+        } else {
+            for (uint32_t k = 0; k < cnt; ++k) o[k] = w[k];
+        }
+    } else if (K == 1u) {
+        const i4v* s = reinterpret_cast<const i4v*>(reinterpret_cast<const int2*>(d.src) + f0);
+        i4v* o = reinterpret_cast<i4v*>(reinterpret_cast<int2*>(d.dst) + f0);
+        if (vec) {
+            i4v w[kMasterRun / 2];
+#pragma unroll
+            for (uint32_t k = 0; k < kMasterRun / 2; ++k) w[k] = *reinterpret_cast<const i4v TD_GLOBAL*>((const TD_GLOBAL char*)(s + k));
+#pragma unroll
+            for (uint32_t k = 0; k < kMasterRun / 2; ++k) {
+                i4v v;
+                v.x = mst_word(w[k].x, g, G[2 * k], d);
+                v.y = mst_word(w[k].y, g, G[2 * k], d);
+                v.z = mst_word(w[k].z, g, G[2 * k + 1], d);
+                v.w = mst_word(w[k].w, g, G[2 * k + 1], d);
+                *reinterpret_cast<i4v TD_GLOBAL*>((TD_GLOBAL char*)(o + k)) = v;
+            }
+        } else {
+            const int2* s2 = reinterpret_cast<const int2*>(d.src) + f0;
+            int2* o2 = reinterpret_cast<int2*>(d.dst) + f0;
+            for (uint32_t k = 0; k < cnt; ++k) {
+                const int2 w = s2[k];
+                o2[k] = make_int2(mst_word(w.x, g, G[k], d), mst_word(w.y, g, G[k], d));
+            }
+        }
+    } else {
+        const float2* s2 = reinterpret_cast<const float2*>(d.src) + f0;
+        float2* o2 = reinterpret_cast<float2*>(d.dst) + f0;
+        if (vec) {
+#pragma unroll
+            for (uint32_t k = 0; k < kMasterRun / 2; ++k) {
+                const float4 x = gload4(s2 + 2 * k);
+                gstore4(o2 + 2 * k, make_float4((float)((double)x.x * g * G[2 * k]), (float)((double)x.y * g * G[2 * k]),
+                                                (float)((double)x.z * g * G[2 * k + 1]), (float)((double)x.w * g * G[2 * k + 1])));
+            }
+        } else {
+            for (uint32_t k = 0; k < cnt; ++k) {
+                const float2 x = s2[k];
+                o2[k] = make_float2((float)((double)x.x * g * G[k]), (float)((double)x.y * g * G[k]));
+            }
+        }
+    }
+}
+template <uint32_t K>
+TD_DEV void master_apply_tile(const MasterDesc& d, double* sv, double* lag, uint32_t* wmin) {
+    const uint32_t tid = threadIdx.x, W = d.W;
+    const int64_t t = blockIdx.x, t0 = t * (int64_t)kMasterTile, N = d.frames, s0 = t0 - (int64_t)W;
+    // PS[j] = sum of e over (s0, j], e = e[0] before frame 0; G[n] = (PS[n] - PS[n - W]) / W.  Rounds over the tiles from the
+    // one holding frame s0 + 1 to this one, each from its carry; PS[j] of j in (s0, t0 + T - W) kept in lag[j - s0].  PS[s0] is
+    // the empty sum, 0: never stored (the tile holding frame s0 is not among the rounds when s0 + 1 starts a tile).
+    const int64_t first = s0 + 1 < 0 ? 0 : (s0 + 1) / kMasterTile;
+    const double e0 = 1.0 - mst_omh(d, d.q[0]);   // (u[0] = max(1 - h[0], a u[-1]) with u[-1] = 0)
+    double running = s0 + 1 < 0 ? (double)(-(s0 + 1)) * e0 : 0.0;
+    double G[kMasterRun];
+    for (int64_t r = first; r <= t; ++r) {
+        const int64_t r0 = r * (int64_t)kMasterTile, f0 = r0 + (int64_t)tid * kMasterRun;
+        double omh[kMasterRun], last;
+        mst_one_minus_h(d, r0, omh);
+        double u = mst_release(d, omh, d.carry[r], sv, &last);
+        double ps[kMasterRun], acc = 0.0;
+#pragma unroll
+        for (uint32_t k = 0; k < kMasterRun; ++k) {
+            u = fmax(omh[k], d.a * u);
+            if (f0 + k > s0) acc += 1.0 - u;
+            ps[k] = acc;
+        }
+        // the lanes' totals: an inclusive scan in lane order, then PS = running + the lanes before + the lane's own
+        double v = acc;
+#pragma unroll 1
+        for (uint32_t off = 1; off < kThreads; off <<= 1) {
+            sv[tid] = v;
+            __syncthreads();
+            if (tid >= off) v = sv[tid - off] + v;
+            __syncthreads();
+        }
+        sv[tid] = v;
+        __syncthreads();
+        const double before = running + (tid ? sv[tid - 1] : 0.0);
+        running = running + sv[kThreads - 1];
+#pragma unroll
+        for (uint32_t k = 0; k < kMasterRun; ++k) {
+            ps[k] = before + ps[k];
+            const int64_t j = f0 + k;
+            if (j > s0 && j >= 0 && j < s0 + (int64_t)kMasterTile) lag[j - s0] = ps[k];
+        }
+        __syncthreads();
+        if (r == t) {
+#pragma unroll
+            for (uint32_t k = 0; k < kMasterRun; ++k) {
+                const int64_t n = f0 + k, i = n - t0;
+                const double back = i == 0 ? 0.0 : n - (int64_t)W < 0 ? (double)i * e0 : lag[i];
+                G[k] = fmax(0.0, (ps[k] - back) / (double)W);
+            }
+        }
+    }
+    const int64_t f0 = t0 + (int64_t)tid * kMasterRun;
+    const uint32_t cnt = f0 >= N ? 0u : (uint32_t)(N - f0 < (int64_t)kMasterRun ? N - f0 : kMasterRun);
+    float gm = __uint_as_float(0x7F800000u);
+    for (uint32_t k = 0; k < cnt; ++k) gm = fminf(gm, (float)G[k]);
+    if (cnt) mst_apply_frames<K>(d, f0, cnt, G);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) gm = fminf(gm, __shfl_xor(gm, off, 64));
+    if ((tid & 63u) == 0u) wmin[tid / 64u] = __float_as_uint(gm);
+    __syncthreads();
+    if (tid == 0u) {
+        uint32_t m = wmin[0];
+        for (uint32_t w = 1; w < kThreads / 64u; ++w) m = min(m, wmin[w]);
+        atomicMin(d.gmin, m);
+    }
+}
+__global__ __launch_bounds__(kThreads) void k_master_apply(const MasterDesc* __restrict__ descs) {
+    const MasterDesc& d = descs[blockIdx.y];
+    if (blockIdx.x >= d.n_tiles) return;
+    __shared__ double sv[kThreads];
+    __shared__ double lag[kMasterTile];
+    __shared__ uint32_t wmin[kThreads / 64];
+    if (d.kind == 0u) master_apply_tile<0>(d, sv, lag, wmin);
+    else if (d.kind == 1u) master_apply_tile<1>(d, sv, lag, wmin);
+    else master_apply_tile<2>(d, sv, lag, wmin);
+}
+
+// ------------------------------------------------------------------------------------------------
 // k_sample_loop: out[m] = sample[(t0 + m) % len]   (extensions.rs:331-341)
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kThreads) void k_sample_loop(const LoopDesc* __restrict__ descs, uint32_t M) {
@@ -4851,6 +5251,21 @@ void launch_stems(const StemDesc* d, int n, uint32_t frames, hipStream_t s) {
 void launch_loudness(const LoudDesc* d, int n, uint32_t max_tiles, hipStream_t s) {
     for (int o = 0; o < n && max_tiles; o += kMaxGridY)
         hipLaunchKernelGGL(k_loudness, dim3(max_tiles, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
+}
+void launch_master_detect(const MasterDesc* d, int n, uint32_t max_tiles, hipStream_t s) {
+    for (int o = 0; o < n && max_tiles; o += kMaxGridY)
+        hipLaunchKernelGGL(k_master_detect, dim3(max_tiles, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
+}
+void launch_master_scan(const MasterDesc* d, int n, uint32_t max_tiles, hipStream_t s) {
+    for (int o = 0; o < n && max_tiles; o += kMaxGridY)
+        hipLaunchKernelGGL(k_master_scan, dim3(max_tiles, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
+}
+void launch_master_carry(const MasterDesc* d, int n, hipStream_t s) {
+    if (n > 0) hipLaunchKernelGGL(k_master_carry, dim3(n), dim3(kThreads), 0, s, d);
+}
+void launch_master_apply(const MasterDesc* d, int n, uint32_t max_tiles, hipStream_t s) {
+    for (int o = 0; o < n && max_tiles; o += kMaxGridY)
+        hipLaunchKernelGGL(k_master_apply, dim3(max_tiles, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
 }
 void launch_sample_loop(const LoopDesc* d, int n, uint32_t frames, hipStream_t s) {
     if (!n || !frames) return;

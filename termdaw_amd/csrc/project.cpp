@@ -19,6 +19,7 @@
 #include "engine.h"
 #include "devmem.h"
 #include "lua_subset.h"
+#include "master.h"
 #include "wav.h"
 #include "midi.h"
 
@@ -143,6 +144,10 @@ struct td_state {
     // td_state_set_stems: vertex names, resolved on the graph at every render (a refresh rebuilds the graph)
     std::vector<std::string> stems;
     bool stems_set = false;
+    // td_state_set_master: the targets every render is mastered to, and the last render's report
+    bool master_on = false, mastered = false;
+    double master_lufs = -14.0, master_dbtp = -1.0;
+    double master_report[TD_MASTER_FIELDS] = {};
 };
 
 namespace {
@@ -569,6 +574,22 @@ int td_state_set_stems(td_state* s, const char* const* names, size_t n) {
     return 1;
 }
 
+int td_state_set_master(td_state* s, int on, double target_lufs, double ceiling_dbtp) {
+    if (on) {
+        const std::string bad = tde::mst::check(target_lufs, ceiling_dbtp, 5.0, 100.0);
+        if (!bad.empty()) return fail(bad);
+        s->master_lufs = target_lufs;
+        s->master_dbtp = ceiling_dbtp;
+    }
+    s->master_on = on != 0;
+    return 1;
+}
+int td_state_master_report(const td_state* s, double* out) {
+    if (!s->mastered) return fail("master: the State's last render was not mastered");
+    if (out) memcpy(out, s->master_report, sizeof s->master_report);
+    return 1;
+}
+
 int td_state_refresh_source(td_state* s, const char* lua_source) { return do_refresh(s, lua_source ? lua_source : ""); }
 
 int td_state_refresh(td_state* s) {
@@ -614,6 +635,7 @@ static std::string stem_path(const std::string& master, const std::string& verte
 }
 
 static int state_render_device(td_state* s) {
+    s->mastered = false;
     if (!s->loaded) return fail("State not loaded!");
     if (!apply_stems(s)) return 0;
     if (!(s->bd == 8 || s->bd == 16 || s->bd == 24 || s->bd == 32))
@@ -636,6 +658,10 @@ static int state_render_device(td_state* s) {
         const size_t n = td_graph_render_all(s->g, s->sb, s->fb, s->cs, (int)s->bd);
         s->g->output_f32 = keep;
         if (!n) return 0;
+    }
+    if (s->master_on) {   // (in place on the graph's words: the read-back below and the file see the mastered words)
+        if (!td_graph_master(s->g, s->master_lufs, s->master_dbtp, 5.0, 100.0, s->master_report)) return 0;
+        s->mastered = true;
     }
     s->out_frames = frames;
     if (!s->host_pcm.resize(frames * 2 * word)) return fail("termdaw_amd: out of page-locked host memory for the PCM read-back");
