@@ -117,6 +117,32 @@ int td_graph_add_adsr(td_graph* g, const char* name, float gain, float angle, fl
                       int use_off, int use_max, int note, const float* adsr, int adsr_len);
 int td_graph_add_bandpass(td_graph* g, const char* name, float gain, float angle, float wet,
                           float cut_off_hz_low, float cut_off_hz_high, int pass);
+/* A compressor vertex -- THIS ENGINE'S OWN: no reference counterpart (the reference reaches dynamics through LV2 plugins,
+ * add_lv2fx, which this engine parses and drops).  A feed-forward, stereo-linked, log-domain compressor with the
+ * decoupled peak detector of Giannoulis, Massberg, Reiss (JAES 2012).  The vertex sums its inputs like every input vertex
+ * (sum_inputs, extensions.rs:310-319), processes, mixes with `wet`, then pan and gain like every vertex (extensions.rs:262-263).
+ *   sr: the graph's rate.  aR = exp(-1 / (release_ms sr / 1000));  aA = exp(-1 / (attack_ms sr / 1000)), aA = 0 for attack_ms = 0;
+ *   T, R, W, M = threshold_db, ratio, knee_db, makeup_db (each f32 parameter widened to f64).  Steps 1-5 in f64 on the f32
+ *   summed input (l[n], r[n]):
+ *   1. level s[n] = max(|l[n]|, |r[n]|).  s[n] zero or not finite: d[n] = 0.
+ *   2. otherwise x = 20 log10(s[n]), o = x - T, and the wanted reduction in dB
+ *        d[n] = 0                                  for 2 o < -W
+ *               (1 - 1/R) (o + W/2)^2 / (2 W)      for 2 |o| <= W  (only when W > 0)
+ *               (1 - 1/R) o                        for 2 o > W
+ *   3. release:  y1[n] = max(d[n], aR y1[n-1])
+ *   4. attack:   yL[n] = aA yL[n-1] + (1 - aA) y1[n]
+ *   5. G[n] = 10^((M - yL[n]) / 20);  p = (float)(l[n] G[n]), the same for r (a NaN / infinite input frame stays what IEEE
+ *      makes of it, at that frame only: step 1 keeps it out of the state)
+ *   6. in f32, the reference's lerp (adsr.rs:42): out = l + wet * (p - l); then pan and gain.  wet < 0.0001: the summed input
+ *      passes through untouched and the state stays as it is.
+ * State: (y1, yL), two doubles, (0, 0) at time 0; carried between consecutive block pulls and between the chunks of a render,
+ * reset to (0, 0) by td_graph_set_time / td_graph_change_time / td_graph_reset (so every whole render starts from (0, 0)).
+ * Ranges, rejected with a td_last_error that names the parameter (NaN included): threshold_db [-80, 0], ratio [1, 1000],
+ * attack_ms [0, 1000], release_ms [1, 10000], knee_db [0, 40], makeup_db [-40, 40].  `wet` is clamped to [0, 1].
+ * Under "band_mode" 2 / "sine_mode" 2 everything upstream of a compressor vertex takes the exact forms (no estimate is carried
+ * through a gain that depends on the signal). */
+int td_graph_add_compressor(td_graph* g, const char* name, float gain, float angle, float wet, float threshold_db,
+                            float ratio, float attack_ms, float release_ms, float knee_db, float makeup_db);
 int td_graph_connect(td_graph* g, const char* a, const char* b);          /* graph.rs:80-96 (+58-78) */
 int td_graph_set_output(td_graph* g, const char* vertex);                 /* graph.rs:141-148 */
 int td_graph_check(const td_graph* g);                                    /* check_graph graph.rs:150-174 */

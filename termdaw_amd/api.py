@@ -65,6 +65,7 @@ SIGNATURES = {
     "td_graph_add_adsr": (_i32, [_vp, _cp, _f32, _f32, _f32, _sz, _i32, _i32, _i32, _fp, _i32]),
     "td_graph_add_sampsyn": (_i32, [_vp, _cp, _f32, _f32, _sz, _fp, _i32, _cp, _sz]),
     "td_graph_add_bandpass": (_i32, [_vp, _cp, _f32, _f32, _f32, _f32, _f32, _i32]),
+    "td_graph_add_compressor": (_i32, [_vp, _cp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32]),
     "td_graph_connect": (_i32, [_vp, _cp, _cp]),
     "td_graph_set_output": (_i32, [_vp, _cp]),
     "td_graph_check": (_i32, [_vp]),
@@ -435,6 +436,11 @@ class Graph:
 
     def add_bandpass(self, name, gain, angle, wet, lo_hz, hi_hz, pass_):
         _check(lib().td_graph_add_bandpass(self.h, name.encode(), gain, angle, wet, lo_hz, hi_hz, int(pass_)))
+
+    def add_compressor(self, name, gain, angle, wet, threshold_db, ratio, attack_ms, release_ms, knee_db, makeup_db):
+        """A feed-forward compressor vertex (this engine's own; the definition is in include/termdaw_amd.h)."""
+        _check(lib().td_graph_add_compressor(self.h, name.encode(), gain, angle, wet, threshold_db, ratio, attack_ms, release_ms,
+                                             knee_db, makeup_db))
 
     def connect(self, a, b):
         return bool(lib().td_graph_connect(self.h, a.encode(), b.encode()))

@@ -21,7 +21,8 @@ namespace tde {
 const char* const kFamilyName[F_COUNT] = {"k_sample_loop", "k_sample_multi", "k_sample_lerp", "k_debug_sine",
                                            "k_synth",       "k_sampsyn", "k_adsr_env", "k_sine_probe", "k_sum",          "k_scale",       "k_norm_fix",
                                            "k_adsr",        "k_band_pass",    "k_band_spec", "k_band_fix", "k_band_fill", "k_band_scan", "k_quantise", "k_band_audit", "k_stems", "k_sources", "k_loudness",
-                                           "k_master_detect", "k_master_scan", "k_master_carry", "k_master_apply"};
+                                           "k_master_detect", "k_master_scan", "k_master_carry", "k_master_apply",
+                                           "k_comp_detect", "k_comp_carry_y1", "k_comp_env", "k_comp_carry_yl", "k_comp_apply"};
 
 
 // ------------------------------------------------------------------------------------------------
@@ -906,6 +907,9 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                 const Vertex& wv = g->vertices[w];
                 long through = down[w].norm;
                 if (through == -2) { nz = -2; break; }
+                // a compressor is no static gain: no estimate is carried through it -- everything upstream takes the exact forms,
+                // as upstream of a stem
+                if (wv.kind == K_COMPRESSOR) { nz = -2; break; }
                 double L = own_gain(wv);
                 if (wv.kind == K_ADSR && !(wv.wet < 0.0001f)) {   // |lerp(1, level x vel, wet)| <= max(1, |level| |vel|)
                     const AdsrConfD& c = wv.conf;
@@ -1427,6 +1431,14 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                         } else {
                             fam_v[F_BAND].push_back(vi);
                         }
+                    }
+                    break;
+                case K_COMPRESSOR:
+                    if (v.wet < 0.0001f) {
+                        fam_v[F_SUM].push_back(vi);   // the summed input passes through, the state stays
+                    } else {
+                        if (M > 0xFFFF0000ull) return fail("compressor: chunk too long");
+                        fam_v[F_COMP_DETECT].push_back(vi);
                     }
                     break;
                 default: break;
@@ -2158,6 +2170,78 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                     }
                     continue;
                 }
+                case F_COMP_DETECT: {   // the five launches of the level's compressor vertices (kernels.h CompDesc)
+                    const uint32_t n_tiles = (uint32_t)((M + kCompTile - 1) / kCompTile), chunk = (n_tiles + kThreads - 1) / kThreads;
+                    std::vector<CompDesc> d;
+                    std::vector<MasterDesc> c1, c2;
+                    for (size_t vi : vs) {
+                        Vertex& v = g->vertices[vi];
+                        CompDesc x{};
+                        x.x = take_buffer(g);
+                        x.dy = reinterpret_cast<double*>(take_buffer(g));   // (an edge buffer holds one double per frame)
+                        if (!x.x || !x.dy) return fail("termdaw_amd: out of device memory for edge buffers");
+                        level_tmp.push_back(x.x);
+                        level_tmp.push_back(reinterpret_cast<float2*>(x.dy));
+                        x.out = g->vbuf[vi];
+                        x.state = &g->dstate[v.state_slot].comp;
+                        x.k = (uint32_t)g->edges[vi].size();
+                        x.term_mode = term_mode[vi];
+                        x.frames = (uint32_t)M;
+                        x.n_tiles = n_tiles;
+                        x.wet = v.wet;
+                        x.thr = (double)v.threshold_db;
+                        x.slope = 1.0 - 1.0 / (double)v.ratio;
+                        x.knee = (double)v.knee_db;
+                        x.makeup = (double)v.makeup_db;
+                        x.aR = exp(-1.0 / ((double)v.release_ms * (double)sr / 1000.0));
+                        x.aA = v.attack_ms > 0.0f ? exp(-1.0 / ((double)v.attack_ms * (double)sr / 1000.0)) : 0.0;
+                        x.oA = 1.0 - x.aA;
+                        x.pg = make_pg(v.gain, v.angle);
+                        MasterDesc y1{}, yl{};
+                        y1.n_tiles = yl.n_tiles = n_tiles;
+                        y1.chunk = yl.chunk = chunk;
+                        yl.op = 1u;
+                        for (int j = 0; j < 8; ++j) {
+                            const double e = (double)(1u << j);
+                            x.pwR[j] = pow(x.aR, (double)kCompRun * e);
+                            x.pwA[j] = pow(x.aA, (double)kCompRun * e);
+                            y1.pwc[j] = pow(x.aR, (double)kCompTile * (double)chunk * e);
+                            yl.pwc[j] = pow(x.aA, (double)kCompTile * (double)chunk * e);
+                        }
+                        y1.a_tile = pow(x.aR, (double)kCompTile);
+                        yl.a_tile = pow(x.aA, (double)kCompTile);
+                        // (a set_time since the vertex last ran: the state restarts from (0, 0) -- consumed here, like a band-pass vertex' first_override)
+                        if (!v.first_pending) {
+                            y1.init = &g->dstate[v.state_slot].comp.y1;
+                            yl.init = &g->dstate[v.state_slot].comp.yL;
+                        }
+                        v.first_pending = false;
+                        d.push_back(x);
+                        c1.push_back(y1);
+                        c2.push_back(yl);
+                    }
+                    off = st.put(d);
+                    const size_t o1 = st.put(c1), o2 = st.put(c2);
+                    for (size_t i = 0; i < vs.size(); ++i) {
+                        const size_t o = off + i * sizeof(CompDesc), tb = (size_t)n_tiles * sizeof(double);
+                        ptr_field(o, offsetof(CompDesc, ins), ins_off[vs[i]]);
+                        const size_t a1 = scratch(tb), k1 = scratch(tb), a2 = scratch(tb), k2 = scratch(tb);
+                        scratch_field(o, offsetof(CompDesc, agg1), a1);
+                        scratch_field(o, offsetof(CompDesc, carry1), k1);
+                        scratch_field(o, offsetof(CompDesc, agg2), a2);
+                        scratch_field(o, offsetof(CompDesc, carry2), k2);
+                        scratch_field(o1 + i * sizeof(MasterDesc), offsetof(MasterDesc, agg), a1);
+                        scratch_field(o1 + i * sizeof(MasterDesc), offsetof(MasterDesc, carry), k1);
+                        scratch_field(o2 + i * sizeof(MasterDesc), offsetof(MasterDesc, agg), a2);
+                        scratch_field(o2 + i * sizeof(MasterDesc), offsetof(MasterDesc, carry), k2);
+                    }
+                    add_launch(F_COMP_DETECT, off, (int)vs.size(), n_tiles, lv);
+                    add_launch(F_COMP_CARRY1, o1, (int)vs.size(), 0u, lv);
+                    add_launch(F_COMP_ENV, off, (int)vs.size(), n_tiles, lv);
+                    add_launch(F_COMP_CARRY2, o2, (int)vs.size(), 0u, lv);
+                    add_launch(F_COMP_APPLY, off, (int)vs.size(), n_tiles, lv);
+                    continue;
+                }
                 default: continue;
             }
             if (fam == F_SUM || fam == F_ADSR) {   // split at term-mode boundaries (vs is sorted by it)
@@ -2336,6 +2420,11 @@ size_t desc_size(int fam) {
         case F_QUANT: return sizeof(QuantDesc);
         case F_AUDIT: return sizeof(AuditHead);
         case F_STEMS: return sizeof(StemDesc);
+        case F_COMP_DETECT:
+        case F_COMP_ENV:
+        case F_COMP_APPLY: return sizeof(CompDesc);
+        case F_COMP_CARRY1:
+        case F_COMP_CARRY2: return sizeof(MasterDesc);
         default: return 0;
     }
 }

@@ -535,6 +535,8 @@ static int pull_state(td_graph* g) {
         g->state_dev_dirty = false;
         for (const auto& v : g->vertices)   // (a set_time not yet carried to the device by a submission)
             if (v.kind == K_BAND_PASS && v.state_slot >= 0 && v.first_pending) g->hstate[(size_t)v.state_slot].band.first = 1u;
+        for (const auto& v : g->vertices)
+            if (v.kind == K_COMPRESSOR && v.state_slot >= 0 && v.first_pending) g->hstate[(size_t)v.state_slot].comp = {0.0, 0.0, {0, 0, 0, 0}};
     }
     return 1;
 }
@@ -884,6 +886,11 @@ static int submit_chunk(Arena& ar, ChunkBuild& cb, hipStream_t stream, ProfCtx& 
                 case F_QUANT: launch_quantise((const QuantDesc*)d, L.n, L.M, s); break;
                 case F_AUDIT: launch_band_audit((const AuditHead*)d, L.n, s); break;
                 case F_STEMS: launch_stems((const StemDesc*)d, L.n, L.M, s); break;   // (prepare_render has checked it exists)
+                case F_COMP_DETECT: launch_comp_detect((const CompDesc*)d, L.n, L.aux, s); break;   // (likewise)
+                case F_COMP_CARRY1:
+                case F_COMP_CARRY2: launch_master_carry((const MasterDesc*)d, L.n, s); break;
+                case F_COMP_ENV: launch_comp_env((const CompDesc*)d, L.n, L.aux, s); break;
+                case F_COMP_APPLY: launch_comp_apply((const CompDesc*)d, L.n, L.aux, s); break;
             }
         }
         li = lj;
@@ -963,6 +970,10 @@ static int prepare_render(td_graph* g, size_t n_blocks, int bits, bool want_pcm,
     if (g->output_vertex < 0) return fail("TermDaw: error: output vertex not found.");
     if (g->plan_dirty) build_plan(g);
     if (!ensure_state_slots(g)) return 0;
+    if (!(launch_comp_detect && launch_comp_env && launch_comp_apply && launch_master_carry))
+        for (size_t vi : g->order)
+            if (g->vertices[vi].kind == K_COMPRESSOR && !(g->vertices[vi].wet < 0.0001f))
+                return fail("termdaw_amd: this build has no k_comp kernels: compressor vertices cannot be rendered");
     const size_t bl = g->bl;
     if (bl == 0) return fail("termdaw_amd: buffer length 0");
     rp->n_blocks = n_blocks;
@@ -1065,7 +1076,7 @@ static bool starts_afresh(const td_graph* g) {
     for (size_t vi : g->order) {
         const Vertex& v = g->vertices[vi];
         if (v.kind == K_NORMALIZE && !v.has_init_override) return false;
-        if (v.kind == K_BAND_PASS && v.state_slot >= 0 && !v.first_pending) return false;
+        if ((v.kind == K_BAND_PASS || v.kind == K_COMPRESSOR) && v.state_slot >= 0 && !v.first_pending) return false;
     }
     return true;
 }
@@ -1243,6 +1254,12 @@ static int graph_set_time_impl(td_graph* g, size_t time) {   // graph.rs:123-128
                     g->hstate[v.state_slot].band.first = 1u;
                     v.first_pending = true;
                     any_band = true;
+                }
+                break;
+            case K_COMPRESSOR:   // the detector restarts from (0, 0): the next submission's carries enter with 0
+                if (v.state_slot >= 0) {
+                    g->hstate[v.state_slot].comp = {0.0, 0.0, {0, 0, 0, 0}};
+                    v.first_pending = true;
                 }
                 break;
             default: break;
@@ -1722,6 +1739,27 @@ int td_graph_add_bandpass(td_graph* g, const char* name, float gain, float angle
     v.pass = pass != 0;
     v.state_slot = slot;
     g->hstate[slot].band = {0.f, 0.f, 0.f, 0.f, 1u, {0, 0, 0}};
+    return 1;
+}
+// This engine's own dynamics vertex (no reference counterpart; the definition is in include/termdaw_amd.h).
+int td_graph_add_compressor(td_graph* g, const char* name, float gain, float angle, float wet, float threshold_db, float ratio,
+                            float attack_ms, float release_ms, float knee_db, float makeup_db) {
+    if (!(threshold_db >= -80.0f && threshold_db <= 0.0f)) return fail("compressor: threshold_db must lie in [-80, 0] dB");
+    if (!(ratio >= 1.0f && ratio <= 1000.0f)) return fail("compressor: ratio must lie in [1, 1000]");
+    if (!(attack_ms >= 0.0f && attack_ms <= 1000.0f)) return fail("compressor: attack_ms must lie in [0, 1000] ms");
+    if (!(release_ms >= 1.0f && release_ms <= 10000.0f)) return fail("compressor: release_ms must lie in [1, 10000] ms");
+    if (!(knee_db >= 0.0f && knee_db <= 40.0f)) return fail("compressor: knee_db must lie in [0, 40] dB");
+    if (!(makeup_db >= -40.0f && makeup_db <= 40.0f)) return fail("compressor: makeup_db must lie in [-40, 40] dB");
+    const int slot = new_slot(g);
+    Vertex& v = add_vertex(g, name, gain, angle, wet, K_COMPRESSOR);
+    v.threshold_db = threshold_db;
+    v.ratio = ratio;
+    v.attack_ms = attack_ms;
+    v.release_ms = release_ms;
+    v.knee_db = knee_db;
+    v.makeup_db = makeup_db;
+    v.state_slot = slot;
+    g->hstate[slot].comp = {0.0, 0.0, {0, 0, 0, 0}};
     return 1;
 }
 

@@ -218,6 +218,41 @@ struct MasterDesc {
     double a_tile;          // a^kMasterTile
     double a;               // the release coefficient
     float fir[4][12];       // the meter's FIR (LoudDesc::fir)
+    // k_master_carry as the carry of ANOTHER scan (a compressor vertex' two recurrences, CompDesc below -- the kernel reads agg,
+    // carry, n_tiles, chunk, a_tile, pwc and these; the mastering passes leave them zero): the value entering tile 0 (device
+    // address; nullptr: 0), and the operator -- 0: u <- max(agg, a_tile u), 1: u <- agg + a_tile u
+    const double* init;
+    uint32_t op, pad_op;
+};
+
+// A compressor vertex (k_comp_detect / k_comp_env / k_comp_apply with k_master_carry in between; the definition is
+// in include/termdaw_amd.h at td_graph_add_compressor).  The chunk is cut into tiles of kCompTile frames, a lane owns kCompRun
+// consecutive frames.  k_comp_detect evaluates the input terms, leaves the summed input in `x` and the wanted reduction d[n]
+// (f64) in `dy`, and each tile's zero-start end value of the release  y1 = max(d, aR y1)  in agg1[]; k_master_carry (op 0)
+// leaves the y1 entering each tile in carry1[]; k_comp_env rebuilds y1 from there, overwrites dy with it, and leaves each
+// tile's zero-start end value of the attack  yL = aA yL + (1 - aA) y1  in agg2[]; k_master_carry (op 1) leaves the yL entering
+// each tile in carry2[]; k_comp_apply rebuilds yL, G = 10^((makeup - yL) / 20) and writes lerp(x, (float)(x G), wet), pan,
+// gain to `out`.  The lane that owns the chunk's last frame stores y1 (k_comp_env) / yL (k_comp_apply) into the carried state.
+constexpr uint32_t kCompRun = 8;                     // frames per lane
+constexpr uint32_t kCompTile = kCompRun * kThreads;  // frames per workgroup
+struct CompState { double y1, yL; uint32_t pad[4]; };
+struct CompDesc {
+    const InTerm* ins;      // k input terms (kinds 0 .. 4), in connect() order
+    float2* x;              // [frames] the summed input
+    double* dy;             // [frames] d, then y1
+    float2* out;
+    CompState* state;       // carried across chunks / block pulls
+    double* agg1;           // [n_tiles] each of the four
+    double* carry1;
+    double* agg2;
+    double* carry2;
+    uint32_t k, term_mode, frames, n_tiles;
+    float wet;
+    uint32_t pad;
+    double thr, slope, knee, makeup;   // T, 1 - 1 / R, W, M (dB)
+    double aR, aA, oA;      // release / attack coefficients, 1 - aA
+    double pwR[8], pwA[8];  // aR^(kCompRun 2^k), aA^(kCompRun 2^k)
+    PanGain pg;
 };
 
 // sample_loop_gen (extensions.rs:331-341): out[m] = sample[(t0 + m) % len]
@@ -652,6 +687,11 @@ __attribute__((weak)) void launch_master_detect(const MasterDesc* d, int n_desc,
 __attribute__((weak)) void launch_master_scan(const MasterDesc* d, int n_desc, uint32_t max_tiles, hipStream_t s);
 __attribute__((weak)) void launch_master_carry(const MasterDesc* d, int n_desc, hipStream_t s);
 __attribute__((weak)) void launch_master_apply(const MasterDesc* d, int n_desc, uint32_t max_tiles, hipStream_t s);
+// Weak for the same reason: a level's compressor vertices, ONE grid per step (grid.x: the largest tile count); the two carries
+// between the steps are launch_master_carry's.
+__attribute__((weak)) void launch_comp_detect(const CompDesc* d, int n_desc, uint32_t max_tiles, hipStream_t s);
+__attribute__((weak)) void launch_comp_env(const CompDesc* d, int n_desc, uint32_t max_tiles, hipStream_t s);
+__attribute__((weak)) void launch_comp_apply(const CompDesc* d, int n_desc, uint32_t max_tiles, hipStream_t s);
 void launch_sinf(const float* in, float* out, uint32_t n, int exact, hipStream_t s);   // out[i] = sin_glibc(in[i]) (exact) or sin_any(in[i])
 void launch_debug_verify(const uint32_t* p, uint32_t n_words, const uint32_t* seg_sums, uint32_t* report, hipStream_t s);   // (TD_DEBUG_SYNC & 16)
 void launch_sample_loop(const LoopDesc* d, int n_desc, uint32_t frames, hipStream_t s);

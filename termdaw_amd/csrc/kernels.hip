@@ -1605,27 +1605,33 @@ __global__ __launch_bounds__(kThreads) void k_master_scan(const MasterDesc* __re
     (void)mst_release(d, omh, 0.0, sv, &last);
     if (threadIdx.x == 0) d.agg[blockIdx.x] = last;
 }
+// (Also the carry of a compressor vertex' two scans -- MasterDesc::init / op: the value entering tile 0, and `+` in place of `max`.)
 __global__ __launch_bounds__(kThreads) void k_master_carry(const MasterDesc* __restrict__ descs) {
     const MasterDesc& d = descs[blockIdx.x];
     __shared__ double sv[kThreads];
     const uint32_t tid = threadIdx.x, n = d.n_tiles, c = d.chunk;
     const uint32_t b = tid * c, e = b + c < n ? b + c : n;
-    double u = 0.0;
-    for (uint32_t r = b; r < e; ++r) u = fmax(d.agg[r], d.a_tile * u);
+    const bool add = d.op != 0u;
+    const double init = d.init ? *d.init : 0.0;
+    double u = tid ? 0.0 : init;
+    for (uint32_t r = b; r < e; ++r) u = add ? d.agg[r] + d.a_tile * u : fmax(d.agg[r], d.a_tile * u);
 #pragma unroll 1
     for (uint32_t k = 0; k < 8; ++k) {
         const uint32_t off = 1u << k;
         sv[tid] = u;
         __syncthreads();
-        if (tid >= off) u = fmax(u, d.pwc[k] * sv[tid - off]);
+        if (tid >= off) {
+            const double o = d.pwc[k] * sv[tid - off];
+            u = add ? u + o : fmax(u, o);
+        }
         __syncthreads();
     }
     sv[tid] = u;
     __syncthreads();
-    u = tid ? sv[tid - 1] : 0.0;
+    u = tid ? sv[tid - 1] : init;
     for (uint32_t r = b; r < e; ++r) {
         d.carry[r] = u;
-        u = fmax(d.agg[r], d.a_tile * u);
+        u = add ? d.agg[r] + d.a_tile * u : fmax(d.agg[r], d.a_tile * u);
     }
 }
 
@@ -1780,6 +1786,148 @@ __global__ __launch_bounds__(kThreads) void k_master_apply(const MasterDesc* __r
     if (d.kind == 0u) master_apply_tile<0>(d, sv, lag, wmin);
     else if (d.kind == 1u) master_apply_tile<1>(d, sv, lag, wmin);
     else master_apply_tile<2>(d, sv, lag, wmin);
+}
+
+// ------------------------------------------------------------------------------------------------
+// k_comp_detect / k_comp_env / k_comp_apply: the compressor vertex (kernels.h CompDesc).  No reference
+// counterpart; the definition is the header's (td_graph_add_compressor), f64 from the level to the gain.
+// ------------------------------------------------------------------------------------------------
+typedef double d2v __attribute__((ext_vector_type(2)));
+TD_DEV d2v gload_d2(const double* p) { return *reinterpret_cast<const d2v TD_GLOBAL*>((const TD_GLOBAL char*)p); }
+TD_DEV void gstore_d2(double* p, double a, double b) { d2v w; w.x = a; w.y = b; *reinterpret_cast<d2v TD_GLOBAL*>((TD_GLOBAL char*)p) = w; }
+// steps 1 and 2: the wanted reduction in dB of one summed input frame
+TD_DEV double comp_want(const CompDesc& d, float l, float r) {
+    const float al = fabsf(l), ar = fabsf(r);
+    if (!(al <= 3.402823466e38f && ar <= 3.402823466e38f)) return 0.0;   // a NaN / infinite frame stays out of the state
+    const float s = fmaxf(al, ar);
+    if (s == 0.0f) return 0.0;
+    const double o = 20.0 * log10((double)s) - d.thr, W = d.knee;
+    if (2.0 * o < -W) return 0.0;
+    if (W > 0.0 && 2.0 * fabs(o) <= W) {
+        const double t = o + W / 2.0;
+        return d.slope * (t * t) / (2.0 * W);
+    }
+    if (2.0 * o > W) return d.slope * o;
+    return 0.0;
+}
+// The lanes' run-end values u (lane 0's run started from u_in) joined in lane order: Hillis-Steele with the host's powers
+// pw[k] = a^(kCompRun 2^k), operator max (the release) or + (the attack's affine recurrence: every lane's factor is the same
+// a^kCompRun).  Returns the value entering the lane's run; *last: the tile's end value.
+template <bool ADD>
+TD_DEV double comp_lane_scan(double u, const double (&pw)[8], double u_in, double* sv, double* last) {
+    const uint32_t tid = threadIdx.x;
+#pragma unroll 1
+    for (uint32_t k = 0; k < 8; ++k) {
+        const uint32_t off = 1u << k;
+        sv[tid] = u;
+        __syncthreads();
+        if (tid >= off) {
+            const double o = pw[k] * sv[tid - off];
+            u = ADD ? u + o : fmax(u, o);
+        }
+        __syncthreads();
+    }
+    sv[tid] = u;
+    __syncthreads();
+    const double in = tid ? sv[tid - 1] : u_in;
+    *last = sv[kThreads - 1];
+    __syncthreads();
+    return in;
+}
+// the lane's kCompRun values of dy (0 from `frames` on)
+TD_DEV void comp_load_run(const CompDesc& d, uint32_t f0, double (&y)[kCompRun]) {
+#pragma unroll
+    for (uint32_t j = 0; j < kCompRun / 2; ++j) {
+        const uint32_t m = f0 + 2u * j;
+        d2v v;
+        v.x = 0.0; v.y = 0.0;
+        if (m < d.frames) v = gload_d2(d.dy + m);
+        y[2 * j] = v.x;
+        y[2 * j + 1] = m + 1u < d.frames ? v.y : 0.0;
+    }
+}
+__global__ __launch_bounds__(kThreads) void k_comp_detect(const CompDesc* __restrict__ descs) {
+    const CompDesc& d = descs[blockIdx.y];
+    if (blockIdx.x >= d.n_tiles) return;
+    __shared__ double sv[kThreads];
+    const uint32_t M = d.frames, f0 = blockIdx.x * kCompTile + threadIdx.x * kCompRun;
+    const double aR = d.aR;
+    double u = 0.0;
+#pragma unroll 1
+    for (uint32_t h = 0; h < kCompRun / 4; ++h) {   // (frames beyond M sum to 0: d = 0)
+        const uint32_t m = f0 + 4u * h;
+        float4 a0, a1;
+        sum_inputs_pairs(d.ins, d.k, d.term_mode, m, m + 2u, M, a0, a1);
+        store_pair(d.x, m, M, a0);
+        store_pair(d.x, m + 2u, M, a1);
+        const double d0 = comp_want(d, a0.x, a0.y), d1 = comp_want(d, a0.z, a0.w);
+        const double d2 = comp_want(d, a1.x, a1.y), d3 = comp_want(d, a1.z, a1.w);
+        if (m < M) gstore_d2(d.dy + m, d0, d1);
+        if (m + 2u < M) gstore_d2(d.dy + m + 2u, d2, d3);
+        u = fmax(d0, aR * u);
+        u = fmax(d1, aR * u);
+        u = fmax(d2, aR * u);
+        u = fmax(d3, aR * u);
+    }
+    double last;
+    (void)comp_lane_scan<false>(u, d.pwR, 0.0, sv, &last);
+    if (threadIdx.x == 0) d.agg1[blockIdx.x] = last;
+}
+__global__ __launch_bounds__(kThreads) void k_comp_env(const CompDesc* __restrict__ descs) {
+    const CompDesc& d = descs[blockIdx.y];
+    if (blockIdx.x >= d.n_tiles) return;
+    __shared__ double sv[kThreads];
+    const uint32_t tid = threadIdx.x, M = d.frames, f0 = blockIdx.x * kCompTile + tid * kCompRun;
+    const double aR = d.aR, aA = d.aA, oA = d.oA, cin = d.carry1[blockIdx.x];
+    double y[kCompRun], last;
+    comp_load_run(d, f0, y);
+    double u = tid ? 0.0 : cin;
+#pragma unroll
+    for (uint32_t k = 0; k < kCompRun; ++k) u = fmax(y[k], aR * u);
+    u = comp_lane_scan<false>(u, d.pwR, cin, sv, &last);
+    double b = 0.0;
+#pragma unroll
+    for (uint32_t k = 0; k < kCompRun; ++k) {
+        u = fmax(y[k], aR * u);
+        y[k] = u;
+        b = aA * b + oA * u;
+        if (f0 + k + 1u == M) d.state->y1 = u;   // the chunk's last frame: what the next chunk / block pull enters with
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < kCompRun / 2; ++j)
+        if (f0 + 2u * j < M) gstore_d2(d.dy + f0 + 2u * j, y[2 * j], y[2 * j + 1]);
+    (void)comp_lane_scan<true>(b, d.pwA, 0.0, sv, &last);
+    if (tid == 0) d.agg2[blockIdx.x] = last;
+}
+__global__ __launch_bounds__(kThreads) void k_comp_apply(const CompDesc* __restrict__ descs) {
+    const CompDesc& d = descs[blockIdx.y];
+    if (blockIdx.x >= d.n_tiles) return;
+    __shared__ double sv[kThreads];
+    const uint32_t tid = threadIdx.x, M = d.frames, f0 = blockIdx.x * kCompTile + tid * kCompRun;
+    const double aA = d.aA, oA = d.oA, mk = d.makeup, cin = d.carry2[blockIdx.x];
+    const float wet = d.wet;
+    double y[kCompRun], last;
+    comp_load_run(d, f0, y);
+    double b = tid ? 0.0 : cin;
+#pragma unroll
+    for (uint32_t k = 0; k < kCompRun; ++k) b = aA * b + oA * y[k];
+    double yl = comp_lane_scan<true>(b, d.pwA, cin, sv, &last);
+#pragma unroll
+    for (uint32_t j = 0; j < kCompRun / 2; ++j) {
+        const uint32_t m = f0 + 2u * j;
+        if (m >= M) break;
+        const float4 x = load_pair(d.x, m, M);
+        yl = aA * yl + oA * y[2 * j];
+        const double g0 = exp10((mk - yl) / 20.0);
+        if (m + 1u == M) d.state->yL = yl;
+        yl = aA * yl + oA * y[2 * j + 1];
+        const double g1 = exp10((mk - yl) / 20.0);
+        if (m + 2u == M) d.state->yL = yl;
+        const float4 p = make_float4((float)((double)x.x * g0), (float)((double)x.y * g0), (float)((double)x.z * g1), (float)((double)x.w * g1));
+        // the reference's lerp (adsr.rs:42), f32
+        const float4 o = make_float4(x.x + wet * (p.x - x.x), x.y + wet * (p.y - x.y), x.z + wet * (p.z - x.z), x.w + wet * (p.w - x.w));
+        store_pair(d.out, m, M, epilogue4(o, d.pg));
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -5266,6 +5414,18 @@ void launch_master_carry(const MasterDesc* d, int n, hipStream_t s) {
 void launch_master_apply(const MasterDesc* d, int n, uint32_t max_tiles, hipStream_t s) {
     for (int o = 0; o < n && max_tiles; o += kMaxGridY)
         hipLaunchKernelGGL(k_master_apply, dim3(max_tiles, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
+}
+void launch_comp_detect(const CompDesc* d, int n, uint32_t max_tiles, hipStream_t s) {
+    for (int o = 0; o < n && max_tiles; o += kMaxGridY)
+        hipLaunchKernelGGL(k_comp_detect, dim3(max_tiles, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
+}
+void launch_comp_env(const CompDesc* d, int n, uint32_t max_tiles, hipStream_t s) {
+    for (int o = 0; o < n && max_tiles; o += kMaxGridY)
+        hipLaunchKernelGGL(k_comp_env, dim3(max_tiles, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
+}
+void launch_comp_apply(const CompDesc* d, int n, uint32_t max_tiles, hipStream_t s) {
+    for (int o = 0; o < n && max_tiles; o += kMaxGridY)
+        hipLaunchKernelGGL(k_comp_apply, dim3(max_tiles, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
 }
 void launch_sample_loop(const LoopDesc* d, int n, uint32_t frames, hipStream_t s) {
     if (!n || !frames) return;

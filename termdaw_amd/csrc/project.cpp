@@ -103,6 +103,7 @@ struct SampsynCall { std::string name; float gain, angle; std::string floww; std
 struct Lv2fxCall { std::string name; float gain, angle, wet; std::string plugin; };
 struct AdsrCall { std::string name; float gain, angle, wet; std::string floww; bool use_off, use_max; int note; std::vector<float> conf; };
 struct BandCall { std::string name; float gain, angle, wet, lo, hi; bool pass; };
+struct CompCall { std::string name; float gain, angle, wet, threshold_db, ratio, attack_ms, release_ms, knee_db, makeup_db; };
 
 using Triple = std::tuple<std::string, std::string, std::string>;
 
@@ -218,6 +219,7 @@ int do_refresh(td_state* s, const std::string& contents) {
     std::vector<Lv2fxCall> lv2fxs;
     std::vector<AdsrCall> adsrs;
     std::vector<BandCall> bandpasses;
+    std::vector<CompCall> compressors;
     size_t cs = s->cs, render_sr = s->render_sr, bd = s->bd;
     // std::mem::take (state.rs:79-80): the locals start from the previous values, the State's own fields are left
     // EMPTY until the script has run (state.rs:169-170) -- so they stay empty when the script fails
@@ -362,6 +364,15 @@ int do_refresh(td_state* s, const std::string& contents) {
         dump += std::string(f) + "(\"" + c.name + "\"," + fnum(c.gain) + "," + fnum(c.angle) + "," + fnum(c.wet) + "," + fnum(c.lo) + "," + fnum(c.hi) + "," + (c.pass ? "true" : "false") + ")\n";
         return Value::nil();
     });
+    lua.set_function("add_compressor", [&](const std::vector<Value>& a) {   // this engine's own vertex (termdaw_amd.h td_graph_add_compressor)
+        const char* f = "add_compressor";
+        compressors.push_back({to_str(f, a, 0), to_f32(f, a, 1), to_f32(f, a, 2), to_f32(f, a, 3), to_f32(f, a, 4), to_f32(f, a, 5), to_f32(f, a, 6),
+                               to_f32(f, a, 7), to_f32(f, a, 8), to_f32(f, a, 9)});
+        auto& c = compressors.back();
+        dump += std::string(f) + "(\"" + c.name + "\"," + fnum(c.gain) + "," + fnum(c.angle) + "," + fnum(c.wet) + "," + fnum(c.threshold_db) + "," + fnum(c.ratio) + "," +
+                fnum(c.attack_ms) + "," + fnum(c.release_ms) + "," + fnum(c.knee_db) + "," + fnum(c.makeup_db) + ")\n";
+        return Value::nil();
+    });
     lua.set_function("connect", [&](const std::vector<Value>& a) {
         edges.push_back({to_str("connect", a, 0), to_str("connect", a, 1)});
         dump += "connect(\"" + edges.back().first + "\",\"" + edges.back().second + "\")\n";
@@ -475,6 +486,9 @@ int do_refresh(td_state* s, const std::string& contents) {
             return 0;
     }
     for (auto& c : bandpasses) td_graph_add_bandpass(s->g, c.name.c_str(), c.gain, c.angle, c.wet, c.lo, c.hi, c.pass);
+    for (auto& c : compressors)
+        if (!td_graph_add_compressor(s->g, c.name.c_str(), c.gain, c.angle, c.wet, c.threshold_db, c.ratio, c.attack_ms, c.release_ms, c.knee_db, c.makeup_db))
+            return 0;
     for (auto& e : edges) td_graph_connect(s->g, e.first.c_str(), e.second.c_str());   // failures only warn (state.rs:459)
     td_graph_set_output(s->g, s->output_vertex.c_str());
     if (!td_graph_check(s->g)) return fail("TermDaw: graph check failed! (" + g_error + ")");

@@ -169,7 +169,7 @@ class ProjectScript:
         self.calls = {k: [] for k in (
             "load_sample", "load_resource", "load_midi_floww", "add_sum", "add_normalize", "add_sampleloop",
             "add_sample_multi", "add_sample_lerp", "add_debug_sine", "add_synth", "add_sampsyn", "add_adsr",
-            "add_bandpass", "connect")}
+            "add_bandpass", "add_compressor", "connect")}
         self.resources = {}                 # path -> bytes (load_resource)
         self.script_order = []              # (fn, args) in call order, for to_lua()
 
@@ -240,6 +240,10 @@ class ProjectScript:
     def add_bandpass(self, name, gain, angle, wet, lo_hz, hi_hz, pass_):
         self._rec("add_bandpass", name, gain, angle, wet, lo_hz, hi_hz, pass_)
 
+    def add_compressor(self, name, gain, angle, wet, threshold_db, ratio, attack_ms, release_ms, knee_db, makeup_db):
+        """This engine's own vertex (include/termdaw_amd.h td_graph_add_compressor): no reference counterpart."""
+        self._rec("add_compressor", name, gain, angle, wet, threshold_db, ratio, attack_ms, release_ms, knee_db, makeup_db)
+
     def connect(self, a, b):
         self._rec("connect", a, b)
 
@@ -295,6 +299,8 @@ class ProjectScript:
             g.add_adsr(name, gain, angle, wet, fidx(f, name), uo, um, note, conf)
         for name, gain, angle, wet, lo, hi, p in self.calls["add_bandpass"]:
             g.add_bandpass(name, gain, angle, wet, lo, hi, p)
+        for args in self.calls["add_compressor"]:
+            g.add_compressor(*args)
         for a, b in self.calls["connect"]:
             g.connect(a, b)
         g.set_output(self.output_vertex)
