@@ -143,6 +143,41 @@ int td_graph_add_bandpass(td_graph* g, const char* name, float gain, float angle
  * through a gain that depends on the signal). */
 int td_graph_add_compressor(td_graph* g, const char* name, float gain, float angle, float wet, float threshold_db,
                             float ratio, float attack_ms, float release_ms, float knee_db, float makeup_db);
+/* A parametric EQ vertex -- THIS ENGINE'S OWN: no reference counterpart (the reference reaches an equaliser only through LV2
+ * plugins, add_lv2fx, which this engine parses and drops).  One biquad of Robert Bristow-Johnson's "Audio EQ
+ * Cookbook" per channel.  The vertex sums its inputs like every input vertex (sum_inputs, extensions.rs:310-319), filters l and
+ * r independently, mixes with `wet`, then pan and gain like every vertex (extensions.rs:262-263).
+ *   Coefficients, once on the host in f64 from the f32 parameters widened; sr: the graph's rate.
+ *     w0 = 2 pi freq_hz / sr,  alpha = sin w0 / (2 q),  A = 10^(gain_db / 40)   (1 - cos w0 is evaluated as 2 sin^2(w0 / 2))
+ *     TD_EQ_LOWPASS    b = ((1 - cos w0) / 2, 1 - cos w0, (1 - cos w0) / 2),    a = (1 + alpha, -2 cos w0, 1 - alpha)
+ *     TD_EQ_HIGHPASS   b = ((1 + cos w0) / 2, -(1 + cos w0), (1 + cos w0) / 2), the same a
+ *     TD_EQ_BANDPASS   b = (alpha, 0, -alpha)  (constant 0 dB peak gain),       the same a
+ *     TD_EQ_NOTCH      b = (1, -2 cos w0, 1),                                   the same a
+ *     TD_EQ_PEAK       b = (1 + alpha A, -2 cos w0, 1 - alpha A),               a = (1 + alpha / A, -2 cos w0, 1 - alpha / A)
+ *     TD_EQ_LOWSHELF   with S = 2 sqrt(A) alpha (the cookbook's shelves in their Q form):
+ *                      b = (A ((A+1) - (A-1) cos w0 + S), 2 A ((A-1) - (A+1) cos w0), A ((A+1) - (A-1) cos w0 - S)),
+ *                      a = ((A+1) + (A-1) cos w0 + S, -2 ((A-1) + (A+1) cos w0), (A+1) + (A-1) cos w0 - S)
+ *     TD_EQ_HIGHSHELF  b = (A ((A+1) + (A-1) cos w0 + S), -2 A ((A-1) + (A+1) cos w0), A ((A+1) + (A-1) cos w0 - S)),
+ *                      a = ((A+1) - (A-1) cos w0 + S, 2 ((A-1) - (A+1) cos w0), (A+1) - (A-1) cos w0 - S)
+ *     each divided by a0: (b0, b1, b2, a1, a2).  td_eq_coefficients returns exactly the values the engine uses.
+ *   Recurrence, per channel, in f64, transposed direct form II, on the f32 summed input x[n]:
+ *     y[n] = b0 x[n] + s1;   s1 = (b1 x[n] - a1 y[n]) + s2;   s2 = b2 x[n] - a2 y[n];   p[n] = (float)y[n]
+ *     A non-finite x[n] enters the recurrence as 0 and its frame's p[n] is x[n] itself: the state never holds a NaN.
+ *   Then in f32, the reference's lerp (adsr.rs:42): out = x + wet * (p - x); then pan and gain.  wet < 0.0001: the summed input
+ *   passes through untouched and the state stays as it is.
+ * State: (s1l, s2l, s1r, s2r), four doubles, zero at time 0; carried between consecutive block pulls and between the chunks of
+ * a render, reset to zero by td_graph_set_time / td_graph_change_time / td_graph_reset (so every whole render starts from zero).
+ * Ranges, rejected with a td_last_error that names the parameter (NaN included): kind 0 .. 6, freq_hz [10, 0.45 sr], q [0.1, 20],
+ * gain_db [-24, 24] (ignored by the four kinds without gain).  `wet` is clamped to [0, 1].
+ * Under "band_mode" 2 / "sine_mode" 2 the estimate is carried through an EQ vertex at the gain (1 - wet) + wet Hmax, Hmax the
+ * largest |H(e^jw)| of the biquad: vertices upstream keep their scan / fast forms. */
+enum { TD_EQ_LOWPASS = 0, TD_EQ_HIGHPASS = 1, TD_EQ_BANDPASS = 2, TD_EQ_NOTCH = 3, TD_EQ_PEAK = 4, TD_EQ_LOWSHELF = 5, TD_EQ_HIGHSHELF = 6 };
+int td_graph_add_eq(td_graph* g, const char* name, float gain, float angle, float wet, int kind, float freq_hz, float q,
+                    float gain_db);
+/* Host only, no GPU: the EQ vertex' coefficients at rate sr -- out[0 .. 4] = b0 b1 b2 a1 a2 (a0 = 1) as the engine uses them,
+ * out[5] = Hmax, the maximum over w of |H(e^jw)|, in closed form (|H|^2 is a ratio of two quadratics in sin^2(w / 2): the
+ * maximum lies at w = 0, w = pi or a root of a quadratic).  The same range checks as td_graph_add_eq. */
+int td_eq_coefficients(int kind, size_t sr, float freq_hz, float q, float gain_db, double out[6]);
 int td_graph_connect(td_graph* g, const char* a, const char* b);          /* graph.rs:80-96 (+58-78) */
 int td_graph_set_output(td_graph* g, const char* vertex);                 /* graph.rs:141-148 */
 int td_graph_check(const td_graph* g);                                    /* check_graph graph.rs:150-174 */

@@ -66,6 +66,8 @@ SIGNATURES = {
     "td_graph_add_sampsyn": (_i32, [_vp, _cp, _f32, _f32, _sz, _fp, _i32, _cp, _sz]),
     "td_graph_add_bandpass": (_i32, [_vp, _cp, _f32, _f32, _f32, _f32, _f32, _i32]),
     "td_graph_add_compressor": (_i32, [_vp, _cp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32]),
+    "td_graph_add_eq": (_i32, [_vp, _cp, _f32, _f32, _f32, _i32, _f32, _f32, _f32]),
+    "td_eq_coefficients": (_i32, [_i32, _sz, _f32, _f32, _f32, C.POINTER(C.c_double)]),
     "td_graph_connect": (_i32, [_vp, _cp, _cp]),
     "td_graph_set_output": (_i32, [_vp, _cp]),
     "td_graph_check": (_i32, [_vp]),
@@ -256,6 +258,27 @@ def loudness_f32(frames, sr):
     return _loudness_dicts(out, 1)[0]
 
 
+EQ_KINDS = ("lowpass", "highpass", "bandpass", "notch", "peak", "lowshelf", "highshelf")   # TD_EQ_* 0 .. 6, the Lua line's names
+
+
+def eq_kind(kind):
+    """A kind name of EQ_KINDS (or an index) as the TD_EQ_* integer."""
+    if isinstance(kind, str):
+        if kind not in EQ_KINDS:
+            raise ValueError("eq: unknown kind %r (one of %s)" % (kind, ", ".join(EQ_KINDS)))
+        return EQ_KINDS.index(kind)
+    return int(kind)
+
+
+def eq_coefficients(kind, sr, freq_hz, q, gain_db):
+    """The EQ vertex' filter at rate sr (host only): (b, a) as float64 arrays with a[0] = 1, exactly as the engine uses them,
+    and Hmax, the largest |H(e^jw)|."""
+    out = (C.c_double * 6)()
+    _check(lib().td_eq_coefficients(eq_kind(kind), int(sr), freq_hz, q, gain_db, out))
+    k = np.array(out[:], np.float64)
+    return k[0:3].copy(), np.array([1.0, k[3], k[4]]), float(k[5])
+
+
 def loudness_filters(sr):
     """The meter's filters at rate sr (host only): (shelf (b, a), high-pass (b, a)) as float64 arrays with a[0] = 1, and the
     true-peak FIR as a (phases, taps) float32 array (phase 0 the unit impulse)."""
@@ -441,6 +464,11 @@ class Graph:
         """A feed-forward compressor vertex (this engine's own; the definition is in include/termdaw_amd.h)."""
         _check(lib().td_graph_add_compressor(self.h, name.encode(), gain, angle, wet, threshold_db, ratio, attack_ms, release_ms,
                                              knee_db, makeup_db))
+
+    def add_eq(self, name, gain, angle, wet, kind, freq_hz, q, gain_db):
+        """A parametric EQ vertex (this engine's own; the definition is in include/termdaw_amd.h).  kind: a name of EQ_KINDS or
+        its TD_EQ_* index."""
+        _check(lib().td_graph_add_eq(self.h, name.encode(), gain, angle, wet, eq_kind(kind), freq_hz, q, gain_db))
 
     def connect(self, a, b):
         return bool(lib().td_graph_connect(self.h, a.encode(), b.encode()))

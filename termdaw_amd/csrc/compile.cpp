@@ -5,6 +5,7 @@
 // writes goes into the plain-memory staging arena of the ChunkBuild (offsets + fix-up lists that submit_chunk patches once
 // the device addresses are known).  tests/test_compile_asan.py builds it with g++ -fsanitize=address,undefined.
 #include "compile.h"
+#include "eq_math.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -22,7 +23,8 @@ const char* const kFamilyName[F_COUNT] = {"k_sample_loop", "k_sample_multi", "k_
                                            "k_synth",       "k_sampsyn", "k_adsr_env", "k_sine_probe", "k_sum",          "k_scale",       "k_norm_fix",
                                            "k_adsr",        "k_band_pass",    "k_band_spec", "k_band_fix", "k_band_fill", "k_band_scan", "k_quantise", "k_band_audit", "k_stems", "k_sources", "k_loudness",
                                            "k_master_detect", "k_master_scan", "k_master_carry", "k_master_apply",
-                                           "k_comp_detect", "k_comp_carry_y1", "k_comp_env", "k_comp_carry_yl", "k_comp_apply"};
+                                           "k_comp_detect", "k_comp_carry_y1", "k_comp_env", "k_comp_carry_yl", "k_comp_apply",
+                                           "k_eq_local", "k_eq_carry", "k_eq_apply"};
 
 
 // ------------------------------------------------------------------------------------------------
@@ -911,6 +913,13 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                 // as upstream of a stem
                 if (wv.kind == K_COMPRESSOR) { nz = -2; break; }
                 double L = own_gain(wv);
+                // an EQ is linear and time-invariant: the estimate goes through it at the L2 gain of its lerp, (1 - wet) + wet Hmax
+                // 
+                if (wv.kind == K_EQ && !(wv.wet < 0.0001f)) {
+                    double c[5];
+                    eq::coefficients(wv.eq_kind, sr, wv.eq_freq, wv.eq_q, wv.eq_gain_db, c);
+                    L *= (1.0 - (double)wv.wet) + (double)wv.wet * eq::hmax(c);
+                }
                 if (wv.kind == K_ADSR && !(wv.wet < 0.0001f)) {   // |lerp(1, level x vel, wet)| <= max(1, |level| |vel|)
                     const AdsrConfD& c = wv.conf;
                     double lv = std::max(std::max(fabs((double)c.std_vel), fabs((double)c.attack_vel)),
@@ -1439,6 +1448,14 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                     } else {
                         if (M > 0xFFFF0000ull) return fail("compressor: chunk too long");
                         fam_v[F_COMP_DETECT].push_back(vi);
+                    }
+                    break;
+                case K_EQ:
+                    if (v.wet < 0.0001f) {
+                        fam_v[F_SUM].push_back(vi);   // the summed input passes through, the state stays
+                    } else {
+                        if (M > 0xFFFF0000ull) return fail("eq: chunk too long");
+                        fam_v[F_EQ_LOCAL].push_back(vi);
                     }
                     break;
                 default: break;
@@ -2242,6 +2259,47 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                     add_launch(F_COMP_APPLY, off, (int)vs.size(), n_tiles, lv);
                     continue;
                 }
+                case F_EQ_LOCAL: {   // the three launches of the level's EQ vertices (kernels.h EqDesc)
+                    const uint32_t n_tiles = (uint32_t)((M + kEqTile - 1) / kEqTile), chunk = (n_tiles + kThreads - 1) / kThreads;
+                    std::vector<EqDesc> d;
+                    for (size_t vi : vs) {
+                        Vertex& v = g->vertices[vi];
+                        EqDesc x{};
+                        x.x = take_buffer(g);
+                        if (!x.x) return fail("termdaw_amd: out of device memory for edge buffers");
+                        level_tmp.push_back(x.x);
+                        x.out = g->vbuf[vi];
+                        x.state = &g->dstate[v.state_slot].eq;
+                        // (a set_time since the vertex last ran: the state restarts from zero -- consumed here, like a compressor's)
+                        x.init = v.first_pending ? nullptr : x.state;
+                        v.first_pending = false;
+                        x.k = (uint32_t)g->edges[vi].size();
+                        x.term_mode = term_mode[vi];
+                        x.frames = (uint32_t)M;
+                        x.n_tiles = n_tiles;
+                        x.chunk = chunk;
+                        x.wet = v.wet;
+                        double c[5];
+                        eq::coefficients(v.eq_kind, sr, v.eq_freq, v.eq_q, v.eq_gain_db, c);
+                        x.b0 = c[0]; x.b1 = c[1]; x.b2 = c[2]; x.a1 = c[3]; x.a2 = c[4];
+                        x.c0 = x.b1 - x.a1 * x.b0;
+                        x.c1 = x.b2 - x.a2 * x.b0;
+                        eq::powers(x.a1, x.a2, kEqRun, chunk, x.pw, x.a_tile, x.pwc);
+                        x.pg = make_pg(v.gain, v.angle);
+                        d.push_back(x);
+                    }
+                    off = st.put(d);
+                    for (size_t i = 0; i < vs.size(); ++i) {
+                        const size_t o = off + i * sizeof(EqDesc), tb = (size_t)n_tiles * 4 * sizeof(double);
+                        ptr_field(o, offsetof(EqDesc, ins), ins_off[vs[i]]);
+                        scratch_field(o, offsetof(EqDesc, agg), scratch(tb));
+                        scratch_field(o, offsetof(EqDesc, carry), scratch(tb));
+                    }
+                    add_launch(F_EQ_LOCAL, off, (int)vs.size(), n_tiles, lv);
+                    add_launch(F_EQ_CARRY, off, (int)vs.size(), 0u, lv);
+                    add_launch(F_EQ_APPLY, off, (int)vs.size(), n_tiles, lv);
+                    continue;
+                }
                 default: continue;
             }
             if (fam == F_SUM || fam == F_ADSR) {   // split at term-mode boundaries (vs is sorted by it)
@@ -2425,6 +2483,9 @@ size_t desc_size(int fam) {
         case F_COMP_APPLY: return sizeof(CompDesc);
         case F_COMP_CARRY1:
         case F_COMP_CARRY2: return sizeof(MasterDesc);
+        case F_EQ_LOCAL:
+        case F_EQ_CARRY:
+        case F_EQ_APPLY: return sizeof(EqDesc);
         default: return 0;
     }
 }

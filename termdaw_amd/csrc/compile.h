@@ -14,6 +14,7 @@ enum Family { F_LOOP, F_MULTI, F_LERP, F_SINE, F_SYNTH, F_SAMPSYN, F_ENV, F_PROB
               F_LOUD /* k_loudness: td_graph_loudness / td_batch_loudness, launched outside the render (never compiled) */,
               F_MASTER_DETECT, F_MASTER_SCAN, F_MASTER_CARRY, F_MASTER_APPLY /* k_master_*: td_graph_master / td_batch_master (never compiled) */,
               F_COMP_DETECT, F_COMP_CARRY1, F_COMP_ENV, F_COMP_CARRY2, F_COMP_APPLY /* a level's compressor vertices: k_comp_detect, k_master_carry (y1), k_comp_env, k_master_carry (yL), k_comp_apply -- in this order */,
+              F_EQ_LOCAL, F_EQ_CARRY, F_EQ_APPLY /* a level's EQ vertices: k_eq_local, k_eq_carry, k_eq_apply -- in this order */,
               F_COUNT };
 extern const char* const kFamilyName[F_COUNT];
 

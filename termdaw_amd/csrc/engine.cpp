@@ -12,6 +12,7 @@
 #include "comm.h"
 #include "compile.h"
 #include "devmem.h"
+#include "eq_math.h"
 #include "midi.h"
 
 #include <math.h>
@@ -537,6 +538,8 @@ static int pull_state(td_graph* g) {
             if (v.kind == K_BAND_PASS && v.state_slot >= 0 && v.first_pending) g->hstate[(size_t)v.state_slot].band.first = 1u;
         for (const auto& v : g->vertices)
             if (v.kind == K_COMPRESSOR && v.state_slot >= 0 && v.first_pending) g->hstate[(size_t)v.state_slot].comp = {0.0, 0.0, {0, 0, 0, 0}};
+        for (const auto& v : g->vertices)
+            if (v.kind == K_EQ && v.state_slot >= 0 && v.first_pending) g->hstate[(size_t)v.state_slot].eq = {0.0, 0.0, 0.0, 0.0};
     }
     return 1;
 }
@@ -891,6 +894,9 @@ static int submit_chunk(Arena& ar, ChunkBuild& cb, hipStream_t stream, ProfCtx& 
                 case F_COMP_CARRY2: launch_master_carry((const MasterDesc*)d, L.n, s); break;
                 case F_COMP_ENV: launch_comp_env((const CompDesc*)d, L.n, L.aux, s); break;
                 case F_COMP_APPLY: launch_comp_apply((const CompDesc*)d, L.n, L.aux, s); break;
+                case F_EQ_LOCAL: launch_eq_local((const EqDesc*)d, L.n, L.aux, s); break;   // (likewise)
+                case F_EQ_CARRY: launch_eq_carry((const EqDesc*)d, L.n, s); break;
+                case F_EQ_APPLY: launch_eq_apply((const EqDesc*)d, L.n, L.aux, s); break;
             }
         }
         li = lj;
@@ -974,6 +980,10 @@ static int prepare_render(td_graph* g, size_t n_blocks, int bits, bool want_pcm,
         for (size_t vi : g->order)
             if (g->vertices[vi].kind == K_COMPRESSOR && !(g->vertices[vi].wet < 0.0001f))
                 return fail("termdaw_amd: this build has no k_comp kernels: compressor vertices cannot be rendered");
+    if (!(launch_eq_local && launch_eq_carry && launch_eq_apply))
+        for (size_t vi : g->order)
+            if (g->vertices[vi].kind == K_EQ && !(g->vertices[vi].wet < 0.0001f))
+                return fail("termdaw_amd: this build has no k_eq kernels: eq vertices cannot be rendered");
     const size_t bl = g->bl;
     if (bl == 0) return fail("termdaw_amd: buffer length 0");
     rp->n_blocks = n_blocks;
@@ -1076,7 +1086,7 @@ static bool starts_afresh(const td_graph* g) {
     for (size_t vi : g->order) {
         const Vertex& v = g->vertices[vi];
         if (v.kind == K_NORMALIZE && !v.has_init_override) return false;
-        if ((v.kind == K_BAND_PASS || v.kind == K_COMPRESSOR) && v.state_slot >= 0 && !v.first_pending) return false;
+        if ((v.kind == K_BAND_PASS || v.kind == K_COMPRESSOR || v.kind == K_EQ) && v.state_slot >= 0 && !v.first_pending) return false;
     }
     return true;
 }
@@ -1259,6 +1269,12 @@ static int graph_set_time_impl(td_graph* g, size_t time) {   // graph.rs:123-128
             case K_COMPRESSOR:   // the detector restarts from (0, 0): the next submission's carries enter with 0
                 if (v.state_slot >= 0) {
                     g->hstate[v.state_slot].comp = {0.0, 0.0, {0, 0, 0, 0}};
+                    v.first_pending = true;
+                }
+                break;
+            case K_EQ:   // the filter restarts from the zero state: the next submission's carry enters with 0
+                if (v.state_slot >= 0) {
+                    g->hstate[v.state_slot].eq = {0.0, 0.0, 0.0, 0.0};
                     v.first_pending = true;
                 }
                 break;
@@ -1760,6 +1776,35 @@ int td_graph_add_compressor(td_graph* g, const char* name, float gain, float ang
     v.makeup_db = makeup_db;
     v.state_slot = slot;
     g->hstate[slot].comp = {0.0, 0.0, {0, 0, 0, 0}};
+    return 1;
+}
+
+// This engine's own filter vertex (no reference counterpart; the definition is in include/termdaw_amd.h).
+static int eq_check(int kind, size_t sr, float freq_hz, float q, float gain_db) {
+    if (!(kind >= 0 && kind < eq::kKinds)) return fail("eq: kind must be one of TD_EQ_LOWPASS .. TD_EQ_HIGHSHELF (0 .. 6)");
+    if (!sr) return fail("eq: the sample rate must be positive");
+    if (!(freq_hz >= 10.0f && 20.0 * (double)freq_hz <= 9.0 * (double)sr)) return fail("eq: freq_hz must lie in [10, 0.45 sr] Hz");
+    if (!(q >= 0.1f && q <= 20.0f)) return fail("eq: q must lie in [0.1, 20]");
+    if (eq::kind_has_gain(kind) && !(gain_db >= -24.0f && gain_db <= 24.0f)) return fail("eq: gain_db must lie in [-24, 24] dB");
+    return 1;
+}
+int td_graph_add_eq(td_graph* g, const char* name, float gain, float angle, float wet, int kind, float freq_hz, float q, float gain_db) {
+    if (!eq_check(kind, g->sr, freq_hz, q, gain_db)) return 0;
+    const int slot = new_slot(g);
+    Vertex& v = add_vertex(g, name, gain, angle, wet, K_EQ);
+    v.eq_kind = kind;
+    v.eq_freq = freq_hz;
+    v.eq_q = q;
+    v.eq_gain_db = eq::kind_has_gain(kind) ? gain_db : 0.0f;
+    v.state_slot = slot;
+    g->hstate[slot].eq = {0.0, 0.0, 0.0, 0.0};
+    return 1;
+}
+int td_eq_coefficients(int kind, size_t sr, float freq_hz, float q, float gain_db, double out[6]) {
+    if (!out) return fail("eq_coefficients: out is null");
+    if (!eq_check(kind, sr, freq_hz, q, gain_db)) return 0;
+    eq::coefficients(kind, sr, freq_hz, q, gain_db, out);
+    out[5] = eq::hmax(out);
     return 1;
 }
 

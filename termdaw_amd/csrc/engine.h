@@ -76,7 +76,7 @@ struct td_flowwbank {
 namespace tde {
 
 enum Kind { K_SUM, K_NORMALIZE, K_SAMPLE_LOOP, K_SAMPLE_MULTI, K_SAMPLE_LERP, K_DEBUG_SINE, K_SYNTH,
-            K_SAMPSYN, K_ADSR, K_BAND_PASS, K_COMPRESSOR, K_COUNT };
+            K_SAMPSYN, K_ADSR, K_BAND_PASS, K_COMPRESSOR, K_EQ, K_COUNT };
 
 struct SineNote { float note, vel; };
 struct SynthNote { float note, vel, env_t, rel_t, hz; };   // hz = 440 * 2^((note - 69) / 12), extensions.rs:503
@@ -121,6 +121,8 @@ struct Vertex {
     bool probe = false;       // (debug_sine, synth; set per chunk by compile_chunk) sine_mode 2: the fast form, its deviation measured by k_sine_probe
     float lgamma = 0, hgamma = 0;
     float threshold_db = 0, ratio = 1, attack_ms = 0, release_ms = 1, knee_db = 0, makeup_db = 0;   // K_COMPRESSOR
+    int eq_kind = 0;   // K_EQ: TD_EQ_*
+    float eq_freq = 1000, eq_q = 1, eq_gain_db = 0;
     tdk::WaveTableD wavetable{};   // K_SAMPSYN: table in HBM (owned by the graph)
     // carried host state (what the reference keeps inside VertexExt, extensions.rs:15-80)
     uint64_t loop_t = 0;
@@ -131,10 +133,10 @@ struct Vertex {
     std::vector<SineNote> sine_notes;
     std::vector<SynthNote> notes;
     Voice3 ap{0, 0, 0}, ag{0, 0, 0};
-    // carried device state slot (Normalize / BandPass / Compressor), index into Graph::dstate
+    // carried device state slot (Normalize / BandPass / Compressor / Eq), index into Graph::dstate
     int state_slot = -1;
     // reset_normalization (extensions.rs:295-299) is kept on the host until the next render consumes it
-    bool first_pending = false;         // band-pass, compressor (its state then restarts from (0, 0)): set_time since the vertex was last compiled into a submission (its descriptor's first_override)
+    bool first_pending = false;         // band-pass, compressor, eq (their state then restarts from zero): set_time since the vertex was last compiled into a submission (its descriptor's first_override)
     bool has_init_override = false;
     float init_override = 0.0f;
     // Normalize: the carried max is the result of a normalize scan (graph.rs:222-237), so a render is expected to
@@ -142,15 +144,16 @@ struct Vertex {
     bool peak_known = false;
     std::shared_ptr<TableCache> tables;   // event-driven kinds only (shared_ptr: Vertex stays copyable)
     bool has_input() const {
-        return kind == K_SUM || kind == K_NORMALIZE || kind == K_ADSR || kind == K_BAND_PASS || kind == K_COMPRESSOR;
+        return kind == K_SUM || kind == K_NORMALIZE || kind == K_ADSR || kind == K_BAND_PASS || kind == K_COMPRESSOR || kind == K_EQ;
     }
 };
 
-// 32-byte slot: NormState, BandState or CompState
+// 32-byte slot: NormState, BandState, CompState or EqState
 union StateSlot {
     tdk::NormState norm;
     tdk::BandState band;
     tdk::CompState comp;
+    tdk::EqState eq;
 };
 static_assert(sizeof(StateSlot) == 32, "carried vertex state: one 32-byte slot");
 

@@ -255,6 +255,36 @@ struct CompDesc {
     PanGain pg;
 };
 
+// A parametric EQ vertex (k_eq_local / k_eq_carry / k_eq_apply; the definition is in include/termdaw_amd.h at
+// td_graph_add_eq): one RBJ biquad per channel in transposed direct form II, f64.  With z = (s1, s2) the recurrence is
+// z[n] = A z[n-1] + c x[n],  A = [[-a1, 1], [-a2, 0]],  c = (b1 - a1 b0, b2 - a2 b0),  y[n] = b0 x[n] + s1[n-1]: an affine scan
+// whose operator is a 2x2 matrix.  The compressor's tiling: tiles of kEqTile frames, a lane owns kEqRun consecutive frames.
+// k_eq_local evaluates the input terms, leaves the summed input in `x` and each tile's zero-start end state (s1l, s2l, s1r,
+// s2r) in agg[4 t ..]; k_eq_carry leaves the state entering each tile in carry[4 t ..] (tile 0: *init, or 0 when init is
+// null); k_eq_apply rebuilds each lane's entry state from there and runs the definition serially.  A 2x2 matrix is stored
+// row-major: {m00, m01, m10, m11}.  Every power is computed on the host in long double and rounded once.
+constexpr uint32_t kEqRun = 8;                   // frames per lane
+constexpr uint32_t kEqTile = kEqRun * kThreads;  // frames per workgroup
+struct EqState { double s1l, s2l, s1r, s2r; };
+struct EqDesc {
+    const InTerm* ins;      // k input terms (kinds 0 .. 4), in connect() order
+    float2* x;              // [frames] the summed input
+    float2* out;
+    EqState* state;         // carried across chunks / block pulls (k_eq_apply stores it)
+    const EqState* init;    // the state entering tile 0 (k_eq_carry reads it): `state`, or nullptr after a set_time
+    double* agg;            // [4 n_tiles]
+    double* carry;          // [4 n_tiles]
+    uint32_t k, term_mode, frames, n_tiles;
+    uint32_t chunk;         // tiles per lane in k_eq_carry
+    float wet;
+    double b0, b1, b2, a1, a2;   // the normalised coefficients (td_eq_coefficients)
+    double c0, c1;          // b1 - a1 b0, b2 - a2 b0
+    double pw[8][4];        // A^(kEqRun 2^k)
+    double a_tile[4];       // A^kEqTile
+    double pwc[8][4];       // A^(kEqTile chunk 2^k)
+    PanGain pg;
+};
+
 // sample_loop_gen (extensions.rs:331-341): out[m] = sample[(t0 + m) % len]
 struct LoopDesc {
     const float2* sample;
@@ -692,6 +722,11 @@ __attribute__((weak)) void launch_master_apply(const MasterDesc* d, int n_desc, 
 __attribute__((weak)) void launch_comp_detect(const CompDesc* d, int n_desc, uint32_t max_tiles, hipStream_t s);
 __attribute__((weak)) void launch_comp_env(const CompDesc* d, int n_desc, uint32_t max_tiles, hipStream_t s);
 __attribute__((weak)) void launch_comp_apply(const CompDesc* d, int n_desc, uint32_t max_tiles, hipStream_t s);
+// Weak for the same reason: a level's EQ vertices, ONE grid per step (grid.x: the largest tile count; the carry: one workgroup
+// per vertex).
+__attribute__((weak)) void launch_eq_local(const EqDesc* d, int n_desc, uint32_t max_tiles, hipStream_t s);
+__attribute__((weak)) void launch_eq_carry(const EqDesc* d, int n_desc, hipStream_t s);
+__attribute__((weak)) void launch_eq_apply(const EqDesc* d, int n_desc, uint32_t max_tiles, hipStream_t s);
 void launch_sinf(const float* in, float* out, uint32_t n, int exact, hipStream_t s);   // out[i] = sin_glibc(in[i]) (exact) or sin_any(in[i])
 void launch_debug_verify(const uint32_t* p, uint32_t n_words, const uint32_t* seg_sums, uint32_t* report, hipStream_t s);   // (TD_DEBUG_SYNC & 16)
 void launch_sample_loop(const LoopDesc* d, int n_desc, uint32_t frames, hipStream_t s);

@@ -1931,6 +1931,164 @@ __global__ __launch_bounds__(kThreads) void k_comp_apply(const CompDesc* __restr
 }
 
 // ------------------------------------------------------------------------------------------------
+// k_eq_local / k_eq_carry / k_eq_apply: the parametric EQ vertex (kernels.h EqDesc).  No reference
+// counterpart; the definition is the header's (td_graph_add_eq): an RBJ biquad per channel, transposed direct form II in f64.
+// ------------------------------------------------------------------------------------------------
+// a non-finite input sample enters the recurrence as 0
+TD_DEV double eq_in(float x) { return fabsf(x) <= 3.402823466e38f ? (double)x : 0.0; }
+// one frame of z <- A z + c x, both channels: u = (s1l, s2l, s1r, s2r)
+TD_DEV void eq_zstep(const EqDesc& d, double (&u)[4], float l, float r) {
+    const double xl = eq_in(l), xr = eq_in(r);
+    const double t0 = (d.c0 * xl - d.a1 * u[0]) + u[1], t1 = d.c1 * xl - d.a2 * u[0];
+    const double t2 = (d.c0 * xr - d.a1 * u[2]) + u[3], t3 = d.c1 * xr - d.a2 * u[2];
+    u[0] = t0; u[1] = t1; u[2] = t2; u[3] = t3;
+}
+// u <- u + P o, per channel (P row-major)
+TD_DEV void eq_mac(double (&u)[4], const double (&P)[4], const double (&o)[4]) {
+    u[0] += P[0] * o[0] + P[1] * o[1];
+    u[1] += P[2] * o[0] + P[3] * o[1];
+    u[2] += P[0] * o[2] + P[1] * o[3];
+    u[3] += P[2] * o[2] + P[3] * o[3];
+}
+// The lanes' run-end states u (lane 0's run started from u_in, the others' from 0) joined in lane order: Hillis-Steele with
+// the host's matrices pw[k] = A^(run 2^k).  in: the state entering the lane's run; last: the state after the last lane's.
+// sv: 4 planes of kThreads doubles.
+TD_DEV void eq_lane_scan(double (&u)[4], const double (&pw)[8][4], const double (&u_in)[4], double* sv, double (&in)[4], double (&last)[4]) {
+    const uint32_t tid = threadIdx.x;
+#pragma unroll 1
+    for (uint32_t k = 0; k < 8; ++k) {
+        const uint32_t off = 1u << k;
+#pragma unroll
+        for (uint32_t i = 0; i < 4; ++i) sv[i * kThreads + tid] = u[i];
+        __syncthreads();
+        if (tid >= off) {
+            double o[4];
+#pragma unroll
+            for (uint32_t i = 0; i < 4; ++i) o[i] = sv[i * kThreads + tid - off];
+            eq_mac(u, pw[k], o);
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (uint32_t i = 0; i < 4; ++i) sv[i * kThreads + tid] = u[i];
+    __syncthreads();
+#pragma unroll
+    for (uint32_t i = 0; i < 4; ++i) {
+        in[i] = tid ? sv[i * kThreads + tid - 1] : u_in[i];
+        last[i] = sv[i * kThreads + kThreads - 1];
+    }
+    __syncthreads();
+}
+__global__ __launch_bounds__(kThreads) void k_eq_local(const EqDesc* __restrict__ descs) {
+    const EqDesc& d = descs[blockIdx.y];
+    if (blockIdx.x >= d.n_tiles) return;
+    __shared__ double sv[4 * kThreads];
+    const uint32_t M = d.frames, f0 = blockIdx.x * kEqTile + threadIdx.x * kEqRun;
+    double u[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll 1
+    for (uint32_t h = 0; h < kEqRun / 4; ++h) {   // (frames beyond M sum to 0)
+        const uint32_t m = f0 + 4u * h;
+        float4 a0, a1;
+        sum_inputs_pairs(d.ins, d.k, d.term_mode, m, m + 2u, M, a0, a1);
+        store_pair(d.x, m, M, a0);
+        store_pair(d.x, m + 2u, M, a1);
+        eq_zstep(d, u, a0.x, a0.y);
+        eq_zstep(d, u, a0.z, a0.w);
+        eq_zstep(d, u, a1.x, a1.y);
+        eq_zstep(d, u, a1.z, a1.w);
+    }
+    const double zero[4] = {0.0, 0.0, 0.0, 0.0};
+    double in[4], last[4];
+    eq_lane_scan(u, d.pw, zero, sv, in, last);
+    if (threadIdx.x == 0) {
+        gstore_d2(d.agg + 4u * blockIdx.x, last[0], last[1]);
+        gstore_d2(d.agg + 4u * blockIdx.x + 2u, last[2], last[3]);
+    }
+}
+// entry[t + 1] = A^kEqTile entry[t] + total[t], entry[0] = *init: k_master_carry's shape (a lane folds `chunk` consecutive
+// tiles, Hillis-Steele over the lanes, a second walk writes the entries) with a 2x2 operator and both channels.  A kernel of
+// its own: k_master_carry and its two users stay as they are.
+__global__ __launch_bounds__(kThreads) void k_eq_carry(const EqDesc* __restrict__ descs) {
+    const EqDesc& d = descs[blockIdx.x];
+    __shared__ double sv[4 * kThreads];
+    const uint32_t tid = threadIdx.x, n = d.n_tiles, c = d.chunk;
+    const uint32_t b = tid * c, e = b + c < n ? b + c : n;
+    double init[4] = {0.0, 0.0, 0.0, 0.0};
+    if (d.init) {
+        const d2v l = gload_d2(&d.init->s1l), r = gload_d2(&d.init->s1r);
+        init[0] = l.x; init[1] = l.y; init[2] = r.x; init[3] = r.y;
+    }
+    double u[4];
+#pragma unroll
+    for (uint32_t i = 0; i < 4; ++i) u[i] = tid ? 0.0 : init[i];
+    for (uint32_t r = b; r < e; ++r) {
+        const d2v l = gload_d2(d.agg + 4u * r), rr = gload_d2(d.agg + 4u * r + 2u);
+        double t[4] = {l.x, l.y, rr.x, rr.y};
+        eq_mac(t, d.a_tile, u);
+#pragma unroll
+        for (uint32_t i = 0; i < 4; ++i) u[i] = t[i];
+    }
+    double in[4], last[4];
+    eq_lane_scan(u, d.pwc, init, sv, in, last);
+    for (uint32_t r = b; r < e; ++r) {
+        gstore_d2(d.carry + 4u * r, in[0], in[1]);
+        gstore_d2(d.carry + 4u * r + 2u, in[2], in[3]);
+        const d2v l = gload_d2(d.agg + 4u * r), rr = gload_d2(d.agg + 4u * r + 2u);
+        double t[4] = {l.x, l.y, rr.x, rr.y};
+        eq_mac(t, d.a_tile, in);
+#pragma unroll
+        for (uint32_t i = 0; i < 4; ++i) in[i] = t[i];
+    }
+}
+// one frame of the definition, one channel: y = b0 x + s1;  s1 = (b1 x - a1 y) + s2;  s2 = b2 x - a2 y;  p = (float)y -- a
+// non-finite x enters as 0 and comes out as itself
+TD_DEV float eq_frame(const EqDesc& d, float xf, double& s1, double& s2) {
+    const double x = eq_in(xf);
+    const double y = d.b0 * x + s1;
+    s1 = (d.b1 * x - d.a1 * y) + s2;
+    s2 = d.b2 * x - d.a2 * y;
+    return fabsf(xf) <= 3.402823466e38f ? (float)y : xf;
+}
+__global__ __launch_bounds__(kThreads) void k_eq_apply(const EqDesc* __restrict__ descs) {
+    const EqDesc& d = descs[blockIdx.y];
+    if (blockIdx.x >= d.n_tiles) return;
+    __shared__ double sv[4 * kThreads];
+    const uint32_t tid = threadIdx.x, M = d.frames, f0 = blockIdx.x * kEqTile + tid * kEqRun;
+    const float wet = d.wet;
+    const d2v cl = gload_d2(d.carry + 4u * blockIdx.x), cr = gload_d2(d.carry + 4u * blockIdx.x + 2u);
+    const double cin[4] = {cl.x, cl.y, cr.x, cr.y};
+    float4 x[kEqRun / 2];
+#pragma unroll
+    for (uint32_t j = 0; j < kEqRun / 2; ++j) x[j] = load_pair(d.x, f0 + 2u * j, M);   // (0 from `frames` on)
+    double u[4];
+#pragma unroll
+    for (uint32_t i = 0; i < 4; ++i) u[i] = tid ? 0.0 : cin[i];
+#pragma unroll
+    for (uint32_t j = 0; j < kEqRun / 2; ++j) {
+        eq_zstep(d, u, x[j].x, x[j].y);
+        eq_zstep(d, u, x[j].z, x[j].w);
+    }
+    double z[4], last[4];
+    eq_lane_scan(u, d.pw, cin, sv, z, last);
+#pragma unroll
+    for (uint32_t j = 0; j < kEqRun / 2; ++j) {
+        const uint32_t m = f0 + 2u * j;
+        if (m >= M) break;
+        float4 p;
+        p.x = eq_frame(d, x[j].x, z[0], z[1]);
+        p.y = eq_frame(d, x[j].y, z[2], z[3]);
+        // the chunk's last frame: what the next chunk / block pull enters with
+        if (m + 1u == M) { d.state->s1l = z[0]; d.state->s2l = z[1]; d.state->s1r = z[2]; d.state->s2r = z[3]; }
+        p.z = eq_frame(d, x[j].z, z[0], z[1]);
+        p.w = eq_frame(d, x[j].w, z[2], z[3]);
+        if (m + 2u == M) { d.state->s1l = z[0]; d.state->s2l = z[1]; d.state->s1r = z[2]; d.state->s2r = z[3]; }
+        // the reference's lerp (adsr.rs:42), f32
+        const float4 o = make_float4(x[j].x + wet * (p.x - x[j].x), x[j].y + wet * (p.y - x[j].y), x[j].z + wet * (p.z - x[j].z), x[j].w + wet * (p.w - x[j].w));
+        store_pair(d.out, m, M, epilogue4(o, d.pg));
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // k_sample_loop: out[m] = sample[(t0 + m) % len]   (extensions.rs:331-341)
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kThreads) void k_sample_loop(const LoopDesc* __restrict__ descs, uint32_t M) {
@@ -5426,6 +5584,17 @@ void launch_comp_env(const CompDesc* d, int n, uint32_t max_tiles, hipStream_t s
 void launch_comp_apply(const CompDesc* d, int n, uint32_t max_tiles, hipStream_t s) {
     for (int o = 0; o < n && max_tiles; o += kMaxGridY)
         hipLaunchKernelGGL(k_comp_apply, dim3(max_tiles, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
+}
+void launch_eq_local(const EqDesc* d, int n, uint32_t max_tiles, hipStream_t s) {
+    for (int o = 0; o < n && max_tiles; o += kMaxGridY)
+        hipLaunchKernelGGL(k_eq_local, dim3(max_tiles, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
+}
+void launch_eq_carry(const EqDesc* d, int n, hipStream_t s) {
+    if (n > 0) hipLaunchKernelGGL(k_eq_carry, dim3(n), dim3(kThreads), 0, s, d);
+}
+void launch_eq_apply(const EqDesc* d, int n, uint32_t max_tiles, hipStream_t s) {
+    for (int o = 0; o < n && max_tiles; o += kMaxGridY)
+        hipLaunchKernelGGL(k_eq_apply, dim3(max_tiles, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
 }
 void launch_sample_loop(const LoopDesc* d, int n, uint32_t frames, hipStream_t s) {
     if (!n || !frames) return;

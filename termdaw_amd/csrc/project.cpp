@@ -18,6 +18,7 @@
 
 #include "engine.h"
 #include "devmem.h"
+#include "eq_math.h"
 #include "lua_subset.h"
 #include "master.h"
 #include "wav.h"
@@ -104,6 +105,7 @@ struct Lv2fxCall { std::string name; float gain, angle, wet; std::string plugin;
 struct AdsrCall { std::string name; float gain, angle, wet; std::string floww; bool use_off, use_max; int note; std::vector<float> conf; };
 struct BandCall { std::string name; float gain, angle, wet, lo, hi; bool pass; };
 struct CompCall { std::string name; float gain, angle, wet, threshold_db, ratio, attack_ms, release_ms, knee_db, makeup_db; };
+struct EqCall { std::string name; float gain, angle, wet; int kind; float freq_hz, q, gain_db; };
 
 using Triple = std::tuple<std::string, std::string, std::string>;
 
@@ -220,6 +222,7 @@ int do_refresh(td_state* s, const std::string& contents) {
     std::vector<AdsrCall> adsrs;
     std::vector<BandCall> bandpasses;
     std::vector<CompCall> compressors;
+    std::vector<EqCall> eqs;
     size_t cs = s->cs, render_sr = s->render_sr, bd = s->bd;
     // std::mem::take (state.rs:79-80): the locals start from the previous values, the State's own fields are left
     // EMPTY until the script has run (state.rs:169-170) -- so they stay empty when the script fails
@@ -373,6 +376,24 @@ int do_refresh(td_state* s, const std::string& contents) {
                 fnum(c.attack_ms) + "," + fnum(c.release_ms) + "," + fnum(c.knee_db) + "," + fnum(c.makeup_db) + ")\n";
         return Value::nil();
     });
+    lua.set_function("add_eq", [&](const std::vector<Value>& a) {   // this engine's own vertex (termdaw_amd.h td_graph_add_eq); kind by name
+        const char* f = "add_eq";
+        const std::string kind = to_str(f, a, 4);
+        int k = 0;
+        while (k < eq::kKinds && kind != eq::kind_name(k)) ++k;
+        if (k == eq::kKinds)
+            throw LuaError{"add_eq: unknown kind \"" + kind + "\" (one of lowpass, highpass, bandpass, notch, peak, lowshelf, highshelf)"};
+        eqs.push_back({to_str(f, a, 0), to_f32(f, a, 1), to_f32(f, a, 2), to_f32(f, a, 3), k, to_f32(f, a, 5), to_f32(f, a, 6), to_f32(f, a, 7)});
+        auto& c = eqs.back();
+        // the ranges that do not depend on the render rate are rejected here, where the line is known; freq_hz's upper end when
+        // the graph is built (td_graph_add_eq)
+        if (!(c.freq_hz >= 10.0f)) throw LuaError{"add_eq: freq_hz must lie in [10, 0.45 sr] Hz"};
+        if (!(c.q >= 0.1f && c.q <= 20.0f)) throw LuaError{"add_eq: q must lie in [0.1, 20]"};
+        if (eq::kind_has_gain(k) && !(c.gain_db >= -24.0f && c.gain_db <= 24.0f)) throw LuaError{"add_eq: gain_db must lie in [-24, 24] dB"};
+        dump += std::string(f) + "(\"" + c.name + "\"," + fnum(c.gain) + "," + fnum(c.angle) + "," + fnum(c.wet) + ",\"" + kind + "\"," + fnum(c.freq_hz) + "," +
+                fnum(c.q) + "," + fnum(c.gain_db) + ")\n";
+        return Value::nil();
+    });
     lua.set_function("connect", [&](const std::vector<Value>& a) {
         edges.push_back({to_str("connect", a, 0), to_str("connect", a, 1)});
         dump += "connect(\"" + edges.back().first + "\",\"" + edges.back().second + "\")\n";
@@ -489,6 +510,8 @@ int do_refresh(td_state* s, const std::string& contents) {
     for (auto& c : compressors)
         if (!td_graph_add_compressor(s->g, c.name.c_str(), c.gain, c.angle, c.wet, c.threshold_db, c.ratio, c.attack_ms, c.release_ms, c.knee_db, c.makeup_db))
             return 0;
+    for (auto& c : eqs)
+        if (!td_graph_add_eq(s->g, c.name.c_str(), c.gain, c.angle, c.wet, c.kind, c.freq_hz, c.q, c.gain_db)) return 0;
     for (auto& e : edges) td_graph_connect(s->g, e.first.c_str(), e.second.c_str());   // failures only warn (state.rs:459)
     td_graph_set_output(s->g, s->output_vertex.c_str());
     if (!td_graph_check(s->g)) return fail("TermDaw: graph check failed! (" + g_error + ")");

@@ -169,7 +169,7 @@ class ProjectScript:
         self.calls = {k: [] for k in (
             "load_sample", "load_resource", "load_midi_floww", "add_sum", "add_normalize", "add_sampleloop",
             "add_sample_multi", "add_sample_lerp", "add_debug_sine", "add_synth", "add_sampsyn", "add_adsr",
-            "add_bandpass", "add_compressor", "connect")}
+            "add_bandpass", "add_compressor", "add_eq", "connect")}
         self.resources = {}                 # path -> bytes (load_resource)
         self.script_order = []              # (fn, args) in call order, for to_lua()
 
@@ -244,6 +244,10 @@ class ProjectScript:
         """This engine's own vertex (include/termdaw_amd.h td_graph_add_compressor): no reference counterpart."""
         self._rec("add_compressor", name, gain, angle, wet, threshold_db, ratio, attack_ms, release_ms, knee_db, makeup_db)
 
+    def add_eq(self, name, gain, angle, wet, kind, freq_hz, q, gain_db):
+        """This engine's own vertex (include/termdaw_amd.h td_graph_add_eq): no reference counterpart.  kind: the string name."""
+        self._rec("add_eq", name, gain, angle, wet, kind, freq_hz, q, gain_db)
+
     def connect(self, a, b):
         self._rec("connect", a, b)
 
@@ -301,6 +305,8 @@ class ProjectScript:
             g.add_bandpass(name, gain, angle, wet, lo, hi, p)
         for args in self.calls["add_compressor"]:
             g.add_compressor(*args)
+        for args in self.calls["add_eq"]:
+            g.add_eq(*args)
         for a, b in self.calls["connect"]:
             g.connect(a, b)
         g.set_output(self.output_vertex)
