@@ -178,6 +178,35 @@ int td_graph_add_eq(td_graph* g, const char* name, float gain, float angle, floa
  * out[5] = Hmax, the maximum over w of |H(e^jw)|, in closed form (|H|^2 is a ratio of two quadratics in sin^2(w / 2): the
  * maximum lies at w = 0, w = pi or a root of a quadratic).  The same range checks as td_graph_add_eq. */
 int td_eq_coefficients(int kind, size_t sr, float freq_hz, float q, float gain_db, double out[6]);
+/* A feedback delay (echo) vertex -- THIS ENGINE'S OWN: no reference counterpart (the reference reaches a delay only through LV2
+ * plugins, add_lv2fx, which this engine parses and drops).  The vertex sums its inputs like every input vertex
+ * (sum_inputs, extensions.rs:310-319), processes, mixes with `wet` by the reference's f32 lerp, then pan and gain like every
+ * vertex (extensions.rs:262-263).
+ *   Constants, once on the host in f64 from the f32 parameters widened; sr: the graph's rate.
+ *     D = max(1, llround(time_ms sr / 1000)),   gs = feedback (1 - cross),   gc = feedback cross
+ *   Recurrence, in f64, on the f32 summed input x[n]; w = u[n - D] comes from the line, which is all zeros before time 0:
+ *     ul[n] = xl[n] + (gs wl + gc wr);   ur[n] = xr[n] + (gs wr + gc wl);   pl[n] = (float)(xl[n] + wl), likewise pr
+ *     in exactly this operation order, with no FMA contraction.  The first echo is therefore at full level and `feedback` sets
+ *     every later one: feedback = 0 is a single slapback; cross = 1 alternates the echoes between the channels.
+ *     A non-finite x[n] enters the line as 0 and its frame's p[n] is x[n] itself: the line never holds a NaN.
+ *   Then in f32, the reference's lerp (adsr.rs:42): out = x + wet * (p - x), which is x + wet * echoes; then pan and gain.
+ *   wet < 0.0001: the summed input passes through untouched (a plain k_sum launch) and the line stays as it is.
+ * State: the line, the last D values of (ul, ur) as doubles, 16 D bytes of device memory (counted by td_graph_device_bytes,
+ * allocated when the vertex is first rendered); zero at time 0, carried between consecutive block pulls and between the chunks of
+ * a render, restarted from zero by td_graph_set_time / td_graph_change_time / td_graph_reset (so every whole render starts from
+ * zero).  A render ends where the project ends: no tail is appended.
+ * Ranges, rejected with a td_last_error that names the parameter (NaN included): time_ms [1, 2000], feedback [0, 0.98],
+ * cross [0, 1].  `wet` is clamped to [0, 1].
+ * Under "band_mode" 2 / "sine_mode" 2 the estimate is carried through a delay vertex at the gain 1 + wet Hecho,
+ * Hecho = 1 / (1 - feedback) the L2 gain of the echo path (G = [[gs, gc], [gc, gs]] is symmetric with eigenvalues feedback and
+ * feedback (1 - 2 cross)): vertices upstream keep their scan / fast forms.
+ * Not part of the vertex: a low-pass in the feedback path ("damping": its u[n-1] term couples the D recurrences), modulated or
+ * fractional delay times, tempo sync, a tail past the project's end. */
+int td_graph_add_delay(td_graph* g, const char* name, float gain, float angle, float wet, float time_ms, float feedback,
+                       float cross);
+/* Host only, no GPU: the delay vertex' constants at rate sr -- out[0 .. 3] = D, gs, gc, Hecho as the engine uses them.  The same
+ * range checks as td_graph_add_delay. */
+int td_delay_params(size_t sr, float time_ms, float feedback, float cross, double out[4]);
 int td_graph_connect(td_graph* g, const char* a, const char* b);          /* graph.rs:80-96 (+58-78) */
 int td_graph_set_output(td_graph* g, const char* vertex);                 /* graph.rs:141-148 */
 int td_graph_check(const td_graph* g);                                    /* check_graph graph.rs:150-174 */
@@ -373,6 +402,7 @@ size_t td_cached_memory_bytes(void);
  *   debug.band_chain 0|1, debug.band_scan_nf 8|16, debug.band_scan n (scan mode: one launch per vertex, frames per lane, bit 0
  *     = every look-back poll times out and predecessors are recomputed; tests/test_gpu_band_scan.py) /
  *   debug.band_serial 0|1 (1: every band-pass vertex on the serial kernel; tests/test_gpu_parity.py) /
+ *   debug.delay_tile 8|16|32|64 (steps per tile of the delay vertex' scan; tests/test_gpu_delay.py) /
  *   debug.band_quick n, debug.band_medium n, debug.band_short n, debug.band_warmup n, debug.band_live_exp n, debug.band_depth n
  *     (the exact band-pass' speculative warm-up lengths in 1 / gamma frames and its liveness thresholds: speed only, the
  *     bit-wise check and repair of k_band_fix keep every result exact; tests/test_gpu_quirks.py, tools/band_*_sweep.py).

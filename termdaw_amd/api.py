@@ -68,6 +68,8 @@ SIGNATURES = {
     "td_graph_add_compressor": (_i32, [_vp, _cp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32]),
     "td_graph_add_eq": (_i32, [_vp, _cp, _f32, _f32, _f32, _i32, _f32, _f32, _f32]),
     "td_eq_coefficients": (_i32, [_i32, _sz, _f32, _f32, _f32, C.POINTER(C.c_double)]),
+    "td_graph_add_delay": (_i32, [_vp, _cp, _f32, _f32, _f32, _f32, _f32, _f32]),
+    "td_delay_params": (_i32, [_sz, _f32, _f32, _f32, C.POINTER(C.c_double)]),
     "td_graph_connect": (_i32, [_vp, _cp, _cp]),
     "td_graph_set_output": (_i32, [_vp, _cp]),
     "td_graph_check": (_i32, [_vp]),
@@ -279,6 +281,14 @@ def eq_coefficients(kind, sr, freq_hz, q, gain_db):
     return k[0:3].copy(), np.array([1.0, k[3], k[4]]), float(k[5])
 
 
+def delay_params(sr, time_ms, feedback, cross):
+    """The delay vertex' constants at rate sr (host only), exactly as the engine uses them: (D, gs, gc, Hecho) -- the delay in
+    frames, the straight and the crossed feedback gain, and 1 / (1 - feedback), the L2 gain of the echo path."""
+    out = (C.c_double * 4)()
+    _check(lib().td_delay_params(int(sr), time_ms, feedback, cross, out))
+    return int(out[0]), float(out[1]), float(out[2]), float(out[3])
+
+
 def loudness_filters(sr):
     """The meter's filters at rate sr (host only): (shelf (b, a), high-pass (b, a)) as float64 arrays with a[0] = 1, and the
     true-peak FIR as a (phases, taps) float32 array (phase 0 the unit impulse)."""
@@ -469,6 +479,10 @@ class Graph:
         """A parametric EQ vertex (this engine's own; the definition is in include/termdaw_amd.h).  kind: a name of EQ_KINDS or
         its TD_EQ_* index."""
         _check(lib().td_graph_add_eq(self.h, name.encode(), gain, angle, wet, eq_kind(kind), freq_hz, q, gain_db))
+
+    def add_delay(self, name, gain, angle, wet, time_ms, feedback, cross):
+        """A feedback delay (echo) vertex (this engine's own; the definition is in include/termdaw_amd.h)."""
+        _check(lib().td_graph_add_delay(self.h, name.encode(), gain, angle, wet, time_ms, feedback, cross))
 
     def connect(self, a, b):
         return bool(lib().td_graph_connect(self.h, a.encode(), b.encode()))

@@ -5,6 +5,7 @@
 // writes goes into the plain-memory staging arena of the ChunkBuild (offsets + fix-up lists that submit_chunk patches once
 // the device addresses are known).  tests/test_compile_asan.py builds it with g++ -fsanitize=address,undefined.
 #include "compile.h"
+#include "delay_math.h"
 #include "eq_math.h"
 
 #include <math.h>
@@ -24,7 +25,8 @@ const char* const kFamilyName[F_COUNT] = {"k_sample_loop", "k_sample_multi", "k_
                                            "k_adsr",        "k_band_pass",    "k_band_spec", "k_band_fix", "k_band_fill", "k_band_scan", "k_quantise", "k_band_audit", "k_stems", "k_sources", "k_loudness",
                                            "k_master_detect", "k_master_scan", "k_master_carry", "k_master_apply",
                                            "k_comp_detect", "k_comp_carry_y1", "k_comp_env", "k_comp_carry_yl", "k_comp_apply",
-                                           "k_eq_local", "k_eq_carry", "k_eq_apply"};
+                                           "k_eq_local", "k_eq_carry", "k_eq_apply",
+                                           "k_delay_local", "k_delay_carry", "k_delay_apply"};
 
 
 // ------------------------------------------------------------------------------------------------
@@ -920,6 +922,12 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                     eq::coefficients(wv.eq_kind, sr, wv.eq_freq, wv.eq_q, wv.eq_gain_db, c);
                     L *= (1.0 - (double)wv.wet) + (double)wv.wet * eq::hmax(c);
                 }
+                // a delay too: out = x + wet (echoes), the echo path's L2 gain is Hecho = 1 / (1 - feedback)
+                if (wv.kind == K_DELAY && !(wv.wet < 0.0001f)) {
+                    double c[4];
+                    delay::params(sr, wv.delay_ms, wv.delay_feedback, wv.delay_cross, c);
+                    L *= 1.0 + (double)wv.wet * c[3];
+                }
                 if (wv.kind == K_ADSR && !(wv.wet < 0.0001f)) {   // |lerp(1, level x vel, wet)| <= max(1, |level| |vel|)
                     const AdsrConfD& c = wv.conf;
                     double lv = std::max(std::max(fabs((double)c.std_vel), fabs((double)c.attack_vel)),
@@ -1456,6 +1464,14 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                     } else {
                         if (M > 0xFFFF0000ull) return fail("eq: chunk too long");
                         fam_v[F_EQ_LOCAL].push_back(vi);
+                    }
+                    break;
+                case K_DELAY:
+                    if (v.wet < 0.0001f) {
+                        fam_v[F_SUM].push_back(vi);   // the summed input passes through, the line stays
+                    } else {
+                        if (M > 0xF0000000ull) return fail("delay: chunk too long");
+                        fam_v[F_DELAY_APPLY].push_back(vi);
                     }
                     break;
                 default: break;
@@ -2300,6 +2316,87 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                     add_launch(F_EQ_APPLY, off, (int)vs.size(), n_tiles, lv);
                     continue;
                 }
+                case F_DELAY_APPLY: {   // the launches of the level's delay vertices (kernels.h DelayDesc)
+                    const uint32_t T = g->delay_tile;
+                    struct Plan { size_t vi; uint32_t D; delay::Tiling t; double c[4]; };
+                    std::vector<Plan> plans;
+                    for (size_t vi : vs) {
+                        const Vertex& v = g->vertices[vi];
+                        Plan p{};
+                        p.vi = vi;
+                        delay::params(sr, v.delay_ms, v.delay_feedback, v.delay_cross, p.c);
+                        p.D = (uint32_t)p.c[0];
+                        p.t = delay::tiling(M, p.D, T);
+                        if ((uint64_t)M + (uint64_t)(T + 4u) * p.D > 0xFFFF0000ull) return fail("delay: chunk too long");
+                        plans.push_back(p);
+                    }
+                    // the vertices whose chunk takes more than one tile first: k_delay_local and k_delay_carry run over those only
+                    std::stable_sort(plans.begin(), plans.end(), [](const Plan& a, const Plan& b) { return (a.t.n_tiles > 1u) > (b.t.n_tiles > 1u); });
+                    std::vector<DelayDesc> d;
+                    int n_multi = 0;
+                    uint32_t g_local = 0, g_carry = 0, g_apply = 0, g_single = 0;
+                    for (const Plan& p : plans) {
+                        Vertex& v = g->vertices[p.vi];
+                        const bool multi = p.t.n_tiles > 1u;
+                        DelayDesc x{};
+                        if (multi) {
+                            x.x = take_buffer(g);
+                            if (!x.x) return fail("termdaw_amd: out of device memory for edge buffers");
+                            level_tmp.push_back(x.x);
+                        }
+                        x.out = g->vbuf[p.vi];
+                        x.line = take_delay_line(g, v, p.D);
+                        if (!x.line) return fail("termdaw_amd: out of device memory for a delay line");
+                        // (a set_time since the vertex last ran: the line restarts from zero -- consumed here, like an EQ's)
+                        if (v.first_pending) v.delay_total = 0;
+                        v.first_pending = false;
+                        x.k = (uint32_t)g->edges[p.vi].size();
+                        x.term_mode = term_mode[p.vi];
+                        x.frames = (uint32_t)M;
+                        x.D = p.D;
+                        x.lanes = p.t.lanes;
+                        x.T = T;
+                        x.n_tiles = p.t.n_tiles;
+                        x.pos = (uint32_t)(v.delay_total % p.D);
+                        x.filled = (uint32_t)std::min<uint64_t>(v.delay_total, p.D);
+                        v.delay_total += M;
+                        x.seg = p.t.seg;
+                        x.chunk = p.t.chunk;
+                        x.wet = v.wet;
+                        x.gs = p.c[1];
+                        x.gc = p.c[2];
+                        delay::powers(x.gs, x.gc, T, x.chunk, x.g_tile, x.pwc);
+                        x.pg = make_pg(v.gain, v.angle);
+                        const uint32_t groups = (uint32_t)(((uint64_t)x.n_tiles * x.lanes + kThreads - 1) / kThreads);
+                        (multi ? g_apply : g_single) = std::max(multi ? g_apply : g_single, groups);
+                        if (multi) {
+                            ++n_multi;
+                            g_local = std::max(g_local, groups);
+                            const uint32_t lw = (uint32_t)kThreads / x.seg;
+                            g_carry = std::max(g_carry, (x.lanes + lw - 1) / lw);
+                        }
+                        d.push_back(x);
+                    }
+                    off = st.put(d);
+                    for (size_t i = 0; i < plans.size(); ++i) {
+                        const size_t o = off + i * sizeof(DelayDesc);
+                        ptr_field(o, offsetof(DelayDesc, ins), ins_off[plans[i].vi]);
+                        if (plans[i].t.n_tiles > 1u) {
+                            const size_t tb = (size_t)plans[i].t.n_tiles * plans[i].t.lanes * 2 * sizeof(double);
+                            scratch_field(o, offsetof(DelayDesc, agg), scratch(tb));
+                            scratch_field(o, offsetof(DelayDesc, carry), scratch(tb));
+                        }
+                    }
+                    if (n_multi) {
+                        add_launch(F_DELAY_LOCAL, off, n_multi, g_local, lv);
+                        add_launch(F_DELAY_CARRY, off, n_multi, g_carry, lv);
+                    }
+                    // (k_delay_apply's two instantiations: the multi-tile vertices stream their scratch buffer, the others run the term loop)
+                    if (n_multi) add_launch(F_DELAY_APPLY, off, n_multi, g_apply, lv);
+                    if ((size_t)n_multi < plans.size())
+                        add_launch(F_DELAY_APPLY, off + (size_t)n_multi * sizeof(DelayDesc), (int)plans.size() - n_multi, g_single | kDelaySingleBit, lv);
+                    continue;
+                }
                 default: continue;
             }
             if (fam == F_SUM || fam == F_ADSR) {   // split at term-mode boundaries (vs is sorted by it)
@@ -2486,9 +2583,13 @@ size_t desc_size(int fam) {
         case F_EQ_LOCAL:
         case F_EQ_CARRY:
         case F_EQ_APPLY: return sizeof(EqDesc);
+        case F_DELAY_LOCAL:
+        case F_DELAY_CARRY:
+        case F_DELAY_APPLY: return sizeof(DelayDesc);
         default: return 0;
     }
 }
 bool is_band_family(int fam) { return fam == F_BAND_SPEC || fam == F_BAND_FIX || fam == F_BAND_FILL; }
+bool is_delay_family(int fam) { return fam == F_DELAY_LOCAL || fam == F_DELAY_CARRY || fam == F_DELAY_APPLY; }
 
 }  // namespace tde

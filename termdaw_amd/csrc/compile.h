@@ -15,6 +15,7 @@ enum Family { F_LOOP, F_MULTI, F_LERP, F_SINE, F_SYNTH, F_SAMPSYN, F_ENV, F_PROB
               F_MASTER_DETECT, F_MASTER_SCAN, F_MASTER_CARRY, F_MASTER_APPLY /* k_master_*: td_graph_master / td_batch_master (never compiled) */,
               F_COMP_DETECT, F_COMP_CARRY1, F_COMP_ENV, F_COMP_CARRY2, F_COMP_APPLY /* a level's compressor vertices: k_comp_detect, k_master_carry (y1), k_comp_env, k_master_carry (yL), k_comp_apply -- in this order */,
               F_EQ_LOCAL, F_EQ_CARRY, F_EQ_APPLY /* a level's EQ vertices: k_eq_local, k_eq_carry, k_eq_apply -- in this order */,
+              F_DELAY_LOCAL, F_DELAY_CARRY, F_DELAY_APPLY /* a level's delay vertices: k_delay_local, k_delay_carry (both over the vertices whose chunk takes more than one tile only), k_delay_apply -- in this order */,
               F_COUNT };
 extern const char* const kFamilyName[F_COUNT];
 
@@ -27,11 +28,13 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb, 
                   bool is_scan, void* pcm_dst, int qmode, float amplitude, ChunkBuild& cb);
 size_t desc_size(int fam);
 bool is_band_family(int fam);
+bool is_delay_family(int fam);
 double ms_between(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b);
 
 // ---- engine.cpp: the device memory the compiler hands out addresses of ----
 int upload_tables(td_graph* g, TableCache& tc, const Staging& tmp);   // a vertex' event tables -> its device buffer (queued on the graph's stream)
 int ensure_buffers(td_graph* g, size_t frames);                      // the edge-buffer pool holds buffers of >= frames frames; all of them free
+double* take_delay_line(td_graph* g, tde::Vertex& v, size_t D);    // a delay vertex' line, allocated on first use (nullptr: out of device memory)
 float2* take_buffer(td_graph* g);                                    // one edge buffer (nullptr: out of device memory)
 
 }  // namespace tde

@@ -11,6 +11,7 @@
 #include "engine.h"
 #include "comm.h"
 #include "compile.h"
+#include "delay_math.h"
 #include "devmem.h"
 #include "eq_math.h"
 #include "midi.h"
@@ -558,6 +559,23 @@ int ensure_buffers(td_graph* g, size_t frames) {
     g->free_bufs = g->pool;
     return 1;
 }
+// The line of a delay vertex: 16 D bytes, allocated when the vertex is first compiled into a submission (never cleared: a word is
+// read only once the vertex has written it, Vertex::delay_total), freed with the graph's vertices.
+double* take_delay_line(td_graph* g, Vertex& v, size_t D) {
+    if (v.delay_line) return v.delay_line;
+    double* p = nullptr;
+    if (hipMalloc(&p, D * 2 * sizeof(double)) != hipSuccess) return nullptr;
+    g->delay_lines.push_back({p, D * 2 * sizeof(double)});
+    g->device_bytes += D * 2 * sizeof(double);
+    v.delay_line = p;
+    v.delay_total = 0;
+    return p;
+}
+static void free_delay_lines(td_graph* g) {
+    for (auto& l : g->delay_lines) { (void)hipFree(l.first); g->device_bytes -= l.second; }
+    g->delay_lines.clear();
+    for (auto& v : g->vertices) v.delay_line = nullptr;
+}
 float2* take_buffer(td_graph* g) {
     if (!g->free_bufs.empty()) {
         float2* p = g->free_bufs.back();
@@ -679,7 +697,8 @@ static int submit_chunk(Arena& ar, ChunkBuild& cb, hipStream_t stream, ProfCtx& 
             if (a.M != b.M) return a.M < b.M;
             if (a.bl != b.bl) return a.bl < b.bl;
             if (a.is_scan != b.is_scan) return a.is_scan < b.is_scan;
-            if (!is_band_family(a.fam) && a.aux != b.aux) return a.aux < b.aux;
+            if (is_delay_family(a.fam) && ((a.aux ^ b.aux) & kDelaySingleBit)) return a.aux < b.aux;   // (k_delay_apply's two instantiations stay apart)
+            if (!is_band_family(a.fam) && !is_delay_family(a.fam) && a.aux != b.aux) return a.aux < b.aux;   // (those two: aux is the largest grid of the launch's descriptors)
             return false;
         };
         std::stable_sort(launches.begin(), launches.end(), key_less);
@@ -691,7 +710,7 @@ static int submit_chunk(Arena& ar, ChunkBuild& cb, hipStream_t stream, ProfCtx& 
             uint32_t aux = launches[i].aux;
             while (j < launches.size() && !key_less(launches[i], launches[j]) && !key_less(launches[j], launches[i])) {
                 n += launches[j].n;
-                aux = std::max(aux, launches[j].aux);   // (equal unless a band family: its largest segment count)
+                aux = std::max(aux, launches[j].aux);   // (equal unless a band family: its largest segment count; or a delay family: its largest grid)
                 ++j;
             }
             Launch L = launches[i];
@@ -897,6 +916,9 @@ static int submit_chunk(Arena& ar, ChunkBuild& cb, hipStream_t stream, ProfCtx& 
                 case F_EQ_LOCAL: launch_eq_local((const EqDesc*)d, L.n, L.aux, s); break;   // (likewise)
                 case F_EQ_CARRY: launch_eq_carry((const EqDesc*)d, L.n, s); break;
                 case F_EQ_APPLY: launch_eq_apply((const EqDesc*)d, L.n, L.aux, s); break;
+                case F_DELAY_LOCAL: launch_delay_local((const DelayDesc*)d, L.n, L.aux, s); break;   // (likewise)
+                case F_DELAY_CARRY: launch_delay_carry((const DelayDesc*)d, L.n, L.aux, s); break;
+                case F_DELAY_APPLY: launch_delay_apply((const DelayDesc*)d, L.n, L.aux & ~kDelaySingleBit, (L.aux & kDelaySingleBit) != 0u, s); break;
             }
         }
         li = lj;
@@ -984,6 +1006,10 @@ static int prepare_render(td_graph* g, size_t n_blocks, int bits, bool want_pcm,
         for (size_t vi : g->order)
             if (g->vertices[vi].kind == K_EQ && !(g->vertices[vi].wet < 0.0001f))
                 return fail("termdaw_amd: this build has no k_eq kernels: eq vertices cannot be rendered");
+    if (!(launch_delay_local && launch_delay_carry && launch_delay_apply))
+        for (size_t vi : g->order)
+            if (g->vertices[vi].kind == K_DELAY && !(g->vertices[vi].wet < 0.0001f))
+                return fail("termdaw_amd: this build has no k_delay kernels: delay vertices cannot be rendered");
     const size_t bl = g->bl;
     if (bl == 0) return fail("termdaw_amd: buffer length 0");
     rp->n_blocks = n_blocks;
@@ -1087,6 +1113,7 @@ static bool starts_afresh(const td_graph* g) {
         const Vertex& v = g->vertices[vi];
         if (v.kind == K_NORMALIZE && !v.has_init_override) return false;
         if ((v.kind == K_BAND_PASS || v.kind == K_COMPRESSOR || v.kind == K_EQ) && v.state_slot >= 0 && !v.first_pending) return false;
+        if (v.kind == K_DELAY && v.delay_line && !v.first_pending) return false;
     }
     return true;
 }
@@ -1127,6 +1154,26 @@ static int guard_begin(td_graph* g, const td_samplebank* sb, td_flowwbank* fb, s
         TD_HIP(hipMemcpyAsync(q.d_backup, g->dstate, n * sizeof(StateSlot), hipMemcpyDeviceToDevice, g->stream));
         q.have_backup = true;
     }
+    // the lines of the delay vertices that continue from what they hold (a vertex with a set_time pending reads nothing of its line)
+    q.lines.clear();
+    size_t need = 0;
+    for (size_t vi : g->order) {
+        const Vertex& v = g->vertices[vi];
+        if (v.kind != K_DELAY || !v.delay_line || v.first_pending || !v.delay_total) continue;
+        for (const auto& l : g->delay_lines)
+            if (l.first == v.delay_line) { q.lines.push_back({vi, need, l.second}); need += l.second; }
+    }
+    if (need > q.lines_cap) {
+        if (q.d_lines) (void)hipFree(q.d_lines);
+        q.d_lines = nullptr;
+        q.lines_cap = 0;
+        uint8_t* p = nullptr;
+        TD_HIP(hipMalloc(&p, need));
+        q.d_lines = p;
+        q.lines_cap = need;
+    }
+    for (const auto& l : q.lines)
+        TD_HIP(hipMemcpyAsync((uint8_t*)q.d_lines + l.off, g->vertices[l.vertex].delay_line, l.bytes, hipMemcpyDeviceToDevice, g->stream));
     return 1;
 }
 // The stream has drained: look at the verdict of the last guarded render, and do that render again with the exact kernels
@@ -1154,6 +1201,10 @@ static int guard_settle(td_graph* g) {
     int ok = 1;
     if (q.have_backup && hipMemcpyAsync(g->dstate, q.d_backup, g->hstate.size() * sizeof(StateSlot), hipMemcpyDeviceToDevice, g->stream) != hipSuccess)
         ok = fail("HIP error: the guard could not restore the carried state");
+    for (const auto& l : q.lines)
+        if (ok && l.vertex < g->vertices.size() && g->vertices[l.vertex].delay_line &&
+            hipMemcpyAsync(g->vertices[l.vertex].delay_line, (const uint8_t*)q.d_lines + l.off, l.bytes, hipMemcpyDeviceToDevice, g->stream) != hipSuccess)
+            ok = fail("HIP error: the guard could not restore a delay line");
     g->state_dev_dirty = true;
     if (ok) ok = graph_render_chunks(g, q.sb, q.fb, q.n_blocks, q.is_scan, q.bits, q.advance, q.scan_t0, q.want_pcm);
     now.put(g, q.fb);
@@ -1185,6 +1236,7 @@ void HostSnapshot::take(const td_graph* g, const td_flowwbank* fb) {
     for (size_t i = 0; i < v.size(); ++i) {
         const Vertex& x = g->vertices[i];
         v[i].loop_t = x.loop_t;
+        v[i].delay_total = x.delay_total;
         v[i].has_init_override = x.has_init_override;
         v[i].peak_known = x.peak_known;
         v[i].first_pending = x.first_pending;
@@ -1200,6 +1252,7 @@ void HostSnapshot::put(td_graph* g, td_flowwbank* fb) const {
     for (size_t i = 0; i < v.size() && i < g->vertices.size(); ++i) {
         Vertex& x = g->vertices[i];
         x.loop_t = v[i].loop_t;
+        x.delay_total = v[i].delay_total;
         x.has_init_override = v[i].has_init_override;
         x.peak_known = v[i].peak_known;
         x.first_pending = v[i].first_pending;
@@ -1277,6 +1330,9 @@ static int graph_set_time_impl(td_graph* g, size_t time) {   // graph.rs:123-128
                     g->hstate[v.state_slot].eq = {0.0, 0.0, 0.0, 0.0};
                     v.first_pending = true;
                 }
+                break;
+            case K_DELAY:   // the line restarts from zero: the next submission reads none of its words
+                v.first_pending = true;
                 break;
             default: break;
         }
@@ -1533,7 +1589,7 @@ void td_graph_free(td_graph* g) {
                 break;
             }
     }
-    const bool has_device_state = g->stream || !g->pool.empty() || !g->wavetables.empty() || g->dstate || g->arena.d || g->d_pcm ||
+    const bool has_device_state = g->stream || !g->pool.empty() || !g->wavetables.empty() || !g->delay_lines.empty() || g->dstate || g->arena.d || g->d_pcm ||
                                   g->d_out_f32 || g->d_resampled || g->d_scalar || g->d_stem_pcm || g->d_stem_peak || g->d_stem_f32 ||
                                   g->d_loud || g->d_master_src || g->d_master;
     if (has_device_state && hipSetDevice(g->device) == hipSuccess) {
@@ -1541,6 +1597,7 @@ void td_graph_free(td_graph* g) {
         else (void)hipDeviceSynchronize();   // (a graph whose stream could not be re-made after td_batch_free)
         for (float2* p : g->pool) (void)hipFree(p);
         for (float* p : g->wavetables) (void)hipFree(p);
+        free_delay_lines(g);
         free_tables(g);
         if (g->dstate) (void)hipFree(g->dstate);
         free_arena(g->arena);
@@ -1555,6 +1612,7 @@ void td_graph_free(td_graph* g) {
         if (g->d_master) (void)hipFree(g->d_master);
         if (g->d_scalar) (void)hipFree(g->d_scalar);
         if (g->guard.d_backup) (void)hipFree(g->guard.d_backup);
+        if (g->guard.d_lines) (void)hipFree(g->guard.d_lines);
         if (g->guard.h_word) (void)hipHostFree(g->guard.h_word);
         free_prof(g->prof);
         if (g->owns_stream && g->stream) (void)hipStreamDestroy(g->stream);
@@ -1564,12 +1622,17 @@ void td_graph_free(td_graph* g) {
 }
 void td_graph_reset(td_graph* g) {
     g->guard.armed = false;   // (the vertices a pending verdict is about are going)
-    if ((g->stream || !g->wavetables.empty()) && hipSetDevice(g->device) == hipSuccess) {
+    if ((g->stream || !g->wavetables.empty() || !g->delay_lines.empty()) && hipSetDevice(g->device) == hipSuccess) {
         if (g->stream) (void)drain(g);   // (a deferred k_norm_fix belongs to the vertices about to go)
         for (float* p : g->wavetables) (void)hipFree(p);
+        free_delay_lines(g);
         free_tables(g);
     }
     g->wavetables.clear();
+    // (lines that could not be given back above -- no device -- leave the books with their vertices all the same)
+    for (auto& l : g->delay_lines) g->device_bytes -= l.second;
+    g->delay_lines.clear();
+    g->guard.lines.clear();
     g->vertices.clear();
     g->edges.clear();
     g->name_map.clear();
@@ -1805,6 +1868,31 @@ int td_eq_coefficients(int kind, size_t sr, float freq_hz, float q, float gain_d
     if (!eq_check(kind, sr, freq_hz, q, gain_db)) return 0;
     eq::coefficients(kind, sr, freq_hz, q, gain_db, out);
     out[5] = eq::hmax(out);
+    return 1;
+}
+
+// This engine's own echo vertex (no reference counterpart; the definition is in include/termdaw_amd.h).
+static int delay_check(size_t sr, float time_ms, float feedback, float cross) {
+    if (!sr) return fail("delay: the sample rate must be positive");
+    if (!(time_ms >= 1.0f && time_ms <= 2000.0f)) return fail("delay: time_ms must lie in [1, 2000] ms");
+    if (!(feedback >= 0.0f && feedback <= 0.98f)) return fail("delay: feedback must lie in [0, 0.98]");
+    if (!(cross >= 0.0f && cross <= 1.0f)) return fail("delay: cross must lie in [0, 1]");
+    if ((double)time_ms * (double)sr / 1000.0 > 268435456.0) return fail("delay: time_ms is more than 2^28 frames at this sample rate");
+    return 1;
+}
+int td_graph_add_delay(td_graph* g, const char* name, float gain, float angle, float wet, float time_ms, float feedback, float cross) {
+    if (!delay_check(g->sr, time_ms, feedback, cross)) return 0;
+    Vertex& v = add_vertex(g, name, gain, angle, wet, K_DELAY);
+    v.delay_ms = time_ms;
+    v.delay_feedback = feedback;
+    v.delay_cross = cross;
+    v.first_pending = true;   // (the line, once it exists, is read from the first word the vertex itself has written)
+    return 1;
+}
+int td_delay_params(size_t sr, float time_ms, float feedback, float cross, double out[4]) {
+    if (!out) return fail("delay_params: out is null");
+    if (!delay_check(sr, time_ms, feedback, cross)) return 0;
+    delay::params(sr, time_ms, feedback, cross, out);
     return 1;
 }
 
@@ -2566,6 +2654,7 @@ static std::vector<OptionRef> option_table(td_graph* g) {
         {"debug.inline_adsr", 0, &g->inline_adsr}, {"debug.spec_normalize", 0, &g->spec_normalize},
         {"debug.single_pass_normalize", 0, &g->single_pass_normalize}, {"debug.fuse_normalize", 0, &g->fuse_normalize},
         {"debug.table_cache", 0, &g->table_cache}, {"debug.band_serial", 0, &g->band_serial}, {"debug.band_chain", 0, &g->band_chain}, {"debug.band_scan_nf", 1, &g->band_scan_nf},
+        {"debug.delay_tile", 2, &g->delay_tile},
         {"debug.band_quick", 2, &g->band_quick}, {"debug.band_short", 2, &g->band_short}, {"debug.band_medium", 2, &g->band_medium},
         {"debug.band_warmup", 2, &g->band_warmup}, {"debug.band_depth", 2, &g->band_depth},
         {"debug.stem_taps", 2, &g->stem_taps},
@@ -2598,6 +2687,11 @@ int td_graph_set_option(td_graph* g, const char* key, long value) {
     if (k == "debug.band_scan_nf") {
         if (value != 8 && value != 16) return fail("debug.band_scan_nf must be 8 or 16");
         g->band_scan_nf = (int)value;
+        return 1;
+    }
+    if (k == "debug.delay_tile") {
+        if (value != 8 && value != 16 && value != 32 && value != 64) return fail("debug.delay_tile must be 8, 16, 32 or 64");
+        g->delay_tile = (unsigned)value;
         return 1;
     }
     if (k == "debug.band_live_exp") { g->band_live_thr = value >= 38 ? 0.0f : powf(10.0f, -(float)value); return 1; }

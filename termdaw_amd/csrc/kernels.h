@@ -285,6 +285,40 @@ struct EqDesc {
     PanGain pg;
 };
 
+// A feedback delay vertex (k_delay_local / k_delay_carry / k_delay_apply; the definition is in
+// include/termdaw_amd.h at td_graph_add_delay): u[n] = x[n] + G u[n - D], G = [[gs, gc], [gc, gs]] over (l, r) -- D independent
+// first-order recurrences, one per residue of n mod D, each a constant 2x2 affine map: §3n's blocked scan with stride D.
+// Lane j = chunk frame mod D, step k = chunk frame div D; a tile is T steps of every lane.  A chunk shorter than D has lanes
+// = min(D, frames) of them, one step each.  One thread owns one lane of one tile: thread index = tile * lanes + j, so a step's loads and stores are contiguous across a wave.
+// The line holds the last D values of (ul, ur), 16 D bytes; the vertex has run `pos` frames (mod D) since the line restarted, so
+// lane j's word is line[2 ((pos + j) mod D)] and no other lane's -- a word below `filled` holds a value, the others read as 0
+// (after a set_time filled = 0: nothing is read and nothing needs clearing).
+// k_delay_local evaluates the input terms, leaves the summed input in `x` and each (tile, lane)'s zero-start end state in
+// agg[2 (tile lanes + j) ..]; k_delay_carry leaves the state entering each tile in carry[..] (per lane: `seg` threads fold
+// `chunk` consecutive tiles each, Hillis-Steele over them); k_delay_apply runs each thread's T steps from its entry state in
+// the definition's order.  When one tile covers the chunk (n_tiles == 1) k_delay_apply runs alone, in an instantiation of its
+// own (launch_delay_apply's `single`): the entry state is the line and the term loop runs inside it (x, agg, carry unused).  A 2x2 matrix is stored row-major; every power is computed on the
+// host in long double and rounded once.
+struct DelayDesc {
+    const InTerm* ins;      // k input terms (kinds 0 .. 4), in connect() order
+    float2* x;              // [frames] the summed input (three-launch form)
+    float2* out;
+    double* line;           // [2 D] carried across chunks / block pulls (k_delay_apply stores the words of the last D frames)
+    double* agg;            // [2 n_tiles lanes]
+    double* carry;          // [2 n_tiles lanes]
+    uint32_t k, term_mode, frames, D;
+    uint32_t lanes;         // min(D, frames)
+    uint32_t T;             // steps per tile (even)
+    uint32_t n_tiles;       // ceil(ceil(frames / D) / T)
+    uint32_t pos, filled;   // the line's rotation and how many of its words hold a value
+    uint32_t seg, chunk;    // k_delay_carry: threads per lane (a power of two <= kThreads), tiles per thread
+    float wet;
+    double gs, gc;          // feedback (1 - cross), feedback cross
+    double g_tile[4];       // G^T
+    double pwc[8][4];       // G^(T chunk 2^k)
+    PanGain pg;
+};
+
 // sample_loop_gen (extensions.rs:331-341): out[m] = sample[(t0 + m) % len]
 struct LoopDesc {
     const float2* sample;
@@ -727,6 +761,13 @@ __attribute__((weak)) void launch_comp_apply(const CompDesc* d, int n_desc, uint
 __attribute__((weak)) void launch_eq_local(const EqDesc* d, int n_desc, uint32_t max_tiles, hipStream_t s);
 __attribute__((weak)) void launch_eq_carry(const EqDesc* d, int n_desc, hipStream_t s);
 __attribute__((weak)) void launch_eq_apply(const EqDesc* d, int n_desc, uint32_t max_tiles, hipStream_t s);
+// Weak for the same reason: a level's delay vertices (grid.x: the largest thread count in workgroups; the carry's: the largest
+// lane count in workgroups of kThreads / seg lanes).  launch_delay_apply takes either the multi-tile vertices of a level or the
+// single-tile ones (`single`), never both: kDelaySingleBit of a launch's aux says which.
+constexpr uint32_t kDelaySingleBit = 0x80000000u;
+__attribute__((weak)) void launch_delay_local(const DelayDesc* d, int n_desc, uint32_t max_groups, hipStream_t s);
+__attribute__((weak)) void launch_delay_carry(const DelayDesc* d, int n_desc, uint32_t max_groups, hipStream_t s);
+__attribute__((weak)) void launch_delay_apply(const DelayDesc* d, int n_desc, uint32_t max_groups, bool single, hipStream_t s);
 void launch_sinf(const float* in, float* out, uint32_t n, int exact, hipStream_t s);   // out[i] = sin_glibc(in[i]) (exact) or sin_any(in[i])
 void launch_debug_verify(const uint32_t* p, uint32_t n_words, const uint32_t* seg_sums, uint32_t* report, hipStream_t s);   // (TD_DEBUG_SYNC & 16)
 void launch_sample_loop(const LoopDesc* d, int n_desc, uint32_t frames, hipStream_t s);

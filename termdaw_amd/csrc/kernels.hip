@@ -2089,6 +2089,157 @@ __global__ __launch_bounds__(kThreads) void k_eq_apply(const EqDesc* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------------
+// k_delay_local / k_delay_carry / k_delay_apply: the feedback delay vertex (kernels.h DelayDesc).  No reference
+// counterpart; the definition is the header's (td_graph_add_delay): u[n] = x[n] + G u[n - D] in f64, D independent lanes.
+// ------------------------------------------------------------------------------------------------
+TD_DEV bool delay_finite(float x) { return fabsf(x) <= 3.402823466e38f; }
+// the term loop works on aligned frame pairs: frame m's half of the pair that holds it
+TD_DEV float2 delay_pick(float4 a, uint32_t m) { return (m & 1u) ? make_float2(a.z, a.w) : make_float2(a.x, a.y); }
+// one frame of the recurrence from the zero-start side: u <- x + G u (a non-finite x enters as 0)
+TD_DEV void delay_ustep(const DelayDesc& d, float2 x, double& ul, double& ur) {
+    const double xl = delay_finite(x.x) ? (double)x.x : 0.0, xr = delay_finite(x.y) ? (double)x.y : 0.0;
+    const double wl = ul, wr = ur;
+    ul = xl + (d.gs * wl + d.gc * wr);
+    ur = xr + (d.gs * wr + d.gc * wl);
+}
+// one frame of the definition: w = u[n - D];  u[n] = x + G w;  p = (float)(x + w) -- a non-finite x comes out as itself; then the
+// reference's lerp (adsr.rs:42) in f32, pan and gain
+TD_DEV float2 delay_frame(const DelayDesc& d, float2 x, double& ul, double& ur) {
+    const bool fl = delay_finite(x.x), fr = delay_finite(x.y);
+    const double xl = fl ? (double)x.x : 0.0, xr = fr ? (double)x.y : 0.0;
+    const double wl = ul, wr = ur;
+    ul = xl + (d.gs * wl + d.gc * wr);
+    ur = xr + (d.gs * wr + d.gc * wl);
+    const float pl = fl ? (float)(xl + wl) : x.x, pr = fr ? (float)(xr + wr) : x.y;
+    return epilogue(make_float2(x.x + d.wet * (pl - x.x), x.y + d.wet * (pr - x.y)), d.pg);
+}
+// t <- t + P o (P row-major)
+TD_DEV void delay_mac(double (&t)[2], const double (&P)[4], const double (&o)[2]) {
+    t[0] += P[0] * o[0] + P[1] * o[1];
+    t[1] += P[2] * o[0] + P[3] * o[1];
+}
+// the summed input of the four frames m, m + D, m + 2 D, m + 3 D (0 from `frames` on)
+TD_DEV void delay_sum4(const DelayDesc& d, uint32_t m, float2 (&x)[4]) {
+    const uint32_t M = d.frames, D = d.D;
+    float4 a[4];
+    sum_inputs_pairs(d.ins, d.k, d.term_mode, m & ~1u, (m + D) & ~1u, M, a[0], a[1]);
+    sum_inputs_pairs(d.ins, d.k, d.term_mode, (m + 2u * D) & ~1u, (m + 3u * D) & ~1u, M, a[2], a[3]);
+#pragma unroll
+    for (uint32_t q = 0; q < 4; ++q) x[q] = delay_pick(a[q], m + q * D);
+}
+__global__ __launch_bounds__(kThreads) void k_delay_local(const DelayDesc* __restrict__ descs) {
+    const DelayDesc& d = descs[blockIdx.y];
+    const uint32_t gid = blockIdx.x * kThreads + threadIdx.x, lanes = d.lanes;
+    if (gid >= d.n_tiles * lanes) return;
+    const uint32_t tile = gid / lanes, j = gid - tile * lanes, M = d.frames, D = d.D, T = d.T;
+    uint32_t m = tile * T * D + j;
+    double ul = 0.0, ur = 0.0;
+#pragma unroll 1
+    for (uint32_t i = 0; i < T && m < M; i += 4u, m += 4u * D) {   // (only the chunk's last tile can be short: its end state is never read)
+        float2 x[4];
+        delay_sum4(d, m, x);
+#pragma unroll
+        for (uint32_t q = 0; q < 4; ++q) {
+            const uint32_t mq = m + q * D;
+            if (mq >= M) break;
+            gstore2(d.x + mq, x[q]);
+            delay_ustep(d, x[q], ul, ur);
+        }
+    }
+    gstore_d2(d.agg + 2u * (size_t)gid, ul, ur);
+}
+// Per lane: entry[t + 1] = G^T entry[t] + total[t], entry[0] = the lane's line word.  k_eq_carry's shape per lane -- `seg` threads
+// fold `chunk` consecutive tiles each, Hillis-Steele over them with the host's pwc[k] = G^(T chunk 2^k), a second walk writes the
+// entries -- with kThreads / seg lanes side by side in a workgroup, lane fastest.
+__global__ __launch_bounds__(kThreads) void k_delay_carry(const DelayDesc* __restrict__ descs) {
+    const DelayDesc& d = descs[blockIdx.y];
+    const uint32_t seg = d.seg, lw = kThreads / seg, lanes = d.lanes;
+    if (blockIdx.x * lw >= lanes) return;
+    __shared__ double sv[2 * kThreads];
+    const uint32_t tid = threadIdx.x, sg = tid / lw, j = blockIdx.x * lw + (tid - sg * lw);
+    const bool live = j < lanes;
+    const uint32_t n = d.n_tiles, c = d.chunk;
+    const uint32_t b = sg * c < n ? sg * c : n, e = b + c < n ? b + c : n;
+    double init[2] = {0.0, 0.0};
+    if (live && sg == 0u) {
+        uint32_t li = d.pos + j;
+        if (li >= d.D) li -= d.D;
+        if (li < d.filled) { const d2v w = gload_d2(d.line + 2u * (size_t)li); init[0] = w.x; init[1] = w.y; }
+    }
+    double u[2] = {init[0], init[1]};   // (0 for every thread but a lane's first)
+    if (live)
+        for (uint32_t r = b; r < e; ++r) {
+            const d2v a = gload_d2(d.agg + 2u * ((size_t)r * lanes + j));
+            double t[2] = {a.x, a.y};
+            delay_mac(t, d.g_tile, u);
+            u[0] = t[0]; u[1] = t[1];
+        }
+#pragma unroll 1
+    for (uint32_t k = 0; (1u << k) < seg; ++k) {
+        const uint32_t off = (1u << k) * lw;
+        sv[tid] = u[0]; sv[kThreads + tid] = u[1];
+        __syncthreads();
+        if (tid >= off) {
+            const double o[2] = {sv[tid - off], sv[kThreads + tid - off]};
+            delay_mac(u, d.pwc[k], o);
+        }
+        __syncthreads();
+    }
+    sv[tid] = u[0]; sv[kThreads + tid] = u[1];
+    __syncthreads();
+    double in[2] = {init[0], init[1]};
+    if (sg) { in[0] = sv[tid - lw]; in[1] = sv[kThreads + tid - lw]; }
+    if (!live) return;
+    for (uint32_t r = b; r < e; ++r) {
+        const size_t w = 2u * ((size_t)r * lanes + j);
+        gstore_d2(d.carry + w, in[0], in[1]);
+        const d2v a = gload_d2(d.agg + w);
+        double t[2] = {a.x, a.y};
+        delay_mac(t, d.g_tile, in);
+        in[0] = t[0]; in[1] = t[1];
+    }
+}
+// SINGLE: one tile covers the chunk -- the line is the entry state and the term loop runs here; otherwise the kernel streams the
+// scratch buffer k_delay_local left and carries none of the term loop's registers
+template <bool SINGLE>
+__global__ __launch_bounds__(kThreads) void k_delay_apply(const DelayDesc* __restrict__ descs) {
+    const DelayDesc& d = descs[blockIdx.y];
+    const uint32_t gid = blockIdx.x * kThreads + threadIdx.x, lanes = d.lanes;
+    if (gid >= d.n_tiles * lanes) return;
+    const uint32_t tile = gid / lanes, j = gid - tile * lanes, M = d.frames, D = d.D, T = d.T;
+    constexpr bool single = SINGLE;
+    uint32_t li = d.pos + j;               // the lane's own word of the line
+    if (li >= D) li -= D;
+    double ul = 0.0, ur = 0.0;
+    if (!single) {
+        const d2v w = gload_d2(d.carry + 2u * (size_t)gid);
+        ul = w.x; ur = w.y;
+    } else if (li < d.filled) {
+        const d2v w = gload_d2(d.line + 2u * (size_t)li);
+        ul = w.x; ur = w.y;
+    }
+    uint32_t m = tile * T * D + j;
+#pragma unroll 1
+    for (uint32_t i = 0; i < T && m < M; i += 4u, m += 4u * D) {
+        float2 x[4];
+        if (single) {
+            delay_sum4(d, m, x);
+        } else {
+#pragma unroll
+            for (uint32_t q = 0; q < 4; ++q) x[q] = m + q * D < M ? gload2(d.x + m + q * D) : make_float2(0.f, 0.f);
+        }
+#pragma unroll
+        for (uint32_t q = 0; q < 4; ++q) {
+            const uint32_t mq = m + q * D;
+            if (mq >= M) break;
+            gstore2(d.out + mq, delay_frame(d, x[q], ul, ur));
+            // one of the chunk's last D frames: what the next chunk / block pull enters this lane with
+            if (mq + D >= M) gstore_d2(d.line + 2u * (size_t)li, ul, ur);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // k_sample_loop: out[m] = sample[(t0 + m) % len]   (extensions.rs:331-341)
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kThreads) void k_sample_loop(const LoopDesc* __restrict__ descs, uint32_t M) {
@@ -5595,6 +5746,20 @@ void launch_eq_carry(const EqDesc* d, int n, hipStream_t s) {
 void launch_eq_apply(const EqDesc* d, int n, uint32_t max_tiles, hipStream_t s) {
     for (int o = 0; o < n && max_tiles; o += kMaxGridY)
         hipLaunchKernelGGL(k_eq_apply, dim3(max_tiles, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
+}
+void launch_delay_local(const DelayDesc* d, int n, uint32_t max_groups, hipStream_t s) {
+    for (int o = 0; o < n && max_groups; o += kMaxGridY)
+        hipLaunchKernelGGL(k_delay_local, dim3(max_groups, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
+}
+void launch_delay_carry(const DelayDesc* d, int n, uint32_t max_groups, hipStream_t s) {
+    for (int o = 0; o < n && max_groups; o += kMaxGridY)
+        hipLaunchKernelGGL(k_delay_carry, dim3(max_groups, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
+}
+void launch_delay_apply(const DelayDesc* d, int n, uint32_t max_groups, bool single, hipStream_t s) {
+    for (int o = 0; o < n && max_groups; o += kMaxGridY) {
+        if (single) hipLaunchKernelGGL(k_delay_apply<true>, dim3(max_groups, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
+        else hipLaunchKernelGGL(k_delay_apply<false>, dim3(max_groups, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
+    }
 }
 void launch_sample_loop(const LoopDesc* d, int n, uint32_t frames, hipStream_t s) {
     if (!n || !frames) return;

@@ -106,6 +106,7 @@ struct AdsrCall { std::string name; float gain, angle, wet; std::string floww; b
 struct BandCall { std::string name; float gain, angle, wet, lo, hi; bool pass; };
 struct CompCall { std::string name; float gain, angle, wet, threshold_db, ratio, attack_ms, release_ms, knee_db, makeup_db; };
 struct EqCall { std::string name; float gain, angle, wet; int kind; float freq_hz, q, gain_db; };
+struct DelayCall { std::string name; float gain, angle, wet, time_ms, feedback, cross; };
 
 using Triple = std::tuple<std::string, std::string, std::string>;
 
@@ -223,6 +224,7 @@ int do_refresh(td_state* s, const std::string& contents) {
     std::vector<BandCall> bandpasses;
     std::vector<CompCall> compressors;
     std::vector<EqCall> eqs;
+    std::vector<DelayCall> delays;
     size_t cs = s->cs, render_sr = s->render_sr, bd = s->bd;
     // std::mem::take (state.rs:79-80): the locals start from the previous values, the State's own fields are left
     // EMPTY until the script has run (state.rs:169-170) -- so they stay empty when the script fails
@@ -394,6 +396,18 @@ int do_refresh(td_state* s, const std::string& contents) {
                 fnum(c.q) + "," + fnum(c.gain_db) + ")\n";
         return Value::nil();
     });
+    lua.set_function("add_delay", [&](const std::vector<Value>& a) {   // this engine's own vertex (termdaw_amd.h td_graph_add_delay)
+        const char* f = "add_delay";
+        delays.push_back({to_str(f, a, 0), to_f32(f, a, 1), to_f32(f, a, 2), to_f32(f, a, 3), to_f32(f, a, 4), to_f32(f, a, 5), to_f32(f, a, 6)});
+        auto& c = delays.back();
+        // (out-of-range parameters are rejected here, where the line is known)
+        if (!(c.time_ms >= 1.0f && c.time_ms <= 2000.0f)) throw LuaError{"add_delay: time_ms must lie in [1, 2000] ms"};
+        if (!(c.feedback >= 0.0f && c.feedback <= 0.98f)) throw LuaError{"add_delay: feedback must lie in [0, 0.98]"};
+        if (!(c.cross >= 0.0f && c.cross <= 1.0f)) throw LuaError{"add_delay: cross must lie in [0, 1]"};
+        dump += std::string(f) + "(\"" + c.name + "\"," + fnum(c.gain) + "," + fnum(c.angle) + "," + fnum(c.wet) + "," + fnum(c.time_ms) + "," +
+                fnum(c.feedback) + "," + fnum(c.cross) + ")\n";
+        return Value::nil();
+    });
     lua.set_function("connect", [&](const std::vector<Value>& a) {
         edges.push_back({to_str("connect", a, 0), to_str("connect", a, 1)});
         dump += "connect(\"" + edges.back().first + "\",\"" + edges.back().second + "\")\n";
@@ -512,6 +526,8 @@ int do_refresh(td_state* s, const std::string& contents) {
             return 0;
     for (auto& c : eqs)
         if (!td_graph_add_eq(s->g, c.name.c_str(), c.gain, c.angle, c.wet, c.kind, c.freq_hz, c.q, c.gain_db)) return 0;
+    for (auto& c : delays)
+        if (!td_graph_add_delay(s->g, c.name.c_str(), c.gain, c.angle, c.wet, c.time_ms, c.feedback, c.cross)) return 0;
     for (auto& e : edges) td_graph_connect(s->g, e.first.c_str(), e.second.c_str());   // failures only warn (state.rs:459)
     td_graph_set_output(s->g, s->output_vertex.c_str());
     if (!td_graph_check(s->g)) return fail("TermDaw: graph check failed! (" + g_error + ")");
