@@ -207,6 +207,57 @@ int td_graph_add_delay(td_graph* g, const char* name, float gain, float angle, f
 /* Host only, no GPU: the delay vertex' constants at rate sr -- out[0 .. 3] = D, gs, gc, Hecho as the engine uses them.  The same
  * range checks as td_graph_add_delay. */
 int td_delay_params(size_t sr, float time_ms, float feedback, float cross, double out[4]);
+/* A saturator vertex: an oversampled waveshaper -- THIS ENGINE'S OWN: no reference counterpart (the reference reaches drive and
+ * clipping only through LV2 plugins, add_lv2fx, which this engine parses and drops).  The vertex sums its inputs
+ * like every input vertex (sum_inputs, extensions.rs:310-319), processes, mixes with `wet` by the reference's f32 lerp, then pan
+ * and gain like every vertex (extensions.rs:262-263).
+ *   Constants, once on the host in f64:  Z = 32,  R = oversample,  L = 2 Z R + 1.
+ *   Prototype low-pass, a 4-term Blackman-Harris windowed sinc; t = k - Z R, fc = (0.5 - 2 / Z) / R cycles per oversampled sample:
+ *     s[k] = 2 fc at t = 0, else sin(2 pi fc t) / (pi t)
+ *     w[k] = 0.35875 - 0.48829 cos(2 pi k / (L - 1)) + 0.14128 cos(4 pi k / (L - 1)) - 0.01168 cos(6 pi k / (L - 1))
+ *     h = s w / sum(s w)
+ *     The taps do not depend on the sample rate: in units of sr the pass band reaches 0.375, the response is -1 dB at 0.417 and
+ *     the stop band (<= -105 dB) starts at 0.5.
+ *   g_in = 10^(drive_db / 20),  g_out = 10^(out_db / 20),  fb = f(bias)   (f32 parameters widened)
+ *   Shapers f (IEEE operations only):  hard  min(max(u, -1), 1);   cubic  1.5 u - ((0.5 u) u) u for |u| < 1, else sign(u);
+ *     soft  u / (1 + |u|).  Lipschitz constants Lf = 1, 1.5, 1.
+ *   Pipeline per channel, in f64 on the f32 summed input x, with no FMA contraction and every sum accumulated from acc = 0.0 in
+ *   ascending index:
+ *     xs[n] = x[n] if finite, else 0; frames before time 0 are 0
+ *     up-sampling, polyphase (no zero-stuffed terms):  v[n R + r] = sum_{j = 0 .. J_r} (R h[r + j R]) xs[n - j],
+ *         J_0 = 2 Z, J_r = 2 Z - 1 for r > 0
+ *     shaper:      w[m] = f(g_in v[m] + bias) - fb
+ *     decimation:  y[n] = sum_{k = 0 .. L - 1} h[k] w[n R - k]
+ *     output:      p[n] = (float)(g_out y[n])
+ *   LATENCY: the two linear-phase filters delay by exactly 2 Z = 64 frames, so the dry leg of the lerp is delayed to match:
+ *     xd[n] = x[n - 64] (raw f32, zeros before time 0);  out = xd + wet * (p - xd) in f32 (adsr.rs:42); then pan and gain.
+ *     The vertex therefore delays its signal by 64 frames (td_saturator_params returns it); nothing compensates for that
+ *     elsewhere in the graph.  A non-finite x[n] reaches the output through xd only, at frame n + 64.
+ *   oversample = 1 has no filters, no latency and no state:  p = (float)(g_out (f(g_in x + bias) - fb)), a non-finite x gives
+ *     p = x;  out = x + wet * (p - x).
+ *   wet < 0.0001: the summed input passes through untouched (a plain k_sum launch) and the line stays as it is.
+ * State (oversample > 1): the line, the last 4 Z = 128 raw input frames (64 for the decimator's reach, 64 more for the up-sampler
+ * under it), kept as two halves used alternately: 2 KB of device memory (counted by td_graph_device_bytes, allocated when the
+ * vertex is first rendered); silent at time 0, carried between consecutive block pulls and between the chunks of a render,
+ * restarted from silence by td_graph_set_time / td_graph_change_time / td_graph_reset.  A render ends where the project ends: no
+ * tail is appended.
+ * Ranges, rejected with a td_last_error that names the parameter (NaN included): kind 0 .. 2, oversample 1 | 2 | 4 | 8, drive_db
+ * [-24, 48], bias [-1, 1], out_db [-48, 24].  `wet` is clamped to [0, 1].
+ * Under "band_mode" 2 / "sine_mode" 2 the estimate is carried through a saturator vertex at the gain (1 - wet) + wet Hsat,
+ * Hsat = g_out Hdown Lf g_in Hup with Hup = sqrt(sum_r max_w |U_r|^2) over the up-sampler's branches U_r = R h[r::R] and Hdown
+ * the same over the decimator's G_r = h[r::R] (Hup Hdown = 1.000005; oversample = 1: Hsat = g_out Lf g_in): vertices upstream
+ * keep their scan / fast forms.
+ * Not part of the vertex: tanh / exp shapers (not IEEE-exact on the device), a tail past the project's end, latency
+ * compensation across the graph, per-band drive. */
+enum { TD_SAT_HARD = 0, TD_SAT_CUBIC = 1, TD_SAT_SOFT = 2 };
+int td_graph_add_saturator(td_graph* g, const char* name, float gain, float angle, float wet, int kind, float drive_db, float bias,
+                           float out_db, int oversample);
+/* Host only, no GPU: the engine's own prototype taps h[0 .. L - 1], L = 64 oversample + 1.  Writes min(L, cap) of them (taps may
+ * be null) and returns L; 0 for an oversample that is not 1, 2, 4 or 8. */
+int td_saturator_taps(int oversample, double* taps, size_t cap);
+/* Host only, no GPU: the saturator vertex' constants -- out[0 .. 5] = g_in, g_out, f(bias), the latency in frames, Lf, Hsat as
+ * the engine uses them.  The same range checks as td_graph_add_saturator. */
+int td_saturator_params(int kind, int oversample, float drive_db, float bias, float out_db, double out[6]);
 int td_graph_connect(td_graph* g, const char* a, const char* b);          /* graph.rs:80-96 (+58-78) */
 int td_graph_set_output(td_graph* g, const char* vertex);                 /* graph.rs:141-148 */
 int td_graph_check(const td_graph* g);                                    /* check_graph graph.rs:150-174 */
@@ -403,6 +454,8 @@ size_t td_cached_memory_bytes(void);
  *     = every look-back poll times out and predecessors are recomputed; tests/test_gpu_band_scan.py) /
  *   debug.band_serial 0|1 (1: every band-pass vertex on the serial kernel; tests/test_gpu_parity.py) /
  *   debug.delay_tile 8|16|32|64 (steps per tile of the delay vertex' scan; tests/test_gpu_delay.py) /
+ *   debug.sat_tile 128|256|384 (output frames per workgroup of the saturator vertex' k_sat; 256 is provisional: nothing was
+ *     timed; tests/test_gpu_saturator.py) /
  *   debug.band_quick n, debug.band_medium n, debug.band_short n, debug.band_warmup n, debug.band_live_exp n, debug.band_depth n
  *     (the exact band-pass' speculative warm-up lengths in 1 / gamma frames and its liveness thresholds: speed only, the
  *     bit-wise check and repair of k_band_fix keep every result exact; tests/test_gpu_quirks.py, tools/band_*_sweep.py).

@@ -70,6 +70,9 @@ SIGNATURES = {
     "td_eq_coefficients": (_i32, [_i32, _sz, _f32, _f32, _f32, C.POINTER(C.c_double)]),
     "td_graph_add_delay": (_i32, [_vp, _cp, _f32, _f32, _f32, _f32, _f32, _f32]),
     "td_delay_params": (_i32, [_sz, _f32, _f32, _f32, C.POINTER(C.c_double)]),
+    "td_graph_add_saturator": (_i32, [_vp, _cp, _f32, _f32, _f32, _i32, _f32, _f32, _f32, _i32]),
+    "td_saturator_taps": (_i32, [_i32, C.POINTER(C.c_double), _sz]),
+    "td_saturator_params": (_i32, [_i32, _i32, _f32, _f32, _f32, C.POINTER(C.c_double)]),
     "td_graph_connect": (_i32, [_vp, _cp, _cp]),
     "td_graph_set_output": (_i32, [_vp, _cp]),
     "td_graph_check": (_i32, [_vp]),
@@ -289,6 +292,36 @@ def delay_params(sr, time_ms, feedback, cross):
     return int(out[0]), float(out[1]), float(out[2]), float(out[3])
 
 
+SAT_KINDS = ("hard", "cubic", "soft")   # TD_SAT_* in order
+
+
+def sat_kind(kind):
+    """A kind name of SAT_KINDS (or an index) as the TD_SAT_* integer."""
+    if isinstance(kind, str):
+        if kind not in SAT_KINDS:
+            raise ValueError("saturator kind %r: one of %s" % (kind, ", ".join(SAT_KINDS)))
+        return SAT_KINDS.index(kind)
+    return int(kind)
+
+
+def saturator_taps(oversample):
+    """The saturator vertex' prototype low-pass at oversampling factor R (host only): the engine's own 2 * 32 * R + 1 taps as
+    a float64 array."""
+    n = lib().td_saturator_taps(int(oversample), None, 0)
+    _check(n)
+    out = (C.c_double * n)()
+    _check(lib().td_saturator_taps(int(oversample), out, n))
+    return np.array(out[:], np.float64)
+
+
+def saturator_params(kind, oversample, drive_db, bias, out_db):
+    """The saturator vertex' constants (host only), exactly as the engine uses them: (g_in, g_out, f(bias), latency in frames,
+    Lf, Hsat) -- Hsat the gain the guard carries its estimate through the wet path at."""
+    out = (C.c_double * 6)()
+    _check(lib().td_saturator_params(sat_kind(kind), int(oversample), drive_db, bias, out_db, out))
+    return float(out[0]), float(out[1]), float(out[2]), int(out[3]), float(out[4]), float(out[5])
+
+
 def loudness_filters(sr):
     """The meter's filters at rate sr (host only): (shelf (b, a), high-pass (b, a)) as float64 arrays with a[0] = 1, and the
     true-peak FIR as a (phases, taps) float32 array (phase 0 the unit impulse)."""
@@ -483,6 +516,11 @@ class Graph:
     def add_delay(self, name, gain, angle, wet, time_ms, feedback, cross):
         """A feedback delay (echo) vertex (this engine's own; the definition is in include/termdaw_amd.h)."""
         _check(lib().td_graph_add_delay(self.h, name.encode(), gain, angle, wet, time_ms, feedback, cross))
+
+    def add_saturator(self, name, gain, angle, wet, kind, drive_db, bias, out_db, oversample):
+        """An oversampled waveshaper vertex (this engine's own; the definition is in include/termdaw_amd.h).  kind: a name of
+        SAT_KINDS or its TD_SAT_* index; oversample: 1, 2, 4 or 8.  The vertex has a latency of 64 frames when oversample > 1."""
+        _check(lib().td_graph_add_saturator(self.h, name.encode(), gain, angle, wet, sat_kind(kind), drive_db, bias, out_db, int(oversample)))
 
     def connect(self, a, b):
         return bool(lib().td_graph_connect(self.h, a.encode(), b.encode()))

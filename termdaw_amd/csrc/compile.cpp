@@ -7,6 +7,7 @@
 #include "compile.h"
 #include "delay_math.h"
 #include "eq_math.h"
+#include "sat_math.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -26,7 +27,8 @@ const char* const kFamilyName[F_COUNT] = {"k_sample_loop", "k_sample_multi", "k_
                                            "k_master_detect", "k_master_scan", "k_master_carry", "k_master_apply",
                                            "k_comp_detect", "k_comp_carry_y1", "k_comp_env", "k_comp_carry_yl", "k_comp_apply",
                                            "k_eq_local", "k_eq_carry", "k_eq_apply",
-                                           "k_delay_local", "k_delay_carry", "k_delay_apply"};
+                                           "k_delay_local", "k_delay_carry", "k_delay_apply",
+                                           "k_sat_sum", "k_sat", "k_sat1"};
 
 
 // ------------------------------------------------------------------------------------------------
@@ -928,6 +930,13 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                     delay::params(sr, wv.delay_ms, wv.delay_feedback, wv.delay_cross, c);
                     L *= 1.0 + (double)wv.wet * c[3];
                 }
+                // a saturator's shaper is Lipschitz: the estimate goes through it at (1 - wet) + wet Hsat, Hsat = g_out Hdown Lf g_in Hup
+                // 
+                if (wv.kind == K_SATURATOR && !(wv.wet < 0.0001f)) {
+                    double c[6];
+                    sat::params(wv.sat_kind, wv.sat_oversample, wv.sat_drive_db, wv.sat_bias, wv.sat_out_db, c);
+                    L *= (1.0 - (double)wv.wet) + (double)wv.wet * c[5];
+                }
                 if (wv.kind == K_ADSR && !(wv.wet < 0.0001f)) {   // |lerp(1, level x vel, wet)| <= max(1, |level| |vel|)
                     const AdsrConfD& c = wv.conf;
                     double lv = std::max(std::max(fabs((double)c.std_vel), fabs((double)c.attack_vel)),
@@ -1472,6 +1481,14 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                     } else {
                         if (M > 0xF0000000ull) return fail("delay: chunk too long");
                         fam_v[F_DELAY_APPLY].push_back(vi);
+                    }
+                    break;
+                case K_SATURATOR:
+                    if (v.wet < 0.0001f) {
+                        fam_v[F_SUM].push_back(vi);   // the summed input passes through, the line stays
+                    } else {
+                        if (M > 0xF0000000ull || (M + g->sat_tile - 1) / g->sat_tile >= 0x100000ull) return fail("saturator: chunk too long");
+                        fam_v[v.sat_oversample == 1 ? F_SAT1 : F_SAT].push_back(vi);
                     }
                     break;
                 default: break;
@@ -2397,6 +2414,71 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                         add_launch(F_DELAY_APPLY, off + (size_t)n_multi * sizeof(DelayDesc), (int)plans.size() - n_multi, g_single | kDelaySingleBit, lv);
                     continue;
                 }
+                case F_SAT:
+                case F_SAT1: {   // the launches of the level's saturator vertices (kernels.h SatDesc)
+                    const uint32_t F = g->sat_tile, n_tiles = (uint32_t)((M + F - 1) / F);
+                    const bool filtered = fam == F_SAT, multi = filtered && M > (size_t)kSatInlineFrames;   // (multi: k_sat_sum first)
+                    std::vector<size_t> ord(vs.begin(), vs.end());   // one k_sat launch per oversampling factor
+                    std::stable_sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return g->vertices[a].sat_oversample < g->vertices[b].sat_oversample; });
+                    std::vector<SatDesc> d;
+                    std::map<int, size_t> taps_off;
+                    for (size_t vi : ord) {
+                        Vertex& v = g->vertices[vi];
+                        double c[6];
+                        sat::params(v.sat_kind, v.sat_oversample, v.sat_drive_db, v.sat_bias, v.sat_out_db, c);
+                        SatDesc x{};
+                        if (multi) {
+                            x.x = take_buffer(g);
+                            if (!x.x) return fail("termdaw_amd: out of device memory for edge buffers");
+                            level_tmp.push_back(x.x);
+                        }
+                        x.out = g->vbuf[vi];
+                        if (filtered) {
+                            x.line = take_sat_line(g, v);
+                            if (!x.line) return fail("termdaw_amd: out of device memory for a saturator line");
+                            // (a set_time since the vertex last ran: the line restarts from silence -- consumed here, like a delay's)
+                            if (v.first_pending) v.sat_total = 0;
+                            x.filled = (uint32_t)std::min<uint64_t>(v.sat_total, sat::kLine);
+                            x.parity = v.sat_parity;
+                            v.sat_total += M;
+                            v.sat_parity ^= 1u;
+                            if (!taps_off.count(v.sat_oversample)) taps_off[v.sat_oversample] = st.put(sat::taps(v.sat_oversample));
+                        }
+                        v.first_pending = false;
+                        x.k = (uint32_t)g->edges[vi].size();
+                        x.term_mode = term_mode[vi];
+                        x.frames = (uint32_t)M;
+                        x.F = F;
+                        x.n_tiles = n_tiles;
+                        x.kind = (uint32_t)v.sat_kind;
+                        x.wet = v.wet;
+                        x.g_in = c[0];
+                        x.g_out = c[1];
+                        x.bias = (double)v.sat_bias;
+                        x.fb = c[2];
+                        x.pg = make_pg(v.gain, v.angle);
+                        d.push_back(x);
+                    }
+                    off = st.put(d);
+                    for (size_t i = 0; i < ord.size(); ++i) {
+                        const size_t o = off + i * sizeof(SatDesc);
+                        ptr_field(o, offsetof(SatDesc, ins), ins_off[ord[i]]);
+                        if (filtered) ptr_field(o, offsetof(SatDesc, taps), taps_off[g->vertices[ord[i]].sat_oversample]);
+                    }
+                    if (!filtered) {
+                        add_launch(F_SAT1, off, (int)ord.size(), 0, lv);
+                        continue;
+                    }
+                    if (multi) add_launch(F_SAT_SUM, off, (int)ord.size(), 0, lv);
+                    for (size_t i = 0; i < ord.size();) {
+                        const int R = g->vertices[ord[i]].sat_oversample;
+                        size_t j = i;
+                        while (j < ord.size() && g->vertices[ord[j]].sat_oversample == R) ++j;
+                        add_launch(F_SAT, off + i * sizeof(SatDesc), (int)(j - i), sat_aux(n_tiles, F, (uint32_t)R, !multi), lv);
+                        i = j;
+                    }
+                    continue;
+                }
                 default: continue;
             }
             if (fam == F_SUM || fam == F_ADSR) {   // split at term-mode boundaries (vs is sorted by it)
@@ -2586,6 +2668,9 @@ size_t desc_size(int fam) {
         case F_DELAY_LOCAL:
         case F_DELAY_CARRY:
         case F_DELAY_APPLY: return sizeof(DelayDesc);
+        case F_SAT_SUM:
+        case F_SAT:
+        case F_SAT1: return sizeof(SatDesc);
         default: return 0;
     }
 }

@@ -15,6 +15,7 @@
 #include "devmem.h"
 #include "eq_math.h"
 #include "midi.h"
+#include "sat_math.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -571,10 +572,32 @@ double* take_delay_line(td_graph* g, Vertex& v, size_t D) {
     v.delay_total = 0;
     return p;
 }
+// The line of a saturator vertex: two halves of 128 float2 (2 KB), kept in the same list; never cleared either
+// (Vertex::sat_total says how many of its frames hold values).
+float2* take_sat_line(td_graph* g, Vertex& v) {
+    if (v.sat_line) return v.sat_line;
+    const size_t bytes = 2 * sat::kLine * sizeof(float2);
+    float2* p = nullptr;
+    if (hipMalloc(&p, bytes) != hipSuccess) return nullptr;
+    g->delay_lines.push_back({reinterpret_cast<double*>(p), bytes});
+    g->device_bytes += bytes;
+    v.sat_line = p;
+    v.sat_total = 0;
+    v.sat_parity = 0;
+    return p;
+}
+// the line a vertex would continue from in its next submission (nullptr: none -- it has none yet, or it starts afresh)
+static void* vertex_line(Vertex& v) { return v.kind == K_SATURATOR ? (void*)v.sat_line : (void*)v.delay_line; }
+static const void* carried_line(const Vertex& v) {
+    if (v.first_pending) return nullptr;
+    if (v.kind == K_DELAY && v.delay_line && v.delay_total) return v.delay_line;
+    if (v.kind == K_SATURATOR && v.sat_line && v.sat_total) return v.sat_line;
+    return nullptr;
+}
 static void free_delay_lines(td_graph* g) {
     for (auto& l : g->delay_lines) { (void)hipFree(l.first); g->device_bytes -= l.second; }
     g->delay_lines.clear();
-    for (auto& v : g->vertices) v.delay_line = nullptr;
+    for (auto& v : g->vertices) { v.delay_line = nullptr; v.sat_line = nullptr; }
 }
 float2* take_buffer(td_graph* g) {
     if (!g->free_bufs.empty()) {
@@ -919,6 +942,9 @@ static int submit_chunk(Arena& ar, ChunkBuild& cb, hipStream_t stream, ProfCtx& 
                 case F_DELAY_LOCAL: launch_delay_local((const DelayDesc*)d, L.n, L.aux, s); break;   // (likewise)
                 case F_DELAY_CARRY: launch_delay_carry((const DelayDesc*)d, L.n, L.aux, s); break;
                 case F_DELAY_APPLY: launch_delay_apply((const DelayDesc*)d, L.n, L.aux & ~kDelaySingleBit, (L.aux & kDelaySingleBit) != 0u, s); break;
+                case F_SAT_SUM: launch_sat_sum((const SatDesc*)d, L.n, L.M, s); break;   // (likewise)
+                case F_SAT: launch_sat((const SatDesc*)d, L.n, (L.aux >> 24) & 15u, L.aux & 0xFFFFFu, ((L.aux >> 20) & 15u) * 128u, (L.aux & kSatTermsBit) != 0u, s); break;
+                case F_SAT1: launch_sat1((const SatDesc*)d, L.n, L.M, s); break;
             }
         }
         li = lj;
@@ -1010,6 +1036,10 @@ static int prepare_render(td_graph* g, size_t n_blocks, int bits, bool want_pcm,
         for (size_t vi : g->order)
             if (g->vertices[vi].kind == K_DELAY && !(g->vertices[vi].wet < 0.0001f))
                 return fail("termdaw_amd: this build has no k_delay kernels: delay vertices cannot be rendered");
+    if (!(launch_sat_sum && launch_sat && launch_sat1))
+        for (size_t vi : g->order)
+            if (g->vertices[vi].kind == K_SATURATOR && !(g->vertices[vi].wet < 0.0001f))
+                return fail("termdaw_amd: this build has no k_sat kernels: saturator vertices cannot be rendered");
     const size_t bl = g->bl;
     if (bl == 0) return fail("termdaw_amd: buffer length 0");
     rp->n_blocks = n_blocks;
@@ -1114,6 +1144,7 @@ static bool starts_afresh(const td_graph* g) {
         if (v.kind == K_NORMALIZE && !v.has_init_override) return false;
         if ((v.kind == K_BAND_PASS || v.kind == K_COMPRESSOR || v.kind == K_EQ) && v.state_slot >= 0 && !v.first_pending) return false;
         if (v.kind == K_DELAY && v.delay_line && !v.first_pending) return false;
+        if (v.kind == K_SATURATOR && v.sat_line && !v.first_pending) return false;
     }
     return true;
 }
@@ -1154,14 +1185,16 @@ static int guard_begin(td_graph* g, const td_samplebank* sb, td_flowwbank* fb, s
         TD_HIP(hipMemcpyAsync(q.d_backup, g->dstate, n * sizeof(StateSlot), hipMemcpyDeviceToDevice, g->stream));
         q.have_backup = true;
     }
-    // the lines of the delay vertices that continue from what they hold (a vertex with a set_time pending reads nothing of its line)
+    // the lines of the delay and saturator vertices that continue from what they hold (a vertex with a set_time pending reads nothing
+    // of its line)
     q.lines.clear();
     size_t need = 0;
     for (size_t vi : g->order) {
         const Vertex& v = g->vertices[vi];
-        if (v.kind != K_DELAY || !v.delay_line || v.first_pending || !v.delay_total) continue;
+        const void* line = carried_line(v);
+        if (!line) continue;
         for (const auto& l : g->delay_lines)
-            if (l.first == v.delay_line) { q.lines.push_back({vi, need, l.second}); need += l.second; }
+            if ((const void*)l.first == line) { q.lines.push_back({vi, need, l.second}); need += l.second; }
     }
     if (need > q.lines_cap) {
         if (q.d_lines) (void)hipFree(q.d_lines);
@@ -1173,7 +1206,7 @@ static int guard_begin(td_graph* g, const td_samplebank* sb, td_flowwbank* fb, s
         q.lines_cap = need;
     }
     for (const auto& l : q.lines)
-        TD_HIP(hipMemcpyAsync((uint8_t*)q.d_lines + l.off, g->vertices[l.vertex].delay_line, l.bytes, hipMemcpyDeviceToDevice, g->stream));
+        TD_HIP(hipMemcpyAsync((uint8_t*)q.d_lines + l.off, vertex_line(g->vertices[l.vertex]), l.bytes, hipMemcpyDeviceToDevice, g->stream));
     return 1;
 }
 // The stream has drained: look at the verdict of the last guarded render, and do that render again with the exact kernels
@@ -1202,8 +1235,8 @@ static int guard_settle(td_graph* g) {
     if (q.have_backup && hipMemcpyAsync(g->dstate, q.d_backup, g->hstate.size() * sizeof(StateSlot), hipMemcpyDeviceToDevice, g->stream) != hipSuccess)
         ok = fail("HIP error: the guard could not restore the carried state");
     for (const auto& l : q.lines)
-        if (ok && l.vertex < g->vertices.size() && g->vertices[l.vertex].delay_line &&
-            hipMemcpyAsync(g->vertices[l.vertex].delay_line, (const uint8_t*)q.d_lines + l.off, l.bytes, hipMemcpyDeviceToDevice, g->stream) != hipSuccess)
+        if (ok && l.vertex < g->vertices.size() && vertex_line(g->vertices[l.vertex]) &&
+            hipMemcpyAsync(vertex_line(g->vertices[l.vertex]), (const uint8_t*)q.d_lines + l.off, l.bytes, hipMemcpyDeviceToDevice, g->stream) != hipSuccess)
             ok = fail("HIP error: the guard could not restore a delay line");
     g->state_dev_dirty = true;
     if (ok) ok = graph_render_chunks(g, q.sb, q.fb, q.n_blocks, q.is_scan, q.bits, q.advance, q.scan_t0, q.want_pcm);
@@ -1237,6 +1270,8 @@ void HostSnapshot::take(const td_graph* g, const td_flowwbank* fb) {
         const Vertex& x = g->vertices[i];
         v[i].loop_t = x.loop_t;
         v[i].delay_total = x.delay_total;
+        v[i].sat_total = x.sat_total;
+        v[i].sat_parity = x.sat_parity;
         v[i].has_init_override = x.has_init_override;
         v[i].peak_known = x.peak_known;
         v[i].first_pending = x.first_pending;
@@ -1253,6 +1288,8 @@ void HostSnapshot::put(td_graph* g, td_flowwbank* fb) const {
         Vertex& x = g->vertices[i];
         x.loop_t = v[i].loop_t;
         x.delay_total = v[i].delay_total;
+        x.sat_total = v[i].sat_total;
+        x.sat_parity = v[i].sat_parity;
         x.has_init_override = v[i].has_init_override;
         x.peak_known = v[i].peak_known;
         x.first_pending = v[i].first_pending;
@@ -1332,6 +1369,7 @@ static int graph_set_time_impl(td_graph* g, size_t time) {   // graph.rs:123-128
                 }
                 break;
             case K_DELAY:   // the line restarts from zero: the next submission reads none of its words
+            case K_SATURATOR:
                 v.first_pending = true;
                 break;
             default: break;
@@ -1893,6 +1931,41 @@ int td_delay_params(size_t sr, float time_ms, float feedback, float cross, doubl
     if (!out) return fail("delay_params: out is null");
     if (!delay_check(sr, time_ms, feedback, cross)) return 0;
     delay::params(sr, time_ms, feedback, cross, out);
+    return 1;
+}
+
+// This engine's own waveshaper vertex (no reference counterpart; the definition is in include/termdaw_amd.h).
+static int sat_check(int kind, int oversample, float drive_db, float bias, float out_db) {
+    if (!(kind >= 0 && kind <= 2)) return fail("saturator: kind must be 0 (hard), 1 (cubic) or 2 (soft)");
+    if (!sat::oversample_ok(oversample)) return fail("saturator: oversample must be 1, 2, 4 or 8");
+    if (!(drive_db >= -24.0f && drive_db <= 48.0f)) return fail("saturator: drive_db must lie in [-24, 48] dB");
+    if (!(bias >= -1.0f && bias <= 1.0f)) return fail("saturator: bias must lie in [-1, 1]");
+    if (!(out_db >= -48.0f && out_db <= 24.0f)) return fail("saturator: out_db must lie in [-48, 24] dB");
+    return 1;
+}
+int td_graph_add_saturator(td_graph* g, const char* name, float gain, float angle, float wet, int kind, float drive_db, float bias,
+                           float out_db, int oversample) {
+    if (!sat_check(kind, oversample, drive_db, bias, out_db)) return 0;
+    Vertex& v = add_vertex(g, name, gain, angle, wet, K_SATURATOR);
+    v.sat_kind = kind;
+    v.sat_oversample = oversample;
+    v.sat_drive_db = drive_db;
+    v.sat_bias = bias;
+    v.sat_out_db = out_db;
+    v.first_pending = true;   // (the line, once it exists, is read from the first frame the vertex itself has written)
+    return 1;
+}
+int td_saturator_taps(int oversample, double* taps, size_t cap) {
+    if (!sat::oversample_ok(oversample)) return fail("saturator_taps: oversample must be 1, 2, 4 or 8");
+    const std::vector<double>& h = sat::taps(oversample);
+    if (taps)
+        for (size_t i = 0; i < h.size() && i < cap; ++i) taps[i] = h[i];
+    return (int)h.size();
+}
+int td_saturator_params(int kind, int oversample, float drive_db, float bias, float out_db, double out[6]) {
+    if (!out) return fail("saturator_params: out is null");
+    if (!sat_check(kind, oversample, drive_db, bias, out_db)) return 0;
+    sat::params(kind, oversample, drive_db, bias, out_db, out);
     return 1;
 }
 
@@ -2654,7 +2727,7 @@ static std::vector<OptionRef> option_table(td_graph* g) {
         {"debug.inline_adsr", 0, &g->inline_adsr}, {"debug.spec_normalize", 0, &g->spec_normalize},
         {"debug.single_pass_normalize", 0, &g->single_pass_normalize}, {"debug.fuse_normalize", 0, &g->fuse_normalize},
         {"debug.table_cache", 0, &g->table_cache}, {"debug.band_serial", 0, &g->band_serial}, {"debug.band_chain", 0, &g->band_chain}, {"debug.band_scan_nf", 1, &g->band_scan_nf},
-        {"debug.delay_tile", 2, &g->delay_tile},
+        {"debug.delay_tile", 2, &g->delay_tile}, {"debug.sat_tile", 2, &g->sat_tile},
         {"debug.band_quick", 2, &g->band_quick}, {"debug.band_short", 2, &g->band_short}, {"debug.band_medium", 2, &g->band_medium},
         {"debug.band_warmup", 2, &g->band_warmup}, {"debug.band_depth", 2, &g->band_depth},
         {"debug.stem_taps", 2, &g->stem_taps},
@@ -2692,6 +2765,11 @@ int td_graph_set_option(td_graph* g, const char* key, long value) {
     if (k == "debug.delay_tile") {
         if (value != 8 && value != 16 && value != 32 && value != 64) return fail("debug.delay_tile must be 8, 16, 32 or 64");
         g->delay_tile = (unsigned)value;
+        return 1;
+    }
+    if (k == "debug.sat_tile") {
+        if (value != 128 && value != 256 && value != 384) return fail("debug.sat_tile must be 128, 256 or 384");
+        g->sat_tile = (unsigned)value;
         return 1;
     }
     if (k == "debug.band_live_exp") { g->band_live_thr = value >= 38 ? 0.0f : powf(10.0f, -(float)value); return 1; }

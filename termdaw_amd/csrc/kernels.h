@@ -319,6 +319,35 @@ struct DelayDesc {
     PanGain pg;
 };
 
+// A saturator vertex (k_sat_sum / k_sat<R> / k_sat1; the definition is in include/termdaw_amd.h at
+// td_graph_add_saturator): polyphase up-sampling by R, a memoryless shaper at R x sr, a linear-phase decimator -- all in f64 on
+// the f32 summed input, every output frame a pure function of the last 128 input frames.  One workgroup owns a tile of F output
+// frames: the tile's raw x with 128 frames of halo in LDS, w for (F + 64) R oversampled samples in LDS as f64, phase-major
+// (w[channel][phase][frame]), one barrier, then the decimation, the lerp against x delayed by 64 frames, pan / gain.
+// The line holds the last 128 raw input frames in two halves of 128 float2, used alternately: a launch reads half `parity`
+// (its first tile's halo; only the `filled` most recent frames hold values, the others read as 0) and its last tile writes half
+// parity ^ 1, so no tile reads what another writes.  line[h][i] is the frame 128 - i back from the chunk's start.
+// A chunk of at most kSatInlineFrames frames -- every block pull -- is ONE launch: k_sat in an instantiation of its own
+// (launch_sat's `terms`) that runs the term loop itself over each tile and its halo; otherwise k_sat_sum leaves the summed input
+// in `x` first and k_sat streams it.  R = 1 (k_sat1) has no
+// filters, no line and no LDS: one launch with the term loop inside.
+struct SatDesc {
+    const InTerm* ins;      // k input terms (kinds 0 .. 4), in connect() order
+    float2* x;              // [frames] the summed input (two-launch form; null in the one-launch form)
+    float2* out;
+    float2* line;           // [2][128] carried across chunks / block pulls (R > 1)
+    const double* taps;     // [2 Z R + 1] the prototype h (R > 1); the up-sampler's R h is formed in the kernel (exact)
+    uint32_t k, term_mode, frames;
+    uint32_t F;             // output frames per tile (even, >= 128)
+    uint32_t n_tiles;       // ceil(frames / F)
+    uint32_t filled;        // min(frames the vertex has run since its line restarted, 128)
+    uint32_t parity;        // the half of the line this launch reads
+    uint32_t kind;          // TD_SAT_*
+    float wet;
+    double g_in, bias, fb, g_out;
+    PanGain pg;
+};
+
 // sample_loop_gen (extensions.rs:331-341): out[m] = sample[(t0 + m) % len]
 struct LoopDesc {
     const float2* sample;
@@ -768,6 +797,17 @@ constexpr uint32_t kDelaySingleBit = 0x80000000u;
 __attribute__((weak)) void launch_delay_local(const DelayDesc* d, int n_desc, uint32_t max_groups, hipStream_t s);
 __attribute__((weak)) void launch_delay_carry(const DelayDesc* d, int n_desc, uint32_t max_groups, hipStream_t s);
 __attribute__((weak)) void launch_delay_apply(const DelayDesc* d, int n_desc, uint32_t max_groups, bool single, hipStream_t s);
+// Weak for the same reason: a level's saturator vertices.  launch_sat_sum: grid.x from `frames`; launch_sat: the vertices of ONE
+// oversampling factor R (2 | 4 | 8), grid.x = n_tiles, F output frames per tile (every descriptor's), `terms`: the instantiation
+// with the term loop inside.  A launch's aux packs these: sat_aux().
+constexpr uint32_t kSatTermsBit = 0x80000000u;
+constexpr uint32_t kSatInlineFrames = 4096;   // chunks up to here take the one-launch form (the halo's terms are evaluated twice)
+inline uint32_t sat_aux(uint32_t n_tiles, uint32_t F, uint32_t R, bool terms) {
+    return n_tiles | ((F / 128u) << 20) | (R << 24) | (terms ? kSatTermsBit : 0u);
+}
+__attribute__((weak)) void launch_sat_sum(const SatDesc* d, int n_desc, uint32_t frames, hipStream_t s);
+__attribute__((weak)) void launch_sat(const SatDesc* d, int n_desc, uint32_t R, uint32_t n_tiles, uint32_t F, bool terms, hipStream_t s);
+__attribute__((weak)) void launch_sat1(const SatDesc* d, int n_desc, uint32_t frames, hipStream_t s);
 void launch_sinf(const float* in, float* out, uint32_t n, int exact, hipStream_t s);   // out[i] = sin_glibc(in[i]) (exact) or sin_any(in[i])
 void launch_debug_verify(const uint32_t* p, uint32_t n_words, const uint32_t* seg_sums, uint32_t* report, hipStream_t s);   // (TD_DEBUG_SYNC & 16)
 void launch_sample_loop(const LoopDesc* d, int n_desc, uint32_t frames, hipStream_t s);

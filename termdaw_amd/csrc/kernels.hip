@@ -2240,6 +2240,142 @@ __global__ __launch_bounds__(kThreads) void k_delay_apply(const DelayDesc* __res
 }
 
 // ------------------------------------------------------------------------------------------------
+// k_sat_sum / k_sat<R> / k_sat1: the saturator vertex (kernels.h SatDesc).  No reference counterpart; the
+// definition is the header's (td_graph_add_saturator): v = up-sampled x, w = f(g_in v + bias) - f(bias), y = decimated w, all in
+// f64 with every sum from 0.0 in ascending index -- each output on its own, so the tiling re-associates nothing.
+// ------------------------------------------------------------------------------------------------
+constexpr uint32_t kSatLat = 64u, kSatHalo = 128u;   // 2 Z and 4 Z frames (sat_math.h)
+typedef const TD_CONST double* SatTaps;              // wave-uniform reads: scalar loads
+// the shapers: IEEE operations only, in sat_math.h's order
+TD_DEV double sat_shape(uint32_t kind, double u) {
+    if (kind == 0u) return fmin(fmax(u, -1.0), 1.0);
+    if (kind == 1u) return fabs(u) < 1.0 ? 1.5 * u - ((0.5 * u) * u) * u : copysign(1.0, u);
+    return u / (1.0 + fabs(u));
+}
+// the summed input, materialised once for the tiles' halos: k_sum's frame mapping, identity epilogue
+__global__ __launch_bounds__(kThreads) void k_sat_sum(const SatDesc* __restrict__ descs) {
+    const SatDesc& d = descs[blockIdx.y];
+    const uint32_t M = d.frames, m0 = blockIdx.x * kTileFrames + 2u * threadIdx.x, m1 = m0 + kTileFrames / 2;
+    if (blockIdx.x * kTileFrames >= M) return;
+    float4 a0, a1;
+    sum_inputs_pairs(d.ins, d.k, d.term_mode, m0, m1, M, a0, a1);
+    store_pair(d.x, m0, M, a0);
+    store_pair(d.x, m1, M, a1);
+}
+// R = 1: p = (float)(g_out (f(g_in x + bias) - f(bias))), a non-finite x is its own p; no filters, no latency, no state
+__global__ __launch_bounds__(kThreads) void k_sat1(const SatDesc* __restrict__ descs) {
+    const SatDesc& d = descs[blockIdx.y];
+    const uint32_t M = d.frames, m0 = blockIdx.x * kTileFrames + 2u * threadIdx.x, m1 = m0 + kTileFrames / 2;
+    if (blockIdx.x * kTileFrames >= M) return;
+    float4 a0, a1;
+    sum_inputs_pairs(d.ins, d.k, d.term_mode, m0, m1, M, a0, a1);
+    auto one = [&](float x) {
+        const float p = delay_finite(x) ? (float)(d.g_out * (sat_shape(d.kind, d.g_in * (double)x + d.bias) - d.fb)) : x;
+        return x + d.wet * (p - x);
+    };
+    auto four = [&](float4 a) { return epilogue4(make_float4(one(a.x), one(a.y), one(a.z), one(a.w)), d.pg); };
+    store_pair(d.out, m0, M, zero_tail(four(a0), m0, M));
+    store_pair(d.out, m1, M, zero_tail(four(a1), m1, M));
+}
+// TERMS: the term loop runs here, over the tile and its halo (a short chunk -- every block pull: one launch); otherwise the kernel
+// streams the buffer k_sat_sum left and carries none of the term loop's registers.  LDS: float2 xs[F + 128] (raw x; index i =
+// tile frame i - 128), then double w[2][R][F + 64] (index i = tile frame i - 64).
+template <int R, bool TERMS>
+__global__ __launch_bounds__(kThreads) void k_sat(const SatDesc* __restrict__ descs) {
+    extern __shared__ __attribute__((aligned(16))) char sat_lds[];
+    const SatDesc& d = descs[blockIdx.y];
+    const uint32_t tile = blockIdx.x;
+    if (tile >= d.n_tiles) return;
+    const uint32_t tid = threadIdx.x, F = d.F, M = d.frames, t0 = tile * F, FW = F + kSatLat, NX = F + kSatHalo;
+    float2* xs = reinterpret_cast<float2*>(sat_lds);
+    double* w = reinterpret_cast<double*>(sat_lds + (size_t)NX * sizeof(float2));
+    const SatTaps h = (SatTaps)(const TD_CONST char*)d.taps;
+    // ---- the tile's raw x and its halo: the chunk's first tile takes the halo from the line (a frame at or beyond `filled` back is 0)
+    auto from_line = [&](uint32_t i) { return kSatHalo - i <= d.filled ? gload2(d.line + d.parity * kSatHalo + i) : make_float2(0.f, 0.f); };
+    if (TERMS) {
+        // one aligned frame pair per thread: F + 128 <= 2 kThreads; wave 0 holds exactly the halo's 64 pairs
+        const uint32_t i = 2u * tid;
+        if (i < NX) {
+            if (t0 + i >= kSatHalo) {
+                float4 a0, a1;
+                sum_inputs_pairs(d.ins, d.k, d.term_mode, t0 + i - kSatHalo, (M + 1u) & ~1u, M, a0, a1);   // (no second pair: a frame at M or beyond is 0)
+                xs[i] = make_float2(a0.x, a0.y);
+                xs[i + 1u] = make_float2(a0.z, a0.w);
+            } else {
+                xs[i] = from_line(i);
+                xs[i + 1u] = from_line(i + 1u);
+            }
+        }
+    } else {
+        for (uint32_t i = tid; i < kSatHalo; i += kThreads) xs[i] = tile == 0u ? from_line(i) : gload2(d.x + (t0 - kSatHalo + i));
+        for (uint32_t i = tid; i < F; i += kThreads) xs[kSatHalo + i] = t0 + i < M ? gload2(d.x + (t0 + i)) : make_float2(0.f, 0.f);
+    }
+    __syncthreads();
+    // ---- the chunk's last tile leaves the last 128 frames of (old line ++ chunk) in the line's other half
+    if (tile + 1u == d.n_tiles)
+        for (uint32_t i = tid; i < kSatHalo; i += kThreads) gstore2(d.line + (d.parity ^ 1u) * kSatHalo + i, xs[M - t0 + i]);
+    // ---- up-sampling and shaper: lane = frame, every phase of it -- a wave's LDS reads are consecutive words, the taps uniform
+    for (uint32_t i = tid; i < FW && t0 + i < M + kSatLat; i += kThreads) {   // (w of a frame at or beyond M is never read)
+        double al[R], ar[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) { al[r] = 0.0; ar[r] = 0.0; }
+        const float2* xp = xs + i + kSatLat;
+#pragma unroll 2
+        for (uint32_t j = 0; j < kSatLat; ++j) {
+            const float2 x = xp[-(int)j];
+            const double xl = delay_finite(x.x) ? (double)x.x : 0.0, xr = delay_finite(x.y) ? (double)x.y : 0.0;
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const double c = (double)R * h[j * R + r];
+                al[r] = al[r] + c * xl;
+                ar[r] = ar[r] + c * xr;
+            }
+        }
+        {   // j = 2 Z: phase 0 alone has the tap
+            const float2 x = xp[-(int)kSatLat];
+            const double c = (double)R * h[kSatLat * R];
+            al[0] = al[0] + c * (delay_finite(x.x) ? (double)x.x : 0.0);
+            ar[0] = ar[0] + c * (delay_finite(x.y) ? (double)x.y : 0.0);
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            w[(size_t)r * FW + i] = sat_shape(d.kind, d.g_in * al[r] + d.bias) - d.fb;
+            w[(size_t)(R + r) * FW + i] = sat_shape(d.kind, d.g_in * ar[r] + d.bias) - d.fb;
+        }
+    }
+    __syncthreads();
+    // ---- decimation in ascending k: k = 0 is phase 0 of the frame itself; then, g frames back, phases R - 1 .. 1 (k = (g - 1) R
+    // + 1 ..) and phase 0 (k = g R).  Then the lerp against x delayed by 64 frames, pan and gain, 16-byte stores by the even lanes.
+    for (uint32_t b = 0; b < F; b += kThreads) {   // (uniform trip count: the shuffle below takes every lane)
+        const uint32_t i = b + tid, n = t0 + i;
+        float2 o = make_float2(0.f, 0.f);
+        if (i < F && n < M) {
+            const double* wl = w + i + kSatLat;
+            const double* wr = wl + (size_t)R * FW;
+            double yl = 0.0, yr = 0.0;
+            { const double c = h[0]; yl = yl + c * wl[0]; yr = yr + c * wr[0]; }
+#pragma unroll 2
+            for (uint32_t g = 1; g <= kSatLat; ++g) {
+#pragma unroll
+                for (int s = 1; s < R; ++s) {
+                    const double c = h[(g - 1u) * R + s];
+                    yl = yl + c * wl[(size_t)(R - s) * FW - g];
+                    yr = yr + c * wr[(size_t)(R - s) * FW - g];
+                }
+                const double c = h[g * R];
+                yl = yl + c * wl[-(int)g];
+                yr = yr + c * wr[-(int)g];
+            }
+            const float2 xd = xs[i + kSatLat];
+            const float pl = (float)(d.g_out * yl), pr = (float)(d.g_out * yr);
+            o = epilogue(make_float2(xd.x + d.wet * (pl - xd.x), xd.y + d.wet * (pr - xd.y)), d.pg);
+        }
+        const float nx = __shfl_down(o.x, 1, 64), ny = __shfl_down(o.y, 1, 64);
+        if (!(tid & 1u) && i < F && n < M) gstore4(d.out + n, make_float4(o.x, o.y, nx, ny));   // (buffers are padded to an even frame count)
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // k_sample_loop: out[m] = sample[(t0 + m) % len]   (extensions.rs:331-341)
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kThreads) void k_sample_loop(const LoopDesc* __restrict__ descs, uint32_t M) {
@@ -5760,6 +5896,28 @@ void launch_delay_apply(const DelayDesc* d, int n, uint32_t max_groups, bool sin
         if (single) hipLaunchKernelGGL(k_delay_apply<true>, dim3(max_groups, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
         else hipLaunchKernelGGL(k_delay_apply<false>, dim3(max_groups, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
     }
+}
+void launch_sat_sum(const SatDesc* d, int n, uint32_t frames, hipStream_t s) {
+    for (int o = 0; o < n && frames; o += kMaxGridY)
+        hipLaunchKernelGGL(k_sat_sum, dim3(tiles(frames), std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
+}
+void launch_sat1(const SatDesc* d, int n, uint32_t frames, hipStream_t s) {
+    for (int o = 0; o < n && frames; o += kMaxGridY)
+        hipLaunchKernelGGL(k_sat1, dim3(tiles(frames), std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
+}
+template <int R>
+static void launch_sat_r(const SatDesc* d, int n, uint32_t n_tiles, uint32_t F, bool terms, hipStream_t s) {
+    // float2 xs[F + 128] + double w[2][R][F + 64]: 61 KB at F = 384, R = 8
+    const size_t lds = (size_t)(F + 128u) * sizeof(float2) + (size_t)2 * R * (F + 64u) * sizeof(double);
+    for (int o = 0; o < n && n_tiles; o += kMaxGridY) {
+        if (terms) hipLaunchKernelGGL((k_sat<R, true>), dim3(n_tiles, std::min(n - o, kMaxGridY)), dim3(kThreads), lds, s, d + o);
+        else hipLaunchKernelGGL((k_sat<R, false>), dim3(n_tiles, std::min(n - o, kMaxGridY)), dim3(kThreads), lds, s, d + o);
+    }
+}
+void launch_sat(const SatDesc* d, int n, uint32_t R, uint32_t n_tiles, uint32_t F, bool terms, hipStream_t s) {
+    if (R == 2u) launch_sat_r<2>(d, n, n_tiles, F, terms, s);
+    else if (R == 4u) launch_sat_r<4>(d, n, n_tiles, F, terms, s);
+    else if (R == 8u) launch_sat_r<8>(d, n, n_tiles, F, terms, s);
 }
 void launch_sample_loop(const LoopDesc* d, int n, uint32_t frames, hipStream_t s) {
     if (!n || !frames) return;

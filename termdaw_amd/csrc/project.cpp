@@ -107,6 +107,7 @@ struct BandCall { std::string name; float gain, angle, wet, lo, hi; bool pass; }
 struct CompCall { std::string name; float gain, angle, wet, threshold_db, ratio, attack_ms, release_ms, knee_db, makeup_db; };
 struct EqCall { std::string name; float gain, angle, wet; int kind; float freq_hz, q, gain_db; };
 struct DelayCall { std::string name; float gain, angle, wet, time_ms, feedback, cross; };
+struct SatCall { std::string name; float gain, angle, wet; int kind; float drive_db, bias, out_db; int oversample; };
 
 using Triple = std::tuple<std::string, std::string, std::string>;
 
@@ -225,6 +226,7 @@ int do_refresh(td_state* s, const std::string& contents) {
     std::vector<CompCall> compressors;
     std::vector<EqCall> eqs;
     std::vector<DelayCall> delays;
+    std::vector<SatCall> saturators;
     size_t cs = s->cs, render_sr = s->render_sr, bd = s->bd;
     // std::mem::take (state.rs:79-80): the locals start from the previous values, the State's own fields are left
     // EMPTY until the script has run (state.rs:169-170) -- so they stay empty when the script fails
@@ -408,6 +410,25 @@ int do_refresh(td_state* s, const std::string& contents) {
                 fnum(c.feedback) + "," + fnum(c.cross) + ")\n";
         return Value::nil();
     });
+    lua.set_function("add_saturator", [&](const std::vector<Value>& a) {   // this engine's own vertex (termdaw_amd.h td_graph_add_saturator); kind by name
+        const char* f = "add_saturator";
+        static const char* const kinds[3] = {"hard", "cubic", "soft"};
+        const std::string kind = to_str(f, a, 4);
+        int k = 0;
+        while (k < 3 && kind != kinds[k]) ++k;
+        if (k == 3) throw LuaError{"add_saturator: unknown kind \"" + kind + "\" (one of hard, cubic, soft)"};
+        const float over = to_f32(f, a, 8);
+        saturators.push_back({to_str(f, a, 0), to_f32(f, a, 1), to_f32(f, a, 2), to_f32(f, a, 3), k, to_f32(f, a, 5), to_f32(f, a, 6), to_f32(f, a, 7), (int)over});
+        auto& c = saturators.back();
+        // (out-of-range parameters are rejected here, where the line is known)
+        if (!(over == 1.0f || over == 2.0f || over == 4.0f || over == 8.0f)) throw LuaError{"add_saturator: oversample must be 1, 2, 4 or 8"};
+        if (!(c.drive_db >= -24.0f && c.drive_db <= 48.0f)) throw LuaError{"add_saturator: drive_db must lie in [-24, 48] dB"};
+        if (!(c.bias >= -1.0f && c.bias <= 1.0f)) throw LuaError{"add_saturator: bias must lie in [-1, 1]"};
+        if (!(c.out_db >= -48.0f && c.out_db <= 24.0f)) throw LuaError{"add_saturator: out_db must lie in [-48, 24] dB"};
+        dump += std::string(f) + "(\"" + c.name + "\"," + fnum(c.gain) + "," + fnum(c.angle) + "," + fnum(c.wet) + ",\"" + kind + "\"," + fnum(c.drive_db) + "," +
+                fnum(c.bias) + "," + fnum(c.out_db) + "," + std::to_string(c.oversample) + ")\n";
+        return Value::nil();
+    });
     lua.set_function("connect", [&](const std::vector<Value>& a) {
         edges.push_back({to_str("connect", a, 0), to_str("connect", a, 1)});
         dump += "connect(\"" + edges.back().first + "\",\"" + edges.back().second + "\")\n";
@@ -528,6 +549,8 @@ int do_refresh(td_state* s, const std::string& contents) {
         if (!td_graph_add_eq(s->g, c.name.c_str(), c.gain, c.angle, c.wet, c.kind, c.freq_hz, c.q, c.gain_db)) return 0;
     for (auto& c : delays)
         if (!td_graph_add_delay(s->g, c.name.c_str(), c.gain, c.angle, c.wet, c.time_ms, c.feedback, c.cross)) return 0;
+    for (auto& c : saturators)
+        if (!td_graph_add_saturator(s->g, c.name.c_str(), c.gain, c.angle, c.wet, c.kind, c.drive_db, c.bias, c.out_db, c.oversample)) return 0;
     for (auto& e : edges) td_graph_connect(s->g, e.first.c_str(), e.second.c_str());   // failures only warn (state.rs:459)
     td_graph_set_output(s->g, s->output_vertex.c_str());
     if (!td_graph_check(s->g)) return fail("TermDaw: graph check failed! (" + g_error + ")");
