@@ -258,6 +258,54 @@ int td_saturator_taps(int oversample, double* taps, size_t cap);
 /* Host only, no GPU: the saturator vertex' constants -- out[0 .. 5] = g_in, g_out, f(bias), the latency in frames, Lf, Hsat as
  * the engine uses them.  The same range checks as td_graph_add_saturator. */
 int td_saturator_params(int kind, int oversample, float drive_db, float bias, float out_db, double out[6]);
+/* A chorus vertex: LFO-modulated fractional delay lines -- THIS ENGINE'S OWN: no reference counterpart (the reference reaches
+ * modulation effects only through LV2 plugins, add_lv2fx, which this engine parses and drops).  The vertex sums its
+ * inputs like every input vertex (sum_inputs, extensions.rs:310-319), processes, mixes with `wet` by the reference's f32 lerp,
+ * then pan and gain like every vertex (extensions.rs:262-263).  wet 0.5 with 2 .. 4 voices is a chorus, wet 1 with one voice a
+ * vibrato, a short delay_ms a feed-forward flanger, depth_ms 0 a static fractional delay.
+ *   Everything is f64 on the f32 summed input x, with no FMA contraction and IEEE add, multiply, floor and fabs only (no libm on
+ *   either side), in exactly the order written here.
+ *   Constants, once on the host from the f32 parameters widened:  D0 = delay_ms sr / 1000,  A = depth_ms sr / 1000 (frames),
+ *     f = rate_hz / sr (cycles per frame),  H = floor(D0 + A) + 3 rounded up to a multiple of 64 (frames of the line),
+ *     s = (2 pi A) f for a sine, (4 A) f for a triangle: the largest change of the delay per frame,  iv = 1 / V.
+ *   LFO, for voice v = 0 .. V - 1 and channel c at frame n -- n is the graph's ABSOLUTE frame time, so a render that
+ *   td_graph_set_time starts in the middle of a project sees the modulation a whole render sees there, whatever the chunking:
+ *     phi = v iv  (left),  v iv + stereo  (right);   th = n f + phi;  th = th - floor(th)
+ *     triangle:  lfo = 1 - 4 |th - 0.5|
+ *     sine:      u = 4 th for th < 0.25,  2 - 4 th for th < 0.75,  else 4 th - 4   (sin(2 pi th) = sin(pi u / 2), u in [-1, 1]);
+ *                u2 = u u;  p = c9;  p = p u2 + c7;  p = p u2 + c5;  p = p u2 + c3;  p = p u2 + c1;  lfo = u p
+ *                with (pi/2)^k / k!, signed:  c1 = 1.5707963267948966, c3 = -0.6459640975062463, c5 = 0.07969262624616705,
+ *                c7 = -0.004681754135318688, c9 = 0.00016044118478735983  -- within 3.6e-6 of sin, |lfo| <= 1 + 3.6e-6
+ *   Read:  d = D0 + A lfo;  i = floor(d);  mu = d - i;  m = n - i
+ *     xs[j] = x[j] if finite, else 0; frames before the line's start are 0
+ *     a = mu - 1, b = mu - 2, e = mu + 1;   four-point Lagrange weights
+ *       w0 = ((mu a) b) (-1/6),  w1 = ((e a) b) (1/2),  w2 = ((e mu) b) (-1/2),  w3 = ((e mu) a) (1/6)      (1/6 = 0.16666666666666666)
+ *     y = 0.0;  y = y + w0 xs[m + 1];  y = y + w1 xs[m];  y = y + w2 xs[m - 1];  y = y + w3 xs[m - 2]
+ *     (D0 - A >= 2 keeps i >= 1 even at the polynomial's overshoot: no future frame is read; at the far end the overshoot can
+ *      carry i to floor(D0 + A) + 1, so i + 2 <= H: the oldest frame read is at most H back, the line's first word)
+ *   Output:  S = 0.0;  S = S + y_v for v ascending;  p[n] = (float)(iv S);
+ *     out = x + wet * (p - x) in f32 with the undelayed input (adsr.rs:42); then pan and gain.  The vertex has no latency.  A
+ *     non-finite x[n] makes frame n of the output non-finite and no other.
+ *   wet < 0.0001: the summed input passes through untouched (a plain k_sum launch) and the line stays as it is.
+ * State: the line, the last H raw input frames (at most 2 432 at 48 kHz), kept as two halves used alternately: 16 H bytes of
+ * device memory (counted by td_graph_device_bytes, allocated when the vertex is first rendered); silent at the start, carried
+ * between consecutive block pulls and between the chunks of a render, restarted from silence by td_graph_set_time /
+ * td_graph_change_time / td_graph_reset -- the LFO is not restarted, it is a function of the time alone.  A render ends where the
+ * project ends: no tail is appended.
+ * Ranges, rejected with a td_last_error that names the parameter (NaN included): voices 1 .. 4, delay_ms [0.5, 50], depth_ms >= 0
+ * with D0 - A >= 2 frames and delay_ms + depth_ms <= 50, rate_hz [0.01, 20] with s <= 0.5 (the error names rate_hz), stereo
+ * [0, 0.5], shape 0 .. 1.  `wet` is clamped to [0, 1].
+ * Under "band_mode" 2 / "sine_mode" 2 the estimate is carried through a chorus vertex at the gain (1 - wet) + wet Hch, Hch =
+ * 2.307 an L2 bound of x -> p for every parameter in range (DESIGN.md 3q has the proof): vertices upstream keep their scan / fast
+ * forms.
+ * Not part of the vertex: feedback around the modulated line (a time-varying recurrence), tempo sync, other interpolators, a
+ * tail past the project's end. */
+enum { TD_CHORUS_SINE = 0, TD_CHORUS_TRIANGLE = 1 };
+int td_graph_add_chorus(td_graph* g, const char* name, float gain, float angle, float wet, int voices, float delay_ms, float depth_ms,
+                        float rate_hz, float stereo, int shape);
+/* Host only, no GPU: the chorus vertex' constants at rate sr -- out[0 .. 5] = D0, A, f, H (frames of the line), s (the largest
+ * delay slope) and Hch as the engine uses them.  The same range checks as td_graph_add_chorus. */
+int td_chorus_params(size_t sr, int voices, float delay_ms, float depth_ms, float rate_hz, float stereo, int shape, double out[6]);
 int td_graph_connect(td_graph* g, const char* a, const char* b);          /* graph.rs:80-96 (+58-78) */
 int td_graph_set_output(td_graph* g, const char* vertex);                 /* graph.rs:141-148 */
 int td_graph_check(const td_graph* g);                                    /* check_graph graph.rs:150-174 */
@@ -456,6 +504,8 @@ size_t td_cached_memory_bytes(void);
  *   debug.delay_tile 8|16|32|64 (steps per tile of the delay vertex' scan; tests/test_gpu_delay.py) /
  *   debug.sat_tile 128|256|384 (output frames per workgroup of the saturator vertex' k_sat; 256 is provisional: nothing was
  *     timed; tests/test_gpu_saturator.py) /
+ *   debug.chorus_tile 256|512|1024 (output frames per workgroup of the chorus vertex' k_chorus; 256 is provisional: nothing was
+ *     timed; tests/test_gpu_chorus.py) /
  *   debug.band_quick n, debug.band_medium n, debug.band_short n, debug.band_warmup n, debug.band_live_exp n, debug.band_depth n
  *     (the exact band-pass' speculative warm-up lengths in 1 / gamma frames and its liveness thresholds: speed only, the
  *     bit-wise check and repair of k_band_fix keep every result exact; tests/test_gpu_quirks.py, tools/band_*_sweep.py).

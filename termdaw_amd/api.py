@@ -73,6 +73,8 @@ SIGNATURES = {
     "td_graph_add_saturator": (_i32, [_vp, _cp, _f32, _f32, _f32, _i32, _f32, _f32, _f32, _i32]),
     "td_saturator_taps": (_i32, [_i32, C.POINTER(C.c_double), _sz]),
     "td_saturator_params": (_i32, [_i32, _i32, _f32, _f32, _f32, C.POINTER(C.c_double)]),
+    "td_graph_add_chorus": (_i32, [_vp, _cp, _f32, _f32, _f32, _i32, _f32, _f32, _f32, _f32, _i32]),
+    "td_chorus_params": (_i32, [_sz, _i32, _f32, _f32, _f32, _f32, _i32, C.POINTER(C.c_double)]),
     "td_graph_connect": (_i32, [_vp, _cp, _cp]),
     "td_graph_set_output": (_i32, [_vp, _cp]),
     "td_graph_check": (_i32, [_vp]),
@@ -322,6 +324,27 @@ def saturator_params(kind, oversample, drive_db, bias, out_db):
     return float(out[0]), float(out[1]), float(out[2]), int(out[3]), float(out[4]), float(out[5])
 
 
+CHORUS_SHAPES = ("sine", "triangle")   # TD_CHORUS_* in order
+
+
+def chorus_shape(shape):
+    """A shape name of CHORUS_SHAPES (or an index) as the TD_CHORUS_* integer."""
+    if isinstance(shape, str):
+        if shape not in CHORUS_SHAPES:
+            raise ValueError("chorus shape %r: one of %s" % (shape, ", ".join(CHORUS_SHAPES)))
+        return CHORUS_SHAPES.index(shape)
+    return int(shape)
+
+
+def chorus_params(sr, voices, delay_ms, depth_ms, rate_hz, stereo, shape):
+    """The chorus vertex' constants at rate sr (host only), exactly as the engine uses them: (D0, A, f, H, s, Hch) -- the centre
+    delay and the depth in frames, the LFO's cycles per frame, the frames of the line, the largest delay slope, and the gain the
+    guard carries its estimate through the wet path at."""
+    out = (C.c_double * 6)()
+    _check(lib().td_chorus_params(int(sr), int(voices), delay_ms, depth_ms, rate_hz, stereo, chorus_shape(shape), out))
+    return float(out[0]), float(out[1]), float(out[2]), int(out[3]), float(out[4]), float(out[5])
+
+
 def loudness_filters(sr):
     """The meter's filters at rate sr (host only): (shelf (b, a), high-pass (b, a)) as float64 arrays with a[0] = 1, and the
     true-peak FIR as a (phases, taps) float32 array (phase 0 the unit impulse)."""
@@ -521,6 +544,11 @@ class Graph:
         """An oversampled waveshaper vertex (this engine's own; the definition is in include/termdaw_amd.h).  kind: a name of
         SAT_KINDS or its TD_SAT_* index; oversample: 1, 2, 4 or 8.  The vertex has a latency of 64 frames when oversample > 1."""
         _check(lib().td_graph_add_saturator(self.h, name.encode(), gain, angle, wet, sat_kind(kind), drive_db, bias, out_db, int(oversample)))
+
+    def add_chorus(self, name, gain, angle, wet, voices, delay_ms, depth_ms, rate_hz, stereo, shape):
+        """A chorus vertex: LFO-modulated fractional delay lines (this engine's own; the definition is in include/termdaw_amd.h).
+        voices: 1 .. 4; shape: a name of CHORUS_SHAPES or its TD_CHORUS_* index.  The vertex has no latency."""
+        _check(lib().td_graph_add_chorus(self.h, name.encode(), gain, angle, wet, int(voices), delay_ms, depth_ms, rate_hz, stereo, chorus_shape(shape)))
 
     def connect(self, a, b):
         return bool(lib().td_graph_connect(self.h, a.encode(), b.encode()))

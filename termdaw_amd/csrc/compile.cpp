@@ -4,6 +4,7 @@
 // (compile.h: take_buffer / ensure_buffers for edge buffers, upload_tables for a vertex' event tables), everything it
 // writes goes into the plain-memory staging arena of the ChunkBuild (offsets + fix-up lists that submit_chunk patches once
 // the device addresses are known).  tests/test_compile_asan.py builds it with g++ -fsanitize=address,undefined.
+#include "chorus_math.h"
 #include "compile.h"
 #include "delay_math.h"
 #include "eq_math.h"
@@ -28,7 +29,8 @@ const char* const kFamilyName[F_COUNT] = {"k_sample_loop", "k_sample_multi", "k_
                                            "k_comp_detect", "k_comp_carry_y1", "k_comp_env", "k_comp_carry_yl", "k_comp_apply",
                                            "k_eq_local", "k_eq_carry", "k_eq_apply",
                                            "k_delay_local", "k_delay_carry", "k_delay_apply",
-                                           "k_sat_sum", "k_sat", "k_sat1"};
+                                           "k_sat_sum", "k_sat", "k_sat1",
+                                           "k_chorus_sum", "k_chorus"};
 
 
 // ------------------------------------------------------------------------------------------------
@@ -937,6 +939,9 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                     sat::params(wv.sat_kind, wv.sat_oversample, wv.sat_drive_db, wv.sat_bias, wv.sat_out_db, c);
                     L *= (1.0 - (double)wv.wet) + (double)wv.wet * c[5];
                 }
+                // a chorus is linear (and time-varying): the estimate goes through it at (1 - wet) + wet Hch, Hch an L2 bound of the
+                // modulated four-point read
+                if (wv.kind == K_CHORUS && !(wv.wet < 0.0001f)) L *= (1.0 - (double)wv.wet) + (double)wv.wet * chorus::kHch;
                 if (wv.kind == K_ADSR && !(wv.wet < 0.0001f)) {   // |lerp(1, level x vel, wet)| <= max(1, |level| |vel|)
                     const AdsrConfD& c = wv.conf;
                     double lv = std::max(std::max(fabs((double)c.std_vel), fabs((double)c.attack_vel)),
@@ -1489,6 +1494,14 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                     } else {
                         if (M > 0xF0000000ull || (M + g->sat_tile - 1) / g->sat_tile >= 0x100000ull) return fail("saturator: chunk too long");
                         fam_v[v.sat_oversample == 1 ? F_SAT1 : F_SAT].push_back(vi);
+                    }
+                    break;
+                case K_CHORUS:
+                    if (v.wet < 0.0001f) {
+                        fam_v[F_SUM].push_back(vi);   // the summed input passes through, the line stays
+                    } else {
+                        if (M > 0xF0000000ull || (M + g->chorus_tile - 1) / g->chorus_tile >= 0x100000ull) return fail("chorus: chunk too long");
+                        fam_v[F_CHORUS].push_back(vi);
                     }
                     break;
                 default: break;
@@ -2479,6 +2492,54 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                     }
                     continue;
                 }
+                case F_CHORUS: {   // the launches of the level's chorus vertices (kernels.h ChorusDesc)
+                    const uint32_t F = g->chorus_tile, n_tiles = (uint32_t)((M + F - 1) / F);
+                    const bool multi = M > (size_t)kSatInlineFrames;   // (multi: k_chorus_sum first)
+                    std::vector<ChorusDesc> d;
+                    for (size_t vi : vs) {
+                        Vertex& v = g->vertices[vi];
+                        double c[6];
+                        chorus::params(sr, v.chorus_voices, v.chorus_delay_ms, v.chorus_depth_ms, v.chorus_rate_hz, v.chorus_stereo, v.chorus_shape, c);
+                        ChorusDesc x{};
+                        if (multi) {
+                            x.x = take_buffer(g);
+                            if (!x.x) return fail("termdaw_amd: out of device memory for edge buffers");
+                            level_tmp.push_back(x.x);
+                        }
+                        x.out = g->vbuf[vi];
+                        x.H = (uint32_t)c[3];
+                        x.line = take_chorus_line(g, v, x.H);
+                        if (!x.line) return fail("termdaw_amd: out of device memory for a chorus line");
+                        // (a set_time since the vertex last ran: the line restarts from silence -- consumed here, like a delay's)
+                        if (v.first_pending) v.chorus_total = 0;
+                        v.first_pending = false;
+                        x.filled = (uint32_t)std::min<uint64_t>(v.chorus_total, x.H);
+                        x.parity = v.chorus_parity;
+                        v.chorus_total += M;
+                        v.chorus_parity ^= 1u;
+                        x.t0 = t0;
+                        x.k = (uint32_t)g->edges[vi].size();
+                        x.term_mode = term_mode[vi];
+                        x.frames = (uint32_t)M;
+                        x.F = F;
+                        x.n_tiles = n_tiles;
+                        x.voices = (uint32_t)v.chorus_voices;
+                        x.shape = (uint32_t)v.chorus_shape;
+                        x.wet = v.wet;
+                        x.D0 = c[0];
+                        x.A = c[1];
+                        x.f = c[2];
+                        x.stereo = (double)v.chorus_stereo;
+                        x.inv_v = 1.0 / (double)v.chorus_voices;
+                        x.pg = make_pg(v.gain, v.angle);
+                        d.push_back(x);
+                    }
+                    off = st.put(d);
+                    for (size_t i = 0; i < vs.size(); ++i) ptr_field(off + i * sizeof(ChorusDesc), offsetof(ChorusDesc, ins), ins_off[vs[i]]);
+                    if (multi) add_launch(F_CHORUS_SUM, off, (int)vs.size(), 0, lv);
+                    add_launch(F_CHORUS, off, (int)vs.size(), chorus_aux(n_tiles, !multi), lv);
+                    continue;
+                }
                 default: continue;
             }
             if (fam == F_SUM || fam == F_ADSR) {   // split at term-mode boundaries (vs is sorted by it)
@@ -2671,6 +2732,8 @@ size_t desc_size(int fam) {
         case F_SAT_SUM:
         case F_SAT:
         case F_SAT1: return sizeof(SatDesc);
+        case F_CHORUS_SUM:
+        case F_CHORUS: return sizeof(ChorusDesc);
         default: return 0;
     }
 }

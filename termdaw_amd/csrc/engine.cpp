@@ -9,6 +9,7 @@
 #include <chrono>
 
 #include "engine.h"
+#include "chorus_math.h"
 #include "comm.h"
 #include "compile.h"
 #include "delay_math.h"
@@ -586,18 +587,35 @@ float2* take_sat_line(td_graph* g, Vertex& v) {
     v.sat_parity = 0;
     return p;
 }
+// The line of a chorus vertex: two halves of H float2 (at most 38 KB at 48 kHz), kept in the same list; never cleared either
+// (Vertex::chorus_total says how many of its frames hold values).
+float2* take_chorus_line(td_graph* g, Vertex& v, size_t H) {
+    if (v.chorus_line) return v.chorus_line;
+    const size_t bytes = 2 * H * sizeof(float2);
+    float2* p = nullptr;
+    if (hipMalloc(&p, bytes) != hipSuccess) return nullptr;
+    g->delay_lines.push_back({reinterpret_cast<double*>(p), bytes});
+    g->device_bytes += bytes;
+    v.chorus_line = p;
+    v.chorus_total = 0;
+    v.chorus_parity = 0;
+    return p;
+}
 // the line a vertex would continue from in its next submission (nullptr: none -- it has none yet, or it starts afresh)
-static void* vertex_line(Vertex& v) { return v.kind == K_SATURATOR ? (void*)v.sat_line : (void*)v.delay_line; }
+static void* vertex_line(Vertex& v) {
+    return v.kind == K_SATURATOR ? (void*)v.sat_line : v.kind == K_CHORUS ? (void*)v.chorus_line : (void*)v.delay_line;
+}
 static const void* carried_line(const Vertex& v) {
     if (v.first_pending) return nullptr;
     if (v.kind == K_DELAY && v.delay_line && v.delay_total) return v.delay_line;
     if (v.kind == K_SATURATOR && v.sat_line && v.sat_total) return v.sat_line;
+    if (v.kind == K_CHORUS && v.chorus_line && v.chorus_total) return v.chorus_line;
     return nullptr;
 }
 static void free_delay_lines(td_graph* g) {
     for (auto& l : g->delay_lines) { (void)hipFree(l.first); g->device_bytes -= l.second; }
     g->delay_lines.clear();
-    for (auto& v : g->vertices) { v.delay_line = nullptr; v.sat_line = nullptr; }
+    for (auto& v : g->vertices) { v.delay_line = nullptr; v.sat_line = nullptr; v.chorus_line = nullptr; }
 }
 float2* take_buffer(td_graph* g) {
     if (!g->free_bufs.empty()) {
@@ -945,6 +963,8 @@ static int submit_chunk(Arena& ar, ChunkBuild& cb, hipStream_t stream, ProfCtx& 
                 case F_SAT_SUM: launch_sat_sum((const SatDesc*)d, L.n, L.M, s); break;   // (likewise)
                 case F_SAT: launch_sat((const SatDesc*)d, L.n, (L.aux >> 24) & 15u, L.aux & 0xFFFFFu, ((L.aux >> 20) & 15u) * 128u, (L.aux & kSatTermsBit) != 0u, s); break;
                 case F_SAT1: launch_sat1((const SatDesc*)d, L.n, L.M, s); break;
+                case F_CHORUS_SUM: launch_chorus_sum((const ChorusDesc*)d, L.n, L.M, s); break;   // (likewise)
+                case F_CHORUS: launch_chorus((const ChorusDesc*)d, L.n, L.aux & 0xFFFFFu, L.M, (L.aux & kChorusTermsBit) != 0u, s); break;
             }
         }
         li = lj;
@@ -1040,6 +1060,10 @@ static int prepare_render(td_graph* g, size_t n_blocks, int bits, bool want_pcm,
         for (size_t vi : g->order)
             if (g->vertices[vi].kind == K_SATURATOR && !(g->vertices[vi].wet < 0.0001f))
                 return fail("termdaw_amd: this build has no k_sat kernels: saturator vertices cannot be rendered");
+    if (!(launch_chorus_sum && launch_chorus))
+        for (size_t vi : g->order)
+            if (g->vertices[vi].kind == K_CHORUS && !(g->vertices[vi].wet < 0.0001f))
+                return fail("termdaw_amd: this build has no k_chorus kernels: chorus vertices cannot be rendered");
     const size_t bl = g->bl;
     if (bl == 0) return fail("termdaw_amd: buffer length 0");
     rp->n_blocks = n_blocks;
@@ -1145,6 +1169,7 @@ static bool starts_afresh(const td_graph* g) {
         if ((v.kind == K_BAND_PASS || v.kind == K_COMPRESSOR || v.kind == K_EQ) && v.state_slot >= 0 && !v.first_pending) return false;
         if (v.kind == K_DELAY && v.delay_line && !v.first_pending) return false;
         if (v.kind == K_SATURATOR && v.sat_line && !v.first_pending) return false;
+        if (v.kind == K_CHORUS && v.chorus_line && !v.first_pending) return false;
     }
     return true;
 }
@@ -1185,7 +1210,7 @@ static int guard_begin(td_graph* g, const td_samplebank* sb, td_flowwbank* fb, s
         TD_HIP(hipMemcpyAsync(q.d_backup, g->dstate, n * sizeof(StateSlot), hipMemcpyDeviceToDevice, g->stream));
         q.have_backup = true;
     }
-    // the lines of the delay and saturator vertices that continue from what they hold (a vertex with a set_time pending reads nothing
+    // the lines of the delay, saturator and chorus vertices that continue from what they hold (a vertex with a set_time pending reads nothing
     // of its line)
     q.lines.clear();
     size_t need = 0;
@@ -1272,6 +1297,8 @@ void HostSnapshot::take(const td_graph* g, const td_flowwbank* fb) {
         v[i].delay_total = x.delay_total;
         v[i].sat_total = x.sat_total;
         v[i].sat_parity = x.sat_parity;
+        v[i].chorus_total = x.chorus_total;
+        v[i].chorus_parity = x.chorus_parity;
         v[i].has_init_override = x.has_init_override;
         v[i].peak_known = x.peak_known;
         v[i].first_pending = x.first_pending;
@@ -1290,6 +1317,8 @@ void HostSnapshot::put(td_graph* g, td_flowwbank* fb) const {
         x.delay_total = v[i].delay_total;
         x.sat_total = v[i].sat_total;
         x.sat_parity = v[i].sat_parity;
+        x.chorus_total = v[i].chorus_total;
+        x.chorus_parity = v[i].chorus_parity;
         x.has_init_override = v[i].has_init_override;
         x.peak_known = v[i].peak_known;
         x.first_pending = v[i].first_pending;
@@ -1370,6 +1399,7 @@ static int graph_set_time_impl(td_graph* g, size_t time) {   // graph.rs:123-128
                 break;
             case K_DELAY:   // the line restarts from zero: the next submission reads none of its words
             case K_SATURATOR:
+            case K_CHORUS:
                 v.first_pending = true;
                 break;
             default: break;
@@ -1966,6 +1996,27 @@ int td_saturator_params(int kind, int oversample, float drive_db, float bias, fl
     if (!out) return fail("saturator_params: out is null");
     if (!sat_check(kind, oversample, drive_db, bias, out_db)) return 0;
     sat::params(kind, oversample, drive_db, bias, out_db, out);
+    return 1;
+}
+
+// This engine's own modulated-delay vertex (no reference counterpart; the definition is in include/termdaw_amd.h).
+int td_graph_add_chorus(td_graph* g, const char* name, float gain, float angle, float wet, int voices, float delay_ms, float depth_ms,
+                        float rate_hz, float stereo, int shape) {
+    if (const char* why = chorus::check(g->sr, voices, delay_ms, depth_ms, rate_hz, stereo, shape)) return fail(std::string("chorus: ") + why);
+    Vertex& v = add_vertex(g, name, gain, angle, wet, K_CHORUS);
+    v.chorus_voices = voices;
+    v.chorus_shape = shape;
+    v.chorus_delay_ms = delay_ms;
+    v.chorus_depth_ms = depth_ms;
+    v.chorus_rate_hz = rate_hz;
+    v.chorus_stereo = stereo;
+    v.first_pending = true;   // (the line, once it exists, is read from the first frame the vertex itself has written)
+    return 1;
+}
+int td_chorus_params(size_t sr, int voices, float delay_ms, float depth_ms, float rate_hz, float stereo, int shape, double out[6]) {
+    if (!out) return fail("chorus_params: out is null");
+    if (const char* why = chorus::check(sr, voices, delay_ms, depth_ms, rate_hz, stereo, shape)) return fail(std::string("chorus: ") + why);
+    chorus::params(sr, voices, delay_ms, depth_ms, rate_hz, stereo, shape, out);
     return 1;
 }
 
@@ -2727,7 +2778,7 @@ static std::vector<OptionRef> option_table(td_graph* g) {
         {"debug.inline_adsr", 0, &g->inline_adsr}, {"debug.spec_normalize", 0, &g->spec_normalize},
         {"debug.single_pass_normalize", 0, &g->single_pass_normalize}, {"debug.fuse_normalize", 0, &g->fuse_normalize},
         {"debug.table_cache", 0, &g->table_cache}, {"debug.band_serial", 0, &g->band_serial}, {"debug.band_chain", 0, &g->band_chain}, {"debug.band_scan_nf", 1, &g->band_scan_nf},
-        {"debug.delay_tile", 2, &g->delay_tile}, {"debug.sat_tile", 2, &g->sat_tile},
+        {"debug.delay_tile", 2, &g->delay_tile}, {"debug.sat_tile", 2, &g->sat_tile}, {"debug.chorus_tile", 2, &g->chorus_tile},
         {"debug.band_quick", 2, &g->band_quick}, {"debug.band_short", 2, &g->band_short}, {"debug.band_medium", 2, &g->band_medium},
         {"debug.band_warmup", 2, &g->band_warmup}, {"debug.band_depth", 2, &g->band_depth},
         {"debug.stem_taps", 2, &g->stem_taps},
@@ -2770,6 +2821,11 @@ int td_graph_set_option(td_graph* g, const char* key, long value) {
     if (k == "debug.sat_tile") {
         if (value != 128 && value != 256 && value != 384) return fail("debug.sat_tile must be 128, 256 or 384");
         g->sat_tile = (unsigned)value;
+        return 1;
+    }
+    if (k == "debug.chorus_tile") {
+        if (value != 256 && value != 512 && value != 1024) return fail("debug.chorus_tile must be 256, 512 or 1024");
+        g->chorus_tile = (unsigned)value;
         return 1;
     }
     if (k == "debug.band_live_exp") { g->band_live_thr = value >= 38 ? 0.0f : powf(10.0f, -(float)value); return 1; }

@@ -348,6 +348,39 @@ struct SatDesc {
     PanGain pg;
 };
 
+// A chorus vertex (k_chorus_sum / k_chorus; the definition is in include/termdaw_amd.h at td_graph_add_chorus):
+// `voices` fractional delay lines per channel, each read by four-point Lagrange interpolation at the distance D0 + A lfo behind
+// the output frame, the LFO a function of the graph's ABSOLUTE frame time -- all in f64 on the f32 summed input, every output
+// frame a pure function of the last H input frames.  One lane per output frame, a workgroup owns a tile of F of them; every
+// voice and both channels of a frame stay in the lane's registers.
+// The line holds the last H raw input frames in two halves of H float2, used alternately: a launch reads half `parity` (only the
+// `filled` most recent frames hold values, the others read as 0) and its last tile writes the last H frames of (old line ++
+// chunk) to half parity ^ 1, so no tile reads a word another tile of the launch writes -- H may exceed the chunk.
+// line[h][i] is the frame H - i back from the chunk's start.
+// A chunk of at most kSatInlineFrames frames -- every block pull -- is ONE launch: k_chorus<true> runs the term loop itself over
+// the part of the chunk its tile can reach, [max(t0 - H, 0), t0 + F), into LDS (at most 32 KB); otherwise k_chorus_sum leaves
+// the summed input in `x` first and k_chorus<false> gathers from it with plain global loads.
+struct ChorusDesc {
+    const InTerm* ins;      // k input terms (kinds 0 .. 4), in connect() order
+    float2* x;              // [frames] the summed input (two-launch form; null in the one-launch form)
+    float2* out;
+    float2* line;           // [2][H] carried across chunks / block pulls
+    uint64_t t0;            // the graph's absolute frame time at the chunk's first frame (the LFO's n)
+    uint32_t k, term_mode, frames;
+    uint32_t F;             // output frames per tile (a multiple of kThreads)
+    uint32_t n_tiles;       // ceil(frames / F)
+    uint32_t H;             // frames per half of the line (a multiple of 64, >= floor(D0 + A) + 3)
+    uint32_t filled;        // min(frames the vertex has run since its line restarted, H)
+    uint32_t parity;        // the half of the line this launch reads
+    uint32_t voices;        // 1 .. 4
+    uint32_t shape;         // TD_CHORUS_*
+    float wet;
+    double D0, A, f;        // centre delay and depth in frames, LFO cycles per frame
+    double stereo;          // the right channel's phase offset in cycles
+    double inv_v;           // 1 / voices
+    PanGain pg;
+};
+
 // sample_loop_gen (extensions.rs:331-341): out[m] = sample[(t0 + m) % len]
 struct LoopDesc {
     const float2* sample;
@@ -808,6 +841,12 @@ inline uint32_t sat_aux(uint32_t n_tiles, uint32_t F, uint32_t R, bool terms) {
 __attribute__((weak)) void launch_sat_sum(const SatDesc* d, int n_desc, uint32_t frames, hipStream_t s);
 __attribute__((weak)) void launch_sat(const SatDesc* d, int n_desc, uint32_t R, uint32_t n_tiles, uint32_t F, bool terms, hipStream_t s);
 __attribute__((weak)) void launch_sat1(const SatDesc* d, int n_desc, uint32_t frames, hipStream_t s);
+// Weak for the same reason: a level's chorus vertices.  launch_chorus_sum: grid.x from `frames`; launch_chorus: grid.x = n_tiles
+// (every descriptor's), `terms`: the instantiation with the term loop inside, whose LDS holds the chunk's `frames` frames.
+constexpr uint32_t kChorusTermsBit = 0x80000000u;
+inline uint32_t chorus_aux(uint32_t n_tiles, bool terms) { return n_tiles | (terms ? kChorusTermsBit : 0u); }
+__attribute__((weak)) void launch_chorus_sum(const ChorusDesc* d, int n_desc, uint32_t frames, hipStream_t s);
+__attribute__((weak)) void launch_chorus(const ChorusDesc* d, int n_desc, uint32_t n_tiles, uint32_t frames, bool terms, hipStream_t s);
 void launch_sinf(const float* in, float* out, uint32_t n, int exact, hipStream_t s);   // out[i] = sin_glibc(in[i]) (exact) or sin_any(in[i])
 void launch_debug_verify(const uint32_t* p, uint32_t n_words, const uint32_t* seg_sums, uint32_t* report, hipStream_t s);   // (TD_DEBUG_SYNC & 16)
 void launch_sample_loop(const LoopDesc* d, int n_desc, uint32_t frames, hipStream_t s);

@@ -2376,6 +2376,123 @@ __global__ __launch_bounds__(kThreads) void k_sat(const SatDesc* __restrict__ de
 }
 
 // ------------------------------------------------------------------------------------------------
+// k_chorus_sum / k_chorus: the chorus vertex (kernels.h ChorusDesc).  No reference counterpart; the definition is
+// the header's (td_graph_add_chorus): per voice and channel th = frac(n f + phi), lfo(th), d = D0 + A lfo, a four-point Lagrange
+// read at n - d, the voices summed from 0.0 in ascending order -- all in f64 with IEEE add, multiply, floor and fabs only, each
+// output on its own, so neither the tiling nor the chunking re-associates anything.
+// ------------------------------------------------------------------------------------------------
+// the LFO: th in [0, 1) -> [-1, 1] (the sine through its odd Taylor polynomial to u^9, |error| <= 3.6e-6)
+TD_DEV double chorus_lfo(uint32_t shape, double th) {
+    if (shape == 1u) return 1.0 - 4.0 * fabs(th - 0.5);
+    // sin(2 pi th) = sin(pi u / 2), u in [-1, 1]
+    const double u = th < 0.25 ? 4.0 * th : (th < 0.75 ? 2.0 - 4.0 * th : 4.0 * th - 4.0);
+    const double u2 = u * u;
+    double p = 0.00016044118478735983;
+    p = p * u2 + -0.004681754135318688;
+    p = p * u2 + 0.07969262624616705;
+    p = p * u2 + -0.6459640975062463;
+    p = p * u2 + 1.5707963267948966;
+    return u * p;
+}
+// the summed input, materialised once for the gathers: k_sum's frame mapping, identity epilogue
+__global__ __launch_bounds__(kThreads) void k_chorus_sum(const ChorusDesc* __restrict__ descs) {
+    const ChorusDesc& d = descs[blockIdx.y];
+    const uint32_t M = d.frames, m0 = blockIdx.x * kTileFrames + 2u * threadIdx.x, m1 = m0 + kTileFrames / 2;
+    if (blockIdx.x * kTileFrames >= M) return;
+    float4 a0, a1;
+    sum_inputs_pairs(d.ins, d.k, d.term_mode, m0, m1, M, a0, a1);
+    store_pair(d.x, m0, M, a0);
+    store_pair(d.x, m1, M, a1);
+}
+// TERMS: the term loop runs here, over the frames of the chunk this tile can reach, into LDS (a short chunk -- every block pull:
+// one launch); otherwise the kernel gathers from the buffer k_chorus_sum left, with plain global loads (adjacent lanes read
+// adjacent frames at a distance that drifts by less than half a frame per lane: L1 / L2 serve the 8 V re-reads).
+// LDS (TERMS only): float2 xs[] -- index i = chunk frame ws + i, ws = max(t0 - H, 0) rounded down to even.
+template <bool TERMS>
+__global__ __launch_bounds__(kThreads) void k_chorus(const ChorusDesc* __restrict__ descs) {
+    extern __shared__ __attribute__((aligned(16))) char chorus_lds[];
+    const ChorusDesc& d = descs[blockIdx.y];
+    const uint32_t tile = blockIdx.x;
+    if (tile >= d.n_tiles) return;
+    const uint32_t tid = threadIdx.x, F = d.F, M = d.frames, t0 = tile * F, H = d.H;
+    float2* xs = reinterpret_cast<float2*>(chorus_lds);
+    const float2* line_r = d.line + (size_t)d.parity * H;
+    const uint32_t ws = TERMS && t0 > H ? (t0 - H) & ~1u : 0u;
+    if (TERMS) {
+        // two aligned frame pairs per thread and step, 2 kThreads frames apart (sum_inputs_pairs' shape); a pair at or beyond the
+        // window's end is not evaluated (frames at M or beyond come out as 0: xs[] has room for an odd chunk's pad frame)
+        const uint32_t we = min(M, t0 + F), none = (M + 1u) & ~1u;
+        for (uint32_t i = ws + 2u * tid; i < we; i += 4u * kThreads) {
+            const uint32_t i1 = i + 2u * kThreads < we ? i + 2u * kThreads : none;
+            float4 a0, a1;
+            sum_inputs_pairs(d.ins, d.k, d.term_mode, i, i1, M, a0, a1);
+            xs[i - ws] = make_float2(a0.x, a0.y);
+            xs[i - ws + 1u] = make_float2(a0.z, a0.w);
+            if (i1 != none) {
+                xs[i1 - ws] = make_float2(a1.x, a1.y);
+                xs[i1 - ws + 1u] = make_float2(a1.z, a1.w);
+            }
+        }
+        __syncthreads();
+    }
+    // the raw input at chunk frame j (j < 0: the line, a frame beyond `filled` back is 0)
+    auto raw = [&](int64_t j) {
+        if (j >= 0) return TERMS ? xs[(uint32_t)j - ws] : gload2(d.x + j);
+        const uint32_t back = (uint32_t)(-j);
+        return back <= d.filled ? gload2(line_r + (H - back)) : make_float2(0.f, 0.f);
+    };
+    // ---- the chunk's last tile leaves the last H frames of (old line ++ chunk) in the line's other half (the words of the old line
+    // are copied as they are: what lay beyond `filled` stays beyond the new `filled`)
+    if (tile + 1u == d.n_tiles) {
+        float2* line_w = d.line + (size_t)(d.parity ^ 1u) * H;
+        for (uint32_t i = tid; i < H; i += kThreads) {
+            const int64_t j = (int64_t)M - (int64_t)H + (int64_t)i;
+            gstore2(line_w + i, j >= 0 ? (TERMS ? xs[(uint32_t)j - ws] : gload2(d.x + j)) : gload2(line_r + (M + i)));
+        }
+    }
+    // ---- one lane per output frame; 16-byte stores by the even lanes
+    const uint32_t V = d.voices, imax = H - 2u;
+    for (uint32_t b = 0; b < F; b += kThreads) {   // (uniform trip count: the shuffle below takes every lane)
+        const uint32_t i = b + tid, n = t0 + i;
+        float2 o = make_float2(0.f, 0.f);
+        if (n < M) {   // (i < F always: F is a multiple of kThreads)
+            const double nf = (double)(d.t0 + (uint64_t)n) * d.f;
+            double sl = 0.0, sr = 0.0;
+            for (uint32_t v = 0; v < V; ++v) {
+                const double phi = (double)v * d.inv_v;
+#pragma unroll
+                for (int c = 0; c < 2; ++c) {
+                    double th = nf + (c ? phi + d.stereo : phi);
+                    th = th - floor(th);
+                    const double dl = d.D0 + d.A * chorus_lfo(d.shape, th);
+                    const double fi = floor(dl), mu = dl - fi;
+                    // (1 <= fi <= H - 2 by the ranges: D0 - A >= 2, H >= floor(D0 + A) + 3, |lfo| <= 1 + 3.6e-6 -- the overshoot can carry fi to
+                    // floor(D0 + A) + 1; the clamp never moves it, and the oldest frame read, m - 2, is at most H back: the line's first word)
+                    const uint32_t id = min(max((uint32_t)fi, 1u), imax);
+                    const int64_t m = (int64_t)n - (int64_t)id;
+                    const double a = mu - 1.0, bb = mu - 2.0, cc = mu + 1.0;
+                    const double w0 = ((mu * a) * bb) * -0.16666666666666666, w1 = ((cc * a) * bb) * 0.5;
+                    const double w2 = ((cc * mu) * bb) * -0.5, w3 = ((cc * mu) * a) * 0.16666666666666666;
+                    const float2 x0 = raw(m + 1), x1 = raw(m), x2 = raw(m - 1), x3 = raw(m - 2);
+                    auto clean = [&](float2 x) { const float s = c ? x.y : x.x; return delay_finite(s) ? (double)s : 0.0; };
+                    double y = 0.0;
+                    y = y + w0 * clean(x0);
+                    y = y + w1 * clean(x1);
+                    y = y + w2 * clean(x2);
+                    y = y + w3 * clean(x3);
+                    if (c) sr = sr + y; else sl = sl + y;
+                }
+            }
+            const float2 x = raw((int64_t)n);
+            const float pl = (float)(d.inv_v * sl), pr = (float)(d.inv_v * sr);
+            o = epilogue(make_float2(x.x + d.wet * (pl - x.x), x.y + d.wet * (pr - x.y)), d.pg);
+        }
+        const float nx = __shfl_down(o.x, 1, 64), ny = __shfl_down(o.y, 1, 64);
+        if (!(tid & 1u) && n < M) gstore4(d.out + n, make_float4(o.x, o.y, nx, ny));   // (buffers are padded to an even frame count)
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // k_sample_loop: out[m] = sample[(t0 + m) % len]   (extensions.rs:331-341)
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kThreads) void k_sample_loop(const LoopDesc* __restrict__ descs, uint32_t M) {
@@ -5918,6 +6035,18 @@ void launch_sat(const SatDesc* d, int n, uint32_t R, uint32_t n_tiles, uint32_t 
     if (R == 2u) launch_sat_r<2>(d, n, n_tiles, F, terms, s);
     else if (R == 4u) launch_sat_r<4>(d, n, n_tiles, F, terms, s);
     else if (R == 8u) launch_sat_r<8>(d, n, n_tiles, F, terms, s);
+}
+void launch_chorus_sum(const ChorusDesc* d, int n, uint32_t frames, hipStream_t s) {
+    for (int o = 0; o < n && frames; o += kMaxGridY)
+        hipLaunchKernelGGL(k_chorus_sum, dim3(tiles(frames), std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
+}
+void launch_chorus(const ChorusDesc* d, int n, uint32_t n_tiles, uint32_t frames, bool terms, hipStream_t s) {
+    // terms: float2 xs[] for the chunk, padded to an even frame count -- at most 32 KB (frames <= kSatInlineFrames)
+    const size_t lds = terms ? (size_t)((frames + 1u) & ~1u) * sizeof(float2) : 0;
+    for (int o = 0; o < n && n_tiles; o += kMaxGridY) {
+        if (terms) hipLaunchKernelGGL((k_chorus<true>), dim3(n_tiles, std::min(n - o, kMaxGridY)), dim3(kThreads), lds, s, d + o);
+        else hipLaunchKernelGGL((k_chorus<false>), dim3(n_tiles, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
+    }
 }
 void launch_sample_loop(const LoopDesc* d, int n, uint32_t frames, hipStream_t s) {
     if (!n || !frames) return;

@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 
 #include "engine.h"
+#include "chorus_math.h"
 #include "devmem.h"
 #include "eq_math.h"
 #include "lua_subset.h"
@@ -107,6 +108,7 @@ struct BandCall { std::string name; float gain, angle, wet, lo, hi; bool pass; }
 struct CompCall { std::string name; float gain, angle, wet, threshold_db, ratio, attack_ms, release_ms, knee_db, makeup_db; };
 struct EqCall { std::string name; float gain, angle, wet; int kind; float freq_hz, q, gain_db; };
 struct DelayCall { std::string name; float gain, angle, wet, time_ms, feedback, cross; };
+struct ChorusCall { std::string name; float gain, angle, wet; int voices; float delay_ms, depth_ms, rate_hz, stereo; int shape; };
 struct SatCall { std::string name; float gain, angle, wet; int kind; float drive_db, bias, out_db; int oversample; };
 
 using Triple = std::tuple<std::string, std::string, std::string>;
@@ -227,6 +229,7 @@ int do_refresh(td_state* s, const std::string& contents) {
     std::vector<EqCall> eqs;
     std::vector<DelayCall> delays;
     std::vector<SatCall> saturators;
+    std::vector<ChorusCall> choruses;
     size_t cs = s->cs, render_sr = s->render_sr, bd = s->bd;
     // std::mem::take (state.rs:79-80): the locals start from the previous values, the State's own fields are left
     // EMPTY until the script has run (state.rs:169-170) -- so they stay empty when the script fails
@@ -429,6 +432,23 @@ int do_refresh(td_state* s, const std::string& contents) {
                 fnum(c.bias) + "," + fnum(c.out_db) + "," + std::to_string(c.oversample) + ")\n";
         return Value::nil();
     });
+    lua.set_function("add_chorus", [&](const std::vector<Value>& a) {   // this engine's own vertex (termdaw_amd.h td_graph_add_chorus); shape by name
+        const char* f = "add_chorus";
+        static const char* const shapes[2] = {"sine", "triangle"};
+        const std::string shape = to_str(f, a, 9);
+        int k = 0;
+        while (k < 2 && shape != shapes[k]) ++k;
+        if (k == 2) throw LuaError{"add_chorus: unknown shape \"" + shape + "\" (one of sine, triangle)"};
+        const float voices = to_f32(f, a, 4);
+        if (!(voices == 1.0f || voices == 2.0f || voices == 3.0f || voices == 4.0f)) throw LuaError{"add_chorus: voices must be 1 .. 4"};
+        choruses.push_back({to_str(f, a, 0), to_f32(f, a, 1), to_f32(f, a, 2), to_f32(f, a, 3), (int)voices, to_f32(f, a, 5), to_f32(f, a, 6), to_f32(f, a, 7), to_f32(f, a, 8), k});
+        auto& c = choruses.back();
+        // (out-of-range parameters are rejected here, where the line is known)
+        if (const char* why = tde::chorus::check(psr, c.voices, c.delay_ms, c.depth_ms, c.rate_hz, c.stereo, c.shape)) throw LuaError{std::string("add_chorus: ") + why};
+        dump += std::string(f) + "(\"" + c.name + "\"," + fnum(c.gain) + "," + fnum(c.angle) + "," + fnum(c.wet) + "," + std::to_string(c.voices) + "," + fnum(c.delay_ms) + "," +
+                fnum(c.depth_ms) + "," + fnum(c.rate_hz) + "," + fnum(c.stereo) + ",\"" + shape + "\")\n";
+        return Value::nil();
+    });
     lua.set_function("connect", [&](const std::vector<Value>& a) {
         edges.push_back({to_str("connect", a, 0), to_str("connect", a, 1)});
         dump += "connect(\"" + edges.back().first + "\",\"" + edges.back().second + "\")\n";
@@ -551,6 +571,8 @@ int do_refresh(td_state* s, const std::string& contents) {
         if (!td_graph_add_delay(s->g, c.name.c_str(), c.gain, c.angle, c.wet, c.time_ms, c.feedback, c.cross)) return 0;
     for (auto& c : saturators)
         if (!td_graph_add_saturator(s->g, c.name.c_str(), c.gain, c.angle, c.wet, c.kind, c.drive_db, c.bias, c.out_db, c.oversample)) return 0;
+    for (auto& c : choruses)
+        if (!td_graph_add_chorus(s->g, c.name.c_str(), c.gain, c.angle, c.wet, c.voices, c.delay_ms, c.depth_ms, c.rate_hz, c.stereo, c.shape)) return 0;
     for (auto& e : edges) td_graph_connect(s->g, e.first.c_str(), e.second.c_str());   // failures only warn (state.rs:459)
     td_graph_set_output(s->g, s->output_vertex.c_str());
     if (!td_graph_check(s->g)) return fail("TermDaw: graph check failed! (" + g_error + ")");
