@@ -493,6 +493,8 @@ size_t td_cached_memory_bytes(void);
  *   debug.norm n (bit 0: every single-pass Normalize tile gives up its wait at once -> the check kernel redoes the vertex;
  *     tests/test_gpu_bench_form.py) / debug.spec_normalize 0|1 / debug.single_pass_normalize 0|1 / debug.fuse_normalize 0|1
  *     (the two-launch Normalize forms; tests/test_gpu_spec_normalize.py, test_gpu_band_scan.py) /
+ *   debug.sum_groups n (0: automatic; n: the wide packed sum in its ragged form on a grid of n workgroups, each carrying 4 .. 16
+ *     quads of 256 frames -- a render whose timeline n cannot carry that way fails; tests/test_gpu_sum_ragged.py) /
  *   debug.inline_adsr 0|1 (an Adsr vertex materialised instead of read through; tests/test_gpu_parity.py) /
  *   debug.one_grid_sources 0|1 (a level's source launches one by one instead of as k_sources; tests/test_gpu_sources_grid.py) /
  *   debug.inline_probe 0|1 (sine_mode 2: k_sine_probe as a launch of its own instead of inside the guarded chain launch's tiles;

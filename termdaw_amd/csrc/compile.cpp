@@ -1422,6 +1422,7 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
         std::vector<size_t> norm_pending;
         std::map<size_t, uint32_t> norm_mode;   // Normalize vertices: SumDesc::mode (1 two passes, 3 / 4 one pass + k_norm_fix, 5 one pass)
         std::map<size_t, int> norm_tpw;         // ... of those, the ones that take k_norm1: tiles per workgroup
+        std::map<size_t, uint32_t> ragged_of;   // Sum / Normalize vertices summed by the ragged form k_sum16r: its grid's workgroups
         for (size_t vi : by_level[lv]) {
             Vertex& v = g->vertices[vi];
             if (inlined[vi]) continue;
@@ -1593,8 +1594,13 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                 // a FRESH render whose sum runs in the wide all-loop kernels (k_sum16w: every tile resident at once) finds the
                 // running peak through granules inside that one launch (mode 4)
                 const uint32_t tm = term_mode[vi];
-                const bool wide = (tm == TERMS_ALL_LOOP16 || tm == TERMS_ALL_LOOP32) && bl == (size_t)kTileFrames &&
-                                  M >= (size_t)1800 * kTileFrames && M < ((size_t)1 << 31);
+                // (test hook debug.sum_groups: the ragged form of the packed sum on a timeline of any length)
+                const bool ragged_forced = g->sum_groups != 0u && tm == TERMS_ALL_LOOP16 && bl == (size_t)kTileFrames && M < ((size_t)1 << 31) &&
+                                           g->single_pass_normalize && !(v.peak_known && !v.has_init_override);
+                if (ragged_forced && !sum16r_groups((uint32_t)M, g->sum_groups, true))
+                    return fail("debug.sum_groups: every workgroup needs 4 .. 16 quads of 256 frames, and the grid must be resident at once");
+                const bool wide = ((tm == TERMS_ALL_LOOP16 || tm == TERMS_ALL_LOOP32) && bl == (size_t)kTileFrames &&
+                                   M >= (size_t)1800 * kTileFrames && M < ((size_t)1 << 31)) || ragged_forced;
                 if (v.peak_known && !v.has_init_override) mode = 3u;
                 else if (!wide && g->single_pass_normalize && bl == (size_t)kTileFrames && M < ((size_t)1 << 31)) {
                     // any other input terms, any timeline whose grid is resident at once: k_norm1
@@ -1605,7 +1611,10 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                     const bool packed = tm == TERMS_ALL_LOOP16;
                     const int nq = (packed && M >= (size_t)2600 * kTileFrames) ? 4 : 2;
                     const size_t gx = (M + (size_t)kTileFrames * nq - 1) / ((size_t)kTileFrames * nq);
-                    mode = (size_t)sum16w_resident_capacity(nq, packed) >= gx ? 5u : 4u;
+                    // (... or the ragged form, where 16 frames per lane would run and its evenly filled grid is resident)
+                    const uint32_t rg = packed ? sum16r_groups((uint32_t)M, g->sum_groups, true) : 0u;
+                    if (rg) { mode = 5u; ragged_of[vi] = rg; }
+                    else mode = (size_t)sum16w_resident_capacity(nq, packed) >= gx ? 5u : 4u;
                 }
             }
             norm_mode[vi] = mode;
@@ -1785,8 +1794,17 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                     for (size_t vi : fam_v[F_BAND_SPEC]) vs.push_back(vi);
                     // one launch per term mode (k_sum is instantiated per mode): group the vertices by it
                     // (a single-pass running-peak Normalize -- mode 4 -- only exists in the wide kernels: a group of its own)
+                    // (plain Sum vertices of packed loops take the ragged form where launch_sum would pick 16 frames per lane)
+                    for (size_t vi : vs) {
+                        if (g->vertices[vi].kind == K_NORMALIZE || band_plan.count(vi) || term_mode[vi] != TERMS_ALL_LOOP16 || M >= ((size_t)1 << 31)) continue;
+                        if (g->sum_groups && !sum16r_groups((uint32_t)M, g->sum_groups, false))
+                            return fail("debug.sum_groups: every workgroup needs 4 .. 16 quads of 256 frames");
+                        const uint32_t rg = sum16r_groups((uint32_t)M, g->sum_groups, false);
+                        if (rg) ragged_of[vi] = rg;
+                    }
+                    auto rg_of = [&](size_t vi) { return ragged_of.count(vi) ? ragged_of[vi] : 0u; };
                     auto sum_key = [&](size_t vi) {
-                        return term_mode[vi] * 16u + ((norm_mode.count(vi) && norm_mode[vi] >= 4u) ? 1u : 0u) + (norm_tpw.count(vi) ? 2u * (uint32_t)norm_tpw[vi] : 0u);
+                        return (uint64_t)rg_of(vi) * 4096u + term_mode[vi] * 16u + ((norm_mode.count(vi) && norm_mode[vi] >= 4u) ? 1u : 0u) + (norm_tpw.count(vi) ? 2u * (uint32_t)norm_tpw[vi] : 0u);
                     };
                     std::stable_sort(vs.begin(), vs.end(), [&](size_t a, size_t b) { return sum_key(a) < sum_key(b); });
                     for (size_t vi : vs) {
@@ -1831,16 +1849,17 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                         const size_t o = off + i * sizeof(SumDesc);
                         ptr_field(o, offsetof(SumDesc, ins), ins_off[vs[i]]);
                         if (g->vertices[vs[i]].kind == K_NORMALIZE) {
-                            const size_t pk = scratch(nb * sizeof(float)), ic = scratch(2 * sizeof(float));
+                            const size_t pk = scratch(2 * nb * sizeof(float)), ic = scratch(2 * sizeof(float));   // (peaks, and the ragged form's second slot per block)
                             norm_scratch[vs[i]] = {pk, ic};
                             audit_norm[vs[i]] = {pk, ic};
                             sum_desc_of[vs[i]] = d[i];
-                            if (d[i].mode >= 4u) {   // one granule per workgroup (at most one per block)
+                            if (d[i].mode >= 4u) {   // one granule per workgroup (at most one per block); the ragged form: two arrays of them
                                 cb.esync_fix.push_back({o + offsetof(SumDesc, sync), cb.esync_bytes});
-                                cb.esync_bytes += (nb * 8 + 63) & ~(size_t)63;
+                                cb.esync_bytes += (2 * nb * 8 + 63) & ~(size_t)63;
                                 cb.flag_fix.push_back(o + offsetof(SumDesc, host_flag));
                             }
                             scratch_field(o, offsetof(SumDesc, peaks), pk);
+                            if (ragged_of.count(vs[i])) scratch_field(o, offsetof(SumDesc, peaks2), pk + nb * sizeof(float));
                             scratch_field(o, offsetof(SumDesc, init_copy), ic);
                             if (peaks_need_zero) cb.zero.push_back({pk, nb * sizeof(float)});
                             g->vertices[vs[i]].has_init_override = false;
@@ -1885,6 +1904,7 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                         const size_t o = off + i * sizeof(SumDesc);
                         ptr_field(o, offsetof(SumDesc, ins), ins_off[vs[i]]);
                         scratch_field(o, offsetof(SumDesc, peaks), norm_scratch[vs[i]].first);
+                        if (ragged_of.count(vs[i])) scratch_field(o, offsetof(SumDesc, peaks2), norm_scratch[vs[i]].first + nb * sizeof(float));
                         scratch_field(o, offsetof(SumDesc, init_copy), norm_scratch[vs[i]].second);
                         if (!deferred(vs[i])) ++n_now;
                     }
@@ -2550,14 +2570,16 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                     bool wide_ok = true;   // (k_sum16w: plain sums, or normalize pass A with the tile as reference block)
                     auto m4 = [&](size_t vi) { return fam == F_SUM && norm_mode.count(vi) && norm_mode[vi] >= 4u; };
                     auto tpw_of = [&](size_t vi) { return (fam == F_SUM && norm_tpw.count(vi)) ? norm_tpw[vi] : 0; };
-                    while (e2 < vs.size() && term_mode[vs[e2]] == term_mode[vs[b]] && m4(vs[e2]) == m4(vs[b]) && tpw_of(vs[e2]) == tpw_of(vs[b])) {
+                    auto rg_of = [&](size_t vi) { return (fam == F_SUM && ragged_of.count(vi)) ? ragged_of[vi] : 0u; };   // (k_sum16r's grid: aux bits 16 ..)
+                    while (e2 < vs.size() && term_mode[vs[e2]] == term_mode[vs[b]] && m4(vs[e2]) == m4(vs[b]) && tpw_of(vs[e2]) == tpw_of(vs[b]) &&
+                           rg_of(vs[e2]) == rg_of(vs[b])) {
                         wide_ok = wide_ok && (g->vertices[vs[e2]].kind != K_NORMALIZE || bl == (size_t)kTileFrames);
                         // (a band-pass vertex' input sum -- mode 2: planar copy, 256-frame liveness -- only exists in the pair-mapped k_sum)
                         wide_ok = wide_ok && !(fam == F_SUM && band_plan.count(vs[e2]));
                         ++e2;
                     }
                     add_launch(fam, off + b * dsz, (int)(e2 - b),
-                               term_mode[vs[b]] | (wide_ok ? 0x100u : 0u) | (m4(vs[b]) ? 0x200u : 0u) | ((uint32_t)tpw_of(vs[b]) << 12), lv);
+                               term_mode[vs[b]] | (wide_ok ? 0x100u : 0u) | (m4(vs[b]) ? 0x200u : 0u) | ((uint32_t)tpw_of(vs[b]) << 12) | (rg_of(vs[b]) << 16), lv);
                     b = e2;
                 }
                 continue;

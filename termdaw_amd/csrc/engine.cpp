@@ -932,8 +932,8 @@ static int submit_chunk(Arena& ar, ChunkBuild& cb, hipStream_t stream, ProfCtx& 
                 case F_ENV: launch_adsr_env((const AdsrVDesc*)d, L.n, L.M, s); break;
                 case F_PROBE: launch_sine_probe((const ProbeDesc*)d, L.n, L.M, L.aux, s); break;
                 case F_SUM:
-                    if (L.aux >> 12) launch_norm1((const SumDesc*)d, L.n, L.M, L.aux & 0xFFu, (int)(L.aux >> 12), sum_tag, s);   // single-pass Normalize, narrow forms
-                    else launch_sum((const SumDesc*)d, L.n, L.M, L.bl, L.aux & 0xFFu, (L.aux & 0x100u) != 0u, (L.aux & 0x200u) != 0u, sum_tag, s);
+                    if ((L.aux >> 12) & 0xFu) launch_norm1((const SumDesc*)d, L.n, L.M, L.aux & 0xFFu, (int)((L.aux >> 12) & 0xFu), sum_tag, s);   // single-pass Normalize, narrow forms
+                    else launch_sum((const SumDesc*)d, L.n, L.M, L.bl, L.aux & 0xFFFF00FFu, (L.aux & 0x100u) != 0u, (L.aux & 0x200u) != 0u, sum_tag, s);   // (bits 16 ..: the ragged form's grid)
                     break;
                 case F_SCALE: launch_scale((const ScaleDesc*)d, L.n, L.M, L.bl, L.is_scan, s); break;
                 case F_NORMFIX: launch_norm_fix((const SumDesc*)d, L.n, L.M, L.bl, s); break;
@@ -2774,7 +2774,7 @@ static std::vector<OptionRef> option_table(td_graph* g) {
         {"fuse_sources", 0, &g->fuse_sources}, {"packed_samples", 0, &g->packed_samples}, {"band_mode", 1, &g->band_mode},
         {"band_guard_ppb", 2, &g->band_guard_ppb}, {"sine_mode", 1, &g->sine_mode}, {"output_f32", 0, &g->output_f32},
         {"max_chunk_frames", 3, &g->max_chunk_frames},
-        {"debug.norm", 1, &g->norm_debug}, {"debug.band_scan", 1, &g->band_scan_debug}, {"debug.one_grid_sources", 0, &g->one_grid_sources}, {"debug.inline_probe", 0, &g->inline_probe},
+        {"debug.norm", 1, &g->norm_debug}, {"debug.sum_groups", 2, &g->sum_groups}, {"debug.band_scan", 1, &g->band_scan_debug}, {"debug.one_grid_sources", 0, &g->one_grid_sources}, {"debug.inline_probe", 0, &g->inline_probe},
         {"debug.inline_adsr", 0, &g->inline_adsr}, {"debug.spec_normalize", 0, &g->spec_normalize},
         {"debug.single_pass_normalize", 0, &g->single_pass_normalize}, {"debug.fuse_normalize", 0, &g->fuse_normalize},
         {"debug.table_cache", 0, &g->table_cache}, {"debug.band_serial", 0, &g->band_serial}, {"debug.band_chain", 0, &g->band_chain}, {"debug.band_scan_nf", 1, &g->band_scan_nf},

@@ -441,6 +441,7 @@ struct td_graph {
     bool one_grid_sources = true;              // a level's source launches (affine Synth, wavetable voice, SampleLerp) and the envelope launch go out as ONE grid (k_sources)
     bool fuse_normalize = true;                // band_mode 1: a Normalize vertex right behind a scan launch is evaluated by that launch (BandScanDesc::norm)
     bool single_pass_normalize = true;         // fresh renders of wide all-loop sums find the running peak inside the sum launch (SumDesc mode 4)
+    unsigned sum_groups = 0;                   // (tests, A/B runs) debug.sum_groups: workgroups of the ragged packed sum's grid; 0 = automatic
     int norm_debug = 0;                        // (tests) bit 0: every single-pass Normalize tile gives up its wait at once -> k_norm_fix
     bool defer_fix = true;                     // (set per render) this render is one chunk: the output vertex' k_norm_fix may wait for settle()
     float band_live_thr = 1e-9f;               // energy from before the short window / energy inside it below which it is enough

@@ -7,7 +7,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
+#include <algorithm>
 #include "adsr_math.h"
+#include "sum_partition.h"
 
 namespace tdk {
 
@@ -120,6 +123,11 @@ struct SumDesc {
     // the vertex is the last thing its submission computes, the engine does not enqueue k_norm_fix behind the launch: it
     // looks at this word once the stream has drained and launches the fix only then (engine.cpp settle()).  nullptr: none.
     uint32_t* host_flag;
+    // the ragged form (k_sum16r, mode 5): a reference block can lie in two workgroups, and each contributor has a slot of its
+    // own -- `peaks[b]` from the workgroup that owns the block's first quad, `peaks2[b]` from the one that owns its last (0
+    // where that is the same workgroup): complete in memory when the launch ends, whatever a wait did.  nullptr: every
+    // other form (k_norm_fix folds the two where it is set).
+    float* peaks2;
 };
 
 // Normalize pass B: running max over the block peaks (`*max = buf_max.max(*max)`), buf.scale(len, 1.0 / max)
@@ -793,10 +801,27 @@ void launch_band_fix(const BandSpecDesc* d, int n_desc, uint32_t frames, uint32_
 // `frames`-long chunk is resident at once, 0 if none; and its launch
 int norm1_tiles_per_workgroup(uint32_t term_mode, uint32_t frames);
 void launch_norm1(const SumDesc* d, int n_desc, uint32_t frames, uint32_t term_mode, int tpw, uint32_t tag, hipStream_t s);   // tag: see launch_sum
-int sum16w_resident_capacity(int nq, bool packed);   // workgroups of k_sum16w<nq, packed> the device holds at once (0: unknown)
+// (nq 0: the ragged form k_sum16r; nq -1: the device's CU count)
+int sum16w_resident_capacity(int nq, bool packed);
+// The ragged form of the wide packed sum (k_sum16r; sum_partition.h): the workgroups of its grid for a timeline of `frames`, 0 where
+// the form does not apply -- tdsp::pick_groups with this device's figures.  Automatic: kSumGroupsPerCU workgroups per CU where
+// launch_sum would pick 16 frames per lane (from 2 600 tiles on).  compile.cpp decides with it, launch_sum gets the answer.
+// kSumGroupsPerCU is 0 -- the automatic choice never takes the form: on config 2 it measured 75 / 79 us at 3 / 4 workgroups per CU
+// against k_sum16w<4>'s 58 (docs/EXPERIMENTS.md 0000); the form is reached through debug.sum_groups, or through the tuning aid
+// TD_SUM_WPC (workgroups per CU; read once per process like TD_FORCE_NQ, which turns the form off).
+constexpr uint32_t kSumGroupsPerCU = 0;
+inline uint32_t sum16r_groups(uint32_t frames, uint32_t forced, bool need_resident) {
+    static const int env_wpc = getenv("TD_SUM_WPC") ? atoi(getenv("TD_SUM_WPC")) : -1;
+    static const bool env_nq = getenv("TD_FORCE_NQ") && atoi(getenv("TD_FORCE_NQ")) != 0;
+    const uint32_t wpc = env_nq ? 0u : (env_wpc >= 0 ? (uint32_t)env_wpc : kSumGroupsPerCU);
+    return tdsp::pick_groups(frames, forced, need_resident, (uint32_t)std::max(0, sum16w_resident_capacity(0, true)),
+                             (uint32_t)std::max(0, sum16w_resident_capacity(-1, true)), wpc, 2600u * 1024u);
+}   // workgroups of k_sum16w<nq, packed> the device holds at once (0: unknown)
 // must_wide: the descriptors hold a mode-4 / mode-5 Normalize, which only the k_sum16w forms implement (the engine sets it where they would run anyway)
 // tag: what a tile word of a single-pass Normalize (SumDesc::sync, modes 4 / 5) carries beside its value -- 1 when the engine has
 // zeroed the words before the launch, otherwise the submission's epoch (engine.cpp, submit_chunk)
+// term_mode: the TermMode in bits 0 .. 7; bits 16 .. 31, if not 0: the ragged form k_sum16r with that many workgroups (the descriptors
+// are plain Sums or mode-5 Normalizes with `peaks2`: compile.cpp)
 void launch_sum(const SumDesc* d, int n_desc, uint32_t frames, uint32_t bl, uint32_t term_mode, bool wide_ok, bool must_wide, uint32_t tag, hipStream_t s);
 void launch_scale(const ScaleDesc* d, int n_desc, uint32_t frames, uint32_t bl, int is_scan, hipStream_t s);
 // second half of the speculative single-pass normalize: a no-op unless a block peak exceeded the carried max

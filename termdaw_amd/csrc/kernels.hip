@@ -11,6 +11,7 @@
 // tile+2t and tile+512+2t, i.e. one 16-byte float4 per lane per access and 1 KiB contiguous per
 // wave-instruction.
 #include "kernels.h"
+#include "sum_partition.h"
 
 #include <algorithm>
 
@@ -452,7 +453,8 @@ template <int NQ>
 TD_DEV uint32_t quad_frame(uint32_t m, int q) { return NQ == 4 ? m + 256u * (uint32_t)q : m + 4u * (uint32_t)q; }
 template <int NQ>
 TD_DEV uint32_t pair_frame(uint32_t m, int p) { return quad_frame<NQ>(m, p >> 1) + 2u * (uint32_t)(p & 1); }
-template <int NQ>
+// (QUAD: the quad shape for any NQ -- the ragged form k_sum16r below, whose waves own 1 .. 4 quads)
+template <int NQ, bool QUAD = (NQ == 4)>
 TD_DEV void sum_terms16w(TermTab ins, uint32_t k, uint32_t m, uint32_t M, float4 acc[2 * NQ]) {
     f2v c[4 * NQ];
 #pragma unroll
@@ -475,7 +477,7 @@ TD_DEV void sum_terms16w(TermTab ins, uint32_t k, uint32_t m, uint32_t M, float4
     auto gather = [&](uint32_t j, uint32_t w[4 * NQ]) {
         const uint32_t len = (uint32_t)ins[j].len;
         const uint32_t idx = barrett_mod((uint32_t)ins[j].t0 + m, len, ins[j].magic);
-        if (NQ == 4) {
+        if (QUAD) {
             const uint32_t* p = reinterpret_cast<const uint32_t*>(ins[j].p);
             const uint32_t step = step256(len, ins[j].magic);
             uint32_t i = idx;
@@ -511,7 +513,7 @@ TD_DEV void sum_terms16w(TermTab ins, uint32_t k, uint32_t m, uint32_t M, float4
     }
     for (; j < k; ++j) { uint32_t w[4 * NQ]; gather(j, w); add_term(j, w); }
 #pragma unroll
-    for (int q = 0; q < 2 * NQ; ++q) acc[q] = zero_tail(make_float4(c[2 * q].x, c[2 * q].y, c[2 * q + 1].x, c[2 * q + 1].y), pair_frame<NQ>(m, q), M);
+    for (int q = 0; q < 2 * NQ; ++q) acc[q] = zero_tail(make_float4(c[2 * q].x, c[2 * q].y, c[2 * q + 1].x, c[2 * q + 1].y), pair_frame<QUAD ? 4 : NQ>(m, q), M);
 }
 
 // the same for all-f32 looping sources (kind 1): 4 * NQ consecutive frames per lane = 2 * NQ 16-byte loads per source
@@ -902,6 +904,171 @@ __global__ __launch_bounds__(kThreads) void k_sum16w(const SumDesc* __restrict__
 }
 
 // ------------------------------------------------------------------------------------------------
+// k_sum16r: the RAGGED form of k_sum16w<4, true> -- the same loads, the same sums, another partition
+// ------------------------------------------------------------------------------------------------
+// k_sum16w welds a wave to a 1 024-frame reference block: 2 813 blocks make 704 workgroups, 2.75 per CU -- three quarters of
+// the CUs hold three, a quarter two, and the fourth wave slot per SIMD that 116 registers leave free stays empty.  Here the
+// unit is the QUAD (256 frames: one load instruction of a wave, 1 KB in one piece): the timeline's quads are dealt evenly over
+// a grid of G workgroups chosen to fill every CU alike (sum_partition.h: workgroup -> 4 .. 16 quads, wave -> 1 .. 4), so a wave
+// owns nq quads 256 frames apart, lane l frames 256 (q0 + i) + 4 l .. + 3 -- the frame shape, the byte shape of every load
+// and the order of the adds per frame are k_sum16w<4>'s: the result is the same to the bit.  The body for nq is chosen by ONE
+// wave-uniform branch outside the source loop (sum_terms16w<nq, quad shape>); nothing is predicated inside it.
+// Modes 0 (Sum) and 5 (single-pass Normalize, resident grid).  The running peak with quad-granular boundaries:
+//   - per-quad peaks, collected per workgroup in LDS;
+//   - the workgroup's whole-range maximum as its granule (sync[g]): the maximum over all LOWER workgroups' granules is exactly
+//     the maximum of every frame before this workgroup's first quad (all their quads lie in blocks at or before its first);
+//   - a HEAD granule (sync[G + g]): the maximum of those of its quads that lie in the block of its first quad.  A workgroup
+//     whose last block continues in workgroup g + 1 needs that workgroup's head granule and only that: the one wait for a
+//     HIGHER workgroup.  It is bounded like the others and harmless for the same reason: both granules are published before
+//     any wait, the grid is resident, and correctness never rests on that -- a wait that gives up raises `violated` and
+//     k_norm_fix redoes the vertex from the block peaks;
+//   - those are complete in memory when the launch ends whatever a wait did: a block touches at most two workgroups, the one
+//     with its first quad stores its part in peaks[b], the one with its last quad in peaks2[b] (SumDesc::peaks2).
+__global__ __launch_bounds__(kThreads) void k_sum16r(const SumDesc* __restrict__ descs, uint32_t M, uint32_t tag) {
+    const SumDesc& d = descs[blockIdx.y];
+    const uint32_t Q = tdsp::quads_of(M), G = gridDim.x, g = blockIdx.x;
+    const tdsp::QuadRange wg = tdsp::group_quads(g, G, Q);
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const tdsp::QuadRange wv = tdsp::wave_quads(wg, wave);
+    const uint32_t nq = wv.n;
+    const uint32_t m = tdsp::kQuadFrames * wv.q0 + 4u * (threadIdx.x & 63u);
+    // (mode 5: the carried max, read before anything else -- the last workgroup replaces it once every one has published)
+    const float init = d.mode >= 4 ? (d.use_init ? d.init_max : gload1(&d.state->max)) : 0.0f;
+    float4 a[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) a[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+    const TermTab ins = term_tab(d.ins);
+    if (nq == 4u) sum_terms16w<4, true>(ins, d.k, m, M, a);
+    else if (nq == 3u) { float4 t[6]; sum_terms16w<3, true>(ins, d.k, m, M, t);
+#pragma unroll
+        for (int q = 0; q < 6; ++q) a[q] = t[q]; }
+    else if (nq == 2u) { float4 t[4]; sum_terms16w<2, true>(ins, d.k, m, M, t);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) a[q] = t[q]; }
+    else if (nq == 1u) { float4 t[2]; sum_terms16w<1, true>(ins, d.k, m, M, t); a[0] = t[0]; a[1] = t[1]; }
+    if (d.mode == 0) {
+#pragma unroll
+        for (int q = 0; q < 8; ++q)
+            if ((uint32_t)(q >> 1) < nq) store_pair(d.out, pair_frame<4>(m, q), M, epilogue4(a[q], d.pg));
+        return;
+    }
+    // ---- mode 5 ----
+    __shared__ float qpk[tdsp::kMaxQuads], pm4[kThreads / 64], head_next;
+    __shared__ uint32_t bad;
+    // per-quad peaks of the RAW sum (frames at or beyond M are zero: they never win)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        if ((uint32_t)q < nq) {
+            const float p = wave_max(absmax4(absmax4(0.0f, a[2 * q]), a[2 * q + 1]));
+            if ((threadIdx.x & 63u) == 0u) qpk[wv.q0 - wg.q0 + (uint32_t)q] = p;
+        }
+    }
+    if (threadIdx.x == 0) { bad = 0u; head_next = 0.0f; }
+    __syncthreads();
+    const uint32_t last_q = wg.q0 + wg.n - 1u;                    // the workgroup's last quad
+    const uint32_t b_first = wg.q0 / tdsp::kQuadsPerBlock, b_last = last_q / tdsp::kQuadsPerBlock;
+    // block peaks, one slot per contributor, BEFORE any wait (a workgroup's quads touch at most five blocks)
+    if (threadIdx.x < 5u) {
+        const uint32_t b = b_first + threadIdx.x;
+        const uint32_t bq0 = b * tdsp::kQuadsPerBlock, bq1 = min(bq0 + tdsp::kQuadsPerBlock - 1u, Q - 1u);   // the block's quads
+        const uint32_t lo = max(bq0, wg.q0), hi = min(bq1, last_q);                                       // ... those of them that are mine
+        if (b <= b_last && lo <= hi) {
+            float p = 0.0f;
+            for (uint32_t j = lo; j <= hi; ++j) p = fmaxf(p, qpk[j - wg.q0]);
+            if (lo == bq0) d.peaks[b] = p;
+            if (hi == bq1) d.peaks2[b] = lo == bq0 ? 0.0f : p;
+        }
+    }
+    float T = 0.0f, H = 0.0f;
+    for (uint32_t j = 0; j < wg.n; ++j) {
+        const float p = qpk[j];
+        T = fmaxf(T, p);
+        if ((wg.q0 + j) / tdsp::kQuadsPerBlock == b_first) H = fmaxf(H, p);
+    }
+    unsigned long long* const sync = d.sync;
+    unsigned long long* const heads = d.sync + G;
+    if (threadIdx.x == 0) {
+        asm volatile("" ::"v"(init));   // (the carried max has been READ before this workgroup counts as published: the last one replaces it)
+        granule_store(sync + g, __float_as_uint(T), tag);
+        granule_store(heads + g, __float_as_uint(H), tag);
+    }
+    const bool forced = (d.debug & 1u) != 0u;   // (tests: every wait gives up at once)
+    const bool tail = tdsp::tail_straddles(wg, Q);
+    // the one wait for a higher workgroup: its first load goes out before the lower granules are gathered
+    const bool fwd = tail && threadIdx.x == (uint32_t)kThreads - 1u;
+    unsigned long long hg = (fwd && !forced) ? granule_load(heads + g + 1u) : 0ull;
+    float pm = 0.0f;
+    bool ok = forced ? g == 0u : for_lower_granules(sync, g, kScanSpinLimitSum, [&pm](uint32_t, uint32_t v) { pm = fmaxf(pm, __uint_as_float(v)); }, tag);
+    if (fwd) {
+        if (!forced) {
+            for (uint32_t spin = 0; (uint32_t)(hg >> 32) != tag && spin < kScanSpinLimitSum; ++spin) {
+                __builtin_amdgcn_s_sleep(2);
+                hg = granule_load(heads + g + 1u);
+            }
+        }
+        if (!forced && (uint32_t)(hg >> 32) == tag) head_next = __uint_as_float((uint32_t)hg);
+        else ok = false;
+    }
+    pm = wave_max(pm);
+    if ((threadIdx.x & 63u) == 0u) pm4[wave] = pm;
+    if (!ok) bad = 1u;
+    __syncthreads();
+    const float run_in = fmaxf(fmaxf(fmaxf(pm4[0], pm4[1]), fmaxf(pm4[2], pm4[3])), init);   // the running peak entering the workgroup's first quad
+    // a frame is scaled by 1 / max(carried, peaks of all blocks up to and including its own): *max = buf_max.max(*max), block by block
+    float r[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const uint32_t b = (wv.q0 + (uint32_t)q) / tdsp::kQuadsPerBlock;
+        float run = run_in;
+        for (uint32_t j = 0; j < wg.n; ++j)
+            if ((wg.q0 + j) / tdsp::kQuadsPerBlock <= b) run = fmaxf(qpk[j], run);
+        if (tail && b == b_last) run = fmaxf(head_next, run);
+        r[q] = 1.0f / run;
+    }
+    if (threadIdx.x == 0) {
+        NormState* st = const_cast<NormState*>(d.state);
+        if (bad) raise_violated(st, d.host_flag);
+        else if (g == G - 1u) st->max = fmaxf(T, run_in);   // (every workgroup has read the old value: see above)
+        if (g == 0u) {
+            d.init_copy[0] = init;
+            d.init_copy[1] = d.state->scan_max;
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 8; ++q) a[q] = epilogue4(make_float4(a[q].x * r[q >> 1], a[q].y * r[q >> 1], a[q].z * r[q >> 1], a[q].w * r[q >> 1]), d.pg);
+    if (d.out) {   // (nullptr: nobody reads the f32 form of this output vertex -- engine option "output_f32" 0)
+#pragma unroll
+        for (int q = 0; q < 8; ++q)
+            if ((uint32_t)(q >> 1) < nq) store_pair(d.out, pair_frame<4>(m, q), M, a[q]);
+    }
+    if (d.qmode == 1u) {
+        // int16 PCM: a quad's four frames of the lane are 16 contiguous bytes -> one 16-byte store
+        uint32_t* o = reinterpret_cast<uint32_t*>(d.pcm);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            if ((uint32_t)q >= nq) continue;
+            const uint32_t mm = quad_frame<4>(m, q);
+            if (mm + 3u < M) {
+                const float4 v0 = a[2 * q], v1 = a[2 * q + 1];
+                u4v w;
+                w.x = ((uint32_t)quant16(v0.x, d.amplitude) & 0xFFFFu) | ((uint32_t)quant16(v0.y, d.amplitude) << 16);
+                w.y = ((uint32_t)quant16(v0.z, d.amplitude) & 0xFFFFu) | ((uint32_t)quant16(v0.w, d.amplitude) << 16);
+                w.z = ((uint32_t)quant16(v1.x, d.amplitude) & 0xFFFFu) | ((uint32_t)quant16(v1.y, d.amplitude) << 16);
+                w.w = ((uint32_t)quant16(v1.z, d.amplitude) & 0xFFFFu) | ((uint32_t)quant16(v1.w, d.amplitude) << 16);
+                *reinterpret_cast<u4v TD_GLOBAL*>((TD_GLOBAL char*)(o + mm)) = w;
+            } else {
+                store_quant_pair(d.pcm, 1u, mm, M, a[2 * q], d.amplitude);
+                store_quant_pair(d.pcm, 1u, mm + 2u, M, a[2 * q + 1], d.amplitude);
+            }
+        }
+    } else if (d.qmode) {
+#pragma unroll
+        for (int q = 0; q < 8; ++q)
+            if ((uint32_t)(q >> 1) < nq) store_quant_pair(d.pcm, d.qmode, pair_frame<4>(m, q), M, a[q], d.amplitude);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // k_norm1: Normalize in ONE launch for any input terms (SumDesc mode 5), reference block = the 1024-frame tile
 // ------------------------------------------------------------------------------------------------
 // The same scheme as k_sum16w's mode 5 for the narrow forms: a workgroup sums TPW consecutive tiles (1, 2 or 4: chosen by the
@@ -1065,6 +1232,12 @@ __global__ __launch_bounds__(kThreads) void k_scale(const ScaleDesc* __restrict_
 // tile whose running max differs from the carried one is redone the two-pass way (sum_inputs again, the exact
 // running max of its blocks from the peak table, scale, epilogue, quantise); the workgroup that finishes last
 // stores the new carried max and re-arms the flag.
+// (a launch of the ragged form k_sum16r leaves a reference block's peak in TWO slots, one per workgroup the block can touch:
+// SumDesc::peaks2)
+TD_DEV float block_peak(const SumDesc& d, uint32_t b) {
+    const float p = d.peaks[b];
+    return d.peaks2 ? fmaxf(p, d.peaks2[b]) : p;
+}
 __global__ __launch_bounds__(kThreads) void k_norm_fix(const SumDesc* __restrict__ descs, uint32_t M, uint32_t bl, uint32_t nb) {
     const SumDesc& d = descs[blockIdx.y];
     NormState* st = const_cast<NormState*>(d.state);
@@ -1078,7 +1251,7 @@ __global__ __launch_bounds__(kThreads) void k_norm_fix(const SumDesc* __restrict
         const uint32_t b_lo = tile0 / bl;
         const uint32_t b_hi = min((min(tile0 + (uint32_t)kTileFrames, M) - 1u) / bl, nb - 1u);
         float p = 0.0f;
-        for (uint32_t b = threadIdx.x; b < b_lo; b += kThreads) p = fmaxf(d.peaks[b], p);
+        for (uint32_t b = threadIdx.x; b < b_lo; b += kThreads) p = fmaxf(block_peak(d, b), p);
         p = wave_max(p);
         __syncthreads();   // (wmax of the previous tile has been read by everyone)
         if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = p;
@@ -1086,7 +1259,7 @@ __global__ __launch_bounds__(kThreads) void k_norm_fix(const SumDesc* __restrict
         const float before = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
         const float upto = b_lo ? fmaxf(before, init) : init;      // running max entering the tile's first block
         float last = upto;
-        for (uint32_t bb = b_lo; bb <= b_hi; ++bb) last = fmaxf(d.peaks[bb], last);
+        for (uint32_t bb = b_lo; bb <= b_hi; ++bb) last = fmaxf(block_peak(d, bb), last);
         if (!(last > init)) continue;   // (uniform) every block of this tile was scaled by 1 / init: already right
         float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0;
         if (d.term_mode == TERMS_ADSR1) sum_terms<TERMS_ADSR1>(term_tab(d.ins), d.k, m0, m1, M, a0, a1);
@@ -1095,7 +1268,7 @@ __global__ __launch_bounds__(kThreads) void k_norm_fix(const SumDesc* __restrict
         auto rscale_of = [&](uint32_t m) -> float {
             float run = upto;
             const uint32_t b = m / bl;
-            for (uint32_t bb = b_lo; bb <= b; ++bb) run = fmaxf(d.peaks[bb], run);
+            for (uint32_t bb = b_lo; bb <= b; ++bb) run = fmaxf(block_peak(d, bb), run);
             return 1.0f / run;
         };
 #pragma unroll
@@ -1116,7 +1289,7 @@ __global__ __launch_bounds__(kThreads) void k_norm_fix(const SumDesc* __restrict
         const uint32_t t = __hip_atomic_fetch_add(&st->ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
         if (t == gridDim.x - 1u) {
             float all = init;
-            for (uint32_t bb = 0; bb < nb; ++bb) all = fmaxf(d.peaks[bb], all);
+            for (uint32_t bb = 0; bb < nb; ++bb) all = fmaxf(block_peak(d, bb), all);
             st->max = all;                       // *max = buf_max.max(*max) over every block of the chunk
             st->ticket = 0u;
             st->violated = 0u;
@@ -5769,16 +5942,18 @@ static const auto k_sum32w_2 = &k_sum16w<2, false>;   // (names without a comma 
 constexpr int kMaxDev = 16;   // the occupancy x CU caches below are kept per device (a process may drive several)
 static inline int cur_dev() { int d = 0; return (hipGetDevice(&d) == hipSuccess && d >= 0 && d < kMaxDev) ? d : 0; }
 int sum16w_resident_capacity(int nq, bool packed) {
-    static int cap_all[kMaxDev][3];   // <4, true>, <2, true>, <2, false>; 0 = not asked yet (stored + 1)
+    static int cap_all[kMaxDev][5];   // <4, true>, <2, true>, <2, false>, k_sum16r (nq 0), the CU count (nq -1); 0 = not asked yet (stored + 1)
     int* const cap = cap_all[cur_dev()];
-    const int i = packed ? (nq == 4 ? 0 : 1) : 2;
+    const int i = nq == 0 ? 3 : nq == -1 ? 4 : packed ? (nq == 4 ? 0 : 1) : 2;
     if (cap[i] > 0) return cap[i] - 1;
     {
-        int per_cu = 0, dev = 0;
+        int per_cu = 1, dev = 0;
         hipDeviceProp_t prop;
         hipError_t e = i == 0 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_sum16w<4, true>, kThreads, 0)
                      : i == 1 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_sum16w<2, true>, kThreads, 0)
-                              : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_sum16w<2, false>, kThreads, 0);
+                     : i == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_sum16w<2, false>, kThreads, 0)
+                     : i == 3 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_sum16r, kThreads, 0)
+                              : hipSuccess;
         cap[i] = 1 + ((e == hipSuccess && hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
                           ? per_cu * prop.multiProcessorCount : 0);
     }
@@ -5846,6 +6021,17 @@ void launch_norm1(const SumDesc* d, int n, uint32_t frames, uint32_t term_mode, 
 }
 void launch_sum(const SumDesc* d, int n, uint32_t frames, uint32_t bl, uint32_t term_mode, bool wide_ok, bool must_wide, uint32_t tag, hipStream_t s) {
     if (!n || !frames) return;
+    const uint32_t ragged_groups = term_mode >> 16;   // (kernels.h)
+    term_mode &= 0xFFu;
+    if (ragged_groups) {
+        if (term_mode != TERMS_ALL_LOOP16 || !tdsp::groups_ok(tdsp::quads_of(frames), ragged_groups)) return;   // (compile.cpp never asks for that)
+        // (slices as below: about one project per launch at config 2's size, so that a slice's workgroups walk the sources
+        // together -- and, mode 5, a slice is resident at once)
+        const int per = std::max(1, sum16w_resident_capacity(0, true) / (int)ragged_groups);
+        for (int o = 0; o < n; o += per)
+            hipLaunchKernelGGL(k_sum16r, dim3(ragged_groups, std::min(per, n - o)), dim3(kThreads), 0, s, d + o, frames, tag);
+        return;
+    }
     const uint32_t tpb = (bl % kTileFrames == 0) ? bl / kTileFrames : 0;
     static const int env_nq = getenv("TD_FORCE_NQ") ? atoi(getenv("TD_FORCE_NQ")) : 0;   // tuning aid: 1 | 2 | 4
     const int forced_nq = (must_wide && env_nq == 1) ? 0 : env_nq;

@@ -7,10 +7,14 @@
 //      a modulo per quad (or one modulo and three conditional wraps)
 //   C  two runs of 8 consecutive frames per lane, 512 frames apart: a load instruction touches 64 halves of 32-byte pieces
 // each with 1 or 2 sources' loads in flight before the first is consumed.
+//   R  shape B's loads, four sources in flight, under the RAGGED partition of k_sum16r (termdaw_amd/csrc/sum_partition.h): the
+//      timeline's quads dealt evenly over G = 768 / 1 024 / 1 280 workgroups (3 / 4 / 5 per CU), a wave owns 1 .. 4 quads --
+//      beside B with four sources in flight on the engine's 704 workgroups: what the partition does to the gather alone
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <vector>
+#include "sum_partition.h"
 #define UB_GLOBAL __attribute__((address_space(1)))
 #define UB_CONST __attribute__((address_space(4)))
 typedef unsigned int u4v_u __attribute__((ext_vector_type(4), aligned(4)));
@@ -80,6 +84,65 @@ __global__ __launch_bounds__(256) void k_gather(const Tab* __restrict__ tabs_gen
         }
     }
 }
+// R: quads [q0, q0 + NQ) of the wave, lane l frames 256 (q0 + i) + 4 l .. + 3; the quad-to-quad step 256 mod len with one wrap
+template <int NQ>
+__device__ __forceinline__ void gather_ragged(const Tab UB_CONST* tabs, int k, uint32_t M, float* out, uint32_t m) {
+    constexpr int B = 4;
+    uint32_t acc[4 * NQ];
+#pragma unroll
+    for (int f = 0; f < 4 * NQ; ++f) acc[f] = 0u;
+    for (int j = 0; j + B <= k; j += B) {
+        u4v_u w[B][NQ];
+#pragma unroll
+        for (int u = 0; u < B; ++u) {
+            const uint32_t len = tabs[j + u].len, magic = tabs[j + u].magic, t0 = tabs[j + u].t0;
+            const uint32_t UB_GLOBAL* g = (const uint32_t UB_GLOBAL*)(const UB_GLOBAL char*)tabs[j + u].p;
+            uint32_t idx = barrett_mod(t0 + m, len, magic);
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                w[u][q] = *(const u4v_u UB_GLOBAL*)(g + idx);
+                idx += 256u;
+                idx = min(idx, idx - len);   // (len >= 1 024: one wrap at most)
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < B; ++u)
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) { acc[4 * q] ^= w[u][q].x; acc[4 * q + 1] ^= w[u][q].y; acc[4 * q + 2] ^= w[u][q].z; acc[4 * q + 3] ^= w[u][q].w; }
+    }
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        const uint32_t mm = m + 256u * q;
+        if (mm + 3 < M) {
+            f4v v0, v1;
+            v0.x = __uint_as_float(acc[4 * q] & 0x3FFFFFFFu); v0.y = __uint_as_float((acc[4 * q] >> 2) & 0x3FFFFFFFu);
+            v0.z = __uint_as_float(acc[4 * q + 1] & 0x3FFFFFFFu); v0.w = __uint_as_float((acc[4 * q + 1] >> 2) & 0x3FFFFFFFu);
+            v1.x = __uint_as_float(acc[4 * q + 2] & 0x3FFFFFFFu); v1.y = __uint_as_float((acc[4 * q + 2] >> 2) & 0x3FFFFFFFu);
+            v1.z = __uint_as_float(acc[4 * q + 3] & 0x3FFFFFFFu); v1.w = __uint_as_float((acc[4 * q + 3] >> 2) & 0x3FFFFFFFu);
+            *(f4v UB_GLOBAL*)((UB_GLOBAL char*)(out + 2 * (size_t)mm)) = v0;
+            *(f4v UB_GLOBAL*)((UB_GLOBAL char*)(out + 2 * (size_t)mm + 4)) = v1;
+        }
+    }
+}
+__global__ __launch_bounds__(256) void k_gather_ragged(const Tab* __restrict__ tabs_generic, int k, uint32_t M, float* __restrict__ out) {
+    const Tab UB_CONST* tabs = (const Tab UB_CONST*)(const UB_CONST char*)tabs_generic;
+    const tdsp::QuadRange wv = tdsp::wave_quads(tdsp::group_quads(blockIdx.x, gridDim.x, tdsp::quads_of(M)), __builtin_amdgcn_readfirstlane(threadIdx.x >> 6));
+    const uint32_t m = 256u * wv.q0 + 4u * (threadIdx.x & 63u);
+    if (wv.n == 4u) gather_ragged<4>(tabs, k, M, out, m);       // (one wave-uniform branch outside the source loop)
+    else if (wv.n == 3u) gather_ragged<3>(tabs, k, M, out, m);
+    else if (wv.n == 2u) gather_ragged<2>(tabs, k, M, out, m);
+    else if (wv.n == 1u) gather_ragged<1>(tabs, k, M, out, m);
+}
+static float run_ragged(const Tab* d_tabs, int k, uint32_t frames, float* d_out, uint32_t G) {
+    if (!tdsp::groups_ok(tdsp::quads_of(frames), G)) return 0.f;
+    hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
+    for (int w = 0; w < 5; ++w) hipLaunchKernelGGL(k_gather_ragged, dim3(G), dim3(256), 0, 0, d_tabs, k, frames, d_out);
+    hipEventRecord(e0, 0);
+    for (int i = 0; i < 50; ++i) hipLaunchKernelGGL(k_gather_ragged, dim3(G), dim3(256), 0, 0, d_tabs, k, frames, d_out);
+    hipEventRecord(e1, 0); hipEventSynchronize(e1);
+    float ms = 0; hipEventElapsedTime(&ms, e0, e1);
+    return ms / 50.f;
+}
 __global__ void k_fill(uint32_t* p, size_t n) {
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = (uint32_t)i * 2654435761u;
 }
@@ -113,6 +176,12 @@ int main() {
         printf("A (16 consecutive per lane)  B=1 %.4f ms %.0f GB/s   B=2 %.4f ms %.0f GB/s\n", a1, bytes / a1 / 1e6, a2, bytes / a2 / 1e6);
         printf("B (wave-coalesced quads)     B=1 %.4f ms %.0f GB/s   B=2 %.4f ms %.0f GB/s\n", b1, bytes / b1 / 1e6, b2, bytes / b2 / 1e6);
         printf("C (2 x 8 consecutive)        B=1 %.4f ms %.0f GB/s   B=2 %.4f ms %.0f GB/s\n", c1, bytes / c1 / 1e6, c2, bytes / c2 / 1e6);
+        const float b4 = run<1, 4>(d_tabs, k, frames, d_out);
+        printf("B, 704 workgroups            B=4 %.4f ms %.0f GB/s\n", b4, bytes / b4 / 1e6);
+        for (uint32_t G : {768u, 1024u, 1280u}) {
+            const float r = run_ragged(d_tabs, k, frames, d_out, G);
+            printf("R (ragged, %4u workgroups)   B=4 %.4f ms %.0f GB/s\n", G, r, r > 0.f ? bytes / r / 1e6 : 0.0);
+        }
     }
     return hipDeviceSynchronize() == hipSuccess ? 0 : 1;
 }
