@@ -200,8 +200,8 @@ int td_eq_coefficients(int kind, size_t sr, float freq_hz, float q, float gain_d
  * Under "band_mode" 2 / "sine_mode" 2 the estimate is carried through a delay vertex at the gain 1 + wet Hecho,
  * Hecho = 1 / (1 - feedback) the L2 gain of the echo path (G = [[gs, gc], [gc, gs]] is symmetric with eigenvalues feedback and
  * feedback (1 - 2 cross)): vertices upstream keep their scan / fast forms.
- * Not part of the vertex: a low-pass in the feedback path ("damping": its u[n-1] term couples the D recurrences), modulated or
- * fractional delay times, tempo sync, a tail past the project's end. */
+ * Not part of the vertex: a low-pass in the feedback path ("damping": its u[n-1] term couples the D recurrences; the reverb vertex
+ * has one, by another kernel shape), modulated or fractional delay times, tempo sync, a tail past the project's end. */
 int td_graph_add_delay(td_graph* g, const char* name, float gain, float angle, float wet, float time_ms, float feedback,
                        float cross);
 /* Host only, no GPU: the delay vertex' constants at rate sr -- out[0 .. 3] = D, gs, gc, Hecho as the engine uses them.  The same
@@ -306,6 +306,42 @@ int td_graph_add_chorus(td_graph* g, const char* name, float gain, float angle, 
 /* Host only, no GPU: the chorus vertex' constants at rate sr -- out[0 .. 5] = D0, A, f, H (frames of the line), s (the largest
  * delay slope) and Hch as the engine uses them.  The same range checks as td_graph_add_chorus. */
 int td_chorus_params(size_t sr, int voices, float delay_ms, float depth_ms, float rate_hz, float stereo, int shape, double out[6]);
+/* A reverb vertex: a damped comb bank and an all-pass chain -- THIS ENGINE'S OWN: no reference counterpart (the reference reaches
+ * reverb only through LV2 plugins, add_lv2fx, which this engine parses and drops).  The topology is the
+ * public-domain Freeverb's: per channel 8 parallel feedback combs with a one-pole low-pass in the feedback path ("damping": the
+ * u[n-1] term the delay vertex leaves out), then 4 all-pass sections in series.  The vertex sums its inputs like every input vertex
+ * (sum_inputs, extensions.rs:310-319), processes, mixes with `wet` by the reference's f32 lerp, then pan and gain like every vertex
+ * (extensions.rs:262-263).
+ *   Everything is f64 on the f32 summed input x, with no FMA contraction, in exactly the order written here.
+ *   Constants, once on the host from the f32 parameters widened:  g = 0.7 + 0.28 room,  d1 = 0.4 damp,  d2 = 1 - d1,
+ *     w1 = (1 + width) / 2,  w2 = (1 - width) / 2.
+ *   Tunings in frames at 44.1 kHz:  combs 1116, 1188, 1277, 1356, 1422, 1491, 1557, 1617;  all-passes 556, 441, 341, 225.
+ *   Line lengths:  D = llround(tuning size sr / 44100) on the left,  llround((tuning + 23) size sr / 44100) on the right
+ *     (D_c the combs', E_a the all-passes').
+ *   Per frame n, xs = x where finite, else 0:   in = (xsl + xsr) 0.015
+ *   Per channel, combs c = 0 .. 7 ascending, S = 0.0 first:
+ *     w = cline_c[n - D_c];   f_c = w d2 + f_c d1;   cline_c[n] = in + f_c g;   S = S + w
+ *   Per channel, all-passes a = 0 .. 3 in series, s = S first:
+ *     v = aline_a[n - E_a];   y = v - s;   aline_a[n] = s + v 0.5;   s = y          then A_ch = s
+ *   Output:  pl = (float)(Al w1 + Ar w2),  pr = (float)(Ar w1 + Al w2);
+ *     out = x + wet * (p - x) in f32 with the raw input (adsr.rs:42); then pan and gain.  A non-finite x[n] makes frame n of the
+ *     output non-finite and enters the lines as 0: the lines never hold a NaN.
+ *   wet < 0.0001: the summed input passes through untouched (a plain k_sum launch) and the state stays as it is.
+ * State: the 24 lines and the 16 f_c, all doubles, one block of device memory (counted by td_graph_device_bytes, allocated when
+ * the vertex is first rendered, 8 (16 + the sum of the line lengths) bytes: 204 KB at 44.1 kHz and size 1); frame m of a line,
+ * counted from the restart, lives in slot m mod D, a read of m - D < 0 is 0; silent at the start, carried between consecutive
+ * block pulls and between the chunks of a render, restarted from silence by td_graph_set_time / td_graph_change_time /
+ * td_graph_reset.  A render ends where the project ends: no tail is appended.
+ * Ranges, rejected with a td_last_error that names the parameter (NaN included): room, damp, width [0, 1]; size [0.5, 2], and the
+ * shortest of the 24 lines must be at least 64 frames (at a low sample rate the error names size).  `wet` is clamped to [0, 1].
+ * Under "band_mode" 2 / "sine_mode" 2 the estimate is carried through a reverb vertex at the gain (1 - wet) + wet Hrev, Hrev =
+ * 0.03 x 8 / (1 - g) x (5/3)^4 an L2 bound of x -> p (DESIGN.md 3r has the proof): vertices upstream keep their scan / fast forms.
+ * Not part of the vertex: pre-delay, a tail past the project's end, modulated lines, convolution. */
+int td_graph_add_reverb(td_graph* g, const char* name, float gain, float angle, float wet, float room, float damp, float width, float size);
+/* Host only, no GPU: the reverb vertex' constants at rate sr -- out[0 .. 4] = g, d1, d2, w1, w2; out[5] = Hrev; out[6] = B, the
+ * frames per window of k_reverb at the default "debug.reverb_block"; out[7 .. 30] = the line lengths: left combs, right combs,
+ * left all-passes, right all-passes.  The same range checks as td_graph_add_reverb. */
+int td_reverb_params(size_t sr, float room, float damp, float width, float size, double out[31]);
 int td_graph_connect(td_graph* g, const char* a, const char* b);          /* graph.rs:80-96 (+58-78) */
 int td_graph_set_output(td_graph* g, const char* vertex);                 /* graph.rs:141-148 */
 int td_graph_check(const td_graph* g);                                    /* check_graph graph.rs:150-174 */
@@ -508,6 +544,9 @@ size_t td_cached_memory_bytes(void);
  *     timed; tests/test_gpu_saturator.py) /
  *   debug.chorus_tile 256|512|1024 (output frames per workgroup of the chorus vertex' k_chorus; 256 is provisional: nothing was
  *     timed; tests/test_gpu_chorus.py) /
+ *   debug.reverb_form 0|1 (the reverb vertex' k_reverb: 0 walks each comb's one-pole serially in the definition's order -- the
+ *     numpy twin's bits -- 1 scans it across the wave; the default is the faster row of profiles/reverb_time.txt) /
+ *   debug.reverb_block 64|128|256 (the cap of k_reverb's frames per window; tests/test_gpu_reverb.py) /
  *   debug.band_quick n, debug.band_medium n, debug.band_short n, debug.band_warmup n, debug.band_live_exp n, debug.band_depth n
  *     (the exact band-pass' speculative warm-up lengths in 1 / gamma frames and its liveness thresholds: speed only, the
  *     bit-wise check and repair of k_band_fix keep every result exact; tests/test_gpu_quirks.py, tools/band_*_sweep.py).

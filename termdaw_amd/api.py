@@ -75,6 +75,8 @@ SIGNATURES = {
     "td_saturator_params": (_i32, [_i32, _i32, _f32, _f32, _f32, C.POINTER(C.c_double)]),
     "td_graph_add_chorus": (_i32, [_vp, _cp, _f32, _f32, _f32, _i32, _f32, _f32, _f32, _f32, _i32]),
     "td_chorus_params": (_i32, [_sz, _i32, _f32, _f32, _f32, _f32, _i32, C.POINTER(C.c_double)]),
+    "td_graph_add_reverb": (_i32, [_vp, _cp, _f32, _f32, _f32, _f32, _f32, _f32, _f32]),
+    "td_reverb_params": (_i32, [_sz, _f32, _f32, _f32, _f32, C.POINTER(C.c_double)]),
     "td_graph_connect": (_i32, [_vp, _cp, _cp]),
     "td_graph_set_output": (_i32, [_vp, _cp]),
     "td_graph_check": (_i32, [_vp]),
@@ -345,6 +347,18 @@ def chorus_params(sr, voices, delay_ms, depth_ms, rate_hz, stereo, shape):
     return float(out[0]), float(out[1]), float(out[2]), int(out[3]), float(out[4]), float(out[5])
 
 
+def reverb_params(sr, room, damp, width, size):
+    """The reverb vertex' constants at rate sr (host only), exactly as the engine uses them: a dict with g, d1, d2, w1, w2, Hrev
+    (the gain the guard carries its estimate through the wet path at), B (the window length at the default cap) and the line
+    lengths in frames: combs_l, combs_r (8 each), allpass_l, allpass_r (4 each)."""
+    out = (C.c_double * 31)()
+    _check(lib().td_reverb_params(int(sr), room, damp, width, size, out))
+    o = [float(x) for x in out]
+    return {"g": o[0], "d1": o[1], "d2": o[2], "w1": o[3], "w2": o[4], "Hrev": o[5], "B": int(o[6]),
+            "combs_l": [int(x) for x in o[7:15]], "combs_r": [int(x) for x in o[15:23]],
+            "allpass_l": [int(x) for x in o[23:27]], "allpass_r": [int(x) for x in o[27:31]]}
+
+
 def loudness_filters(sr):
     """The meter's filters at rate sr (host only): (shelf (b, a), high-pass (b, a)) as float64 arrays with a[0] = 1, and the
     true-peak FIR as a (phases, taps) float32 array (phase 0 the unit impulse)."""
@@ -549,6 +563,11 @@ class Graph:
         """A chorus vertex: LFO-modulated fractional delay lines (this engine's own; the definition is in include/termdaw_amd.h).
         voices: 1 .. 4; shape: a name of CHORUS_SHAPES or its TD_CHORUS_* index.  The vertex has no latency."""
         _check(lib().td_graph_add_chorus(self.h, name.encode(), gain, angle, wet, int(voices), delay_ms, depth_ms, rate_hz, stereo, chorus_shape(shape)))
+
+    def add_reverb(self, name, gain, angle, wet, room, damp, width, size):
+        """A reverb vertex: 8 damped feedback combs and 4 all-pass sections per channel (this engine's own; the definition is in
+        include/termdaw_amd.h).  room, damp, width: [0, 1]; size: [0.5, 2], a factor on every line's length."""
+        _check(lib().td_graph_add_reverb(self.h, name.encode(), gain, angle, wet, room, damp, width, size))
 
     def connect(self, a, b):
         return bool(lib().td_graph_connect(self.h, a.encode(), b.encode()))

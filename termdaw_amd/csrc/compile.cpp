@@ -8,6 +8,7 @@
 #include "compile.h"
 #include "delay_math.h"
 #include "eq_math.h"
+#include "reverb_math.h"
 #include "sat_math.h"
 
 #include <math.h>
@@ -30,7 +31,8 @@ const char* const kFamilyName[F_COUNT] = {"k_sample_loop", "k_sample_multi", "k_
                                            "k_eq_local", "k_eq_carry", "k_eq_apply",
                                            "k_delay_local", "k_delay_carry", "k_delay_apply",
                                            "k_sat_sum", "k_sat", "k_sat1",
-                                           "k_chorus_sum", "k_chorus"};
+                                           "k_chorus_sum", "k_chorus",
+                                           "k_reverb_sum", "k_reverb"};
 
 
 // ------------------------------------------------------------------------------------------------
@@ -942,6 +944,13 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                 // a chorus is linear (and time-varying): the estimate goes through it at (1 - wet) + wet Hch, Hch an L2 bound of the
                 // modulated four-point read
                 if (wv.kind == K_CHORUS && !(wv.wet < 0.0001f)) L *= (1.0 - (double)wv.wet) + (double)wv.wet * chorus::kHch;
+                // a reverb is linear and time-invariant: the estimate goes through it at (1 - wet) + wet Hrev, Hrev the product of its
+                // stages' largest gains
+                if (wv.kind == K_REVERB && !(wv.wet < 0.0001f)) {
+                    double c[reverb::kParams];
+                    reverb::params(sr, wv.reverb_room, wv.reverb_damp, wv.reverb_width, wv.reverb_size, c);
+                    L *= (1.0 - (double)wv.wet) + (double)wv.wet * c[5];
+                }
                 if (wv.kind == K_ADSR && !(wv.wet < 0.0001f)) {   // |lerp(1, level x vel, wet)| <= max(1, |level| |vel|)
                     const AdsrConfD& c = wv.conf;
                     double lv = std::max(std::max(fabs((double)c.std_vel), fabs((double)c.attack_vel)),
@@ -1503,6 +1512,14 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                     } else {
                         if (M > 0xF0000000ull || (M + g->chorus_tile - 1) / g->chorus_tile >= 0x100000ull) return fail("chorus: chunk too long");
                         fam_v[F_CHORUS].push_back(vi);
+                    }
+                    break;
+                case K_REVERB:
+                    if (v.wet < 0.0001f) {
+                        fam_v[F_SUM].push_back(vi);   // the summed input passes through, the state stays
+                    } else {
+                        if (M > 0xF0000000ull) return fail("reverb: chunk too long");
+                        fam_v[F_REVERB].push_back(vi);
                     }
                     break;
                 default: break;
@@ -2560,6 +2577,54 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                     add_launch(F_CHORUS, off, (int)vs.size(), chorus_aux(n_tiles, !multi), lv);
                     continue;
                 }
+                case F_REVERB: {   // the launches of the level's reverb vertices (kernels.h ReverbDesc)
+                    std::vector<ReverbDesc> d;
+                    for (size_t vi : vs) {
+                        Vertex& v = g->vertices[vi];
+                        double c[reverb::kParams];
+                        reverb::params(sr, v.reverb_room, v.reverb_damp, v.reverb_width, v.reverb_size, c);
+                        ReverbDesc x{};
+                        x.x = take_buffer(g);
+                        if (!x.x) return fail("termdaw_amd: out of device memory for edge buffers");
+                        level_tmp.push_back(x.x);
+                        x.out = g->vbuf[vi];
+                        // (a set_time since the vertex last ran: the lines and the one-pole states restart from zero -- consumed here, like a delay's)
+                        if (v.first_pending) v.reverb_total = 0;
+                        v.first_pending = false;
+                        uint32_t at = 16, shortest = 0xFFFFFFFFu;
+                        for (int i = 0; i < reverb::kLines; ++i) {
+                            const uint32_t D = (uint32_t)c[7 + i];
+                            x.len[i] = D;
+                            x.off[i] = at;
+                            x.pos[i] = (uint32_t)(v.reverb_total % D);
+                            x.skip[i] = v.reverb_total < D ? (uint32_t)(D - v.reverb_total) : 0u;
+                            at += D;
+                            shortest = std::min(shortest, D);
+                        }
+                        x.state = take_reverb_state(g, v, at);
+                        if (!x.state) return fail("termdaw_amd: out of device memory for a reverb vertex' lines");
+                        x.fresh = v.reverb_total == 0 ? 1u : 0u;
+                        v.reverb_total += M;
+                        x.k = (uint32_t)g->edges[vi].size();
+                        x.term_mode = term_mode[vi];
+                        x.frames = (uint32_t)M;
+                        x.B = reverb::window(shortest, g->reverb_block);
+                        x.wet = v.wet;
+                        x.g = c[0];
+                        x.d1 = c[1];
+                        x.d2 = c[2];
+                        x.w1 = c[3];
+                        x.w2 = c[4];
+                        reverb::powers(x.d1, x.B / 64u, x.pw);
+                        x.pg = make_pg(v.gain, v.angle);
+                        d.push_back(x);
+                    }
+                    off = st.put(d);
+                    for (size_t i = 0; i < vs.size(); ++i) ptr_field(off + i * sizeof(ReverbDesc), offsetof(ReverbDesc, ins), ins_off[vs[i]]);
+                    add_launch(F_REVERB_SUM, off, (int)vs.size(), 0, lv);
+                    add_launch(F_REVERB, off, (int)vs.size(), g->reverb_form, lv);
+                    continue;
+                }
                 default: continue;
             }
             if (fam == F_SUM || fam == F_ADSR) {   // split at term-mode boundaries (vs is sorted by it)
@@ -2756,6 +2821,8 @@ size_t desc_size(int fam) {
         case F_SAT1: return sizeof(SatDesc);
         case F_CHORUS_SUM:
         case F_CHORUS: return sizeof(ChorusDesc);
+        case F_REVERB_SUM:
+        case F_REVERB: return sizeof(ReverbDesc);
         default: return 0;
     }
 }

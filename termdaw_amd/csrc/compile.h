@@ -18,6 +18,7 @@ enum Family { F_LOOP, F_MULTI, F_LERP, F_SINE, F_SYNTH, F_SAMPSYN, F_ENV, F_PROB
               F_DELAY_LOCAL, F_DELAY_CARRY, F_DELAY_APPLY /* a level's delay vertices: k_delay_local, k_delay_carry (both over the vertices whose chunk takes more than one tile only), k_delay_apply -- in this order */,
               F_SAT_SUM, F_SAT, F_SAT1 /* a level's saturator vertices: k_sat_sum (over the vertices whose chunk takes more than one tile only), k_sat (one launch per oversampling factor), k_sat1 (R = 1) */,
               F_CHORUS_SUM, F_CHORUS /* a level's chorus vertices: k_chorus_sum (when the chunk is longer than the one-launch form takes), k_chorus */,
+              F_REVERB_SUM, F_REVERB /* a level's reverb vertices: k_reverb_sum, k_reverb -- in this order */,
               F_COUNT };
 extern const char* const kFamilyName[F_COUNT];
 
@@ -39,6 +40,7 @@ int ensure_buffers(td_graph* g, size_t frames);                      // the edge
 double* take_delay_line(td_graph* g, tde::Vertex& v, size_t D);    // a delay vertex' line, allocated on first use (nullptr: out of device memory)
 float2* take_sat_line(td_graph* g, tde::Vertex& v);                  // a saturator vertex' line, allocated on first use (nullptr: out of device memory)
 float2* take_chorus_line(td_graph* g, tde::Vertex& v, size_t H);    // a chorus vertex' line (two halves of H frames), allocated on first use (nullptr: out of device memory)
+double* take_reverb_state(td_graph* g, tde::Vertex& v, size_t doubles);   // a reverb vertex' state block, allocated on first use (nullptr: out of device memory)
 float2* take_buffer(td_graph* g);                                    // one edge buffer (nullptr: out of device memory)
 
 }  // namespace tde

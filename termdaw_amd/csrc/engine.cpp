@@ -13,6 +13,7 @@
 #include "comm.h"
 #include "compile.h"
 #include "delay_math.h"
+#include "reverb_math.h"
 #include "devmem.h"
 #include "eq_math.h"
 #include "midi.h"
@@ -601,21 +602,34 @@ float2* take_chorus_line(td_graph* g, Vertex& v, size_t H) {
     v.chorus_parity = 0;
     return p;
 }
+// The state block of a reverb vertex: f[16] and the 24 lines, doubles, kept in the same list; never cleared either
+// (Vertex::reverb_total says which of its words hold values).
+double* take_reverb_state(td_graph* g, Vertex& v, size_t doubles) {
+    if (v.reverb_state) return v.reverb_state;
+    double* p = nullptr;
+    if (hipMalloc(&p, doubles * sizeof(double)) != hipSuccess) return nullptr;
+    g->delay_lines.push_back({p, doubles * sizeof(double)});
+    g->device_bytes += doubles * sizeof(double);
+    v.reverb_state = p;
+    v.reverb_total = 0;
+    return p;
+}
 // the line a vertex would continue from in its next submission (nullptr: none -- it has none yet, or it starts afresh)
 static void* vertex_line(Vertex& v) {
-    return v.kind == K_SATURATOR ? (void*)v.sat_line : v.kind == K_CHORUS ? (void*)v.chorus_line : (void*)v.delay_line;
+    return v.kind == K_SATURATOR ? (void*)v.sat_line : v.kind == K_CHORUS ? (void*)v.chorus_line : v.kind == K_REVERB ? (void*)v.reverb_state : (void*)v.delay_line;
 }
 static const void* carried_line(const Vertex& v) {
     if (v.first_pending) return nullptr;
     if (v.kind == K_DELAY && v.delay_line && v.delay_total) return v.delay_line;
     if (v.kind == K_SATURATOR && v.sat_line && v.sat_total) return v.sat_line;
     if (v.kind == K_CHORUS && v.chorus_line && v.chorus_total) return v.chorus_line;
+    if (v.kind == K_REVERB && v.reverb_state && v.reverb_total) return v.reverb_state;
     return nullptr;
 }
 static void free_delay_lines(td_graph* g) {
     for (auto& l : g->delay_lines) { (void)hipFree(l.first); g->device_bytes -= l.second; }
     g->delay_lines.clear();
-    for (auto& v : g->vertices) { v.delay_line = nullptr; v.sat_line = nullptr; v.chorus_line = nullptr; }
+    for (auto& v : g->vertices) { v.delay_line = nullptr; v.sat_line = nullptr; v.chorus_line = nullptr; v.reverb_state = nullptr; }
 }
 float2* take_buffer(td_graph* g) {
     if (!g->free_bufs.empty()) {
@@ -964,6 +978,8 @@ static int submit_chunk(Arena& ar, ChunkBuild& cb, hipStream_t stream, ProfCtx& 
                 case F_SAT: launch_sat((const SatDesc*)d, L.n, (L.aux >> 24) & 15u, L.aux & 0xFFFFFu, ((L.aux >> 20) & 15u) * 128u, (L.aux & kSatTermsBit) != 0u, s); break;
                 case F_SAT1: launch_sat1((const SatDesc*)d, L.n, L.M, s); break;
                 case F_CHORUS_SUM: launch_chorus_sum((const ChorusDesc*)d, L.n, L.M, s); break;   // (likewise)
+                case F_REVERB_SUM: launch_reverb_sum((const ReverbDesc*)d, L.n, L.M, s); break;   // (likewise)
+                case F_REVERB: launch_reverb((const ReverbDesc*)d, L.n, L.aux, s); break;
                 case F_CHORUS: launch_chorus((const ChorusDesc*)d, L.n, L.aux & 0xFFFFFu, L.M, (L.aux & kChorusTermsBit) != 0u, s); break;
             }
         }
@@ -1064,6 +1080,10 @@ static int prepare_render(td_graph* g, size_t n_blocks, int bits, bool want_pcm,
         for (size_t vi : g->order)
             if (g->vertices[vi].kind == K_CHORUS && !(g->vertices[vi].wet < 0.0001f))
                 return fail("termdaw_amd: this build has no k_chorus kernels: chorus vertices cannot be rendered");
+    if (!(launch_reverb_sum && launch_reverb))
+        for (size_t vi : g->order)
+            if (g->vertices[vi].kind == K_REVERB && !(g->vertices[vi].wet < 0.0001f))
+                return fail("termdaw_amd: this build has no k_reverb kernels: reverb vertices cannot be rendered");
     const size_t bl = g->bl;
     if (bl == 0) return fail("termdaw_amd: buffer length 0");
     rp->n_blocks = n_blocks;
@@ -1170,6 +1190,7 @@ static bool starts_afresh(const td_graph* g) {
         if (v.kind == K_DELAY && v.delay_line && !v.first_pending) return false;
         if (v.kind == K_SATURATOR && v.sat_line && !v.first_pending) return false;
         if (v.kind == K_CHORUS && v.chorus_line && !v.first_pending) return false;
+        if (v.kind == K_REVERB && v.reverb_state && !v.first_pending) return false;
     }
     return true;
 }
@@ -1210,7 +1231,7 @@ static int guard_begin(td_graph* g, const td_samplebank* sb, td_flowwbank* fb, s
         TD_HIP(hipMemcpyAsync(q.d_backup, g->dstate, n * sizeof(StateSlot), hipMemcpyDeviceToDevice, g->stream));
         q.have_backup = true;
     }
-    // the lines of the delay, saturator and chorus vertices that continue from what they hold (a vertex with a set_time pending reads nothing
+    // the lines of the delay, saturator, chorus and reverb vertices that continue from what they hold (a vertex with a set_time pending reads nothing
     // of its line)
     q.lines.clear();
     size_t need = 0;
@@ -1299,6 +1320,7 @@ void HostSnapshot::take(const td_graph* g, const td_flowwbank* fb) {
         v[i].sat_parity = x.sat_parity;
         v[i].chorus_total = x.chorus_total;
         v[i].chorus_parity = x.chorus_parity;
+        v[i].reverb_total = x.reverb_total;
         v[i].has_init_override = x.has_init_override;
         v[i].peak_known = x.peak_known;
         v[i].first_pending = x.first_pending;
@@ -1319,6 +1341,7 @@ void HostSnapshot::put(td_graph* g, td_flowwbank* fb) const {
         x.sat_parity = v[i].sat_parity;
         x.chorus_total = v[i].chorus_total;
         x.chorus_parity = v[i].chorus_parity;
+        x.reverb_total = v[i].reverb_total;
         x.has_init_override = v[i].has_init_override;
         x.peak_known = v[i].peak_known;
         x.first_pending = v[i].first_pending;
@@ -1400,6 +1423,7 @@ static int graph_set_time_impl(td_graph* g, size_t time) {   // graph.rs:123-128
             case K_DELAY:   // the line restarts from zero: the next submission reads none of its words
             case K_SATURATOR:
             case K_CHORUS:
+            case K_REVERB:
                 v.first_pending = true;
                 break;
             default: break;
@@ -2017,6 +2041,24 @@ int td_chorus_params(size_t sr, int voices, float delay_ms, float depth_ms, floa
     if (!out) return fail("chorus_params: out is null");
     if (const char* why = chorus::check(sr, voices, delay_ms, depth_ms, rate_hz, stereo, shape)) return fail(std::string("chorus: ") + why);
     chorus::params(sr, voices, delay_ms, depth_ms, rate_hz, stereo, shape, out);
+    return 1;
+}
+
+// This engine's own reverb vertex (no reference counterpart; the definition is in include/termdaw_amd.h).
+int td_graph_add_reverb(td_graph* g, const char* name, float gain, float angle, float wet, float room, float damp, float width, float size) {
+    if (const char* why = reverb::check(g->sr, room, damp, width, size)) return fail(std::string("reverb: ") + why);
+    Vertex& v = add_vertex(g, name, gain, angle, wet, K_REVERB);
+    v.reverb_room = room;
+    v.reverb_damp = damp;
+    v.reverb_width = width;
+    v.reverb_size = size;
+    v.first_pending = true;   // (the state block, once it exists, is read only where the vertex itself has written it)
+    return 1;
+}
+int td_reverb_params(size_t sr, float room, float damp, float width, float size, double out[31]) {
+    if (!out) return fail("reverb_params: out is null");
+    if (const char* why = reverb::check(sr, room, damp, width, size)) return fail(std::string("reverb: ") + why);
+    reverb::params(sr, room, damp, width, size, out);
     return 1;
 }
 
@@ -2779,6 +2821,7 @@ static std::vector<OptionRef> option_table(td_graph* g) {
         {"debug.single_pass_normalize", 0, &g->single_pass_normalize}, {"debug.fuse_normalize", 0, &g->fuse_normalize},
         {"debug.table_cache", 0, &g->table_cache}, {"debug.band_serial", 0, &g->band_serial}, {"debug.band_chain", 0, &g->band_chain}, {"debug.band_scan_nf", 1, &g->band_scan_nf},
         {"debug.delay_tile", 2, &g->delay_tile}, {"debug.sat_tile", 2, &g->sat_tile}, {"debug.chorus_tile", 2, &g->chorus_tile},
+        {"debug.reverb_form", 2, &g->reverb_form}, {"debug.reverb_block", 2, &g->reverb_block},
         {"debug.band_quick", 2, &g->band_quick}, {"debug.band_short", 2, &g->band_short}, {"debug.band_medium", 2, &g->band_medium},
         {"debug.band_warmup", 2, &g->band_warmup}, {"debug.band_depth", 2, &g->band_depth},
         {"debug.stem_taps", 2, &g->stem_taps},
@@ -2826,6 +2869,16 @@ int td_graph_set_option(td_graph* g, const char* key, long value) {
     if (k == "debug.chorus_tile") {
         if (value != 256 && value != 512 && value != 1024) return fail("debug.chorus_tile must be 256, 512 or 1024");
         g->chorus_tile = (unsigned)value;
+        return 1;
+    }
+    if (k == "debug.reverb_form") {
+        if (value != 0 && value != 1) return fail("debug.reverb_form must be 0 (serial) or 1 (scan)");
+        g->reverb_form = (unsigned)value;
+        return 1;
+    }
+    if (k == "debug.reverb_block") {
+        if (value != 64 && value != 128 && value != 256) return fail("debug.reverb_block must be 64, 128 or 256");
+        g->reverb_block = (unsigned)value;
         return 1;
     }
     if (k == "debug.band_live_exp") { g->band_live_thr = value >= 38 ? 0.0f : powf(10.0f, -(float)value); return 1; }

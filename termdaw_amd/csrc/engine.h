@@ -76,7 +76,7 @@ struct td_flowwbank {
 namespace tde {
 
 enum Kind { K_SUM, K_NORMALIZE, K_SAMPLE_LOOP, K_SAMPLE_MULTI, K_SAMPLE_LERP, K_DEBUG_SINE, K_SYNTH,
-            K_SAMPSYN, K_ADSR, K_BAND_PASS, K_COMPRESSOR, K_EQ, K_DELAY, K_SATURATOR, K_CHORUS, K_COUNT };
+            K_SAMPSYN, K_ADSR, K_BAND_PASS, K_COMPRESSOR, K_EQ, K_DELAY, K_SATURATOR, K_CHORUS, K_REVERB, K_COUNT };
 
 struct SineNote { float note, vel; };
 struct SynthNote { float note, vel, env_t, rel_t, hz; };   // hz = 440 * 2^((note - 69) / 12), extensions.rs:503
@@ -136,6 +136,9 @@ struct Vertex {
     float2* chorus_line = nullptr;  // K_CHORUS: the last H raw input frames, two halves of H float2 used alternately (owned by the graph: td_graph::delay_lines), allocated when the vertex is first compiled into a submission
     uint64_t chorus_total = 0;      // K_CHORUS: frames the vertex has run since its line restarted (a frame beyond min(this, H) back reads as 0)
     uint32_t chorus_parity = 0;     // K_CHORUS: the half of the line the next launch reads (the one the last launch wrote)
+    float reverb_room = 0.5f, reverb_damp = 0.5f, reverb_width = 1.0f, reverb_size = 1.0f;   // K_REVERB
+    double* reverb_state = nullptr;   // K_REVERB: f[16] and the 24 lines, one block of doubles (owned by the graph: td_graph::delay_lines), allocated when the vertex is first compiled into a submission
+    uint64_t reverb_total = 0;        // K_REVERB: frames the vertex has run since its restart (frame m of a line lives in slot m mod D; a read of m - D < 0 is 0)
     tdk::WaveTableD wavetable{};   // K_SAMPSYN: table in HBM (owned by the graph)
     // carried host state (what the reference keeps inside VertexExt, extensions.rs:15-80)
     uint64_t loop_t = 0;
@@ -149,7 +152,7 @@ struct Vertex {
     // carried device state slot (Normalize / BandPass / Compressor / Eq), index into Graph::dstate
     int state_slot = -1;
     // reset_normalization (extensions.rs:295-299) is kept on the host until the next render consumes it
-    bool first_pending = false;         // band-pass, compressor, eq, delay, saturator, chorus (their state then restarts from zero): set_time since the vertex was last compiled into a submission (its descriptor's first_override)
+    bool first_pending = false;         // band-pass, compressor, eq, delay, saturator, chorus, reverb (their state then restarts from zero): set_time since the vertex was last compiled into a submission (its descriptor's first_override)
     bool has_init_override = false;
     float init_override = 0.0f;
     // Normalize: the carried max is the result of a normalize scan (graph.rs:222-237), so a render is expected to
@@ -158,7 +161,7 @@ struct Vertex {
     std::shared_ptr<TableCache> tables;   // event-driven kinds only (shared_ptr: Vertex stays copyable)
     bool has_input() const {
         return kind == K_SUM || kind == K_NORMALIZE || kind == K_ADSR || kind == K_BAND_PASS || kind == K_COMPRESSOR || kind == K_EQ ||
-               kind == K_DELAY || kind == K_SATURATOR || kind == K_CHORUS;
+               kind == K_DELAY || kind == K_SATURATOR || kind == K_CHORUS || kind == K_REVERB;
     }
 };
 
@@ -316,7 +319,7 @@ namespace tde {
 struct HostSnapshot {
     size_t t = 0, fb_frame = 0;
     std::vector<size_t> fb_start;
-    struct V { uint64_t loop_t, delay_total, sat_total, chorus_total; uint32_t sat_parity, chorus_parity; bool has_init_override, peak_known, first_pending; float init_override; std::string state; };
+    struct V { uint64_t loop_t, delay_total, sat_total, chorus_total, reverb_total; uint32_t sat_parity, chorus_parity; bool has_init_override, peak_known, first_pending; float init_override; std::string state; };
     std::vector<V> v;
     void take(const td_graph* g, const td_flowwbank* fb);
     void put(td_graph* g, td_flowwbank* fb) const;
@@ -348,7 +351,7 @@ struct Guard {
     bool have_backup = false;
     void* d_backup = nullptr;        // StateSlot[backup_cap]
     size_t backup_cap = 0;
-    // ... and the lines of the reachable delay, saturator and chorus vertices that do not start afresh, back to back in d_lines (allocated on first need)
+    // ... and the lines of the reachable delay, saturator, chorus and reverb vertices that do not start afresh, back to back in d_lines (allocated on first need)
     struct LineCopy { size_t vertex, off, bytes; };
     std::vector<LineCopy> lines;
     void* d_lines = nullptr;
@@ -374,9 +377,11 @@ struct td_graph {
     std::vector<int> level;                   // per vertex, -1 = unreachable
     int n_levels = 0;
     std::vector<float*> wavetables;            // device tables of K_SAMPSYN vertices
-    std::vector<std::pair<double*, size_t>> delay_lines;   // the lines of K_DELAY vertices (Vertex::delay_line) of K_SATURATOR vertices (Vertex::sat_line) and of K_CHORUS vertices (Vertex::chorus_line), and their bytes
+    std::vector<std::pair<double*, size_t>> delay_lines;   // the lines of K_DELAY vertices (Vertex::delay_line) of K_SATURATOR vertices (Vertex::sat_line) of K_CHORUS vertices (Vertex::chorus_line) and the state blocks of K_REVERB vertices (Vertex::reverb_state), and their bytes
     unsigned sat_tile = 256;                   // output frames per workgroup of k_sat (128 | 256 | 384: "debug.sat_tile"; provisional)
     unsigned chorus_tile = 256;                // output frames per workgroup of k_chorus (256 | 512 | 1024: "debug.chorus_tile"; provisional)
+    unsigned reverb_form = 1;                  // k_reverb: 0 the serial walk of each comb's one-pole, 1 the wave scan ("debug.reverb_form")
+    unsigned reverb_block = 256;               // the cap of k_reverb's window length B (64 | 128 | 256: "debug.reverb_block")
     unsigned delay_tile = 16;                  // steps per tile of the delay vertex' scan (8 | 16 | 32 | 64: "debug.delay_tile")
     std::vector<float2*> pool;                // every edge buffer ever allocated (cap_frames each)
     std::vector<float2*> free_bufs;

@@ -389,6 +389,35 @@ struct ChorusDesc {
     PanGain pg;
 };
 
+// A reverb vertex (k_reverb_sum / k_reverb; the definition is in include/termdaw_amd.h at td_graph_add_reverb):
+// per channel 8 parallel damped feedback combs, then 4 series all-pass sections, all in f64 on the f32 summed input.
+// ONE workgroup of kReverbThreads per vertex walks the chunk in windows of B frames, B <= the vertex' shortest line: inside a
+// window every delayed read line[n - D] is history, so a comb is a first-order recurrence with the constant coefficient d1 over
+// known data and the all-pass chain is elementwise.  Wave w owns comb w & 7 of channel w >> 3; a lane takes B / 64 consecutive
+// frames.  The windows are serial, everything inside one is parallel.
+// `state` is one block of doubles: f[16] (the combs' one-pole states, index = wave), then the 24 lines at off[i]; frame m of a line
+// (m counted from the vertex' restart) lives in slot m mod D, read and then rewritten by the same lane in the same window.  The
+// block is never cleared: a line's first `skip` frames of this chunk read as 0 (m - D < 0), and f reads as 0 when `fresh`.
+// Lines are indexed 0 .. 7 left combs, 8 .. 15 right combs, 16 .. 19 left all-passes, 20 .. 23 right all-passes.
+struct ReverbDesc {
+    const InTerm* ins;      // k input terms (kinds 0 .. 4), in connect() order
+    float2* x;              // [frames] the summed input (k_reverb_sum leaves it)
+    float2* out;
+    double* state;          // f[16], then the lines
+    uint32_t k, term_mode, frames;
+    uint32_t B;             // frames per window: 64 | 128 | 256, <= every len[]
+    uint32_t fresh;         // 1: the vertex has not run since its restart -- f reads as 0
+    float wet;
+    uint32_t len[24];       // D: frames of each line
+    uint32_t off[24];       // where each line starts in state[] (doubles)
+    uint32_t pos[24];       // (frames run since the restart) mod D: the slot of the chunk's first frame
+    uint32_t skip[24];      // the chunk's frames before this one read the line as 0: max(D - frames run since the restart, 0)
+    double g, d1, d2, w1, w2;
+    double pw[6];           // d1^((B / 64) 2^k): the wave scan's lane strides
+    PanGain pg;
+};
+constexpr int kReverbThreads = 1024;   // 16 wave64: one per (comb, channel)
+
 // sample_loop_gen (extensions.rs:331-341): out[m] = sample[(t0 + m) % len]
 struct LoopDesc {
     const float2* sample;
@@ -872,6 +901,10 @@ constexpr uint32_t kChorusTermsBit = 0x80000000u;
 inline uint32_t chorus_aux(uint32_t n_tiles, bool terms) { return n_tiles | (terms ? kChorusTermsBit : 0u); }
 __attribute__((weak)) void launch_chorus_sum(const ChorusDesc* d, int n_desc, uint32_t frames, hipStream_t s);
 __attribute__((weak)) void launch_chorus(const ChorusDesc* d, int n_desc, uint32_t n_tiles, uint32_t frames, bool terms, hipStream_t s);
+// Weak for the same reason: a level's reverb vertices.  launch_reverb_sum: grid.x from `frames`; launch_reverb: one workgroup per
+// descriptor, `form` 0 the serial walk of each comb's one-pole, 1 the wave scan.
+__attribute__((weak)) void launch_reverb_sum(const ReverbDesc* d, int n_desc, uint32_t frames, hipStream_t s);
+__attribute__((weak)) void launch_reverb(const ReverbDesc* d, int n_desc, uint32_t form, hipStream_t s);
 void launch_sinf(const float* in, float* out, uint32_t n, int exact, hipStream_t s);   // out[i] = sin_glibc(in[i]) (exact) or sin_any(in[i])
 void launch_debug_verify(const uint32_t* p, uint32_t n_words, const uint32_t* seg_sums, uint32_t* report, hipStream_t s);   // (TD_DEBUG_SYNC & 16)
 void launch_sample_loop(const LoopDesc* d, int n_desc, uint32_t frames, hipStream_t s);

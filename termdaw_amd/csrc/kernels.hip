@@ -2666,6 +2666,157 @@ __global__ __launch_bounds__(kThreads) void k_chorus(const ChorusDesc* __restric
 }
 
 // ------------------------------------------------------------------------------------------------
+// k_reverb_sum / k_reverb: the reverb vertex (kernels.h ReverbDesc).  No reference counterpart; the definition is
+// the header's (td_graph_add_reverb): 8 damped feedback combs per channel summed from 0.0 in ascending order, 4 series all-pass
+// sections, cross-mix, wet lerp, pan and gain -- f64 on the f32 summed input.
+// ------------------------------------------------------------------------------------------------
+TD_DEV double gloadd(const double* p) { return *reinterpret_cast<const double TD_GLOBAL*>((const TD_GLOBAL char*)p); }
+TD_DEV void gstored(double* p, double v) { *reinterpret_cast<double TD_GLOBAL*>((TD_GLOBAL char*)p) = v; }
+// the summed input, materialised once: k_sum's frame mapping, identity epilogue
+__global__ __launch_bounds__(kThreads) void k_reverb_sum(const ReverbDesc* __restrict__ descs) {
+    const ReverbDesc& d = descs[blockIdx.y];
+    const uint32_t M = d.frames, m0 = blockIdx.x * kTileFrames + 2u * threadIdx.x, m1 = m0 + kTileFrames / 2;
+    if (blockIdx.x * kTileFrames >= M) return;
+    float4 a0, a1;
+    sum_inputs_pairs(d.ins, d.k, d.term_mode, m0, m1, M, a0, a1);
+    store_pair(d.x, m0, M, a0);
+    store_pair(d.x, m1, M, a1);
+}
+constexpr uint32_t kReverbRow = 256;   // doubles per (comb, channel) row of the window's delayed reads in LDS
+// The chunk in windows of B = 64 Q frames.  Per window:
+//   combs (all 16 waves; a lane takes Q consecutive frames): w = cline[n - D] from global memory, kept in registers and left in
+//     LDS row `wave`; the one-pole f = w d2 + f d1 over the window -- FORM 0: every lane of the wave walks the window's B steps in
+//     the definition's order, in lockstep, the words passed round by shuffles, and keeps its own frames' values: nothing is
+//     re-associated; FORM 1: a lane-local pass from 0 (lane 0 from the carried f), a Hillis-Steele scan over the 64 lanes with the
+//     powers pw[k], and a lane-local pass again from the scanned carry -- then cline[n] = in + f g goes back to the slot w came from;
+//   one barrier (the LDS rows are double-buffered by the window's parity, so the next window's combs may start at once);
+//   all-passes and epilogue (threads 0 .. B - 1, one frame each, both channels): S from the 8 rows in ascending order, the 4
+//     sections elementwise on slots this thread alone touches in this window, cross-mix, lerp with the raw input, pan and gain.
+// A line written in one window is read in a later one by another lane: the barrier between them orders the two at workgroup
+// scope (one workgroup runs on one CU and its waves share the vector L1).
+template <int Q, int FORM>
+TD_DEV void reverb_windows(const ReverbDesc& d, double* wl) {
+    constexpr uint32_t B = 64u * Q;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const uint32_t M = d.frames;
+    const uint32_t cD = d.len[wave], cskip = d.skip[wave];
+    double* const cline = d.state + d.off[wave];
+    uint32_t cbase = d.pos[wave];
+    double fprev = d.fresh ? 0.0 : gloadd(d.state + wave);
+    const double g = d.g, d1 = d.d1, d2 = d.d2;
+    uint32_t abase[8];
+#pragma unroll
+    for (int a = 0; a < 8; ++a) abase[a] = d.pos[16 + a];
+    uint32_t par = 0;
+    for (uint32_t n0 = 0; n0 < M; n0 += B, par ^= 1u) {
+        const uint32_t Bw = min(B, M - n0);
+        double* const rows = wl + par * (16u * kReverbRow);
+        // ---- combs
+        double w[Q], in[Q], fv[Q];
+        uint32_t slot[Q];
+#pragma unroll
+        for (int i = 0; i < Q; ++i) {
+            const uint32_t j = lane * Q + i, n = n0 + j;
+            uint32_t s = cbase + j;   // (cbase < D and j < B <= D)
+            if (s >= cD) s -= cD;
+            slot[i] = s;
+            const bool live = j < Bw;
+            w[i] = live && n >= cskip ? gloadd(cline + s) : 0.0;
+            const float2 x = live ? gload2(d.x + n) : make_float2(0.f, 0.f);
+            const double xl = delay_finite(x.x) ? (double)x.x : 0.0, xr = delay_finite(x.y) ? (double)x.y : 0.0;
+            in[i] = (xl + xr) * 0.015;
+            rows[wave * kReverbRow + j] = w[i];
+        }
+        if (FORM == 0) {
+            double t = fprev;
+            for (uint32_t l = 0; l < 64u; ++l) {
+#pragma unroll
+                for (int i = 0; i < Q; ++i) {
+                    const double wv = __shfl(w[i], (int)l, 64);
+                    t = wv * d2 + t * d1;
+                    if (lane == l) fv[i] = t;
+                }
+            }
+        } else {
+            double t = lane == 0u ? fprev : 0.0;
+#pragma unroll
+            for (int i = 0; i < Q; ++i) t = w[i] * d2 + t * d1;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                const double u = __shfl_up(t, 1u << k, 64);
+                if (lane >= (1u << k)) t = t + d.pw[k] * u;
+            }
+            double c = __shfl_up(t, 1u, 64);
+            if (lane == 0u) c = fprev;
+#pragma unroll
+            for (int i = 0; i < Q; ++i) {
+                c = w[i] * d2 + c * d1;
+                fv[i] = c;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < Q; ++i)
+            if (lane * Q + i < Bw) gstored(cline + slot[i], in[i] + fv[i] * g);
+        {   // the window's last frame carries f on
+            const uint32_t lj = Bw - 1u;
+            double sel = fv[0];
+#pragma unroll
+            for (int i = 1; i < Q; ++i)
+                if ((lj & (uint32_t)(Q - 1)) == (uint32_t)i) sel = fv[i];
+            fprev = __shfl(sel, (int)(lj / Q), 64);
+        }
+        cbase += B;
+        if (cbase >= cD) cbase -= cD;
+        __syncthreads();
+        // ---- all-passes and epilogue
+        if (tid < Bw) {
+            const uint32_t j = tid, n = n0 + j;
+            const float2 x = gload2(d.x + n);
+            double* p[8];
+            double v[8], A[2];
+#pragma unroll
+            for (int a = 0; a < 8; ++a) {
+                const uint32_t E = d.len[16 + a];
+                uint32_t s = abase[a] + j;
+                if (s >= E) s -= E;
+                p[a] = d.state + d.off[16 + a] + s;
+                v[a] = n >= d.skip[16 + a] ? gloadd(p[a]) : 0.0;
+            }
+#pragma unroll
+            for (int ch = 0; ch < 2; ++ch) {
+                double s = 0.0;
+#pragma unroll
+                for (int c = 0; c < 8; ++c) s = s + rows[(ch * 8 + c) * kReverbRow + j];
+#pragma unroll
+                for (int a = 0; a < 4; ++a) {
+                    const double va = v[ch * 4 + a], y = va - s;
+                    gstored(p[ch * 4 + a], s + va * 0.5);
+                    s = y;
+                }
+                A[ch] = s;
+            }
+            const float pl = (float)(A[0] * d.w1 + A[1] * d.w2), pr = (float)(A[1] * d.w1 + A[0] * d.w2);
+            gstore2(d.out + n, epilogue(make_float2(x.x + d.wet * (pl - x.x), x.y + d.wet * (pr - x.y)), d.pg));
+        }
+#pragma unroll
+        for (int a = 0; a < 8; ++a) {
+            abase[a] += B;
+            if (abase[a] >= d.len[16 + a]) abase[a] -= d.len[16 + a];
+        }
+    }
+    if (lane == 0u) gstored(d.state + wave, fprev);
+}
+template <int FORM>
+__global__ __launch_bounds__(kReverbThreads) void k_reverb(const ReverbDesc* __restrict__ descs) {
+    __shared__ double wl[2u * 16u * kReverbRow];   // 64 KB: [parity][comb, channel][frame of the window]
+    const ReverbDesc& d = descs[blockIdx.y];
+    if (d.B == 256u) reverb_windows<4, FORM>(d, wl);
+    else if (d.B == 128u) reverb_windows<2, FORM>(d, wl);
+    else reverb_windows<1, FORM>(d, wl);
+}
+
+// ------------------------------------------------------------------------------------------------
 // k_sample_loop: out[m] = sample[(t0 + m) % len]   (extensions.rs:331-341)
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kThreads) void k_sample_loop(const LoopDesc* __restrict__ descs, uint32_t M) {
@@ -6232,6 +6383,16 @@ void launch_chorus(const ChorusDesc* d, int n, uint32_t n_tiles, uint32_t frames
     for (int o = 0; o < n && n_tiles; o += kMaxGridY) {
         if (terms) hipLaunchKernelGGL((k_chorus<true>), dim3(n_tiles, std::min(n - o, kMaxGridY)), dim3(kThreads), lds, s, d + o);
         else hipLaunchKernelGGL((k_chorus<false>), dim3(n_tiles, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
+    }
+}
+void launch_reverb_sum(const ReverbDesc* d, int n, uint32_t frames, hipStream_t s) {
+    for (int o = 0; o < n && frames; o += kMaxGridY)
+        hipLaunchKernelGGL(k_reverb_sum, dim3(tiles(frames), std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
+}
+void launch_reverb(const ReverbDesc* d, int n, uint32_t form, hipStream_t s) {
+    for (int o = 0; o < n; o += kMaxGridY) {
+        if (form == 0u) hipLaunchKernelGGL((k_reverb<0>), dim3(1, std::min(n - o, kMaxGridY)), dim3(kReverbThreads), 0, s, d + o);
+        else hipLaunchKernelGGL((k_reverb<1>), dim3(1, std::min(n - o, kMaxGridY)), dim3(kReverbThreads), 0, s, d + o);
     }
 }
 void launch_sample_loop(const LoopDesc* d, int n, uint32_t frames, hipStream_t s) {

@@ -169,7 +169,7 @@ class ProjectScript:
         self.calls = {k: [] for k in (
             "load_sample", "load_resource", "load_midi_floww", "add_sum", "add_normalize", "add_sampleloop",
             "add_sample_multi", "add_sample_lerp", "add_debug_sine", "add_synth", "add_sampsyn", "add_adsr",
-            "add_bandpass", "add_compressor", "add_eq", "add_delay", "add_saturator", "add_chorus", "connect")}
+            "add_bandpass", "add_compressor", "add_eq", "add_delay", "add_saturator", "add_chorus", "add_reverb", "connect")}
         self.resources = {}                 # path -> bytes (load_resource)
         self.script_order = []              # (fn, args) in call order, for to_lua()
 
@@ -260,6 +260,10 @@ class ProjectScript:
         """This engine's own vertex (include/termdaw_amd.h td_graph_add_chorus): no reference counterpart.  shape: the string name."""
         self._rec("add_chorus", name, gain, angle, wet, voices, delay_ms, depth_ms, rate_hz, stereo, shape)
 
+    def add_reverb(self, name, gain, angle, wet, room, damp, width, size):
+        """This engine's own vertex (include/termdaw_amd.h td_graph_add_reverb): no reference counterpart."""
+        self._rec("add_reverb", name, gain, angle, wet, room, damp, width, size)
+
     def connect(self, a, b):
         self._rec("connect", a, b)
 
@@ -325,6 +329,8 @@ class ProjectScript:
             g.add_saturator(*args)
         for args in self.calls["add_chorus"]:
             g.add_chorus(*args)
+        for args in self.calls["add_reverb"]:
+            g.add_reverb(*args)
         for a, b in self.calls["connect"]:
             g.connect(a, b)
         g.set_output(self.output_vertex)

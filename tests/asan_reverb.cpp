@@ -1,0 +1,135 @@
+// Sanitizer run of the reverb vertex' host side (built by tests/test_reverb_host.py with g++ -fsanitize=address,undefined
+// against tests/mock_hip.cpp + tests/mock_reverb.cpp -- no GPU, nothing computed): every project goes through the front-end and the C
+// ABI in every band mode with sine modes 1 and 2, un-chunked and in 4 096-frame chunks, with the window length capped at 64 and the
+// serial form in some of them -- fresh, scanned and continued renders, block pulls, a set_time in between, a batch of the project
+// with a second copy of itself.
+// Per project it prints the launch families one profiled render under the guard modes went through ("launches <dir>: name=count
+// ..."), the static gain the guard carried from its last guarded launch to the output ("guard <dir>: path=..."), and what three
+// block pulls under the guard, each told to run again, found in the state block on entry ("redo <dir>: redos=<n> entries=<stamps>",
+// mock_reverb.cpp) -- which is what the guard-rule, backup and launch-list tests read.
+//   usage: asan_reverb <dir> ...     each <dir> holds project.lua and meta.txt ("<buffer length>")
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <string>
+#include <vector>
+
+#include "termdaw_amd.h"
+
+extern size_t g_rev_launches[2], g_rev_vertices, g_rev_serial, g_rev_fresh, g_rev_carried;
+extern double g_rev_path_gain;
+extern int g_rev_force_redo, g_rev_after_set_time;
+extern size_t g_rev_restarts, g_rev_short;
+extern std::vector<double> g_rev_entry_log;
+
+static std::string slurp(const std::string& p) {
+    std::string s; FILE* f = fopen(p.c_str(), "rb"); if (!f) return s;
+    char b[4096]; size_t n; while ((n = fread(b, 1, sizeof b, f)) > 0) s.append(b, n); fclose(f); return s;
+}
+int main(int argc, char** argv) {
+    size_t renders = 0, rejected = 0, failed = 0, pulls = 0;
+    auto bad = [&](const std::string& what) { ++failed; fprintf(stderr, "%s: %s\n", what.c_str(), td_last_error()); };
+    for (int a = 1; a < argc; ++a) {
+        const std::string dir = argv[a];
+        const std::string lua = slurp(dir + "/project.lua");
+        const size_t bl = (size_t)atol(slurp(dir + "/meta.txt").c_str());
+        if (lua.empty() || !bl) { fprintf(stderr, "bad project dir %s\n", dir.c_str()); return 2; }
+        for (int mode = 0; mode < 6; ++mode)
+            for (int chunked = 0; chunked < 2; ++chunked) {
+                td_state* s = td_state_new(dir.c_str(), 48000, bl);
+                if (!s) return 3;
+                td_state_set_option(s, "band_mode", mode % 3);
+                td_state_set_option(s, "sine_mode", mode < 3 ? 1 : 2);
+                if (chunked) td_state_set_option(s, "max_chunk_frames", 4096);
+                if (chunked && (mode & 1)) td_state_set_option(s, "debug.reverb_block", 64);
+                if (mode & 2) td_state_set_option(s, "debug.reverb_form", 0);
+                if (mode % 3 == 2 && chunked) td_state_set_option(s, "band_guard_ppb", 0);   // (every audited render is done again)
+                if (!td_state_refresh_source(s, lua.c_str())) { ++rejected; td_state_free(s); continue; }
+                td_graph* g = td_state_graph(s);
+                const size_t cs = td_state_chunk_count(s);
+                std::vector<unsigned char> pcm(td_state_render_to_memory(s, nullptr, 0) + 16);
+                if (mode == 5 && !chunked) {
+                    td_graph_set_profiling(g, 1);
+                    g_rev_path_gain = 0.0;
+                }
+                for (int k = 0; k < 3; ++k) {
+                    if (k == 1 && !td_state_scan_exact(s)) bad(dir + " scan");
+                    if (pcm.size() > 16 && !td_state_render_to_memory(s, pcm.data(), pcm.size())) bad(dir + " render");
+                    ++renders;
+                    if (mode == 5 && !chunked && k == 0) {
+                        const char* names[64]; float ms[64]; size_t cnt[64];
+                        const size_t n = td_graph_last_kernel_times(g, names, ms, cnt, 64);
+                        printf("launches %s:", dir.c_str());
+                        for (size_t i = 0; i < n && i < 64; ++i) printf(" %s=%zu", names[i], cnt[i]);
+                        printf("\n");
+                        printf("guard %s: path=%.9g\n", dir.c_str(), g_rev_path_gain);
+                        td_graph_set_profiling(g, 0);
+                    }
+                }
+                if (cs && (mode == 0 || mode == 5)) {
+                    // block pulls continue from the lines; a set_time in between restarts them; then a whole render again
+                    std::vector<float> l(bl), r(bl);
+                    for (int k = 0; k < 3; ++k) {
+                        // (mock_reverb.cpp checks that the pull right behind the set_time enters with nothing of its state)
+                        if (k == 2) { td_graph_set_time(g, 0); td_flowwbank_set_time(td_state_flowwbank(s), 0); g_rev_after_set_time = 1; }
+                        if (td_graph_render_block(g, td_state_samplebank(s), td_state_flowwbank(s), l.data(), r.data()) < 0) bad(dir + " pull");
+                        g_rev_after_set_time = 0;
+                        ++pulls;
+                    }
+                    if (mode == 5 && !chunked) {
+                        // three pulls under the guard, every one of them told to run again: the second and the third enter with the
+                        // state block, which the guard has to put back in front of the second run
+                        double st0[4] = {0, 0, 0, 0}, st1[4] = {0, 0, 0, 0};
+                        td_graph_set_time(g, 0);
+                        td_flowwbank_set_time(td_state_flowwbank(s), 0);
+                        td_graph_sync(g);
+                        td_graph_band_guard_stats(g, st0);
+                        g_rev_entry_log.clear();
+                        g_rev_force_redo = 1;
+                        for (int k = 0; k < 3; ++k) {
+                            if (td_graph_render_block(g, td_state_samplebank(s), td_state_flowwbank(s), l.data(), r.data()) < 0) bad(dir + " guarded pull");
+                            td_flowwbank_set_time_to_next_block(td_state_flowwbank(s));
+                            ++pulls;
+                        }
+                        td_graph_sync(g);
+                        g_rev_force_redo = 0;
+                        td_graph_band_guard_stats(g, st1);
+                        printf("redo %s: redos=%d entries=", dir.c_str(), (int)(st1[1] - st0[1]));
+                        for (size_t i = 0; i < g_rev_entry_log.size(); ++i) printf("%s%.0f", i ? "," : "", g_rev_entry_log[i]);
+                        printf("\n");
+                    }
+                    td_graph_set_time(g, 0);
+                    td_flowwbank_set_time(td_state_flowwbank(s), 0);
+                    td_graph_reset_normalize_vertices(g);
+                    if (!td_graph_render_all(g, td_state_samplebank(s), td_state_flowwbank(s), cs, 24)) bad(dir + " render_all");
+                    ++renders;
+                    // a batch: this project and a second State of it, merged launches
+                    td_state* s2 = td_state_new(dir.c_str(), 48000, bl);
+                    if (chunked) td_state_set_option(s2, "max_chunk_frames", 4096);
+                    if (s2 && td_state_refresh_source(s2, lua.c_str())) {
+                        td_batch* b = td_batch_new();
+                        if (td_batch_add(b, g, td_state_samplebank(s), td_state_flowwbank(s)) < 0) bad(dir + " batch add");
+                        if (td_batch_add(b, td_state_graph(s2), td_state_samplebank(s2), td_state_flowwbank(s2)) < 0) bad(dir + " batch add");
+                        if (!td_batch_render_all(b, cs, 16)) bad(dir + " batch render");
+                        if (!td_batch_sync(b)) bad(dir + " batch sync");
+                        ++renders;
+                        td_batch_free(b);
+                    } else {
+                        bad(dir + " second state");
+                    }
+                    if (s2) td_state_free(s2);
+                }
+                td_state_free(s);
+            }
+    }
+    if (g_rev_launches[1] != g_rev_launches[0]) {   // (every k_reverb_sum is followed by a k_reverb)
+        ++failed;
+        fprintf(stderr, "launch counts: k_reverb_sum %zu k_reverb %zu\n", g_rev_launches[0], g_rev_launches[1]);
+    }
+    printf("asan_reverb done: %d projects, %zu renders, %zu pulls, %zu rejected refreshes, %zu failed calls; k_reverb launches %zu "
+           "(%zu vertices, %zu serial-form, %zu entered fresh, %zu entered with the state; %zu k_reverb_sum launches; "
+           "%zu restarts checked; %zu short chunks)\n",
+           argc - 1, renders, pulls, rejected, failed, g_rev_launches[1], g_rev_vertices, g_rev_serial, g_rev_fresh, g_rev_carried,
+           g_rev_launches[0], g_rev_restarts, g_rev_short);
+    return failed ? 1 : 0;
+}
