@@ -18,6 +18,7 @@
 #include "eq_math.h"
 #include "midi.h"
 #include "sat_math.h"
+#include "sum_index.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -386,7 +387,7 @@ static int bank_add_stream(td_samplebank* sb, const std::string& name, const flo
     // (every mode but mix-down) and no resample follows
     bool want16 = method != LM_MIX && sr == sb->sample_rate && n >= 1 && n < 0x3FFFFFF0u;
     if (want16) {
-        e.d16 = static_cast<uint32_t*>(sb->alloc(1, ((n + 18) & ~(size_t)3) * sizeof(uint32_t)));   // the loop + its first 15 frames again
+        e.d16 = static_cast<uint32_t*>(sb->alloc(1, (size_t)tdsi::packed_words((uint32_t)n) * sizeof(uint32_t)));   // the loop + its first 255 frames again (sum_index.h)
         if (!e.d16) return 0;
         TD_HIP(hipMemsetAsync(d_s + 8, 0, sizeof(uint32_t), st));
         launch_sample_pack16(d_l, d_r, e.d16, (uint32_t)n, reinterpret_cast<uint32_t*>(d_s + 8), st);

@@ -35,7 +35,7 @@ struct PanGain {
 //           magic = floor(2^32 / len).
 //   kind 2: the same with 64-bit cursor / length (generic modulo).
 //   kind 3: kind 1 over the sample's packed 16-bit form: one 32-bit word per frame (int16 l | int16 r << 16), the
-//           loop followed by its own first 15 frames, so that up to 16 consecutive loop frames are dword-aligned
+//           loop followed by its own first 255 frames (sum_index.h), so that up to 256 consecutive loop frames are dword-aligned
 //           16-byte loads behind ONE modulo; the f32 frame is rebuilt as (float)l * scale_l, (float)r * scale_r -- the
 //           very expression the load pipeline used to produce the f32 bank entry (sample.rs:270-273 `as f32`,
 //           sample.rs:121-129 `* (1.0 / max)`), so the values are bit-identical at half the gather bytes.

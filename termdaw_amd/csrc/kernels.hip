@@ -12,6 +12,7 @@
 // wave-instruction.
 #include "kernels.h"
 #include "sum_partition.h"
+#include "sum_index.h"
 
 #include <algorithm>
 
@@ -376,7 +377,8 @@ TD_DEV float2 unpack16(uint32_t w, float sl, float sr) {
     return make_float2((float)(int16_t)(w & 0xFFFFu) * sl, (float)(int16_t)(w >> 16) * sr);
 }
 // Frames idx .. idx+3 of a looping sample in ONE 16-byte load: the packed form is the loop followed by its own
-// first 15 frames (the wide kernels read up to 16 consecutive frames behind one modulo), and global_load_dwordx4
+// first tdsi::kWavePad (255) frames -- the readers with a modulo per lane read up to 16 consecutive frames behind it, the
+// quad shape of sum_terms16w 256 behind one index per WAVE (sum_index.h) -- and global_load_dwordx4
 // only needs dword alignment.  (A first version kept four
 // phase-shifted copies to make the load 16-byte aligned: four times the footprint in L2 / Infinity Cache for
 // nothing -- 0.101 ms against 0.086 ms for the 64-source sum.)
@@ -385,6 +387,17 @@ TD_DEV void loop16_quad(const uint32_t* s, uint32_t len, uint32_t idx, uint32_t 
     (void)len;
     const uint32_t TD_GLOBAL* g = reinterpret_cast<const uint32_t TD_GLOBAL*>((const TD_GLOBAL char*)s);
     const u4v_u q = *reinterpret_cast<const u4v_u TD_GLOBAL*>(g + idx);   // dword-aligned global_load_dwordx4
+    out[0] = q.x; out[1] = q.y; out[2] = q.z; out[3] = q.w;
+}
+// The same load for a whole wave: words idx + 4 lane .. + 3 with `s`, `idx` uniform and `lane16` = 16 bytes x lane -- a scalar
+// base (table + 4 idx, computed on the scalar unit) plus a zero-extended 32-bit lane offset, which is the addressing mode of
+// global_load_dwordx4 itself: no vector instruction computes an address.  idx < len, and the table carries 255 wrap frames.
+TD_DEV void loop16_quad_wave(const uint32_t* s, uint32_t idx, uint32_t lane16, uint32_t out[4]) {
+    const TD_GLOBAL char* g = reinterpret_cast<const TD_GLOBAL char*>((const TD_GLOBAL char*)s) + 4ull * idx;
+    // (the empty statement keeps the offset a 32-bit value HERE: extended to 64 bits once in front of the loop, the compiler adds
+    // it to every address with a vector instruction instead of handing it to the load)
+    asm("" : "+v"(lane16));
+    const u4v_u q = *reinterpret_cast<const u4v_u TD_GLOBAL*>(g + lane16);
     out[0] = q.x; out[1] = q.y; out[2] = q.z; out[3] = q.w;
 }
 // all terms kind 3: lane t owns frames m, m+1 (acc0) and m+2, m+3 (acc1) with m = tile + 4t.
@@ -434,28 +447,29 @@ TD_DEV void sum_terms16(TermTab ins, uint32_t k, uint32_t m, uint32_t M, float4&
 
 // all terms kind 3, 4 * NQ consecutive frames per lane (NQ 16-byte gathers per source).  More frames per lane =
 // more of the timeline resident per XCD at any moment = more of the concurrently running tiles touch the same
-// lines of a looping source while they are still in L2.  The packed form carries 15 wrap frames, so one modulo
-// per source and lane is enough.
+// lines of a looping source while they are still in L2.  The packed form carries wrap frames (255 of them), so the
+// consecutive shape needs one modulo per source and lane, and the quad shape one per source and WAVE, none per lane.
 // Which frames a lane owns (round 6).  NQ < 4: 4 NQ consecutive ones from m.  NQ == 4 (BASELINE config 2's fused launch): quad q =
 // frames m + 256 q of the wave's 1 024, m = the wave's base + 4 lane -- every load instruction of the wave reads ONE KILOBYTE IN ONE
 // PIECE.  With sixteen consecutive frames per lane a lane's four 16-byte loads lie 64 bytes from the next lane's: every load
 // instruction touches 64 separate 64-byte pieces and takes a quarter of each, and the lines have to stay in the CU's L1 until the
 // fourth instruction has had its quarter (tools/ubench/gather_shape.hip, config 2's 737 MB with the arithmetic taken out: 52 us in
 // that shape, 40 us in this one with two sources' loads in flight -- in the old shape a second source in flight LOSES).
-// 256 mod len on the scalar unit (len, magic are a source's: uniform): a quad's index = the one before + this, wrapped ONCE, whatever
-// the loop's length -- no branch on `len > 256` in the gather (behind a branch the compiler's waits for the loads in flight fall
-// back to "all of them")
-TD_DEV uint32_t step256(uint32_t len, uint32_t magic) {
-    const uint32_t r = 256u - __umulhi(256u, magic) * len;   // (magic = floor(2^32 / len): the quotient is short by 1 at most)
-    return r >= len ? r - len : r;
-}
+// The quad shape's index (sum_index.h) lives on the scalar unit: a wave's first frame `wbase`, and a source's t0, len, magic are all
+// uniform, so the wave's start = (t0 + wbase) mod len, the quad-to-quad step 256 mod len and the wrap -- ONCE, whatever the loop's
+// length: no branch on `len > 256` in the gather (behind a branch the compiler's waits for the loads in flight fall back to "all
+// of them") -- are scalar instructions, and the load adds the lane's 16 bytes itself (loop16_quad_wave).  Until the table carried
+// a wave's worth of wrap frames every LANE had to take the modulo and the wrap for itself: 19 vector instructions per source
+// and wave that computed addresses only, four of them in a dependent chain in front of every load but a source's first.
 template <int NQ>
 TD_DEV uint32_t quad_frame(uint32_t m, int q) { return NQ == 4 ? m + 256u * (uint32_t)q : m + 4u * (uint32_t)q; }
 template <int NQ>
 TD_DEV uint32_t pair_frame(uint32_t m, int p) { return quad_frame<NQ>(m, p >> 1) + 2u * (uint32_t)(p & 1); }
 // (QUAD: the quad shape for any NQ -- the ragged form k_sum16r below, whose waves own 1 .. 4 quads)
+// (wbase, QUAD only: the wave's first frame, UNIFORM -- m = wbase + 4 lane)
 template <int NQ, bool QUAD = (NQ == 4)>
-TD_DEV void sum_terms16w(TermTab ins, uint32_t k, uint32_t m, uint32_t M, float4 acc[2 * NQ]) {
+TD_DEV void sum_terms16w(TermTab ins, uint32_t k, uint32_t m, uint32_t wbase, uint32_t M, float4 acc[2 * NQ]) {
+    const uint32_t lane16 = 16u * (threadIdx.x & 63u);
     f2v c[4 * NQ];
 #pragma unroll
     for (int f = 0; f < 4 * NQ; ++f) { c[f].x = 0.f; c[f].y = 0.f; }
@@ -476,26 +490,25 @@ TD_DEV void sum_terms16w(TermTab ins, uint32_t k, uint32_t m, uint32_t M, float4
     };
     auto gather = [&](uint32_t j, uint32_t w[4 * NQ]) {
         const uint32_t len = (uint32_t)ins[j].len;
-        const uint32_t idx = barrett_mod((uint32_t)ins[j].t0 + m, len, ins[j].magic);
         if (QUAD) {
             const uint32_t* p = reinterpret_cast<const uint32_t*>(ins[j].p);
-            const uint32_t step = step256(len, ins[j].magic);
-            uint32_t i = idx;
+            const uint32_t step = tdsi::quad_step(len, ins[j].magic);
+            uint32_t i = tdsi::wave_start((uint32_t)ins[j].t0 + wbase, len, ins[j].magic);
 #pragma unroll
             for (int q = 0; q < NQ; ++q) {
-                loop16_quad(p, len, i, w + 4 * q);
-                i += step;
-                i = min(i, i - len);
+                loop16_quad_wave(p, i, lane16, w + 4 * q);
+                i = tdsi::next_quad(i, step, len);
             }
             return;
         }
+        const uint32_t idx = barrett_mod((uint32_t)ins[j].t0 + m, len, ins[j].magic);
 #pragma unroll
         for (int q = 0; q < NQ; ++q) loop16_quad(reinterpret_cast<const uint32_t*>(ins[j].p), len, idx + 4u * q, w + 4 * q);
     };
     uint32_t j = 0;
     // sources per batch: 16 x 16-byte loads in flight per lane (NQ == 4, round 6: four sources since every load instruction reads whole
     // lines -- in the old shape a second source in flight lost: 1 / 2 / 3 / 4 sources 63.1 / 64.5 / 62.9 / 61.9 us on config 2;
-    // with the wrap made branch-free, step256 above, 58.9 us).  Measured and dropped: the same loads as a ROLLING pipeline -- the
+    // with the wrap made branch-free, tdsi::quad_step today, 58.9 us; with the index on the scalar unit 56.3 against 57.9 us).  Measured and dropped: the same loads as a ROLLING pipeline -- the
     // next sources' loads issued while this one's frames are added, two or four register sets in rotation, records a source ahead --
     // 68 us: the memory side serves a wave's burst of sixteen loads followed by silence faster than a steady trickle.
     // (Also measured and dropped, same instruction mix to the last VALU operation: the four records of a batch as explicit,
@@ -765,12 +778,14 @@ __global__ __launch_bounds__(kThreads) void k_sum16w(const SumDesc* __restrict__
     const SumDesc& d = descs[blockIdx.y];
     // (the lane's frames: quad_frame / pair_frame above -- NQ == 4 with packed sources: four quads 256 frames apart inside the wave's block)
     constexpr int SH = (NQ == 4 && PACKED) ? 4 : 1;   // (the frame shape's tag: 1 = consecutive)
-    const uint32_t m = SH == 4 ? blockIdx.x * (kTileFrames * NQ) + (threadIdx.x >> 6) * kTileFrames + 4u * (threadIdx.x & 63u)
+    // (the wave's first frame, made uniform for the compiler: the quad shape's indices stay on the scalar unit, sum_index.h)
+    const uint32_t wbase = SH == 4 ? blockIdx.x * (kTileFrames * NQ) + (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * kTileFrames : 0u;
+    const uint32_t m = SH == 4 ? wbase + 4u * (threadIdx.x & 63u)
                                : blockIdx.x * (kTileFrames * NQ) + 4u * NQ * threadIdx.x;
     // (mode 4: the carried max, read before anything else -- the last tile replaces it once every tile has published)
     const float spec_init_early = d.mode >= 4 ? (d.use_init ? d.init_max : gload1(&d.state->max)) : 0.0f;
     float4 a[2 * NQ];
-    if (PACKED) sum_terms16w<NQ>(term_tab(d.ins), d.k, m, M, a);
+    if (PACKED) sum_terms16w<NQ>(term_tab(d.ins), d.k, m, wbase, M, a);
     else sum_terms32w<NQ>(term_tab(d.ins), d.k, m, M, a);
     if (d.mode == 0) {
 #pragma unroll
@@ -931,21 +946,21 @@ __global__ __launch_bounds__(kThreads) void k_sum16r(const SumDesc* __restrict__
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const tdsp::QuadRange wv = tdsp::wave_quads(wg, wave);
     const uint32_t nq = wv.n;
-    const uint32_t m = tdsp::kQuadFrames * wv.q0 + 4u * (threadIdx.x & 63u);
+    const uint32_t wbase = tdsp::kQuadFrames * wv.q0, m = wbase + 4u * (threadIdx.x & 63u);
     // (mode 5: the carried max, read before anything else -- the last workgroup replaces it once every one has published)
     const float init = d.mode >= 4 ? (d.use_init ? d.init_max : gload1(&d.state->max)) : 0.0f;
     float4 a[8];
 #pragma unroll
     for (int q = 0; q < 8; ++q) a[q] = make_float4(0.f, 0.f, 0.f, 0.f);
     const TermTab ins = term_tab(d.ins);
-    if (nq == 4u) sum_terms16w<4, true>(ins, d.k, m, M, a);
-    else if (nq == 3u) { float4 t[6]; sum_terms16w<3, true>(ins, d.k, m, M, t);
+    if (nq == 4u) sum_terms16w<4, true>(ins, d.k, m, wbase, M, a);
+    else if (nq == 3u) { float4 t[6]; sum_terms16w<3, true>(ins, d.k, m, wbase, M, t);
 #pragma unroll
         for (int q = 0; q < 6; ++q) a[q] = t[q]; }
-    else if (nq == 2u) { float4 t[4]; sum_terms16w<2, true>(ins, d.k, m, M, t);
+    else if (nq == 2u) { float4 t[4]; sum_terms16w<2, true>(ins, d.k, m, wbase, M, t);
 #pragma unroll
         for (int q = 0; q < 4; ++q) a[q] = t[q]; }
-    else if (nq == 1u) { float4 t[2]; sum_terms16w<1, true>(ins, d.k, m, M, t); a[0] = t[0]; a[1] = t[1]; }
+    else if (nq == 1u) { float4 t[2]; sum_terms16w<1, true>(ins, d.k, m, wbase, M, t); a[0] = t[0]; a[1] = t[1]; }
     if (d.mode == 0) {
 #pragma unroll
         for (int q = 0; q < 8; ++q)
@@ -6598,9 +6613,9 @@ void launch_add_planar(const float* a, const float* b, float* out, uint32_t n, h
 }
 __global__ __launch_bounds__(kThreads) void k_sample_pack16(const float* __restrict__ l, const float* __restrict__ r,
                                                             uint32_t* __restrict__ packed, uint32_t n, uint32_t* not_int16) {
-    // word i = frame i % n for i < roundup(n + 3, 4): the loop plus its first frames again, so that any four
-    // consecutive loop frames (wrap included) are four consecutive words
-    const uint32_t total = (n + 15u + 3u) & ~3u;
+    // word i = frame i % n for i < packed_words(n) (sum_index.h): the loop plus its first 255 frames again (a loop shorter
+    // than that simply repeats), so that any 256 consecutive loop frames (wrap included) are 256 consecutive words
+    const uint32_t total = tdsi::packed_words(n);
     bool bad = false;
     for (uint32_t i = blockIdx.x * kThreads + threadIdx.x; i < total; i += gridDim.x * kThreads) {
         const uint32_t f = i % n;
@@ -6612,7 +6627,7 @@ __global__ __launch_bounds__(kThreads) void k_sample_pack16(const float* __restr
     if (__any(bad ? 1 : 0) && (threadIdx.x & 63) == 0) atomicOr(not_int16, 1u);
 }
 void launch_sample_pack16(const float* l, const float* r, uint32_t* packed, uint32_t n, uint32_t* not_int16, hipStream_t s) {
-    if (n) hipLaunchKernelGGL(k_sample_pack16, dim3(grid_for((n + 18u) & ~3u)), dim3(kThreads), 0, s, l, r, packed, n, not_int16);
+    if (n) hipLaunchKernelGGL(k_sample_pack16, dim3(grid_for(tdsi::packed_words(n))), dim3(kThreads), 0, s, l, r, packed, n, not_int16);
 }
 void launch_sample_pack(const float* l, const float* r, const float* max_l, const float* max_r, float2* frames, uint32_t n,
                         hipStream_t s) {

@@ -20,6 +20,8 @@
 #include <algorithm>
 #include <vector>
 
+#include "sum_index.h"
+
 namespace {
 
 struct Tab {
@@ -38,7 +40,9 @@ __device__ __forceinline__ uint32_t barrett_mod(uint32_t x, uint32_t len, uint32
 }
 
 // NQ x 16-byte gathers per source and lane, B sources' gathers issued before the first is consumed
-template <int NQ, int B>
+// (SC, NQ == 4: the engine's addressing -- termdaw_amd/csrc/sum_index.h: the wave's index on the scalar unit, the lane's 16 bytes
+// added by the load itself, on tables that carry 255 wrap frames)
+template <int NQ, int B, bool SC = false>
 __global__ __launch_bounds__(256) void k_gather(const Tab* __restrict__ tabs_generic, int k, uint32_t M, float* __restrict__ out) {
     const Tab UB_CONST* tabs = (const Tab UB_CONST*)(const UB_CONST char*)(tabs_generic + (size_t)blockIdx.y * k);
     out += (size_t)blockIdx.y * 2 * ((size_t)M + 64);
@@ -53,8 +57,20 @@ __global__ __launch_bounds__(256) void k_gather(const Tab* __restrict__ tabs_gen
 #pragma unroll
         for (int u = 0; u < B; ++u) {
             const uint32_t len = tabs[j + u].len;
-            const uint32_t idx = barrett_mod(tabs[j + u].t0 + m, len, tabs[j + u].magic);
             const uint32_t UB_GLOBAL* g = (const uint32_t UB_GLOBAL*)(const UB_GLOBAL char*)tabs[j + u].p;
+            if (NQ == 4 && SC) {
+                const uint32_t ub = blockIdx.x * (1024u * NQ) + (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * 1024u;
+                const uint32_t step = tdsi::quad_step(len, tabs[j + u].magic);
+                uint32_t i = tdsi::wave_start(tabs[j + u].t0 + ub, len, tabs[j + u].magic);
+#pragma unroll
+                for (int q = 0; q < NQ; ++q) {
+                    uint32_t lane16 = 16u * (threadIdx.x & 63u);
+                    asm("" : "+v"(lane16));   // (kept 32 bits wide here: the load's own offset operand)
+                    w[u][q] = *(const u4v_u UB_GLOBAL*)((const UB_GLOBAL char*)(g + i) + lane16);
+                    i = tdsi::next_quad(i, step, len);
+                }
+                continue;
+            }
             if (NQ == 4) {   // the engine's shape since round 6 (kernels.hip quad_frame): quad q = frames 256 q + 4 lane of the wave's 1 024
                 uint32_t i = barrett_mod(tabs[j + u].t0 + mw, len, tabs[j + u].magic);
 #pragma unroll
@@ -65,6 +81,7 @@ __global__ __launch_bounds__(256) void k_gather(const Tab* __restrict__ tabs_gen
                 }
                 continue;
             }
+            const uint32_t idx = barrett_mod(tabs[j + u].t0 + m, len, tabs[j + u].magic);
 #pragma unroll
             for (int q = 0; q < NQ; ++q) w[u][q] = *(const u4v_u UB_GLOBAL*)(g + idx + 4u * q);
         }
@@ -150,13 +167,13 @@ __global__ void k_fill(uint32_t* p, size_t n, uint32_t salt) {
 }
 
 // `per` table sets per launch (0: all n_sets in one grid), the rest in further launches -- the engine's batch slicing
-template <int NQ, int B>
+template <int NQ, int B, bool SC = false>
 float time_gather(const Tab* d_tabs, int k, uint32_t frames, float* d_out, int iters, int n_sets, int per) {
     const uint32_t gx = (frames + 1024u * NQ - 1) / (1024u * NQ);
     if (per <= 0 || per > n_sets) per = n_sets;
     auto pass = [&]() {
         for (int o = 0; o < n_sets; o += per)
-            hipLaunchKernelGGL((k_gather<NQ, B>), dim3(gx, std::min(per, n_sets - o)), dim3(256), 0, 0, d_tabs + (size_t)o * k, k, frames,
+            hipLaunchKernelGGL((k_gather<NQ, B, SC>), dim3(gx, std::min(per, n_sets - o)), dim3(256), 0, 0, d_tabs + (size_t)o * k, k, frames,
                                d_out + (size_t)o * 2 * ((size_t)frames + 64));
     };
     hipEvent_t e0, e1;
@@ -181,12 +198,13 @@ extern "C" {
 // lens[k]: loop lengths in frames (= packed 32-bit words) of ONE project; n_sets projects (each with its own tables of
 // those lengths, `per` of them per launch like a batch submission; 0 = all in one grid).  frames: timeline length.  nq: 1 | 2 | 4 (4 * nq consecutive
 // frames per lane, as the engine's k_sum<loop16> / k_sum16w<2> / k_sum16w<4>).  Returns the best (smallest) average
-// ms per launch over the issue variants (1, 2 or 4 sources' gathers in flight before the first use), < 0 on failure.
+// ms per launch over the issue variants (1, 2 or 4 sources' gathers in flight before the first use; nq 4: the per-lane and the
+// scalar-unit addressing both), < 0 on failure.
 float td_ubench_gather(const uint32_t* lens, int k, uint32_t frames, int nq, int iters, int n_sets, int per) {
     if (k <= 0 || frames == 0 || iters <= 0 || n_sets <= 0) return -1.f;
     std::vector<Tab> tabs((size_t)k * n_sets);
     size_t words_set = 0;
-    for (int j = 0; j < k; ++j) words_set += ((size_t)lens[j] + 18) & ~(size_t)3;
+    for (int j = 0; j < k; ++j) words_set += tdsi::packed_words(lens[j]);   // (the engine's tables: 255 wrap frames)
     uint32_t* d_all = nullptr;
     Tab* d_tabs = nullptr;
     float* d_out = nullptr;
@@ -200,14 +218,15 @@ float td_ubench_gather(const uint32_t* lens, int k, uint32_t frames, int nq, int
             for (int j = 0; j < k; ++j) {
                 const uint32_t len = lens[j];
                 tabs[(size_t)s * k + j] = {d_all + off, len, len >= 2 ? (uint32_t)(0x100000000ull / len) : 0xFFFFFFFFu, 0u, 0u};
-                off += ((size_t)len + 18) & ~(size_t)3;
+                off += tdsi::packed_words(len);
             }
         if (hipMemcpy(d_tabs, tabs.data(), sizeof(Tab) * tabs.size(), hipMemcpyHostToDevice) == hipSuccess) {
-            float t[3] = {0, 0, 0};
-            if (nq == 4) { t[0] = time_gather<4, 1>(d_tabs, k, frames, d_out, iters, n_sets, per); t[1] = time_gather<4, 2>(d_tabs, k, frames, d_out, iters, n_sets, per); t[2] = time_gather<4, 4>(d_tabs, k, frames, d_out, iters, n_sets, per); }
+            float t[3] = {0, 0, 0}, sc = 3.4e38f;
+            if (nq == 4) { t[0] = time_gather<4, 1>(d_tabs, k, frames, d_out, iters, n_sets, per); t[1] = time_gather<4, 2>(d_tabs, k, frames, d_out, iters, n_sets, per); t[2] = time_gather<4, 4>(d_tabs, k, frames, d_out, iters, n_sets, per);
+                           sc = std::min(time_gather<4, 2, true>(d_tabs, k, frames, d_out, iters, n_sets, per), time_gather<4, 4, true>(d_tabs, k, frames, d_out, iters, n_sets, per)); }
             else if (nq == 2) { t[0] = time_gather<2, 1>(d_tabs, k, frames, d_out, iters, n_sets, per); t[1] = time_gather<2, 2>(d_tabs, k, frames, d_out, iters, n_sets, per); t[2] = time_gather<2, 4>(d_tabs, k, frames, d_out, iters, n_sets, per); }
             else { t[0] = time_gather<1, 1>(d_tabs, k, frames, d_out, iters, n_sets, per); t[1] = time_gather<1, 2>(d_tabs, k, frames, d_out, iters, n_sets, per); t[2] = time_gather<1, 4>(d_tabs, k, frames, d_out, iters, n_sets, per); }
-            if (hipDeviceSynchronize() == hipSuccess && hipGetLastError() == hipSuccess) best = std::min(t[0], std::min(t[1], t[2]));
+            if (hipDeviceSynchronize() == hipSuccess && hipGetLastError() == hipSuccess) best = std::min(std::min(t[0], sc), std::min(t[1], t[2]));
         }
     }
     if (d_tabs) (void)hipFree(d_tabs);

@@ -7,6 +7,10 @@
 //      a modulo per quad (or one modulo and three conditional wraps)
 //   C  two runs of 8 consecutive frames per lane, 512 frames apart: a load instruction touches 64 halves of 32-byte pieces
 // each with 1 or 2 sources' loads in flight before the first is consumed.
+//   S  shape B's quads with the index on the SCALAR unit (termdaw_amd/csrc/sum_index.h): tables padded by 255 wrap frames, the
+//      wave's start index and the quad-to-quad wrap uniform, the lane's 16 bytes added by the load itself -- no vector instruction
+//      computes an address and the loads of a batch issue back to back; 2 and 4 sources in flight on the engine's 704 workgroups,
+//      beside B at the same depths
 //   R  shape B's loads, four sources in flight, under the RAGGED partition of k_sum16r (termdaw_amd/csrc/sum_partition.h): the
 //      timeline's quads dealt evenly over G = 768 / 1 024 / 1 280 workgroups (3 / 4 / 5 per CU), a wave owns 1 .. 4 quads --
 //      beside B with four sources in flight on the engine's 704 workgroups: what the partition does to the gather alone
@@ -15,6 +19,7 @@
 #include <stdio.h>
 #include <vector>
 #include "sum_partition.h"
+#include "sum_index.h"
 #define UB_GLOBAL __attribute__((address_space(1)))
 #define UB_CONST __attribute__((address_space(4)))
 typedef unsigned int u4v_u __attribute__((ext_vector_type(4), aligned(4)));
@@ -32,6 +37,7 @@ __global__ __launch_bounds__(256) void k_gather(const Tab* __restrict__ tabs_gen
     auto frame_of = [&](int q) -> uint32_t {   // first frame of the lane's quad q
         if (SHAPE == 0) return wbase + 16u * lane + 4u * q;
         if (SHAPE == 1) return wbase + 256u * q + 4u * lane;
+        if (SHAPE == 3) return wbase + 256u * q + 4u * lane;
         return wbase + 512u * (q >> 1) + 8u * lane + 4u * (q & 1);
     };
     uint32_t acc[16];
@@ -54,6 +60,17 @@ __global__ __launch_bounds__(256) void k_gather(const Tab* __restrict__ tabs_gen
                     w[u][q] = *(const u4v_u UB_GLOBAL*)(g + idx);
                     idx += 256u;
                     idx = min(idx, idx - len);   // (len >= 1 024: one wrap at most)
+                }
+            } else if (SHAPE == 3) {
+                const uint32_t ub = blockIdx.x * 4096u + (uint32_t)__builtin_amdgcn_readfirstlane(wave) * 1024u;
+                const uint32_t step = tdsi::quad_step(len, magic);
+                uint32_t idx = tdsi::wave_start(t0 + ub, len, magic);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    uint32_t lane16 = 16u * lane;
+                    asm("" : "+v"(lane16));   // (kept 32 bits wide here: the load's own offset operand)
+                    w[u][q] = *(const u4v_u UB_GLOBAL*)((const UB_GLOBAL char*)(g + idx) + lane16);
+                    idx = tdsi::next_quad(idx, step, len);
                 }
             } else {
                 uint32_t idx = barrett_mod(t0 + frame_of(0), len, magic);
@@ -168,6 +185,15 @@ int main() {
     size_t off = 0;
     for (int j = 0; j < k; ++j) { const uint32_t len = 48000 + 977 * j; tabs[j] = {d_all + off, len, (uint32_t)(0x100000000ull / len), 0u, 0u}; off += ((size_t)len + 18) & ~(size_t)3; }
     hipMemcpy(d_tabs, tabs.data(), sizeof(Tab) * k, hipMemcpyHostToDevice);
+    // S: the same loops with 255 wrap frames each (the fill is arbitrary data: only the addresses matter here)
+    size_t words_s = 0;
+    for (int j = 0; j < k; ++j) words_s += tdsi::packed_words(48000u + 977u * j);
+    uint32_t* d_all_s; Tab* d_tabs_s;
+    hipMalloc(&d_all_s, words_s * 4); hipMalloc(&d_tabs_s, sizeof(Tab) * k);
+    hipLaunchKernelGGL(k_fill, dim3(2048), dim3(256), 0, 0, d_all_s, words_s);
+    off = 0;
+    for (int j = 0; j < k; ++j) { const uint32_t len = 48000 + 977 * j; tabs[j] = {d_all_s + off, len, (uint32_t)(0x100000000ull / len), 0u, 0u}; off += tdsi::packed_words(len); }
+    hipMemcpy(d_tabs_s, tabs.data(), sizeof(Tab) * k, hipMemcpyHostToDevice);
     const double bytes = (double)frames * k * 4.0;
     for (int rep = 0; rep < 2; ++rep) {
         const float a1 = run<0, 1>(d_tabs, k, frames, d_out), a2 = run<0, 2>(d_tabs, k, frames, d_out);
@@ -178,6 +204,10 @@ int main() {
         printf("C (2 x 8 consecutive)        B=1 %.4f ms %.0f GB/s   B=2 %.4f ms %.0f GB/s\n", c1, bytes / c1 / 1e6, c2, bytes / c2 / 1e6);
         const float b4 = run<1, 4>(d_tabs, k, frames, d_out);
         printf("B, 704 workgroups            B=4 %.4f ms %.0f GB/s\n", b4, bytes / b4 / 1e6);
+        const float s2 = run<3, 2>(d_tabs_s, k, frames, d_out), s4 = run<3, 4>(d_tabs_s, k, frames, d_out);
+        const float b2b = run<1, 2>(d_tabs, k, frames, d_out), b4b = run<1, 4>(d_tabs, k, frames, d_out);
+        printf("S (B, index on scalar unit)  B=2 %.4f ms %.0f GB/s   B=4 %.4f ms %.0f GB/s\n", s2, bytes / s2 / 1e6, s4, bytes / s4 / 1e6);
+        printf("B again, beside S            B=2 %.4f ms %.0f GB/s   B=4 %.4f ms %.0f GB/s\n", b2b, bytes / b2b / 1e6, b4b, bytes / b4b / 1e6);
         for (uint32_t G : {768u, 1024u, 1280u}) {
             const float r = run_ragged(d_tabs, k, frames, d_out, G);
             printf("R (ragged, %4u workgroups)   B=4 %.4f ms %.0f GB/s\n", G, r, r > 0.f ? bytes / r / 1e6 : 0.0);
