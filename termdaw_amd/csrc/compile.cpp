@@ -816,6 +816,18 @@ static bool plan_band_scan(const td_graph* g, const Vertex& v, size_t M, ScanPla
     return true;
 }
 
+// A delay, saturator, chorus or reverb vertex enters a chunk of M frames: a set_time since the vertex last ran is consumed here
+// (the block restarts from zero, like an EQ's state), the books move on behind the chunk -- `alternates`: the launch writes the other
+// half of the line, which the next one reads.  Returns the frames run up to the chunk (Vertex::Line::total as the chunk finds it).
+static uint64_t enter_chunk(Vertex& v, size_t M, bool alternates) {
+    if (v.first_pending) v.line.total = 0;
+    v.first_pending = false;
+    const uint64_t total = v.line.total;
+    v.line.total += M;
+    if (alternates) v.line.parity ^= 1u;
+    return total;
+}
+
 // ------------------------------------------------------------------------------------------------
 // one chunk: compile tables + descriptors (compile_chunk), then upload and launch level by level (submit_chunk)
 // ------------------------------------------------------------------------------------------------
@@ -2412,11 +2424,9 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                             level_tmp.push_back(x.x);
                         }
                         x.out = g->vbuf[p.vi];
-                        x.line = take_delay_line(g, v, p.D);
+                        x.line = (double*)take_line(g, v, (size_t)p.D * 2 * sizeof(double));
                         if (!x.line) return fail("termdaw_amd: out of device memory for a delay line");
-                        // (a set_time since the vertex last ran: the line restarts from zero -- consumed here, like an EQ's)
-                        if (v.first_pending) v.delay_total = 0;
-                        v.first_pending = false;
+                        const uint64_t total = enter_chunk(v, M, false);
                         x.k = (uint32_t)g->edges[p.vi].size();
                         x.term_mode = term_mode[p.vi];
                         x.frames = (uint32_t)M;
@@ -2424,9 +2434,8 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                         x.lanes = p.t.lanes;
                         x.T = T;
                         x.n_tiles = p.t.n_tiles;
-                        x.pos = (uint32_t)(v.delay_total % p.D);
-                        x.filled = (uint32_t)std::min<uint64_t>(v.delay_total, p.D);
-                        v.delay_total += M;
+                        x.pos = (uint32_t)(total % p.D);
+                        x.filled = (uint32_t)std::min<uint64_t>(total, p.D);
                         x.seg = p.t.seg;
                         x.chunk = p.t.chunk;
                         x.wet = v.wet;
@@ -2484,17 +2493,13 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                         }
                         x.out = g->vbuf[vi];
                         if (filtered) {
-                            x.line = take_sat_line(g, v);
+                            x.line = (float2*)take_line(g, v, 2 * sat::kLine * sizeof(float2));
                             if (!x.line) return fail("termdaw_amd: out of device memory for a saturator line");
-                            // (a set_time since the vertex last ran: the line restarts from silence -- consumed here, like a delay's)
-                            if (v.first_pending) v.sat_total = 0;
-                            x.filled = (uint32_t)std::min<uint64_t>(v.sat_total, sat::kLine);
-                            x.parity = v.sat_parity;
-                            v.sat_total += M;
-                            v.sat_parity ^= 1u;
+                            x.parity = v.line.parity;
+                            x.filled = (uint32_t)std::min<uint64_t>(enter_chunk(v, M, true), sat::kLine);
                             if (!taps_off.count(v.sat_oversample)) taps_off[v.sat_oversample] = st.put(sat::taps(v.sat_oversample));
                         }
-                        v.first_pending = false;
+                        v.first_pending = false;   // (R = 1 has no line: the set_time is consumed all the same)
                         x.k = (uint32_t)g->edges[vi].size();
                         x.term_mode = term_mode[vi];
                         x.frames = (uint32_t)M;
@@ -2545,15 +2550,10 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                         }
                         x.out = g->vbuf[vi];
                         x.H = (uint32_t)c[3];
-                        x.line = take_chorus_line(g, v, x.H);
+                        x.line = (float2*)take_line(g, v, 2 * (size_t)x.H * sizeof(float2));
                         if (!x.line) return fail("termdaw_amd: out of device memory for a chorus line");
-                        // (a set_time since the vertex last ran: the line restarts from silence -- consumed here, like a delay's)
-                        if (v.first_pending) v.chorus_total = 0;
-                        v.first_pending = false;
-                        x.filled = (uint32_t)std::min<uint64_t>(v.chorus_total, x.H);
-                        x.parity = v.chorus_parity;
-                        v.chorus_total += M;
-                        v.chorus_parity ^= 1u;
+                        x.parity = v.line.parity;
+                        x.filled = (uint32_t)std::min<uint64_t>(enter_chunk(v, M, true), x.H);
                         x.t0 = t0;
                         x.k = (uint32_t)g->edges[vi].size();
                         x.term_mode = term_mode[vi];
@@ -2588,23 +2588,22 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                         if (!x.x) return fail("termdaw_amd: out of device memory for edge buffers");
                         level_tmp.push_back(x.x);
                         x.out = g->vbuf[vi];
-                        // (a set_time since the vertex last ran: the lines and the one-pole states restart from zero -- consumed here, like a delay's)
-                        if (v.first_pending) v.reverb_total = 0;
-                        v.first_pending = false;
                         uint32_t at = 16, shortest = 0xFFFFFFFFu;
                         for (int i = 0; i < reverb::kLines; ++i) {
-                            const uint32_t D = (uint32_t)c[7 + i];
-                            x.len[i] = D;
+                            x.len[i] = (uint32_t)c[7 + i];
                             x.off[i] = at;
-                            x.pos[i] = (uint32_t)(v.reverb_total % D);
-                            x.skip[i] = v.reverb_total < D ? (uint32_t)(D - v.reverb_total) : 0u;
-                            at += D;
-                            shortest = std::min(shortest, D);
+                            at += x.len[i];
+                            shortest = std::min(shortest, x.len[i]);
                         }
-                        x.state = take_reverb_state(g, v, at);
+                        x.state = (double*)take_line(g, v, at * sizeof(double));
                         if (!x.state) return fail("termdaw_amd: out of device memory for a reverb vertex' lines");
-                        x.fresh = v.reverb_total == 0 ? 1u : 0u;
-                        v.reverb_total += M;
+                        const uint64_t total = enter_chunk(v, M, false);
+                        for (int i = 0; i < reverb::kLines; ++i) {
+                            const uint32_t D = x.len[i];
+                            x.pos[i] = (uint32_t)(total % D);
+                            x.skip[i] = total < D ? (uint32_t)(D - total) : 0u;
+                        }
+                        x.fresh = total == 0 ? 1u : 0u;
                         x.k = (uint32_t)g->edges[vi].size();
                         x.term_mode = term_mode[vi];
                         x.frames = (uint32_t)M;

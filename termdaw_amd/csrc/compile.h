@@ -37,10 +37,7 @@ double ms_between(std::chrono::steady_clock::time_point a, std::chrono::steady_c
 // ---- engine.cpp: the device memory the compiler hands out addresses of ----
 int upload_tables(td_graph* g, TableCache& tc, const Staging& tmp);   // a vertex' event tables -> its device buffer (queued on the graph's stream)
 int ensure_buffers(td_graph* g, size_t frames);                      // the edge-buffer pool holds buffers of >= frames frames; all of them free
-double* take_delay_line(td_graph* g, tde::Vertex& v, size_t D);    // a delay vertex' line, allocated on first use (nullptr: out of device memory)
-float2* take_sat_line(td_graph* g, tde::Vertex& v);                  // a saturator vertex' line, allocated on first use (nullptr: out of device memory)
-float2* take_chorus_line(td_graph* g, tde::Vertex& v, size_t H);    // a chorus vertex' line (two halves of H frames), allocated on first use (nullptr: out of device memory)
-double* take_reverb_state(td_graph* g, tde::Vertex& v, size_t doubles);   // a reverb vertex' state block, allocated on first use (nullptr: out of device memory)
+void* take_line(td_graph* g, tde::Vertex& v, size_t bytes);   // the block a delay, saturator, chorus or reverb vertex carries (Vertex::line), allocated on first use (nullptr: out of device memory)
 float2* take_buffer(td_graph* g);                                    // one edge buffer (nullptr: out of device memory)
 
 }  // namespace tde

@@ -563,74 +563,33 @@ int ensure_buffers(td_graph* g, size_t frames) {
     g->free_bufs = g->pool;
     return 1;
 }
-// The line of a delay vertex: 16 D bytes, allocated when the vertex is first compiled into a submission (never cleared: a word is
-// read only once the vertex has written it, Vertex::delay_total), freed with the graph's vertices.
-double* take_delay_line(td_graph* g, Vertex& v, size_t D) {
-    if (v.delay_line) return v.delay_line;
-    double* p = nullptr;
-    if (hipMalloc(&p, D * 2 * sizeof(double)) != hipSuccess) return nullptr;
-    g->delay_lines.push_back({p, D * 2 * sizeof(double)});
-    g->device_bytes += D * 2 * sizeof(double);
-    v.delay_line = p;
-    v.delay_total = 0;
-    return p;
-}
-// The line of a saturator vertex: two halves of 128 float2 (2 KB), kept in the same list; never cleared either
-// (Vertex::sat_total says how many of its frames hold values).
-float2* take_sat_line(td_graph* g, Vertex& v) {
-    if (v.sat_line) return v.sat_line;
-    const size_t bytes = 2 * sat::kLine * sizeof(float2);
-    float2* p = nullptr;
+// The block a delay, saturator, chorus or reverb vertex carries (Vertex::line): allocated when the vertex is first compiled into a
+// submission (never cleared: a word is read only once the vertex has written it, Line::total), freed with the graph's vertices.
+void* take_line(td_graph* g, Vertex& v, size_t bytes) {
+    if (v.line.d) return v.line.d;
+    void* p = nullptr;
     if (hipMalloc(&p, bytes) != hipSuccess) return nullptr;
-    g->delay_lines.push_back({reinterpret_cast<double*>(p), bytes});
     g->device_bytes += bytes;
-    v.sat_line = p;
-    v.sat_total = 0;
-    v.sat_parity = 0;
-    return p;
-}
-// The line of a chorus vertex: two halves of H float2 (at most 38 KB at 48 kHz), kept in the same list; never cleared either
-// (Vertex::chorus_total says how many of its frames hold values).
-float2* take_chorus_line(td_graph* g, Vertex& v, size_t H) {
-    if (v.chorus_line) return v.chorus_line;
-    const size_t bytes = 2 * H * sizeof(float2);
-    float2* p = nullptr;
-    if (hipMalloc(&p, bytes) != hipSuccess) return nullptr;
-    g->delay_lines.push_back({reinterpret_cast<double*>(p), bytes});
-    g->device_bytes += bytes;
-    v.chorus_line = p;
-    v.chorus_total = 0;
-    v.chorus_parity = 0;
-    return p;
-}
-// The state block of a reverb vertex: f[16] and the 24 lines, doubles, kept in the same list; never cleared either
-// (Vertex::reverb_total says which of its words hold values).
-double* take_reverb_state(td_graph* g, Vertex& v, size_t doubles) {
-    if (v.reverb_state) return v.reverb_state;
-    double* p = nullptr;
-    if (hipMalloc(&p, doubles * sizeof(double)) != hipSuccess) return nullptr;
-    g->delay_lines.push_back({p, doubles * sizeof(double)});
-    g->device_bytes += doubles * sizeof(double);
-    v.reverb_state = p;
-    v.reverb_total = 0;
+    v.line = {p, bytes, 0, 0};
     return p;
 }
 // the line a vertex would continue from in its next submission (nullptr: none -- it has none yet, or it starts afresh)
-static void* vertex_line(Vertex& v) {
-    return v.kind == K_SATURATOR ? (void*)v.sat_line : v.kind == K_CHORUS ? (void*)v.chorus_line : v.kind == K_REVERB ? (void*)v.reverb_state : (void*)v.delay_line;
-}
 static const void* carried_line(const Vertex& v) {
-    if (v.first_pending) return nullptr;
-    if (v.kind == K_DELAY && v.delay_line && v.delay_total) return v.delay_line;
-    if (v.kind == K_SATURATOR && v.sat_line && v.sat_total) return v.sat_line;
-    if (v.kind == K_CHORUS && v.chorus_line && v.chorus_total) return v.chorus_line;
-    if (v.kind == K_REVERB && v.reverb_state && v.reverb_total) return v.reverb_state;
-    return nullptr;
+    return !v.first_pending && v.line.total ? v.line.d : nullptr;
 }
-static void free_delay_lines(td_graph* g) {
-    for (auto& l : g->delay_lines) { (void)hipFree(l.first); g->device_bytes -= l.second; }
-    g->delay_lines.clear();
-    for (auto& v : g->vertices) { v.delay_line = nullptr; v.sat_line = nullptr; v.chorus_line = nullptr; v.reverb_state = nullptr; }
+static bool has_lines(const td_graph* g) {
+    for (const auto& v : g->vertices)
+        if (v.line.d) return true;
+    return false;
+}
+// (give_back false: no device to give them back to -- they leave the books with their vertices all the same)
+static void free_lines(td_graph* g, bool give_back) {
+    for (auto& v : g->vertices) {
+        if (!v.line.d) continue;
+        if (give_back) (void)hipFree(v.line.d);
+        g->device_bytes -= v.line.bytes;
+        v.line = {};
+    }
 }
 float2* take_buffer(td_graph* g) {
     if (!g->free_bufs.empty()) {
@@ -1061,30 +1020,19 @@ static int prepare_render(td_graph* g, size_t n_blocks, int bits, bool want_pcm,
     if (g->output_vertex < 0) return fail("TermDaw: error: output vertex not found.");
     if (g->plan_dirty) build_plan(g);
     if (!ensure_state_slots(g)) return 0;
-    if (!(launch_comp_detect && launch_comp_env && launch_comp_apply && launch_master_carry))
-        for (size_t vi : g->order)
-            if (g->vertices[vi].kind == K_COMPRESSOR && !(g->vertices[vi].wet < 0.0001f))
-                return fail("termdaw_amd: this build has no k_comp kernels: compressor vertices cannot be rendered");
-    if (!(launch_eq_local && launch_eq_carry && launch_eq_apply))
-        for (size_t vi : g->order)
-            if (g->vertices[vi].kind == K_EQ && !(g->vertices[vi].wet < 0.0001f))
-                return fail("termdaw_amd: this build has no k_eq kernels: eq vertices cannot be rendered");
-    if (!(launch_delay_local && launch_delay_carry && launch_delay_apply))
-        for (size_t vi : g->order)
-            if (g->vertices[vi].kind == K_DELAY && !(g->vertices[vi].wet < 0.0001f))
-                return fail("termdaw_amd: this build has no k_delay kernels: delay vertices cannot be rendered");
-    if (!(launch_sat_sum && launch_sat && launch_sat1))
-        for (size_t vi : g->order)
-            if (g->vertices[vi].kind == K_SATURATOR && !(g->vertices[vi].wet < 0.0001f))
-                return fail("termdaw_amd: this build has no k_sat kernels: saturator vertices cannot be rendered");
-    if (!(launch_chorus_sum && launch_chorus))
-        for (size_t vi : g->order)
-            if (g->vertices[vi].kind == K_CHORUS && !(g->vertices[vi].wet < 0.0001f))
-                return fail("termdaw_amd: this build has no k_chorus kernels: chorus vertices cannot be rendered");
-    if (!(launch_reverb_sum && launch_reverb))
-        for (size_t vi : g->order)
-            if (g->vertices[vi].kind == K_REVERB && !(g->vertices[vi].wet < 0.0001f))
-                return fail("termdaw_amd: this build has no k_reverb kernels: reverb vertices cannot be rendered");
+    const struct { Kind kind; bool built; const char* k; const char* name; } fx[] = {
+        {K_COMPRESSOR, launch_comp_detect && launch_comp_env && launch_comp_apply && launch_master_carry, "comp", "compressor"},
+        {K_EQ, launch_eq_local && launch_eq_carry && launch_eq_apply, "eq", "eq"},
+        {K_DELAY, launch_delay_local && launch_delay_carry && launch_delay_apply, "delay", "delay"},
+        {K_SATURATOR, launch_sat_sum && launch_sat && launch_sat1, "sat", "saturator"},
+        {K_CHORUS, launch_chorus_sum && launch_chorus, "chorus", "chorus"},
+        {K_REVERB, launch_reverb_sum && launch_reverb, "reverb", "reverb"},
+    };
+    for (const auto& f : fx)
+        if (!f.built)
+            for (size_t vi : g->order)
+                if (g->vertices[vi].kind == f.kind && !(g->vertices[vi].wet < 0.0001f))
+                    return fail(std::string("termdaw_amd: this build has no k_") + f.k + " kernels: " + f.name + " vertices cannot be rendered");
     const size_t bl = g->bl;
     if (bl == 0) return fail("termdaw_amd: buffer length 0");
     rp->n_blocks = n_blocks;
@@ -1188,10 +1136,7 @@ static bool starts_afresh(const td_graph* g) {
         const Vertex& v = g->vertices[vi];
         if (v.kind == K_NORMALIZE && !v.has_init_override) return false;
         if ((v.kind == K_BAND_PASS || v.kind == K_COMPRESSOR || v.kind == K_EQ) && v.state_slot >= 0 && !v.first_pending) return false;
-        if (v.kind == K_DELAY && v.delay_line && !v.first_pending) return false;
-        if (v.kind == K_SATURATOR && v.sat_line && !v.first_pending) return false;
-        if (v.kind == K_CHORUS && v.chorus_line && !v.first_pending) return false;
-        if (v.kind == K_REVERB && v.reverb_state && !v.first_pending) return false;
+        if (v.line.d && !v.first_pending) return false;
     }
     return true;
 }
@@ -1238,10 +1183,9 @@ static int guard_begin(td_graph* g, const td_samplebank* sb, td_flowwbank* fb, s
     size_t need = 0;
     for (size_t vi : g->order) {
         const Vertex& v = g->vertices[vi];
-        const void* line = carried_line(v);
-        if (!line) continue;
-        for (const auto& l : g->delay_lines)
-            if ((const void*)l.first == line) { q.lines.push_back({vi, need, l.second}); need += l.second; }
+        if (!carried_line(v)) continue;
+        q.lines.push_back({vi, need, v.line.bytes});
+        need += v.line.bytes;
     }
     if (need > q.lines_cap) {
         if (q.d_lines) (void)hipFree(q.d_lines);
@@ -1253,7 +1197,7 @@ static int guard_begin(td_graph* g, const td_samplebank* sb, td_flowwbank* fb, s
         q.lines_cap = need;
     }
     for (const auto& l : q.lines)
-        TD_HIP(hipMemcpyAsync((uint8_t*)q.d_lines + l.off, vertex_line(g->vertices[l.vertex]), l.bytes, hipMemcpyDeviceToDevice, g->stream));
+        TD_HIP(hipMemcpyAsync((uint8_t*)q.d_lines + l.off, g->vertices[l.vertex].line.d, l.bytes, hipMemcpyDeviceToDevice, g->stream));
     return 1;
 }
 // The stream has drained: look at the verdict of the last guarded render, and do that render again with the exact kernels
@@ -1282,8 +1226,8 @@ static int guard_settle(td_graph* g) {
     if (q.have_backup && hipMemcpyAsync(g->dstate, q.d_backup, g->hstate.size() * sizeof(StateSlot), hipMemcpyDeviceToDevice, g->stream) != hipSuccess)
         ok = fail("HIP error: the guard could not restore the carried state");
     for (const auto& l : q.lines)
-        if (ok && l.vertex < g->vertices.size() && vertex_line(g->vertices[l.vertex]) &&
-            hipMemcpyAsync(vertex_line(g->vertices[l.vertex]), (const uint8_t*)q.d_lines + l.off, l.bytes, hipMemcpyDeviceToDevice, g->stream) != hipSuccess)
+        if (ok && l.vertex < g->vertices.size() && g->vertices[l.vertex].line.d &&
+            hipMemcpyAsync(g->vertices[l.vertex].line.d, (const uint8_t*)q.d_lines + l.off, l.bytes, hipMemcpyDeviceToDevice, g->stream) != hipSuccess)
             ok = fail("HIP error: the guard could not restore a delay line");
     g->state_dev_dirty = true;
     if (ok) ok = graph_render_chunks(g, q.sb, q.fb, q.n_blocks, q.is_scan, q.bits, q.advance, q.scan_t0, q.want_pcm);
@@ -1316,12 +1260,8 @@ void HostSnapshot::take(const td_graph* g, const td_flowwbank* fb) {
     for (size_t i = 0; i < v.size(); ++i) {
         const Vertex& x = g->vertices[i];
         v[i].loop_t = x.loop_t;
-        v[i].delay_total = x.delay_total;
-        v[i].sat_total = x.sat_total;
-        v[i].sat_parity = x.sat_parity;
-        v[i].chorus_total = x.chorus_total;
-        v[i].chorus_parity = x.chorus_parity;
-        v[i].reverb_total = x.reverb_total;
+        v[i].total = x.line.total;
+        v[i].parity = x.line.parity;
         v[i].has_init_override = x.has_init_override;
         v[i].peak_known = x.peak_known;
         v[i].first_pending = x.first_pending;
@@ -1337,12 +1277,8 @@ void HostSnapshot::put(td_graph* g, td_flowwbank* fb) const {
     for (size_t i = 0; i < v.size() && i < g->vertices.size(); ++i) {
         Vertex& x = g->vertices[i];
         x.loop_t = v[i].loop_t;
-        x.delay_total = v[i].delay_total;
-        x.sat_total = v[i].sat_total;
-        x.sat_parity = v[i].sat_parity;
-        x.chorus_total = v[i].chorus_total;
-        x.chorus_parity = v[i].chorus_parity;
-        x.reverb_total = v[i].reverb_total;
+        x.line.total = v[i].total;
+        x.line.parity = v[i].parity;
         x.has_init_override = v[i].has_init_override;
         x.peak_known = v[i].peak_known;
         x.first_pending = v[i].first_pending;
@@ -1682,7 +1618,7 @@ void td_graph_free(td_graph* g) {
                 break;
             }
     }
-    const bool has_device_state = g->stream || !g->pool.empty() || !g->wavetables.empty() || !g->delay_lines.empty() || g->dstate || g->arena.d || g->d_pcm ||
+    const bool has_device_state = g->stream || !g->pool.empty() || !g->wavetables.empty() || has_lines(g) || g->dstate || g->arena.d || g->d_pcm ||
                                   g->d_out_f32 || g->d_resampled || g->d_scalar || g->d_stem_pcm || g->d_stem_peak || g->d_stem_f32 ||
                                   g->d_loud || g->d_master_src || g->d_master;
     if (has_device_state && hipSetDevice(g->device) == hipSuccess) {
@@ -1690,7 +1626,7 @@ void td_graph_free(td_graph* g) {
         else (void)hipDeviceSynchronize();   // (a graph whose stream could not be re-made after td_batch_free)
         for (float2* p : g->pool) (void)hipFree(p);
         for (float* p : g->wavetables) (void)hipFree(p);
-        free_delay_lines(g);
+        free_lines(g, true);
         free_tables(g);
         if (g->dstate) (void)hipFree(g->dstate);
         free_arena(g->arena);
@@ -1715,16 +1651,14 @@ void td_graph_free(td_graph* g) {
 }
 void td_graph_reset(td_graph* g) {
     g->guard.armed = false;   // (the vertices a pending verdict is about are going)
-    if ((g->stream || !g->wavetables.empty() || !g->delay_lines.empty()) && hipSetDevice(g->device) == hipSuccess) {
+    if ((g->stream || !g->wavetables.empty() || has_lines(g)) && hipSetDevice(g->device) == hipSuccess) {
         if (g->stream) (void)drain(g);   // (a deferred k_norm_fix belongs to the vertices about to go)
         for (float* p : g->wavetables) (void)hipFree(p);
-        free_delay_lines(g);
+        free_lines(g, true);
         free_tables(g);
     }
     g->wavetables.clear();
-    // (lines that could not be given back above -- no device -- leave the books with their vertices all the same)
-    for (auto& l : g->delay_lines) g->device_bytes -= l.second;
-    g->delay_lines.clear();
+    free_lines(g, false);   // (lines that could not be given back above -- no device)
     g->guard.lines.clear();
     g->vertices.clear();
     g->edges.clear();

@@ -124,21 +124,23 @@ struct Vertex {
     int eq_kind = 0;   // K_EQ: TD_EQ_*
     float eq_freq = 1000, eq_q = 1, eq_gain_db = 0;
     float delay_ms = 1, delay_feedback = 0, delay_cross = 0;   // K_DELAY
-    double* delay_line = nullptr;   // K_DELAY: the last D values of (ul, ur) in HBM, 16 D bytes (owned by the graph: td_graph::delay_lines), allocated when the vertex is first compiled into a submission
-    uint64_t delay_total = 0;       // K_DELAY: frames the vertex has run since its line restarted (the line's rotation is this mod D, its words below min(this, D) hold values)
     int sat_kind = 0, sat_oversample = 1;   // K_SATURATOR: TD_SAT_*, R
     float sat_drive_db = 0, sat_bias = 0, sat_out_db = 0;
-    float2* sat_line = nullptr;     // K_SATURATOR (R > 1): the last 128 raw input frames, two halves of 128 float2 used alternately (owned by the graph: td_graph::delay_lines), allocated when the vertex is first compiled into a submission
-    uint64_t sat_total = 0;         // K_SATURATOR: frames the vertex has run since its line restarted (a frame at or beyond min(this, 128) back reads as 0)
-    uint32_t sat_parity = 0;        // K_SATURATOR: the half of the line the next launch reads (the one the last launch wrote)
     int chorus_voices = 1, chorus_shape = 0;   // K_CHORUS: V, TD_CHORUS_*
     float chorus_delay_ms = 1, chorus_depth_ms = 0, chorus_rate_hz = 1, chorus_stereo = 0;
-    float2* chorus_line = nullptr;  // K_CHORUS: the last H raw input frames, two halves of H float2 used alternately (owned by the graph: td_graph::delay_lines), allocated when the vertex is first compiled into a submission
-    uint64_t chorus_total = 0;      // K_CHORUS: frames the vertex has run since its line restarted (a frame beyond min(this, H) back reads as 0)
-    uint32_t chorus_parity = 0;     // K_CHORUS: the half of the line the next launch reads (the one the last launch wrote)
     float reverb_room = 0.5f, reverb_damp = 0.5f, reverb_width = 1.0f, reverb_size = 1.0f;   // K_REVERB
-    double* reverb_state = nullptr;   // K_REVERB: f[16] and the 24 lines, one block of doubles (owned by the graph: td_graph::delay_lines), allocated when the vertex is first compiled into a submission
-    uint64_t reverb_total = 0;        // K_REVERB: frames the vertex has run since its restart (frame m of a line lives in slot m mod D; a read of m - D < 0 is 0)
+    // The block of device memory a delay, saturator, chorus or reverb vertex carries from chunk to chunk: allocated when the vertex
+    // is first compiled into a submission (take_line), never cleared, freed with the graph's vertices.
+    //   K_DELAY             the last D values of (ul, ur), 16 D bytes: the rotation is total mod D, the words below min(total, D) hold values
+    //   K_SATURATOR (R > 1) the last 128 raw input frames, two halves of 128 float2: a frame at or beyond min(total, 128) back reads as 0
+    //   K_CHORUS            the last H raw input frames, two halves of H float2: a frame beyond min(total, H) back reads as 0
+    //   K_REVERB            f[16] and the 24 lines, doubles: frame m of a line lives in slot m mod D, a read of m - D < 0 is 0
+    struct Line {
+        void* d = nullptr;
+        size_t bytes = 0;
+        uint64_t total = 0;    // frames the vertex has run since the block restarted
+        uint32_t parity = 0;   // (saturator, chorus) the half the next launch reads: the one the last launch wrote
+    } line;
     tdk::WaveTableD wavetable{};   // K_SAMPSYN: table in HBM (owned by the graph)
     // carried host state (what the reference keeps inside VertexExt, extensions.rs:15-80)
     uint64_t loop_t = 0;
@@ -319,7 +321,7 @@ namespace tde {
 struct HostSnapshot {
     size_t t = 0, fb_frame = 0;
     std::vector<size_t> fb_start;
-    struct V { uint64_t loop_t, delay_total, sat_total, chorus_total, reverb_total; uint32_t sat_parity, chorus_parity; bool has_init_override, peak_known, first_pending; float init_override; std::string state; };
+    struct V { uint64_t loop_t, total; uint32_t parity; bool has_init_override, peak_known, first_pending; float init_override; std::string state; };
     std::vector<V> v;
     void take(const td_graph* g, const td_flowwbank* fb);
     void put(td_graph* g, td_flowwbank* fb) const;
@@ -377,7 +379,6 @@ struct td_graph {
     std::vector<int> level;                   // per vertex, -1 = unreachable
     int n_levels = 0;
     std::vector<float*> wavetables;            // device tables of K_SAMPSYN vertices
-    std::vector<std::pair<double*, size_t>> delay_lines;   // the lines of K_DELAY vertices (Vertex::delay_line) of K_SATURATOR vertices (Vertex::sat_line) of K_CHORUS vertices (Vertex::chorus_line) and the state blocks of K_REVERB vertices (Vertex::reverb_state), and their bytes
     unsigned sat_tile = 256;                   // output frames per workgroup of k_sat (128 | 256 | 384: "debug.sat_tile"; provisional)
     unsigned chorus_tile = 256;                // output frames per workgroup of k_chorus (256 | 512 | 1024: "debug.chorus_tile"; provisional)
     unsigned reverb_form = 1;                  // k_reverb: 0 the serial walk of each comb's one-pole, 1 the wave scan ("debug.reverb_form")

@@ -2440,9 +2440,12 @@ TD_DEV double sat_shape(uint32_t kind, double u) {
     if (kind == 1u) return fabs(u) < 1.0 ? 1.5 * u - ((0.5 * u) * u) * u : copysign(1.0, u);
     return u / (1.0 + fabs(u));
 }
-// the summed input, materialised once for the tiles' halos: k_sum's frame mapping, identity epilogue
-__global__ __launch_bounds__(kThreads) void k_sat_sum(const SatDesc* __restrict__ descs) {
-    const SatDesc& d = descs[blockIdx.y];
+// the summed input of an effect vertex (SatDesc, ChorusDesc, ReverbDesc: ins, k, term_mode, frames, x), materialised once:
+// k_sum's frame mapping, identity epilogue -- here for the tiles' halos
+// (the body takes the kernel's own __restrict__ pointer: handed the descriptor by reference, the scalar load of d.x moves)
+template <class Desc>
+TD_DEV void fx_sum(const Desc* __restrict__ descs) {
+    const Desc& d = descs[blockIdx.y];
     const uint32_t M = d.frames, m0 = blockIdx.x * kTileFrames + 2u * threadIdx.x, m1 = m0 + kTileFrames / 2;
     if (blockIdx.x * kTileFrames >= M) return;
     float4 a0, a1;
@@ -2450,6 +2453,7 @@ __global__ __launch_bounds__(kThreads) void k_sat_sum(const SatDesc* __restrict_
     store_pair(d.x, m0, M, a0);
     store_pair(d.x, m1, M, a1);
 }
+__global__ __launch_bounds__(kThreads) void k_sat_sum(const SatDesc* __restrict__ descs) { fx_sum(descs); }
 // R = 1: p = (float)(g_out (f(g_in x + bias) - f(bias))), a non-finite x is its own p; no filters, no latency, no state
 __global__ __launch_bounds__(kThreads) void k_sat1(const SatDesc* __restrict__ descs) {
     const SatDesc& d = descs[blockIdx.y];
@@ -2583,15 +2587,7 @@ TD_DEV double chorus_lfo(uint32_t shape, double th) {
     return u * p;
 }
 // the summed input, materialised once for the gathers: k_sum's frame mapping, identity epilogue
-__global__ __launch_bounds__(kThreads) void k_chorus_sum(const ChorusDesc* __restrict__ descs) {
-    const ChorusDesc& d = descs[blockIdx.y];
-    const uint32_t M = d.frames, m0 = blockIdx.x * kTileFrames + 2u * threadIdx.x, m1 = m0 + kTileFrames / 2;
-    if (blockIdx.x * kTileFrames >= M) return;
-    float4 a0, a1;
-    sum_inputs_pairs(d.ins, d.k, d.term_mode, m0, m1, M, a0, a1);
-    store_pair(d.x, m0, M, a0);
-    store_pair(d.x, m1, M, a1);
-}
+__global__ __launch_bounds__(kThreads) void k_chorus_sum(const ChorusDesc* __restrict__ descs) { fx_sum(descs); }
 // TERMS: the term loop runs here, over the frames of the chunk this tile can reach, into LDS (a short chunk -- every block pull:
 // one launch); otherwise the kernel gathers from the buffer k_chorus_sum left, with plain global loads (adjacent lanes read
 // adjacent frames at a distance that drifts by less than half a frame per lane: L1 / L2 serve the 8 V re-reads).
@@ -2688,15 +2684,7 @@ __global__ __launch_bounds__(kThreads) void k_chorus(const ChorusDesc* __restric
 TD_DEV double gloadd(const double* p) { return *reinterpret_cast<const double TD_GLOBAL*>((const TD_GLOBAL char*)p); }
 TD_DEV void gstored(double* p, double v) { *reinterpret_cast<double TD_GLOBAL*>((TD_GLOBAL char*)p) = v; }
 // the summed input, materialised once: k_sum's frame mapping, identity epilogue
-__global__ __launch_bounds__(kThreads) void k_reverb_sum(const ReverbDesc* __restrict__ descs) {
-    const ReverbDesc& d = descs[blockIdx.y];
-    const uint32_t M = d.frames, m0 = blockIdx.x * kTileFrames + 2u * threadIdx.x, m1 = m0 + kTileFrames / 2;
-    if (blockIdx.x * kTileFrames >= M) return;
-    float4 a0, a1;
-    sum_inputs_pairs(d.ins, d.k, d.term_mode, m0, m1, M, a0, a1);
-    store_pair(d.x, m0, M, a0);
-    store_pair(d.x, m1, M, a1);
-}
+__global__ __launch_bounds__(kThreads) void k_reverb_sum(const ReverbDesc* __restrict__ descs) { fx_sum(descs); }
 constexpr uint32_t kReverbRow = 256;   // doubles per (comb, channel) row of the window's delayed reads in LDS
 // The chunk in windows of B = 64 Q frames.  Per window:
 //   combs (all 16 waves; a lane takes Q consecutive frames): w = cline[n - D] from global memory, kept in registers and left in

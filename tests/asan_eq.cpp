@@ -15,7 +15,7 @@
 #include "termdaw_amd.h"
 
 extern size_t g_eq_launches[3], g_eq_vertices, g_eq_fresh, g_eq_carried;
-extern double g_eq_path_gain;
+extern double g_fx_path_gain;
 
 static std::string slurp(const std::string& p) {
     std::string s; FILE* f = fopen(p.c_str(), "rb"); if (!f) return s;
@@ -43,7 +43,7 @@ int main(int argc, char** argv) {
                 std::vector<unsigned char> pcm(td_state_render_to_memory(s, nullptr, 0) + 16);
                 if (mode == 5 && !chunked) {
                     td_graph_set_profiling(g, 1);
-                    g_eq_path_gain = 0.0;
+                    g_fx_path_gain = 0.0;
                 }
                 for (int k = 0; k < 3; ++k) {
                     if (k == 1 && !td_state_scan_exact(s)) bad(dir + " scan");
@@ -55,7 +55,7 @@ int main(int argc, char** argv) {
                         printf("launches %s:", dir.c_str());
                         for (size_t i = 0; i < n && i < 64; ++i) printf(" %s=%zu", names[i], cnt[i]);
                         printf("\n");
-                        printf("guard %s: path=%.9g\n", dir.c_str(), g_eq_path_gain);
+                        printf("guard %s: path=%.9g\n", dir.c_str(), g_fx_path_gain);
                         td_graph_set_profiling(g, 0);
                     }
                 }

@@ -1,26 +1,22 @@
-// Sanitizer run of the chorus vertex' host side (built by tests/test_chorus_host.py with g++ -fsanitize=address,undefined
-// against tests/mock_hip.cpp + tests/mock_chorus.cpp -- no GPU, nothing computed): every project goes through the front-end and the C
-// ABI in every band mode with sine modes 1 and 2, un-chunked and in 4 096-frame chunks (the one-launch form), with 256 and
-// (chunked) 512 frames per tile -- fresh, scanned and continued renders, block pulls, a set_time in between, a batch of the
-// project with a second copy of itself.
+// Sanitizer run of the host side of an effect vertex that carries a line -- delay, saturator, chorus, reverb (built by
+// tests/test_{delay,saturator,chorus,reverb}_host.py with g++ -fsanitize=address,undefined against tests/mock_hip.cpp +
+// tests/mock_guard.cpp + the ONE kind's mock, whose g_fx names the kind and holds what differs between them: asan_fx.h -- no GPU,
+// nothing computed): every project goes through the front-end and the C ABI in every band mode with sine modes 1 and 2, un-chunked
+// and in 4 096-frame chunks, with the kind's debug.* options in some of them -- fresh, scanned and continued renders, block pulls, a
+// set_time in between, a batch of the project with a second copy of itself.
 // Per project it prints the launch families one profiled render under the guard modes went through ("launches <dir>: name=count
 // ..."), the static gain the guard carried from its last guarded launch to the output ("guard <dir>: path=..."), and what three
 // block pulls under the guard, each told to run again, found in the line on entry ("redo <dir>: redos=<n> entries=<stamps>",
-// mock_chorus.cpp) -- which is what the guard-rule, backup and launch-list tests read.
-//   usage: asan_chorus <dir> ...     each <dir> holds project.lua and meta.txt ("<buffer length>")
+// the mock's) -- which is what the guard-rule, backup and launch-list tests read.
+//   usage: asan_<kind> <dir> ...     each <dir> holds project.lua and meta.txt ("<buffer length>")
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <string>
 #include <vector>
 
+#include "asan_fx.h"
 #include "termdaw_amd.h"
-
-extern size_t g_cho_launches[2], g_cho_vertices, g_cho_single, g_cho_fresh, g_cho_carried;
-extern double g_cho_path_gain;
-extern int g_cho_force_redo, g_cho_after_set_time;
-extern size_t g_cho_restarts, g_cho_short;
-extern std::vector<double> g_cho_entry_log;
 
 static std::string slurp(const std::string& p) {
     std::string s; FILE* f = fopen(p.c_str(), "rb"); if (!f) return s;
@@ -41,7 +37,7 @@ int main(int argc, char** argv) {
                 td_state_set_option(s, "band_mode", mode % 3);
                 td_state_set_option(s, "sine_mode", mode < 3 ? 1 : 2);
                 if (chunked) td_state_set_option(s, "max_chunk_frames", 4096);
-                if (chunked && (mode & 1)) td_state_set_option(s, "debug.chorus_tile", 512);
+                g_fx.options(s, mode, chunked);
                 if (mode % 3 == 2 && chunked) td_state_set_option(s, "band_guard_ppb", 0);   // (every audited render is done again)
                 if (!td_state_refresh_source(s, lua.c_str())) { ++rejected; td_state_free(s); continue; }
                 td_graph* g = td_state_graph(s);
@@ -49,7 +45,7 @@ int main(int argc, char** argv) {
                 std::vector<unsigned char> pcm(td_state_render_to_memory(s, nullptr, 0) + 16);
                 if (mode == 5 && !chunked) {
                     td_graph_set_profiling(g, 1);
-                    g_cho_path_gain = 0.0;
+                    g_fx_path_gain = 0.0;
                 }
                 for (int k = 0; k < 3; ++k) {
                     if (k == 1 && !td_state_scan_exact(s)) bad(dir + " scan");
@@ -61,7 +57,7 @@ int main(int argc, char** argv) {
                         printf("launches %s:", dir.c_str());
                         for (size_t i = 0; i < n && i < 64; ++i) printf(" %s=%zu", names[i], cnt[i]);
                         printf("\n");
-                        printf("guard %s: path=%.9g\n", dir.c_str(), g_cho_path_gain);
+                        printf("guard %s: path=%.9g\n", dir.c_str(), g_fx_path_gain);
                         td_graph_set_profiling(g, 0);
                     }
                 }
@@ -69,10 +65,10 @@ int main(int argc, char** argv) {
                     // block pulls continue from the line; a set_time in between restarts it; then a whole render again
                     std::vector<float> l(bl), r(bl);
                     for (int k = 0; k < 3; ++k) {
-                        // (mock_chorus.cpp checks that the pull right behind the set_time enters with nothing of the line)
-                        if (k == 2) { td_graph_set_time(g, 0); td_flowwbank_set_time(td_state_flowwbank(s), 0); g_cho_after_set_time = 1; }
+                        // (the mock checks that the pull right behind the set_time enters with nothing of the line)
+                        if (k == 2) { td_graph_set_time(g, 0); td_flowwbank_set_time(td_state_flowwbank(s), 0); g_fx_after_set_time = 1; }
                         if (td_graph_render_block(g, td_state_samplebank(s), td_state_flowwbank(s), l.data(), r.data()) < 0) bad(dir + " pull");
-                        g_cho_after_set_time = 0;
+                        g_fx_after_set_time = 0;
                         ++pulls;
                     }
                     if (mode == 5 && !chunked) {
@@ -83,18 +79,18 @@ int main(int argc, char** argv) {
                         td_flowwbank_set_time(td_state_flowwbank(s), 0);
                         td_graph_sync(g);
                         td_graph_band_guard_stats(g, st0);
-                        g_cho_entry_log.clear();
-                        g_cho_force_redo = 1;
+                        g_fx_entry_log.clear();
+                        g_fx_force_redo = 1;
                         for (int k = 0; k < 3; ++k) {
                             if (td_graph_render_block(g, td_state_samplebank(s), td_state_flowwbank(s), l.data(), r.data()) < 0) bad(dir + " guarded pull");
                             td_flowwbank_set_time_to_next_block(td_state_flowwbank(s));
                             ++pulls;
                         }
                         td_graph_sync(g);
-                        g_cho_force_redo = 0;
+                        g_fx_force_redo = 0;
                         td_graph_band_guard_stats(g, st1);
                         printf("redo %s: redos=%d entries=", dir.c_str(), (int)(st1[1] - st0[1]));
-                        for (size_t i = 0; i < g_cho_entry_log.size(); ++i) printf("%s%.0f", i ? "," : "", g_cho_entry_log[i]);
+                        for (size_t i = 0; i < g_fx_entry_log.size(); ++i) printf("%s%.0f", i ? "," : "", g_fx_entry_log[i]);
                         printf("\n");
                     }
                     td_graph_set_time(g, 0);
@@ -121,14 +117,8 @@ int main(int argc, char** argv) {
                 td_state_free(s);
             }
     }
-    if (g_cho_launches[1] < g_cho_launches[0]) {   // (every k_chorus_sum is followed by a k_chorus)
-        ++failed;
-        fprintf(stderr, "launch counts: k_chorus_sum %zu k_chorus %zu\n", g_cho_launches[0], g_cho_launches[1]);
-    }
-    printf("asan_chorus done: %d projects, %zu renders, %zu pulls, %zu rejected refreshes, %zu failed calls; k_chorus launches %zu "
-           "(%zu vertices, %zu one-launch, %zu entered fresh, %zu entered with the line; %zu k_chorus_sum launches; "
-           "%zu restarts checked; %zu short chunks)\n",
-           argc - 1, renders, pulls, rejected, failed, g_cho_launches[1], g_cho_vertices, g_cho_single, g_cho_fresh, g_cho_carried,
-           g_cho_launches[0], g_cho_restarts, g_cho_short);
+    if (!g_fx.closing()) ++failed;
+    printf("asan_%s done: %d projects, %zu renders, %zu pulls, %zu rejected refreshes, %zu failed calls; ", g_fx.name, argc - 1, renders, pulls, rejected, failed);
+    g_fx.summary();
     return failed ? 1 : 0;
 }

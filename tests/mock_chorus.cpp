@@ -6,9 +6,8 @@
 // absolute time, the line (2 H frames, `filled` <= H and equal to the frames the vertex has run since it restarted, the half a
 // launch reads being the half a launch before it wrote; nothing after a set_time), chunks shorter than the line, and that
 // k_chorus_sum comes first exactly when the chunk is longer than kSatInlineFrames.
-// It also listens to the guard: the audit launches of mock_hip.cpp are wrapped at link time (-Wl,--wrap); the static gain the
-// engine carried from a guarded launch to the graph's output is kept for the driver to print, and with g_cho_force_redo set
-// every audited render is told to run again.  For that case k_chorus stamps the half of the line it writes and logs the stamp it
+// With g_fx_force_redo set the guard's listeners (tests/mock_guard.cpp) tell every audited render to run again.  For that case
+// k_chorus stamps the half of the line it writes and logs the stamp it
 // finds in the half it reads: a render done again must find what the first one found, not what the first one left.
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
@@ -20,34 +19,17 @@
 #include <map>
 #include <vector>
 
-#include "kernels.h"
+#define MOCK_NAME "mock_chorus"
+#include "mock_util.h"
+#include "asan_fx.h"
+#include "termdaw_amd.h"
 
-static volatile unsigned char g_cho_sink;
-static void touch(const void* p, size_t bytes) {
-    if (!p || !bytes) return;
-    const volatile unsigned char* b = (const volatile unsigned char*)p;
-    g_cho_sink ^= b[0];
-    g_cho_sink ^= b[bytes - 1];
-}
-static void touch_w(void* p, size_t bytes) {
-    if (!p || !bytes) return;
-    volatile unsigned char* b = (volatile unsigned char*)p;
-    b[0] = b[0];
-    b[bytes - 1] = b[bytes - 1];
-}
-[[noreturn]] static void die(const char* what) {
-    fprintf(stderr, "mock_chorus: %s\n", what);
-    abort();
-}
-
-size_t g_cho_launches[2] = {0, 0}, g_cho_vertices = 0, g_cho_single = 0, g_cho_fresh = 0, g_cho_carried = 0;
-double g_cho_path_gain = 0.0;   // the last guarded launch's static gain to the output (0: none since the driver cleared it)
-int g_cho_force_redo = 0;       // every audited render is to be done again
-int g_cho_after_set_time = 0;   // the driver has called td_graph_set_time and not submitted since: every vertex must enter with nothing of its line
-size_t g_cho_restarts = 0;      // descriptors checked under that flag
-size_t g_cho_short = 0;         // descriptors whose chunk was shorter than the line
-std::vector<double> g_cho_entry_log;   // per k_chorus descriptor that enters with the line: the stamp found in the half it reads
-static float g_cho_stamp = 0.0f;
+size_t g_fx_launches[3] = {0, 0, 0}, g_fx_vertices = 0, g_fx_single = 0, g_fx_fresh = 0, g_fx_carried = 0;
+int g_fx_after_set_time = 0;   // the driver has called td_graph_set_time and not submitted since: every vertex must enter with nothing of its line
+size_t g_fx_restarts = 0;      // descriptors checked under that flag
+size_t g_fx_short = 0;         // descriptors whose chunk was shorter than the line
+std::vector<double> g_fx_entry_log;   // per k_chorus descriptor that enters with the line: the stamp found in the half it reads
+static float g_fx_stamp = 0.0f;
 
 namespace {
 struct LineBook { uint64_t total; uint32_t written; };   // frames since the restart; the half the last launch wrote
@@ -58,20 +40,10 @@ std::map<const float2*, uint32_t> g_summed;   // x buffers k_chorus_sum has fill
 }  // namespace
 
 namespace tdk {
-static void touch_chorus_terms(const InTerm* ins, uint32_t k, uint32_t frames) {
-    touch(ins, (size_t)k * sizeof(InTerm));
-    for (uint32_t i = 0; i < k; ++i) {
-        const InTerm& t = ins[i];
-        if (t.kind == 0u || t.kind == 4u) touch(t.p, (size_t)frames * sizeof(float2));
-        else if (t.kind == 3u) touch(t.p, ((size_t)t.len + 15) * 4);
-        else if (t.kind == 1u || t.kind == 2u) touch(t.p, ((size_t)t.len + 15) * sizeof(float2));
-        else die("a chorus vertex takes terms of kinds 0 .. 4 only");
-    }
-}
 // which: 0 k_chorus_sum, 1 k_chorus
 static void check(const ChorusDesc* d, int n, int which, uint32_t n_tiles, bool terms, uint32_t frames) {
     touch(d, (size_t)std::max(n, 0) * sizeof(ChorusDesc));
-    g_cho_launches[which] += 1;
+    g_fx_launches[which] += 1;
     if (n <= 0) die("an empty launch");
     for (int i = 0; i < n; ++i) {
         const ChorusDesc& s = d[i];
@@ -89,7 +61,7 @@ static void check(const ChorusDesc* d, int n, int which, uint32_t n_tiles, bool 
         if (s.n_tiles != (s.frames + s.F - 1u) / s.F || s.n_tiles >= (1u << 20)) die("tiling");
         if (s.filled > s.H || s.parity > 1u) die("line fill / parity");
         if (s.t0 > (1ull << 40)) die("the absolute time");
-        touch_chorus_terms(s.ins, s.k, s.frames);
+        touch_terms(s.ins, s.k, s.frames, "a chorus vertex takes terms of kinds 0 .. 4 only");
         touch_w(s.out, (size_t)s.frames * sizeof(float2));
         touch_w(s.line, (size_t)2 * s.H * sizeof(float2));
         const bool multi = s.frames > kSatInlineFrames;
@@ -114,13 +86,13 @@ static void check(const ChorusDesc* d, int n, int which, uint32_t n_tiles, bool 
             g_summed.erase(it);
         }
         // the line's books: filled = min(frames since the restart, H), the half read is the half the last launch wrote
-        g_cho_vertices += 1;
-        if (terms) g_cho_single += 1;
-        if (s.frames < s.H) g_cho_short += 1;
-        (s.filled ? g_cho_carried : g_cho_fresh) += 1;
-        if (g_cho_after_set_time) {
+        g_fx_vertices += 1;
+        if (terms) g_fx_single += 1;
+        if (s.frames < s.H) g_fx_short += 1;
+        (s.filled ? g_fx_carried : g_fx_fresh) += 1;
+        if (g_fx_after_set_time) {
             if (s.filled != 0u) die("a vertex entered with its line after a set_time");
-            g_cho_restarts += 1;
+            g_fx_restarts += 1;
         }
         std::vector<LineBook>& hist = g_lines[s.line];
         uint64_t total = 0;
@@ -128,40 +100,34 @@ static void check(const ChorusDesc* d, int n, int which, uint32_t n_tiles, bool 
             while (!hist.empty() && !(s.filled == std::min<uint64_t>(hist.back().total, s.H) && s.parity == hist.back().written)) hist.pop_back();
             if (hist.empty()) die("filled / parity: the vertex enters with no state its line has been in since it restarted");
             total = hist.back().total;
-            g_cho_entry_log.push_back((double)s.line[(size_t)s.parity * s.H + s.H - 1u].x);
+            g_fx_entry_log.push_back((double)s.line[(size_t)s.parity * s.H + s.H - 1u].x);
         } else {
             hist.clear();
         }
         hist.push_back(LineBook{total + s.frames, s.parity ^ 1u});
-        g_cho_stamp += 1.0f;
-        for (uint32_t m = 0; m < s.H; ++m) s.line[(size_t)(s.parity ^ 1u) * s.H + m] = make_float2(g_cho_stamp, g_cho_stamp);
+        g_fx_stamp += 1.0f;
+        for (uint32_t m = 0; m < s.H; ++m) s.line[(size_t)(s.parity ^ 1u) * s.H + m] = make_float2(g_fx_stamp, g_fx_stamp);
     }
 }
 void launch_chorus_sum(const ChorusDesc* d, int n, uint32_t frames, hipStream_t) { check(d, n, 0, 0, false, frames); }
 void launch_chorus(const ChorusDesc* d, int n, uint32_t n_tiles, uint32_t frames, bool terms, hipStream_t) { check(d, n, 1, n_tiles, terms, frames); }
-
-// ---- the guard's launches, wrapped (ld --wrap: the engine's calls arrive here, __real_ is mock_hip.cpp's) ----
-void real_band_audit(const AuditHead* h, int n, hipStream_t s) asm("__real__ZN3tdk17launch_band_auditEPKNS_9AuditHeadEiP12ihipStream_t");
-void wrap_band_audit(const AuditHead* h, int n, hipStream_t s) asm("__wrap__ZN3tdk17launch_band_auditEPKNS_9AuditHeadEiP12ihipStream_t");
-void wrap_band_audit(const AuditHead* h, int n, hipStream_t s) {
-    for (int i = 0; i < n; ++i) {
-        for (uint32_t j = 0; j < h[i].n; ++j) g_cho_path_gain = (double)h[i].descs[j].gain;
-        if (g_cho_force_redo) h[i].host_word[0] = 1u;
-    }
-    real_band_audit(h, n, s);
-}
-void real_band_chain(const BandScanDesc* d, int n, uint32_t frames, uint32_t a, bool guarded, hipStream_t s)
-    asm("__real__ZN3tdk17launch_band_chainEPKNS_12BandScanDescEijjbP12ihipStream_t");
-void wrap_band_chain(const BandScanDesc* d, int n, uint32_t frames, uint32_t a, bool guarded, hipStream_t s)
-    asm("__wrap__ZN3tdk17launch_band_chainEPKNS_12BandScanDescEijjbP12ihipStream_t");
-void wrap_band_chain(const BandScanDesc* d, int n, uint32_t frames, uint32_t a, bool guarded, hipStream_t s) {
-    // (a chain launch that gives its own verdict: nz_scale = gain^2 / frames)
-    if (guarded)
-        for (int i = 0; i < n; ++i)
-            if (d[i].nz_scale > 0.0f) {
-                g_cho_path_gain = std::sqrt((double)d[i].nz_scale * (double)frames);
-                if (g_cho_force_redo && d[i].nz_host) d[i].nz_host[0] = 1u;
-            }
-    real_band_chain(d, n, frames, a, guarded, s);
-}
 }  // namespace tdk
+
+// ---- what tests/asan_fx.cpp needs to know about the kind: 256 and (chunked, odd modes) 512 frames per tile; the 4 096-frame chunks
+// are the one-launch form
+const FxHooks g_fx = {
+    "chorus",
+    [](td_state* s, int mode, int chunked) {
+        if (chunked && (mode & 1)) td_state_set_option(s, "debug.chorus_tile", 512);
+    },
+    []() {
+        if (g_fx_launches[1] >= g_fx_launches[0]) return true;   // (every k_chorus_sum is followed by a k_chorus)
+        fprintf(stderr, "launch counts: k_chorus_sum %zu k_chorus %zu\n", g_fx_launches[0], g_fx_launches[1]);
+        return false;
+    },
+    []() {
+        printf("k_chorus launches %zu (%zu vertices, %zu one-launch, %zu entered fresh, %zu entered with the line; %zu k_chorus_sum launches; "
+               "%zu restarts checked; %zu short chunks)\n",
+               g_fx_launches[1], g_fx_vertices, g_fx_single, g_fx_fresh, g_fx_carried, g_fx_launches[0], g_fx_restarts, g_fx_short);
+    },
+};

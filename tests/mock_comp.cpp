@@ -13,25 +13,8 @@
 #include <cmath>
 #include <map>
 
-#include "kernels.h"
-
-static volatile unsigned char g_comp_sink;
-static void touch(const void* p, size_t bytes) {
-    if (!p || !bytes) return;
-    const volatile unsigned char* b = (const volatile unsigned char*)p;
-    g_comp_sink ^= b[0];
-    g_comp_sink ^= b[bytes - 1];
-}
-static void touch_w(void* p, size_t bytes) {
-    if (!p || !bytes) return;
-    volatile unsigned char* b = (volatile unsigned char*)p;
-    b[0] = b[0];
-    b[bytes - 1] = b[bytes - 1];
-}
-[[noreturn]] static void die(const char* what) {
-    fprintf(stderr, "mock_comp: %s\n", what);
-    abort();
-}
+#define MOCK_NAME "mock_comp"
+#include "mock_util.h"
 
 size_t g_comp_launches[5] = {0, 0, 0, 0, 0}, g_comp_vertices = 0, g_comp_fresh = 0, g_comp_carried = 0;
 
@@ -42,16 +25,6 @@ std::map<const double*, const double*> g_agg2_of;  // agg2 words -> agg1 words
 }  // namespace
 
 namespace tdk {
-static void touch_comp_terms(const InTerm* ins, uint32_t k, uint32_t frames) {
-    touch(ins, (size_t)k * sizeof(InTerm));
-    for (uint32_t i = 0; i < k; ++i) {
-        const InTerm& t = ins[i];
-        if (t.kind == 0u || t.kind == 4u) touch(t.p, (size_t)frames * sizeof(float2));
-        else if (t.kind == 3u) touch(t.p, ((size_t)t.len + 15) * 4);
-        else if (t.kind == 1u || t.kind == 2u) touch(t.p, ((size_t)t.len + 15) * sizeof(float2));
-        else die("a compressor vertex takes terms of kinds 0 .. 4 only");
-    }
-}
 static void check(const CompDesc* d, int n, uint32_t max_tiles, int which) {
     touch(d, (size_t)std::max(n, 0) * sizeof(CompDesc));
     g_comp_launches[which] += 1;
@@ -70,7 +43,7 @@ static void check(const CompDesc* d, int n, uint32_t max_tiles, int which) {
             if (std::fabs(s.pwR[k] - std::pow(s.aR, e)) > 1e-12 || std::fabs(s.pwA[k] - std::pow(s.aA, e)) > 1e-12) die("powers");
         }
         if ((((uintptr_t)s.x) | ((uintptr_t)s.dy) | ((uintptr_t)s.out)) & 15u) die("alignment");
-        touch_comp_terms(s.ins, s.k, s.frames);
+        touch_terms(s.ins, s.k, s.frames, "a compressor vertex takes terms of kinds 0 .. 4 only");
         touch_w(s.x, (size_t)s.frames * sizeof(float2));
         touch_w(s.dy, (size_t)((s.frames + 1u) & ~1u) * sizeof(double));   // (pairs: an odd chunk's last store covers one frame more)
         touch_w(s.out, (size_t)s.frames * sizeof(float2));

@@ -6,9 +6,8 @@
 // (16 D bytes, the rotation below D, no more words read than the vertex has written; none after a set_time), that every matrix
 // power is within 2 ulp of a long-double recomputation done here, that the launches of a vertex come in order (local, carry,
 // apply) and that a vertex takes k_delay_apply alone exactly when one tile covers its chunk.
-// It also listens to the guard: the audit launches of mock_hip.cpp are wrapped at link time (-Wl,--wrap); the static gain the
-// engine carried from a guarded launch to the graph's output is kept for the driver to print, and with g_delay_force_redo set
-// every audited render is told to run again.  For that case k_delay_apply stamps the line words it rewrites and logs the stamp
+// With g_fx_force_redo set the guard's listeners (tests/mock_guard.cpp) tell every audited render to run again.  For that case
+// k_delay_apply stamps the line words it rewrites and logs the stamp
 // its lane 0 finds on entry: a render done again must find what the first one found, not what the first one left.
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
@@ -20,33 +19,17 @@
 #include <map>
 #include <vector>
 
-#include "kernels.h"
+#define MOCK_NAME "mock_delay"
+#include "mock_util.h"
+#include "asan_fx.h"
+#include "termdaw_amd.h"
 
-static volatile unsigned char g_delay_sink;
-static void touch(const void* p, size_t bytes) {
-    if (!p || !bytes) return;
-    const volatile unsigned char* b = (const volatile unsigned char*)p;
-    g_delay_sink ^= b[0];
-    g_delay_sink ^= b[bytes - 1];
-}
-static void touch_w(void* p, size_t bytes) {
-    if (!p || !bytes) return;
-    volatile unsigned char* b = (volatile unsigned char*)p;
-    b[0] = b[0];
-    b[bytes - 1] = b[bytes - 1];
-}
-[[noreturn]] static void die(const char* what) {
-    fprintf(stderr, "mock_delay: %s\n", what);
-    abort();
-}
-
-size_t g_delay_launches[3] = {0, 0, 0}, g_delay_vertices = 0, g_delay_single = 0, g_delay_fresh = 0, g_delay_carried = 0;
-double g_delay_path_gain = 0.0;   // the last guarded launch's static gain to the output (0: none since the driver cleared it)
-int g_delay_force_redo = 0;       // every audited render is to be done again
-int g_delay_after_set_time = 0;   // the driver has called td_graph_set_time and not submitted since: every vertex must enter with nothing of its line
-size_t g_delay_restarts = 0;      // descriptors checked under that flag
-std::vector<double> g_delay_entry_log;   // per k_delay_apply descriptor whose lane 0 enters with a written word: the stamp found there
-static double g_delay_stamp = 0.0;
+size_t g_fx_launches[3] = {0, 0, 0}, g_fx_vertices = 0, g_fx_single = 0, g_fx_fresh = 0, g_fx_carried = 0;
+int g_fx_after_set_time = 0;   // the driver has called td_graph_set_time and not submitted since: every vertex must enter with nothing of its line
+size_t g_fx_restarts = 0;      // descriptors checked under that flag
+std::vector<double> g_fx_entry_log;   // per k_delay_apply descriptor whose lane 0 enters with a written word: the stamp found there
+size_t g_fx_short = 0;         // (none counted: the delay has no short-chunk form)
+static double g_fx_stamp = 0.0;
 
 namespace {
 struct Track { int phase; const double* carry; const double* line; uint32_t n_tiles, lanes, pos, filled; };
@@ -80,19 +63,9 @@ void near(const double (&got)[4], const M2& want, const char* what) {
 }  // namespace
 
 namespace tdk {
-static void touch_delay_terms(const InTerm* ins, uint32_t k, uint32_t frames) {
-    touch(ins, (size_t)k * sizeof(InTerm));
-    for (uint32_t i = 0; i < k; ++i) {
-        const InTerm& t = ins[i];
-        if (t.kind == 0u || t.kind == 4u) touch(t.p, (size_t)frames * sizeof(float2));
-        else if (t.kind == 3u) touch(t.p, ((size_t)t.len + 15) * 4);
-        else if (t.kind == 1u || t.kind == 2u) touch(t.p, ((size_t)t.len + 15) * sizeof(float2));
-        else die("a delay vertex takes terms of kinds 0 .. 4 only");
-    }
-}
 static void check(const DelayDesc* d, int n, uint32_t max_groups, int which, bool single_launch = false) {
     touch(d, (size_t)std::max(n, 0) * sizeof(DelayDesc));
-    g_delay_launches[which] += 1;
+    g_fx_launches[which] += 1;
     if (n <= 0 || !max_groups) die("an empty launch");
     for (int i = 0; i < n; ++i) {
         const DelayDesc& s = d[i];
@@ -112,7 +85,7 @@ static void check(const DelayDesc* d, int n, uint32_t max_groups, int which, boo
         if (!(s.wet >= 0.0001f && s.wet <= 1.0f)) die("wet");
         if (!(s.gs >= 0.0 && s.gc >= 0.0 && s.gs + s.gc <= 0.98 + 1e-7)) die("feedback");
         if ((((uintptr_t)s.out) | ((uintptr_t)s.line)) & 15u) die("alignment");
-        touch_delay_terms(s.ins, s.k, s.frames);
+        touch_terms(s.ins, s.k, s.frames, "a delay vertex takes terms of kinds 0 .. 4 only");
         touch_w(s.out, (size_t)s.frames * sizeof(float2));
         touch_w(s.line, (size_t)s.D * 16);
         if (!single) {
@@ -137,12 +110,12 @@ static void check(const DelayDesc* d, int n, uint32_t max_groups, int which, boo
                 near(s.pwc[k], p, "carry powers");
                 p = mul(p, p);
             }
-            g_delay_vertices += 1;
-            if (single) g_delay_single += 1;
-            (s.filled ? g_delay_carried : g_delay_fresh) += 1;
-            if (g_delay_after_set_time) {   // none of the line after a set_time: no word holds a value, the rotation starts over
+            g_fx_vertices += 1;
+            if (single) g_fx_single += 1;
+            (s.filled ? g_fx_carried : g_fx_fresh) += 1;
+            if (g_fx_after_set_time) {   // none of the line after a set_time: no word holds a value, the rotation starts over
                 if (s.filled != 0u || s.pos != 0u) die("a vertex entered with its line after a set_time");
-                g_delay_restarts += 1;
+                g_fx_restarts += 1;
             }
         }
         if (which == 0) {
@@ -157,13 +130,13 @@ static void check(const DelayDesc* d, int n, uint32_t max_groups, int which, boo
             it->second.phase = which == 1 ? 2 : 0;
         }
         if (which == 2) {
-            if (s.pos < s.filled) g_delay_entry_log.push_back(s.line[2u * (size_t)s.pos]);
+            if (s.pos < s.filled) g_fx_entry_log.push_back(s.line[2u * (size_t)s.pos]);
             // (the words of the chunk's last D frames are rewritten, as the kernel does)
-            g_delay_stamp += 1.0;
+            g_fx_stamp += 1.0;
             for (uint32_t m = 0; m < s.lanes; ++m) {
                 const size_t w = 2u * (size_t)(((uint64_t)s.pos + m) % s.D);
-                s.line[w] = g_delay_stamp;
-                s.line[w + 1u] = g_delay_stamp;
+                s.line[w] = g_fx_stamp;
+                s.line[w + 1u] = g_fx_stamp;
             }
         }
     }
@@ -174,29 +147,22 @@ void launch_delay_apply(const DelayDesc* d, int n, uint32_t max_groups, bool sin
     if (max_groups & kDelaySingleBit) die("the instantiation bit reached the launch");
     check(d, n, max_groups, 2, single);
 }
-
-// ---- the guard's launches, wrapped (ld --wrap: the engine's calls arrive here, __real_ is mock_hip.cpp's) ----
-void real_band_audit(const AuditHead* h, int n, hipStream_t s) asm("__real__ZN3tdk17launch_band_auditEPKNS_9AuditHeadEiP12ihipStream_t");
-void wrap_band_audit(const AuditHead* h, int n, hipStream_t s) asm("__wrap__ZN3tdk17launch_band_auditEPKNS_9AuditHeadEiP12ihipStream_t");
-void wrap_band_audit(const AuditHead* h, int n, hipStream_t s) {
-    for (int i = 0; i < n; ++i) {
-        for (uint32_t j = 0; j < h[i].n; ++j) g_delay_path_gain = (double)h[i].descs[j].gain;
-        if (g_delay_force_redo) h[i].host_word[0] = 1u;
-    }
-    real_band_audit(h, n, s);
-}
-void real_band_chain(const BandScanDesc* d, int n, uint32_t frames, uint32_t a, bool guarded, hipStream_t s)
-    asm("__real__ZN3tdk17launch_band_chainEPKNS_12BandScanDescEijjbP12ihipStream_t");
-void wrap_band_chain(const BandScanDesc* d, int n, uint32_t frames, uint32_t a, bool guarded, hipStream_t s)
-    asm("__wrap__ZN3tdk17launch_band_chainEPKNS_12BandScanDescEijjbP12ihipStream_t");
-void wrap_band_chain(const BandScanDesc* d, int n, uint32_t frames, uint32_t a, bool guarded, hipStream_t s) {
-    // (a chain launch that gives its own verdict: nz_scale = gain^2 / frames)
-    if (guarded)
-        for (int i = 0; i < n; ++i)
-            if (d[i].nz_scale > 0.0f) {
-                g_delay_path_gain = std::sqrt((double)d[i].nz_scale * (double)frames);
-                if (g_delay_force_redo && d[i].nz_host) d[i].nz_host[0] = 1u;
-            }
-    real_band_chain(d, n, frames, a, guarded, s);
-}
 }  // namespace tdk
+
+// ---- what tests/asan_fx.cpp needs to know about the kind: 16 and (chunked, odd modes) 8 steps per tile
+const FxHooks g_fx = {
+    "delay",
+    [](td_state* s, int mode, int chunked) {
+        if (chunked && (mode & 1)) td_state_set_option(s, "debug.delay_tile", 8);
+    },
+    []() {
+        if (g_fx_launches[1] == g_fx_launches[0] && g_fx_launches[2] >= g_fx_launches[0]) return true;
+        fprintf(stderr, "launch counts: local %zu carry %zu apply %zu\n", g_fx_launches[0], g_fx_launches[1], g_fx_launches[2]);
+        return false;
+    },
+    []() {
+        printf("k_delay_apply launches %zu (%zu vertices, %zu single-launch, %zu entered fresh, %zu entered with the line; %zu k_delay_local launches; "
+               "%zu restarts checked)\n",
+               g_fx_launches[2], g_fx_vertices, g_fx_single, g_fx_fresh, g_fx_carried, g_fx_launches[0], g_fx_restarts);
+    },
+};

@@ -5,8 +5,8 @@
 // words the vertex' descriptor named at k_eq_local, the entry state (the vertex' own slot, or none after a set_time), that every
 // matrix power is within 2 ulp of a long-double recomputation done here, and that the three launches of a vertex come in order
 // (local, carry, apply).
-// It also listens to the guard: the audit launches of mock_hip.cpp are wrapped at link time (-Wl,--wrap), and the static gain
-// the engine carried from a guarded launch to the graph's output is kept for the driver to print.
+// (The guard's listeners, which keep the static gain the engine carried from a guarded launch to the graph's output for the driver
+// to print, are tests/mock_guard.cpp's.)
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -16,28 +16,10 @@
 #include <cmath>
 #include <map>
 
-#include "kernels.h"
-
-static volatile unsigned char g_eq_sink;
-static void touch(const void* p, size_t bytes) {
-    if (!p || !bytes) return;
-    const volatile unsigned char* b = (const volatile unsigned char*)p;
-    g_eq_sink ^= b[0];
-    g_eq_sink ^= b[bytes - 1];
-}
-static void touch_w(void* p, size_t bytes) {
-    if (!p || !bytes) return;
-    volatile unsigned char* b = (volatile unsigned char*)p;
-    b[0] = b[0];
-    b[bytes - 1] = b[bytes - 1];
-}
-[[noreturn]] static void die(const char* what) {
-    fprintf(stderr, "mock_eq: %s\n", what);
-    abort();
-}
+#define MOCK_NAME "mock_eq"
+#include "mock_util.h"
 
 size_t g_eq_launches[3] = {0, 0, 0}, g_eq_vertices = 0, g_eq_fresh = 0, g_eq_carried = 0;
-double g_eq_path_gain = 0.0;   // the last guarded launch's static gain to the output (0: none since the driver cleared it)
 
 namespace {
 struct Track { int phase; const double* carry; const tdk::EqState* state; const tdk::EqState* init; uint32_t n_tiles; };
@@ -71,16 +53,6 @@ void near(const double (&got)[4], const M2& want, const char* what) {
 }  // namespace
 
 namespace tdk {
-static void touch_eq_terms(const InTerm* ins, uint32_t k, uint32_t frames) {
-    touch(ins, (size_t)k * sizeof(InTerm));
-    for (uint32_t i = 0; i < k; ++i) {
-        const InTerm& t = ins[i];
-        if (t.kind == 0u || t.kind == 4u) touch(t.p, (size_t)frames * sizeof(float2));
-        else if (t.kind == 3u) touch(t.p, ((size_t)t.len + 15) * 4);
-        else if (t.kind == 1u || t.kind == 2u) touch(t.p, ((size_t)t.len + 15) * sizeof(float2));
-        else die("an eq vertex takes terms of kinds 0 .. 4 only");
-    }
-}
 static void check(const EqDesc* d, int n, uint32_t max_tiles, int which) {
     touch(d, (size_t)std::max(n, 0) * sizeof(EqDesc));
     g_eq_launches[which] += 1;
@@ -95,7 +67,7 @@ static void check(const EqDesc* d, int n, uint32_t max_tiles, int which) {
         if (!(std::fabs(s.a2) < 1.0 && std::fabs(s.a1) < 1.0 + s.a2)) die("an unstable filter");
         if (s.c0 != s.b1 - s.a1 * s.b0 || s.c1 != s.b2 - s.a2 * s.b0) die("c");
         if ((((uintptr_t)s.x) | ((uintptr_t)s.out) | ((uintptr_t)s.agg) | ((uintptr_t)s.carry) | ((uintptr_t)s.state)) & 15u) die("alignment");
-        touch_eq_terms(s.ins, s.k, s.frames);
+        touch_terms(s.ins, s.k, s.frames, "an eq vertex takes terms of kinds 0 .. 4 only");
         touch_w(s.x, (size_t)s.frames * sizeof(float2));
         touch_w(s.out, (size_t)s.frames * sizeof(float2));
         touch_w(s.state, sizeof(EqState));
@@ -130,24 +102,4 @@ static void check(const EqDesc* d, int n, uint32_t max_tiles, int which) {
 void launch_eq_local(const EqDesc* d, int n, uint32_t max_tiles, hipStream_t) { check(d, n, max_tiles, 0); }
 void launch_eq_carry(const EqDesc* d, int n, hipStream_t) { check(d, n, 0u, 1); }
 void launch_eq_apply(const EqDesc* d, int n, uint32_t max_tiles, hipStream_t) { check(d, n, max_tiles, 2); }
-
-// ---- the guard's launches, wrapped (ld --wrap: the engine's calls arrive here, __real_ is mock_hip.cpp's) ----
-void real_band_audit(const AuditHead* h, int n, hipStream_t s) asm("__real__ZN3tdk17launch_band_auditEPKNS_9AuditHeadEiP12ihipStream_t");
-void wrap_band_audit(const AuditHead* h, int n, hipStream_t s) asm("__wrap__ZN3tdk17launch_band_auditEPKNS_9AuditHeadEiP12ihipStream_t");
-void wrap_band_audit(const AuditHead* h, int n, hipStream_t s) {
-    for (int i = 0; i < n; ++i)
-        for (uint32_t j = 0; j < h[i].n; ++j) g_eq_path_gain = (double)h[i].descs[j].gain;
-    real_band_audit(h, n, s);
-}
-void real_band_chain(const BandScanDesc* d, int n, uint32_t frames, uint32_t a, bool guarded, hipStream_t s)
-    asm("__real__ZN3tdk17launch_band_chainEPKNS_12BandScanDescEijjbP12ihipStream_t");
-void wrap_band_chain(const BandScanDesc* d, int n, uint32_t frames, uint32_t a, bool guarded, hipStream_t s)
-    asm("__wrap__ZN3tdk17launch_band_chainEPKNS_12BandScanDescEijjbP12ihipStream_t");
-void wrap_band_chain(const BandScanDesc* d, int n, uint32_t frames, uint32_t a, bool guarded, hipStream_t s) {
-    // (a chain launch that gives its own verdict: nz_scale = gain^2 / frames)
-    if (guarded)
-        for (int i = 0; i < n; ++i)
-            if (d[i].nz_scale > 0.0f) g_eq_path_gain = std::sqrt((double)d[i].nz_scale * (double)frames);
-    real_band_chain(d, n, frames, a, guarded, s);
-}
 }  // namespace tdk

@@ -6,9 +6,8 @@
 // least 64 frames each, back to back behind the 16 one-pole words, every slot index below its line's length), the books (`pos`,
 // `skip` and `fresh` of all 24 lines the ones of ONE count of frames run since the restart, and that count the one the launch
 // before left; nothing after a set_time), chunks shorter than the window, and that k_reverb_sum has filled the buffer k_reverb reads.
-// It also listens to the guard: the audit launches of mock_hip.cpp are wrapped at link time (-Wl,--wrap); the static gain the
-// engine carried from a guarded launch to the graph's output is kept for the driver to print, and with g_rev_force_redo set
-// every audited render is told to run again.  For that case k_reverb stamps the state block's first word and logs the stamp it
+// With g_fx_force_redo set the guard's listeners (tests/mock_guard.cpp) tell every audited render to run again.  For that case
+// k_reverb stamps the state block's first word and logs the stamp it
 // finds there on entry: a render done again must find what the first one found, not what the first one left.
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
@@ -20,34 +19,17 @@
 #include <map>
 #include <vector>
 
-#include "kernels.h"
+#define MOCK_NAME "mock_reverb"
+#include "mock_util.h"
+#include "asan_fx.h"
+#include "termdaw_amd.h"
 
-static volatile unsigned char g_rev_sink;
-static void touch(const void* p, size_t bytes) {
-    if (!p || !bytes) return;
-    const volatile unsigned char* b = (const volatile unsigned char*)p;
-    g_rev_sink ^= b[0];
-    g_rev_sink ^= b[bytes - 1];
-}
-static void touch_w(void* p, size_t bytes) {
-    if (!p || !bytes) return;
-    volatile unsigned char* b = (volatile unsigned char*)p;
-    b[0] = b[0];
-    b[bytes - 1] = b[bytes - 1];
-}
-[[noreturn]] static void die(const char* what) {
-    fprintf(stderr, "mock_reverb: %s\n", what);
-    abort();
-}
-
-size_t g_rev_launches[2] = {0, 0}, g_rev_vertices = 0, g_rev_serial = 0, g_rev_fresh = 0, g_rev_carried = 0;
-double g_rev_path_gain = 0.0;   // the last guarded launch's static gain to the output (0: none since the driver cleared it)
-int g_rev_force_redo = 0;       // every audited render is to be done again
-int g_rev_after_set_time = 0;   // the driver has called td_graph_set_time and not submitted since: every vertex must enter with nothing of its state
-size_t g_rev_restarts = 0;      // descriptors checked under that flag
-size_t g_rev_short = 0;         // descriptors whose chunk was shorter than the window
-std::vector<double> g_rev_entry_log;   // per k_reverb descriptor that enters with its state: the stamp found in the block's first word
-static double g_rev_stamp = 0.0;
+size_t g_fx_launches[3] = {0, 0, 0}, g_fx_vertices = 0, g_fx_single = 0 /* the serial form */, g_fx_fresh = 0, g_fx_carried = 0;
+int g_fx_after_set_time = 0;   // the driver has called td_graph_set_time and not submitted since: every vertex must enter with nothing of its state
+size_t g_fx_restarts = 0;      // descriptors checked under that flag
+size_t g_fx_short = 0;         // descriptors whose chunk was shorter than the window
+std::vector<double> g_fx_entry_log;   // per k_reverb descriptor that enters with its state: the stamp found in the block's first word
+static double g_fx_stamp = 0.0;
 
 namespace {
 // per state block: the counts of frames run since the restart it has stood at, oldest first.  A launch must enter with one of them:
@@ -58,16 +40,6 @@ std::map<const float2*, uint32_t> g_summed;   // x buffers k_reverb_sum has fill
 }  // namespace
 
 namespace tdk {
-static void touch_reverb_terms(const InTerm* ins, uint32_t k, uint32_t frames) {
-    touch(ins, (size_t)k * sizeof(InTerm));
-    for (uint32_t i = 0; i < k; ++i) {
-        const InTerm& t = ins[i];
-        if (t.kind == 0u || t.kind == 4u) touch(t.p, (size_t)frames * sizeof(float2));
-        else if (t.kind == 3u) touch(t.p, ((size_t)t.len + 15) * 4);
-        else if (t.kind == 1u || t.kind == 2u) touch(t.p, ((size_t)t.len + 15) * sizeof(float2));
-        else die("a reverb vertex takes terms of kinds 0 .. 4 only");
-    }
-}
 static bool books_match(const ReverbDesc& s, uint64_t total) {
     for (int i = 0; i < 24; ++i) {
         if (s.pos[i] != (uint32_t)(total % s.len[i])) return false;
@@ -78,7 +50,7 @@ static bool books_match(const ReverbDesc& s, uint64_t total) {
 // which: 0 k_reverb_sum, 1 k_reverb
 static void check(const ReverbDesc* d, int n, int which, uint32_t frames, uint32_t form) {
     touch(d, (size_t)std::max(n, 0) * sizeof(ReverbDesc));
-    g_rev_launches[which] += 1;
+    g_fx_launches[which] += 1;
     if (n <= 0) die("an empty launch");
     if (which == 1 && form > 1u) die("form");
     for (int i = 0; i < n; ++i) {
@@ -104,7 +76,7 @@ static void check(const ReverbDesc* d, int n, int which, uint32_t frames, uint32
         if (std::fabs(s.pw[0] - std::pow(s.d1, (double)(s.B / 64u))) > 1e-15) die("pw[0]");
         for (int k = 1; k < 6; ++k)
             if (std::fabs(s.pw[k] - s.pw[k - 1] * s.pw[k - 1]) > 1e-14 * s.pw[k] + 1e-300) die("pw[k] is not the square of pw[k - 1]");
-        touch_reverb_terms(s.ins, s.k, s.frames);
+        touch_terms(s.ins, s.k, s.frames, "a reverb vertex takes terms of kinds 0 .. 4 only");
         touch_w(s.out, (size_t)s.frames * sizeof(float2));
         touch_w(s.x, (size_t)s.frames * sizeof(float2));
         touch_w(s.state, (size_t)at * sizeof(double));
@@ -119,13 +91,13 @@ static void check(const ReverbDesc* d, int n, int which, uint32_t frames, uint32
             if (it == g_summed.end() || it->second != s.frames) die("k_reverb reads a buffer k_reverb_sum has not filled");
             g_summed.erase(it);
         }
-        g_rev_vertices += 1;
-        if (form == 0u) g_rev_serial += 1;
-        if (s.frames < s.B) g_rev_short += 1;
-        (s.fresh ? g_rev_fresh : g_rev_carried) += 1;
-        if (g_rev_after_set_time) {
+        g_fx_vertices += 1;
+        if (form == 0u) g_fx_single += 1;
+        if (s.frames < s.B) g_fx_short += 1;
+        (s.fresh ? g_fx_fresh : g_fx_carried) += 1;
+        if (g_fx_after_set_time) {
             if (!s.fresh) die("a vertex entered with its state after a set_time");
-            g_rev_restarts += 1;
+            g_fx_restarts += 1;
         }
         std::vector<uint64_t>& hist = g_books[s.state];
         uint64_t total = 0;
@@ -133,41 +105,36 @@ static void check(const ReverbDesc* d, int n, int which, uint32_t frames, uint32
             while (!hist.empty() && !(hist.back() > 0 && books_match(s, hist.back()))) hist.pop_back();
             if (hist.empty()) die("pos / skip: the vertex enters with no count of frames its state block has stood at since it restarted");
             total = hist.back();
-            g_rev_entry_log.push_back(s.state[0]);
+            g_fx_entry_log.push_back(s.state[0]);
         } else {
             if (!books_match(s, 0)) die("a fresh vertex whose books are not those of frame 0");
             hist.clear();
         }
         hist.push_back(total + s.frames);
-        g_rev_stamp += 1.0;
-        s.state[0] = g_rev_stamp;
+        g_fx_stamp += 1.0;
+        s.state[0] = g_fx_stamp;
     }
 }
 void launch_reverb_sum(const ReverbDesc* d, int n, uint32_t frames, hipStream_t) { check(d, n, 0, frames, 0); }
 void launch_reverb(const ReverbDesc* d, int n, uint32_t form, hipStream_t) { check(d, n, 1, 0, form); }
-
-// ---- the guard's launches, wrapped (ld --wrap: the engine's calls arrive here, __real_ is mock_hip.cpp's) ----
-void real_band_audit(const AuditHead* h, int n, hipStream_t s) asm("__real__ZN3tdk17launch_band_auditEPKNS_9AuditHeadEiP12ihipStream_t");
-void wrap_band_audit(const AuditHead* h, int n, hipStream_t s) asm("__wrap__ZN3tdk17launch_band_auditEPKNS_9AuditHeadEiP12ihipStream_t");
-void wrap_band_audit(const AuditHead* h, int n, hipStream_t s) {
-    for (int i = 0; i < n; ++i) {
-        for (uint32_t j = 0; j < h[i].n; ++j) g_rev_path_gain = (double)h[i].descs[j].gain;
-        if (g_rev_force_redo) h[i].host_word[0] = 1u;
-    }
-    real_band_audit(h, n, s);
-}
-void real_band_chain(const BandScanDesc* d, int n, uint32_t frames, uint32_t a, bool guarded, hipStream_t s)
-    asm("__real__ZN3tdk17launch_band_chainEPKNS_12BandScanDescEijjbP12ihipStream_t");
-void wrap_band_chain(const BandScanDesc* d, int n, uint32_t frames, uint32_t a, bool guarded, hipStream_t s)
-    asm("__wrap__ZN3tdk17launch_band_chainEPKNS_12BandScanDescEijjbP12ihipStream_t");
-void wrap_band_chain(const BandScanDesc* d, int n, uint32_t frames, uint32_t a, bool guarded, hipStream_t s) {
-    // (a chain launch that gives its own verdict: nz_scale = gain^2 / frames)
-    if (guarded)
-        for (int i = 0; i < n; ++i)
-            if (d[i].nz_scale > 0.0f) {
-                g_rev_path_gain = std::sqrt((double)d[i].nz_scale * (double)frames);
-                if (g_rev_force_redo && d[i].nz_host) d[i].nz_host[0] = 1u;
-            }
-    real_band_chain(d, n, frames, a, guarded, s);
-}
 }  // namespace tdk
+
+// ---- what tests/asan_fx.cpp needs to know about the kind: the window length capped at 64 (chunked, odd modes), the serial form in
+// the modes with bit 1
+const FxHooks g_fx = {
+    "reverb",
+    [](td_state* s, int mode, int chunked) {
+        if (chunked && (mode & 1)) td_state_set_option(s, "debug.reverb_block", 64);
+        if (mode & 2) td_state_set_option(s, "debug.reverb_form", 0);
+    },
+    []() {
+        if (g_fx_launches[1] == g_fx_launches[0]) return true;   // (every k_reverb_sum is followed by a k_reverb)
+        fprintf(stderr, "launch counts: k_reverb_sum %zu k_reverb %zu\n", g_fx_launches[0], g_fx_launches[1]);
+        return false;
+    },
+    []() {
+        printf("k_reverb launches %zu (%zu vertices, %zu serial-form, %zu entered fresh, %zu entered with the state; %zu k_reverb_sum launches; "
+               "%zu restarts checked; %zu short chunks)\n",
+               g_fx_launches[1], g_fx_vertices, g_fx_single, g_fx_fresh, g_fx_carried, g_fx_launches[0], g_fx_restarts, g_fx_short);
+    },
+};

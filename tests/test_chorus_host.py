@@ -2,7 +2,7 @@
 polynomial against sin, the float64 twin (tests/np_chorus.py) split anywhere, as a static fractional delay against the analytic
 delayed tone, and its L2 gain against the guard's bound Hch; ranges, the Lua line and its dump; the host engine on random
 projects with chorus vertices under AddressSanitizer / UBSan against launches that check every descriptor
-(tests/mock_chorus.cpp, tests/asan_chorus.cpp); the guard's path gain and its backup of the line; and the launch lists of
+(tests/mock_chorus.cpp, tests/asan_fx.cpp); the guard's path gain and its backup of the line; and the launch lists of
 projects without the vertex."""
 import math
 import multiprocessing
@@ -263,12 +263,12 @@ def _build(out_dir):
     flags = ["-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-ffp-contract=off",
              "-D__HIP_PLATFORM_AMD__", "-I", "/opt/rocm/include", "-I", CSRC, "-I", os.path.join(ROOT, "include")]
     jobs = [(os.path.join(CSRC, f), os.path.join(out_dir, f + ".o")) for f in L.SOURCES]
-    jobs += [(os.path.join(ROOT, "tests", f), os.path.join(out_dir, f + ".o")) for f in ("mock_hip.cpp", "mock_chorus.cpp", "asan_chorus.cpp")]
+    jobs += [(os.path.join(ROOT, "tests", f), os.path.join(out_dir, f + ".o")) for f in ("mock_hip.cpp", "mock_guard.cpp", "mock_chorus.cpp", "asan_fx.cpp")]
     procs = [subprocess.Popen(["g++"] + flags + ["-c", src, "-o", obj]) for src, obj in jobs]
     for p in procs:
         assert p.wait() == 0
     exe = os.path.join(out_dir, "asan_chorus")
-    # (mock_chorus.cpp listens to the guard's launches of mock_hip.cpp: ld --wrap)
+    # (mock_guard.cpp listens to the guard's launches of mock_hip.cpp: ld --wrap)
     subprocess.check_call(["g++", "-fsanitize=address,undefined", "-o", exe] + WRAPS + [o for _, o in jobs] + ["-lpthread", "-ldl"])
     return exe
 

@@ -313,12 +313,12 @@ def _build(out_dir):
     flags = ["-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-ffp-contract=off",
              "-D__HIP_PLATFORM_AMD__", "-I", "/opt/rocm/include", "-I", CSRC, "-I", os.path.join(ROOT, "include")]
     jobs = [(os.path.join(CSRC, f), os.path.join(out_dir, f + ".o")) for f in L.SOURCES]
-    jobs += [(os.path.join(ROOT, "tests", f), os.path.join(out_dir, f + ".o")) for f in ("mock_hip.cpp", "mock_eq.cpp", "asan_eq.cpp")]
+    jobs += [(os.path.join(ROOT, "tests", f), os.path.join(out_dir, f + ".o")) for f in ("mock_hip.cpp", "mock_guard.cpp", "mock_eq.cpp", "asan_eq.cpp")]
     procs = [subprocess.Popen(["g++"] + flags + ["-c", src, "-o", obj]) for src, obj in jobs]
     for p in procs:
         assert p.wait() == 0
     exe = os.path.join(out_dir, "asan_eq")
-    # (mock_eq.cpp listens to the guard's launches of mock_hip.cpp: ld --wrap)
+    # (mock_guard.cpp listens to the guard's launches of mock_hip.cpp: ld --wrap)
     wraps = ["-Wl,--wrap=_ZN3tdk17launch_band_auditEPKNS_9AuditHeadEiP12ihipStream_t",
              "-Wl,--wrap=_ZN3tdk17launch_band_chainEPKNS_12BandScanDescEijjbP12ihipStream_t"]
     subprocess.check_call(["g++", "-fsanitize=address,undefined", "-o", exe] + wraps + [o for _, o in jobs] + ["-lpthread", "-ldl"])

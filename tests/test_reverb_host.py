@@ -2,7 +2,7 @@
 (tests/np_reverb.py) split anywhere, its impulse response (the 8 comb delays, an undamped decay of g per pass) and its L2 gain
 against the guard's bound Hrev; the constant of the GPU test's bound from the numpy emulation of the windowed scan; ranges, the Lua
 line and its dump; the host engine on random projects with reverb vertices under AddressSanitizer / UBSan against launches that
-check every descriptor (tests/mock_reverb.cpp, tests/asan_reverb.cpp); the guard's path gain and its backup of the state block; and
+check every descriptor (tests/mock_reverb.cpp, tests/asan_fx.cpp); the guard's path gain and its backup of the state block; and
 the launch lists of projects without the vertex."""
 import math
 import multiprocessing
@@ -315,12 +315,12 @@ def _build(out_dir):
     flags = ["-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-ffp-contract=off",
              "-D__HIP_PLATFORM_AMD__", "-I", "/opt/rocm/include", "-I", CSRC, "-I", os.path.join(ROOT, "include")]
     jobs = [(os.path.join(CSRC, f), os.path.join(out_dir, f + ".o")) for f in L.SOURCES]
-    jobs += [(os.path.join(ROOT, "tests", f), os.path.join(out_dir, f + ".o")) for f in ("mock_hip.cpp", "mock_reverb.cpp", "asan_reverb.cpp")]
+    jobs += [(os.path.join(ROOT, "tests", f), os.path.join(out_dir, f + ".o")) for f in ("mock_hip.cpp", "mock_guard.cpp", "mock_reverb.cpp", "asan_fx.cpp")]
     procs = [subprocess.Popen(["g++"] + flags + ["-c", src, "-o", obj]) for src, obj in jobs]
     for p in procs:
         assert p.wait() == 0
     exe = os.path.join(out_dir, "asan_reverb")
-    # (mock_reverb.cpp listens to the guard's launches of mock_hip.cpp: ld --wrap)
+    # (mock_guard.cpp listens to the guard's launches of mock_hip.cpp: ld --wrap)
     subprocess.check_call(["g++", "-fsanitize=address,undefined", "-o", exe] + WRAPS + [o for _, o in jobs] + ["-lpthread", "-ldl"])
     return exe
 

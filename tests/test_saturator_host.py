@@ -2,7 +2,7 @@
 frequency response, td_saturator_params against the formulas; the float64 twin (tests/np_saturator.py) split anywhere, on an
 impulse, and on the aliasing case the vertex exists for; ranges, the Lua line and its dump; the host engine on random projects
 with saturator vertices under AddressSanitizer / UBSan against launches that check every descriptor (tests/mock_sat.cpp,
-tests/asan_sat.cpp); the guard's path gain and its backup of the line; and the launch lists of projects without the vertex."""
+tests/asan_fx.cpp); the guard's path gain and its backup of the line; and the launch lists of projects without the vertex."""
 import math
 import multiprocessing
 import os
@@ -247,12 +247,12 @@ def _build(out_dir):
     flags = ["-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-ffp-contract=off",
              "-D__HIP_PLATFORM_AMD__", "-I", "/opt/rocm/include", "-I", CSRC, "-I", os.path.join(ROOT, "include")]
     jobs = [(os.path.join(CSRC, f), os.path.join(out_dir, f + ".o")) for f in L.SOURCES]
-    jobs += [(os.path.join(ROOT, "tests", f), os.path.join(out_dir, f + ".o")) for f in ("mock_hip.cpp", "mock_sat.cpp", "asan_sat.cpp")]
+    jobs += [(os.path.join(ROOT, "tests", f), os.path.join(out_dir, f + ".o")) for f in ("mock_hip.cpp", "mock_guard.cpp", "mock_sat.cpp", "asan_fx.cpp")]
     procs = [subprocess.Popen(["g++"] + flags + ["-c", src, "-o", obj]) for src, obj in jobs]
     for p in procs:
         assert p.wait() == 0
     exe = os.path.join(out_dir, "asan_sat")
-    # (mock_sat.cpp listens to the guard's launches of mock_hip.cpp: ld --wrap)
+    # (mock_guard.cpp listens to the guard's launches of mock_hip.cpp: ld --wrap)
     subprocess.check_call(["g++", "-fsanitize=address,undefined", "-o", exe] + WRAPS + [o for _, o in jobs] + ["-lpthread", "-ldl"])
     return exe
 
