@@ -342,6 +342,36 @@ int td_graph_add_reverb(td_graph* g, const char* name, float gain, float angle, 
  * frames per window of k_reverb at the default "debug.reverb_block"; out[7 .. 30] = the line lengths: left combs, right combs,
  * left all-passes, right all-passes.  The same range checks as td_graph_add_reverb. */
 int td_reverb_params(size_t sr, float room, float damp, float width, float size, double out[31]);
+/* A noise gate vertex -- THIS ENGINE'S OWN: no reference counterpart (the reference reaches dynamics through LV2 plugins,
+ * add_lv2fx, which this engine parses and drops).  Stereo-linked level detection with hysteresis, a hold counter and
+ * an attack / release fade of the gain between `range_db` and 0 dB.  The vertex sums its inputs like every input vertex
+ * (sum_inputs, extensions.rs:310-319), processes, mixes with `wet` by the reference's f32 lerp, then pan and gain like every
+ * vertex (extensions.rs:262-263).
+ *   Constants, f64, once on the host, each from the f32 parameter widened to f64 (td_gate_params returns them):
+ *     To = 10^(threshold_db / 20);  Tc = 10^((threshold_db - hysteresis_db) / 20);  H = llround(hold_ms sr / 1000) frames;
+ *     aA = exp(-1 / (attack_ms sr / 1000)), aA = 0 for attack_ms = 0;  aR the same from release_ms;  F = 10^(range_db / 20).
+ *   Steps 1-5 in f64 on the f32 summed input (l[n], r[n]), with no FMA contraction, in the order written:
+ *   1. level s[n] = max(|l[n]|, |r[n]|).  A frame with a NaN or infinite sample forces nothing in step 2 (it comes out as what
+ *      IEEE makes of it, at that frame only).
+ *   2. hysteresis, in the linear domain:  h[n] = 1 if s[n] >= To;  h[n] = 0 if s[n] < Tc;  h[n] = h[n-1] otherwise.
+ *   3. hold:  c[n] = 0 if h[n] == 1, else min(c[n-1] + 1, H + 1).  The target t[n] = 1 if c[n] <= H, else 0.
+ *   4. fade:  a[n] = aA if t[n] == 1, else aR;   env[n] = a[n] env[n-1] + (1 - a[n]) t[n].
+ *   5. G[n] = F + (1 - F) env[n];  p = (float)(l[n] G[n]), the same for r.
+ *   6. in f32, the reference's lerp (adsr.rs:42): out = l + wet * (p - l); then pan and gain.  wet < 0.0001: the summed input
+ *      passes through untouched (a plain k_sum launch) and the state stays as it is.
+ * State: (env, h, c), closed -- (0, 0, H + 1) -- at time 0; carried between consecutive block pulls and between the chunks of a
+ * render, restarted from closed by td_graph_set_time / td_graph_change_time / td_graph_reset.
+ * Ranges, rejected with a td_last_error that names the parameter (NaN included): threshold_db [-80, 0], hysteresis_db [0, 24],
+ * hold_ms [0, 2000], attack_ms [0, 1000], release_ms [1, 10000], range_db [-120, 0].  `wet` is clamped to [0, 1].
+ * Under "band_mode" 2 / "sine_mode" 2 everything upstream of a gate vertex takes the exact forms (no estimate is carried
+ * through a gain that depends on the signal); vertices downstream are unaffected.
+ * Not part of the vertex: an external key input (ducking), lookahead. */
+int td_graph_add_gate(td_graph* g, const char* name, float gain, float angle, float wet, float threshold_db, float hysteresis_db,
+                      float hold_ms, float attack_ms, float release_ms, float range_db);
+/* Host only, no GPU: the gate vertex' constants at rate sr, exactly the doubles the engine uses -- out[0 .. 5] = To, Tc, H, aA,
+ * aR, F.  The same range checks as td_graph_add_gate. */
+int td_gate_params(size_t sr, float threshold_db, float hysteresis_db, float hold_ms, float attack_ms, float release_ms,
+                   float range_db, double out[6]);
 int td_graph_connect(td_graph* g, const char* a, const char* b);          /* graph.rs:80-96 (+58-78) */
 int td_graph_set_output(td_graph* g, const char* vertex);                 /* graph.rs:141-148 */
 int td_graph_check(const td_graph* g);                                    /* check_graph graph.rs:150-174 */

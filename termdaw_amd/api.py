@@ -76,6 +76,8 @@ SIGNATURES = {
     "td_graph_add_chorus": (_i32, [_vp, _cp, _f32, _f32, _f32, _i32, _f32, _f32, _f32, _f32, _i32]),
     "td_chorus_params": (_i32, [_sz, _i32, _f32, _f32, _f32, _f32, _i32, C.POINTER(C.c_double)]),
     "td_graph_add_reverb": (_i32, [_vp, _cp, _f32, _f32, _f32, _f32, _f32, _f32, _f32]),
+    "td_graph_add_gate": (_i32, [_vp, _cp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32]),
+    "td_gate_params": (_i32, [_sz, _f32, _f32, _f32, _f32, _f32, _f32, C.POINTER(C.c_double)]),
     "td_reverb_params": (_i32, [_sz, _f32, _f32, _f32, _f32, C.POINTER(C.c_double)]),
     "td_graph_connect": (_i32, [_vp, _cp, _cp]),
     "td_graph_set_output": (_i32, [_vp, _cp]),
@@ -338,6 +340,13 @@ def chorus_shape(shape):
     return int(shape)
 
 
+def gate_params(sr, threshold_db, hysteresis_db, hold_ms, attack_ms, release_ms, range_db):
+    """(To, Tc, H, aA, aR, F): the gate vertex' constants at rate sr, exactly the doubles the engine uses (host only; H an int)."""
+    out = (C.c_double * 6)()
+    _check(lib().td_gate_params(int(sr), threshold_db, hysteresis_db, hold_ms, attack_ms, release_ms, range_db, out))
+    return (out[0], out[1], int(out[2]), out[3], out[4], out[5])
+
+
 def chorus_params(sr, voices, delay_ms, depth_ms, rate_hz, stereo, shape):
     """The chorus vertex' constants at rate sr (host only), exactly as the engine uses them: (D0, A, f, H, s, Hch) -- the centre
     delay and the depth in frames, the LFO's cycles per frame, the frames of the line, the largest delay slope, and the gain the
@@ -568,6 +577,12 @@ class Graph:
         """A reverb vertex: 8 damped feedback combs and 4 all-pass sections per channel (this engine's own; the definition is in
         include/termdaw_amd.h).  room, damp, width: [0, 1]; size: [0.5, 2], a factor on every line's length."""
         _check(lib().td_graph_add_reverb(self.h, name.encode(), gain, angle, wet, room, damp, width, size))
+
+    def add_gate(self, name, gain, angle, wet, threshold_db, hysteresis_db, hold_ms, attack_ms, release_ms, range_db):
+        """A noise gate vertex: hysteresis, hold and an attack / release fade (this engine's own; the definition is in
+        include/termdaw_amd.h)."""
+        _check(lib().td_graph_add_gate(self.h, name.encode(), gain, angle, wet, threshold_db, hysteresis_db, hold_ms, attack_ms, release_ms,
+                                       range_db))
 
     def connect(self, a, b):
         return bool(lib().td_graph_connect(self.h, a.encode(), b.encode()))

@@ -5,6 +5,7 @@
 // writes goes into the plain-memory staging arena of the ChunkBuild (offsets + fix-up lists that submit_chunk patches once
 // the device addresses are known).  tests/test_compile_asan.py builds it with g++ -fsanitize=address,undefined.
 #include "chorus_math.h"
+#include "gate_math.h"
 #include "compile.h"
 #include "delay_math.h"
 #include "eq_math.h"
@@ -32,7 +33,8 @@ const char* const kFamilyName[F_COUNT] = {"k_sample_loop", "k_sample_multi", "k_
                                            "k_delay_local", "k_delay_carry", "k_delay_apply",
                                            "k_sat_sum", "k_sat", "k_sat1",
                                            "k_chorus_sum", "k_chorus",
-                                           "k_reverb_sum", "k_reverb"};
+                                           "k_reverb_sum", "k_reverb",
+                                           "k_gate_detect", "k_gate_carry_hc", "k_gate_env", "k_gate_carry_env", "k_gate_apply"};
 
 
 // ------------------------------------------------------------------------------------------------
@@ -932,6 +934,8 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                 // a compressor is no static gain: no estimate is carried through it -- everything upstream takes the exact forms,
                 // as upstream of a stem
                 if (wv.kind == K_COMPRESSOR) { nz = -2; break; }
+                // ... and so is a gate, unless it is dry: then it is the Sum it compiles to
+                if (wv.kind == K_GATE && !(wv.wet < 0.0001f)) { nz = -2; break; }
                 double L = own_gain(wv);
                 // an EQ is linear and time-invariant: the estimate goes through it at the L2 gain of its lerp, (1 - wet) + wet Hmax
                 // 
@@ -1492,6 +1496,14 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                     } else {
                         if (M > 0xFFFF0000ull) return fail("compressor: chunk too long");
                         fam_v[F_COMP_DETECT].push_back(vi);
+                    }
+                    break;
+                case K_GATE:
+                    if (v.wet < 0.0001f) {
+                        fam_v[F_SUM].push_back(vi);   // the summed input passes through, the state stays
+                    } else {
+                        if (M > 0xFFFF0000ull) return fail("gate: chunk too long");
+                        fam_v[F_GATE_DETECT].push_back(vi);
                     }
                     break;
                 case K_EQ:
@@ -2354,6 +2366,59 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                     add_launch(F_COMP_APPLY, off, (int)vs.size(), n_tiles, lv);
                     continue;
                 }
+                case F_GATE_DETECT: {   // the five launches of the level's gate vertices (kernels.h GateDesc)
+                    const uint32_t n_tiles = (uint32_t)((M + kGateTile - 1) / kGateTile), chunk = (n_tiles + kThreads - 1) / kThreads;
+                    std::vector<GateDesc> d;
+                    for (size_t vi : vs) {
+                        Vertex& v = g->vertices[vi];
+                        GateDesc x{};
+                        x.x = take_buffer(g);
+                        if (!x.x) return fail("termdaw_amd: out of device memory for edge buffers");
+                        level_tmp.push_back(x.x);
+                        x.out = g->vbuf[vi];
+                        x.state = &g->dstate[v.state_slot].gate;
+                        // (a set_time since the vertex last ran: the state restarts closed -- consumed here, like a compressor's)
+                        x.init = v.first_pending ? nullptr : x.state;
+                        v.first_pending = false;
+                        x.k = (uint32_t)g->edges[vi].size();
+                        x.term_mode = term_mode[vi];
+                        x.frames = (uint32_t)M;
+                        x.n_tiles = n_tiles;
+                        x.chunk = chunk;
+                        x.wet = v.wet;
+                        double c[6];
+                        gate::params(sr, v.gate_threshold_db, v.gate_hysteresis_db, v.gate_hold_ms, v.gate_attack_ms, v.gate_release_ms, v.gate_range_db, c);
+                        if (!(c[2] <= gate::kMaxHold)) return fail("gate: hold_ms is too many frames at this sample rate");
+                        x.To = c[0];
+                        x.Tc = c[1];
+                        x.cap = (uint32_t)c[2] + 1u;
+                        x.aA = c[3];
+                        x.aR = c[4];
+                        x.oA = 1.0 - x.aA;
+                        x.oR = 1.0 - x.aR;
+                        x.F = c[5];
+                        x.oF = 1.0 - x.F;
+                        x.pg = make_pg(v.gain, v.angle);
+                        d.push_back(x);
+                    }
+                    off = st.put(d);
+                    for (size_t i = 0; i < vs.size(); ++i) {
+                        const size_t o = off + i * sizeof(GateDesc), tb = (size_t)n_tiles * sizeof(double);
+                        ptr_field(o, offsetof(GateDesc, ins), ins_off[vs[i]]);
+                        scratch_field(o, offsetof(GateDesc, map), scratch(tb));
+                        scratch_field(o, offsetof(GateDesc, carry_hc), scratch((size_t)n_tiles * sizeof(uint32_t)));
+                        scratch_field(o, offsetof(GateDesc, tbits), scratch((size_t)n_tiles * kThreads));
+                        scratch_field(o, offsetof(GateDesc, aggA), scratch(tb));
+                        scratch_field(o, offsetof(GateDesc, aggB), scratch(tb));
+                        scratch_field(o, offsetof(GateDesc, carry_env), scratch(tb));
+                    }
+                    add_launch(F_GATE_DETECT, off, (int)vs.size(), n_tiles, lv);
+                    add_launch(F_GATE_CARRY_H, off, (int)vs.size(), 0u, lv);
+                    add_launch(F_GATE_ENV, off, (int)vs.size(), n_tiles, lv);
+                    add_launch(F_GATE_CARRY_ENV, off, (int)vs.size(), 0u, lv);
+                    add_launch(F_GATE_APPLY, off, (int)vs.size(), n_tiles, lv);
+                    continue;
+                }
                 case F_EQ_LOCAL: {   // the three launches of the level's EQ vertices (kernels.h EqDesc)
                     const uint32_t n_tiles = (uint32_t)((M + kEqTile - 1) / kEqTile), chunk = (n_tiles + kThreads - 1) / kThreads;
                     std::vector<EqDesc> d;
@@ -2822,6 +2887,11 @@ size_t desc_size(int fam) {
         case F_CHORUS: return sizeof(ChorusDesc);
         case F_REVERB_SUM:
         case F_REVERB: return sizeof(ReverbDesc);
+        case F_GATE_DETECT:
+        case F_GATE_CARRY_H:
+        case F_GATE_ENV:
+        case F_GATE_CARRY_ENV:
+        case F_GATE_APPLY: return sizeof(GateDesc);
         default: return 0;
     }
 }

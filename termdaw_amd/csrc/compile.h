@@ -19,6 +19,7 @@ enum Family { F_LOOP, F_MULTI, F_LERP, F_SINE, F_SYNTH, F_SAMPSYN, F_ENV, F_PROB
               F_SAT_SUM, F_SAT, F_SAT1 /* a level's saturator vertices: k_sat_sum (over the vertices whose chunk takes more than one tile only), k_sat (one launch per oversampling factor), k_sat1 (R = 1) */,
               F_CHORUS_SUM, F_CHORUS /* a level's chorus vertices: k_chorus_sum (when the chunk is longer than the one-launch form takes), k_chorus */,
               F_REVERB_SUM, F_REVERB /* a level's reverb vertices: k_reverb_sum, k_reverb -- in this order */,
+              F_GATE_DETECT, F_GATE_CARRY_H, F_GATE_ENV, F_GATE_CARRY_ENV, F_GATE_APPLY /* a level's gate vertices: k_gate_detect, k_gate_carry (the (h, c) entering each tile), k_gate_env, k_gate_carry (the env entering each tile), k_gate_apply -- in this order */,
               F_COUNT };
 extern const char* const kFamilyName[F_COUNT];
 

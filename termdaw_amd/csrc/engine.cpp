@@ -10,6 +10,7 @@
 
 #include "engine.h"
 #include "chorus_math.h"
+#include "gate_math.h"
 #include "comm.h"
 #include "compile.h"
 #include "delay_math.h"
@@ -533,6 +534,12 @@ static int ensure_state_slots(td_graph* g) {
     return 1;
 }
 
+// A gate vertex' state at time 0: closed, the hold run out -- (env, h, c) = (0, 0, H + 1)
+static tdk::GateState gate_closed(const td_graph* g, const Vertex& v) {
+    double c[6];
+    gate::params(g->sr, v.gate_threshold_db, v.gate_hysteresis_db, v.gate_hold_ms, v.gate_attack_ms, v.gate_release_ms, v.gate_range_db, c);
+    return {0.0, 0u, (uint32_t)std::min(c[2] + 1.0, gate::kMaxHold + 1.0), {0, 0, 0, 0}};
+}
 static int drain(td_graph* g);   // stream drained + deferred k_norm_fix settled (defined with the render loop)
 static int pull_state(td_graph* g) {
     if (g->state_dev_dirty && g->dstate && !g->hstate.empty()) {
@@ -545,6 +552,8 @@ static int pull_state(td_graph* g) {
             if (v.kind == K_COMPRESSOR && v.state_slot >= 0 && v.first_pending) g->hstate[(size_t)v.state_slot].comp = {0.0, 0.0, {0, 0, 0, 0}};
         for (const auto& v : g->vertices)
             if (v.kind == K_EQ && v.state_slot >= 0 && v.first_pending) g->hstate[(size_t)v.state_slot].eq = {0.0, 0.0, 0.0, 0.0};
+        for (const auto& v : g->vertices)
+            if (v.kind == K_GATE && v.state_slot >= 0 && v.first_pending) g->hstate[(size_t)v.state_slot].gate = gate_closed(g, v);
     }
     return 1;
 }
@@ -940,6 +949,11 @@ static int submit_chunk(Arena& ar, ChunkBuild& cb, hipStream_t stream, ProfCtx& 
                 case F_CHORUS_SUM: launch_chorus_sum((const ChorusDesc*)d, L.n, L.M, s); break;   // (likewise)
                 case F_REVERB_SUM: launch_reverb_sum((const ReverbDesc*)d, L.n, L.M, s); break;   // (likewise)
                 case F_REVERB: launch_reverb((const ReverbDesc*)d, L.n, L.aux, s); break;
+                case F_GATE_DETECT: launch_gate_detect((const GateDesc*)d, L.n, L.aux, s); break;   // (likewise)
+                case F_GATE_CARRY_H: launch_gate_carry((const GateDesc*)d, L.n, false, s); break;
+                case F_GATE_ENV: launch_gate_env((const GateDesc*)d, L.n, L.aux, s); break;
+                case F_GATE_CARRY_ENV: launch_gate_carry((const GateDesc*)d, L.n, true, s); break;
+                case F_GATE_APPLY: launch_gate_apply((const GateDesc*)d, L.n, L.aux, s); break;
                 case F_CHORUS: launch_chorus((const ChorusDesc*)d, L.n, L.aux & 0xFFFFFu, L.M, (L.aux & kChorusTermsBit) != 0u, s); break;
             }
         }
@@ -1027,6 +1041,7 @@ static int prepare_render(td_graph* g, size_t n_blocks, int bits, bool want_pcm,
         {K_SATURATOR, launch_sat_sum && launch_sat && launch_sat1, "sat", "saturator"},
         {K_CHORUS, launch_chorus_sum && launch_chorus, "chorus", "chorus"},
         {K_REVERB, launch_reverb_sum && launch_reverb, "reverb", "reverb"},
+        {K_GATE, launch_gate_detect && launch_gate_carry && launch_gate_env && launch_gate_apply, "gate", "gate"},
     };
     for (const auto& f : fx)
         if (!f.built)
@@ -1135,7 +1150,7 @@ static bool starts_afresh(const td_graph* g) {
     for (size_t vi : g->order) {
         const Vertex& v = g->vertices[vi];
         if (v.kind == K_NORMALIZE && !v.has_init_override) return false;
-        if ((v.kind == K_BAND_PASS || v.kind == K_COMPRESSOR || v.kind == K_EQ) && v.state_slot >= 0 && !v.first_pending) return false;
+        if ((v.kind == K_BAND_PASS || v.kind == K_COMPRESSOR || v.kind == K_EQ || v.kind == K_GATE) && v.state_slot >= 0 && !v.first_pending) return false;
         if (v.line.d && !v.first_pending) return false;
     }
     return true;
@@ -1354,6 +1369,12 @@ static int graph_set_time_impl(td_graph* g, size_t time) {   // graph.rs:123-128
             case K_EQ:   // the filter restarts from the zero state: the next submission's carry enters with 0
                 if (v.state_slot >= 0) {
                     g->hstate[v.state_slot].eq = {0.0, 0.0, 0.0, 0.0};
+                    v.first_pending = true;
+                }
+                break;
+            case K_GATE:   // the gate restarts closed: the next submission's carries enter with (0, 0, H + 1)
+                if (v.state_slot >= 0) {
+                    g->hstate[v.state_slot].gate = gate_closed(g, v);
                     v.first_pending = true;
                 }
                 break;
@@ -1994,6 +2015,30 @@ int td_reverb_params(size_t sr, float room, float damp, float width, float size,
     if (!out) return fail("reverb_params: out is null");
     if (const char* why = reverb::check(sr, room, damp, width, size)) return fail(std::string("reverb: ") + why);
     reverb::params(sr, room, damp, width, size, out);
+    return 1;
+}
+
+// This engine's own noise gate vertex (no reference counterpart; the definition is in include/termdaw_amd.h).
+int td_graph_add_gate(td_graph* g, const char* name, float gain, float angle, float wet, float threshold_db, float hysteresis_db,
+                      float hold_ms, float attack_ms, float release_ms, float range_db) {
+    if (const char* why = gate::check(threshold_db, hysteresis_db, hold_ms, attack_ms, release_ms, range_db)) return fail(std::string("gate: ") + why);
+    const int slot = new_slot(g);
+    Vertex& v = add_vertex(g, name, gain, angle, wet, K_GATE);
+    v.gate_threshold_db = threshold_db;
+    v.gate_hysteresis_db = hysteresis_db;
+    v.gate_hold_ms = hold_ms;
+    v.gate_attack_ms = attack_ms;
+    v.gate_release_ms = release_ms;
+    v.gate_range_db = range_db;
+    v.state_slot = slot;
+    g->hstate[slot].gate = gate_closed(g, v);
+    return 1;
+}
+int td_gate_params(size_t sr, float threshold_db, float hysteresis_db, float hold_ms, float attack_ms, float release_ms, float range_db,
+                   double out[6]) {
+    if (!out) return fail("gate_params: out is null");
+    if (const char* why = gate::check(threshold_db, hysteresis_db, hold_ms, attack_ms, release_ms, range_db)) return fail(std::string("gate: ") + why);
+    gate::params(sr, threshold_db, hysteresis_db, hold_ms, attack_ms, release_ms, range_db, out);
     return 1;
 }
 

@@ -263,6 +263,45 @@ struct CompDesc {
     PanGain pg;
 };
 
+// A gate vertex (k_gate_detect / k_gate_carry / k_gate_env / k_gate_carry / k_gate_apply; the definition is in
+// include/termdaw_amd.h at td_graph_add_gate).  The compressor's tiling: tiles of kGateTile frames, a lane owns kGateRun consecutive
+// frames; ONE descriptor read by every launch.
+//   The discrete recurrence (h, c) is scanned over a monoid of state maps.  A map is a word per entering h (kGateH: the leaving
+//   h; kGateR: "c restarts"; the low 30 bits: k, the closed frames since the restart or on top of the entering c, capped at
+//   cap = H + 1).  A state (h, c) is the constant map {h, restart, c}: one word of the same layout.
+//   The fade env[n] = a[n] env[n-1] + (1 - a[n]) t[n] is scanned over pairs (A, B): env_out = A env_in + B.
+// k_gate_detect evaluates the input terms, leaves the summed input in `x` and each tile's map in map[t]; k_gate_carry (discrete)
+// leaves the state word entering each tile in carry_hc[t] (tile 0: *init, or closed when init is nullptr); k_gate_env rebuilds
+// t[n] from there, leaves a byte of eight t per lane in tbits, each tile's pair in aggA / aggB and (h, c) behind the chunk's
+// last frame in *state; k_gate_carry (affine) leaves the env entering each tile in carry_env[t]; k_gate_apply rebuilds env, G = F +
+// (1 - F) env and writes lerp(x, (float)(x G), wet), pan, gain to `out`, and env behind the chunk's last frame to *state.
+constexpr uint32_t kGateRun = 8;                     // frames per lane
+constexpr uint32_t kGateTile = kGateRun * kThreads;  // frames per workgroup
+constexpr uint32_t kGateH = 0x80000000u, kGateR = 0x40000000u, kGateK = 0x3FFFFFFFu;
+struct GateState { double env; uint32_t h, c; uint32_t pad[4]; };
+struct GateDesc {
+    const InTerm* ins;      // k input terms (kinds 0 .. 4), in connect() order
+    float2* x;              // [frames] the summed input
+    float2* out;
+    GateState* state;       // carried across chunks / block pulls
+    const GateState* init;  // the state entering tile 0 (k_gate_carry reads it): `state`, or nullptr after a set_time (closed)
+    uint32_t* map;          // [2 n_tiles] each tile's map, one packed word pair: word 0 for entering h = 0, word 1 for entering h = 1
+    uint32_t* carry_hc;     // [n_tiles] the state word entering each tile
+    uint8_t* tbits;         // [n_tiles kThreads] bit j: t of the lane's frame j
+    double* aggA;           // [n_tiles] each tile's pair
+    double* aggB;
+    double* carry_env;      // [n_tiles] the env entering each tile
+    uint32_t k, term_mode, frames, n_tiles;
+    uint32_t chunk;         // tiles per lane in k_gate_carry
+    uint32_t cap;           // H + 1
+    float wet;
+    uint32_t pad;
+    double To, Tc;          // open at s >= To, close at s < Tc (linear)
+    double aA, aR, oA, oR;  // attack / release coefficients, 1 - aA, 1 - aR
+    double F, oF;           // the closed gain, 1 - F
+    PanGain pg;
+};
+
 // A parametric EQ vertex (k_eq_local / k_eq_carry / k_eq_apply; the definition is in include/termdaw_amd.h at
 // td_graph_add_eq): one RBJ biquad per channel in transposed direct form II, f64.  With z = (s1, s2) the recurrence is
 // z[n] = A z[n-1] + c x[n],  A = [[-a1, 1], [-a2, 0]],  c = (b1 - a1 b0, b2 - a2 b0),  y[n] = b0 x[n] + s1[n-1]: an affine scan
@@ -901,6 +940,12 @@ constexpr uint32_t kChorusTermsBit = 0x80000000u;
 inline uint32_t chorus_aux(uint32_t n_tiles, bool terms) { return n_tiles | (terms ? kChorusTermsBit : 0u); }
 __attribute__((weak)) void launch_chorus_sum(const ChorusDesc* d, int n_desc, uint32_t frames, hipStream_t s);
 __attribute__((weak)) void launch_chorus(const ChorusDesc* d, int n_desc, uint32_t n_tiles, uint32_t frames, bool terms, hipStream_t s);
+// Weak for the same reason: a level's gate vertices, ONE grid per step (grid.x: the largest tile count); launch_gate_carry: one
+// workgroup per vertex, the discrete carry or (affine) the fade's.
+__attribute__((weak)) void launch_gate_detect(const GateDesc* d, int n_desc, uint32_t max_tiles, hipStream_t s);
+__attribute__((weak)) void launch_gate_carry(const GateDesc* d, int n_desc, bool affine, hipStream_t s);
+__attribute__((weak)) void launch_gate_env(const GateDesc* d, int n_desc, uint32_t max_tiles, hipStream_t s);
+__attribute__((weak)) void launch_gate_apply(const GateDesc* d, int n_desc, uint32_t max_tiles, hipStream_t s);
 // Weak for the same reason: a level's reverb vertices.  launch_reverb_sum: grid.x from `frames`; launch_reverb: one workgroup per
 // descriptor, `form` 0 the serial walk of each comb's one-pole, 1 the wave scan.
 __attribute__((weak)) void launch_reverb_sum(const ReverbDesc* d, int n_desc, uint32_t frames, hipStream_t s);

@@ -6083,6 +6083,243 @@ __global__ __launch_bounds__(kThreads) void k_sample_pack(const float* __restric
 // launch wrappers
 // ------------------------------------------------------------------------------------------------
 static inline uint32_t tiles(uint32_t frames) { return (frames + kTileFrames - 1) / kTileFrames; }
+// ------------------------------------------------------------------------------------------------
+// k_gate_detect / k_gate_carry / k_gate_env / k_gate_apply: the gate vertex (kernels.h GateDesc).  No reference
+// counterpart; the definition is the header's (td_graph_add_gate): hysteresis and hold as a scan over state maps (exact), the
+// fade as a scan over (A, B) pairs, f64.
+// ------------------------------------------------------------------------------------------------
+// step 2's class of one summed input frame: 0 forces nothing, 1 opens, 2 closes
+TD_DEV uint32_t gate_class(double To, double Tc, float l, float r) {
+    const float al = fabsf(l), ar = fabsf(r);
+    if (!(al <= 3.402823466e38f && ar <= 3.402823466e38f)) return 0u;   // a NaN / infinite frame forces nothing
+    const double s = (double)fmaxf(al, ar);
+    return s >= To ? 1u : (s < Tc ? 2u : 0u);
+}
+// One frame behind a map word (or a state word): steps 2 and 3
+TD_DEV uint32_t gate_step(uint32_t w, uint32_t cls, uint32_t cap) {
+    const bool h = cls == 1u || (cls == 0u && (w & kGateH) != 0u);
+    if (h) return kGateH | kGateR;   // open: c restarts at 0
+    const uint32_t k = (w & kGateK) + 1u;
+    return (w & kGateR) | (k < cap ? k : cap);
+}
+// The word `l` (a map's word, or a state) followed by the map (r0, r1)
+TD_DEV uint32_t gate_join(uint32_t l, uint32_t r0, uint32_t r1, uint32_t cap) {
+    const uint32_t r = (l & kGateH) ? r1 : r0;
+    if (r & kGateR) return r;
+    const uint32_t k = (l & kGateK) + (r & kGateK);
+    return (r & kGateH) | (l & kGateR) | (k < cap ? k : cap);
+}
+// The lanes' maps joined in lane order (Hillis-Steele, two 32-bit planes): on return (m0, m1) is the lane's inclusive prefix,
+// (*e0, *e1) the exclusive one (lane 0: the identity), and lane kThreads - 1's inclusive prefix is the tile's map.
+TD_DEV void gate_map_scan(uint32_t& m0, uint32_t& m1, uint32_t cap, uint32_t* s0, uint32_t* s1, uint32_t* e0, uint32_t* e1) {
+    const uint32_t tid = threadIdx.x;
+#pragma unroll 1
+    for (uint32_t k = 0; k < 8; ++k) {
+        const uint32_t off = 1u << k;
+        s0[tid] = m0;
+        s1[tid] = m1;
+        __syncthreads();
+        if (tid >= off) {
+            const uint32_t l0 = s0[tid - off], l1 = s1[tid - off];
+            const uint32_t n0 = gate_join(l0, m0, m1, cap), n1 = gate_join(l1, m0, m1, cap);
+            m0 = n0;
+            m1 = n1;
+        }
+        __syncthreads();
+    }
+    s0[tid] = m0;
+    s1[tid] = m1;
+    __syncthreads();
+    *e0 = tid ? s0[tid - 1] : 0u;
+    *e1 = tid ? s1[tid - 1] : kGateH;
+    __syncthreads();
+}
+// The lanes' pairs joined in lane order (two planes of doubles): env behind (Al, Bl) then (A, B) is A (Al e + Bl) + B.  Returns
+// the B entering the lane's run -- the env there when lane 0's run started from the tile's entry -- with `in` for lane 0; on
+// return (A, B) is the lane's inclusive prefix.
+TD_DEV double gate_pair_scan(double& A, double& B, double in, double* sa, double* sb) {
+    const uint32_t tid = threadIdx.x;
+#pragma unroll 1
+    for (uint32_t k = 0; k < 8; ++k) {
+        const uint32_t off = 1u << k;
+        sa[tid] = A;
+        sb[tid] = B;
+        __syncthreads();
+        if (tid >= off) {
+            const double Al = sa[tid - off], Bl = sb[tid - off];
+            B = A * Bl + B;
+            A = Al * A;
+        }
+        __syncthreads();
+    }
+    sb[tid] = B;
+    __syncthreads();
+    const double e = tid ? sb[tid - 1] : in;
+    __syncthreads();
+    return e;
+}
+__global__ __launch_bounds__(kThreads) void k_gate_detect(const GateDesc* __restrict__ descs) {
+    const GateDesc& d = descs[blockIdx.y];
+    if (blockIdx.x >= d.n_tiles) return;
+    __shared__ uint32_t s0[kThreads], s1[kThreads];
+    const uint32_t M = d.frames, cap = d.cap, f0 = blockIdx.x * kGateTile + threadIdx.x * kGateRun;
+    const double To = d.To, Tc = d.Tc;
+    uint32_t m0 = 0u, m1 = kGateH;   // the identity: frames from M on leave it as it is
+#pragma unroll 1
+    for (uint32_t h = 0; h < kGateRun / 4; ++h) {
+        const uint32_t m = f0 + 4u * h;
+        float4 a0, a1;
+        sum_inputs_pairs(d.ins, d.k, d.term_mode, m, m + 2u, M, a0, a1);
+        store_pair(d.x, m, M, a0);
+        store_pair(d.x, m + 2u, M, a1);
+        const uint32_t c0 = gate_class(To, Tc, a0.x, a0.y), c1 = gate_class(To, Tc, a0.z, a0.w);
+        const uint32_t c2 = gate_class(To, Tc, a1.x, a1.y), c3 = gate_class(To, Tc, a1.z, a1.w);
+        if (m < M) { m0 = gate_step(m0, c0, cap); m1 = gate_step(m1, c0, cap); }
+        if (m + 1u < M) { m0 = gate_step(m0, c1, cap); m1 = gate_step(m1, c1, cap); }
+        if (m + 2u < M) { m0 = gate_step(m0, c2, cap); m1 = gate_step(m1, c2, cap); }
+        if (m + 3u < M) { m0 = gate_step(m0, c3, cap); m1 = gate_step(m1, c3, cap); }
+    }
+    uint32_t e0, e1;
+    gate_map_scan(m0, m1, cap, s0, s1, &e0, &e1);
+    if (threadIdx.x == kThreads - 1u) {
+        d.map[2u * blockIdx.x] = m0;
+        d.map[2u * blockIdx.x + 1u] = m1;
+    }
+}
+// The value entering every tile, from the carried state: a lane folds `chunk` consecutive tiles, the lanes are joined, and a
+// second walk writes the carries (k_master_carry's shape).  AFFINE: the fade's pairs, entry[t + 1] = A[t] entry[t] + B[t]; else
+// the discrete state word through the tiles' maps.
+template <bool AFFINE>
+__global__ __launch_bounds__(kThreads) void k_gate_carry(const GateDesc* __restrict__ descs) {
+    const GateDesc& d = descs[blockIdx.x];
+    __shared__ double sa[AFFINE ? kThreads : 1], sb[AFFINE ? kThreads : 1];
+    __shared__ uint32_t s0[AFFINE ? 1 : kThreads], s1[AFFINE ? 1 : kThreads];
+    const uint32_t tid = threadIdx.x, n = d.n_tiles, c = d.chunk, cap = d.cap;
+    const uint32_t b = tid * c < n ? tid * c : n, e = b + c < n ? b + c : n;
+    if (AFFINE) {
+        const double init = d.init ? d.init->env : 0.0;
+        double A = 1.0, B = tid ? 0.0 : init;
+        for (uint32_t r = b; r < e; ++r) {
+            const double At = d.aggA[r];
+            B = At * B + d.aggB[r];
+            A = A * At;
+        }
+        double u = gate_pair_scan(A, B, init, sa, sb);
+        for (uint32_t r = b; r < e; ++r) {
+            d.carry_env[r] = u;
+            u = d.aggA[r] * u + d.aggB[r];
+        }
+    } else {
+        const uint32_t hc = d.init ? d.init->c : cap;
+        const uint32_t init = d.init ? ((d.init->h ? kGateH : 0u) | kGateR | (hc < cap ? hc : cap)) : (kGateR | cap);
+        uint32_t m0 = 0u, m1 = kGateH, e0, e1;
+        for (uint32_t r = b; r < e; ++r) {
+            const uint32_t r0 = d.map[2u * r], r1 = d.map[2u * r + 1u];
+            const uint32_t n0 = gate_join(m0, r0, r1, cap), n1 = gate_join(m1, r0, r1, cap);
+            m0 = n0;
+            m1 = n1;
+        }
+        gate_map_scan(m0, m1, cap, s0, s1, &e0, &e1);
+        uint32_t w = gate_join(init, e0, e1, cap);
+        for (uint32_t r = b; r < e; ++r) {
+            d.carry_hc[r] = w;
+            w = gate_join(w, d.map[2u * r], d.map[2u * r + 1u], cap);
+        }
+    }
+}
+// the lane's eight frames of the summed input (0 from `frames` on)
+TD_DEV void gate_load_run(const GateDesc& d, uint32_t f0, float4 (&x)[kGateRun / 2]) {
+#pragma unroll
+    for (uint32_t j = 0; j < kGateRun / 2; ++j) x[j] = load_pair(d.x, f0 + 2u * j, d.frames);
+}
+__global__ __launch_bounds__(kThreads) void k_gate_env(const GateDesc* __restrict__ descs) {
+    const GateDesc& d = descs[blockIdx.y];
+    if (blockIdx.x >= d.n_tiles) return;
+    __shared__ uint32_t s0[kThreads], s1[kThreads];
+    __shared__ double sa[kThreads], sb[kThreads];
+    const uint32_t tid = threadIdx.x, M = d.frames, cap = d.cap, f0 = blockIdx.x * kGateTile + tid * kGateRun;
+    const double To = d.To, Tc = d.Tc, aA = d.aA, aR = d.aR, oA = d.oA, oR = d.oR;
+    float4 x[kGateRun / 2];
+    gate_load_run(d, f0, x);
+    uint32_t cls[kGateRun];
+#pragma unroll
+    for (uint32_t j = 0; j < kGateRun / 2; ++j) {
+        cls[2 * j] = gate_class(To, Tc, x[j].x, x[j].y);
+        cls[2 * j + 1] = gate_class(To, Tc, x[j].z, x[j].w);
+    }
+    uint32_t m0 = 0u, m1 = kGateH, e0, e1;
+#pragma unroll
+    for (uint32_t k = 0; k < kGateRun; ++k)
+        if (f0 + k < M) { m0 = gate_step(m0, cls[k], cap); m1 = gate_step(m1, cls[k], cap); }
+    gate_map_scan(m0, m1, cap, s0, s1, &e0, &e1);
+    uint32_t w = gate_join(d.carry_hc[blockIdx.x], e0, e1, cap);   // the state entering the lane's run
+    uint32_t tb = 0u;
+    double A = 1.0, B = 0.0;
+#pragma unroll
+    for (uint32_t k = 0; k < kGateRun; ++k) {
+        if (f0 + k < M) {
+            w = gate_step(w, cls[k], cap);
+            const bool t = (w & kGateK) < cap;   // c <= H
+            tb |= (t ? 1u : 0u) << k;
+            const double a = t ? aA : aR, o = t ? oA : oR, tt = t ? 1.0 : 0.0;
+            B = a * B + o * tt;
+            A = A * a;
+            if (f0 + k + 1u == M) {   // the chunk's last frame: what the next chunk / block pull enters with
+                d.state->h = (w & kGateH) ? 1u : 0u;
+                d.state->c = w & kGateK;
+            }
+        }
+    }
+    d.tbits[(size_t)blockIdx.x * kThreads + tid] = (uint8_t)tb;
+    (void)gate_pair_scan(A, B, 0.0, sa, sb);
+    if (tid == kThreads - 1u) {
+        d.aggA[blockIdx.x] = A;
+        d.aggB[blockIdx.x] = B;
+    }
+}
+__global__ __launch_bounds__(kThreads) void k_gate_apply(const GateDesc* __restrict__ descs) {
+    const GateDesc& d = descs[blockIdx.y];
+    if (blockIdx.x >= d.n_tiles) return;
+    __shared__ double sa[kThreads], sb[kThreads];
+    const uint32_t tid = threadIdx.x, M = d.frames, f0 = blockIdx.x * kGateTile + tid * kGateRun;
+    const double aA = d.aA, aR = d.aR, oA = d.oA, oR = d.oR, F = d.F, oF = d.oF, cin = d.carry_env[blockIdx.x];
+    const float wet = d.wet;
+    const uint32_t tb = d.tbits[(size_t)blockIdx.x * kThreads + tid];
+    float4 x[kGateRun / 2];
+    gate_load_run(d, f0, x);
+    double A = 1.0, B = tid ? 0.0 : cin;
+#pragma unroll
+    for (uint32_t k = 0; k < kGateRun; ++k) {
+        if (f0 + k < M) {
+            const bool t = ((tb >> k) & 1u) != 0u;
+            const double a = t ? aA : aR, o = t ? oA : oR, tt = t ? 1.0 : 0.0;
+            B = a * B + o * tt;
+            A = A * a;
+        }
+    }
+    double env = gate_pair_scan(A, B, cin, sa, sb);
+#pragma unroll
+    for (uint32_t j = 0; j < kGateRun / 2; ++j) {
+        const uint32_t m = f0 + 2u * j;
+        if (m >= M) break;
+        const bool t0 = ((tb >> (2u * j)) & 1u) != 0u, t1 = ((tb >> (2u * j + 1u)) & 1u) != 0u;
+        env = (t0 ? aA : aR) * env + (t0 ? oA : oR) * (t0 ? 1.0 : 0.0);
+        const double g0 = F + oF * env;
+        if (m + 1u == M) d.state->env = env;
+        double g1 = g0;
+        if (m + 1u < M) {
+            env = (t1 ? aA : aR) * env + (t1 ? oA : oR) * (t1 ? 1.0 : 0.0);
+            g1 = F + oF * env;
+            if (m + 2u == M) d.state->env = env;
+        }
+        const float4 v = x[j];
+        const float4 p = make_float4((float)((double)v.x * g0), (float)((double)v.y * g0), (float)((double)v.z * g1), (float)((double)v.w * g1));
+        // the reference's lerp (adsr.rs:42), f32
+        const float4 o = make_float4(v.x + wet * (p.x - v.x), v.y + wet * (p.y - v.y), v.z + wet * (p.z - v.z), v.w + wet * (p.w - v.w));
+        store_pair(d.out, m, M, epilogue4(o, d.pg));
+    }
+}
+
 constexpr int kMaxGridY = 65535;
 
 // Batched launches put the vertex index in grid.y (limit 65535): larger batches go out in slices.
@@ -6397,6 +6634,23 @@ void launch_reverb(const ReverbDesc* d, int n, uint32_t form, hipStream_t s) {
         if (form == 0u) hipLaunchKernelGGL((k_reverb<0>), dim3(1, std::min(n - o, kMaxGridY)), dim3(kReverbThreads), 0, s, d + o);
         else hipLaunchKernelGGL((k_reverb<1>), dim3(1, std::min(n - o, kMaxGridY)), dim3(kReverbThreads), 0, s, d + o);
     }
+}
+void launch_gate_detect(const GateDesc* d, int n, uint32_t max_tiles, hipStream_t s) {
+    for (int o = 0; o < n && max_tiles; o += kMaxGridY)
+        hipLaunchKernelGGL(k_gate_detect, dim3(max_tiles, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
+}
+void launch_gate_carry(const GateDesc* d, int n, bool affine, hipStream_t s) {
+    if (n <= 0) return;
+    if (affine) hipLaunchKernelGGL(k_gate_carry<true>, dim3(n), dim3(kThreads), 0, s, d);
+    else hipLaunchKernelGGL(k_gate_carry<false>, dim3(n), dim3(kThreads), 0, s, d);
+}
+void launch_gate_env(const GateDesc* d, int n, uint32_t max_tiles, hipStream_t s) {
+    for (int o = 0; o < n && max_tiles; o += kMaxGridY)
+        hipLaunchKernelGGL(k_gate_env, dim3(max_tiles, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
+}
+void launch_gate_apply(const GateDesc* d, int n, uint32_t max_tiles, hipStream_t s) {
+    for (int o = 0; o < n && max_tiles; o += kMaxGridY)
+        hipLaunchKernelGGL(k_gate_apply, dim3(max_tiles, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
 }
 void launch_sample_loop(const LoopDesc* d, int n, uint32_t frames, hipStream_t s) {
     if (!n || !frames) return;

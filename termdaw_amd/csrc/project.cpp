@@ -20,6 +20,7 @@
 #include "chorus_math.h"
 #include "devmem.h"
 #include "eq_math.h"
+#include "gate_math.h"
 #include "lua_subset.h"
 #include "reverb_math.h"
 #include "master.h"
@@ -111,6 +112,7 @@ struct EqCall { std::string name; float gain, angle, wet; int kind; float freq_h
 struct DelayCall { std::string name; float gain, angle, wet, time_ms, feedback, cross; };
 struct ChorusCall { std::string name; float gain, angle, wet; int voices; float delay_ms, depth_ms, rate_hz, stereo; int shape; };
 struct ReverbCall { std::string name; float gain, angle, wet, room, damp, width, size; };
+struct GateCall { std::string name; float gain, angle, wet, threshold_db, hysteresis_db, hold_ms, attack_ms, release_ms, range_db; };
 struct SatCall { std::string name; float gain, angle, wet; int kind; float drive_db, bias, out_db; int oversample; };
 
 using Triple = std::tuple<std::string, std::string, std::string>;
@@ -233,6 +235,7 @@ int do_refresh(td_state* s, const std::string& contents) {
     std::vector<SatCall> saturators;
     std::vector<ChorusCall> choruses;
     std::vector<ReverbCall> reverbs;
+    std::vector<GateCall> gates;
     size_t cs = s->cs, render_sr = s->render_sr, bd = s->bd;
     // std::mem::take (state.rs:79-80): the locals start from the previous values, the State's own fields are left
     // EMPTY until the script has run (state.rs:169-170) -- so they stay empty when the script fails
@@ -462,6 +465,17 @@ int do_refresh(td_state* s, const std::string& contents) {
                 fnum(c.width) + "," + fnum(c.size) + ")\n";
         return Value::nil();
     });
+    lua.set_function("add_gate", [&](const std::vector<Value>& a) {   // this engine's own vertex (termdaw_amd.h td_graph_add_gate)
+        const char* f = "add_gate";
+        gates.push_back({to_str(f, a, 0), to_f32(f, a, 1), to_f32(f, a, 2), to_f32(f, a, 3), to_f32(f, a, 4), to_f32(f, a, 5), to_f32(f, a, 6),
+                         to_f32(f, a, 7), to_f32(f, a, 8), to_f32(f, a, 9)});
+        auto& c = gates.back();
+        // (out-of-range parameters are rejected here, where the line is known)
+        if (const char* why = tde::gate::check(c.threshold_db, c.hysteresis_db, c.hold_ms, c.attack_ms, c.release_ms, c.range_db)) throw LuaError{std::string("add_gate: ") + why};
+        dump += std::string(f) + "(\"" + c.name + "\"," + fnum(c.gain) + "," + fnum(c.angle) + "," + fnum(c.wet) + "," + fnum(c.threshold_db) + "," + fnum(c.hysteresis_db) + "," +
+                fnum(c.hold_ms) + "," + fnum(c.attack_ms) + "," + fnum(c.release_ms) + "," + fnum(c.range_db) + ")\n";
+        return Value::nil();
+    });
     lua.set_function("connect", [&](const std::vector<Value>& a) {
         edges.push_back({to_str("connect", a, 0), to_str("connect", a, 1)});
         dump += "connect(\"" + edges.back().first + "\",\"" + edges.back().second + "\")\n";
@@ -588,6 +602,8 @@ int do_refresh(td_state* s, const std::string& contents) {
         if (!td_graph_add_chorus(s->g, c.name.c_str(), c.gain, c.angle, c.wet, c.voices, c.delay_ms, c.depth_ms, c.rate_hz, c.stereo, c.shape)) return 0;
     for (auto& c : reverbs)
         if (!td_graph_add_reverb(s->g, c.name.c_str(), c.gain, c.angle, c.wet, c.room, c.damp, c.width, c.size)) return 0;
+    for (auto& c : gates)
+        if (!td_graph_add_gate(s->g, c.name.c_str(), c.gain, c.angle, c.wet, c.threshold_db, c.hysteresis_db, c.hold_ms, c.attack_ms, c.release_ms, c.range_db)) return 0;
     for (auto& e : edges) td_graph_connect(s->g, e.first.c_str(), e.second.c_str());   // failures only warn (state.rs:459)
     td_graph_set_output(s->g, s->output_vertex.c_str());
     if (!td_graph_check(s->g)) return fail("TermDaw: graph check failed! (" + g_error + ")");

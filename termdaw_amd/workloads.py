@@ -169,7 +169,7 @@ class ProjectScript:
         self.calls = {k: [] for k in (
             "load_sample", "load_resource", "load_midi_floww", "add_sum", "add_normalize", "add_sampleloop",
             "add_sample_multi", "add_sample_lerp", "add_debug_sine", "add_synth", "add_sampsyn", "add_adsr",
-            "add_bandpass", "add_compressor", "add_eq", "add_delay", "add_saturator", "add_chorus", "add_reverb", "connect")}
+            "add_bandpass", "add_compressor", "add_eq", "add_delay", "add_saturator", "add_chorus", "add_reverb", "add_gate", "connect")}
         self.resources = {}                 # path -> bytes (load_resource)
         self.script_order = []              # (fn, args) in call order, for to_lua()
 
@@ -264,6 +264,10 @@ class ProjectScript:
         """This engine's own vertex (include/termdaw_amd.h td_graph_add_reverb): no reference counterpart."""
         self._rec("add_reverb", name, gain, angle, wet, room, damp, width, size)
 
+    def add_gate(self, name, gain, angle, wet, threshold_db, hysteresis_db, hold_ms, attack_ms, release_ms, range_db):
+        """This engine's own vertex (include/termdaw_amd.h td_graph_add_gate): no reference counterpart."""
+        self._rec("add_gate", name, gain, angle, wet, threshold_db, hysteresis_db, hold_ms, attack_ms, release_ms, range_db)
+
     def connect(self, a, b):
         self._rec("connect", a, b)
 
@@ -331,6 +335,8 @@ class ProjectScript:
             g.add_chorus(*args)
         for args in self.calls["add_reverb"]:
             g.add_reverb(*args)
+        for args in self.calls["add_gate"]:
+            g.add_gate(*args)
         for a, b in self.calls["connect"]:
             g.connect(a, b)
         g.set_output(self.output_vertex)
