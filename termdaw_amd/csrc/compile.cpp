@@ -3,14 +3,10 @@
 // this file calls the HIP runtime: device memory reaches it as addresses handed out by three functions of engine.cpp
 // (compile.h: take_buffer / ensure_buffers for edge buffers, upload_tables for a vertex' event tables), everything it
 // writes goes into the plain-memory staging arena of the ChunkBuild (offsets + fix-up lists that submit_chunk patches once
-// the device addresses are known).  tests/test_compile_asan.py builds it with g++ -fsanitize=address,undefined.
-#include "chorus_math.h"
-#include "gate_math.h"
+// the device addresses are known).  The effect kinds (compressor .. gate) are lowered by compile_fx.cpp, through the table there;
+// that file is included at the end of this one (see there).  tests/test_compile_asan.py builds it with g++
+// -fsanitize=address,undefined.
 #include "compile.h"
-#include "delay_math.h"
-#include "eq_math.h"
-#include "reverb_math.h"
-#include "sat_math.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -113,20 +109,13 @@ struct IntervalBuilder {
 
 static inline float note_hz(float note) { return 440.0f * powf(2.0f, (note - 69.0f) / 12.0f); }   // extensions.rs:451,503
 
-struct VTables {   // per-vertex compile result: offsets into the vertex' table buffer (TableCache)
+struct VTables {   // per-vertex compile result
+    TableLayout lay;                // offsets into the vertex' table buffer (TableCache)
     const uint8_t* dev = nullptr;   // device address the offsets refer to
-    size_t hits_off = 0;
-    uint32_t n_hits = 0;
-    size_t istart_off = 0, ivoff_off = 0, voices_off = 0, tile_first_off = 0, tile_order_off = 0;
-    uint32_t n_int = 0;
     uint64_t t0 = 0;
-    size_t raw_istart_off = 0, raw_ivoff_off = 0, raw_voices_off = 0, raw_tile_first_off = 0;   // (TableCache: a probed affine Synth vertex)
-    uint32_t raw_n_int = 0;
-    size_t probe_v_off = 0;   // (a probed sine / Synth vertex) per sample of k_sine_probe: its frame's voice range in the raw table
-    float hz_max = 0.0f;      // (Synth) the largest |hz| of any voice record of the tables (NaN: +inf): SynthDesc::small_args
 };
 
-static PanGain make_pg(float gain, float angle) {
+PanGain make_pg(float gain, float angle) {
     PanGain pg{1.0f, 1.0f, 1.0f, 0u};
     if (!(fabsf(angle) < 0.001f)) {   // sample.rs:98
         const float angle_rad = angle * 0.5f * 0.01745329f;
@@ -164,8 +153,8 @@ static void compile_multi(Vertex& v, size_t L, const td_flowwbank* fb, const std
     v.ts.clear();
     for (auto& h : hits)
         if (h.origin + (int64_t)L > (int64_t)M) v.ts.push_back({(int64_t)M - h.origin, h.vel});
-    vt.n_hits = (uint32_t)hits.size();
-    vt.hits_off = st.put(hits);
+    vt.lay.n_hits = (uint32_t)hits.size();
+    vt.lay.hits_off = st.put(hits);
     // per tile: first hit whose voice can still sound at the tile's first frame
     std::vector<uint32_t> tf((M + kTileFrames - 1) / kTileFrames + 1);
     uint32_t j = 0;
@@ -174,7 +163,7 @@ static void compile_multi(Vertex& v, size_t L, const td_flowwbank* fb, const std
         while (j < hits.size() && hits[j].origin <= lo_key) ++j;
         tf[t] = j;
     }
-    vt.tile_first_off = st.put(tf);
+    vt.lay.tile_first_off = st.put(tf);
 }
 
 // ---- SampleLerp (extensions.rs:384-421) ----
@@ -203,8 +192,8 @@ static void compile_lerp(Vertex& v, const td_flowwbank* fb, const std::vector<Bl
     v.p_vel = p.vel;
     v.g_off = M - g.origin;
     v.g_vel = g.vel;
-    vt.n_hits = (uint32_t)hits.size();
-    vt.hits_off = st.put(hits);
+    vt.lay.n_hits = (uint32_t)hits.size();
+    vt.lay.hits_off = st.put(hits);
     // per tile: number of entries whose key is <= the tile's first frame
     std::vector<uint32_t> tf((size_t)(M + kTileFrames - 1) / kTileFrames + 1);
     uint32_t j = 0;
@@ -212,7 +201,7 @@ static void compile_lerp(Vertex& v, const td_flowwbank* fb, const std::vector<Bl
         while (j < hits.size() && hits[j].key <= (int64_t)(t * kTileFrames)) ++j;
         tf[t] = j;
     }
-    vt.tile_first_off = st.put(tf);
+    vt.lay.tile_first_off = st.put(tf);
 }
 
 struct IntervalView {   // what put_intervals reads of an interval table
@@ -227,7 +216,7 @@ static void put_intervals(IntervalBuilder& b, Staging& st, VTables& vt) {
     put_intervals(IntervalView{b.istart, b.ivoff, b.voices, b.limit}, st, vt);
 }
 static void put_intervals(IntervalView ib, Staging& st, VTables& vt) {
-    vt.n_int = (uint32_t)ib.istart.size();
+    vt.lay.n_int = (uint32_t)ib.istart.size();
     // per 1024-frame tile: the interval that holds the tile's first frame (istart[0] == 0, ascending)
     std::vector<uint32_t> tile_first((ib.limit + kTileFrames - 1) / kTileFrames + 1);
     uint32_t it = 0;
@@ -236,7 +225,7 @@ static void put_intervals(IntervalView ib, Staging& st, VTables& vt) {
         while (it + 1 < ib.istart.size() && ib.istart[it + 1] <= m) ++it;
         tile_first[t] = it;
     }
-    vt.tile_first_off = st.put(tile_first);
+    vt.lay.tile_first_off = st.put(tile_first);
     {   // IntervalTab::tile_order: the costliest tiles first -- a tile's cost is a pass of the voice loop per interval it holds
         // frames of (the tiles with an interval start strictly inside them: the waves that take the per-interval passes), each as
         // long as the interval has voices.  Longest first, the grid's last workgroups are the cheap ones -- the tiles between two
@@ -254,11 +243,11 @@ static void put_intervals(IntervalView ib, Staging& st, VTables& vt) {
         std::vector<uint32_t> order(nt);
         for (size_t t = 0; t < nt; ++t) order[t] = (uint32_t)t;
         std::stable_sort(order.begin(), order.end(), [&cost](uint32_t a, uint32_t b) { return cost[a] > cost[b]; });
-        vt.tile_order_off = st.put(order);
+        vt.lay.tile_order_off = st.put(order);
     }
-    vt.istart_off = st.put(ib.istart);
-    vt.ivoff_off = st.put(ib.ivoff);
-    vt.voices_off = st.put(ib.voices);
+    vt.lay.istart_off = st.put(ib.istart);
+    vt.lay.ivoff_off = st.put(ib.ivoff);
+    vt.lay.voices_off = st.put(ib.voices);
 }
 
 // k_sine_probe's sampling of a chunk of M frames (kernels.h ProbeDesc): one frame in every `1 << lg` -- every 256th of a long
@@ -312,7 +301,7 @@ static void compile_sine(Vertex& v, const td_flowwbank* fb, const std::vector<Bl
             [&](size_t i) { emit(b * bl + i); });
     }
     put_intervals(ib, st, vt);
-    if (v.probe) vt.probe_v_off = put_probe_ranges(IntervalView{ib.istart, ib.ivoff, ib.voices, ib.limit}, st);
+    if (v.probe) vt.lay.probe_v_off = put_probe_ranges(IntervalView{ib.istart, ib.ivoff, ib.voices, ib.limit}, st);
 }
 
 // ---- Synth (extensions.rs:460-529) ----
@@ -507,8 +496,8 @@ static int compile_synth(Vertex& v, const td_flowwbank* fb, const std::vector<Bl
                       v.notes.end());
     }
     if (impossible) return fail("Synth: impossible release stage note");
-    vt.hz_max = 0.0f;
-    for (const float4& n : ib.voices) vt.hz_max = fabsf(n.x) <= vt.hz_max ? vt.hz_max : (n.x == n.x ? fabsf(n.x) : INFINITY);
+    vt.lay.hz_max = 0.0f;
+    for (const float4& n : ib.voices) vt.lay.hz_max = fabsf(n.x) <= vt.lay.hz_max ? vt.lay.hz_max : (n.x == n.x ? fabsf(n.x) : INFINITY);
     if (v.kind == K_SYNTH && synth_affine_ok(v)) {
         ib.finish();
         std::vector<uint32_t> istart, ivoff;
@@ -518,16 +507,16 @@ static int compile_synth(Vertex& v, const td_flowwbank* fb, const std::vector<Bl
         if (v.probe) {   // (sine_mode 2) the raw table too: k_sine_probe evaluates the reference's own per-frame form
             VTables raw;
             put_intervals(IntervalView{ib.istart, ib.ivoff, ib.voices, ib.limit}, st, raw);
-            vt.raw_istart_off = raw.istart_off; vt.raw_ivoff_off = raw.ivoff_off; vt.raw_voices_off = raw.voices_off;
-            vt.raw_tile_first_off = raw.tile_first_off; vt.raw_n_int = raw.n_int;
-            vt.probe_v_off = put_probe_ranges(IntervalView{ib.istart, ib.ivoff, ib.voices, ib.limit}, st);
+            vt.lay.raw_istart_off = raw.lay.istart_off; vt.lay.raw_ivoff_off = raw.lay.ivoff_off; vt.lay.raw_voices_off = raw.lay.voices_off;
+            vt.lay.raw_tile_first_off = raw.lay.tile_first_off; vt.lay.raw_n_int = raw.lay.n_int;
+            vt.lay.probe_v_off = put_probe_ranges(IntervalView{ib.istart, ib.ivoff, ib.voices, ib.limit}, st);
         }
         return 1;
     }
     put_intervals(ib, st, vt);
-    vt.raw_istart_off = vt.istart_off; vt.raw_ivoff_off = vt.ivoff_off; vt.raw_voices_off = vt.voices_off;
-    vt.raw_tile_first_off = vt.tile_first_off; vt.raw_n_int = vt.n_int;
-    if (v.probe) vt.probe_v_off = put_probe_ranges(IntervalView{ib.istart, ib.ivoff, ib.voices, ib.limit}, st);
+    vt.lay.raw_istart_off = vt.lay.istart_off; vt.lay.raw_ivoff_off = vt.lay.ivoff_off; vt.lay.raw_voices_off = vt.lay.voices_off;
+    vt.lay.raw_tile_first_off = vt.lay.tile_first_off; vt.lay.raw_n_int = vt.lay.n_int;
+    if (v.probe) vt.lay.probe_v_off = put_probe_ranges(IntervalView{ib.istart, ib.ivoff, ib.voices, ib.limit}, st);
     return 1;
 }
 
@@ -818,18 +807,6 @@ static bool plan_band_scan(const td_graph* g, const Vertex& v, size_t M, ScanPla
     return true;
 }
 
-// A delay, saturator, chorus or reverb vertex enters a chunk of M frames: a set_time since the vertex last ran is consumed here
-// (the block restarts from zero, like an EQ's state), the books move on behind the chunk -- `alternates`: the launch writes the other
-// half of the line, which the next one reads.  Returns the frames run up to the chunk (Vertex::Line::total as the chunk finds it).
-static uint64_t enter_chunk(Vertex& v, size_t M, bool alternates) {
-    if (v.first_pending) v.line.total = 0;
-    v.first_pending = false;
-    const uint64_t total = v.line.total;
-    v.line.total += M;
-    if (alternates) v.line.parity ^= 1u;
-    return total;
-}
-
 // ------------------------------------------------------------------------------------------------
 // one chunk: compile tables + descriptors (compile_chunk), then upload and launch level by level (submit_chunk)
 // ------------------------------------------------------------------------------------------------
@@ -931,42 +908,11 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                 const Vertex& wv = g->vertices[w];
                 long through = down[w].norm;
                 if (through == -2) { nz = -2; break; }
-                // a compressor is no static gain: no estimate is carried through it -- everything upstream takes the exact forms,
-                // as upstream of a stem
-                if (wv.kind == K_COMPRESSOR) { nz = -2; break; }
-                // ... and so is a gate, unless it is dry: then it is the Sum it compiles to
-                if (wv.kind == K_GATE && !(wv.wet < 0.0001f)) { nz = -2; break; }
-                double L = own_gain(wv);
-                // an EQ is linear and time-invariant: the estimate goes through it at the L2 gain of its lerp, (1 - wet) + wet Hmax
-                // 
-                if (wv.kind == K_EQ && !(wv.wet < 0.0001f)) {
-                    double c[5];
-                    eq::coefficients(wv.eq_kind, sr, wv.eq_freq, wv.eq_q, wv.eq_gain_db, c);
-                    L *= (1.0 - (double)wv.wet) + (double)wv.wet * eq::hmax(c);
-                }
-                // a delay too: out = x + wet (echoes), the echo path's L2 gain is Hecho = 1 / (1 - feedback)
-                if (wv.kind == K_DELAY && !(wv.wet < 0.0001f)) {
-                    double c[4];
-                    delay::params(sr, wv.delay_ms, wv.delay_feedback, wv.delay_cross, c);
-                    L *= 1.0 + (double)wv.wet * c[3];
-                }
-                // a saturator's shaper is Lipschitz: the estimate goes through it at (1 - wet) + wet Hsat, Hsat = g_out Hdown Lf g_in Hup
-                // 
-                if (wv.kind == K_SATURATOR && !(wv.wet < 0.0001f)) {
-                    double c[6];
-                    sat::params(wv.sat_kind, wv.sat_oversample, wv.sat_drive_db, wv.sat_bias, wv.sat_out_db, c);
-                    L *= (1.0 - (double)wv.wet) + (double)wv.wet * c[5];
-                }
-                // a chorus is linear (and time-varying): the estimate goes through it at (1 - wet) + wet Hch, Hch an L2 bound of the
-                // modulated four-point read
-                if (wv.kind == K_CHORUS && !(wv.wet < 0.0001f)) L *= (1.0 - (double)wv.wet) + (double)wv.wet * chorus::kHch;
-                // a reverb is linear and time-invariant: the estimate goes through it at (1 - wet) + wet Hrev, Hrev the product of its
-                // stages' largest gains
-                if (wv.kind == K_REVERB && !(wv.wet < 0.0001f)) {
-                    double c[reverb::kParams];
-                    reverb::params(sr, wv.reverb_room, wv.reverb_damp, wv.reverb_width, wv.reverb_size, c);
-                    L *= (1.0 - (double)wv.wet) + (double)wv.wet * c[5];
-                }
+                // an effect vertex: at its kind's static gain, if it has one (compile_fx.cpp FxKind::through)
+                const FxKind* fx = fx_kind(wv.kind);
+                const double fx_gain = fx ? fx->through(wv, sr) : 1.0;
+                if (fx_gain == kNoStaticGain) { nz = -2; break; }
+                double L = own_gain(wv) * fx_gain;
                 if (wv.kind == K_ADSR && !(wv.wet < 0.0001f)) {   // |lerp(1, level x vel, wet)| <= max(1, |level| |vel|)
                     const AdsrConfD& c = wv.conf;
                     double lv = std::max(std::max(fabs((double)c.std_vel), fabs((double)c.attack_vel)),
@@ -1059,28 +1005,15 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                 }
                 tc->key.clear();   // (not valid until the upload below has been queued)
                 if (!upload_tables(g, *tc, tmp)) return 0;
-                tc->hits_off = t.hits_off; tc->n_hits = t.n_hits;
-                tc->istart_off = t.istart_off; tc->ivoff_off = t.ivoff_off; tc->voices_off = t.voices_off;
-                tc->tile_first_off = t.tile_first_off; tc->n_int = t.n_int;
-                tc->tile_order_off = t.tile_order_off;
-                tc->raw_istart_off = t.raw_istart_off; tc->raw_ivoff_off = t.raw_ivoff_off; tc->raw_voices_off = t.raw_voices_off;
-                tc->raw_tile_first_off = t.raw_tile_first_off; tc->raw_n_int = t.raw_n_int; tc->probe_v_off = t.probe_v_off;
-                tc->hz_max = t.hz_max;
+                tc->lay = t.lay;
                 tc->end_state.clear();
                 save_state(v, tc->end_state);
                 tc->key = key;
             }
             chunk_keys[key] = vi;
         }
-        VTables& o = vt[vi];
-        o.dev = tc->d;
-        o.hits_off = tc->hits_off; o.n_hits = tc->n_hits;
-        o.istart_off = tc->istart_off; o.ivoff_off = tc->ivoff_off; o.voices_off = tc->voices_off;
-        o.tile_first_off = tc->tile_first_off; o.n_int = tc->n_int;
-        o.tile_order_off = tc->tile_order_off;
-        o.raw_istart_off = tc->raw_istart_off; o.raw_ivoff_off = tc->raw_ivoff_off; o.raw_voices_off = tc->raw_voices_off;
-        o.raw_tile_first_off = tc->raw_tile_first_off; o.raw_n_int = tc->raw_n_int; o.probe_v_off = tc->probe_v_off;
-        o.hz_max = tc->hz_max;
+        vt[vi].lay = tc->lay;
+        vt[vi].dev = tc->d;
     }
 
     // ---- 2. descriptors: walk levels, assign edge buffers
@@ -1305,6 +1238,21 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                 if (!inlined[bw]) last_use[bw] = std::max(last_use[bw], g->level[last]);
             }
         }
+    // pointer to a table of an event-driven vertex: those live in the vertex' own device buffer (TableCache)
+    auto tab_field = [&](size_t desc_off, size_t field_off, const VTables& t, size_t off) {
+        const uint64_t p = (uint64_t)(uintptr_t)(t.dev + off);
+        memcpy(&st.b[desc_off + field_off], &p, 8);
+    };
+    // an interval table's pointers (kernels.h IntervalTab at arena offset `tab`): the vertex' own table, or the raw one beside an affine
+    // Synth vertex' (k_sine_probe); tile_order where the kernel walks its tiles by it
+    auto interval_tab = [&](size_t tab, const VTables& t, bool raw, bool with_order = false) {
+        if (with_order) tab_field(tab, offsetof(IntervalTab, tile_order), t, t.lay.tile_order_off);
+        tab_field(tab, offsetof(IntervalTab, istart), t, raw ? t.lay.raw_istart_off : t.lay.istart_off);
+        tab_field(tab, offsetof(IntervalTab, tile_first), t, raw ? t.lay.raw_tile_first_off : t.lay.tile_first_off);
+        tab_field(tab, offsetof(IntervalTab, ivoff), t, raw ? t.lay.raw_ivoff_off : t.lay.ivoff_off);
+        tab_field(tab, offsetof(IntervalTab, voices), t, raw ? t.lay.raw_voices_off : t.lay.voices_off);
+    };
+
     // ---- gain buffers of the Adsr vertices that are read through (k_adsr_env), before everything else: they depend on
     // the event tables only, and a chain launch needs those of its links however deep they sit in the graph
     {
@@ -1314,9 +1262,9 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
             const Vertex& v = g->vertices[vi];
             std::string key;
             put_pod(key, (uint64_t)(uintptr_t)vt[vi].dev);
-            put_pod(key, (uint64_t)vt[vi].istart_off); put_pod(key, (uint64_t)vt[vi].ivoff_off);
-            put_pod(key, (uint64_t)vt[vi].voices_off); put_pod(key, (uint64_t)vt[vi].tile_first_off);
-            put_pod(key, vt[vi].n_int);
+            put_pod(key, (uint64_t)vt[vi].lay.istart_off); put_pod(key, (uint64_t)vt[vi].lay.ivoff_off);
+            put_pod(key, (uint64_t)vt[vi].lay.voices_off); put_pod(key, (uint64_t)vt[vi].lay.tile_first_off);
+            put_pod(key, vt[vi].lay.n_int);
             put_pod(key, v.conf); put_pod(key, v.wet);
             put_pod(key, (uint8_t)v.use_off); put_pod(key, (uint8_t)v.use_max);
             auto it = env_of_key.find(key);
@@ -1334,7 +1282,7 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
             for (size_t vi : envs) {
                 const Vertex& v = g->vertices[vi];
                 AdsrVDesc x{};
-                x.tab.n_int = vt[vi].n_int;
+                x.tab.n_int = vt[vi].lay.n_int;
                 x.sr = (uint32_t)sr;
                 x.bl = (uint32_t)bl;
                 x.use_off = v.use_off;
@@ -1353,31 +1301,11 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                     env_tile_at[env_of[envs[i]]] = so;
                     cb.scratch_fix.push_back({off + i * sizeof(AdsrVDesc) + offsetof(AdsrVDesc, env_tile), so});
                 }
-                const size_t t = off + i * sizeof(AdsrVDesc) + offsetof(AdsrVDesc, tab);
-                const auto tf = [&](size_t field_off, size_t o2) {
-                    const uint64_t p = (uint64_t)(uintptr_t)(vt[envs[i]].dev + o2);
-                    memcpy(&st.b[t + field_off], &p, 8);
-                };
-                tf(offsetof(IntervalTab, istart), vt[envs[i]].istart_off);
-                tf(offsetof(IntervalTab, tile_first), vt[envs[i]].tile_first_off);
-                tf(offsetof(IntervalTab, ivoff), vt[envs[i]].ivoff_off);
-                tf(offsetof(IntervalTab, voices), vt[envs[i]].voices_off);
+                interval_tab(off + i * sizeof(AdsrVDesc) + offsetof(AdsrVDesc, tab), vt[envs[i]], false);
             }
             add_launch(F_ENV, off, (int)envs.size(), 0u, 0);   // (level 0: beside the source vertices, which it may share a grid with -- k_sources)
         }
     }
-
-    // scratch (device-only) region is laid out after the uploaded region
-    auto scratch = [&](size_t n) { size_t o = cb.scratch_bytes; cb.scratch_bytes += (n + 255) & ~(size_t)255; return o; };
-    auto ptr_field = [&](size_t desc_off, size_t field_off, size_t staging_off) {
-        cb.table_fix.push_back({desc_off + field_off, staging_off});
-    };
-    // pointer to a table of an event-driven vertex: those live in the vertex' own device buffer (TableCache)
-    auto tab_field = [&](size_t desc_off, size_t field_off, const VTables& t, size_t off) {
-        const uint64_t p = (uint64_t)(uintptr_t)(t.dev + off);
-        memcpy(&st.b[desc_off + field_off], &p, 8);
-    };
-    auto scratch_field = [&](size_t desc_off, size_t field_off, size_t s_off) { cb.scratch_fix.push_back({desc_off + field_off, s_off}); };
 
     const bool peaks_need_zero = !(bl == (size_t)kTileFrames);
     // the guard's bookkeeping (band_mode 2): where every Normalize vertex of the chunk keeps its peak table and carried max,
@@ -1389,7 +1317,7 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
     auto synth_desc_of = [&](size_t vi) {   // a Synth vertex' descriptor, tables aside
         const Vertex& v = g->vertices[vi];
         SynthDesc x{};
-        x.tab.n_int = vt[vi].n_int;
+        x.tab.n_int = vt[vi].lay.n_int;
         x.out = g->vbuf[vi];
         x.t0 = t0;
         x.sr = (uint32_t)sr;
@@ -1404,7 +1332,7 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
         x.pg = make_pg(v.gain, v.angle);
         x.affine = synth_affine_ok(v) ? 1u : 0u;   // (the tables then hold affine records: compile_synth)
         x.exact_sin = v.exact_sin ? 1u : 0u;
-        x.small_args = ((double)(t0 + M + 2) / (double)sr) * (double)vt[vi].hz_max * 6.2831854 < 2.0e6 ? 1u : 0u;
+        x.small_args = ((double)(t0 + M + 2) / (double)sr) * (double)vt[vi].lay.hz_max * 6.2831854 < 2.0e6 ? 1u : 0u;
         {
             auto same = [](const AdsrConfD& a, const AdsrConfD& b) { return memcmp(&a, &b, sizeof(AdsrConfD)) == 0; };
             const bool sq = v.square.volume > 0.0f, tf = v.topflat.volume > 0.0f;
@@ -1490,63 +1418,13 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                         }
                     }
                     break;
-                case K_COMPRESSOR:
-                    if (v.wet < 0.0001f) {
-                        fam_v[F_SUM].push_back(vi);   // the summed input passes through, the state stays
-                    } else {
-                        if (M > 0xFFFF0000ull) return fail("compressor: chunk too long");
-                        fam_v[F_COMP_DETECT].push_back(vi);
+                default:
+                    if (const FxKind* fx = fx_kind(v.kind)) {   // an effect vertex (compile_fx.cpp)
+                        if (v.wet < 0.0001f) fam_v[F_SUM].push_back(vi);   // the summed input passes through, the state / line stays
+                        else if (!fx->fits(g, v, M)) return fail(std::string(fx->name) + ": chunk too long");
+                        else fam_v[fx->family_of(v)].push_back(vi);
                     }
                     break;
-                case K_GATE:
-                    if (v.wet < 0.0001f) {
-                        fam_v[F_SUM].push_back(vi);   // the summed input passes through, the state stays
-                    } else {
-                        if (M > 0xFFFF0000ull) return fail("gate: chunk too long");
-                        fam_v[F_GATE_DETECT].push_back(vi);
-                    }
-                    break;
-                case K_EQ:
-                    if (v.wet < 0.0001f) {
-                        fam_v[F_SUM].push_back(vi);   // the summed input passes through, the state stays
-                    } else {
-                        if (M > 0xFFFF0000ull) return fail("eq: chunk too long");
-                        fam_v[F_EQ_LOCAL].push_back(vi);
-                    }
-                    break;
-                case K_DELAY:
-                    if (v.wet < 0.0001f) {
-                        fam_v[F_SUM].push_back(vi);   // the summed input passes through, the line stays
-                    } else {
-                        if (M > 0xF0000000ull) return fail("delay: chunk too long");
-                        fam_v[F_DELAY_APPLY].push_back(vi);
-                    }
-                    break;
-                case K_SATURATOR:
-                    if (v.wet < 0.0001f) {
-                        fam_v[F_SUM].push_back(vi);   // the summed input passes through, the line stays
-                    } else {
-                        if (M > 0xF0000000ull || (M + g->sat_tile - 1) / g->sat_tile >= 0x100000ull) return fail("saturator: chunk too long");
-                        fam_v[v.sat_oversample == 1 ? F_SAT1 : F_SAT].push_back(vi);
-                    }
-                    break;
-                case K_CHORUS:
-                    if (v.wet < 0.0001f) {
-                        fam_v[F_SUM].push_back(vi);   // the summed input passes through, the line stays
-                    } else {
-                        if (M > 0xF0000000ull || (M + g->chorus_tile - 1) / g->chorus_tile >= 0x100000ull) return fail("chorus: chunk too long");
-                        fam_v[F_CHORUS].push_back(vi);
-                    }
-                    break;
-                case K_REVERB:
-                    if (v.wet < 0.0001f) {
-                        fam_v[F_SUM].push_back(vi);   // the summed input passes through, the state stays
-                    } else {
-                        if (M > 0xF0000000ull) return fail("reverb: chunk too long");
-                        fam_v[F_REVERB].push_back(vi);
-                    }
-                    break;
-                default: break;
             }
         }
         // input term tables: an edge buffer, or an inlined sample_loop source gathered by the consumer
@@ -1604,7 +1482,7 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                 const size_t a = th.second;
                 const Vertex& av = g->vertices[a];
                 AdsrVDesc x{};
-                x.tab.n_int = vt[a].n_int;
+                x.tab.n_int = vt[a].lay.n_int;
                 x.k = 1u;   // its one input, as a term table of its own (kind 0 .. 4)
                 x.sr = (uint32_t)sr;
                 x.bl = (uint32_t)bl;
@@ -1618,13 +1496,9 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                 const size_t in_off = st.put(std::vector<InTerm>{plain_term(g->edges[a][0])});
                 const size_t o = st.alloc(sizeof x);
                 memcpy(&st.b[o], &x, sizeof x);
-                ptr_field(o, offsetof(AdsrVDesc, ins), in_off);
-                const size_t t = o + offsetof(AdsrVDesc, tab);
-                tab_field(t, offsetof(IntervalTab, istart), vt[a], vt[a].istart_off);
-                tab_field(t, offsetof(IntervalTab, tile_first), vt[a], vt[a].tile_first_off);
-                tab_field(t, offsetof(IntervalTab, ivoff), vt[a], vt[a].ivoff_off);
-                tab_field(t, offsetof(IntervalTab, voices), vt[a], vt[a].voices_off);
-                ptr_field(ins_off[vi] + th.first * sizeof(InTerm), offsetof(InTerm, len), o);
+                cb.ptr_field(o, offsetof(AdsrVDesc, ins), in_off);
+                interval_tab(o + offsetof(AdsrVDesc, tab), vt[a], false);
+                cb.ptr_field(ins_off[vi] + th.first * sizeof(InTerm), offsetof(InTerm, len), o);
             }
         }
         for (size_t vi : norm_pending) {
@@ -1673,6 +1547,14 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
             if (fam == F_BAND_FILL) continue;   // (the parked stretches' output is filled in by k_band_fix itself)
             if (fam == F_BAND_FIX) vs = fam_v[F_BAND_SPEC];   // same vertices, follow-up launch
             if (vs.empty() && !(fam == F_SUM && !fam_v[F_BAND_SPEC].empty())) continue;
+            // the level's vertices of an effect kind (compile_fx.cpp), lowered at the family FxKind::family_of filed them under: the
+            // kind's first family -- or, for the saturator, F_SAT1 as well (R = 1), so that one kind may be lowered at two families of
+            // its row, each with its own vertices; lower_sat tells them apart by FxLevel::fam
+            if (const FxKind* fx = fx_of_family(fam)) {
+                FxLevel fl{g, cb, M, sr, bl, t0, lv, is_scan, fam, ins_off, term_mode, level_tmp};
+                if (!fx->lower(fl, vs)) return 0;
+                continue;
+            }
             size_t off = 0;
             switch (fam) {
                 case F_LOOP: {
@@ -1691,12 +1573,12 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                     for (size_t vi : vs) {
                         const Vertex& v = g->vertices[vi];
                         const SampleEntry& s = sb->samples[v.sample_index];
-                        d.push_back({s.d, g->vbuf[vi], nullptr, s.len, vt[vi].n_hits, 0, make_pg(v.gain, v.angle), nullptr});
+                        d.push_back({s.d, g->vbuf[vi], nullptr, s.len, vt[vi].lay.n_hits, 0, make_pg(v.gain, v.angle), nullptr});
                     }
                     off = st.put(d);
                     for (size_t i = 0; i < vs.size(); ++i) {
-                        tab_field(off + i * sizeof(MultiDesc), offsetof(MultiDesc, hits), vt[vs[i]], vt[vs[i]].hits_off);
-                        tab_field(off + i * sizeof(MultiDesc), offsetof(MultiDesc, tile_first), vt[vs[i]], vt[vs[i]].tile_first_off);
+                        tab_field(off + i * sizeof(MultiDesc), offsetof(MultiDesc, hits), vt[vs[i]], vt[vs[i]].lay.hits_off);
+                        tab_field(off + i * sizeof(MultiDesc), offsetof(MultiDesc, tile_first), vt[vs[i]], vt[vs[i]].lay.tile_first_off);
                     }
                 } break;
                 case F_LERP: {
@@ -1704,13 +1586,13 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                     for (size_t vi : vs) {
                         const Vertex& v = g->vertices[vi];
                         const SampleEntry& s = sb->samples[v.sample_index];
-                        d.push_back({s.d, g->vbuf[vi], nullptr, s.len, vt[vi].n_hits, (uint32_t)v.lerp_len,
+                        d.push_back({s.d, g->vbuf[vi], nullptr, s.len, vt[vi].lay.n_hits, (uint32_t)v.lerp_len,
                                      make_pg(v.gain, v.angle), nullptr});
                     }
                     off = st.put(d);
                     for (size_t i = 0; i < vs.size(); ++i) {
-                        tab_field(off + i * sizeof(LerpDesc), offsetof(LerpDesc, hits), vt[vs[i]], vt[vs[i]].hits_off);
-                        tab_field(off + i * sizeof(LerpDesc), offsetof(LerpDesc, tile_first), vt[vs[i]], vt[vs[i]].tile_first_off);
+                        tab_field(off + i * sizeof(LerpDesc), offsetof(LerpDesc, hits), vt[vs[i]], vt[vs[i]].lay.hits_off);
+                        tab_field(off + i * sizeof(LerpDesc), offsetof(LerpDesc, tile_first), vt[vs[i]], vt[vs[i]].lay.tile_first_off);
                     }
                 } break;
                 case F_SINE: {
@@ -1718,7 +1600,7 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                     for (size_t vi : vs) {
                         const Vertex& v = g->vertices[vi];
                         SineDesc x{};
-                        x.tab.n_int = vt[vi].n_int;
+                        x.tab.n_int = vt[vi].lay.n_int;
                         x.out = g->vbuf[vi];
                         x.t0 = t0;
                         x.sr = (uint32_t)sr;
@@ -1727,13 +1609,7 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                         d.push_back(x);
                     }
                     off = st.put(d);
-                    for (size_t i = 0; i < vs.size(); ++i) {
-                        const size_t o = off + i * sizeof(SineDesc) + offsetof(SineDesc, tab);
-                        tab_field(o, offsetof(IntervalTab, istart), vt[vs[i]], vt[vs[i]].istart_off);
-                        tab_field(o, offsetof(IntervalTab, tile_first), vt[vs[i]], vt[vs[i]].tile_first_off);
-                        tab_field(o, offsetof(IntervalTab, ivoff), vt[vs[i]], vt[vs[i]].ivoff_off);
-                        tab_field(o, offsetof(IntervalTab, voices), vt[vs[i]], vt[vs[i]].voices_off);
-                    }
+                    for (size_t i = 0; i < vs.size(); ++i) interval_tab(off + i * sizeof(SineDesc) + offsetof(SineDesc, tab), vt[vs[i]], false);
                 } break;
                 case F_SYNTH: {
                     std::vector<SynthDesc> d;
@@ -1741,14 +1617,7 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                     std::stable_sort(vs.begin(), vs.end(), [&](size_t a, size_t b) { return synth_affine_ok(g->vertices[a]) < synth_affine_ok(g->vertices[b]); });
                     for (size_t vi : vs) d.push_back(synth_desc_of(vi));
                     off = st.put(d);
-                    for (size_t i = 0; i < vs.size(); ++i) {
-                        const size_t o = off + i * sizeof(SynthDesc) + offsetof(SynthDesc, tab);
-                        tab_field(o, offsetof(IntervalTab, tile_order), vt[vs[i]], vt[vs[i]].tile_order_off);
-                        tab_field(o, offsetof(IntervalTab, istart), vt[vs[i]], vt[vs[i]].istart_off);
-                        tab_field(o, offsetof(IntervalTab, tile_first), vt[vs[i]], vt[vs[i]].tile_first_off);
-                        tab_field(o, offsetof(IntervalTab, ivoff), vt[vs[i]], vt[vs[i]].ivoff_off);
-                        tab_field(o, offsetof(IntervalTab, voices), vt[vs[i]], vt[vs[i]].voices_off);
-                    }
+                    for (size_t i = 0; i < vs.size(); ++i) interval_tab(off + i * sizeof(SynthDesc) + offsetof(SynthDesc, tab), vt[vs[i]], false, true);
                     size_t n_gen = 0;
                     while (n_gen < vs.size() && !d[n_gen].affine) ++n_gen;
                     if (n_gen) add_launch(fam, off, (int)n_gen, 0u, lv);
@@ -1760,7 +1629,7 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                     for (size_t vi : vs) {
                         const Vertex& v = g->vertices[vi];
                         SampsynDesc x{};
-                        x.tab.n_int = vt[vi].n_int;
+                        x.tab.n_int = vt[vi].lay.n_int;
                         x.out = g->vbuf[vi];
                         x.wt = v.wavetable;
                         x.sr = (uint32_t)sr;
@@ -1771,14 +1640,7 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                         d.push_back(x);
                     }
                     off = st.put(d);
-                    for (size_t i = 0; i < vs.size(); ++i) {
-                        const size_t o = off + i * sizeof(SampsynDesc) + offsetof(SampsynDesc, tab);
-                        tab_field(o, offsetof(IntervalTab, tile_order), vt[vs[i]], vt[vs[i]].tile_order_off);
-                        tab_field(o, offsetof(IntervalTab, istart), vt[vs[i]], vt[vs[i]].istart_off);
-                        tab_field(o, offsetof(IntervalTab, tile_first), vt[vs[i]], vt[vs[i]].tile_first_off);
-                        tab_field(o, offsetof(IntervalTab, ivoff), vt[vs[i]], vt[vs[i]].ivoff_off);
-                        tab_field(o, offsetof(IntervalTab, voices), vt[vs[i]], vt[vs[i]].voices_off);
-                    }
+                    for (size_t i = 0; i < vs.size(); ++i) interval_tab(off + i * sizeof(SampsynDesc) + offsetof(SampsynDesc, tab), vt[vs[i]], false, true);
                 } break;
                 case F_PROBE: {   // (behind F_SINE / F_SYNTH of this level: their buffers are assigned)
                     std::vector<ProbeDesc> d;
@@ -1792,9 +1654,9 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                             x.syn = synth_desc_of(vi);
                             x.syn.affine = 0u;
                             x.syn.exact_sin = 1u;
-                            x.syn.tab.n_int = vt[vi].raw_n_int;
+                            x.syn.tab.n_int = vt[vi].lay.raw_n_int;
                         } else {
-                            x.sine.tab.n_int = vt[vi].n_int;
+                            x.sine.tab.n_int = vt[vi].lay.n_int;
                             x.sine.out = g->vbuf[vi];
                             x.sine.t0 = t0;
                             x.sine.sr = (uint32_t)sr;
@@ -1807,22 +1669,11 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                     for (size_t i = 0; i < vs.size(); ++i) {
                         const VTables& t = vt[vs[i]];
                         const size_t po = off + i * sizeof(ProbeDesc);
-                        if (d[i].kind) {
-                            const size_t o = po + offsetof(ProbeDesc, syn) + offsetof(SynthDesc, tab);
-                            tab_field(o, offsetof(IntervalTab, istart), t, t.raw_istart_off);
-                            tab_field(o, offsetof(IntervalTab, tile_first), t, t.raw_tile_first_off);
-                            tab_field(o, offsetof(IntervalTab, ivoff), t, t.raw_ivoff_off);
-                            tab_field(o, offsetof(IntervalTab, voices), t, t.raw_voices_off);
-                        } else {
-                            const size_t o = po + offsetof(ProbeDesc, sine) + offsetof(SineDesc, tab);
-                            tab_field(o, offsetof(IntervalTab, istart), t, t.istart_off);
-                            tab_field(o, offsetof(IntervalTab, tile_first), t, t.tile_first_off);
-                            tab_field(o, offsetof(IntervalTab, ivoff), t, t.ivoff_off);
-                            tab_field(o, offsetof(IntervalTab, voices), t, t.voices_off);
-                        }
-                        tab_field(po, offsetof(ProbeDesc, ranges), t, t.probe_v_off);
-                        const size_t no = scratch((size_t)probe_groups * 16 * sizeof(float));
-                        scratch_field(po, offsetof(ProbeDesc, noise), no);
+                        if (d[i].kind) interval_tab(po + offsetof(ProbeDesc, syn) + offsetof(SynthDesc, tab), t, true);
+                        else interval_tab(po + offsetof(ProbeDesc, sine) + offsetof(SineDesc, tab), t, false);
+                        tab_field(po, offsetof(ProbeDesc, ranges), t, t.lay.probe_v_off);
+                        const size_t no = cb.scratch((size_t)probe_groups * 16 * sizeof(float));
+                        cb.scratch_field(po, offsetof(ProbeDesc, noise), no);
                         probe_src.push_back({vs[i], no});
                         probe_desc_off.push_back(po);
                     }
@@ -1875,8 +1726,8 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                             rp.gh = bp.Kh ? (double)v.hgamma : 0.0;
                             bp.rp_off = st.alloc(sizeof rp);
                             memcpy(&st.b[bp.rp_off], &rp, sizeof rp);
-                            bp.resp_off = scratch(((M + 255) / 256) * 4 * sizeof(double));
-                            scratch_field(bp.rp_off, offsetof(BandRespParam, resp), bp.resp_off);
+                            bp.resp_off = cb.scratch(((M + 255) / 256) * 4 * sizeof(double));
+                            cb.scratch_field(bp.rp_off, offsetof(BandRespParam, resp), bp.resp_off);
                         }
                         if (v.kind == K_NORMALIZE) {
                             x.state = &g->dstate[v.state_slot].norm;
@@ -1888,9 +1739,9 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                     off = st.put(d);
                     for (size_t i = 0; i < vs.size(); ++i) {
                         const size_t o = off + i * sizeof(SumDesc);
-                        ptr_field(o, offsetof(SumDesc, ins), ins_off[vs[i]]);
+                        cb.ptr_field(o, offsetof(SumDesc, ins), ins_off[vs[i]]);
                         if (g->vertices[vs[i]].kind == K_NORMALIZE) {
-                            const size_t pk = scratch(2 * nb * sizeof(float)), ic = scratch(2 * sizeof(float));   // (peaks, and the ragged form's second slot per block)
+                            const size_t pk = cb.scratch(2 * nb * sizeof(float)), ic = cb.scratch(2 * sizeof(float));   // (peaks, and the ragged form's second slot per block)
                             norm_scratch[vs[i]] = {pk, ic};
                             audit_norm[vs[i]] = {pk, ic};
                             sum_desc_of[vs[i]] = d[i];
@@ -1899,16 +1750,16 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                                 cb.esync_bytes += (2 * nb * 8 + 63) & ~(size_t)63;
                                 cb.flag_fix.push_back(o + offsetof(SumDesc, host_flag));
                             }
-                            scratch_field(o, offsetof(SumDesc, peaks), pk);
-                            if (ragged_of.count(vs[i])) scratch_field(o, offsetof(SumDesc, peaks2), pk + nb * sizeof(float));
-                            scratch_field(o, offsetof(SumDesc, init_copy), ic);
+                            cb.scratch_field(o, offsetof(SumDesc, peaks), pk);
+                            if (ragged_of.count(vs[i])) cb.scratch_field(o, offsetof(SumDesc, peaks2), pk + nb * sizeof(float));
+                            cb.scratch_field(o, offsetof(SumDesc, init_copy), ic);
                             if (peaks_need_zero) cb.zero.push_back({pk, nb * sizeof(float)});
                             g->vertices[vs[i]].has_init_override = false;
                         } else if (band_plan.count(vs[i])) {
-                            const size_t bpk = scratch(((M + 255) / 256) * sizeof(float));
+                            const size_t bpk = cb.scratch(((M + 255) / 256) * sizeof(float));
                             band_plan[vs[i]].blk_peaks_off = bpk;
-                            scratch_field(o, offsetof(SumDesc, peaks), bpk);
-                            if (band_plan[vs[i]].Wq) ptr_field(o, offsetof(SumDesc, rp), band_plan[vs[i]].rp_off);
+                            cb.scratch_field(o, offsetof(SumDesc, peaks), bpk);
+                            if (band_plan[vs[i]].Wq) cb.ptr_field(o, offsetof(SumDesc, rp), band_plan[vs[i]].rp_off);
                         }
                     }
                 } break;
@@ -1929,8 +1780,8 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                     }
                     off = st.put(d);
                     for (size_t i = 0; i < vs.size(); ++i) {
-                        scratch_field(off + i * sizeof(ScaleDesc), offsetof(ScaleDesc, peaks), norm_scratch[vs[i]].first);
-                        scratch_field(off + i * sizeof(ScaleDesc), offsetof(ScaleDesc, init_copy), norm_scratch[vs[i]].second);
+                        cb.scratch_field(off + i * sizeof(ScaleDesc), offsetof(ScaleDesc, peaks), norm_scratch[vs[i]].first);
+                        cb.scratch_field(off + i * sizeof(ScaleDesc), offsetof(ScaleDesc, init_copy), norm_scratch[vs[i]].second);
                     }
                 } break;
                 case F_NORMFIX: {   // the same descriptors the speculative k_sum launch got
@@ -1943,10 +1794,10 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                     size_t n_now = 0;
                     for (size_t i = 0; i < vs.size(); ++i) {
                         const size_t o = off + i * sizeof(SumDesc);
-                        ptr_field(o, offsetof(SumDesc, ins), ins_off[vs[i]]);
-                        scratch_field(o, offsetof(SumDesc, peaks), norm_scratch[vs[i]].first);
-                        if (ragged_of.count(vs[i])) scratch_field(o, offsetof(SumDesc, peaks2), norm_scratch[vs[i]].first + nb * sizeof(float));
-                        scratch_field(o, offsetof(SumDesc, init_copy), norm_scratch[vs[i]].second);
+                        cb.ptr_field(o, offsetof(SumDesc, ins), ins_off[vs[i]]);
+                        cb.scratch_field(o, offsetof(SumDesc, peaks), norm_scratch[vs[i]].first);
+                        if (ragged_of.count(vs[i])) cb.scratch_field(o, offsetof(SumDesc, peaks2), norm_scratch[vs[i]].first + nb * sizeof(float));
+                        cb.scratch_field(o, offsetof(SumDesc, init_copy), norm_scratch[vs[i]].second);
                         if (!deferred(vs[i])) ++n_now;
                     }
                     if (n_now) add_launch(fam, off, (int)n_now, 0u, lv);
@@ -1962,7 +1813,7 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                     for (size_t vi : vs) {
                         const Vertex& v = g->vertices[vi];
                         AdsrVDesc x{};
-                        x.tab.n_int = vt[vi].n_int;
+                        x.tab.n_int = vt[vi].lay.n_int;
                         x.out = g->vbuf[vi];
                         x.k = (uint32_t)g->edges[vi].size();
                         x.sr = (uint32_t)sr;
@@ -1979,12 +1830,8 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                     off = st.put(d);
                     for (size_t i = 0; i < vs.size(); ++i) {
                         const size_t o = off + i * sizeof(AdsrVDesc);
-                        ptr_field(o, offsetof(AdsrVDesc, ins), ins_off[vs[i]]);
-                        const size_t t = o + offsetof(AdsrVDesc, tab);
-                        tab_field(t, offsetof(IntervalTab, istart), vt[vs[i]], vt[vs[i]].istart_off);
-                        tab_field(t, offsetof(IntervalTab, tile_first), vt[vs[i]], vt[vs[i]].tile_first_off);
-                        tab_field(t, offsetof(IntervalTab, ivoff), vt[vs[i]], vt[vs[i]].ivoff_off);
-                        tab_field(t, offsetof(IntervalTab, voices), vt[vs[i]], vt[vs[i]].voices_off);
+                        cb.ptr_field(o, offsetof(AdsrVDesc, ins), ins_off[vs[i]]);
+                        interval_tab(o + offsetof(AdsrVDesc, tab), vt[vs[i]], false);
                     }
                 } break;
                 case F_BAND: {
@@ -2006,7 +1853,7 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                     }
                     off = st.put(d);
                     for (size_t i = 0; i < vs.size(); ++i)
-                        ptr_field(off + i * sizeof(BandDesc), offsetof(BandDesc, ins), ins_off[vs[i]]);
+                        cb.ptr_field(off + i * sizeof(BandDesc), offsetof(BandDesc, ins), ins_off[vs[i]]);
                 } break;
                 case F_BAND_SPEC: {
                     std::vector<BandSpecDesc> d;
@@ -2051,16 +1898,16 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                     for (size_t i = 0; i < vs.size(); ++i) {
                         const size_t o = off + i * sizeof(BandSpecDesc);
                         const uint32_t ns = band_plan[vs[i]].nseg;
-                        scratch_field(o, offsetof(BandSpecDesc, seg_start), scratch((size_t)ns * 16));
-                        scratch_field(o, offsetof(BandSpecDesc, seg_final), scratch((size_t)ns * 16));
-                        scratch_field(o, offsetof(BandSpecDesc, seg_flags), scratch((size_t)ns * 4));
-                        scratch_field(o, offsetof(BandSpecDesc, blk_peaks), band_plan[vs[i]].blk_peaks_off);
-                        if (band_plan[vs[i]].Wq) scratch_field(o, offsetof(BandSpecDesc, resp), band_plan[vs[i]].resp_off);
-                        scratch_field(o, offsetof(BandSpecDesc, seg_x0), scratch((size_t)ns * 8));
-                        scratch_field(o, offsetof(BandSpecDesc, jobs), scratch((size_t)ns * sizeof(BandJob)));
-                        scratch_field(o, offsetof(BandSpecDesc, seg_job), scratch((size_t)ns * 4));
-                        const size_t so = scratch(256);   // counters [0..7], verdict + fill claims on a line of their own [32..33]
-                        scratch_field(o, offsetof(BandSpecDesc, stats), so);
+                        cb.scratch_field(o, offsetof(BandSpecDesc, seg_start), cb.scratch((size_t)ns * 16));
+                        cb.scratch_field(o, offsetof(BandSpecDesc, seg_final), cb.scratch((size_t)ns * 16));
+                        cb.scratch_field(o, offsetof(BandSpecDesc, seg_flags), cb.scratch((size_t)ns * 4));
+                        cb.scratch_field(o, offsetof(BandSpecDesc, blk_peaks), band_plan[vs[i]].blk_peaks_off);
+                        if (band_plan[vs[i]].Wq) cb.scratch_field(o, offsetof(BandSpecDesc, resp), band_plan[vs[i]].resp_off);
+                        cb.scratch_field(o, offsetof(BandSpecDesc, seg_x0), cb.scratch((size_t)ns * 8));
+                        cb.scratch_field(o, offsetof(BandSpecDesc, jobs), cb.scratch((size_t)ns * sizeof(BandJob)));
+                        cb.scratch_field(o, offsetof(BandSpecDesc, seg_job), cb.scratch((size_t)ns * 4));
+                        const size_t so = cb.scratch(256);   // counters [0..7], verdict + fill claims on a line of their own [32..33]
+                        cb.scratch_field(o, offsetof(BandSpecDesc, stats), so);
                         g->band_stats_off.push_back(so);
                     }
                 } break;
@@ -2200,8 +2047,8 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                         stages_off.push_back(so);
                         for (size_t i = 0; i < piece.size(); ++i) {
                             const size_t o = so + i * sizeof(BandStageDesc);
-                            ptr_field(o, offsetof(BandStageDesc, pw), scan_plan[piece[i]].pw_off);
-                            if (chain_of.count(vi)) ptr_field(o, offsetof(BandStageDesc, pk), scan_plan[piece[i]].pk_off);
+                            cb.ptr_field(o, offsetof(BandStageDesc, pw), scan_plan[piece[i]].pw_off);
+                            if (chain_of.count(vi)) cb.ptr_field(o, offsetof(BandStageDesc, pk), scan_plan[piece[i]].pk_off);
                             cb.sync_fix.push_back({o + offsetof(BandStageDesc, sync), cb.sync_bytes});
                             cb.sync_bytes += (size_t)sp0.n_tiles * 128;   // 8 granules per tile, or 4 per wave-tile (chain)
                             if (guard_on && stage_env[i]) {
@@ -2231,7 +2078,7 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                             const bool is_chain = chain_of.count(vi) != 0;
                             const uint32_t tf = is_chain ? (uint32_t)kTileFrames : band_scan_tile_frames(sp0.nf);
                             const uint32_t n_wt = is_chain ? (uint32_t)((M + (size_t)kTileFrames - 1) / (size_t)kTileFrames) : sp0.n_tiles;
-                            audit_src.push_back({scratch((size_t)n_wt * sizeof(float)), n_wt, norm_of.count(vi) ? norm_of[vi] : vi, norm_of.count(vi) != 0, 0, tf});
+                            audit_src.push_back({cb.scratch((size_t)n_wt * sizeof(float)), n_wt, norm_of.count(vi) ? norm_of[vi] : vi, norm_of.count(vi) != 0, 0, tf});
                         }
                         if (norm_of.count(vi)) {   // the Normalize vertex behind the launch: its descriptor as k_norm1 would get it (mode 5)
                             const size_t ni = norm_of[vi];
@@ -2253,9 +2100,9 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                             nv.has_init_override = false;
                             const size_t no = st.put(std::vector<SumDesc>{y});
                             norm_desc_off.push_back(no);
-                            const size_t pk = scratch(nb * sizeof(float)), ic = scratch(2 * sizeof(float));
-                            scratch_field(no, offsetof(SumDesc, peaks), pk);
-                            scratch_field(no, offsetof(SumDesc, init_copy), ic);
+                            const size_t pk = cb.scratch(nb * sizeof(float)), ic = cb.scratch(2 * sizeof(float));
+                            cb.scratch_field(no, offsetof(SumDesc, peaks), pk);
+                            cb.scratch_field(no, offsetof(SumDesc, init_copy), ic);
                             audit_norm[ni] = {pk, ic};
                             if (peaks_need_zero) cb.zero.push_back({pk, nb * sizeof(float)});
                             cb.sync_fix.push_back({no + offsetof(SumDesc, sync), cb.sync_bytes});   // one granule per tile
@@ -2267,13 +2114,13 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                     off = st.put(d);
                     for (size_t i = 0; i < vs.size(); ++i) {
                         const size_t o = off + i * sizeof(BandScanDesc);
-                        ptr_field(o, offsetof(BandScanDesc, ins), ins_off[first_of(vs[i])]);
-                        ptr_field(o, offsetof(BandScanDesc, stages), stages_off[i]);
-                        if (norm_desc_off[i] != (size_t)-1) ptr_field(o, offsetof(BandScanDesc, norm), norm_desc_off[i]);
+                        cb.ptr_field(o, offsetof(BandScanDesc, ins), ins_off[first_of(vs[i])]);
+                        cb.ptr_field(o, offsetof(BandScanDesc, stages), stages_off[i]);
+                        if (norm_desc_off[i] != (size_t)-1) cb.ptr_field(o, offsetof(BandScanDesc, norm), norm_desc_off[i]);
                         if (guard_on) {
                             AuditSrc& as = audit_src[audit_src.size() - vs.size() + i];
                             as.desc_off = o;
-                            scratch_field(o, offsetof(BandScanDesc, noise), as.noise_off);
+                            cb.scratch_field(o, offsetof(BandScanDesc, noise), as.noise_off);
                         }
                         cb.sync_fix.push_back({o + offsetof(BandScanDesc, ticket), cb.sync_bytes});   // {tile counter, "states read"}
                         cb.sync_bytes += 64;
@@ -2292,401 +2139,6 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                                    launch_key(vs[b]) | ((uint32_t)scan_plan[first_of(vs[b])].nf << 8) | (guard_on ? 0x20000u : 0u), lv);
                         b = e2;
                     }
-                    continue;
-                }
-                case F_COMP_DETECT: {   // the five launches of the level's compressor vertices (kernels.h CompDesc)
-                    const uint32_t n_tiles = (uint32_t)((M + kCompTile - 1) / kCompTile), chunk = (n_tiles + kThreads - 1) / kThreads;
-                    std::vector<CompDesc> d;
-                    std::vector<MasterDesc> c1, c2;
-                    for (size_t vi : vs) {
-                        Vertex& v = g->vertices[vi];
-                        CompDesc x{};
-                        x.x = take_buffer(g);
-                        x.dy = reinterpret_cast<double*>(take_buffer(g));   // (an edge buffer holds one double per frame)
-                        if (!x.x || !x.dy) return fail("termdaw_amd: out of device memory for edge buffers");
-                        level_tmp.push_back(x.x);
-                        level_tmp.push_back(reinterpret_cast<float2*>(x.dy));
-                        x.out = g->vbuf[vi];
-                        x.state = &g->dstate[v.state_slot].comp;
-                        x.k = (uint32_t)g->edges[vi].size();
-                        x.term_mode = term_mode[vi];
-                        x.frames = (uint32_t)M;
-                        x.n_tiles = n_tiles;
-                        x.wet = v.wet;
-                        x.thr = (double)v.threshold_db;
-                        x.slope = 1.0 - 1.0 / (double)v.ratio;
-                        x.knee = (double)v.knee_db;
-                        x.makeup = (double)v.makeup_db;
-                        x.aR = exp(-1.0 / ((double)v.release_ms * (double)sr / 1000.0));
-                        x.aA = v.attack_ms > 0.0f ? exp(-1.0 / ((double)v.attack_ms * (double)sr / 1000.0)) : 0.0;
-                        x.oA = 1.0 - x.aA;
-                        x.pg = make_pg(v.gain, v.angle);
-                        MasterDesc y1{}, yl{};
-                        y1.n_tiles = yl.n_tiles = n_tiles;
-                        y1.chunk = yl.chunk = chunk;
-                        yl.op = 1u;
-                        for (int j = 0; j < 8; ++j) {
-                            const double e = (double)(1u << j);
-                            x.pwR[j] = pow(x.aR, (double)kCompRun * e);
-                            x.pwA[j] = pow(x.aA, (double)kCompRun * e);
-                            y1.pwc[j] = pow(x.aR, (double)kCompTile * (double)chunk * e);
-                            yl.pwc[j] = pow(x.aA, (double)kCompTile * (double)chunk * e);
-                        }
-                        y1.a_tile = pow(x.aR, (double)kCompTile);
-                        yl.a_tile = pow(x.aA, (double)kCompTile);
-                        // (a set_time since the vertex last ran: the state restarts from (0, 0) -- consumed here, like a band-pass vertex' first_override)
-                        if (!v.first_pending) {
-                            y1.init = &g->dstate[v.state_slot].comp.y1;
-                            yl.init = &g->dstate[v.state_slot].comp.yL;
-                        }
-                        v.first_pending = false;
-                        d.push_back(x);
-                        c1.push_back(y1);
-                        c2.push_back(yl);
-                    }
-                    off = st.put(d);
-                    const size_t o1 = st.put(c1), o2 = st.put(c2);
-                    for (size_t i = 0; i < vs.size(); ++i) {
-                        const size_t o = off + i * sizeof(CompDesc), tb = (size_t)n_tiles * sizeof(double);
-                        ptr_field(o, offsetof(CompDesc, ins), ins_off[vs[i]]);
-                        const size_t a1 = scratch(tb), k1 = scratch(tb), a2 = scratch(tb), k2 = scratch(tb);
-                        scratch_field(o, offsetof(CompDesc, agg1), a1);
-                        scratch_field(o, offsetof(CompDesc, carry1), k1);
-                        scratch_field(o, offsetof(CompDesc, agg2), a2);
-                        scratch_field(o, offsetof(CompDesc, carry2), k2);
-                        scratch_field(o1 + i * sizeof(MasterDesc), offsetof(MasterDesc, agg), a1);
-                        scratch_field(o1 + i * sizeof(MasterDesc), offsetof(MasterDesc, carry), k1);
-                        scratch_field(o2 + i * sizeof(MasterDesc), offsetof(MasterDesc, agg), a2);
-                        scratch_field(o2 + i * sizeof(MasterDesc), offsetof(MasterDesc, carry), k2);
-                    }
-                    add_launch(F_COMP_DETECT, off, (int)vs.size(), n_tiles, lv);
-                    add_launch(F_COMP_CARRY1, o1, (int)vs.size(), 0u, lv);
-                    add_launch(F_COMP_ENV, off, (int)vs.size(), n_tiles, lv);
-                    add_launch(F_COMP_CARRY2, o2, (int)vs.size(), 0u, lv);
-                    add_launch(F_COMP_APPLY, off, (int)vs.size(), n_tiles, lv);
-                    continue;
-                }
-                case F_GATE_DETECT: {   // the five launches of the level's gate vertices (kernels.h GateDesc)
-                    const uint32_t n_tiles = (uint32_t)((M + kGateTile - 1) / kGateTile), chunk = (n_tiles + kThreads - 1) / kThreads;
-                    std::vector<GateDesc> d;
-                    for (size_t vi : vs) {
-                        Vertex& v = g->vertices[vi];
-                        GateDesc x{};
-                        x.x = take_buffer(g);
-                        if (!x.x) return fail("termdaw_amd: out of device memory for edge buffers");
-                        level_tmp.push_back(x.x);
-                        x.out = g->vbuf[vi];
-                        x.state = &g->dstate[v.state_slot].gate;
-                        // (a set_time since the vertex last ran: the state restarts closed -- consumed here, like a compressor's)
-                        x.init = v.first_pending ? nullptr : x.state;
-                        v.first_pending = false;
-                        x.k = (uint32_t)g->edges[vi].size();
-                        x.term_mode = term_mode[vi];
-                        x.frames = (uint32_t)M;
-                        x.n_tiles = n_tiles;
-                        x.chunk = chunk;
-                        x.wet = v.wet;
-                        double c[6];
-                        gate::params(sr, v.gate_threshold_db, v.gate_hysteresis_db, v.gate_hold_ms, v.gate_attack_ms, v.gate_release_ms, v.gate_range_db, c);
-                        if (!(c[2] <= gate::kMaxHold)) return fail("gate: hold_ms is too many frames at this sample rate");
-                        x.To = c[0];
-                        x.Tc = c[1];
-                        x.cap = (uint32_t)c[2] + 1u;
-                        x.aA = c[3];
-                        x.aR = c[4];
-                        x.oA = 1.0 - x.aA;
-                        x.oR = 1.0 - x.aR;
-                        x.F = c[5];
-                        x.oF = 1.0 - x.F;
-                        x.pg = make_pg(v.gain, v.angle);
-                        d.push_back(x);
-                    }
-                    off = st.put(d);
-                    for (size_t i = 0; i < vs.size(); ++i) {
-                        const size_t o = off + i * sizeof(GateDesc), tb = (size_t)n_tiles * sizeof(double);
-                        ptr_field(o, offsetof(GateDesc, ins), ins_off[vs[i]]);
-                        scratch_field(o, offsetof(GateDesc, map), scratch(tb));
-                        scratch_field(o, offsetof(GateDesc, carry_hc), scratch((size_t)n_tiles * sizeof(uint32_t)));
-                        scratch_field(o, offsetof(GateDesc, tbits), scratch((size_t)n_tiles * kThreads));
-                        scratch_field(o, offsetof(GateDesc, aggA), scratch(tb));
-                        scratch_field(o, offsetof(GateDesc, aggB), scratch(tb));
-                        scratch_field(o, offsetof(GateDesc, carry_env), scratch(tb));
-                    }
-                    add_launch(F_GATE_DETECT, off, (int)vs.size(), n_tiles, lv);
-                    add_launch(F_GATE_CARRY_H, off, (int)vs.size(), 0u, lv);
-                    add_launch(F_GATE_ENV, off, (int)vs.size(), n_tiles, lv);
-                    add_launch(F_GATE_CARRY_ENV, off, (int)vs.size(), 0u, lv);
-                    add_launch(F_GATE_APPLY, off, (int)vs.size(), n_tiles, lv);
-                    continue;
-                }
-                case F_EQ_LOCAL: {   // the three launches of the level's EQ vertices (kernels.h EqDesc)
-                    const uint32_t n_tiles = (uint32_t)((M + kEqTile - 1) / kEqTile), chunk = (n_tiles + kThreads - 1) / kThreads;
-                    std::vector<EqDesc> d;
-                    for (size_t vi : vs) {
-                        Vertex& v = g->vertices[vi];
-                        EqDesc x{};
-                        x.x = take_buffer(g);
-                        if (!x.x) return fail("termdaw_amd: out of device memory for edge buffers");
-                        level_tmp.push_back(x.x);
-                        x.out = g->vbuf[vi];
-                        x.state = &g->dstate[v.state_slot].eq;
-                        // (a set_time since the vertex last ran: the state restarts from zero -- consumed here, like a compressor's)
-                        x.init = v.first_pending ? nullptr : x.state;
-                        v.first_pending = false;
-                        x.k = (uint32_t)g->edges[vi].size();
-                        x.term_mode = term_mode[vi];
-                        x.frames = (uint32_t)M;
-                        x.n_tiles = n_tiles;
-                        x.chunk = chunk;
-                        x.wet = v.wet;
-                        double c[5];
-                        eq::coefficients(v.eq_kind, sr, v.eq_freq, v.eq_q, v.eq_gain_db, c);
-                        x.b0 = c[0]; x.b1 = c[1]; x.b2 = c[2]; x.a1 = c[3]; x.a2 = c[4];
-                        x.c0 = x.b1 - x.a1 * x.b0;
-                        x.c1 = x.b2 - x.a2 * x.b0;
-                        eq::powers(x.a1, x.a2, kEqRun, chunk, x.pw, x.a_tile, x.pwc);
-                        x.pg = make_pg(v.gain, v.angle);
-                        d.push_back(x);
-                    }
-                    off = st.put(d);
-                    for (size_t i = 0; i < vs.size(); ++i) {
-                        const size_t o = off + i * sizeof(EqDesc), tb = (size_t)n_tiles * 4 * sizeof(double);
-                        ptr_field(o, offsetof(EqDesc, ins), ins_off[vs[i]]);
-                        scratch_field(o, offsetof(EqDesc, agg), scratch(tb));
-                        scratch_field(o, offsetof(EqDesc, carry), scratch(tb));
-                    }
-                    add_launch(F_EQ_LOCAL, off, (int)vs.size(), n_tiles, lv);
-                    add_launch(F_EQ_CARRY, off, (int)vs.size(), 0u, lv);
-                    add_launch(F_EQ_APPLY, off, (int)vs.size(), n_tiles, lv);
-                    continue;
-                }
-                case F_DELAY_APPLY: {   // the launches of the level's delay vertices (kernels.h DelayDesc)
-                    const uint32_t T = g->delay_tile;
-                    struct Plan { size_t vi; uint32_t D; delay::Tiling t; double c[4]; };
-                    std::vector<Plan> plans;
-                    for (size_t vi : vs) {
-                        const Vertex& v = g->vertices[vi];
-                        Plan p{};
-                        p.vi = vi;
-                        delay::params(sr, v.delay_ms, v.delay_feedback, v.delay_cross, p.c);
-                        p.D = (uint32_t)p.c[0];
-                        p.t = delay::tiling(M, p.D, T);
-                        if ((uint64_t)M + (uint64_t)(T + 4u) * p.D > 0xFFFF0000ull) return fail("delay: chunk too long");
-                        plans.push_back(p);
-                    }
-                    // the vertices whose chunk takes more than one tile first: k_delay_local and k_delay_carry run over those only
-                    std::stable_sort(plans.begin(), plans.end(), [](const Plan& a, const Plan& b) { return (a.t.n_tiles > 1u) > (b.t.n_tiles > 1u); });
-                    std::vector<DelayDesc> d;
-                    int n_multi = 0;
-                    uint32_t g_local = 0, g_carry = 0, g_apply = 0, g_single = 0;
-                    for (const Plan& p : plans) {
-                        Vertex& v = g->vertices[p.vi];
-                        const bool multi = p.t.n_tiles > 1u;
-                        DelayDesc x{};
-                        if (multi) {
-                            x.x = take_buffer(g);
-                            if (!x.x) return fail("termdaw_amd: out of device memory for edge buffers");
-                            level_tmp.push_back(x.x);
-                        }
-                        x.out = g->vbuf[p.vi];
-                        x.line = (double*)take_line(g, v, (size_t)p.D * 2 * sizeof(double));
-                        if (!x.line) return fail("termdaw_amd: out of device memory for a delay line");
-                        const uint64_t total = enter_chunk(v, M, false);
-                        x.k = (uint32_t)g->edges[p.vi].size();
-                        x.term_mode = term_mode[p.vi];
-                        x.frames = (uint32_t)M;
-                        x.D = p.D;
-                        x.lanes = p.t.lanes;
-                        x.T = T;
-                        x.n_tiles = p.t.n_tiles;
-                        x.pos = (uint32_t)(total % p.D);
-                        x.filled = (uint32_t)std::min<uint64_t>(total, p.D);
-                        x.seg = p.t.seg;
-                        x.chunk = p.t.chunk;
-                        x.wet = v.wet;
-                        x.gs = p.c[1];
-                        x.gc = p.c[2];
-                        delay::powers(x.gs, x.gc, T, x.chunk, x.g_tile, x.pwc);
-                        x.pg = make_pg(v.gain, v.angle);
-                        const uint32_t groups = (uint32_t)(((uint64_t)x.n_tiles * x.lanes + kThreads - 1) / kThreads);
-                        (multi ? g_apply : g_single) = std::max(multi ? g_apply : g_single, groups);
-                        if (multi) {
-                            ++n_multi;
-                            g_local = std::max(g_local, groups);
-                            const uint32_t lw = (uint32_t)kThreads / x.seg;
-                            g_carry = std::max(g_carry, (x.lanes + lw - 1) / lw);
-                        }
-                        d.push_back(x);
-                    }
-                    off = st.put(d);
-                    for (size_t i = 0; i < plans.size(); ++i) {
-                        const size_t o = off + i * sizeof(DelayDesc);
-                        ptr_field(o, offsetof(DelayDesc, ins), ins_off[plans[i].vi]);
-                        if (plans[i].t.n_tiles > 1u) {
-                            const size_t tb = (size_t)plans[i].t.n_tiles * plans[i].t.lanes * 2 * sizeof(double);
-                            scratch_field(o, offsetof(DelayDesc, agg), scratch(tb));
-                            scratch_field(o, offsetof(DelayDesc, carry), scratch(tb));
-                        }
-                    }
-                    if (n_multi) {
-                        add_launch(F_DELAY_LOCAL, off, n_multi, g_local, lv);
-                        add_launch(F_DELAY_CARRY, off, n_multi, g_carry, lv);
-                    }
-                    // (k_delay_apply's two instantiations: the multi-tile vertices stream their scratch buffer, the others run the term loop)
-                    if (n_multi) add_launch(F_DELAY_APPLY, off, n_multi, g_apply, lv);
-                    if ((size_t)n_multi < plans.size())
-                        add_launch(F_DELAY_APPLY, off + (size_t)n_multi * sizeof(DelayDesc), (int)plans.size() - n_multi, g_single | kDelaySingleBit, lv);
-                    continue;
-                }
-                case F_SAT:
-                case F_SAT1: {   // the launches of the level's saturator vertices (kernels.h SatDesc)
-                    const uint32_t F = g->sat_tile, n_tiles = (uint32_t)((M + F - 1) / F);
-                    const bool filtered = fam == F_SAT, multi = filtered && M > (size_t)kSatInlineFrames;   // (multi: k_sat_sum first)
-                    std::vector<size_t> ord(vs.begin(), vs.end());   // one k_sat launch per oversampling factor
-                    std::stable_sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return g->vertices[a].sat_oversample < g->vertices[b].sat_oversample; });
-                    std::vector<SatDesc> d;
-                    std::map<int, size_t> taps_off;
-                    for (size_t vi : ord) {
-                        Vertex& v = g->vertices[vi];
-                        double c[6];
-                        sat::params(v.sat_kind, v.sat_oversample, v.sat_drive_db, v.sat_bias, v.sat_out_db, c);
-                        SatDesc x{};
-                        if (multi) {
-                            x.x = take_buffer(g);
-                            if (!x.x) return fail("termdaw_amd: out of device memory for edge buffers");
-                            level_tmp.push_back(x.x);
-                        }
-                        x.out = g->vbuf[vi];
-                        if (filtered) {
-                            x.line = (float2*)take_line(g, v, 2 * sat::kLine * sizeof(float2));
-                            if (!x.line) return fail("termdaw_amd: out of device memory for a saturator line");
-                            x.parity = v.line.parity;
-                            x.filled = (uint32_t)std::min<uint64_t>(enter_chunk(v, M, true), sat::kLine);
-                            if (!taps_off.count(v.sat_oversample)) taps_off[v.sat_oversample] = st.put(sat::taps(v.sat_oversample));
-                        }
-                        v.first_pending = false;   // (R = 1 has no line: the set_time is consumed all the same)
-                        x.k = (uint32_t)g->edges[vi].size();
-                        x.term_mode = term_mode[vi];
-                        x.frames = (uint32_t)M;
-                        x.F = F;
-                        x.n_tiles = n_tiles;
-                        x.kind = (uint32_t)v.sat_kind;
-                        x.wet = v.wet;
-                        x.g_in = c[0];
-                        x.g_out = c[1];
-                        x.bias = (double)v.sat_bias;
-                        x.fb = c[2];
-                        x.pg = make_pg(v.gain, v.angle);
-                        d.push_back(x);
-                    }
-                    off = st.put(d);
-                    for (size_t i = 0; i < ord.size(); ++i) {
-                        const size_t o = off + i * sizeof(SatDesc);
-                        ptr_field(o, offsetof(SatDesc, ins), ins_off[ord[i]]);
-                        if (filtered) ptr_field(o, offsetof(SatDesc, taps), taps_off[g->vertices[ord[i]].sat_oversample]);
-                    }
-                    if (!filtered) {
-                        add_launch(F_SAT1, off, (int)ord.size(), 0, lv);
-                        continue;
-                    }
-                    if (multi) add_launch(F_SAT_SUM, off, (int)ord.size(), 0, lv);
-                    for (size_t i = 0; i < ord.size();) {
-                        const int R = g->vertices[ord[i]].sat_oversample;
-                        size_t j = i;
-                        while (j < ord.size() && g->vertices[ord[j]].sat_oversample == R) ++j;
-                        add_launch(F_SAT, off + i * sizeof(SatDesc), (int)(j - i), sat_aux(n_tiles, F, (uint32_t)R, !multi), lv);
-                        i = j;
-                    }
-                    continue;
-                }
-                case F_CHORUS: {   // the launches of the level's chorus vertices (kernels.h ChorusDesc)
-                    const uint32_t F = g->chorus_tile, n_tiles = (uint32_t)((M + F - 1) / F);
-                    const bool multi = M > (size_t)kSatInlineFrames;   // (multi: k_chorus_sum first)
-                    std::vector<ChorusDesc> d;
-                    for (size_t vi : vs) {
-                        Vertex& v = g->vertices[vi];
-                        double c[6];
-                        chorus::params(sr, v.chorus_voices, v.chorus_delay_ms, v.chorus_depth_ms, v.chorus_rate_hz, v.chorus_stereo, v.chorus_shape, c);
-                        ChorusDesc x{};
-                        if (multi) {
-                            x.x = take_buffer(g);
-                            if (!x.x) return fail("termdaw_amd: out of device memory for edge buffers");
-                            level_tmp.push_back(x.x);
-                        }
-                        x.out = g->vbuf[vi];
-                        x.H = (uint32_t)c[3];
-                        x.line = (float2*)take_line(g, v, 2 * (size_t)x.H * sizeof(float2));
-                        if (!x.line) return fail("termdaw_amd: out of device memory for a chorus line");
-                        x.parity = v.line.parity;
-                        x.filled = (uint32_t)std::min<uint64_t>(enter_chunk(v, M, true), x.H);
-                        x.t0 = t0;
-                        x.k = (uint32_t)g->edges[vi].size();
-                        x.term_mode = term_mode[vi];
-                        x.frames = (uint32_t)M;
-                        x.F = F;
-                        x.n_tiles = n_tiles;
-                        x.voices = (uint32_t)v.chorus_voices;
-                        x.shape = (uint32_t)v.chorus_shape;
-                        x.wet = v.wet;
-                        x.D0 = c[0];
-                        x.A = c[1];
-                        x.f = c[2];
-                        x.stereo = (double)v.chorus_stereo;
-                        x.inv_v = 1.0 / (double)v.chorus_voices;
-                        x.pg = make_pg(v.gain, v.angle);
-                        d.push_back(x);
-                    }
-                    off = st.put(d);
-                    for (size_t i = 0; i < vs.size(); ++i) ptr_field(off + i * sizeof(ChorusDesc), offsetof(ChorusDesc, ins), ins_off[vs[i]]);
-                    if (multi) add_launch(F_CHORUS_SUM, off, (int)vs.size(), 0, lv);
-                    add_launch(F_CHORUS, off, (int)vs.size(), chorus_aux(n_tiles, !multi), lv);
-                    continue;
-                }
-                case F_REVERB: {   // the launches of the level's reverb vertices (kernels.h ReverbDesc)
-                    std::vector<ReverbDesc> d;
-                    for (size_t vi : vs) {
-                        Vertex& v = g->vertices[vi];
-                        double c[reverb::kParams];
-                        reverb::params(sr, v.reverb_room, v.reverb_damp, v.reverb_width, v.reverb_size, c);
-                        ReverbDesc x{};
-                        x.x = take_buffer(g);
-                        if (!x.x) return fail("termdaw_amd: out of device memory for edge buffers");
-                        level_tmp.push_back(x.x);
-                        x.out = g->vbuf[vi];
-                        uint32_t at = 16, shortest = 0xFFFFFFFFu;
-                        for (int i = 0; i < reverb::kLines; ++i) {
-                            x.len[i] = (uint32_t)c[7 + i];
-                            x.off[i] = at;
-                            at += x.len[i];
-                            shortest = std::min(shortest, x.len[i]);
-                        }
-                        x.state = (double*)take_line(g, v, at * sizeof(double));
-                        if (!x.state) return fail("termdaw_amd: out of device memory for a reverb vertex' lines");
-                        const uint64_t total = enter_chunk(v, M, false);
-                        for (int i = 0; i < reverb::kLines; ++i) {
-                            const uint32_t D = x.len[i];
-                            x.pos[i] = (uint32_t)(total % D);
-                            x.skip[i] = total < D ? (uint32_t)(D - total) : 0u;
-                        }
-                        x.fresh = total == 0 ? 1u : 0u;
-                        x.k = (uint32_t)g->edges[vi].size();
-                        x.term_mode = term_mode[vi];
-                        x.frames = (uint32_t)M;
-                        x.B = reverb::window(shortest, g->reverb_block);
-                        x.wet = v.wet;
-                        x.g = c[0];
-                        x.d1 = c[1];
-                        x.d2 = c[2];
-                        x.w1 = c[3];
-                        x.w2 = c[4];
-                        reverb::powers(x.d1, x.B / 64u, x.pw);
-                        x.pg = make_pg(v.gain, v.angle);
-                        d.push_back(x);
-                    }
-                    off = st.put(d);
-                    for (size_t i = 0; i < vs.size(); ++i) ptr_field(off + i * sizeof(ReverbDesc), offsetof(ReverbDesc, ins), ins_off[vs[i]]);
-                    add_launch(F_REVERB_SUM, off, (int)vs.size(), 0, lv);
-                    add_launch(F_REVERB, off, (int)vs.size(), g->reverb_form, lv);
                     continue;
                 }
                 default: continue;
@@ -2788,8 +2240,8 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
             else cb.launches.erase(cb.launches.begin() + (long)at);
         }
         for (size_t q = 0; q < probe_src.size(); ++q) {
-            if (inl) ptr_field(o, offsetof(BandScanDesc, nz_probe), probe_desc_off[q]);
-            else scratch_field(o, offsetof(BandScanDesc, nz_extra) + q * sizeof(const float*), probe_src[q].second);
+            if (inl) cb.ptr_field(o, offsetof(BandScanDesc, nz_probe), probe_desc_off[q]);
+            else cb.scratch_field(o, offsetof(BandScanDesc, nz_extra) + q * sizeof(const float*), probe_src[q].second);
             const float g2 = (float)probe_g2[q];
             memcpy(&st.b[o + offsetof(BandScanDesc, nz_xg2) + q * sizeof(float)], &g2, 4);
         }
@@ -2821,14 +2273,14 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
         const size_t ao = st.put(ad);
         for (size_t i = 0; i < audit_src.size(); ++i) {
             const size_t o = ao + i * sizeof(AuditDesc);
-            scratch_field(o, offsetof(AuditDesc, noise), audit_src[i].noise_off);
+            cb.scratch_field(o, offsetof(AuditDesc, noise), audit_src[i].noise_off);
             const long nz = audit_src[i].fused ? -1 : down[audit_src[i].from].norm;   // (a fused Normalize vertex: 1 / max already applied by the launch)
             if (nz >= 0) {
                 const auto it = audit_norm.find((size_t)nz);
                 if (it == audit_norm.end()) return fail("termdaw_amd: internal: the guard lost a Normalize vertex");
-                scratch_field(o, offsetof(AuditDesc, peaks), it->second.first);
+                cb.scratch_field(o, offsetof(AuditDesc, peaks), it->second.first);
                 // (a scan pass measures against scan_max, graph.rs:222-237: what matters there is the recorded peak's relative error)
-                scratch_field(o, offsetof(AuditDesc, init_copy), it->second.second + (is_scan ? sizeof(float) : 0));
+                cb.scratch_field(o, offsetof(AuditDesc, init_copy), it->second.second + (is_scan ? sizeof(float) : 0));
             }
         }
         AuditHead hd{};
@@ -2837,7 +2289,7 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
         hd.thr2 = (float)(guard_thr * guard_thr);
         hd.host_word = g->guard.d_word;
         const size_t ho = st.put(std::vector<AuditHead>{hd});
-        ptr_field(ho, offsetof(AuditHead, descs), ao);
+        cb.ptr_field(ho, offsetof(AuditHead, descs), ao);
         add_launch(F_AUDIT, ho, 1, 0u, g->n_levels + 1);
     }
     const auto tp2 = std::chrono::steady_clock::now();
@@ -2869,33 +2321,21 @@ size_t desc_size(int fam) {
         case F_QUANT: return sizeof(QuantDesc);
         case F_AUDIT: return sizeof(AuditHead);
         case F_STEMS: return sizeof(StemDesc);
-        case F_COMP_DETECT:
-        case F_COMP_ENV:
-        case F_COMP_APPLY: return sizeof(CompDesc);
         case F_COMP_CARRY1:
-        case F_COMP_CARRY2: return sizeof(MasterDesc);
-        case F_EQ_LOCAL:
-        case F_EQ_CARRY:
-        case F_EQ_APPLY: return sizeof(EqDesc);
-        case F_DELAY_LOCAL:
-        case F_DELAY_CARRY:
-        case F_DELAY_APPLY: return sizeof(DelayDesc);
-        case F_SAT_SUM:
-        case F_SAT:
-        case F_SAT1: return sizeof(SatDesc);
-        case F_CHORUS_SUM:
-        case F_CHORUS: return sizeof(ChorusDesc);
-        case F_REVERB_SUM:
-        case F_REVERB: return sizeof(ReverbDesc);
-        case F_GATE_DETECT:
-        case F_GATE_CARRY_H:
-        case F_GATE_ENV:
-        case F_GATE_CARRY_ENV:
-        case F_GATE_APPLY: return sizeof(GateDesc);
-        default: return 0;
+        case F_COMP_CARRY2: return sizeof(MasterDesc);   // (k_master_carry, inside the compressor's families)
+        default: {
+            const FxKind* fx = fx_of_family(fam);
+            return fx ? fx->desc_bytes : 0;
+        }
     }
 }
 bool is_band_family(int fam) { return fam == F_BAND_SPEC || fam == F_BAND_FIX || fam == F_BAND_FILL; }
-bool is_delay_family(int fam) { return fam == F_DELAY_LOCAL || fam == F_DELAY_CARRY || fam == F_DELAY_APPLY; }
+bool is_delay_family(int fam) { const FxKind* fx = fx_of_family(fam); return fx && fx->kind == K_DELAY; }
 
 }  // namespace tde
+
+// The effect kinds' table and lowering functions: a file of its own, one translation unit with this one.  The host sources are
+// linked by explicit lists -- the Makefile's objects, the SOURCES of the stand-alone sanitizer programs in tests/ -- and every such
+// list that names compile.cpp, an older checkout's too, builds the effect kinds with it.  (What only that file uses sits in
+// namespace tde::fxk.)
+#include "compile_fx.cpp"

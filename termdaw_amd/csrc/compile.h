@@ -1,6 +1,7 @@
 // compile.h -- what the host compiler (compile.cpp) and the device side of the engine (engine.cpp) share.
 #pragma once
 #include <chrono>
+#include <map>
 #include <string>
 #include <vector>
 
@@ -34,6 +35,65 @@ size_t desc_size(int fam);
 bool is_band_family(int fam);
 bool is_delay_family(int fam);
 double ms_between(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b);
+tdk::PanGain make_pg(float gain, float angle);           // a vertex' pan / gain as its kernel's epilogue applies it (sample.rs:98-109)
+
+// ---- compile_fx.cpp: the effect kinds (compressor, EQ, delay, saturator, chorus, reverb, gate) ----
+// What lowering the vertices of one effect kind at one level needs of compile_chunk, and the steps every kind's lowering
+// shares.  The kinds' own functions (lower_comp ..) keep what is theirs: coefficients, tiling, scratch, launches.
+struct FxLevel {
+    td_graph* g;
+    ChunkBuild& cb;
+    size_t M, sr, bl;     // frames of the chunk, sample rate, reference block length
+    uint64_t t0;          // the chunk's first frame on the timeline
+    int lv;
+    bool is_scan;
+    int fam;              // the family the level's loop has reached (FxKind::family of the vertices handed over)
+    std::map<size_t, size_t>& ins_off;        // vertex -> staging offset of its input terms
+    std::map<size_t, uint32_t>& term_mode;    // vertex -> TERMS_* of those
+    std::vector<float2*>& level_tmp;          // scratch edge buffers, given back behind the level
+
+    float2* tmp_buffer();   // an edge buffer for this level only; nullptr: failed (g_error set)
+    // the fields every effect descriptor has, under the same names
+    template <class D>
+    void head(D& x, size_t vi) {
+        const Vertex& v = g->vertices[vi];
+        x.out = g->vbuf[vi];
+        x.k = (uint32_t)g->edges[vi].size();
+        x.term_mode = term_mode[vi];
+        x.frames = (uint32_t)M;
+        x.wet = v.wet;
+        x.pg = make_pg(v.gain, v.angle);
+    }
+    // the descriptors of vertices `vs` into the arena, each pointed at its vertex' input terms; returns their offset
+    template <class D>
+    size_t put(const std::vector<D>& d, const std::vector<size_t>& vs) {
+        const size_t off = cb.st->put(d);
+        for (size_t i = 0; i < vs.size(); ++i) cb.ptr_field(off + i * sizeof(D), offsetof(D, ins), ins_off[vs[i]]);
+        return off;
+    }
+    void add_launch(int family, size_t off, int n, uint32_t aux) {
+        cb.launches.push_back({family, off, n, aux, lv, (uint32_t)M, (uint32_t)bl, is_scan ? 1 : 0});
+    }
+};
+
+// One row per effect kind (the table: compile_fx.cpp), in the order of their families in `Family` -- the order a level launches them in.
+constexpr double kNoStaticGain = -1.0;   // FxKind::through: no estimate is carried through this vertex
+struct FxKind {
+    Kind kind;
+    const char* name;       // as in "<name>: chunk too long"
+    int first_family;       // the kind's families are [first_family, first_family + n_families)
+    int n_families;
+    size_t desc_bytes;      // of the descriptors its launches take (the compressor's two carries aside: MasterDesc)
+    bool (*fits)(const td_graph* g, const Vertex& v, size_t M);   // a chunk of M frames is within the kernels' index ranges
+    int (*family)(const Vertex& v);                               // the family a vertex is lowered at; nullptr: first_family (all but the saturator)
+    // the factor the guard's estimate goes through a vertex at, its own pan / gain aside (1 when dry); kNoStaticGain: none
+    double (*through)(const Vertex& v, size_t sr);
+    // descriptors + launches of the level's vertices of one family (FxLevel::fam), called where the level's loop reaches it; 0: failed
+    int (*lower)(FxLevel& L, std::vector<size_t>& vs);
+    int family_of(const Vertex& v) const { return family ? family(v) : first_family; }
+};
+const FxKind* fx_kind(Kind k);          // nullptr: not an effect kind
+const FxKind* fx_of_family(int fam);    // nullptr: not an effect kind's family
 
 // ---- engine.cpp: the device memory the compiler hands out addresses of ----
 int upload_tables(td_graph* g, TableCache& tc, const Staging& tmp);   // a vertex' event tables -> its device buffer (queued on the graph's stream)

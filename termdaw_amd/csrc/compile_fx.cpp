@@ -1,0 +1,486 @@
+// compile_fx.cpp -- the effect kinds of the host compiler (compile.h FxKind / FxLevel): compressor, EQ, delay, saturator,
+// chorus, reverb, gate.  One table row per kind -- its chunk limit, the family its launches start at, the factor the guard
+// carries an estimate through it at -- and one function per kind that lowers a level's vertices of that kind to descriptors
+// and launches.  compile_chunk enumerates the kinds through the table only.  Like compile.cpp: no HIP call.  Not an object of its
+// own: compile.cpp includes this file at its end, so no build list changes with it.
+#include "chorus_math.h"
+#include "compile.h"
+#include "delay_math.h"
+#include "eq_math.h"
+#include "gate_math.h"
+#include "reverb_math.h"
+#include "sat_math.h"
+
+#include <math.h>
+
+#include <algorithm>
+
+using namespace tdk;
+
+namespace tde {
+
+float2* FxLevel::tmp_buffer() {
+    float2* b = take_buffer(g);
+    if (!b) { fail("termdaw_amd: out of device memory for edge buffers"); return nullptr; }
+    level_tmp.push_back(b);
+    return b;
+}
+
+namespace fxk {   // (compile.cpp includes this file: what is only used here keeps a scope of its own)
+
+// A delay, saturator, chorus or reverb vertex enters a chunk of M frames: a set_time since the vertex last ran is consumed here
+// (the block restarts from zero, like an EQ's state), the books move on behind the chunk -- `alternates`: the launch writes the other
+// half of the line, which the next one reads.  Returns the frames run up to the chunk (Vertex::Line::total as the chunk finds it).
+static uint64_t enter_chunk(Vertex& v, size_t M, bool alternates) {
+    if (v.first_pending) v.line.total = 0;
+    v.first_pending = false;
+    const uint64_t total = v.line.total;
+    v.line.total += M;
+    if (alternates) v.line.parity ^= 1u;
+    return total;
+}
+
+// ---- compressor: five launches (kernels.h CompDesc) ----
+static int lower_comp(FxLevel& L, std::vector<size_t>& vs) {
+    td_graph* g = L.g;
+    const size_t M = L.M, sr = L.sr;
+    const uint32_t n_tiles = (uint32_t)((M + kCompTile - 1) / kCompTile), chunk = (n_tiles + kThreads - 1) / kThreads;
+    std::vector<CompDesc> d;
+    std::vector<MasterDesc> c1, c2;
+    for (size_t vi : vs) {
+        Vertex& v = g->vertices[vi];
+        CompDesc x{};
+        x.x = L.tmp_buffer();
+        x.dy = reinterpret_cast<double*>(L.tmp_buffer());   // (an edge buffer holds one double per frame)
+        if (!x.x || !x.dy) return 0;
+        L.head(x, vi);
+        x.state = &g->dstate[v.state_slot].comp;
+        x.n_tiles = n_tiles;
+        x.thr = (double)v.threshold_db;
+        x.slope = 1.0 - 1.0 / (double)v.ratio;
+        x.knee = (double)v.knee_db;
+        x.makeup = (double)v.makeup_db;
+        x.aR = exp(-1.0 / ((double)v.release_ms * (double)sr / 1000.0));
+        x.aA = v.attack_ms > 0.0f ? exp(-1.0 / ((double)v.attack_ms * (double)sr / 1000.0)) : 0.0;
+        x.oA = 1.0 - x.aA;
+        MasterDesc y1{}, yl{};
+        y1.n_tiles = yl.n_tiles = n_tiles;
+        y1.chunk = yl.chunk = chunk;
+        yl.op = 1u;
+        for (int j = 0; j < 8; ++j) {
+            const double e = (double)(1u << j);
+            x.pwR[j] = pow(x.aR, (double)kCompRun * e);
+            x.pwA[j] = pow(x.aA, (double)kCompRun * e);
+            y1.pwc[j] = pow(x.aR, (double)kCompTile * (double)chunk * e);
+            yl.pwc[j] = pow(x.aA, (double)kCompTile * (double)chunk * e);
+        }
+        y1.a_tile = pow(x.aR, (double)kCompTile);
+        yl.a_tile = pow(x.aA, (double)kCompTile);
+        // (a set_time since the vertex last ran: the state restarts from (0, 0) -- consumed here, like a band-pass vertex' first_override)
+        if (!v.first_pending) {
+            y1.init = &g->dstate[v.state_slot].comp.y1;
+            yl.init = &g->dstate[v.state_slot].comp.yL;
+        }
+        v.first_pending = false;
+        d.push_back(x);
+        c1.push_back(y1);
+        c2.push_back(yl);
+    }
+    const size_t off = L.put(d, vs);
+    const size_t o1 = L.cb.st->put(c1), o2 = L.cb.st->put(c2);
+    for (size_t i = 0; i < vs.size(); ++i) {
+        const size_t o = off + i * sizeof(CompDesc), tb = (size_t)n_tiles * sizeof(double);
+        const size_t a1 = L.cb.scratch(tb), k1 = L.cb.scratch(tb), a2 = L.cb.scratch(tb), k2 = L.cb.scratch(tb);
+        L.cb.scratch_field(o, offsetof(CompDesc, agg1), a1);
+        L.cb.scratch_field(o, offsetof(CompDesc, carry1), k1);
+        L.cb.scratch_field(o, offsetof(CompDesc, agg2), a2);
+        L.cb.scratch_field(o, offsetof(CompDesc, carry2), k2);
+        L.cb.scratch_field(o1 + i * sizeof(MasterDesc), offsetof(MasterDesc, agg), a1);
+        L.cb.scratch_field(o1 + i * sizeof(MasterDesc), offsetof(MasterDesc, carry), k1);
+        L.cb.scratch_field(o2 + i * sizeof(MasterDesc), offsetof(MasterDesc, agg), a2);
+        L.cb.scratch_field(o2 + i * sizeof(MasterDesc), offsetof(MasterDesc, carry), k2);
+    }
+    L.add_launch(F_COMP_DETECT, off, (int)vs.size(), n_tiles);
+    L.add_launch(F_COMP_CARRY1, o1, (int)vs.size(), 0u);
+    L.add_launch(F_COMP_ENV, off, (int)vs.size(), n_tiles);
+    L.add_launch(F_COMP_CARRY2, o2, (int)vs.size(), 0u);
+    L.add_launch(F_COMP_APPLY, off, (int)vs.size(), n_tiles);
+    return 1;
+}
+
+// ---- EQ: three launches (kernels.h EqDesc) ----
+static int lower_eq(FxLevel& L, std::vector<size_t>& vs) {
+    td_graph* g = L.g;
+    const uint32_t n_tiles = (uint32_t)((L.M + kEqTile - 1) / kEqTile), chunk = (n_tiles + kThreads - 1) / kThreads;
+    std::vector<EqDesc> d;
+    for (size_t vi : vs) {
+        Vertex& v = g->vertices[vi];
+        EqDesc x{};
+        x.x = L.tmp_buffer();
+        if (!x.x) return 0;
+        L.head(x, vi);
+        x.state = &g->dstate[v.state_slot].eq;
+        // (a set_time since the vertex last ran: the state restarts from zero -- consumed here, like a compressor's)
+        x.init = v.first_pending ? nullptr : x.state;
+        v.first_pending = false;
+        x.n_tiles = n_tiles;
+        x.chunk = chunk;
+        double c[5];
+        eq::coefficients(v.eq_kind, L.sr, v.eq_freq, v.eq_q, v.eq_gain_db, c);
+        x.b0 = c[0]; x.b1 = c[1]; x.b2 = c[2]; x.a1 = c[3]; x.a2 = c[4];
+        x.c0 = x.b1 - x.a1 * x.b0;
+        x.c1 = x.b2 - x.a2 * x.b0;
+        eq::powers(x.a1, x.a2, kEqRun, chunk, x.pw, x.a_tile, x.pwc);
+        d.push_back(x);
+    }
+    const size_t off = L.put(d, vs);
+    for (size_t i = 0; i < vs.size(); ++i) {
+        const size_t o = off + i * sizeof(EqDesc), tb = (size_t)n_tiles * 4 * sizeof(double);
+        L.cb.scratch_field(o, offsetof(EqDesc, agg), L.cb.scratch(tb));
+        L.cb.scratch_field(o, offsetof(EqDesc, carry), L.cb.scratch(tb));
+    }
+    L.add_launch(F_EQ_LOCAL, off, (int)vs.size(), n_tiles);
+    L.add_launch(F_EQ_CARRY, off, (int)vs.size(), 0u);
+    L.add_launch(F_EQ_APPLY, off, (int)vs.size(), n_tiles);
+    return 1;
+}
+
+// ---- delay (kernels.h DelayDesc) ----
+static int lower_delay(FxLevel& L, std::vector<size_t>& vs) {
+    td_graph* g = L.g;
+    const size_t M = L.M;
+    const uint32_t T = g->delay_tile;
+    struct Plan { size_t vi; uint32_t D; delay::Tiling t; double c[4]; };
+    std::vector<Plan> plans;
+    for (size_t vi : vs) {
+        const Vertex& v = g->vertices[vi];
+        Plan p{};
+        p.vi = vi;
+        delay::params(L.sr, v.delay_ms, v.delay_feedback, v.delay_cross, p.c);
+        p.D = (uint32_t)p.c[0];
+        p.t = delay::tiling(M, p.D, T);
+        if ((uint64_t)M + (uint64_t)(T + 4u) * p.D > 0xFFFF0000ull) return fail("delay: chunk too long");
+        plans.push_back(p);
+    }
+    // the vertices whose chunk takes more than one tile first: k_delay_local and k_delay_carry run over those only
+    std::stable_sort(plans.begin(), plans.end(), [](const Plan& a, const Plan& b) { return (a.t.n_tiles > 1u) > (b.t.n_tiles > 1u); });
+    std::vector<DelayDesc> d;
+    std::vector<size_t> ord;
+    int n_multi = 0;
+    uint32_t g_local = 0, g_carry = 0, g_apply = 0, g_single = 0;
+    for (const Plan& p : plans) {
+        Vertex& v = g->vertices[p.vi];
+        const bool multi = p.t.n_tiles > 1u;
+        DelayDesc x{};
+        if (multi && !(x.x = L.tmp_buffer())) return 0;
+        L.head(x, p.vi);
+        x.line = (double*)take_line(g, v, (size_t)p.D * 2 * sizeof(double));
+        if (!x.line) return fail("termdaw_amd: out of device memory for a delay line");
+        const uint64_t total = enter_chunk(v, M, false);
+        x.D = p.D;
+        x.lanes = p.t.lanes;
+        x.T = T;
+        x.n_tiles = p.t.n_tiles;
+        x.pos = (uint32_t)(total % p.D);
+        x.filled = (uint32_t)std::min<uint64_t>(total, p.D);
+        x.seg = p.t.seg;
+        x.chunk = p.t.chunk;
+        x.gs = p.c[1];
+        x.gc = p.c[2];
+        delay::powers(x.gs, x.gc, T, x.chunk, x.g_tile, x.pwc);
+        const uint32_t groups = (uint32_t)(((uint64_t)x.n_tiles * x.lanes + kThreads - 1) / kThreads);
+        (multi ? g_apply : g_single) = std::max(multi ? g_apply : g_single, groups);
+        if (multi) {
+            ++n_multi;
+            g_local = std::max(g_local, groups);
+            const uint32_t lw = (uint32_t)kThreads / x.seg;
+            g_carry = std::max(g_carry, (x.lanes + lw - 1) / lw);
+        }
+        d.push_back(x);
+        ord.push_back(p.vi);
+    }
+    const size_t off = L.put(d, ord);
+    for (size_t i = 0; i < plans.size(); ++i) {
+        if (plans[i].t.n_tiles <= 1u) continue;
+        const size_t o = off + i * sizeof(DelayDesc), tb = (size_t)plans[i].t.n_tiles * plans[i].t.lanes * 2 * sizeof(double);
+        L.cb.scratch_field(o, offsetof(DelayDesc, agg), L.cb.scratch(tb));
+        L.cb.scratch_field(o, offsetof(DelayDesc, carry), L.cb.scratch(tb));
+    }
+    if (n_multi) {
+        L.add_launch(F_DELAY_LOCAL, off, n_multi, g_local);
+        L.add_launch(F_DELAY_CARRY, off, n_multi, g_carry);
+    }
+    // (k_delay_apply's two instantiations: the multi-tile vertices stream their scratch buffer, the others run the term loop)
+    if (n_multi) L.add_launch(F_DELAY_APPLY, off, n_multi, g_apply);
+    if ((size_t)n_multi < plans.size())
+        L.add_launch(F_DELAY_APPLY, off + (size_t)n_multi * sizeof(DelayDesc), (int)plans.size() - n_multi, g_single | kDelaySingleBit);
+    return 1;
+}
+
+// ---- saturator (kernels.h SatDesc): the vertices with R > 1 (L.fam == F_SAT_SUM) or those with R = 1 (F_SAT1) ----
+static int lower_sat(FxLevel& L, std::vector<size_t>& vs) {
+    td_graph* g = L.g;
+    const size_t M = L.M;
+    const uint32_t F = g->sat_tile, n_tiles = (uint32_t)((M + F - 1) / F);
+    const bool filtered = L.fam != F_SAT1, multi = filtered && M > (size_t)kSatInlineFrames;   // (multi: k_sat_sum first)
+    std::vector<size_t> ord(vs.begin(), vs.end());   // one k_sat launch per oversampling factor
+    std::stable_sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return g->vertices[a].sat_oversample < g->vertices[b].sat_oversample; });
+    std::vector<SatDesc> d;
+    std::map<int, size_t> taps_off;
+    for (size_t vi : ord) {
+        Vertex& v = g->vertices[vi];
+        double c[6];
+        sat::params(v.sat_kind, v.sat_oversample, v.sat_drive_db, v.sat_bias, v.sat_out_db, c);
+        SatDesc x{};
+        if (multi && !(x.x = L.tmp_buffer())) return 0;
+        L.head(x, vi);
+        if (filtered) {
+            x.line = (float2*)take_line(g, v, 2 * sat::kLine * sizeof(float2));
+            if (!x.line) return fail("termdaw_amd: out of device memory for a saturator line");
+            x.parity = v.line.parity;
+            x.filled = (uint32_t)std::min<uint64_t>(enter_chunk(v, M, true), sat::kLine);
+            if (!taps_off.count(v.sat_oversample)) taps_off[v.sat_oversample] = L.cb.st->put(sat::taps(v.sat_oversample));
+        }
+        v.first_pending = false;   // (R = 1 has no line: the set_time is consumed all the same)
+        x.F = F;
+        x.n_tiles = n_tiles;
+        x.kind = (uint32_t)v.sat_kind;
+        x.g_in = c[0];
+        x.g_out = c[1];
+        x.bias = (double)v.sat_bias;
+        x.fb = c[2];
+        d.push_back(x);
+    }
+    const size_t off = L.put(d, ord);
+    if (!filtered) {
+        L.add_launch(F_SAT1, off, (int)ord.size(), 0);
+        return 1;
+    }
+    for (size_t i = 0; i < ord.size(); ++i)
+        L.cb.ptr_field(off + i * sizeof(SatDesc), offsetof(SatDesc, taps), taps_off[g->vertices[ord[i]].sat_oversample]);
+    if (multi) L.add_launch(F_SAT_SUM, off, (int)ord.size(), 0);
+    for (size_t i = 0; i < ord.size();) {
+        const int R = g->vertices[ord[i]].sat_oversample;
+        size_t j = i;
+        while (j < ord.size() && g->vertices[ord[j]].sat_oversample == R) ++j;
+        L.add_launch(F_SAT, off + i * sizeof(SatDesc), (int)(j - i), sat_aux(n_tiles, F, (uint32_t)R, !multi));
+        i = j;
+    }
+    return 1;
+}
+
+// ---- chorus (kernels.h ChorusDesc) ----
+static int lower_chorus(FxLevel& L, std::vector<size_t>& vs) {
+    td_graph* g = L.g;
+    const size_t M = L.M;
+    const uint32_t F = g->chorus_tile, n_tiles = (uint32_t)((M + F - 1) / F);
+    const bool multi = M > (size_t)kSatInlineFrames;   // (multi: k_chorus_sum first)
+    std::vector<ChorusDesc> d;
+    for (size_t vi : vs) {
+        Vertex& v = g->vertices[vi];
+        double c[6];
+        chorus::params(L.sr, v.chorus_voices, v.chorus_delay_ms, v.chorus_depth_ms, v.chorus_rate_hz, v.chorus_stereo, v.chorus_shape, c);
+        ChorusDesc x{};
+        if (multi && !(x.x = L.tmp_buffer())) return 0;
+        L.head(x, vi);
+        x.H = (uint32_t)c[3];
+        x.line = (float2*)take_line(g, v, 2 * (size_t)x.H * sizeof(float2));
+        if (!x.line) return fail("termdaw_amd: out of device memory for a chorus line");
+        x.parity = v.line.parity;
+        x.filled = (uint32_t)std::min<uint64_t>(enter_chunk(v, M, true), x.H);
+        x.t0 = L.t0;
+        x.F = F;
+        x.n_tiles = n_tiles;
+        x.voices = (uint32_t)v.chorus_voices;
+        x.shape = (uint32_t)v.chorus_shape;
+        x.D0 = c[0];
+        x.A = c[1];
+        x.f = c[2];
+        x.stereo = (double)v.chorus_stereo;
+        x.inv_v = 1.0 / (double)v.chorus_voices;
+        d.push_back(x);
+    }
+    const size_t off = L.put(d, vs);
+    if (multi) L.add_launch(F_CHORUS_SUM, off, (int)vs.size(), 0);
+    L.add_launch(F_CHORUS, off, (int)vs.size(), chorus_aux(n_tiles, !multi));
+    return 1;
+}
+
+// ---- reverb (kernels.h ReverbDesc) ----
+static int lower_reverb(FxLevel& L, std::vector<size_t>& vs) {
+    td_graph* g = L.g;
+    std::vector<ReverbDesc> d;
+    for (size_t vi : vs) {
+        Vertex& v = g->vertices[vi];
+        double c[reverb::kParams];
+        reverb::params(L.sr, v.reverb_room, v.reverb_damp, v.reverb_width, v.reverb_size, c);
+        ReverbDesc x{};
+        x.x = L.tmp_buffer();
+        if (!x.x) return 0;
+        L.head(x, vi);
+        uint32_t at = 16, shortest = 0xFFFFFFFFu;
+        for (int i = 0; i < reverb::kLines; ++i) {
+            x.len[i] = (uint32_t)c[7 + i];
+            x.off[i] = at;
+            at += x.len[i];
+            shortest = std::min(shortest, x.len[i]);
+        }
+        x.state = (double*)take_line(g, v, at * sizeof(double));
+        if (!x.state) return fail("termdaw_amd: out of device memory for a reverb vertex' lines");
+        const uint64_t total = enter_chunk(v, L.M, false);
+        for (int i = 0; i < reverb::kLines; ++i) {
+            const uint32_t D = x.len[i];
+            x.pos[i] = (uint32_t)(total % D);
+            x.skip[i] = total < D ? (uint32_t)(D - total) : 0u;
+        }
+        x.fresh = total == 0 ? 1u : 0u;
+        x.B = reverb::window(shortest, g->reverb_block);
+        x.g = c[0];
+        x.d1 = c[1];
+        x.d2 = c[2];
+        x.w1 = c[3];
+        x.w2 = c[4];
+        reverb::powers(x.d1, x.B / 64u, x.pw);
+        d.push_back(x);
+    }
+    const size_t off = L.put(d, vs);
+    L.add_launch(F_REVERB_SUM, off, (int)vs.size(), 0);
+    L.add_launch(F_REVERB, off, (int)vs.size(), g->reverb_form);
+    return 1;
+}
+
+// ---- gate: five launches (kernels.h GateDesc) ----
+static int lower_gate(FxLevel& L, std::vector<size_t>& vs) {
+    td_graph* g = L.g;
+    const uint32_t n_tiles = (uint32_t)((L.M + kGateTile - 1) / kGateTile), chunk = (n_tiles + kThreads - 1) / kThreads;
+    std::vector<GateDesc> d;
+    for (size_t vi : vs) {
+        Vertex& v = g->vertices[vi];
+        GateDesc x{};
+        x.x = L.tmp_buffer();
+        if (!x.x) return 0;
+        L.head(x, vi);
+        x.state = &g->dstate[v.state_slot].gate;
+        // (a set_time since the vertex last ran: the state restarts closed -- consumed here, like a compressor's)
+        x.init = v.first_pending ? nullptr : x.state;
+        v.first_pending = false;
+        x.n_tiles = n_tiles;
+        x.chunk = chunk;
+        double c[6];
+        gate::params(L.sr, v.gate_threshold_db, v.gate_hysteresis_db, v.gate_hold_ms, v.gate_attack_ms, v.gate_release_ms, v.gate_range_db, c);
+        if (!(c[2] <= gate::kMaxHold)) return fail("gate: hold_ms is too many frames at this sample rate");
+        x.To = c[0];
+        x.Tc = c[1];
+        x.cap = (uint32_t)c[2] + 1u;
+        x.aA = c[3];
+        x.aR = c[4];
+        x.oA = 1.0 - x.aA;
+        x.oR = 1.0 - x.aR;
+        x.F = c[5];
+        x.oF = 1.0 - x.F;
+        d.push_back(x);
+    }
+    const size_t off = L.put(d, vs);
+    for (size_t i = 0; i < vs.size(); ++i) {
+        const size_t o = off + i * sizeof(GateDesc), tb = (size_t)n_tiles * sizeof(double);
+        L.cb.scratch_field(o, offsetof(GateDesc, map), L.cb.scratch(tb));
+        L.cb.scratch_field(o, offsetof(GateDesc, carry_hc), L.cb.scratch((size_t)n_tiles * sizeof(uint32_t)));
+        L.cb.scratch_field(o, offsetof(GateDesc, tbits), L.cb.scratch((size_t)n_tiles * kThreads));
+        L.cb.scratch_field(o, offsetof(GateDesc, aggA), L.cb.scratch(tb));
+        L.cb.scratch_field(o, offsetof(GateDesc, aggB), L.cb.scratch(tb));
+        L.cb.scratch_field(o, offsetof(GateDesc, carry_env), L.cb.scratch(tb));
+    }
+    L.add_launch(F_GATE_DETECT, off, (int)vs.size(), n_tiles);
+    L.add_launch(F_GATE_CARRY_H, off, (int)vs.size(), 0u);
+    L.add_launch(F_GATE_ENV, off, (int)vs.size(), n_tiles);
+    L.add_launch(F_GATE_CARRY_ENV, off, (int)vs.size(), 0u);
+    L.add_launch(F_GATE_APPLY, off, (int)vs.size(), n_tiles);
+    return 1;
+}
+
+// ---- the table ----
+// fits: the largest chunk the kind's kernels index (32-bit frames; the line kinds keep room for their look-back, the tiled
+// ones for the tile count packed into a launch's aux)
+static bool fits_scan(const td_graph*, const Vertex&, size_t M) { return M <= 0xFFFF0000ull; }
+static bool fits_line(const td_graph*, const Vertex&, size_t M) { return M <= 0xF0000000ull; }
+static bool fits_sat(const td_graph* g, const Vertex&, size_t M) { return M <= 0xF0000000ull && (M + g->sat_tile - 1) / g->sat_tile < 0x100000ull; }
+static bool fits_chorus(const td_graph* g, const Vertex&, size_t M) { return M <= 0xF0000000ull && (M + g->chorus_tile - 1) / g->chorus_tile < 0x100000ull; }
+
+static int family_sat(const Vertex& v) { return v.sat_oversample == 1 ? F_SAT1 : F_SAT_SUM; }
+
+// through: a dry vertex is the Sum it compiles to (factor 1); `lerp`: the estimate goes through (1 - wet) x + wet f(x) at
+// (1 - wet) + wet H, H the L2 gain (or Lipschitz bound) of f
+static bool dry(const Vertex& v) { return v.wet < 0.0001f; }
+static double lerp_gain(const Vertex& v, double H) { return (1.0 - (double)v.wet) + (double)v.wet * H; }
+// a compressor is no static gain: no estimate is carried through it -- everything upstream takes the exact forms, as upstream
+// of a stem
+static double through_comp(const Vertex&, size_t) { return kNoStaticGain; }
+// ... and so is a gate, unless it is dry
+static double through_gate(const Vertex& v, size_t) { return dry(v) ? 1.0 : kNoStaticGain; }
+// an EQ is linear and time-invariant: Hmax of its biquad
+static double through_eq(const Vertex& v, size_t sr) {
+    if (dry(v)) return 1.0;
+    double c[5];
+    eq::coefficients(v.eq_kind, sr, v.eq_freq, v.eq_q, v.eq_gain_db, c);
+    return lerp_gain(v, eq::hmax(c));
+}
+// a delay too: out = x + wet (echoes), the echo path's L2 gain is Hecho = 1 / (1 - feedback)
+static double through_delay(const Vertex& v, size_t sr) {
+    if (dry(v)) return 1.0;
+    double c[4];
+    delay::params(sr, v.delay_ms, v.delay_feedback, v.delay_cross, c);
+    return 1.0 + (double)v.wet * c[3];
+}
+// a saturator's shaper is Lipschitz: Hsat = g_out Hdown Lf g_in Hup
+static double through_sat(const Vertex& v, size_t) {
+    if (dry(v)) return 1.0;
+    double c[6];
+    sat::params(v.sat_kind, v.sat_oversample, v.sat_drive_db, v.sat_bias, v.sat_out_db, c);
+    return lerp_gain(v, c[5]);
+}
+// a chorus is linear (and time-varying): Hch, an L2 bound of the modulated four-point read
+static double through_chorus(const Vertex& v, size_t) { return dry(v) ? 1.0 : lerp_gain(v, chorus::kHch); }
+// a reverb is linear and time-invariant: Hrev, the product of its stages' largest gains
+static double through_reverb(const Vertex& v, size_t sr) {
+    if (dry(v)) return 1.0;
+    double c[reverb::kParams];
+    reverb::params(sr, v.reverb_room, v.reverb_damp, v.reverb_width, v.reverb_size, c);
+    return lerp_gain(v, c[5]);
+}
+
+// (a function's static: these sources also go through the HIP compiler, whose device pass would want a copy of a namespace-scope
+// constant -- and of the host functions it points to.)  A row's family count is the distance to the next row's first family, so
+// the rows cover the effect families of `Family` without gap or overlap as long as they stand in its order:
+constexpr int kFxKinds = 7;
+static_assert(F_COMP_DETECT < F_EQ_LOCAL && F_EQ_LOCAL < F_DELAY_LOCAL && F_DELAY_LOCAL < F_SAT_SUM && F_SAT_SUM < F_CHORUS_SUM &&
+              F_CHORUS_SUM < F_REVERB_SUM && F_REVERB_SUM < F_GATE_DETECT && F_GATE_DETECT < F_COUNT,
+              "the rows of the effect kinds' table stand in the order of their families");
+static const FxKind* table() {
+    static const FxKind rows[kFxKinds] = {
+        {K_COMPRESSOR, "compressor", F_COMP_DETECT, F_EQ_LOCAL - F_COMP_DETECT, sizeof(CompDesc), fits_scan, nullptr, through_comp, lower_comp},
+        {K_EQ, "eq", F_EQ_LOCAL, F_DELAY_LOCAL - F_EQ_LOCAL, sizeof(EqDesc), fits_scan, nullptr, through_eq, lower_eq},
+        {K_DELAY, "delay", F_DELAY_LOCAL, F_SAT_SUM - F_DELAY_LOCAL, sizeof(DelayDesc), fits_line, nullptr, through_delay, lower_delay},
+        {K_SATURATOR, "saturator", F_SAT_SUM, F_CHORUS_SUM - F_SAT_SUM, sizeof(SatDesc), fits_sat, family_sat, through_sat, lower_sat},
+        {K_CHORUS, "chorus", F_CHORUS_SUM, F_REVERB_SUM - F_CHORUS_SUM, sizeof(ChorusDesc), fits_chorus, nullptr, through_chorus, lower_chorus},
+        {K_REVERB, "reverb", F_REVERB_SUM, F_GATE_DETECT - F_REVERB_SUM, sizeof(ReverbDesc), fits_line, nullptr, through_reverb, lower_reverb},
+        {K_GATE, "gate", F_GATE_DETECT, F_COUNT - F_GATE_DETECT, sizeof(GateDesc), fits_scan, nullptr, through_gate, lower_gate},
+    };
+    return rows;
+}
+
+}  // namespace fxk
+
+const FxKind* fx_kind(Kind k) {
+    const FxKind* rows = fxk::table();
+    for (int i = 0; i < fxk::kFxKinds; ++i)
+        if (rows[i].kind == k) return &rows[i];
+    return nullptr;
+}
+const FxKind* fx_of_family(int fam) {
+    const FxKind* rows = fxk::table();
+    for (int i = 0; i < fxk::kFxKinds; ++i)
+        if (fam >= rows[i].first_family && fam < rows[i].first_family + rows[i].n_families) return &rows[i];
+    return nullptr;
+}
+
+}  // namespace tde

@@ -82,6 +82,21 @@ struct SineNote { float note, vel; };
 struct SynthNote { float note, vel, env_t, rel_t, hz; };   // hz = 440 * 2^((note - 69) / 12), extensions.rs:503
 struct Voice3 { float t, vel, rel; };
 
+// Where the compiled tables of an event-driven vertex stand in its table buffer: byte offsets and counts, as the compile_*
+// functions of compile.cpp leave them.  Kept by the TableCache, handed to the descriptor pass as part of a VTables.
+struct TableLayout {
+    size_t hits_off = 0;
+    uint32_t n_hits = 0;
+    size_t istart_off = 0, ivoff_off = 0, voices_off = 0, tile_first_off = 0, tile_order_off = 0;
+    uint32_t n_int = 0;
+    // a probed affine Synth vertex (sine_mode 2): the RAW interval table beside the affine one -- k_sine_probe evaluates the
+    // reference's own form, which reads (hz, vel, env_t, rel_t) records
+    size_t raw_istart_off = 0, raw_ivoff_off = 0, raw_voices_off = 0, raw_tile_first_off = 0;
+    uint32_t raw_n_int = 0;
+    size_t probe_v_off = 0;   // (a probed sine / Synth vertex) k_sine_probe's per-sample voice ranges in the raw table (ProbeDesc::ranges)
+    float hz_max = 0.0f;      // (Synth) the largest |hz| of any voice record of the tables (NaN: +inf): SynthDesc::small_args
+};
+
 // Compiled event tables of one event-driven vertex (hit lists / interval tables), resident in a device buffer of their
 // own together with the key they were compiled from.  A chunk whose key is byte-identical -- same events, same
 // FlowwBank cursor, same chunk shape, same carried vertex state at the chunk start -- reuses the tables without
@@ -94,15 +109,7 @@ struct TableCache {
     size_t cap = 0;
     hipEvent_t copied = nullptr;
     bool inflight = false;
-    // table layout: offsets into d
-    size_t hits_off = 0, istart_off = 0, ivoff_off = 0, voices_off = 0, tile_first_off = 0, tile_order_off = 0;
-    uint32_t n_hits = 0, n_int = 0;
-    // a probed affine Synth vertex (sine_mode 2): the RAW interval table beside the affine one -- k_sine_probe evaluates the
-    // reference's own form, which reads (hz, vel, env_t, rel_t) records
-    size_t raw_istart_off = 0, raw_ivoff_off = 0, raw_voices_off = 0, raw_tile_first_off = 0;
-    uint32_t raw_n_int = 0;
-    size_t probe_v_off = 0;   // ... and k_sine_probe's per-sample voice ranges (ProbeDesc::ranges)
-    float hz_max = 0.0f;      // (Synth) the tables' largest |hz|: SynthDesc::small_args
+    TableLayout lay;                 // where the tables stand in d
 };
 
 struct Vertex {
@@ -163,8 +170,7 @@ struct Vertex {
     bool peak_known = false;
     std::shared_ptr<TableCache> tables;   // event-driven kinds only (shared_ptr: Vertex stays copyable)
     bool has_input() const {
-        return kind == K_SUM || kind == K_NORMALIZE || kind == K_ADSR || kind == K_BAND_PASS || kind == K_COMPRESSOR || kind == K_EQ ||
-               kind == K_DELAY || kind == K_SATURATOR || kind == K_CHORUS || kind == K_REVERB || kind == K_GATE;
+        return kind == K_SUM || kind == K_NORMALIZE || (kind >= K_ADSR && kind < K_COUNT);   // (Adsr, band-pass and the effect kinds)
     }
 };
 
@@ -296,6 +302,12 @@ struct ChunkBuild {
     std::vector<Launch> launches;
     size_t n_graphs = 0;
     bool one_grid_sources = true;   // every graph compiled in has engine option "one_grid_sources" set (submit_chunk: k_sources)
+    // Descriptor patching.  scratch: a range of the device-only region behind the uploaded part, in 256-byte steps;
+    // ptr_field / scratch_field: a pointer field of a staged descriptor that submit_chunk points at a staging offset / at a
+    // scratch range once the device addresses are known.
+    size_t scratch(size_t n) { const size_t o = scratch_bytes; scratch_bytes += (n + 255) & ~(size_t)255; return o; }
+    void ptr_field(size_t desc_off, size_t field_off, size_t staging_off) { table_fix.push_back({desc_off + field_off, staging_off}); }
+    void scratch_field(size_t desc_off, size_t field_off, size_t s_off) { scratch_fix.push_back({desc_off + field_off, s_off}); }
     void clear() {
         st->b.clear();
         scratch_bytes = 0;
