@@ -365,7 +365,7 @@ int td_reverb_params(size_t sr, float room, float damp, float width, float size,
  * hold_ms [0, 2000], attack_ms [0, 1000], release_ms [1, 10000], range_db [-120, 0].  `wet` is clamped to [0, 1].
  * Under "band_mode" 2 / "sine_mode" 2 everything upstream of a gate vertex takes the exact forms (no estimate is carried
  * through a gain that depends on the signal); vertices downstream are unaffected.
- * Not part of the vertex: an external key input (ducking), lookahead. */
+ * An external key input (ducking): td_graph_connect_key below.  Not part of the vertex: lookahead. */
 int td_graph_add_gate(td_graph* g, const char* name, float gain, float angle, float wet, float threshold_db, float hysteresis_db,
                       float hold_ms, float attack_ms, float release_ms, float range_db);
 /* Host only, no GPU: the gate vertex' constants at rate sr, exactly the doubles the engine uses -- out[0 .. 5] = To, Tc, H, aA,
@@ -373,6 +373,26 @@ int td_graph_add_gate(td_graph* g, const char* name, float gain, float angle, fl
 int td_gate_params(size_t sr, float threshold_db, float hysteresis_db, float hold_ms, float attack_ms, float release_ms,
                    float range_db, double out[6]);
 int td_graph_connect(td_graph* g, const char* a, const char* b);          /* graph.rs:80-96 (+58-78) */
+/* A key edge (sidechain) from any vertex `a` to a compressor or gate vertex `b` -- THIS ENGINE'S OWN, like the two vertices.  A
+ * vertex with at least one key edge takes its LEVEL from the sum of its key sources; everything else is as without: it processes
+ * the sum of its inputs, carries the same state, keeps its wet mix, pan and gain.
+ *   The key frames (kl[n], kr[n]) are the f32 sum of the key sources' outputs, each with its own pan and gain applied, summed in
+ *   connect_key order by the arithmetic of sum_inputs (extensions.rs:310-319, as every input sum here); a duplicate key edge is
+ *   summed twice.  They are summed per chunk / block pull: nothing new is carried.
+ *   With one or more key edges, step 1 of the compressor (the level s[n], and through it d[n]) and steps 1 and 2 of the gate (the
+ *   level and its class against To / Tc) read (kl, kr) where they read (l, r).  The NaN / infinite-frame rule is applied to the
+ *   key frame: such a key frame stays out of the compressor's state (d[n] = 0), or forces nothing in the gate's step 2.  Every
+ *   later step is unchanged and acts on the summed INPUT: a non-finite input frame comes out as what IEEE makes of it.
+ *   A key is not an input: td_graph_check's "output receives no inputs" is unchanged, and a keyed vertex without inputs
+ *   processes silence.  A dry vertex (wet < 0.0001) ignores its key edges: its output is bit for bit that of the same vertex
+ *   without them.
+ * Returns 0 (td_last_error) for an unknown name (td_graph_connect's messages); when `b` is not a compressor or gate vertex
+ * ("connect_key: <b> takes no key input"); when the edge would close a loop.  The loop test of td_graph_connect and of
+ * td_graph_connect_key runs over the union of input and key edges.  td_graph_reset clears key edges, as it clears edges.  A key
+ * source is rendered like an input, also when only the key edge reaches it.
+ * Under "band_mode" 2 / "sine_mode" 2 everything upstream of a key edge into a vertex that is not dry takes the exact forms (the
+ * level decides a gain: no estimate is carried through it); a dry keyed vertex contributes nothing. */
+int td_graph_connect_key(td_graph* g, const char* a, const char* b);
 int td_graph_set_output(td_graph* g, const char* vertex);                 /* graph.rs:141-148 */
 int td_graph_check(const td_graph* g);                                    /* check_graph graph.rs:150-174 */
 void td_graph_set_time(td_graph* g, size_t time);                         /* graph.rs:123-128 */

@@ -80,6 +80,7 @@ SIGNATURES = {
     "td_gate_params": (_i32, [_sz, _f32, _f32, _f32, _f32, _f32, _f32, C.POINTER(C.c_double)]),
     "td_reverb_params": (_i32, [_sz, _f32, _f32, _f32, _f32, C.POINTER(C.c_double)]),
     "td_graph_connect": (_i32, [_vp, _cp, _cp]),
+    "td_graph_connect_key": (_i32, [_vp, _cp, _cp]),
     "td_graph_set_output": (_i32, [_vp, _cp]),
     "td_graph_check": (_i32, [_vp]),
     "td_graph_set_time": (None, [_vp, _sz]),
@@ -586,6 +587,11 @@ class Graph:
 
     def connect(self, a, b):
         return bool(lib().td_graph_connect(self.h, a.encode(), b.encode()))
+
+    def connect_key(self, a, b):
+        """A key edge (sidechain) from any vertex a to a compressor or gate vertex b: b takes its level from the sum of its key
+        sources and goes on processing the sum of its inputs (include/termdaw_amd.h td_graph_connect_key).  False: last_error()."""
+        return bool(lib().td_graph_connect_key(self.h, a.encode(), b.encode()))
 
     def set_output(self, name):
         return bool(lib().td_graph_set_output(self.h, name.encode()))

@@ -676,8 +676,11 @@ void build_plan(td_graph* g) {
         while (!stack.empty()) {
             auto& top = stack.back();
             const size_t v = top.first;
-            if (top.second < g->edges[v].size()) {
-                const size_t u = g->edges[v][top.second++];
+            // (a vertex' key edges after its input edges: a key source is computed like an input, also when nothing else reaches it)
+            const size_t n_in = g->edges[v].size();
+            if (top.second < n_in + g->key_edges[v].size()) {
+                const size_t at = top.second++;
+                const size_t u = at < n_in ? g->edges[v][at] : g->key_edges[v][at - n_in];
                 if (!seen[u]) {
                     seen[u] = 1;
                     stack.push_back({u, 0});
@@ -685,6 +688,7 @@ void build_plan(td_graph* g) {
             } else {
                 int lv = 0;
                 for (size_t u : g->edges[v]) lv = std::max(lv, g->level[u] + 1);
+                for (size_t u : g->key_edges[v]) lv = std::max(lv, g->level[u] + 1);
                 g->level[v] = lv;
                 g->n_levels = std::max(g->n_levels, lv + 1);
                 g->order.push_back(v);
@@ -828,9 +832,27 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
     g->band_stats_off.clear();
     g->band_stats_base = nullptr;
     g->guard.chunk_audited = false;
+    // `cons`: who reads a vertex' frames, through an input edge or a key edge (td_graph_connect_key) -- what every rule below
+    // that elides or releases a source's frames counts; `live_key`: the vertex is the key source of a vertex that is not dry
     std::vector<std::vector<size_t>> cons(nv);
-    for (size_t vi : g->order)
+    std::vector<char> live_key(nv, 0);
+    bool any_key = false;
+    for (size_t vi : g->order) {
         for (size_t u : g->edges[vi]) cons[u].push_back(vi);
+        for (size_t u : g->key_edges[vi]) {
+            cons[u].push_back(vi);
+            any_key = true;
+            if (!(g->vertices[vi].wet < 0.0001f)) live_key[u] = 1;
+        }
+    }
+    // ... and who reads them as an input: what the guard carries its estimate along
+    std::vector<std::vector<size_t>> in_cons_store;
+    if (any_key) {
+        in_cons_store.resize(nv);
+        for (size_t vi : g->order)
+            for (size_t u : g->edges[vi]) in_cons_store[u].push_back(vi);
+    }
+    const std::vector<std::vector<size_t>>& in_cons = any_key ? in_cons_store : cons;
     // ---- tapped vertices: the output and the stems (td_graph_set_stems).  Their frames must exist in full, pan and gain
     // applied, when the render's last launches read them: no read-through, no chain membership, no pre-sum folding, no fused
     // Normalize behind them, no buffer release.  (The exception: a stem on a sample_loop source stays inlined -- the stem
@@ -852,8 +874,10 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
         std::vector<char> reach(nv, 0);
         reach[(size_t)g->output_vertex] = 1;
         for (size_t k = g->order.size(); k-- > 0;)
-            if (reach[g->order[k]])
+            if (reach[g->order[k]]) {
                 for (size_t u : g->edges[g->order[k]]) reach[u] = 1;
+                for (size_t u : g->key_edges[g->order[k]]) reach[u] = 1;
+            }
         for (size_t sv : g->stems)
             if (!reach[sv]) g->stem_taps |= 32u;
     }
@@ -895,6 +919,10 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
             // a stem: the guard carries nothing to it -- everything upstream takes the exact kernels; the output
             // too, when a stem sits downstream of it (it then has consumers in the plan, and they lead to stems only)
             if (stem_only(u)) { down[u] = PathGain{0.0, -2}; continue; }
+            // the key source of a vertex that is not dry: the level decides a gain, no estimate is carried through it --
+            // everything upstream takes the exact forms, as upstream of a stem or a compressor; a dry keyed
+            // vertex ignores its key and contributes nothing
+            if (live_key[u]) { down[u] = PathGain{0.0, -2}; continue; }
             if ((long)u == g->output_vertex) {
                 down[u] = PathGain{1.0, -1};
                 for (size_t w : cons[u])
@@ -904,7 +932,7 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
             double sum = 0.0;
             long nz = -1;
             bool first = true;
-            for (size_t w : cons[u]) {   // (a duplicate edge is listed twice: the term is summed twice)
+            for (size_t w : in_cons[u]) {   // (a duplicate edge is listed twice: the term is summed twice)
                 const Vertex& wv = g->vertices[w];
                 long through = down[w].norm;
                 if (through == -2) { nz = -2; break; }
@@ -1021,8 +1049,10 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
     if (!ensure_buffers(g, M)) return 0;
     g->vbuf.assign(nv, nullptr);
     std::vector<int> last_use(nv, -1);
-    for (size_t vi : g->order)
+    for (size_t vi : g->order) {
         for (size_t u : g->edges[vi]) last_use[u] = std::max(last_use[u], g->level[vi]);
+        for (size_t u : g->key_edges[vi]) last_use[u] = std::max(last_use[u], g->level[vi]);
+    }
 
     // source inlining: a sample_loop vertex that is not the output is gathered directly by its consumers
     // (all of them sum their inputs through the same term loop), so its edge buffer is never materialised
@@ -1430,6 +1460,8 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
         // input term tables: an edge buffer, or an inlined sample_loop source gathered by the consumer
         std::map<size_t, size_t> ins_off;
         std::map<size_t, uint32_t> term_mode;
+        std::map<size_t, size_t> key_off;        // a keyed compressor / gate vertex that is not dry -> staging offset of its key terms
+        std::map<size_t, uint32_t> key_mode;     // ... and TERMS_* of those
         for (size_t vl : by_level[lv]) {
             if (!g->vertices[vl].has_input() || inlined[vl] || fused_norm.count(vl)) continue;   // (an inlined vertex' terms belong to its consumers)
             // (the launch of a band-pass chain sits at its last vertex and evaluates the first vertex' input terms)
@@ -1478,6 +1510,22 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                                      : (all_loop16 ? TERMS_ALL_LOOP16 : (all_loop ? TERMS_ALL_LOOP32 : TERMS_MIXED));
             ins_off[vi] = st.put(ins);
             if (!adsr_through.empty()) term_mode[vi] = ins.size() == 1 ? TERMS_ADSR1 : TERMS_WITH_ADSR;
+            // the key terms (td_graph_connect_key), next to the input terms: kinds 0 .. 4 -- a key source has the keyed vertex
+            // among its consumers, so it is never read through as an envelope, never inside a chain launch, never a folded pre-sum
+            if (!g->key_edges[vi].empty() && !(g->vertices[vi].wet < 0.0001f)) {
+                std::vector<InTerm> kin;
+                bool k_edge = true, k_loop = true, k_loop16 = true;
+                for (size_t u : g->key_edges[vi]) {
+                    const InTerm t = plain_term(u);
+                    k_edge = k_edge && t.kind == 0;
+                    k_loop = k_loop && t.kind == 1;
+                    k_loop16 = k_loop16 && t.kind == 3;
+                    kin.push_back(t);
+                }
+                key_mode[vi] = k_edge ? (kin.size() < 8 ? TERMS_EDGE_FEW : TERMS_ALL_EDGE)
+                                      : (k_loop16 ? TERMS_ALL_LOOP16 : (k_loop ? TERMS_ALL_LOOP32 : TERMS_MIXED));
+                key_off[vi] = st.put(kin);
+            }
             for (const auto& th : adsr_through) {   // the vertex' descriptor, as k_adsr would get it
                 const size_t a = th.second;
                 const Vertex& av = g->vertices[a];
@@ -1551,7 +1599,7 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
             // kind's first family -- or, for the saturator, F_SAT1 as well (R = 1), so that one kind may be lowered at two families of
             // its row, each with its own vertices; lower_sat tells them apart by FxLevel::fam
             if (const FxKind* fx = fx_of_family(fam)) {
-                FxLevel fl{g, cb, M, sr, bl, t0, lv, is_scan, fam, ins_off, term_mode, level_tmp};
+                FxLevel fl{g, cb, M, sr, bl, t0, lv, is_scan, fam, ins_off, term_mode, key_off, key_mode, level_tmp};
                 if (!fx->lower(fl, vs)) return 0;
                 continue;
             }

@@ -50,6 +50,8 @@ struct FxLevel {
     int fam;              // the family the level's loop has reached (FxKind::family of the vertices handed over)
     std::map<size_t, size_t>& ins_off;        // vertex -> staging offset of its input terms
     std::map<size_t, uint32_t>& term_mode;    // vertex -> TERMS_* of those
+    std::map<size_t, size_t>& key_off;        // keyed compressor / gate vertex (not dry) -> staging offset of its key terms
+    std::map<size_t, uint32_t>& key_mode;     // ... -> TERMS_* of those
     std::vector<float2*>& level_tmp;          // scratch edge buffers, given back behind the level
 
     float2* tmp_buffer();   // an edge buffer for this level only; nullptr: failed (g_error set)
@@ -70,6 +72,22 @@ struct FxLevel {
         const size_t off = cb.st->put(d);
         for (size_t i = 0; i < vs.size(); ++i) cb.ptr_field(off + i * sizeof(D), offsetof(D, ins), ins_off[vs[i]]);
         return off;
+    }
+    // the vertices of `vs` without a key first, the keyed ones behind them, each group in the order it came in; returns how many
+    // have no key.  The keyed forms of the detect (and the gate's env) launch run over the second group only, so the unkeyed
+    // launches keep the code, registers and occupancy they have without any key in the graph.
+    size_t keyed_last(std::vector<size_t>& vs) const {
+        std::vector<size_t> a, b;
+        for (size_t vi : vs) (key_off.count(vi) ? b : a).push_back(vi);
+        vs = a;
+        vs.insert(vs.end(), b.begin(), b.end());
+        return a.size();
+    }
+    // a keyed descriptor's key fields (CompDesc / GateDesc; key_ins is pointed at key_off[vi] once the descriptors are staged)
+    template <class D>
+    void key_fields(D& x, size_t vi) {
+        x.key_k = (uint32_t)g->key_edges[vi].size();
+        x.key_term_mode = key_mode[vi];
     }
     void add_launch(int family, size_t off, int n, uint32_t aux) {
         cb.launches.push_back({family, off, n, aux, lv, (uint32_t)M, (uint32_t)bl, is_scan ? 1 : 0});

@@ -47,6 +47,7 @@ static int lower_comp(FxLevel& L, std::vector<size_t>& vs) {
     const uint32_t n_tiles = (uint32_t)((M + kCompTile - 1) / kCompTile), chunk = (n_tiles + kThreads - 1) / kThreads;
     std::vector<CompDesc> d;
     std::vector<MasterDesc> c1, c2;
+    const size_t n_plain = L.keyed_last(vs);   // (the keyed vertices behind the others: k_comp_detect<true> runs over those)
     for (size_t vi : vs) {
         Vertex& v = g->vertices[vi];
         CompDesc x{};
@@ -54,6 +55,7 @@ static int lower_comp(FxLevel& L, std::vector<size_t>& vs) {
         x.dy = reinterpret_cast<double*>(L.tmp_buffer());   // (an edge buffer holds one double per frame)
         if (!x.x || !x.dy) return 0;
         L.head(x, vi);
+        if (L.key_off.count(vi)) L.key_fields(x, vi);
         x.state = &g->dstate[v.state_slot].comp;
         x.n_tiles = n_tiles;
         x.thr = (double)v.threshold_db;
@@ -99,8 +101,10 @@ static int lower_comp(FxLevel& L, std::vector<size_t>& vs) {
         L.cb.scratch_field(o1 + i * sizeof(MasterDesc), offsetof(MasterDesc, carry), k1);
         L.cb.scratch_field(o2 + i * sizeof(MasterDesc), offsetof(MasterDesc, agg), a2);
         L.cb.scratch_field(o2 + i * sizeof(MasterDesc), offsetof(MasterDesc, carry), k2);
+        if (i >= n_plain) L.cb.ptr_field(o, offsetof(CompDesc, key_ins), L.key_off[vs[i]]);
     }
-    L.add_launch(F_COMP_DETECT, off, (int)vs.size(), n_tiles);
+    if (n_plain) L.add_launch(F_COMP_DETECT, off, (int)n_plain, n_tiles);
+    if (n_plain < vs.size()) L.add_launch(F_COMP_DETECT, off + n_plain * sizeof(CompDesc), (int)(vs.size() - n_plain), n_tiles | kKeyedBit);
     L.add_launch(F_COMP_CARRY1, o1, (int)vs.size(), 0u);
     L.add_launch(F_COMP_ENV, off, (int)vs.size(), n_tiles);
     L.add_launch(F_COMP_CARRY2, o2, (int)vs.size(), 0u);
@@ -354,12 +358,14 @@ static int lower_gate(FxLevel& L, std::vector<size_t>& vs) {
     td_graph* g = L.g;
     const uint32_t n_tiles = (uint32_t)((L.M + kGateTile - 1) / kGateTile), chunk = (n_tiles + kThreads - 1) / kThreads;
     std::vector<GateDesc> d;
+    const size_t n_plain = L.keyed_last(vs);   // (the keyed vertices behind the others: k_gate_detect<true> / k_gate_env<true> run over those)
     for (size_t vi : vs) {
         Vertex& v = g->vertices[vi];
         GateDesc x{};
         x.x = L.tmp_buffer();
         if (!x.x) return 0;
         L.head(x, vi);
+        if (L.key_off.count(vi)) L.key_fields(x, vi);
         x.state = &g->dstate[v.state_slot].gate;
         // (a set_time since the vertex last ran: the state restarts closed -- consumed here, like a compressor's)
         x.init = v.first_pending ? nullptr : x.state;
@@ -389,10 +395,18 @@ static int lower_gate(FxLevel& L, std::vector<size_t>& vs) {
         L.cb.scratch_field(o, offsetof(GateDesc, aggA), L.cb.scratch(tb));
         L.cb.scratch_field(o, offsetof(GateDesc, aggB), L.cb.scratch(tb));
         L.cb.scratch_field(o, offsetof(GateDesc, carry_env), L.cb.scratch(tb));
+        if (i >= n_plain) {   // a keyed vertex: its key terms, and the lanes' class words between detect and env
+            L.cb.ptr_field(o, offsetof(GateDesc, key_ins), L.key_off[vs[i]]);
+            L.cb.scratch_field(o, offsetof(GateDesc, cls), L.cb.scratch((size_t)n_tiles * kThreads * sizeof(uint16_t)));
+        }
     }
-    L.add_launch(F_GATE_DETECT, off, (int)vs.size(), n_tiles);
+    const size_t off_k = off + n_plain * sizeof(GateDesc);
+    const int n_keyed = (int)(vs.size() - n_plain);
+    if (n_plain) L.add_launch(F_GATE_DETECT, off, (int)n_plain, n_tiles);
+    if (n_keyed) L.add_launch(F_GATE_DETECT, off_k, n_keyed, n_tiles | kKeyedBit);
     L.add_launch(F_GATE_CARRY_H, off, (int)vs.size(), 0u);
-    L.add_launch(F_GATE_ENV, off, (int)vs.size(), n_tiles);
+    if (n_plain) L.add_launch(F_GATE_ENV, off, (int)n_plain, n_tiles);
+    if (n_keyed) L.add_launch(F_GATE_ENV, off_k, n_keyed, n_tiles | kKeyedBit);
     L.add_launch(F_GATE_CARRY_ENV, off, (int)vs.size(), 0u);
     L.add_launch(F_GATE_APPLY, off, (int)vs.size(), n_tiles);
     return 1;

@@ -932,7 +932,10 @@ static int submit_chunk(Arena& ar, ChunkBuild& cb, hipStream_t stream, ProfCtx& 
                 case F_QUANT: launch_quantise((const QuantDesc*)d, L.n, L.M, s); break;
                 case F_AUDIT: launch_band_audit((const AuditHead*)d, L.n, s); break;
                 case F_STEMS: launch_stems((const StemDesc*)d, L.n, L.M, s); break;   // (prepare_render has checked it exists)
-                case F_COMP_DETECT: launch_comp_detect((const CompDesc*)d, L.n, L.aux, s); break;   // (likewise)
+                case F_COMP_DETECT:   // (likewise; the keyed form: prepare_render has checked it exists where a key edge asks for it)
+                    if (L.aux & kKeyedBit) launch_comp_detect_keyed((const CompDesc*)d, L.n, L.aux & ~kKeyedBit, s);
+                    else launch_comp_detect((const CompDesc*)d, L.n, L.aux, s);
+                    break;
                 case F_COMP_CARRY1:
                 case F_COMP_CARRY2: launch_master_carry((const MasterDesc*)d, L.n, s); break;
                 case F_COMP_ENV: launch_comp_env((const CompDesc*)d, L.n, L.aux, s); break;
@@ -949,9 +952,15 @@ static int submit_chunk(Arena& ar, ChunkBuild& cb, hipStream_t stream, ProfCtx& 
                 case F_CHORUS_SUM: launch_chorus_sum((const ChorusDesc*)d, L.n, L.M, s); break;   // (likewise)
                 case F_REVERB_SUM: launch_reverb_sum((const ReverbDesc*)d, L.n, L.M, s); break;   // (likewise)
                 case F_REVERB: launch_reverb((const ReverbDesc*)d, L.n, L.aux, s); break;
-                case F_GATE_DETECT: launch_gate_detect((const GateDesc*)d, L.n, L.aux, s); break;   // (likewise)
+                case F_GATE_DETECT:   // (likewise)
+                    if (L.aux & kKeyedBit) launch_gate_detect_keyed((const GateDesc*)d, L.n, L.aux & ~kKeyedBit, s);
+                    else launch_gate_detect((const GateDesc*)d, L.n, L.aux, s);
+                    break;
                 case F_GATE_CARRY_H: launch_gate_carry((const GateDesc*)d, L.n, false, s); break;
-                case F_GATE_ENV: launch_gate_env((const GateDesc*)d, L.n, L.aux, s); break;
+                case F_GATE_ENV:
+                    if (L.aux & kKeyedBit) launch_gate_env_keyed((const GateDesc*)d, L.n, L.aux & ~kKeyedBit, s);
+                    else launch_gate_env((const GateDesc*)d, L.n, L.aux, s);
+                    break;
                 case F_GATE_CARRY_ENV: launch_gate_carry((const GateDesc*)d, L.n, true, s); break;
                 case F_GATE_APPLY: launch_gate_apply((const GateDesc*)d, L.n, L.aux, s); break;
                 case F_CHORUS: launch_chorus((const ChorusDesc*)d, L.n, L.aux & 0xFFFFFu, L.M, (L.aux & kChorusTermsBit) != 0u, s); break;
@@ -1024,9 +1033,12 @@ static int prepare_stems(td_graph* g, size_t frames, size_t word) {
 static bool output_read(const td_graph* g) {
     for (size_t sv : g->stems)
         if ((long)sv == g->output_vertex) return true;
-    for (size_t vi : g->order)
+    for (size_t vi : g->order) {
         for (size_t u : g->edges[vi])
             if ((long)u == g->output_vertex) return true;
+        for (size_t u : g->key_edges[vi])
+            if ((long)u == g->output_vertex) return true;
+    }
     return false;
 }
 static int prepare_render(td_graph* g, size_t n_blocks, int bits, bool want_pcm, RenderPlan* rp) {
@@ -1048,6 +1060,12 @@ static int prepare_render(td_graph* g, size_t n_blocks, int bits, bool want_pcm,
             for (size_t vi : g->order)
                 if (g->vertices[vi].kind == f.kind && !(g->vertices[vi].wet < 0.0001f))
                     return fail(std::string("termdaw_amd: this build has no k_") + f.k + " kernels: " + f.name + " vertices cannot be rendered");
+    for (size_t vi : g->order) {   // ... and the keyed forms, where a key edge asks for them (td_graph_connect_key)
+        const Vertex& v = g->vertices[vi];
+        if (g->key_edges[vi].empty() || v.wet < 0.0001f) continue;
+        if (v.kind == K_COMPRESSOR ? !launch_comp_detect_keyed : !(launch_gate_detect_keyed && launch_gate_env_keyed))
+            return fail("termdaw_amd: this build has no keyed compressor / gate kernels: a vertex with a key edge cannot be rendered");
+    }
     const size_t bl = g->bl;
     if (bl == 0) return fail("termdaw_amd: buffer length 0");
     rp->n_blocks = n_blocks;
@@ -1683,6 +1701,7 @@ void td_graph_reset(td_graph* g) {
     g->guard.lines.clear();
     g->vertices.clear();
     g->edges.clear();
+    g->key_edges.clear();
     g->name_map.clear();
     g->output_vertex = -1;
     g->stems.clear();
@@ -1713,6 +1732,7 @@ static Vertex& add_vertex(td_graph* g, const char* name, float gain, float angle
     v.wet = fmaxf(fminf(wet, 1.0f), 0.0f);          // graph.rs:256
     g->vertices.push_back(v);
     g->edges.emplace_back();
+    g->key_edges.emplace_back();
     g->name_map[name] = g->vertices.size() - 1;     // later duplicates overwrite (graph.rs:54)
     g->plan_dirty = true;
     return g->vertices.back();
@@ -2042,10 +2062,13 @@ int td_gate_params(size_t sr, float threshold_db, float hysteresis_db, float hol
     return 1;
 }
 
-static bool has_loop(size_t x, size_t b, const std::vector<std::vector<size_t>>& edges) {   // graph.rs:66-72
+// (over the union of input and key edges: a key source is computed before the vertex it keys, like an input)
+static bool has_loop(size_t x, size_t b, const td_graph* g) {   // graph.rs:66-72
     if (x == b) return true;
-    for (size_t y : edges[x])
-        if (has_loop(y, b, edges)) return true;
+    for (size_t y : g->edges[x])
+        if (has_loop(y, b, g)) return true;
+    for (size_t y : g->key_edges[x])
+        if (has_loop(y, b, g)) return true;
     return false;
 }
 int td_graph_connect(td_graph* g, const char* a, const char* b) {   // graph.rs:58-96
@@ -2056,8 +2079,21 @@ int td_graph_connect(td_graph* g, const char* a, const char* b) {   // graph.rs:
     const size_t ai = ia->second, bi = ib->second;
     if (ai == bi) return fail("connect: self edge");
     if (!g->vertices[bi].has_input()) return fail("connect: target vertex takes no input");
-    if (has_loop(ai, bi, g->edges)) return fail("connect: edge would close a loop");
+    if (has_loop(ai, bi, g)) return fail("connect: edge would close a loop");
     g->edges[bi].push_back(ai);
+    g->plan_dirty = true;
+    return 1;
+}
+int td_graph_connect_key(td_graph* g, const char* a, const char* b) {
+    settle_guard_before_edit(g);
+    auto ia = g->name_map.find(a), ib = g->name_map.find(b);
+    if (ia == g->name_map.end()) return fail(std::string("TermDaw: warning: vertex \"") + a + "\" cannot be found and thus can't be connected.");
+    if (ib == g->name_map.end()) return fail(std::string("TermDaw: warning: vertex \"") + b + "\" cannot be found and thus can't be connected to.");
+    const size_t ai = ia->second, bi = ib->second;
+    if (g->vertices[bi].kind != K_COMPRESSOR && g->vertices[bi].kind != K_GATE) return fail(std::string("connect_key: ") + b + " takes no key input");
+    if (ai == bi) return fail("connect_key: self edge");
+    if (has_loop(ai, bi, g)) return fail("connect_key: edge would close a loop");
+    g->key_edges[bi].push_back(ai);
     g->plan_dirty = true;
     return 1;
 }

@@ -381,6 +381,10 @@ struct td_graph {
     // graph.rs:12-22
     std::vector<tde::Vertex> vertices;
     std::vector<std::vector<size_t>> edges;   // reverse edges: edges[b] = [a...] in connect() order
+    // key edges (td_graph_connect_key), reverse like `edges`: key_edges[b] = [a...] in connect_key() order; only a compressor or
+    // gate vertex has any.  The plan and every liveness rule of compile_chunk count them as consumers of a; the level of b's
+    // dynamics is taken from their sum
+    std::vector<std::vector<size_t>> key_edges;
     std::map<std::string, size_t> name_map;
     long output_vertex = -1;
     size_t bl = 0, sr = 0, t = 0;

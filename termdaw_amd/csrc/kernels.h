@@ -261,7 +261,16 @@ struct CompDesc {
     double aR, aA, oA;      // release / attack coefficients, 1 - aA
     double pwR[8], pwA[8];  // aR^(kCompRun 2^k), aA^(kCompRun 2^k)
     PanGain pg;
+    // a keyed vertex (td_graph_connect_key; null / 0 without key edges): key_k key terms (kinds 0 .. 4), in
+    // connect_key() order.  k_comp_detect<true> sums them for the level of step 1 -- d[n] is taken from the key frame -- and
+    // the input terms into `x` as ever; the later launches read dy and x only and are the unkeyed vertex' own.
+    const InTerm* key_ins;
+    uint32_t key_k, key_term_mode;
 };
+// Bit 31 of the aux word of a compressor / gate launch whose descriptors are keyed (the keyed instantiation: F_COMP_DETECT,
+// F_GATE_DETECT, F_GATE_ENV); the low bits stay the largest tile count.  A level's unkeyed descriptors go out first, the keyed
+// ones in a launch of their own behind them.
+constexpr uint32_t kKeyedBit = 0x80000000u;
 
 // A gate vertex (k_gate_detect / k_gate_carry / k_gate_env / k_gate_carry / k_gate_apply; the definition is in
 // include/termdaw_amd.h at td_graph_add_gate).  The compressor's tiling: tiles of kGateTile frames, a lane owns kGateRun consecutive
@@ -300,6 +309,13 @@ struct GateDesc {
     double aA, aR, oA, oR;  // attack / release coefficients, 1 - aA, 1 - aR
     double F, oF;           // the closed gain, 1 - F
     PanGain pg;
+    // a keyed vertex (td_graph_connect_key; null / 0 without key edges): key_k key terms (kinds 0 .. 4), in
+    // connect_key() order.  k_gate_detect<true> sums them for steps 1 and 2 and leaves the lane's eight 2-bit classes as one
+    // 16-bit word in cls (frame j of the lane in bits 2 j, 2 j + 1; 0 from `frames` on); k_gate_env<true> reads the word
+    // instead of deriving the classes from `x` -- 2 bytes per lane where the unkeyed form reads 64.
+    const InTerm* key_ins;
+    uint16_t* cls;          // [n_tiles kThreads]
+    uint32_t key_k, key_term_mode;
 };
 
 // A parametric EQ vertex (k_eq_local / k_eq_carry / k_eq_apply; the definition is in include/termdaw_amd.h at
@@ -911,6 +927,8 @@ __attribute__((weak)) void launch_master_apply(const MasterDesc* d, int n_desc, 
 __attribute__((weak)) void launch_comp_detect(const CompDesc* d, int n_desc, uint32_t max_tiles, hipStream_t s);
 __attribute__((weak)) void launch_comp_env(const CompDesc* d, int n_desc, uint32_t max_tiles, hipStream_t s);
 __attribute__((weak)) void launch_comp_apply(const CompDesc* d, int n_desc, uint32_t max_tiles, hipStream_t s);
+// ... and the keyed form of the first (CompDesc::key_ins; a launch whose aux carries kKeyedBit)
+__attribute__((weak)) void launch_comp_detect_keyed(const CompDesc* d, int n_desc, uint32_t max_tiles, hipStream_t s);
 // Weak for the same reason: a level's EQ vertices, ONE grid per step (grid.x: the largest tile count; the carry: one workgroup
 // per vertex).
 __attribute__((weak)) void launch_eq_local(const EqDesc* d, int n_desc, uint32_t max_tiles, hipStream_t s);
@@ -946,6 +964,9 @@ __attribute__((weak)) void launch_gate_detect(const GateDesc* d, int n_desc, uin
 __attribute__((weak)) void launch_gate_carry(const GateDesc* d, int n_desc, bool affine, hipStream_t s);
 __attribute__((weak)) void launch_gate_env(const GateDesc* d, int n_desc, uint32_t max_tiles, hipStream_t s);
 __attribute__((weak)) void launch_gate_apply(const GateDesc* d, int n_desc, uint32_t max_tiles, hipStream_t s);
+// ... and the keyed forms of detect and env (GateDesc::key_ins / cls; launches whose aux carries kKeyedBit)
+__attribute__((weak)) void launch_gate_detect_keyed(const GateDesc* d, int n_desc, uint32_t max_tiles, hipStream_t s);
+__attribute__((weak)) void launch_gate_env_keyed(const GateDesc* d, int n_desc, uint32_t max_tiles, hipStream_t s);
 // Weak for the same reason: a level's reverb vertices.  launch_reverb_sum: grid.x from `frames`; launch_reverb: one workgroup per
 // descriptor, `form` 0 the serial walk of each comb's one-pole, 1 the wave scan.
 __attribute__((weak)) void launch_reverb_sum(const ReverbDesc* d, int n_desc, uint32_t frames, hipStream_t s);

@@ -2034,6 +2034,10 @@ TD_DEV void comp_load_run(const CompDesc& d, uint32_t f0, double (&y)[kCompRun])
         y[2 * j + 1] = m + 1u < d.frames ? v.y : 0.0;
     }
 }
+// KEYED (td_graph_connect_key): the level of step 1 is taken from the sum of the key terms, evaluated by the same
+// sum_inputs_pairs behind the input terms; `x` holds the summed INPUT either way.  An instantiation of its own, launched over a
+// level's keyed descriptors only: the unkeyed form is the code it was.
+template <bool KEYED>
 __global__ __launch_bounds__(kThreads) void k_comp_detect(const CompDesc* __restrict__ descs) {
     const CompDesc& d = descs[blockIdx.y];
     if (blockIdx.x >= d.n_tiles) return;
@@ -2048,6 +2052,7 @@ __global__ __launch_bounds__(kThreads) void k_comp_detect(const CompDesc* __rest
         sum_inputs_pairs(d.ins, d.k, d.term_mode, m, m + 2u, M, a0, a1);
         store_pair(d.x, m, M, a0);
         store_pair(d.x, m + 2u, M, a1);
+        if (KEYED) sum_inputs_pairs(d.key_ins, d.key_k, d.key_term_mode, m, m + 2u, M, a0, a1);   // (kl, kr): what the level reads
         const double d0 = comp_want(d, a0.x, a0.y), d1 = comp_want(d, a0.z, a0.w);
         const double d2 = comp_want(d, a1.x, a1.y), d3 = comp_want(d, a1.z, a1.w);
         if (m < M) gstore_d2(d.dy + m, d0, d1);
@@ -6158,6 +6163,10 @@ TD_DEV double gate_pair_scan(double& A, double& B, double in, double* sa, double
     __syncthreads();
     return e;
 }
+// KEYED (td_graph_connect_key): steps 1 and 2 read the sum of the key terms, and the lane's eight classes are left
+// in GateDesc::cls for k_gate_env<true>, which cannot derive them from `x`.  Instantiations of their own, launched over a
+// level's keyed descriptors only: the unkeyed forms are the code they were.
+template <bool KEYED>
 __global__ __launch_bounds__(kThreads) void k_gate_detect(const GateDesc* __restrict__ descs) {
     const GateDesc& d = descs[blockIdx.y];
     if (blockIdx.x >= d.n_tiles) return;
@@ -6165,6 +6174,7 @@ __global__ __launch_bounds__(kThreads) void k_gate_detect(const GateDesc* __rest
     const uint32_t M = d.frames, cap = d.cap, f0 = blockIdx.x * kGateTile + threadIdx.x * kGateRun;
     const double To = d.To, Tc = d.Tc;
     uint32_t m0 = 0u, m1 = kGateH;   // the identity: frames from M on leave it as it is
+    uint32_t cw = 0u;                // (KEYED) the lane's classes, two bits a frame
 #pragma unroll 1
     for (uint32_t h = 0; h < kGateRun / 4; ++h) {
         const uint32_t m = f0 + 4u * h;
@@ -6172,13 +6182,16 @@ __global__ __launch_bounds__(kThreads) void k_gate_detect(const GateDesc* __rest
         sum_inputs_pairs(d.ins, d.k, d.term_mode, m, m + 2u, M, a0, a1);
         store_pair(d.x, m, M, a0);
         store_pair(d.x, m + 2u, M, a1);
+        if (KEYED) sum_inputs_pairs(d.key_ins, d.key_k, d.key_term_mode, m, m + 2u, M, a0, a1);   // (kl, kr): what the level reads
         const uint32_t c0 = gate_class(To, Tc, a0.x, a0.y), c1 = gate_class(To, Tc, a0.z, a0.w);
         const uint32_t c2 = gate_class(To, Tc, a1.x, a1.y), c3 = gate_class(To, Tc, a1.z, a1.w);
         if (m < M) { m0 = gate_step(m0, c0, cap); m1 = gate_step(m1, c0, cap); }
         if (m + 1u < M) { m0 = gate_step(m0, c1, cap); m1 = gate_step(m1, c1, cap); }
         if (m + 2u < M) { m0 = gate_step(m0, c2, cap); m1 = gate_step(m1, c2, cap); }
         if (m + 3u < M) { m0 = gate_step(m0, c3, cap); m1 = gate_step(m1, c3, cap); }
+        if (KEYED) cw |= (c0 | (c1 << 2) | (c2 << 4) | (c3 << 6)) << (8u * h);   // (frames from M on are never stepped: their bits are not read)
     }
+    if (KEYED) d.cls[(size_t)blockIdx.x * kThreads + threadIdx.x] = (uint16_t)cw;
     uint32_t e0, e1;
     gate_map_scan(m0, m1, cap, s0, s1, &e0, &e1);
     if (threadIdx.x == kThreads - 1u) {
@@ -6232,6 +6245,7 @@ TD_DEV void gate_load_run(const GateDesc& d, uint32_t f0, float4 (&x)[kGateRun /
 #pragma unroll
     for (uint32_t j = 0; j < kGateRun / 2; ++j) x[j] = load_pair(d.x, f0 + 2u * j, d.frames);
 }
+template <bool KEYED>
 __global__ __launch_bounds__(kThreads) void k_gate_env(const GateDesc* __restrict__ descs) {
     const GateDesc& d = descs[blockIdx.y];
     if (blockIdx.x >= d.n_tiles) return;
@@ -6239,13 +6253,19 @@ __global__ __launch_bounds__(kThreads) void k_gate_env(const GateDesc* __restric
     __shared__ double sa[kThreads], sb[kThreads];
     const uint32_t tid = threadIdx.x, M = d.frames, cap = d.cap, f0 = blockIdx.x * kGateTile + tid * kGateRun;
     const double To = d.To, Tc = d.Tc, aA = d.aA, aR = d.aR, oA = d.oA, oR = d.oR;
-    float4 x[kGateRun / 2];
-    gate_load_run(d, f0, x);
     uint32_t cls[kGateRun];
+    if (KEYED) {   // the classes k_gate_detect<true> took from the key sum
+        const uint32_t cw = d.cls[(size_t)blockIdx.x * kThreads + tid];
 #pragma unroll
-    for (uint32_t j = 0; j < kGateRun / 2; ++j) {
-        cls[2 * j] = gate_class(To, Tc, x[j].x, x[j].y);
-        cls[2 * j + 1] = gate_class(To, Tc, x[j].z, x[j].w);
+        for (uint32_t k = 0; k < kGateRun; ++k) cls[k] = (cw >> (2u * k)) & 3u;
+    } else {
+        float4 x[kGateRun / 2];
+        gate_load_run(d, f0, x);
+#pragma unroll
+        for (uint32_t j = 0; j < kGateRun / 2; ++j) {
+            cls[2 * j] = gate_class(To, Tc, x[j].x, x[j].y);
+            cls[2 * j + 1] = gate_class(To, Tc, x[j].z, x[j].w);
+        }
     }
     uint32_t m0 = 0u, m1 = kGateH, e0, e1;
 #pragma unroll
@@ -6556,7 +6576,11 @@ void launch_master_apply(const MasterDesc* d, int n, uint32_t max_tiles, hipStre
 }
 void launch_comp_detect(const CompDesc* d, int n, uint32_t max_tiles, hipStream_t s) {
     for (int o = 0; o < n && max_tiles; o += kMaxGridY)
-        hipLaunchKernelGGL(k_comp_detect, dim3(max_tiles, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
+        hipLaunchKernelGGL(k_comp_detect<false>, dim3(max_tiles, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
+}
+void launch_comp_detect_keyed(const CompDesc* d, int n, uint32_t max_tiles, hipStream_t s) {
+    for (int o = 0; o < n; o += kMaxGridY)
+        hipLaunchKernelGGL(k_comp_detect<true>, dim3(max_tiles, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
 }
 void launch_comp_env(const CompDesc* d, int n, uint32_t max_tiles, hipStream_t s) {
     for (int o = 0; o < n && max_tiles; o += kMaxGridY)
@@ -6637,7 +6661,11 @@ void launch_reverb(const ReverbDesc* d, int n, uint32_t form, hipStream_t s) {
 }
 void launch_gate_detect(const GateDesc* d, int n, uint32_t max_tiles, hipStream_t s) {
     for (int o = 0; o < n && max_tiles; o += kMaxGridY)
-        hipLaunchKernelGGL(k_gate_detect, dim3(max_tiles, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
+        hipLaunchKernelGGL(k_gate_detect<false>, dim3(max_tiles, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
+}
+void launch_gate_detect_keyed(const GateDesc* d, int n, uint32_t max_tiles, hipStream_t s) {
+    for (int o = 0; o < n; o += kMaxGridY)
+        hipLaunchKernelGGL(k_gate_detect<true>, dim3(max_tiles, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
 }
 void launch_gate_carry(const GateDesc* d, int n, bool affine, hipStream_t s) {
     if (n <= 0) return;
@@ -6646,7 +6674,11 @@ void launch_gate_carry(const GateDesc* d, int n, bool affine, hipStream_t s) {
 }
 void launch_gate_env(const GateDesc* d, int n, uint32_t max_tiles, hipStream_t s) {
     for (int o = 0; o < n && max_tiles; o += kMaxGridY)
-        hipLaunchKernelGGL(k_gate_env, dim3(max_tiles, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
+        hipLaunchKernelGGL(k_gate_env<false>, dim3(max_tiles, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
+}
+void launch_gate_env_keyed(const GateDesc* d, int n, uint32_t max_tiles, hipStream_t s) {
+    for (int o = 0; o < n; o += kMaxGridY)
+        hipLaunchKernelGGL(k_gate_env<true>, dim3(max_tiles, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
 }
 void launch_gate_apply(const GateDesc* d, int n, uint32_t max_tiles, hipStream_t s) {
     for (int o = 0; o < n && max_tiles; o += kMaxGridY)

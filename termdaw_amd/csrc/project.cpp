@@ -217,7 +217,7 @@ int do_refresh(td_state* s, const std::string& contents) {
     s->dump.clear();
     const size_t psr = s->psr, bl = s->bl;
     std::vector<Triple> new_samples;
-    std::vector<std::pair<std::string, std::string>> new_resources, midis, new_lv2plugins, edges;
+    std::vector<std::pair<std::string, std::string>> new_resources, midis, new_lv2plugins, edges, key_edges;
     std::vector<std::string> streams;
     std::vector<SumCall> sums, norms;
     std::vector<LoopCall> sampleloops;
@@ -481,6 +481,11 @@ int do_refresh(td_state* s, const std::string& contents) {
         dump += "connect(\"" + edges.back().first + "\",\"" + edges.back().second + "\")\n";
         return Value::nil();
     });
+    lua.set_function("connect_key", [&](const std::vector<Value>& a) {   // this engine's own: td_graph_connect_key
+        key_edges.push_back({to_str("connect_key", a, 0), to_str("connect_key", a, 1)});
+        dump += "connect_key(\"" + key_edges.back().first + "\",\"" + key_edges.back().second + "\")\n";
+        return Value::nil();
+    });
     lua.set_function("set_output", [&](const std::vector<Value>& a) {
         output_vertex = to_str("set_output", a, 0);
         dump += "set_output(\"" + output_vertex + "\")\n";
@@ -605,6 +610,7 @@ int do_refresh(td_state* s, const std::string& contents) {
     for (auto& c : gates)
         if (!td_graph_add_gate(s->g, c.name.c_str(), c.gain, c.angle, c.wet, c.threshold_db, c.hysteresis_db, c.hold_ms, c.attack_ms, c.release_ms, c.range_db)) return 0;
     for (auto& e : edges) td_graph_connect(s->g, e.first.c_str(), e.second.c_str());   // failures only warn (state.rs:459)
+    for (auto& e : key_edges) td_graph_connect_key(s->g, e.first.c_str(), e.second.c_str());   // (after the edges; failures only warn, like theirs)
     td_graph_set_output(s->g, s->output_vertex.c_str());
     if (!td_graph_check(s->g)) return fail("TermDaw: graph check failed! (" + g_error + ")");
     td_graph_reset_normalize_vertices(s->g);   // state.rs:467

@@ -169,7 +169,7 @@ class ProjectScript:
         self.calls = {k: [] for k in (
             "load_sample", "load_resource", "load_midi_floww", "add_sum", "add_normalize", "add_sampleloop",
             "add_sample_multi", "add_sample_lerp", "add_debug_sine", "add_synth", "add_sampsyn", "add_adsr",
-            "add_bandpass", "add_compressor", "add_eq", "add_delay", "add_saturator", "add_chorus", "add_reverb", "add_gate", "connect")}
+            "add_bandpass", "add_compressor", "add_eq", "add_delay", "add_saturator", "add_chorus", "add_reverb", "add_gate", "connect", "connect_key")}
         self.resources = {}                 # path -> bytes (load_resource)
         self.script_order = []              # (fn, args) in call order, for to_lua()
 
@@ -271,6 +271,10 @@ class ProjectScript:
     def connect(self, a, b):
         self._rec("connect", a, b)
 
+    def connect_key(self, a, b):
+        """This engine's own edge (include/termdaw_amd.h td_graph_connect_key): the key input of a compressor or gate vertex."""
+        self._rec("connect_key", a, b)
+
     # -- State::refresh (state.rs:202-467) --
     def build(self, backend):
         """Returns (sb, fb, g) built exactly in the reference's order, or raises on a failed refresh."""
@@ -339,6 +343,8 @@ class ProjectScript:
             g.add_gate(*args)
         for a, b in self.calls["connect"]:
             g.connect(a, b)
+        for a, b in self.calls["connect_key"]:   # (after the connect calls, as the front-end applies them)
+            g.connect_key(a, b)
         g.set_output(self.output_vertex)
         if not g.check_graph():
             raise RuntimeError("TermDaw: graph check failed!")
