@@ -372,6 +372,41 @@ int td_graph_add_gate(td_graph* g, const char* name, float gain, float angle, fl
  * aR, F.  The same range checks as td_graph_add_gate. */
 int td_gate_params(size_t sr, float threshold_db, float hysteresis_db, float hold_ms, float attack_ms, float release_ms,
                    float range_db, double out[6]);
+/* A phaser vertex: a swept all-pass chain with feedback -- THIS ENGINE'S OWN: no reference counterpart (the reference reaches
+ * modulation effects only through LV2 plugins, add_lv2fx, which this engine parses and drops).  Per channel N
+ * first-order all-pass sections in series (transposed direct form II) share one coefficient a[n], swept by the chorus' LFO
+ * between the coefficients of lo_hz and hi_hz; the chain's output is fed back to its input.  The vertex sums its inputs like
+ * every input vertex (sum_inputs, extensions.rs:310-319), processes, mixes with `wet` by the reference's f32 lerp, then pan and
+ * gain like every vertex (extensions.rs:262-263).
+ *   Constants, f64, once on the host, each from the f32 parameter widened to f64 (td_phaser_params returns them):
+ *     N = stages;  g(fc) = (tan(pi fc / sr) - 1) / (tan(pi fc / sr) + 1);  a_lo = g(lo_hz);  a_hi = g(hi_hz);
+ *     am = 0.5 (a_lo + a_hi);  ad = 0.5 (a_hi - a_lo);  f = rate_hz / sr;  fb = feedback.
+ *   The sweep is linear in the all-pass COEFFICIENT, not in Hz: the device stays on IEEE add, multiply, floor and fabs (the
+ *   chorus' rule), so a[n] is the same bits wherever it is computed.
+ *   Per channel c, at the ABSOLUTE frame n (the graph's time, as for the chorus), phi = 0 on the left, phi = stereo on the
+ *   right, in f64 with no FMA contraction, in the order written:
+ *     th = n f + phi;  th = th - floor(th);  a = am + ad lfo(shape, th)       (lfo: td_graph_add_chorus' -- sine or triangle)
+ *     xs = x[n] if finite, else 0;   v = xs + fb z
+ *     for k = 1 .. N:   w = a v + s_k;   s_k = v - a w;   v = w
+ *     z = v;   p[n] = (float)v
+ *   Output: out = x + wet * (p - x) in f32 (adsr.rs:42); then pan and gain.  wet 0.5: the classic phaser, N / 2 moving notches;
+ *   wet 1: a swept phase shift.  wet < 0.0001: the summed input passes through untouched (a plain k_sum launch) and the state
+ *   stays as it is.
+ * State: (s_1 .. s_N, z) per channel, f64, zero at time 0; carried between consecutive block pulls and between the chunks of a
+ * render, restarted from zero by td_graph_set_time / td_graph_change_time / td_graph_reset.  The LFO never restarts: it is a
+ * function of the graph's time.  No latency, no tail.
+ * Ranges, rejected with a td_last_error that names the parameter (NaN included): stages 2 | 4 | 6 | 8; lo_hz >= 20; hi_hz <=
+ * 0.45 sr; lo_hz <= hi_hz (equal: a static chain); rate_hz [0.01, 20]; feedback [-0.95, 0.95]; stereo [0, 0.5]; shape 0 .. 1
+ * (TD_CHORUS_*).  `wet` is clamped to [0, 1].
+ * Under "band_mode" 2 / "sine_mode" 2 everything upstream of a phaser vertex takes the exact forms: the vertex is linear but
+ * time-varying with feedback, and no L2 bound of it is proven; vertices downstream are unaffected.
+ * Not part of the vertex: an exponential (linear-in-Hz or in octaves) sweep law, tempo sync, more than 8 stages, barber-pole
+ * forms. */
+int td_graph_add_phaser(td_graph* g, const char* name, float gain, float angle, float wet, int stages, float lo_hz, float hi_hz,
+                        float rate_hz, float feedback, float stereo, int shape);
+/* Host only, no GPU: the phaser vertex' constants at rate sr, exactly the doubles the engine uses -- out[0 .. 6] = N, a_lo, a_hi,
+ * am, ad, f, fb.  The same range checks as td_graph_add_phaser. */
+int td_phaser_params(size_t sr, int stages, float lo_hz, float hi_hz, float rate_hz, float feedback, float stereo, int shape, double out[7]);
 int td_graph_connect(td_graph* g, const char* a, const char* b);          /* graph.rs:80-96 (+58-78) */
 /* A key edge (sidechain) from any vertex `a` to a compressor or gate vertex `b` -- THIS ENGINE'S OWN, like the two vertices.  A
  * vertex with at least one key edge takes its LEVEL from the sum of its key sources; everything else is as without: it processes

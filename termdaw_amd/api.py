@@ -76,6 +76,8 @@ SIGNATURES = {
     "td_graph_add_chorus": (_i32, [_vp, _cp, _f32, _f32, _f32, _i32, _f32, _f32, _f32, _f32, _i32]),
     "td_chorus_params": (_i32, [_sz, _i32, _f32, _f32, _f32, _f32, _i32, C.POINTER(C.c_double)]),
     "td_graph_add_reverb": (_i32, [_vp, _cp, _f32, _f32, _f32, _f32, _f32, _f32, _f32]),
+    "td_graph_add_phaser": (_i32, [_vp, _cp, _f32, _f32, _f32, _i32, _f32, _f32, _f32, _f32, _f32, _i32]),
+    "td_phaser_params": (_i32, [_sz, _i32, _f32, _f32, _f32, _f32, _f32, _i32, C.POINTER(C.c_double)]),
     "td_graph_add_gate": (_i32, [_vp, _cp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32]),
     "td_gate_params": (_i32, [_sz, _f32, _f32, _f32, _f32, _f32, _f32, C.POINTER(C.c_double)]),
     "td_reverb_params": (_i32, [_sz, _f32, _f32, _f32, _f32, C.POINTER(C.c_double)]),
@@ -341,6 +343,14 @@ def chorus_shape(shape):
     return int(shape)
 
 
+def phaser_params(sr, stages, lo_hz, hi_hz, rate_hz, feedback, stereo, shape):
+    """(N, a_lo, a_hi, am, ad, f, fb): the phaser vertex' constants at rate sr, exactly the doubles the engine uses (host only; N an
+    int).  shape: the chorus' names."""
+    out = (C.c_double * 7)()
+    _check(lib().td_phaser_params(int(sr), int(stages), lo_hz, hi_hz, rate_hz, feedback, stereo, chorus_shape(shape), out))
+    return (int(out[0]),) + tuple(out[1:7])
+
+
 def gate_params(sr, threshold_db, hysteresis_db, hold_ms, attack_ms, release_ms, range_db):
     """(To, Tc, H, aA, aR, F): the gate vertex' constants at rate sr, exactly the doubles the engine uses (host only; H an int)."""
     out = (C.c_double * 6)()
@@ -584,6 +594,12 @@ class Graph:
         include/termdaw_amd.h)."""
         _check(lib().td_graph_add_gate(self.h, name.encode(), gain, angle, wet, threshold_db, hysteresis_db, hold_ms, attack_ms, release_ms,
                                        range_db))
+
+    def add_phaser(self, name, gain, angle, wet, stages, lo_hz, hi_hz, rate_hz, feedback, stereo, shape):
+        """A phaser vertex: a swept all-pass chain with feedback (this engine's own; the definition is in include/termdaw_amd.h).
+        stages 2 | 4 | 6 | 8; shape "sine" or "triangle" (or the chorus' constants)."""
+        _check(lib().td_graph_add_phaser(self.h, name.encode(), gain, angle, wet, int(stages), lo_hz, hi_hz, rate_hz, feedback, stereo,
+                                         chorus_shape(shape)))
 
     def connect(self, a, b):
         return bool(lib().td_graph_connect(self.h, a.encode(), b.encode()))

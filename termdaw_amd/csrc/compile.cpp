@@ -3,7 +3,7 @@
 // this file calls the HIP runtime: device memory reaches it as addresses handed out by three functions of engine.cpp
 // (compile.h: take_buffer / ensure_buffers for edge buffers, upload_tables for a vertex' event tables), everything it
 // writes goes into the plain-memory staging arena of the ChunkBuild (offsets + fix-up lists that submit_chunk patches once
-// the device addresses are known).  The effect kinds (compressor .. gate) are lowered by compile_fx.cpp, through the table there;
+// the device addresses are known).  The effect kinds (compressor .. phaser) are lowered by compile_fx.cpp, through the table there;
 // that file is included at the end of this one (see there).  tests/test_compile_asan.py builds it with g++
 // -fsanitize=address,undefined.
 #include "compile.h"
@@ -30,7 +30,8 @@ const char* const kFamilyName[F_COUNT] = {"k_sample_loop", "k_sample_multi", "k_
                                            "k_sat_sum", "k_sat", "k_sat1",
                                            "k_chorus_sum", "k_chorus",
                                            "k_reverb_sum", "k_reverb",
-                                           "k_gate_detect", "k_gate_carry_hc", "k_gate_env", "k_gate_carry_env", "k_gate_apply"};
+                                           "k_gate_detect", "k_gate_carry_hc", "k_gate_env", "k_gate_carry_env", "k_gate_apply",
+                                           "k_phaser_local", "k_phaser_carry", "k_phaser_apply"};
 
 
 // ------------------------------------------------------------------------------------------------

@@ -21,6 +21,7 @@ enum Family { F_LOOP, F_MULTI, F_LERP, F_SINE, F_SYNTH, F_SAMPSYN, F_ENV, F_PROB
               F_CHORUS_SUM, F_CHORUS /* a level's chorus vertices: k_chorus_sum (when the chunk is longer than the one-launch form takes), k_chorus */,
               F_REVERB_SUM, F_REVERB /* a level's reverb vertices: k_reverb_sum, k_reverb -- in this order */,
               F_GATE_DETECT, F_GATE_CARRY_H, F_GATE_ENV, F_GATE_CARRY_ENV, F_GATE_APPLY /* a level's gate vertices: k_gate_detect, k_gate_carry (the (h, c) entering each tile), k_gate_env, k_gate_carry (the env entering each tile), k_gate_apply -- in this order */,
+              F_PHASER_LOCAL, F_PHASER_CARRY, F_PHASER_APPLY /* a level's phaser vertices, per stage count: k_phaser_local, k_phaser_carry (both over multi-tile chunks only), k_phaser_apply -- in this order */,
               F_COUNT };
 extern const char* const kFamilyName[F_COUNT];
 
@@ -37,7 +38,7 @@ bool is_delay_family(int fam);
 double ms_between(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b);
 tdk::PanGain make_pg(float gain, float angle);           // a vertex' pan / gain as its kernel's epilogue applies it (sample.rs:98-109)
 
-// ---- compile_fx.cpp: the effect kinds (compressor, EQ, delay, saturator, chorus, reverb, gate) ----
+// ---- compile_fx.cpp: the effect kinds (compressor, EQ, delay, saturator, chorus, reverb, gate, phaser) ----
 // What lowering the vertices of one effect kind at one level needs of compile_chunk, and the steps every kind's lowering
 // shares.  The kinds' own functions (lower_comp ..) keep what is theirs: coefficients, tiling, scratch, launches.
 struct FxLevel {

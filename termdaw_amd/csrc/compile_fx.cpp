@@ -1,5 +1,5 @@
 // compile_fx.cpp -- the effect kinds of the host compiler (compile.h FxKind / FxLevel): compressor, EQ, delay, saturator,
-// chorus, reverb, gate.  One table row per kind -- its chunk limit, the family its launches start at, the factor the guard
+// chorus, reverb, gate, phaser.  One table row per kind -- its chunk limit, the family its launches start at, the factor the guard
 // carries an estimate through it at -- and one function per kind that lowers a level's vertices of that kind to descriptors
 // and launches.  compile_chunk enumerates the kinds through the table only.  Like compile.cpp: no HIP call.  Not an object of its
 // own: compile.cpp includes this file at its end, so no build list changes with it.
@@ -8,6 +8,7 @@
 #include "delay_math.h"
 #include "eq_math.h"
 #include "gate_math.h"
+#include "phaser_math.h"
 #include "reverb_math.h"
 #include "sat_math.h"
 
@@ -412,6 +413,57 @@ static int lower_gate(FxLevel& L, std::vector<size_t>& vs) {
     return 1;
 }
 
+// ---- phaser: three launches per stage count, or one (kernels.h PhaserDesc) ----
+static int lower_phaser(FxLevel& L, std::vector<size_t>& vs) {
+    td_graph* g = L.g;
+    const uint32_t n_tiles = (uint32_t)((L.M + kPhaserTile - 1) / kPhaserTile);
+    const bool multi = n_tiles > 1u;   // (multi: k_phaser_local and k_phaser_carry first)
+    std::vector<size_t> ord(vs.begin(), vs.end());   // one launch per stage count: the kernels are templates on it
+    std::stable_sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return g->vertices[a].phaser_stages < g->vertices[b].phaser_stages; });
+    std::vector<PhaserDesc> d;
+    for (size_t vi : ord) {
+        Vertex& v = g->vertices[vi];
+        PhaserDesc x{};
+        if (multi && !(x.x = L.tmp_buffer())) return 0;
+        L.head(x, vi);
+        x.state = reinterpret_cast<PhaserState*>(&g->dstate[v.state_slot]);
+        // (a set_time since the vertex last ran: the state restarts from zero -- consumed here, like an EQ's)
+        x.init = v.first_pending ? nullptr : x.state;
+        v.first_pending = false;
+        x.t0 = L.t0;
+        x.n_tiles = n_tiles;
+        double c[phaser::kParams];
+        phaser::params(L.sr, v.phaser_stages, v.phaser_lo_hz, v.phaser_hi_hz, v.phaser_rate_hz, v.phaser_feedback, v.phaser_stereo, v.phaser_shape, c);
+        x.stages = (uint32_t)v.phaser_stages;
+        x.shape = (uint32_t)v.phaser_shape;
+        x.am = c[3];
+        x.ad = c[4];
+        x.f = c[5];
+        x.fb = c[6];
+        x.stereo = (double)v.phaser_stereo;
+        d.push_back(x);
+    }
+    const size_t off = L.put(d, ord);
+    for (size_t i = 0; multi && i < ord.size(); ++i) {
+        const size_t o = off + i * sizeof(PhaserDesc), D = (size_t)d[i].stages + 1;
+        L.cb.scratch_field(o, offsetof(PhaserDesc, agg), L.cb.scratch((size_t)n_tiles * 2 * D * (D + 1) * sizeof(double)));
+        L.cb.scratch_field(o, offsetof(PhaserDesc, carry), L.cb.scratch((size_t)n_tiles * 2 * D * sizeof(double)));
+    }
+    for (size_t i = 0; i < ord.size();) {
+        const uint32_t N = d[i].stages;
+        size_t j = i;
+        while (j < ord.size() && d[j].stages == N) ++j;
+        const size_t o = off + i * sizeof(PhaserDesc);
+        if (multi) {
+            L.add_launch(F_PHASER_LOCAL, o, (int)(j - i), phaser_aux(n_tiles, N, false));
+            L.add_launch(F_PHASER_CARRY, o, (int)(j - i), phaser_aux(0u, N, false));
+        }
+        L.add_launch(F_PHASER_APPLY, o, (int)(j - i), phaser_aux(n_tiles, N, !multi));
+        i = j;
+    }
+    return 1;
+}
+
 // ---- the table ----
 // fits: the largest chunk the kind's kernels index (32-bit frames; the line kinds keep room for their look-back, the tiled
 // ones for the tile count packed into a launch's aux)
@@ -431,6 +483,8 @@ static double lerp_gain(const Vertex& v, double H) { return (1.0 - (double)v.wet
 static double through_comp(const Vertex&, size_t) { return kNoStaticGain; }
 // ... and so is a gate, unless it is dry
 static double through_gate(const Vertex& v, size_t) { return dry(v) ? 1.0 : kNoStaticGain; }
+// a phaser is linear, but time-varying with feedback, and no L2 bound of it is proven: none is guessed
+static double through_phaser(const Vertex& v, size_t) { return dry(v) ? 1.0 : kNoStaticGain; }
 // an EQ is linear and time-invariant: Hmax of its biquad
 static double through_eq(const Vertex& v, size_t sr) {
     if (dry(v)) return 1.0;
@@ -465,9 +519,9 @@ static double through_reverb(const Vertex& v, size_t sr) {
 // (a function's static: these sources also go through the HIP compiler, whose device pass would want a copy of a namespace-scope
 // constant -- and of the host functions it points to.)  A row's family count is the distance to the next row's first family, so
 // the rows cover the effect families of `Family` without gap or overlap as long as they stand in its order:
-constexpr int kFxKinds = 7;
+constexpr int kFxKinds = 8;
 static_assert(F_COMP_DETECT < F_EQ_LOCAL && F_EQ_LOCAL < F_DELAY_LOCAL && F_DELAY_LOCAL < F_SAT_SUM && F_SAT_SUM < F_CHORUS_SUM &&
-              F_CHORUS_SUM < F_REVERB_SUM && F_REVERB_SUM < F_GATE_DETECT && F_GATE_DETECT < F_COUNT,
+              F_CHORUS_SUM < F_REVERB_SUM && F_REVERB_SUM < F_GATE_DETECT && F_GATE_DETECT < F_PHASER_LOCAL && F_PHASER_LOCAL < F_COUNT,
               "the rows of the effect kinds' table stand in the order of their families");
 static const FxKind* table() {
     static const FxKind rows[kFxKinds] = {
@@ -477,7 +531,8 @@ static const FxKind* table() {
         {K_SATURATOR, "saturator", F_SAT_SUM, F_CHORUS_SUM - F_SAT_SUM, sizeof(SatDesc), fits_sat, family_sat, through_sat, lower_sat},
         {K_CHORUS, "chorus", F_CHORUS_SUM, F_REVERB_SUM - F_CHORUS_SUM, sizeof(ChorusDesc), fits_chorus, nullptr, through_chorus, lower_chorus},
         {K_REVERB, "reverb", F_REVERB_SUM, F_GATE_DETECT - F_REVERB_SUM, sizeof(ReverbDesc), fits_line, nullptr, through_reverb, lower_reverb},
-        {K_GATE, "gate", F_GATE_DETECT, F_COUNT - F_GATE_DETECT, sizeof(GateDesc), fits_scan, nullptr, through_gate, lower_gate},
+        {K_GATE, "gate", F_GATE_DETECT, F_PHASER_LOCAL - F_GATE_DETECT, sizeof(GateDesc), fits_scan, nullptr, through_gate, lower_gate},
+        {K_PHASER, "phaser", F_PHASER_LOCAL, F_COUNT - F_PHASER_LOCAL, sizeof(PhaserDesc), fits_scan, nullptr, through_phaser, lower_phaser},
     };
     return rows;
 }

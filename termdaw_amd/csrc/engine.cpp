@@ -11,6 +11,7 @@
 #include "engine.h"
 #include "chorus_math.h"
 #include "gate_math.h"
+#include "phaser_math.h"
 #include "comm.h"
 #include "compile.h"
 #include "delay_math.h"
@@ -540,6 +541,10 @@ static tdk::GateState gate_closed(const td_graph* g, const Vertex& v) {
     gate::params(g->sr, v.gate_threshold_db, v.gate_hysteresis_db, v.gate_hold_ms, v.gate_attack_ms, v.gate_release_ms, v.gate_range_db, c);
     return {0.0, 0u, (uint32_t)std::min(c[2] + 1.0, gate::kMaxHold + 1.0), {0, 0, 0, 0}};
 }
+// A phaser vertex' state at time 0: (s_1 .. s_N, z) = 0 on both channels -- its run of slots, all zero
+static void phaser_rest(td_graph* g, const Vertex& v) {
+    memset(&g->hstate[(size_t)v.state_slot], 0, sizeof(tdk::PhaserState));
+}
 static int drain(td_graph* g);   // stream drained + deferred k_norm_fix settled (defined with the render loop)
 static int pull_state(td_graph* g) {
     if (g->state_dev_dirty && g->dstate && !g->hstate.empty()) {
@@ -554,6 +559,8 @@ static int pull_state(td_graph* g) {
             if (v.kind == K_EQ && v.state_slot >= 0 && v.first_pending) g->hstate[(size_t)v.state_slot].eq = {0.0, 0.0, 0.0, 0.0};
         for (const auto& v : g->vertices)
             if (v.kind == K_GATE && v.state_slot >= 0 && v.first_pending) g->hstate[(size_t)v.state_slot].gate = gate_closed(g, v);
+        for (const auto& v : g->vertices)
+            if (v.kind == K_PHASER && v.state_slot >= 0 && v.first_pending) phaser_rest(g, v);
     }
     return 1;
 }
@@ -963,6 +970,9 @@ static int submit_chunk(Arena& ar, ChunkBuild& cb, hipStream_t stream, ProfCtx& 
                     break;
                 case F_GATE_CARRY_ENV: launch_gate_carry((const GateDesc*)d, L.n, true, s); break;
                 case F_GATE_APPLY: launch_gate_apply((const GateDesc*)d, L.n, L.aux, s); break;
+                case F_PHASER_LOCAL: launch_phaser_local((const PhaserDesc*)d, L.n, (L.aux >> 24) & 15u, L.aux & 0xFFFFFFu, s); break;
+                case F_PHASER_CARRY: launch_phaser_carry((const PhaserDesc*)d, L.n, (L.aux >> 24) & 15u, s); break;
+                case F_PHASER_APPLY: launch_phaser_apply((const PhaserDesc*)d, L.n, (L.aux >> 24) & 15u, L.aux & 0xFFFFFFu, (L.aux & kPhaserSingleBit) != 0u, s); break;
                 case F_CHORUS: launch_chorus((const ChorusDesc*)d, L.n, L.aux & 0xFFFFFu, L.M, (L.aux & kChorusTermsBit) != 0u, s); break;
             }
         }
@@ -1054,6 +1064,7 @@ static int prepare_render(td_graph* g, size_t n_blocks, int bits, bool want_pcm,
         {K_CHORUS, launch_chorus_sum && launch_chorus, "chorus", "chorus"},
         {K_REVERB, launch_reverb_sum && launch_reverb, "reverb", "reverb"},
         {K_GATE, launch_gate_detect && launch_gate_carry && launch_gate_env && launch_gate_apply, "gate", "gate"},
+        {K_PHASER, launch_phaser_local && launch_phaser_carry && launch_phaser_apply, "phaser", "phaser"},
     };
     for (const auto& f : fx)
         if (!f.built)
@@ -1168,7 +1179,7 @@ static bool starts_afresh(const td_graph* g) {
     for (size_t vi : g->order) {
         const Vertex& v = g->vertices[vi];
         if (v.kind == K_NORMALIZE && !v.has_init_override) return false;
-        if ((v.kind == K_BAND_PASS || v.kind == K_COMPRESSOR || v.kind == K_EQ || v.kind == K_GATE) && v.state_slot >= 0 && !v.first_pending) return false;
+        if ((v.kind == K_BAND_PASS || v.kind == K_COMPRESSOR || v.kind == K_EQ || v.kind == K_GATE || v.kind == K_PHASER) && v.state_slot >= 0 && !v.first_pending) return false;
         if (v.line.d && !v.first_pending) return false;
     }
     return true;
@@ -1393,6 +1404,12 @@ static int graph_set_time_impl(td_graph* g, size_t time) {   // graph.rs:123-128
             case K_GATE:   // the gate restarts closed: the next submission's carries enter with (0, 0, H + 1)
                 if (v.state_slot >= 0) {
                     g->hstate[v.state_slot].gate = gate_closed(g, v);
+                    v.first_pending = true;
+                }
+                break;
+            case K_PHASER:   // the chain restarts from the zero state (the LFO does not: it runs on the graph's time)
+                if (v.state_slot >= 0) {
+                    phaser_rest(g, v);
                     v.first_pending = true;
                 }
                 break;
@@ -2063,6 +2080,30 @@ int td_gate_params(size_t sr, float threshold_db, float hysteresis_db, float hol
 }
 
 // (over the union of input and key edges: a key source is computed before the vertex it keys, like an input)
+// This engine's own phaser vertex (no reference counterpart; the definition is in include/termdaw_amd.h).
+int td_graph_add_phaser(td_graph* g, const char* name, float gain, float angle, float wet, int stages, float lo_hz, float hi_hz,
+                        float rate_hz, float feedback, float stereo, int shape) {
+    if (const char* why = phaser::check(g->sr, stages, lo_hz, hi_hz, rate_hz, feedback, stereo, shape)) return fail(std::string("phaser: ") + why);
+    const int slot = new_slot(g);   // (a run of zeroed slots: tdk::PhaserState)
+    for (int i = 1; i < kPhaserSlots; ++i) new_slot(g);
+    Vertex& v = add_vertex(g, name, gain, angle, wet, K_PHASER);
+    v.phaser_stages = stages;
+    v.phaser_shape = shape;
+    v.phaser_lo_hz = lo_hz;
+    v.phaser_hi_hz = hi_hz;
+    v.phaser_rate_hz = rate_hz;
+    v.phaser_feedback = feedback;
+    v.phaser_stereo = stereo;
+    v.state_slot = slot;
+    return 1;
+}
+int td_phaser_params(size_t sr, int stages, float lo_hz, float hi_hz, float rate_hz, float feedback, float stereo, int shape, double out[7]) {
+    if (!out) return fail("phaser_params: out is null");
+    if (const char* why = phaser::check(sr, stages, lo_hz, hi_hz, rate_hz, feedback, stereo, shape)) return fail(std::string("phaser: ") + why);
+    phaser::params(sr, stages, lo_hz, hi_hz, rate_hz, feedback, stereo, shape, out);
+    return 1;
+}
+
 static bool has_loop(size_t x, size_t b, const td_graph* g) {   // graph.rs:66-72
     if (x == b) return true;
     for (size_t y : g->edges[x])

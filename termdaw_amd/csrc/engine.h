@@ -76,7 +76,7 @@ struct td_flowwbank {
 namespace tde {
 
 enum Kind { K_SUM, K_NORMALIZE, K_SAMPLE_LOOP, K_SAMPLE_MULTI, K_SAMPLE_LERP, K_DEBUG_SINE, K_SYNTH,
-            K_SAMPSYN, K_ADSR, K_BAND_PASS, K_COMPRESSOR, K_EQ, K_DELAY, K_SATURATOR, K_CHORUS, K_REVERB, K_GATE, K_COUNT };
+            K_SAMPSYN, K_ADSR, K_BAND_PASS, K_COMPRESSOR, K_EQ, K_DELAY, K_SATURATOR, K_CHORUS, K_REVERB, K_GATE, K_PHASER, K_COUNT };
 
 struct SineNote { float note, vel; };
 struct SynthNote { float note, vel, env_t, rel_t, hz; };   // hz = 440 * 2^((note - 69) / 12), extensions.rs:503
@@ -137,6 +137,8 @@ struct Vertex {
     float chorus_delay_ms = 1, chorus_depth_ms = 0, chorus_rate_hz = 1, chorus_stereo = 0;
     float reverb_room = 0.5f, reverb_damp = 0.5f, reverb_width = 1.0f, reverb_size = 1.0f;   // K_REVERB
     float gate_threshold_db = 0, gate_hysteresis_db = 0, gate_hold_ms = 0, gate_attack_ms = 0, gate_release_ms = 1, gate_range_db = 0;   // K_GATE
+    int phaser_stages = 2, phaser_shape = 0;   // K_PHASER: N, TD_CHORUS_*
+    float phaser_lo_hz = 20, phaser_hi_hz = 20, phaser_rate_hz = 1, phaser_feedback = 0, phaser_stereo = 0;
     // The block of device memory a delay, saturator, chorus or reverb vertex carries from chunk to chunk: allocated when the vertex
     // is first compiled into a submission (take_line), never cleared, freed with the graph's vertices.
     //   K_DELAY             the last D values of (ul, ur), 16 D bytes: the rotation is total mod D, the words below min(total, D) hold values
@@ -159,10 +161,11 @@ struct Vertex {
     std::vector<SineNote> sine_notes;
     std::vector<SynthNote> notes;
     Voice3 ap{0, 0, 0}, ag{0, 0, 0};
-    // carried device state slot (Normalize / BandPass / Compressor / Eq / Gate), index into Graph::dstate
+    // carried device state slot (Normalize / BandPass / Compressor / Eq / Gate; a phaser: the first of kPhaserSlots consecutive
+    // ones, a tdk::PhaserState), index into Graph::dstate
     int state_slot = -1;
     // reset_normalization (extensions.rs:295-299) is kept on the host until the next render consumes it
-    bool first_pending = false;         // band-pass, compressor, eq, gate, delay, saturator, chorus, reverb (their state then restarts from zero): set_time since the vertex was last compiled into a submission (its descriptor's first_override)
+    bool first_pending = false;         // band-pass, compressor, eq, gate, phaser, delay, saturator, chorus, reverb (their state then restarts from zero): set_time since the vertex was last compiled into a submission (its descriptor's first_override)
     bool has_init_override = false;
     float init_override = 0.0f;
     // Normalize: the carried max is the result of a normalize scan (graph.rs:222-237), so a render is expected to
@@ -183,6 +186,9 @@ union StateSlot {
     tdk::GateState gate;
 };
 static_assert(sizeof(StateSlot) == 32, "carried vertex state: one 32-byte slot");
+// a phaser vertex' 2 x (N + 1) doubles take a run of slots
+constexpr int kPhaserSlots = (int)(sizeof(tdk::PhaserState) / sizeof(StateSlot));
+static_assert(sizeof(tdk::PhaserState) == kPhaserSlots * sizeof(StateSlot), "a phaser vertex' state: whole slots");
 
 struct KernelTime { std::string name; float ms = 0; size_t launches = 0; };
 

@@ -318,6 +318,45 @@ struct GateDesc {
     uint32_t key_k, key_term_mode;
 };
 
+// A phaser vertex (k_phaser_local<N> / k_phaser_carry<N> / k_phaser_apply<N>; the definition is in
+// include/termdaw_amd.h at td_graph_add_phaser): per channel N first-order all-pass sections in transposed direct form II
+// with one swept coefficient a[n] and a feedback fb z around the chain, f64.  One frame is the affine map S -> M[n] S + c[n] xs[n]
+// on the state S = (s_1 .. s_N, z) of dimension D = N + 1; M[n] depends on a[n] and fb alone, a[n] on the graph's ABSOLUTE frame
+// time (ChorusDesc::t0), so the scan's operator is a D x D matrix plus a D-vector per channel and frame: §3n's blocked scan with
+// a per-frame matrix.  A map is stored augmented and row-major, D rows of D + 1 words: {P | q}, S_out = P S_in + q.
+// Tiles of kPhaserTile frames; a lane owns kPhaserRun consecutive frames; a workgroup is ONE wave of kPhaserLanes lanes.
+// k_phaser_local evaluates the input terms, leaves the summed input in `x` and each tile's total map, per channel, in
+// agg[(2 t + c) D (D + 1) ..]; k_phaser_carry leaves the state entering each tile in carry[(2 t + c) D ..] (tile 0: *init, or 0
+// when init is null); k_phaser_apply rebuilds the lanes' maps and their in-tile prefix, each lane's entry state from there, and
+// runs the definition serially over the lane's run.  When one tile covers the chunk (every block pull) k_phaser_apply runs alone,
+// in an instantiation of its own (kPhaserSingleBit): the term loop runs inside it and tile 0 enters with *init (x, agg, carry
+// unused).
+constexpr uint32_t kPhaserLanes = 64;                            // lanes per workgroup
+constexpr uint32_t kPhaserRun = 32;                              // frames per lane
+constexpr uint32_t kPhaserTile = kPhaserRun * kPhaserLanes;      // frames per workgroup
+constexpr uint32_t kPhaserMaxD = 9;                              // D at 8 stages
+struct PhaserState { double s[2][kPhaserMaxD]; double pad[2]; };   // channel c's (s_1 .. s_N, z) in s[c][0 .. N]; five 32-byte slots
+struct PhaserDesc {
+    const InTerm* ins;      // k input terms (kinds 0 .. 4), in connect() order
+    float2* x;              // [frames] the summed input (three-launch form; null in the one-launch form)
+    float2* out;
+    PhaserState* state;     // carried across chunks / block pulls (k_phaser_apply stores it)
+    const PhaserState* init;   // the state entering tile 0: `state`, or nullptr after a set_time
+    double* agg;            // [2 n_tiles D (D + 1)] each tile's total map, per channel
+    double* carry;          // [2 n_tiles D] the state entering each tile, per channel
+    uint64_t t0;            // the graph's absolute frame time at the chunk's first frame (the LFO's n)
+    uint32_t k, term_mode, frames, n_tiles;
+    uint32_t stages;        // N: 2 | 4 | 6 | 8
+    uint32_t shape;         // TD_CHORUS_*
+    float wet;
+    uint32_t pad;
+    double am, ad;          // a[n] = am + ad lfo
+    double f;               // LFO cycles per frame
+    double fb;              // feedback
+    double stereo;          // the right channel's phase offset in cycles
+    PanGain pg;
+};
+
 // A parametric EQ vertex (k_eq_local / k_eq_carry / k_eq_apply; the definition is in include/termdaw_amd.h at
 // td_graph_add_eq): one RBJ biquad per channel in transposed direct form II, f64.  With z = (s1, s2) the recurrence is
 // z[n] = A z[n-1] + c x[n],  A = [[-a1, 1], [-a2, 0]],  c = (b1 - a1 b0, b2 - a2 b0),  y[n] = b0 x[n] + s1[n-1]: an affine scan
@@ -967,6 +1006,14 @@ __attribute__((weak)) void launch_gate_apply(const GateDesc* d, int n_desc, uint
 // ... and the keyed forms of detect and env (GateDesc::key_ins / cls; launches whose aux carries kKeyedBit)
 __attribute__((weak)) void launch_gate_detect_keyed(const GateDesc* d, int n_desc, uint32_t max_tiles, hipStream_t s);
 __attribute__((weak)) void launch_gate_env_keyed(const GateDesc* d, int n_desc, uint32_t max_tiles, hipStream_t s);
+// Weak for the same reason: a level's phaser vertices of ONE stage count (the kernels are templates on it), grid.x = n_tiles
+// (every descriptor's; the carry: one workgroup per vertex).  A launch's aux packs tile count, stage count and, for
+// launch_phaser_apply, `single`: the instantiation with the term loop inside, entered with the carried state.
+constexpr uint32_t kPhaserSingleBit = 0x80000000u;
+inline uint32_t phaser_aux(uint32_t n_tiles, uint32_t stages, bool single) { return n_tiles | (stages << 24) | (single ? kPhaserSingleBit : 0u); }
+__attribute__((weak)) void launch_phaser_local(const PhaserDesc* d, int n_desc, uint32_t stages, uint32_t n_tiles, hipStream_t s);
+__attribute__((weak)) void launch_phaser_carry(const PhaserDesc* d, int n_desc, uint32_t stages, hipStream_t s);
+__attribute__((weak)) void launch_phaser_apply(const PhaserDesc* d, int n_desc, uint32_t stages, uint32_t n_tiles, bool single, hipStream_t s);
 // Weak for the same reason: a level's reverb vertices.  launch_reverb_sum: grid.x from `frames`; launch_reverb: one workgroup per
 // descriptor, `form` 0 the serial walk of each comb's one-pole, 1 the wave scan.
 __attribute__((weak)) void launch_reverb_sum(const ReverbDesc* d, int n_desc, uint32_t frames, hipStream_t s);

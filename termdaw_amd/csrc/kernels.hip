@@ -6340,6 +6340,240 @@ __global__ __launch_bounds__(kThreads) void k_gate_apply(const GateDesc* __restr
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// k_phaser_local / k_phaser_carry / k_phaser_apply: the phaser vertex (kernels.h PhaserDesc).  No reference
+// counterpart; the definition is the header's (td_graph_add_phaser): N all-pass sections with one swept coefficient and a
+// feedback around the chain, f64.  Templates on N: a map's D (D + 1) words, D = N + 1, live in registers under constant indices.
+// A workgroup is one wave; a map's word e of lane t lies at pm[e kPhaserLanes + t], frame j of lane t at xs[j kPhaserLanes + t].
+// ------------------------------------------------------------------------------------------------
+// a[n] at the absolute frame n (the chorus' LFO and its phase arithmetic)
+TD_DEV double phaser_coef(const PhaserDesc& d, uint64_t n, uint32_t ch) {
+    double th = (double)n * d.f + (ch ? d.stereo : 0.0);
+    th = th - floor(th);
+    return d.am + d.ad * chorus_lfo(d.shape, th);
+}
+// one frame of the definition, one channel: v = xs + fb z;  per section w = a v + s_k, s_k = v - a w, v = w;  z = v
+template <int N>
+TD_DEV double phaser_frame(double (&S)[N + 1], double a, double fb, double xs) {
+    double v = xs + fb * S[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        const double w = a * v + S[k];
+        S[k] = v - a * w;
+        v = w;
+    }
+    S[N] = v;
+    return v;
+}
+// ... and of a map {P | q}: every column goes through the definition, the basis columns with xs = 0
+template <int N>
+TD_DEV void phaser_map_frame(double (&P)[(N + 1) * (N + 2)], double a, double fb, double xs) {
+    constexpr int D = N + 1, W = N + 2;
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+        double v = j == D ? xs + fb * P[N * W + j] : fb * P[N * W + j];
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+            const double w = a * v + P[k * W + j];
+            P[k * W + j] = v - a * w;
+            v = w;
+        }
+        P[N * W + j] = v;
+    }
+}
+// The map of the lane's run of channel ch: the identity pushed through kPhaserRun frames (frames from `frames` on hold x = 0)
+template <int N>
+TD_DEV void phaser_lane_map(const PhaserDesc& d, uint32_t f0, uint32_t ch, const float2* xs, double (&P)[(N + 1) * (N + 2)]) {
+    constexpr int D = N + 1, W = N + 2;
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+        for (int j = 0; j < W; ++j) P[i * W + j] = i == j ? 1.0 : 0.0;
+    const double fb = d.fb;
+#pragma unroll 1
+    for (uint32_t j = 0; j < kPhaserRun; ++j) {
+        const float2 x = xs[j * kPhaserLanes + threadIdx.x];
+        const float xf = ch ? x.y : x.x;
+        phaser_map_frame<N>(P, phaser_coef(d, d.t0 + (uint64_t)(f0 + j), ch), fb, eq_in(xf));
+    }
+}
+// The lanes' maps joined in lane order, Hillis-Steele: behind it pm holds, per lane, the map of lanes 0 .. t.  A join is own o
+// left, one received column at a time: the lane keeps its own map in registers, reads a column of the left one, and leaves the
+// product's column in its own words of pm, which every lane that wanted them has read by then.
+template <int N>
+TD_DEV void phaser_lane_scan(double (&P)[(N + 1) * (N + 2)], double* pm) {
+    constexpr int D = N + 1, W = N + 2;
+    const uint32_t tid = threadIdx.x;
+#pragma unroll
+    for (int e = 0; e < D * W; ++e) pm[e * kPhaserLanes + tid] = P[e];
+    __syncthreads();
+#pragma unroll 1
+    for (uint32_t off = 1; off < kPhaserLanes; off <<= 1) {
+        const bool act = tid >= off;
+#pragma unroll
+        for (int j = 0; j < W; ++j) {
+            double c[D];
+#pragma unroll
+            for (int i = 0; i < D; ++i) c[i] = act ? pm[(i * W + j) * kPhaserLanes + tid - off] : 0.0;
+            __syncthreads();
+            if (act) {
+#pragma unroll
+                for (int i = 0; i < D; ++i) {
+                    double n = P[i * W] * c[0];
+#pragma unroll
+                    for (int k = 1; k < D; ++k) n = n + P[i * W + k] * c[k];
+                    if (j == D) n = n + P[i * W + D];
+                    pm[(i * W + j) * kPhaserLanes + tid] = n;
+                }
+            }
+        }
+        __syncthreads();
+        if (act) {
+#pragma unroll
+            for (int e = 0; e < D * W; ++e) P[e] = pm[e * kPhaserLanes + tid];
+        }
+    }
+}
+template <int N>
+__global__ __launch_bounds__(kPhaserLanes) void k_phaser_local(const PhaserDesc* __restrict__ descs) {
+    constexpr int D = N + 1, W = N + 2;
+    const PhaserDesc& d = descs[blockIdx.y];
+    if (blockIdx.x >= d.n_tiles) return;
+    __shared__ double pm[D * W * kPhaserLanes];
+    __shared__ float2 xs[kPhaserTile];
+    const uint32_t tid = threadIdx.x, M = d.frames, f0 = blockIdx.x * kPhaserTile + tid * kPhaserRun;
+#pragma unroll 1
+    for (uint32_t h = 0; h < kPhaserRun / 4; ++h) {   // (frames beyond M sum to 0)
+        const uint32_t m = f0 + 4u * h;
+        float4 a0, a1;
+        sum_inputs_pairs(d.ins, d.k, d.term_mode, m, m + 2u, M, a0, a1);
+        store_pair(d.x, m, M, a0);
+        store_pair(d.x, m + 2u, M, a1);
+        xs[(4u * h) * kPhaserLanes + tid] = make_float2(a0.x, a0.y);
+        xs[(4u * h + 1u) * kPhaserLanes + tid] = make_float2(a0.z, a0.w);
+        xs[(4u * h + 2u) * kPhaserLanes + tid] = make_float2(a1.x, a1.y);
+        xs[(4u * h + 3u) * kPhaserLanes + tid] = make_float2(a1.z, a1.w);
+    }
+    double* agg = d.agg + (size_t)blockIdx.x * (2 * D * W);
+#pragma unroll 1
+    for (uint32_t ch = 0; ch < 2; ++ch) {
+        double P[D * W];
+        phaser_lane_map<N>(d, f0, ch, xs, P);
+        phaser_lane_scan<N>(P, pm);
+        // the last lane's words are the tile's
+        for (uint32_t e = tid; e < (uint32_t)(D * W); e += kPhaserLanes) gstored(agg + ch * (D * W) + e, pm[e * kPhaserLanes + kPhaserLanes - 1u]);
+        __syncthreads();
+    }
+}
+// entry[t + 1] = P[t] entry[t] + q[t], entry[0] = *init: the tiles in series, a matrix-vector product each.  One wave per vertex;
+// lane 16 c + i holds row i of channel c and takes the next tile's row while the product of this one runs.
+template <int N>
+__global__ __launch_bounds__(kPhaserLanes) void k_phaser_carry(const PhaserDesc* __restrict__ descs) {
+    constexpr int D = N + 1, W = N + 2;
+    const PhaserDesc& d = descs[blockIdx.x];
+    __shared__ double se[2][16];
+    const uint32_t tid = threadIdx.x, ch = tid >> 4, row = tid & 15u, n = d.n_tiles;
+    const bool act = ch < 2u && row < (uint32_t)D;
+    double e = act && d.init ? gloadd(&d.init->s[ch][row]) : 0.0;
+    const double* a = d.agg + (act ? (size_t)ch * (D * W) + (size_t)row * W : 0u);
+    double cur[W], nxt[W];
+#pragma unroll
+    for (int k = 0; k < W; ++k) cur[k] = act && n > 1u ? gloadd(a + k) : 0.0;
+    for (uint32_t t = 0; t < n; ++t) {
+        if (act) gstored(d.carry + ((size_t)2u * t + ch) * D + row, e);
+        if (t + 1u == n) break;   // (the last tile's map is no one's entry)
+        const bool more = act && t + 2u < n;
+#pragma unroll
+        for (int k = 0; k < W; ++k) nxt[k] = more ? gloadd(a + (size_t)(t + 1u) * (2 * D * W) + k) : 0.0;
+        if (act) se[ch][row] = e;
+        __syncthreads();
+        if (act) {
+            double s = cur[0] * se[ch][0];
+#pragma unroll
+            for (int k = 1; k < D; ++k) s = s + cur[k] * se[ch][k];
+            e = s + cur[D];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < W; ++k) cur[k] = nxt[k];
+    }
+}
+// SINGLE: the chunk is this one tile -- the term loop runs here and the tile enters with *init (a block pull: one launch)
+template <int N, bool SINGLE>
+__global__ __launch_bounds__(kPhaserLanes) void k_phaser_apply(const PhaserDesc* __restrict__ descs) {
+    constexpr int D = N + 1, W = N + 2;
+    const PhaserDesc& d = descs[blockIdx.y];
+    if (blockIdx.x >= d.n_tiles) return;
+    __shared__ double pm[D * W * kPhaserLanes];
+    __shared__ float2 xs[kPhaserTile];
+    const uint32_t tid = threadIdx.x, M = d.frames, f0 = blockIdx.x * kPhaserTile + tid * kPhaserRun;
+    const float wet = d.wet;
+    const double fb = d.fb;
+#pragma unroll 1
+    for (uint32_t h = 0; h < kPhaserRun / 4; ++h) {   // (0 from `frames` on)
+        const uint32_t m = f0 + 4u * h;
+        float4 a0, a1;
+        if (SINGLE) sum_inputs_pairs(d.ins, d.k, d.term_mode, m, m + 2u, M, a0, a1);
+        else { a0 = load_pair(d.x, m, M); a1 = load_pair(d.x, m + 2u, M); }
+        xs[(4u * h) * kPhaserLanes + tid] = make_float2(a0.x, a0.y);
+        xs[(4u * h + 1u) * kPhaserLanes + tid] = make_float2(a0.z, a0.w);
+        xs[(4u * h + 2u) * kPhaserLanes + tid] = make_float2(a1.x, a1.y);
+        xs[(4u * h + 3u) * kPhaserLanes + tid] = make_float2(a1.z, a1.w);
+    }
+#pragma unroll 1
+    for (uint32_t ch = 0; ch < 2; ++ch) {
+        // the state entering the tile
+        double S[D];
+#pragma unroll
+        for (int i = 0; i < D; ++i) {
+            if (SINGLE) S[i] = d.init ? gloadd(&d.init->s[ch][i]) : 0.0;
+            else S[i] = gloadd(d.carry + ((size_t)2u * blockIdx.x + ch) * D + i);
+        }
+        {
+            double P[D * W];
+            phaser_lane_map<N>(d, f0, ch, xs, P);
+            phaser_lane_scan<N>(P, pm);
+        }
+        // ... and the lane's run: the map of the lanes before it, applied
+        if (tid) {
+            double T[D];
+#pragma unroll
+            for (int i = 0; i < D; ++i) {
+                double n = pm[(i * W) * kPhaserLanes + tid - 1u] * S[0];
+#pragma unroll
+                for (int k = 1; k < D; ++k) n = n + pm[(i * W + k) * kPhaserLanes + tid - 1u] * S[k];
+                T[i] = n + pm[(i * W + D) * kPhaserLanes + tid - 1u];
+            }
+#pragma unroll
+            for (int i = 0; i < D; ++i) S[i] = T[i];
+        }
+        __syncthreads();
+        // the definition, serially; the lerp (adsr.rs:42, f32) takes the channel's place in xs
+#pragma unroll 1
+        for (uint32_t j = 0; j < kPhaserRun; ++j) {
+            const uint32_t m = f0 + j;
+            if (m >= M) break;
+            float2 x = xs[j * kPhaserLanes + tid];
+            const float xf = ch ? x.y : x.x;
+            const float p = (float)phaser_frame<N>(S, phaser_coef(d, d.t0 + (uint64_t)m, ch), fb, eq_in(xf));
+            const float o = xf + wet * (p - xf);
+            if (ch) x.y = o; else x.x = o;
+            xs[j * kPhaserLanes + tid] = x;
+            if (m + 1u == M) {   // the chunk's last frame: what the next chunk / block pull enters with
+#pragma unroll
+                for (int i = 0; i < D; ++i) gstored(&d.state->s[ch][i], S[i]);
+            }
+        }
+    }
+#pragma unroll 1
+    for (uint32_t j = 0; j < kPhaserRun; j += 2u) {
+        const uint32_t m = f0 + j;
+        if (m >= M) break;
+        const float2 a = xs[j * kPhaserLanes + tid], b = xs[(j + 1u) * kPhaserLanes + tid];
+        store_pair(d.out, m, M, epilogue4(make_float4(a.x, a.y, b.x, b.y), d.pg));
+    }
+}
+
 constexpr int kMaxGridY = 65535;
 
 // Batched launches put the vertex index in grid.y (limit 65535): larger batches go out in slices.
@@ -6683,6 +6917,29 @@ void launch_gate_env_keyed(const GateDesc* d, int n, uint32_t max_tiles, hipStre
 void launch_gate_apply(const GateDesc* d, int n, uint32_t max_tiles, hipStream_t s) {
     for (int o = 0; o < n && max_tiles; o += kMaxGridY)
         hipLaunchKernelGGL(k_gate_apply, dim3(max_tiles, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
+}
+// (a launch holds the vertices of one stage count: the kernels are templates on it)
+#define TD_PHASER_STAGES(CALL)                \
+    switch (stages) {                         \
+        case 2: { constexpr int N = 2; CALL; break; } \
+        case 4: { constexpr int N = 4; CALL; break; } \
+        case 6: { constexpr int N = 6; CALL; break; } \
+        case 8: { constexpr int N = 8; CALL; break; } \
+        default: break;                       \
+    }
+void launch_phaser_local(const PhaserDesc* d, int n, uint32_t stages, uint32_t n_tiles, hipStream_t s) {
+    for (int o = 0; o < n && n_tiles; o += kMaxGridY)
+        TD_PHASER_STAGES(hipLaunchKernelGGL(k_phaser_local<N>, dim3(n_tiles, std::min(n - o, kMaxGridY)), dim3(kPhaserLanes), 0, s, d + o));
+}
+void launch_phaser_carry(const PhaserDesc* d, int n, uint32_t stages, hipStream_t s) {
+    if (n <= 0) return;
+    TD_PHASER_STAGES(hipLaunchKernelGGL(k_phaser_carry<N>, dim3(n), dim3(kPhaserLanes), 0, s, d));
+}
+void launch_phaser_apply(const PhaserDesc* d, int n, uint32_t stages, uint32_t n_tiles, bool single, hipStream_t s) {
+    for (int o = 0; o < n && n_tiles; o += kMaxGridY) {
+        if (single) { TD_PHASER_STAGES(hipLaunchKernelGGL((k_phaser_apply<N, true>), dim3(n_tiles, std::min(n - o, kMaxGridY)), dim3(kPhaserLanes), 0, s, d + o)); }
+        else { TD_PHASER_STAGES(hipLaunchKernelGGL((k_phaser_apply<N, false>), dim3(n_tiles, std::min(n - o, kMaxGridY)), dim3(kPhaserLanes), 0, s, d + o)); }
+    }
 }
 void launch_sample_loop(const LoopDesc* d, int n, uint32_t frames, hipStream_t s) {
     if (!n || !frames) return;

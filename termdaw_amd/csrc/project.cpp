@@ -21,6 +21,7 @@
 #include "devmem.h"
 #include "eq_math.h"
 #include "gate_math.h"
+#include "phaser_math.h"
 #include "lua_subset.h"
 #include "reverb_math.h"
 #include "master.h"
@@ -112,6 +113,7 @@ struct EqCall { std::string name; float gain, angle, wet; int kind; float freq_h
 struct DelayCall { std::string name; float gain, angle, wet, time_ms, feedback, cross; };
 struct ChorusCall { std::string name; float gain, angle, wet; int voices; float delay_ms, depth_ms, rate_hz, stereo; int shape; };
 struct ReverbCall { std::string name; float gain, angle, wet, room, damp, width, size; };
+struct PhaserCall { std::string name; float gain, angle, wet; int stages; float lo_hz, hi_hz, rate_hz, feedback, stereo; int shape; };
 struct GateCall { std::string name; float gain, angle, wet, threshold_db, hysteresis_db, hold_ms, attack_ms, release_ms, range_db; };
 struct SatCall { std::string name; float gain, angle, wet; int kind; float drive_db, bias, out_db; int oversample; };
 
@@ -236,6 +238,7 @@ int do_refresh(td_state* s, const std::string& contents) {
     std::vector<ChorusCall> choruses;
     std::vector<ReverbCall> reverbs;
     std::vector<GateCall> gates;
+    std::vector<PhaserCall> phasers;
     size_t cs = s->cs, render_sr = s->render_sr, bd = s->bd;
     // std::mem::take (state.rs:79-80): the locals start from the previous values, the State's own fields are left
     // EMPTY until the script has run (state.rs:169-170) -- so they stay empty when the script fails
@@ -476,6 +479,23 @@ int do_refresh(td_state* s, const std::string& contents) {
                 fnum(c.hold_ms) + "," + fnum(c.attack_ms) + "," + fnum(c.release_ms) + "," + fnum(c.range_db) + ")\n";
         return Value::nil();
     });
+    lua.set_function("add_phaser", [&](const std::vector<Value>& a) {   // this engine's own vertex (termdaw_amd.h td_graph_add_phaser); shape by name
+        const char* f = "add_phaser";
+        static const char* const shapes[2] = {"sine", "triangle"};
+        const std::string shape = to_str(f, a, 10);
+        int k = 0;
+        while (k < 2 && shape != shapes[k]) ++k;
+        if (k == 2) throw LuaError{"add_phaser: unknown shape \"" + shape + "\" (one of sine, triangle)"};
+        const float stages = to_f32(f, a, 4);
+        if (!(stages == 2.0f || stages == 4.0f || stages == 6.0f || stages == 8.0f)) throw LuaError{"add_phaser: stages must be 2, 4, 6 or 8"};
+        phasers.push_back({to_str(f, a, 0), to_f32(f, a, 1), to_f32(f, a, 2), to_f32(f, a, 3), (int)stages, to_f32(f, a, 5), to_f32(f, a, 6), to_f32(f, a, 7), to_f32(f, a, 8), to_f32(f, a, 9), k});
+        auto& c = phasers.back();
+        // (out-of-range parameters are rejected here, where the line is known)
+        if (const char* why = tde::phaser::check(psr, c.stages, c.lo_hz, c.hi_hz, c.rate_hz, c.feedback, c.stereo, c.shape)) throw LuaError{std::string("add_phaser: ") + why};
+        dump += std::string(f) + "(\"" + c.name + "\"," + fnum(c.gain) + "," + fnum(c.angle) + "," + fnum(c.wet) + "," + std::to_string(c.stages) + "," + fnum(c.lo_hz) + "," +
+                fnum(c.hi_hz) + "," + fnum(c.rate_hz) + "," + fnum(c.feedback) + "," + fnum(c.stereo) + ",\"" + shape + "\")\n";
+        return Value::nil();
+    });
     lua.set_function("connect", [&](const std::vector<Value>& a) {
         edges.push_back({to_str("connect", a, 0), to_str("connect", a, 1)});
         dump += "connect(\"" + edges.back().first + "\",\"" + edges.back().second + "\")\n";
@@ -609,6 +629,8 @@ int do_refresh(td_state* s, const std::string& contents) {
         if (!td_graph_add_reverb(s->g, c.name.c_str(), c.gain, c.angle, c.wet, c.room, c.damp, c.width, c.size)) return 0;
     for (auto& c : gates)
         if (!td_graph_add_gate(s->g, c.name.c_str(), c.gain, c.angle, c.wet, c.threshold_db, c.hysteresis_db, c.hold_ms, c.attack_ms, c.release_ms, c.range_db)) return 0;
+    for (auto& c : phasers)
+        if (!td_graph_add_phaser(s->g, c.name.c_str(), c.gain, c.angle, c.wet, c.stages, c.lo_hz, c.hi_hz, c.rate_hz, c.feedback, c.stereo, c.shape)) return 0;
     for (auto& e : edges) td_graph_connect(s->g, e.first.c_str(), e.second.c_str());   // failures only warn (state.rs:459)
     for (auto& e : key_edges) td_graph_connect_key(s->g, e.first.c_str(), e.second.c_str());   // (after the edges; failures only warn, like theirs)
     td_graph_set_output(s->g, s->output_vertex.c_str());

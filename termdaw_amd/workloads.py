@@ -169,7 +169,7 @@ class ProjectScript:
         self.calls = {k: [] for k in (
             "load_sample", "load_resource", "load_midi_floww", "add_sum", "add_normalize", "add_sampleloop",
             "add_sample_multi", "add_sample_lerp", "add_debug_sine", "add_synth", "add_sampsyn", "add_adsr",
-            "add_bandpass", "add_compressor", "add_eq", "add_delay", "add_saturator", "add_chorus", "add_reverb", "add_gate", "connect", "connect_key")}
+            "add_bandpass", "add_compressor", "add_eq", "add_delay", "add_saturator", "add_chorus", "add_reverb", "add_gate", "add_phaser", "connect", "connect_key")}
         self.resources = {}                 # path -> bytes (load_resource)
         self.script_order = []              # (fn, args) in call order, for to_lua()
 
@@ -268,6 +268,10 @@ class ProjectScript:
         """This engine's own vertex (include/termdaw_amd.h td_graph_add_gate): no reference counterpart."""
         self._rec("add_gate", name, gain, angle, wet, threshold_db, hysteresis_db, hold_ms, attack_ms, release_ms, range_db)
 
+    def add_phaser(self, name, gain, angle, wet, stages, lo_hz, hi_hz, rate_hz, feedback, stereo, shape):
+        """This engine's own vertex (include/termdaw_amd.h td_graph_add_phaser): no reference counterpart.  shape: the string name."""
+        self._rec("add_phaser", name, gain, angle, wet, stages, lo_hz, hi_hz, rate_hz, feedback, stereo, shape)
+
     def connect(self, a, b):
         self._rec("connect", a, b)
 
@@ -341,6 +345,8 @@ class ProjectScript:
             g.add_reverb(*args)
         for args in self.calls["add_gate"]:
             g.add_gate(*args)
+        for args in self.calls["add_phaser"]:
+            g.add_phaser(*args)
         for a, b in self.calls["connect"]:
             g.connect(a, b)
         for a, b in self.calls["connect_key"]:   # (after the connect calls, as the front-end applies them)

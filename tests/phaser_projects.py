@@ -1,0 +1,96 @@
+"""Projects that contain phaser vertices (TEST INFRASTRUCTURE, a generator of its own: the generators the existing tests and
+soaks draw from keep producing the graphs they always did).
+
+* base_project / grid_cases / E: the inputs, the parameter grid and the bound's constant that tests/test_gpu_phaser.py (on the
+  device) and tests/test_phaser_host.py (the derivation of E, on the CPU) share.  The inputs are eq_projects': drums, noise and a
+  burst between silences.
+* random_phaser_project / write_projects: a project of tests/test_gpu_fuzz.py's generator with one to three phaser vertices
+  spliced into edges it already has and, now and then, one more as the output (the sanitizer run's input)."""
+import itertools
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import eq_projects as EP  # noqa: E402
+import np_phaser as NP  # noqa: E402
+
+RATES = EP.RATES
+INPUTS = EP.INPUTS
+SHAPES = ("sine", "triangle")
+# The GPU test's bound, per value: |y - want| <= 2^-23 |want| + E max|want|.  E_EMULATED is the worst
+# max|blocked - serial| / max|serial| that np_phaser.blocked() -- the tiled scan in numpy, with the kernels' tile geometry and
+# join order -- shows over grid_cases() on the three inputs at the three rates, rounded up (test_phaser_host.py recomputes it and
+# fails above this figure); the device's own order of the same float64 operations gets the project's factor 8 on top.  E must
+# stay <= 2^-28, a sixteenth of half an f32 ulp at the render's peak.
+E_EMULATED = 2.0e-14
+E = 8 * E_EMULATED
+assert E <= 2 ** -28
+
+base_project = EP.base_project
+
+
+def grid_cases(sr):
+    """(stages, lo_hz, hi_hz, rate_hz, feedback, stereo, shape): the issue's grid at rate sr, 108 cases -- stages x sweep x rate x
+    feedback; shape and stereo alternate with the case's index, so that all four pairs occur."""
+    out = []
+    for i, (n, (lo, hi), rate, fb) in enumerate(itertools.product((2, 4, 6, 8), ((20.0, 0.45 * sr), (200.0, 2000.0), (1000.0, 1000.0)),
+                                                                  (0.01, 1.0, 20.0), (-0.95, 0.0, 0.95))):
+        out.append((n, lo, hi, rate, fb, 0.25 * ((i // 2) % 2), SHAPES[i % 2]))
+    return out
+
+
+def spec(api, sr, case):
+    """What np_phaser takes, on the engine's own constants."""
+    return NP.spec(api.phaser_params(sr, *case), case[5], case[6])
+
+
+def add_phaser(p, name, src, case, wet=1.0, gain=1.0, angle=0.0):
+    p.add_phaser(name, gain, angle, wet, *case)
+    p.connect(src, name)
+
+
+def random_phaser_params(rng):
+    lo, hi = [(20.0, 21600.0), (200.0, 2000.0), (1000.0, 1000.0), (20.0, 20.0)][int(rng.integers(0, 4))]   # (the driver opens every project at 48 kHz)
+    return (float(rng.choice([1.0, 1.0, 0.5, 0.0])),                     # wet
+            int(rng.choice([2, 4, 6, 8])), lo, hi,
+            float(rng.choice([0.01, 1.0, 20.0])),                         # rate_hz
+            float(rng.choice([-0.95, 0.0, 0.5, 0.95])),                   # feedback
+            float(rng.choice([0.0, 0.25, 0.5])),                          # stereo
+            str(rng.choice(SHAPES)))
+
+
+def random_phaser_project(seed, allow_sinf=True):
+    import test_gpu_fuzz as F
+    p = F.random_project(seed, allow_sinf=allow_sinf)
+    rng = np.random.default_rng(990_000 + seed)
+    gains, angles = [1.0, 1.0005, 0.5, 1.7, -0.8], [0.0, 0.0009, 30.0, -75.0, 120.0]
+    edges = [i for i, (fn, a) in enumerate(p.script_order) if fn == "connect" and a[0] != a[1]]
+    picks = sorted(set(int(i) for i in rng.choice(edges, size=min(len(edges), int(rng.integers(1, 4))), replace=False)), reverse=True)
+    first_add = min(i for i, (fn, _) in enumerate(p.script_order) if fn.startswith("add_"))
+    phasers = []
+    for k, i in enumerate(picks):   # (from the back: the indices in front stay valid)
+        a, b = p.script_order[i][1]
+        nm = "ph%d" % k
+        ci = p.calls["connect"].index((a, b))
+        p.calls["connect"][ci:ci + 1] = [(a, nm), (nm, b)]
+        p.script_order[i:i + 1] = [("connect", (a, nm)), ("connect", (nm, b))]
+        phasers.append((nm, float(rng.choice(gains)), float(rng.choice(angles))) + random_phaser_params(rng))
+    if rng.random() < 0.3:   # ... and one as the output, behind whatever the output was
+        nm = "phout"
+        phasers.append((nm, 1.0, 0.0) + random_phaser_params(rng))
+        p.calls["connect"].append((p.output_vertex, nm))
+        oi = max(i for i, (fn, _) in enumerate(p.script_order) if fn == "set_output")
+        p.script_order[oi:oi + 1] = [("connect", (p.output_vertex, nm)), ("set_output", (nm,))]
+        p.output_vertex = nm
+    for c in phasers:
+        p.calls["add_phaser"].append(c)
+        p.script_order.insert(first_add, ("add_phaser", c))
+    return p
+
+
+def write_projects(args):
+    """(base dir, seeds) -> the project dirs written: project.lua + assets, meta.txt (the block length)."""
+    base, seeds = args
+    return [EP.write_project(random_phaser_project(seed), os.path.join(base, "s%d" % seed)) for seed in seeds]
