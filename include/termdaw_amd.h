@@ -407,8 +407,45 @@ int td_graph_add_phaser(td_graph* g, const char* name, float gain, float angle, 
 /* Host only, no GPU: the phaser vertex' constants at rate sr, exactly the doubles the engine uses -- out[0 .. 6] = N, a_lo, a_hi,
  * am, ad, f, fb.  The same range checks as td_graph_add_phaser. */
 int td_phaser_params(size_t sr, int stages, float lo_hz, float hi_hz, float rate_hz, float feedback, float stereo, int shape, double out[7]);
+/* A vocoder vertex: a keyed band-pass bank (the channel vocoder) -- THIS ENGINE'S OWN: no reference counterpart (the reference
+ * reaches it only through LV2 plugins, add_lv2fx, which this engine parses and drops).  The vertex sums its inputs
+ * like every input vertex (sum_inputs, extensions.rs:310-319): that sum (l, r) is the CARRIER.  Its MODULATOR comes through key
+ * edges (td_graph_connect_key below): the key frames (kl, kr) are the f32 sum of its key sources.  Without a key edge the vertex
+ * uses its own summed input as modulator, (kl, kr) = (l, r), as an unkeyed compressor listens to itself -- so a vocoder keyed by
+ * its own source is bit for bit the unkeyed one.
+ *   Constants, f64, once on the host, each from the f32 parameter widened to f64 (td_vocoder_params returns them), B = bands:
+ *     f_b = lo_hz (hi_hz / lo_hz)^(b / (B - 1)),  b = 0 .. B - 1;
+ *     (b0, b1, b2, a1, a2)_b: the RBJ band-pass with constant 0 dB peak gain (td_graph_add_eq's TD_EQ_BANDPASS formulas) at
+ *     frequency f_b (f64, not rounded to f32) and `q`;
+ *     a = exp(-1 / (response_ms sr / 1000));  g = 10^(out_db / 20).
+ *   Per frame n, in f64 on the f32 sums with no FMA contraction, in the order written.  A non-finite carrier sample enters as
+ *   0 (the EQ's rule); a modulator frame with a NaN or infinite sample enters as m = 0 (the key frame's rule of
+ *   td_graph_connect_key):
+ *     1. m = 0.5 ((double)kl + (double)kr)
+ *     2. for every band b, three biquads BP_b with the same coefficients and a state (s1, s2) each, in td_graph_add_eq's order
+ *        y = b0 x + s1;  s1 = (b1 x - a1 y) + s2;  s2 = b2 x - a2 y:     cl_b = BP_b(l);  cr_b = BP_b(r);  km_b = BP_b(m)
+ *     3. e_b = a e_b + (1 - a) |km_b|            (1 - a is rounded once; a rectifier and a one-pole low-pass: linear on purpose)
+ *     4. sl = 0;  for b = 0 .. B - 1: sl = sl + e_b cl_b;   pl = (float)(g sl);   pr likewise from cr_b
+ *   Output: out = x + wet * (p - x) in f32 (adsr.rs:42) -- a non-finite x comes out as what IEEE makes of it -- then pan and gain.
+ *   wet < 0.0001: the summed input passes through untouched (a plain k_sum launch); the vertex ignores its key edges bit for
+ *   bit and its state stays as it is.
+ * State: seven doubles per band -- (s1, s2) of the three biquads, and e_b -- zero at time 0; carried between consecutive block
+ * pulls and between the chunks of a render, restarted from zero by td_graph_set_time / td_graph_change_time / td_graph_reset.
+ * No latency, no tail.
+ * Ranges, rejected with a td_last_error that names the parameter (NaN included): bands 4 | 8 | 16; lo_hz >= 40; hi_hz <= 0.45 sr;
+ * lo_hz < hi_hz; q [0.5, 20]; response_ms [0.1, 1000]; out_db [-24, 48].  `wet` is clamped to [0, 1].
+ * Under "band_mode" 2 / "sine_mode" 2 everything upstream of a vocoder vertex that is not dry -- of its inputs and of its key --
+ * takes the exact forms: the gain on the carrier is the modulator's envelope, no static bound of it exists.
+ * Not part of the vertex: an unvoiced / sibilance path, a separate attack and release, formant shift, more than 16 bands. */
+int td_graph_add_vocoder(td_graph* g, const char* name, float gain, float angle, float wet, int bands, float lo_hz, float hi_hz,
+                         float q, float response_ms, float out_db);
+/* Host only, no GPU: the vocoder vertex' constants at rate sr, exactly the doubles the engine uses -- out[6 b .. 6 b + 5] = f_b,
+ * b0, b1, b2, a1, a2 for b = 0 .. bands - 1, then out[6 bands] = a, out[6 bands + 1] = g.  `cap`: the doubles `out` holds, at least
+ * 6 bands + 2.  The same range checks as td_graph_add_vocoder. */
+int td_vocoder_params(size_t sr, int bands, float lo_hz, float hi_hz, float q, float response_ms, float out_db, double* out, size_t cap);
 int td_graph_connect(td_graph* g, const char* a, const char* b);          /* graph.rs:80-96 (+58-78) */
-/* A key edge (sidechain) from any vertex `a` to a compressor or gate vertex `b` -- THIS ENGINE'S OWN, like the two vertices.  A
+/* A key edge (sidechain) from any vertex `a` to a compressor, gate or vocoder vertex `b` -- THIS ENGINE'S OWN, like the vertices.  A
+ * vocoder vertex takes its MODULATOR from the key frames defined here (td_graph_add_vocoder above); for the other two: a
  * vertex with at least one key edge takes its LEVEL from the sum of its key sources; everything else is as without: it processes
  * the sum of its inputs, carries the same state, keeps its wet mix, pan and gain.
  *   The key frames (kl[n], kr[n]) are the f32 sum of the key sources' outputs, each with its own pan and gain applied, summed in
@@ -421,7 +458,7 @@ int td_graph_connect(td_graph* g, const char* a, const char* b);          /* gra
  *   A key is not an input: td_graph_check's "output receives no inputs" is unchanged, and a keyed vertex without inputs
  *   processes silence.  A dry vertex (wet < 0.0001) ignores its key edges: its output is bit for bit that of the same vertex
  *   without them.
- * Returns 0 (td_last_error) for an unknown name (td_graph_connect's messages); when `b` is not a compressor or gate vertex
+ * Returns 0 (td_last_error) for an unknown name (td_graph_connect's messages); when `b` is not a compressor, gate or vocoder vertex
  * ("connect_key: <b> takes no key input"); when the edge would close a loop.  The loop test of td_graph_connect and of
  * td_graph_connect_key runs over the union of input and key edges.  td_graph_reset clears key edges, as it clears edges.  A key
  * source is rendered like an input, also when only the key edge reaches it.

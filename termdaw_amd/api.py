@@ -79,6 +79,8 @@ SIGNATURES = {
     "td_graph_add_phaser": (_i32, [_vp, _cp, _f32, _f32, _f32, _i32, _f32, _f32, _f32, _f32, _f32, _i32]),
     "td_phaser_params": (_i32, [_sz, _i32, _f32, _f32, _f32, _f32, _f32, _i32, C.POINTER(C.c_double)]),
     "td_graph_add_gate": (_i32, [_vp, _cp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32]),
+    "td_graph_add_vocoder": (_i32, [_vp, _cp, _f32, _f32, _f32, _i32, _f32, _f32, _f32, _f32, _f32]),
+    "td_vocoder_params": (_i32, [_sz, _i32, _f32, _f32, _f32, _f32, _f32, C.POINTER(C.c_double), _sz]),
     "td_gate_params": (_i32, [_sz, _f32, _f32, _f32, _f32, _f32, _f32, C.POINTER(C.c_double)]),
     "td_reverb_params": (_i32, [_sz, _f32, _f32, _f32, _f32, C.POINTER(C.c_double)]),
     "td_graph_connect": (_i32, [_vp, _cp, _cp]),
@@ -351,6 +353,16 @@ def phaser_params(sr, stages, lo_hz, hi_hz, rate_hz, feedback, stereo, shape):
     return (int(out[0]),) + tuple(out[1:7])
 
 
+def vocoder_params(sr, bands, lo_hz, hi_hz, q, response_ms, out_db):
+    """(rows, a, g): the vocoder vertex' constants at rate sr, exactly the doubles the engine uses (host only) -- rows[b] = (f_b, b0,
+    b1, b2, a1, a2) per band, a the follower's coefficient, g the output gain."""
+    n = 6 * 16 + 2
+    out = (C.c_double * n)()
+    _check(lib().td_vocoder_params(int(sr), int(bands), lo_hz, hi_hz, q, response_ms, out_db, out, n))
+    B = int(bands)
+    return [tuple(out[6 * b:6 * b + 6]) for b in range(B)], out[6 * B], out[6 * B + 1]
+
+
 def gate_params(sr, threshold_db, hysteresis_db, hold_ms, attack_ms, release_ms, range_db):
     """(To, Tc, H, aA, aR, F): the gate vertex' constants at rate sr, exactly the doubles the engine uses (host only; H an int)."""
     out = (C.c_double * 6)()
@@ -601,12 +613,17 @@ class Graph:
         _check(lib().td_graph_add_phaser(self.h, name.encode(), gain, angle, wet, int(stages), lo_hz, hi_hz, rate_hz, feedback, stereo,
                                          chorus_shape(shape)))
 
+    def add_vocoder(self, name, gain, angle, wet, bands, lo_hz, hi_hz, q, response_ms, out_db):
+        """A vocoder vertex: a keyed band-pass bank (this engine's own; the definition is in include/termdaw_amd.h).  bands 4 | 8 |
+        16; its inputs are the carrier, its key edges (connect_key) the modulator."""
+        _check(lib().td_graph_add_vocoder(self.h, name.encode(), gain, angle, wet, int(bands), lo_hz, hi_hz, q, response_ms, out_db))
+
     def connect(self, a, b):
         return bool(lib().td_graph_connect(self.h, a.encode(), b.encode()))
 
     def connect_key(self, a, b):
-        """A key edge (sidechain) from any vertex a to a compressor or gate vertex b: b takes its level from the sum of its key
-        sources and goes on processing the sum of its inputs (include/termdaw_amd.h td_graph_connect_key).  False: last_error()."""
+        """A key edge (sidechain) from any vertex a to a compressor, gate or vocoder vertex b: b takes its level (a vocoder: its
+        modulator) from the sum of its key sources and goes on processing the sum of its inputs (include/termdaw_amd.h td_graph_connect_key).  False: last_error()."""
         return bool(lib().td_graph_connect_key(self.h, a.encode(), b.encode()))
 
     def set_output(self, name):

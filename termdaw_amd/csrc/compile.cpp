@@ -3,7 +3,7 @@
 // this file calls the HIP runtime: device memory reaches it as addresses handed out by three functions of engine.cpp
 // (compile.h: take_buffer / ensure_buffers for edge buffers, upload_tables for a vertex' event tables), everything it
 // writes goes into the plain-memory staging arena of the ChunkBuild (offsets + fix-up lists that submit_chunk patches once
-// the device addresses are known).  The effect kinds (compressor .. phaser) are lowered by compile_fx.cpp, through the table there;
+// the device addresses are known).  The effect kinds (compressor .. vocoder) are lowered by compile_fx.cpp, through the table there;
 // that file is included at the end of this one (see there).  tests/test_compile_asan.py builds it with g++
 // -fsanitize=address,undefined.
 #include "compile.h"
@@ -31,7 +31,8 @@ const char* const kFamilyName[F_COUNT] = {"k_sample_loop", "k_sample_multi", "k_
                                            "k_chorus_sum", "k_chorus",
                                            "k_reverb_sum", "k_reverb",
                                            "k_gate_detect", "k_gate_carry_hc", "k_gate_env", "k_gate_carry_env", "k_gate_apply",
-                                           "k_phaser_local", "k_phaser_carry", "k_phaser_apply"};
+                                           "k_phaser_local", "k_phaser_carry", "k_phaser_apply",
+                                           "k_voc_local", "k_voc_carry_z", "k_voc_env", "k_voc_carry_env", "k_voc_apply"};
 
 
 // ------------------------------------------------------------------------------------------------
@@ -1461,7 +1462,7 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
         // input term tables: an edge buffer, or an inlined sample_loop source gathered by the consumer
         std::map<size_t, size_t> ins_off;
         std::map<size_t, uint32_t> term_mode;
-        std::map<size_t, size_t> key_off;        // a keyed compressor / gate vertex that is not dry -> staging offset of its key terms
+        std::map<size_t, size_t> key_off;        // a keyed compressor / gate / vocoder vertex that is not dry -> staging offset of its key terms
         std::map<size_t, uint32_t> key_mode;     // ... and TERMS_* of those
         for (size_t vl : by_level[lv]) {
             if (!g->vertices[vl].has_input() || inlined[vl] || fused_norm.count(vl)) continue;   // (an inlined vertex' terms belong to its consumers)

@@ -22,6 +22,7 @@ enum Family { F_LOOP, F_MULTI, F_LERP, F_SINE, F_SYNTH, F_SAMPSYN, F_ENV, F_PROB
               F_REVERB_SUM, F_REVERB /* a level's reverb vertices: k_reverb_sum, k_reverb -- in this order */,
               F_GATE_DETECT, F_GATE_CARRY_H, F_GATE_ENV, F_GATE_CARRY_ENV, F_GATE_APPLY /* a level's gate vertices: k_gate_detect, k_gate_carry (the (h, c) entering each tile), k_gate_env, k_gate_carry (the env entering each tile), k_gate_apply -- in this order */,
               F_PHASER_LOCAL, F_PHASER_CARRY, F_PHASER_APPLY /* a level's phaser vertices, per stage count: k_phaser_local, k_phaser_carry (both over multi-tile chunks only), k_phaser_apply -- in this order */,
+              F_VOC_LOCAL, F_VOC_CARRY, F_VOC_ENV, F_VOC_CARRY_ENV, F_VOC_APPLY /* a level's vocoder vertices, per band count and keyed or not: k_voc_local, k_voc_carry (the biquads' states entering each tile), k_voc_env, k_voc_carry (the followers'), all four over multi-tile chunks only, k_voc_apply -- in this order */,
               F_COUNT };
 extern const char* const kFamilyName[F_COUNT];
 
@@ -38,7 +39,7 @@ bool is_delay_family(int fam);
 double ms_between(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b);
 tdk::PanGain make_pg(float gain, float angle);           // a vertex' pan / gain as its kernel's epilogue applies it (sample.rs:98-109)
 
-// ---- compile_fx.cpp: the effect kinds (compressor, EQ, delay, saturator, chorus, reverb, gate, phaser) ----
+// ---- compile_fx.cpp: the effect kinds (compressor, EQ, delay, saturator, chorus, reverb, gate, phaser, vocoder) ----
 // What lowering the vertices of one effect kind at one level needs of compile_chunk, and the steps every kind's lowering
 // shares.  The kinds' own functions (lower_comp ..) keep what is theirs: coefficients, tiling, scratch, launches.
 struct FxLevel {
@@ -51,7 +52,7 @@ struct FxLevel {
     int fam;              // the family the level's loop has reached (FxKind::family of the vertices handed over)
     std::map<size_t, size_t>& ins_off;        // vertex -> staging offset of its input terms
     std::map<size_t, uint32_t>& term_mode;    // vertex -> TERMS_* of those
-    std::map<size_t, size_t>& key_off;        // keyed compressor / gate vertex (not dry) -> staging offset of its key terms
+    std::map<size_t, size_t>& key_off;        // keyed compressor / gate / vocoder vertex (not dry) -> staging offset of its key terms
     std::map<size_t, uint32_t>& key_mode;     // ... -> TERMS_* of those
     std::vector<float2*>& level_tmp;          // scratch edge buffers, given back behind the level
 
@@ -84,7 +85,7 @@ struct FxLevel {
         vs.insert(vs.end(), b.begin(), b.end());
         return a.size();
     }
-    // a keyed descriptor's key fields (CompDesc / GateDesc; key_ins is pointed at key_off[vi] once the descriptors are staged)
+    // a keyed descriptor's key fields (CompDesc / GateDesc / VocDesc; key_ins is pointed at key_off[vi] once the descriptors are staged)
     template <class D>
     void key_fields(D& x, size_t vi) {
         x.key_k = (uint32_t)g->key_edges[vi].size();
@@ -117,7 +118,7 @@ const FxKind* fx_of_family(int fam);    // nullptr: not an effect kind's family
 // ---- engine.cpp: the device memory the compiler hands out addresses of ----
 int upload_tables(td_graph* g, TableCache& tc, const Staging& tmp);   // a vertex' event tables -> its device buffer (queued on the graph's stream)
 int ensure_buffers(td_graph* g, size_t frames);                      // the edge-buffer pool holds buffers of >= frames frames; all of them free
-void* take_line(td_graph* g, tde::Vertex& v, size_t bytes);   // the block a delay, saturator, chorus or reverb vertex carries (Vertex::line), allocated on first use (nullptr: out of device memory)
+void* take_line(td_graph* g, tde::Vertex& v, size_t bytes);   // the block a delay, saturator, chorus, reverb or vocoder vertex carries (Vertex::line), allocated on first use (nullptr: out of device memory)
 float2* take_buffer(td_graph* g);                                    // one edge buffer (nullptr: out of device memory)
 
 }  // namespace tde

@@ -1,5 +1,5 @@
 // compile_fx.cpp -- the effect kinds of the host compiler (compile.h FxKind / FxLevel): compressor, EQ, delay, saturator,
-// chorus, reverb, gate, phaser.  One table row per kind -- its chunk limit, the family its launches start at, the factor the guard
+// chorus, reverb, gate, phaser, vocoder.  One table row per kind -- its chunk limit, the family its launches start at, the factor the guard
 // carries an estimate through it at -- and one function per kind that lowers a level's vertices of that kind to descriptors
 // and launches.  compile_chunk enumerates the kinds through the table only.  Like compile.cpp: no HIP call.  Not an object of its
 // own: compile.cpp includes this file at its end, so no build list changes with it.
@@ -11,6 +11,7 @@
 #include "phaser_math.h"
 #include "reverb_math.h"
 #include "sat_math.h"
+#include "vocoder_math.h"
 
 #include <math.h>
 
@@ -29,7 +30,7 @@ float2* FxLevel::tmp_buffer() {
 
 namespace fxk {   // (compile.cpp includes this file: what is only used here keeps a scope of its own)
 
-// A delay, saturator, chorus or reverb vertex enters a chunk of M frames: a set_time since the vertex last ran is consumed here
+// A delay, saturator, chorus, reverb or vocoder vertex enters a chunk of M frames: a set_time since the vertex last ran is consumed here
 // (the block restarts from zero, like an EQ's state), the books move on behind the chunk -- `alternates`: the launch writes the other
 // half of the line, which the next one reads.  Returns the frames run up to the chunk (Vertex::Line::total as the chunk finds it).
 static uint64_t enter_chunk(Vertex& v, size_t M, bool alternates) {
@@ -464,6 +465,94 @@ static int lower_phaser(FxLevel& L, std::vector<size_t>& vs) {
     return 1;
 }
 
+// ---- vocoder: five launches per band count and key form, or one (kernels.h VocDesc) ----
+static int lower_vocoder(FxLevel& L, std::vector<size_t>& vs) {
+    td_graph* g = L.g;
+    const uint32_t n_tiles = (uint32_t)((L.M + kVocTile - 1) / kVocTile), chunk = (n_tiles + kThreads - 1) / kThreads;
+    const bool multi = n_tiles > 1u;   // (multi: the four launches in front of k_voc_apply)
+    // the keyed vertices behind the others (FxLevel::keyed_last), each group by band count: the kernels are templates on it
+    std::vector<size_t> ord(vs.begin(), vs.end());
+    const size_t n_plain = L.keyed_last(ord);
+    auto by_bands = [&](size_t a, size_t b) { return g->vertices[a].voc_bands < g->vertices[b].voc_bands; };
+    std::stable_sort(ord.begin(), ord.begin() + (long)n_plain, by_bands);
+    std::stable_sort(ord.begin() + (long)n_plain, ord.end(), by_bands);
+    std::vector<VocDesc> d;
+    std::vector<size_t> band_off;
+    for (size_t i = 0; i < ord.size(); ++i) {
+        const size_t vi = ord[i];
+        Vertex& v = g->vertices[vi];
+        const bool keyed = i >= n_plain;
+        const int B = v.voc_bands;
+        VocDesc x{};
+        if (multi) {
+            if (!(x.x = L.tmp_buffer())) return 0;
+            x.kx = x.x;   // (an unkeyed vertex listens to itself)
+            if (keyed && !(x.kx = L.tmp_buffer())) return 0;
+        }
+        L.head(x, vi);
+        if (keyed) L.key_fields(x, vi);
+        x.line = (double*)take_line(g, v, (size_t)B * kVocState * sizeof(double));
+        if (!x.line) return fail("termdaw_amd: out of device memory for a vocoder vertex' state");
+        x.init = enter_chunk(v, L.M, false) ? x.line : nullptr;   // (afresh: the state is zero, the line is not read)
+        x.n_tiles = n_tiles;
+        x.chunk = chunk;
+        x.bands = (uint32_t)B;
+        double c[vocoder::kMaxParams];
+        vocoder::params(L.sr, B, v.voc_lo_hz, v.voc_hi_hz, v.voc_q, v.voc_response_ms, v.voc_out_db, c);
+        std::vector<VocBand> bands((size_t)B);
+        for (int b = 0; b < B; ++b) {
+            VocBand& y = bands[(size_t)b];
+            const double* cb = c + vocoder::kBandParams * b + 1;
+            y.b0 = cb[0]; y.b1 = cb[1]; y.b2 = cb[2]; y.a1 = cb[3]; y.a2 = cb[4];
+            y.c0 = y.b1 - y.a1 * y.b0;
+            y.c1 = y.b2 - y.a2 * y.b0;
+            y.pad = 0.0;
+            eq::powers(y.a1, y.a2, kVocRun, chunk, y.pw, y.a_tile, y.pwc);
+        }
+        band_off.push_back(L.cb.st->put(bands));
+        x.a = c[vocoder::kBandParams * B];
+        x.oa = 1.0 - x.a;
+        x.g = c[vocoder::kBandParams * B + 1];
+        // the follower's powers, in long double like the matrices', each rounded once
+        long double p = powl((long double)x.a, (long double)kVocRun);
+        for (int k = 0; k < 8; ++k) { x.pwa[k] = (double)p; p *= p; }
+        x.a_tile = (double)p;
+        p = powl(p, (long double)chunk);
+        for (int k = 0; k < 8; ++k) { x.pwac[k] = (double)p; p *= p; }
+        d.push_back(x);
+    }
+    const size_t off = L.put(d, ord);
+    for (size_t i = 0; i < ord.size(); ++i) {
+        const size_t o = off + i * sizeof(VocDesc), B = d[i].bands;
+        L.cb.ptr_field(o, offsetof(VocDesc, band), band_off[i]);
+        if (i >= n_plain) L.cb.ptr_field(o, offsetof(VocDesc, key_ins), L.key_off[ord[i]]);
+        if (!multi) continue;
+        L.cb.scratch_field(o, offsetof(VocDesc, agg), L.cb.scratch((size_t)n_tiles * B * 6 * sizeof(double)));
+        L.cb.scratch_field(o, offsetof(VocDesc, carry), L.cb.scratch((size_t)n_tiles * B * 6 * sizeof(double)));
+        L.cb.scratch_field(o, offsetof(VocDesc, agge), L.cb.scratch((size_t)n_tiles * B * sizeof(double)));
+        L.cb.scratch_field(o, offsetof(VocDesc, carrye), L.cb.scratch((size_t)n_tiles * B * sizeof(double)));
+    }
+    for (size_t i = 0; i < ord.size();) {
+        const uint32_t B = d[i].bands;
+        const bool keyed = i >= n_plain;
+        size_t j = i;
+        while (j < ord.size() && d[j].bands == B && (j >= n_plain) == keyed) ++j;
+        const size_t o = off + i * sizeof(VocDesc);
+        const int n = (int)(j - i);
+        if (multi) {   // (only k_voc_local has a keyed form here: the later launches read x and kx)
+            L.add_launch(F_VOC_LOCAL, o, n, voc_aux(n_tiles, B, false, keyed));
+            L.add_launch(F_VOC_CARRY, o, n, voc_aux(0u, B, false, false));
+            L.add_launch(F_VOC_ENV, o, n, voc_aux(n_tiles, B, false, false));
+            L.add_launch(F_VOC_CARRY_ENV, o, n, voc_aux(0u, B, false, false));
+            L.add_launch(F_VOC_APPLY, o, n, voc_aux(n_tiles, B, false, false));
+        } else {
+            L.add_launch(F_VOC_APPLY, o, n, voc_aux(n_tiles, B, true, keyed));
+        }
+        i = j;
+    }
+    return 1;
+}
+
 // ---- the table ----
 // fits: the largest chunk the kind's kernels index (32-bit frames; the line kinds keep room for their look-back, the tiled
 // ones for the tile count packed into a launch's aux)
@@ -471,6 +560,8 @@ static bool fits_scan(const td_graph*, const Vertex&, size_t M) { return M <= 0x
 static bool fits_line(const td_graph*, const Vertex&, size_t M) { return M <= 0xF0000000ull; }
 static bool fits_sat(const td_graph* g, const Vertex&, size_t M) { return M <= 0xF0000000ull && (M + g->sat_tile - 1) / g->sat_tile < 0x100000ull; }
 static bool fits_chorus(const td_graph* g, const Vertex&, size_t M) { return M <= 0xF0000000ull && (M + g->chorus_tile - 1) / g->chorus_tile < 0x100000ull; }
+
+static bool fits_voc(const td_graph*, const Vertex&, size_t M) { return M <= 0xFFFF0000ull && (M + kVocTile - 1) / kVocTile < 0x1000000ull; }
 
 static int family_sat(const Vertex& v) { return v.sat_oversample == 1 ? F_SAT1 : F_SAT_SUM; }
 
@@ -485,6 +576,8 @@ static double through_comp(const Vertex&, size_t) { return kNoStaticGain; }
 static double through_gate(const Vertex& v, size_t) { return dry(v) ? 1.0 : kNoStaticGain; }
 // a phaser is linear, but time-varying with feedback, and no L2 bound of it is proven: none is guessed
 static double through_phaser(const Vertex& v, size_t) { return dry(v) ? 1.0 : kNoStaticGain; }
+// a vocoder's gain on its carrier is the modulator's envelope: no static gain -- like a compressor's, unless it is dry
+static double through_vocoder(const Vertex& v, size_t) { return dry(v) ? 1.0 : kNoStaticGain; }
 // an EQ is linear and time-invariant: Hmax of its biquad
 static double through_eq(const Vertex& v, size_t sr) {
     if (dry(v)) return 1.0;
@@ -519,9 +612,10 @@ static double through_reverb(const Vertex& v, size_t sr) {
 // (a function's static: these sources also go through the HIP compiler, whose device pass would want a copy of a namespace-scope
 // constant -- and of the host functions it points to.)  A row's family count is the distance to the next row's first family, so
 // the rows cover the effect families of `Family` without gap or overlap as long as they stand in its order:
-constexpr int kFxKinds = 8;
+constexpr int kFxKinds = 9;
 static_assert(F_COMP_DETECT < F_EQ_LOCAL && F_EQ_LOCAL < F_DELAY_LOCAL && F_DELAY_LOCAL < F_SAT_SUM && F_SAT_SUM < F_CHORUS_SUM &&
-              F_CHORUS_SUM < F_REVERB_SUM && F_REVERB_SUM < F_GATE_DETECT && F_GATE_DETECT < F_PHASER_LOCAL && F_PHASER_LOCAL < F_COUNT,
+              F_CHORUS_SUM < F_REVERB_SUM && F_REVERB_SUM < F_GATE_DETECT && F_GATE_DETECT < F_PHASER_LOCAL && F_PHASER_LOCAL < F_VOC_LOCAL &&
+              F_VOC_LOCAL < F_COUNT,
               "the rows of the effect kinds' table stand in the order of their families");
 static const FxKind* table() {
     static const FxKind rows[kFxKinds] = {
@@ -532,7 +626,8 @@ static const FxKind* table() {
         {K_CHORUS, "chorus", F_CHORUS_SUM, F_REVERB_SUM - F_CHORUS_SUM, sizeof(ChorusDesc), fits_chorus, nullptr, through_chorus, lower_chorus},
         {K_REVERB, "reverb", F_REVERB_SUM, F_GATE_DETECT - F_REVERB_SUM, sizeof(ReverbDesc), fits_line, nullptr, through_reverb, lower_reverb},
         {K_GATE, "gate", F_GATE_DETECT, F_PHASER_LOCAL - F_GATE_DETECT, sizeof(GateDesc), fits_scan, nullptr, through_gate, lower_gate},
-        {K_PHASER, "phaser", F_PHASER_LOCAL, F_COUNT - F_PHASER_LOCAL, sizeof(PhaserDesc), fits_scan, nullptr, through_phaser, lower_phaser},
+        {K_PHASER, "phaser", F_PHASER_LOCAL, F_VOC_LOCAL - F_PHASER_LOCAL, sizeof(PhaserDesc), fits_scan, nullptr, through_phaser, lower_phaser},
+        {K_VOCODER, "vocoder", F_VOC_LOCAL, F_COUNT - F_VOC_LOCAL, sizeof(VocDesc), fits_voc, nullptr, through_vocoder, lower_vocoder},
     };
     return rows;
 }

@@ -12,6 +12,7 @@
 #include "chorus_math.h"
 #include "gate_math.h"
 #include "phaser_math.h"
+#include "vocoder_math.h"
 #include "comm.h"
 #include "compile.h"
 #include "delay_math.h"
@@ -579,7 +580,7 @@ int ensure_buffers(td_graph* g, size_t frames) {
     g->free_bufs = g->pool;
     return 1;
 }
-// The block a delay, saturator, chorus or reverb vertex carries (Vertex::line): allocated when the vertex is first compiled into a
+// The block a delay, saturator, chorus, reverb or vocoder vertex carries (Vertex::line): allocated when the vertex is first compiled into a
 // submission (never cleared: a word is read only once the vertex has written it, Line::total), freed with the graph's vertices.
 void* take_line(td_graph* g, Vertex& v, size_t bytes) {
     if (v.line.d) return v.line.d;
@@ -973,6 +974,17 @@ static int submit_chunk(Arena& ar, ChunkBuild& cb, hipStream_t stream, ProfCtx& 
                 case F_PHASER_LOCAL: launch_phaser_local((const PhaserDesc*)d, L.n, (L.aux >> 24) & 15u, L.aux & 0xFFFFFFu, s); break;
                 case F_PHASER_CARRY: launch_phaser_carry((const PhaserDesc*)d, L.n, (L.aux >> 24) & 15u, s); break;
                 case F_PHASER_APPLY: launch_phaser_apply((const PhaserDesc*)d, L.n, (L.aux >> 24) & 15u, L.aux & 0xFFFFFFu, (L.aux & kPhaserSingleBit) != 0u, s); break;
+                case F_VOC_LOCAL:   // (the keyed forms: prepare_render has checked they exist where a key edge asks for them)
+                    if (L.aux & kKeyedBit) launch_voc_local_keyed((const VocDesc*)d, L.n, voc_aux_bands(L.aux), voc_aux_tiles(L.aux), s);
+                    else launch_voc_local((const VocDesc*)d, L.n, voc_aux_bands(L.aux), voc_aux_tiles(L.aux), s);
+                    break;
+                case F_VOC_CARRY: launch_voc_carry((const VocDesc*)d, L.n, voc_aux_bands(L.aux), false, s); break;
+                case F_VOC_ENV: launch_voc_env((const VocDesc*)d, L.n, voc_aux_bands(L.aux), voc_aux_tiles(L.aux), s); break;
+                case F_VOC_CARRY_ENV: launch_voc_carry((const VocDesc*)d, L.n, voc_aux_bands(L.aux), true, s); break;
+                case F_VOC_APPLY:
+                    if (L.aux & kKeyedBit) launch_voc_apply_keyed((const VocDesc*)d, L.n, voc_aux_bands(L.aux), voc_aux_tiles(L.aux), s);
+                    else launch_voc_apply((const VocDesc*)d, L.n, voc_aux_bands(L.aux), voc_aux_tiles(L.aux), (L.aux & kVocSingleBit) != 0u, s);
+                    break;
                 case F_CHORUS: launch_chorus((const ChorusDesc*)d, L.n, L.aux & 0xFFFFFu, L.M, (L.aux & kChorusTermsBit) != 0u, s); break;
             }
         }
@@ -1065,6 +1077,7 @@ static int prepare_render(td_graph* g, size_t n_blocks, int bits, bool want_pcm,
         {K_REVERB, launch_reverb_sum && launch_reverb, "reverb", "reverb"},
         {K_GATE, launch_gate_detect && launch_gate_carry && launch_gate_env && launch_gate_apply, "gate", "gate"},
         {K_PHASER, launch_phaser_local && launch_phaser_carry && launch_phaser_apply, "phaser", "phaser"},
+        {K_VOCODER, launch_voc_local && launch_voc_carry && launch_voc_env && launch_voc_apply, "voc", "vocoder"},
     };
     for (const auto& f : fx)
         if (!f.built)
@@ -1074,6 +1087,11 @@ static int prepare_render(td_graph* g, size_t n_blocks, int bits, bool want_pcm,
     for (size_t vi : g->order) {   // ... and the keyed forms, where a key edge asks for them (td_graph_connect_key)
         const Vertex& v = g->vertices[vi];
         if (g->key_edges[vi].empty() || v.wet < 0.0001f) continue;
+        if (v.kind == K_VOCODER) {
+            if (!(launch_voc_local_keyed && launch_voc_apply_keyed))
+                return fail("termdaw_amd: this build has no keyed vocoder kernels: a vertex with a key edge cannot be rendered");
+            continue;
+        }
         if (v.kind == K_COMPRESSOR ? !launch_comp_detect_keyed : !(launch_gate_detect_keyed && launch_gate_env_keyed))
             return fail("termdaw_amd: this build has no keyed compressor / gate kernels: a vertex with a key edge cannot be rendered");
     }
@@ -1417,6 +1435,7 @@ static int graph_set_time_impl(td_graph* g, size_t time) {   // graph.rs:123-128
             case K_SATURATOR:
             case K_CHORUS:
             case K_REVERB:
+            case K_VOCODER:   // (the filters and followers restart from zero: the line is not read)
                 v.first_pending = true;
                 break;
             default: break;
@@ -2104,6 +2123,28 @@ int td_phaser_params(size_t sr, int stages, float lo_hz, float hi_hz, float rate
     return 1;
 }
 
+// This engine's own vocoder vertex (no reference counterpart; the definition is in include/termdaw_amd.h).  Its state is a
+// carried line (7 doubles per band), allocated when the vertex is first compiled into a submission.
+int td_graph_add_vocoder(td_graph* g, const char* name, float gain, float angle, float wet, int bands, float lo_hz, float hi_hz, float q,
+                         float response_ms, float out_db) {
+    if (const char* why = vocoder::check(g->sr, bands, lo_hz, hi_hz, q, response_ms, out_db)) return fail(std::string("vocoder: ") + why);
+    Vertex& v = add_vertex(g, name, gain, angle, wet, K_VOCODER);
+    v.voc_bands = bands;
+    v.voc_lo_hz = lo_hz;
+    v.voc_hi_hz = hi_hz;
+    v.voc_q = q;
+    v.voc_response_ms = response_ms;
+    v.voc_out_db = out_db;
+    return 1;
+}
+int td_vocoder_params(size_t sr, int bands, float lo_hz, float hi_hz, float q, float response_ms, float out_db, double* out, size_t cap) {
+    if (!out) return fail("vocoder_params: out is null");
+    if (const char* why = vocoder::check(sr, bands, lo_hz, hi_hz, q, response_ms, out_db)) return fail(std::string("vocoder: ") + why);
+    if (cap < vocoder::n_params(bands)) return fail("vocoder_params: out holds fewer than 6 bands + 2 doubles");
+    vocoder::params(sr, bands, lo_hz, hi_hz, q, response_ms, out_db, out);
+    return 1;
+}
+
 static bool has_loop(size_t x, size_t b, const td_graph* g) {   // graph.rs:66-72
     if (x == b) return true;
     for (size_t y : g->edges[x])
@@ -2131,7 +2172,7 @@ int td_graph_connect_key(td_graph* g, const char* a, const char* b) {
     if (ia == g->name_map.end()) return fail(std::string("TermDaw: warning: vertex \"") + a + "\" cannot be found and thus can't be connected.");
     if (ib == g->name_map.end()) return fail(std::string("TermDaw: warning: vertex \"") + b + "\" cannot be found and thus can't be connected to.");
     const size_t ai = ia->second, bi = ib->second;
-    if (g->vertices[bi].kind != K_COMPRESSOR && g->vertices[bi].kind != K_GATE) return fail(std::string("connect_key: ") + b + " takes no key input");
+    if (g->vertices[bi].kind != K_COMPRESSOR && g->vertices[bi].kind != K_GATE && g->vertices[bi].kind != K_VOCODER) return fail(std::string("connect_key: ") + b + " takes no key input");
     if (ai == bi) return fail("connect_key: self edge");
     if (has_loop(ai, bi, g)) return fail("connect_key: edge would close a loop");
     g->key_edges[bi].push_back(ai);

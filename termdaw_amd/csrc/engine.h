@@ -76,7 +76,7 @@ struct td_flowwbank {
 namespace tde {
 
 enum Kind { K_SUM, K_NORMALIZE, K_SAMPLE_LOOP, K_SAMPLE_MULTI, K_SAMPLE_LERP, K_DEBUG_SINE, K_SYNTH,
-            K_SAMPSYN, K_ADSR, K_BAND_PASS, K_COMPRESSOR, K_EQ, K_DELAY, K_SATURATOR, K_CHORUS, K_REVERB, K_GATE, K_PHASER, K_COUNT };
+            K_SAMPSYN, K_ADSR, K_BAND_PASS, K_COMPRESSOR, K_EQ, K_DELAY, K_SATURATOR, K_CHORUS, K_REVERB, K_GATE, K_PHASER, K_VOCODER, K_COUNT };
 
 struct SineNote { float note, vel; };
 struct SynthNote { float note, vel, env_t, rel_t, hz; };   // hz = 440 * 2^((note - 69) / 12), extensions.rs:503
@@ -139,12 +139,15 @@ struct Vertex {
     float gate_threshold_db = 0, gate_hysteresis_db = 0, gate_hold_ms = 0, gate_attack_ms = 0, gate_release_ms = 1, gate_range_db = 0;   // K_GATE
     int phaser_stages = 2, phaser_shape = 0;   // K_PHASER: N, TD_CHORUS_*
     float phaser_lo_hz = 20, phaser_hi_hz = 20, phaser_rate_hz = 1, phaser_feedback = 0, phaser_stereo = 0;
-    // The block of device memory a delay, saturator, chorus or reverb vertex carries from chunk to chunk: allocated when the vertex
+    int voc_bands = 4;   // K_VOCODER: B
+    float voc_lo_hz = 40, voc_hi_hz = 80, voc_q = 1, voc_response_ms = 10, voc_out_db = 0;
+    // The block of device memory a delay, saturator, chorus, reverb or vocoder vertex carries from chunk to chunk: allocated when the vertex
     // is first compiled into a submission (take_line), never cleared, freed with the graph's vertices.
     //   K_DELAY             the last D values of (ul, ur), 16 D bytes: the rotation is total mod D, the words below min(total, D) hold values
     //   K_SATURATOR (R > 1) the last 128 raw input frames, two halves of 128 float2: a frame at or beyond min(total, 128) back reads as 0
     //   K_CHORUS            the last H raw input frames, two halves of H float2: a frame beyond min(total, H) back reads as 0
     //   K_REVERB            f[16] and the 24 lines, doubles: frame m of a line lives in slot m mod D, a read of m - D < 0 is 0
+    //   K_VOCODER           7 doubles per band, (s1l, s2l, s1r, s2r, s1m, s2m, e): read only once total > 0
     struct Line {
         void* d = nullptr;
         size_t bytes = 0;
@@ -165,7 +168,7 @@ struct Vertex {
     // ones, a tdk::PhaserState), index into Graph::dstate
     int state_slot = -1;
     // reset_normalization (extensions.rs:295-299) is kept on the host until the next render consumes it
-    bool first_pending = false;         // band-pass, compressor, eq, gate, phaser, delay, saturator, chorus, reverb (their state then restarts from zero): set_time since the vertex was last compiled into a submission (its descriptor's first_override)
+    bool first_pending = false;         // band-pass, compressor, eq, gate, phaser, delay, saturator, chorus, reverb, vocoder (their state then restarts from zero): set_time since the vertex was last compiled into a submission (its descriptor's first_override)
     bool has_init_override = false;
     float init_override = 0.0f;
     // Normalize: the carried max is the result of a normalize scan (graph.rs:222-237), so a render is expected to
@@ -387,8 +390,8 @@ struct td_graph {
     // graph.rs:12-22
     std::vector<tde::Vertex> vertices;
     std::vector<std::vector<size_t>> edges;   // reverse edges: edges[b] = [a...] in connect() order
-    // key edges (td_graph_connect_key), reverse like `edges`: key_edges[b] = [a...] in connect_key() order; only a compressor or
-    // gate vertex has any.  The plan and every liveness rule of compile_chunk count them as consumers of a; the level of b's
+    // key edges (td_graph_connect_key), reverse like `edges`: key_edges[b] = [a...] in connect_key() order; only a compressor,
+    // gate or vocoder vertex has any.  The plan and every liveness rule of compile_chunk count them as consumers of a; the level of b's
     // dynamics is taken from their sum
     std::vector<std::vector<size_t>> key_edges;
     std::map<std::string, size_t> name_map;

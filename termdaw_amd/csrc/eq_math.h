@@ -18,13 +18,14 @@ inline bool kind_has_gain(int kind) { return kind >= 4; }
 
 // (b0, b1, b2, a1, a2), normalised by a0.  f64 from the f32 parameters, widened; 1 - cos w0 as 2 sin^2(w0 / 2), which has no
 // cancellation at low frequencies.
-inline void coefficients(int kind, size_t sr, float freq_hz, float q, float gain_db, double out[5]) {
-    const double w0 = 2.0 * M_PI * (double)freq_hz / (double)sr;
+// (the f64 form: the vocoder vertex' band centres are f64, vocoder_math.h; the f32 form below widens and calls it)
+inline void coefficients_f64(int kind, size_t sr, double freq_hz, double q, double gain_db, double out[5]) {
+    const double w0 = 2.0 * M_PI * freq_hz / (double)sr;
     const double cw = cos(w0), sw = sin(w0), sh = sin(0.5 * w0);
     const double omc = 2.0 * sh * sh;   // 1 - cos w0
     const double opc = 1.0 + cw;
-    const double alpha = sw / (2.0 * (double)q);
-    const double A = kind_has_gain(kind) ? pow(10.0, (double)gain_db / 40.0) : 1.0;
+    const double alpha = sw / (2.0 * q);
+    const double A = kind_has_gain(kind) ? pow(10.0, gain_db / 40.0) : 1.0;
     double b0 = 1.0, b1 = 0.0, b2 = 0.0, a0 = 1.0, a1 = 0.0, a2 = 0.0;
     switch (kind) {
         case 0: b0 = omc / 2.0; b1 = omc; b2 = omc / 2.0; a0 = 1.0 + alpha; a1 = -2.0 * cw; a2 = 1.0 - alpha; break;
@@ -49,6 +50,9 @@ inline void coefficients(int kind, size_t sr, float freq_hz, float q, float gain
         }
     }
     out[0] = b0 / a0; out[1] = b1 / a0; out[2] = b2 / a0; out[3] = a1 / a0; out[4] = a2 / a0;
+}
+inline void coefficients(int kind, size_t sr, float freq_hz, float q, float gain_db, double out[5]) {
+    coefficients_f64(kind, sr, (double)freq_hz, (double)q, (double)gain_db, out);
 }
 
 // |H(e^jw)| of the normalised coefficients at s = sin^2(w / 2), in long double, from the complex form (the squared-magnitude

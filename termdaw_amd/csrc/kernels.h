@@ -357,6 +357,62 @@ struct PhaserDesc {
     PanGain pg;
 };
 
+// A vocoder vertex (k_voc_local<B, KEYED> / k_voc_carry / k_voc_env<B> / k_voc_carry / k_voc_apply<B>; the
+// definition is in include/termdaw_amd.h at td_graph_add_vocoder): B RBJ band-pass biquads (the EQ's transposed direct form II,
+// f64) over the carrier's two channels and the mono modulator m = 0.5 (kl + kr), a one-pole follower e_b of |BP_b(m)| per band,
+// p = g sum_b e_b BP_b(x).  The compressor's five steps with the EQ's operator inside: per band three 2x2 affine scans that share
+// A_b = [[-a1, 1], [-a2, 0]], then one scalar affine scan.  The compressor's tiling: tiles of kVocTile frames, a lane owns kVocRun
+// consecutive frames; kVocJoin bands are joined per barrier round.
+// k_voc_local evaluates the input terms into `x` (KEYED: and the key terms into `kx`; an unkeyed vertex has kx == x) and leaves
+// each tile's zero-start end states (s1l, s2l, s1r, s2r, s1m, s2m) per band in agg[(t B + b) 6 ..]; k_voc_carry (mode 0) leaves the
+// states entering each tile in carry[(t B + b) 6 ..] (tile 0: the line, or 0 when init is null); k_voc_env rebuilds BP_b(m) from
+// there and leaves each tile's zero-start end value of e_b in agge[t B + b]; k_voc_carry (mode 1) leaves the e_b entering each tile in
+// carrye[t B + b]; k_voc_apply rebuilds everything, writes lerp(x, p, wet), pan, gain to `out`, and the lane that owns the chunk's
+// last frame writes the line back.  When one tile covers the chunk (every block pull) k_voc_apply runs alone (kVocSingleBit): the
+// term loops run inside it and the tile enters with the line (x, kx, agg .. carrye unused).
+// The line: 7 doubles per band, (s1l, s2l, s1r, s2r, s1m, s2m, e) at line[7 b ..].
+constexpr uint32_t kVocRun = 8;                     // frames per lane
+constexpr uint32_t kVocTile = kVocRun * kThreads;   // frames per workgroup
+constexpr uint32_t kVocJoin = 4;                    // bands per barrier round (k_voc_local, k_voc_env)
+constexpr uint32_t kVocApplyJoin = 2;               // ... in k_voc_apply, which holds every band's full state beside its sums
+constexpr uint32_t kVocMaxBands = 16;
+constexpr uint32_t kVocState = 7;                   // doubles of the line per band
+struct VocBand {
+    double b0, b1, b2, a1, a2;   // the normalised band-pass coefficients (td_vocoder_params)
+    double c0, c1;          // b1 - a1 b0, b2 - a2 b0
+    double pad;
+    double pw[8][4];        // A_b^(kVocRun 2^k)
+    double a_tile[4];       // A_b^kVocTile
+    double pwc[8][4];       // A_b^(kVocTile chunk 2^k)
+};
+struct VocDesc {
+    const InTerm* ins;      // k input terms (kinds 0 .. 4), in connect() order: the carrier
+    float2* x;              // [frames] the summed input (five-launch form)
+    const float2* kx;       // [frames] the summed key terms (five-launch form): a buffer of its own when keyed, else x
+    float2* out;
+    double* line;           // carried across chunks / block pulls (k_voc_apply stores it)
+    const double* init;     // the state entering tile 0: `line`, or nullptr when the vertex starts afresh
+    const VocBand* band;    // [bands]
+    double* agg;            // [6 n_tiles bands]
+    double* carry;          // [6 n_tiles bands]
+    double* agge;           // [n_tiles bands]
+    double* carrye;         // [n_tiles bands]
+    uint32_t k, term_mode, frames, n_tiles;
+    uint32_t chunk;         // tiles per lane in k_voc_carry
+    uint32_t bands;         // B: 4 | 8 | 16
+    float wet;
+    uint32_t pad;
+    double a, oa;           // the follower's coefficient, 1 - a
+    double g;               // the output gain
+    double pwa[8];          // a^(kVocRun 2^k)
+    double a_tile;          // a^kVocTile
+    double pwac[8];         // a^(kVocTile chunk 2^k)
+    PanGain pg;
+    // a keyed vertex (td_graph_connect_key; null / 0 without key edges): key_k key terms (kinds 0 .. 4), in connect_key() order
+    const InTerm* key_ins;
+    uint32_t key_k, key_term_mode;
+};
+
 // A parametric EQ vertex (k_eq_local / k_eq_carry / k_eq_apply; the definition is in include/termdaw_amd.h at
 // td_graph_add_eq): one RBJ biquad per channel in transposed direct form II, f64.  With z = (s1, s2) the recurrence is
 // z[n] = A z[n-1] + c x[n],  A = [[-a1, 1], [-a2, 0]],  c = (b1 - a1 b0, b2 - a2 b0),  y[n] = b0 x[n] + s1[n-1]: an affine scan
@@ -1014,6 +1070,23 @@ inline uint32_t phaser_aux(uint32_t n_tiles, uint32_t stages, bool single) { ret
 __attribute__((weak)) void launch_phaser_local(const PhaserDesc* d, int n_desc, uint32_t stages, uint32_t n_tiles, hipStream_t s);
 __attribute__((weak)) void launch_phaser_carry(const PhaserDesc* d, int n_desc, uint32_t stages, hipStream_t s);
 __attribute__((weak)) void launch_phaser_apply(const PhaserDesc* d, int n_desc, uint32_t stages, uint32_t n_tiles, bool single, hipStream_t s);
+// Weak for the same reason: a level's vocoder vertices of ONE band count (the kernels are templates on it), grid.x = n_tiles
+// (every descriptor's; the carries: one workgroup per band and vertex).  A launch's aux packs tile count, band count, for
+// F_VOC_APPLY `single` (the instantiation with the term loops inside, entered with the line), and kKeyedBit where the descriptors
+// are keyed: those go through the *_keyed entry points only.
+constexpr uint32_t kVocSingleBit = 0x40000000u;
+inline uint32_t voc_aux(uint32_t n_tiles, uint32_t bands, bool single, bool keyed) {
+    return n_tiles | (bands << 24) | (single ? kVocSingleBit : 0u) | (keyed ? kKeyedBit : 0u);
+}
+inline uint32_t voc_aux_tiles(uint32_t aux) { return aux & 0xFFFFFFu; }
+inline uint32_t voc_aux_bands(uint32_t aux) { return (aux >> 24) & 31u; }
+__attribute__((weak)) void launch_voc_local(const VocDesc* d, int n_desc, uint32_t bands, uint32_t n_tiles, hipStream_t s);
+__attribute__((weak)) void launch_voc_local_keyed(const VocDesc* d, int n_desc, uint32_t bands, uint32_t n_tiles, hipStream_t s);
+__attribute__((weak)) void launch_voc_carry(const VocDesc* d, int n_desc, uint32_t bands, bool env, hipStream_t s);
+__attribute__((weak)) void launch_voc_env(const VocDesc* d, int n_desc, uint32_t bands, uint32_t n_tiles, hipStream_t s);
+__attribute__((weak)) void launch_voc_apply(const VocDesc* d, int n_desc, uint32_t bands, uint32_t n_tiles, bool single, hipStream_t s);
+// (single and keyed: the one-launch form of a keyed vertex, with both term loops inside)
+__attribute__((weak)) void launch_voc_apply_keyed(const VocDesc* d, int n_desc, uint32_t bands, uint32_t n_tiles, hipStream_t s);
 // Weak for the same reason: a level's reverb vertices.  launch_reverb_sum: grid.x from `frames`; launch_reverb: one workgroup per
 // descriptor, `form` 0 the serial walk of each comb's one-pole, 1 the wave scan.
 __attribute__((weak)) void launch_reverb_sum(const ReverbDesc* d, int n_desc, uint32_t frames, hipStream_t s);

@@ -6574,6 +6574,386 @@ __global__ __launch_bounds__(kPhaserLanes) void k_phaser_apply(const PhaserDesc*
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// k_voc_local / k_voc_carry / k_voc_env / k_voc_apply: the vocoder vertex (kernels.h VocDesc).  No reference
+// counterpart; the definition is the header's (td_graph_add_vocoder): B band-pass biquads over (l, r, m), a one-pole follower of
+// |BP_b(m)| per band, p = g sum_b e_b BP_b(x), f64.  Templates on B: the band loop runs in groups of kVocJoin bands, whose
+// states live in registers under constant indices and are joined in ONE Hillis-Steele pass (sv: one plane of kThreads doubles
+// per joined word).
+// ------------------------------------------------------------------------------------------------
+// the modulator frame: m = 0.5 (kl + kr); a frame with a NaN or infinite sample enters as 0
+TD_DEV double voc_mod(float kl, float kr) {
+    return (fabsf(kl) <= 3.402823466e38f && fabsf(kr) <= 3.402823466e38f) ? 0.5 * ((double)kl + (double)kr) : 0.0;
+}
+// one frame of z <- A z + c x (eq_zstep's order), one signal
+TD_DEV void voc_zstep(double c0, double c1, double a1, double a2, double& s1, double& s2, double x) {
+    const double t0 = (c0 * x - a1 * s1) + s2, t1 = c1 * x - a2 * s1;
+    s1 = t0; s2 = t1;
+}
+// one frame of the definition (eq_frame's order), one signal: y = b0 x + s1;  s1 = (b1 x - a1 y) + s2;  s2 = b2 x - a2 y
+TD_DEV double voc_frame(double b0, double b1, double b2, double a1, double a2, double& s1, double& s2, double x) {
+    const double y = b0 * x + s1;
+    s1 = (b1 * x - a1 * y) + s2;
+    s2 = b2 * x - a2 * y;
+    return y;
+}
+// The lanes' run-end states joined in lane order, NB bands of NV two-vectors each (band j's vectors share its matrices:
+// TILES ? pwc : pw), eq_lane_scan's arithmetic.  u: lane 0's run started from u_in, the others' from 0.  in: the state entering
+// the lane's run; last: the state after the last lane's.  sv: 2 NV NB planes.
+template <int NB, int NV, bool TILES>
+TD_DEV void voc_lane_scan(double (&u)[2 * NV * NB], const VocBand* bd, const double (&u_in)[2 * NV * NB], double* sv, double (&in)[2 * NV * NB],
+                          double (&last)[2 * NV * NB]) {
+    constexpr int W = 2 * NV * NB;
+    const uint32_t tid = threadIdx.x;
+#pragma unroll 1
+    for (uint32_t k = 0; k < 8; ++k) {
+        const uint32_t off = 1u << k;
+#pragma unroll
+        for (int i = 0; i < W; ++i) sv[i * kThreads + tid] = u[i];
+        __syncthreads();
+        if (tid >= off) {
+#pragma unroll
+            for (int j = 0; j < NB; ++j) {
+                const double* P = TILES ? bd[j].pwc[k] : bd[j].pw[k];
+                const double p0 = gloadd(P), p1 = gloadd(P + 1), p2 = gloadd(P + 2), p3 = gloadd(P + 3);
+#pragma unroll
+                for (int v = 0; v < NV; ++v) {
+                    const int i = 2 * (NV * j + v);
+                    const double o0 = sv[i * kThreads + tid - off], o1 = sv[(i + 1) * kThreads + tid - off];
+                    u[i] += p0 * o0 + p1 * o1;
+                    u[i + 1] += p2 * o0 + p3 * o1;
+                }
+            }
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int i = 0; i < W; ++i) sv[i * kThreads + tid] = u[i];
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < W; ++i) {
+        in[i] = tid ? sv[i * kThreads + tid - 1] : u_in[i];
+        last[i] = sv[i * kThreads + kThreads - 1];
+    }
+    __syncthreads();
+}
+// ... and NB scalar chains that share the factors pw[k] (comp_lane_scan<true>'s arithmetic)
+template <int NB>
+TD_DEV void voc_env_scan(double (&e)[NB], const double (&pw)[8], const double (&e_in)[NB], double* sv, double (&in)[NB], double (&last)[NB]) {
+    const uint32_t tid = threadIdx.x;
+#pragma unroll 1
+    for (uint32_t k = 0; k < 8; ++k) {
+        const uint32_t off = 1u << k;
+#pragma unroll
+        for (int i = 0; i < NB; ++i) sv[i * kThreads + tid] = e[i];
+        __syncthreads();
+        if (tid >= off) {
+            const double p = pw[k];
+#pragma unroll
+            for (int i = 0; i < NB; ++i) e[i] = e[i] + p * sv[i * kThreads + tid - off];
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int i = 0; i < NB; ++i) sv[i * kThreads + tid] = e[i];
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < NB; ++i) {
+        in[i] = tid ? sv[i * kThreads + tid - 1] : e_in[i];
+        last[i] = sv[i * kThreads + kThreads - 1];
+    }
+    __syncthreads();
+}
+// The lane's kVocRun frames of the carrier and the modulator through the term loops (KEYED: the key terms too; else m is taken
+// from the carrier's frames).  STORE: the sums go to d.x (and d.kx).  The term loop stays rolled: its frames pass through the
+// lane's own words of sv (a float2 plane pair), so the registers are filled under constant indices.  Ends behind a barrier.
+template <bool KEYED, bool STORE>
+TD_DEV void voc_sum_run(const VocDesc& d, uint32_t f0, double* sv, float (&xl)[kVocRun], float (&xr)[kVocRun], double (&xm)[kVocRun]) {
+    float2* xs = reinterpret_cast<float2*>(sv);        // [kVocRun][kThreads]
+    float2* ks = xs + kVocRun * kThreads;
+    const uint32_t tid = threadIdx.x, M = d.frames;
+#pragma unroll 1
+    for (uint32_t h = 0; h < kVocRun / 4; ++h) {   // (frames beyond M sum to 0)
+        const uint32_t m = f0 + 4u * h;
+        float4 a0, a1;
+        sum_inputs_pairs(d.ins, d.k, d.term_mode, m, m + 2u, M, a0, a1);
+        if (STORE) { store_pair(d.x, m, M, a0); store_pair(d.x, m + 2u, M, a1); }
+        xs[(4u * h) * kThreads + tid] = make_float2(a0.x, a0.y);
+        xs[(4u * h + 1u) * kThreads + tid] = make_float2(a0.z, a0.w);
+        xs[(4u * h + 2u) * kThreads + tid] = make_float2(a1.x, a1.y);
+        xs[(4u * h + 3u) * kThreads + tid] = make_float2(a1.z, a1.w);
+        if (KEYED) {
+            sum_inputs_pairs(d.key_ins, d.key_k, d.key_term_mode, m, m + 2u, M, a0, a1);
+            if (STORE) { store_pair(const_cast<float2*>(d.kx), m, M, a0); store_pair(const_cast<float2*>(d.kx), m + 2u, M, a1); }
+            ks[(4u * h) * kThreads + tid] = make_float2(a0.x, a0.y);
+            ks[(4u * h + 1u) * kThreads + tid] = make_float2(a0.z, a0.w);
+            ks[(4u * h + 2u) * kThreads + tid] = make_float2(a1.x, a1.y);
+            ks[(4u * h + 3u) * kThreads + tid] = make_float2(a1.z, a1.w);
+        }
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < kVocRun; ++j) {
+        const float2 x = xs[j * kThreads + tid];
+        const float2 kk = KEYED ? ks[j * kThreads + tid] : x;
+        xl[j] = x.x; xr[j] = x.y;
+        xm[j] = voc_mod(kk.x, kk.y);
+    }
+    __syncthreads();   // (the scans write other lanes' words of sv from here on)
+}
+// ... and from the buffers the five-launch form left them in (0 from `frames` on)
+TD_DEV void voc_load_mod(const VocDesc& d, uint32_t f0, double (&xm)[kVocRun]) {
+#pragma unroll
+    for (uint32_t j = 0; j < kVocRun / 2; ++j) {
+        const float4 kk = load_pair(d.kx, f0 + 2u * j, d.frames);
+        xm[2 * j] = voc_mod(kk.x, kk.y);
+        xm[2 * j + 1] = voc_mod(kk.z, kk.w);
+    }
+}
+template <int B, bool KEYED>
+__global__ __launch_bounds__(kThreads) void k_voc_local(const VocDesc* __restrict__ descs) {
+    constexpr int J = kVocJoin;
+    const VocDesc& d = descs[blockIdx.y];
+    if (blockIdx.x >= d.n_tiles) return;
+    __shared__ double sv[6 * J * kThreads];
+    const uint32_t tid = threadIdx.x, f0 = blockIdx.x * kVocTile + tid * kVocRun;
+    float xl[kVocRun], xr[kVocRun];
+    double xm[kVocRun];
+    voc_sum_run<KEYED, true>(d, f0, sv, xl, xr, xm);
+#pragma unroll 1
+    for (uint32_t g = 0; g < (uint32_t)(B / J); ++g) {
+        const VocBand* bd = d.band + g * J;
+        double u[6 * J], zero[6 * J], in[6 * J], last[6 * J];
+#pragma unroll
+        for (int i = 0; i < 6 * J; ++i) { u[i] = 0.0; zero[i] = 0.0; }
+#pragma unroll
+        for (int jb = 0; jb < J; ++jb) {
+            const double c0 = gloadd(&bd[jb].c0), c1 = gloadd(&bd[jb].c1), a1 = gloadd(&bd[jb].a1), a2 = gloadd(&bd[jb].a2);
+#pragma unroll
+            for (uint32_t j = 0; j < kVocRun; ++j) {
+                voc_zstep(c0, c1, a1, a2, u[6 * jb], u[6 * jb + 1], eq_in(xl[j]));
+                voc_zstep(c0, c1, a1, a2, u[6 * jb + 2], u[6 * jb + 3], eq_in(xr[j]));
+                voc_zstep(c0, c1, a1, a2, u[6 * jb + 4], u[6 * jb + 5], xm[j]);
+            }
+        }
+        voc_lane_scan<J, 3, false>(u, bd, zero, sv, in, last);
+        if (tid == 0) {
+            double* a = d.agg + ((size_t)blockIdx.x * B + g * J) * 6u;
+#pragma unroll
+            for (int i = 0; i < 6 * J; i += 2) gstore_d2(a + i, last[i], last[i + 1]);
+        }
+    }
+}
+// MODE 0: entry[t + 1] = A_b^kVocTile entry[t] + total[t] for band b's three two-vectors, entry[0] the line's (k_eq_carry's
+// shape: a lane folds `chunk` consecutive tiles, Hillis-Steele over the lanes, a second walk writes the entries).  MODE 1: the
+// scalar affine carry of e_b with a^kVocTile.  One workgroup per band and vertex: grid (B, n_desc).
+template <int MODE>
+__global__ __launch_bounds__(kThreads) void k_voc_carry(const VocDesc* __restrict__ descs) {
+    const VocDesc& d = descs[blockIdx.y];
+    const uint32_t band = blockIdx.x, B = d.bands;
+    if (band >= B) return;
+    __shared__ double sv[6 * kThreads];
+    const uint32_t tid = threadIdx.x, n = d.n_tiles, c = d.chunk;
+    const uint32_t b = tid * c < n ? tid * c : n, e = b + c < n ? b + c : n;
+    if (MODE == 0) {
+        const VocBand* bd = d.band + band;
+        double P[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) P[i] = gloadd(&bd->a_tile[i]);
+        double init[6], u[6], in[6], last[6];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            init[i] = d.init ? gloadd(d.init + kVocState * band + i) : 0.0;
+            u[i] = tid ? 0.0 : init[i];
+        }
+        for (uint32_t r = b; r < e; ++r) {
+            const double* a = d.agg + ((size_t)r * B + band) * 6u;
+#pragma unroll
+            for (int v = 0; v < 3; ++v) {
+                const d2v t = gload_d2(a + 2 * v);
+                const double n0 = t.x + (P[0] * u[2 * v] + P[1] * u[2 * v + 1]), n1 = t.y + (P[2] * u[2 * v] + P[3] * u[2 * v + 1]);
+                u[2 * v] = n0; u[2 * v + 1] = n1;
+            }
+        }
+        voc_lane_scan<1, 3, true>(u, bd, init, sv, in, last);
+        for (uint32_t r = b; r < e; ++r) {
+            const double* a = d.agg + ((size_t)r * B + band) * 6u;
+            double* o = d.carry + ((size_t)r * B + band) * 6u;
+#pragma unroll
+            for (int v = 0; v < 3; ++v) {
+                gstore_d2(o + 2 * v, in[2 * v], in[2 * v + 1]);
+                const d2v t = gload_d2(a + 2 * v);
+                const double n0 = t.x + (P[0] * in[2 * v] + P[1] * in[2 * v + 1]), n1 = t.y + (P[2] * in[2 * v] + P[3] * in[2 * v + 1]);
+                in[2 * v] = n0; in[2 * v + 1] = n1;
+            }
+        }
+    } else {
+        const double at = d.a_tile;
+        double init[1], u[1], in[1], last[1];
+        init[0] = d.init ? gloadd(d.init + kVocState * band + 6u) : 0.0;
+        u[0] = tid ? 0.0 : init[0];
+        for (uint32_t r = b; r < e; ++r) u[0] = gloadd(d.agge + (size_t)r * B + band) + at * u[0];
+        voc_env_scan<1>(u, d.pwac, init, sv, in, last);
+        for (uint32_t r = b; r < e; ++r) {
+            gstored(d.carrye + (size_t)r * B + band, in[0]);
+            in[0] = gloadd(d.agge + (size_t)r * B + band) + at * in[0];
+        }
+    }
+}
+template <int B>
+__global__ __launch_bounds__(kThreads) void k_voc_env(const VocDesc* __restrict__ descs) {
+    constexpr int J = kVocJoin;
+    const VocDesc& d = descs[blockIdx.y];
+    if (blockIdx.x >= d.n_tiles) return;
+    __shared__ double sv[2 * J * kThreads];
+    const uint32_t tid = threadIdx.x, f0 = blockIdx.x * kVocTile + tid * kVocRun;
+    const double fa = d.a, oa = d.oa;
+    double xm[kVocRun];
+    voc_load_mod(d, f0, xm);
+#pragma unroll 1
+    for (uint32_t g = 0; g < (uint32_t)(B / J); ++g) {
+        const VocBand* bd = d.band + g * J;
+        const double* cy = d.carry + ((size_t)blockIdx.x * B + g * J) * 6u;
+        double cin[2 * J], u[2 * J], z[2 * J], last[2 * J];
+#pragma unroll
+        for (int jb = 0; jb < J; ++jb) {
+            const d2v t = gload_d2(cy + 6 * jb + 4);
+            cin[2 * jb] = t.x; cin[2 * jb + 1] = t.y;
+            u[2 * jb] = tid ? 0.0 : t.x; u[2 * jb + 1] = tid ? 0.0 : t.y;
+            const double c0 = gloadd(&bd[jb].c0), c1 = gloadd(&bd[jb].c1), a1 = gloadd(&bd[jb].a1), a2 = gloadd(&bd[jb].a2);
+#pragma unroll
+            for (uint32_t j = 0; j < kVocRun; ++j) voc_zstep(c0, c1, a1, a2, u[2 * jb], u[2 * jb + 1], xm[j]);
+        }
+        voc_lane_scan<J, 1, false>(u, bd, cin, sv, z, last);
+        double e[J], ezero[J], ein[J], elast[J];
+#pragma unroll
+        for (int jb = 0; jb < J; ++jb) {
+            const double b0 = gloadd(&bd[jb].b0), b1 = gloadd(&bd[jb].b1), b2 = gloadd(&bd[jb].b2), a1 = gloadd(&bd[jb].a1), a2 = gloadd(&bd[jb].a2);
+            e[jb] = 0.0; ezero[jb] = 0.0;
+#pragma unroll
+            for (uint32_t j = 0; j < kVocRun; ++j) e[jb] = fa * e[jb] + oa * fabs(voc_frame(b0, b1, b2, a1, a2, z[2 * jb], z[2 * jb + 1], xm[j]));
+        }
+        voc_env_scan<J>(e, d.pwa, ezero, sv, ein, elast);
+        if (tid < (uint32_t)J) {
+            double w = elast[0];
+#pragma unroll
+            for (int jb = 1; jb < J; ++jb) w = tid == (uint32_t)jb ? elast[jb] : w;
+            gstored(d.agge + (size_t)blockIdx.x * B + g * J + tid, w);
+        }
+    }
+}
+// MODE 0: the five-launch form's last launch (x, kx, carry, carrye from the launches before);  1: the chunk is this one tile --
+// the term loop runs here and the tile enters with the line (a block pull: one launch);  2: the same with the key terms.
+template <int B, int MODE>
+__global__ __launch_bounds__(kThreads) void k_voc_apply(const VocDesc* __restrict__ descs) {
+    constexpr int J = kVocApplyJoin;
+    const VocDesc& d = descs[blockIdx.y];
+    if (blockIdx.x >= d.n_tiles) return;
+    __shared__ double sv[(6 * J > 2 * (int)kVocRun ? 6 * J : 2 * (int)kVocRun) * kThreads];   // (voc_sum_run's two float2 plane sets: 2 kVocRun planes)
+    const uint32_t tid = threadIdx.x, M = d.frames, f0 = blockIdx.x * kVocTile + tid * kVocRun;
+    const double fa = d.a, oa = d.oa;
+    float xl[kVocRun], xr[kVocRun];
+    double xm[kVocRun];
+    if (MODE == 0) {
+#pragma unroll
+        for (uint32_t j = 0; j < kVocRun / 2; ++j) {   // (0 from `frames` on)
+            const float4 x = load_pair(d.x, f0 + 2u * j, M);
+            xl[2 * j] = x.x; xr[2 * j] = x.y; xl[2 * j + 1] = x.z; xr[2 * j + 1] = x.w;
+        }
+        voc_load_mod(d, f0, xm);
+    } else {
+        voc_sum_run<MODE == 2, false>(d, f0, sv, xl, xr, xm);
+    }
+    double accl[kVocRun], accr[kVocRun];
+#pragma unroll
+    for (uint32_t j = 0; j < kVocRun; ++j) { accl[j] = 0.0; accr[j] = 0.0; }
+#pragma unroll 1
+    for (uint32_t g = 0; g < (uint32_t)(B / J); ++g) {
+        const VocBand* bd = d.band + g * J;
+        // the states entering the tile: the carries', or the line's
+        double cin[6 * J], cine[J];
+#pragma unroll
+        for (int jb = 0; jb < J; ++jb) {
+            if (MODE == 0) {
+                const double* cy = d.carry + ((size_t)blockIdx.x * B + g * J + jb) * 6u;
+#pragma unroll
+                for (int v = 0; v < 3; ++v) {
+                    const d2v t = gload_d2(cy + 2 * v);
+                    cin[6 * jb + 2 * v] = t.x; cin[6 * jb + 2 * v + 1] = t.y;
+                }
+                cine[jb] = gloadd(d.carrye + (size_t)blockIdx.x * B + g * J + jb);
+            } else {
+#pragma unroll
+                for (int i = 0; i < 6; ++i) cin[6 * jb + i] = d.init ? gloadd(d.init + kVocState * (g * J + jb) + i) : 0.0;
+                cine[jb] = d.init ? gloadd(d.init + kVocState * (g * J + jb) + 6u) : 0.0;
+            }
+        }
+        double z[6 * J];
+        {
+            double u[6 * J], last[6 * J];
+#pragma unroll
+            for (int jb = 0; jb < J; ++jb) {
+#pragma unroll
+                for (int i = 0; i < 6; ++i) u[6 * jb + i] = tid ? 0.0 : cin[6 * jb + i];
+                const double c0 = gloadd(&bd[jb].c0), c1 = gloadd(&bd[jb].c1), a1 = gloadd(&bd[jb].a1), a2 = gloadd(&bd[jb].a2);
+#pragma unroll
+                for (uint32_t j = 0; j < kVocRun; ++j) {
+                    voc_zstep(c0, c1, a1, a2, u[6 * jb], u[6 * jb + 1], eq_in(xl[j]));
+                    voc_zstep(c0, c1, a1, a2, u[6 * jb + 2], u[6 * jb + 3], eq_in(xr[j]));
+                    voc_zstep(c0, c1, a1, a2, u[6 * jb + 4], u[6 * jb + 5], xm[j]);
+                }
+            }
+            voc_lane_scan<J, 3, false>(u, bd, cin, sv, z, last);
+        }
+        // the follower entering the lane's run: its zero-start run-end value from a copy of the modulator's state, joined
+        double ein[J];
+        {
+            double e[J], elast[J];
+#pragma unroll
+            for (int jb = 0; jb < J; ++jb) {
+                const double b0 = gloadd(&bd[jb].b0), b1 = gloadd(&bd[jb].b1), b2 = gloadd(&bd[jb].b2), a1 = gloadd(&bd[jb].a1), a2 = gloadd(&bd[jb].a2);
+                double s1 = z[6 * jb + 4], s2 = z[6 * jb + 5];
+                e[jb] = tid ? 0.0 : cine[jb];
+#pragma unroll
+                for (uint32_t j = 0; j < kVocRun; ++j) e[jb] = fa * e[jb] + oa * fabs(voc_frame(b0, b1, b2, a1, a2, s1, s2, xm[j]));
+            }
+            voc_env_scan<J>(e, d.pwa, cine, sv, ein, elast);
+        }
+        // the definition, serially; the bands add up in band order
+#pragma unroll
+        for (int jb = 0; jb < J; ++jb) {
+            const double b0 = gloadd(&bd[jb].b0), b1 = gloadd(&bd[jb].b1), b2 = gloadd(&bd[jb].b2), a1 = gloadd(&bd[jb].a1), a2 = gloadd(&bd[jb].a2);
+            double e = ein[jb];
+#pragma unroll
+            for (uint32_t j = 0; j < kVocRun; ++j) {
+                const double cl = voc_frame(b0, b1, b2, a1, a2, z[6 * jb], z[6 * jb + 1], eq_in(xl[j]));
+                const double cr = voc_frame(b0, b1, b2, a1, a2, z[6 * jb + 2], z[6 * jb + 3], eq_in(xr[j]));
+                const double km = voc_frame(b0, b1, b2, a1, a2, z[6 * jb + 4], z[6 * jb + 5], xm[j]);
+                e = fa * e + oa * fabs(km);
+                accl[j] = accl[j] + e * cl;
+                accr[j] = accr[j] + e * cr;
+                if (f0 + j + 1u == M) {   // the chunk's last frame: what the next chunk / block pull enters with
+                    double* ln = d.line + kVocState * (g * J + jb);
+#pragma unroll
+                    for (int i = 0; i < 6; ++i) gstored(ln + i, z[6 * jb + i]);
+                    gstored(ln + 6, e);
+                }
+            }
+        }
+    }
+    const double gn = d.g;
+    const float wet = d.wet;
+#pragma unroll
+    for (uint32_t j = 0; j < kVocRun / 2; ++j) {
+        const uint32_t m = f0 + 2u * j;
+        if (m >= M) break;
+        const float4 x = make_float4(xl[2 * j], xr[2 * j], xl[2 * j + 1], xr[2 * j + 1]);
+        const float4 p = make_float4((float)(gn * accl[2 * j]), (float)(gn * accr[2 * j]), (float)(gn * accl[2 * j + 1]), (float)(gn * accr[2 * j + 1]));
+        // the reference's lerp (adsr.rs:42), f32
+        const float4 o = make_float4(x.x + wet * (p.x - x.x), x.y + wet * (p.y - x.y), x.z + wet * (p.z - x.z), x.w + wet * (p.w - x.w));
+        store_pair(d.out, m, M, epilogue4(o, d.pg));
+    }
+}
+
 constexpr int kMaxGridY = 65535;
 
 // Batched launches put the vertex index in grid.y (limit 65535): larger batches go out in slices.
@@ -6940,6 +7320,42 @@ void launch_phaser_apply(const PhaserDesc* d, int n, uint32_t stages, uint32_t n
         if (single) { TD_PHASER_STAGES(hipLaunchKernelGGL((k_phaser_apply<N, true>), dim3(n_tiles, std::min(n - o, kMaxGridY)), dim3(kPhaserLanes), 0, s, d + o)); }
         else { TD_PHASER_STAGES(hipLaunchKernelGGL((k_phaser_apply<N, false>), dim3(n_tiles, std::min(n - o, kMaxGridY)), dim3(kPhaserLanes), 0, s, d + o)); }
     }
+}
+// (a launch holds the vertices of one band count: the kernels are templates on it)
+#define TD_VOC_BANDS(CALL)                     \
+    switch (bands) {                           \
+        case 4: { constexpr int B = 4; CALL; break; }   \
+        case 8: { constexpr int B = 8; CALL; break; }   \
+        case 16: { constexpr int B = 16; CALL; break; } \
+        default: break;                        \
+    }
+void launch_voc_local(const VocDesc* d, int n, uint32_t bands, uint32_t n_tiles, hipStream_t s) {
+    for (int o = 0; o < n && n_tiles; o += kMaxGridY)
+        TD_VOC_BANDS(hipLaunchKernelGGL((k_voc_local<B, false>), dim3(n_tiles, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o));
+}
+void launch_voc_local_keyed(const VocDesc* d, int n, uint32_t bands, uint32_t n_tiles, hipStream_t s) {
+    for (int o = 0; o < n && n_tiles; o += kMaxGridY)
+        TD_VOC_BANDS(hipLaunchKernelGGL((k_voc_local<B, true>), dim3(n_tiles, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o));
+}
+void launch_voc_carry(const VocDesc* d, int n, uint32_t bands, bool env, hipStream_t s) {
+    for (int o = 0; o < n && bands; o += kMaxGridY) {
+        if (env) hipLaunchKernelGGL(k_voc_carry<1>, dim3(bands, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
+        else hipLaunchKernelGGL(k_voc_carry<0>, dim3(bands, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
+    }
+}
+void launch_voc_env(const VocDesc* d, int n, uint32_t bands, uint32_t n_tiles, hipStream_t s) {
+    for (int o = 0; o < n && n_tiles; o += kMaxGridY)
+        TD_VOC_BANDS(hipLaunchKernelGGL(k_voc_env<B>, dim3(n_tiles, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o));
+}
+void launch_voc_apply(const VocDesc* d, int n, uint32_t bands, uint32_t n_tiles, bool single, hipStream_t s) {
+    for (int o = 0; o < n && n_tiles; o += kMaxGridY) {
+        if (single) { TD_VOC_BANDS(hipLaunchKernelGGL((k_voc_apply<B, 1>), dim3(n_tiles, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o)); }
+        else { TD_VOC_BANDS(hipLaunchKernelGGL((k_voc_apply<B, 0>), dim3(n_tiles, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o)); }
+    }
+}
+void launch_voc_apply_keyed(const VocDesc* d, int n, uint32_t bands, uint32_t n_tiles, hipStream_t s) {
+    for (int o = 0; o < n && n_tiles; o += kMaxGridY)
+        TD_VOC_BANDS(hipLaunchKernelGGL((k_voc_apply<B, 2>), dim3(n_tiles, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o));
 }
 void launch_sample_loop(const LoopDesc* d, int n, uint32_t frames, hipStream_t s) {
     if (!n || !frames) return;

@@ -22,6 +22,7 @@
 #include "eq_math.h"
 #include "gate_math.h"
 #include "phaser_math.h"
+#include "vocoder_math.h"
 #include "lua_subset.h"
 #include "reverb_math.h"
 #include "master.h"
@@ -114,6 +115,7 @@ struct DelayCall { std::string name; float gain, angle, wet, time_ms, feedback, 
 struct ChorusCall { std::string name; float gain, angle, wet; int voices; float delay_ms, depth_ms, rate_hz, stereo; int shape; };
 struct ReverbCall { std::string name; float gain, angle, wet, room, damp, width, size; };
 struct PhaserCall { std::string name; float gain, angle, wet; int stages; float lo_hz, hi_hz, rate_hz, feedback, stereo; int shape; };
+struct VocoderCall { std::string name; float gain, angle, wet; int bands; float lo_hz, hi_hz, q, response_ms, out_db; };
 struct GateCall { std::string name; float gain, angle, wet, threshold_db, hysteresis_db, hold_ms, attack_ms, release_ms, range_db; };
 struct SatCall { std::string name; float gain, angle, wet; int kind; float drive_db, bias, out_db; int oversample; };
 
@@ -239,6 +241,7 @@ int do_refresh(td_state* s, const std::string& contents) {
     std::vector<ReverbCall> reverbs;
     std::vector<GateCall> gates;
     std::vector<PhaserCall> phasers;
+    std::vector<VocoderCall> vocoders;
     size_t cs = s->cs, render_sr = s->render_sr, bd = s->bd;
     // std::mem::take (state.rs:79-80): the locals start from the previous values, the State's own fields are left
     // EMPTY until the script has run (state.rs:169-170) -- so they stay empty when the script fails
@@ -496,6 +499,18 @@ int do_refresh(td_state* s, const std::string& contents) {
                 fnum(c.hi_hz) + "," + fnum(c.rate_hz) + "," + fnum(c.feedback) + "," + fnum(c.stereo) + ",\"" + shape + "\")\n";
         return Value::nil();
     });
+    lua.set_function("add_vocoder", [&](const std::vector<Value>& a) {   // this engine's own vertex (termdaw_amd.h td_graph_add_vocoder)
+        const char* f = "add_vocoder";
+        const float bands = to_f32(f, a, 4);
+        if (!(bands == 4.0f || bands == 8.0f || bands == 16.0f)) throw LuaError{"add_vocoder: bands must be 4, 8 or 16"};
+        vocoders.push_back({to_str(f, a, 0), to_f32(f, a, 1), to_f32(f, a, 2), to_f32(f, a, 3), (int)bands, to_f32(f, a, 5), to_f32(f, a, 6), to_f32(f, a, 7), to_f32(f, a, 8), to_f32(f, a, 9)});
+        auto& c = vocoders.back();
+        // (out-of-range parameters are rejected here, where the line is known)
+        if (const char* why = tde::vocoder::check(psr, c.bands, c.lo_hz, c.hi_hz, c.q, c.response_ms, c.out_db)) throw LuaError{std::string("add_vocoder: ") + why};
+        dump += std::string(f) + "(\"" + c.name + "\"," + fnum(c.gain) + "," + fnum(c.angle) + "," + fnum(c.wet) + "," + std::to_string(c.bands) + "," + fnum(c.lo_hz) + "," +
+                fnum(c.hi_hz) + "," + fnum(c.q) + "," + fnum(c.response_ms) + "," + fnum(c.out_db) + ")\n";
+        return Value::nil();
+    });
     lua.set_function("connect", [&](const std::vector<Value>& a) {
         edges.push_back({to_str("connect", a, 0), to_str("connect", a, 1)});
         dump += "connect(\"" + edges.back().first + "\",\"" + edges.back().second + "\")\n";
@@ -631,6 +646,8 @@ int do_refresh(td_state* s, const std::string& contents) {
         if (!td_graph_add_gate(s->g, c.name.c_str(), c.gain, c.angle, c.wet, c.threshold_db, c.hysteresis_db, c.hold_ms, c.attack_ms, c.release_ms, c.range_db)) return 0;
     for (auto& c : phasers)
         if (!td_graph_add_phaser(s->g, c.name.c_str(), c.gain, c.angle, c.wet, c.stages, c.lo_hz, c.hi_hz, c.rate_hz, c.feedback, c.stereo, c.shape)) return 0;
+    for (auto& c : vocoders)
+        if (!td_graph_add_vocoder(s->g, c.name.c_str(), c.gain, c.angle, c.wet, c.bands, c.lo_hz, c.hi_hz, c.q, c.response_ms, c.out_db)) return 0;
     for (auto& e : edges) td_graph_connect(s->g, e.first.c_str(), e.second.c_str());   // failures only warn (state.rs:459)
     for (auto& e : key_edges) td_graph_connect_key(s->g, e.first.c_str(), e.second.c_str());   // (after the edges; failures only warn, like theirs)
     td_graph_set_output(s->g, s->output_vertex.c_str());

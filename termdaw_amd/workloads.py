@@ -169,7 +169,7 @@ class ProjectScript:
         self.calls = {k: [] for k in (
             "load_sample", "load_resource", "load_midi_floww", "add_sum", "add_normalize", "add_sampleloop",
             "add_sample_multi", "add_sample_lerp", "add_debug_sine", "add_synth", "add_sampsyn", "add_adsr",
-            "add_bandpass", "add_compressor", "add_eq", "add_delay", "add_saturator", "add_chorus", "add_reverb", "add_gate", "add_phaser", "connect", "connect_key")}
+            "add_bandpass", "add_compressor", "add_eq", "add_delay", "add_saturator", "add_chorus", "add_reverb", "add_gate", "add_phaser", "add_vocoder", "connect", "connect_key")}
         self.resources = {}                 # path -> bytes (load_resource)
         self.script_order = []              # (fn, args) in call order, for to_lua()
 
@@ -272,11 +272,15 @@ class ProjectScript:
         """This engine's own vertex (include/termdaw_amd.h td_graph_add_phaser): no reference counterpart.  shape: the string name."""
         self._rec("add_phaser", name, gain, angle, wet, stages, lo_hz, hi_hz, rate_hz, feedback, stereo, shape)
 
+    def add_vocoder(self, name, gain, angle, wet, bands, lo_hz, hi_hz, q, response_ms, out_db):
+        """This engine's own vertex (include/termdaw_amd.h td_graph_add_vocoder): no reference counterpart."""
+        self._rec("add_vocoder", name, gain, angle, wet, bands, lo_hz, hi_hz, q, response_ms, out_db)
+
     def connect(self, a, b):
         self._rec("connect", a, b)
 
     def connect_key(self, a, b):
-        """This engine's own edge (include/termdaw_amd.h td_graph_connect_key): the key input of a compressor or gate vertex."""
+        """This engine's own edge (include/termdaw_amd.h td_graph_connect_key): the key input of a compressor, gate or vocoder vertex."""
         self._rec("connect_key", a, b)
 
     # -- State::refresh (state.rs:202-467) --
@@ -347,6 +351,8 @@ class ProjectScript:
             g.add_gate(*args)
         for args in self.calls["add_phaser"]:
             g.add_phaser(*args)
+        for args in self.calls["add_vocoder"]:
+            g.add_vocoder(*args)
         for a, b in self.calls["connect"]:
             g.connect(a, b)
         for a, b in self.calls["connect_key"]:   # (after the connect calls, as the front-end applies them)
@@ -571,6 +577,39 @@ def synth_project(seconds=3.0, bl=1024, voices=5):
     p.connect("env48", "mix")
     p.connect("mix", "cut")
     p.connect("cut", "sum")
+    p.set_output("sum")
+    return p
+
+
+def vocoder_project(seconds=3.0, bl=1024, bands=16, wet=1.0):
+    """A sustained synth chord as carrier, the drum loop as key: the chord only sounds where, and in the bands in which, the
+    drums do (a vocoder vertex, this engine's own)."""
+    p = ProjectScript(48000, bl)
+    p.set_length(seconds)
+    p.assets["kick"] = Asset(kick_int16(12, 15000))
+    p.assets["snare"] = Asset(snare_int16(14, 9000))
+    p.load_sample("kick", "kick", "mix-down")
+    p.load_sample("snare", "snare", "mix-down")
+    ev = [(0.005 + 0.0003 * j, n, 0.6) for j, n in enumerate((48.0, 52.0, 55.0, 59.0, 62.0))]   # one chord, held to the end
+    p.event_files["chord"] = np.array(ev, dtype=np.float32)
+    kicks = [(0.5 * i, 36.0, 1.0) for i in range(int(seconds / 0.5))]
+    snares = [(0.25 + 0.5 * i, 38.0, 0.8) for i in range(int(seconds / 0.5))]
+    p.event_files["kicks"] = np.array(kicks, dtype=np.float32)
+    p.event_files["snares"] = np.array(snares, dtype=np.float32)
+    p.load_midi_floww("chord", "chord")
+    p.load_midi_floww("kicks", "kicks")
+    p.load_midi_floww("snares", "snares")
+    p.add_synth("pad", 0.8, 0.0, "chord", 0.4, 0.3, HIT_ADSR, 1.0, 0.8, NOTE_ADSR, 0.5, STD_ADSR)
+    p.add_sample_lerp("kick", 1.0, -10.0, "kick", "kicks", -1, 40)
+    p.add_sample_lerp("snare", 0.8, 15.0, "snare", "snares", -1, 40)
+    p.add_sum("drums", 1.0, 0.0)
+    p.add_vocoder("voc", 1.0, 0.0, wet, bands, 100.0, 8000.0, 6.0, 8.0, 24.0)
+    p.add_normalize("sum", 0.9, 0.0)
+    p.connect("kick", "drums")
+    p.connect("snare", "drums")
+    p.connect("pad", "voc")
+    p.connect_key("drums", "voc")
+    p.connect("voc", "sum")
     p.set_output("sum")
     return p
 
