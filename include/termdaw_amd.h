@@ -443,9 +443,69 @@ int td_graph_add_vocoder(td_graph* g, const char* name, float gain, float angle,
  * b0, b1, b2, a1, a2 for b = 0 .. bands - 1, then out[6 bands] = a, out[6 bands + 1] = g.  `cap`: the doubles `out` holds, at least
  * 6 bands + 2.  The same range checks as td_graph_add_vocoder. */
 int td_vocoder_params(size_t sr, int bands, float lo_hz, float hi_hz, float q, float response_ms, float out_db, double* out, size_t cap);
+/* A filter vertex: a resonant state-variable filter whose cutoff is swept by an LFO and by an envelope follower -- THIS ENGINE'S
+ * OWN: no reference counterpart (add_bandpass and td_graph_add_eq have fixed coefficients).  The vertex sums its
+ * inputs like every input vertex (sum_inputs, extensions.rs:310-319), processes the sum (l, r), mixes with `wet` by the
+ * reference's f32 lerp, then pan and gain like every vertex (extensions.rs:262-263).  Everything below is f64 on the f32 sums,
+ * with no FMA contraction, in the order written.
+ *   Constants, once on the host, each from the f32 parameter widened to f64 (td_filter_params returns exactly these):
+ *     g0 = tan(pi freq_hz / sr);  k = 1 / q;  gmin = tan(pi 20 / sr);  gmax = tan(0.45 pi);
+ *     cl = ln2 lfo_oct;  ce = ln2 env_oct;  f = rate_hz / sr;  S = 10^(sens_db / 20);
+ *     aA = exp(-1 / (attack_ms sr / 1000)), 0 for attack_ms = 0;  aR likewise from release_ms.
+ *   Per frame, at the ABSOLUTE frame n (the graph's time, as for the chorus and the phaser):
+ *     1. Level, stereo-linked, in the linear domain (the compressor's steps 1, 3 and 4).  The key frame (kl, kr) is the f32 sum of
+ *        the vertex' key sources (td_graph_connect_key below); without a key edge (kl, kr) = (l, r), as an unkeyed compressor
+ *        listens to itself.
+ *          s[n] = max(|kl|, |kr|), and 0 for a key frame with a NaN or an infinity
+ *          y1[n] = max(s[n], aR y1[n-1])
+ *          e[n] = aA e[n-1] + (1 - aA) y1[n]                              (1 - aA is rounded once)
+ *     2. Control, per channel c: phi = 0 on the left, phi = stereo on the right
+ *          th = n f + phi;  th = th - floor(th)
+ *          t = cl lfo(shape, th) + ce min(S e[n], 1)       (lfo: td_graph_add_chorus' -- sine or triangle; there is no second LFO)
+ *     3. Cutoff.  The sweep is exponential: octaves of the prewarped coefficient g, which are octaves of Hz below about sr / 8.
+ *          g = min(max(g0 E(t), gmin), gmax)
+ *        E(t) is this FIXED sequence of IEEE multiplies and adds -- no libm call runs on the device; every implementation computes
+ *        the same E(t) from the same t:
+ *          x = t 0.0625;  p = 1;  for j = 10 down to 1: p = 1 + p (x c_j);  then four times: p = p p;  E = p
+ *          c_j is the double nearest 1 / j: c_10 = 0.1, c_9 = 0.1111111111111111, c_8 = 0.125, c_7 = 0.14285714285714285,
+ *          c_6 = 0.16666666666666666, c_5 = 0.2, c_4 = 0.25, c_3 = 0.3333333333333333, c_2 = 0.5, c_1 = 1.
+ *        Over |t| <= 10.5 it is within 7.2e-9 relative of exp(t); the ranges below keep |t| <= 12 ln2 = 8.32.
+ *     4. The filter: the trapezoidal (zero-delay-feedback) state-variable filter, per channel, state (i1, i2).  xs = x[n] if
+ *        finite, else 0.
+ *          a1 = 1 / (1 + g (g + k));  a2 = g a1;  a3 = g a2                   (one correctly rounded f64 division)
+ *          v3 = xs - i2;  v1 = a1 i1 + a2 v3;  v2 = (i2 + a2 i1) + a3 v3
+ *          i1 = 2 v1 - i1;  i2 = 2 v2 - i2
+ *          low-pass p = v2;  band-pass p = k v1 (0 dB peak);  high-pass p = (xs - k v1) - v2;  notch p = xs - k v1
+ *          p[n] = (float)p
+ *     5. Output: out = x + wet * (p - x) in f32 (adsr.rs:42) -- a non-finite x[n] comes out as what IEEE makes of it, at that
+ *        frame only -- then pan and gain.  wet < 0.0001: the summed input passes through untouched (a plain k_sum launch), the
+ *        state stays as it is and key edges are ignored bit for bit.
+ * State: (y1, e, i1l, i2l, i1r, i2r), six doubles, zero at time 0; carried between consecutive block pulls and between the chunks
+ * of a render, restarted from zero by td_graph_set_time / td_graph_change_time / td_graph_reset.  The LFO never restarts: it is a
+ * function of the graph's time.  No latency, no tail.
+ * env_oct == 0: the detector is not run -- y1 and e stay as they are, key edges are ignored, and the output is bit for bit that
+ * of the same vertex without them.
+ * Ranges, rejected with a td_last_error that names the parameter (NaN and the infinities included): kind 0 .. 3 (TD_FILTER_*);
+ * freq_hz [20, 0.45 sr]; q [0.5, 30]; lfo_oct [0, 4]; rate_hz [0.01, 20]; stereo [0, 0.5]; shape 0 .. 1 (TD_CHORUS_*); env_oct
+ * [-8, 8]; sens_db [0, 60]; attack_ms [0, 1000]; release_ms [1, 10000].  `wet` is clamped to [0, 1].
+ * Under "band_mode" 2 / "sine_mode" 2 everything upstream of a filter vertex that is not dry takes the exact forms, and so does
+ * everything upstream of a key edge into one whose follower runs: the resonance gain follows the signal and the time, and no
+ * static bound of it is proven; vertices downstream are unaffected.
+ * Not part of the vertex: a ladder or other topology, slopes beyond 12 dB / octave (two vertices in series give 24), tempo sync,
+ * a per-note envelope, audio-rate modulation of the cutoff. */
+enum { TD_FILTER_LOWPASS = 0, TD_FILTER_HIGHPASS = 1, TD_FILTER_BANDPASS = 2, TD_FILTER_NOTCH = 3 };
+int td_graph_add_filter(td_graph* g, const char* name, float gain, float angle, float wet, int kind, float freq_hz, float q,
+                        float lfo_oct, float rate_hz, float stereo, int shape,
+                        float env_oct, float sens_db, float attack_ms, float release_ms);
+/* Host only, no GPU: the filter vertex' constants at rate sr, exactly the doubles the engine uses -- out[0 .. 10] = g0, k, gmin,
+ * gmax, cl, ce, f, S, aA, 1 - aA, aR.  `cap`: the doubles `out` holds, at least 11.  The same range checks as
+ * td_graph_add_filter. */
+int td_filter_params(size_t sr, int kind, float freq_hz, float q, float lfo_oct, float rate_hz, float stereo, int shape,
+                     float env_oct, float sens_db, float attack_ms, float release_ms, double* out, size_t cap);
 int td_graph_connect(td_graph* g, const char* a, const char* b);          /* graph.rs:80-96 (+58-78) */
-/* A key edge (sidechain) from any vertex `a` to a compressor, gate or vocoder vertex `b` -- THIS ENGINE'S OWN, like the vertices.  A
- * vocoder vertex takes its MODULATOR from the key frames defined here (td_graph_add_vocoder above); for the other two: a
+/* A key edge (sidechain) from any vertex `a` to a compressor, gate, vocoder or filter vertex `b` -- THIS ENGINE'S OWN, like the
+ * vertices.  A vocoder vertex takes its MODULATOR from the key frames defined here (td_graph_add_vocoder above), a filter vertex
+ * the LEVEL its envelope follows (td_graph_add_filter above; ignored when its env_oct is 0); for the other two: a
  * vertex with at least one key edge takes its LEVEL from the sum of its key sources; everything else is as without: it processes
  * the sum of its inputs, carries the same state, keeps its wet mix, pan and gain.
  *   The key frames (kl[n], kr[n]) are the f32 sum of the key sources' outputs, each with its own pan and gain applied, summed in
@@ -458,7 +518,7 @@ int td_graph_connect(td_graph* g, const char* a, const char* b);          /* gra
  *   A key is not an input: td_graph_check's "output receives no inputs" is unchanged, and a keyed vertex without inputs
  *   processes silence.  A dry vertex (wet < 0.0001) ignores its key edges: its output is bit for bit that of the same vertex
  *   without them.
- * Returns 0 (td_last_error) for an unknown name (td_graph_connect's messages); when `b` is not a compressor, gate or vocoder vertex
+ * Returns 0 (td_last_error) for an unknown name (td_graph_connect's messages); when `b` is not a compressor, gate, vocoder or filter vertex
  * ("connect_key: <b> takes no key input"); when the edge would close a loop.  The loop test of td_graph_connect and of
  * td_graph_connect_key runs over the union of input and key edges.  td_graph_reset clears key edges, as it clears edges.  A key
  * source is rendered like an input, also when only the key edge reaches it.

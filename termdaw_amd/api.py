@@ -81,6 +81,8 @@ SIGNATURES = {
     "td_graph_add_gate": (_i32, [_vp, _cp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32]),
     "td_graph_add_vocoder": (_i32, [_vp, _cp, _f32, _f32, _f32, _i32, _f32, _f32, _f32, _f32, _f32]),
     "td_vocoder_params": (_i32, [_sz, _i32, _f32, _f32, _f32, _f32, _f32, C.POINTER(C.c_double), _sz]),
+    "td_graph_add_filter": (_i32, [_vp, _cp, _f32, _f32, _f32, _i32, _f32, _f32, _f32, _f32, _f32, _i32, _f32, _f32, _f32, _f32]),
+    "td_filter_params": (_i32, [_sz, _i32, _f32, _f32, _f32, _f32, _f32, _i32, _f32, _f32, _f32, _f32, C.POINTER(C.c_double), _sz]),
     "td_gate_params": (_i32, [_sz, _f32, _f32, _f32, _f32, _f32, _f32, C.POINTER(C.c_double)]),
     "td_reverb_params": (_i32, [_sz, _f32, _f32, _f32, _f32, C.POINTER(C.c_double)]),
     "td_graph_connect": (_i32, [_vp, _cp, _cp]),
@@ -353,6 +355,27 @@ def phaser_params(sr, stages, lo_hz, hi_hz, rate_hz, feedback, stereo, shape):
     return (int(out[0]),) + tuple(out[1:7])
 
 
+FILTER_KINDS = ("lowpass", "highpass", "bandpass", "notch")   # TD_FILTER_* in order
+
+
+def filter_kind(kind):
+    """A kind name of FILTER_KINDS (or an index) as the TD_FILTER_* integer."""
+    if isinstance(kind, str):
+        if kind not in FILTER_KINDS:
+            raise ValueError("filter kind %r: one of %s" % (kind, ", ".join(FILTER_KINDS)))
+        return FILTER_KINDS.index(kind)
+    return int(kind)
+
+
+def filter_params(sr, kind, freq_hz, q, lfo_oct, rate_hz, stereo, shape, env_oct, sens_db, attack_ms, release_ms):
+    """(g0, k, gmin, gmax, cl, ce, f, S, aA, 1 - aA, aR): the filter vertex' constants at rate sr, exactly the doubles the engine uses
+    (host only).  kind: "lowpass" | "highpass" | "bandpass" | "notch"; shape: the chorus' names."""
+    out = (C.c_double * 11)()
+    _check(lib().td_filter_params(int(sr), filter_kind(kind), freq_hz, q, lfo_oct, rate_hz, stereo, chorus_shape(shape), env_oct, sens_db,
+                                  attack_ms, release_ms, out, 11))
+    return tuple(out[0:11])
+
+
 def vocoder_params(sr, bands, lo_hz, hi_hz, q, response_ms, out_db):
     """(rows, a, g): the vocoder vertex' constants at rate sr, exactly the doubles the engine uses (host only) -- rows[b] = (f_b, b0,
     b1, b2, a1, a2) per band, a the follower's coefficient, g the output gain."""
@@ -618,11 +641,18 @@ class Graph:
         16; its inputs are the carrier, its key edges (connect_key) the modulator."""
         _check(lib().td_graph_add_vocoder(self.h, name.encode(), gain, angle, wet, int(bands), lo_hz, hi_hz, q, response_ms, out_db))
 
+    def add_filter(self, name, gain, angle, wet, kind, freq_hz, q, lfo_oct, rate_hz, stereo, shape, env_oct, sens_db, attack_ms, release_ms):
+        """A filter vertex: a state-variable filter swept by an LFO and an envelope follower (this engine's own; the definition is in
+        include/termdaw_amd.h).  kind "lowpass" | "highpass" | "bandpass" | "notch"; shape "sine" or "triangle" (or the constants);
+        its key edges (connect_key) feed the follower."""
+        _check(lib().td_graph_add_filter(self.h, name.encode(), gain, angle, wet, filter_kind(kind), freq_hz, q, lfo_oct, rate_hz, stereo,
+                                         chorus_shape(shape), env_oct, sens_db, attack_ms, release_ms))
+
     def connect(self, a, b):
         return bool(lib().td_graph_connect(self.h, a.encode(), b.encode()))
 
     def connect_key(self, a, b):
-        """A key edge (sidechain) from any vertex a to a compressor, gate or vocoder vertex b: b takes its level (a vocoder: its
+        """A key edge (sidechain) from any vertex a to a compressor, gate, vocoder or filter vertex b: b takes its level (a vocoder: its
         modulator) from the sum of its key sources and goes on processing the sum of its inputs (include/termdaw_amd.h td_graph_connect_key).  False: last_error()."""
         return bool(lib().td_graph_connect_key(self.h, a.encode(), b.encode()))
 
@@ -743,7 +773,7 @@ class Graph:
         lib().td_graph_set_profiling(self.h, int(on))
 
     def kernel_times(self):
-        cap = 32
+        cap = 64   # (a level with every effect kind in it takes more than 32 launch families)
         names = (_cp * cap)()
         ms = (C.c_float * cap)()
         cnt = (_sz * cap)()
@@ -980,7 +1010,7 @@ class Batch:
         lib().td_batch_set_profiling(self.h, int(on))
 
     def kernel_times(self):
-        cap = 32
+        cap = 64   # (a level with every effect kind in it takes more than 32 launch families)
         names = (_cp * cap)()
         ms = (C.c_float * cap)()
         cnt = (_sz * cap)()

@@ -3,7 +3,7 @@
 // this file calls the HIP runtime: device memory reaches it as addresses handed out by three functions of engine.cpp
 // (compile.h: take_buffer / ensure_buffers for edge buffers, upload_tables for a vertex' event tables), everything it
 // writes goes into the plain-memory staging arena of the ChunkBuild (offsets + fix-up lists that submit_chunk patches once
-// the device addresses are known).  The effect kinds (compressor .. vocoder) are lowered by compile_fx.cpp, through the table there;
+// the device addresses are known).  The effect kinds (compressor .. filter) are lowered by compile_fx.cpp, through the table there;
 // that file is included at the end of this one (see there).  tests/test_compile_asan.py builds it with g++
 // -fsanitize=address,undefined.
 #include "compile.h"
@@ -32,7 +32,8 @@ const char* const kFamilyName[F_COUNT] = {"k_sample_loop", "k_sample_multi", "k_
                                            "k_reverb_sum", "k_reverb",
                                            "k_gate_detect", "k_gate_carry_hc", "k_gate_env", "k_gate_carry_env", "k_gate_apply",
                                            "k_phaser_local", "k_phaser_carry", "k_phaser_apply",
-                                           "k_voc_local", "k_voc_carry_z", "k_voc_env", "k_voc_carry_env", "k_voc_apply"};
+                                           "k_voc_local", "k_voc_carry_z", "k_voc_env", "k_voc_carry_env", "k_voc_apply",
+                                           "k_filt_detect", "k_filt_carry_y1", "k_filt_env", "k_filt_carry_e", "k_filt_local", "k_filt_carry", "k_filt_apply"};
 
 
 // ------------------------------------------------------------------------------------------------
@@ -835,7 +836,7 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
     g->band_stats_base = nullptr;
     g->guard.chunk_audited = false;
     // `cons`: who reads a vertex' frames, through an input edge or a key edge (td_graph_connect_key) -- what every rule below
-    // that elides or releases a source's frames counts; `live_key`: the vertex is the key source of a vertex that is not dry
+    // that elides or releases a source's frames counts; `live_key`: the vertex is the key source of a vertex that reads its key (not dry; a filter: its follower runs)
     std::vector<std::vector<size_t>> cons(nv);
     std::vector<char> live_key(nv, 0);
     bool any_key = false;
@@ -844,7 +845,7 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
         for (size_t u : g->key_edges[vi]) {
             cons[u].push_back(vi);
             any_key = true;
-            if (!(g->vertices[vi].wet < 0.0001f)) live_key[u] = 1;
+            if (g->vertices[vi].reads_key()) live_key[u] = 1;
         }
     }
     // ... and who reads them as an input: what the guard carries its estimate along
@@ -1514,7 +1515,7 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
             if (!adsr_through.empty()) term_mode[vi] = ins.size() == 1 ? TERMS_ADSR1 : TERMS_WITH_ADSR;
             // the key terms (td_graph_connect_key), next to the input terms: kinds 0 .. 4 -- a key source has the keyed vertex
             // among its consumers, so it is never read through as an envelope, never inside a chain launch, never a folded pre-sum
-            if (!g->key_edges[vi].empty() && !(g->vertices[vi].wet < 0.0001f)) {
+            if (!g->key_edges[vi].empty() && g->vertices[vi].reads_key()) {
                 std::vector<InTerm> kin;
                 bool k_edge = true, k_loop = true, k_loop16 = true;
                 for (size_t u : g->key_edges[vi]) {
@@ -2372,7 +2373,9 @@ size_t desc_size(int fam) {
         case F_AUDIT: return sizeof(AuditHead);
         case F_STEMS: return sizeof(StemDesc);
         case F_COMP_CARRY1:
-        case F_COMP_CARRY2: return sizeof(MasterDesc);   // (k_master_carry, inside the compressor's families)
+        case F_COMP_CARRY2:
+        case F_FILT_CARRY1:
+        case F_FILT_CARRY2: return sizeof(MasterDesc);   // (k_master_carry, inside the compressor's and the filter's families)
         default: {
             const FxKind* fx = fx_of_family(fam);
             return fx ? fx->desc_bytes : 0;

@@ -23,6 +23,7 @@ enum Family { F_LOOP, F_MULTI, F_LERP, F_SINE, F_SYNTH, F_SAMPSYN, F_ENV, F_PROB
               F_GATE_DETECT, F_GATE_CARRY_H, F_GATE_ENV, F_GATE_CARRY_ENV, F_GATE_APPLY /* a level's gate vertices: k_gate_detect, k_gate_carry (the (h, c) entering each tile), k_gate_env, k_gate_carry (the env entering each tile), k_gate_apply -- in this order */,
               F_PHASER_LOCAL, F_PHASER_CARRY, F_PHASER_APPLY /* a level's phaser vertices, per stage count: k_phaser_local, k_phaser_carry (both over multi-tile chunks only), k_phaser_apply -- in this order */,
               F_VOC_LOCAL, F_VOC_CARRY, F_VOC_ENV, F_VOC_CARRY_ENV, F_VOC_APPLY /* a level's vocoder vertices, per band count and keyed or not: k_voc_local, k_voc_carry (the biquads' states entering each tile), k_voc_env, k_voc_carry (the followers'), all four over multi-tile chunks only, k_voc_apply -- in this order */,
+              F_FILT_DETECT, F_FILT_CARRY1, F_FILT_ENV, F_FILT_CARRY2, F_FILT_LOCAL, F_FILT_CARRY, F_FILT_APPLY /* a level's filter vertices: k_filt_detect, k_master_carry (y1), k_filt_env, k_master_carry (e) -- these four over the vertices whose follower runs -- k_filt_local, k_filt_carry, all six over multi-tile chunks only, k_filt_apply -- in this order */,
               F_COUNT };
 extern const char* const kFamilyName[F_COUNT];
 
@@ -39,7 +40,7 @@ bool is_delay_family(int fam);
 double ms_between(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b);
 tdk::PanGain make_pg(float gain, float angle);           // a vertex' pan / gain as its kernel's epilogue applies it (sample.rs:98-109)
 
-// ---- compile_fx.cpp: the effect kinds (compressor, EQ, delay, saturator, chorus, reverb, gate, phaser, vocoder) ----
+// ---- compile_fx.cpp: the effect kinds (compressor, EQ, delay, saturator, chorus, reverb, gate, phaser, vocoder, filter) ----
 // What lowering the vertices of one effect kind at one level needs of compile_chunk, and the steps every kind's lowering
 // shares.  The kinds' own functions (lower_comp ..) keep what is theirs: coefficients, tiling, scratch, launches.
 struct FxLevel {
@@ -52,7 +53,7 @@ struct FxLevel {
     int fam;              // the family the level's loop has reached (FxKind::family of the vertices handed over)
     std::map<size_t, size_t>& ins_off;        // vertex -> staging offset of its input terms
     std::map<size_t, uint32_t>& term_mode;    // vertex -> TERMS_* of those
-    std::map<size_t, size_t>& key_off;        // keyed compressor / gate / vocoder vertex (not dry) -> staging offset of its key terms
+    std::map<size_t, size_t>& key_off;        // keyed compressor / gate / vocoder / filter vertex that reads its key (Vertex::reads_key) -> staging offset of its key terms
     std::map<size_t, uint32_t>& key_mode;     // ... -> TERMS_* of those
     std::vector<float2*>& level_tmp;          // scratch edge buffers, given back behind the level
 
@@ -103,7 +104,7 @@ struct FxKind {
     const char* name;       // as in "<name>: chunk too long"
     int first_family;       // the kind's families are [first_family, first_family + n_families)
     int n_families;
-    size_t desc_bytes;      // of the descriptors its launches take (the compressor's two carries aside: MasterDesc)
+    size_t desc_bytes;      // of the descriptors its launches take (the compressor's and the filter's two carries aside: MasterDesc)
     bool (*fits)(const td_graph* g, const Vertex& v, size_t M);   // a chunk of M frames is within the kernels' index ranges
     int (*family)(const Vertex& v);                               // the family a vertex is lowered at; nullptr: first_family (all but the saturator)
     // the factor the guard's estimate goes through a vertex at, its own pan / gain aside (1 when dry); kNoStaticGain: none

@@ -1,5 +1,5 @@
 // compile_fx.cpp -- the effect kinds of the host compiler (compile.h FxKind / FxLevel): compressor, EQ, delay, saturator,
-// chorus, reverb, gate, phaser, vocoder.  One table row per kind -- its chunk limit, the family its launches start at, the factor the guard
+// chorus, reverb, gate, phaser, vocoder, filter.  One table row per kind -- its chunk limit, the family its launches start at, the factor the guard
 // carries an estimate through it at -- and one function per kind that lowers a level's vertices of that kind to descriptors
 // and launches.  compile_chunk enumerates the kinds through the table only.  Like compile.cpp: no HIP call.  Not an object of its
 // own: compile.cpp includes this file at its end, so no build list changes with it.
@@ -7,6 +7,7 @@
 #include "compile.h"
 #include "delay_math.h"
 #include "eq_math.h"
+#include "filter_math.h"
 #include "gate_math.h"
 #include "phaser_math.h"
 #include "reverb_math.h"
@@ -553,6 +554,114 @@ static int lower_vocoder(FxLevel& L, std::vector<size_t>& vs) {
     return 1;
 }
 
+// ---- filter: the follower's four launches, then three, or one (kernels.h FiltDesc) ----
+static int lower_filter(FxLevel& L, std::vector<size_t>& vs) {
+    td_graph* g = L.g;
+    const uint32_t n_tiles = (uint32_t)((L.M + kFiltTile - 1) / kFiltTile), chunk = (n_tiles + kThreads - 1) / kThreads;
+    const bool multi = n_tiles > 1u;   // (multi: the six launches in front of k_filt_apply)
+    // the vertices whose follower does not run first, then those that listen to themselves, the keyed ones last (a vertex with
+    // env_oct == 0 has no entry in key_off: Vertex::reads_key)
+    std::vector<size_t> ord;
+    for (size_t vi : vs)
+        if (!g->vertices[vi].filt_follows()) ord.push_back(vi);
+    const size_t n_still = ord.size();
+    for (size_t vi : vs)
+        if (g->vertices[vi].filt_follows() && !L.key_off.count(vi)) ord.push_back(vi);
+    const size_t n_plain = ord.size();
+    for (size_t vi : vs)
+        if (g->vertices[vi].filt_follows() && L.key_off.count(vi)) ord.push_back(vi);
+    const size_t n_all = ord.size(), n_env = n_all - n_still;
+    std::vector<FiltDesc> d;
+    std::vector<MasterDesc> c1, c2;
+    for (size_t i = 0; i < n_all; ++i) {
+        const size_t vi = ord[i];
+        Vertex& v = g->vertices[vi];
+        FiltDesc x{};
+        if (multi) {
+            if (!(x.x = L.tmp_buffer())) return 0;
+            if (i >= n_still && !(x.lv = reinterpret_cast<double*>(L.tmp_buffer()))) return 0;   // (an edge buffer holds one double per frame)
+        }
+        L.head(x, vi);
+        if (i >= n_plain) L.key_fields(x, vi);
+        x.state = reinterpret_cast<FiltState*>(&g->dstate[v.state_slot]);
+        // (a set_time since the vertex last ran: the state restarts from zero -- consumed here, like an EQ's)
+        x.init = v.first_pending ? nullptr : x.state;
+        v.first_pending = false;
+        x.t0 = L.t0;
+        x.n_tiles = n_tiles;
+        double c[filter::kParams];
+        filter::params(L.sr, v.filt_kind, v.filt_freq_hz, v.filt_q, v.filt_lfo_oct, v.filt_rate_hz, v.filt_stereo, v.filt_shape,
+                       v.filt_env_oct, v.filt_sens_db, v.filt_attack_ms, v.filt_release_ms, c);
+        x.kind = (uint32_t)v.filt_kind;
+        x.shape = (uint32_t)v.filt_shape;
+        x.env = i >= n_still ? 1u : 0u;
+        x.g0 = c[0]; x.kq = c[1]; x.gmin = c[2]; x.gmax = c[3]; x.cl = c[4]; x.ce = c[5]; x.f = c[6];
+        x.stereo = (double)v.filt_stereo;
+        x.S = c[7]; x.aA = c[8]; x.oA = c[9]; x.aR = c[10];
+        for (int j = 0; j < 8; ++j) {
+            const double e = (double)(1u << j);
+            x.pwR[j] = pow(x.aR, (double)kFiltRun * e);
+            x.pwA[j] = pow(x.aA, (double)kFiltRun * e);
+        }
+        d.push_back(x);
+        if (!multi || i < n_still) continue;
+        MasterDesc y1{}, ye{};
+        y1.n_tiles = ye.n_tiles = n_tiles;
+        y1.chunk = ye.chunk = chunk;
+        ye.op = 1u;
+        for (int j = 0; j < 8; ++j) {
+            const double e = (double)(1u << j);
+            y1.pwc[j] = pow(x.aR, (double)kFiltTile * (double)chunk * e);
+            ye.pwc[j] = pow(x.aA, (double)kFiltTile * (double)chunk * e);
+        }
+        y1.a_tile = pow(x.aR, (double)kFiltTile);
+        ye.a_tile = pow(x.aA, (double)kFiltTile);
+        if (x.init) {
+            y1.init = &x.state->y1;
+            ye.init = &x.state->e;
+        }
+        c1.push_back(y1);
+        c2.push_back(ye);
+    }
+    const size_t off = L.put(d, ord);
+    for (size_t i = n_plain; i < n_all; ++i) L.cb.ptr_field(off + i * sizeof(FiltDesc), offsetof(FiltDesc, key_ins), L.key_off[ord[i]]);
+    const size_t off_e = off + n_still * sizeof(FiltDesc), off_k = off + n_plain * sizeof(FiltDesc);
+    const int n_keyed = (int)(n_all - n_plain), n_self = (int)(n_plain - n_still);
+    if (!multi) {
+        if (n_plain) L.add_launch(F_FILT_APPLY, off, (int)n_plain, filt_aux(n_tiles, true, false));
+        if (n_keyed) L.add_launch(F_FILT_APPLY, off_k, n_keyed, filt_aux(n_tiles, true, true));
+        return 1;
+    }
+    const size_t o1 = n_env ? L.cb.st->put(c1) : 0, o2 = n_env ? L.cb.st->put(c2) : 0;
+    for (size_t i = 0; i < n_all; ++i) {
+        const size_t o = off + i * sizeof(FiltDesc), tb = (size_t)n_tiles * sizeof(double);
+        L.cb.scratch_field(o, offsetof(FiltDesc, agg), L.cb.scratch(12 * tb));
+        L.cb.scratch_field(o, offsetof(FiltDesc, carry), L.cb.scratch(4 * tb));
+        if (i < n_still) continue;
+        const size_t m1 = o1 + (i - n_still) * sizeof(MasterDesc), m2 = o2 + (i - n_still) * sizeof(MasterDesc);
+        const size_t a1 = L.cb.scratch(tb), k1 = L.cb.scratch(tb), a2 = L.cb.scratch(tb), k2 = L.cb.scratch(tb);
+        L.cb.scratch_field(o, offsetof(FiltDesc, agg1), a1);
+        L.cb.scratch_field(o, offsetof(FiltDesc, carry1), k1);
+        L.cb.scratch_field(o, offsetof(FiltDesc, agg2), a2);
+        L.cb.scratch_field(o, offsetof(FiltDesc, carry2), k2);
+        L.cb.scratch_field(m1, offsetof(MasterDesc, agg), a1);
+        L.cb.scratch_field(m1, offsetof(MasterDesc, carry), k1);
+        L.cb.scratch_field(m2, offsetof(MasterDesc, agg), a2);
+        L.cb.scratch_field(m2, offsetof(MasterDesc, carry), k2);
+    }
+    if (n_self) L.add_launch(F_FILT_DETECT, off_e, n_self, filt_aux(n_tiles, false, false));
+    if (n_keyed) L.add_launch(F_FILT_DETECT, off_k, n_keyed, filt_aux(n_tiles, false, true));
+    if (n_env) {
+        L.add_launch(F_FILT_CARRY1, o1, (int)n_env, 0u);
+        L.add_launch(F_FILT_ENV, off_e, (int)n_env, filt_aux(n_tiles, false, false));
+        L.add_launch(F_FILT_CARRY2, o2, (int)n_env, 0u);
+    }
+    L.add_launch(F_FILT_LOCAL, off, (int)n_all, filt_aux(n_tiles, false, false));
+    L.add_launch(F_FILT_CARRY, off, (int)n_all, 0u);
+    L.add_launch(F_FILT_APPLY, off, (int)n_all, filt_aux(n_tiles, false, false));
+    return 1;
+}
+
 // ---- the table ----
 // fits: the largest chunk the kind's kernels index (32-bit frames; the line kinds keep room for their look-back, the tiled
 // ones for the tile count packed into a launch's aux)
@@ -578,6 +687,8 @@ static double through_gate(const Vertex& v, size_t) { return dry(v) ? 1.0 : kNoS
 static double through_phaser(const Vertex& v, size_t) { return dry(v) ? 1.0 : kNoStaticGain; }
 // a vocoder's gain on its carrier is the modulator's envelope: no static gain -- like a compressor's, unless it is dry
 static double through_vocoder(const Vertex& v, size_t) { return dry(v) ? 1.0 : kNoStaticGain; }
+// a filter's resonance gain depends on the signal through e[n], and on the time: no static bound of it is proven
+static double through_filter(const Vertex& v, size_t) { return dry(v) ? 1.0 : kNoStaticGain; }
 // an EQ is linear and time-invariant: Hmax of its biquad
 static double through_eq(const Vertex& v, size_t sr) {
     if (dry(v)) return 1.0;
@@ -612,10 +723,10 @@ static double through_reverb(const Vertex& v, size_t sr) {
 // (a function's static: these sources also go through the HIP compiler, whose device pass would want a copy of a namespace-scope
 // constant -- and of the host functions it points to.)  A row's family count is the distance to the next row's first family, so
 // the rows cover the effect families of `Family` without gap or overlap as long as they stand in its order:
-constexpr int kFxKinds = 9;
+constexpr int kFxKinds = 10;
 static_assert(F_COMP_DETECT < F_EQ_LOCAL && F_EQ_LOCAL < F_DELAY_LOCAL && F_DELAY_LOCAL < F_SAT_SUM && F_SAT_SUM < F_CHORUS_SUM &&
               F_CHORUS_SUM < F_REVERB_SUM && F_REVERB_SUM < F_GATE_DETECT && F_GATE_DETECT < F_PHASER_LOCAL && F_PHASER_LOCAL < F_VOC_LOCAL &&
-              F_VOC_LOCAL < F_COUNT,
+              F_VOC_LOCAL < F_FILT_DETECT && F_FILT_DETECT < F_COUNT,
               "the rows of the effect kinds' table stand in the order of their families");
 static const FxKind* table() {
     static const FxKind rows[kFxKinds] = {
@@ -627,7 +738,8 @@ static const FxKind* table() {
         {K_REVERB, "reverb", F_REVERB_SUM, F_GATE_DETECT - F_REVERB_SUM, sizeof(ReverbDesc), fits_line, nullptr, through_reverb, lower_reverb},
         {K_GATE, "gate", F_GATE_DETECT, F_PHASER_LOCAL - F_GATE_DETECT, sizeof(GateDesc), fits_scan, nullptr, through_gate, lower_gate},
         {K_PHASER, "phaser", F_PHASER_LOCAL, F_VOC_LOCAL - F_PHASER_LOCAL, sizeof(PhaserDesc), fits_scan, nullptr, through_phaser, lower_phaser},
-        {K_VOCODER, "vocoder", F_VOC_LOCAL, F_COUNT - F_VOC_LOCAL, sizeof(VocDesc), fits_voc, nullptr, through_vocoder, lower_vocoder},
+        {K_VOCODER, "vocoder", F_VOC_LOCAL, F_FILT_DETECT - F_VOC_LOCAL, sizeof(VocDesc), fits_voc, nullptr, through_vocoder, lower_vocoder},
+        {K_FILTER, "filter", F_FILT_DETECT, F_COUNT - F_FILT_DETECT, sizeof(FiltDesc), fits_scan, nullptr, through_filter, lower_filter},
     };
     return rows;
 }

@@ -13,6 +13,7 @@
 #include "gate_math.h"
 #include "phaser_math.h"
 #include "vocoder_math.h"
+#include "filter_math.h"
 #include "comm.h"
 #include "compile.h"
 #include "delay_math.h"
@@ -546,6 +547,10 @@ static tdk::GateState gate_closed(const td_graph* g, const Vertex& v) {
 static void phaser_rest(td_graph* g, const Vertex& v) {
     memset(&g->hstate[(size_t)v.state_slot], 0, sizeof(tdk::PhaserState));
 }
+// A filter vertex' state at time 0: (y1, e, i1l, i2l, i1r, i2r) = 0 -- its run of slots, all zero
+static void filt_rest(td_graph* g, const Vertex& v) {
+    memset(&g->hstate[(size_t)v.state_slot], 0, sizeof(tdk::FiltState));
+}
 static int drain(td_graph* g);   // stream drained + deferred k_norm_fix settled (defined with the render loop)
 static int pull_state(td_graph* g) {
     if (g->state_dev_dirty && g->dstate && !g->hstate.empty()) {
@@ -562,6 +567,8 @@ static int pull_state(td_graph* g) {
             if (v.kind == K_GATE && v.state_slot >= 0 && v.first_pending) g->hstate[(size_t)v.state_slot].gate = gate_closed(g, v);
         for (const auto& v : g->vertices)
             if (v.kind == K_PHASER && v.state_slot >= 0 && v.first_pending) phaser_rest(g, v);
+        for (const auto& v : g->vertices)
+            if (v.kind == K_FILTER && v.state_slot >= 0 && v.first_pending) filt_rest(g, v);
     }
     return 1;
 }
@@ -985,6 +992,13 @@ static int submit_chunk(Arena& ar, ChunkBuild& cb, hipStream_t stream, ProfCtx& 
                     if (L.aux & kKeyedBit) launch_voc_apply_keyed((const VocDesc*)d, L.n, voc_aux_bands(L.aux), voc_aux_tiles(L.aux), s);
                     else launch_voc_apply((const VocDesc*)d, L.n, voc_aux_bands(L.aux), voc_aux_tiles(L.aux), (L.aux & kVocSingleBit) != 0u, s);
                     break;
+                case F_FILT_DETECT: launch_filt_detect((const FiltDesc*)d, L.n, filt_aux_tiles(L.aux), (L.aux & kKeyedBit) != 0u, s); break;   // (likewise)
+                case F_FILT_CARRY1:
+                case F_FILT_CARRY2: launch_master_carry((const MasterDesc*)d, L.n, s); break;
+                case F_FILT_ENV: launch_filt_env((const FiltDesc*)d, L.n, filt_aux_tiles(L.aux), s); break;
+                case F_FILT_LOCAL: launch_filt_local((const FiltDesc*)d, L.n, filt_aux_tiles(L.aux), s); break;
+                case F_FILT_CARRY: launch_filt_carry((const FiltDesc*)d, L.n, s); break;
+                case F_FILT_APPLY: launch_filt_apply((const FiltDesc*)d, L.n, filt_aux_tiles(L.aux), (L.aux & kFiltSingleBit) != 0u, (L.aux & kKeyedBit) != 0u, s); break;
                 case F_CHORUS: launch_chorus((const ChorusDesc*)d, L.n, L.aux & 0xFFFFFu, L.M, (L.aux & kChorusTermsBit) != 0u, s); break;
             }
         }
@@ -1078,6 +1092,7 @@ static int prepare_render(td_graph* g, size_t n_blocks, int bits, bool want_pcm,
         {K_GATE, launch_gate_detect && launch_gate_carry && launch_gate_env && launch_gate_apply, "gate", "gate"},
         {K_PHASER, launch_phaser_local && launch_phaser_carry && launch_phaser_apply, "phaser", "phaser"},
         {K_VOCODER, launch_voc_local && launch_voc_carry && launch_voc_env && launch_voc_apply, "voc", "vocoder"},
+        {K_FILTER, launch_filt_detect && launch_filt_env && launch_filt_local && launch_filt_carry && launch_filt_apply && launch_master_carry, "filt", "filter"},
     };
     for (const auto& f : fx)
         if (!f.built)
@@ -1087,6 +1102,7 @@ static int prepare_render(td_graph* g, size_t n_blocks, int bits, bool want_pcm,
     for (size_t vi : g->order) {   // ... and the keyed forms, where a key edge asks for them (td_graph_connect_key)
         const Vertex& v = g->vertices[vi];
         if (g->key_edges[vi].empty() || v.wet < 0.0001f) continue;
+        if (v.kind == K_FILTER) continue;   // (its keyed forms are instantiations behind the entry points checked above)
         if (v.kind == K_VOCODER) {
             if (!(launch_voc_local_keyed && launch_voc_apply_keyed))
                 return fail("termdaw_amd: this build has no keyed vocoder kernels: a vertex with a key edge cannot be rendered");
@@ -1197,7 +1213,7 @@ static bool starts_afresh(const td_graph* g) {
     for (size_t vi : g->order) {
         const Vertex& v = g->vertices[vi];
         if (v.kind == K_NORMALIZE && !v.has_init_override) return false;
-        if ((v.kind == K_BAND_PASS || v.kind == K_COMPRESSOR || v.kind == K_EQ || v.kind == K_GATE || v.kind == K_PHASER) && v.state_slot >= 0 && !v.first_pending) return false;
+        if ((v.kind == K_BAND_PASS || v.kind == K_COMPRESSOR || v.kind == K_EQ || v.kind == K_GATE || v.kind == K_PHASER || v.kind == K_FILTER) && v.state_slot >= 0 && !v.first_pending) return false;
         if (v.line.d && !v.first_pending) return false;
     }
     return true;
@@ -1428,6 +1444,12 @@ static int graph_set_time_impl(td_graph* g, size_t time) {   // graph.rs:123-128
             case K_PHASER:   // the chain restarts from the zero state (the LFO does not: it runs on the graph's time)
                 if (v.state_slot >= 0) {
                     phaser_rest(g, v);
+                    v.first_pending = true;
+                }
+                break;
+            case K_FILTER:   // the follower and the filter restart from the zero state (the LFO does not: it runs on the graph's time)
+                if (v.state_slot >= 0) {
+                    filt_rest(g, v);
                     v.first_pending = true;
                 }
                 break;
@@ -2145,6 +2167,38 @@ int td_vocoder_params(size_t sr, int bands, float lo_hz, float hi_hz, float q, f
     return 1;
 }
 
+// This engine's own filter vertex (no reference counterpart; the definition is in include/termdaw_amd.h).
+int td_graph_add_filter(td_graph* g, const char* name, float gain, float angle, float wet, int kind, float freq_hz, float q,
+                        float lfo_oct, float rate_hz, float stereo, int shape, float env_oct, float sens_db, float attack_ms, float release_ms) {
+    if (const char* why = filter::check(g->sr, kind, freq_hz, q, lfo_oct, rate_hz, stereo, shape, env_oct, sens_db, attack_ms, release_ms))
+        return fail(std::string("filter: ") + why);
+    const int slot = new_slot(g);   // (a run of zeroed slots: tdk::FiltState)
+    for (int i = 1; i < kFiltSlots; ++i) new_slot(g);
+    Vertex& v = add_vertex(g, name, gain, angle, wet, K_FILTER);
+    v.filt_kind = kind;
+    v.filt_shape = shape;
+    v.filt_freq_hz = freq_hz;
+    v.filt_q = q;
+    v.filt_lfo_oct = lfo_oct;
+    v.filt_rate_hz = rate_hz;
+    v.filt_stereo = stereo;
+    v.filt_env_oct = env_oct;
+    v.filt_sens_db = sens_db;
+    v.filt_attack_ms = attack_ms;
+    v.filt_release_ms = release_ms;
+    v.state_slot = slot;
+    return 1;
+}
+int td_filter_params(size_t sr, int kind, float freq_hz, float q, float lfo_oct, float rate_hz, float stereo, int shape, float env_oct,
+                     float sens_db, float attack_ms, float release_ms, double* out, size_t cap) {
+    if (!out) return fail("filter_params: out is null");
+    if (const char* why = filter::check(sr, kind, freq_hz, q, lfo_oct, rate_hz, stereo, shape, env_oct, sens_db, attack_ms, release_ms))
+        return fail(std::string("filter: ") + why);
+    if (cap < (size_t)filter::kParams) return fail("filter_params: out holds fewer than 11 doubles");
+    filter::params(sr, kind, freq_hz, q, lfo_oct, rate_hz, stereo, shape, env_oct, sens_db, attack_ms, release_ms, out);
+    return 1;
+}
+
 static bool has_loop(size_t x, size_t b, const td_graph* g) {   // graph.rs:66-72
     if (x == b) return true;
     for (size_t y : g->edges[x])
@@ -2172,7 +2226,7 @@ int td_graph_connect_key(td_graph* g, const char* a, const char* b) {
     if (ia == g->name_map.end()) return fail(std::string("TermDaw: warning: vertex \"") + a + "\" cannot be found and thus can't be connected.");
     if (ib == g->name_map.end()) return fail(std::string("TermDaw: warning: vertex \"") + b + "\" cannot be found and thus can't be connected to.");
     const size_t ai = ia->second, bi = ib->second;
-    if (g->vertices[bi].kind != K_COMPRESSOR && g->vertices[bi].kind != K_GATE && g->vertices[bi].kind != K_VOCODER) return fail(std::string("connect_key: ") + b + " takes no key input");
+    if (g->vertices[bi].kind != K_COMPRESSOR && g->vertices[bi].kind != K_GATE && g->vertices[bi].kind != K_VOCODER && g->vertices[bi].kind != K_FILTER) return fail(std::string("connect_key: ") + b + " takes no key input");
     if (ai == bi) return fail("connect_key: self edge");
     if (has_loop(ai, bi, g)) return fail("connect_key: edge would close a loop");
     g->key_edges[bi].push_back(ai);

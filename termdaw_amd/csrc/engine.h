@@ -76,7 +76,7 @@ struct td_flowwbank {
 namespace tde {
 
 enum Kind { K_SUM, K_NORMALIZE, K_SAMPLE_LOOP, K_SAMPLE_MULTI, K_SAMPLE_LERP, K_DEBUG_SINE, K_SYNTH,
-            K_SAMPSYN, K_ADSR, K_BAND_PASS, K_COMPRESSOR, K_EQ, K_DELAY, K_SATURATOR, K_CHORUS, K_REVERB, K_GATE, K_PHASER, K_VOCODER, K_COUNT };
+            K_SAMPSYN, K_ADSR, K_BAND_PASS, K_COMPRESSOR, K_EQ, K_DELAY, K_SATURATOR, K_CHORUS, K_REVERB, K_GATE, K_PHASER, K_VOCODER, K_FILTER, K_COUNT };
 
 struct SineNote { float note, vel; };
 struct SynthNote { float note, vel, env_t, rel_t, hz; };   // hz = 440 * 2^((note - 69) / 12), extensions.rs:503
@@ -141,6 +141,13 @@ struct Vertex {
     float phaser_lo_hz = 20, phaser_hi_hz = 20, phaser_rate_hz = 1, phaser_feedback = 0, phaser_stereo = 0;
     int voc_bands = 4;   // K_VOCODER: B
     float voc_lo_hz = 40, voc_hi_hz = 80, voc_q = 1, voc_response_ms = 10, voc_out_db = 0;
+    int filt_kind = 0, filt_shape = 0;   // K_FILTER: TD_FILTER_*, TD_CHORUS_*
+    float filt_freq_hz = 1000, filt_q = 1, filt_lfo_oct = 0, filt_rate_hz = 1, filt_stereo = 0;
+    float filt_env_oct = 0, filt_sens_db = 0, filt_attack_ms = 0, filt_release_ms = 1;
+    // a filter vertex whose follower runs: env_oct != 0 (otherwise y1, e stay as they are and key edges are ignored)
+    bool filt_follows() const { return filt_env_oct != 0.0f; }
+    // a vertex with key edges reads them: it is not dry, and a filter's follower runs
+    bool reads_key() const { return !(wet < 0.0001f) && (kind != K_FILTER || filt_follows()); }
     // The block of device memory a delay, saturator, chorus, reverb or vocoder vertex carries from chunk to chunk: allocated when the vertex
     // is first compiled into a submission (take_line), never cleared, freed with the graph's vertices.
     //   K_DELAY             the last D values of (ul, ur), 16 D bytes: the rotation is total mod D, the words below min(total, D) hold values
@@ -165,10 +172,10 @@ struct Vertex {
     std::vector<SynthNote> notes;
     Voice3 ap{0, 0, 0}, ag{0, 0, 0};
     // carried device state slot (Normalize / BandPass / Compressor / Eq / Gate; a phaser: the first of kPhaserSlots consecutive
-    // ones, a tdk::PhaserState), index into Graph::dstate
+    // ones, a tdk::PhaserState; a filter: the first of kFiltSlots, a tdk::FiltState), index into Graph::dstate
     int state_slot = -1;
     // reset_normalization (extensions.rs:295-299) is kept on the host until the next render consumes it
-    bool first_pending = false;         // band-pass, compressor, eq, gate, phaser, delay, saturator, chorus, reverb, vocoder (their state then restarts from zero): set_time since the vertex was last compiled into a submission (its descriptor's first_override)
+    bool first_pending = false;         // band-pass, compressor, eq, gate, phaser, filter, delay, saturator, chorus, reverb, vocoder (their state then restarts from zero): set_time since the vertex was last compiled into a submission (its descriptor's first_override)
     bool has_init_override = false;
     float init_override = 0.0f;
     // Normalize: the carried max is the result of a normalize scan (graph.rs:222-237), so a render is expected to
@@ -192,6 +199,9 @@ static_assert(sizeof(StateSlot) == 32, "carried vertex state: one 32-byte slot")
 // a phaser vertex' 2 x (N + 1) doubles take a run of slots
 constexpr int kPhaserSlots = (int)(sizeof(tdk::PhaserState) / sizeof(StateSlot));
 static_assert(sizeof(tdk::PhaserState) == kPhaserSlots * sizeof(StateSlot), "a phaser vertex' state: whole slots");
+// ... and a filter vertex' six doubles
+constexpr int kFiltSlots = (int)(sizeof(tdk::FiltState) / sizeof(StateSlot));
+static_assert(sizeof(tdk::FiltState) == kFiltSlots * sizeof(StateSlot), "a filter vertex' state: whole slots");
 
 struct KernelTime { std::string name; float ms = 0; size_t launches = 0; };
 

@@ -413,6 +413,62 @@ struct VocDesc {
     uint32_t key_k, key_term_mode;
 };
 
+// A filter vertex (k_filt_detect<KEYED> / k_filt_env / k_filt_local / k_filt_carry / k_filt_apply<SINGLE, KEYED> with
+// k_master_carry behind the first two; the definition is in include/termdaw_amd.h at td_graph_add_filter): a
+// trapezoidal state-variable filter per channel, f64, whose coefficient g[n] follows the chorus' LFO on the graph's ABSOLUTE frame
+// time and a linear-domain level follower e[n] of the key (or the input).  Two stages:
+//   the follower -- the compressor's pair of scalar scans, y1 = max(s, aR y1) and e = aA e + (1 - aA) y1, in the compressor's
+//   tiling: k_filt_detect evaluates the input terms into `x` (KEYED: and the key terms), leaves s[n] (f64) in `lv` and each tile's
+//   zero-start end value of y1 in agg1[]; k_master_carry (op 0) the y1 entering each tile in carry1[]; k_filt_env rebuilds y1,
+//   overwrites lv with it and leaves each tile's zero-start end value of e in agg2[]; k_master_carry (op 1) the e entering each tile
+//   in carry2[].  With `env` 0 (env_oct == 0) none of the four runs and y1, e stay as they are.
+//   the filter -- one frame is the affine map z -> M[n] z + b[n] xs[n] on z = (i1, i2), M and b from g[n]: the phaser's blocked
+//   scan at D = 2, with both channels' maps in a lane's registers.  A map is stored augmented and row-major, {p00, p01, q0, p10,
+//   p11, q1}: z_out = P z_in + q.  k_filt_local rebuilds e (env: overwriting lv with it; otherwise it evaluates the input terms into
+//   `x` itself) and leaves each tile's total map, per channel, in agg[(2 t + c) 6 ..]; k_filt_carry leaves the state entering each
+//   tile in carry[4 t ..] = (i1l, i2l, i1r, i2r) (tile 0: *init, or 0 when init is null); k_filt_apply rebuilds the lanes' maps
+//   from x and lv (g[n] is recomputed, not stored), their in-tile prefix, each lane's entry state, and runs the definition serially.
+// Tiles of kFiltTile frames, a lane owns kFiltRun consecutive frames.  When one tile covers the chunk (every block pull)
+// k_filt_apply runs alone (kFiltSingleBit): term loops, follower and filter inside, entered with the carried state (x, lv and all
+// of agg1 .. carry unused).  The lane that owns the chunk's last frame stores y1 (k_filt_env), e (k_filt_local) and the four
+// filter words (k_filt_apply) into the carried state.
+constexpr uint32_t kFiltRun = 8;                     // frames per lane
+constexpr uint32_t kFiltTile = kFiltRun * kThreads;  // frames per workgroup
+struct FiltState { double y1, e, z[2][2]; double pad[2]; };   // z[c] = (i1, i2) of channel c; two 32-byte slots
+struct FiltDesc {
+    const InTerm* ins;      // k input terms (kinds 0 .. 4), in connect() order
+    float2* x;              // [frames] the summed input (multi-tile form)
+    double* lv;             // [frames] s, then y1, then e (multi-tile form with env)
+    float2* out;
+    FiltState* state;       // carried across chunks / block pulls
+    const FiltState* init;  // the state entering tile 0: `state`, or nullptr after a set_time
+    double* agg1;           // [n_tiles] each of the four (env)
+    double* carry1;
+    double* agg2;
+    double* carry2;
+    double* agg;            // [12 n_tiles] each tile's total map, per channel
+    double* carry;          // [4 n_tiles] the filter state entering each tile
+    uint64_t t0;            // the graph's absolute frame time at the chunk's first frame (the LFO's n)
+    uint32_t k, term_mode, frames, n_tiles;
+    uint32_t kind;          // TD_FILTER_*
+    uint32_t shape;         // TD_CHORUS_*
+    uint32_t env;           // 1: the follower runs (env_oct != 0)
+    float wet;
+    double g0, kq;          // tan(pi freq / sr), 1 / q
+    double gmin, gmax;
+    double cl, ce;          // ln2 lfo_oct, ln2 env_oct
+    double f;               // LFO cycles per frame
+    double stereo;          // the right channel's phase offset in cycles
+    double S;               // the follower's sensitivity, linear
+    double aR, aA, oA;      // release / attack coefficients, 1 - aA
+    double pwR[8], pwA[8];  // aR^(kFiltRun 2^k), aA^(kFiltRun 2^k)
+    PanGain pg;
+    // a keyed vertex (td_graph_connect_key; null / 0 without key edges, and with env 0): key_k key terms (kinds 0 .. 4), in
+    // connect_key() order -- the level s[n] is taken from their sum
+    const InTerm* key_ins;
+    uint32_t key_k, key_term_mode;
+};
+
 // A parametric EQ vertex (k_eq_local / k_eq_carry / k_eq_apply; the definition is in include/termdaw_amd.h at
 // td_graph_add_eq): one RBJ biquad per channel in transposed direct form II, f64.  With z = (s1, s2) the recurrence is
 // z[n] = A z[n-1] + c x[n],  A = [[-a1, 1], [-a2, 0]],  c = (b1 - a1 b0, b2 - a2 b0),  y[n] = b0 x[n] + s1[n-1]: an affine scan
@@ -1087,6 +1143,18 @@ __attribute__((weak)) void launch_voc_env(const VocDesc* d, int n_desc, uint32_t
 __attribute__((weak)) void launch_voc_apply(const VocDesc* d, int n_desc, uint32_t bands, uint32_t n_tiles, bool single, hipStream_t s);
 // (single and keyed: the one-launch form of a keyed vertex, with both term loops inside)
 __attribute__((weak)) void launch_voc_apply_keyed(const VocDesc* d, int n_desc, uint32_t bands, uint32_t n_tiles, hipStream_t s);
+// Weak for the same reason: a level's filter vertices, grid.x = n_tiles (every descriptor's; the carry: one workgroup per vertex).
+// A launch's aux packs the tile count, for F_FILT_APPLY `single` (the one-launch form, entered with the carried state), and
+// kKeyedBit where the descriptors are keyed (F_FILT_DETECT, and F_FILT_APPLY when single).  The follower's two carries are
+// launch_master_carry's, over MasterDesc.
+constexpr uint32_t kFiltSingleBit = 0x40000000u;
+inline uint32_t filt_aux(uint32_t n_tiles, bool single, bool keyed) { return n_tiles | (single ? kFiltSingleBit : 0u) | (keyed ? kKeyedBit : 0u); }
+inline uint32_t filt_aux_tiles(uint32_t aux) { return aux & 0xFFFFFFu; }
+__attribute__((weak)) void launch_filt_detect(const FiltDesc* d, int n_desc, uint32_t n_tiles, bool keyed, hipStream_t s);
+__attribute__((weak)) void launch_filt_env(const FiltDesc* d, int n_desc, uint32_t n_tiles, hipStream_t s);
+__attribute__((weak)) void launch_filt_local(const FiltDesc* d, int n_desc, uint32_t n_tiles, hipStream_t s);
+__attribute__((weak)) void launch_filt_carry(const FiltDesc* d, int n_desc, hipStream_t s);
+__attribute__((weak)) void launch_filt_apply(const FiltDesc* d, int n_desc, uint32_t n_tiles, bool single, bool keyed, hipStream_t s);
 // Weak for the same reason: a level's reverb vertices.  launch_reverb_sum: grid.x from `frames`; launch_reverb: one workgroup per
 // descriptor, `form` 0 the serial walk of each comb's one-pole, 1 the wave scan.
 __attribute__((weak)) void launch_reverb_sum(const ReverbDesc* d, int n_desc, uint32_t frames, hipStream_t s);

@@ -6954,6 +6954,370 @@ __global__ __launch_bounds__(kThreads) void k_voc_apply(const VocDesc* __restric
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// k_filt_detect / k_filt_env / k_filt_local / k_filt_carry / k_filt_apply: the filter vertex (kernels.h FiltDesc).
+// No reference counterpart; the definition is the header's (td_graph_add_filter): a level follower in the linear domain (the
+// compressor's two scans), the chorus' LFO, an exponential sweep of the prewarped coefficient g[n] through a fixed polynomial,
+// and the trapezoidal state-variable filter, f64.  One frame of the filter is an affine map on (i1, i2) whose matrix depends on
+// g[n]: the phaser's blocked scan at D = 2.  A lane holds both channels' maps {p00, p01, q0, p10, p11, q1} in registers; word e
+// of lane t lies at pm[e kThreads + t].
+// ------------------------------------------------------------------------------------------------
+// E(t) of the header (filter_math.h filter::E restates it for the host): IEEE multiplies and adds only
+TD_DEV double filt_exp(double t) {
+    const double x = t * 0.0625;
+    double p = 1.0;
+    p = 1.0 + p * (x * (1.0 / 10.0));
+    p = 1.0 + p * (x * (1.0 / 9.0));
+    p = 1.0 + p * (x * (1.0 / 8.0));
+    p = 1.0 + p * (x * (1.0 / 7.0));
+    p = 1.0 + p * (x * (1.0 / 6.0));
+    p = 1.0 + p * (x * (1.0 / 5.0));
+    p = 1.0 + p * (x * (1.0 / 4.0));
+    p = 1.0 + p * (x * (1.0 / 3.0));
+    p = 1.0 + p * (x * (1.0 / 2.0));
+    p = 1.0 + p * (x * 1.0);
+    p = p * p;
+    p = p * p;
+    p = p * p;
+    p = p * p;
+    return p;
+}
+// steps 2 and 3: g[n] of channel ch at the absolute frame n, with the follower at e; then a1, a2, a3 of step 4
+TD_DEV void filt_coef(const FiltDesc& d, uint64_t n, uint32_t ch, double e, double& a1, double& a2, double& a3) {
+    double th = (double)n * d.f + (ch ? d.stereo : 0.0);
+    th = th - floor(th);
+    const double t = d.cl * chorus_lfo(d.shape, th) + d.ce * fmin(d.S * e, 1.0);
+    const double g = fmin(fmax(d.g0 * filt_exp(t), d.gmin), d.gmax);
+    a1 = 1.0 / (1.0 + g * (g + d.kq));
+    a2 = g * a1;
+    a3 = g * a2;
+}
+// step 4, one frame of one channel's state
+TD_DEV void filt_frame(double& i1, double& i2, double a1, double a2, double a3, double xs, double& v1, double& v2) {
+    const double v3 = xs - i2;
+    v1 = a1 * i1 + a2 * v3;
+    v2 = (i2 + a2 * i1) + a3 * v3;
+    i1 = 2.0 * v1 - i1;
+    i2 = 2.0 * v2 - i2;
+}
+// step 1's s[n]: a key frame with a NaN or an infinity stays out
+TD_DEV double filt_level(float l, float r) {
+    const float al = fabsf(l), ar = fabsf(r);
+    if (!(al <= 3.402823466e38f && ar <= 3.402823466e38f)) return 0.0;
+    return (double)fmaxf(al, ar);
+}
+// the lane's kFiltRun values of p (0 from `frames` on)
+TD_DEV void filt_load_run(const double* p, uint32_t M, uint32_t f0, double (&y)[kFiltRun]) {
+#pragma unroll
+    for (uint32_t j = 0; j < kFiltRun / 2; ++j) {
+        const uint32_t m = f0 + 2u * j;
+        d2v v;
+        v.x = 0.0; v.y = 0.0;
+        if (m < M) v = gload_d2(p + m);
+        y[2 * j] = v.x;
+        y[2 * j + 1] = m + 1u < M ? v.y : 0.0;
+    }
+}
+TD_DEV void filt_store_run(double* p, uint32_t M, uint32_t f0, const double (&y)[kFiltRun]) {
+#pragma unroll
+    for (uint32_t j = 0; j < kFiltRun / 2; ++j)
+        if (f0 + 2u * j < M) gstore_d2(p + f0 + 2u * j, y[2 * j], y[2 * j + 1]);
+}
+// the lane's kFiltRun frames of the summed input terms (0 from `frames` on)
+TD_DEV void filt_sum_run(const InTerm* ins, uint32_t k, uint32_t term_mode, uint32_t M, uint32_t f0, float2 (&x)[kFiltRun]) {
+#pragma unroll
+    for (uint32_t h = 0; h < kFiltRun / 4; ++h) {
+        float4 a0, a1;
+        sum_inputs_pairs(ins, k, term_mode, f0 + 4u * h, f0 + 4u * h + 2u, M, a0, a1);
+        x[4 * h] = make_float2(a0.x, a0.y);
+        x[4 * h + 1] = make_float2(a0.z, a0.w);
+        x[4 * h + 2] = make_float2(a1.x, a1.y);
+        x[4 * h + 3] = make_float2(a1.z, a1.w);
+    }
+}
+TD_DEV void filt_load_x(const float2* p, uint32_t M, uint32_t f0, float2 (&x)[kFiltRun]) {
+#pragma unroll
+    for (uint32_t j = 0; j < kFiltRun / 2; ++j) {
+        const float4 a = load_pair(p, f0 + 2u * j, M);
+        x[2 * j] = make_float2(a.x, a.y);
+        x[2 * j + 1] = make_float2(a.z, a.w);
+    }
+}
+TD_DEV void filt_store_x(float2* p, uint32_t M, uint32_t f0, const float2 (&x)[kFiltRun]) {
+#pragma unroll
+    for (uint32_t j = 0; j < kFiltRun / 2; ++j) store_pair(p, f0 + 2u * j, M, make_float4(x[2 * j].x, x[2 * j].y, x[2 * j + 1].x, x[2 * j + 1].y));
+}
+// The maps of the lane's run, both channels: the identity pushed through kFiltRun frames, every column through the definition,
+// the basis columns with xs = 0 (frames from `frames` on hold x = 0)
+TD_DEV void filt_lane_maps(const FiltDesc& d, uint32_t f0, const float2 (&x)[kFiltRun], const double (&e)[kFiltRun], double (&P)[2][6]) {
+#pragma unroll
+    for (uint32_t ch = 0; ch < 2; ++ch) {
+        P[ch][0] = 1.0; P[ch][1] = 0.0; P[ch][2] = 0.0;
+        P[ch][3] = 0.0; P[ch][4] = 1.0; P[ch][5] = 0.0;
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < kFiltRun; ++j) {   // (unrolled: x and e stay in registers)
+#pragma unroll
+        for (uint32_t ch = 0; ch < 2; ++ch) {
+            double a1, a2, a3, v1, v2;
+            filt_coef(d, d.t0 + (uint64_t)(f0 + j), ch, e[j], a1, a2, a3);
+            const double xs = eq_in(ch ? x[j].y : x[j].x);
+            filt_frame(P[ch][0], P[ch][3], a1, a2, a3, 0.0, v1, v2);
+            filt_frame(P[ch][1], P[ch][4], a1, a2, a3, 0.0, v1, v2);
+            filt_frame(P[ch][2], P[ch][5], a1, a2, a3, xs, v1, v2);
+        }
+    }
+}
+// The lanes' maps joined in lane order, Hillis-Steele: behind it P holds the map of lanes 0 .. t, and so do the lane's words of pm.
+// A join is own o left: {P PL | P qL + q}.
+TD_DEV void filt_lane_scan(double (&P)[2][6], double* pm) {
+    const uint32_t tid = threadIdx.x;
+#pragma unroll 1
+    for (uint32_t off = 1; off < (uint32_t)kThreads; off <<= 1) {
+#pragma unroll
+        for (uint32_t e = 0; e < 12; ++e) pm[e * kThreads + tid] = P[e / 6][e % 6];
+        __syncthreads();
+        double L[2][6];
+        const bool act = tid >= off;
+#pragma unroll
+        for (uint32_t e = 0; e < 12; ++e) L[e / 6][e % 6] = act ? pm[e * kThreads + tid - off] : 0.0;
+        __syncthreads();
+        if (act) {
+#pragma unroll
+            for (uint32_t ch = 0; ch < 2; ++ch) {
+                double N[6];
+#pragma unroll
+                for (uint32_t i = 0; i < 2; ++i) {
+                    const double pa = P[ch][3 * i], pb = P[ch][3 * i + 1];
+                    N[3 * i] = pa * L[ch][0] + pb * L[ch][3];
+                    N[3 * i + 1] = pa * L[ch][1] + pb * L[ch][4];
+                    N[3 * i + 2] = (pa * L[ch][2] + pb * L[ch][5]) + P[ch][3 * i + 2];
+                }
+#pragma unroll
+                for (uint32_t i = 0; i < 6; ++i) P[ch][i] = N[i];
+            }
+        }
+    }
+#pragma unroll
+    for (uint32_t e = 0; e < 12; ++e) pm[e * kThreads + tid] = P[e / 6][e % 6];
+    __syncthreads();
+}
+// the value at the chunk's last frame, from the lane that owns it: what the next chunk / block pull enters with
+TD_DEV void filt_keep(double* p, const double (&y)[kFiltRun], uint32_t M, uint32_t f0) {
+#pragma unroll
+    for (uint32_t k = 0; k < kFiltRun; ++k)
+        if (f0 + k + 1u == M) gstored(p, y[k]);
+}
+// the release: the lane's run of s from u (lane 0: the entering y1), joined; then y1 per frame, in place
+TD_DEV void filt_release(const FiltDesc& d, double (&y)[kFiltRun], double cin, double* sv) {
+    const double aR = d.aR;
+    double u = threadIdx.x ? 0.0 : cin, last;
+#pragma unroll
+    for (uint32_t k = 0; k < kFiltRun; ++k) u = fmax(y[k], aR * u);
+    u = comp_lane_scan<false>(u, d.pwR, cin, sv, &last);
+#pragma unroll
+    for (uint32_t k = 0; k < kFiltRun; ++k) {
+        u = fmax(y[k], aR * u);
+        y[k] = u;
+    }
+}
+// the attack: e per frame from y1, in place, entered with cin
+TD_DEV void filt_attack(const FiltDesc& d, double (&y)[kFiltRun], double cin, double* sv) {
+    const double aA = d.aA, oA = d.oA;
+    double b = threadIdx.x ? 0.0 : cin, last;
+#pragma unroll
+    for (uint32_t k = 0; k < kFiltRun; ++k) b = aA * b + oA * y[k];
+    double e = comp_lane_scan<true>(b, d.pwA, cin, sv, &last);
+#pragma unroll
+    for (uint32_t k = 0; k < kFiltRun; ++k) {
+        e = aA * e + oA * y[k];
+        y[k] = e;
+    }
+}
+// KEYED: the level is taken from the sum of the key terms; `x` holds the summed INPUT either way
+template <bool KEYED>
+__global__ __launch_bounds__(kThreads) void k_filt_detect(const FiltDesc* __restrict__ descs) {
+    const FiltDesc& d = descs[blockIdx.y];
+    if (blockIdx.x >= d.n_tiles) return;
+    __shared__ double sv[kThreads];
+    const uint32_t M = d.frames, f0 = blockIdx.x * kFiltTile + threadIdx.x * kFiltRun;
+    float2 x[kFiltRun];
+    filt_sum_run(d.ins, d.k, d.term_mode, M, f0, x);
+    filt_store_x(d.x, M, f0, x);
+    if (KEYED) filt_sum_run(d.key_ins, d.key_k, d.key_term_mode, M, f0, x);   // (kl, kr): what the level reads
+    double y[kFiltRun], last;
+#pragma unroll
+    for (uint32_t k = 0; k < kFiltRun; ++k) y[k] = filt_level(x[k].x, x[k].y);
+    filt_store_run(d.lv, M, f0, y);
+    const double aR = d.aR;
+    double u = 0.0;
+#pragma unroll
+    for (uint32_t k = 0; k < kFiltRun; ++k) u = fmax(y[k], aR * u);
+    (void)comp_lane_scan<false>(u, d.pwR, 0.0, sv, &last);
+    if (threadIdx.x == 0) d.agg1[blockIdx.x] = last;
+}
+__global__ __launch_bounds__(kThreads) void k_filt_env(const FiltDesc* __restrict__ descs) {
+    const FiltDesc& d = descs[blockIdx.y];
+    if (blockIdx.x >= d.n_tiles) return;
+    __shared__ double sv[kThreads];
+    const uint32_t tid = threadIdx.x, M = d.frames, f0 = blockIdx.x * kFiltTile + tid * kFiltRun;
+    const double aA = d.aA, oA = d.oA;
+    double y[kFiltRun], last;
+    filt_load_run(d.lv, M, f0, y);
+    filt_release(d, y, d.carry1[blockIdx.x], sv);
+    filt_keep(&d.state->y1, y, M, f0);
+    filt_store_run(d.lv, M, f0, y);
+    double b = 0.0;
+#pragma unroll
+    for (uint32_t k = 0; k < kFiltRun; ++k) b = aA * b + oA * y[k];
+    (void)comp_lane_scan<true>(b, d.pwA, 0.0, sv, &last);
+    if (tid == 0) d.agg2[blockIdx.x] = last;
+}
+__global__ __launch_bounds__(kThreads) void k_filt_local(const FiltDesc* __restrict__ descs) {
+    const FiltDesc& d = descs[blockIdx.y];
+    if (blockIdx.x >= d.n_tiles) return;
+    __shared__ double pm[12 * kThreads];
+    __shared__ double sv[kThreads];
+    const uint32_t tid = threadIdx.x, M = d.frames, f0 = blockIdx.x * kFiltTile + tid * kFiltRun;
+    float2 x[kFiltRun];
+    double e[kFiltRun];
+    if (d.env) {
+        filt_load_x(d.x, M, f0, x);
+        filt_load_run(d.lv, M, f0, e);
+        filt_attack(d, e, d.carry2[blockIdx.x], sv);
+        filt_keep(&d.state->e, e, M, f0);
+        filt_store_run(d.lv, M, f0, e);
+    } else {   // (no follower in front: the term loop runs here)
+        filt_sum_run(d.ins, d.k, d.term_mode, M, f0, x);
+        filt_store_x(d.x, M, f0, x);
+#pragma unroll
+        for (uint32_t k = 0; k < kFiltRun; ++k) e[k] = 0.0;
+    }
+    double P[2][6];
+    filt_lane_maps(d, f0, x, e, P);
+    filt_lane_scan(P, pm);
+    // the last lane's words are the tile's
+    if (tid < 12u) gstored(d.agg + (size_t)blockIdx.x * 12u + tid, pm[tid * kThreads + kThreads - 1u]);
+}
+// entry[t + 1] = P[t] entry[t] + q[t], entry[0] = *init: the tiles in series, a 2x2 matrix-vector product per channel each.  One
+// wave per vertex: the lanes stage 64 tiles' maps in LDS together, lane c walks channel c through them.
+__global__ __launch_bounds__(64) void k_filt_carry(const FiltDesc* __restrict__ descs) {
+    const FiltDesc& d = descs[blockIdx.x];
+    __shared__ double sm[64 * 12];
+    const uint32_t tid = threadIdx.x, n = d.n_tiles, ch = tid & 1u;
+    double s0 = d.init ? gloadd(&d.init->z[ch][0]) : 0.0, s1 = d.init ? gloadd(&d.init->z[ch][1]) : 0.0;
+    for (uint32_t b = 0; b < n; b += 64u) {
+        const uint32_t cnt = n - b < 64u ? n - b : 64u;
+        __syncthreads();
+        for (uint32_t i = tid; i < cnt * 12u; i += 64u) sm[i] = gloadd(d.agg + (size_t)b * 12u + i);
+        __syncthreads();
+        if (tid < 2u) {
+            for (uint32_t t = 0; t < cnt; ++t) {
+                gstore_d2(d.carry + (size_t)(b + t) * 4u + 2u * ch, s0, s1);
+                const double* m = sm + t * 12u + ch * 6u;
+                const double n0 = (m[0] * s0 + m[1] * s1) + m[2], n1 = (m[3] * s0 + m[4] * s1) + m[5];
+                s0 = n0;
+                s1 = n1;
+            }
+        }
+    }
+}
+// SINGLE: the chunk is this one tile -- the term loops and the follower run here, and the tile enters with *init (a block pull:
+// one launch).  KEYED (SINGLE only): the level is taken from the sum of the key terms.
+template <bool SINGLE, bool KEYED>
+__global__ __launch_bounds__(kThreads) void k_filt_apply(const FiltDesc* __restrict__ descs) {
+    const FiltDesc& d = descs[blockIdx.y];
+    if (blockIdx.x >= d.n_tiles) return;
+    __shared__ double pm[12 * kThreads];
+    __shared__ double sv[kThreads];
+    const uint32_t tid = threadIdx.x, M = d.frames, f0 = blockIdx.x * kFiltTile + tid * kFiltRun;
+    float2 x[kFiltRun];
+    double e[kFiltRun];
+#pragma unroll
+    for (uint32_t k = 0; k < kFiltRun; ++k) e[k] = 0.0;
+    double S[2][2];
+    if (SINGLE) {
+        filt_sum_run(d.ins, d.k, d.term_mode, M, f0, x);
+        if (d.env) {
+            if (KEYED) {
+                float2 kx[kFiltRun];
+                filt_sum_run(d.key_ins, d.key_k, d.key_term_mode, M, f0, kx);
+#pragma unroll
+                for (uint32_t k = 0; k < kFiltRun; ++k) e[k] = filt_level(kx[k].x, kx[k].y);
+            } else {
+#pragma unroll
+                for (uint32_t k = 0; k < kFiltRun; ++k) e[k] = filt_level(x[k].x, x[k].y);
+            }
+            filt_release(d, e, d.init ? gloadd(&d.init->y1) : 0.0, sv);
+            filt_keep(&d.state->y1, e, M, f0);
+            filt_attack(d, e, d.init ? gloadd(&d.init->e) : 0.0, sv);
+            filt_keep(&d.state->e, e, M, f0);
+        }
+#pragma unroll
+        for (uint32_t c = 0; c < 2; ++c) {
+            S[c][0] = d.init ? gloadd(&d.init->z[c][0]) : 0.0;
+            S[c][1] = d.init ? gloadd(&d.init->z[c][1]) : 0.0;
+        }
+    } else {
+        filt_load_x(d.x, M, f0, x);
+        if (d.env) filt_load_run(d.lv, M, f0, e);
+        const d2v a = gload_d2(d.carry + (size_t)blockIdx.x * 4u), b = gload_d2(d.carry + (size_t)blockIdx.x * 4u + 2u);
+        S[0][0] = a.x; S[0][1] = a.y; S[1][0] = b.x; S[1][1] = b.y;
+    }
+    {
+        double P[2][6];
+        filt_lane_maps(d, f0, x, e, P);
+        filt_lane_scan(P, pm);
+    }
+    // the lane's entry state: the map of the lanes before it, applied to the tile's
+    if (tid) {
+#pragma unroll
+        for (uint32_t c = 0; c < 2; ++c) {
+            const double* m = pm + (6u * c) * kThreads + tid - 1u;
+            const double n0 = (m[0] * S[c][0] + m[kThreads] * S[c][1]) + m[2 * kThreads];
+            const double n1 = (m[3 * kThreads] * S[c][0] + m[4 * kThreads] * S[c][1]) + m[5 * kThreads];
+            S[c][0] = n0;
+            S[c][1] = n1;
+        }
+    }
+    // the definition, serially; the lerp (adsr.rs:42, f32) takes the sample's place in x
+    const float wet = d.wet;
+    const double kq = d.kq;
+    const uint32_t kind = d.kind;
+#pragma unroll
+    for (uint32_t j = 0; j < kFiltRun; ++j) {   // (unrolled: x and e stay in registers)
+        const uint32_t m = f0 + j;
+        if (m >= M) continue;
+        float o[2];
+#pragma unroll
+        for (uint32_t c = 0; c < 2; ++c) {
+            double a1, a2, a3, v1, v2;
+            filt_coef(d, d.t0 + (uint64_t)m, c, e[j], a1, a2, a3);
+            const float xf = c ? x[j].y : x[j].x;
+            const double xs = eq_in(xf);
+            filt_frame(S[c][0], S[c][1], a1, a2, a3, xs, v1, v2);
+            double p;
+            if (kind == 0u) p = v2;
+            else if (kind == 1u) p = (xs - kq * v1) - v2;
+            else if (kind == 2u) p = kq * v1;
+            else p = xs - kq * v1;
+            const float pf = (float)p;
+            o[c] = xf + wet * (pf - xf);
+        }
+        x[j] = make_float2(o[0], o[1]);
+        if (m + 1u == M) {   // the chunk's last frame: what the next chunk / block pull enters with
+            gstore_d2(&d.state->z[0][0], S[0][0], S[0][1]);
+            gstore_d2(&d.state->z[1][0], S[1][0], S[1][1]);
+        }
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < kFiltRun / 2; ++j) {
+        const uint32_t m = f0 + 2u * j;
+        if (m >= M) break;
+        store_pair(d.out, m, M, epilogue4(make_float4(x[2 * j].x, x[2 * j].y, x[2 * j + 1].x, x[2 * j + 1].y), d.pg));
+    }
+}
+
 constexpr int kMaxGridY = 65535;
 
 // Batched launches put the vertex index in grid.y (limit 65535): larger batches go out in slices.
@@ -7356,6 +7720,32 @@ void launch_voc_apply(const VocDesc* d, int n, uint32_t bands, uint32_t n_tiles,
 void launch_voc_apply_keyed(const VocDesc* d, int n, uint32_t bands, uint32_t n_tiles, hipStream_t s) {
     for (int o = 0; o < n && n_tiles; o += kMaxGridY)
         TD_VOC_BANDS(hipLaunchKernelGGL((k_voc_apply<B, 2>), dim3(n_tiles, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o));
+}
+void launch_filt_detect(const FiltDesc* d, int n, uint32_t n_tiles, bool keyed, hipStream_t s) {
+    for (int o = 0; o < n && n_tiles; o += kMaxGridY) {
+        const dim3 grid(n_tiles, std::min(n - o, kMaxGridY));
+        if (keyed) hipLaunchKernelGGL(k_filt_detect<true>, grid, dim3(kThreads), 0, s, d + o);
+        else hipLaunchKernelGGL(k_filt_detect<false>, grid, dim3(kThreads), 0, s, d + o);
+    }
+}
+void launch_filt_env(const FiltDesc* d, int n, uint32_t n_tiles, hipStream_t s) {
+    for (int o = 0; o < n && n_tiles; o += kMaxGridY)
+        hipLaunchKernelGGL(k_filt_env, dim3(n_tiles, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
+}
+void launch_filt_local(const FiltDesc* d, int n, uint32_t n_tiles, hipStream_t s) {
+    for (int o = 0; o < n && n_tiles; o += kMaxGridY)
+        hipLaunchKernelGGL(k_filt_local, dim3(n_tiles, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
+}
+void launch_filt_carry(const FiltDesc* d, int n, hipStream_t s) {
+    if (n > 0) hipLaunchKernelGGL(k_filt_carry, dim3(n), dim3(64), 0, s, d);
+}
+void launch_filt_apply(const FiltDesc* d, int n, uint32_t n_tiles, bool single, bool keyed, hipStream_t s) {
+    for (int o = 0; o < n && n_tiles; o += kMaxGridY) {
+        const dim3 grid(n_tiles, std::min(n - o, kMaxGridY));
+        if (!single) hipLaunchKernelGGL((k_filt_apply<false, false>), grid, dim3(kThreads), 0, s, d + o);
+        else if (keyed) hipLaunchKernelGGL((k_filt_apply<true, true>), grid, dim3(kThreads), 0, s, d + o);
+        else hipLaunchKernelGGL((k_filt_apply<true, false>), grid, dim3(kThreads), 0, s, d + o);
+    }
 }
 void launch_sample_loop(const LoopDesc* d, int n, uint32_t frames, hipStream_t s) {
     if (!n || !frames) return;

@@ -23,6 +23,7 @@
 #include "gate_math.h"
 #include "phaser_math.h"
 #include "vocoder_math.h"
+#include "filter_math.h"
 #include "lua_subset.h"
 #include "reverb_math.h"
 #include "master.h"
@@ -116,6 +117,7 @@ struct ChorusCall { std::string name; float gain, angle, wet; int voices; float 
 struct ReverbCall { std::string name; float gain, angle, wet, room, damp, width, size; };
 struct PhaserCall { std::string name; float gain, angle, wet; int stages; float lo_hz, hi_hz, rate_hz, feedback, stereo; int shape; };
 struct VocoderCall { std::string name; float gain, angle, wet; int bands; float lo_hz, hi_hz, q, response_ms, out_db; };
+struct FilterCall { std::string name; float gain, angle, wet; int kind; float freq_hz, q, lfo_oct, rate_hz, stereo; int shape; float env_oct, sens_db, attack_ms, release_ms; };
 struct GateCall { std::string name; float gain, angle, wet, threshold_db, hysteresis_db, hold_ms, attack_ms, release_ms, range_db; };
 struct SatCall { std::string name; float gain, angle, wet; int kind; float drive_db, bias, out_db; int oversample; };
 
@@ -242,6 +244,7 @@ int do_refresh(td_state* s, const std::string& contents) {
     std::vector<GateCall> gates;
     std::vector<PhaserCall> phasers;
     std::vector<VocoderCall> vocoders;
+    std::vector<FilterCall> filters;
     size_t cs = s->cs, render_sr = s->render_sr, bd = s->bd;
     // std::mem::take (state.rs:79-80): the locals start from the previous values, the State's own fields are left
     // EMPTY until the script has run (state.rs:169-170) -- so they stay empty when the script fails
@@ -511,6 +514,27 @@ int do_refresh(td_state* s, const std::string& contents) {
                 fnum(c.hi_hz) + "," + fnum(c.q) + "," + fnum(c.response_ms) + "," + fnum(c.out_db) + ")\n";
         return Value::nil();
     });
+    lua.set_function("add_filter", [&](const std::vector<Value>& a) {   // this engine's own vertex (termdaw_amd.h td_graph_add_filter); kind and shape by name
+        const char* f = "add_filter";
+        static const char* const kinds[4] = {"lowpass", "highpass", "bandpass", "notch"};
+        static const char* const shapes[2] = {"sine", "triangle"};
+        const std::string kind = to_str(f, a, 4), shape = to_str(f, a, 10);
+        int k = 0, sh = 0;
+        while (k < 4 && kind != kinds[k]) ++k;
+        if (k == 4) throw LuaError{"add_filter: unknown kind \"" + kind + "\" (one of lowpass, highpass, bandpass, notch)"};
+        while (sh < 2 && shape != shapes[sh]) ++sh;
+        if (sh == 2) throw LuaError{"add_filter: unknown shape \"" + shape + "\" (one of sine, triangle)"};
+        filters.push_back({to_str(f, a, 0), to_f32(f, a, 1), to_f32(f, a, 2), to_f32(f, a, 3), k, to_f32(f, a, 5), to_f32(f, a, 6), to_f32(f, a, 7), to_f32(f, a, 8),
+                           to_f32(f, a, 9), sh, to_f32(f, a, 11), to_f32(f, a, 12), to_f32(f, a, 13), to_f32(f, a, 14)});
+        auto& c = filters.back();
+        // (out-of-range parameters are rejected here, where the line is known)
+        if (const char* why = tde::filter::check(psr, c.kind, c.freq_hz, c.q, c.lfo_oct, c.rate_hz, c.stereo, c.shape, c.env_oct, c.sens_db, c.attack_ms, c.release_ms))
+            throw LuaError{std::string("add_filter: ") + why};
+        dump += std::string(f) + "(\"" + c.name + "\"," + fnum(c.gain) + "," + fnum(c.angle) + "," + fnum(c.wet) + ",\"" + kind + "\"," + fnum(c.freq_hz) + "," + fnum(c.q) + "," +
+                fnum(c.lfo_oct) + "," + fnum(c.rate_hz) + "," + fnum(c.stereo) + ",\"" + shape + "\"," + fnum(c.env_oct) + "," + fnum(c.sens_db) + "," + fnum(c.attack_ms) + "," +
+                fnum(c.release_ms) + ")\n";
+        return Value::nil();
+    });
     lua.set_function("connect", [&](const std::vector<Value>& a) {
         edges.push_back({to_str("connect", a, 0), to_str("connect", a, 1)});
         dump += "connect(\"" + edges.back().first + "\",\"" + edges.back().second + "\")\n";
@@ -648,6 +672,9 @@ int do_refresh(td_state* s, const std::string& contents) {
         if (!td_graph_add_phaser(s->g, c.name.c_str(), c.gain, c.angle, c.wet, c.stages, c.lo_hz, c.hi_hz, c.rate_hz, c.feedback, c.stereo, c.shape)) return 0;
     for (auto& c : vocoders)
         if (!td_graph_add_vocoder(s->g, c.name.c_str(), c.gain, c.angle, c.wet, c.bands, c.lo_hz, c.hi_hz, c.q, c.response_ms, c.out_db)) return 0;
+    for (auto& c : filters)
+        if (!td_graph_add_filter(s->g, c.name.c_str(), c.gain, c.angle, c.wet, c.kind, c.freq_hz, c.q, c.lfo_oct, c.rate_hz, c.stereo, c.shape, c.env_oct, c.sens_db,
+                                 c.attack_ms, c.release_ms)) return 0;
     for (auto& e : edges) td_graph_connect(s->g, e.first.c_str(), e.second.c_str());   // failures only warn (state.rs:459)
     for (auto& e : key_edges) td_graph_connect_key(s->g, e.first.c_str(), e.second.c_str());   // (after the edges; failures only warn, like theirs)
     td_graph_set_output(s->g, s->output_vertex.c_str());

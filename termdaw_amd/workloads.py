@@ -169,7 +169,7 @@ class ProjectScript:
         self.calls = {k: [] for k in (
             "load_sample", "load_resource", "load_midi_floww", "add_sum", "add_normalize", "add_sampleloop",
             "add_sample_multi", "add_sample_lerp", "add_debug_sine", "add_synth", "add_sampsyn", "add_adsr",
-            "add_bandpass", "add_compressor", "add_eq", "add_delay", "add_saturator", "add_chorus", "add_reverb", "add_gate", "add_phaser", "add_vocoder", "connect", "connect_key")}
+            "add_bandpass", "add_compressor", "add_eq", "add_delay", "add_saturator", "add_chorus", "add_reverb", "add_gate", "add_phaser", "add_vocoder", "add_filter", "connect", "connect_key")}
         self.resources = {}                 # path -> bytes (load_resource)
         self.script_order = []              # (fn, args) in call order, for to_lua()
 
@@ -276,11 +276,15 @@ class ProjectScript:
         """This engine's own vertex (include/termdaw_amd.h td_graph_add_vocoder): no reference counterpart."""
         self._rec("add_vocoder", name, gain, angle, wet, bands, lo_hz, hi_hz, q, response_ms, out_db)
 
+    def add_filter(self, name, gain, angle, wet, kind, freq_hz, q, lfo_oct, rate_hz, stereo, shape, env_oct, sens_db, attack_ms, release_ms):
+        """This engine's own vertex (include/termdaw_amd.h td_graph_add_filter): no reference counterpart.  kind, shape: the string names."""
+        self._rec("add_filter", name, gain, angle, wet, kind, freq_hz, q, lfo_oct, rate_hz, stereo, shape, env_oct, sens_db, attack_ms, release_ms)
+
     def connect(self, a, b):
         self._rec("connect", a, b)
 
     def connect_key(self, a, b):
-        """This engine's own edge (include/termdaw_amd.h td_graph_connect_key): the key input of a compressor, gate or vocoder vertex."""
+        """This engine's own edge (include/termdaw_amd.h td_graph_connect_key): the key input of a compressor, gate, vocoder or filter vertex."""
         self._rec("connect_key", a, b)
 
     # -- State::refresh (state.rs:202-467) --
@@ -353,6 +357,8 @@ class ProjectScript:
             g.add_phaser(*args)
         for args in self.calls["add_vocoder"]:
             g.add_vocoder(*args)
+        for args in self.calls["add_filter"]:
+            g.add_filter(*args)
         for a, b in self.calls["connect"]:
             g.connect(a, b)
         for a, b in self.calls["connect_key"]:   # (after the connect calls, as the front-end applies them)

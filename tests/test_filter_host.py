@@ -1,0 +1,498 @@
+"""The filter vertex on the host, no GPU (include/termdaw_amd.h td_graph_add_filter): parameter ranges rejected
+with messages that name the parameter, through the C ABI and through the Lua front-end (NaN and the infinities included); the
+canonical dump line; td_filter_params against numpy's evaluation of the formulas; the sweep's E(t) against exp; facts of the
+float64 twin (tests/np_filter.py) that can be derived by hand; the tiled scans restated in numpy (np_filter.blocked, the kernels'
+tile geometry and join order, the follower's included) against the serial loops, within the bound's constant, which this file
+derives; the host engine on random projects with filter vertices under AddressSanitizer / UBSan (a stand-alone program:
+tests/asan_comp.cpp as it is, against tests/mock_hip.cpp + tests/mock_filter.cpp, whose mock launches check every descriptor's
+bounds, tile counts, scratch sizes, key forms and launch order); and the guard rule and the launch lists, read from the launch
+families the mock build reports."""
+import math
+import multiprocessing
+import os
+import shutil
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from termdaw_amd import workloads as W
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import eq_projects as EP  # noqa: E402
+import filter_projects as FP  # noqa: E402
+import np_filter as NF  # noqa: E402
+import test_loudness_host as L  # noqa: E402
+from test_eq_host import oracle_input  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "termdaw_amd", "csrc")
+SR = 48000
+
+GOOD = dict(kind=0, freq_hz=1000.0, q=5.0, lfo_oct=2.0, rate_hz=1.0, stereo=0.25, shape=0, env_oct=3.0, sens_db=12.0, attack_ms=5.0, release_ms=100.0)
+ORDER = ["kind", "freq_hz", "q", "lfo_oct", "rate_hz", "stereo", "shape", "env_oct", "sens_db", "attack_ms", "release_ms"]
+RANGES = dict(freq_hz=(20.0, 0.45 * SR), q=(0.5, 30.0), lfo_oct=(0.0, 4.0), rate_hz=(0.01, 20.0), stereo=(0.0, 0.5), env_oct=(-8.0, 8.0),
+              sens_db=(0.0, 60.0), attack_ms=(0.0, 1000.0), release_ms=(1.0, 10000.0))
+NON_FINITE = (float("nan"), float("inf"), float("-inf"))
+
+
+def _below(v):
+    return float(np.nextafter(np.float32(v), np.float32(-1e9)))
+
+
+def _above(v):
+    return float(np.nextafter(np.float32(v), np.float32(1e9)))
+
+
+BAD = [(k, _below(lo)) for k, (lo, hi) in RANGES.items()] + [(k, _above(hi)) for k, (lo, hi) in RANGES.items()]
+BAD += [(k, v) for k in RANGES for v in NON_FINITE]
+BAD += [("kind", 4), ("kind", -1), ("shape", 2), ("shape", -1)]
+
+
+def _args(**kw):
+    a = dict(GOOD)
+    a.update(kw)
+    return [a[k] for k in ORDER]
+
+
+# ---- ranges, the Lua line, the project script ----
+@pytest.mark.parametrize("name,value", BAD)
+def test_out_of_range_parameters_are_rejected_by_name(api, name, value):
+    g = api.Graph(64, SR)
+    with pytest.raises(api.TermdawError, match=name):
+        g.add_filter("f", 1.0, 0.0, 1.0, *_args(**{name: value}))
+    with pytest.raises(api.TermdawError, match=name):
+        api.filter_params(SR, *_args(**{name: value}))
+
+
+def test_range_ends_are_accepted_and_follow_the_rate(api):
+    g = api.Graph(64, SR)
+    g.add_sum("in", 1.0, 0.0)
+    ends = [("lowpass", 20.0, 0.5, 0.0, 0.01, 0.0, "sine", -8.0, 0.0, 0.0, 1.0),
+            ("notch", 0.45 * SR, 30.0, 4.0, 20.0, 0.5, "triangle", 8.0, 60.0, 1000.0, 10000.0),
+            (1, 1000.0, 5.0, 2.0, 1.0, 0.25, 1, 0.0, 0.0, 0.0, 1.0), (2, 1000.0, 5.0, 2.0, 1.0, 0.25, 0, -0.0, 0.0, 0.0, 1.0)]
+    for i, c in enumerate(ends):
+        g.add_filter("f%d" % i, 1.0, 0.0, 1.0, *c)
+        assert g.connect("in", "f%d" % i) and g.connect_key("in", "f%d" % i)
+    g.add_filter("wet", 1.0, 0.0, 7.0, *_args())   # (wet is clamped, not rejected: graph.rs:256)
+    g.add_filter("dry", 1.0, 0.0, -3.0, *_args())
+    assert g.set_output("f1") and g.check_graph()
+    for sr in (44100, 96000):   # freq_hz's end is 0.45 of the graph's own rate
+        h = api.Graph(64, sr)
+        h.add_filter("p", 1.0, 0.0, 1.0, *_args(freq_hz=0.45 * sr))
+        with pytest.raises(api.TermdawError, match="freq_hz"):
+            h.add_filter("q", 1.0, 0.0, 1.0, *_args(freq_hz=_above(0.45 * sr)))
+    with pytest.raises(api.TermdawError, match="11"):   # td_filter_params: cap
+        out = (api.C.c_double * 11)()
+        api._check(api.lib().td_filter_params(SR, *_args(), out, 10))
+
+
+def test_a_filter_takes_a_key_and_cannot_close_a_loop_with_it(api):
+    g = api.Graph(64, SR)
+    g.add_sum("a", 1.0, 0.0)
+    g.add_filter("f", 1.0, 0.0, 1.0, *_args())
+    g.add_sum("post", 1.0, 0.0)
+    assert g.connect("a", "f") and g.connect("f", "post") and g.connect_key("a", "f")
+    assert not g.connect_key("post", "f") and "loop" in api.last_error()
+    assert not g.connect_key("a", "post") and api.last_error() == "connect_key: post takes no key input"
+
+
+def _lua(line):
+    return 'add_sum("in", 1.0, 0.0);\n%s\nconnect("in", "g");\nconnect_key("in", "g");\nset_output("g");\n' % line
+
+
+def _lit(v):
+    if isinstance(v, str):
+        return '"%s"' % v
+    if isinstance(v, int):
+        return str(v)
+    if math.isnan(v):
+        return "0/0"
+    if math.isinf(v):
+        return "1/0" if v > 0 else "-1/0"
+    return repr(float(v))
+
+
+def _lua_args(**kw):
+    a = _args(**kw)
+    a[0], a[6] = "lowpass", "sine"
+    return ", ".join(_lit(v) for v in a)
+
+
+@pytest.mark.parametrize("name,value", [(k, v) for k, v in BAD if k not in ("kind", "shape")])
+def test_lua_rejects_the_same_ranges(api, name, value):
+    s = api.State("", SR, 64)
+    assert not s.refresh(_lua('add_filter("g", 1.0, 0.0, 1.0, %s);' % _lua_args(**{name: value})))
+    assert name in api.last_error(), api.last_error()
+
+
+def test_lua_rejects_unknown_kind_and_shape_strings(api):
+    s = api.State("", SR, 64)
+    assert not s.refresh(_lua('add_filter("g", 1.0, 0.0, 1.0, "ladder", 1000.0, 5.0, 2.0, 1.0, 0.25, "sine", 3.0, 12.0, 5.0, 100.0);'))
+    assert "kind" in api.last_error(), api.last_error()
+    assert not s.refresh(_lua('add_filter("g", 1.0, 0.0, 1.0, "notch", 1000.0, 5.0, 2.0, 1.0, 0.25, "square", 3.0, 12.0, 5.0, 100.0);'))
+    assert "shape" in api.last_error(), api.last_error()
+
+
+def test_lua_accepts_and_dumps_the_canonical_line(api):
+    s = api.State("", SR, 64)
+    assert s.refresh(_lua('add_filter("g", 0.5, -30, 1, "bandpass", 100.5, 4, 0.5, 1, 0.25, "triangle", 4, 0.5, 1, 100.5);')), api.last_error()
+    dump = s.dump_calls()
+    band = api.State("", SR, 64)
+    assert band.refresh('add_sum("in", 1.0, 0.0);\nadd_bandpass("b", 0.5, -30, 1, 100.5, 4, true);\nconnect("in", "b");\nset_output("b");\n'), api.last_error()
+    # the numbers print as add_bandpass prints the same values
+    half, m30, one, x1005, four = band.dump_calls().split('add_bandpass("b",')[1].split(")")[0].split(",")[:5]
+    line = [ln for ln in dump.splitlines() if ln.startswith("add_filter(")]
+    assert len(line) == 1 and 'connect_key("in","g")' in dump
+    args = line[0][len("add_filter("):-1].split(",")
+    assert args[:4] == ['"g"', half, m30, one] and args[4] == '"bandpass"' and args[5] == x1005 and args[6] == four and args[7] == half, line
+    assert args[8] == one and args[10] == '"triangle"' and args[11] == four and args[12] == half and args[13] == one and args[14] == x1005
+    assert len(args) == 15 and " " not in line[0]
+
+
+def test_project_script_records_and_writes_the_call(tmp_path):
+    p = W.ProjectScript(SR, 64)
+    p.add_sum("in", 1.0, 0.0)
+    c = ("g", 1.0, 0.0, 1.0, "notch", 200.0, 2.0, 1.0, 0.5, 0.25, "sine", -3.0, 6.0, 1.0, 50.0)
+    p.add_filter(*c)
+    p.connect("in", "g")
+    p.set_output("g")
+    assert p.calls["add_filter"] == [c]
+    assert 'add_filter("g", 1.0, 0.0, 1.0, "notch", 200.0, 2.0, 1.0, 0.5, 0.25, "sine", -3.0, 6.0, 1.0, 50.0);' in p.to_lua(str(tmp_path))
+
+
+# ---- td_filter_params, E(t) ----
+def test_filter_params_match_the_formulas(api):
+    """The tangents, the power and the exponentials against numpy's float64: they come from the same libm on both sides here, but
+    only correct rounding would make that a promise: four ulp.  k, cl, ce, f and 1 - aA are IEEE operations and agree to the bit."""
+    worst = 0.0
+    for sr in FP.RATES + (8000, 192000):
+        for c in FP.grid_cases(sr) + [("notch", 333.3, 0.77, 1.1, 3.3, 0.1, "sine", -2.2, 7.7, 3.3, 77.7)]:
+            fr, q, lo, rate, st_, _, eo, sens, att, rel = (float(np.float32(v)) if not isinstance(v, str) else v for v in c[1:])
+            g0, k, gmin, gmax, cl, ce, f, S, aA, oA, aR = api.filter_params(sr, *c)
+            want = (np.tan(np.pi * fr / sr), None, np.tan(np.pi * 20.0 / sr), np.tan(0.45 * np.pi), None, None, None, np.power(10.0, sens / 20.0),
+                    np.exp(-1.0 / (att * sr / 1000.0)) if att > 0.0 else 0.0, None, np.exp(-1.0 / (rel * sr / 1000.0)))
+            for got, w in zip((g0, k, gmin, gmax, cl, ce, f, S, aA, oA, aR), want):
+                if w is None or w == 0.0:
+                    continue
+                ulps = abs(got - float(w)) / np.spacing(abs(float(w)))
+                worst = max(worst, ulps)
+                assert ulps <= 4.0, (sr, c, got, w)
+            assert k == 1.0 / q and cl == math.log(2.0) * lo and ce == math.log(2.0) * eo and f == rate / sr and oA == 1.0 - aA
+            assert (aA == 0.0) == (att == 0.0) and 0.0 < gmin <= g0 <= gmax * (1.0 + 1e-12)   # (0.45 sr / sr and 0.45 round apart: the clamp is what holds g)
+    print("filter_params: worst disagreement with numpy %.3g ulp" % worst)
+
+
+def test_sweep_exponential_is_close_to_exp_and_monotone():
+    t = np.linspace(-8.4, 8.4, 400001)
+    e = NF.sweep_exp(t)
+    rel = np.abs(e / np.exp(t) - 1.0).max()
+    print("E(t): worst relative distance from exp over |t| <= 8.4: %.3g" % rel)
+    assert rel <= 1e-8 and (np.diff(e) > 0.0).all() and NF.sweep_exp(0.0) == 1.0
+    # the header's list of c_j: the doubles nearest 1 / j
+    assert NF.C == (1.0, 0.5, 0.3333333333333333, 0.25, 0.2, 0.16666666666666666, 0.14285714285714285, 0.125, 0.1111111111111111, 0.1)
+
+
+# ---- facts of the twin ----
+def _spec(api, **kw):
+    c = _args(**kw)
+    return NF.spec(api.filter_params(SR, *c), c[0], c[5], c[6])
+
+
+STATIC = dict(lfo_oct=0.0, env_oct=0.0)
+
+
+def test_twin_low_pass_and_high_pass_sum_to_the_notch(api):
+    x = np.random.default_rng(3).uniform(-0.5, 0.5, (6000, 2)).astype(np.float32)
+    lp, hp, _, no = (NF.serial(x, _spec(api, kind=k, **STATIC))[0] for k in range(4))
+    assert np.abs((lp + hp) - no).max() <= 1e-12 * np.abs(no).max() and np.abs(no).max() > 0.1
+
+
+def test_twin_magnitude_at_the_cutoff_is_q_for_the_low_pass_and_one_for_the_band_pass(api):
+    fc, q = 1000.0, 5.0
+    n = np.arange(14400)
+    tone = (0.25 * np.sin(2.0 * np.pi * fc * n / SR)).astype(np.float32)
+    x = np.stack([tone, tone], axis=1)
+    ph = 2.0 * np.pi * fc * n[4800:] / SR
+
+    def amplitude(v):   # of the fc component over 200 whole periods, once the transient has died
+        return 2.0 * math.hypot(float(np.mean(v * np.sin(ph))), float(np.mean(v * np.cos(ph))))
+    a_in = amplitude(tone[4800:].astype(np.float64))
+    for kind, want in ((0, q), (2, 1.0)):
+        v, _ = NF.serial(x, _spec(api, kind=kind, freq_hz=fc, q=q, **STATIC))
+        got = amplitude(v[4800:, 0]) / a_in
+        assert abs(got / want - 1.0) <= 1e-6, (kind, got)
+
+
+def test_twin_env_oct_zero_with_a_key_is_the_unkeyed_vertex_bitwise(api):
+    rng = np.random.default_rng(4)
+    x, k = (rng.uniform(-0.5, 0.5, (5000, 2)).astype(np.float32) for _ in range(2))
+    sp = _spec(api, env_oct=0.0)
+    st = (0.3, 0.2, 0.01, -0.02, 0.03, 0.04)
+    (a, ea), (b, eb) = NF.serial(x, sp, st), NF.serial(x, sp, st, key=k)
+    assert np.array_equal(a, b) and np.array_equal(ea, eb) and ea[0] == 0.3 and ea[1] == 0.2   # (y1, e stay as they are)
+    c, _ = NF.serial(x, _spec(api), key=k)
+    assert np.abs(c - NF.serial(x, _spec(api))[0]).max() > 1e-3   # (with a follower the key is heard)
+
+
+def test_twin_splits_give_the_one_piece_result_bitwise(api):
+    rng = np.random.default_rng(8)
+    x, k = (rng.uniform(-0.5, 0.5, (6000, 2)).astype(np.float32) for _ in range(2))
+    sp = _spec(api, kind=1, rate_hz=7.0, q=12.0)
+    whole, end = NF.process(x, sp, wet=0.7, gain=1.7, angle=30.0, key=k)
+    for cut in (1, 777, 2048, 4999):
+        a, st = NF.process(x[:cut], sp, wet=0.7, gain=1.7, angle=30.0, key=k[:cut])
+        b, st = NF.process(x[cut:], sp, wet=0.7, gain=1.7, angle=30.0, state=st, t0=cut, key=k[cut:])
+        assert np.array_equal(np.concatenate([a, b]).view(np.uint32), whole.view(np.uint32)) and np.array_equal(st, end), cut
+
+
+def test_twin_stereo_zero_gives_equal_channels_for_equal_input(api):
+    m = np.random.default_rng(6).uniform(-0.5, 0.5, 5000).astype(np.float32)
+    x = np.stack([m, m], axis=1)
+    v, end = NF.serial(x, _spec(api, stereo=0.0, rate_hz=20.0))
+    assert np.array_equal(v[:, 0], v[:, 1]) and end[2] == end[4] and end[3] == end[5]
+    w, _ = NF.serial(x, _spec(api, stereo=0.25, rate_hz=20.0))
+    assert np.array_equal(w[:, 0], v[:, 0]) and np.abs(w[:, 1] - v[:, 1]).max() > 1e-3
+
+
+def test_twin_a_louder_key_opens_a_low_pass(api):
+    """env_oct > 0 on a low-pass at 300 Hz: the output's energy above 2 kHz rises with the key's level."""
+    rng = np.random.default_rng(9)
+    x = rng.uniform(-0.5, 0.5, (9600, 2)).astype(np.float32)
+    key = rng.uniform(-1.0, 1.0, (9600, 2)).astype(np.float32)
+    sp = _spec(api, freq_hz=300.0, q=0.707, lfo_oct=0.0, env_oct=4.0, sens_db=0.0, attack_ms=1.0, release_ms=50.0)
+    high = []
+    for level in (0.0, 0.25, 1.0):
+        v, _ = NF.serial(x, sp, key=(np.float32(level) * key))
+        spec = np.abs(np.fft.rfft(v[2400:, 0])) ** 2
+        high.append(float(spec[int(2000.0 * 7200 / SR):].sum()))
+    assert high[0] * 4.0 < high[1] and high[1] * 4.0 < high[2], high
+
+
+# ---- the tiled scans restated ----
+def _emulate(args):
+    """One rate and input (a worker of its own: numpy only): the worst max|blocked - serial| / max|serial| (the end states
+    included) and its case's index, the largest word of a prefix map, the largest output peak over the input's."""
+    x, specs = args
+    maps = {}
+    ser, end = NF.serial(x, specs)
+    blk, endb = NF.blocked(x, specs, maps=maps)
+    peak = np.abs(ser).max(axis=(1, 2))
+    r = np.maximum(np.abs(blk - ser).max(axis=(1, 2)), np.abs(endb - end).max(axis=1)) / peak
+    i = int(r.argmax())
+    return (float(r[i]), i), maps["peak"], float((peak / np.abs(x).max()).max())
+
+
+def test_blocked_scans_stay_inside_the_committed_constant(api):
+    """E = 8 x the worst max|blocked - serial| / max|serial| of the numpy emulation over the GPU test's own grid and inputs at
+    the three rates; this recomputes that worst figure and fails above E / 8.  Also printed: the largest word of a prefix map and
+    the largest output peak over the input's."""
+    jobs, what = [], []
+    for sr in FP.RATES:
+        cases = FP.grid_cases(sr)
+        assert len(cases) == 108
+        specs = [FP.spec(api, sr, c) for c in cases]
+        for kind in FP.INPUTS:
+            x = oracle_input(kind, sr)
+            assert len(x) > 5 * NF.TILE and np.abs(x).max() > 0.05
+            jobs.append((x, specs))
+            what.append((cases, sr, kind))
+    with multiprocessing.Pool(max(1, min(len(jobs), os.cpu_count() or 1))) as pool:
+        results = pool.map(_emulate, jobs)
+    worst, maps, gain, n = (0.0, None), {"peak": 0.0}, 0.0, 0
+    for (w, peak, g), (cases, sr, kind) in zip(results, what):
+        if w[0] > worst[0]:
+            worst = (w[0], (cases[w[1]], sr, kind))
+        maps["peak"], gain, n = max(maps["peak"], peak), max(gain, g), n + len(cases)
+    print("blocked scans: %d cases, worst max|blocked - serial| / max|serial| %.3g at %s (E_EMULATED %.3g, E %.3g = 2^%.1f); prefix "
+          "maps up to %.3g, output peaks up to %.3g x the input's" % (n, worst[0], worst[1], FP.E_EMULATED, FP.E, math.log2(FP.E), maps["peak"], gain))
+    assert n == 3 * 3 * 108
+    assert 0.0 < worst[0] <= FP.E_EMULATED and FP.E == min(8 * FP.E_EMULATED, 2.0 ** -28) and FP.E <= 2 ** -28
+
+
+def test_blocked_scans_continue_from_a_carried_state(api):
+    x = oracle_input("noise", SR)[:9000]
+    k = oracle_input("drums", SR)[:9000]
+    sp = _spec(api, q=20.0, rate_hz=3.0)
+    v, end = NF.serial(x, sp, key=k)
+    for cut in (1, 777, 2048, 4999):
+        a, st = NF.blocked(x[:cut], sp, key=k[:cut])
+        b, st = NF.blocked(x[cut:], sp, state=st, t0=cut, key=k[cut:])
+        assert np.abs(np.concatenate([a, b]) - v).max() <= FP.E_EMULATED * np.abs(v).max()
+        assert np.abs(st - end).max() <= FP.E_EMULATED * np.abs(v).max()
+
+
+# ---- the host engine under sanitizers ----
+def _build(out_dir):
+    flags = ["-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-ffp-contract=off",
+             "-D__HIP_PLATFORM_AMD__", "-I", "/opt/rocm/include", "-I", CSRC, "-I", os.path.join(ROOT, "include")]
+    jobs = [(os.path.join(CSRC, f), os.path.join(out_dir, f + ".o")) for f in L.SOURCES]
+    jobs += [(os.path.join(ROOT, "tests", f), os.path.join(out_dir, f + ".o")) for f in ("mock_hip.cpp", "mock_filter.cpp", "asan_comp.cpp")]
+    procs = [subprocess.Popen(["g++"] + flags + ["-c", src, "-o", obj]) for src, obj in jobs]
+    for p in procs:
+        assert p.wait() == 0
+    exe = os.path.join(out_dir, "asan_filter")
+    subprocess.check_call(["g++", "-fsanitize=address,undefined", "-o", exe] + [o for _, o in jobs] + ["-lpthread", "-ldl"])
+    return exe
+
+
+@pytest.fixture(scope="module")
+def asan_exe(tmp_path_factory):
+    if shutil.which("g++") is None or not os.path.exists("/opt/rocm/include/hip/hip_runtime_api.h"):
+        pytest.skip("needs g++ and the HIP headers")
+    return _build(str(tmp_path_factory.mktemp("asan_filter")))
+
+
+ENV = dict(ASAN_OPTIONS="detect_leaks=0:allocator_may_return_null=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1", TD_ALLOC_CACHE_MB="0")
+FOLLOWER = ("k_filt_detect", "k_filt_carry_y1", "k_filt_env", "k_filt_carry_e")
+FILTER = ("k_filt_local", "k_filt_carry", "k_filt_apply")
+
+
+def test_filter_projects_under_sanitizers(asan_exe, tmp_path):
+    n = int(os.environ.get("TD_ASAN_FILTER_SEEDS", "32"))
+    workers = max(1, min(8, os.cpu_count() or 1))
+    seeds = list(range(n))
+    base = str(tmp_path / "p")
+    with multiprocessing.Pool(workers) as pool:
+        lists = pool.map(FP.write_projects, [(base, seeds[i::workers]) for i in range(workers) if seeds[i::workers]])
+    procs = [subprocess.Popen([asan_exe] + lst, env=dict(os.environ, **ENV), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True) for lst in lists]
+    launches = vertices = carried = fresh = rejected = 0
+    for p in procs:
+        out, err = p.communicate(timeout=1800)
+        assert p.returncode == 0, (out[-800:], err[-4000:])
+        # (the driver is the compressor's, as it is: its summary calls the effect launches it counted "k_comp")
+        tail = out.split("asan_comp done:")[1]
+        launches += int(tail.split("k_comp launches ")[1].split()[0])
+        vertices += int(tail.split("(")[1].split()[0])
+        fresh += int(tail.split(" entered fresh")[0].split()[-1])
+        carried += int(tail.split(" entered with carried state")[0].split()[-1])
+        rejected += int(tail.split(" rejected refreshes")[0].split()[-1])
+    # multi-chunk renders and block pulls enter with carried state; every project is within the ranges
+    assert rejected == 0 and launches >= n // 2 and vertices >= launches and fresh > 0 and carried > 0, (rejected, launches, vertices, fresh, carried)
+    print("asan_filter: %d projects, %d launches, %d vertices (%d fresh, %d carried) clean" % (n, launches, vertices, fresh, carried))
+
+
+CASE = ("lowpass", 400.0, 4.0, 2.0, 3.0, 0.25, "sine", 4.0, 18.0, 2.0, 80.0)
+STILL = CASE[:7] + (0.0, 0.0, 0.0, 1.0)
+
+
+def _guard_project(shape, seconds=0.5):
+    p = W.ProjectScript(SR, 1024)
+    p.set_length(seconds)
+    p.assets["a"] = W.Asset(W.noise_int16(7, 9000))
+    p.load_sample("a", "a", "")
+    p.event_files["f"] = np.array([(0.01, 60.0, 0.8), (0.2, 60.0, 0.0), (0.25, 62.0, 0.6)], np.float32)
+    p.load_midi_floww("f", "f")
+    fl = ("c", 1.0, 0.0, 0.0 if shape in ("band_dry", "key_dry") else 1.0) + (STILL if shape in ("still", "key_still") else CASE)
+    if shape == "band_up":       # loop -> band-pass -> filter
+        p.add_sampleloop("s", 1.0, 0.0, "a")
+        p.add_bandpass("b", 1.0, 0.0, 1.0, 300.0, 5000.0, True)
+        p.add_filter(*fl)
+        p.connect("s", "b"); p.connect("b", "c"); p.set_output("c")
+    elif shape == "band_down":   # loop -> filter -> band-pass
+        p.add_sampleloop("s", 1.0, 0.0, "a")
+        p.add_filter(*fl)
+        p.add_bandpass("b", 1.0, 0.0, 1.0, 300.0, 5000.0, True)
+        p.connect("s", "c"); p.connect("c", "b"); p.set_output("b")
+    elif shape in ("band_dry", "band_plain"):   # loop -> band-pass -> a dry filter / a Sum in its place
+        p.add_sampleloop("s", 1.0, 0.0, "a")
+        p.add_bandpass("b", 1.0, 0.0, 1.0, 300.0, 5000.0, True)
+        if shape == "band_dry":
+            p.add_filter(*fl)
+        else:
+            p.add_sum("c", 1.0, 0.0)
+        p.connect("s", "b"); p.connect("b", "c"); p.set_output("c")
+    elif shape in ("key_up", "key_still", "key_dry"):   # loop -> band-pass -> out, and the band-pass is the KEY of a filter on a second loop
+        p.add_sampleloop("s", 1.0, 0.0, "a")
+        p.add_sampleloop("s2", 0.5, 0.0, "a")
+        p.add_bandpass("b", 1.0, 0.0, 1.0, 300.0, 5000.0, True)
+        p.add_filter(*fl)
+        p.add_sum("out", 1.0, 0.0)
+        p.connect("s", "b"); p.connect("s2", "c"); p.connect_key("b", "c"); p.connect("b", "out"); p.connect("c", "out"); p.set_output("out")
+    elif shape in ("sine_up", "one_tile", "still", "mixed"):     # synth -> filter (one_tile: a render of 2 048 frames)
+        p.add_synth("y", 1.0, 0.0, "f", 0.4, 0.3, W.HIT_ADSR, 1.0, 0.8, W.NOTE_ADSR, 0.5, W.STD_ADSR)
+        p.add_filter(*fl)
+        p.connect("y", "c")
+        if shape == "mixed":     # ... and three more in the same level: one without a follower, two keyed (one of them without)
+            p.add_sampleloop("s", 1.0, 0.0, "a")
+            p.add_filter("c0", 1.0, 0.0, 1.0, *STILL)
+            p.add_filter("ck", 1.0, 0.0, 1.0, *CASE)
+            p.add_filter("ck0", 1.0, 0.0, 1.0, *STILL)
+            p.add_sum("m", 1.0, 0.0)
+            for v in ("c0", "ck", "ck0"):
+                p.connect("y", v)
+            p.connect_key("s", "ck"); p.connect_key("s", "ck0")
+            for v in ("c", "c0", "ck", "ck0"):
+                p.connect(v, "m")
+        p.set_output("m" if shape == "mixed" else "c")
+    else:                        # synth -> sum: the control
+        p.add_synth("y", 1.0, 0.0, "f", 0.4, 0.3, W.HIT_ADSR, 1.0, 0.8, W.NOTE_ADSR, 0.5, W.STD_ADSR)
+        p.add_sum("c", 1.0, 0.0)
+        p.connect("y", "c"); p.set_output("c")
+    return p
+
+
+def _families(asan_exe, tmp_path, projects):
+    dirs = {name: EP.write_project(p, str(tmp_path / name)) for name, p in projects.items()}
+    r = subprocess.run([asan_exe] + list(dirs.values()), env=dict(os.environ, **ENV), capture_output=True, text=True, timeout=1800)
+    assert r.returncode == 0, (r.stdout[-800:], r.stderr[-4000:])
+    back = {d: name for name, d in dirs.items()}
+    fams = {}
+    for ln in r.stdout.splitlines():
+        if ln.startswith("launches "):
+            d, rest = ln[len("launches "):].split(":", 1)
+            fams[back[d]] = dict((kv.split("=")[0], int(kv.split("=")[1])) for kv in rest.split())   # (dicts keep the driver's order)
+    return fams
+
+
+def _filt(f):
+    return [(k, v) for k, v in f.items() if k.startswith("k_filt")]
+
+
+def test_launch_lists_and_the_guard_rule(asan_exe, tmp_path):
+    """band_mode 2 / sine_mode 2 (the driver's profiled render): the launch families each shape went through."""
+    shapes = ("band_up", "band_down", "band_dry", "band_plain", "key_up", "key_still", "key_dry", "sine_up", "sine_free", "still", "mixed")
+    projects = {s: _guard_project(s) for s in shapes}
+    projects["one_tile"] = _guard_project("one_tile", seconds=0.04)
+    assert projects["one_tile"].cs * 1024 == NF.TILE
+    fams = _families(asan_exe, tmp_path, projects)
+    exact = ("k_band_pass", "k_band_spec")
+    whole = [(k, 1) for k in FOLLOWER + FILTER]
+    # upstream of a filter's input the exact forms; downstream the scan
+    up, down = fams["band_up"], fams["band_down"]
+    assert "k_band_scan" not in up and any(k in up for k in exact), up
+    assert "k_band_scan" in down and not any(k in down for k in exact), down
+    assert _filt(up) == whole and _filt(down) == whole   # (seven launches, in this order)
+    # upstream of a key into a filter whose follower runs: the exact forms; a key no follower hears, or into a dry vertex: the scan
+    assert "k_band_scan" not in fams["key_up"] and any(k in fams["key_up"] for k in exact), fams["key_up"]
+    for s in ("key_still", "key_dry"):
+        assert "k_band_scan" in fams[s] and not any(k in fams[s] for k in exact), (s, fams[s])
+    assert _filt(fams["key_up"]) == whole and _filt(fams["key_still"]) == [(k, 1) for k in FILTER] and _filt(fams["key_dry"]) == []
+    # wet < 0.0001 compiles to k_sum: the launch list of the project with a Sum in the filter's place
+    dry, plain = fams["band_dry"], fams["band_plain"]
+    assert not _filt(dry) and list(dry.items()) == list(plain.items()), (dry, plain)
+    sup, sfree = fams["sine_up"], fams["sine_free"]
+    assert "k_sine_probe" not in sup and "k_synth" in sup, sup
+    assert "k_sine_probe" in sfree and not _filt(sfree), sfree
+    # env_oct == 0: no follower launches; a chunk of one tile is k_filt_apply alone
+    assert _filt(fams["still"]) == [(k, 1) for k in FILTER], fams["still"]
+    assert _filt(fams["one_tile"]) == [("k_filt_apply", 1)], fams["one_tile"]
+    # a level with all four forms: the keyed detect launch behind the unkeyed one, every other step once
+    assert _filt(fams["mixed"]) == [("k_filt_detect", 2)] + [(k, 1) for k in FOLLOWER[1:] + FILTER], fams["mixed"]
+
+
+# (test_eq_host.py's record of the parent's lists)
+PARENT_LAUNCHES = {
+    "drums": "k_sample_multi=1 k_sum=1 k_band_scan=2 k_band_audit=1 k_sources=1",
+    "config2": "k_sum=1",
+    "config4": "k_band_scan=1 k_sources=1",
+}
+
+
+def test_projects_without_a_filter_keep_their_launch_list(asan_exe, tmp_path):
+    projects = {"drums": W.drum_project(seconds=0.5), "config2": W.config2(seconds=0.5, n_src=8), "config4": W.config4(seconds=0.5, depth=6)}
+    fams = _families(asan_exe, tmp_path, projects)
+    for name in projects:
+        got = " ".join("%s=%d" % kv for kv in fams[name].items())
+        assert not _filt(fams[name]) and got == PARENT_LAUNCHES[name], (name, got)
