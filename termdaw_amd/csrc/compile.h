@@ -97,24 +97,38 @@ struct FxLevel {
     }
 };
 
-// One row per effect kind (the table: compile_fx.cpp), in the order of their families in `Family` -- the order a level launches them in.
+// One row per effect kind (the table: compile_fx.cpp), in the order of their families in `Family` -- the order a level launches them
+// in.  Everything the compiler AND the engine know of a kind beyond its vertex' parameter fields (engine.cpp td_graph_add_*).
 constexpr double kNoStaticGain = -1.0;   // FxKind::through: no estimate is carried through this vertex
 struct FxKind {
     Kind kind;
     const char* name;       // as in "<name>: chunk too long"
+    const char* k;          // as in "this build has no k_<k> kernels"
     int first_family;       // the kind's families are [first_family, first_family + n_families)
     int n_families;
     size_t desc_bytes;      // of the descriptors its launches take (the compressor's and the filter's two carries aside: MasterDesc)
+    int state_slots;        // the consecutive StateSlots of td_graph::dstate a vertex carries from Vertex::state_slot on; 0: a Vertex::line, or nothing
+    bool takes_key;         // td_graph_connect_key may end at a vertex of this kind
     bool (*fits)(const td_graph* g, const Vertex& v, size_t M);   // a chunk of M frames is within the kernels' index ranges
     int (*family)(const Vertex& v);                               // the family a vertex is lowered at; nullptr: first_family (all but the saturator)
     // the factor the guard's estimate goes through a vertex at, its own pan / gain aside (1 when dry); kNoStaticGain: none
     double (*through)(const Vertex& v, size_t sr);
     // descriptors + launches of the level's vertices of one family (FxLevel::fam), called where the level's loop reaches it; 0: failed
     int (*lower)(FxLevel& L, std::vector<size_t>& vs);
+    // one of those launches onto the stream, `d` its descriptors on the device: decodes the Launch::aux that `lower` encoded
+    void (*launch)(const Launch& L, const void* d, hipStream_t s);
+    bool built;               // the weak launch_* entry points of the kind are linked
+    bool keyed_built;         // ... and those of its keyed forms (true where there are none beyond `built`)
+    const char* keyed_name;   // as in "this build has no keyed <keyed_name> kernels"
+    void (*rest)(const td_graph* g, const Vertex& v, StateSlot* run);   // the state at time 0 into the vertex' slots; nullptr: all-zero bytes
     int family_of(const Vertex& v) const { return family ? family(v) : first_family; }
+    void put_rest(const td_graph* g, const Vertex& v, StateSlot* run) const {
+        memset(run, 0, (size_t)state_slots * sizeof(StateSlot));
+        if (rest) rest(g, v, run);
+    }
 };
 const FxKind* fx_kind(Kind k);          // nullptr: not an effect kind
-const FxKind* fx_of_family(int fam);    // nullptr: not an effect kind's family
+const FxKind* fx_of_family(int fam);    // nullptr: not an effect kind's family (one array read: submit_chunk asks per launch)
 
 // ---- engine.cpp: the device memory the compiler hands out addresses of ----
 int upload_tables(td_graph* g, TableCache& tc, const Staging& tmp);   // a vertex' event tables -> its device buffer (queued on the graph's stream)

@@ -1,8 +1,10 @@
 // compile_fx.cpp -- the effect kinds of the host compiler (compile.h FxKind / FxLevel): compressor, EQ, delay, saturator,
 // chorus, reverb, gate, phaser, vocoder, filter.  One table row per kind -- its chunk limit, the family its launches start at, the factor the guard
-// carries an estimate through it at -- and one function per kind that lowers a level's vertices of that kind to descriptors
-// and launches.  compile_chunk enumerates the kinds through the table only.  Like compile.cpp: no HIP call.  Not an object of its
-// own: compile.cpp includes this file at its end, so no build list changes with it.
+// carries an estimate through it at, the state slots it carries and their state at time 0, whether it takes a key, whether its
+// kernels are linked -- one function per kind that lowers a level's vertices of that kind to descriptors and launches, and right
+// behind it the one that decodes such a launch and calls the kernels' entry points (kernels.h launch_*: the only calls out of the
+// host compiler; no HIP call of its own, like compile.cpp).  compile_chunk and engine.cpp enumerate the kinds through the table
+// only.  Not an object of its own: compile.cpp includes this file at its end, so no build list changes with it.
 #include "chorus_math.h"
 #include "compile.h"
 #include "delay_math.h"
@@ -114,6 +116,16 @@ static int lower_comp(FxLevel& L, std::vector<size_t>& vs) {
     L.add_launch(F_COMP_APPLY, off, (int)vs.size(), n_tiles);
     return 1;
 }
+// (a keyed form: prepare_render has checked it exists where a key edge asks for it -- here and in the kinds below)
+static void launch_comp(const Launch& L, const void* d, hipStream_t s) {
+    switch (L.fam) {
+        case F_COMP_DETECT: (L.aux & kKeyedBit ? launch_comp_detect_keyed : launch_comp_detect)((const CompDesc*)d, L.n, L.aux & ~kKeyedBit, s); break;
+        case F_COMP_CARRY1:
+        case F_COMP_CARRY2: launch_master_carry((const MasterDesc*)d, L.n, s); break;
+        case F_COMP_ENV: launch_comp_env((const CompDesc*)d, L.n, L.aux, s); break;
+        case F_COMP_APPLY: launch_comp_apply((const CompDesc*)d, L.n, L.aux, s); break;
+    }
+}
 
 // ---- EQ: three launches (kernels.h EqDesc) ----
 static int lower_eq(FxLevel& L, std::vector<size_t>& vs) {
@@ -150,6 +162,13 @@ static int lower_eq(FxLevel& L, std::vector<size_t>& vs) {
     L.add_launch(F_EQ_CARRY, off, (int)vs.size(), 0u);
     L.add_launch(F_EQ_APPLY, off, (int)vs.size(), n_tiles);
     return 1;
+}
+static void launch_eq(const Launch& L, const void* d, hipStream_t s) {
+    switch (L.fam) {
+        case F_EQ_LOCAL: launch_eq_local((const EqDesc*)d, L.n, L.aux, s); break;
+        case F_EQ_CARRY: launch_eq_carry((const EqDesc*)d, L.n, s); break;
+        case F_EQ_APPLY: launch_eq_apply((const EqDesc*)d, L.n, L.aux, s); break;
+    }
 }
 
 // ---- delay (kernels.h DelayDesc) ----
@@ -223,6 +242,13 @@ static int lower_delay(FxLevel& L, std::vector<size_t>& vs) {
         L.add_launch(F_DELAY_APPLY, off + (size_t)n_multi * sizeof(DelayDesc), (int)plans.size() - n_multi, g_single | kDelaySingleBit);
     return 1;
 }
+static void launch_delay(const Launch& L, const void* d, hipStream_t s) {
+    switch (L.fam) {
+        case F_DELAY_LOCAL: launch_delay_local((const DelayDesc*)d, L.n, L.aux, s); break;
+        case F_DELAY_CARRY: launch_delay_carry((const DelayDesc*)d, L.n, L.aux, s); break;
+        case F_DELAY_APPLY: launch_delay_apply((const DelayDesc*)d, L.n, L.aux & ~kDelaySingleBit, (L.aux & kDelaySingleBit) != 0u, s); break;
+    }
+}
 
 // ---- saturator (kernels.h SatDesc): the vertices with R > 1 (L.fam == F_SAT_SUM) or those with R = 1 (F_SAT1) ----
 static int lower_sat(FxLevel& L, std::vector<size_t>& vs) {
@@ -275,6 +301,13 @@ static int lower_sat(FxLevel& L, std::vector<size_t>& vs) {
     }
     return 1;
 }
+static void launch_sat_kind(const Launch& L, const void* d, hipStream_t s) {
+    switch (L.fam) {
+        case F_SAT_SUM: launch_sat_sum((const SatDesc*)d, L.n, L.M, s); break;
+        case F_SAT: launch_sat((const SatDesc*)d, L.n, (L.aux >> 24) & 15u, L.aux & 0xFFFFFu, ((L.aux >> 20) & 15u) * 128u, (L.aux & kSatTermsBit) != 0u, s); break;
+        case F_SAT1: launch_sat1((const SatDesc*)d, L.n, L.M, s); break;
+    }
+}
 
 // ---- chorus (kernels.h ChorusDesc) ----
 static int lower_chorus(FxLevel& L, std::vector<size_t>& vs) {
@@ -311,6 +344,10 @@ static int lower_chorus(FxLevel& L, std::vector<size_t>& vs) {
     if (multi) L.add_launch(F_CHORUS_SUM, off, (int)vs.size(), 0);
     L.add_launch(F_CHORUS, off, (int)vs.size(), chorus_aux(n_tiles, !multi));
     return 1;
+}
+static void launch_chorus_kind(const Launch& L, const void* d, hipStream_t s) {
+    if (L.fam == F_CHORUS_SUM) launch_chorus_sum((const ChorusDesc*)d, L.n, L.M, s);
+    else launch_chorus((const ChorusDesc*)d, L.n, L.aux & 0xFFFFFu, L.M, (L.aux & kChorusTermsBit) != 0u, s);
 }
 
 // ---- reverb (kernels.h ReverbDesc) ----
@@ -354,6 +391,10 @@ static int lower_reverb(FxLevel& L, std::vector<size_t>& vs) {
     L.add_launch(F_REVERB_SUM, off, (int)vs.size(), 0);
     L.add_launch(F_REVERB, off, (int)vs.size(), g->reverb_form);
     return 1;
+}
+static void launch_reverb_kind(const Launch& L, const void* d, hipStream_t s) {
+    if (L.fam == F_REVERB_SUM) launch_reverb_sum((const ReverbDesc*)d, L.n, L.M, s);
+    else launch_reverb((const ReverbDesc*)d, L.n, L.aux, s);
 }
 
 // ---- gate: five launches (kernels.h GateDesc) ----
@@ -414,6 +455,21 @@ static int lower_gate(FxLevel& L, std::vector<size_t>& vs) {
     L.add_launch(F_GATE_APPLY, off, (int)vs.size(), n_tiles);
     return 1;
 }
+static void launch_gate(const Launch& L, const void* d, hipStream_t s) {
+    switch (L.fam) {
+        case F_GATE_DETECT: (L.aux & kKeyedBit ? launch_gate_detect_keyed : launch_gate_detect)((const GateDesc*)d, L.n, L.aux & ~kKeyedBit, s); break;
+        case F_GATE_CARRY_H: launch_gate_carry((const GateDesc*)d, L.n, false, s); break;
+        case F_GATE_ENV: (L.aux & kKeyedBit ? launch_gate_env_keyed : launch_gate_env)((const GateDesc*)d, L.n, L.aux & ~kKeyedBit, s); break;
+        case F_GATE_CARRY_ENV: launch_gate_carry((const GateDesc*)d, L.n, true, s); break;
+        case F_GATE_APPLY: launch_gate_apply((const GateDesc*)d, L.n, L.aux, s); break;
+    }
+}
+// A gate vertex' state at time 0: closed, the hold run out -- (env, h, c) = (0, 0, H + 1)
+static void rest_gate(const td_graph* g, const Vertex& v, StateSlot* run) {
+    double c[6];
+    gate::params(g->sr, v.gate_threshold_db, v.gate_hysteresis_db, v.gate_hold_ms, v.gate_attack_ms, v.gate_release_ms, v.gate_range_db, c);
+    run->gate = {0.0, 0u, (uint32_t)std::min(c[2] + 1.0, gate::kMaxHold + 1.0), {0, 0, 0, 0}};
+}
 
 // ---- phaser: three launches per stage count, or one (kernels.h PhaserDesc) ----
 static int lower_phaser(FxLevel& L, std::vector<size_t>& vs) {
@@ -464,6 +520,14 @@ static int lower_phaser(FxLevel& L, std::vector<size_t>& vs) {
         i = j;
     }
     return 1;
+}
+static void launch_phaser(const Launch& L, const void* d, hipStream_t s) {
+    const uint32_t N = (L.aux >> 24) & 15u, n_tiles = L.aux & 0xFFFFFFu;
+    switch (L.fam) {
+        case F_PHASER_LOCAL: launch_phaser_local((const PhaserDesc*)d, L.n, N, n_tiles, s); break;
+        case F_PHASER_CARRY: launch_phaser_carry((const PhaserDesc*)d, L.n, N, s); break;
+        case F_PHASER_APPLY: launch_phaser_apply((const PhaserDesc*)d, L.n, N, n_tiles, (L.aux & kPhaserSingleBit) != 0u, s); break;
+    }
 }
 
 // ---- vocoder: five launches per band count and key form, or one (kernels.h VocDesc) ----
@@ -552,6 +616,19 @@ static int lower_vocoder(FxLevel& L, std::vector<size_t>& vs) {
         i = j;
     }
     return 1;
+}
+static void launch_vocoder(const Launch& L, const void* d, hipStream_t s) {
+    const uint32_t B = voc_aux_bands(L.aux), n_tiles = voc_aux_tiles(L.aux);
+    switch (L.fam) {
+        case F_VOC_LOCAL: (L.aux & kKeyedBit ? launch_voc_local_keyed : launch_voc_local)((const VocDesc*)d, L.n, B, n_tiles, s); break;
+        case F_VOC_CARRY: launch_voc_carry((const VocDesc*)d, L.n, B, false, s); break;
+        case F_VOC_ENV: launch_voc_env((const VocDesc*)d, L.n, B, n_tiles, s); break;
+        case F_VOC_CARRY_ENV: launch_voc_carry((const VocDesc*)d, L.n, B, true, s); break;
+        case F_VOC_APPLY:
+            if (L.aux & kKeyedBit) launch_voc_apply_keyed((const VocDesc*)d, L.n, B, n_tiles, s);
+            else launch_voc_apply((const VocDesc*)d, L.n, B, n_tiles, (L.aux & kVocSingleBit) != 0u, s);
+            break;
+    }
 }
 
 // ---- filter: the follower's four launches, then three, or one (kernels.h FiltDesc) ----
@@ -661,6 +738,19 @@ static int lower_filter(FxLevel& L, std::vector<size_t>& vs) {
     L.add_launch(F_FILT_APPLY, off, (int)n_all, filt_aux(n_tiles, false, false));
     return 1;
 }
+static void launch_filter(const Launch& L, const void* d, hipStream_t s) {
+    const uint32_t n_tiles = filt_aux_tiles(L.aux);
+    const bool keyed = (L.aux & kKeyedBit) != 0u;
+    switch (L.fam) {
+        case F_FILT_DETECT: launch_filt_detect((const FiltDesc*)d, L.n, n_tiles, keyed, s); break;
+        case F_FILT_CARRY1:
+        case F_FILT_CARRY2: launch_master_carry((const MasterDesc*)d, L.n, s); break;
+        case F_FILT_ENV: launch_filt_env((const FiltDesc*)d, L.n, n_tiles, s); break;
+        case F_FILT_LOCAL: launch_filt_local((const FiltDesc*)d, L.n, n_tiles, s); break;
+        case F_FILT_CARRY: launch_filt_carry((const FiltDesc*)d, L.n, s); break;
+        case F_FILT_APPLY: launch_filt_apply((const FiltDesc*)d, L.n, n_tiles, (L.aux & kFiltSingleBit) != 0u, keyed, s); break;
+    }
+}
 
 // ---- the table ----
 // fits: the largest chunk the kind's kernels index (32-bit frames; the line kinds keep room for their look-back, the tiled
@@ -720,9 +810,15 @@ static double through_reverb(const Vertex& v, size_t sr) {
     return lerp_gain(v, c[5]);
 }
 
+// state_slots: a phaser vertex' 2 x (N + 1) doubles and a filter vertex' six take a run of slots
+constexpr int kPhaserSlots = (int)(sizeof(PhaserState) / sizeof(StateSlot)), kFiltSlots = (int)(sizeof(FiltState) / sizeof(StateSlot));
+static_assert(sizeof(PhaserState) == kPhaserSlots * sizeof(StateSlot) && sizeof(FiltState) == kFiltSlots * sizeof(StateSlot), "a phaser's and a filter's state: whole slots");
+
 // (a function's static: these sources also go through the HIP compiler, whose device pass would want a copy of a namespace-scope
 // constant -- and of the host functions it points to.)  A row's family count is the distance to the next row's first family, so
-// the rows cover the effect families of `Family` without gap or overlap as long as they stand in its order:
+// the rows cover the effect families of `Family` without gap or overlap as long as they stand in its order.  built / keyed_built:
+// the entry points the kind's `launch` calls are linked (kernels.h declares them weak); the filter's keyed forms are instantiations
+// behind the entry points of its unkeyed ones.
 constexpr int kFxKinds = 10;
 static_assert(F_COMP_DETECT < F_EQ_LOCAL && F_EQ_LOCAL < F_DELAY_LOCAL && F_DELAY_LOCAL < F_SAT_SUM && F_SAT_SUM < F_CHORUS_SUM &&
               F_CHORUS_SUM < F_REVERB_SUM && F_REVERB_SUM < F_GATE_DETECT && F_GATE_DETECT < F_PHASER_LOCAL && F_PHASER_LOCAL < F_VOC_LOCAL &&
@@ -730,16 +826,16 @@ static_assert(F_COMP_DETECT < F_EQ_LOCAL && F_EQ_LOCAL < F_DELAY_LOCAL && F_DELA
               "the rows of the effect kinds' table stand in the order of their families");
 static const FxKind* table() {
     static const FxKind rows[kFxKinds] = {
-        {K_COMPRESSOR, "compressor", F_COMP_DETECT, F_EQ_LOCAL - F_COMP_DETECT, sizeof(CompDesc), fits_scan, nullptr, through_comp, lower_comp},
-        {K_EQ, "eq", F_EQ_LOCAL, F_DELAY_LOCAL - F_EQ_LOCAL, sizeof(EqDesc), fits_scan, nullptr, through_eq, lower_eq},
-        {K_DELAY, "delay", F_DELAY_LOCAL, F_SAT_SUM - F_DELAY_LOCAL, sizeof(DelayDesc), fits_line, nullptr, through_delay, lower_delay},
-        {K_SATURATOR, "saturator", F_SAT_SUM, F_CHORUS_SUM - F_SAT_SUM, sizeof(SatDesc), fits_sat, family_sat, through_sat, lower_sat},
-        {K_CHORUS, "chorus", F_CHORUS_SUM, F_REVERB_SUM - F_CHORUS_SUM, sizeof(ChorusDesc), fits_chorus, nullptr, through_chorus, lower_chorus},
-        {K_REVERB, "reverb", F_REVERB_SUM, F_GATE_DETECT - F_REVERB_SUM, sizeof(ReverbDesc), fits_line, nullptr, through_reverb, lower_reverb},
-        {K_GATE, "gate", F_GATE_DETECT, F_PHASER_LOCAL - F_GATE_DETECT, sizeof(GateDesc), fits_scan, nullptr, through_gate, lower_gate},
-        {K_PHASER, "phaser", F_PHASER_LOCAL, F_VOC_LOCAL - F_PHASER_LOCAL, sizeof(PhaserDesc), fits_scan, nullptr, through_phaser, lower_phaser},
-        {K_VOCODER, "vocoder", F_VOC_LOCAL, F_FILT_DETECT - F_VOC_LOCAL, sizeof(VocDesc), fits_voc, nullptr, through_vocoder, lower_vocoder},
-        {K_FILTER, "filter", F_FILT_DETECT, F_COUNT - F_FILT_DETECT, sizeof(FiltDesc), fits_scan, nullptr, through_filter, lower_filter},
+        {K_COMPRESSOR, "compressor", "comp", F_COMP_DETECT, F_EQ_LOCAL - F_COMP_DETECT, sizeof(CompDesc), 1, true, fits_scan, nullptr, through_comp, lower_comp, launch_comp, launch_comp_detect && launch_comp_env && launch_comp_apply && launch_master_carry, launch_comp_detect_keyed != nullptr, "compressor / gate", nullptr},
+        {K_EQ, "eq", "eq", F_EQ_LOCAL, F_DELAY_LOCAL - F_EQ_LOCAL, sizeof(EqDesc), 1, false, fits_scan, nullptr, through_eq, lower_eq, launch_eq, launch_eq_local && launch_eq_carry && launch_eq_apply, true, nullptr, nullptr},
+        {K_DELAY, "delay", "delay", F_DELAY_LOCAL, F_SAT_SUM - F_DELAY_LOCAL, sizeof(DelayDesc), 0, false, fits_line, nullptr, through_delay, lower_delay, launch_delay, launch_delay_local && launch_delay_carry && launch_delay_apply, true, nullptr, nullptr},
+        {K_SATURATOR, "saturator", "sat", F_SAT_SUM, F_CHORUS_SUM - F_SAT_SUM, sizeof(SatDesc), 0, false, fits_sat, family_sat, through_sat, lower_sat, launch_sat_kind, launch_sat_sum && launch_sat && launch_sat1, true, nullptr, nullptr},
+        {K_CHORUS, "chorus", "chorus", F_CHORUS_SUM, F_REVERB_SUM - F_CHORUS_SUM, sizeof(ChorusDesc), 0, false, fits_chorus, nullptr, through_chorus, lower_chorus, launch_chorus_kind, launch_chorus_sum && launch_chorus, true, nullptr, nullptr},
+        {K_REVERB, "reverb", "reverb", F_REVERB_SUM, F_GATE_DETECT - F_REVERB_SUM, sizeof(ReverbDesc), 0, false, fits_line, nullptr, through_reverb, lower_reverb, launch_reverb_kind, launch_reverb_sum && launch_reverb, true, nullptr, nullptr},
+        {K_GATE, "gate", "gate", F_GATE_DETECT, F_PHASER_LOCAL - F_GATE_DETECT, sizeof(GateDesc), 1, true, fits_scan, nullptr, through_gate, lower_gate, launch_gate, launch_gate_detect && launch_gate_carry && launch_gate_env && launch_gate_apply, launch_gate_detect_keyed && launch_gate_env_keyed, "compressor / gate", rest_gate},
+        {K_PHASER, "phaser", "phaser", F_PHASER_LOCAL, F_VOC_LOCAL - F_PHASER_LOCAL, sizeof(PhaserDesc), kPhaserSlots, false, fits_scan, nullptr, through_phaser, lower_phaser, launch_phaser, launch_phaser_local && launch_phaser_carry && launch_phaser_apply, true, nullptr, nullptr},
+        {K_VOCODER, "vocoder", "voc", F_VOC_LOCAL, F_FILT_DETECT - F_VOC_LOCAL, sizeof(VocDesc), 0, true, fits_voc, nullptr, through_vocoder, lower_vocoder, launch_vocoder, launch_voc_local && launch_voc_carry && launch_voc_env && launch_voc_apply, launch_voc_local_keyed && launch_voc_apply_keyed, "vocoder", nullptr},
+        {K_FILTER, "filter", "filt", F_FILT_DETECT, F_COUNT - F_FILT_DETECT, sizeof(FiltDesc), kFiltSlots, true, fits_scan, nullptr, through_filter, lower_filter, launch_filter, launch_filt_detect && launch_filt_env && launch_filt_local && launch_filt_carry && launch_filt_apply && launch_master_carry, true, nullptr, nullptr},
     };
     return rows;
 }
@@ -753,10 +849,14 @@ const FxKind* fx_kind(Kind k) {
     return nullptr;
 }
 const FxKind* fx_of_family(int fam) {
-    const FxKind* rows = fxk::table();
-    for (int i = 0; i < fxk::kFxKinds; ++i)
-        if (fam >= rows[i].first_family && fam < rows[i].first_family + rows[i].n_families) return &rows[i];
-    return nullptr;
+    static const FxKind* const* const by = [] {   // the row of every family, filled once
+        static const FxKind* row[F_COUNT] = {};
+        const FxKind* rows = fxk::table();
+        for (int i = 0; i < fxk::kFxKinds; ++i)
+            for (int f = rows[i].first_family; f < rows[i].first_family + rows[i].n_families; ++f) row[f] = &rows[i];
+        return row;
+    }();
+    return fam >= 0 && fam < F_COUNT ? by[fam] : nullptr;
 }
 
 }  // namespace tde

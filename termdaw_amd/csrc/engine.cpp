@@ -537,19 +537,10 @@ static int ensure_state_slots(td_graph* g) {
     return 1;
 }
 
-// A gate vertex' state at time 0: closed, the hold run out -- (env, h, c) = (0, 0, H + 1)
-static tdk::GateState gate_closed(const td_graph* g, const Vertex& v) {
-    double c[6];
-    gate::params(g->sr, v.gate_threshold_db, v.gate_hysteresis_db, v.gate_hold_ms, v.gate_attack_ms, v.gate_release_ms, v.gate_range_db, c);
-    return {0.0, 0u, (uint32_t)std::min(c[2] + 1.0, gate::kMaxHold + 1.0), {0, 0, 0, 0}};
-}
-// A phaser vertex' state at time 0: (s_1 .. s_N, z) = 0 on both channels -- its run of slots, all zero
-static void phaser_rest(td_graph* g, const Vertex& v) {
-    memset(&g->hstate[(size_t)v.state_slot], 0, sizeof(tdk::PhaserState));
-}
-// A filter vertex' state at time 0: (y1, e, i1l, i2l, i1r, i2r) = 0 -- its run of slots, all zero
-static void filt_rest(td_graph* g, const Vertex& v) {
-    memset(&g->hstate[(size_t)v.state_slot], 0, sizeof(tdk::FiltState));
+// The effect kind of a vertex that carries state slots (FxKind::state_slots) and has them; nullptr: any other vertex
+static const FxKind* slot_kind(const Vertex& v) {
+    const FxKind* fx = fx_kind(v.kind);
+    return fx && fx->state_slots && v.state_slot >= 0 ? fx : nullptr;
 }
 static int drain(td_graph* g);   // stream drained + deferred k_norm_fix settled (defined with the render loop)
 static int pull_state(td_graph* g) {
@@ -557,18 +548,11 @@ static int pull_state(td_graph* g) {
         if (!drain(g)) return 0;
         TD_HIP(hipMemcpy(g->hstate.data(), g->dstate, g->hstate.size() * sizeof(StateSlot), hipMemcpyDeviceToHost));
         g->state_dev_dirty = false;
-        for (const auto& v : g->vertices)   // (a set_time not yet carried to the device by a submission)
-            if (v.kind == K_BAND_PASS && v.state_slot >= 0 && v.first_pending) g->hstate[(size_t)v.state_slot].band.first = 1u;
-        for (const auto& v : g->vertices)
-            if (v.kind == K_COMPRESSOR && v.state_slot >= 0 && v.first_pending) g->hstate[(size_t)v.state_slot].comp = {0.0, 0.0, {0, 0, 0, 0}};
-        for (const auto& v : g->vertices)
-            if (v.kind == K_EQ && v.state_slot >= 0 && v.first_pending) g->hstate[(size_t)v.state_slot].eq = {0.0, 0.0, 0.0, 0.0};
-        for (const auto& v : g->vertices)
-            if (v.kind == K_GATE && v.state_slot >= 0 && v.first_pending) g->hstate[(size_t)v.state_slot].gate = gate_closed(g, v);
-        for (const auto& v : g->vertices)
-            if (v.kind == K_PHASER && v.state_slot >= 0 && v.first_pending) phaser_rest(g, v);
-        for (const auto& v : g->vertices)
-            if (v.kind == K_FILTER && v.state_slot >= 0 && v.first_pending) filt_rest(g, v);
+        for (const auto& v : g->vertices) {   // (a set_time not yet carried to the device by a submission)
+            if (!v.first_pending) continue;
+            if (v.kind == K_BAND_PASS && v.state_slot >= 0) g->hstate[(size_t)v.state_slot].band.first = 1u;
+            if (const FxKind* fx = slot_kind(v)) fx->put_rest(g, v, &g->hstate[(size_t)v.state_slot]);
+        }
     }
     return 1;
 }
@@ -947,59 +931,9 @@ static int submit_chunk(Arena& ar, ChunkBuild& cb, hipStream_t stream, ProfCtx& 
                 case F_QUANT: launch_quantise((const QuantDesc*)d, L.n, L.M, s); break;
                 case F_AUDIT: launch_band_audit((const AuditHead*)d, L.n, s); break;
                 case F_STEMS: launch_stems((const StemDesc*)d, L.n, L.M, s); break;   // (prepare_render has checked it exists)
-                case F_COMP_DETECT:   // (likewise; the keyed form: prepare_render has checked it exists where a key edge asks for it)
-                    if (L.aux & kKeyedBit) launch_comp_detect_keyed((const CompDesc*)d, L.n, L.aux & ~kKeyedBit, s);
-                    else launch_comp_detect((const CompDesc*)d, L.n, L.aux, s);
+                default:   // an effect kind's family (likewise: prepare_render has checked that its kernels exist)
+                    if (const FxKind* fx = fx_of_family(L.fam)) fx->launch(L, d, s);
                     break;
-                case F_COMP_CARRY1:
-                case F_COMP_CARRY2: launch_master_carry((const MasterDesc*)d, L.n, s); break;
-                case F_COMP_ENV: launch_comp_env((const CompDesc*)d, L.n, L.aux, s); break;
-                case F_COMP_APPLY: launch_comp_apply((const CompDesc*)d, L.n, L.aux, s); break;
-                case F_EQ_LOCAL: launch_eq_local((const EqDesc*)d, L.n, L.aux, s); break;   // (likewise)
-                case F_EQ_CARRY: launch_eq_carry((const EqDesc*)d, L.n, s); break;
-                case F_EQ_APPLY: launch_eq_apply((const EqDesc*)d, L.n, L.aux, s); break;
-                case F_DELAY_LOCAL: launch_delay_local((const DelayDesc*)d, L.n, L.aux, s); break;   // (likewise)
-                case F_DELAY_CARRY: launch_delay_carry((const DelayDesc*)d, L.n, L.aux, s); break;
-                case F_DELAY_APPLY: launch_delay_apply((const DelayDesc*)d, L.n, L.aux & ~kDelaySingleBit, (L.aux & kDelaySingleBit) != 0u, s); break;
-                case F_SAT_SUM: launch_sat_sum((const SatDesc*)d, L.n, L.M, s); break;   // (likewise)
-                case F_SAT: launch_sat((const SatDesc*)d, L.n, (L.aux >> 24) & 15u, L.aux & 0xFFFFFu, ((L.aux >> 20) & 15u) * 128u, (L.aux & kSatTermsBit) != 0u, s); break;
-                case F_SAT1: launch_sat1((const SatDesc*)d, L.n, L.M, s); break;
-                case F_CHORUS_SUM: launch_chorus_sum((const ChorusDesc*)d, L.n, L.M, s); break;   // (likewise)
-                case F_REVERB_SUM: launch_reverb_sum((const ReverbDesc*)d, L.n, L.M, s); break;   // (likewise)
-                case F_REVERB: launch_reverb((const ReverbDesc*)d, L.n, L.aux, s); break;
-                case F_GATE_DETECT:   // (likewise)
-                    if (L.aux & kKeyedBit) launch_gate_detect_keyed((const GateDesc*)d, L.n, L.aux & ~kKeyedBit, s);
-                    else launch_gate_detect((const GateDesc*)d, L.n, L.aux, s);
-                    break;
-                case F_GATE_CARRY_H: launch_gate_carry((const GateDesc*)d, L.n, false, s); break;
-                case F_GATE_ENV:
-                    if (L.aux & kKeyedBit) launch_gate_env_keyed((const GateDesc*)d, L.n, L.aux & ~kKeyedBit, s);
-                    else launch_gate_env((const GateDesc*)d, L.n, L.aux, s);
-                    break;
-                case F_GATE_CARRY_ENV: launch_gate_carry((const GateDesc*)d, L.n, true, s); break;
-                case F_GATE_APPLY: launch_gate_apply((const GateDesc*)d, L.n, L.aux, s); break;
-                case F_PHASER_LOCAL: launch_phaser_local((const PhaserDesc*)d, L.n, (L.aux >> 24) & 15u, L.aux & 0xFFFFFFu, s); break;
-                case F_PHASER_CARRY: launch_phaser_carry((const PhaserDesc*)d, L.n, (L.aux >> 24) & 15u, s); break;
-                case F_PHASER_APPLY: launch_phaser_apply((const PhaserDesc*)d, L.n, (L.aux >> 24) & 15u, L.aux & 0xFFFFFFu, (L.aux & kPhaserSingleBit) != 0u, s); break;
-                case F_VOC_LOCAL:   // (the keyed forms: prepare_render has checked they exist where a key edge asks for them)
-                    if (L.aux & kKeyedBit) launch_voc_local_keyed((const VocDesc*)d, L.n, voc_aux_bands(L.aux), voc_aux_tiles(L.aux), s);
-                    else launch_voc_local((const VocDesc*)d, L.n, voc_aux_bands(L.aux), voc_aux_tiles(L.aux), s);
-                    break;
-                case F_VOC_CARRY: launch_voc_carry((const VocDesc*)d, L.n, voc_aux_bands(L.aux), false, s); break;
-                case F_VOC_ENV: launch_voc_env((const VocDesc*)d, L.n, voc_aux_bands(L.aux), voc_aux_tiles(L.aux), s); break;
-                case F_VOC_CARRY_ENV: launch_voc_carry((const VocDesc*)d, L.n, voc_aux_bands(L.aux), true, s); break;
-                case F_VOC_APPLY:
-                    if (L.aux & kKeyedBit) launch_voc_apply_keyed((const VocDesc*)d, L.n, voc_aux_bands(L.aux), voc_aux_tiles(L.aux), s);
-                    else launch_voc_apply((const VocDesc*)d, L.n, voc_aux_bands(L.aux), voc_aux_tiles(L.aux), (L.aux & kVocSingleBit) != 0u, s);
-                    break;
-                case F_FILT_DETECT: launch_filt_detect((const FiltDesc*)d, L.n, filt_aux_tiles(L.aux), (L.aux & kKeyedBit) != 0u, s); break;   // (likewise)
-                case F_FILT_CARRY1:
-                case F_FILT_CARRY2: launch_master_carry((const MasterDesc*)d, L.n, s); break;
-                case F_FILT_ENV: launch_filt_env((const FiltDesc*)d, L.n, filt_aux_tiles(L.aux), s); break;
-                case F_FILT_LOCAL: launch_filt_local((const FiltDesc*)d, L.n, filt_aux_tiles(L.aux), s); break;
-                case F_FILT_CARRY: launch_filt_carry((const FiltDesc*)d, L.n, s); break;
-                case F_FILT_APPLY: launch_filt_apply((const FiltDesc*)d, L.n, filt_aux_tiles(L.aux), (L.aux & kFiltSingleBit) != 0u, (L.aux & kKeyedBit) != 0u, s); break;
-                case F_CHORUS: launch_chorus((const ChorusDesc*)d, L.n, L.aux & 0xFFFFFu, L.M, (L.aux & kChorusTermsBit) != 0u, s); break;
             }
         }
         li = lj;
@@ -1082,34 +1016,20 @@ static int prepare_render(td_graph* g, size_t n_blocks, int bits, bool want_pcm,
     if (g->output_vertex < 0) return fail("TermDaw: error: output vertex not found.");
     if (g->plan_dirty) build_plan(g);
     if (!ensure_state_slots(g)) return 0;
-    const struct { Kind kind; bool built; const char* k; const char* name; } fx[] = {
-        {K_COMPRESSOR, launch_comp_detect && launch_comp_env && launch_comp_apply && launch_master_carry, "comp", "compressor"},
-        {K_EQ, launch_eq_local && launch_eq_carry && launch_eq_apply, "eq", "eq"},
-        {K_DELAY, launch_delay_local && launch_delay_carry && launch_delay_apply, "delay", "delay"},
-        {K_SATURATOR, launch_sat_sum && launch_sat && launch_sat1, "sat", "saturator"},
-        {K_CHORUS, launch_chorus_sum && launch_chorus, "chorus", "chorus"},
-        {K_REVERB, launch_reverb_sum && launch_reverb, "reverb", "reverb"},
-        {K_GATE, launch_gate_detect && launch_gate_carry && launch_gate_env && launch_gate_apply, "gate", "gate"},
-        {K_PHASER, launch_phaser_local && launch_phaser_carry && launch_phaser_apply, "phaser", "phaser"},
-        {K_VOCODER, launch_voc_local && launch_voc_carry && launch_voc_env && launch_voc_apply, "voc", "vocoder"},
-        {K_FILTER, launch_filt_detect && launch_filt_env && launch_filt_local && launch_filt_carry && launch_filt_apply && launch_master_carry, "filt", "filter"},
-    };
-    for (const auto& f : fx)
-        if (!f.built)
-            for (size_t vi : g->order)
-                if (g->vertices[vi].kind == f.kind && !(g->vertices[vi].wet < 0.0001f))
-                    return fail(std::string("termdaw_amd: this build has no k_") + f.k + " kernels: " + f.name + " vertices cannot be rendered");
+    // the effect kinds' kernels are linked (a dry vertex compiles to a Sum: it needs none), the first kind of the table first
+    for (int k = 0; k < K_COUNT; ++k) {
+        const FxKind* fx = fx_kind((Kind)k);
+        if (!fx || fx->built) continue;
+        for (size_t vi : g->order)
+            if (g->vertices[vi].kind == fx->kind && !(g->vertices[vi].wet < 0.0001f))
+                return fail(std::string("termdaw_amd: this build has no k_") + fx->k + " kernels: " + fx->name + " vertices cannot be rendered");
+    }
     for (size_t vi : g->order) {   // ... and the keyed forms, where a key edge asks for them (td_graph_connect_key)
         const Vertex& v = g->vertices[vi];
         if (g->key_edges[vi].empty() || v.wet < 0.0001f) continue;
-        if (v.kind == K_FILTER) continue;   // (its keyed forms are instantiations behind the entry points checked above)
-        if (v.kind == K_VOCODER) {
-            if (!(launch_voc_local_keyed && launch_voc_apply_keyed))
-                return fail("termdaw_amd: this build has no keyed vocoder kernels: a vertex with a key edge cannot be rendered");
-            continue;
-        }
-        if (v.kind == K_COMPRESSOR ? !launch_comp_detect_keyed : !(launch_gate_detect_keyed && launch_gate_env_keyed))
-            return fail("termdaw_amd: this build has no keyed compressor / gate kernels: a vertex with a key edge cannot be rendered");
+        const FxKind* fx = fx_kind(v.kind);
+        if (fx && !fx->keyed_built)
+            return fail(std::string("termdaw_amd: this build has no keyed ") + fx->keyed_name + " kernels: a vertex with a key edge cannot be rendered");
     }
     const size_t bl = g->bl;
     if (bl == 0) return fail("termdaw_amd: buffer length 0");
@@ -1213,7 +1133,7 @@ static bool starts_afresh(const td_graph* g) {
     for (size_t vi : g->order) {
         const Vertex& v = g->vertices[vi];
         if (v.kind == K_NORMALIZE && !v.has_init_override) return false;
-        if ((v.kind == K_BAND_PASS || v.kind == K_COMPRESSOR || v.kind == K_EQ || v.kind == K_GATE || v.kind == K_PHASER || v.kind == K_FILTER) && v.state_slot >= 0 && !v.first_pending) return false;
+        if (((v.kind == K_BAND_PASS && v.state_slot >= 0) || slot_kind(v)) && !v.first_pending) return false;
         if (v.line.d && !v.first_pending) return false;
     }
     return true;
@@ -1423,44 +1343,13 @@ static int graph_set_time_impl(td_graph* g, size_t time) {   // graph.rs:123-128
                     any_band = true;
                 }
                 break;
-            case K_COMPRESSOR:   // the detector restarts from (0, 0): the next submission's carries enter with 0
-                if (v.state_slot >= 0) {
-                    g->hstate[v.state_slot].comp = {0.0, 0.0, {0, 0, 0, 0}};
-                    v.first_pending = true;
-                }
-                break;
-            case K_EQ:   // the filter restarts from the zero state: the next submission's carry enters with 0
-                if (v.state_slot >= 0) {
-                    g->hstate[v.state_slot].eq = {0.0, 0.0, 0.0, 0.0};
-                    v.first_pending = true;
-                }
-                break;
-            case K_GATE:   // the gate restarts closed: the next submission's carries enter with (0, 0, H + 1)
-                if (v.state_slot >= 0) {
-                    g->hstate[v.state_slot].gate = gate_closed(g, v);
-                    v.first_pending = true;
-                }
-                break;
-            case K_PHASER:   // the chain restarts from the zero state (the LFO does not: it runs on the graph's time)
-                if (v.state_slot >= 0) {
-                    phaser_rest(g, v);
-                    v.first_pending = true;
-                }
-                break;
-            case K_FILTER:   // the follower and the filter restart from the zero state (the LFO does not: it runs on the graph's time)
-                if (v.state_slot >= 0) {
-                    filt_rest(g, v);
-                    v.first_pending = true;
-                }
-                break;
-            case K_DELAY:   // the line restarts from zero: the next submission reads none of its words
-            case K_SATURATOR:
-            case K_CHORUS:
-            case K_REVERB:
-            case K_VOCODER:   // (the filters and followers restart from zero: the line is not read)
+            default: {   // an effect kind: its slots restart from the state at time 0, of its line the next submission reads no word (an LFO runs on: the graph's time)
+                const FxKind* fx = fx_kind(v.kind);
+                if (!fx || (fx->state_slots && v.state_slot < 0)) break;
+                if (fx->state_slots) fx->put_rest(g, v, &g->hstate[(size_t)v.state_slot]);
                 v.first_pending = true;
                 break;
-            default: break;
+            }
         }
     }
     (void)any_band;   // (no device work: the next submission's descriptors carry the vertices' first_override)
@@ -1804,6 +1693,15 @@ static int new_slot(td_graph* g) {
     g->state_host_dirty = true;
     return (int)g->hstate.size() - 1;
 }
+// A vertex of an effect kind with the state slots its kind carries (FxKind::state_slots).  The slots first: new_slot pulls the state of
+// the vertices that exist.  They are zeroed: every kind's state at time 0 but the gate's, which needs the vertex' parameters (FxKind::rest).
+static Vertex& add_fx_vertex(td_graph* g, const char* name, float gain, float angle, float wet, Kind kind) {
+    const int n = fx_kind(kind)->state_slots, slot = n ? new_slot(g) : -1;
+    for (int i = 1; i < n; ++i) new_slot(g);
+    Vertex& v = add_vertex(g, name, gain, angle, wet, kind);
+    v.state_slot = slot;
+    return v;
+}
 static bool conf_from(const float* arr, int n, AdsrConfD* c) {   // adsr.rs:94-114
     if (n == 0) { *c = AdsrConfD{0, 0, 0, 0, 0, 0, 0, 0, 0}; return true; }
     if (n == 6) { *c = AdsrConfD{0.0f, arr[0], 1.0f, arr[1], arr[2], arr[3], arr[4], arr[5], 0.0f}; return true; }
@@ -1955,16 +1853,13 @@ int td_graph_add_compressor(td_graph* g, const char* name, float gain, float ang
     if (!(release_ms >= 1.0f && release_ms <= 10000.0f)) return fail("compressor: release_ms must lie in [1, 10000] ms");
     if (!(knee_db >= 0.0f && knee_db <= 40.0f)) return fail("compressor: knee_db must lie in [0, 40] dB");
     if (!(makeup_db >= -40.0f && makeup_db <= 40.0f)) return fail("compressor: makeup_db must lie in [-40, 40] dB");
-    const int slot = new_slot(g);
-    Vertex& v = add_vertex(g, name, gain, angle, wet, K_COMPRESSOR);
+    Vertex& v = add_fx_vertex(g, name, gain, angle, wet, K_COMPRESSOR);
     v.threshold_db = threshold_db;
     v.ratio = ratio;
     v.attack_ms = attack_ms;
     v.release_ms = release_ms;
     v.knee_db = knee_db;
     v.makeup_db = makeup_db;
-    v.state_slot = slot;
-    g->hstate[slot].comp = {0.0, 0.0, {0, 0, 0, 0}};
     return 1;
 }
 
@@ -1979,14 +1874,11 @@ static int eq_check(int kind, size_t sr, float freq_hz, float q, float gain_db) 
 }
 int td_graph_add_eq(td_graph* g, const char* name, float gain, float angle, float wet, int kind, float freq_hz, float q, float gain_db) {
     if (!eq_check(kind, g->sr, freq_hz, q, gain_db)) return 0;
-    const int slot = new_slot(g);
-    Vertex& v = add_vertex(g, name, gain, angle, wet, K_EQ);
+    Vertex& v = add_fx_vertex(g, name, gain, angle, wet, K_EQ);
     v.eq_kind = kind;
     v.eq_freq = freq_hz;
     v.eq_q = q;
     v.eq_gain_db = eq::kind_has_gain(kind) ? gain_db : 0.0f;
-    v.state_slot = slot;
-    g->hstate[slot].eq = {0.0, 0.0, 0.0, 0.0};
     return 1;
 }
 int td_eq_coefficients(int kind, size_t sr, float freq_hz, float q, float gain_db, double out[6]) {
@@ -2008,7 +1900,7 @@ static int delay_check(size_t sr, float time_ms, float feedback, float cross) {
 }
 int td_graph_add_delay(td_graph* g, const char* name, float gain, float angle, float wet, float time_ms, float feedback, float cross) {
     if (!delay_check(g->sr, time_ms, feedback, cross)) return 0;
-    Vertex& v = add_vertex(g, name, gain, angle, wet, K_DELAY);
+    Vertex& v = add_fx_vertex(g, name, gain, angle, wet, K_DELAY);
     v.delay_ms = time_ms;
     v.delay_feedback = feedback;
     v.delay_cross = cross;
@@ -2034,7 +1926,7 @@ static int sat_check(int kind, int oversample, float drive_db, float bias, float
 int td_graph_add_saturator(td_graph* g, const char* name, float gain, float angle, float wet, int kind, float drive_db, float bias,
                            float out_db, int oversample) {
     if (!sat_check(kind, oversample, drive_db, bias, out_db)) return 0;
-    Vertex& v = add_vertex(g, name, gain, angle, wet, K_SATURATOR);
+    Vertex& v = add_fx_vertex(g, name, gain, angle, wet, K_SATURATOR);
     v.sat_kind = kind;
     v.sat_oversample = oversample;
     v.sat_drive_db = drive_db;
@@ -2061,7 +1953,7 @@ int td_saturator_params(int kind, int oversample, float drive_db, float bias, fl
 int td_graph_add_chorus(td_graph* g, const char* name, float gain, float angle, float wet, int voices, float delay_ms, float depth_ms,
                         float rate_hz, float stereo, int shape) {
     if (const char* why = chorus::check(g->sr, voices, delay_ms, depth_ms, rate_hz, stereo, shape)) return fail(std::string("chorus: ") + why);
-    Vertex& v = add_vertex(g, name, gain, angle, wet, K_CHORUS);
+    Vertex& v = add_fx_vertex(g, name, gain, angle, wet, K_CHORUS);
     v.chorus_voices = voices;
     v.chorus_shape = shape;
     v.chorus_delay_ms = delay_ms;
@@ -2081,7 +1973,7 @@ int td_chorus_params(size_t sr, int voices, float delay_ms, float depth_ms, floa
 // This engine's own reverb vertex (no reference counterpart; the definition is in include/termdaw_amd.h).
 int td_graph_add_reverb(td_graph* g, const char* name, float gain, float angle, float wet, float room, float damp, float width, float size) {
     if (const char* why = reverb::check(g->sr, room, damp, width, size)) return fail(std::string("reverb: ") + why);
-    Vertex& v = add_vertex(g, name, gain, angle, wet, K_REVERB);
+    Vertex& v = add_fx_vertex(g, name, gain, angle, wet, K_REVERB);
     v.reverb_room = room;
     v.reverb_damp = damp;
     v.reverb_width = width;
@@ -2100,16 +1992,14 @@ int td_reverb_params(size_t sr, float room, float damp, float width, float size,
 int td_graph_add_gate(td_graph* g, const char* name, float gain, float angle, float wet, float threshold_db, float hysteresis_db,
                       float hold_ms, float attack_ms, float release_ms, float range_db) {
     if (const char* why = gate::check(threshold_db, hysteresis_db, hold_ms, attack_ms, release_ms, range_db)) return fail(std::string("gate: ") + why);
-    const int slot = new_slot(g);
-    Vertex& v = add_vertex(g, name, gain, angle, wet, K_GATE);
+    Vertex& v = add_fx_vertex(g, name, gain, angle, wet, K_GATE);
     v.gate_threshold_db = threshold_db;
     v.gate_hysteresis_db = hysteresis_db;
     v.gate_hold_ms = hold_ms;
     v.gate_attack_ms = attack_ms;
     v.gate_release_ms = release_ms;
     v.gate_range_db = range_db;
-    v.state_slot = slot;
-    g->hstate[slot].gate = gate_closed(g, v);
+    fx_kind(K_GATE)->put_rest(g, v, &g->hstate[(size_t)v.state_slot]);   // (closed: it depends on the parameters)
     return 1;
 }
 int td_gate_params(size_t sr, float threshold_db, float hysteresis_db, float hold_ms, float attack_ms, float release_ms, float range_db,
@@ -2125,9 +2015,7 @@ int td_gate_params(size_t sr, float threshold_db, float hysteresis_db, float hol
 int td_graph_add_phaser(td_graph* g, const char* name, float gain, float angle, float wet, int stages, float lo_hz, float hi_hz,
                         float rate_hz, float feedback, float stereo, int shape) {
     if (const char* why = phaser::check(g->sr, stages, lo_hz, hi_hz, rate_hz, feedback, stereo, shape)) return fail(std::string("phaser: ") + why);
-    const int slot = new_slot(g);   // (a run of zeroed slots: tdk::PhaserState)
-    for (int i = 1; i < kPhaserSlots; ++i) new_slot(g);
-    Vertex& v = add_vertex(g, name, gain, angle, wet, K_PHASER);
+    Vertex& v = add_fx_vertex(g, name, gain, angle, wet, K_PHASER);   // (its slots: a tdk::PhaserState)
     v.phaser_stages = stages;
     v.phaser_shape = shape;
     v.phaser_lo_hz = lo_hz;
@@ -2135,7 +2023,6 @@ int td_graph_add_phaser(td_graph* g, const char* name, float gain, float angle, 
     v.phaser_rate_hz = rate_hz;
     v.phaser_feedback = feedback;
     v.phaser_stereo = stereo;
-    v.state_slot = slot;
     return 1;
 }
 int td_phaser_params(size_t sr, int stages, float lo_hz, float hi_hz, float rate_hz, float feedback, float stereo, int shape, double out[7]) {
@@ -2150,7 +2037,7 @@ int td_phaser_params(size_t sr, int stages, float lo_hz, float hi_hz, float rate
 int td_graph_add_vocoder(td_graph* g, const char* name, float gain, float angle, float wet, int bands, float lo_hz, float hi_hz, float q,
                          float response_ms, float out_db) {
     if (const char* why = vocoder::check(g->sr, bands, lo_hz, hi_hz, q, response_ms, out_db)) return fail(std::string("vocoder: ") + why);
-    Vertex& v = add_vertex(g, name, gain, angle, wet, K_VOCODER);
+    Vertex& v = add_fx_vertex(g, name, gain, angle, wet, K_VOCODER);
     v.voc_bands = bands;
     v.voc_lo_hz = lo_hz;
     v.voc_hi_hz = hi_hz;
@@ -2172,9 +2059,7 @@ int td_graph_add_filter(td_graph* g, const char* name, float gain, float angle, 
                         float lfo_oct, float rate_hz, float stereo, int shape, float env_oct, float sens_db, float attack_ms, float release_ms) {
     if (const char* why = filter::check(g->sr, kind, freq_hz, q, lfo_oct, rate_hz, stereo, shape, env_oct, sens_db, attack_ms, release_ms))
         return fail(std::string("filter: ") + why);
-    const int slot = new_slot(g);   // (a run of zeroed slots: tdk::FiltState)
-    for (int i = 1; i < kFiltSlots; ++i) new_slot(g);
-    Vertex& v = add_vertex(g, name, gain, angle, wet, K_FILTER);
+    Vertex& v = add_fx_vertex(g, name, gain, angle, wet, K_FILTER);   // (its slots: a tdk::FiltState)
     v.filt_kind = kind;
     v.filt_shape = shape;
     v.filt_freq_hz = freq_hz;
@@ -2186,7 +2071,6 @@ int td_graph_add_filter(td_graph* g, const char* name, float gain, float angle, 
     v.filt_sens_db = sens_db;
     v.filt_attack_ms = attack_ms;
     v.filt_release_ms = release_ms;
-    v.state_slot = slot;
     return 1;
 }
 int td_filter_params(size_t sr, int kind, float freq_hz, float q, float lfo_oct, float rate_hz, float stereo, int shape, float env_oct,
@@ -2226,7 +2110,8 @@ int td_graph_connect_key(td_graph* g, const char* a, const char* b) {
     if (ia == g->name_map.end()) return fail(std::string("TermDaw: warning: vertex \"") + a + "\" cannot be found and thus can't be connected.");
     if (ib == g->name_map.end()) return fail(std::string("TermDaw: warning: vertex \"") + b + "\" cannot be found and thus can't be connected to.");
     const size_t ai = ia->second, bi = ib->second;
-    if (g->vertices[bi].kind != K_COMPRESSOR && g->vertices[bi].kind != K_GATE && g->vertices[bi].kind != K_VOCODER && g->vertices[bi].kind != K_FILTER) return fail(std::string("connect_key: ") + b + " takes no key input");
+    const FxKind* fx = fx_kind(g->vertices[bi].kind);
+    if (!(fx && fx->takes_key)) return fail(std::string("connect_key: ") + b + " takes no key input");
     if (ai == bi) return fail("connect_key: self edge");
     if (has_loop(ai, bi, g)) return fail("connect_key: edge would close a loop");
     g->key_edges[bi].push_back(ai);

@@ -171,8 +171,8 @@ struct Vertex {
     std::vector<SineNote> sine_notes;
     std::vector<SynthNote> notes;
     Voice3 ap{0, 0, 0}, ag{0, 0, 0};
-    // carried device state slot (Normalize / BandPass / Compressor / Eq / Gate; a phaser: the first of kPhaserSlots consecutive
-    // ones, a tdk::PhaserState; a filter: the first of kFiltSlots, a tdk::FiltState), index into Graph::dstate
+    // carried device state slot (Normalize / BandPass; an effect kind: the first of its FxKind::state_slots consecutive ones,
+    // compile.h -- a phaser's hold a tdk::PhaserState, a filter's a tdk::FiltState), index into Graph::dstate
     int state_slot = -1;
     // reset_normalization (extensions.rs:295-299) is kept on the host until the next render consumes it
     bool first_pending = false;         // band-pass, compressor, eq, gate, phaser, filter, delay, saturator, chorus, reverb, vocoder (their state then restarts from zero): set_time since the vertex was last compiled into a submission (its descriptor's first_override)
@@ -196,12 +196,6 @@ union StateSlot {
     tdk::GateState gate;
 };
 static_assert(sizeof(StateSlot) == 32, "carried vertex state: one 32-byte slot");
-// a phaser vertex' 2 x (N + 1) doubles take a run of slots
-constexpr int kPhaserSlots = (int)(sizeof(tdk::PhaserState) / sizeof(StateSlot));
-static_assert(sizeof(tdk::PhaserState) == kPhaserSlots * sizeof(StateSlot), "a phaser vertex' state: whole slots");
-// ... and a filter vertex' six doubles
-constexpr int kFiltSlots = (int)(sizeof(tdk::FiltState) / sizeof(StateSlot));
-static_assert(sizeof(tdk::FiltState) == kFiltSlots * sizeof(StateSlot), "a filter vertex' state: whole slots");
 
 struct KernelTime { std::string name; float ms = 0; size_t launches = 0; };
 
