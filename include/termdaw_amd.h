@@ -502,6 +502,46 @@ int td_graph_add_filter(td_graph* g, const char* name, float gain, float angle, 
  * td_graph_add_filter. */
 int td_filter_params(size_t sr, int kind, float freq_hz, float q, float lfo_oct, float rate_hz, float stereo, int shape,
                      float env_oct, float sens_db, float attack_ms, float release_ms, double* out, size_t cap);
+/* A limiter vertex: a lookahead brickwall limiter -- THIS ENGINE'S OWN: no reference counterpart.  It is the
+ * limiter of td_graph_master (below) in causal form, inside the graph: on a bus, on a stem, in a block pull.  The vertex sums its
+ * inputs like every input vertex (sum_inputs, extensions.rs:310-319), processes the sum (l, r), mixes with `wet` by the
+ * reference's f32 lerp, then pan and gain like every vertex (extensions.rs:262-263).
+ *   Constants, f64, once on the host, each from the f32 parameter widened to f64 (td_limiter_params returns exactly these):
+ *     c = 10^(ceiling_db / 20);  gin = 10^(drive_db / 20);  L = max(1, llround(lookahead_ms sr / 1000)) frames;
+ *     a = exp(-1 / (release_ms sr / 1000)).
+ *   Per frame n, on the f32 summed input with no FMA contraction, in the order written.  Frames before the restart time (time 0,
+ *   or the last td_graph_set_time) count as 0:
+ *     1. s[n] = max(|l[n]|, |r[n]|) as f32 (exact); a frame with a NaN or an infinite sample has s = 0: it stays out of the state
+ *     2. Q[n] = max of s over [n - L + 1, n]                                  (f32, exact in any order)
+ *     3. d = gin (double)Q[n];  h[n] = c / d if d > c, else 1
+ *     4. u[n] = max(1 - h[n], a u[n-1]), u = 0 at the restart;  e[n] = 1 - u[n];  frames before the restart have e = 1
+ *     5. G[n] = (sum of e over [n - L + 1, n]) / (double)L
+ *     6. xd[n] = x[n - L + 1], the raw f32 input;  p = (float)(((double)xd gin) G[n]) per channel;
+ *        out = xd + wet * (p - xd) in f32 (adsr.rs:42); then pan and gain.
+ *   The engine forms the sum of step 5 as a difference of f64 prefix sums of e taken in a fixed order, so a render is bitwise
+ *   reproducible; it differs from the serial sum by rounding alone (DESIGN.md 3x gives the bound).
+ *   wet < 0.0001: the summed input passes through untouched and UNDELAYED (a plain k_sum launch) and the state stays as it is.
+ * Latency: the vertex delays its signal by L - 1 frames (td_limiter_params returns the figure).  Nothing compensates for it
+ * elsewhere in the graph -- the saturator's rule.  L = 1 is an instantaneous limiter with no latency.
+ * What the definition guarantees:
+ *   every e[j] in the window of frame n was formed from a Q[j] that contains frame n - L + 1, so gin |xd[n]| G[n] <= c: no
+ *   output sample of the wet path exceeds the ceiling, up to its one f32 rounding;
+ *   when nothing exceeds the ceiling G is exactly 1: the wet path is then the input times gin, delayed.
+ * State: zero at time 0.  u at the last frame, the last L - 1 raw input frames and the last L - 1 values of e (the engine keeps
+ * e itself, not the further input it could be rebuilt from); carried between consecutive block pulls and between the chunks of
+ * a render, restarted by td_graph_set_time / td_graph_change_time / td_graph_reset.
+ * Ranges, rejected with a td_last_error that names the parameter (NaN and the infinities included): ceiling_db [-24, 0];
+ * drive_db [-24, 24]; lookahead_ms [0, 50] and L <= 2048 frames (the error names lookahead_ms too); release_ms [1, 10000].
+ * `wet` is clamped to [0, 1].
+ * Under "band_mode" 2 / "sine_mode" 2 everything upstream of a limiter vertex that is not dry takes the exact forms: the gain
+ * depends on the signal, the compressor's case; vertices downstream are unaffected.  td_graph_connect_key refuses a limiter.
+ * Not part of the vertex: true-peak (oversampled) detection, which td_graph_master has; a key input; a gain-reduction read-out;
+ * latency compensation across the graph; a tail past the project's end (the last L - 1 input frames are not played out). */
+int td_graph_add_limiter(td_graph* g, const char* name, float gain, float angle, float wet, float ceiling_db, float lookahead_ms,
+                         float release_ms, float drive_db);
+/* Host only, no GPU: the limiter vertex' constants at rate sr, exactly the doubles the engine uses -- out[0 .. 4] = c, gin, L, a,
+ * latency (L - 1 frames).  The same range checks as td_graph_add_limiter. */
+int td_limiter_params(size_t sr, float ceiling_db, float lookahead_ms, float release_ms, float drive_db, double out[5]);
 int td_graph_connect(td_graph* g, const char* a, const char* b);          /* graph.rs:80-96 (+58-78) */
 /* A key edge (sidechain) from any vertex `a` to a compressor, gate, vocoder or filter vertex `b` -- THIS ENGINE'S OWN, like the
  * vertices.  A vocoder vertex takes its MODULATOR from the key frames defined here (td_graph_add_vocoder above), a filter vertex

@@ -83,6 +83,8 @@ SIGNATURES = {
     "td_vocoder_params": (_i32, [_sz, _i32, _f32, _f32, _f32, _f32, _f32, C.POINTER(C.c_double), _sz]),
     "td_graph_add_filter": (_i32, [_vp, _cp, _f32, _f32, _f32, _i32, _f32, _f32, _f32, _f32, _f32, _i32, _f32, _f32, _f32, _f32]),
     "td_filter_params": (_i32, [_sz, _i32, _f32, _f32, _f32, _f32, _f32, _i32, _f32, _f32, _f32, _f32, C.POINTER(C.c_double), _sz]),
+    "td_graph_add_limiter": (_i32, [_vp, _cp, _f32, _f32, _f32, _f32, _f32, _f32, _f32]),
+    "td_limiter_params": (_i32, [_sz, _f32, _f32, _f32, _f32, C.POINTER(C.c_double)]),
     "td_gate_params": (_i32, [_sz, _f32, _f32, _f32, _f32, _f32, _f32, C.POINTER(C.c_double)]),
     "td_reverb_params": (_i32, [_sz, _f32, _f32, _f32, _f32, C.POINTER(C.c_double)]),
     "td_graph_connect": (_i32, [_vp, _cp, _cp]),
@@ -393,6 +395,14 @@ def gate_params(sr, threshold_db, hysteresis_db, hold_ms, attack_ms, release_ms,
     return (out[0], out[1], int(out[2]), out[3], out[4], out[5])
 
 
+def limiter_params(sr, ceiling_db, lookahead_ms, release_ms, drive_db):
+    """(c, gin, L, a, latency): the limiter vertex' constants at rate sr, exactly the doubles the engine uses (host only; L and the
+    latency, L - 1 frames, as ints)."""
+    out = (C.c_double * 5)()
+    _check(lib().td_limiter_params(int(sr), ceiling_db, lookahead_ms, release_ms, drive_db, out))
+    return (out[0], out[1], int(out[2]), out[3], int(out[4]))
+
+
 def chorus_params(sr, voices, delay_ms, depth_ms, rate_hz, stereo, shape):
     """The chorus vertex' constants at rate sr (host only), exactly as the engine uses them: (D0, A, f, H, s, Hch) -- the centre
     delay and the depth in frames, the LFO's cycles per frame, the frames of the line, the largest delay slope, and the gain the
@@ -647,6 +657,11 @@ class Graph:
         its key edges (connect_key) feed the follower."""
         _check(lib().td_graph_add_filter(self.h, name.encode(), gain, angle, wet, filter_kind(kind), freq_hz, q, lfo_oct, rate_hz, stereo,
                                          chorus_shape(shape), env_oct, sens_db, attack_ms, release_ms))
+
+    def add_limiter(self, name, gain, angle, wet, ceiling_db, lookahead_ms, release_ms, drive_db):
+        """A limiter vertex: a lookahead brickwall limiter, L - 1 frames of latency (this engine's own; the definition is in
+        include/termdaw_amd.h)."""
+        _check(lib().td_graph_add_limiter(self.h, name.encode(), gain, angle, wet, ceiling_db, lookahead_ms, release_ms, drive_db))
 
     def connect(self, a, b):
         return bool(lib().td_graph_connect(self.h, a.encode(), b.encode()))

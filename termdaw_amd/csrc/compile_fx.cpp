@@ -1,5 +1,5 @@
 // compile_fx.cpp -- the effect kinds of the host compiler (compile.h FxKind / FxLevel): compressor, EQ, delay, saturator,
-// chorus, reverb, gate, phaser, vocoder, filter.  One table row per kind -- its chunk limit, the family its launches start at, the factor the guard
+// chorus, reverb, gate, phaser, vocoder, filter, limiter.  One table row per kind -- its chunk limit, the family its launches start at, the factor the guard
 // carries an estimate through it at, the state slots it carries and their state at time 0, whether it takes a key, whether its
 // kernels are linked -- one function per kind that lowers a level's vertices of that kind to descriptors and launches, and right
 // behind it the one that decodes such a launch and calls the kernels' entry points (kernels.h launch_*: the only calls out of the
@@ -11,6 +11,7 @@
 #include "eq_math.h"
 #include "filter_math.h"
 #include "gate_math.h"
+#include "limiter_math.h"
 #include "phaser_math.h"
 #include "reverb_math.h"
 #include "sat_math.h"
@@ -33,7 +34,7 @@ float2* FxLevel::tmp_buffer() {
 
 namespace fxk {   // (compile.cpp includes this file: what is only used here keeps a scope of its own)
 
-// A delay, saturator, chorus, reverb or vocoder vertex enters a chunk of M frames: a set_time since the vertex last ran is consumed here
+// A delay, saturator, chorus, reverb, vocoder or limiter vertex enters a chunk of M frames: a set_time since the vertex last ran is consumed here
 // (the block restarts from zero, like an EQ's state), the books move on behind the chunk -- `alternates`: the launch writes the other
 // half of the line, which the next one reads.  Returns the frames run up to the chunk (Vertex::Line::total as the chunk finds it).
 static uint64_t enter_chunk(Vertex& v, size_t M, bool alternates) {
@@ -752,6 +753,71 @@ static void launch_filter(const Launch& L, const void* d, hipStream_t s) {
     }
 }
 
+// ---- limiter: three launches, or one (kernels.h LimDesc) ----
+static int lower_limiter(FxLevel& L, std::vector<size_t>& vs) {
+    td_graph* g = L.g;
+    const uint32_t n_tiles = (uint32_t)((L.M + kLimTile - 1) / kLimTile), chunk = (n_tiles + kThreads - 1) / kThreads;
+    const bool multi = n_tiles > 1u;   // (multi: k_lim_detect and k_master_carry first)
+    std::vector<LimDesc> d;
+    std::vector<MasterDesc> c1;
+    for (size_t vi : vs) {
+        Vertex& v = g->vertices[vi];
+        double c[limiter::kParams];
+        limiter::params(L.sr, v.lim_ceiling_db, v.lim_lookahead_ms, v.lim_release_ms, v.lim_drive_db, c);
+        if (!(c[2] <= limiter::kMaxL)) return fail("limiter: lookahead_ms is too many frames at this sample rate");
+        LimDesc x{};
+        if (multi) {
+            if (!(x.x = L.tmp_buffer())) return 0;
+            if (!(x.q = reinterpret_cast<float*>(L.tmp_buffer()))) return 0;   // (an edge buffer holds two floats per frame)
+        }
+        L.head(x, vi);
+        x.L = (uint32_t)c[2];
+        x.line = (double*)take_line(g, v, (size_t)4 * x.L * sizeof(double));
+        if (!x.line) return fail("termdaw_amd: out of device memory for a limiter vertex' line");
+        x.parity = v.line.parity;
+        x.fresh = enter_chunk(v, L.M, true) ? 0u : 1u;   // (afresh: the state is that of time 0, the half is not read)
+        x.n_tiles = n_tiles;
+        x.c = c[0];
+        x.gin = c[1];
+        x.a = c[3];
+        for (int j = 0; j < 8; ++j) x.pw[j] = pow(x.a, (double)kLimRun * (double)(1u << j));
+        d.push_back(x);
+        if (!multi) continue;
+        MasterDesc y{};
+        y.n_tiles = n_tiles;
+        y.chunk = chunk;
+        for (int j = 0; j < 8; ++j) y.pwc[j] = pow(x.a, (double)kLimTile * (double)chunk * (double)(1u << j));
+        y.a_tile = pow(x.a, (double)kLimTile);
+        if (!x.fresh) y.init = x.line + (size_t)x.parity * 2u * x.L;   // (word 0 of the half this chunk reads: u)
+        c1.push_back(y);
+    }
+    const size_t off = L.put(d, vs);
+    if (!multi) {
+        L.add_launch(F_LIM_APPLY, off, (int)vs.size(), lim_aux(n_tiles, true));
+        return 1;
+    }
+    const size_t o1 = L.cb.st->put(c1);
+    for (size_t i = 0; i < vs.size(); ++i) {
+        const size_t o = off + i * sizeof(LimDesc), m = o1 + i * sizeof(MasterDesc), tb = (size_t)n_tiles * sizeof(double);
+        const size_t a1 = L.cb.scratch(tb), k1 = L.cb.scratch(tb);
+        L.cb.scratch_field(o, offsetof(LimDesc, agg), a1);
+        L.cb.scratch_field(o, offsetof(LimDesc, carry), k1);
+        L.cb.scratch_field(m, offsetof(MasterDesc, agg), a1);
+        L.cb.scratch_field(m, offsetof(MasterDesc, carry), k1);
+    }
+    L.add_launch(F_LIM_DETECT, off, (int)vs.size(), lim_aux(n_tiles, false));
+    L.add_launch(F_LIM_CARRY, o1, (int)vs.size(), 0u);
+    L.add_launch(F_LIM_APPLY, off, (int)vs.size(), lim_aux(n_tiles, false));
+    return 1;
+}
+static void launch_limiter(const Launch& L, const void* d, hipStream_t s) {
+    switch (L.fam) {
+        case F_LIM_DETECT: launch_lim_detect((const LimDesc*)d, L.n, lim_aux_tiles(L.aux), s); break;
+        case F_LIM_CARRY: launch_master_carry((const MasterDesc*)d, L.n, s); break;
+        case F_LIM_APPLY: launch_lim_apply((const LimDesc*)d, L.n, lim_aux_tiles(L.aux), (L.aux & kLimSingleBit) != 0u, s); break;
+    }
+}
+
 // ---- the table ----
 // fits: the largest chunk the kind's kernels index (32-bit frames; the line kinds keep room for their look-back, the tiled
 // ones for the tile count packed into a launch's aux)
@@ -779,6 +845,8 @@ static double through_phaser(const Vertex& v, size_t) { return dry(v) ? 1.0 : kN
 static double through_vocoder(const Vertex& v, size_t) { return dry(v) ? 1.0 : kNoStaticGain; }
 // a filter's resonance gain depends on the signal through e[n], and on the time: no static bound of it is proven
 static double through_filter(const Vertex& v, size_t) { return dry(v) ? 1.0 : kNoStaticGain; }
+// a limiter's gain follows the signal's peaks: no static gain -- the compressor's case, unless it is dry
+static double through_limiter(const Vertex& v, size_t) { return dry(v) ? 1.0 : kNoStaticGain; }
 // an EQ is linear and time-invariant: Hmax of its biquad
 static double through_eq(const Vertex& v, size_t sr) {
     if (dry(v)) return 1.0;
@@ -819,10 +887,10 @@ static_assert(sizeof(PhaserState) == kPhaserSlots * sizeof(StateSlot) && sizeof(
 // the rows cover the effect families of `Family` without gap or overlap as long as they stand in its order.  built / keyed_built:
 // the entry points the kind's `launch` calls are linked (kernels.h declares them weak); the filter's keyed forms are instantiations
 // behind the entry points of its unkeyed ones.
-constexpr int kFxKinds = 10;
+constexpr int kFxKinds = 11;
 static_assert(F_COMP_DETECT < F_EQ_LOCAL && F_EQ_LOCAL < F_DELAY_LOCAL && F_DELAY_LOCAL < F_SAT_SUM && F_SAT_SUM < F_CHORUS_SUM &&
               F_CHORUS_SUM < F_REVERB_SUM && F_REVERB_SUM < F_GATE_DETECT && F_GATE_DETECT < F_PHASER_LOCAL && F_PHASER_LOCAL < F_VOC_LOCAL &&
-              F_VOC_LOCAL < F_FILT_DETECT && F_FILT_DETECT < F_COUNT,
+              F_VOC_LOCAL < F_FILT_DETECT && F_FILT_DETECT < F_LIM_DETECT && F_LIM_DETECT < F_COUNT,
               "the rows of the effect kinds' table stand in the order of their families");
 static const FxKind* table() {
     static const FxKind rows[kFxKinds] = {
@@ -835,7 +903,8 @@ static const FxKind* table() {
         {K_GATE, "gate", "gate", F_GATE_DETECT, F_PHASER_LOCAL - F_GATE_DETECT, sizeof(GateDesc), 1, true, fits_scan, nullptr, through_gate, lower_gate, launch_gate, launch_gate_detect && launch_gate_carry && launch_gate_env && launch_gate_apply, launch_gate_detect_keyed && launch_gate_env_keyed, "compressor / gate", rest_gate},
         {K_PHASER, "phaser", "phaser", F_PHASER_LOCAL, F_VOC_LOCAL - F_PHASER_LOCAL, sizeof(PhaserDesc), kPhaserSlots, false, fits_scan, nullptr, through_phaser, lower_phaser, launch_phaser, launch_phaser_local && launch_phaser_carry && launch_phaser_apply, true, nullptr, nullptr},
         {K_VOCODER, "vocoder", "voc", F_VOC_LOCAL, F_FILT_DETECT - F_VOC_LOCAL, sizeof(VocDesc), 0, true, fits_voc, nullptr, through_vocoder, lower_vocoder, launch_vocoder, launch_voc_local && launch_voc_carry && launch_voc_env && launch_voc_apply, launch_voc_local_keyed && launch_voc_apply_keyed, "vocoder", nullptr},
-        {K_FILTER, "filter", "filt", F_FILT_DETECT, F_COUNT - F_FILT_DETECT, sizeof(FiltDesc), kFiltSlots, true, fits_scan, nullptr, through_filter, lower_filter, launch_filter, launch_filt_detect && launch_filt_env && launch_filt_local && launch_filt_carry && launch_filt_apply && launch_master_carry, true, nullptr, nullptr},
+        {K_FILTER, "filter", "filt", F_FILT_DETECT, F_LIM_DETECT - F_FILT_DETECT, sizeof(FiltDesc), kFiltSlots, true, fits_scan, nullptr, through_filter, lower_filter, launch_filter, launch_filt_detect && launch_filt_env && launch_filt_local && launch_filt_carry && launch_filt_apply && launch_master_carry, true, nullptr, nullptr},
+        {K_LIMITER, "limiter", "lim", F_LIM_DETECT, F_COUNT - F_LIM_DETECT, sizeof(LimDesc), 0, false, fits_scan, nullptr, through_limiter, lower_limiter, launch_limiter, launch_lim_detect && launch_lim_apply && launch_master_carry, true, nullptr, nullptr},
     };
     return rows;
 }

@@ -14,6 +14,7 @@
 #include "phaser_math.h"
 #include "vocoder_math.h"
 #include "filter_math.h"
+#include "limiter_math.h"
 #include "comm.h"
 #include "compile.h"
 #include "delay_math.h"
@@ -571,7 +572,7 @@ int ensure_buffers(td_graph* g, size_t frames) {
     g->free_bufs = g->pool;
     return 1;
 }
-// The block a delay, saturator, chorus, reverb or vocoder vertex carries (Vertex::line): allocated when the vertex is first compiled into a
+// The block a delay, saturator, chorus, reverb, vocoder or limiter vertex carries (Vertex::line): allocated when the vertex is first compiled into a
 // submission (never cleared: a word is read only once the vertex has written it, Line::total), freed with the graph's vertices.
 void* take_line(td_graph* g, Vertex& v, size_t bytes) {
     if (v.line.d) return v.line.d;
@@ -2080,6 +2081,25 @@ int td_filter_params(size_t sr, int kind, float freq_hz, float q, float lfo_oct,
         return fail(std::string("filter: ") + why);
     if (cap < (size_t)filter::kParams) return fail("filter_params: out holds fewer than 11 doubles");
     filter::params(sr, kind, freq_hz, q, lfo_oct, rate_hz, stereo, shape, env_oct, sens_db, attack_ms, release_ms, out);
+    return 1;
+}
+
+// This engine's own limiter vertex (no reference counterpart; the definition is in include/termdaw_amd.h).  Its state is a
+// carried line (u, and the e and the raw input of the last L - 1 frames), allocated when the vertex is first compiled into a submission.
+int td_graph_add_limiter(td_graph* g, const char* name, float gain, float angle, float wet, float ceiling_db, float lookahead_ms,
+                         float release_ms, float drive_db) {
+    if (const char* why = limiter::check(g->sr, ceiling_db, lookahead_ms, release_ms, drive_db)) return fail(std::string("limiter: ") + why);
+    Vertex& v = add_fx_vertex(g, name, gain, angle, wet, K_LIMITER);
+    v.lim_ceiling_db = ceiling_db;
+    v.lim_lookahead_ms = lookahead_ms;
+    v.lim_release_ms = release_ms;
+    v.lim_drive_db = drive_db;
+    return 1;
+}
+int td_limiter_params(size_t sr, float ceiling_db, float lookahead_ms, float release_ms, float drive_db, double out[5]) {
+    if (!out) return fail("limiter_params: out is null");
+    if (const char* why = limiter::check(sr, ceiling_db, lookahead_ms, release_ms, drive_db)) return fail(std::string("limiter: ") + why);
+    limiter::params(sr, ceiling_db, lookahead_ms, release_ms, drive_db, out);
     return 1;
 }
 

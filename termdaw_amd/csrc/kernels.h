@@ -469,6 +469,45 @@ struct FiltDesc {
     uint32_t key_k, key_term_mode;
 };
 
+// A limiter vertex (k_lim_detect / k_master_carry / k_lim_apply; the definition is in include/termdaw_amd.h at
+// td_graph_add_limiter): the mastering pass' lookahead limiter in causal form.  The compressor's tiling: tiles of kLimTile frames,
+// a lane owns kLimRun consecutive frames; L <= kLimTile, so a tile's halo of L - 1 frames lies within the tile before it -- or,
+// for the chunk's first tile, in the carried line.
+//   k_lim_detect evaluates the tile's input terms into `x`, forms s over the tile and its halo in LDS (the halo's terms are
+//   evaluated a second time for s alone; tile 0 reads the line's frames), the window maximum Q by doubling, stores Q as f32 in `q`
+//   and leaves the tile's zero-start end value of the release u = max(1 - h, a u) in agg[t].  k_master_carry (op 0, init the
+//   line's u) leaves the u entering each tile in carry[t].  k_lim_apply rebuilds u and e = 1 - u over the tile BEFORE its own from
+//   carry[t - 1] (tile 0: reads the line's e) and over its own from carry[t], forms the prefix sums PS of e from frame t0 - L + 1
+//   on in lane order, G[n] = (PS[n] - PS[n - L]) / L, reads xd[n] = x[n - L + 1] from `x` or the line and writes lerp(xd,
+//   (float)((xd gin) G), wet), pan, gain to `out`.  The workgroup of the chunk's last tile stores the next state.
+//   When one tile covers the chunk (every block pull) k_lim_apply runs alone (kLimSingleBit): all of the above in one workgroup,
+//   x and s in LDS (x, q, agg, carry unused).
+// The line: two halves of 2 L doubles, read at `parity`, written at `parity ^ 1` (no workgroup writes what another of the same
+// launch reads).  A half holds what the next chunk needs of the frames before it: word 0 the u of the last frame, words
+// 2 .. L the e of the last L - 1 frames, oldest first, words L + 1 .. 2 L - 1 their raw input frames as float2.  Frames before
+// the restart are x = 0, e = 1, written out like any other, so a half is always whole; `fresh` (the first chunk since the
+// restart): the read half is not read at all.
+constexpr uint32_t kLimRun = 8;                    // frames per lane
+constexpr uint32_t kLimTile = kLimRun * kThreads;  // frames per workgroup
+struct LimDesc {
+    const InTerm* ins;      // k input terms (kinds 0 .. 4), in connect() order
+    float2* x;              // [frames] the summed input (multi-tile form)
+    float* q;               // [frames] Q (multi-tile form)
+    float2* out;
+    double* line;           // the carried line, 4 L doubles
+    double* agg;            // [n_tiles] each tile's zero-start end value of u
+    double* carry;          // [n_tiles] the u entering each tile
+    uint32_t k, term_mode, frames, n_tiles;
+    uint32_t L;             // the lookahead window, frames (1 .. kLimTile)
+    uint32_t parity;        // the half this launch reads
+    uint32_t fresh;         // 1: the state is that of time 0 (u = 0; the frames before are x = 0, e = 1)
+    float wet;
+    double c, gin;          // ceiling and drive, linear
+    double a;               // the release coefficient
+    double pw[8];           // a^(kLimRun 2^k)
+    PanGain pg;
+};
+
 // A parametric EQ vertex (k_eq_local / k_eq_carry / k_eq_apply; the definition is in include/termdaw_amd.h at
 // td_graph_add_eq): one RBJ biquad per channel in transposed direct form II, f64.  With z = (s1, s2) the recurrence is
 // z[n] = A z[n-1] + c x[n],  A = [[-a1, 1], [-a2, 0]],  c = (b1 - a1 b0, b2 - a2 b0),  y[n] = b0 x[n] + s1[n-1]: an affine scan
@@ -1155,6 +1194,14 @@ __attribute__((weak)) void launch_filt_env(const FiltDesc* d, int n_desc, uint32
 __attribute__((weak)) void launch_filt_local(const FiltDesc* d, int n_desc, uint32_t n_tiles, hipStream_t s);
 __attribute__((weak)) void launch_filt_carry(const FiltDesc* d, int n_desc, hipStream_t s);
 __attribute__((weak)) void launch_filt_apply(const FiltDesc* d, int n_desc, uint32_t n_tiles, bool single, bool keyed, hipStream_t s);
+// Weak for the same reason: a level's limiter vertices, grid.x = n_tiles (every descriptor's).  F_LIM_APPLY's aux packs the tile
+// count and `single` (the one-launch form of a one-tile chunk: term loop, detector, release and window mean inside).  The carry in
+// between is launch_master_carry's, over MasterDesc.
+constexpr uint32_t kLimSingleBit = 0x40000000u;
+inline uint32_t lim_aux(uint32_t n_tiles, bool single) { return n_tiles | (single ? kLimSingleBit : 0u); }
+inline uint32_t lim_aux_tiles(uint32_t aux) { return aux & 0xFFFFFFu; }
+__attribute__((weak)) void launch_lim_detect(const LimDesc* d, int n_desc, uint32_t n_tiles, hipStream_t s);
+__attribute__((weak)) void launch_lim_apply(const LimDesc* d, int n_desc, uint32_t n_tiles, bool single, hipStream_t s);
 // Weak for the same reason: a level's reverb vertices.  launch_reverb_sum: grid.x from `frames`; launch_reverb: one workgroup per
 // descriptor, `form` 0 the serial walk of each comb's one-pole, 1 the wave scan.
 __attribute__((weak)) void launch_reverb_sum(const ReverbDesc* d, int n_desc, uint32_t frames, hipStream_t s);

@@ -7318,6 +7318,271 @@ __global__ __launch_bounds__(kThreads) void k_filt_apply(const FiltDesc* __restr
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// k_lim_detect / k_lim_apply: the limiter vertex (kernels.h LimDesc).  No reference counterpart; the definition is
+// the header's (td_graph_add_limiter): the mastering pass' window maximum, release and window mean in causal form, the halo read
+// across the chunk boundary out of the carried line.
+// ------------------------------------------------------------------------------------------------
+// step 1's s[n]: a frame with a NaN or an infinity stays out of the state
+TD_DEV float lim_level(float2 x) {
+    const float al = fabsf(x.x), ar = fabsf(x.y);
+    if (!(al <= 3.402823466e38f && ar <= 3.402823466e38f)) return 0.f;
+    return fmaxf(al, ar);
+}
+// steps 3 and 4's 1 - h[n] for one held detector value
+TD_DEV double lim_omh(const LimDesc& d, float Q) {
+    const double v = d.gin * (double)Q;
+    return v > d.c ? 1.0 - d.c / v : 0.0;
+}
+// the line's halves: word 0 u, words 2 .. L the halo's e, words L + 1 .. 2 L - 1 the halo's raw frames
+TD_DEV double* lim_half(const LimDesc& d, uint32_t parity) { return d.line + (size_t)parity * 2u * d.L; }
+TD_DEV float2* lim_half_x(double* half, uint32_t L) { return reinterpret_cast<float2*>(half + 1u + L); }
+// sp[0 .. kLimTile + L - 1): s of the frames from L - 1 before the tile on (the caller has joined the lanes behind the fill).  Q of
+// the lane's run: tile frame j takes max sp[j .. j + L - 1] -- r_k[i] = max sp[i .. i + 2^k - 1] by doubling, then two of them
+TD_DEV void lim_window_max(float* sp, uint32_t L, float (&Q)[kLimRun]) {
+    const uint32_t tid = threadIdx.x, n = kLimTile + L - 1u;
+    uint32_t k2 = 0;
+    while ((2u << k2) <= L) ++k2;
+    for (uint32_t j = 0; j < k2; ++j) {
+        const uint32_t s = 1u << j;
+        float r[2 * kLimRun];
+#pragma unroll
+        for (uint32_t k = 0; k < 2 * kLimRun; ++k) {
+            const uint32_t i = tid + k * kThreads;
+            r[k] = i + s < n ? fmaxf(sp[i], sp[i + s]) : (i < n ? sp[i] : 0.f);
+        }
+        __syncthreads();
+#pragma unroll
+        for (uint32_t k = 0; k < 2 * kLimRun; ++k) {
+            const uint32_t i = tid + k * kThreads;
+            if (i < n) sp[i] = r[k];
+        }
+        __syncthreads();
+    }
+    const uint32_t sh = L - (1u << k2);
+#pragma unroll
+    for (uint32_t k = 0; k < kLimRun; ++k) {
+        const uint32_t j = tid * kLimRun + k;
+        Q[k] = fmaxf(sp[j], sp[j + sh]);
+    }
+}
+// the lane's kLimRun values of Q out of `q` (0 from `frames` on)
+TD_DEV void lim_load_q(const float* q, uint32_t M, uint32_t f0, float (&Q)[kLimRun]) {
+    if (f0 + kLimRun <= M) {
+        const float4 a = gload4(q + f0), b = gload4(q + f0 + 4);
+        Q[0] = a.x; Q[1] = a.y; Q[2] = a.z; Q[3] = a.w; Q[4] = b.x; Q[5] = b.y; Q[6] = b.z; Q[7] = b.w;
+    } else {
+#pragma unroll
+        for (uint32_t k = 0; k < kLimRun; ++k) Q[k] = f0 + k < M ? gload1(q + f0 + k) : 0.f;
+    }
+}
+// the release over one tile entered at cin: 1 - h of the lane's run in, u per frame out
+TD_DEV void lim_release(const LimDesc& d, double (&y)[kLimRun], double cin, double* sv) {
+    const double a = d.a;
+    double u = threadIdx.x ? 0.0 : cin, last;
+#pragma unroll
+    for (uint32_t k = 0; k < kLimRun; ++k) u = fmax(y[k], a * u);
+    u = comp_lane_scan<false>(u, d.pw, cin, sv, &last);
+#pragma unroll
+    for (uint32_t k = 0; k < kLimRun; ++k) {
+        u = fmax(y[k], a * u);
+        y[k] = u;
+    }
+}
+// PS[j] = sum of e over (s0, j] for the lane's run from frame fa on, a round behind `running`: the lane's own sums, the lanes'
+// totals scanned in lane order, then running + the lanes before + the lane's own.  PS[s0 + 1 .. s0 + kLimTile - 1] stay in lag.
+TD_DEV void lim_prefix(const double (&e)[kLimRun], int64_t fa, int64_t s0, double& running, double* sv, double* lag, double (&ps)[kLimRun]) {
+    const uint32_t tid = threadIdx.x;
+    double acc = 0.0;
+#pragma unroll
+    for (uint32_t k = 0; k < kLimRun; ++k) {
+        if (fa + k > s0) acc += e[k];
+        ps[k] = acc;
+    }
+    double v = acc;
+#pragma unroll 1
+    for (uint32_t off = 1; off < kThreads; off <<= 1) {
+        sv[tid] = v;
+        __syncthreads();
+        if (tid >= off) v = sv[tid - off] + v;
+        __syncthreads();
+    }
+    sv[tid] = v;
+    __syncthreads();
+    const double before = running + (tid ? sv[tid - 1] : 0.0);
+    running = running + sv[kThreads - 1];
+#pragma unroll
+    for (uint32_t k = 0; k < kLimRun; ++k) {
+        ps[k] = before + ps[k];
+        const int64_t j = fa + k;
+        if (j > s0 && j < s0 + (int64_t)kLimTile) lag[j - s0] = ps[k];
+    }
+    __syncthreads();
+}
+__global__ __launch_bounds__(kThreads) void k_lim_detect(const LimDesc* __restrict__ descs) {
+    const LimDesc& d = descs[blockIdx.y];
+    if (blockIdx.x >= d.n_tiles) return;
+    __shared__ float sp[2 * kLimTile];
+    __shared__ double sv[kThreads];
+    const uint32_t tid = threadIdx.x, M = d.frames, L = d.L, H = L - 1u, t0 = blockIdx.x * kLimTile, f0 = t0 + tid * kLimRun;
+    float2 x[kLimRun];
+    filt_sum_run(d.ins, d.k, d.term_mode, M, f0, x);
+    filt_store_x(d.x, M, f0, x);
+#pragma unroll
+    for (uint32_t k = 0; k < kLimRun; ++k) sp[H + tid * kLimRun + k] = lim_level(x[k]);
+    if (blockIdx.x == 0u) {   // the halo lies before the chunk: the line's frames (none after a restart)
+        const float2* hx = lim_half_x(lim_half(d, d.parity), L);
+        for (uint32_t i = tid; i < H; i += kThreads) sp[i] = d.fresh ? 0.f : lim_level(gload2(hx + i));
+    } else {   // the halo is the end of the tile before: its terms once more, for s alone (aligned frame pairs, two per call)
+        const uint32_t hs = t0 - H, hs_e = hs & ~1u, none = (M + 1u) & ~1u;
+        for (uint32_t p = tid; hs_e + 2u * p < t0; p += 2u * kThreads) {
+            const uint32_t m0 = hs_e + 2u * p, m1c = m0 + 2u * kThreads, m1 = m1c < t0 ? m1c : none;
+            float4 a0, a1;
+            sum_inputs_pairs(d.ins, d.k, d.term_mode, m0, m1, M, a0, a1);
+            if (m0 >= hs) sp[m0 - hs] = lim_level(make_float2(a0.x, a0.y));
+            sp[m0 + 1u - hs] = lim_level(make_float2(a0.z, a0.w));
+            if (m1c < t0) {
+                sp[m1c - hs] = lim_level(make_float2(a1.x, a1.y));
+                sp[m1c + 1u - hs] = lim_level(make_float2(a1.z, a1.w));
+            }
+        }
+    }
+    __syncthreads();
+    float Q[kLimRun];
+    lim_window_max(sp, L, Q);
+    if (f0 + kLimRun <= M) {
+        gstore4(d.q + f0, make_float4(Q[0], Q[1], Q[2], Q[3]));
+        gstore4(d.q + f0 + 4, make_float4(Q[4], Q[5], Q[6], Q[7]));
+    } else {
+#pragma unroll
+        for (uint32_t k = 0; k < kLimRun; ++k)
+            if (f0 + k < M) d.q[f0 + k] = Q[k];
+    }
+    const double a = d.a;
+    double u = 0.0, last;
+#pragma unroll
+    for (uint32_t k = 0; k < kLimRun; ++k) u = fmax(f0 + k < M ? lim_omh(d, Q[k]) : 0.0, a * u);
+    (void)comp_lane_scan<false>(u, d.pw, 0.0, sv, &last);
+    if (tid == 0) d.agg[blockIdx.x] = last;
+}
+// SINGLE: one tile covers the chunk (every block pull) -- the term loop, s, Q and the release run here, x and s in LDS, entered
+// with the line's u; otherwise Q comes out of `q`, the u entering a tile out of carry[], xd out of `x`.
+template <bool SINGLE>
+__global__ __launch_bounds__(kThreads) void k_lim_apply(const LimDesc* __restrict__ descs) {
+    const LimDesc& d = descs[blockIdx.y];
+    const uint32_t tile = blockIdx.x;
+    if (tile >= d.n_tiles) return;
+    __shared__ __attribute__((aligned(16))) char buf[kLimTile * sizeof(double)];   // float sp[2 T] (SINGLE: s, until Q is formed), then double lag[T]
+    __shared__ float2 xs[SINGLE ? 2 * kLimTile : 1];                               // SINGLE: index i = chunk frame i - (L - 1)
+    __shared__ double sv[kThreads];
+    float* sp = reinterpret_cast<float*>(buf);
+    double* lag = reinterpret_cast<double*>(buf);
+    const uint32_t tid = threadIdx.x, M = d.frames, L = d.L, H = L - 1u, t0 = tile * kLimTile, f0 = t0 + tid * kLimRun;
+    const bool fresh = d.fresh != 0u, last_tile = tile + 1u == d.n_tiles;
+    double* lr = lim_half(d, d.parity);
+    double* lw = lim_half(d, d.parity ^ 1u);
+    const float2* lrx = lim_half_x(lr, L);
+    float2* lwx = lim_half_x(lw, L);
+    const double gin = d.gin, Ld = (double)L;
+    const float wet = d.wet;
+    float Q[kLimRun];
+    if (SINGLE) {
+        float2 x[kLimRun];
+        filt_sum_run(d.ins, d.k, d.term_mode, M, f0, x);
+#pragma unroll
+        for (uint32_t k = 0; k < kLimRun; ++k) {
+            xs[H + tid * kLimRun + k] = x[k];
+            sp[H + tid * kLimRun + k] = lim_level(x[k]);
+        }
+        for (uint32_t i = tid; i < H; i += kThreads) {
+            const float2 v = fresh ? make_float2(0.f, 0.f) : gload2(lrx + i);
+            xs[i] = v;
+            sp[i] = lim_level(v);
+        }
+        __syncthreads();
+        lim_window_max(sp, L, Q);
+        __syncthreads();   // (sp is dead from here: lag takes its place)
+    } else {
+        lim_load_q(d.q, M, f0, Q);
+    }
+    // ---- the next state's frames, by the workgroup that owns the chunk's end: word i of the halo is chunk frame lo + i -- out of
+    // the chunk, or, where the chunk is shorter than the halo, out of the half this launch reads (e of a chunk frame: below)
+    const int64_t lo = (int64_t)M - (int64_t)H;
+    if (last_tile) {
+        for (uint32_t i = tid; i < H; i += kThreads) {
+            const int64_t j = lo + (int64_t)i;
+            float2 v;
+            if (j >= 0) {
+                v = SINGLE ? xs[(uint32_t)j + H] : gload2(d.x + j);
+            } else {
+                v = fresh ? make_float2(0.f, 0.f) : gload2(lrx + (i + M));
+                gstored(lw + 2u + i, fresh ? 1.0 : gloadd(lr + 2u + i + M));
+            }
+            gstore2(lwx + i, v);
+        }
+    }
+    // ---- PS[j] = sum of e over (s0, j]; G[n] = (PS[n] - PS[n - L]) / L.  Round A: the tile before this one (tile 0: the line's
+    // e), round B: this one.
+    const int64_t s0 = (int64_t)t0 - (int64_t)L;
+    double running = 0.0, y[kLimRun], ps[kLimRun];
+    if (H) {
+        const int64_t fa = (int64_t)t0 - (int64_t)kLimTile + (int64_t)(tid * kLimRun);
+        if (tile == 0u) {
+#pragma unroll
+            for (uint32_t k = 0; k < kLimRun; ++k) {
+                const int64_t j = fa + k;
+                y[k] = j > s0 ? (fresh ? 1.0 : gloadd(lr + 2 + (j + (int64_t)H))) : 0.0;
+            }
+        } else {   // (a whole tile of the chunk)
+            float Qa[kLimRun];
+            lim_load_q(d.q, M, (uint32_t)fa, Qa);
+#pragma unroll
+            for (uint32_t k = 0; k < kLimRun; ++k) y[k] = lim_omh(d, Qa[k]);
+            lim_release(d, y, d.carry[tile - 1u], sv);
+#pragma unroll
+            for (uint32_t k = 0; k < kLimRun; ++k) {
+                y[k] = 1.0 - y[k];
+                const int64_t j = fa + k;
+                if (last_tile && j >= lo) gstored(lw + 2 + (j - lo), y[k]);
+            }
+        }
+        lim_prefix(y, fa, s0, running, sv, lag, ps);
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < kLimRun; ++k) y[k] = f0 + k < M ? lim_omh(d, Q[k]) : 0.0;
+    lim_release(d, y, SINGLE ? (fresh ? 0.0 : gloadd(lr)) : d.carry[tile], sv);
+#pragma unroll
+    for (uint32_t k = 0; k < kLimRun; ++k) {
+        if (f0 + k + 1u == M) gstored(lw, y[k]);   // the chunk's last frame: the u the next chunk / block pull enters with
+        y[k] = 1.0 - y[k];
+        const int64_t j = (int64_t)f0 + k;
+        if (last_tile && j >= lo && j < (int64_t)M) gstored(lw + 2 + (j - lo), y[k]);
+    }
+    lim_prefix(y, (int64_t)f0, s0, running, sv, lag, ps);
+#pragma unroll
+    for (uint32_t h = 0; h < kLimRun / 2; ++h) {
+        const uint32_t m = f0 + 2u * h;
+        if (m >= M) break;
+        float2 xd[2];
+        double G[2];
+#pragma unroll
+        for (uint32_t c = 0; c < 2; ++c) {
+            const uint32_t n = m + c, i = n - t0;
+            const double back = i == 0u ? 0.0 : lag[i];
+            G[c] = fmax(0.0, (ps[2 * h + c] - back) / Ld);
+            if (SINGLE) xd[c] = xs[n];
+            else if (n >= H) xd[c] = gload2(d.x + (n - H));
+            else xd[c] = fresh ? make_float2(0.f, 0.f) : gload2(lrx + n);
+        }
+        const float4 p = make_float4((float)(((double)xd[0].x * gin) * G[0]), (float)(((double)xd[0].y * gin) * G[0]),
+                                     (float)(((double)xd[1].x * gin) * G[1]), (float)(((double)xd[1].y * gin) * G[1]));
+        // the reference's lerp (adsr.rs:42), f32
+        const float4 o = make_float4(xd[0].x + wet * (p.x - xd[0].x), xd[0].y + wet * (p.y - xd[0].y), xd[1].x + wet * (p.z - xd[1].x),
+                                     xd[1].y + wet * (p.w - xd[1].y));
+        store_pair(d.out, m, M, zero_tail(epilogue4(o, d.pg), m, M));
+    }
+}
+
 constexpr int kMaxGridY = 65535;
 
 // Batched launches put the vertex index in grid.y (limit 65535): larger batches go out in slices.
@@ -7745,6 +8010,17 @@ void launch_filt_apply(const FiltDesc* d, int n, uint32_t n_tiles, bool single, 
         if (!single) hipLaunchKernelGGL((k_filt_apply<false, false>), grid, dim3(kThreads), 0, s, d + o);
         else if (keyed) hipLaunchKernelGGL((k_filt_apply<true, true>), grid, dim3(kThreads), 0, s, d + o);
         else hipLaunchKernelGGL((k_filt_apply<true, false>), grid, dim3(kThreads), 0, s, d + o);
+    }
+}
+void launch_lim_detect(const LimDesc* d, int n, uint32_t n_tiles, hipStream_t s) {
+    for (int o = 0; o < n && n_tiles; o += kMaxGridY)
+        hipLaunchKernelGGL(k_lim_detect, dim3(n_tiles, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
+}
+void launch_lim_apply(const LimDesc* d, int n, uint32_t n_tiles, bool single, hipStream_t s) {
+    for (int o = 0; o < n && n_tiles; o += kMaxGridY) {
+        const dim3 grid(n_tiles, std::min(n - o, kMaxGridY));
+        if (single) hipLaunchKernelGGL(k_lim_apply<true>, grid, dim3(kThreads), 0, s, d + o);
+        else hipLaunchKernelGGL(k_lim_apply<false>, grid, dim3(kThreads), 0, s, d + o);
     }
 }
 void launch_sample_loop(const LoopDesc* d, int n, uint32_t frames, hipStream_t s) {

@@ -24,6 +24,7 @@
 #include "phaser_math.h"
 #include "vocoder_math.h"
 #include "filter_math.h"
+#include "limiter_math.h"
 #include "lua_subset.h"
 #include "reverb_math.h"
 #include "master.h"
@@ -118,6 +119,7 @@ struct ReverbCall { std::string name; float gain, angle, wet, room, damp, width,
 struct PhaserCall { std::string name; float gain, angle, wet; int stages; float lo_hz, hi_hz, rate_hz, feedback, stereo; int shape; };
 struct VocoderCall { std::string name; float gain, angle, wet; int bands; float lo_hz, hi_hz, q, response_ms, out_db; };
 struct FilterCall { std::string name; float gain, angle, wet; int kind; float freq_hz, q, lfo_oct, rate_hz, stereo; int shape; float env_oct, sens_db, attack_ms, release_ms; };
+struct LimiterCall { std::string name; float gain, angle, wet, ceiling_db, lookahead_ms, release_ms, drive_db; };
 struct GateCall { std::string name; float gain, angle, wet, threshold_db, hysteresis_db, hold_ms, attack_ms, release_ms, range_db; };
 struct SatCall { std::string name; float gain, angle, wet; int kind; float drive_db, bias, out_db; int oversample; };
 
@@ -245,6 +247,7 @@ int do_refresh(td_state* s, const std::string& contents) {
     std::vector<PhaserCall> phasers;
     std::vector<VocoderCall> vocoders;
     std::vector<FilterCall> filters;
+    std::vector<LimiterCall> limiters;
     size_t cs = s->cs, render_sr = s->render_sr, bd = s->bd;
     // std::mem::take (state.rs:79-80): the locals start from the previous values, the State's own fields are left
     // EMPTY until the script has run (state.rs:169-170) -- so they stay empty when the script fails
@@ -535,6 +538,16 @@ int do_refresh(td_state* s, const std::string& contents) {
                 fnum(c.release_ms) + ")\n";
         return Value::nil();
     });
+    lua.set_function("add_limiter", [&](const std::vector<Value>& a) {   // this engine's own vertex (termdaw_amd.h td_graph_add_limiter)
+        const char* f = "add_limiter";
+        limiters.push_back({to_str(f, a, 0), to_f32(f, a, 1), to_f32(f, a, 2), to_f32(f, a, 3), to_f32(f, a, 4), to_f32(f, a, 5), to_f32(f, a, 6), to_f32(f, a, 7)});
+        auto& c = limiters.back();
+        // (out-of-range parameters are rejected here, where the line is known)
+        if (const char* why = tde::limiter::check(psr, c.ceiling_db, c.lookahead_ms, c.release_ms, c.drive_db)) throw LuaError{std::string("add_limiter: ") + why};
+        dump += std::string(f) + "(\"" + c.name + "\"," + fnum(c.gain) + "," + fnum(c.angle) + "," + fnum(c.wet) + "," + fnum(c.ceiling_db) + "," + fnum(c.lookahead_ms) + "," +
+                fnum(c.release_ms) + "," + fnum(c.drive_db) + ")\n";
+        return Value::nil();
+    });
     lua.set_function("connect", [&](const std::vector<Value>& a) {
         edges.push_back({to_str("connect", a, 0), to_str("connect", a, 1)});
         dump += "connect(\"" + edges.back().first + "\",\"" + edges.back().second + "\")\n";
@@ -675,6 +688,8 @@ int do_refresh(td_state* s, const std::string& contents) {
     for (auto& c : filters)
         if (!td_graph_add_filter(s->g, c.name.c_str(), c.gain, c.angle, c.wet, c.kind, c.freq_hz, c.q, c.lfo_oct, c.rate_hz, c.stereo, c.shape, c.env_oct, c.sens_db,
                                  c.attack_ms, c.release_ms)) return 0;
+    for (auto& c : limiters)
+        if (!td_graph_add_limiter(s->g, c.name.c_str(), c.gain, c.angle, c.wet, c.ceiling_db, c.lookahead_ms, c.release_ms, c.drive_db)) return 0;
     for (auto& e : edges) td_graph_connect(s->g, e.first.c_str(), e.second.c_str());   // failures only warn (state.rs:459)
     for (auto& e : key_edges) td_graph_connect_key(s->g, e.first.c_str(), e.second.c_str());   // (after the edges; failures only warn, like theirs)
     td_graph_set_output(s->g, s->output_vertex.c_str());

@@ -169,7 +169,7 @@ class ProjectScript:
         self.calls = {k: [] for k in (
             "load_sample", "load_resource", "load_midi_floww", "add_sum", "add_normalize", "add_sampleloop",
             "add_sample_multi", "add_sample_lerp", "add_debug_sine", "add_synth", "add_sampsyn", "add_adsr",
-            "add_bandpass", "add_compressor", "add_eq", "add_delay", "add_saturator", "add_chorus", "add_reverb", "add_gate", "add_phaser", "add_vocoder", "add_filter", "connect", "connect_key")}
+            "add_bandpass", "add_compressor", "add_eq", "add_delay", "add_saturator", "add_chorus", "add_reverb", "add_gate", "add_phaser", "add_vocoder", "add_filter", "add_limiter", "connect", "connect_key")}
         self.resources = {}                 # path -> bytes (load_resource)
         self.script_order = []              # (fn, args) in call order, for to_lua()
 
@@ -280,6 +280,10 @@ class ProjectScript:
         """This engine's own vertex (include/termdaw_amd.h td_graph_add_filter): no reference counterpart.  kind, shape: the string names."""
         self._rec("add_filter", name, gain, angle, wet, kind, freq_hz, q, lfo_oct, rate_hz, stereo, shape, env_oct, sens_db, attack_ms, release_ms)
 
+    def add_limiter(self, name, gain, angle, wet, ceiling_db, lookahead_ms, release_ms, drive_db):
+        """This engine's own vertex (include/termdaw_amd.h td_graph_add_limiter): no reference counterpart."""
+        self._rec("add_limiter", name, gain, angle, wet, ceiling_db, lookahead_ms, release_ms, drive_db)
+
     def connect(self, a, b):
         self._rec("connect", a, b)
 
@@ -359,6 +363,8 @@ class ProjectScript:
             g.add_vocoder(*args)
         for args in self.calls["add_filter"]:
             g.add_filter(*args)
+        for args in self.calls["add_limiter"]:
+            g.add_limiter(*args)
         for a, b in self.calls["connect"]:
             g.connect(a, b)
         for a, b in self.calls["connect_key"]:   # (after the connect calls, as the front-end applies them)
@@ -584,6 +590,16 @@ def synth_project(seconds=3.0, bl=1024, voices=5):
     p.connect("mix", "cut")
     p.connect("cut", "sum")
     p.set_output("sum")
+    return p
+
+
+def limiter_project(seconds=3.0, bl=1024, ceiling_db=-1.0, lookahead_ms=5.0, release_ms=80.0, drive_db=12.0, wet=1.0):
+    """The drum project's bus driven into a limiter (a limiter vertex, this engine's own): `drive_db` of gain into a brickwall
+    ceiling, in place of the project's Normalize."""
+    p = drum_project(seconds, bl)
+    p.add_limiter("lim", 1.0, 0.0, wet, ceiling_db, lookahead_ms, release_ms, drive_db)
+    p.connect("band", "lim")
+    p.set_output("lim")
     return p
 
 

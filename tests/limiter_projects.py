@@ -1,0 +1,116 @@
+"""Projects that contain limiter vertices (TEST INFRASTRUCTURE, a generator of its own: the generators the existing tests and
+soaks draw from keep producing the graphs they always did).
+
+* base_project / grid_cases / E: the inputs, the parameter grid and the bound's constant that tests/test_gpu_limiter.py (on the
+  device) and tests/test_limiter_host.py (the derivation of E, on the CPU) share.  The inputs are the gate's three: eq_projects'
+  drums and noise, and gate_projects' `gated` (noise at a constant level per segment: loud stretches, quiet ones, and steps
+  between them that a lookahead has to ramp into).
+* random_limiter_project / write_projects: a project of tests/test_gpu_fuzz.py's generator with one to three limiter vertices
+  spliced into edges it already has, and, now and then, one more as the output (the sanitizer run's input)."""
+import itertools
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import eq_projects as EP  # noqa: E402
+import gate_projects as GP  # noqa: E402
+
+RATES = GP.RATES
+INPUTS = GP.INPUTS
+SECONDS = 0.25   # at least 5 tiles at every rate
+# The GPU test's bound, per value: |p' - p| <= 2^-23 |p| + E max|p|.  E_EMULATED is the worst max|blocked - serial| / max|serial|
+# of p before its f32 rounding that np_limiter.blocked() -- the kernels' lane runs, carries and prefix sums in numpy -- shows
+# against the serial twin over grid_cases() on the three inputs at the three rates, rounded up (test_limiter_host.py recomputes it
+# and fails above this figure); the device's own order of the same float64 operations gets the project's factor 8 on top.  The
+# largest figures come from L = 1 and 2, where G is a difference of two prefix sums hundreds of times its size, at the grid's
+# deepest reduction.  E must stay <= 2^-28, the EQ's cap.
+E_EMULATED = 4e-11
+E = 8.0 * E_EMULATED
+assert E <= 2.0 ** -28
+
+RELEASES = (1.0, 50.0, 1000.0)
+LEVELS = ((-6.0, 12.0), (-0.1, 0.0), (-24.0, 24.0))   # (ceiling_db, drive_db)
+
+
+def windows(sr):
+    """The grid's L: 1, 2, about 1 ms, about 10 ms, exactly 2 048 frames."""
+    return (1, 2, int(round(sr / 1000.0)), int(round(sr / 100.0)), 2048)
+
+
+def lookahead_ms(sr, L):
+    """A lookahead_ms (as the f32 the engine gets) whose window is L frames at rate sr; 0 for L = 1."""
+    return 0.0 if L == 1 else float(np.float32(L * 1000.0 / sr))
+
+
+def grid_cases(sr):
+    """(ceiling_db, lookahead_ms, release_ms, drive_db): the issue's grid, 45 cases, with the L each one means."""
+    return [((ce, lookahead_ms(sr, L), re, dr), L) for L, re, (ce, dr) in itertools.product(windows(sr), RELEASES, LEVELS)]
+
+
+def base_project(kind, sr=48000, bl=1024, seconds=SECONDS, seed=0):
+    """Sources -> Sum `bus` (the vertex in front of the limiter vertices under test)."""
+    return GP.base_project(kind, sr=sr, bl=bl, seconds=seconds, seed=seed)
+
+
+def add_limiter(p, name, src, case, wet=1.0, gain=1.0, angle=0.0):
+    p.add_limiter(name, gain, angle, wet, *case)
+    p.connect(src, name)
+
+
+def oracle_input(kind, sr):
+    """The grid's input as the GPU test sees it: the second render of `bus` (the first leaves the sample_multi voices sounding),
+    here by the CPU oracle -- the engine's own render is the oracle's, bit for bit."""
+    from oracle import binding as oracle
+    p = base_project(kind, sr=sr)
+    sb, fb, g = p.build(oracle)
+    g.render_all(sb, fb, p.cs, 16)
+    fb.set_time(0)
+    g.set_time(0)
+    g.reset_normalize_vertices()
+    return g.render_all(sb, fb, p.cs, 16)[1]
+
+
+def random_limiter_params(rng, sr):
+    L = int(rng.choice([1, 2, 48, 480, 2048]))
+    return (float(rng.choice([1.0, 1.0, 0.5, 0.0])),                 # wet
+            float(rng.choice([-24.0, -6.0, -0.1, 0.0])),              # ceiling_db
+            lookahead_ms(sr, L),                                      # lookahead_ms
+            float(rng.choice([1.0, 50.0, 1000.0, 10000.0])),          # release_ms
+            float(rng.choice([-24.0, 0.0, 12.0, 24.0])))              # drive_db
+
+
+def random_limiter_project(seed, allow_sinf=True):
+    import test_gpu_fuzz as F
+    p = F.random_project(seed, allow_sinf=allow_sinf)
+    rng = np.random.default_rng(990_000 + seed)
+    gains, angles = [1.0, 1.0005, 0.5, 1.7, -0.8], [0.0, 0.0009, 30.0, -75.0, 120.0]
+    edges = [i for i, (fn, a) in enumerate(p.script_order) if fn == "connect" and a[0] != a[1]]
+    picks = sorted(set(int(i) for i in rng.choice(edges, size=min(len(edges), int(rng.integers(1, 4))), replace=False)), reverse=True)
+    first_add = min(i for i, (fn, _) in enumerate(p.script_order) if fn.startswith("add_"))
+    lims = []
+    for k, i in enumerate(picks):   # (from the back: the indices in front stay valid)
+        a, b = p.script_order[i][1]
+        nm = "lm%d" % k
+        ci = p.calls["connect"].index((a, b))
+        p.calls["connect"][ci:ci + 1] = [(a, nm), (nm, b)]
+        p.script_order[i:i + 1] = [("connect", (a, nm)), ("connect", (nm, b))]
+        lims.append((nm, float(rng.choice(gains)), float(rng.choice(angles))) + random_limiter_params(rng, p.psr))
+    if rng.random() < 0.3:   # ... and one as the output, behind whatever the output was
+        nm = "lmout"
+        lims.append((nm, 1.0, 0.0) + random_limiter_params(rng, p.psr))
+        p.calls["connect"].append((p.output_vertex, nm))
+        oi = max(i for i, (fn, _) in enumerate(p.script_order) if fn == "set_output")
+        p.script_order[oi:oi + 1] = [("connect", (p.output_vertex, nm)), ("set_output", (nm,))]
+        p.output_vertex = nm
+    for c in lims:
+        p.calls["add_limiter"].append(c)
+        p.script_order.insert(first_add, ("add_limiter", c))
+    return p
+
+
+def write_projects(args):
+    """(base dir, seeds) -> the project dirs written: project.lua + assets, meta.txt (the block length)."""
+    base, seeds = args
+    return [EP.write_project(random_limiter_project(seed), os.path.join(base, "s%d" % seed)) for seed in seeds]
