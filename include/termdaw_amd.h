@@ -542,6 +542,45 @@ int td_graph_add_limiter(td_graph* g, const char* name, float gain, float angle,
 /* Host only, no GPU: the limiter vertex' constants at rate sr, exactly the doubles the engine uses -- out[0 .. 4] = c, gin, L, a,
  * latency (L - 1 frames).  The same range checks as td_graph_add_limiter. */
 int td_limiter_params(size_t sr, float ceiling_db, float lookahead_ms, float release_ms, float drive_db, double out[5]);
+/* A multiband vertex: a three-way Linkwitz-Riley crossover into three band compressors -- THIS ENGINE'S OWN: no reference
+ * counterpart (the reference reaches it only through LV2 plugins, add_lv2fx, which this engine parses and drops).
+ * With one band working it is a de-esser.  The vertex sums its inputs like every input vertex (sum_inputs,
+ * extensions.rs:310-319); everything below is f64 on the f32 summed input (l, r), per channel, with no FMA contraction, in the
+ * order written.  Bands are in the order low, mid, high (b = 0, 1, 2) wherever three values stand together.
+ *   1. Coefficients, f64, once on the host, from the f32 parameters widened to f64 (td_multiband_params returns them); Q =
+ *      sqrt(0.5) throughout.  L1 and H1: the RBJ low-pass and high-pass (td_graph_add_eq's TD_EQ_LOWPASS / TD_EQ_HIGHPASS formulas)
+ *      at lo_hz; L2 and H2: those at hi_hz; A2: the RBJ all-pass at hi_hz, b = (1 - alpha, -2 cos w0, 1 + alpha) / (1 + alpha)
+ *      with the same a1 and a2 as L2.  aR = exp(-1 / (release_ms sr / 1000)), aA likewise from attack_ms (0 for attack_ms = 0).
+ *   2. Crossover: Linkwitz-Riley, 24 dB per octave.  Every section is td_graph_add_eq's transposed direct form II in its
+ *      operation order, y = b0 u + s1;  s1 = (b1 u - a1 y) + s2;  s2 = b2 u - a2 y, with a state (s1, s2) of its own:
+ *        low = A2(L1(L1(x)));  rest = H1(H1(x));  mid = L2(L2(rest));  high = H2(H2(rest))
+ *      -- nine biquads per channel, in that order.  A non-finite input sample enters as 0 (the EQ's rule) and reaches the output
+ *      through the dry leg of the lerp only.  A2 on the low band makes low + mid + high an all-pass of x.
+ *   3. Per band b, td_graph_add_compressor's steps 1 - 4 with the band's own T_b = threshold_db[b], R_b = ratio[b], M_b =
+ *      makeup_db[b] and the shared knee W, aA and aR, on the level s_b[n] = max(|l_b[n]|, |r_b[n]|) of the f64 band signals
+ *      (zero or not finite: d_b = 0):  d_b from 20 log10 s_b - T_b;  y1_b = max(d_b, aR y1_b);  yL_b = aA yL_b + (1 - aA) y1_b;
+ *      G_b = 10^((M_b - yL_b) / 20).
+ *   4. p = (float)(((0.0 + low G_0) + mid G_1) + high G_2) per channel, rounded once; out = x + wet * (p - x) in f32
+ *      (adsr.rs:42); then pan and gain.
+ *   wet < 0.0001: the summed input passes through untouched (a plain k_sum launch) and the state stays as it is.
+ * State: 42 doubles -- (s1, s2) of the 18 biquads and (y1, yL) of the three bands -- zero at time 0; carried between consecutive
+ * block pulls and between the chunks of a render, restarted from zero by td_graph_set_time / td_graph_change_time /
+ * td_graph_reset.  No latency, no tail.  No key input: td_graph_connect_key refuses a multiband ("takes no key input").
+ * Ranges, rejected with a td_last_error that names the parameter and starts "multiband:" (NaN fails every comparison):
+ * lo_hz >= 40; hi_hz <= 0.45 sr; hi_hz >= 2 lo_hz; per band threshold_db [-60, 0]; and the compressor's own for ratio [1, 1000],
+ * attack_ms [0, 1000], release_ms [1, 10000], knee_db [0, 40], makeup_db [-40, 40].  `wet` is clamped to [0, 1].
+ * Under "band_mode" 2 / "sine_mode" 2 everything upstream of a multiband vertex that is not dry takes the exact forms: the gains
+ * depend on the signal, the compressor's case; vertices downstream are unaffected.
+ * Not part of the vertex: a key input; more than three bands, or two; per-band attack / release / knee; linear-phase
+ * crossovers; lookahead. */
+int td_graph_add_multiband(td_graph* g, const char* name, float gain, float angle, float wet, float lo_hz, float hi_hz,
+                           const float threshold_db[3], const float ratio[3], float attack_ms, float release_ms, float knee_db,
+                           const float makeup_db[3]);
+/* Host only, no GPU: the multiband vertex' constants at rate sr, exactly the doubles the engine uses -- out[5 s .. 5 s + 4] = (b0,
+ * b1, b2, a1, a2) of set s = L1, H1, L2, H2, A2, then out[25] = aA, out[26] = aR.  `n`: the doubles `out` holds, at least 27.  The
+ * same range checks as td_graph_add_multiband. */
+int td_multiband_params(size_t sr, float lo_hz, float hi_hz, const float threshold_db[3], const float ratio[3], float attack_ms,
+                        float release_ms, float knee_db, const float makeup_db[3], double* out, size_t n);
 int td_graph_connect(td_graph* g, const char* a, const char* b);          /* graph.rs:80-96 (+58-78) */
 /* A key edge (sidechain) from any vertex `a` to a compressor, gate, vocoder or filter vertex `b` -- THIS ENGINE'S OWN, like the
  * vertices.  A vocoder vertex takes its MODULATOR from the key frames defined here (td_graph_add_vocoder above), a filter vertex

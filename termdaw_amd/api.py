@@ -85,6 +85,8 @@ SIGNATURES = {
     "td_filter_params": (_i32, [_sz, _i32, _f32, _f32, _f32, _f32, _f32, _i32, _f32, _f32, _f32, _f32, C.POINTER(C.c_double), _sz]),
     "td_graph_add_limiter": (_i32, [_vp, _cp, _f32, _f32, _f32, _f32, _f32, _f32, _f32]),
     "td_limiter_params": (_i32, [_sz, _f32, _f32, _f32, _f32, C.POINTER(C.c_double)]),
+    "td_graph_add_multiband": (_i32, [_vp, _cp, _f32, _f32, _f32, _f32, _f32, C.POINTER(C.c_float), C.POINTER(C.c_float), _f32, _f32, _f32, C.POINTER(C.c_float)]),
+    "td_multiband_params": (_i32, [_sz, _f32, _f32, C.POINTER(C.c_float), C.POINTER(C.c_float), _f32, _f32, _f32, C.POINTER(C.c_float), C.POINTER(C.c_double), _sz]),
     "td_gate_params": (_i32, [_sz, _f32, _f32, _f32, _f32, _f32, _f32, C.POINTER(C.c_double)]),
     "td_reverb_params": (_i32, [_sz, _f32, _f32, _f32, _f32, C.POINTER(C.c_double)]),
     "td_graph_connect": (_i32, [_vp, _cp, _cp]),
@@ -395,6 +397,22 @@ def gate_params(sr, threshold_db, hysteresis_db, hold_ms, attack_ms, release_ms,
     return (out[0], out[1], int(out[2]), out[3], out[4], out[5])
 
 
+def _f3(v):
+    """Three floats for a per-band parameter (low, mid, high)."""
+    v = tuple(v)
+    if len(v) != 3:
+        raise ValueError("a multiband vertex takes three values per band parameter")
+    return (C.c_float * 3)(*v)
+
+
+def multiband_params(sr, lo_hz, hi_hz, threshold_db, ratio, attack_ms, release_ms, knee_db, makeup_db):
+    """(sets, aA, aR): the multiband vertex' constants at rate sr, exactly the doubles the engine uses (host only) -- sets[s] = (b0, b1,
+    b2, a1, a2) for s = L1, H1, L2, H2, A2."""
+    out = (C.c_double * 27)()
+    _check(lib().td_multiband_params(int(sr), lo_hz, hi_hz, _f3(threshold_db), _f3(ratio), attack_ms, release_ms, knee_db, _f3(makeup_db), out, 27))
+    return [tuple(out[5 * s:5 * s + 5]) for s in range(5)], out[25], out[26]
+
+
 def limiter_params(sr, ceiling_db, lookahead_ms, release_ms, drive_db):
     """(c, gin, L, a, latency): the limiter vertex' constants at rate sr, exactly the doubles the engine uses (host only; L and the
     latency, L - 1 frames, as ints)."""
@@ -662,6 +680,12 @@ class Graph:
         """A limiter vertex: a lookahead brickwall limiter, L - 1 frames of latency (this engine's own; the definition is in
         include/termdaw_amd.h)."""
         _check(lib().td_graph_add_limiter(self.h, name.encode(), gain, angle, wet, ceiling_db, lookahead_ms, release_ms, drive_db))
+
+    def add_multiband(self, name, gain, angle, wet, lo_hz, hi_hz, threshold_db, ratio, attack_ms, release_ms, knee_db, makeup_db):
+        """A multiband vertex: a three-way Linkwitz-Riley crossover into three band compressors (this engine's own; the definition is
+        in include/termdaw_amd.h).  threshold_db, ratio and makeup_db: three values each, for the low, mid and high band."""
+        _check(lib().td_graph_add_multiband(self.h, name.encode(), gain, angle, wet, lo_hz, hi_hz, _f3(threshold_db), _f3(ratio), attack_ms,
+                                            release_ms, knee_db, _f3(makeup_db)))
 
     def connect(self, a, b):
         return bool(lib().td_graph_connect(self.h, a.encode(), b.encode()))

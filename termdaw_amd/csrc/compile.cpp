@@ -3,7 +3,7 @@
 // this file calls the HIP runtime: device memory reaches it as addresses handed out by three functions of engine.cpp
 // (compile.h: take_buffer / ensure_buffers for edge buffers, upload_tables for a vertex' event tables), everything it
 // writes goes into the plain-memory staging arena of the ChunkBuild (offsets + fix-up lists that submit_chunk patches once
-// the device addresses are known).  The effect kinds (compressor .. limiter) are lowered by compile_fx.cpp, through the table there;
+// the device addresses are known).  The effect kinds (compressor .. multiband) are lowered by compile_fx.cpp, through the table there;
 // that file is included at the end of this one (see there).  tests/test_compile_asan.py builds it with g++
 // -fsanitize=address,undefined.
 #include "compile.h"
@@ -34,7 +34,8 @@ const char* const kFamilyName[F_COUNT] = {"k_sample_loop", "k_sample_multi", "k_
                                            "k_phaser_local", "k_phaser_carry", "k_phaser_apply",
                                            "k_voc_local", "k_voc_carry_z", "k_voc_env", "k_voc_carry_env", "k_voc_apply",
                                            "k_filt_detect", "k_filt_carry_y1", "k_filt_env", "k_filt_carry_e", "k_filt_local", "k_filt_carry", "k_filt_apply",
-                                           "k_lim_detect", "k_lim_carry", "k_lim_apply"};
+                                           "k_lim_detect", "k_lim_carry", "k_lim_apply",
+                                           "k_mb_local", "k_mb_carry", "k_mb_detect", "k_mb_carry_y1", "k_mb_env", "k_mb_carry_yl", "k_mb_apply"};
 
 
 // ------------------------------------------------------------------------------------------------
@@ -2377,7 +2378,10 @@ size_t desc_size(int fam) {
         case F_COMP_CARRY2:
         case F_FILT_CARRY1:
         case F_FILT_CARRY2:
-        case F_LIM_CARRY: return sizeof(MasterDesc);   // (k_master_carry, inside the compressor's, the filter's and the limiter's families)
+        case F_LIM_CARRY:
+        case F_MB_CARRY1:
+        case F_MB_CARRY2: return sizeof(MasterDesc);   // (k_master_carry, inside the compressor's, the filter's, the limiter's and the multiband's families)
+        case F_MB_ENV: return sizeof(CompDesc);   // (k_comp_env over a multiband vertex' three bands)
         default: {
             const FxKind* fx = fx_of_family(fam);
             return fx ? fx->desc_bytes : 0;

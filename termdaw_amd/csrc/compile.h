@@ -25,6 +25,7 @@ enum Family { F_LOOP, F_MULTI, F_LERP, F_SINE, F_SYNTH, F_SAMPSYN, F_ENV, F_PROB
               F_VOC_LOCAL, F_VOC_CARRY, F_VOC_ENV, F_VOC_CARRY_ENV, F_VOC_APPLY /* a level's vocoder vertices, per band count and keyed or not: k_voc_local, k_voc_carry (the biquads' states entering each tile), k_voc_env, k_voc_carry (the followers'), all four over multi-tile chunks only, k_voc_apply -- in this order */,
               F_FILT_DETECT, F_FILT_CARRY1, F_FILT_ENV, F_FILT_CARRY2, F_FILT_LOCAL, F_FILT_CARRY, F_FILT_APPLY /* a level's filter vertices: k_filt_detect, k_master_carry (y1), k_filt_env, k_master_carry (e) -- these four over the vertices whose follower runs -- k_filt_local, k_filt_carry, all six over multi-tile chunks only, k_filt_apply -- in this order */,
               F_LIM_DETECT, F_LIM_CARRY, F_LIM_APPLY /* a level's limiter vertices: k_lim_detect, k_master_carry (the u entering each tile), both over multi-tile chunks only, k_lim_apply -- in this order */,
+              F_MB_LOCAL, F_MB_CARRY, F_MB_DETECT, F_MB_CARRY1, F_MB_ENV, F_MB_CARRY2, F_MB_APPLY /* a level's multiband vertices: k_mb_local, k_mb_carry (the crossover's states entering each tile), k_mb_detect, k_master_carry (y1 of the three bands), k_comp_env (over the bands), k_master_carry (yL), all six over multi-tile chunks only, k_mb_apply -- in this order */,
               F_COUNT };
 extern const char* const kFamilyName[F_COUNT];
 
@@ -41,7 +42,7 @@ bool is_delay_family(int fam);
 double ms_between(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b);
 tdk::PanGain make_pg(float gain, float angle);           // a vertex' pan / gain as its kernel's epilogue applies it (sample.rs:98-109)
 
-// ---- compile_fx.cpp: the effect kinds (compressor, EQ, delay, saturator, chorus, reverb, gate, phaser, vocoder, filter, limiter) ----
+// ---- compile_fx.cpp: the effect kinds (compressor, EQ, delay, saturator, chorus, reverb, gate, phaser, vocoder, filter, limiter, multiband) ----
 // What lowering the vertices of one effect kind at one level needs of compile_chunk, and the steps every kind's lowering
 // shares.  The kinds' own functions (lower_comp ..) keep what is theirs: coefficients, tiling, scratch, launches.
 struct FxLevel {
@@ -107,7 +108,7 @@ struct FxKind {
     const char* k;          // as in "this build has no k_<k> kernels"
     int first_family;       // the kind's families are [first_family, first_family + n_families)
     int n_families;
-    size_t desc_bytes;      // of the descriptors its launches take (the compressor's and the filter's two carries and the limiter's one aside: MasterDesc)
+    size_t desc_bytes;      // of the descriptors its launches take (the compressor's, the filter's and the multiband's two carries and the limiter's one aside: MasterDesc; the multiband's F_MB_ENV: CompDesc)
     int state_slots;        // the consecutive StateSlots of td_graph::dstate a vertex carries from Vertex::state_slot on; 0: a Vertex::line, or nothing
     bool takes_key;         // td_graph_connect_key may end at a vertex of this kind
     bool (*fits)(const td_graph* g, const Vertex& v, size_t M);   // a chunk of M frames is within the kernels' index ranges
@@ -134,7 +135,7 @@ const FxKind* fx_of_family(int fam);    // nullptr: not an effect kind's family 
 // ---- engine.cpp: the device memory the compiler hands out addresses of ----
 int upload_tables(td_graph* g, TableCache& tc, const Staging& tmp);   // a vertex' event tables -> its device buffer (queued on the graph's stream)
 int ensure_buffers(td_graph* g, size_t frames);                      // the edge-buffer pool holds buffers of >= frames frames; all of them free
-void* take_line(td_graph* g, tde::Vertex& v, size_t bytes);   // the block a delay, saturator, chorus, reverb, vocoder or limiter vertex carries (Vertex::line), allocated on first use (nullptr: out of device memory)
+void* take_line(td_graph* g, tde::Vertex& v, size_t bytes);   // the block a delay, saturator, chorus, reverb, vocoder, limiter or multiband vertex carries (Vertex::line), allocated on first use (nullptr: out of device memory)
 float2* take_buffer(td_graph* g);                                    // one edge buffer (nullptr: out of device memory)
 
 }  // namespace tde

@@ -1,5 +1,5 @@
 // compile_fx.cpp -- the effect kinds of the host compiler (compile.h FxKind / FxLevel): compressor, EQ, delay, saturator,
-// chorus, reverb, gate, phaser, vocoder, filter, limiter.  One table row per kind -- its chunk limit, the family its launches start at, the factor the guard
+// chorus, reverb, gate, phaser, vocoder, filter, limiter, multiband.  One table row per kind -- its chunk limit, the family its launches start at, the factor the guard
 // carries an estimate through it at, the state slots it carries and their state at time 0, whether it takes a key, whether its
 // kernels are linked -- one function per kind that lowers a level's vertices of that kind to descriptors and launches, and right
 // behind it the one that decodes such a launch and calls the kernels' entry points (kernels.h launch_*: the only calls out of the
@@ -12,6 +12,7 @@
 #include "filter_math.h"
 #include "gate_math.h"
 #include "limiter_math.h"
+#include "multiband_math.h"
 #include "phaser_math.h"
 #include "reverb_math.h"
 #include "sat_math.h"
@@ -34,7 +35,7 @@ float2* FxLevel::tmp_buffer() {
 
 namespace fxk {   // (compile.cpp includes this file: what is only used here keeps a scope of its own)
 
-// A delay, saturator, chorus, reverb, vocoder or limiter vertex enters a chunk of M frames: a set_time since the vertex last ran is consumed here
+// A delay, saturator, chorus, reverb, vocoder, limiter or multiband vertex enters a chunk of M frames: a set_time since the vertex last ran is consumed here
 // (the block restarts from zero, like an EQ's state), the books move on behind the chunk -- `alternates`: the launch writes the other
 // half of the line, which the next one reads.  Returns the frames run up to the chunk (Vertex::Line::total as the chunk finds it).
 static uint64_t enter_chunk(Vertex& v, size_t M, bool alternates) {
@@ -818,6 +819,128 @@ static void launch_limiter(const Launch& L, const void* d, hipStream_t s) {
     }
 }
 
+// ---- multiband: seven launches, or one (kernels.h MbDesc) ----
+static int lower_multiband(FxLevel& L, std::vector<size_t>& vs) {
+    td_graph* g = L.g;
+    const uint32_t n_tiles = (uint32_t)((L.M + kMbTile - 1) / kMbTile), chunk = (n_tiles + kThreads - 1) / kThreads;
+    const bool multi = n_tiles > 1u;   // (multi: the six launches in front of k_mb_apply)
+    static_assert(kMbWords == (uint32_t)multiband::kWords && kMbBlocks == (uint32_t)multiband::kBlocks, "the crossover's operator: one shape on both sides");
+    std::vector<MbDesc> d;
+    std::vector<CompDesc> bands;
+    std::vector<MasterDesc> c1, c2;
+    std::vector<size_t> pow_off;
+    for (size_t vi : vs) {
+        Vertex& v = g->vertices[vi];
+        MbDesc x{};
+        if (!(x.x = L.tmp_buffer())) return 0;
+        for (int b = 0; b < 3; ++b)
+            if (!(x.dy[b] = reinterpret_cast<double*>(L.tmp_buffer()))) return 0;   // (an edge buffer holds one double per frame)
+        L.head(x, vi);
+        x.line = (double*)take_line(g, v, (size_t)kMbState * sizeof(double));
+        if (!x.line) return fail("termdaw_amd: out of device memory for a multiband vertex' state");
+        x.init = enter_chunk(v, L.M, false) ? x.line : nullptr;   // (afresh: the state is zero, the line is not read)
+        x.n_tiles = n_tiles;
+        x.chunk = chunk;
+        double c[multiband::kParams];
+        multiband::params(L.sr, v.mb_lo_hz, v.mb_hi_hz, v.mb_attack_ms, v.mb_release_ms, c);
+        for (int s = 0; s < 5; ++s)
+            for (int i = 0; i < 5; ++i) x.co[s][i] = c[5 * s + i];
+        std::vector<MbPowers> pw(1);
+        multiband::powers(c, kMbRun, chunk, pw[0].pw, pw[0].a_tile, pw[0].pwc);
+        pow_off.push_back(L.cb.st->put(pw));
+        x.aA = c[25];
+        x.aR = c[26];
+        x.oA = 1.0 - x.aA;
+        x.knee = (double)v.mb_knee_db;
+        for (int b = 0; b < 3; ++b) {
+            x.thr[b] = (double)v.mb_threshold_db[b];
+            x.slope[b] = 1.0 - 1.0 / (double)v.mb_ratio[b];
+            x.makeup[b] = (double)v.mb_makeup_db[b];
+        }
+        for (int j = 0; j < 8; ++j) {   // (the compressor's powers: k_comp_env runs over the bands)
+            const double e = (double)(1u << j);
+            x.pwR[j] = pow(x.aR, (double)kMbRun * e);
+            x.pwA[j] = pow(x.aA, (double)kMbRun * e);
+        }
+        if (multi) {
+            for (int b = 0; b < 3; ++b) {
+                CompDesc y{};   // what k_comp_env reads of a compressor's descriptor, for band b
+                y.dy = x.dy[b];
+                y.state = reinterpret_cast<CompState*>(x.line + 2u * kMbWords + 2u * b);   // (k_comp_env stores y1 only: the pair's first word)
+                y.frames = x.frames;
+                y.n_tiles = n_tiles;
+                y.aR = x.aR; y.aA = x.aA; y.oA = x.oA;
+                for (int j = 0; j < 8; ++j) { y.pwR[j] = x.pwR[j]; y.pwA[j] = x.pwA[j]; }
+                bands.push_back(y);
+                MasterDesc y1{}, yl{};
+                y1.n_tiles = yl.n_tiles = n_tiles;
+                y1.chunk = yl.chunk = chunk;
+                yl.op = 1u;
+                for (int j = 0; j < 8; ++j) {
+                    const double e = (double)(1u << j);
+                    y1.pwc[j] = pow(x.aR, (double)kMbTile * (double)chunk * e);
+                    yl.pwc[j] = pow(x.aA, (double)kMbTile * (double)chunk * e);
+                }
+                y1.a_tile = pow(x.aR, (double)kMbTile);
+                yl.a_tile = pow(x.aA, (double)kMbTile);
+                if (x.init) {
+                    y1.init = x.line + 2u * kMbWords + 2u * b;
+                    yl.init = x.line + 2u * kMbWords + 2u * b + 1u;
+                }
+                c1.push_back(y1);
+                c2.push_back(yl);
+            }
+        }
+        d.push_back(x);
+    }
+    const size_t off = L.put(d, vs);
+    for (size_t i = 0; i < vs.size(); ++i) L.cb.ptr_field(off + i * sizeof(MbDesc), offsetof(MbDesc, pow), pow_off[i]);
+    if (!multi) {
+        L.add_launch(F_MB_APPLY, off, (int)vs.size(), mb_aux(n_tiles, true));
+        return 1;
+    }
+    const size_t ob = L.cb.st->put(bands), o1 = L.cb.st->put(c1), o2 = L.cb.st->put(c2);
+    for (size_t i = 0; i < vs.size(); ++i) {
+        const size_t o = off + i * sizeof(MbDesc), zb = (size_t)n_tiles * 2u * kMbWords * sizeof(double), tb = (size_t)n_tiles * sizeof(double);
+        L.cb.scratch_field(o, offsetof(MbDesc, agg), L.cb.scratch(zb));
+        L.cb.scratch_field(o, offsetof(MbDesc, carry), L.cb.scratch(zb));
+        for (size_t b = 0; b < 3; ++b) {
+            const size_t a1 = L.cb.scratch(tb), k1 = L.cb.scratch(tb), a2 = L.cb.scratch(tb), k2 = L.cb.scratch(tb);
+            const size_t q = 3 * i + b, oc = ob + q * sizeof(CompDesc), m1 = o1 + q * sizeof(MasterDesc), m2 = o2 + q * sizeof(MasterDesc);
+            L.cb.scratch_field(o, offsetof(MbDesc, agg1) + b * sizeof(double*), a1);
+            L.cb.scratch_field(o, offsetof(MbDesc, carry2) + b * sizeof(double*), k2);
+            L.cb.scratch_field(oc, offsetof(CompDesc, agg1), a1);
+            L.cb.scratch_field(oc, offsetof(CompDesc, carry1), k1);
+            L.cb.scratch_field(oc, offsetof(CompDesc, agg2), a2);
+            L.cb.scratch_field(oc, offsetof(CompDesc, carry2), k2);
+            L.cb.scratch_field(m1, offsetof(MasterDesc, agg), a1);
+            L.cb.scratch_field(m1, offsetof(MasterDesc, carry), k1);
+            L.cb.scratch_field(m2, offsetof(MasterDesc, agg), a2);
+            L.cb.scratch_field(m2, offsetof(MasterDesc, carry), k2);
+        }
+    }
+    const int n = (int)vs.size();
+    L.add_launch(F_MB_LOCAL, off, n, mb_aux(n_tiles, false));
+    L.add_launch(F_MB_CARRY, off, n, 0u);
+    L.add_launch(F_MB_DETECT, off, n, mb_aux(n_tiles, false));
+    L.add_launch(F_MB_CARRY1, o1, 3 * n, 0u);
+    L.add_launch(F_MB_ENV, ob, 3 * n, n_tiles);
+    L.add_launch(F_MB_CARRY2, o2, 3 * n, 0u);
+    L.add_launch(F_MB_APPLY, off, n, mb_aux(n_tiles, false));
+    return 1;
+}
+static void launch_multiband(const Launch& L, const void* d, hipStream_t s) {
+    switch (L.fam) {
+        case F_MB_LOCAL: launch_mb_local((const MbDesc*)d, L.n, mb_aux_tiles(L.aux), s); break;
+        case F_MB_CARRY: launch_mb_carry((const MbDesc*)d, L.n, s); break;
+        case F_MB_DETECT: launch_mb_detect((const MbDesc*)d, L.n, mb_aux_tiles(L.aux), s); break;
+        case F_MB_CARRY1:
+        case F_MB_CARRY2: launch_master_carry((const MasterDesc*)d, L.n, s); break;
+        case F_MB_ENV: launch_comp_env((const CompDesc*)d, L.n, L.aux, s); break;
+        case F_MB_APPLY: launch_mb_apply((const MbDesc*)d, L.n, mb_aux_tiles(L.aux), (L.aux & kMbSingleBit) != 0u, s); break;
+    }
+}
+
 // ---- the table ----
 // fits: the largest chunk the kind's kernels index (32-bit frames; the line kinds keep room for their look-back, the tiled
 // ones for the tile count packed into a launch's aux)
@@ -827,6 +950,8 @@ static bool fits_sat(const td_graph* g, const Vertex&, size_t M) { return M <= 0
 static bool fits_chorus(const td_graph* g, const Vertex&, size_t M) { return M <= 0xF0000000ull && (M + g->chorus_tile - 1) / g->chorus_tile < 0x100000ull; }
 
 static bool fits_voc(const td_graph*, const Vertex&, size_t M) { return M <= 0xFFFF0000ull && (M + kVocTile - 1) / kVocTile < 0x1000000ull; }
+
+static bool fits_mb(const td_graph*, const Vertex&, size_t M) { return M <= 0xFFFF0000ull && (M + kMbTile - 1) / kMbTile < 0x1000000ull; }
 
 static int family_sat(const Vertex& v) { return v.sat_oversample == 1 ? F_SAT1 : F_SAT_SUM; }
 
@@ -847,6 +972,8 @@ static double through_vocoder(const Vertex& v, size_t) { return dry(v) ? 1.0 : k
 static double through_filter(const Vertex& v, size_t) { return dry(v) ? 1.0 : kNoStaticGain; }
 // a limiter's gain follows the signal's peaks: no static gain -- the compressor's case, unless it is dry
 static double through_limiter(const Vertex& v, size_t) { return dry(v) ? 1.0 : kNoStaticGain; }
+// a multiband's three gains follow the bands' levels: no static gain -- the compressor's case, unless it is dry
+static double through_multiband(const Vertex& v, size_t) { return dry(v) ? 1.0 : kNoStaticGain; }
 // an EQ is linear and time-invariant: Hmax of its biquad
 static double through_eq(const Vertex& v, size_t sr) {
     if (dry(v)) return 1.0;
@@ -887,10 +1014,10 @@ static_assert(sizeof(PhaserState) == kPhaserSlots * sizeof(StateSlot) && sizeof(
 // the rows cover the effect families of `Family` without gap or overlap as long as they stand in its order.  built / keyed_built:
 // the entry points the kind's `launch` calls are linked (kernels.h declares them weak); the filter's keyed forms are instantiations
 // behind the entry points of its unkeyed ones.
-constexpr int kFxKinds = 11;
+constexpr int kFxKinds = 12;
 static_assert(F_COMP_DETECT < F_EQ_LOCAL && F_EQ_LOCAL < F_DELAY_LOCAL && F_DELAY_LOCAL < F_SAT_SUM && F_SAT_SUM < F_CHORUS_SUM &&
               F_CHORUS_SUM < F_REVERB_SUM && F_REVERB_SUM < F_GATE_DETECT && F_GATE_DETECT < F_PHASER_LOCAL && F_PHASER_LOCAL < F_VOC_LOCAL &&
-              F_VOC_LOCAL < F_FILT_DETECT && F_FILT_DETECT < F_LIM_DETECT && F_LIM_DETECT < F_COUNT,
+              F_VOC_LOCAL < F_FILT_DETECT && F_FILT_DETECT < F_LIM_DETECT && F_LIM_DETECT < F_MB_LOCAL && F_MB_LOCAL < F_COUNT,
               "the rows of the effect kinds' table stand in the order of their families");
 static const FxKind* table() {
     static const FxKind rows[kFxKinds] = {
@@ -904,7 +1031,8 @@ static const FxKind* table() {
         {K_PHASER, "phaser", "phaser", F_PHASER_LOCAL, F_VOC_LOCAL - F_PHASER_LOCAL, sizeof(PhaserDesc), kPhaserSlots, false, fits_scan, nullptr, through_phaser, lower_phaser, launch_phaser, launch_phaser_local && launch_phaser_carry && launch_phaser_apply, true, nullptr, nullptr},
         {K_VOCODER, "vocoder", "voc", F_VOC_LOCAL, F_FILT_DETECT - F_VOC_LOCAL, sizeof(VocDesc), 0, true, fits_voc, nullptr, through_vocoder, lower_vocoder, launch_vocoder, launch_voc_local && launch_voc_carry && launch_voc_env && launch_voc_apply, launch_voc_local_keyed && launch_voc_apply_keyed, "vocoder", nullptr},
         {K_FILTER, "filter", "filt", F_FILT_DETECT, F_LIM_DETECT - F_FILT_DETECT, sizeof(FiltDesc), kFiltSlots, true, fits_scan, nullptr, through_filter, lower_filter, launch_filter, launch_filt_detect && launch_filt_env && launch_filt_local && launch_filt_carry && launch_filt_apply && launch_master_carry, true, nullptr, nullptr},
-        {K_LIMITER, "limiter", "lim", F_LIM_DETECT, F_COUNT - F_LIM_DETECT, sizeof(LimDesc), 0, false, fits_scan, nullptr, through_limiter, lower_limiter, launch_limiter, launch_lim_detect && launch_lim_apply && launch_master_carry, true, nullptr, nullptr},
+        {K_LIMITER, "limiter", "lim", F_LIM_DETECT, F_MB_LOCAL - F_LIM_DETECT, sizeof(LimDesc), 0, false, fits_scan, nullptr, through_limiter, lower_limiter, launch_limiter, launch_lim_detect && launch_lim_apply && launch_master_carry, true, nullptr, nullptr},
+        {K_MULTIBAND, "multiband", "mb", F_MB_LOCAL, F_COUNT - F_MB_LOCAL, sizeof(MbDesc), 0, false, fits_mb, nullptr, through_multiband, lower_multiband, launch_multiband, launch_mb_local && launch_mb_carry && launch_mb_detect && launch_mb_apply && launch_comp_env && launch_master_carry, true, nullptr, nullptr},
     };
     return rows;
 }

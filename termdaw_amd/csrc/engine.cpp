@@ -15,6 +15,7 @@
 #include "vocoder_math.h"
 #include "filter_math.h"
 #include "limiter_math.h"
+#include "multiband_math.h"
 #include "comm.h"
 #include "compile.h"
 #include "delay_math.h"
@@ -572,7 +573,7 @@ int ensure_buffers(td_graph* g, size_t frames) {
     g->free_bufs = g->pool;
     return 1;
 }
-// The block a delay, saturator, chorus, reverb, vocoder or limiter vertex carries (Vertex::line): allocated when the vertex is first compiled into a
+// The block a delay, saturator, chorus, reverb, vocoder, limiter or multiband vertex carries (Vertex::line): allocated when the vertex is first compiled into a
 // submission (never cleared: a word is read only once the vertex has written it, Line::total), freed with the graph's vertices.
 void* take_line(td_graph* g, Vertex& v, size_t bytes) {
     if (v.line.d) return v.line.d;
@@ -2100,6 +2101,38 @@ int td_limiter_params(size_t sr, float ceiling_db, float lookahead_ms, float rel
     if (!out) return fail("limiter_params: out is null");
     if (const char* why = limiter::check(sr, ceiling_db, lookahead_ms, release_ms, drive_db)) return fail(std::string("limiter: ") + why);
     limiter::params(sr, ceiling_db, lookahead_ms, release_ms, drive_db, out);
+    return 1;
+}
+
+// This engine's own multiband vertex (no reference counterpart; the definition is in include/termdaw_amd.h).  Its state is a
+// carried line (42 doubles), allocated when the vertex is first compiled into a submission.
+int td_graph_add_multiband(td_graph* g, const char* name, float gain, float angle, float wet, float lo_hz, float hi_hz,
+                           const float threshold_db[3], const float ratio[3], float attack_ms, float release_ms, float knee_db,
+                           const float makeup_db[3]) {
+    if (!threshold_db || !ratio || !makeup_db) return fail("multiband: threshold_db, ratio and makeup_db must point at three floats each");
+    if (const char* why = multiband::check(g->sr, lo_hz, hi_hz, threshold_db, ratio, attack_ms, release_ms, knee_db, makeup_db))
+        return fail(std::string("multiband: ") + why);
+    Vertex& v = add_fx_vertex(g, name, gain, angle, wet, K_MULTIBAND);
+    v.mb_lo_hz = lo_hz;
+    v.mb_hi_hz = hi_hz;
+    v.mb_attack_ms = attack_ms;
+    v.mb_release_ms = release_ms;
+    v.mb_knee_db = knee_db;
+    for (int b = 0; b < 3; ++b) {
+        v.mb_threshold_db[b] = threshold_db[b];
+        v.mb_ratio[b] = ratio[b];
+        v.mb_makeup_db[b] = makeup_db[b];
+    }
+    return 1;
+}
+int td_multiband_params(size_t sr, float lo_hz, float hi_hz, const float threshold_db[3], const float ratio[3], float attack_ms,
+                        float release_ms, float knee_db, const float makeup_db[3], double* out, size_t n) {
+    if (!out) return fail("multiband_params: out is null");
+    if (!threshold_db || !ratio || !makeup_db) return fail("multiband: threshold_db, ratio and makeup_db must point at three floats each");
+    if (const char* why = multiband::check(sr, lo_hz, hi_hz, threshold_db, ratio, attack_ms, release_ms, knee_db, makeup_db))
+        return fail(std::string("multiband: ") + why);
+    if (n < (size_t)multiband::kParams) return fail("multiband_params: out holds fewer than 27 doubles");
+    multiband::params(sr, lo_hz, hi_hz, attack_ms, release_ms, out);
     return 1;
 }
 

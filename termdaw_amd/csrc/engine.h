@@ -76,7 +76,7 @@ struct td_flowwbank {
 namespace tde {
 
 enum Kind { K_SUM, K_NORMALIZE, K_SAMPLE_LOOP, K_SAMPLE_MULTI, K_SAMPLE_LERP, K_DEBUG_SINE, K_SYNTH,
-            K_SAMPSYN, K_ADSR, K_BAND_PASS, K_COMPRESSOR, K_EQ, K_DELAY, K_SATURATOR, K_CHORUS, K_REVERB, K_GATE, K_PHASER, K_VOCODER, K_FILTER, K_LIMITER, K_COUNT };
+            K_SAMPSYN, K_ADSR, K_BAND_PASS, K_COMPRESSOR, K_EQ, K_DELAY, K_SATURATOR, K_CHORUS, K_REVERB, K_GATE, K_PHASER, K_VOCODER, K_FILTER, K_LIMITER, K_MULTIBAND, K_COUNT };
 
 struct SineNote { float note, vel; };
 struct SynthNote { float note, vel, env_t, rel_t, hz; };   // hz = 440 * 2^((note - 69) / 12), extensions.rs:503
@@ -145,11 +145,13 @@ struct Vertex {
     float filt_freq_hz = 1000, filt_q = 1, filt_lfo_oct = 0, filt_rate_hz = 1, filt_stereo = 0;
     float filt_env_oct = 0, filt_sens_db = 0, filt_attack_ms = 0, filt_release_ms = 1;
     float lim_ceiling_db = 0, lim_lookahead_ms = 0, lim_release_ms = 1, lim_drive_db = 0;   // K_LIMITER
+    float mb_lo_hz = 40, mb_hi_hz = 80, mb_attack_ms = 0, mb_release_ms = 1, mb_knee_db = 0;   // K_MULTIBAND
+    float mb_threshold_db[3] = {0, 0, 0}, mb_ratio[3] = {1, 1, 1}, mb_makeup_db[3] = {0, 0, 0};   // ... per band: low, mid, high
     // a filter vertex whose follower runs: env_oct != 0 (otherwise y1, e stay as they are and key edges are ignored)
     bool filt_follows() const { return filt_env_oct != 0.0f; }
     // a vertex with key edges reads them: it is not dry, and a filter's follower runs
     bool reads_key() const { return !(wet < 0.0001f) && (kind != K_FILTER || filt_follows()); }
-    // The block of device memory a delay, saturator, chorus, reverb, vocoder or limiter vertex carries from chunk to chunk: allocated when the vertex
+    // The block of device memory a delay, saturator, chorus, reverb, vocoder, limiter or multiband vertex carries from chunk to chunk: allocated when the vertex
     // is first compiled into a submission (take_line), never cleared, freed with the graph's vertices.
     //   K_DELAY             the last D values of (ul, ur), 16 D bytes: the rotation is total mod D, the words below min(total, D) hold values
     //   K_SATURATOR (R > 1) the last 128 raw input frames, two halves of 128 float2: a frame at or beyond min(total, 128) back reads as 0
@@ -157,6 +159,7 @@ struct Vertex {
     //   K_REVERB            f[16] and the 24 lines, doubles: frame m of a line lives in slot m mod D, a read of m - D < 0 is 0
     //   K_VOCODER           7 doubles per band, (s1l, s2l, s1r, s2r, s1m, s2m, e): read only once total > 0
     //   K_LIMITER           two halves of 2 L doubles (kernels.h LimDesc): u, the e and the raw input of the last L - 1 frames; read only once total > 0
+    //   K_MULTIBAND         42 doubles (kernels.h MbDesc): (s1, s2) of the nine biquads of the left channel, of the right, then (y1, yL) per band; read only once total > 0
     struct Line {
         void* d = nullptr;
         size_t bytes = 0;
@@ -177,7 +180,7 @@ struct Vertex {
     // compile.h -- a phaser's hold a tdk::PhaserState, a filter's a tdk::FiltState), index into Graph::dstate
     int state_slot = -1;
     // reset_normalization (extensions.rs:295-299) is kept on the host until the next render consumes it
-    bool first_pending = false;         // band-pass, compressor, eq, gate, phaser, filter, delay, saturator, chorus, reverb, vocoder, limiter (their state then restarts from zero): set_time since the vertex was last compiled into a submission (its descriptor's first_override)
+    bool first_pending = false;         // band-pass, compressor, eq, gate, phaser, filter, delay, saturator, chorus, reverb, vocoder, limiter, multiband (their state then restarts from zero): set_time since the vertex was last compiled into a submission (its descriptor's first_override)
     bool has_init_override = false;
     float init_override = 0.0f;
     // Normalize: the carried max is the result of a normalize scan (graph.rs:222-237), so a render is expected to

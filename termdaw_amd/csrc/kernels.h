@@ -508,6 +508,59 @@ struct LimDesc {
     PanGain pg;
 };
 
+// A multiband vertex (k_mb_local / k_mb_carry / k_mb_detect / k_master_carry / k_comp_env / k_master_carry / k_mb_apply, DESIGN.md
+// §3y; the definition is in include/termdaw_amd.h at td_graph_add_multiband): a three-way Linkwitz-Riley crossover -- nine biquads
+// per channel in the EQ's transposed direct form II, f64, a CASCADE -- into three of the compressor's detectors, one per band.
+// With z the 18 state words of a channel (biquad i: words 2 i, 2 i + 1; order L1 L1 A2 | H1 H1 | L2 L2 | H2 H2) the crossover is
+// z[n] = A z[n-1] + c x[n], A block lower triangular in 2x2 blocks with kMbBlocks of the 81 not zero (multiband_math.h kBlockRow /
+// kBlockCol: biquad `col` reaches biquad `row`).  The compressor's tiling: tiles of kMbTile frames, a lane owns kMbRun consecutive frames;
+// the lanes' run-end states are joined one channel at a time, 18 planes of LDS.
+//   k_mb_local evaluates the input terms into `x` and leaves each tile's zero-start end state in agg[(2 t + ch) 18 ..];
+//   k_mb_carry (one workgroup per channel and vertex) the state entering each tile in carry[(2 t + ch) 18 ..] (tile 0: the
+//   line's, or 0 when init is null); k_mb_detect rebuilds the lanes' entry states, runs the cascade and writes the wanted
+//   reduction d_b[n] (f64) of band b to dy[b], each tile's zero-start end value of the release to agg1[b][t]; k_master_carry
+//   (op 0) and k_comp_env -- the compressor's own, over three MasterDesc / CompDesc per vertex -- overwrite dy[b] with y1_b and
+//   leave the attack's tile totals, k_master_carry (op 1) the yL_b entering each tile in carry2[b][t]; k_mb_apply rebuilds the
+//   band signals and yL_b, G_b = 10^((M_b - yL_b) / 20), p = (float)(((0 + low G_0) + mid G_1) + high G_2), writes lerp(x, p, wet),
+//   pan, gain to `out`, and the lane that owns the chunk's last frame writes the 36 filter words and yL_b back (y1_b: k_comp_env).
+//   When one tile covers the chunk (every block pull) k_mb_apply runs alone (kMbSingleBit): the term loop and both detector
+//   recurrences run inside it and the tile enters with the line; a lane keeps its frames of x, d_b and y1_b in `x` and `dy` as the
+//   seven-launch form does and reads back only what it wrote itself (agg .. carry2 unused).
+// The line: 42 doubles -- z of the left channel, z of the right, then (y1_b, yL_b) for b = 0, 1, 2.
+constexpr uint32_t kMbRun = 8;                    // frames per lane
+constexpr uint32_t kMbTile = kMbRun * kThreads;   // frames per workgroup
+constexpr uint32_t kMbBiquads = 9;
+constexpr uint32_t kMbWords = 2 * kMbBiquads;     // state words of a channel
+constexpr uint32_t kMbState = 2 * kMbWords + 6;   // doubles of the line
+constexpr uint32_t kMbBlocks = 23;
+struct MbPowers {
+    double pw[8][kMbBlocks * 4];    // the blocks of A^(kMbRun 2^k): (p00, p01, p10, p11) each
+    double a_tile[kMbBlocks * 4];   // ... of A^kMbTile
+    double pwc[8][kMbBlocks * 4];   // ... of A^(kMbTile chunk 2^k)
+};
+struct MbDesc {
+    const InTerm* ins;      // k input terms (kinds 0 .. 4), in connect() order
+    float2* x;              // [frames] the summed input
+    float2* out;
+    double* line;           // carried across chunks / block pulls
+    const double* init;     // the state entering tile 0: `line`, or nullptr when the vertex starts afresh
+    const MbPowers* pow;
+    double* agg;            // [36 n_tiles]
+    double* carry;          // [36 n_tiles]
+    double* dy[3];          // [frames] each: d_b, then y1_b (the bands' CompDesc::dy)
+    double* agg1[3];        // [n_tiles] each (the bands' CompDesc::agg1)
+    const double* carry2[3];   // [n_tiles] each (the bands' CompDesc::carry2)
+    uint32_t k, term_mode, frames, n_tiles;
+    uint32_t chunk;         // tiles per lane in k_mb_carry
+    float wet;
+    double co[5][5];        // (b0, b1, b2, a1, a2) of L1, H1, L2, H2, A2
+    double thr[3], slope[3], makeup[3];   // T_b, 1 - 1 / R_b, M_b (dB)
+    double knee;
+    double aR, aA, oA;      // release / attack coefficients, 1 - aA
+    double pwR[8], pwA[8];  // aR^(kMbRun 2^k), aA^(kMbRun 2^k)
+    PanGain pg;
+};
+
 // A parametric EQ vertex (k_eq_local / k_eq_carry / k_eq_apply; the definition is in include/termdaw_amd.h at
 // td_graph_add_eq): one RBJ biquad per channel in transposed direct form II, f64.  With z = (s1, s2) the recurrence is
 // z[n] = A z[n-1] + c x[n],  A = [[-a1, 1], [-a2, 0]],  c = (b1 - a1 b0, b2 - a2 b0),  y[n] = b0 x[n] + s1[n-1]: an affine scan
@@ -1202,6 +1255,16 @@ inline uint32_t lim_aux(uint32_t n_tiles, bool single) { return n_tiles | (singl
 inline uint32_t lim_aux_tiles(uint32_t aux) { return aux & 0xFFFFFFu; }
 __attribute__((weak)) void launch_lim_detect(const LimDesc* d, int n_desc, uint32_t n_tiles, hipStream_t s);
 __attribute__((weak)) void launch_lim_apply(const LimDesc* d, int n_desc, uint32_t n_tiles, bool single, hipStream_t s);
+// Weak for the same reason: a level's multiband vertices, grid.x = n_tiles (every descriptor's; launch_mb_carry: one workgroup per
+// channel and vertex).  F_MB_APPLY's aux packs the tile count and `single` (the one-launch form of a one-tile chunk).  The two
+// scalar carries are launch_master_carry's over MasterDesc, the launch between them launch_comp_env's over CompDesc.
+constexpr uint32_t kMbSingleBit = 0x40000000u;
+inline uint32_t mb_aux(uint32_t n_tiles, bool single) { return n_tiles | (single ? kMbSingleBit : 0u); }
+inline uint32_t mb_aux_tiles(uint32_t aux) { return aux & 0xFFFFFFu; }
+__attribute__((weak)) void launch_mb_local(const MbDesc* d, int n_desc, uint32_t n_tiles, hipStream_t s);
+__attribute__((weak)) void launch_mb_carry(const MbDesc* d, int n_desc, hipStream_t s);
+__attribute__((weak)) void launch_mb_detect(const MbDesc* d, int n_desc, uint32_t n_tiles, hipStream_t s);
+__attribute__((weak)) void launch_mb_apply(const MbDesc* d, int n_desc, uint32_t n_tiles, bool single, hipStream_t s);
 // Weak for the same reason: a level's reverb vertices.  launch_reverb_sum: grid.x from `frames`; launch_reverb: one workgroup per
 // descriptor, `form` 0 the serial walk of each comb's one-pole, 1 the wave scan.
 __attribute__((weak)) void launch_reverb_sum(const ReverbDesc* d, int n_desc, uint32_t frames, hipStream_t s);

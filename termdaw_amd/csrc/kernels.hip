@@ -7583,6 +7583,369 @@ __global__ __launch_bounds__(kThreads) void k_lim_apply(const LimDesc* __restric
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// k_mb_local / k_mb_carry / k_mb_detect / k_mb_apply: the multiband vertex (kernels.h MbDesc).  No reference
+// counterpart; the definition is the header's (td_graph_add_multiband): a three-way Linkwitz-Riley crossover, nine biquads per
+// channel in a cascade, into three of the compressor's detectors, f64.  The crossover's 18 state words of a channel are ONE
+// affine scan whose operator is block lower triangular: a join multiplies by the 23 blocks that are not zero, not by 81.
+// ------------------------------------------------------------------------------------------------
+// (block, row biquad, column biquad): the blocks in row order, the order the joins add them in (multiband_math.h kBlockRow / kBlockCol)
+#define TD_MB_BLOCKS(X)                                                                                            \
+    X(0, 0, 0) X(1, 1, 0) X(2, 1, 1) X(3, 2, 0) X(4, 2, 1) X(5, 2, 2) X(6, 3, 3) X(7, 4, 3) X(8, 4, 4) X(9, 5, 3)  \
+    X(10, 5, 4) X(11, 5, 5) X(12, 6, 3) X(13, 6, 4) X(14, 6, 5) X(15, 6, 6) X(16, 7, 3) X(17, 7, 4) X(18, 7, 7)    \
+    X(19, 8, 3) X(20, 8, 4) X(21, 8, 7) X(22, 8, 8)
+struct MbCo { double c[5][5]; };
+TD_DEV void mb_load_co(const MbDesc& d, MbCo& c) {
+#pragma unroll
+    for (int s = 0; s < 5; ++s)
+#pragma unroll
+        for (int i = 0; i < 5; ++i) c.c[s][i] = d.co[s][i];
+}
+// biquad I of the cascade with coefficient set S, one frame (the definition's order: voc_frame)
+template <int S, int I>
+TD_DEV double mb_bq(const MbCo& c, double (&z)[kMbWords], double u) {
+    return voc_frame(c.c[S][0], c.c[S][1], c.c[S][2], c.c[S][3], c.c[S][4], z[2 * I], z[2 * I + 1], u);
+}
+// one frame of one channel: low = A2(L1(L1(x))), rest = H1(H1(x)), mid = L2(L2(rest)), high = H2(H2(rest))
+TD_DEV void mb_frame(const MbCo& c, double (&z)[kMbWords], double x, double& low, double& mid, double& high) {
+    const double l1 = mb_bq<0, 0>(c, z, x);
+    const double l2 = mb_bq<0, 1>(c, z, l1);
+    low = mb_bq<4, 2>(c, z, l2);
+    const double h1 = mb_bq<1, 3>(c, z, x);
+    const double rest = mb_bq<1, 4>(c, z, h1);
+    const double m1 = mb_bq<2, 5>(c, z, rest);
+    mid = mb_bq<2, 6>(c, z, m1);
+    const double g1 = mb_bq<3, 7>(c, z, rest);
+    high = mb_bq<3, 8>(c, z, g1);
+}
+// u <- u + P o over the 23 blocks, in block order: u[r] = u[r] + (p00 o[c] + p01 o[c + 1]), u[r + 1] likewise
+TD_DEV void mb_matvec_add(const double* P, const double (&o)[kMbWords], double (&u)[kMbWords]) {
+#define TD_MB_X(B, R, C)                                                             \
+    {                                                                                \
+        const d2v p = gload_d2(P + 4 * B), q = gload_d2(P + 4 * B + 2);              \
+        u[2 * R] = u[2 * R] + (p.x * o[2 * C] + p.y * o[2 * C + 1]);                 \
+        u[2 * R + 1] = u[2 * R + 1] + (q.x * o[2 * C] + q.y * o[2 * C + 1]);         \
+    }
+    TD_MB_BLOCKS(TD_MB_X)
+#undef TD_MB_X
+}
+// The lanes' run-end states of one channel joined in lane order (eq_lane_scan's shape over 18 planes): TILES ? pwc : pw.  u: lane
+// 0's run started from u_in, the others' from 0.  in: the state entering the lane's run; last: the state after the last lane's.
+template <bool TILES>
+TD_DEV void mb_lane_scan(double (&u)[kMbWords], const MbPowers* pw, const double (&u_in)[kMbWords], double* sv, double (&in)[kMbWords],
+                         double (&last)[kMbWords]) {
+    const uint32_t tid = threadIdx.x;
+#pragma unroll 1
+    for (uint32_t k = 0; k < 8; ++k) {
+        const uint32_t off = 1u << k;
+#pragma unroll
+        for (uint32_t i = 0; i < kMbWords; ++i) sv[i * kThreads + tid] = u[i];
+        __syncthreads();
+        if (tid >= off) {
+            double o[kMbWords];
+#pragma unroll
+            for (uint32_t i = 0; i < kMbWords; ++i) o[i] = sv[i * kThreads + tid - off];
+            mb_matvec_add(TILES ? pw->pwc[k] : pw->pw[k], o, u);
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (uint32_t i = 0; i < kMbWords; ++i) sv[i * kThreads + tid] = u[i];
+    __syncthreads();
+#pragma unroll
+    for (uint32_t i = 0; i < kMbWords; ++i) {
+        in[i] = tid ? sv[i * kThreads + tid - 1] : u_in[i];
+        last[i] = sv[i * kThreads + kThreads - 1];
+    }
+    __syncthreads();
+}
+// steps 1 and 2 of the compressor on one band's f64 frame (comp_want's order)
+TD_DEV double mb_want(double thr, double slope, double W, double l, double r) {
+    const double al = fabs(l), ar = fabs(r);
+    if (!(al <= 1.7976931348623157e308 && ar <= 1.7976931348623157e308)) return 0.0;   // a NaN / infinite frame stays out of the state
+    const double s = fmax(al, ar);
+    if (s == 0.0) return 0.0;
+    const double o = 20.0 * log10(s) - thr;
+    if (2.0 * o < -W) return 0.0;
+    if (W > 0.0 && 2.0 * fabs(o) <= W) {
+        const double t = o + W / 2.0;
+        return slope * (t * t) / (2.0 * W);
+    }
+    if (2.0 * o > W) return slope * o;
+    return 0.0;
+}
+// Two frames (x.x, x.y), (x.z, x.w) through both channels' cascades; the band signals are dropped (a run for its end state)
+TD_DEV void mb_run_pair(const MbCo& c, double (&zl)[kMbWords], double (&zr)[kMbWords], float4 x) {
+    double lo, mi, hi;
+    mb_frame(c, zl, eq_in(x.x), lo, mi, hi);
+    mb_frame(c, zr, eq_in(x.y), lo, mi, hi);
+    mb_frame(c, zl, eq_in(x.z), lo, mi, hi);
+    mb_frame(c, zr, eq_in(x.w), lo, mi, hi);
+}
+// The lane's run over the summed input in d.x (0 from `frames` on) from the states in (zl, zr).  The frame loops of these
+// kernels stay rolled, two frames per round: unrolled, the nine biquads of eight frames cost the registers of one wave per SIMD.
+TD_DEV void mb_run_x(const MbDesc& d, const MbCo& c, uint32_t f0, double (&zl)[kMbWords], double (&zr)[kMbWords]) {
+#pragma unroll 1
+    for (uint32_t j = 0; j < kMbRun; j += 2) mb_run_pair(c, zl, zr, load_pair(d.x, f0 + j, d.frames));
+}
+// ... and through the term loop, the sums written to d.x on the way
+TD_DEV void mb_run_terms(const MbDesc& d, const MbCo& c, uint32_t f0, double (&zl)[kMbWords], double (&zr)[kMbWords]) {
+    const uint32_t M = d.frames;
+#pragma unroll 1
+    for (uint32_t h = 0; h < kMbRun / 4; ++h) {   // (frames beyond M sum to 0)
+        const uint32_t m = f0 + 4u * h;
+        float4 a0, a1;
+        sum_inputs_pairs(d.ins, d.k, d.term_mode, m, m + 2u, M, a0, a1);
+        store_pair(d.x, m, M, a0);
+        store_pair(d.x, m + 2u, M, a1);
+        mb_run_pair(c, zl, zr, a0);
+        mb_run_pair(c, zl, zr, a1);
+    }
+}
+// The tile entered with the 36 words at cy (nullptr: zero): lane 0's states into (zl, zr), the other lanes' zero
+TD_DEV void mb_start(const double* cy, double (&cl)[kMbWords], double (&cr)[kMbWords], double (&zl)[kMbWords], double (&zr)[kMbWords]) {
+#pragma unroll
+    for (uint32_t i = 0; i < kMbWords; i += 2) {
+        d2v a, b;
+        a.x = 0.0; a.y = 0.0; b = a;
+        if (cy) { a = gload_d2(cy + i); b = gload_d2(cy + kMbWords + i); }
+        cl[i] = a.x; cl[i + 1] = a.y; cr[i] = b.x; cr[i + 1] = b.y;
+        zl[i] = threadIdx.x ? 0.0 : a.x; zl[i + 1] = threadIdx.x ? 0.0 : a.y;
+        zr[i] = threadIdx.x ? 0.0 : b.x; zr[i + 1] = threadIdx.x ? 0.0 : b.y;
+    }
+}
+// (zl, zr): the lanes' run-end states -> the states entering the lanes' runs, one channel joined after the other
+TD_DEV void mb_join(const MbPowers* pw, const double (&cl)[kMbWords], const double (&cr)[kMbWords], double* sv, double (&zl)[kMbWords],
+                    double (&zr)[kMbWords]) {
+    double in[kMbWords], last[kMbWords];
+    mb_lane_scan<false>(zl, pw, cl, sv, in, last);
+#pragma unroll
+    for (uint32_t i = 0; i < kMbWords; ++i) zl[i] = in[i];
+    mb_lane_scan<false>(zr, pw, cr, sv, in, last);
+#pragma unroll
+    for (uint32_t i = 0; i < kMbWords; ++i) zr[i] = in[i];
+}
+__global__ __launch_bounds__(kThreads) void k_mb_local(const MbDesc* __restrict__ descs) {
+    const MbDesc& d = descs[blockIdx.y];
+    if (blockIdx.x >= d.n_tiles) return;
+    __shared__ double sv[kMbWords * kThreads];
+    const uint32_t tid = threadIdx.x, f0 = blockIdx.x * kMbTile + tid * kMbRun;
+    MbCo c;
+    mb_load_co(d, c);
+    double zero[kMbWords], zl[kMbWords], zr[kMbWords], in[kMbWords], last[kMbWords];
+#pragma unroll
+    for (uint32_t i = 0; i < kMbWords; ++i) { zero[i] = 0.0; zl[i] = 0.0; zr[i] = 0.0; }
+    mb_run_terms(d, c, f0, zl, zr);
+    double* a = d.agg + (size_t)blockIdx.x * 2u * kMbWords;
+    mb_lane_scan<false>(zl, d.pow, zero, sv, in, last);
+    if (tid == 0) {
+#pragma unroll
+        for (uint32_t i = 0; i < kMbWords; i += 2) gstore_d2(a + i, last[i], last[i + 1]);
+    }
+    mb_lane_scan<false>(zr, d.pow, zero, sv, in, last);
+    if (tid == 0) {
+#pragma unroll
+        for (uint32_t i = 0; i < kMbWords; i += 2) gstore_d2(a + kMbWords + i, last[i], last[i + 1]);
+    }
+}
+// entry[t + 1] = A^kMbTile entry[t] + total[t] for one channel's 18 words, entry[0] the line's (k_eq_carry's shape: a lane folds
+// `chunk` consecutive tiles, Hillis-Steele over the lanes, a second walk writes the entries).  One workgroup per channel and
+// vertex: grid (2, n_desc).
+__global__ __launch_bounds__(kThreads) void k_mb_carry(const MbDesc* __restrict__ descs) {
+    const MbDesc& d = descs[blockIdx.y];
+    const uint32_t ch = blockIdx.x;
+    __shared__ double sv[kMbWords * kThreads];
+    const uint32_t tid = threadIdx.x, n = d.n_tiles, c = d.chunk;
+    const uint32_t b = tid * c < n ? tid * c : n, e = b + c < n ? b + c : n;
+    const double* P = d.pow->a_tile;
+    double init[kMbWords], u[kMbWords], in[kMbWords], last[kMbWords];
+#pragma unroll
+    for (uint32_t i = 0; i < kMbWords; ++i) {
+        init[i] = d.init ? gloadd(d.init + kMbWords * ch + i) : 0.0;
+        u[i] = tid ? 0.0 : init[i];
+    }
+    for (uint32_t r = b; r < e; ++r) {
+        const double* a = d.agg + ((size_t)r * 2u + ch) * kMbWords;
+        double t[kMbWords];
+#pragma unroll
+        for (uint32_t i = 0; i < kMbWords; i += 2) {
+            const d2v w = gload_d2(a + i);
+            t[i] = w.x; t[i + 1] = w.y;
+        }
+        mb_matvec_add(P, u, t);
+#pragma unroll
+        for (uint32_t i = 0; i < kMbWords; ++i) u[i] = t[i];
+    }
+    mb_lane_scan<true>(u, d.pow, init, sv, in, last);
+    for (uint32_t r = b; r < e; ++r) {
+        const double* a = d.agg + ((size_t)r * 2u + ch) * kMbWords;
+        double* o = d.carry + ((size_t)r * 2u + ch) * kMbWords;
+        double t[kMbWords];
+#pragma unroll
+        for (uint32_t i = 0; i < kMbWords; i += 2) {
+            gstore_d2(o + i, in[i], in[i + 1]);
+            const d2v w = gload_d2(a + i);
+            t[i] = w.x; t[i + 1] = w.y;
+        }
+        mb_matvec_add(P, in, t);
+#pragma unroll
+        for (uint32_t i = 0; i < kMbWords; ++i) in[i] = t[i];
+    }
+}
+// The lane's run from its entry states: d_b of every frame to dy[b] (0 from `frames` on), u[b] the release over the run from u[b]
+TD_DEV void mb_detect_run(const MbDesc& d, const MbCo& c, uint32_t f0, double (&zl)[kMbWords], double (&zr)[kMbWords], double (&u)[3]) {
+    const uint32_t M = d.frames;
+    const double aR = d.aR, W = d.knee;
+#pragma unroll 1
+    for (uint32_t j = 0; j < kMbRun; j += 2) {
+        const uint32_t m = f0 + j;
+        const float4 x = load_pair(d.x, m, M);
+        double bl[2][3], br[2][3];
+        mb_frame(c, zl, eq_in(x.x), bl[0][0], bl[0][1], bl[0][2]);
+        mb_frame(c, zr, eq_in(x.y), br[0][0], br[0][1], br[0][2]);
+        mb_frame(c, zl, eq_in(x.z), bl[1][0], bl[1][1], bl[1][2]);
+        mb_frame(c, zr, eq_in(x.w), br[1][0], br[1][1], br[1][2]);
+#pragma unroll
+        for (int b = 0; b < 3; ++b) {   // (a frame at `frames` or beyond: d = 0, like the compressor's)
+            const double d0 = m < M ? mb_want(d.thr[b], d.slope[b], W, bl[0][b], br[0][b]) : 0.0;
+            const double d1 = m + 1u < M ? mb_want(d.thr[b], d.slope[b], W, bl[1][b], br[1][b]) : 0.0;
+            if (m < M) gstore_d2(d.dy[b] + m, d0, d1);
+            u[b] = fmax(d0, aR * u[b]);
+            u[b] = fmax(d1, aR * u[b]);
+        }
+    }
+}
+// a pair of dy[b] (0 from `frames` on)
+TD_DEV d2v mb_load_dy(const MbDesc& d, int b, uint32_t m) {
+    d2v v;
+    v.x = 0.0; v.y = 0.0;
+    if (m < d.frames) v = gload_d2(d.dy[b] + m);
+    if (!(m + 1u < d.frames)) v.y = 0.0;
+    return v;
+}
+__global__ __launch_bounds__(kThreads) void k_mb_detect(const MbDesc* __restrict__ descs) {
+    const MbDesc& d = descs[blockIdx.y];
+    if (blockIdx.x >= d.n_tiles) return;
+    __shared__ double sv[kMbWords * kThreads];
+    const uint32_t tid = threadIdx.x, f0 = blockIdx.x * kMbTile + tid * kMbRun;
+    MbCo c;
+    mb_load_co(d, c);
+    double cl[kMbWords], cr[kMbWords], zl[kMbWords], zr[kMbWords];
+    mb_start(d.carry + (size_t)blockIdx.x * 2u * kMbWords, cl, cr, zl, zr);
+    mb_run_x(d, c, f0, zl, zr);
+    mb_join(d.pow, cl, cr, sv, zl, zr);
+    double u[3] = {0.0, 0.0, 0.0};
+    mb_detect_run(d, c, f0, zl, zr, u);
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+        double last;
+        (void)comp_lane_scan<false>(u[b], d.pwR, 0.0, sv, &last);
+        if (tid == 0) gstored(d.agg1[b] + blockIdx.x, last);
+    }
+}
+// MODE 0: the seven-launch form's last launch (x, carry, dy = y1_b, carry2 from the launches before);  1: the chunk is this one
+// tile -- the term loop runs here, the tile enters with the line and both detector recurrences run inside it (a block pull: one
+// launch).  A lane of MODE 1 keeps its frames of x, d_b and y1_b where the seven-launch form has them, in d.x and d.dy: it reads
+// back what it wrote itself, no other lane's.
+template <int MODE>
+__global__ __launch_bounds__(kThreads) void k_mb_apply(const MbDesc* __restrict__ descs) {
+    const MbDesc& d = descs[blockIdx.y];
+    if (blockIdx.x >= d.n_tiles) return;
+    __shared__ double sv[kMbWords * kThreads];
+    const uint32_t tid = threadIdx.x, M = d.frames, f0 = blockIdx.x * kMbTile + tid * kMbRun;
+    const double aR = d.aR, aA = d.aA, oA = d.oA;
+    MbCo c;
+    mb_load_co(d, c);
+    double zl[kMbWords], zr[kMbWords], yl[3];
+    {
+        double cl[kMbWords], cr[kMbWords];
+        mb_start(MODE == 0 ? d.carry + (size_t)blockIdx.x * 2u * kMbWords : d.init, cl, cr, zl, zr);
+        if (MODE == 0) mb_run_x(d, c, f0, zl, zr);
+        else mb_run_terms(d, c, f0, zl, zr);
+        mb_join(d.pow, cl, cr, sv, zl, zr);
+    }
+    if (MODE == 1) {
+        // d_b over the run from a copy of the entry states, the release from 0 (lane 0: from the line's y1_b), joined; then y1_b over d_b
+        double cy1[3], u[3];
+#pragma unroll
+        for (int b = 0; b < 3; ++b) {
+            cy1[b] = d.init ? gloadd(d.init + 2u * kMbWords + 2u * b) : 0.0;
+            u[b] = tid ? 0.0 : cy1[b];
+        }
+        {
+            double tl[kMbWords], tr[kMbWords];
+#pragma unroll
+            for (uint32_t i = 0; i < kMbWords; ++i) { tl[i] = zl[i]; tr[i] = zr[i]; }
+            mb_detect_run(d, c, f0, tl, tr, u);
+        }
+#pragma unroll
+        for (int b = 0; b < 3; ++b) {
+            double last;
+            double v = comp_lane_scan<false>(u[b], d.pwR, cy1[b], sv, &last);
+#pragma unroll 1
+            for (uint32_t j = 0; j < kMbRun; j += 2) {
+                const uint32_t m = f0 + j;
+                d2v w = mb_load_dy(d, b, m);
+                v = fmax(w.x, aR * v);
+                w.x = v;
+                if (m + 1u == M) gstored(d.line + 2u * kMbWords + 2u * b, v);   // the chunk's last frame
+                v = fmax(w.y, aR * v);
+                w.y = v;
+                if (m + 2u == M) gstored(d.line + 2u * kMbWords + 2u * b, v);
+                if (m < M) gstore_d2(d.dy[b] + m, w.x, w.y);
+            }
+        }
+    }
+    // the attack over y1_b from 0 (lane 0: from the value entering the tile), joined: the yL_b entering the lane's run
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+        const double cin = MODE == 0 ? gloadd(d.carry2[b] + blockIdx.x) : (d.init ? gloadd(d.init + 2u * kMbWords + 2u * b + 1u) : 0.0);
+        double a = tid ? 0.0 : cin, last;
+#pragma unroll 1
+        for (uint32_t j = 0; j < kMbRun; j += 2) {
+            const d2v w = mb_load_dy(d, b, f0 + j);
+            a = aA * a + oA * w.x;
+            a = aA * a + oA * w.y;
+        }
+        yl[b] = comp_lane_scan<true>(a, d.pwA, cin, sv, &last);
+    }
+    const double mk0 = d.makeup[0], mk1 = d.makeup[1], mk2 = d.makeup[2];
+    const float wet = d.wet;
+#pragma unroll 1
+    for (uint32_t j = 0; j < kMbRun; j += 2) {
+        const uint32_t m = f0 + j;
+        if (m >= M) break;
+        const float4 x = load_pair(d.x, m, M);
+        const d2v y0 = mb_load_dy(d, 0, m), y1 = mb_load_dy(d, 1, m), y2 = mb_load_dy(d, 2, m);
+        float pl[2], pr[2];
+#pragma unroll
+        for (uint32_t h = 0; h < 2u; ++h) {
+            double bl[3], br[3];
+            mb_frame(c, zl, eq_in(h ? x.z : x.x), bl[0], bl[1], bl[2]);
+            mb_frame(c, zr, eq_in(h ? x.w : x.y), br[0], br[1], br[2]);
+            yl[0] = aA * yl[0] + oA * (h ? y0.y : y0.x);
+            yl[1] = aA * yl[1] + oA * (h ? y1.y : y1.x);
+            yl[2] = aA * yl[2] + oA * (h ? y2.y : y2.x);
+            const double g0 = exp10((mk0 - yl[0]) / 20.0), g1 = exp10((mk1 - yl[1]) / 20.0), g2 = exp10((mk2 - yl[2]) / 20.0);
+            pl[h] = (float)(((0.0 + bl[0] * g0) + bl[1] * g1) + bl[2] * g2);
+            pr[h] = (float)(((0.0 + br[0] * g0) + br[1] * g1) + br[2] * g2);
+            if (m + h + 1u == M) {   // the chunk's last frame: what the next chunk / block pull enters with
+#pragma unroll
+                for (uint32_t i = 0; i < kMbWords; i += 2) {
+                    gstore_d2(d.line + i, zl[i], zl[i + 1]);
+                    gstore_d2(d.line + kMbWords + i, zr[i], zr[i + 1]);
+                }
+#pragma unroll
+                for (uint32_t b = 0; b < 3u; ++b) gstored(d.line + 2u * kMbWords + 2u * b + 1u, yl[b]);
+            }
+        }
+        const float4 p = make_float4(pl[0], pr[0], pl[1], pr[1]);
+        // the reference's lerp (adsr.rs:42), f32
+        const float4 o = make_float4(x.x + wet * (p.x - x.x), x.y + wet * (p.y - x.y), x.z + wet * (p.z - x.z), x.w + wet * (p.w - x.w));
+        store_pair(d.out, m, M, epilogue4(o, d.pg));
+    }
+}
+
 constexpr int kMaxGridY = 65535;
 
 // Batched launches put the vertex index in grid.y (limit 65535): larger batches go out in slices.
@@ -8021,6 +8384,25 @@ void launch_lim_apply(const LimDesc* d, int n, uint32_t n_tiles, bool single, hi
         const dim3 grid(n_tiles, std::min(n - o, kMaxGridY));
         if (single) hipLaunchKernelGGL(k_lim_apply<true>, grid, dim3(kThreads), 0, s, d + o);
         else hipLaunchKernelGGL(k_lim_apply<false>, grid, dim3(kThreads), 0, s, d + o);
+    }
+}
+void launch_mb_local(const MbDesc* d, int n, uint32_t n_tiles, hipStream_t s) {
+    for (int o = 0; o < n && n_tiles; o += kMaxGridY)
+        hipLaunchKernelGGL(k_mb_local, dim3(n_tiles, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
+}
+void launch_mb_carry(const MbDesc* d, int n, hipStream_t s) {
+    for (int o = 0; o < n; o += kMaxGridY)
+        hipLaunchKernelGGL(k_mb_carry, dim3(2, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
+}
+void launch_mb_detect(const MbDesc* d, int n, uint32_t n_tiles, hipStream_t s) {
+    for (int o = 0; o < n && n_tiles; o += kMaxGridY)
+        hipLaunchKernelGGL(k_mb_detect, dim3(n_tiles, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
+}
+void launch_mb_apply(const MbDesc* d, int n, uint32_t n_tiles, bool single, hipStream_t s) {
+    for (int o = 0; o < n && n_tiles; o += kMaxGridY) {
+        const dim3 grid(n_tiles, std::min(n - o, kMaxGridY));
+        if (single) hipLaunchKernelGGL(k_mb_apply<1>, grid, dim3(kThreads), 0, s, d + o);
+        else hipLaunchKernelGGL(k_mb_apply<0>, grid, dim3(kThreads), 0, s, d + o);
     }
 }
 void launch_sample_loop(const LoopDesc* d, int n, uint32_t frames, hipStream_t s) {

@@ -25,6 +25,7 @@
 #include "vocoder_math.h"
 #include "filter_math.h"
 #include "limiter_math.h"
+#include "multiband_math.h"
 #include "lua_subset.h"
 #include "reverb_math.h"
 #include "master.h"
@@ -120,6 +121,7 @@ struct PhaserCall { std::string name; float gain, angle, wet; int stages; float 
 struct VocoderCall { std::string name; float gain, angle, wet; int bands; float lo_hz, hi_hz, q, response_ms, out_db; };
 struct FilterCall { std::string name; float gain, angle, wet; int kind; float freq_hz, q, lfo_oct, rate_hz, stereo; int shape; float env_oct, sens_db, attack_ms, release_ms; };
 struct LimiterCall { std::string name; float gain, angle, wet, ceiling_db, lookahead_ms, release_ms, drive_db; };
+struct MultibandCall { std::string name; float gain, angle, wet, lo_hz, hi_hz, threshold_db[3], ratio[3], attack_ms, release_ms, knee_db, makeup_db[3]; };
 struct GateCall { std::string name; float gain, angle, wet, threshold_db, hysteresis_db, hold_ms, attack_ms, release_ms, range_db; };
 struct SatCall { std::string name; float gain, angle, wet; int kind; float drive_db, bias, out_db; int oversample; };
 
@@ -248,6 +250,7 @@ int do_refresh(td_state* s, const std::string& contents) {
     std::vector<VocoderCall> vocoders;
     std::vector<FilterCall> filters;
     std::vector<LimiterCall> limiters;
+    std::vector<MultibandCall> multibands;
     size_t cs = s->cs, render_sr = s->render_sr, bd = s->bd;
     // std::mem::take (state.rs:79-80): the locals start from the previous values, the State's own fields are left
     // EMPTY until the script has run (state.rs:169-170) -- so they stay empty when the script fails
@@ -548,6 +551,21 @@ int do_refresh(td_state* s, const std::string& contents) {
                 fnum(c.release_ms) + "," + fnum(c.drive_db) + ")\n";
         return Value::nil();
     });
+    lua.set_function("add_multiband", [&](const std::vector<Value>& a) {   // this engine's own vertex (termdaw_amd.h td_graph_add_multiband)
+        const char* f = "add_multiband";   // (flat; the bands in the order low, mid, high)
+        multibands.push_back({to_str(f, a, 0), to_f32(f, a, 1), to_f32(f, a, 2), to_f32(f, a, 3), to_f32(f, a, 4), to_f32(f, a, 5),
+                              {to_f32(f, a, 6), to_f32(f, a, 7), to_f32(f, a, 8)}, {to_f32(f, a, 9), to_f32(f, a, 10), to_f32(f, a, 11)},
+                              to_f32(f, a, 12), to_f32(f, a, 13), to_f32(f, a, 14), {to_f32(f, a, 15), to_f32(f, a, 16), to_f32(f, a, 17)}});
+        auto& c = multibands.back();
+        // (out-of-range parameters are rejected here, where the line is known)
+        if (const char* why = tde::multiband::check(psr, c.lo_hz, c.hi_hz, c.threshold_db, c.ratio, c.attack_ms, c.release_ms, c.knee_db, c.makeup_db))
+            throw LuaError{std::string("add_multiband: multiband: ") + why};
+        dump += std::string(f) + "(\"" + c.name + "\"," + fnum(c.gain) + "," + fnum(c.angle) + "," + fnum(c.wet) + "," + fnum(c.lo_hz) + "," + fnum(c.hi_hz) + "," +
+                fnum(c.threshold_db[0]) + "," + fnum(c.threshold_db[1]) + "," + fnum(c.threshold_db[2]) + "," + fnum(c.ratio[0]) + "," + fnum(c.ratio[1]) + "," +
+                fnum(c.ratio[2]) + "," + fnum(c.attack_ms) + "," + fnum(c.release_ms) + "," + fnum(c.knee_db) + "," + fnum(c.makeup_db[0]) + "," +
+                fnum(c.makeup_db[1]) + "," + fnum(c.makeup_db[2]) + ")\n";
+        return Value::nil();
+    });
     lua.set_function("connect", [&](const std::vector<Value>& a) {
         edges.push_back({to_str("connect", a, 0), to_str("connect", a, 1)});
         dump += "connect(\"" + edges.back().first + "\",\"" + edges.back().second + "\")\n";
@@ -690,6 +708,8 @@ int do_refresh(td_state* s, const std::string& contents) {
                                  c.attack_ms, c.release_ms)) return 0;
     for (auto& c : limiters)
         if (!td_graph_add_limiter(s->g, c.name.c_str(), c.gain, c.angle, c.wet, c.ceiling_db, c.lookahead_ms, c.release_ms, c.drive_db)) return 0;
+    for (auto& c : multibands)
+        if (!td_graph_add_multiband(s->g, c.name.c_str(), c.gain, c.angle, c.wet, c.lo_hz, c.hi_hz, c.threshold_db, c.ratio, c.attack_ms, c.release_ms, c.knee_db, c.makeup_db)) return 0;
     for (auto& e : edges) td_graph_connect(s->g, e.first.c_str(), e.second.c_str());   // failures only warn (state.rs:459)
     for (auto& e : key_edges) td_graph_connect_key(s->g, e.first.c_str(), e.second.c_str());   // (after the edges; failures only warn, like theirs)
     td_graph_set_output(s->g, s->output_vertex.c_str());

@@ -169,7 +169,7 @@ class ProjectScript:
         self.calls = {k: [] for k in (
             "load_sample", "load_resource", "load_midi_floww", "add_sum", "add_normalize", "add_sampleloop",
             "add_sample_multi", "add_sample_lerp", "add_debug_sine", "add_synth", "add_sampsyn", "add_adsr",
-            "add_bandpass", "add_compressor", "add_eq", "add_delay", "add_saturator", "add_chorus", "add_reverb", "add_gate", "add_phaser", "add_vocoder", "add_filter", "add_limiter", "connect", "connect_key")}
+            "add_bandpass", "add_compressor", "add_eq", "add_delay", "add_saturator", "add_chorus", "add_reverb", "add_gate", "add_phaser", "add_vocoder", "add_filter", "add_limiter", "add_multiband", "connect", "connect_key")}
         self.resources = {}                 # path -> bytes (load_resource)
         self.script_order = []              # (fn, args) in call order, for to_lua()
 
@@ -284,6 +284,12 @@ class ProjectScript:
         """This engine's own vertex (include/termdaw_amd.h td_graph_add_limiter): no reference counterpart."""
         self._rec("add_limiter", name, gain, angle, wet, ceiling_db, lookahead_ms, release_ms, drive_db)
 
+    def add_multiband(self, name, gain, angle, wet, lo_hz, hi_hz, threshold_db, ratio, attack_ms, release_ms, knee_db, makeup_db):
+        """This engine's own vertex (include/termdaw_amd.h td_graph_add_multiband): no reference counterpart.  threshold_db, ratio and
+        makeup_db: three values each (low, mid, high); the script line is flat."""
+        self._rec("add_multiband", name, gain, angle, wet, lo_hz, hi_hz, tuple(threshold_db), tuple(ratio), attack_ms, release_ms, knee_db,
+                  tuple(makeup_db))
+
     def connect(self, a, b):
         self._rec("connect", a, b)
 
@@ -365,6 +371,8 @@ class ProjectScript:
             g.add_filter(*args)
         for args in self.calls["add_limiter"]:
             g.add_limiter(*args)
+        for args in self.calls["add_multiband"]:
+            g.add_multiband(*args)
         for a, b in self.calls["connect"]:
             g.connect(a, b)
         for a, b in self.calls["connect_key"]:   # (after the connect calls, as the front-end applies them)
@@ -419,6 +427,8 @@ class ProjectScript:
         for fn, args in self.script_order:
             if fn in ("load_sample", "load_midi_floww", "load_resource"):
                 args = (args[0], paths[args[1]]) + tuple(args[2:])
+            if fn == "add_multiband":   # (the script line is flat: the per-band triples in place)
+                args = tuple(y for a in args for y in (a if isinstance(a, tuple) else (a,)))
             lines.append("%s(%s);" % (fn, ", ".join(lit(a) for a in args)))
         return "\n".join(lines) + "\n"
 
@@ -600,6 +610,24 @@ def limiter_project(seconds=3.0, bl=1024, ceiling_db=-1.0, lookahead_ms=5.0, rel
     p.add_limiter("lim", 1.0, 0.0, wet, ceiling_db, lookahead_ms, release_ms, drive_db)
     p.connect("band", "lim")
     p.set_output("lim")
+    return p
+
+
+def multiband_project(seconds=3.0, n_src=8, lo_hz=200.0, hi_hz=2000.0, threshold_db=(-30.0, -30.0, -30.0), ratio=(4.0, 4.0, 4.0),
+                      attack_ms=5.0, release_ms=50.0, knee_db=6.0, makeup_db=(0.0, 0.0, 0.0), wet=1.0, seed_offset=0):
+    """BASELINE config 2's loops summed into a bus, the bus through a multiband vertex (this engine's own) into the output, in place
+    of the project's Normalize.  The loops' gains are scaled so the bus of `n_src` full-scale loops sits near -6 dB."""
+    p = config2(seconds, n_src, seed_offset)
+    loops = [a for a, b in p.calls["connect"] if b == "sum"]
+    p.calls["add_normalize"] = []
+    p.calls["connect"] = []
+    p.script_order = [(fn, a) for fn, a in p.script_order if fn not in ("add_normalize", "connect", "set_output")]
+    p.add_sum("bus", float(0.5 / np.sqrt(n_src)), 0.0)
+    p.add_multiband("mb", 1.0, 0.0, wet, lo_hz, hi_hz, threshold_db, ratio, attack_ms, release_ms, knee_db, makeup_db)
+    for a in loops:
+        p.connect(a, "bus")
+    p.connect("bus", "mb")
+    p.set_output("mb")
     return p
 
 
