@@ -10,10 +10,9 @@ import itertools
 import os
 import sys
 
-import numpy as np
-
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import eq_projects as EP  # noqa: E402
+import fx_rig  # noqa: E402
 
 RATES = EP.RATES
 INPUTS = EP.INPUTS
@@ -56,39 +55,10 @@ def random_delay_params(rng):
 
 
 def random_delay_project(seed, allow_sinf=True):
-    import test_gpu_fuzz as F
-    p = F.random_project(seed, allow_sinf=allow_sinf)
-    rng = np.random.default_rng(920_000 + seed)
-    gains, angles = [1.0, 1.0005, 0.5, 1.7, -0.8], [0.0, 0.0009, 30.0, -75.0, 120.0]
-    edges = [i for i, (fn, a) in enumerate(p.script_order) if fn == "connect" and a[0] != a[1]]
-    picks = sorted(set(int(i) for i in rng.choice(edges, size=min(len(edges), int(rng.integers(1, 4))), replace=False)), reverse=True)
-    first_add = min(i for i, (fn, _) in enumerate(p.script_order) if fn.startswith("add_"))
-    delays = []
-
-    def one(nm, gain, angle):
-        wet, t, f, c = random_delay_params(rng)
-        return (nm, gain, angle, wet, t, f, c)
-    for k, i in enumerate(picks):   # (from the back: the indices in front stay valid)
-        a, b = p.script_order[i][1]
-        nm = "d%d" % k
-        ci = p.calls["connect"].index((a, b))
-        p.calls["connect"][ci:ci + 1] = [(a, nm), (nm, b)]
-        p.script_order[i:i + 1] = [("connect", (a, nm)), ("connect", (nm, b))]
-        delays.append(one(nm, float(rng.choice(gains)), float(rng.choice(angles))))
-    if rng.random() < 0.3:   # ... and one as the output, behind whatever the output was
-        nm = "dout"
-        delays.append(one(nm, 1.0, 0.0))
-        p.calls["connect"].append((p.output_vertex, nm))
-        oi = max(i for i, (fn, _) in enumerate(p.script_order) if fn == "set_output")
-        p.script_order[oi:oi + 1] = [("connect", (p.output_vertex, nm)), ("set_output", (nm,))]
-        p.output_vertex = nm
-    for c in delays:
-        p.calls["add_delay"].append(c)
-        p.script_order.insert(first_add, ("add_delay", c))
-    return p
+    return fx_rig.splice_project(seed, allow_sinf, rng_offset=920_000, prefix="d", add_call="add_delay",
+                                 draw=lambda rng, p: random_delay_params(rng))
 
 
 def write_projects(args):
     """(base dir, seeds) -> the project dirs written: project.lua + assets, meta.txt (the block length)."""
-    base, seeds = args
-    return [write_project(random_delay_project(seed), os.path.join(base, "s%d" % seed)) for seed in seeds]
+    return fx_rig.write_projects(random_delay_project, args)

@@ -15,6 +15,7 @@ import numpy as np
 from termdaw_amd import workloads as W
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import fx_rig  # noqa: E402
 import np_eq as NE  # noqa: E402
 
 RATES = (44100, 48000, 96000)
@@ -115,48 +116,13 @@ def random_eq_params(rng, sr):
 
 
 def random_eq_project(seed, allow_sinf=True):
-    import test_gpu_fuzz as F
-    p = F.random_project(seed, allow_sinf=allow_sinf)
-    rng = np.random.default_rng(910_000 + seed)
-    gains, angles = [1.0, 1.0005, 0.5, 1.7, -0.8], [0.0, 0.0009, 30.0, -75.0, 120.0]
-    edges = [i for i, (fn, a) in enumerate(p.script_order) if fn == "connect" and a[0] != a[1]]
-    picks = sorted(set(int(i) for i in rng.choice(edges, size=min(len(edges), int(rng.integers(1, 4))), replace=False)), reverse=True)
-    first_add = min(i for i, (fn, _) in enumerate(p.script_order) if fn.startswith("add_"))
-    eqs = []
-
-    def one(nm, gain, angle):
-        wet, kind, f, q, g = random_eq_params(rng, 48000)   # (the sanitizer driver opens every project at 48 kHz)
-        return (nm, gain, angle, wet, kind, f, q, g)
-    for k, i in enumerate(picks):   # (from the back: the indices in front stay valid)
-        a, b = p.script_order[i][1]
-        nm = "q%d" % k
-        ci = p.calls["connect"].index((a, b))
-        p.calls["connect"][ci:ci + 1] = [(a, nm), (nm, b)]
-        p.script_order[i:i + 1] = [("connect", (a, nm)), ("connect", (nm, b))]
-        eqs.append(one(nm, float(rng.choice(gains)), float(rng.choice(angles))))
-    if rng.random() < 0.3:   # ... and one as the output, behind whatever the output was
-        nm = "qout"
-        eqs.append(one(nm, 1.0, 0.0))
-        p.calls["connect"].append((p.output_vertex, nm))
-        oi = max(i for i, (fn, _) in enumerate(p.script_order) if fn == "set_output")
-        p.script_order[oi:oi + 1] = [("connect", (p.output_vertex, nm)), ("set_output", (nm,))]
-        p.output_vertex = nm
-    for c in eqs:
-        p.calls["add_eq"].append(c)
-        p.script_order.insert(first_add, ("add_eq", c))
-    return p
+    return fx_rig.splice_project(seed, allow_sinf, rng_offset=910_000, prefix="q", add_call="add_eq",
+                                 draw=lambda rng, p: random_eq_params(rng, 48000))
 
 
-def write_project(p, d):
-    lua = p.to_lua(os.path.join(d, "assets"))
-    with open(os.path.join(d, "project.lua"), "w") as f:
-        f.write(lua)
-    with open(os.path.join(d, "meta.txt"), "w") as f:
-        f.write(str(p.bl))
-    return d
+write_project = fx_rig.write_project
 
 
 def write_projects(args):
     """(base dir, seeds) -> the project dirs written: project.lua + assets, meta.txt (the block length)."""
-    base, seeds = args
-    return [write_project(random_eq_project(seed), os.path.join(base, "s%d" % seed)) for seed in seeds]
+    return fx_rig.write_projects(random_eq_project, args)

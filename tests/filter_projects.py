@@ -11,10 +11,9 @@ import itertools
 import os
 import sys
 
-import numpy as np
-
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import eq_projects as EP  # noqa: E402
+import fx_rig  # noqa: E402
 import np_filter as NF  # noqa: E402
 
 RATES = EP.RATES
@@ -68,43 +67,17 @@ def random_filter_params(rng):
             str(rng.choice(SHAPES))) + env
 
 
+def _random_key(rng, order, nm):
+    """Half of the time a key from somewhere else in the graph."""
+    sources = sorted({a[0] for fn, a in order if fn == "connect"})
+    return [(str(rng.choice(sources)), nm)] if rng.random() < 0.5 else []
+
+
 def random_filter_project(seed, allow_sinf=True):
-    import test_gpu_fuzz as F
-    p = F.random_project(seed, allow_sinf=allow_sinf)
-    rng = np.random.default_rng(1_030_000 + seed)
-    gains, angles = [1.0, 1.0005, 0.5, 1.7, -0.8], [0.0, 0.0009, 30.0, -75.0, 120.0]
-    edges = [i for i, (fn, a) in enumerate(p.script_order) if fn == "connect" and a[0] != a[1]]
-    picks = sorted(set(int(i) for i in rng.choice(edges, size=min(len(edges), int(rng.integers(1, 4))), replace=False)), reverse=True)
-    first_add = min(i for i, (fn, _) in enumerate(p.script_order) if fn.startswith("add_"))
-    sources = sorted({a[0] for fn, a in p.script_order if fn == "connect"})
-    filters, keys = [], []
-    for k, i in enumerate(picks):   # (from the back: the indices in front stay valid)
-        a, b = p.script_order[i][1]
-        nm = "fl%d" % k
-        ci = p.calls["connect"].index((a, b))
-        p.calls["connect"][ci:ci + 1] = [(a, nm), (nm, b)]
-        p.script_order[i:i + 1] = [("connect", (a, nm)), ("connect", (nm, b))]
-        filters.append((nm, float(rng.choice(gains)), float(rng.choice(angles))) + random_filter_params(rng))
-        if rng.random() < 0.5:   # a key from somewhere else in the graph (an edge that would close a loop only warns)
-            keys.append((str(rng.choice(sources)), nm))
-    if rng.random() < 0.3:   # ... and one as the output, behind whatever the output was
-        nm = "flout"
-        filters.append((nm, 1.0, 0.0) + random_filter_params(rng))
-        p.calls["connect"].append((p.output_vertex, nm))
-        oi = max(i for i, (fn, _) in enumerate(p.script_order) if fn == "set_output")
-        p.script_order[oi:oi + 1] = [("connect", (p.output_vertex, nm)), ("set_output", (nm,))]
-        p.output_vertex = nm
-    for c in filters:
-        p.calls["add_filter"].append(c)
-        p.script_order.insert(first_add, ("add_filter", c))
-    oi = max(i for i, (fn, _) in enumerate(p.script_order) if fn == "set_output")
-    for kk in keys:
-        p.calls["connect_key"].append(kk)
-        p.script_order.insert(oi, ("connect_key", kk))
-    return p
+    return fx_rig.splice_project(seed, allow_sinf, rng_offset=1_030_000, prefix="fl", add_call="add_filter",
+                                 draw=lambda rng, p: random_filter_params(rng), draw_keys=_random_key)
 
 
 def write_projects(args):
     """(base dir, seeds) -> the project dirs written: project.lua + assets, meta.txt (the block length)."""
-    base, seeds = args
-    return [EP.write_project(random_filter_project(seed), os.path.join(base, "s%d" % seed)) for seed in seeds]
+    return fx_rig.write_projects(random_filter_project, args)

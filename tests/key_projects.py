@@ -15,6 +15,7 @@ from termdaw_amd import workloads as W
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import eq_projects as EP  # noqa: E402
+import fx_rig  # noqa: E402
 import gate_projects as GP  # noqa: E402
 
 GATE_CASE = (-30.0, 6.0, 10.0, 1.0, 100.0, -20.0)   # test_gpu_gate.CASE: threshold, hysteresis, hold, attack, release, range
@@ -107,5 +108,4 @@ def random_key_project(seed, allow_sinf=True):
 
 def write_projects(args):
     """(base dir, seeds) -> the project dirs written: project.lua + assets, meta.txt (the block length)."""
-    base, seeds = args
-    return [EP.write_project(random_key_project(seed), os.path.join(base, "s%d" % seed)) for seed in seeds]
+    return fx_rig.write_projects(random_key_project, args)

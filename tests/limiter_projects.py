@@ -14,7 +14,7 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import eq_projects as EP  # noqa: E402
+import fx_rig  # noqa: E402
 import gate_projects as GP  # noqa: E402
 
 RATES = GP.RATES
@@ -60,16 +60,7 @@ def add_limiter(p, name, src, case, wet=1.0, gain=1.0, angle=0.0):
 
 
 def oracle_input(kind, sr):
-    """The grid's input as the GPU test sees it: the second render of `bus` (the first leaves the sample_multi voices sounding),
-    here by the CPU oracle -- the engine's own render is the oracle's, bit for bit."""
-    from oracle import binding as oracle
-    p = base_project(kind, sr=sr)
-    sb, fb, g = p.build(oracle)
-    g.render_all(sb, fb, p.cs, 16)
-    fb.set_time(0)
-    g.set_time(0)
-    g.reset_normalize_vertices()
-    return g.render_all(sb, fb, p.cs, 16)[1]
+    return fx_rig.oracle_input(kind, sr, base_project)
 
 
 def random_limiter_params(rng, sr):
@@ -82,35 +73,10 @@ def random_limiter_params(rng, sr):
 
 
 def random_limiter_project(seed, allow_sinf=True):
-    import test_gpu_fuzz as F
-    p = F.random_project(seed, allow_sinf=allow_sinf)
-    rng = np.random.default_rng(990_000 + seed)
-    gains, angles = [1.0, 1.0005, 0.5, 1.7, -0.8], [0.0, 0.0009, 30.0, -75.0, 120.0]
-    edges = [i for i, (fn, a) in enumerate(p.script_order) if fn == "connect" and a[0] != a[1]]
-    picks = sorted(set(int(i) for i in rng.choice(edges, size=min(len(edges), int(rng.integers(1, 4))), replace=False)), reverse=True)
-    first_add = min(i for i, (fn, _) in enumerate(p.script_order) if fn.startswith("add_"))
-    lims = []
-    for k, i in enumerate(picks):   # (from the back: the indices in front stay valid)
-        a, b = p.script_order[i][1]
-        nm = "lm%d" % k
-        ci = p.calls["connect"].index((a, b))
-        p.calls["connect"][ci:ci + 1] = [(a, nm), (nm, b)]
-        p.script_order[i:i + 1] = [("connect", (a, nm)), ("connect", (nm, b))]
-        lims.append((nm, float(rng.choice(gains)), float(rng.choice(angles))) + random_limiter_params(rng, p.psr))
-    if rng.random() < 0.3:   # ... and one as the output, behind whatever the output was
-        nm = "lmout"
-        lims.append((nm, 1.0, 0.0) + random_limiter_params(rng, p.psr))
-        p.calls["connect"].append((p.output_vertex, nm))
-        oi = max(i for i, (fn, _) in enumerate(p.script_order) if fn == "set_output")
-        p.script_order[oi:oi + 1] = [("connect", (p.output_vertex, nm)), ("set_output", (nm,))]
-        p.output_vertex = nm
-    for c in lims:
-        p.calls["add_limiter"].append(c)
-        p.script_order.insert(first_add, ("add_limiter", c))
-    return p
+    return fx_rig.splice_project(seed, allow_sinf, rng_offset=990_000, prefix="lm", add_call="add_limiter",
+                                 draw=lambda rng, p: random_limiter_params(rng, p.psr))
 
 
 def write_projects(args):
     """(base dir, seeds) -> the project dirs written: project.lua + assets, meta.txt (the block length)."""
-    base, seeds = args
-    return [EP.write_project(random_limiter_project(seed), os.path.join(base, "s%d" % seed)) for seed in seeds]
+    return fx_rig.write_projects(random_limiter_project, args)

@@ -14,6 +14,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import eq_projects as EP  # noqa: E402
+import fx_rig  # noqa: E402
 import np_multiband as NM  # noqa: E402
 
 RATES = EP.RATES
@@ -72,28 +73,22 @@ def random_multiband_params(rng):
 
 
 def random_multiband_project(seed, allow_sinf=True):
-    import test_gpu_fuzz as F
-    p = F.random_project(seed, allow_sinf=allow_sinf)
-    rng = np.random.default_rng(1_212_000 + seed)
-    gains, angles = [1.0, 1.0005, 0.5, 1.7, -0.8], [0.0, 0.0009, 30.0, -75.0, 120.0]
-    edges = [i for i, (fn, a) in enumerate(p.script_order) if fn == "connect" and a[0] != a[1]]
-    picks = sorted(set(int(i) for i in rng.choice(edges, size=min(len(edges), int(rng.integers(1, 4))), replace=False)), reverse=True)
-    first_add = min(i for i, (fn, _) in enumerate(p.script_order) if fn.startswith("add_"))
-    mbs = []
-    for k, i in enumerate(picks):   # (from the back: the indices in front stay valid)
-        a, b = p.script_order[i][1]
-        nm = "mb%d" % k
-        ci = p.calls["connect"].index((a, b))
-        p.calls["connect"][ci:ci + 1] = [(a, nm), (nm, b)]
-        p.script_order[i:i + 1] = [("connect", (a, nm)), ("connect", (nm, b))]
-        mbs.append((nm, float(rng.choice(gains)), float(rng.choice(angles))) + random_multiband_params(rng))
-    for c in mbs:
-        p.calls["add_multiband"].append(c)
-        p.script_order.insert(first_add, ("add_multiband", c))
-    return p
+    return fx_rig.splice_project(seed, allow_sinf, rng_offset=1_212_000, prefix="mb", add_call="add_multiband",
+                                 draw=lambda rng, p: random_multiband_params(rng), as_output=False)
 
 
 def write_projects(args):
     """(base dir, seeds) -> the project dirs written: project.lua + assets, meta.txt (the block length)."""
-    base, seeds = args
-    return [EP.write_project(random_multiband_project(seed), os.path.join(base, "s%d" % seed)) for seed in seeds]
+    return fx_rig.write_projects(random_multiband_project, args)
+
+
+# ---- the two-tone case of the non-vacuity tests (host and GPU) ----
+TONE_CASE = (400.0, 3000.0, (0.0, 0.0, -30.0), (1.0, 1.0, 4.0), 5.0, 50.0, 6.0, (0.0, 0.0, 0.0))
+
+
+def tone_lines(y, sr=48000):
+    """(100 Hz, 8 kHz): the two lines' amplitudes over the last 8 192 frames, in dB."""
+    seg = y[-8192:, 0].astype(np.float64)
+    t = np.arange(len(seg)) / sr
+    w = np.hanning(len(seg))
+    return tuple(20.0 * np.log10(2.0 * abs(np.sum(seg * w * np.exp(-2j * np.pi * f * t))) / w.sum()) for f in (100.0, 8000.0))

@@ -7,7 +7,6 @@ projects without the vertex."""
 import math
 import multiprocessing
 import os
-import shutil
 import subprocess
 import sys
 
@@ -18,12 +17,9 @@ from termdaw_amd import workloads as W
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import chorus_projects as CP  # noqa: E402
+import fx_rig  # noqa: E402
 import np_chorus as NC  # noqa: E402
-import test_eq_host as TE  # noqa: E402
-import test_loudness_host as L  # noqa: E402
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "termdaw_amd", "csrc")
+from fx_rig import ENV, driver_report, PARENT_LAUNCHES  # noqa: E402
 SR = 48000
 
 
@@ -206,7 +202,7 @@ def test_range_ends_are_accepted_and_wet_is_clamped(api):
 
 
 def _lua(line):
-    return 'add_sum("in", 1.0, 0.0);\n%s\nconnect("in", "w");\nset_output("w");\n' % line
+    return fx_rig._lua(line, "w")
 
 
 LUA_BAD = [(k, c) for k, c in BAD if k != "shape" and all(math.isfinite(v) for v in c.values())]
@@ -255,32 +251,11 @@ def test_project_script_records_and_writes_the_call(tmp_path):
 
 
 # ---- the host engine under sanitizers ----
-WRAPS = ["-Wl,--wrap=_ZN3tdk17launch_band_auditEPKNS_9AuditHeadEiP12ihipStream_t",
-         "-Wl,--wrap=_ZN3tdk17launch_band_chainEPKNS_12BandScanDescEijjbP12ihipStream_t"]
-
-
-def _build(out_dir):
-    flags = ["-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-ffp-contract=off",
-             "-D__HIP_PLATFORM_AMD__", "-I", "/opt/rocm/include", "-I", CSRC, "-I", os.path.join(ROOT, "include")]
-    jobs = [(os.path.join(CSRC, f), os.path.join(out_dir, f + ".o")) for f in L.SOURCES]
-    jobs += [(os.path.join(ROOT, "tests", f), os.path.join(out_dir, f + ".o")) for f in ("mock_hip.cpp", "mock_guard.cpp", "mock_chorus.cpp", "asan_fx.cpp")]
-    procs = [subprocess.Popen(["g++"] + flags + ["-c", src, "-o", obj]) for src, obj in jobs]
-    for p in procs:
-        assert p.wait() == 0
-    exe = os.path.join(out_dir, "asan_chorus")
-    # (mock_guard.cpp listens to the guard's launches of mock_hip.cpp: ld --wrap)
-    subprocess.check_call(["g++", "-fsanitize=address,undefined", "-o", exe] + WRAPS + [o for _, o in jobs] + ["-lpthread", "-ldl"])
-    return exe
 
 
 @pytest.fixture(scope="module")
 def asan_exe(tmp_path_factory):
-    if shutil.which("g++") is None or not os.path.exists("/opt/rocm/include/hip/hip_runtime_api.h"):
-        pytest.skip("needs g++ and the HIP headers")
-    return _build(str(tmp_path_factory.mktemp("asan_chorus")))
-
-
-ENV = TE.ENV
+    return fx_rig.asan_exe(tmp_path_factory, "asan_chorus", ["mock_guard.cpp", "mock_chorus.cpp", "asan_fx.cpp"])
 
 
 def test_chorus_projects_under_sanitizers(asan_exe, tmp_path):
@@ -318,54 +293,14 @@ CHO = (3, 20.0, 4.0, 0.8, 0.25, "sine")
 
 
 def _guard_project(shape, wet=0.75, bl=1024):
-    p = W.ProjectScript(SR, bl)
-    p.set_length(0.5)
-    p.assets["a"] = W.Asset(W.noise_int16(7, 9000))
-    p.load_sample("a", "a", "")
-    p.event_files["f"] = np.array([(0.01, 60.0, 0.8), (0.2, 60.0, 0.0), (0.25, 62.0, 0.6)], np.float32)
-    p.load_midi_floww("f", "f")
-    if shape in ("band_up", "band_plain", "band_dry"):   # loop -> band-pass -> chorus | sum | chorus with wet < 0.0001 (a k_sum launch, gain 1)
-        p.add_sampleloop("s", 1.0, 0.0, "a")
-        p.add_bandpass("b", 1.0, 0.0, 1.0, 300.0, 5000.0, True)
-        if shape == "band_up":
-            p.add_chorus("e", 1.0, 0.0, wet, *CHO)
-        elif shape == "band_dry":
-            p.add_chorus("e", 1.0, 0.0, 0.00009, *CHO)
-        else:
-            p.add_sum("e", 1.0, 0.0)
-        p.connect("s", "b"); p.connect("b", "e"); p.set_output("e")
-    else:                        # synth -> chorus | sum
-        p.add_synth("y", 1.0, 0.0, "f", 0.4, 0.3, W.HIT_ADSR, 1.0, 0.8, W.NOTE_ADSR, 0.5, W.STD_ADSR)
-        if shape == "sine_up":
-            p.add_chorus("e", 1.0, 0.0, wet, *CHO)
-        else:
-            p.add_sum("e", 1.0, 0.0)
-        p.connect("y", "e"); p.set_output("e")
-    return p
-
-
-def _run(asan_exe, tmp_path, projects):
-    dirs = {name: CP.write_project(p, str(tmp_path / name)) for name, p in projects.items()}
-    r = subprocess.run([asan_exe] + list(dirs.values()), env=dict(os.environ, **ENV), capture_output=True, text=True, timeout=1800)
-    assert r.returncode == 0, (r.stdout[-800:], r.stderr[-4000:])
-    fams, gains, redo = {}, {}, {}
-    for ln in r.stdout.splitlines():
-        for tag, store in (("launches ", fams), ("guard ", gains), ("redo ", redo)):
-            if ln.startswith(tag):
-                d, rest = ln[len(tag):].split(":", 1)
-                store[d] = rest.split()
-    back = {d: name for name, d in dirs.items()}
-    fams = {back[d]: dict((kv.split("=")[0], int(kv.split("=")[1])) for kv in v) for d, v in fams.items()}   # (dicts keep the driver's order)
-    gains = {back[d]: dict((kv.split("=")[0], float(kv.split("=")[1])) for kv in v) for d, v in gains.items()}
-    redo = {back[d]: dict(kv.split("=") for kv in v) for d, v in redo.items()}
-    return fams, gains, redo
+    return fx_rig.guard_project(shape, lambda p, name, dry: p.add_chorus(name, 1.0, 0.0, 0.00009 if dry else wet, *CHO), name="e", sr=SR, bl=bl)
 
 
 def test_guard_modes_carry_the_estimate_through_a_chorus(api, asan_exe, tmp_path):
     """band_mode 2 / sine_mode 2 (the driver's profiled render): upstream of a chorus the scan / fast forms stay, and the guard's
     estimate at the output is the one of the same project without the vertex times (1 - wet) + wet Hch."""
     shapes = ("band_up", "band_plain", "band_dry", "sine_up", "sine_free")
-    fams, gains, _ = _run(asan_exe, tmp_path, {s: _guard_project(s) for s in shapes})
+    fams, gains, _ = driver_report(asan_exe, tmp_path, {s: _guard_project(s) for s in shapes})
     exact = ("k_band_pass", "k_band_spec")
     for s in ("band_up", "band_plain", "band_dry"):
         assert "k_band_scan" in fams[s] and not any(k in fams[s] for k in exact), (s, fams[s])
@@ -390,7 +325,7 @@ def test_a_guarded_pull_that_runs_again_enters_with_the_line_it_first_entered_wi
     the line; the second and the third continue from it, so the guard copies both halves in front of the pull and puts them -- and
     the parity and the frame count on the host -- back in front of the second run: both runs find the same stamp in the same
     half, the one the run before them left last."""
-    _, _, redo = _run(asan_exe, tmp_path, {"band_up": _guard_project("band_up"), "band_plain": _guard_project("band_plain")})
+    _, _, redo = driver_report(asan_exe, tmp_path, {"band_up": _guard_project("band_up"), "band_plain": _guard_project("band_plain")})
     assert int(redo["band_up"]["redos"]) == 3 and int(redo["band_plain"]["redos"]) == 3, redo
     e = [int(v) for v in redo["band_up"]["entries"].split(",")]
     assert len(e) == 4 and e[0] == e[1] and e[2] == e[3] and e[2] == e[0] + 2, e
@@ -401,7 +336,7 @@ def test_projects_without_a_chorus_keep_their_launch_list(asan_exe, tmp_path):
     """The launch lists of drum_project, config 2 and config 4 (families and launch counts of one profiled render under the
     front-end's guard modes) as the parent commit compiled them."""
     projects = {"drums": W.drum_project(seconds=0.5), "config2": W.config2(seconds=0.5, n_src=8), "config4": W.config4(seconds=0.5, depth=6)}
-    fams, _, _ = _run(asan_exe, tmp_path, projects)
+    fams, _, _ = driver_report(asan_exe, tmp_path, projects)
     for name in projects:
         got = " ".join("%s=%d" % kv for kv in fams[name].items())
-        assert not any(k.startswith("k_chorus") for k in fams[name]) and got == TE.PARENT_LAUNCHES[name], (name, got)
+        assert not any(k.startswith("k_chorus") for k in fams[name]) and got == PARENT_LAUNCHES[name], (name, got)

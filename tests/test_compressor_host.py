@@ -7,7 +7,6 @@ compressor the exact forms, downstream of it the scan -- read from the launch fa
 import math
 import multiprocessing
 import os
-import shutil
 import subprocess
 import sys
 
@@ -18,11 +17,9 @@ from termdaw_amd import workloads as W
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import comp_projects as CP  # noqa: E402
+import fx_rig  # noqa: E402
 import np_compressor as NC  # noqa: E402
-import test_loudness_host as L  # noqa: E402
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "termdaw_amd", "csrc")
+from fx_rig import ENV, _families  # noqa: E402
 
 GOOD = dict(threshold_db=-18.0, ratio=4.0, attack_ms=5.0, release_ms=100.0, knee_db=6.0, makeup_db=0.0)
 RANGES = dict(threshold_db=(-80.0, 0.0), ratio=(1.0, 1000.0), attack_ms=(0.0, 1000.0), release_ms=(1.0, 10000.0), knee_db=(0.0, 40.0),
@@ -33,39 +30,25 @@ BAD = [(k, v) for k, (lo, hi) in RANGES.items() for v in (np.nextafter(np.float3
 
 
 def _args(**kw):
-    a = dict(GOOD)
-    a.update(kw)
-    return [float(a[k]) for k in ORDER]
+    return fx_rig._args(GOOD, ORDER, as_float=True, **kw)
 
 
 @pytest.mark.parametrize("name,value", BAD)
 def test_out_of_range_parameters_are_rejected_by_name(api, name, value):
-    g = api.Graph(64, 48000)
-    with pytest.raises(api.TermdawError, match=name):
-        g.add_compressor("c", 1.0, 0.0, 1.0, *_args(**{name: value}))
+    fx_rig.out_of_range_is_rejected_by_name(api, 48000, lambda g, *a: g.add_compressor("c", 1.0, 0.0, 1.0, *a), None, _args(**{name: value}), name)
 
 
 def test_range_ends_are_accepted(api):
-    g = api.Graph(64, 48000)
-    g.add_sum("in", 1.0, 0.0)
-    for i, end in enumerate((0, 1)):
-        g.add_compressor("c%d" % i, 1.0, 0.0, 1.0, *[RANGES[k][end] for k in ORDER])
-        assert g.connect("in", "c%d" % i)
-    g.add_compressor("wet", 1.0, 0.0, 7.0, *_args())   # (wet is clamped, not rejected: graph.rs:256)
-    g.add_compressor("dry", 1.0, 0.0, -3.0, *_args())
-    assert g.set_output("c1") and g.check_graph()
+    fx_rig.range_ends_are_accepted(api, 48000, lambda g, *a: g.add_compressor(*a), "c", RANGES, ORDER, _args())
 
 
 def _lua(line):
-    return 'add_sum("in", 1.0, 0.0);\n%s\nconnect("in", "c");\nset_output("c");\n' % line
+    return fx_rig._lua(line, "c")
 
 
 @pytest.mark.parametrize("name,value", [(k, v) for k, v in BAD if math.isfinite(v)])
 def test_lua_rejects_the_same_ranges(api, name, value):
-    s = api.State("", 48000, 64)
-    line = 'add_compressor("c", 1.0, 0.0, 1.0, %s);' % ", ".join(repr(float(v)) for v in _args(**{name: value}))
-    assert not s.refresh(_lua(line))
-    assert name in api.last_error(), api.last_error()
+    fx_rig.lua_rejects_the_same_ranges(api, 48000, "add_compressor", _args(**{name: value}), name)
 
 
 def test_lua_accepts_and_dumps_the_canonical_line(api):
@@ -186,27 +169,9 @@ def test_twin_split_anywhere_is_the_one_piece_result(cut):
 
 
 # ---- the host engine under sanitizers ----
-def _build(out_dir):
-    flags = ["-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-ffp-contract=off",
-             "-D__HIP_PLATFORM_AMD__", "-I", "/opt/rocm/include", "-I", CSRC, "-I", os.path.join(ROOT, "include")]
-    jobs = [(os.path.join(CSRC, f), os.path.join(out_dir, f + ".o")) for f in L.SOURCES]
-    jobs += [(os.path.join(ROOT, "tests", f), os.path.join(out_dir, f + ".o")) for f in ("mock_hip.cpp", "mock_comp.cpp", "asan_comp.cpp")]
-    procs = [subprocess.Popen(["g++"] + flags + ["-c", src, "-o", obj]) for src, obj in jobs]
-    for p in procs:
-        assert p.wait() == 0
-    exe = os.path.join(out_dir, "asan_comp")
-    subprocess.check_call(["g++", "-fsanitize=address,undefined", "-o", exe] + [o for _, o in jobs] + ["-lpthread", "-ldl"])
-    return exe
-
-
 @pytest.fixture(scope="module")
 def asan_exe(tmp_path_factory):
-    if shutil.which("g++") is None or not os.path.exists("/opt/rocm/include/hip/hip_runtime_api.h"):
-        pytest.skip("needs g++ and the HIP headers")
-    return _build(str(tmp_path_factory.mktemp("asan_comp")))
-
-
-ENV = dict(ASAN_OPTIONS="detect_leaks=0:allocator_may_return_null=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1", TD_ALLOC_CACHE_MB="0")
+    return fx_rig.asan_exe(tmp_path_factory, "asan_comp", ["mock_comp.cpp", "asan_comp.cpp"])
 
 
 def test_compressor_projects_under_sanitizers(asan_exe, tmp_path):
@@ -232,67 +197,20 @@ def test_compressor_projects_under_sanitizers(asan_exe, tmp_path):
 
 
 def _guard_project(shape):
-    p = W.ProjectScript(48000, 1024)
-    p.set_length(0.5)
-    p.assets["a"] = W.Asset(W.noise_int16(7, 9000))
-    p.load_sample("a", "a", "")
-    p.event_files["f"] = np.array([(0.01, 60.0, 0.8), (0.2, 60.0, 0.0), (0.25, 62.0, 0.6)], np.float32)
-    p.load_midi_floww("f", "f")
-    comp = ("c", 1.0, 0.0, 1.0, -30.0, 4.0, 1.0, 100.0, 6.0, 0.0)
-    if shape == "band_up":       # loop -> band-pass -> compressor
-        p.add_sampleloop("s", 1.0, 0.0, "a")
-        p.add_bandpass("b", 1.0, 0.0, 1.0, 300.0, 5000.0, True)
-        p.add_compressor(*comp)
-        p.connect("s", "b"); p.connect("b", "c"); p.set_output("c")
-    elif shape == "band_down":   # loop -> compressor -> band-pass
-        p.add_sampleloop("s", 1.0, 0.0, "a")
-        p.add_compressor(*comp)
-        p.add_bandpass("b", 1.0, 0.0, 1.0, 300.0, 5000.0, True)
-        p.connect("s", "c"); p.connect("c", "b"); p.set_output("b")
-    elif shape == "band_both":   # loop -> band-pass -> compressor -> band-pass
-        p.add_sampleloop("s", 1.0, 0.0, "a")
-        p.add_bandpass("b", 1.0, 0.0, 1.0, 300.0, 5000.0, True)
-        p.add_compressor(*comp)
-        p.add_bandpass("b2", 1.0, 0.0, 1.0, 300.0, 5000.0, True)
-        p.connect("s", "b"); p.connect("b", "c"); p.connect("c", "b2"); p.set_output("b2")
-    elif shape == "sine_up":     # synth -> compressor
-        p.add_synth("y", 1.0, 0.0, "f", 0.4, 0.3, W.HIT_ADSR, 1.0, 0.8, W.NOTE_ADSR, 0.5, W.STD_ADSR)
-        p.add_compressor(*comp)
-        p.connect("y", "c"); p.set_output("c")
-    else:                        # synth -> sum: the control
-        p.add_synth("y", 1.0, 0.0, "f", 0.4, 0.3, W.HIT_ADSR, 1.0, 0.8, W.NOTE_ADSR, 0.5, W.STD_ADSR)
-        p.add_sum("c", 1.0, 0.0)
-        p.connect("y", "c"); p.set_output("c")
-    return p
+    return fx_rig.guard_project(shape, lambda p, name, dry: p.add_compressor(name, 1.0, 0.0, 1.0, -30.0, 4.0, 1.0, 100.0, 6.0, 0.0))
 
 
 def test_guard_modes_keep_the_exact_forms_upstream_of_a_compressor(asan_exe, tmp_path):
     """band_mode 2 / sine_mode 2 (the driver's profiled render): the launch families each shape went through."""
-    dirs = {}
-    for shape in ("band_up", "band_down", "band_both", "sine_up", "sine_free"):
-        d = str(tmp_path / shape)
-        p = _guard_project(shape)
-        lua = p.to_lua(os.path.join(d, "assets"))
-        with open(os.path.join(d, "project.lua"), "w") as f:
-            f.write(lua)
-        with open(os.path.join(d, "meta.txt"), "w") as f:
-            f.write(str(p.bl))
-        dirs[shape] = d
-    r = subprocess.run([asan_exe] + list(dirs.values()), env=dict(os.environ, **ENV), capture_output=True, text=True, timeout=1800)
-    assert r.returncode == 0, (r.stdout[-800:], r.stderr[-4000:])
-    fams = {}
-    for ln in r.stdout.splitlines():
-        if ln.startswith("launches "):
-            d, rest = ln[len("launches "):].split(":", 1)
-            fams[d] = dict((kv.split("=")[0], int(kv.split("=")[1])) for kv in rest.split())
+    fams = _families(asan_exe, tmp_path, {s: _guard_project(s) for s in ("band_up", "band_down", "band_both", "sine_up", "sine_free")})
     exact = ("k_band_pass", "k_band_spec")
-    up, down, both = fams[dirs["band_up"]], fams[dirs["band_down"]], fams[dirs["band_both"]]
+    up, down, both = fams["band_up"], fams["band_down"], fams["band_both"]
     assert "k_band_scan" not in up and any(k in up for k in exact), up
     assert "k_band_scan" in down and not any(k in down for k in exact), down
     assert "k_band_scan" in both and any(k in both for k in exact), both
     for f in (up, down, both):
         assert all(f.get(k) == 1 for k in ("k_comp_detect", "k_comp_carry_y1", "k_comp_env", "k_comp_carry_yl", "k_comp_apply")), f
-    sup, sfree = fams[dirs["sine_up"]], fams[dirs["sine_free"]]
+    sup, sfree = fams["sine_up"], fams["sine_free"]
     assert "k_sine_probe" not in sup and "k_synth" in sup, sup
     assert "k_sine_probe" in sfree or "k_sources" in sfree or "k_synth" in sfree, sfree
     assert ("k_sine_probe" in sfree), sfree

@@ -6,7 +6,6 @@ backup of the line; and the launch lists of projects without the vertex."""
 import math
 import multiprocessing
 import os
-import shutil
 import subprocess
 import sys
 
@@ -17,12 +16,9 @@ from termdaw_amd import workloads as W
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import delay_projects as DP  # noqa: E402
+import fx_rig  # noqa: E402
 import np_delay as ND  # noqa: E402
-import test_eq_host as TE  # noqa: E402
-import test_loudness_host as L  # noqa: E402
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "termdaw_amd", "csrc")
+from fx_rig import ENV, driver_report, PARENT_LAUNCHES, oracle_input  # noqa: E402
 
 
 # ---- td_delay_params ----
@@ -154,7 +150,7 @@ def test_range_ends_are_accepted_and_wet_is_clamped(api):
 
 
 def _lua(line):
-    return 'add_sum("in", 1.0, 0.0);\n%s\nconnect("in", "d");\nset_output("d");\n' % line
+    return fx_rig._lua(line, "d")
 
 
 @pytest.mark.parametrize("name,value", [(k, v) for k, v in BAD if math.isfinite(v)])
@@ -202,7 +198,7 @@ def test_the_emulated_scan_stays_inside_the_committed_constant():
     worst, weakest, changed, multi = (0.0, None), (9e9, None), 0, 0
     for sr in DP.RATES:
         for kind in DP.INPUTS:
-            x = TE.oracle_input(kind, sr)
+            x = oracle_input(kind, sr)
             assert np.abs(x).max() > 0.05
             for t, f, c in DP.grid_cases(sr):
                 D, gs, gc, _ = ND.params(sr, t, f, c)
@@ -229,32 +225,11 @@ def test_the_emulated_scan_stays_inside_the_committed_constant():
 
 
 # ---- the host engine under sanitizers ----
-WRAPS = ["-Wl,--wrap=_ZN3tdk17launch_band_auditEPKNS_9AuditHeadEiP12ihipStream_t",
-         "-Wl,--wrap=_ZN3tdk17launch_band_chainEPKNS_12BandScanDescEijjbP12ihipStream_t"]
-
-
-def _build(out_dir):
-    flags = ["-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-ffp-contract=off",
-             "-D__HIP_PLATFORM_AMD__", "-I", "/opt/rocm/include", "-I", CSRC, "-I", os.path.join(ROOT, "include")]
-    jobs = [(os.path.join(CSRC, f), os.path.join(out_dir, f + ".o")) for f in L.SOURCES]
-    jobs += [(os.path.join(ROOT, "tests", f), os.path.join(out_dir, f + ".o")) for f in ("mock_hip.cpp", "mock_guard.cpp", "mock_delay.cpp", "asan_fx.cpp")]
-    procs = [subprocess.Popen(["g++"] + flags + ["-c", src, "-o", obj]) for src, obj in jobs]
-    for p in procs:
-        assert p.wait() == 0
-    exe = os.path.join(out_dir, "asan_delay")
-    # (mock_guard.cpp listens to the guard's launches of mock_hip.cpp: ld --wrap)
-    subprocess.check_call(["g++", "-fsanitize=address,undefined", "-o", exe] + WRAPS + [o for _, o in jobs] + ["-lpthread", "-ldl"])
-    return exe
 
 
 @pytest.fixture(scope="module")
 def asan_exe(tmp_path_factory):
-    if shutil.which("g++") is None or not os.path.exists("/opt/rocm/include/hip/hip_runtime_api.h"):
-        pytest.skip("needs g++ and the HIP headers")
-    return _build(str(tmp_path_factory.mktemp("asan_delay")))
-
-
-ENV = TE.ENV
+    return fx_rig.asan_exe(tmp_path_factory, "asan_delay", ["mock_guard.cpp", "mock_delay.cpp", "asan_fx.cpp"])
 
 
 def test_delay_projects_under_sanitizers(asan_exe, tmp_path):
@@ -287,58 +262,18 @@ def test_delay_projects_under_sanitizers(asan_exe, tmp_path):
 
 
 def _guard_project(shape, wet=0.75, feedback=0.5):
-    p = W.ProjectScript(48000, 1024)
-    p.set_length(0.5)
-    p.assets["a"] = W.Asset(W.noise_int16(7, 9000))
-    p.load_sample("a", "a", "")
-    p.event_files["f"] = np.array([(0.01, 60.0, 0.8), (0.2, 60.0, 0.0), (0.25, 62.0, 0.6)], np.float32)
-    p.load_midi_floww("f", "f")
-    dl = ("e", 1.0, 0.0, wet, 10.0, feedback, 0.35)   # 480 frames: below the block length
-    if shape in ("band_up", "band_plain", "band_dry"):   # loop -> band-pass -> delay | sum | delay with wet < 0.0001 (a k_sum launch, gain 1)
-        p.add_sampleloop("s", 1.0, 0.0, "a")
-        p.add_bandpass("b", 1.0, 0.0, 1.0, 300.0, 5000.0, True)
-        if shape == "band_up":
-            p.add_delay(*dl)
-        elif shape == "band_dry":
-            p.add_delay("e", 1.0, 0.0, 0.00009, 10.0, feedback, 0.35)
-        else:
-            p.add_sum("e", 1.0, 0.0)
-        p.connect("s", "b"); p.connect("b", "e"); p.set_output("e")
-    else:                        # synth -> delay | sum
-        p.add_synth("y", 1.0, 0.0, "f", 0.4, 0.3, W.HIT_ADSR, 1.0, 0.8, W.NOTE_ADSR, 0.5, W.STD_ADSR)
-        if shape == "sine_up":
-            p.add_delay(*dl)
-        else:
-            p.add_sum("e", 1.0, 0.0)
-        p.connect("y", "e"); p.set_output("e")
-    return p
+    """(10 ms are 480 frames: below the block length)"""
+    return fx_rig.guard_project(shape, lambda p, name, dry: p.add_delay(name, 1.0, 0.0, 0.00009 if dry else wet, 10.0, feedback, 0.35), name="e")
 
 
 DELAY_LAUNCHES = ("k_delay_local", "k_delay_carry", "k_delay_apply")
-
-
-def _run(asan_exe, tmp_path, projects):
-    dirs = {name: DP.write_project(p, str(tmp_path / name)) for name, p in projects.items()}
-    r = subprocess.run([asan_exe] + list(dirs.values()), env=dict(os.environ, **ENV), capture_output=True, text=True, timeout=1800)
-    assert r.returncode == 0, (r.stdout[-800:], r.stderr[-4000:])
-    fams, gains, redo = {}, {}, {}
-    for ln in r.stdout.splitlines():
-        for tag, store in (("launches ", fams), ("guard ", gains), ("redo ", redo)):
-            if ln.startswith(tag):
-                d, rest = ln[len(tag):].split(":", 1)
-                store[d] = rest.split()
-    back = {d: name for name, d in dirs.items()}
-    fams = {back[d]: dict((kv.split("=")[0], int(kv.split("=")[1])) for kv in v) for d, v in fams.items()}   # (dicts keep the driver's order)
-    gains = {back[d]: dict((kv.split("=")[0], float(kv.split("=")[1])) for kv in v) for d, v in gains.items()}
-    redo = {back[d]: dict(kv.split("=") for kv in v) for d, v in redo.items()}
-    return fams, gains, redo
 
 
 def test_guard_modes_carry_the_estimate_through_a_delay(api, asan_exe, tmp_path):
     """band_mode 2 / sine_mode 2 (the driver's profiled render): upstream of a delay the scan / fast forms stay, and the guard's
     estimate at the output is the one of the same project without the delay times 1 + wet Hecho."""
     shapes = ("band_up", "band_plain", "band_dry", "sine_up", "sine_free")
-    fams, gains, _ = _run(asan_exe, tmp_path, {s: _guard_project(s) for s in shapes})
+    fams, gains, _ = driver_report(asan_exe, tmp_path, {s: _guard_project(s) for s in shapes})
     exact = ("k_band_pass", "k_band_spec")
     for s in ("band_up", "band_plain", "band_dry"):
         assert "k_band_scan" in fams[s] and not any(k in fams[s] for k in exact), (s, fams[s])
@@ -362,7 +297,7 @@ def test_a_guarded_pull_that_runs_again_enters_with_the_line_it_first_entered_wi
     """Three guarded block pulls, each told to run again (mock_delay.cpp): the first starts afresh both times and reads nothing of
     the line; the second and the third continue from it, so the guard copies it in front of the pull and puts it back in front
     of the second run -- both runs find the same stamp, the one the run before them left last."""
-    _, _, redo = _run(asan_exe, tmp_path, {"band_up": _guard_project("band_up"), "band_plain": _guard_project("band_plain")})
+    _, _, redo = driver_report(asan_exe, tmp_path, {"band_up": _guard_project("band_up"), "band_plain": _guard_project("band_plain")})
     assert int(redo["band_up"]["redos"]) == 3 and int(redo["band_plain"]["redos"]) == 3, redo
     e = [int(v) for v in redo["band_up"]["entries"].split(",")]
     assert len(e) == 4 and e[0] == e[1] and e[2] == e[3] and e[2] == e[0] + 2, e
@@ -373,7 +308,7 @@ def test_projects_without_a_delay_keep_their_launch_list(asan_exe, tmp_path):
     """The launch lists of drum_project, config 2 and config 4 (families and launch counts of one profiled render under the
     front-end's guard modes) as the parent commit compiled them."""
     projects = {"drums": W.drum_project(seconds=0.5), "config2": W.config2(seconds=0.5, n_src=8), "config4": W.config4(seconds=0.5, depth=6)}
-    fams, _, _ = _run(asan_exe, tmp_path, projects)
+    fams, _, _ = driver_report(asan_exe, tmp_path, projects)
     for name in projects:
         got = " ".join("%s=%d" % kv for kv in fams[name].items())
-        assert not any(k.startswith("k_delay") for k in fams[name]) and got == TE.PARENT_LAUNCHES[name], (name, got)
+        assert not any(k.startswith("k_delay") for k in fams[name]) and got == PARENT_LAUNCHES[name], (name, got)

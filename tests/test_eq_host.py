@@ -9,7 +9,6 @@ path gains the mock build reports."""
 import math
 import multiprocessing
 import os
-import shutil
 import subprocess
 import sys
 
@@ -20,11 +19,9 @@ from termdaw_amd import workloads as W
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import eq_projects as EP  # noqa: E402
+import fx_rig  # noqa: E402
 import np_eq as NE  # noqa: E402
-import test_loudness_host as L  # noqa: E402
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "termdaw_amd", "csrc")
+from fx_rig import ENV, driver_report, PARENT_LAUNCHES, _families, oracle_input  # noqa: E402
 
 
 def coeffs(api, kind, sr, f, q, g):
@@ -206,7 +203,7 @@ def test_range_ends_are_accepted_and_follow_the_rate(api):
 
 
 def _lua(line):
-    return 'add_sum("in", 1.0, 0.0);\n%s\nconnect("in", "e");\nset_output("e");\n' % line
+    return fx_rig._lua(line, "e")
 
 
 @pytest.mark.parametrize("name,value", [(k, v) for k, v in BAD if math.isfinite(v)])
@@ -254,17 +251,6 @@ def test_project_script_records_and_writes_the_call(tmp_path):
 
 
 # ---- the bound of tests/test_gpu_eq.py ----
-def oracle_input(kind, sr):
-    """The grid's input as the GPU test sees it: the second render of `bus` (the first leaves the sample_multi voices sounding),
-    here by the CPU oracle -- the engine's own render is the oracle's, bit for bit."""
-    from oracle import binding as oracle
-    p = EP.base_project(kind, sr=sr)
-    sb, fb, g = p.build(oracle)
-    g.render_all(sb, fb, p.cs, 16)
-    fb.set_time(0)
-    g.set_time(0)
-    g.reset_normalize_vertices()
-    return g.render_all(sb, fb, p.cs, 16)[1]
 
 
 def _emulate(api, sr, cases, want_f64):
@@ -309,30 +295,9 @@ def test_the_emulated_scan_stays_inside_the_committed_constant(api):
 
 
 # ---- the host engine under sanitizers ----
-def _build(out_dir):
-    flags = ["-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-ffp-contract=off",
-             "-D__HIP_PLATFORM_AMD__", "-I", "/opt/rocm/include", "-I", CSRC, "-I", os.path.join(ROOT, "include")]
-    jobs = [(os.path.join(CSRC, f), os.path.join(out_dir, f + ".o")) for f in L.SOURCES]
-    jobs += [(os.path.join(ROOT, "tests", f), os.path.join(out_dir, f + ".o")) for f in ("mock_hip.cpp", "mock_guard.cpp", "mock_eq.cpp", "asan_eq.cpp")]
-    procs = [subprocess.Popen(["g++"] + flags + ["-c", src, "-o", obj]) for src, obj in jobs]
-    for p in procs:
-        assert p.wait() == 0
-    exe = os.path.join(out_dir, "asan_eq")
-    # (mock_guard.cpp listens to the guard's launches of mock_hip.cpp: ld --wrap)
-    wraps = ["-Wl,--wrap=_ZN3tdk17launch_band_auditEPKNS_9AuditHeadEiP12ihipStream_t",
-             "-Wl,--wrap=_ZN3tdk17launch_band_chainEPKNS_12BandScanDescEijjbP12ihipStream_t"]
-    subprocess.check_call(["g++", "-fsanitize=address,undefined", "-o", exe] + wraps + [o for _, o in jobs] + ["-lpthread", "-ldl"])
-    return exe
-
-
 @pytest.fixture(scope="module")
 def asan_exe(tmp_path_factory):
-    if shutil.which("g++") is None or not os.path.exists("/opt/rocm/include/hip/hip_runtime_api.h"):
-        pytest.skip("needs g++ and the HIP headers")
-    return _build(str(tmp_path_factory.mktemp("asan_eq")))
-
-
-ENV = dict(ASAN_OPTIONS="detect_leaks=0:allocator_may_return_null=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1", TD_ALLOC_CACHE_MB="0")
+    return fx_rig.asan_exe(tmp_path_factory, "asan_eq", ["mock_guard.cpp", "mock_eq.cpp", "asan_eq.cpp"])
 
 
 def test_eq_projects_under_sanitizers(asan_exe, tmp_path):
@@ -359,62 +324,18 @@ def test_eq_projects_under_sanitizers(asan_exe, tmp_path):
 
 
 def _guard_project(shape):
-    p = W.ProjectScript(48000, 1024)
-    p.set_length(0.5)
-    p.assets["a"] = W.Asset(W.noise_int16(7, 9000))
-    p.load_sample("a", "a", "")
-    p.event_files["f"] = np.array([(0.01, 60.0, 0.8), (0.2, 60.0, 0.0), (0.25, 62.0, 0.6)], np.float32)
-    p.load_midi_floww("f", "f")
-    eq = ("e", 1.0, 0.0, 0.75, "peak", 1000.0, 2.0, 12.0)
-    if shape == "band_up":       # loop -> band-pass -> eq
-        p.add_sampleloop("s", 1.0, 0.0, "a")
-        p.add_bandpass("b", 1.0, 0.0, 1.0, 300.0, 5000.0, True)
-        p.add_eq(*eq)
-        p.connect("s", "b"); p.connect("b", "e"); p.set_output("e")
-    elif shape == "band_plain":  # loop -> band-pass -> sum: the control of the path gain
-        p.add_sampleloop("s", 1.0, 0.0, "a")
-        p.add_bandpass("b", 1.0, 0.0, 1.0, 300.0, 5000.0, True)
-        p.add_sum("e", 1.0, 0.0)
-        p.connect("s", "b"); p.connect("b", "e"); p.set_output("e")
-    elif shape == "band_dry":    # loop -> band-pass -> eq with wet < 0.0001: a k_sum launch, gain 1
-        p.add_sampleloop("s", 1.0, 0.0, "a")
-        p.add_bandpass("b", 1.0, 0.0, 1.0, 300.0, 5000.0, True)
-        p.add_eq("e", 1.0, 0.0, 0.00009, "peak", 1000.0, 2.0, 12.0)
-        p.connect("s", "b"); p.connect("b", "e"); p.set_output("e")
-    elif shape == "sine_up":     # synth -> eq
-        p.add_synth("y", 1.0, 0.0, "f", 0.4, 0.3, W.HIT_ADSR, 1.0, 0.8, W.NOTE_ADSR, 0.5, W.STD_ADSR)
-        p.add_eq(*eq)
-        p.connect("y", "e"); p.set_output("e")
-    else:                        # synth -> sum: the control
-        p.add_synth("y", 1.0, 0.0, "f", 0.4, 0.3, W.HIT_ADSR, 1.0, 0.8, W.NOTE_ADSR, 0.5, W.STD_ADSR)
-        p.add_sum("e", 1.0, 0.0)
-        p.connect("y", "e"); p.set_output("e")
-    return p
+    """(band_plain is the control of the path gain; the dry one has wet < 0.0001: a k_sum launch, gain 1)"""
+    return fx_rig.guard_project(shape, lambda p, name, dry: p.add_eq(name, 1.0, 0.0, 0.00009 if dry else 0.75, "peak", 1000.0, 2.0, 12.0), name="e")
 
 
 EQ_LAUNCHES = ("k_eq_local", "k_eq_carry", "k_eq_apply")
-
-
-def _families(asan_exe, tmp_path, projects):
-    dirs = {name: EP.write_project(p, str(tmp_path / name)) for name, p in projects.items()}
-    r = subprocess.run([asan_exe] + list(dirs.values()), env=dict(os.environ, **ENV), capture_output=True, text=True, timeout=1800)
-    assert r.returncode == 0, (r.stdout[-800:], r.stderr[-4000:])
-    fams, gains = {}, {}
-    for ln in r.stdout.splitlines():
-        for tag, store in (("launches ", fams), ("guard ", gains)):
-            if ln.startswith(tag):
-                d, rest = ln[len(tag):].split(":", 1)
-                store[d] = rest.split()
-    back = {d: name for name, d in dirs.items()}
-    fams = {back[d]: dict((kv.split("=")[0], int(kv.split("=")[1])) for kv in v) for d, v in fams.items()}   # (dicts keep the driver's order)
-    return fams, {back[d]: dict((kv.split("=")[0], float(kv.split("=")[1])) for kv in v) for d, v in gains.items()}
 
 
 def test_guard_modes_carry_the_estimate_through_an_eq(api, asan_exe, tmp_path):
     """band_mode 2 / sine_mode 2 (the driver's profiled render): upstream of an EQ the scan / fast forms stay, and the guard's
     estimate at the output is the one of the same project without the EQ times (1 - wet) + wet Hmax."""
     shapes = ("band_up", "band_plain", "band_dry", "sine_up", "sine_free")
-    fams, gains = _families(asan_exe, tmp_path, {s: _guard_project(s) for s in shapes})
+    fams, gains, _ = driver_report(asan_exe, tmp_path, {s: _guard_project(s) for s in shapes})
     exact = ("k_band_pass", "k_band_spec")
     for s in ("band_up", "band_plain", "band_dry"):
         assert "k_band_scan" in fams[s] and not any(k in fams[s] for k in exact), (s, fams[s])
@@ -438,15 +359,10 @@ def test_projects_without_an_eq_keep_their_launch_list(asan_exe, tmp_path):
     """The launch lists of drum_project, config 2 and config 4 (families and launch counts of one profiled render under the
     front-end's guard modes) as the parent commit compiled them."""
     projects = {"drums": W.drum_project(seconds=0.5), "config2": W.config2(seconds=0.5, n_src=8), "config4": W.config4(seconds=0.5, depth=6)}
-    fams, _ = _families(asan_exe, tmp_path, projects)
+    fams = _families(asan_exe, tmp_path, projects)
     for name in projects:
         got = " ".join("%s=%d" % kv for kv in fams[name].items())
         assert not any(k.startswith("k_eq") for k in fams[name]) and got == PARENT_LAUNCHES[name], (name, got)
 
 
 # (recorded on the parent commit with its own driver of the same form, tests/asan_comp.cpp, on these project directories)
-PARENT_LAUNCHES = {
-    "drums": "k_sample_multi=1 k_sum=1 k_band_scan=2 k_band_audit=1 k_sources=1",
-    "config2": "k_sum=1",
-    "config4": "k_band_scan=1 k_sources=1",
-}

@@ -10,7 +10,6 @@ families the mock build reports."""
 import math
 import multiprocessing
 import os
-import shutil
 import subprocess
 import sys
 
@@ -20,14 +19,10 @@ import pytest
 from termdaw_amd import workloads as W
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import eq_projects as EP  # noqa: E402
 import filter_projects as FP  # noqa: E402
+import fx_rig  # noqa: E402
 import np_filter as NF  # noqa: E402
-import test_loudness_host as L  # noqa: E402
-from test_eq_host import oracle_input  # noqa: E402
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "termdaw_amd", "csrc")
+from fx_rig import ENV, PARENT_LAUNCHES, _families, oracle_input  # noqa: E402
 SR = 48000
 
 GOOD = dict(kind=0, freq_hz=1000.0, q=5.0, lfo_oct=2.0, rate_hz=1.0, stereo=0.25, shape=0, env_oct=3.0, sens_db=12.0, attack_ms=5.0, release_ms=100.0)
@@ -51,19 +46,13 @@ BAD += [("kind", 4), ("kind", -1), ("shape", 2), ("shape", -1)]
 
 
 def _args(**kw):
-    a = dict(GOOD)
-    a.update(kw)
-    return [a[k] for k in ORDER]
+    return fx_rig._args(GOOD, ORDER, **kw)
 
 
 # ---- ranges, the Lua line, the project script ----
 @pytest.mark.parametrize("name,value", BAD)
 def test_out_of_range_parameters_are_rejected_by_name(api, name, value):
-    g = api.Graph(64, SR)
-    with pytest.raises(api.TermdawError, match=name):
-        g.add_filter("f", 1.0, 0.0, 1.0, *_args(**{name: value}))
-    with pytest.raises(api.TermdawError, match=name):
-        api.filter_params(SR, *_args(**{name: value}))
+    fx_rig.out_of_range_is_rejected_by_name(api, SR, lambda g, *a: g.add_filter("f", 1.0, 0.0, 1.0, *a), api.filter_params, _args(**{name: value}), name)
 
 
 def test_range_ends_are_accepted_and_follow_the_rate(api):
@@ -99,7 +88,7 @@ def test_a_filter_takes_a_key_and_cannot_close_a_loop_with_it(api):
 
 
 def _lua(line):
-    return 'add_sum("in", 1.0, 0.0);\n%s\nconnect("in", "g");\nconnect_key("in", "g");\nset_output("g");\n' % line
+    return fx_rig._lua(line, "g", key="in")
 
 
 def _lit(v):
@@ -324,27 +313,11 @@ def test_blocked_scans_continue_from_a_carried_state(api):
 
 
 # ---- the host engine under sanitizers ----
-def _build(out_dir):
-    flags = ["-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-ffp-contract=off",
-             "-D__HIP_PLATFORM_AMD__", "-I", "/opt/rocm/include", "-I", CSRC, "-I", os.path.join(ROOT, "include")]
-    jobs = [(os.path.join(CSRC, f), os.path.join(out_dir, f + ".o")) for f in L.SOURCES]
-    jobs += [(os.path.join(ROOT, "tests", f), os.path.join(out_dir, f + ".o")) for f in ("mock_hip.cpp", "mock_filter.cpp", "asan_comp.cpp")]
-    procs = [subprocess.Popen(["g++"] + flags + ["-c", src, "-o", obj]) for src, obj in jobs]
-    for p in procs:
-        assert p.wait() == 0
-    exe = os.path.join(out_dir, "asan_filter")
-    subprocess.check_call(["g++", "-fsanitize=address,undefined", "-o", exe] + [o for _, o in jobs] + ["-lpthread", "-ldl"])
-    return exe
-
-
 @pytest.fixture(scope="module")
 def asan_exe(tmp_path_factory):
-    if shutil.which("g++") is None or not os.path.exists("/opt/rocm/include/hip/hip_runtime_api.h"):
-        pytest.skip("needs g++ and the HIP headers")
-    return _build(str(tmp_path_factory.mktemp("asan_filter")))
+    return fx_rig.asan_exe(tmp_path_factory, "asan_filter", ["mock_filter.cpp", "asan_comp.cpp"])
 
 
-ENV = dict(ASAN_OPTIONS="detect_leaks=0:allocator_may_return_null=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1", TD_ALLOC_CACHE_MB="0")
 FOLLOWER = ("k_filt_detect", "k_filt_carry_y1", "k_filt_env", "k_filt_carry_e")
 FILTER = ("k_filt_local", "k_filt_carry", "k_filt_apply")
 
@@ -433,19 +406,6 @@ def _guard_project(shape, seconds=0.5):
     return p
 
 
-def _families(asan_exe, tmp_path, projects):
-    dirs = {name: EP.write_project(p, str(tmp_path / name)) for name, p in projects.items()}
-    r = subprocess.run([asan_exe] + list(dirs.values()), env=dict(os.environ, **ENV), capture_output=True, text=True, timeout=1800)
-    assert r.returncode == 0, (r.stdout[-800:], r.stderr[-4000:])
-    back = {d: name for name, d in dirs.items()}
-    fams = {}
-    for ln in r.stdout.splitlines():
-        if ln.startswith("launches "):
-            d, rest = ln[len("launches "):].split(":", 1)
-            fams[back[d]] = dict((kv.split("=")[0], int(kv.split("=")[1])) for kv in rest.split())   # (dicts keep the driver's order)
-    return fams
-
-
 def _filt(f):
     return [(k, v) for k, v in f.items() if k.startswith("k_filt")]
 
@@ -480,14 +440,6 @@ def test_launch_lists_and_the_guard_rule(asan_exe, tmp_path):
     assert _filt(fams["one_tile"]) == [("k_filt_apply", 1)], fams["one_tile"]
     # a level with all four forms: the keyed detect launch behind the unkeyed one, every other step once
     assert _filt(fams["mixed"]) == [("k_filt_detect", 2)] + [(k, 1) for k in FOLLOWER[1:] + FILTER], fams["mixed"]
-
-
-# (test_eq_host.py's record of the parent's lists)
-PARENT_LAUNCHES = {
-    "drums": "k_sample_multi=1 k_sum=1 k_band_scan=2 k_band_audit=1 k_sources=1",
-    "config2": "k_sum=1",
-    "config4": "k_band_scan=1 k_sources=1",
-}
 
 
 def test_projects_without_a_filter_keep_their_launch_list(asan_exe, tmp_path):

@@ -35,7 +35,7 @@ def _digest(pcm):
     return hashlib.sha256(np.ascontiguousarray(pcm, dtype="<i2").tobytes()).hexdigest()
 
 
-def _families(g, render):
+def _profiled(g, render):
     g.set_profiling(1)
     out = render()
     fam = g.kernel_times()
@@ -54,7 +54,7 @@ def test_config2_full_size_exactly_as_the_bench_times_it(gpu_api, oracle):
     for rep in range(2):
         g.reset_normalize_vertices()          # the bench's step(): batch.rewind() + render
         fb.set_time(0)
-        (pcm, f32), fam = _families(g, lambda: g.render_all(sb, fb, p.cs, 16, want_f32=False))
+        (pcm, f32), fam = _profiled(g, lambda: g.render_all(sb, fb, p.cs, 16, want_f32=False))
         assert set(fam) == {"k_sum"} and fam["k_sum"][1] == 1, fam      # ONE launch: no k_scale, no k_norm_fix
         assert f32 is None
         assert np.array_equal(pcm, ref_pcm)
@@ -103,7 +103,7 @@ def test_config2_120s_grid_beyond_the_resident_capacity(gpu_api, oracle, debug):
     for rep in range(2):
         fb.set_time(0)
         ofb.set_time(0)
-        (pcm, _), fam = _families(g, lambda: g.render_all(sb, fb, p.cs, 16, want_f32=False))
+        (pcm, _), fam = _profiled(g, lambda: g.render_all(sb, fb, p.cs, 16, want_f32=False))
         ref, _ = og.render_all(osb, ofb, p.cs, 16, want_f32=False)
         assert "k_scale" not in fam and "k_sum" in fam, fam
         assert np.array_equal(pcm, ref), "render %d" % rep

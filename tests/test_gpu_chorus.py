@@ -6,13 +6,11 @@ the vertex in front, read as f32 -- the oracle-verified part of the graph is not
 
 Bound: none.  Every output frame is a sum the kernel accumulates from 0.0 in the definition's order, on its own, from IEEE add,
 multiply, floor and fabs alone, whatever the tiling and the chunking: at wet = 1, gain = 1, angle = 0 every finite f32 is
-BIT-EQUAL to the twin and the non-finite ones sit at the same frames.  With wet in (0, 1), pan and gain: tests/test_gpu_eq.py's
+BIT-EQUAL to the twin and the non-finite ones sit at the same frames.  With wet in (0, 1), pan and gain: tests/fx_rig.py's
 mix_bound (the pan amplitudes come from two sine implementations).  PCM cases: within one word of the twin's quantised value.
 Every test renders 0.25 s at 48 kHz at the most."""
 import os
-import subprocess
 import sys
-import wave
 
 import numpy as np
 import pytest
@@ -22,11 +20,9 @@ from termdaw_amd import workloads as W
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import chorus_projects as CP  # noqa: E402
 import np_chorus as NC  # noqa: E402
-import test_gpu_eq as TG  # noqa: E402
-from test_gpu_stems import _write_project  # noqa: E402
+import fx_rig as TG  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SR = 48000
 build, render_f32, mix_bound, _pull_all, _quantise16 = TG.build, TG.render_f32, TG.mix_bound, TG._pull_all, TG._quantise16
 LUSH = CP.case(3, (20.0, 4.0, 0.8, 0.25), "sine")         # H = 1 216
@@ -386,52 +382,14 @@ def test_fed_by_an_inlined_loop_source_and_a_gain_stage(gpu_api):
 
 
 def test_front_end_renders_a_drum_bus_with_a_chorus(gpu_api, tmp_path):
-    p = W.drum_project(seconds=0.25)
     # the drum bus `drums` feeds the band-pass in front of the output: put the chorus in between
-    line = ("wide", 1.0, 0.0, 0.5, 3, 20.0, 4.0, 0.8, 0.25, "sine")
-    i = p.calls["connect"].index(("drums", "band"))
-    p.calls["connect"][i:i + 1] = [("drums", "wide"), ("wide", "band")]
-    j = p.script_order.index(("connect", ("drums", "band")))
-    p.script_order[j:j + 1] = [("add_chorus", line), ("connect", ("drums", "wide")), ("connect", ("wide", "band"))]
-    p.calls["add_chorus"].append(line)
-    d = str(tmp_path / "proj")
-    _write_project(p, d)
-    out = str(tmp_path / "m.wav")
-    r = subprocess.run([sys.executable, "-m", "termdaw_amd", d, "-o", out], env=dict(os.environ, PYTHONPATH=ROOT), capture_output=True,
-                       text=True, timeout=600)
-    assert r.returncode == 0, r.stderr
-    st = gpu_api.State(open_dir=d)
-    assert st.refresh(), gpu_api.last_error()
-    assert 'add_chorus("wide",' in st.dump_calls() and '"sine"' in st.dump_calls()
-    mem = st.render_to_memory()
-    with wave.open(out, "rb") as w:
-        words = np.frombuffer(w.readframes(w.getnframes()), np.int16).reshape(-1, 2)
-    assert words.shape == mem.shape and np.array_equal(words, mem) and np.abs(mem).max() > 1000
-    # ... and the chorus is really in the path: without it the words differ
-    q = W.drum_project(seconds=0.25)
-    d2 = str(tmp_path / "plain")
-    _write_project(q, d2)
-    st2 = gpu_api.State(open_dir=d2)
-    assert st2.refresh()
-    assert not np.array_equal(st2.render_to_memory(), mem)
+    p = TG.into_the_drum_bus("add_chorus", ("wide", 1.0, 0.0, 0.5, 3, 20.0, 4.0, 0.8, 0.25, "sine"), seconds=0.25)
+    mem = TG.front_end_renders(gpu_api, tmp_path, p, 'add_chorus("wide",', '"sine"')
+    TG.front_end_words_differ(gpu_api, tmp_path, W.drum_project(seconds=0.25), mem)
 
 
 def _guard_project(bl=1024, seconds=0.25):
-    p = W.ProjectScript(48000, bl)
-    p.set_length(seconds)
-    p.assets["a"] = W.Asset(W.noise_int16(7, 9000))
-    p.load_sample("a", "a", "")
-    p.event_files["f"] = np.array([(0.01, 60.0, 0.8), (0.1, 60.0, 0.0), (0.12, 64.0, 0.6), (0.22, 64.0, 0.0)], np.float32)
-    p.load_midi_floww("f", "f")
-    p.add_sampleloop("s", 0.5, 0.0, "a")
-    p.add_bandpass("b1", 1.0, 0.0, 1.0, 300.0, 5000.0, True)
-    p.add_bandpass("b2", 1.0, 10.0, 1.0, 200.0, 8000.0, True)
-    p.add_synth("y", 0.5, 0.0, "f", 0.4, 0.3, W.HIT_ADSR, 1.0, 0.8, W.NOTE_ADSR, 0.5, W.STD_ADSR)
-    p.add_sum("bus", 1.0, 0.0)
-    p.add_chorus("c", 1.0, 0.0, 0.5, 3, 20.0, 4.0, 0.8, 0.25, "sine")
-    p.connect("s", "b1"); p.connect("b1", "b2"); p.connect("b2", "bus"); p.connect("y", "bus"); p.connect("bus", "c")
-    p.set_output("c")
-    return p
+    return TG.gpu_guard_project("add_chorus", "c", (3, 20.0, 4.0, 0.8, 0.25, "sine"), False, wet=0.5, bl=bl, seconds=seconds, notes=TG.SHORT_NOTES)
 
 
 def test_guard_keeps_the_scan_and_fast_sines_in_front_of_a_chorus(gpu_api):

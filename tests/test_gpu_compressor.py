@@ -11,9 +11,7 @@ f64 log10 / pow (and the scans' f64 re-association) flipping that rounding.  Wit
 ulp of an operand no larger than that.  PCM cases: within one word of the twin's quantised value."""
 import itertools
 import os
-import subprocess
 import sys
-import wave
 
 import numpy as np
 import pytest
@@ -21,13 +19,13 @@ import pytest
 from termdaw_amd import workloads as W
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import fx_rig  # noqa: E402
 import np_compressor as NC  # noqa: E402
 from np_twin import pan_gain  # noqa: E402
-from test_gpu_stems import _write_project  # noqa: E402
+from fx_rig import MIX, REL, _pull_all, _quantise16, assert_close_f32 as assert_close, build, render_f32  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REL = 2.0 ** -23
+
 PARAMS = ["threshold_db", "ratio", "attack_ms", "release_ms", "knee_db", "makeup_db"]
 
 
@@ -81,35 +79,6 @@ def add_comp(p, name, src, wet=1.0, gain=1.0, angle=0.0, **kw):
     p.connect(src, name)
 
 
-def build(api, p):
-    """The built project after one discarded render of `bus`: the sample_multi vertices keep voices that are still sounding when
-    a render ends (the reference's carried state), so only from the second render on does every render see the same input."""
-    built = p.build(api)
-    render_f32(api, built, "bus", p.cs)
-    return built
-
-
-def render_f32(api, built, out, cs, **opts):
-    sb, fb, g = built
-    for k, v in opts.items():
-        g.set_option(k, v)
-    assert g.set_output(out)
-    fb.set_time(0)
-    g.set_time(0)
-    g.reset_normalize_vertices()
-    return g.render_all(sb, fb, cs, 16, want_pcm=False)[1]
-
-
-def assert_close(y, want, what=""):
-    y64, w64 = y.astype(np.float64), want.astype(np.float64)
-    err = np.abs(y64 - w64)
-    lim = REL * np.abs(w64) + NC.F32_TINY
-    bad = ~(err <= lim)
-    worst = float(np.max(np.where(w64 != 0, err / np.maximum(np.abs(w64), 1e-300), 0.0))) if len(y) else 0.0
-    print("%s: worst relative error %.3g x 2^-23" % (what, worst / REL))
-    assert not bad.any(), (what, int(bad.sum()), np.argwhere(bad)[:4].tolist(), y[bad][:4], want[bad][:4])
-
-
 GRID = list(itertools.product((0.0, 1.0, 40.0), (1.0, 100.0, 2000.0), (1.0, 2.0, 1000.0)))   # attack, release, ratio
 
 
@@ -137,26 +106,16 @@ def test_grid_matches_the_twin(gpu_api, sr, kind, knee):
     assert np.array_equal(render_f32(gpu_api, built, "bus", p.cs), x)   # (and every render above saw this input)
 
 
-MIX = [(0.3, 0.5, 30.0), (0.75, 1.7, -75.0), (0.5, -0.8, 0.0), (0.999, 1.0, 90.0), (0.0001, 1.0005, 0.0009)]
+# (of the shared bodies the compressor takes the mix test alone: its bound is on the output as it stands, its cases are keywords)
+COMP = fx_rig.FxKind("compressor", "k_comp", None, lambda p, name, src, case, **kw: add_comp(p, name, src, **kw, **case), base_project,
+                     dict(threshold_db=-28.0, ratio=5.0, attack_ms=2.0, release_ms=60.0, knee_db=6.0, makeup_db=3.0), None, None,
+                     twin=lambda api, sr, case, x: (NC.compress(x, sr, processed=True, **case)[0], x),
+                     mix=lambda api, sr, case, x, **kw: NC.compress(x, sr, **kw, **case)[0])
 
 
 @pytest.mark.parametrize("wet,gain,angle", MIX)
 def test_wet_pan_and_gain(gpu_api, wet, gain, angle):
-    kw = dict(threshold_db=-28.0, ratio=5.0, attack_ms=2.0, release_ms=60.0, knee_db=6.0, makeup_db=3.0)
-    p = base_project("drums")
-    add_comp(p, "c", "bus", wet=wet, gain=gain, angle=angle, **kw)
-    built = build(gpu_api, p)
-    x = render_f32(gpu_api, built, "bus", p.cs)
-    y = render_f32(gpu_api, built, "c", p.cs)
-    want, _ = NC.compress(x, 48000, wet=wet, gain=gain, angle=angle, **kw)
-    proc, _ = NC.compress(x, 48000, processed=True, **kw)
-    al, ar = pan_gain(np.ones(1, np.float32), np.ones(1, np.float32), gain, angle)
-    amp = np.abs(np.array([float(al[0]), float(ar[0])]))
-    lim = 4.0 * REL * np.maximum(np.abs(x), np.abs(proc)).astype(np.float64) * amp[None, :] + NC.F32_TINY
-    err = np.abs(y.astype(np.float64) - want.astype(np.float64))
-    print("wet %g gain %g angle %g: worst error / bound %.3g" % (wet, gain, angle, float(np.max(err / lim))))
-    assert (err <= lim).all(), (float(np.max(err / lim)), np.argwhere(err > lim)[:4].tolist())
-    assert np.abs(want - x).max() > 1e-3 * wet   # (the vertex does something, in proportion to the mix)
+    fx_rig.wet_pan_and_gain(gpu_api, COMP, wet, gain, angle, vertex="c")
 
 
 def test_unit_ratio_and_dry_pass_the_input_through(gpu_api):
@@ -176,20 +135,6 @@ def test_unit_ratio_and_dry_pass_the_input_through(gpu_api):
 
 
 CHUNK_KW = dict(threshold_db=-26.0, ratio=4.0, attack_ms=5.0, release_ms=400.0, knee_db=6.0, makeup_db=2.0)
-
-
-def _pull_all(api, built, out, cs):
-    sb, fb, g = built
-    assert g.set_output(out)
-    fb.set_time(0)
-    g.set_time(0)
-    g.reset_normalize_vertices()
-    blocks = []
-    for _ in range(cs):
-        l, r = g.render(sb, fb)
-        fb.set_time_to_next_block()   # (the caller moves the events on, as the reference's pull loop does)
-        blocks.append(np.stack([l, r], axis=1))
-    return np.concatenate(blocks)
 
 
 @pytest.mark.parametrize("bl", [1024, 64])
@@ -268,11 +213,6 @@ def test_batch_members_are_bitwise_their_own_renders(gpu_api):
         assert batch.render_all(cs, 16) == cs * 1024
         for i in range(8):
             assert np.array_equal(batch.read_pcm(i, cs), own[i][rep]), (rep, i)
-
-
-def _quantise16(x):
-    v = x.astype(np.float32) * np.float32(32767.0)
-    return np.clip(np.trunc(v.astype(np.float64)), -32768, 32767).astype(np.int64)
 
 
 def test_in_front_of_a_normalize_output(gpu_api):
@@ -355,12 +295,7 @@ def test_fed_by_an_inlined_loop_source_and_a_gain_stage(gpu_api):
 
 
 def test_projects_without_a_compressor_launch_no_compressor_kernel(gpu_api):
-    for p in (W.drum_project(seconds=1.0), W.config2(seconds=1.0, n_src=8)):
-        sb, fb, g = p.build(gpu_api)
-        g.set_profiling(1)
-        g.render_all(sb, fb, p.cs, 16, want_f32=False)
-        names = list(g.kernel_times())
-        assert names and not any(n.startswith("k_comp") for n in names), names
+    fx_rig.projects_without_the_kind_launch_no_kernel_of_it(gpu_api, "k_comp")
     p = base_project("drums")
     add_comp(p, "c", "bus", **CHUNK_KW)
     p.set_output("c")
@@ -372,31 +307,7 @@ def test_projects_without_a_compressor_launch_no_compressor_kernel(gpu_api):
 
 
 def test_front_end_renders_a_compressed_drum_bus(gpu_api, tmp_path):
-    p = W.drum_project(seconds=1.0)
     # the drum bus `drums` feeds the band-pass in front of the output: put the compressor in between
-    i = p.calls["connect"].index(("drums", "band"))
-    p.calls["connect"][i:i + 1] = [("drums", "comp"), ("comp", "band")]
-    j = p.script_order.index(("connect", ("drums", "band")))
-    p.script_order[j:j + 1] = [("add_compressor", ("comp", 1.0, 0.0, 1.0, -24.0, 4.0, 2.0, 120.0, 6.0, 3.0)), ("connect", ("drums", "comp")),
-                               ("connect", ("comp", "band"))]
-    p.calls["add_compressor"].append(("comp", 1.0, 0.0, 1.0, -24.0, 4.0, 2.0, 120.0, 6.0, 3.0))
-    d = str(tmp_path / "proj")
-    _write_project(p, d)
-    out = str(tmp_path / "m.wav")
-    r = subprocess.run([sys.executable, "-m", "termdaw_amd", d, "-o", out], env=dict(os.environ, PYTHONPATH=ROOT), capture_output=True,
-                       text=True, timeout=600)
-    assert r.returncode == 0, r.stderr
-    st = gpu_api.State(open_dir=d)
-    assert st.refresh(), gpu_api.last_error()
-    assert 'add_compressor("comp",' in st.dump_calls()
-    mem = st.render_to_memory()
-    with wave.open(out, "rb") as w:
-        words = np.frombuffer(w.readframes(w.getnframes()), np.int16).reshape(-1, 2)
-    assert words.shape == mem.shape and np.array_equal(words, mem) and np.abs(mem).max() > 1000
-    # ... and the compressor is really in the path: without it the words differ
-    q = W.drum_project(seconds=1.0)
-    d2 = str(tmp_path / "plain")
-    _write_project(q, d2)
-    st2 = gpu_api.State(open_dir=d2)
-    assert st2.refresh()
-    assert not np.array_equal(st2.render_to_memory(), mem)
+    p = fx_rig.into_the_drum_bus("add_compressor", ("comp", 1.0, 0.0, 1.0, -24.0, 4.0, 2.0, 120.0, 6.0, 3.0))
+    mem = fx_rig.front_end_renders(gpu_api, tmp_path, p, 'add_compressor("comp",')
+    fx_rig.front_end_words_differ(gpu_api, tmp_path, W.drum_project(seconds=1.0), mem)

@@ -15,9 +15,7 @@ cases: within one word of the twin's quantised value.
 
 Every case prints its worst error over the bound.  No device figures are recorded yet."""
 import os
-import subprocess
 import sys
-import wave
 
 import numpy as np
 import pytest
@@ -25,82 +23,17 @@ import pytest
 from termdaw_amd import workloads as W
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import fx_rig  # noqa: E402
 import eq_projects as EP  # noqa: E402
 import np_eq as NE  # noqa: E402
-from np_twin import pan_gain  # noqa: E402
-from test_gpu_stems import _write_project  # noqa: E402
+from fx_rig import MIX, REL, _pull_all, _quantise16, assert_close, build, mix_bound, over_bound, render_f32  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REL = 2.0 ** -23
-F32_TINY = float(np.float32(2.0) ** -149)
 
 
 def coeffs(api, sr, kind, f, q, g):
     b, a, _ = api.eq_coefficients(kind, sr, f, q, g)
     return np.concatenate([b, a[1:]])
-
-
-def build(api, p):
-    """The built project after one discarded render of `bus`: the sample_multi vertices keep voices that are still sounding when
-    a render ends (the reference's carried state), so only from the second render on does every render see the same input."""
-    built = p.build(api)
-    render_f32(api, built, "bus", p.cs)
-    return built
-
-
-def render_f32(api, built, out, cs, **opts):
-    sb, fb, g = built
-    for k, v in opts.items():
-        g.set_option(k, v)
-    assert g.set_output(out)
-    fb.set_time(0)
-    g.set_time(0)
-    g.reset_normalize_vertices()
-    return g.render_all(sb, fb, cs, 16, want_pcm=False)[1]
-
-
-def over_bound(y, want, E):
-    """The worst |y - want| over 2^-23 |want| + E max|want|, and where."""
-    y64, w64 = y.astype(np.float64), want.astype(np.float64)
-    lim = REL * np.abs(w64) + E * np.abs(w64).max()
-    r = np.abs(y64 - w64) / lim
-    r = np.where(np.isnan(r), np.inf, r)
-    i = np.unravel_index(int(r.argmax()), r.shape)
-    return float(r[i]), i
-
-
-def _f32_up(v):
-    r = v.astype(np.float32)
-    return np.where(r.astype(np.float64) < v, np.nextafter(r, np.float32(np.inf)), r).astype(np.float32)
-
-
-def _f32_down(v):
-    r = v.astype(np.float32)
-    return np.where(r.astype(np.float64) > v, np.nextafter(r, np.float32(-np.inf)), r).astype(np.float32)
-
-
-def assert_close(y, x, p, what="", E=EP.E):
-    """wet = 1, no pan, no gain.  The bound is on p, the filtered signal rounded once to f32, where the definition puts that
-    rounding: |p' - p| <= 2^-23 |p| + E max|p| for the device's p' against the twin's p.  What the vertex hands on is the
-    definition's f32 lerp of it, out = x + 1 (p' - x), and that lerp is not the identity: where |x| is much larger than |p| --
-    a 10 Hz low-pass on a drum bus -- p' - x rounds to an ulp of x, so one flipped rounding of p moves `out` by an ulp of x,
-    many times 2^-23 |out|.  So the check goes through the lerp, which is monotone in p': with p_lo / p_hi the f32 ends of the
-    allowed interval, lerp(p_lo) <= y <= lerp(p_hi).  Returns the largest |y - lerp(p)| in units of the plain form of the bound
-    on `out` (a figure to print, not asserted: above 1 only where the lerp magnifies a flip)."""
-    assert y.shape == x.shape == p.shape
-    one = np.float32(1.0)
-    p64 = p.astype(np.float64)
-    lim = REL * np.abs(p64) + E * np.abs(p64).max()
-    lo = x + one * (_f32_up(p64 - lim) - x)
-    hi = x + one * (_f32_down(p64 + lim) - x)
-    want = x + one * (p - x)
-    plain, at = over_bound(y, want, E)
-    same = float(np.mean(y.view(np.uint32) == want.view(np.uint32)))
-    bad = ~((lo <= y) & (y <= hi))
-    print("%s: %.4f of the values bit-identical to the twin, worst |y - want| %.3g x the plain bound, %d outside" % (what, same, plain, int(bad.sum())))
-    assert not bad.any(), (what, int(bad.sum()), np.argwhere(bad)[:4].tolist(), y[bad][:4], lo[bad][:4], hi[bad][:4])
-    return plain
 
 
 def twin_p(api_coeffs, x):
@@ -144,30 +77,16 @@ def test_below_the_grid_at_96_khz(gpu_api, kind):
 
 
 PEAK = ("peak", 900.0, 2.5, 9.0)
-MIX = [(0.3, 0.5, 30.0), (0.75, 1.7, -75.0), (0.5, -0.8, 0.0), (0.999, 1.0, 90.0), (0.0001, 1.0005, 0.0009)]
-
-
-def mix_bound(x, proc, gain, angle):
-    al, ar = pan_gain(np.ones(1, np.float32), np.ones(1, np.float32), gain, angle)
-    amp = np.abs(np.array([float(al[0]), float(ar[0])]))
-    return 4.0 * REL * np.maximum(np.abs(x), np.abs(proc)).astype(np.float64) * amp[None, :] + F32_TINY
+EQ_LAUNCHES = ["k_eq_local", "k_eq_carry", "k_eq_apply"]
+# (of the shared bodies the EQ takes the mix test alone: its other placement tests have cases and bounds of their own)
+EQ = fx_rig.FxKind("EQ", "k_eq", EQ_LAUNCHES, lambda p, name, src, case, **kw: EP.add_eq(p, name, src, *case, **kw), EP.base_project, PEAK, None, EP.E,
+                   twin=lambda api, sr, case, x: (twin_p(coeffs(api, sr, *case), x), x),
+                   mix=lambda api, sr, case, x, **kw: NE.eq(x, coeffs(api, sr, *case), **kw)[0])
 
 
 @pytest.mark.parametrize("wet,gain,angle", MIX)
 def test_wet_pan_and_gain(gpu_api, wet, gain, angle):
-    p = EP.base_project("drums")
-    EP.add_eq(p, "e", "bus", *PEAK, wet=wet, gain=gain, angle=angle)
-    built = build(gpu_api, p)
-    x = render_f32(gpu_api, built, "bus", p.cs)
-    y = render_f32(gpu_api, built, "e", p.cs)
-    c = coeffs(gpu_api, 48000, *PEAK)
-    want, _ = NE.eq(x, c, wet=wet, gain=gain, angle=angle)
-    proc, _ = NE.eq(x, c, processed=True)
-    lim = mix_bound(x, proc, gain, angle)
-    err = np.abs(y.astype(np.float64) - want.astype(np.float64))
-    print("wet %g gain %g angle %g: worst error / bound %.3g" % (wet, gain, angle, float(np.max(err / lim))))
-    assert (err <= lim).all(), (float(np.max(err / lim)), np.argwhere(err > lim)[:4].tolist())
-    assert np.abs(want - x).max() > 1e-3 * wet   # (the vertex does something, in proportion to the mix)
+    fx_rig.wet_pan_and_gain(gpu_api, EQ, wet, gain, angle, vertex="e")
 
 
 def test_dry_passes_the_input_through_as_a_sum_launch(gpu_api):
@@ -187,20 +106,6 @@ def test_dry_passes_the_input_through_as_a_sum_launch(gpu_api):
 
 
 CHUNK = ("lowshelf", 120.0, 0.9, 9.0)
-
-
-def _pull_all(api, built, out, cs):
-    sb, fb, g = built
-    assert g.set_output(out)
-    fb.set_time(0)
-    g.set_time(0)
-    g.reset_normalize_vertices()
-    blocks = []
-    for _ in range(cs):
-        l, r = g.render(sb, fb)
-        fb.set_time_to_next_block()   # (the caller moves the events on, as the reference's pull loop does)
-        blocks.append(np.stack([l, r], axis=1))
-    return np.concatenate(blocks)
 
 
 @pytest.mark.parametrize("bl", [1024, 64])
@@ -280,11 +185,6 @@ def test_batch_members_are_bitwise_their_own_renders(gpu_api):
         assert batch.render_all(cs, 16) == cs * 1024
         for i in range(8):
             assert np.array_equal(batch.read_pcm(i, cs), own[i][rep]), (rep, i)
-
-
-def _quantise16(x):
-    v = x.astype(np.float32) * np.float32(32767.0)
-    return np.clip(np.trunc(v.astype(np.float64)), -32768, 32767).astype(np.int64)
 
 
 def test_in_front_of_a_normalize_output(gpu_api):
@@ -390,56 +290,16 @@ def test_a_non_finite_input_frame_leaves_later_frames_finite(gpu_api):
 
 
 def test_front_end_renders_a_drum_bus_with_an_eq(gpu_api, tmp_path):
-    p = W.drum_project(seconds=1.0)
     # the drum bus `drums` feeds the band-pass in front of the output: put the EQ in between
-    line = ("eq", 1.0, 0.0, 1.0, "peak", 180.0, 1.5, 9.0)
-    i = p.calls["connect"].index(("drums", "band"))
-    p.calls["connect"][i:i + 1] = [("drums", "eq"), ("eq", "band")]
-    j = p.script_order.index(("connect", ("drums", "band")))
-    p.script_order[j:j + 1] = [("add_eq", line), ("connect", ("drums", "eq")), ("connect", ("eq", "band"))]
-    p.calls["add_eq"].append(line)
-    d = str(tmp_path / "proj")
-    _write_project(p, d)
-    out = str(tmp_path / "m.wav")
-    r = subprocess.run([sys.executable, "-m", "termdaw_amd", d, "-o", out], env=dict(os.environ, PYTHONPATH=ROOT), capture_output=True,
-                       text=True, timeout=600)
-    assert r.returncode == 0, r.stderr
-    st = gpu_api.State(open_dir=d)
-    assert st.refresh(), gpu_api.last_error()
-    assert 'add_eq("eq",' in st.dump_calls() and '"peak"' in st.dump_calls()
-    mem = st.render_to_memory()
-    with wave.open(out, "rb") as w:
-        words = np.frombuffer(w.readframes(w.getnframes()), np.int16).reshape(-1, 2)
-    assert words.shape == mem.shape and np.array_equal(words, mem) and np.abs(mem).max() > 1000
-    # ... and the EQ is really in the path: without it the words differ
-    q = W.drum_project(seconds=1.0)
-    d2 = str(tmp_path / "plain")
-    _write_project(q, d2)
-    st2 = gpu_api.State(open_dir=d2)
-    assert st2.refresh()
-    assert not np.array_equal(st2.render_to_memory(), mem)
+    p = fx_rig.into_the_drum_bus("add_eq", ("eq", 1.0, 0.0, 1.0, "peak", 180.0, 1.5, 9.0))
+    mem = fx_rig.front_end_renders(gpu_api, tmp_path, p, 'add_eq("eq",', '"peak"')
+    fx_rig.front_end_words_differ(gpu_api, tmp_path, W.drum_project(seconds=1.0), mem)
 
 
 def test_guard_keeps_the_scan_and_fast_sines_in_front_of_an_eq(gpu_api):
     """A scanned band-pass chain plus fast sines in front of a +12 dB peak EQ, in the front-end's defaults (band_mode 2,
     sine_mode 2): within 1e-6 RMS of the exact forms (band_mode 0, sine_mode 1), and the upstream launches are the scan forms."""
-    def project():
-        p = W.ProjectScript(48000, 1024)
-        p.set_length(1.0)
-        p.assets["a"] = W.Asset(W.noise_int16(7, 9000))
-        p.load_sample("a", "a", "")
-        p.event_files["f"] = np.array([(0.01, 60.0, 0.8), (0.4, 60.0, 0.0), (0.5, 64.0, 0.6), (0.9, 64.0, 0.0)], np.float32)
-        p.load_midi_floww("f", "f")
-        p.add_sampleloop("s", 0.5, 0.0, "a")
-        p.add_bandpass("b1", 1.0, 0.0, 1.0, 300.0, 5000.0, True)
-        p.add_bandpass("b2", 1.0, 10.0, 1.0, 200.0, 8000.0, True)
-        p.add_synth("y", 0.5, 0.0, "f", 0.4, 0.3, W.HIT_ADSR, 1.0, 0.8, W.NOTE_ADSR, 0.5, W.STD_ADSR)
-        p.add_sum("bus", 1.0, 0.0)
-        p.add_eq("e", 1.0, 0.0, 1.0, "peak", 1000.0, 2.0, 12.0)
-        p.connect("s", "b1"); p.connect("b1", "b2"); p.connect("b2", "bus"); p.connect("y", "bus"); p.connect("bus", "e")
-        p.set_output("e")
-        return p
-    p = project()
+    p = fx_rig.gpu_guard_project("add_eq", "e", ("peak", 1000.0, 2.0, 12.0), False)
     outs, names = {}, {}
     for mode, (bm, sm) in (("guard", (2, 2)), ("exact", (0, 1))):
         sb, fb, g = p.build(gpu_api)
@@ -458,16 +318,11 @@ def test_guard_keeps_the_scan_and_fast_sines_in_front_of_an_eq(gpu_api):
     assert not any(n in names["guard"] for n in ("k_band_pass", "k_band_spec")), names["guard"]
     assert "k_band_scan" not in names["exact"] and "k_sine_probe" not in names["exact"], names["exact"]
     for m in names:
-        assert [n for n in names[m] if n.startswith("k_eq")] == ["k_eq_local", "k_eq_carry", "k_eq_apply"], names[m]
+        assert [n for n in names[m] if n.startswith("k_eq")] == EQ_LAUNCHES, names[m]
 
 
 def test_kernel_names_with_and_without_an_eq(gpu_api):
-    for p in (W.drum_project(seconds=1.0), W.config2(seconds=1.0, n_src=8)):
-        sb, fb, g = p.build(gpu_api)
-        g.set_profiling(1)
-        g.render_all(sb, fb, p.cs, 16, want_f32=False)
-        names = list(g.kernel_times())
-        assert names and not any(n.startswith("k_eq") for n in names), names
+    fx_rig.projects_without_the_kind_launch_no_kernel_of_it(gpu_api, "k_eq")
     p = EP.base_project("drums")
     EP.add_eq(p, "e", "bus", *CHUNK)
     p.set_output("e")
@@ -475,5 +330,5 @@ def test_kernel_names_with_and_without_an_eq(gpu_api):
     g.set_profiling(1)
     g.render_all(sb, fb, p.cs, 16, want_f32=False)
     kt = g.kernel_times()
-    assert [n for n in kt if n.startswith("k_eq")] == ["k_eq_local", "k_eq_carry", "k_eq_apply"], list(kt)
-    assert all(kt[n][1] == 1 for n in ("k_eq_local", "k_eq_carry", "k_eq_apply")), kt
+    assert [n for n in kt if n.startswith("k_eq")] == EQ_LAUNCHES, list(kt)
+    assert all(kt[n][1] == 1 for n in EQ_LAUNCHES), kt

@@ -5,7 +5,7 @@ The input of the vertex under test -- and its key -- always come from the engine
 set_output on the vertex in front, read as f32 -- the oracle-verified part of the graph is not restated here.
 
 Bounds.  wet = 1, gain = 1, angle = 0, per value:  |p' - p| <= 2^-23 |p| + E max|p| on the filter's output p, carried through the
-definition's f32 lerp to the vertex' output (test_gpu_eq.assert_close says why it is not asserted on the output as it stands).
+definition's f32 lerp to the vertex' output (fx_rig.assert_close says why it is not asserted on the output as it stands).
 The first term is the one f32 rounding of p, which may flip; E covers the float64 re-association of the scans, the follower's
 included: 8 x what the numpy emulation of the tiled scans shows over this file's own grid and inputs (tests/filter_projects.py E,
 derived and re-checked on the CPU by tests/test_filter_host.py; far under the cap 2^-28).  g[n] is the same bits on both sides
@@ -14,9 +14,7 @@ With wet in (0, 1), pan and gain: 4 x 2^-23 x max(|dry|, |p|) x |amplitude| abso
 
 Every case prints its worst error over the bound; DESIGN.md §3w records how many cases came out bit-identical."""
 import os
-import subprocess
 import sys
-import wave
 
 import numpy as np
 import pytest
@@ -24,15 +22,13 @@ import pytest
 from termdaw_amd import workloads as W
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import fx_rig  # noqa: E402
 import filter_projects as FP  # noqa: E402
 import key_projects as KP  # noqa: E402
 import np_filter as NF  # noqa: E402
-from test_gpu_compressor import MIX, _quantise16  # noqa: E402
-from test_gpu_eq import REL, F32_TINY, _pull_all, assert_close, build, mix_bound, render_f32  # noqa: E402
-from test_gpu_stems import _write_project  # noqa: E402
+from fx_rig import MIX, REL, _guard_renders, _pull_all, assert_close, build, render_f32  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FOLLOWER = ["k_filt_detect", "k_filt_carry_y1", "k_filt_env", "k_filt_carry_e"]
 FILTER = ["k_filt_local", "k_filt_carry", "k_filt_apply"]
 # kind, freq, q, lfo_oct, rate, stereo, shape, env_oct, sens_db, attack_ms, release_ms
@@ -53,6 +49,11 @@ def twin(api, sr, case, x, state=None, t0=0, key=None):
 
 def close(y, x, p, what):
     return assert_close(y, x, p, what, FP.E)
+
+
+FILT = fx_rig.FxKind("filter", "k_filt", FOLLOWER + FILTER, FP.add_filter, FP.base_project, CASE, CASE_HP, FP.E,
+                     twin=lambda api, sr, case, x: (twin(api, sr, case, x)[0], x),
+                     mix=lambda api, sr, case, x, **kw: NF.process(x, FP.spec(api, sr, case), **kw)[0])
 
 
 # ---- the grid ----
@@ -254,19 +255,7 @@ def test_a_non_finite_input_frame_is_non_finite_at_that_frame_only(gpu_api):
 # ---- the mix ----
 @pytest.mark.parametrize("wet,gain,angle", MIX)
 def test_wet_pan_and_gain(gpu_api, wet, gain, angle):
-    p = FP.base_project("drums")
-    FP.add_filter(p, "fl", "bus", CASE, wet=wet, gain=gain, angle=angle)
-    built = build(gpu_api, p)
-    x = render_f32(gpu_api, built, "bus", p.cs)
-    y = render_f32(gpu_api, built, "fl", p.cs)
-    sp = FP.spec(gpu_api, 48000, CASE)
-    want, _ = NF.process(x, sp, wet=wet, gain=gain, angle=angle)
-    proc, _ = NF.process(x, sp, processed=True)
-    lim = mix_bound(x, proc, gain, angle)
-    err = np.abs(y.astype(np.float64) - want.astype(np.float64))
-    print("wet %g gain %g angle %g: worst error / bound %.3g" % (wet, gain, angle, float(np.max(err / lim))))
-    assert (err <= lim).all(), (float(np.max(err / lim)), np.argwhere(err > lim)[:4].tolist())
-    assert np.abs(want - x).max() > 1e-3 * wet   # (the vertex does something, in proportion to the mix)
+    fx_rig.wet_pan_and_gain(gpu_api, FILT, wet, gain, angle, vertex="fl")
 
 
 def test_dry_passes_the_input_through_as_a_sum_launch(gpu_api):
@@ -299,78 +288,15 @@ def test_dry_passes_the_input_through_as_a_sum_launch(gpu_api):
 
 # ---- placement ----
 def test_in_front_of_a_normalize_output(gpu_api):
-    p = FP.base_project("drums", seconds=1.0)
-    FP.add_filter(p, "fl", "bus", CASE)
-    p.add_normalize("out", 1.0, 0.0)
-    p.connect("fl", "out")
-    built = build(gpu_api, p)
-    x = render_f32(gpu_api, built, "bus", p.cs)
-    c = render_f32(gpu_api, built, "fl", p.cs)
-    close(c, x, twin(gpu_api, 48000, CASE, x)[0], "in front of Normalize")
-    # normalize_gen (extensions.rs:321-329) on what the filter really handed on: the running block peak from 1e-6, f32
-    pk = np.abs(c).reshape(-1, p.bl * 2).max(axis=1)
-    run = np.maximum.accumulate(np.concatenate([[np.float32(0.000001)], pk]).astype(np.float32))[1:]
-    want = c * np.repeat(np.float32(1.0) / run, p.bl)[:, None]
-    sb, fb, g = built
-    g.set_output("out")
-    fb.set_time(0)
-    g.set_time(0)
-    g.reset_normalize_vertices()
-    pcm, f = g.render_all(sb, fb, p.cs, 16)
-    assert (np.abs(f.astype(np.float64) - want) <= 2.0 * REL * np.abs(want) + F32_TINY).all()
-    assert np.abs(pcm.astype(np.int64) - _quantise16(want)).max() <= 1
+    fx_rig.in_front_of_a_normalize_output(gpu_api, FILT, vertex="fl")
 
 
 def test_as_a_stem_and_two_in_series(gpu_api):
-    p = FP.base_project("drums", seconds=1.0)
-    FP.add_filter(p, "f1", "bus", CASE)
-    FP.add_filter(p, "f2", "f1", CASE_HP, gain=0.8, angle=-20.0)
-    p.add_sum("post", 0.5, 10.0)
-    p.connect("f2", "post")
-    built = build(gpu_api, p)
-    x = render_f32(gpu_api, built, "bus", p.cs)
-    y1 = render_f32(gpu_api, built, "f1", p.cs)
-    close(y1, x, twin(gpu_api, 48000, CASE, x)[0], "first of two")
-    # the second one against the twin on what the first one really handed it
-    y2 = render_f32(gpu_api, built, "f2", p.cs)
-    s2 = FP.spec(gpu_api, 48000, CASE_HP)
-    w2, _ = NF.process(y1, s2, gain=0.8, angle=-20.0)
-    proc, _ = NF.process(y1, s2, processed=True)
-    assert (np.abs(y2.astype(np.float64) - w2) <= mix_bound(y1, proc, 0.8, -20.0)).all()
-    # both as stems of a render whose output sits downstream
-    sb, fb, g = built
-    g.set_output("post")
-    g.set_stems(["f2", "f1"])
-    fb.set_time(0)
-    g.set_time(0)
-    g.render_all(sb, fb, p.cs, 16)
-    assert np.abs(g.read_stem_pcm(0).astype(np.int64) - _quantise16(y2)).max() == 0
-    assert np.abs(g.read_stem_pcm(1).astype(np.int64) - _quantise16(y1)).max() == 0
-    g.set_stems([])
+    fx_rig.as_a_stem_and_two_in_series(gpu_api, FILT, "f1", "f2")
 
 
 def test_fed_by_an_inlined_loop_source_and_a_gain_stage(gpu_api):
-    p = W.ProjectScript(48000, 1024)
-    p.set_length(0.5)
-    p.assets["a0"] = W.Asset(W.noise_int16(50, 20011))
-    p.assets["a1"] = W.Asset(W.noise_int16(51, 9001))
-    p.load_sample("a0", "a0", "")
-    p.load_sample("a1", "a1", "normalize-seperate")
-    p.add_sampleloop("l0", 0.7, 30.0, "a0")     # read by the filter itself (term kinds 1 / 3)
-    p.add_sampleloop("l1", 0.02, 0.0, "a1")
-    p.add_sum("stage", 0.5, -45.0)              # one input: a gain / pan stage, read through (term kind 4)
-    p.connect("l1", "stage")
-    FP.add_filter(p, "fl", "l0", CASE)
-    p.connect("stage", "fl")
-    p.set_output("fl")
-    built = p.build(gpu_api)
-    a = render_f32(gpu_api, built, "l0", p.cs)
-    b = render_f32(gpu_api, built, "stage", p.cs)
-    x = (np.float32(0.0) + a) + b               # sum_inputs (extensions.rs:310-319), f32, in connect() order
-    pw, _ = twin(gpu_api, 48000, CASE, x)
-    for packed in (1, 0):
-        y = render_f32(gpu_api, built, "fl", p.cs, packed_samples=packed)
-        close(y, x, pw, "inlined terms, packed_samples %d" % packed)
+    fx_rig.fed_by_an_inlined_loop_source_and_a_gain_stage(gpu_api, FILT, CASE, W.noise_int16(50, 20011), vertex="fl")
 
 
 def test_batch_members_are_bitwise_their_own_renders(gpu_api):
@@ -390,47 +316,17 @@ def test_batch_members_are_bitwise_their_own_renders(gpu_api):
         else:
             p.set_output("fl")
         projects.append(p)
-    cs = projects[0].cs
-    own = []   # per project: its first and its second render (the second starts with the voices the first left sounding)
-    for p in projects:
-        sb, fb, g = p.build(gpu_api)
-        first = g.render_all(sb, fb, cs, 16, want_f32=False)[0]
-        g.reset_normalize_vertices()
-        fb.set_time(0)
-        g.set_time(0)
-        own.append((first, g.render_all(sb, fb, cs, 16, want_f32=False)[0]))
-    batch = gpu_api.Batch()
-    for p in projects:
-        batch.add(*p.build(gpu_api))
-    for rep in range(2):
-        batch.rewind()
-        assert batch.render_all(cs, 16) == cs * 1024
-        for i in range(8):
-            assert np.array_equal(batch.read_pcm(i, cs), own[i][rep]), (rep, i)
+    # (every other project is the same ducking project: the first renders are not all different)
+    fx_rig.batch_matches_own_renders(gpu_api, projects, distinct=False)
 
 
 def test_projects_without_a_filter_launch_no_filter_kernel(gpu_api):
-    for p in (W.drum_project(seconds=1.0), W.config2(seconds=1.0, n_src=8)):
-        sb, fb, g = p.build(gpu_api)
-        g.set_profiling(1)
-        g.render_all(sb, fb, p.cs, 16, want_f32=False)
-        names = list(g.kernel_times())
-        assert names and not any(n.startswith("k_filt") for n in names), names
+    fx_rig.projects_without_the_kind_launch_no_kernel_of_it(gpu_api, "k_filt")
 
 
 # ---- the guard modes ----
 def _guard_project(shape):
-    p = W.ProjectScript(48000, 1024)
-    p.set_length(1.0)
-    p.assets["a"] = W.Asset(W.noise_int16(7, 9000))
-    p.load_sample("a", "a", "")
-    p.event_files["f"] = np.array([(0.01, 60.0, 0.8), (0.4, 60.0, 0.0), (0.5, 64.0, 0.6), (0.9, 64.0, 0.0)], np.float32)
-    p.load_midi_floww("f", "f")
-    p.add_sampleloop("s", 0.5, 0.0, "a")
-    p.add_bandpass("b1", 1.0, 0.0, 1.0, 300.0, 5000.0, True)
-    p.add_bandpass("b2", 1.0, 10.0, 1.0, 200.0, 8000.0, True)
-    p.add_synth("y", 0.5, 0.0, "f", 0.4, 0.3, W.HIT_ADSR, 1.0, 0.8, W.NOTE_ADSR, 0.5, W.STD_ADSR)
-    p.add_sum("bus", 1.0, 0.0)
+    p = fx_rig.gpu_guard_base()
     p.add_filter("fl", 1.0, 0.0, 1.0, *(STILL if shape == "key_unheard" else CASE))
     if shape == "down":   # loop -> filter -> band-pass chain; the synth joins behind the filter
         p.connect("s", "fl"); p.connect("fl", "b1"); p.connect("b1", "b2"); p.connect("b2", "bus"); p.connect("y", "bus")
@@ -447,34 +343,13 @@ def _guard_project(shape):
     return p
 
 
-def _guard_renders(gpu_api, p):
-    outs, names = {}, {}
-    for mode, (bm, sm) in (("guard", (2, 2)), ("exact", (0, 1))):
-        sb, fb, g = p.build(gpu_api)
-        g.set_option("band_mode", bm)
-        g.set_option("sine_mode", sm)
-        g.set_profiling(1)
-        outs[mode] = g.render_all(sb, fb, p.cs, 16, want_pcm=False)[1]
-        names[mode] = list(g.kernel_times())
-    return outs, names
-
-
 def test_guard_keeps_the_scan_and_fast_sines_downstream_of_a_filter(gpu_api):
-    outs, names = _guard_renders(gpu_api, _guard_project("down"))
-    rms = float(np.sqrt(np.mean((outs["guard"].astype(np.float64) - outs["exact"].astype(np.float64)) ** 2)))
-    print("guarded scan + fast sines downstream of a filter: rms %.3g against the exact forms" % rms)
-    assert rms <= 1e-6 and np.abs(outs["exact"]).max() > 0.05
-    assert "k_band_scan" in names["guard"] and "k_sine_probe" in names["guard"], names["guard"]
-    assert not any(n in names["guard"] for n in ("k_band_pass", "k_band_spec")), names["guard"]
-    assert [n for n in names["guard"] if n.startswith("k_filt")] == FOLLOWER + FILTER
+    fx_rig.guard_keeps_the_scan_and_fast_sines_downstream(gpu_api, _guard_project("down"), "filter", "k_filt", FOLLOWER + FILTER)
 
 
 @pytest.mark.parametrize("shape", ["up", "key"])
 def test_guard_renders_the_exact_forms_upstream_of_a_filter_and_of_its_key(gpu_api, shape):
-    outs, names = _guard_renders(gpu_api, _guard_project(shape))
-    assert np.array_equal(_bits(outs["guard"]), _bits(outs["exact"])) and np.abs(outs["exact"]).max() > 0.05
-    assert "k_band_scan" not in names["guard"] and "k_sine_probe" not in names["guard"], names["guard"]
-    assert any(n in names["guard"] for n in ("k_band_pass", "k_band_spec")), names["guard"]
+    fx_rig.guard_renders_the_exact_forms_upstream(gpu_api, _guard_project(shape))
 
 
 def test_guard_carries_its_estimate_past_a_key_that_no_follower_hears(gpu_api):
@@ -486,33 +361,8 @@ def test_guard_carries_its_estimate_past_a_key_that_no_follower_hears(gpu_api):
 
 # ---- the front end ----
 def test_front_end_renders_a_drum_bus_with_a_keyed_filter(gpu_api, tmp_path):
-    fl = ("wah", 1.0, 0.0, 0.8, "lowpass", 300.0, 6.0, 1.0, 2.0, 0.25, "sine", 5.0, 12.0, 1.0, 120.0)
-    p = W.drum_project(seconds=1.0)
     # the drum bus `drums` feeds the band-pass in front of the output: put the filter in between, keyed by the kick band
-    i = p.calls["connect"].index(("drums", "band"))
-    p.calls["connect"][i:i + 1] = [("drums", "wah"), ("wah", "band")]
-    j = p.script_order.index(("connect", ("drums", "band")))
-    p.script_order[j:j + 1] = [("add_filter", fl), ("connect", ("drums", "wah")), ("connect", ("wah", "band")), ("connect_key", ("kickband", "wah"))]
-    p.calls["add_filter"].append(fl)
-    p.calls["connect_key"].append(("kickband", "wah"))
-    d = str(tmp_path / "proj")
-    _write_project(p, d)
-    out = str(tmp_path / "m.wav")
-    r = subprocess.run([sys.executable, "-m", "termdaw_amd", d, "-o", out], env=dict(os.environ, PYTHONPATH=ROOT), capture_output=True,
-                       text=True, timeout=600)
-    assert r.returncode == 0, r.stderr
-    st = gpu_api.State(open_dir=d)
-    assert st.refresh(), gpu_api.last_error()
-    dump = st.dump_calls()
-    assert 'add_filter("wah",' in dump and 'connect_key("kickband","wah")' in dump
-    mem = st.render_to_memory()
-    with wave.open(out, "rb") as w:
-        words = np.frombuffer(w.readframes(w.getnframes()), np.int16).reshape(-1, 2)
-    assert words.shape == mem.shape and np.array_equal(words, mem) and np.abs(mem).max() > 1000
-    # ... and the filter is really in the path: without it the words differ
-    q = W.drum_project(seconds=1.0)
-    d2 = str(tmp_path / "plain")
-    _write_project(q, d2)
-    st2 = gpu_api.State(open_dir=d2)
-    assert st2.refresh()
-    assert not np.array_equal(st2.render_to_memory(), mem)
+    fl = ("wah", 1.0, 0.0, 0.8, "lowpass", 300.0, 6.0, 1.0, 2.0, 0.25, "sine", 5.0, 12.0, 1.0, 120.0)
+    p = fx_rig.into_the_drum_bus("add_filter", fl, key="kickband")
+    mem = fx_rig.front_end_renders(gpu_api, tmp_path, p, 'add_filter("wah",', 'connect_key("kickband","wah")')
+    fx_rig.front_end_words_differ(gpu_api, tmp_path, W.drum_project(seconds=1.0), mem)

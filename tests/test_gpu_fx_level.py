@@ -1,7 +1,7 @@
 """The effect kinds in ONE level: a drum bus feeds the first n of a compressor, an EQ, a delay, a saturator, a chorus, a reverb, a
-gate, a phaser, a vocoder and a filter in parallel, the n feed a Sum `mix`, and every effect vertex is a stem (graph B); n = 7, 8,
-9 and 10, the sizes the level had as the kinds were added.  The vocoder and the filter take their key from the snare alone, a
-vertex two levels up.  The per-kind suites put one kind in a level at a time; here the kinds' lowerings share the level's scratch
+gate, a phaser, a vocoder, a filter, a limiter and a multiband in parallel, the n feed a Sum `mix`, and every effect vertex is a
+stem (graph B); n = 7 .. 12, the sizes the level had as the kinds were added.  The vocoder and the filter take their key from the
+snare alone, a vertex two levels up.  The per-kind suites put one kind in a level at a time; here the kinds' lowerings share the level's scratch
 edge buffers, its scratch region and the loop over the launch families.
 
 Against B stand graphs A, one per kind: the bus feeds that kind alone and the kind is the output.  Same kernels on the same input,
@@ -11,7 +11,11 @@ kind named as the output, the stem list -- and with it the level of n -- unchang
 
 0.25 s at 48 kHz in blocks of 256: about 12 k frames, longer than the 4 096 frames up to which the saturator and the chorus take their
 one-launch forms (k_sat_sum / k_chorus_sum first) and six 2 048-frame tiles of the scans; in chunks of 4 096 frames neither *_sum
-launch may appear, the scans keep their launches at two tiles.  The parameters are the per-kind suites' mid-range ones at wet 1,
+launch may appear, the scans keep their launches at two tiles.  The limiter's lowering takes two scratch edge buffers and a carried
+line beside the other kinds' in the same level; its window of 480 frames makes the chunks' second tile read its halo from the first
+and the first from the line.  The multiband's takes four scratch edge buffers, a carried line, a block table in the arena and -- over
+three descriptors of its own per vertex -- the compressor's k_comp_env and the scalar carry beside the compressor's own launches of
+them in the same level.  The parameters are the per-kind suites' mid-range ones at wet 1,
 gain 1, angle 0; the delay's D = 1 024 keeps it to one k_delay_apply tile in both forms, as in tests/test_gpu_fx_lines.py."""
 import os
 import sys
@@ -22,7 +26,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import chorus_projects as CP  # noqa: E402
 import eq_projects as EP  # noqa: E402
-import test_gpu_eq as TG  # noqa: E402
+import fx_rig as TG  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 BL = 256
@@ -42,6 +46,9 @@ KINDS = {
             ("k_voc_local", "k_voc_carry_z", "k_voc_env", "k_voc_carry_env", "k_voc_apply"), True),
     "filt": ("add_filter", ("lowpass", 400.0, 4.0, 2.0, 3.0, 0.25, "sine", 4.0, 18.0, 2.0, 80.0),
              ("k_filt_detect", "k_filt_carry_y1", "k_filt_env", "k_filt_carry_e", "k_filt_local", "k_filt_carry", "k_filt_apply"), True),
+    "lim": ("add_limiter", (-6.0, 10.0, 50.0, 12.0), ("k_lim_detect", "k_lim_carry", "k_lim_apply"), True),
+    "mb": ("add_multiband", (200.0, 2000.0, (-40.0, -30.0, -36.0), (4.0, 8.0, 2.0), 5.0, 50.0, 6.0, (0.0, 3.0, 6.0)),
+           ("k_mb_local", "k_mb_carry", "k_mb_detect", "k_mb_carry_y1", "k_mb_env", "k_mb_carry_yl", "k_mb_apply"), True),
 }
 KEYED = ("voc", "filt")
 LONG_FORM_ONLY = {"k_sat_sum", "k_chorus_sum"}   # (chunks of more than 4 096 frames)
@@ -79,7 +86,7 @@ def same_bits(a, b):
 
 
 def level(gpu_api, n):
-    """(cs, B): the first n kinds in one level, every one a stem, after the discarded first render of tests/test_gpu_eq.py's build()."""
+    """(cs, B): the first n kinds in one level, every one a stem, after the discarded first render of tests/fx_rig.py's build()."""
     kinds = list(KINDS)[:n]
     pb = project(kinds, mix=True)
     b = TG.build(gpu_api, pb)
@@ -90,12 +97,13 @@ def level(gpu_api, n):
 
 @pytest.fixture(scope="module")
 def alone(gpu_api):
-    """The ten A, built like B: a kind alone computes the same whatever else B holds, so every level size shares them."""
-    assert len(KINDS) == 10 and gpu_api.delay_params(48000, *KINDS["dly"][1])[0] == 1024
+    """The twelve A, built like B: a kind alone computes the same whatever else B holds, so every level size shares them."""
+    assert len(KINDS) == 12 and list(KINDS)[-2:] == ["lim", "mb"] and gpu_api.delay_params(48000, *KINDS["dly"][1])[0] == 1024
+    assert gpu_api.limiter_params(48000, *KINDS["lim"][1])[2] == 480
     return {k: TG.build(gpu_api, project([k], mix=False)) for k in KINDS}
 
 
-@pytest.fixture(scope="module", params=[7, 8, 9, 10])
+@pytest.fixture(scope="module", params=[7, 8, 9, 10, 11, 12])
 def graphs(request, gpu_api, alone):
     """B of the first n kinds and their A."""
     cs, b = level(gpu_api, request.param)
@@ -139,6 +147,11 @@ def test_every_kind_in_one_level_has_the_bits_of_the_kind_alone(graphs, chunk):
         want_f32[k] = want
     if "voc" in kinds:
         assert np.abs(want_f32["voc"]).max() > 0.005
+    if "lim" in kinds:   # the limiter works on this bus: its stem is held under the ceiling, which the bus driven by 12 dB would pass
+        assert np.abs(want_f32["lim"]).max() <= 10.0 ** (-6.0 / 20.0) * (1.0 + 2.0 ** -22)
+    if "mb" in kinds:    # the multiband works on this bus: its stem differs from the bus by far more than a rounding
+        bus = render(a["mb"], "bus", cs, chunk)[1]
+        assert np.abs(want_f32["mb"].astype(np.float64) - bus).max() > 1e-2 * np.abs(bus).max()
     # a kind as B's output: the stems keep the others in its level (their launches are there), `mix` is not computed
     for k in (kinds if len(kinds) == 7 else kinds[-1:]):
         (_, got), k_names = profiled(g, lambda: render(b, k, cs, chunk))

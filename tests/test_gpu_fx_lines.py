@@ -22,7 +22,7 @@ import np_chorus as NC  # noqa: E402
 import np_delay as ND  # noqa: E402
 import np_reverb as NR  # noqa: E402
 import np_saturator as NS  # noqa: E402
-import test_gpu_eq as TG  # noqa: E402
+import fx_rig as TG  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 SR = 48000

@@ -2,9 +2,9 @@
 level from the sum of its key sources, against tests/np_key.py -- the two vertices' twins composed -- on the input x and the key k
 the engine itself renders at the vertices in front.
 
-The bounds are the two vertices' own and are not derived again: the gate's test_gpu_eq.assert_close with gate_projects.E (the env
+The bounds are the two vertices' own and are not derived again: the gate's fx_rig.assert_close with gate_projects.E (the env
 sequence of a gate keyed by `gated` is that of the unkeyed gate on `gated`, which E was derived on), the compressor's
-test_gpu_compressor.assert_close, test_gpu_eq.mix_bound where wet, pan or gain are in play, one word for PCM.  Shapes: 0.5 s
+fx_rig.assert_close_f32, fx_rig.mix_bound where wet, pan or gain are in play, one word for PCM.  Shapes: 0.5 s
 (24 576 frames at 48 kHz, 12 tiles of 2 048), 4 096-frame chunks, block pulls of 1 024 and 64 frames."""
 import os
 import subprocess
@@ -20,10 +20,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import gate_projects as GP  # noqa: E402
 import key_projects as KP  # noqa: E402
 import np_key as NK  # noqa: E402
-import test_gpu_compressor as TC  # noqa: E402
-from test_gpu_compressor import _quantise16  # noqa: E402
-from test_gpu_eq import _pull_all, assert_close, build, mix_bound, render_f32  # noqa: E402
-from test_gpu_stems import _write_project  # noqa: E402
+from fx_rig import MIX, assert_close, assert_close_f32, build, mix_bound, _pull_all, _quantise16, render_f32, _write_project  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -55,7 +52,7 @@ def _close(api, kind, sr, case, y, x, k, what):
     if kind == "gate":
         assert_close(y, x, p, what, GP.E)
     else:
-        TC.assert_close(y, want, what)
+        assert_close_f32(y, want, what)
     return want
 
 
@@ -275,7 +272,7 @@ def test_a_dry_keyed_vertex_is_bitwise_the_dry_unkeyed_one(gpu_api, kind):
     assert not any(n.startswith(("k_gate", "k_comp")) for n in g.kernel_times())
 
 
-@pytest.mark.parametrize("wet,gain,angle", TC.MIX[:3])
+@pytest.mark.parametrize("wet,gain,angle", MIX[:3])
 @pytest.mark.parametrize("kind", KINDS)
 def test_wet_pan_and_gain(gpu_api, kind, wet, gain, angle):
     p, key = KP.ducking_project("keybus")

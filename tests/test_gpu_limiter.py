@@ -5,7 +5,7 @@ The input of the vertex under test always comes from the engine itself: a second
 the vertex in front, read as f32 -- the oracle-verified part of the graph is not restated here.
 
 Bounds.  wet = 1, gain = 1, angle = 0, per value:  |p' - p| <= 2^-23 |p| + E max|p| on the limited signal p, carried through the
-definition's f32 lerp against the DELAYED input xd to the vertex' output (test_gpu_eq.assert_close says why it is not asserted on
+definition's f32 lerp against the DELAYED input xd to the vertex' output (fx_rig.assert_close says why it is not asserted on
 the output as it stands).  The first term is the one f32 rounding of the chain, which may flip; E covers the float64 order of the
 release scan and of the prefix sums behind G: 8 x what the numpy emulation of the kernels' order shows over this file's own grid
 and inputs (tests/limiter_projects.py E, derived and re-checked on the CPU by tests/test_limiter_host.py; E = 3.2e-10, under the
@@ -16,9 +16,7 @@ of the twin's quantised value.
 
 Every case prints its worst error over the bound; DESIGN.md §3x records how many cases came out bit-identical."""
 import os
-import subprocess
 import sys
-import wave
 
 import numpy as np
 import pytest
@@ -26,14 +24,12 @@ import pytest
 from termdaw_amd import workloads as W
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import fx_rig  # noqa: E402
 import limiter_projects as LP  # noqa: E402
 import np_limiter as NL  # noqa: E402
-from test_gpu_compressor import MIX, _quantise16  # noqa: E402
-from test_gpu_eq import REL, F32_TINY, _f32_down, _pull_all, assert_close, build, mix_bound, render_f32  # noqa: E402
-from test_gpu_stems import _write_project  # noqa: E402
+from fx_rig import MIX, _f32_down, _pull_all, assert_close, build, render_f32  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIM_LAUNCHES = ["k_lim_detect", "k_lim_carry", "k_lim_apply"]
 CASE = (-6.0, 10.0, 50.0, 12.0)   # ceiling, lookahead (480 frames at 48 kHz), release, drive
 
@@ -54,6 +50,12 @@ def under_the_ceiling(y, xd, c, what):
     lo, hi = xd + one * (-top - xd), xd + one * (top - xd)
     bad = ~((lo <= y) & (y <= hi))
     assert not bad.any(), (what, int(bad.sum()), np.argwhere(bad)[:4].tolist(), y[bad][:4], c)
+
+
+LIMITER = fx_rig.FxKind("limiter", "k_lim", LIM_LAUNCHES, LP.add_limiter, LP.base_project, CASE, (-12.0, 0.0, 5.0, 0.0), LP.E,
+                        twin=lambda api, sr, case, x: twin(api, sr, case, x)[:2],
+                        mix=lambda api, sr, case, x, **kw: NL.process(x, api.limiter_params(sr, *case), **kw)[0],
+                        acts=lambda proc, xd: np.abs(proc - xd).max() > 1e-3)
 
 
 # ---- the grid ----
@@ -176,174 +178,40 @@ def test_more_than_256_tiles(gpu_api):
 # ---- the mix ----
 @pytest.mark.parametrize("wet,gain,angle", MIX)
 def test_wet_pan_and_gain(gpu_api, wet, gain, angle):
-    p = LP.base_project("drums", seconds=0.5)
-    LP.add_limiter(p, "m", "bus", CASE, wet=wet, gain=gain, angle=angle)
-    built = build(gpu_api, p)
-    x = render_f32(gpu_api, built, "bus", p.cs)
-    y = render_f32(gpu_api, built, "m", p.cs)
-    c = gpu_api.limiter_params(48000, *CASE)
-    want, _ = NL.process(x, c, wet=wet, gain=gain, angle=angle)
-    proc, xd = NL.serial(x, c)[:2]
-    lim = mix_bound(xd, proc, gain, angle)
-    err = np.abs(y.astype(np.float64) - want.astype(np.float64))
-    print("wet %g gain %g angle %g: worst error / bound %.3g" % (wet, gain, angle, float(np.max(err / lim))))
-    assert (err <= lim).all(), (float(np.max(err / lim)), np.argwhere(err > lim)[:4].tolist())
-    assert np.abs(proc - xd).max() > 1e-3   # (the vertex does something)
+    fx_rig.wet_pan_and_gain(gpu_api, LIMITER, wet, gain, angle, vertex="m", seconds=0.5)
 
 
 def test_dry_passes_the_input_through_undelayed(gpu_api):
-    p = LP.base_project("drums", seconds=0.5)
-    LP.add_limiter(p, "dry", "bus", CASE, wet=0.0)
-    LP.add_limiter(p, "almost", "bus", CASE, wet=0.00009)
-    LP.add_limiter(p, "wet", "bus", CASE)
-    built = build(gpu_api, p)
-    x = render_f32(gpu_api, built, "bus", p.cs)
-    for name in ("dry", "almost"):
-        y = render_f32(gpu_api, built, name, p.cs)
-        assert np.array_equal(y, x), (name, np.argwhere(y != x)[:4].tolist())
-    g = built[2]
-    g.set_profiling(1)
-    render_f32(gpu_api, built, "dry", p.cs)
-    names = list(g.kernel_times())
-    assert not any(n.startswith("k_lim") for n in names) and "k_sum" in names, names   # wet < 0.0001: a plain sum launch
-    render_f32(gpu_api, built, "wet", p.cs)
-    assert [n for n in g.kernel_times() if n.startswith("k_lim")] == LIM_LAUNCHES
+    fx_rig.dry_passes_the_input_through(gpu_api, LIMITER, seconds=0.5)
 
 
 # ---- placement ----
 def test_in_front_of_a_normalize_output(gpu_api):
-    p = LP.base_project("drums", seconds=1.0)
-    LP.add_limiter(p, "m", "bus", CASE)
-    p.add_normalize("out", 1.0, 0.0)
-    p.connect("m", "out")
-    built = build(gpu_api, p)
-    x = render_f32(gpu_api, built, "bus", p.cs)
-    c = render_f32(gpu_api, built, "m", p.cs)
-    pw, xd, _, _ = twin(gpu_api, 48000, CASE, x)
-    close(c, xd, pw, "in front of Normalize")
-    # normalize_gen (extensions.rs:321-329) on what the limiter really handed on: the running block peak from 1e-6, f32
-    pk = np.abs(c).reshape(-1, p.bl * 2).max(axis=1)
-    run = np.maximum.accumulate(np.concatenate([[np.float32(0.000001)], pk]).astype(np.float32))[1:]
-    want = c * np.repeat(np.float32(1.0) / run, p.bl)[:, None]
-    sb, fb, g = built
-    g.set_output("out")
-    fb.set_time(0)
-    g.set_time(0)
-    g.reset_normalize_vertices()
-    pcm, f = g.render_all(sb, fb, p.cs, 16)
-    assert (np.abs(f.astype(np.float64) - want) <= 2.0 * REL * np.abs(want) + F32_TINY).all()
-    assert np.abs(pcm.astype(np.int64) - _quantise16(want)).max() <= 1
+    fx_rig.in_front_of_a_normalize_output(gpu_api, LIMITER, vertex="m")
 
 
 def test_as_a_stem_and_two_in_series(gpu_api):
-    c2 = (-12.0, 0.0, 5.0, 0.0)
-    p = LP.base_project("drums", seconds=1.0)
-    LP.add_limiter(p, "m1", "bus", CASE)
-    LP.add_limiter(p, "m2", "m1", c2, gain=0.8, angle=-20.0)
-    p.add_sum("post", 0.5, 10.0)
-    p.connect("m2", "post")
-    built = build(gpu_api, p)
-    x = render_f32(gpu_api, built, "bus", p.cs)
-    y1 = render_f32(gpu_api, built, "m1", p.cs)
-    pw, xd, _, _ = twin(gpu_api, 48000, CASE, x)
-    close(y1, xd, pw, "first of two")
-    # the second one against the twin on what the first one really handed it
-    y2 = render_f32(gpu_api, built, "m2", p.cs)
-    k2 = gpu_api.limiter_params(48000, *c2)
-    w2, _ = NL.process(y1, k2, gain=0.8, angle=-20.0)
-    proc, xd2 = NL.serial(y1, k2)[:2]
-    assert np.abs(proc - xd2).max() > 1e-3
-    assert (np.abs(y2.astype(np.float64) - w2) <= mix_bound(xd2, proc, 0.8, -20.0)).all()
-    # both as stems of a render whose output sits downstream
-    sb, fb, g = built
-    g.set_output("post")
-    g.set_stems(["m2", "m1"])
-    fb.set_time(0)
-    g.set_time(0)
-    g.render_all(sb, fb, p.cs, 16)
-    assert np.abs(g.read_stem_pcm(0).astype(np.int64) - _quantise16(y2)).max() == 0
-    assert np.abs(g.read_stem_pcm(1).astype(np.int64) - _quantise16(y1)).max() == 0
-    g.set_stems([])
+    fx_rig.as_a_stem_and_two_in_series(gpu_api, LIMITER, "m1", "m2")
 
 
 def test_fed_by_an_inlined_loop_source_and_a_gain_stage(gpu_api):
     import gate_projects as GP
     case = (-12.0, 2.0, 30.0, 6.0)
-    p = W.ProjectScript(48000, 1024)
-    p.set_length(0.5)
-    p.assets["a0"] = W.Asset(GP.gated_int16(3))
-    p.assets["a1"] = W.Asset(W.noise_int16(51, 9001))
-    p.load_sample("a0", "a0", "")
-    p.load_sample("a1", "a1", "normalize-seperate")
-    p.add_sampleloop("l0", 0.7, 30.0, "a0")     # read by the limiter itself (term kinds 1 / 3)
-    p.add_sampleloop("l1", 0.02, 0.0, "a1")
-    p.add_sum("stage", 0.5, -45.0)              # one input: a gain / pan stage, read through (term kind 4)
-    p.connect("l1", "stage")
-    LP.add_limiter(p, "m", "l0", case)
-    p.connect("stage", "m")
-    p.set_output("m")
-    built = p.build(gpu_api)
-    a = render_f32(gpu_api, built, "l0", p.cs)
-    b = render_f32(gpu_api, built, "stage", p.cs)
-    x = (np.float32(0.0) + a) + b               # sum_inputs (extensions.rs:310-319), f32, in connect() order
-    pw, xd, G, _ = twin(gpu_api, 48000, case, x)
-    assert G.min() < 0.7 and G.max() - G.min() > 0.2   # (the limiter works, and its gain moves)
-    for packed in (1, 0):
-        y = render_f32(gpu_api, built, "m", p.cs, packed_samples=packed)
-        close(y, xd, pw, "inlined terms, packed_samples %d" % packed)
+
+    def works_and_its_gain_moves(x):
+        G = twin(gpu_api, 48000, case, x)[2]
+        assert G.min() < 0.7 and G.max() - G.min() > 0.2
+    fx_rig.fed_by_an_inlined_loop_source_and_a_gain_stage(gpu_api, LIMITER, case, GP.gated_int16(3), vertex="m", check=works_and_its_gain_moves)
 
 
 def test_batch_members_are_bitwise_their_own_renders(gpu_api):
-    projects = []   # (`noise` has a source called m: the limiters are lm)
-    cases = [c for c, _ in LP.grid_cases(48000)]
-    for i in range(8):
-        p = LP.base_project(LP.INPUTS[i % 3], seconds=1.0, seed=i)
-        c = cases[(13 * i + 5) % len(cases)]
-        LP.add_limiter(p, "lm", "bus", c, wet=[1.0, 0.6][i % 2], gain=[1.0, 0.7][(i // 4) % 2])
-        if i % 4 == 1:     # a second one in series, as the output
-            LP.add_limiter(p, "lm2", "lm", cases[(29 * i + 1) % len(cases)])
-            p.set_output("lm2")
-        elif i % 4 == 2:   # in front of a Normalize output
-            p.add_normalize("out", 1.0, 0.0)
-            p.connect("lm", "out")
-            p.set_output("out")
-        else:
-            p.set_output("lm")
-        projects.append(p)
-    cs = projects[0].cs
-    own = []   # per project: its first and its second render (the second starts with the voices the first left sounding)
-    for p in projects:
-        sb, fb, g = p.build(gpu_api)
-        first = g.render_all(sb, fb, cs, 16, want_f32=False)[0]
-        g.reset_normalize_vertices()
-        fb.set_time(0)
-        g.set_time(0)
-        own.append((first, g.render_all(sb, fb, cs, 16, want_f32=False)[0]))
-    assert len({o[0].tobytes() for o in own}) == 8
-    batch = gpu_api.Batch()
-    for p in projects:
-        batch.add(*p.build(gpu_api))
-    for rep in range(2):
-        batch.rewind()
-        assert batch.render_all(cs, 16) == cs * 1024
-        for i in range(8):
-            assert np.array_equal(batch.read_pcm(i, cs), own[i][rep]), (rep, i)
+    # (`noise` has a source called m: the limiters are lm)
+    fx_rig.batch_members_are_bitwise_their_own_renders(gpu_api, LIMITER, LP.INPUTS, [c for c, _ in LP.grid_cases(48000)], vertex="lm")
 
 
 def test_projects_without_a_limiter_launch_no_limiter_kernel(gpu_api):
-    for p in (W.drum_project(seconds=1.0), W.config2(seconds=1.0, n_src=8)):
-        sb, fb, g = p.build(gpu_api)
-        g.set_profiling(1)
-        g.render_all(sb, fb, p.cs, 16, want_f32=False)
-        names = list(g.kernel_times())
-        assert names and not any(n.startswith("k_lim") for n in names), names
-    p = LP.base_project("drums")
-    LP.add_limiter(p, "m", "bus", CASE)
-    p.set_output("m")
-    sb, fb, g = p.build(gpu_api)
-    g.set_profiling(1)
-    g.render_all(sb, fb, p.cs, 16, want_f32=False)
-    assert [n for n in g.kernel_times() if n.startswith("k_lim")] == LIM_LAUNCHES
+    fx_rig.projects_without_the_kind_launch_no_kernel_of_it(gpu_api, "k_lim")
+    sb, fb, g = fx_rig.a_whole_render_launches_the_kinds_kernels(gpu_api, LIMITER, vertex="m")
     # a render of one tile (2 048 frames) is k_lim_apply alone, as every block pull is
     g.set_time(0)
     fb.set_time(0)
@@ -354,78 +222,21 @@ def test_projects_without_a_limiter_launch_no_limiter_kernel(gpu_api):
 
 # ---- the guard modes ----
 def _guard_project(limiter_first):
-    p = W.ProjectScript(48000, 1024)
-    p.set_length(1.0)
-    p.assets["a"] = W.Asset(W.noise_int16(7, 9000))
-    p.load_sample("a", "a", "")
-    p.event_files["f"] = np.array([(0.01, 60.0, 0.8), (0.4, 60.0, 0.0), (0.5, 64.0, 0.6), (0.9, 64.0, 0.0)], np.float32)
-    p.load_midi_floww("f", "f")
-    p.add_sampleloop("s", 0.5, 0.0, "a")
-    p.add_bandpass("b1", 1.0, 0.0, 1.0, 300.0, 5000.0, True)
-    p.add_bandpass("b2", 1.0, 10.0, 1.0, 200.0, 8000.0, True)
-    p.add_synth("y", 0.5, 0.0, "f", 0.4, 0.3, W.HIT_ADSR, 1.0, 0.8, W.NOTE_ADSR, 0.5, W.STD_ADSR)
-    p.add_sum("bus", 1.0, 0.0)
-    p.add_limiter("m", 1.0, 0.0, 1.0, -12.0, 5.0, 80.0, 6.0)
-    if limiter_first:   # loop -> limiter -> band-pass chain; the synth joins behind the limiter
-        p.connect("s", "m"); p.connect("m", "b1"); p.connect("b1", "b2"); p.connect("b2", "bus"); p.connect("y", "bus")
-        p.set_output("bus")
-    else:               # band-pass chain and synth -> bus -> limiter
-        p.connect("s", "b1"); p.connect("b1", "b2"); p.connect("b2", "bus"); p.connect("y", "bus"); p.connect("bus", "m")
-        p.set_output("m")
-    return p
-
-
-def _guard_renders(gpu_api, p):
-    outs, names = {}, {}
-    for mode, (bm, sm) in (("guard", (2, 2)), ("exact", (0, 1))):
-        sb, fb, g = p.build(gpu_api)
-        g.set_option("band_mode", bm)
-        g.set_option("sine_mode", sm)
-        g.set_profiling(1)
-        outs[mode] = g.render_all(sb, fb, p.cs, 16, want_pcm=False)[1]
-        names[mode] = list(g.kernel_times())
-    return outs, names
+    return fx_rig.gpu_guard_project("add_limiter", "m", (-12.0, 5.0, 80.0, 6.0), limiter_first)
 
 
 def test_guard_keeps_the_scan_and_fast_sines_downstream_of_a_limiter(gpu_api):
-    outs, names = _guard_renders(gpu_api, _guard_project(True))
-    rms = float(np.sqrt(np.mean((outs["guard"].astype(np.float64) - outs["exact"].astype(np.float64)) ** 2)))
-    print("guarded scan + fast sines downstream of a limiter: rms %.3g against the exact forms" % rms)
-    assert rms <= 1e-6 and np.abs(outs["exact"]).max() > 0.05
-    assert "k_band_scan" in names["guard"] and "k_sine_probe" in names["guard"], names["guard"]
-    assert not any(n in names["guard"] for n in ("k_band_pass", "k_band_spec")), names["guard"]
-    assert [n for n in names["guard"] if n.startswith("k_lim")] == LIM_LAUNCHES
+    fx_rig.guard_keeps_the_scan_and_fast_sines_downstream(gpu_api, _guard_project(True), "limiter", "k_lim", LIM_LAUNCHES)
 
 
 def test_guard_renders_the_exact_forms_upstream_of_a_limiter(gpu_api):
-    outs, names = _guard_renders(gpu_api, _guard_project(False))
-    assert np.array_equal(outs["guard"].view(np.uint32), outs["exact"].view(np.uint32)) and np.abs(outs["exact"]).max() > 0.05
-    assert "k_band_scan" not in names["guard"] and "k_sine_probe" not in names["guard"], names["guard"]
-    assert any(n in names["guard"] for n in ("k_band_pass", "k_band_spec")), names["guard"]
+    fx_rig.guard_renders_the_exact_forms_upstream(gpu_api, _guard_project(False))
 
 
 # ---- the front end ----
 def test_front_end_renders_a_limited_drum_bus(gpu_api, tmp_path):
-    p = W.limiter_project(seconds=1.0)
-    d = str(tmp_path / "proj")
-    _write_project(p, d)
-    out = str(tmp_path / "m.wav")
-    r = subprocess.run([sys.executable, "-m", "termdaw_amd", d, "-o", out], env=dict(os.environ, PYTHONPATH=ROOT), capture_output=True,
-                       text=True, timeout=600)
-    assert r.returncode == 0, r.stderr
-    st = gpu_api.State(open_dir=d)
-    assert st.refresh(), gpu_api.last_error()
-    assert 'add_limiter("lim",' in st.dump_calls()
-    mem = st.render_to_memory()
-    with wave.open(out, "rb") as w:
-        words = np.frombuffer(w.readframes(w.getnframes()), np.int16).reshape(-1, 2)
-    assert words.shape == mem.shape and np.array_equal(words, mem) and np.abs(mem).max() > 1000
+    mem = fx_rig.front_end_renders(gpu_api, tmp_path, W.limiter_project(seconds=1.0), 'add_limiter("lim",')
     # the ceiling holds on the words: -1 dB of full scale
     assert np.abs(mem.astype(np.int64)).max() <= int(10.0 ** (-1.0 / 20.0) * 32767.0) + 1
     # ... and the limiter is really in the path: with it dry the words differ
-    q = W.limiter_project(seconds=1.0, wet=0.0)
-    d2 = str(tmp_path / "plain")
-    _write_project(q, d2)
-    st2 = gpu_api.State(open_dir=d2)
-    assert st2.refresh()
-    assert not np.array_equal(st2.render_to_memory(), mem)
+    fx_rig.front_end_words_differ(gpu_api, tmp_path, W.limiter_project(seconds=1.0, wet=0.0), mem)

@@ -18,7 +18,8 @@ from termdaw_amd import workloads as W
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from test_gpu_loudness import reference  # noqa: E402
-from test_gpu_stems import _loops_project, _write_project  # noqa: E402
+from fx_rig import _write_project  # noqa: E402
+from test_gpu_stems import _loops_project  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -5,7 +5,7 @@ The input of the vertex under test always comes from the engine itself: renders 
 front, read as f32 -- the oracle-verified part of the graph is not restated here.
 
 Bounds.  wet = 1, gain = 1, angle = 0, per value:  |p' - p| <= 2^-23 |p| + E max|p| on the bands' sum p, carried through the
-definition's f32 lerp to the vertex' output (test_gpu_eq.assert_close says why it is not asserted on the output as it stands).
+definition's f32 lerp to the vertex' output (fx_rig.assert_close says why it is not asserted on the output as it stands).
 The first term is the one f32 rounding of p, which may flip; E covers the float64 re-association of the scans and the device's
 log10 / exp10: 8 x what the numpy emulation of the crossover's tiled scans shows over this file's own grid and inputs
 (tests/multiband_projects.py E, derived and re-checked on the CPU by tests/test_multiband_host.py; under the cap 2^-28).  With wet
@@ -15,9 +15,7 @@ Chunked renders and block pulls go against the twin and the bound: a chunk bound
 bitwise the whole render.  24 576 frames are 12 tiles, 4 096-frame chunks two tiles each, pulls of 1 024 and 64 the one-launch
 form; 9 blocks of 2 817 frames (25 353 = 24 576 + 777) end in a partial tile, whole and in every chunk."""
 import os
-import subprocess
 import sys
-import wave
 
 import numpy as np
 import pytest
@@ -25,16 +23,13 @@ import pytest
 from termdaw_amd import workloads as W
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import fx_rig  # noqa: E402
 import eq_projects as EP  # noqa: E402
 import multiband_projects as MP  # noqa: E402
 import np_multiband as NM  # noqa: E402
-from test_gpu_compressor import MIX  # noqa: E402
-from test_gpu_eq import REL, _pull_all, assert_close, build, mix_bound, render_f32  # noqa: E402
-from test_gpu_stems import _write_project  # noqa: E402
-from test_multiband_host import TONE_CASE, tone_lines  # noqa: E402
+from fx_rig import assert_close, build, MIX, mix_bound, _pull_all, REL, render_f32  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MB_LAUNCHES = ["k_mb_local", "k_mb_carry", "k_mb_detect", "k_mb_carry_y1", "k_mb_env", "k_mb_carry_yl", "k_mb_apply"]
 CASE = MP.case(200.0, 2000.0, MP.BAND_SETTINGS[0], 6.0, (5.0, 50.0))
 CASE_LOW = MP.case(40.0, 80.0, MP.BAND_SETTINGS[1], 0.0, (0.0, 1.0))          # the poles nearest z = 1, a hard low band, no attack
@@ -53,6 +48,11 @@ def twin(api, sr, case, x, state=None):
 
 def close(y, x, p, what):
     return assert_close(y, x, p, what, MP.E)
+
+
+MULTIBAND = fx_rig.FxKind("multiband", "k_mb", MB_LAUNCHES, MP.add_multiband, EP.base_project, CASE, CASE_LOW, MP.E,
+                          twin=lambda api, sr, case, x: (twin(api, sr, case, x)[0], x),
+                          mix=lambda api, sr, case, x, **kw: NM.process(x, MP.spec(api, sr, case), **kw)[0])
 
 
 # ---- the grid ----
@@ -135,19 +135,7 @@ def test_more_than_256_tiles(gpu_api):
 # ---- the mix ----
 @pytest.mark.parametrize("wet,gain,angle", MIX + [(1.0, 1.7, -75.0)])
 def test_wet_pan_and_gain(gpu_api, wet, gain, angle):
-    p = EP.base_project("drums")
-    MP.add_multiband(p, "v", "bus", CASE, wet=wet, gain=gain, angle=angle)
-    built = build(gpu_api, p)
-    x = render_f32(gpu_api, built, "bus", p.cs)
-    y = render_f32(gpu_api, built, "v", p.cs)
-    sp = MP.spec(gpu_api, 48000, CASE)
-    want, _ = NM.process(x, sp, wet=wet, gain=gain, angle=angle)
-    proc = NM.serial(x, sp)[0].astype(np.float32)
-    lim = mix_bound(x, proc, gain, angle)
-    err = np.abs(y.astype(np.float64) - want.astype(np.float64))
-    print("wet %g gain %g angle %g: worst error / bound %.3g" % (wet, gain, angle, float(np.max(err / lim))))
-    assert (err <= lim).all(), (float(np.max(err / lim)), np.argwhere(err > lim)[:4].tolist())
-    assert np.abs(want - x).max() > 1e-3 * wet   # (the vertex does something, in proportion to the mix)
+    fx_rig.wet_pan_and_gain(gpu_api, MULTIBAND, wet, gain, angle)
 
 
 def test_dry_is_a_sum_launch_and_leaves_the_line_alone(gpu_api):
@@ -192,12 +180,7 @@ def test_dry_is_a_sum_launch_and_leaves_the_line_alone(gpu_api):
 
 
 def test_projects_without_a_multiband_launch_no_multiband_kernel(gpu_api):
-    for p in (W.drum_project(seconds=1.0), W.config2(seconds=1.0, n_src=8)):
-        sb, fb, g = p.build(gpu_api)
-        g.set_profiling(1)
-        g.render_all(sb, fb, p.cs, 16, want_f32=False)
-        names = list(g.kernel_times())
-        assert names and not any(n.startswith("k_mb") for n in names), names
+    fx_rig.projects_without_the_kind_launch_no_kernel_of_it(gpu_api, "k_mb")
 
 
 # ---- non-vacuity ----
@@ -215,15 +198,15 @@ def test_only_the_high_band_works_on_a_two_tone_input(gpu_api):
     p.load_sample("t", "t", "")
     p.add_sampleloop("t", 0.5 * float(np.abs(tone).max()) / 32767.0, 0.0, "t")   # (a loaded sample is scaled to a peak of 1: back to 0.25 per tone, over two edges)
     p.add_sum("bus", 1.0, 0.0); p.connect("t", "bus"); p.connect("t", "bus")
-    MP.add_multiband(p, "v", "bus", TONE_CASE)
+    MP.add_multiband(p, "v", "bus", MP.TONE_CASE)
     p.set_output("v")
     built = build(gpu_api, p)
     x = render_f32(gpu_api, built, "bus", p.cs)
     y = render_f32(gpu_api, built, "v", p.cs)
     assert len(y) == 24576
-    lo_in, hi_in = tone_lines(x)
-    lo_out, hi_out = tone_lines(y)
-    lo_twin, hi_twin = tone_lines(twin(gpu_api, sr, TONE_CASE, x)[0])
+    lo_in, hi_in = MP.tone_lines(x)
+    lo_out, hi_out = MP.tone_lines(y)
+    lo_twin, hi_twin = MP.tone_lines(twin(gpu_api, sr, MP.TONE_CASE, x)[0])
     print("100 Hz line in at %.2f dB, moves %.3g dB; 8 kHz line moves %.3f dB (twin: %.3g, %.3f)" % (lo_in, lo_out - lo_in, hi_out - hi_in, lo_twin - lo_in, hi_twin - hi_in))
     assert abs(lo_in - 20.0 * np.log10(0.25)) < 0.05 and abs(hi_in - lo_in) < 0.05
     assert hi_out - hi_in <= -6.0 and abs(lo_out - lo_in) < 0.1
@@ -232,54 +215,15 @@ def test_only_the_high_band_works_on_a_two_tone_input(gpu_api):
 
 # ---- the guard modes ----
 def _guard_project(where):
-    p = W.ProjectScript(48000, 1024)
-    p.set_length(1.0)
-    p.assets["a"] = W.Asset(W.noise_int16(7, 9000))
-    p.load_sample("a", "a", "")
-    p.event_files["f"] = np.array([(0.01, 60.0, 0.8), (0.4, 60.0, 0.0), (0.5, 64.0, 0.6), (0.9, 64.0, 0.0)], np.float32)
-    p.load_midi_floww("f", "f")
-    p.add_sampleloop("s", 0.5, 0.0, "a")
-    p.add_bandpass("b1", 1.0, 0.0, 1.0, 300.0, 5000.0, True)
-    p.add_bandpass("b2", 1.0, 10.0, 1.0, 200.0, 8000.0, True)
-    p.add_synth("y", 0.5, 0.0, "f", 0.4, 0.3, W.HIT_ADSR, 1.0, 0.8, W.NOTE_ADSR, 0.5, W.STD_ADSR)
-    p.add_sum("bus", 1.0, 0.0)
-    p.add_multiband("v", 1.0, 0.0, 1.0, *CASE)
-    if where == "downstream":   # loop -> multiband -> band-pass chain; the synth joins behind the multiband
-        p.connect("s", "v"); p.connect("v", "b1"); p.connect("b1", "b2"); p.connect("b2", "bus"); p.connect("y", "bus")
-        p.set_output("bus")
-    else:                       # band-pass chain and synth -> bus -> multiband
-        p.connect("s", "b1"); p.connect("b1", "b2"); p.connect("b2", "bus"); p.connect("y", "bus"); p.connect("bus", "v")
-        p.set_output("v")
-    return p
-
-
-def _guard_renders(gpu_api, p):
-    outs, names = {}, {}
-    for mode, (bm, sm) in (("guard", (2, 2)), ("exact", (0, 1))):
-        sb, fb, g = p.build(gpu_api)
-        g.set_option("band_mode", bm)
-        g.set_option("sine_mode", sm)
-        g.set_profiling(1)
-        outs[mode] = g.render_all(sb, fb, p.cs, 16, want_pcm=False)[1]
-        names[mode] = list(g.kernel_times())
-    return outs, names
+    return fx_rig.gpu_guard_project("add_multiband", "v", CASE, where == "downstream")
 
 
 def test_guard_keeps_the_scan_and_fast_sines_downstream_of_a_multiband(gpu_api):
-    outs, names = _guard_renders(gpu_api, _guard_project("downstream"))
-    rms = float(np.sqrt(np.mean((outs["guard"].astype(np.float64) - outs["exact"].astype(np.float64)) ** 2)))
-    print("guarded scan + fast sines downstream of a multiband: rms %.3g against the exact forms" % rms)
-    assert rms <= 1e-6 and np.abs(outs["exact"]).max() > 0.05
-    assert "k_band_scan" in names["guard"] and "k_sine_probe" in names["guard"], names["guard"]
-    assert not any(n in names["guard"] for n in ("k_band_pass", "k_band_spec")), names["guard"]
-    assert [n for n in names["guard"] if n.startswith("k_mb")] == MB_LAUNCHES
+    fx_rig.guard_keeps_the_scan_and_fast_sines_downstream(gpu_api, _guard_project("downstream"), "multiband", "k_mb", MB_LAUNCHES)
 
 
 def test_guard_renders_the_exact_forms_upstream_of_a_multiband(gpu_api):
-    outs, names = _guard_renders(gpu_api, _guard_project("input"))
-    assert np.array_equal(_bits(outs["guard"]), _bits(outs["exact"])) and np.abs(outs["exact"]).max() > 1e-3
-    assert "k_band_scan" not in names["guard"] and "k_sine_probe" not in names["guard"], names["guard"]
-    assert any(n in names["guard"] for n in ("k_band_pass", "k_band_spec")), names["guard"]
+    fx_rig.guard_renders_the_exact_forms_upstream(gpu_api, _guard_project("input"), floor=1e-3)
 
 
 # ---- batches ----
@@ -300,49 +244,14 @@ def test_batch_members_are_bitwise_their_own_renders(gpu_api):
         else:
             p.set_output("mix")
         projects.append(p)
-    cs = projects[0].cs
-    own = []   # per project: its first and its second render (the second starts with the voices the first left sounding)
-    for p in projects:
-        sb, fb, g = p.build(gpu_api)
-        first = g.render_all(sb, fb, cs, 16, want_f32=False)[0]
-        g.reset_normalize_vertices()
-        fb.set_time(0)
-        g.set_time(0)
-        own.append((first, g.render_all(sb, fb, cs, 16, want_f32=False)[0]))
-    assert len({o[0].tobytes() for o in own}) == 8
-    batch = gpu_api.Batch()
-    for p in projects:
-        batch.add(*p.build(gpu_api))
-    for rep in range(2):
-        batch.rewind()
-        assert batch.render_all(cs, 16) == cs * 1024
-        for i in range(8):
-            assert np.array_equal(batch.read_pcm(i, cs), own[i][rep]), (rep, i)
+    fx_rig.batch_matches_own_renders(gpu_api, projects)
 
 
 # ---- the front end ----
 def test_front_end_renders_the_multiband_project(gpu_api, tmp_path):
-    p = W.multiband_project(seconds=1.0)
-    d = str(tmp_path / "proj")
-    _write_project(p, d)
-    out = str(tmp_path / "m.wav")
-    r = subprocess.run([sys.executable, "-m", "termdaw_amd", d, "-o", out], env=dict(os.environ, PYTHONPATH=ROOT), capture_output=True,
-                       text=True, timeout=600)
-    assert r.returncode == 0, r.stderr
-    st = gpu_api.State(open_dir=d)
-    assert st.refresh(), gpu_api.last_error()
-    assert 'add_multiband("mb",' in st.dump_calls()
-    mem = st.render_to_memory()
-    with wave.open(out, "rb") as w:
-        words = np.frombuffer(w.readframes(w.getnframes()), np.int16).reshape(-1, 2)
-    assert words.shape == mem.shape and np.array_equal(words, mem) and np.abs(mem).max() > 1000
+    mem = fx_rig.front_end_renders(gpu_api, tmp_path, W.multiband_project(seconds=1.0), 'add_multiband("mb",')
     # ... and the vertex is really in the path: dry, the same project is the plain bus
-    q = W.multiband_project(seconds=1.0, wet=0.0)
-    d2 = str(tmp_path / "plain")
-    _write_project(q, d2)
-    st2 = gpu_api.State(open_dir=d2)
-    assert st2.refresh()
-    assert not np.array_equal(st2.render_to_memory(), mem)
+    fx_rig.front_end_words_differ(gpu_api, tmp_path, W.multiband_project(seconds=1.0, wet=0.0), mem)
 
 
 # ---- random projects ----

@@ -6,8 +6,8 @@ the vertex in front, read as f32 -- the oracle-verified part of the graph is not
 
 Bounds.  "debug.reverb_form" 0, the serial form, re-associates nothing: at wet = 1, gain = 1, angle = 0 every finite f32 is
 BIT-EQUAL to the twin, whatever the window length and the chunking.  Form 1, the wave scan: |p' - p| <= 2^-23 |p| + E max|p| per
-value (tests/test_gpu_eq.py's assert_close), E = tests/reverb_projects.py's, derived on the CPU by tests/test_reverb_host.py; with
-damp 0 the scan adds only zeros and is bit-equal too.  With wet in (0, 1), pan and gain: test_gpu_eq.py's mix_bound.  PCM: within
+value (tests/fx_rig.py's assert_close), E = tests/reverb_projects.py's, derived on the CPU by tests/test_reverb_host.py; with
+damp 0 the scan adds only zeros and is bit-equal too.  With wet in (0, 1), pan and gain: fx_rig.py's mix_bound.  PCM: within
 one word of the twin's quantised value.  Every project is 0.5 s at the most."""
 import os
 import sys
@@ -20,7 +20,7 @@ from termdaw_amd import workloads as W
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import np_reverb as NR  # noqa: E402
 import reverb_projects as RP  # noqa: E402
-import test_gpu_eq as TG  # noqa: E402
+import fx_rig as TG  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 SR = 48000
@@ -330,21 +330,7 @@ def test_the_state_block_is_counted_and_goes_with_the_vertices(gpu_api):
 
 
 def _guard_project(bl=1024, seconds=0.5):
-    p = W.ProjectScript(48000, bl)
-    p.set_length(seconds)
-    p.assets["a"] = W.Asset(W.noise_int16(7, 9000))
-    p.load_sample("a", "a", "")
-    p.event_files["f"] = np.array([(0.01, 60.0, 0.8), (0.1, 60.0, 0.0), (0.12, 64.0, 0.6), (0.22, 64.0, 0.0)], np.float32)
-    p.load_midi_floww("f", "f")
-    p.add_sampleloop("s", 0.5, 0.0, "a")
-    p.add_bandpass("b1", 1.0, 0.0, 1.0, 300.0, 5000.0, True)
-    p.add_bandpass("b2", 1.0, 10.0, 1.0, 200.0, 8000.0, True)
-    p.add_synth("y", 0.5, 0.0, "f", 0.4, 0.3, W.HIT_ADSR, 1.0, 0.8, W.NOTE_ADSR, 0.5, W.STD_ADSR)
-    p.add_sum("bus", 1.0, 0.0)
-    p.add_reverb("r", 1.0, 0.0, 0.5, *HALL)
-    p.connect("s", "b1"); p.connect("b1", "b2"); p.connect("b2", "bus"); p.connect("y", "bus"); p.connect("bus", "r")
-    p.set_output("r")
-    return p
+    return TG.gpu_guard_project("add_reverb", "r", HALL, False, wet=0.5, bl=bl, seconds=seconds, notes=TG.SHORT_NOTES)
 
 
 def test_guard_keeps_the_scan_and_fast_sines_in_front_of_a_reverb(gpu_api):

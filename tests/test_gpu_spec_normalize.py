@@ -11,7 +11,7 @@ from test_gpu_parity import assert_bit_exact, assert_close
 pytestmark = pytest.mark.gpu
 
 
-def _families(g, render):
+def _profiled(g, render):
     g.set_profiling(1)
     out = render()
     names = set(g.kernel_times())
@@ -27,7 +27,7 @@ def test_scanned_render_takes_the_single_pass(gpu_api, oracle, spec, single):
     g.set_option("debug.spec_normalize", spec)
     g.set_option("debug.single_pass_normalize", single)
     fresh_two_pass = not (spec and single)
-    got, fam = _families(g, lambda: g.render_all(sb, fb, p.cs, 16))
+    got, fam = _profiled(g, lambda: g.render_all(sb, fb, p.cs, 16))
     # un-scanned: the running peak -- in ONE launch (k_norm1 / k_sum16w mode 5: the grid is resident at once, the tiles hand
     # their maxima over through granules) or, with that switched off, the two passes k_sum + k_scale
     assert ("k_scale" in fam) == fresh_two_pass and "k_norm_fix" not in fam
@@ -35,13 +35,13 @@ def test_scanned_render_takes_the_single_pass(gpu_api, oracle, spec, single):
     g.true_normalize_scan(sb, fb, p.cs)
     og.true_normalize_scan(osb, ofb, p.cs)
     for _ in range(2):
-        got, fam = _families(g, lambda: g.render_all(sb, fb, p.cs, 16))
+        got, fam = _profiled(g, lambda: g.render_all(sb, fb, p.cs, 16))
         assert ("k_norm_fix" in fam and "k_scale" not in fam) if spec else ("k_scale" in fam and "k_norm_fix" not in fam)
         assert_bit_exact(got, og.render_all(osb, ofb, p.cs, 16))
         assert g.get_normalization_value("sum") == og.get_normalization_value("sum")
     g.reset_normalize_vertices()                                   # back to the running-peak form
     og.reset_normalize_vertices()
-    got, fam = _families(g, lambda: g.render_all(sb, fb, p.cs, 16))
+    got, fam = _profiled(g, lambda: g.render_all(sb, fb, p.cs, 16))
     assert ("k_scale" in fam) == fresh_two_pass and "k_norm_fix" not in fam
     assert_bit_exact(got, og.render_all(osb, ofb, p.cs, 16))
 
@@ -72,7 +72,7 @@ def test_violated_speculation_falls_back_exactly(gpu_api, oracle, bl, bits, chun
     g.true_normalize_scan(sb, fb, 2)
     og.true_normalize_scan(osb, ofb, 2)
     for rep in range(3):   # the first render fails the speculation and raises the carried max; later ones mostly keep it
-        got, fam = _families(g, lambda: g.render_all(sb, fb, p.cs, bits))
+        got, fam = _profiled(g, lambda: g.render_all(sb, fb, p.cs, bits))
         assert "k_norm_fix" in fam and "k_scale" not in fam
         assert_bit_exact(got, og.render_all(osb, ofb, p.cs, bits))
         for name in ("inner", "out"):

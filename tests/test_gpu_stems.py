@@ -14,6 +14,7 @@ import pytest
 from termdaw_amd import workloads as W
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from fx_rig import _write_project  # noqa: E402
 from test_gpu_fuzz import random_project  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -212,14 +213,6 @@ def test_zero_stems_is_free(gpu_api):
     pb, _ = b[2].render_all(b[0], b[1], p.cs, 16)
     assert _launches(a[2]) == _launches(b[2])
     assert np.array_equal(pa, pb)
-
-
-def _write_project(p, d):
-    os.makedirs(d, exist_ok=True)
-    with open(os.path.join(d, "project.lua"), "w") as f:
-        f.write(p.to_lua(os.path.join(d, "assets")))
-    with open(os.path.join(d, "project.toml"), "w") as f:
-        f.write('[settings]\nmain = "project.lua"\nbuffer_length = %d\nproject_samplerate = %d\n' % (p.bl, p.psr))
 
 
 def test_front_end_writes_stem_files(gpu_api, tmp_path):

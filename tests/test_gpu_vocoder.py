@@ -5,7 +5,7 @@ The carrier and the key of the vertex under test always come from the engine its
 on the vertices in front, read as f32 -- the oracle-verified part of the graph is not restated here.
 
 Bounds.  wet = 1, gain = 1, angle = 0, per value:  |p' - p| <= 2^-23 |p| + E max|p| on the bank's output p, carried through the
-definition's f32 lerp to the vertex' output (test_gpu_eq.assert_close says why it is not asserted on the output as it stands).
+definition's f32 lerp to the vertex' output (fx_rig.assert_close says why it is not asserted on the output as it stands).
 The first term is the one f32 rounding of p, which may flip; E covers the float64 re-association of the scans: 8 x what the numpy
 emulation of the tiled scans shows over this file's own grid and inputs (tests/vocoder_projects.py E, derived and re-checked on
 the CPU by tests/test_vocoder_host.py; far under the cap 2^-28).  With wet in (0, 1), pan and gain: 4 x 2^-23 x max(|dry|, |p|) x
@@ -15,9 +15,7 @@ Chunked renders and block pulls go against the twin and the bound: a chunk bound
 bitwise the whole render.  24 576 frames are 12 tiles, 4 096-frame chunks two tiles each, pulls of 1 024 and 64 the one-launch
 form; 9 blocks of 2 817 frames (25 353 = 24 576 + 777) end in a partial tile, whole and in every chunk."""
 import os
-import subprocess
 import sys
-import wave
 
 import numpy as np
 import pytest
@@ -25,14 +23,12 @@ import pytest
 from termdaw_amd import workloads as W
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import fx_rig  # noqa: E402
 import np_vocoder as NV  # noqa: E402
 import vocoder_projects as VP  # noqa: E402
-from test_gpu_compressor import MIX, _quantise16  # noqa: E402
-from test_gpu_eq import REL, _pull_all, assert_close, mix_bound, render_f32  # noqa: E402
-from test_gpu_stems import _write_project  # noqa: E402
+from fx_rig import assert_close, MIX, mix_bound, _pull_all, _quantise16, REL, render_f32  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 VOC_LAUNCHES = ["k_voc_local", "k_voc_carry_z", "k_voc_env", "k_voc_carry_env", "k_voc_apply"]
 CASE = (8, 200.0, 4000.0, 4.0, 10.0, 12.0)   # bands, lo, hi, q, response_ms, out_db
 CASE16 = (16, 60.0, 12000.0, 8.0, 3.0, 18.0)
@@ -261,12 +257,7 @@ def test_dry_ignores_its_key_and_is_a_sum_launch(gpu_api):
 
 
 def test_projects_without_a_vocoder_launch_no_vocoder_kernel(gpu_api):
-    for p in (W.drum_project(seconds=1.0), W.config2(seconds=1.0, n_src=8)):
-        sb, fb, g = p.build(gpu_api)
-        g.set_profiling(1)
-        g.render_all(sb, fb, p.cs, 16, want_f32=False)
-        names = list(g.kernel_times())
-        assert names and not any(n.startswith("k_voc") for n in names), names
+    fx_rig.projects_without_the_kind_launch_no_kernel_of_it(gpu_api, "k_voc")
 
 
 # ---- key sources ----
@@ -367,34 +358,13 @@ def _guard_project(where):
     return p
 
 
-def _guard_renders(gpu_api, p):
-    outs, names = {}, {}
-    for mode, (bm, sm) in (("guard", (2, 2)), ("exact", (0, 1))):
-        sb, fb, g = p.build(gpu_api)
-        g.set_option("band_mode", bm)
-        g.set_option("sine_mode", sm)
-        g.set_profiling(1)
-        outs[mode] = g.render_all(sb, fb, p.cs, 16, want_pcm=False)[1]
-        names[mode] = list(g.kernel_times())
-    return outs, names
-
-
 def test_guard_keeps_the_scan_and_fast_sines_downstream_of_a_vocoder(gpu_api):
-    outs, names = _guard_renders(gpu_api, _guard_project("downstream"))
-    rms = float(np.sqrt(np.mean((outs["guard"].astype(np.float64) - outs["exact"].astype(np.float64)) ** 2)))
-    print("guarded scan + fast sines downstream of a vocoder: rms %.3g against the exact forms" % rms)
-    assert rms <= 1e-6 and np.abs(outs["exact"]).max() > 0.05
-    assert "k_band_scan" in names["guard"] and "k_sine_probe" in names["guard"], names["guard"]
-    assert not any(n in names["guard"] for n in ("k_band_pass", "k_band_spec")), names["guard"]
-    assert [n for n in names["guard"] if n.startswith("k_voc")] == VOC_LAUNCHES
+    fx_rig.guard_keeps_the_scan_and_fast_sines_downstream(gpu_api, _guard_project("downstream"), "vocoder", "k_voc", VOC_LAUNCHES)
 
 
 @pytest.mark.parametrize("where", ["input", "key"])
 def test_guard_renders_the_exact_forms_upstream_of_a_vocoder(gpu_api, where):
-    outs, names = _guard_renders(gpu_api, _guard_project(where))
-    assert np.array_equal(_bits(outs["guard"]), _bits(outs["exact"])) and np.abs(outs["exact"]).max() > 1e-3
-    assert "k_band_scan" not in names["guard"] and "k_sine_probe" not in names["guard"], names["guard"]
-    assert any(n in names["guard"] for n in ("k_band_pass", "k_band_spec")), names["guard"]
+    fx_rig.guard_renders_the_exact_forms_upstream(gpu_api, _guard_project(where), floor=1e-3)
 
 
 # ---- batches ----
@@ -415,49 +385,14 @@ def test_batch_members_are_bitwise_their_own_renders(gpu_api):
         else:
             p.set_output("mix")
         projects.append(p)
-    cs = projects[0].cs
-    own = []   # per project: its first and its second render (the second starts with the voices the first left sounding)
-    for p in projects:
-        sb, fb, g = p.build(gpu_api)
-        first = g.render_all(sb, fb, cs, 16, want_f32=False)[0]
-        g.reset_normalize_vertices()
-        fb.set_time(0)
-        g.set_time(0)
-        own.append((first, g.render_all(sb, fb, cs, 16, want_f32=False)[0]))
-    assert len({o[0].tobytes() for o in own}) == 8
-    batch = gpu_api.Batch()
-    for p in projects:
-        batch.add(*p.build(gpu_api))
-    for rep in range(2):
-        batch.rewind()
-        assert batch.render_all(cs, 16) == cs * 1024
-        for i in range(8):
-            assert np.array_equal(batch.read_pcm(i, cs), own[i][rep]), (rep, i)
+    fx_rig.batch_matches_own_renders(gpu_api, projects)
 
 
 # ---- the front end ----
 def test_front_end_renders_the_vocoder_project(gpu_api, tmp_path):
-    p = W.vocoder_project(seconds=1.0)
-    d = str(tmp_path / "proj")
-    _write_project(p, d)
-    out = str(tmp_path / "m.wav")
-    r = subprocess.run([sys.executable, "-m", "termdaw_amd", d, "-o", out], env=dict(os.environ, PYTHONPATH=ROOT), capture_output=True,
-                       text=True, timeout=600)
-    assert r.returncode == 0, r.stderr
-    st = gpu_api.State(open_dir=d)
-    assert st.refresh(), gpu_api.last_error()
-    assert 'add_vocoder("voc",' in st.dump_calls() and 'connect_key("drums","voc")' in st.dump_calls()
-    mem = st.render_to_memory()
-    with wave.open(out, "rb") as w:
-        words = np.frombuffer(w.readframes(w.getnframes()), np.int16).reshape(-1, 2)
-    assert words.shape == mem.shape and np.array_equal(words, mem) and np.abs(mem).max() > 1000
+    mem = fx_rig.front_end_renders(gpu_api, tmp_path, W.vocoder_project(seconds=1.0), 'add_vocoder("voc",', 'connect_key("drums","voc")')
     # ... and the key is really in the path: the chord sounds where the drums do -- dry, the same project is the plain chord
-    q = W.vocoder_project(seconds=1.0, wet=0.0)
-    d2 = str(tmp_path / "plain")
-    _write_project(q, d2)
-    st2 = gpu_api.State(open_dir=d2)
-    assert st2.refresh()
-    assert not np.array_equal(st2.render_to_memory(), mem)
+    fx_rig.front_end_words_differ(gpu_api, tmp_path, W.vocoder_project(seconds=1.0, wet=0.0), mem)
 
 
 # ---- random projects ----

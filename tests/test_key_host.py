@@ -6,7 +6,6 @@ tests/mock_key.cpp, whose mock launches check the key term tables, the class wor
 through); and the guard rule, read from the launch families the mock build reports."""
 import multiprocessing
 import os
-import shutil
 import subprocess
 import sys
 
@@ -17,15 +16,13 @@ from termdaw_amd import workloads as W
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import eq_projects as EP  # noqa: E402
+import fx_rig  # noqa: E402
 import gate_projects as GP  # noqa: E402
 import key_projects as KP  # noqa: E402
 import np_compressor as NC  # noqa: E402
 import np_gate as NG  # noqa: E402
 import np_key as NK  # noqa: E402
-import test_loudness_host as L  # noqa: E402
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "termdaw_amd", "csrc")
+from fx_rig import ENV, PARENT_LAUNCHES, _families  # noqa: E402
 GATE = (-30.0, 6.0, 10.0, 1.0, 100.0, -20.0)
 COMP = (-30.0, 4.0, 1.0, 20.0, 6.0, 0.0)
 
@@ -249,27 +246,9 @@ def test_random_key_projects_key_from_upstream_or_aside_only():
 
 
 # ---- the host engine under sanitizers: a stand-alone program ----
-def _build(out_dir):
-    flags = ["-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-ffp-contract=off",
-             "-D__HIP_PLATFORM_AMD__", "-I", "/opt/rocm/include", "-I", CSRC, "-I", os.path.join(ROOT, "include")]
-    jobs = [(os.path.join(CSRC, f), os.path.join(out_dir, f + ".o")) for f in L.SOURCES]
-    jobs += [(os.path.join(ROOT, "tests", f), os.path.join(out_dir, f + ".o")) for f in ("mock_hip.cpp", "mock_key.cpp", "asan_comp.cpp")]
-    procs = [subprocess.Popen(["g++"] + flags + ["-c", src, "-o", obj]) for src, obj in jobs]
-    for p in procs:
-        assert p.wait() == 0
-    exe = os.path.join(out_dir, "asan_key")
-    subprocess.check_call(["g++", "-fsanitize=address,undefined", "-o", exe] + [o for _, o in jobs] + ["-lpthread", "-ldl"])
-    return exe
-
-
 @pytest.fixture(scope="module")
 def asan_exe(tmp_path_factory):
-    if shutil.which("g++") is None or not os.path.exists("/opt/rocm/include/hip/hip_runtime_api.h"):
-        pytest.skip("needs g++ and the HIP headers")
-    return _build(str(tmp_path_factory.mktemp("asan_key")))
-
-
-ENV = dict(ASAN_OPTIONS="detect_leaks=0:allocator_may_return_null=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1", TD_ALLOC_CACHE_MB="0")
+    return fx_rig.asan_exe(tmp_path_factory, "asan_key", ["mock_key.cpp", "asan_comp.cpp"])
 
 
 def test_key_projects_under_sanitizers(asan_exe, tmp_path):
@@ -331,15 +310,7 @@ def _guard_project(shape):
 def test_guard_modes_keep_the_exact_forms_upstream_of_a_key(asan_exe, tmp_path):
     """band_mode 2 / sine_mode 2 (the driver's profiled render): the launch families each shape went through."""
     shapes = [k + "_" + w for k in ("gate", "comp") for w in ("wet", "dry", "plain")]
-    dirs = {name: EP.write_project(_guard_project(name), str(tmp_path / name)) for name in shapes}
-    r = subprocess.run([asan_exe] + list(dirs.values()), env=dict(os.environ, **ENV), capture_output=True, text=True, timeout=1800)
-    assert r.returncode == 0, (r.stdout[-800:], r.stderr[-4000:])
-    back = {d: name for name, d in dirs.items()}
-    fams = {}
-    for ln in r.stdout.splitlines():
-        if ln.startswith("launches "):
-            d, rest = ln[len("launches "):].split(":", 1)
-            fams[back[d]] = dict((kv.split("=")[0], int(kv.split("=")[1])) for kv in rest.split())
+    fams = _families(asan_exe, tmp_path, {name: _guard_project(name) for name in shapes})
     exact = ("k_band_pass", "k_band_spec")
     for kind in ("gate", "comp"):
         wet, dry, plain = fams[kind + "_wet"], fams[kind + "_dry"], fams[kind + "_plain"]
@@ -349,14 +320,6 @@ def test_guard_modes_keep_the_exact_forms_upstream_of_a_key(asan_exe, tmp_path):
         assert "k_band_scan" in plain and "k_sine_probe" in plain and not any(k in plain for k in exact), plain
         assert list(dry.items()) != [] and "k_band_scan" in dry and "k_sine_probe" in dry and not any(k in dry for k in exact), dry
         assert not any(k.startswith(("k_gate", "k_comp")) for k in dry), dry
-
-
-# (test_eq_host.py's record of the parent's lists)
-PARENT_LAUNCHES = {
-    "drums": "k_sample_multi=1 k_sum=1 k_band_scan=2 k_band_audit=1 k_sources=1",
-    "config2": "k_sum=1",
-    "config4": "k_band_scan=1 k_sources=1",
-}
 
 
 def test_projects_without_a_key_keep_their_launch_list(asan_exe, tmp_path):

@@ -6,7 +6,6 @@ launches check every descriptor -- and the guard rule and the launch lists, read
 import math
 import multiprocessing
 import os
-import shutil
 import subprocess
 import sys
 
@@ -16,14 +15,10 @@ import pytest
 from termdaw_amd import workloads as W
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import eq_projects as EP  # noqa: E402
+import fx_rig  # noqa: E402
 import limiter_projects as LP  # noqa: E402
 import np_limiter as NL  # noqa: E402
-import test_loudness_host as L  # noqa: E402
-from test_chorus_host import WRAPS  # noqa: E402
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "termdaw_amd", "csrc")
+from fx_rig import ENV, PARENT_LAUNCHES, _families  # noqa: E402
 
 GOOD = dict(ceiling_db=-1.0, lookahead_ms=5.0, release_ms=80.0, drive_db=6.0)
 RANGES = dict(ceiling_db=(-24.0, 0.0), lookahead_ms=(0.0, 50.0), release_ms=(1.0, 10000.0), drive_db=(-24.0, 24.0))
@@ -34,30 +29,17 @@ SR_ENDS = 40000   # (the range ends are taken at a rate where 50 ms is no more t
 
 
 def _args(**kw):
-    a = dict(GOOD)
-    a.update(kw)
-    return [float(a[k]) for k in ORDER]
+    return fx_rig._args(GOOD, ORDER, as_float=True, **kw)
 
 
 # ---- ranges, the Lua line, the project script ----
 @pytest.mark.parametrize("name,value", BAD)
 def test_out_of_range_parameters_are_rejected_by_name(api, name, value):
-    g = api.Graph(64, SR_ENDS)
-    with pytest.raises(api.TermdawError, match=name):
-        g.add_limiter("m", 1.0, 0.0, 1.0, *_args(**{name: value}))
-    with pytest.raises(api.TermdawError, match=name):
-        api.limiter_params(SR_ENDS, *_args(**{name: value}))
+    fx_rig.out_of_range_is_rejected_by_name(api, SR_ENDS, lambda g, *a: g.add_limiter("m", 1.0, 0.0, 1.0, *a), api.limiter_params, _args(**{name: value}), name)
 
 
 def test_range_ends_are_accepted(api):
-    g = api.Graph(64, SR_ENDS)
-    g.add_sum("in", 1.0, 0.0)
-    for i, end in enumerate((0, 1)):
-        g.add_limiter("m%d" % i, 1.0, 0.0, 1.0, *[RANGES[k][end] for k in ORDER])
-        assert g.connect("in", "m%d" % i)
-    g.add_limiter("wet", 1.0, 0.0, 7.0, *_args())   # (wet is clamped, not rejected: graph.rs:256)
-    g.add_limiter("dry", 1.0, 0.0, -3.0, *_args())
-    assert g.set_output("m1") and g.check_graph()
+    fx_rig.range_ends_are_accepted(api, SR_ENDS, lambda g, *a: g.add_limiter(*a), "m", RANGES, ORDER, _args())
     assert api.limiter_params(SR_ENDS, *[RANGES[k][1] for k in ORDER])[2] == 2000
 
 
@@ -79,15 +61,12 @@ def test_a_window_of_2048_frames_is_accepted_and_2049_rejected(api, sr):
 
 
 def _lua(line):
-    return 'add_sum("in", 1.0, 0.0);\n%s\nconnect("in", "g");\nset_output("g");\n' % line
+    return fx_rig._lua(line, "g")
 
 
 @pytest.mark.parametrize("name,value", [(k, v) for k, v in BAD if math.isfinite(v)])
 def test_lua_rejects_the_same_ranges(api, name, value):
-    s = api.State("", SR_ENDS, 64)
-    line = 'add_limiter("g", 1.0, 0.0, 1.0, %s);' % ", ".join(repr(float(v)) for v in _args(**{name: value}))
-    assert not s.refresh(_lua(line))
-    assert name in api.last_error(), api.last_error()
+    fx_rig.lua_rejects_the_same_ranges(api, SR_ENDS, "add_limiter", _args(**{name: value}), name)
 
 
 def test_lua_accepts_and_dumps_the_canonical_line(api):
@@ -282,28 +261,11 @@ def test_blocked_order_continues_from_a_carried_state(api):
 
 
 # ---- the host engine under sanitizers ----
-def _build(out_dir):
-    flags = ["-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-ffp-contract=off",
-             "-D__HIP_PLATFORM_AMD__", "-I", "/opt/rocm/include", "-I", CSRC, "-I", os.path.join(ROOT, "include")]
-    jobs = [(os.path.join(CSRC, f), os.path.join(out_dir, f + ".o")) for f in L.SOURCES]
-    jobs += [(os.path.join(ROOT, "tests", f), os.path.join(out_dir, f + ".o")) for f in ("mock_hip.cpp", "mock_guard.cpp", "mock_limiter.cpp", "asan_fx.cpp")]
-    procs = [subprocess.Popen(["g++"] + flags + ["-c", src, "-o", obj]) for src, obj in jobs]
-    for p in procs:
-        assert p.wait() == 0
-    exe = os.path.join(out_dir, "asan_limiter")
-    # (mock_guard.cpp listens to the guard's launches of mock_hip.cpp: ld --wrap)
-    subprocess.check_call(["g++", "-fsanitize=address,undefined", "-o", exe] + WRAPS + [o for _, o in jobs] + ["-lpthread", "-ldl"])
-    return exe
-
-
 @pytest.fixture(scope="module")
 def asan_exe(tmp_path_factory):
-    if shutil.which("g++") is None or not os.path.exists("/opt/rocm/include/hip/hip_runtime_api.h"):
-        pytest.skip("needs g++ and the HIP headers")
-    return _build(str(tmp_path_factory.mktemp("asan_limiter")))
+    return fx_rig.asan_exe(tmp_path_factory, "asan_limiter", ["mock_guard.cpp", "mock_limiter.cpp", "asan_fx.cpp"])
 
 
-ENV = dict(ASAN_OPTIONS="detect_leaks=0:allocator_may_return_null=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1", TD_ALLOC_CACHE_MB="0")
 LIM_LAUNCHES = ("k_lim_detect", "k_lim_carry", "k_lim_apply")
 
 
@@ -350,54 +312,7 @@ LIM = (-6.0, 5.0, 80.0, 12.0)
 
 
 def _guard_project(shape, seconds=0.5):
-    """The guard's shapes: `b` / `y` is what the guard would speed up (a band-pass under band_mode 2, a synth under sine_mode 2)."""
-    p = W.ProjectScript(48000, 1024)
-    p.set_length(seconds)
-    p.assets["a"] = W.Asset(W.noise_int16(7, 9000))
-    p.load_sample("a", "a", "")
-    p.event_files["f"] = np.array([(0.01, 60.0, 0.8), (0.2, 60.0, 0.0), (0.25, 62.0, 0.6)], np.float32)
-    p.load_midi_floww("f", "f")
-    lim = ("c", 1.0, 0.0, 0.0 if shape == "band_dry" else 1.0) + LIM
-    if shape == "band_up":       # loop -> band-pass -> limiter
-        p.add_sampleloop("s", 1.0, 0.0, "a")
-        p.add_bandpass("b", 1.0, 0.0, 1.0, 300.0, 5000.0, True)
-        p.add_limiter(*lim)
-        p.connect("s", "b"); p.connect("b", "c"); p.set_output("c")
-    elif shape == "band_down":   # loop -> limiter -> band-pass
-        p.add_sampleloop("s", 1.0, 0.0, "a")
-        p.add_limiter(*lim)
-        p.add_bandpass("b", 1.0, 0.0, 1.0, 300.0, 5000.0, True)
-        p.connect("s", "c"); p.connect("c", "b"); p.set_output("b")
-    elif shape in ("band_dry", "band_plain"):   # loop -> band-pass -> a dry limiter / a Sum in its place
-        p.add_sampleloop("s", 1.0, 0.0, "a")
-        p.add_bandpass("b", 1.0, 0.0, 1.0, 300.0, 5000.0, True)
-        if shape == "band_dry":
-            p.add_limiter(*lim)
-        else:
-            p.add_sum("c", 1.0, 0.0)
-        p.connect("s", "b"); p.connect("b", "c"); p.set_output("c")
-    elif shape in ("sine_up", "one_tile"):     # synth -> limiter (one_tile: a render of 2 048 frames)
-        p.add_synth("y", 1.0, 0.0, "f", 0.4, 0.3, W.HIT_ADSR, 1.0, 0.8, W.NOTE_ADSR, 0.5, W.STD_ADSR)
-        p.add_limiter(*lim)
-        p.connect("y", "c"); p.set_output("c")
-    else:                        # synth -> sum: the control
-        p.add_synth("y", 1.0, 0.0, "f", 0.4, 0.3, W.HIT_ADSR, 1.0, 0.8, W.NOTE_ADSR, 0.5, W.STD_ADSR)
-        p.add_sum("c", 1.0, 0.0)
-        p.connect("y", "c"); p.set_output("c")
-    return p
-
-
-def _families(asan_exe, tmp_path, projects):
-    dirs = {name: EP.write_project(p, str(tmp_path / name)) for name, p in projects.items()}
-    r = subprocess.run([asan_exe] + list(dirs.values()), env=dict(os.environ, **ENV), capture_output=True, text=True, timeout=1800)
-    assert r.returncode == 0, (r.stdout[-800:], r.stderr[-4000:])
-    back = {d: name for name, d in dirs.items()}
-    fams = {}
-    for ln in r.stdout.splitlines():
-        if ln.startswith("launches "):
-            d, rest = ln[len("launches "):].split(":", 1)
-            fams[back[d]] = dict((kv.split("=")[0], int(kv.split("=")[1])) for kv in rest.split())   # (dicts keep the driver's order)
-    return fams
+    return fx_rig.guard_project(shape, lambda p, name, dry: p.add_limiter(name, 1.0, 0.0, 0.0 if dry else 1.0, *LIM), seconds=seconds)
 
 
 def test_launch_families_and_the_guard_rule(asan_exe, tmp_path):
@@ -422,14 +337,6 @@ def test_launch_families_and_the_guard_rule(asan_exe, tmp_path):
     assert "k_sine_probe" in sfree and not any(k.startswith("k_lim") for k in sfree), sfree
     # a chunk of one tile is k_lim_apply alone
     assert [(k, v) for k, v in fams["one_tile"].items() if k.startswith("k_lim")] == [("k_lim_apply", 1)], fams["one_tile"]
-
-
-# (test_eq_host.py's record of the parent's lists)
-PARENT_LAUNCHES = {
-    "drums": "k_sample_multi=1 k_sum=1 k_band_scan=2 k_band_audit=1 k_sources=1",
-    "config2": "k_sum=1",
-    "config4": "k_band_scan=1 k_sources=1",
-}
 
 
 def test_projects_without_a_limiter_keep_their_launch_list(asan_exe, tmp_path):

@@ -13,8 +13,8 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "termdaw_amd", "csrc")
-SOURCES = ["engine.cpp", "compile.cpp", "devmem.cpp", "comm.cpp", "project.cpp", "lua_subset.cpp", "wav.cpp", "midi.cpp"]
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import fx_rig  # noqa: E402
 
 
 def kweight_numpy(fs):
@@ -115,27 +115,12 @@ def _write_projects(args):
     return out
 
 
-def _build(out_dir):
-    flags = ["-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-ffp-contract=off",
-             "-D__HIP_PLATFORM_AMD__", "-I", "/opt/rocm/include", "-I", CSRC, "-I", os.path.join(ROOT, "include")]
-    jobs = [(os.path.join(CSRC, f), os.path.join(out_dir, f + ".o")) for f in SOURCES]
-    jobs += [(os.path.join(ROOT, "tests", f), os.path.join(out_dir, f + ".o"))
-             for f in ("mock_hip.cpp", "mock_stems.cpp", "mock_loudness.cpp", "asan_loudness.cpp")]
-    procs = [subprocess.Popen(["g++"] + flags + ["-c", src, "-o", obj]) for src, obj in jobs]
-    for p in procs:
-        assert p.wait() == 0
-    exe = os.path.join(out_dir, "asan_loudness")
-    subprocess.check_call(["g++", "-fsanitize=address,undefined", "-o", exe] + [o for _, o in jobs] + ["-lpthread", "-ldl"])
-    return exe
-
-
 @pytest.mark.skipif(shutil.which("g++") is None or not os.path.exists("/opt/rocm/include/hip/hip_runtime_api.h"), reason="needs g++ and the HIP headers")
-def test_loudness_under_sanitizers(tmp_path):
-    exe = _build(str(tmp_path))
+def test_loudness_under_sanitizers(tmp_path, tmp_path_factory):
+    exe = fx_rig.asan_exe(tmp_path_factory, "asan_loudness", ["mock_stems.cpp", "mock_loudness.cpp", "asan_loudness.cpp"])
     n = int(os.environ.get("TD_ASAN_LOUD_SEEDS", "48"))
     workers = max(1, min(8, os.cpu_count() or 1))
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:allocator_may_return_null=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1",
-               TD_ALLOC_CACHE_MB="0")
+    env = dict(os.environ, **fx_rig.ENV)
     seeds = list(range(n))
     base = str(tmp_path / "p")
     with multiprocessing.Pool(workers) as pool:

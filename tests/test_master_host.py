@@ -11,10 +11,9 @@ import subprocess
 import numpy as np
 import pytest
 
+import fx_rig
 import test_loudness_host as L
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "termdaw_amd", "csrc")
 
 BAD = [(dict(target_lufs=-61.0), "target_lufs"), (dict(target_lufs=0.5), "target_lufs"), (dict(target_lufs=float("nan")), "target_lufs"),
        (dict(ceiling_dbtp=-31.0), "ceiling_dbtp"), (dict(ceiling_dbtp=0.1), "ceiling_dbtp"),
@@ -79,27 +78,12 @@ def test_device_mastering_fails_without_a_gpu(api):
         api.master_f32(np.zeros((48000, 2), np.float32), 48000, -14.0)
 
 
-def _build(out_dir):
-    flags = ["-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-ffp-contract=off",
-             "-D__HIP_PLATFORM_AMD__", "-I", "/opt/rocm/include", "-I", CSRC, "-I", os.path.join(ROOT, "include")]
-    jobs = [(os.path.join(CSRC, f), os.path.join(out_dir, f + ".o")) for f in L.SOURCES]
-    jobs += [(os.path.join(ROOT, "tests", f), os.path.join(out_dir, f + ".o"))
-             for f in ("mock_hip.cpp", "mock_stems.cpp", "mock_master.cpp", "asan_master.cpp")]
-    procs = [subprocess.Popen(["g++"] + flags + ["-c", src, "-o", obj]) for src, obj in jobs]
-    for p in procs:
-        assert p.wait() == 0
-    exe = os.path.join(out_dir, "asan_master")
-    subprocess.check_call(["g++", "-fsanitize=address,undefined", "-o", exe] + [o for _, o in jobs] + ["-lpthread", "-ldl"])
-    return exe
-
-
 @pytest.mark.skipif(shutil.which("g++") is None or not os.path.exists("/opt/rocm/include/hip/hip_runtime_api.h"), reason="needs g++ and the HIP headers")
-def test_master_under_sanitizers(tmp_path):
-    exe = _build(str(tmp_path))
+def test_master_under_sanitizers(tmp_path, tmp_path_factory):
+    exe = fx_rig.asan_exe(tmp_path_factory, "asan_master", ["mock_stems.cpp", "mock_master.cpp", "asan_master.cpp"])
     n = int(os.environ.get("TD_ASAN_MASTER_SEEDS", "32"))
     workers = max(1, min(8, os.cpu_count() or 1))
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:allocator_may_return_null=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1",
-               TD_ALLOC_CACHE_MB="0")
+    env = dict(os.environ, **fx_rig.ENV)
     seeds = list(range(n))
     base = str(tmp_path / "p")
     with multiprocessing.Pool(workers) as pool:

@@ -10,7 +10,6 @@ launch families the mock build reports."""
 import math
 import multiprocessing
 import os
-import shutil
 import subprocess
 import sys
 
@@ -20,15 +19,10 @@ import pytest
 from termdaw_amd import workloads as W
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import eq_projects as EP  # noqa: E402
+import fx_rig  # noqa: E402
 import multiband_projects as MP  # noqa: E402
 import np_multiband as NM  # noqa: E402
-import test_loudness_host as L  # noqa: E402
-from test_chorus_host import WRAPS  # noqa: E402
-from test_eq_host import oracle_input  # noqa: E402
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "termdaw_amd", "csrc")
+from fx_rig import ENV, PARENT_LAUNCHES, _families, oracle_input  # noqa: E402
 SR = 48000
 
 # add_multiband's arguments behind `wet`, flat, as the Lua line has them
@@ -138,7 +132,7 @@ def test_reset_clears_multibands(api):
 
 
 def _lua(line):
-    return 'add_sum("in", 1.0, 0.0);\n%s\nconnect("in", "g");\nset_output("g");\n' % line
+    return fx_rig._lua(line, "g")
 
 
 def _lit(v):
@@ -287,24 +281,13 @@ def tone_input(n=24576, sr=SR):
     return np.stack([v, v], axis=1)
 
 
-TONE_CASE = (400.0, 3000.0, (0.0, 0.0, -30.0), (1.0, 1.0, 4.0), 5.0, 50.0, 6.0, (0.0, 0.0, 0.0))
-
-
-def tone_lines(y, sr=SR):
-    """(100 Hz, 8 kHz): the two lines' amplitudes over the last 8 192 frames, in dB."""
-    seg = y[-8192:, 0].astype(np.float64)
-    t = np.arange(len(seg)) / sr
-    w = np.hanning(len(seg))
-    return tuple(20.0 * np.log10(2.0 * abs(np.sum(seg * w * np.exp(-2j * np.pi * f * t))) / w.sum()) for f in (100.0, 8000.0))
-
-
 def test_twin_only_the_high_band_works_on_a_two_tone_input(api):
     """Non-vacuity, measured from the spectrum: 0.25 sin 100 Hz + 0.25 sin 8 kHz through a 400 / 3 000 Hz crossover whose low and
     mid band sit at ratio 1 and whose high band compresses 4:1 above -30 dB -- the 8 kHz line falls, the 100 Hz line stays."""
     x = tone_input()
-    p, _ = NM.serial(x, MP.spec(api, SR, TONE_CASE))
-    lo_in, hi_in = tone_lines(x)
-    lo_out, hi_out = tone_lines(p.astype(np.float32))
+    p, _ = NM.serial(x, MP.spec(api, SR, MP.TONE_CASE))
+    lo_in, hi_in = MP.tone_lines(x)
+    lo_out, hi_out = MP.tone_lines(p.astype(np.float32))
     print("100 Hz line moves %.3g dB, 8 kHz line %.3f dB" % (lo_out - lo_in, hi_out - hi_in))
     assert hi_out - hi_in <= -6.0 and abs(lo_out - lo_in) < 0.1
 
@@ -379,28 +362,11 @@ def test_operator_has_the_23_blocks_and_steps_like_the_cascade(api):
 
 
 # ---- the host engine under sanitizers ----
-def _build(out_dir):
-    flags = ["-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-ffp-contract=off",
-             "-D__HIP_PLATFORM_AMD__", "-I", "/opt/rocm/include", "-I", CSRC, "-I", os.path.join(ROOT, "include")]
-    jobs = [(os.path.join(CSRC, f), os.path.join(out_dir, f + ".o")) for f in L.SOURCES]
-    jobs += [(os.path.join(ROOT, "tests", f), os.path.join(out_dir, f + ".o")) for f in ("mock_hip.cpp", "mock_guard.cpp", "mock_multiband.cpp", "asan_fx.cpp")]
-    procs = [subprocess.Popen(["g++"] + flags + ["-c", src, "-o", obj]) for src, obj in jobs]
-    for p in procs:
-        assert p.wait() == 0
-    exe = os.path.join(out_dir, "asan_multiband")
-    # (mock_guard.cpp listens to the guard's launches of mock_hip.cpp: ld --wrap)
-    subprocess.check_call(["g++", "-fsanitize=address,undefined", "-o", exe] + WRAPS + [o for _, o in jobs] + ["-lpthread", "-ldl"])
-    return exe
-
-
 @pytest.fixture(scope="module")
 def asan_exe(tmp_path_factory):
-    if shutil.which("g++") is None or not os.path.exists("/opt/rocm/include/hip/hip_runtime_api.h"):
-        pytest.skip("needs g++ and the HIP headers")
-    return _build(str(tmp_path_factory.mktemp("asan_multiband")))
+    return fx_rig.asan_exe(tmp_path_factory, "asan_multiband", ["mock_guard.cpp", "mock_multiband.cpp", "asan_fx.cpp"])
 
 
-ENV = dict(ASAN_OPTIONS="detect_leaks=0:allocator_may_return_null=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1", TD_ALLOC_CACHE_MB="0")
 MB_LAUNCHES = ("k_mb_local", "k_mb_carry", "k_mb_detect", "k_mb_carry_y1", "k_mb_env", "k_mb_carry_yl", "k_mb_apply")
 
 
@@ -490,19 +456,6 @@ def _guard_project(shape, seconds=0.5):
     return p
 
 
-def _families(asan_exe, tmp_path, projects):
-    dirs = {name: EP.write_project(p, str(tmp_path / name)) for name, p in projects.items()}
-    r = subprocess.run([asan_exe] + list(dirs.values()), env=dict(os.environ, **ENV), capture_output=True, text=True, timeout=1800)
-    assert r.returncode == 0, (r.stdout[-800:], r.stderr[-4000:])
-    back = {d: name for name, d in dirs.items()}
-    fams = {}
-    for ln in r.stdout.splitlines():
-        if ln.startswith("launches "):
-            d, rest = ln[len("launches "):].split(":", 1)
-            fams[back[d]] = dict((kv.split("=")[0], int(kv.split("=")[1])) for kv in rest.split())   # (dicts keep the driver's order)
-    return fams
-
-
 def test_guard_modes_keep_the_exact_forms_upstream_of_a_multiband(asan_exe, tmp_path):
     """band_mode 2 / sine_mode 2 (the driver's profiled render): the launch families each shape went through."""
     shapes = ("in_up", "in_dry", "in_plain", "down", "sine_up", "sine_free", "level")
@@ -527,14 +480,6 @@ def test_guard_modes_keep_the_exact_forms_upstream_of_a_multiband(asan_exe, tmp_
     # a chunk of one tile is k_mb_apply alone; three vertices in one level take each step once
     assert [(k, v) for k, v in fams["one_tile"].items() if k.startswith("k_mb")] == [("k_mb_apply", 1)], fams["one_tile"]
     assert [(k, v) for k, v in fams["level"].items() if k.startswith("k_mb")] == [(k, 1) for k in MB_LAUNCHES], fams["level"]
-
-
-# (test_eq_host.py's record of the parent's lists)
-PARENT_LAUNCHES = {
-    "drums": "k_sample_multi=1 k_sum=1 k_band_scan=2 k_band_audit=1 k_sources=1",
-    "config2": "k_sum=1",
-    "config4": "k_band_scan=1 k_sources=1",
-}
 
 
 def test_projects_without_a_multiband_keep_their_launch_list(asan_exe, tmp_path):

@@ -9,7 +9,6 @@ guard rule and the launch lists, read from the launch families the mock build re
 import math
 import multiprocessing
 import os
-import shutil
 import subprocess
 import sys
 
@@ -19,14 +18,10 @@ import pytest
 from termdaw_amd import workloads as W
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import eq_projects as EP  # noqa: E402
+import fx_rig  # noqa: E402
 import np_phaser as NP  # noqa: E402
 import phaser_projects as PP  # noqa: E402
-import test_loudness_host as L  # noqa: E402
-from test_eq_host import oracle_input  # noqa: E402
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "termdaw_amd", "csrc")
+from fx_rig import ENV, PARENT_LAUNCHES, _families, oracle_input  # noqa: E402
 SR = 48000
 
 GOOD = dict(stages=4, lo_hz=200.0, hi_hz=2000.0, rate_hz=1.0, feedback=0.5, stereo=0.25, shape=0)
@@ -50,19 +45,13 @@ BAD += [("lo_hz", 2000.5), ("hi_hz", 199.5)]   # lo_hz <= hi_hz: the message nam
 
 
 def _args(**kw):
-    a = dict(GOOD)
-    a.update(kw)
-    return [a[k] for k in ORDER]
+    return fx_rig._args(GOOD, ORDER, **kw)
 
 
 # ---- ranges, the Lua line, the project script ----
 @pytest.mark.parametrize("name,value", BAD)
 def test_out_of_range_parameters_are_rejected_by_name(api, name, value):
-    g = api.Graph(64, SR)
-    with pytest.raises(api.TermdawError, match=name):
-        g.add_phaser("p", 1.0, 0.0, 1.0, *_args(**{name: value}))
-    with pytest.raises(api.TermdawError, match=name):
-        api.phaser_params(SR, *_args(**{name: value}))
+    fx_rig.out_of_range_is_rejected_by_name(api, SR, lambda g, *a: g.add_phaser("p", 1.0, 0.0, 1.0, *a), api.phaser_params, _args(**{name: value}), name)
 
 
 def test_range_ends_are_accepted_and_follow_the_rate(api):
@@ -83,7 +72,7 @@ def test_range_ends_are_accepted_and_follow_the_rate(api):
 
 
 def _lua(line):
-    return 'add_sum("in", 1.0, 0.0);\n%s\nconnect("in", "g");\nset_output("g");\n' % line
+    return fx_rig._lua(line, "g")
 
 
 def _lit(v):
@@ -281,27 +270,11 @@ def test_blocked_scan_continues_from_a_carried_state(api):
 
 
 # ---- the host engine under sanitizers ----
-def _build(out_dir):
-    flags = ["-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-ffp-contract=off",
-             "-D__HIP_PLATFORM_AMD__", "-I", "/opt/rocm/include", "-I", CSRC, "-I", os.path.join(ROOT, "include")]
-    jobs = [(os.path.join(CSRC, f), os.path.join(out_dir, f + ".o")) for f in L.SOURCES]
-    jobs += [(os.path.join(ROOT, "tests", f), os.path.join(out_dir, f + ".o")) for f in ("mock_hip.cpp", "mock_phaser.cpp", "asan_comp.cpp")]
-    procs = [subprocess.Popen(["g++"] + flags + ["-c", src, "-o", obj]) for src, obj in jobs]
-    for p in procs:
-        assert p.wait() == 0
-    exe = os.path.join(out_dir, "asan_phaser")
-    subprocess.check_call(["g++", "-fsanitize=address,undefined", "-o", exe] + [o for _, o in jobs] + ["-lpthread", "-ldl"])
-    return exe
-
-
 @pytest.fixture(scope="module")
 def asan_exe(tmp_path_factory):
-    if shutil.which("g++") is None or not os.path.exists("/opt/rocm/include/hip/hip_runtime_api.h"):
-        pytest.skip("needs g++ and the HIP headers")
-    return _build(str(tmp_path_factory.mktemp("asan_phaser")))
+    return fx_rig.asan_exe(tmp_path_factory, "asan_phaser", ["mock_phaser.cpp", "asan_comp.cpp"])
 
 
-ENV = dict(ASAN_OPTIONS="detect_leaks=0:allocator_may_return_null=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1", TD_ALLOC_CACHE_MB="0")
 PHASER_LAUNCHES = ("k_phaser_local", "k_phaser_carry", "k_phaser_apply")
 
 
@@ -380,19 +353,6 @@ def _guard_project(shape, seconds=0.5):
     return p
 
 
-def _families(asan_exe, tmp_path, projects):
-    dirs = {name: EP.write_project(p, str(tmp_path / name)) for name, p in projects.items()}
-    r = subprocess.run([asan_exe] + list(dirs.values()), env=dict(os.environ, **ENV), capture_output=True, text=True, timeout=1800)
-    assert r.returncode == 0, (r.stdout[-800:], r.stderr[-4000:])
-    back = {d: name for name, d in dirs.items()}
-    fams = {}
-    for ln in r.stdout.splitlines():
-        if ln.startswith("launches "):
-            d, rest = ln[len("launches "):].split(":", 1)
-            fams[back[d]] = dict((kv.split("=")[0], int(kv.split("=")[1])) for kv in rest.split())   # (dicts keep the driver's order)
-    return fams
-
-
 def test_guard_modes_keep_the_exact_forms_upstream_of_a_phaser(asan_exe, tmp_path):
     """band_mode 2 / sine_mode 2 (the driver's profiled render): the launch families each shape went through."""
     shapes = ("band_up", "band_down", "band_both", "band_dry", "band_plain", "sine_up", "sine_free", "mixed")
@@ -418,14 +378,6 @@ def test_guard_modes_keep_the_exact_forms_upstream_of_a_phaser(asan_exe, tmp_pat
     # a chunk of one tile is k_phaser_apply alone; a level with two stage counts takes each step once per count
     assert [(k, v) for k, v in fams["one_tile"].items() if k.startswith("k_phaser")] == [("k_phaser_apply", 1)], fams["one_tile"]
     assert [(k, v) for k, v in fams["mixed"].items() if k.startswith("k_phaser")] == [(k, 2) for k in PHASER_LAUNCHES], fams["mixed"]
-
-
-# (test_eq_host.py's record of the parent's lists)
-PARENT_LAUNCHES = {
-    "drums": "k_sample_multi=1 k_sum=1 k_band_scan=2 k_band_audit=1 k_sources=1",
-    "config2": "k_sum=1",
-    "config4": "k_band_scan=1 k_sources=1",
-}
 
 
 def test_projects_without_a_phaser_keep_their_launch_list(asan_exe, tmp_path):

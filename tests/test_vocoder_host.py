@@ -10,7 +10,6 @@ families the mock build reports."""
 import math
 import multiprocessing
 import os
-import shutil
 import subprocess
 import sys
 
@@ -20,15 +19,10 @@ import pytest
 from termdaw_amd import workloads as W
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import eq_projects as EP  # noqa: E402
+import fx_rig  # noqa: E402
 import np_vocoder as NV  # noqa: E402
 import vocoder_projects as VP  # noqa: E402
-import test_loudness_host as L  # noqa: E402
-from test_chorus_host import WRAPS  # noqa: E402
-from test_eq_host import oracle_input  # noqa: E402
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "termdaw_amd", "csrc")
+from fx_rig import ENV, PARENT_LAUNCHES, _families, oracle_input  # noqa: E402
 SR = 48000
 
 GOOD = dict(bands=8, lo_hz=200.0, hi_hz=4000.0, q=4.0, response_ms=10.0, out_db=12.0)
@@ -52,19 +46,13 @@ BAD += [("lo_hz", 4000.0), ("lo_hz", 4000.5), ("hi_hz", 200.0), ("hi_hz", 199.5)
 
 
 def _args(**kw):
-    a = dict(GOOD)
-    a.update(kw)
-    return [a[k] for k in ORDER]
+    return fx_rig._args(GOOD, ORDER, **kw)
 
 
 # ---- ranges, key edges, the Lua line, the project script ----
 @pytest.mark.parametrize("name,value", BAD)
 def test_out_of_range_parameters_are_rejected_by_name(api, name, value):
-    g = api.Graph(64, SR)
-    with pytest.raises(api.TermdawError, match=name):
-        g.add_vocoder("v", 1.0, 0.0, 1.0, *_args(**{name: value}))
-    with pytest.raises(api.TermdawError, match=name):
-        api.vocoder_params(SR, *_args(**{name: value}))
+    fx_rig.out_of_range_is_rejected_by_name(api, SR, lambda g, *a: g.add_vocoder("v", 1.0, 0.0, 1.0, *a), api.vocoder_params, _args(**{name: value}), name)
 
 
 def test_range_ends_are_accepted_and_follow_the_rate(api):
@@ -134,7 +122,7 @@ def test_reset_clears_vocoders_and_their_key_edges(api):
 
 
 def _lua(line):
-    return 'add_sum("in", 1.0, 0.0);\nadd_sum("k", 1.0, 0.0);\n%s\nconnect("in", "g");\nconnect_key("k", "g");\nset_output("g");\n' % line
+    return fx_rig._lua(line, "g", key="k")
 
 
 def _lit(v):
@@ -346,28 +334,11 @@ def test_blocked_scan_continues_from_a_carried_state(api):
 
 
 # ---- the host engine under sanitizers ----
-def _build(out_dir):
-    flags = ["-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-ffp-contract=off",
-             "-D__HIP_PLATFORM_AMD__", "-I", "/opt/rocm/include", "-I", CSRC, "-I", os.path.join(ROOT, "include")]
-    jobs = [(os.path.join(CSRC, f), os.path.join(out_dir, f + ".o")) for f in L.SOURCES]
-    jobs += [(os.path.join(ROOT, "tests", f), os.path.join(out_dir, f + ".o")) for f in ("mock_hip.cpp", "mock_guard.cpp", "mock_vocoder.cpp", "asan_fx.cpp")]
-    procs = [subprocess.Popen(["g++"] + flags + ["-c", src, "-o", obj]) for src, obj in jobs]
-    for p in procs:
-        assert p.wait() == 0
-    exe = os.path.join(out_dir, "asan_vocoder")
-    # (mock_guard.cpp listens to the guard's launches of mock_hip.cpp: ld --wrap)
-    subprocess.check_call(["g++", "-fsanitize=address,undefined", "-o", exe] + WRAPS + [o for _, o in jobs] + ["-lpthread", "-ldl"])
-    return exe
-
-
 @pytest.fixture(scope="module")
 def asan_exe(tmp_path_factory):
-    if shutil.which("g++") is None or not os.path.exists("/opt/rocm/include/hip/hip_runtime_api.h"):
-        pytest.skip("needs g++ and the HIP headers")
-    return _build(str(tmp_path_factory.mktemp("asan_vocoder")))
+    return fx_rig.asan_exe(tmp_path_factory, "asan_vocoder", ["mock_guard.cpp", "mock_vocoder.cpp", "asan_fx.cpp"])
 
 
-ENV = dict(ASAN_OPTIONS="detect_leaks=0:allocator_may_return_null=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1", TD_ALLOC_CACHE_MB="0")
 VOC_LAUNCHES = ("k_voc_local", "k_voc_carry_z", "k_voc_env", "k_voc_carry_env", "k_voc_apply")
 
 
@@ -480,19 +451,6 @@ def _guard_project(shape, seconds=0.5):
     return p
 
 
-def _families(asan_exe, tmp_path, projects):
-    dirs = {name: EP.write_project(p, str(tmp_path / name)) for name, p in projects.items()}
-    r = subprocess.run([asan_exe] + list(dirs.values()), env=dict(os.environ, **ENV), capture_output=True, text=True, timeout=1800)
-    assert r.returncode == 0, (r.stdout[-800:], r.stderr[-4000:])
-    back = {d: name for name, d in dirs.items()}
-    fams = {}
-    for ln in r.stdout.splitlines():
-        if ln.startswith("launches "):
-            d, rest = ln[len("launches "):].split(":", 1)
-            fams[back[d]] = dict((kv.split("=")[0], int(kv.split("=")[1])) for kv in rest.split())   # (dicts keep the driver's order)
-    return fams
-
-
 def test_guard_modes_keep_the_exact_forms_upstream_of_a_vocoder(asan_exe, tmp_path):
     """band_mode 2 / sine_mode 2 (the driver's profiled render): the launch families each shape went through."""
     shapes = ("in_up", "in_dry", "in_plain", "key_up", "key_dry", "key_plain", "down", "sine_up", "sine_free", "mixed")
@@ -522,14 +480,6 @@ def test_guard_modes_keep_the_exact_forms_upstream_of_a_vocoder(asan_exe, tmp_pa
     # a chunk of one tile is k_voc_apply alone; a level with two band counts, keyed and not, takes each step once per group
     assert [(k, v) for k, v in fams["one_tile"].items() if k.startswith("k_voc")] == [("k_voc_apply", 1)], fams["one_tile"]
     assert [(k, v) for k, v in fams["mixed"].items() if k.startswith("k_voc")] == [(k, 4) for k in VOC_LAUNCHES], fams["mixed"]
-
-
-# (test_eq_host.py's record of the parent's lists)
-PARENT_LAUNCHES = {
-    "drums": "k_sample_multi=1 k_sum=1 k_band_scan=2 k_band_audit=1 k_sources=1",
-    "config2": "k_sum=1",
-    "config4": "k_band_scan=1 k_sources=1",
-}
 
 
 def test_projects_without_a_vocoder_keep_their_launch_list(asan_exe, tmp_path):

@@ -16,6 +16,7 @@ from termdaw_amd import workloads as W
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import eq_projects as EP  # noqa: E402
+import fx_rig  # noqa: E402
 import np_vocoder as NV  # noqa: E402
 
 RATES = EP.RATES
@@ -121,37 +122,17 @@ def random_vocoder_params(rng):
             float(rng.choice(QS)), float(rng.choice(RESPONSES)), float(rng.choice([-24.0, 0.0, 12.0, 48.0])))
 
 
+def _random_keys(rng, order, nm):
+    """Up to two keys from anywhere in the project."""
+    names = sorted({a[0] for fn, a in order if fn.startswith("add_")})
+    return [(str(rng.choice(names)), nm) for _ in range(int(rng.integers(0, 3)))]
+
+
 def random_vocoder_project(seed, allow_sinf=True):
-    import test_gpu_fuzz as F
-    p = F.random_project(seed, allow_sinf=allow_sinf)
-    rng = np.random.default_rng(1_010_000 + seed)
-    gains, angles = [1.0, 1.0005, 0.5, 1.7, -0.8], [0.0, 0.0009, 30.0, -75.0, 120.0]
-    edges = [i for i, (fn, a) in enumerate(p.script_order) if fn == "connect" and a[0] != a[1]]
-    picks = sorted(set(int(i) for i in rng.choice(edges, size=min(len(edges), int(rng.integers(1, 4))), replace=False)), reverse=True)
-    first_add = min(i for i, (fn, _) in enumerate(p.script_order) if fn.startswith("add_"))
-    names = sorted({a[0] for fn, a in p.script_order if fn.startswith("add_")})
-    vocs, keys = [], []
-    for k, i in enumerate(picks):   # (from the back: the indices in front stay valid)
-        a, b = p.script_order[i][1]
-        nm = "vo%d" % k
-        ci = p.calls["connect"].index((a, b))
-        p.calls["connect"][ci:ci + 1] = [(a, nm), (nm, b)]
-        p.script_order[i:i + 1] = [("connect", (a, nm)), ("connect", (nm, b))]
-        vocs.append((nm, float(rng.choice(gains)), float(rng.choice(angles))) + random_vocoder_params(rng))
-        # a key from anywhere in the project: an edge that would close a loop only warns (the front end goes on without it)
-        for _ in range(int(rng.integers(0, 3))):
-            keys.append((str(rng.choice(names)), nm))
-    for c in vocs:
-        p.calls["add_vocoder"].append(c)
-        p.script_order.insert(first_add, ("add_vocoder", c))
-    oi = max(i for i, (fn, _) in enumerate(p.script_order) if fn == "set_output")
-    for e in keys:
-        p.calls["connect_key"].append(e)
-        p.script_order.insert(oi, ("connect_key", e))
-    return p
+    return fx_rig.splice_project(seed, allow_sinf, rng_offset=1_010_000, prefix="vo", add_call="add_vocoder",
+                                 draw=lambda rng, p: random_vocoder_params(rng), as_output=False, draw_keys=_random_keys)
 
 
 def write_projects(args):
     """(base dir, seeds) -> the project dirs written: project.lua + assets, meta.txt (the block length)."""
-    base, seeds = args
-    return [EP.write_project(random_vocoder_project(seed), os.path.join(base, "s%d" % seed)) for seed in seeds]
+    return fx_rig.write_projects(random_vocoder_project, args)
