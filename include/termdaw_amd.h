@@ -336,7 +336,8 @@ int td_chorus_params(size_t sr, int voices, float delay_ms, float depth_ms, floa
  * shortest of the 24 lines must be at least 64 frames (at a low sample rate the error names size).  `wet` is clamped to [0, 1].
  * Under "band_mode" 2 / "sine_mode" 2 the estimate is carried through a reverb vertex at the gain (1 - wet) + wet Hrev, Hrev =
  * 0.03 x 8 / (1 - g) x (5/3)^4 an L2 bound of x -> p (DESIGN.md 3r has the proof): vertices upstream keep their scan / fast forms.
- * Not part of the vertex: pre-delay, a tail past the project's end, modulated lines, convolution. */
+ * Not part of the vertex: pre-delay, a tail past the project's end, modulated lines; convolution with a measured response is a
+ * vertex of its own (td_graph_add_convolution below). */
 int td_graph_add_reverb(td_graph* g, const char* name, float gain, float angle, float wet, float room, float damp, float width, float size);
 /* Host only, no GPU: the reverb vertex' constants at rate sr -- out[0 .. 4] = g, d1, d2, w1, w2; out[5] = Hrev; out[6] = B, the
  * frames per window of k_reverb at the default "debug.reverb_block"; out[7 .. 30] = the line lengths: left combs, right combs,
@@ -581,6 +582,47 @@ int td_graph_add_multiband(td_graph* g, const char* name, float gain, float angl
  * same range checks as td_graph_add_multiband. */
 int td_multiband_params(size_t sr, float lo_hz, float hi_hz, const float threshold_db[3], const float ratio[3], float attack_ms,
                         float release_ms, float knee_db, const float makeup_db[3], double* out, size_t n);
+/* A convolution vertex: an impulse response from the sample bank, applied by FFT -- THIS ENGINE'S OWN: no reference counterpart
+ * (the reference reaches it only through LV2, add_lv2fx).  A room or plate response, a speaker cabinet, a measured
+ * linear-phase filter: any WAV that td_samplebank_add / load_sample brought into the bank at the project's rate.  The vertex sums its
+ * inputs like every input vertex (sum_inputs, extensions.rs:310-319), processes the sum x = (l, r), mixes with `wet` by the
+ * reference's f32 lerp, then pan and gain like every vertex (extensions.rs:262-263).  It takes no key.
+ *   The response: h_c[k], c = left or right, is the bank's sample at `sample_index`, exactly the f32 frames td_samplebank_read returns.
+ *     Lh = sample_len if length_ms == 0, else min(sample_len, llround(length_ms sr / 1000)) frames of it are used; 1 <= Lh <= 262144:
+ *     a longer response is an error that names length_ms, raised where the bank is first seen -- by the render, by
+ *     td_convolution_params, and by a project script's refresh.
+ *   Pre-delay and trim, f64, from the f32 parameters widened (td_convolution_params returns exactly these):
+ *     D = llround(predelay_ms sr / 1000) frames;  g = 10^(out_db / 20).
+ *   norm = 1 divides g by sqrt(max_c sum_k h_c[k]^2), the sums in f64 over the Lh frames used, so that white noise leaves at the
+ *     RMS it came in at.  An all-zero response with norm = 1 is an error that names norm, raised by the render that first sees it.
+ *   The wet path, in f64 on the f32 summed input:  p_c[n] = (float)(g sum_{k < Lh} h_c[k] x_c[n - D - k]); x is 0 before the
+ *     restart time (time 0, or the last td_graph_set_time).  The left response acts on the left channel, the right on the right.  A
+ *     NaN or infinite input sample enters the sum as 0 (and passes to the output through the mix alone).
+ *   The mix, f32:  out = x + wet (p - x) (adsr.rs:42), then pan and gain.  The dry path is NOT delayed.
+ *   The engine forms the sum by uniform-partitioned overlap-save with f64 transforms in a fixed order, so a render is bitwise
+ *   reproducible; it differs from the direct sum by rounding alone (DESIGN.md 3z gives the bound), and a render cut into chunks or
+ *   block pulls from the same render in one piece by that rounding too.
+ *   wet < 0.0001: the summed input passes through untouched (a plain k_sum launch) and the state stays as it is.
+ * State: the last D + Lh - 1 summed input frames, zero at time 0; carried between consecutive block pulls and between the chunks
+ * of a render, restarted by td_graph_set_time / td_graph_change_time / td_graph_reset.  When the bank's sample behind the index is
+ * replaced by one of another length the vertex restarts from silence.
+ * Ranges, rejected with a td_last_error that names the parameter (NaN and the infinities included): length_ms [0, 60000];
+ * predelay_ms [0, 500]; out_db [-60, 24]; norm 0 or 1.  `wet` is clamped to [0, 1].
+ * Under "band_mode" 2 / "sine_mode" 2 everything upstream of a convolution vertex that is not dry takes the exact forms: its gain is
+ * the peak of the response's spectrum, which the host does not hold; vertices downstream are unaffected.  td_graph_connect_key
+ * refuses a convolution vertex.
+ * Not part of the vertex: a tail past the project's end; a true-stereo (four-channel) response; resampling of the response at
+ * render time (the bank holds it at the project's rate); a spectra ring that would spare block pulls the transforms of the
+ * carried frames (every pull transforms them again). */
+int td_graph_add_convolution(td_graph* g, const char* name, float gain, float angle, float wet, size_t sample_index, float length_ms,
+                             float predelay_ms, float out_db, int norm);
+/* Host only, no GPU: the convolution vertex' constants at rate sr for a sample of sample_len frames -- out[0 .. 5] = Lh, D, g
+ * (before norm), P = ceil((D + Lh) / B) partitions, the carried frames D + Lh - 1, B (the partition, 1024 frames).  The same range
+ * checks as td_graph_add_convolution, and the response's length. */
+int td_convolution_params(size_t sr, size_t sample_len, float length_ms, float predelay_ms, float out_db, int norm, double out[6]);
+/* Host only: the twiddle table of the engine's transforms, (cos, -sin)(2 pi j / 2048) for j = 0 .. 1023 as 2048 doubles, computed
+ * in long double -- the table the kernels read.  Returns 2048; writes only when cap >= 2048. */
+size_t td_convolution_twiddles(double* out, size_t cap);
 int td_graph_connect(td_graph* g, const char* a, const char* b);          /* graph.rs:80-96 (+58-78) */
 /* A key edge (sidechain) from any vertex `a` to a compressor, gate, vocoder or filter vertex `b` -- THIS ENGINE'S OWN, like the
  * vertices.  A vocoder vertex takes its MODULATOR from the key frames defined here (td_graph_add_vocoder above), a filter vertex

@@ -87,6 +87,9 @@ SIGNATURES = {
     "td_limiter_params": (_i32, [_sz, _f32, _f32, _f32, _f32, C.POINTER(C.c_double)]),
     "td_graph_add_multiband": (_i32, [_vp, _cp, _f32, _f32, _f32, _f32, _f32, C.POINTER(C.c_float), C.POINTER(C.c_float), _f32, _f32, _f32, C.POINTER(C.c_float)]),
     "td_multiband_params": (_i32, [_sz, _f32, _f32, C.POINTER(C.c_float), C.POINTER(C.c_float), _f32, _f32, _f32, C.POINTER(C.c_float), C.POINTER(C.c_double), _sz]),
+    "td_graph_add_convolution": (_i32, [_vp, _cp, _f32, _f32, _f32, _sz, _f32, _f32, _f32, _i32]),
+    "td_convolution_params": (_i32, [_sz, _sz, _f32, _f32, _f32, _i32, C.POINTER(C.c_double)]),
+    "td_convolution_twiddles": (_sz, [C.POINTER(C.c_double), _sz]),
     "td_gate_params": (_i32, [_sz, _f32, _f32, _f32, _f32, _f32, _f32, C.POINTER(C.c_double)]),
     "td_reverb_params": (_i32, [_sz, _f32, _f32, _f32, _f32, C.POINTER(C.c_double)]),
     "td_graph_connect": (_i32, [_vp, _cp, _cp]),
@@ -421,6 +424,25 @@ def limiter_params(sr, ceiling_db, lookahead_ms, release_ms, drive_db):
     return (out[0], out[1], int(out[2]), out[3], int(out[4]))
 
 
+def convolution_params(sr, sample_len, length_ms, predelay_ms, out_db, norm):
+    """(Lh, D, g, P, H, B): the convolution vertex' constants at rate sr for a response sample of sample_len frames, exactly as the
+    engine uses them (host only) -- the response's frames, the pre-delay in frames, the trim before `norm`, the partitions, the
+    frames the vertex carries (D + Lh - 1) and the partition length; all but g as ints."""
+    out = (C.c_double * 6)()
+    _check(lib().td_convolution_params(int(sr), int(sample_len), length_ms, predelay_ms, out_db, int(norm), out))
+    return (int(out[0]), int(out[1]), out[2], int(out[3]), int(out[4]), int(out[5]))
+
+
+def convolution_twiddles():
+    """The twiddle table of the engine's transforms (host only): exp(-2 pi i j / 2048), j = 0 .. 1023, as complex128 -- the doubles the
+    kernels read."""
+    n = int(lib().td_convolution_twiddles(None, 0))
+    out = (C.c_double * n)()
+    lib().td_convolution_twiddles(out, n)
+    a = np.frombuffer(out, dtype=np.float64).copy()
+    return a[0::2] + 1j * a[1::2]
+
+
 def chorus_params(sr, voices, delay_ms, depth_ms, rate_hz, stereo, shape):
     """The chorus vertex' constants at rate sr (host only), exactly as the engine uses them: (D0, A, f, H, s, Hch) -- the centre
     delay and the depth in frames, the LFO's cycles per frame, the frames of the line, the largest delay slope, and the gain the
@@ -686,6 +708,11 @@ class Graph:
         in include/termdaw_amd.h).  threshold_db, ratio and makeup_db: three values each, for the low, mid and high band."""
         _check(lib().td_graph_add_multiband(self.h, name.encode(), gain, angle, wet, lo_hz, hi_hz, _f3(threshold_db), _f3(ratio), attack_ms,
                                             release_ms, knee_db, _f3(makeup_db)))
+
+    def add_convolution(self, name, gain, angle, wet, sample_index, length_ms, predelay_ms, out_db, norm):
+        """A convolution vertex: the bank's sample at sample_index as an impulse response, by partitioned FFT (this engine's own; the
+        definition is in include/termdaw_amd.h)."""
+        _check(lib().td_graph_add_convolution(self.h, name.encode(), gain, angle, wet, int(sample_index), length_ms, predelay_ms, out_db, int(norm)))
 
     def connect(self, a, b):
         return bool(lib().td_graph_connect(self.h, a.encode(), b.encode()))

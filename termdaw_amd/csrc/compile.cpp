@@ -3,7 +3,7 @@
 // this file calls the HIP runtime: device memory reaches it as addresses handed out by three functions of engine.cpp
 // (compile.h: take_buffer / ensure_buffers for edge buffers, upload_tables for a vertex' event tables), everything it
 // writes goes into the plain-memory staging arena of the ChunkBuild (offsets + fix-up lists that submit_chunk patches once
-// the device addresses are known).  The effect kinds (compressor .. multiband) are lowered by compile_fx.cpp, through the table there;
+// the device addresses are known).  The effect kinds (compressor .. convolution) are lowered by compile_fx.cpp, through the table there;
 // that file is included at the end of this one (see there).  tests/test_compile_asan.py builds it with g++
 // -fsanitize=address,undefined.
 #include "compile.h"
@@ -35,7 +35,8 @@ const char* const kFamilyName[F_COUNT] = {"k_sample_loop", "k_sample_multi", "k_
                                            "k_voc_local", "k_voc_carry_z", "k_voc_env", "k_voc_carry_env", "k_voc_apply",
                                            "k_filt_detect", "k_filt_carry_y1", "k_filt_env", "k_filt_carry_e", "k_filt_local", "k_filt_carry", "k_filt_apply",
                                            "k_lim_detect", "k_lim_carry", "k_lim_apply",
-                                           "k_mb_local", "k_mb_carry", "k_mb_detect", "k_mb_carry_y1", "k_mb_env", "k_mb_carry_yl", "k_mb_apply"};
+                                           "k_mb_local", "k_mb_carry", "k_mb_detect", "k_mb_carry_y1", "k_mb_env", "k_mb_carry_yl", "k_mb_apply",
+                                           "k_conv_ir", "k_conv_fwd", "k_conv_mac", "k_conv_inv"};
 
 
 // ------------------------------------------------------------------------------------------------
@@ -1604,7 +1605,7 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
             // kind's first family -- or, for the saturator, F_SAT1 as well (R = 1), so that one kind may be lowered at two families of
             // its row, each with its own vertices; lower_sat tells them apart by FxLevel::fam
             if (const FxKind* fx = fx_of_family(fam)) {
-                FxLevel fl{g, cb, M, sr, bl, t0, lv, is_scan, fam, ins_off, term_mode, key_off, key_mode, level_tmp};
+                FxLevel fl{g, cb, M, sr, bl, t0, lv, is_scan, fam, ins_off, term_mode, key_off, key_mode, level_tmp, sb};
                 if (!fx->lower(fl, vs)) return 0;
                 continue;
             }

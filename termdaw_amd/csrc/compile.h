@@ -26,6 +26,7 @@ enum Family { F_LOOP, F_MULTI, F_LERP, F_SINE, F_SYNTH, F_SAMPSYN, F_ENV, F_PROB
               F_FILT_DETECT, F_FILT_CARRY1, F_FILT_ENV, F_FILT_CARRY2, F_FILT_LOCAL, F_FILT_CARRY, F_FILT_APPLY /* a level's filter vertices: k_filt_detect, k_master_carry (y1), k_filt_env, k_master_carry (e) -- these four over the vertices whose follower runs -- k_filt_local, k_filt_carry, all six over multi-tile chunks only, k_filt_apply -- in this order */,
               F_LIM_DETECT, F_LIM_CARRY, F_LIM_APPLY /* a level's limiter vertices: k_lim_detect, k_master_carry (the u entering each tile), both over multi-tile chunks only, k_lim_apply -- in this order */,
               F_MB_LOCAL, F_MB_CARRY, F_MB_DETECT, F_MB_CARRY1, F_MB_ENV, F_MB_CARRY2, F_MB_APPLY /* a level's multiband vertices: k_mb_local, k_mb_carry (the crossover's states entering each tile), k_mb_detect, k_master_carry (y1 of the three bands), k_comp_env (over the bands), k_master_carry (yL), all six over multi-tile chunks only, k_mb_apply -- in this order */,
+              F_CONV_IR, F_CONV_FWD, F_CONV_MAC, F_CONV_INV /* a level's convolution vertices: k_conv_ir (over the vertices whose spectra have to be built only), k_conv_fwd, k_conv_mac, k_conv_inv -- in this order */,
               F_COUNT };
 extern const char* const kFamilyName[F_COUNT];
 
@@ -42,7 +43,7 @@ bool is_delay_family(int fam);
 double ms_between(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b);
 tdk::PanGain make_pg(float gain, float angle);           // a vertex' pan / gain as its kernel's epilogue applies it (sample.rs:98-109)
 
-// ---- compile_fx.cpp: the effect kinds (compressor, EQ, delay, saturator, chorus, reverb, gate, phaser, vocoder, filter, limiter, multiband) ----
+// ---- compile_fx.cpp: the effect kinds (compressor, EQ, delay, saturator, chorus, reverb, gate, phaser, vocoder, filter, limiter, multiband, convolution) ----
 // What lowering the vertices of one effect kind at one level needs of compile_chunk, and the steps every kind's lowering
 // shares.  The kinds' own functions (lower_comp ..) keep what is theirs: coefficients, tiling, scratch, launches.
 struct FxLevel {
@@ -58,6 +59,7 @@ struct FxLevel {
     std::map<size_t, size_t>& key_off;        // keyed compressor / gate / vocoder / filter vertex that reads its key (Vertex::reads_key) -> staging offset of its key terms
     std::map<size_t, uint32_t>& key_mode;     // ... -> TERMS_* of those
     std::vector<float2*>& level_tmp;          // scratch edge buffers, given back behind the level
+    const td_samplebank* sb;                  // the bank of the render (a convolution vertex' response)
 
     float2* tmp_buffer();   // an edge buffer for this level only; nullptr: failed (g_error set)
     // the fields every effect descriptor has, under the same names
@@ -137,5 +139,9 @@ int upload_tables(td_graph* g, TableCache& tc, const Staging& tmp);   // a verte
 int ensure_buffers(td_graph* g, size_t frames);                      // the edge-buffer pool holds buffers of >= frames frames; all of them free
 void* take_line(td_graph* g, tde::Vertex& v, size_t bytes);   // the block a delay, saturator, chorus, reverb, vocoder, limiter or multiband vertex carries (Vertex::line), allocated on first use (nullptr: out of device memory)
 float2* take_buffer(td_graph* g);                                    // one edge buffer (nullptr: out of device memory)
+// a convolution vertex' spectra block of `bytes`, for the sample at `src` of `src_len` frames; *build: the block is new or was
+// built from another sample, k_conv_ir has to run (nullptr: out of device memory).  A line of another size than line_bytes goes.
+void* take_spectra(td_graph* g, tde::Vertex& v, size_t bytes, const void* src, size_t src_len, size_t line_bytes, bool* build);
+const double* take_twiddles(td_graph* g);                            // the transforms' twiddle table on the graph's device, uploaded once per process and device (nullptr: failed)
 
 }  // namespace tde

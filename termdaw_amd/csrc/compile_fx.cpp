@@ -1,5 +1,5 @@
 // compile_fx.cpp -- the effect kinds of the host compiler (compile.h FxKind / FxLevel): compressor, EQ, delay, saturator,
-// chorus, reverb, gate, phaser, vocoder, filter, limiter, multiband.  One table row per kind -- its chunk limit, the family its launches start at, the factor the guard
+// chorus, reverb, gate, phaser, vocoder, filter, limiter, multiband, convolution.  One table row per kind -- its chunk limit, the family its launches start at, the factor the guard
 // carries an estimate through it at, the state slots it carries and their state at time 0, whether it takes a key, whether its
 // kernels are linked -- one function per kind that lowers a level's vertices of that kind to descriptors and launches, and right
 // behind it the one that decodes such a launch and calls the kernels' entry points (kernels.h launch_*: the only calls out of the
@@ -7,6 +7,7 @@
 // only.  Not an object of its own: compile.cpp includes this file at its end, so no build list changes with it.
 #include "chorus_math.h"
 #include "compile.h"
+#include "conv_math.h"
 #include "delay_math.h"
 #include "eq_math.h"
 #include "filter_math.h"
@@ -35,7 +36,7 @@ float2* FxLevel::tmp_buffer() {
 
 namespace fxk {   // (compile.cpp includes this file: what is only used here keeps a scope of its own)
 
-// A delay, saturator, chorus, reverb, vocoder, limiter or multiband vertex enters a chunk of M frames: a set_time since the vertex last ran is consumed here
+// A delay, saturator, chorus, reverb, vocoder, limiter, multiband or convolution vertex enters a chunk of M frames: a set_time since the vertex last ran is consumed here
 // (the block restarts from zero, like an EQ's state), the books move on behind the chunk -- `alternates`: the launch writes the other
 // half of the line, which the next one reads.  Returns the frames run up to the chunk (Vertex::Line::total as the chunk finds it).
 static uint64_t enter_chunk(Vertex& v, size_t M, bool alternates) {
@@ -941,6 +942,71 @@ static void launch_multiband(const Launch& L, const void* d, hipStream_t s) {
     }
 }
 
+// ---- convolution: three launches, four when spectra have to be built (kernels.h ConvDesc) ----
+static int lower_convolution(FxLevel& L, std::vector<size_t>& vs) {
+    td_graph* g = L.g;
+    const uint32_t n_tiles = (uint32_t)((L.M + kConvB - 1) / kConvB);
+    static_assert(kConvB == (uint32_t)conv::kB && kConvN == (uint32_t)conv::kN, "the partition: one size on both sides");
+    std::vector<ConvDesc> d, ir;
+    uint32_t g_ir = 0, g_fwd = 0, g_inv = 0;
+    for (size_t vi : vs) {
+        Vertex& v = g->vertices[vi];
+        if (!L.sb || v.sample_index >= L.sb->samples.size()) return fail("convolution: sample index out of range");
+        const SampleEntry& smp = L.sb->samples[v.sample_index];
+        if (const char* why = conv::check_len(L.sr, smp.len, v.conv_length_ms)) return fail(std::string("convolution: ") + why);
+        double c[conv::kParams];
+        conv::params(L.sr, smp.len, v.conv_length_ms, v.conv_predelay_ms, v.conv_out_db, c);
+        ConvDesc x{};
+        if (!(x.x = L.tmp_buffer())) return 0;
+        L.head(x, vi);
+        x.Lh = (uint32_t)c[0];
+        x.D = (uint32_t)c[1];
+        x.g = c[2];
+        x.P = (uint32_t)c[3];
+        x.hist = (uint32_t)c[4];
+        x.n_tiles = n_tiles;
+        x.norm = (uint32_t)v.conv_norm;
+        x.ir = smp.d;
+        if (!(x.tw = take_twiddles(g))) return fail("termdaw_amd: out of device memory for the convolution vertices' twiddle table");
+        const size_t line_bytes = std::max<size_t>(16, 2 * (size_t)x.hist * sizeof(float2));
+        bool build = false;
+        x.spec = (double*)take_spectra(g, v, (kConvHead + (size_t)x.P * kConvBins * 4u) * sizeof(double), smp.d, smp.len, line_bytes, &build);
+        if (!x.spec) return fail("termdaw_amd: out of device memory for a convolution vertex' spectra");
+        x.line = (float2*)take_line(g, v, line_bytes);
+        if (!x.line) return fail("termdaw_amd: out of device memory for a convolution vertex' line");
+        x.parity = v.line.parity;
+        x.fresh = enter_chunk(v, L.M, true) ? 0u : 1u;   // (afresh: the frames in front of the chunk are 0, the half is not read)
+        x.hist_groups = std::min<uint32_t>(kConvHistGroups, (x.hist + kConvHistFrames - 1u) / kConvHistFrames);
+        g_fwd = std::max(g_fwd, n_tiles + x.P - 1u);
+        g_inv = std::max(g_inv, n_tiles + x.hist_groups);
+        if (build) {
+            ir.push_back(x);
+            g_ir = std::max(g_ir, x.P);
+            if (x.norm) g->conv_checks.push_back(vi);
+        }
+        d.push_back(x);
+    }
+    const size_t off = L.put(d, vs);
+    for (size_t i = 0; i < vs.size(); ++i) {
+        const size_t o = off + i * sizeof(ConvDesc), wb = (size_t)kConvN * 2u * sizeof(double);
+        L.cb.scratch_field(o, offsetof(ConvDesc, xs), L.cb.scratch((size_t)(n_tiles + d[i].P - 1u) * wb));
+        L.cb.scratch_field(o, offsetof(ConvDesc, ys), L.cb.scratch((size_t)n_tiles * wb));
+    }
+    if (!ir.empty()) L.add_launch(F_CONV_IR, L.cb.st->put(ir), (int)ir.size(), g_ir);
+    L.add_launch(F_CONV_FWD, off, (int)vs.size(), g_fwd);
+    L.add_launch(F_CONV_MAC, off, (int)vs.size(), ((n_tiles + kConvTT - 1u) / kConvTT) * kConvMacGroups);
+    L.add_launch(F_CONV_INV, off, (int)vs.size(), g_inv);
+    return 1;
+}
+static void launch_convolution(const Launch& L, const void* d, hipStream_t s) {
+    switch (L.fam) {
+        case F_CONV_IR: launch_conv_ir((const ConvDesc*)d, L.n, L.aux, s); break;
+        case F_CONV_FWD: launch_conv_fwd((const ConvDesc*)d, L.n, L.aux, s); break;
+        case F_CONV_MAC: launch_conv_mac((const ConvDesc*)d, L.n, L.aux, s); break;
+        case F_CONV_INV: launch_conv_inv((const ConvDesc*)d, L.n, L.aux, s); break;
+    }
+}
+
 // ---- the table ----
 // fits: the largest chunk the kind's kernels index (32-bit frames; the line kinds keep room for their look-back, the tiled
 // ones for the tile count packed into a launch's aux)
@@ -952,6 +1018,9 @@ static bool fits_chorus(const td_graph* g, const Vertex&, size_t M) { return M <
 static bool fits_voc(const td_graph*, const Vertex&, size_t M) { return M <= 0xFFFF0000ull && (M + kVocTile - 1) / kVocTile < 0x1000000ull; }
 
 static bool fits_mb(const td_graph*, const Vertex&, size_t M) { return M <= 0xFFFF0000ull && (M + kMbTile - 1) / kMbTile < 0x1000000ull; }
+
+// the windows of a chunk and the partitions in front of them stay a 32-bit grid, the frames a 32-bit index
+static bool fits_conv(const td_graph*, const Vertex&, size_t M) { return M <= 0xF0000000ull; }
 
 static int family_sat(const Vertex& v) { return v.sat_oversample == 1 ? F_SAT1 : F_SAT_SUM; }
 
@@ -974,6 +1043,9 @@ static double through_filter(const Vertex& v, size_t) { return dry(v) ? 1.0 : kN
 static double through_limiter(const Vertex& v, size_t) { return dry(v) ? 1.0 : kNoStaticGain; }
 // a multiband's three gains follow the bands' levels: no static gain -- the compressor's case, unless it is dry
 static double through_multiband(const Vertex& v, size_t) { return dry(v) ? 1.0 : kNoStaticGain; }
+// a convolution is linear and time-invariant, but its L2 gain is the peak of the response's spectrum, which lives in the bank
+// on the device: no static gain is carried through it unless it is dry
+static double through_convolution(const Vertex& v, size_t) { return dry(v) ? 1.0 : kNoStaticGain; }
 // an EQ is linear and time-invariant: Hmax of its biquad
 static double through_eq(const Vertex& v, size_t sr) {
     if (dry(v)) return 1.0;
@@ -1014,10 +1086,10 @@ static_assert(sizeof(PhaserState) == kPhaserSlots * sizeof(StateSlot) && sizeof(
 // the rows cover the effect families of `Family` without gap or overlap as long as they stand in its order.  built / keyed_built:
 // the entry points the kind's `launch` calls are linked (kernels.h declares them weak); the filter's keyed forms are instantiations
 // behind the entry points of its unkeyed ones.
-constexpr int kFxKinds = 12;
+constexpr int kFxKinds = 13;
 static_assert(F_COMP_DETECT < F_EQ_LOCAL && F_EQ_LOCAL < F_DELAY_LOCAL && F_DELAY_LOCAL < F_SAT_SUM && F_SAT_SUM < F_CHORUS_SUM &&
               F_CHORUS_SUM < F_REVERB_SUM && F_REVERB_SUM < F_GATE_DETECT && F_GATE_DETECT < F_PHASER_LOCAL && F_PHASER_LOCAL < F_VOC_LOCAL &&
-              F_VOC_LOCAL < F_FILT_DETECT && F_FILT_DETECT < F_LIM_DETECT && F_LIM_DETECT < F_MB_LOCAL && F_MB_LOCAL < F_COUNT,
+              F_VOC_LOCAL < F_FILT_DETECT && F_FILT_DETECT < F_LIM_DETECT && F_LIM_DETECT < F_MB_LOCAL && F_MB_LOCAL < F_CONV_IR && F_CONV_IR < F_COUNT,
               "the rows of the effect kinds' table stand in the order of their families");
 static const FxKind* table() {
     static const FxKind rows[kFxKinds] = {
@@ -1032,7 +1104,8 @@ static const FxKind* table() {
         {K_VOCODER, "vocoder", "voc", F_VOC_LOCAL, F_FILT_DETECT - F_VOC_LOCAL, sizeof(VocDesc), 0, true, fits_voc, nullptr, through_vocoder, lower_vocoder, launch_vocoder, launch_voc_local && launch_voc_carry && launch_voc_env && launch_voc_apply, launch_voc_local_keyed && launch_voc_apply_keyed, "vocoder", nullptr},
         {K_FILTER, "filter", "filt", F_FILT_DETECT, F_LIM_DETECT - F_FILT_DETECT, sizeof(FiltDesc), kFiltSlots, true, fits_scan, nullptr, through_filter, lower_filter, launch_filter, launch_filt_detect && launch_filt_env && launch_filt_local && launch_filt_carry && launch_filt_apply && launch_master_carry, true, nullptr, nullptr},
         {K_LIMITER, "limiter", "lim", F_LIM_DETECT, F_MB_LOCAL - F_LIM_DETECT, sizeof(LimDesc), 0, false, fits_scan, nullptr, through_limiter, lower_limiter, launch_limiter, launch_lim_detect && launch_lim_apply && launch_master_carry, true, nullptr, nullptr},
-        {K_MULTIBAND, "multiband", "mb", F_MB_LOCAL, F_COUNT - F_MB_LOCAL, sizeof(MbDesc), 0, false, fits_mb, nullptr, through_multiband, lower_multiband, launch_multiband, launch_mb_local && launch_mb_carry && launch_mb_detect && launch_mb_apply && launch_comp_env && launch_master_carry, true, nullptr, nullptr},
+        {K_MULTIBAND, "multiband", "mb", F_MB_LOCAL, F_CONV_IR - F_MB_LOCAL, sizeof(MbDesc), 0, false, fits_mb, nullptr, through_multiband, lower_multiband, launch_multiband, launch_mb_local && launch_mb_carry && launch_mb_detect && launch_mb_apply && launch_comp_env && launch_master_carry, true, nullptr, nullptr},
+        {K_CONVOLUTION, "convolution", "conv", F_CONV_IR, F_COUNT - F_CONV_IR, sizeof(ConvDesc), 0, false, fits_conv, nullptr, through_convolution, lower_convolution, launch_convolution, launch_conv_ir && launch_conv_fwd && launch_conv_mac && launch_conv_inv, true, nullptr, nullptr},
     };
     return rows;
 }

@@ -15,6 +15,7 @@
 #include "vocoder_math.h"
 #include "filter_math.h"
 #include "limiter_math.h"
+#include "conv_math.h"
 #include "multiband_math.h"
 #include "comm.h"
 #include "compile.h"
@@ -583,18 +584,71 @@ void* take_line(td_graph* g, Vertex& v, size_t bytes) {
     v.line = {p, bytes, 0, 0};
     return p;
 }
+// A convolution vertex' spectra block (Vertex::spectra): allocated when the vertex is first compiled into a submission, again when
+// the response has another partition count; *build whenever the sample behind the index is not the one the block was built from.
+// A line whose size no longer fits the response goes with it: the vertex then restarts from silence.
+void* take_spectra(td_graph* g, Vertex& v, size_t bytes, const void* src, size_t src_len, size_t line_bytes, bool* build) {
+    Vertex::Spectra& sp = v.spectra;
+    *build = !sp.d || sp.bytes != bytes || sp.src != src || sp.src_len != src_len;
+    if (sp.d && sp.bytes != bytes) {
+        (void)hipFree(sp.d);   // (waits for the device)
+        g->device_bytes -= sp.bytes;
+        sp = {};
+    }
+    if (v.line.d && v.line.bytes != line_bytes) {
+        (void)hipFree(v.line.d);
+        g->device_bytes -= v.line.bytes;
+        v.line = {};
+    }
+    if (!sp.d) {
+        void* p = nullptr;
+        if (hipMalloc(&p, bytes) != hipSuccess) return nullptr;
+        g->device_bytes += bytes;
+        sp.d = p;
+        sp.bytes = bytes;
+    }
+    sp.src = src;
+    sp.src_len = src_len;
+    return sp.d;
+}
+// The twiddle table of the convolution vertices' transforms: computed once per process in long double, uploaded once per device,
+// kept for the life of the process.
+const double* take_twiddles(td_graph* g) {
+    static std::mutex mu;
+    static std::map<int, double*> by_device;
+    std::lock_guard<std::mutex> lock(mu);
+    auto it = by_device.find(g->device);
+    if (it != by_device.end()) return it->second;
+    std::vector<double> h((size_t)conv::kN);
+    conv::twiddles(h.data());
+    double* p = nullptr;
+    if (hipMalloc(&p, h.size() * sizeof(double)) != hipSuccess) return nullptr;
+    if (hipMemcpy(p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(p); return nullptr; }
+    by_device[g->device] = p;
+    return p;
+}
+// (a chunk that failed to compile or to submit may have claimed spectra whose k_conv_ir never ran: they are built again)
+static void forget_spectra(td_graph* g) {
+    for (auto& v : g->vertices) v.spectra.src = nullptr;
+    g->conv_checks.clear();
+}
 // the line a vertex would continue from in its next submission (nullptr: none -- it has none yet, or it starts afresh)
 static const void* carried_line(const Vertex& v) {
     return !v.first_pending && v.line.total ? v.line.d : nullptr;
 }
 static bool has_lines(const td_graph* g) {
     for (const auto& v : g->vertices)
-        if (v.line.d) return true;
+        if (v.line.d || v.spectra.d) return true;
     return false;
 }
 // (give_back false: no device to give them back to -- they leave the books with their vertices all the same)
 static void free_lines(td_graph* g, bool give_back) {
     for (auto& v : g->vertices) {
+        if (v.spectra.d) {
+            if (give_back) (void)hipFree(v.spectra.d);
+            g->device_bytes -= v.spectra.bytes;
+            v.spectra = {};
+        }
         if (!v.line.d) continue;
         if (give_back) (void)hipFree(v.line.d);
         g->device_bytes -= v.line.bytes;
@@ -1100,6 +1154,20 @@ static int compile_next_chunk(td_graph* g, const td_samplebank* sb, td_flowwbank
 static int finish_chunk(td_graph* g, const RenderPlan& rp, size_t done, size_t nb, bool advance_graph_time,
                         const uint8_t* scratch_base) {
     g->band_stats_base = scratch_base;
+    if (!g->conv_checks.empty()) {
+        // the submission built the spectra of convolution vertices with `norm`: an all-zero response has no energy to normalise to
+        const std::vector<size_t> checks = g->conv_checks;
+        g->conv_checks.clear();
+        TD_HIP(hipStreamSynchronize(g->stream));
+        for (size_t vi : checks) {
+            double e[2] = {0.0, 0.0};
+            TD_HIP(hipMemcpy(e, g->vertices[vi].spectra.d, sizeof e, hipMemcpyDeviceToHost));
+            if (!(std::max(e[0], e[1]) > 0.0)) {
+                forget_spectra(g);
+                return fail("convolution: norm is 1 and the response of vertex '" + g->vertices[vi].name + "' is all zero (or not finite)");
+            }
+        }
+    }
     if (advance_graph_time) g->t += nb * g->bl;
     if (rp.multi)
         TD_HIP(hipMemcpyAsync(g->d_out_f32 + done * g->bl, g->vbuf[(size_t)g->output_vertex], nb * g->bl * sizeof(float2),
@@ -1226,7 +1294,7 @@ static int guard_settle(td_graph* g) {
     if (q.have_backup && hipMemcpyAsync(g->dstate, q.d_backup, g->hstate.size() * sizeof(StateSlot), hipMemcpyDeviceToDevice, g->stream) != hipSuccess)
         ok = fail("HIP error: the guard could not restore the carried state");
     for (const auto& l : q.lines)
-        if (ok && l.vertex < g->vertices.size() && g->vertices[l.vertex].line.d &&
+        if (ok && l.vertex < g->vertices.size() && g->vertices[l.vertex].line.d && g->vertices[l.vertex].line.bytes == l.bytes &&   // (a convolution vertex whose response changed size has a new line)
             hipMemcpyAsync(g->vertices[l.vertex].line.d, (const uint8_t*)q.d_lines + l.off, l.bytes, hipMemcpyDeviceToDevice, g->stream) != hipSuccess)
             ok = fail("HIP error: the guard could not restore a delay line");
     g->state_dev_dirty = true;
@@ -1313,12 +1381,14 @@ int graph_render_chunks(td_graph* g, const td_samplebank* sb, td_flowwbank* fb, 
         g->snapshot.take(g, fb);   // (a chunk that fails to compile or to submit leaves the host state where it found it)
         if (!compile_next_chunk(g, sb, fb, rp, done, nb, is_scan, advance_graph_time, scan_t0, cb)) {
             g->snapshot.put(g, fb);
+            forget_spectra(g);
             return 0;
         }
         audited = audited || (guarded && g->guard.chunk_audited);
         const uint8_t* scratch_base = nullptr;
         if (!submit_chunk(g->arena, cb, g->stream, g->prof, g, &scratch_base, &g->host_ms[2])) {
             g->snapshot.put(g, fb);
+            forget_spectra(g);
             return 0;
         }
         g->host_chunks += 1;
@@ -1402,7 +1472,7 @@ static int batch_render_range(td_batch* b, size_t lo, size_t hi, size_t n_blocks
         // carried voices, a consumed reset_normalization all go back to where this step found them)
         auto roll_back = [&]() {
             for (size_t q = 0; q < P; ++q)
-                if (nb[q]) b->graphs[lo + q]->snapshot.put(b->graphs[lo + q], b->fbs[lo + q]);
+                if (nb[q]) { b->graphs[lo + q]->snapshot.put(b->graphs[lo + q], b->fbs[lo + q]); forget_spectra(b->graphs[lo + q]); }
         };
         for (size_t i = 0; i < P; ++i) nb[i] = std::min(rp[i].chunk_blocks, n_blocks - done[i]);
         for (size_t i = 0; i < P; ++i)
@@ -2134,6 +2204,32 @@ int td_multiband_params(size_t sr, float lo_hz, float hi_hz, const float thresho
     if (n < (size_t)multiband::kParams) return fail("multiband_params: out holds fewer than 27 doubles");
     multiband::params(sr, lo_hz, hi_hz, attack_ms, release_ms, out);
     return 1;
+}
+
+// This engine's own convolution vertex (no reference counterpart; the definition is in include/termdaw_amd.h).  Its state is a
+// carried line (the last D + Lh - 1 input frames) beside the response's partition spectra, both allocated when the vertex is first
+// compiled into a submission: the response is the bank's sample, which only a render brings.
+int td_graph_add_convolution(td_graph* g, const char* name, float gain, float angle, float wet, size_t sample_index, float length_ms,
+                             float predelay_ms, float out_db, int norm) {
+    if (const char* why = conv::check(g->sr, length_ms, predelay_ms, out_db, norm)) return fail(std::string("convolution: ") + why);
+    Vertex& v = add_fx_vertex(g, name, gain, angle, wet, K_CONVOLUTION);
+    v.sample_index = sample_index;
+    v.conv_length_ms = length_ms;
+    v.conv_predelay_ms = predelay_ms;
+    v.conv_out_db = out_db;
+    v.conv_norm = norm;
+    return 1;
+}
+int td_convolution_params(size_t sr, size_t sample_len, float length_ms, float predelay_ms, float out_db, int norm, double out[6]) {
+    if (!out) return fail("convolution_params: out is null");
+    if (const char* why = conv::check(sr, length_ms, predelay_ms, out_db, norm)) return fail(std::string("convolution: ") + why);
+    if (const char* why = conv::check_len(sr, sample_len, length_ms)) return fail(std::string("convolution: ") + why);
+    conv::params(sr, sample_len, length_ms, predelay_ms, out_db, out);
+    return 1;
+}
+size_t td_convolution_twiddles(double* out, size_t cap) {
+    if (out && cap >= (size_t)conv::kN) conv::twiddles(out);
+    return (size_t)conv::kN;
 }
 
 static bool has_loop(size_t x, size_t b, const td_graph* g) {   // graph.rs:66-72

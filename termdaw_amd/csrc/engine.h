@@ -76,7 +76,7 @@ struct td_flowwbank {
 namespace tde {
 
 enum Kind { K_SUM, K_NORMALIZE, K_SAMPLE_LOOP, K_SAMPLE_MULTI, K_SAMPLE_LERP, K_DEBUG_SINE, K_SYNTH,
-            K_SAMPSYN, K_ADSR, K_BAND_PASS, K_COMPRESSOR, K_EQ, K_DELAY, K_SATURATOR, K_CHORUS, K_REVERB, K_GATE, K_PHASER, K_VOCODER, K_FILTER, K_LIMITER, K_MULTIBAND, K_COUNT };
+            K_SAMPSYN, K_ADSR, K_BAND_PASS, K_COMPRESSOR, K_EQ, K_DELAY, K_SATURATOR, K_CHORUS, K_REVERB, K_GATE, K_PHASER, K_VOCODER, K_FILTER, K_LIMITER, K_MULTIBAND, K_CONVOLUTION, K_COUNT };
 
 struct SineNote { float note, vel; };
 struct SynthNote { float note, vel, env_t, rel_t, hz; };   // hz = 440 * 2^((note - 69) / 12), extensions.rs:503
@@ -147,6 +147,8 @@ struct Vertex {
     float lim_ceiling_db = 0, lim_lookahead_ms = 0, lim_release_ms = 1, lim_drive_db = 0;   // K_LIMITER
     float mb_lo_hz = 40, mb_hi_hz = 80, mb_attack_ms = 0, mb_release_ms = 1, mb_knee_db = 0;   // K_MULTIBAND
     float mb_threshold_db[3] = {0, 0, 0}, mb_ratio[3] = {1, 1, 1}, mb_makeup_db[3] = {0, 0, 0};   // ... per band: low, mid, high
+    float conv_length_ms = 0, conv_predelay_ms = 0, conv_out_db = 0;   // K_CONVOLUTION (the response: sample_index)
+    int conv_norm = 0;
     // a filter vertex whose follower runs: env_oct != 0 (otherwise y1, e stay as they are and key edges are ignored)
     bool filt_follows() const { return filt_env_oct != 0.0f; }
     // a vertex with key edges reads them: it is not dry, and a filter's follower runs
@@ -160,12 +162,22 @@ struct Vertex {
     //   K_VOCODER           7 doubles per band, (s1l, s2l, s1r, s2r, s1m, s2m, e): read only once total > 0
     //   K_LIMITER           two halves of 2 L doubles (kernels.h LimDesc): u, the e and the raw input of the last L - 1 frames; read only once total > 0
     //   K_MULTIBAND         42 doubles (kernels.h MbDesc): (s1, s2) of the nine biquads of the left channel, of the right, then (y1, yL) per band; read only once total > 0
+    //   K_CONVOLUTION       two halves of D + Lh - 1 float2 (kernels.h ConvDesc): the last raw input frames, every half written whole; read only once total > 0
     struct Line {
         void* d = nullptr;
         size_t bytes = 0;
         uint64_t total = 0;    // frames the vertex has run since the block restarted
-        uint32_t parity = 0;   // (saturator, chorus, limiter) the half the next launch reads: the one the last launch wrote
+        uint32_t parity = 0;   // (saturator, chorus, limiter, convolution) the half the next launch reads: the one the last launch wrote
     } line;
+    // K_CONVOLUTION: the partition spectra of the response (kernels.h ConvDesc::spec), built by k_conv_ir from the bank's sample at
+    // `src` of `src_len` frames -- built again only when the sample behind the index has another address or length; allocated like
+    // the line, freed with it
+    struct Spectra {
+        void* d = nullptr;
+        size_t bytes = 0;
+        const void* src = nullptr;
+        size_t src_len = 0;
+    } spectra;
     tdk::WaveTableD wavetable{};   // K_SAMPSYN: table in HBM (owned by the graph)
     // carried host state (what the reference keeps inside VertexExt, extensions.rs:15-80)
     uint64_t loop_t = 0;
@@ -180,7 +192,7 @@ struct Vertex {
     // compile.h -- a phaser's hold a tdk::PhaserState, a filter's a tdk::FiltState), index into Graph::dstate
     int state_slot = -1;
     // reset_normalization (extensions.rs:295-299) is kept on the host until the next render consumes it
-    bool first_pending = false;         // band-pass, compressor, eq, gate, phaser, filter, delay, saturator, chorus, reverb, vocoder, limiter, multiband (their state then restarts from zero): set_time since the vertex was last compiled into a submission (its descriptor's first_override)
+    bool first_pending = false;         // band-pass, compressor, eq, gate, phaser, filter, delay, saturator, chorus, reverb, vocoder, limiter, multiband, convolution (their state then restarts from zero): set_time since the vertex was last compiled into a submission (its descriptor's first_override)
     bool has_init_override = false;
     float init_override = 0.0f;
     // Normalize: the carried max is the result of a normalize scan (graph.rs:222-237), so a render is expected to
@@ -514,6 +526,7 @@ struct td_graph {
     double host_ms[4] = {0, 0, 0, 0};   // host time per run_chunk phase: compile, descriptors, upload, launches
     size_t host_chunks = 0;
     tde::HostSnapshot snapshot;         // host state at the start of the chunk being compiled (restored if it fails)
+    std::vector<size_t> conv_checks;    // convolution vertices with `norm` whose spectra the chunk being submitted builds: the sums k_conv_ir leaves are looked at behind the submission (an all-zero response is an error)
 };
 
 // Many independent projects rendered together (BASELINE config 5: the body of State::render's loop,

@@ -1265,6 +1265,63 @@ __attribute__((weak)) void launch_mb_local(const MbDesc* d, int n_desc, uint32_t
 __attribute__((weak)) void launch_mb_carry(const MbDesc* d, int n_desc, hipStream_t s);
 __attribute__((weak)) void launch_mb_detect(const MbDesc* d, int n_desc, uint32_t n_tiles, hipStream_t s);
 __attribute__((weak)) void launch_mb_apply(const MbDesc* d, int n_desc, uint32_t n_tiles, bool single, hipStream_t s);
+// A convolution vertex (k_conv_ir / k_conv_fwd / k_conv_mac / k_conv_inv; the definition is in
+// include/termdaw_amd.h at td_graph_add_convolution): an impulse response from the sample bank by uniform-partitioned
+// overlap-save in f64.  The partition is kConvB frames, a transform kConvN = 2 kConvB complex points (32 KB of LDS); both
+// channels ride one transform as z = l + i r, so with Z = FFT(z) and the real responses' spectra H_l, H_r a product is
+//   Y[k] = Z[k] A[k] + conj(Z[N - k]) C[k],   A = (H_l + H_r) / 2,  C = (H_l - H_r) / 2,
+// and since A[N - k] = conj A[k], C[N - k] = conj C[k] only the bins 0 .. N / 2 of A and C are kept (kConvBins per partition).
+//   k_conv_ir (one workgroup per partition p; only when the spectra have to be built) transforms frames [p B, (p + 1) B) of
+//   the effective response -- D zeros, then g h, g divided by sqrt(max_c sum h_c^2) when `norm` (every workgroup forms that sum
+//   itself, in one fixed order) -- and stores A_p, C_p in `spec` behind a header of kConvHead doubles (word 0, 1: the two sums,
+//   -1 without `norm`; word 2: the g used).
+//   k_conv_fwd (one workgroup per window w = 0 .. n_tiles + P - 2) evaluates the input terms of chunk frames
+//   [(j - 1) B, (j + 1) B), j = w - (P - 1), takes the frames in front of the chunk from the line's half `parity` (0 beyond
+//   `hist` back, and all of them when `fresh`; a non-finite sample enters as 0), stores the raw sum of [j B, (j + 1) B) in
+//   `x`, and leaves the window's spectrum in xs[w] (natural bin order).
+//   k_conv_mac: ys[t][k] = sum over p = 0 .. P - 1, ascending, of the product above with Z = xs[t - p + P - 1]; a lane holds
+//   one bin pair (k, N - k) of kConvTT consecutive tiles, so an (A_p, C_p) and a window's pair are read once for
+//   2 kConvTT products.  No atomics.
+//   k_conv_inv (one workgroup per tile, `hist_groups` more for the line) transforms ys[t] back, keeps the last B frames,
+//   rounds once to f32, p = (float)(re / N), (float)(im / N), lerps against x with `wet`, pan, gain -> `out`; the extra
+//   workgroups write the last `hist` frames of (old half ++ chunk) into the half parity ^ 1, whole.
+// The transforms are radix 2 over a table of N / 2 twiddles (cos, -sin)(2 pi j / N) the host computes in long double: forward
+// decimation in frequency, natural order in, bit-reversed out; inverse decimation in time, bit-reversed in, natural out.
+constexpr uint32_t kConvB = 1024;                  // frames per partition
+constexpr uint32_t kConvN = 2 * kConvB;            // complex points per transform
+constexpr uint32_t kConvBins = kConvN / 2 + 1;     // bins of A and C kept per partition
+constexpr uint32_t kConvTT = 4;                    // tiles per lane of k_conv_mac
+constexpr uint32_t kConvMacGroups = (kConvBins + kThreads - 1) / kThreads;   // workgroups per kConvTT tiles
+constexpr uint32_t kConvHead = 32;                 // doubles in front of the spectra
+constexpr uint32_t kConvHistFrames = 8192;         // line frames per extra workgroup of k_conv_inv
+constexpr uint32_t kConvHistGroups = 64;           // ... at most this many
+struct ConvDesc {
+    const InTerm* ins;      // k input terms (kinds 0 .. 4), in connect() order
+    float2* x;              // [frames] the summed input
+    float2* out;
+    float2* line;           // the carried line: two halves of `hist` frames
+    const float2* ir;       // the bank's sample: the response's frames
+    double* spec;           // kConvHead doubles, then P x kConvBins x (A.re, A.im, C.re, C.im)
+    const double* tw;       // kConvN / 2 twiddles (re, im)
+    double* xs;             // [n_tiles + P - 1][kConvN] window spectra (re, im)
+    double* ys;             // [n_tiles][kConvN] products
+    uint32_t k, term_mode, frames, n_tiles;
+    uint32_t P, Lh, D, hist;   // partitions; response frames; pre-delay frames; D + Lh - 1
+    uint32_t parity;        // the half this chunk reads
+    uint32_t fresh;         // 1: the frames in front of the chunk are all 0, the half is not read
+    uint32_t norm, hist_groups;
+    float wet;
+    uint32_t pad;
+    double g;               // 10^(out_db / 20)
+    PanGain pg;
+};
+// Weak for the same reason: a level's convolution vertices.  The second argument behind the count is grid.x, the largest of the
+// launch's descriptors (a workgroup beyond its own descriptor's range returns): partitions, windows, kConvMacGroups x tile
+// groups, tiles + hist_groups.
+__attribute__((weak)) void launch_conv_ir(const ConvDesc* d, int n_desc, uint32_t grid_x, hipStream_t s);
+__attribute__((weak)) void launch_conv_fwd(const ConvDesc* d, int n_desc, uint32_t grid_x, hipStream_t s);
+__attribute__((weak)) void launch_conv_mac(const ConvDesc* d, int n_desc, uint32_t grid_x, hipStream_t s);
+__attribute__((weak)) void launch_conv_inv(const ConvDesc* d, int n_desc, uint32_t grid_x, hipStream_t s);
 // Weak for the same reason: a level's reverb vertices.  launch_reverb_sum: grid.x from `frames`; launch_reverb: one workgroup per
 // descriptor, `form` 0 the serial walk of each comb's one-pole, 1 the wave scan.
 __attribute__((weak)) void launch_reverb_sum(const ReverbDesc* d, int n_desc, uint32_t frames, hipStream_t s);

@@ -7946,6 +7946,227 @@ __global__ __launch_bounds__(kThreads) void k_mb_apply(const MbDesc* __restrict_
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// k_conv_ir / k_conv_fwd / k_conv_mac / k_conv_inv: the convolution vertex (kernels.h ConvDesc).  No reference
+// counterpart; the definition is the header's (td_graph_add_convolution).  Uniform-partitioned overlap-save in f64: every
+// operation below is an IEEE add, subtract or multiply in the order written (tests/np_convolution.py restates them).
+// ------------------------------------------------------------------------------------------------
+TD_DEV uint32_t conv_rev(uint32_t i) { return __brev(i) >> 21; }   // 11 bits: kConvN = 2048
+static_assert(kConvN == 2048u, "conv_rev reverses 11 bits");
+TD_DEV d2v conv_d2(double a, double b) { d2v w; w.x = a; w.y = b; return w; }
+// (a + i b)(c + i d)
+TD_DEV d2v conv_mul(d2v u, d2v w) { return conv_d2(u.x * w.x - u.y * w.y, u.x * w.y + u.y * w.x); }
+// forward, decimation in frequency: natural order in, bit-reversed out.  The caller has written z[]; on return every lane has
+// passed the last barrier.
+TD_DEV void conv_fft_fwd(d2v* z, const double* tw, uint32_t tid) {
+    uint32_t sh = 0;
+    for (uint32_t half = kConvN / 2; half >= 1u; half >>= 1, ++sh) {
+        __syncthreads();
+        for (uint32_t b = tid; b < kConvN / 2; b += kThreads) {
+            const uint32_t pos = b & (half - 1u), i0 = ((b - pos) << 1) + pos, i1 = i0 + half;
+            const d2v u = z[i0], v = z[i1], w = gload_d2(tw + 2u * (pos << sh));
+            z[i0] = conv_d2(u.x + v.x, u.y + v.y);
+            z[i1] = conv_mul(conv_d2(u.x - v.x, u.y - v.y), w);
+        }
+    }
+    __syncthreads();
+}
+// inverse (unscaled), decimation in time: bit-reversed in, natural order out
+TD_DEV void conv_fft_inv(d2v* z, const double* tw, uint32_t tid) {
+    uint32_t sh = 10;
+    for (uint32_t half = 1u; half <= kConvN / 2; half <<= 1, --sh) {
+        __syncthreads();
+        for (uint32_t b = tid; b < kConvN / 2; b += kThreads) {
+            const uint32_t pos = b & (half - 1u), i0 = ((b - pos) << 1) + pos, i1 = i0 + half;
+            const d2v w = gload_d2(tw + 2u * (pos << sh));
+            const d2v u = z[i0], v = conv_mul(z[i1], conv_d2(w.x, -w.y));
+            z[i0] = conv_d2(u.x + v.x, u.y + v.y);
+            z[i1] = conv_d2(u.x - v.x, u.y - v.y);
+        }
+    }
+    __syncthreads();
+}
+__global__ __launch_bounds__(kThreads) void k_conv_ir(const ConvDesc* __restrict__ descs) {
+    __shared__ d2v z[kConvN];
+    __shared__ double red[2 * kThreads];
+    const ConvDesc& d = descs[blockIdx.y];
+    const uint32_t p = blockIdx.x, tid = threadIdx.x;
+    if (p >= d.P) return;
+    double scale = d.g, el = -1.0, er = -1.0;
+    if (d.norm) {   // every workgroup forms the same two sums in the same order: lane-strided, then a tree
+        el = 0.0; er = 0.0;
+        for (uint32_t i = tid; i < d.Lh; i += kThreads) {
+            const float2 h = gload2(d.ir + i);
+            el = el + (double)h.x * (double)h.x;
+            er = er + (double)h.y * (double)h.y;
+        }
+        red[tid] = el; red[kThreads + tid] = er;
+        __syncthreads();
+        for (uint32_t s = kThreads / 2; s > 0u; s >>= 1) {
+            if (tid < s) { red[tid] = red[tid] + red[tid + s]; red[kThreads + tid] = red[kThreads + tid] + red[kThreads + tid + s]; }
+            __syncthreads();
+        }
+        el = red[0]; er = red[kThreads];
+        scale = d.g / sqrt(fmax(el, er));
+    }
+    if (p == 0u && tid == 0u) { gstore_d2(d.spec, el, er); gstored(d.spec + 2, scale); }
+    for (uint32_t i = tid; i < kConvN; i += kThreads) {
+        const uint64_t e = (uint64_t)p * kConvB + i;   // frame of the effective response: D zeros, then g h
+        d2v v = conv_d2(0.0, 0.0);
+        if (i < kConvB && e >= d.D && e - d.D < d.Lh) {
+            const float2 h = gload2(d.ir + (e - d.D));
+            v = conv_d2(scale * (double)h.x, scale * (double)h.y);
+        }
+        z[i] = v;
+    }
+    conv_fft_fwd(z, d.tw, tid);
+    double* out = d.spec + kConvHead + (size_t)p * kConvBins * 4u;
+    for (uint32_t k = tid; k < kConvBins; k += kThreads) {
+        const d2v a = z[conv_rev(k)], b = z[conv_rev((kConvN - k) & (kConvN - 1u))];
+        // H_l = (a + conj b) / 2, H_r = (a - conj b) / (2 i);  A = (H_l + H_r) / 2, C = (H_l - H_r) / 2
+        const double lx = 0.5 * (a.x + b.x), ly = 0.5 * (a.y - b.y), rx = 0.5 * (a.y + b.y), ry = -0.5 * (a.x - b.x);
+        gstore_d2(out + 4u * k, 0.5 * (lx + rx), 0.5 * (ly + ry));
+        gstore_d2(out + 4u * k + 2u, 0.5 * (lx - rx), 0.5 * (ly - ry));
+    }
+}
+__global__ __launch_bounds__(kThreads) void k_conv_fwd(const ConvDesc* __restrict__ descs) {
+    __shared__ d2v z[kConvN];
+    const ConvDesc& d = descs[blockIdx.y];
+    const uint32_t w = blockIdx.x, tid = threadIdx.x, M = d.frames;
+    if (w >= d.n_tiles + d.P - 1u) return;
+    const int64_t f0 = ((int64_t)w - (int64_t)d.P) * (int64_t)kConvB;   // the window's first chunk frame: (j - 1) B, j = w - (P - 1)
+    const float2* line_r = d.line + (size_t)d.parity * d.hist;
+    auto clean = [](float v) { return delay_finite(v) ? (double)v : 0.0; };
+    for (uint32_t i = tid; i < kConvN; i += kThreads) {
+        const int64_t f = f0 + (int64_t)i;
+        d2v v = conv_d2(0.0, 0.0);
+        if (f < 0 && !d.fresh && (uint64_t)(-f) <= (uint64_t)d.hist) {
+            const float2 h = gload2(line_r + ((int64_t)d.hist + f));
+            v = conv_d2(clean(h.x), clean(h.y));
+        }
+        z[i] = v;
+    }
+    __syncthreads();
+    if (f0 + (int64_t)kConvN > 0) {
+        // the chunk's frames of the window: two aligned frame pairs per thread and step (sum_inputs_pairs' shape); a pair at or
+        // beyond the end is not evaluated
+        const uint32_t ws = f0 > 0 ? (uint32_t)f0 : 0u, we = f0 + (int64_t)kConvN < (int64_t)M ? (uint32_t)(f0 + (int64_t)kConvN) : M;
+        const uint32_t none = (M + 1u) & ~1u, own = (uint32_t)(f0 + (int64_t)kConvB);   // (own: the frames this window stores in x)
+        for (uint32_t i = ws + 2u * tid; i < we; i += 4u * kThreads) {
+            const uint32_t i1 = i + 2u * kThreads < we ? i + 2u * kThreads : none;
+            float4 a0, a1;
+            sum_inputs_pairs(d.ins, d.k, d.term_mode, i, i1, M, a0, a1);
+            a0 = zero_tail(a0, i, M);
+            const uint32_t q = (uint32_t)((int64_t)i - f0);
+            z[q] = conv_d2(clean(a0.x), clean(a0.y));
+            z[q + 1u] = conv_d2(clean(a0.z), clean(a0.w));
+            if (i >= own) store_pair(d.x, i, M, a0);
+            if (i1 != none) {
+                a1 = zero_tail(a1, i1, M);
+                const uint32_t q1 = (uint32_t)((int64_t)i1 - f0);
+                z[q1] = conv_d2(clean(a1.x), clean(a1.y));
+                z[q1 + 1u] = conv_d2(clean(a1.z), clean(a1.w));
+                if (i1 >= own) store_pair(d.x, i1, M, a1);
+            }
+        }
+    }
+    conv_fft_fwd(z, d.tw, tid);
+    double* out = d.xs + (size_t)w * kConvN * 2u;
+    for (uint32_t i = tid; i < kConvN; i += kThreads) {
+        const d2v v = z[i];
+        gstore_d2(out + 2u * conv_rev(i), v.x, v.y);
+    }
+}
+__global__ __launch_bounds__(kThreads) void k_conv_mac(const ConvDesc* __restrict__ descs) {
+    const ConvDesc& d = descs[blockIdx.y];
+    const uint32_t tg = blockIdx.x / kConvMacGroups, k = (blockIdx.x % kConvMacGroups) * kThreads + threadIdx.x;
+    const uint32_t t0 = tg * kConvTT, T = d.n_tiles, P = d.P;
+    if (t0 >= T || k >= kConvBins) return;
+    const uint32_t kn = (kConvN - k) & (kConvN - 1u);
+    const uint32_t live = min(kConvTT, T - t0);
+    // window of tile t and partition p: t - p + P - 1
+    const double* xk = d.xs + 2u * (size_t)k;
+    const double* xn = d.xs + 2u * (size_t)kn;
+    d2v xa[kConvTT], xb[kConvTT], yk[kConvTT], yn[kConvTT];
+#pragma unroll
+    for (uint32_t i = 0; i < kConvTT; ++i) {
+        yk[i] = conv_d2(0.0, 0.0);
+        yn[i] = conv_d2(0.0, 0.0);
+        xa[i] = conv_d2(0.0, 0.0);
+        xb[i] = conv_d2(0.0, 0.0);
+        if (i < live) {
+            const size_t w = (size_t)(t0 + i + P - 1u) * kConvN * 2u;
+            xa[i] = gload_d2(xk + w);
+            xb[i] = gload_d2(xn + w);
+        }
+    }
+    const double* sp = d.spec + kConvHead + 4u * (size_t)k;
+#pragma unroll 1
+    for (uint32_t p = 0; p < P; ++p) {
+        const d2v A = gload_d2(sp + (size_t)p * kConvBins * 4u), C = gload_d2(sp + (size_t)p * kConvBins * 4u + 2u);
+        const d2v Ac = conv_d2(A.x, -A.y), Cc = conv_d2(C.x, -C.y);
+#pragma unroll
+        for (uint32_t i = 0; i < kConvTT; ++i) {
+            const d2v a = xa[i], b = xb[i];
+            const d2v u = conv_mul(a, A), v = conv_mul(conv_d2(b.x, -b.y), C);
+            yk[i] = conv_d2((yk[i].x + u.x) + v.x, (yk[i].y + u.y) + v.y);
+            const d2v un = conv_mul(b, Ac), vn = conv_mul(conv_d2(a.x, -a.y), Cc);
+            yn[i] = conv_d2((yn[i].x + un.x) + vn.x, (yn[i].y + un.y) + vn.y);
+        }
+        if (p + 1u < P) {   // the windows one further back: tile t0 + i takes the pair of tile t0 + i - 1, tile t0 a new one
+#pragma unroll
+            for (uint32_t i = kConvTT - 1u; i > 0u; --i) { xa[i] = xa[i - 1u]; xb[i] = xb[i - 1u]; }
+            const size_t w = (size_t)(t0 + P - 2u - p) * kConvN * 2u;
+            xa[0] = gload_d2(xk + w);
+            xb[0] = gload_d2(xn + w);
+        }
+    }
+#pragma unroll
+    for (uint32_t i = 0; i < kConvTT; ++i) {
+        if (i >= live) break;
+        double* y = d.ys + (size_t)(t0 + i) * kConvN * 2u;
+        gstore_d2(y + 2u * (size_t)k, yk[i].x, yk[i].y);
+        if (kn != k) gstore_d2(y + 2u * (size_t)kn, yn[i].x, yn[i].y);
+    }
+}
+__global__ __launch_bounds__(kThreads) void k_conv_inv(const ConvDesc* __restrict__ descs) {
+    __shared__ d2v z[kConvN];
+    const ConvDesc& d = descs[blockIdx.y];
+    const uint32_t t = blockIdx.x, tid = threadIdx.x, M = d.frames, T = d.n_tiles;
+    if (t >= T) {
+        // the last `hist` frames of (old half ++ chunk) into the other half, whole: a frame older than the old half, or any frame
+        // in front of a fresh chunk, is 0
+        const uint32_t e = t - T, H = d.hist;
+        if (e >= d.hist_groups) return;
+        const float2* line_r = d.line + (size_t)d.parity * H;
+        float2* line_w = d.line + (size_t)(d.parity ^ 1u) * H;
+        for (uint32_t i = e * kThreads + tid; i < H; i += d.hist_groups * kThreads) {
+            const int64_t j = (int64_t)M - (int64_t)H + (int64_t)i;
+            float2 v = make_float2(0.f, 0.f);
+            if (j >= 0) v = gload2(d.x + j);
+            else if (!d.fresh) v = gload2(line_r + ((int64_t)H + j));
+            gstore2(line_w + i, v);
+        }
+        return;
+    }
+    const double* y = d.ys + (size_t)t * kConvN * 2u;
+    for (uint32_t i = tid; i < kConvN; i += kThreads) z[i] = gload_d2(y + 2u * conv_rev(i));
+    conv_fft_inv(z, d.tw, tid);
+    constexpr double inv_n = 1.0 / (double)kConvN;
+    for (uint32_t b = 0; b < kConvB; b += kThreads) {   // (uniform trip count: the shuffle below takes every lane)
+        const uint32_t i = b + tid, n = t * kConvB + i;
+        float2 o = make_float2(0.f, 0.f);
+        if (n < M) {
+            const d2v v = z[kConvB + i];
+            const float pl = (float)(v.x * inv_n), pr = (float)(v.y * inv_n);
+            const float2 x = gload2(d.x + n);
+            o = epilogue(make_float2(x.x + d.wet * (pl - x.x), x.y + d.wet * (pr - x.y)), d.pg);
+        }
+        const float nx = __shfl_down(o.x, 1, 64), ny = __shfl_down(o.y, 1, 64);
+        if (!(tid & 1u) && n < M) gstore4(d.out + n, make_float4(o.x, o.y, nx, ny));   // (buffers are padded to an even frame count)
+    }
+}
+
 constexpr int kMaxGridY = 65535;
 
 // Batched launches put the vertex index in grid.y (limit 65535): larger batches go out in slices.
@@ -8404,6 +8625,22 @@ void launch_mb_apply(const MbDesc* d, int n, uint32_t n_tiles, bool single, hipS
         if (single) hipLaunchKernelGGL(k_mb_apply<1>, grid, dim3(kThreads), 0, s, d + o);
         else hipLaunchKernelGGL(k_mb_apply<0>, grid, dim3(kThreads), 0, s, d + o);
     }
+}
+void launch_conv_ir(const ConvDesc* d, int n, uint32_t grid_x, hipStream_t s) {
+    for (int o = 0; o < n && grid_x; o += kMaxGridY)
+        hipLaunchKernelGGL(k_conv_ir, dim3(grid_x, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
+}
+void launch_conv_fwd(const ConvDesc* d, int n, uint32_t grid_x, hipStream_t s) {
+    for (int o = 0; o < n && grid_x; o += kMaxGridY)
+        hipLaunchKernelGGL(k_conv_fwd, dim3(grid_x, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
+}
+void launch_conv_mac(const ConvDesc* d, int n, uint32_t grid_x, hipStream_t s) {
+    for (int o = 0; o < n && grid_x; o += kMaxGridY)
+        hipLaunchKernelGGL(k_conv_mac, dim3(grid_x, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
+}
+void launch_conv_inv(const ConvDesc* d, int n, uint32_t grid_x, hipStream_t s) {
+    for (int o = 0; o < n && grid_x; o += kMaxGridY)
+        hipLaunchKernelGGL(k_conv_inv, dim3(grid_x, std::min(n - o, kMaxGridY)), dim3(kThreads), 0, s, d + o);
 }
 void launch_sample_loop(const LoopDesc* d, int n, uint32_t frames, hipStream_t s) {
     if (!n || !frames) return;

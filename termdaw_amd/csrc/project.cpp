@@ -25,6 +25,7 @@
 #include "vocoder_math.h"
 #include "filter_math.h"
 #include "limiter_math.h"
+#include "conv_math.h"
 #include "multiband_math.h"
 #include "lua_subset.h"
 #include "reverb_math.h"
@@ -121,6 +122,7 @@ struct PhaserCall { std::string name; float gain, angle, wet; int stages; float 
 struct VocoderCall { std::string name; float gain, angle, wet; int bands; float lo_hz, hi_hz, q, response_ms, out_db; };
 struct FilterCall { std::string name; float gain, angle, wet; int kind; float freq_hz, q, lfo_oct, rate_hz, stereo; int shape; float env_oct, sens_db, attack_ms, release_ms; };
 struct LimiterCall { std::string name; float gain, angle, wet, ceiling_db, lookahead_ms, release_ms, drive_db; };
+struct ConvolutionCall { std::string name; float gain, angle, wet; std::string sample; float length_ms, predelay_ms, out_db; int norm; };
 struct MultibandCall { std::string name; float gain, angle, wet, lo_hz, hi_hz, threshold_db[3], ratio[3], attack_ms, release_ms, knee_db, makeup_db[3]; };
 struct GateCall { std::string name; float gain, angle, wet, threshold_db, hysteresis_db, hold_ms, attack_ms, release_ms, range_db; };
 struct SatCall { std::string name; float gain, angle, wet; int kind; float drive_db, bias, out_db; int oversample; };
@@ -251,6 +253,7 @@ int do_refresh(td_state* s, const std::string& contents) {
     std::vector<FilterCall> filters;
     std::vector<LimiterCall> limiters;
     std::vector<MultibandCall> multibands;
+    std::vector<ConvolutionCall> convolutions;
     size_t cs = s->cs, render_sr = s->render_sr, bd = s->bd;
     // std::mem::take (state.rs:79-80): the locals start from the previous values, the State's own fields are left
     // EMPTY until the script has run (state.rs:169-170) -- so they stay empty when the script fails
@@ -566,6 +569,19 @@ int do_refresh(td_state* s, const std::string& contents) {
                 fnum(c.makeup_db[1]) + "," + fnum(c.makeup_db[2]) + ")\n";
         return Value::nil();
     });
+    lua.set_function("add_convolution", [&](const std::vector<Value>& a) {   // this engine's own vertex (termdaw_amd.h td_graph_add_convolution)
+        const char* f = "add_convolution";
+        const float nf = to_f32(f, a, 8);
+        if (!(nf == 0.0f || nf == 1.0f)) throw LuaError{"add_convolution: convolution: norm must be 0 or 1"};
+        convolutions.push_back({to_str(f, a, 0), to_f32(f, a, 1), to_f32(f, a, 2), to_f32(f, a, 3), to_str(f, a, 4), to_f32(f, a, 5), to_f32(f, a, 6), to_f32(f, a, 7),
+                                nf == 1.0f ? 1 : 0});
+        auto& c = convolutions.back();
+        // (out-of-range parameters are rejected here, where the line is known; the response's length once the bank is loaded)
+        if (const char* why = tde::conv::check(psr, c.length_ms, c.predelay_ms, c.out_db, c.norm)) throw LuaError{std::string("add_convolution: convolution: ") + why};
+        dump += std::string(f) + "(\"" + c.name + "\"," + fnum(c.gain) + "," + fnum(c.angle) + "," + fnum(c.wet) + ",\"" + c.sample + "\"," + fnum(c.length_ms) + "," +
+                fnum(c.predelay_ms) + "," + fnum(c.out_db) + "," + (c.norm ? "1" : "0") + ")\n";
+        return Value::nil();
+    });
     lua.set_function("connect", [&](const std::vector<Value>& a) {
         edges.push_back({to_str("connect", a, 0), to_str("connect", a, 1)});
         dump += "connect(\"" + edges.back().first + "\",\"" + edges.back().second + "\")\n";
@@ -708,6 +724,12 @@ int do_refresh(td_state* s, const std::string& contents) {
                                  c.attack_ms, c.release_ms)) return 0;
     for (auto& c : limiters)
         if (!td_graph_add_limiter(s->g, c.name.c_str(), c.gain, c.angle, c.wet, c.ceiling_db, c.lookahead_ms, c.release_ms, c.drive_db)) return 0;
+    for (auto& c : convolutions) {
+        if (!sample_index(c.sample, c.name, &si)) return 0;
+        // (the bank is loaded: a response over the cap fails here, by name, not at the first render)
+        if (const char* why = tde::conv::check_len(psr, s->sb->samples[si].len, c.length_ms)) return fail(std::string("add_convolution: convolution: ") + why);
+        if (!td_graph_add_convolution(s->g, c.name.c_str(), c.gain, c.angle, c.wet, si, c.length_ms, c.predelay_ms, c.out_db, c.norm)) return 0;
+    }
     for (auto& c : multibands)
         if (!td_graph_add_multiband(s->g, c.name.c_str(), c.gain, c.angle, c.wet, c.lo_hz, c.hi_hz, c.threshold_db, c.ratio, c.attack_ms, c.release_ms, c.knee_db, c.makeup_db)) return 0;
     for (auto& e : edges) td_graph_connect(s->g, e.first.c_str(), e.second.c_str());   // failures only warn (state.rs:459)

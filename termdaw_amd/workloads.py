@@ -155,6 +155,17 @@ def chunk_count(psr, seconds, bl):
     return int(np.ceil(v))
 
 
+class _Calls(dict):
+    """ProjectScript.calls: the lists of the calls every script has stand from the start; "add_convolution" comes into being when
+    it is first asked for, so that the recorded form of a project without such a vertex -- what the tests' digests of the random
+    projects are taken over -- is what it was before the kind existed."""
+    def __missing__(self, k):
+        if k != "add_convolution":
+            raise KeyError(k)
+        v = self[k] = []
+        return v
+
+
 class ProjectScript:
     def __init__(self, project_samplerate=48000, buffer_length=1024):
         self.psr = project_samplerate       # config.rs:62-64 default 44100; BASELINE configs use 48000
@@ -166,10 +177,10 @@ class ProjectScript:
         self.output_vertex = ""
         self.assets = {}                    # path -> Asset
         self.event_files = {}               # path -> ndarray [n,3] (t_sec, note, vel)
-        self.calls = {k: [] for k in (
+        self.calls = _Calls((k, []) for k in (
             "load_sample", "load_resource", "load_midi_floww", "add_sum", "add_normalize", "add_sampleloop",
             "add_sample_multi", "add_sample_lerp", "add_debug_sine", "add_synth", "add_sampsyn", "add_adsr",
-            "add_bandpass", "add_compressor", "add_eq", "add_delay", "add_saturator", "add_chorus", "add_reverb", "add_gate", "add_phaser", "add_vocoder", "add_filter", "add_limiter", "add_multiband", "connect", "connect_key")}
+            "add_bandpass", "add_compressor", "add_eq", "add_delay", "add_saturator", "add_chorus", "add_reverb", "add_gate", "add_phaser", "add_vocoder", "add_filter", "add_limiter", "add_multiband", "connect", "connect_key"))
         self.resources = {}                 # path -> bytes (load_resource)
         self.script_order = []              # (fn, args) in call order, for to_lua()
 
@@ -290,6 +301,11 @@ class ProjectScript:
         self._rec("add_multiband", name, gain, angle, wet, lo_hz, hi_hz, tuple(threshold_db), tuple(ratio), attack_ms, release_ms, knee_db,
                   tuple(makeup_db))
 
+    def add_convolution(self, name, gain, angle, wet, sample, length_ms, predelay_ms, out_db, norm):
+        """This engine's own vertex (include/termdaw_amd.h td_graph_add_convolution): no reference counterpart.  sample: a load_sample
+        name, the impulse response, as in add_sampleloop; norm: 0 or 1."""
+        self._rec("add_convolution", name, gain, angle, wet, sample, length_ms, predelay_ms, out_db, int(norm))
+
     def connect(self, a, b):
         self._rec("connect", a, b)
 
@@ -373,6 +389,8 @@ class ProjectScript:
             g.add_limiter(*args)
         for args in self.calls["add_multiband"]:
             g.add_multiband(*args)
+        for name, gain, angle, wet, smp, length_ms, predelay_ms, out_db, norm in self.calls.get("add_convolution", []):
+            g.add_convolution(name, gain, angle, wet, sidx(smp, name), length_ms, predelay_ms, out_db, norm)
         for a, b in self.calls["connect"]:
             g.connect(a, b)
         for a, b in self.calls["connect_key"]:   # (after the connect calls, as the front-end applies them)
@@ -628,6 +646,26 @@ def multiband_project(seconds=3.0, n_src=8, lo_hz=200.0, hi_hz=2000.0, threshold
         p.connect(a, "bus")
     p.connect("bus", "mb")
     p.set_output("mb")
+    return p
+
+
+def convolution_project(seconds=3.0, bl=1024, ir_seconds=0.5, predelay_ms=10.0, out_db=-6.0, wet=0.35):
+    """The drum project's bus through a convolution vertex (this engine's own): a synthetic room response -- decaying noise, the
+    two channels drawn apart -- loaded like any sample, normalised, in place of the project's Normalize."""
+    p = drum_project(seconds, bl)
+    n = max(1, int(round(ir_seconds * p.psr)))
+    rng = np.random.default_rng(77)
+    env = np.exp(-6.9 * np.arange(n) / n)[:, None]
+    ir = rng.uniform(-1.0, 1.0, (n, 2)) * env
+    ir[0] = 1.0
+    p.assets["ir"] = Asset(np.round(ir * 32767.0).astype(np.int16))
+    # (in front of the first vertex: the front end loads every sample before it builds the graph either way)
+    first_add = min(i for i, (fn, _) in enumerate(p.script_order) if fn.startswith("add_"))
+    p.load_sample("ir", "ir", "")
+    p.script_order.insert(first_add, p.script_order.pop())
+    p.add_convolution("conv", 1.0, 0.0, wet, "ir", 0.0, predelay_ms, out_db, 1)
+    p.connect("band", "conv")
+    p.set_output("conv")
     return p
 
 
