@@ -1571,6 +1571,149 @@ __global__ __launch_bounds__(kThreads) void k_loudness(const LoudDesc* __restric
 }
 
 // ------------------------------------------------------------------------------------------------
+// lane_join / tile_carry: what the affine-scan kernels share (DESIGN.md "The shared scan pieces") -- the mastering pass, comp, eq,
+// voc, filt, lim, mb.
+// A linear recurrence over a chunk in three steps: each lane runs its frames from zero (lane 0 from the value entering the
+// tile), the kThreads lanes of a tile are joined by Hillis-Steele in LDS with the host's powers (lane_join), and a carry launch
+// joins the tiles the same way (tile_carry).  An operator Op is a small struct over the host's tables with
+//   op(k, o, u):   u <- u (+) P_k o, P_k the power of step k (pw[k] in a tile, pwc[k] among the tiles);
+//   op.tile(o, u): u <- u (+) A_tile o, one tile on (the carries only).
+// -ffp-contract=off: the shape of these expressions fixes the bits -- the accumulator on the left, the product on the right.
+// ------------------------------------------------------------------------------------------------
+typedef double d2v __attribute__((ext_vector_type(2)));
+TD_DEV d2v gload_d2(const double* p) { return *reinterpret_cast<const d2v TD_GLOBAL*>((const TD_GLOBAL char*)p); }
+TD_DEV void gstore_d2(double* p, double a, double b) { d2v w; w.x = a; w.y = b; *reinterpret_cast<d2v TD_GLOBAL*>((TD_GLOBAL char*)p) = w; }
+TD_DEV double gloadd(const double* p) { return *reinterpret_cast<const double TD_GLOBAL*>((const TD_GLOBAL char*)p); }
+TD_DEV void gstored(double* p, double v) { *reinterpret_cast<double TD_GLOBAL*>((TD_GLOBAL char*)p) = v; }
+// The lanes' run-end words u (lane 0's run started from u_in, the others' from 0) joined in lane order.  in: the words entering
+// the lane's run; last: the words after the last lane's, the tile's end.  sv: W planes of kThreads doubles.
+template <int W, class Op>
+TD_DEV void lane_join(double (&u)[W], const Op& op, const double (&u_in)[W], double* sv, double (&in)[W], double (&last)[W]) {
+    const uint32_t tid = threadIdx.x;
+#pragma unroll 1
+    for (uint32_t k = 0; k < 8; ++k) {   // after step k, lane j holds the lanes (j - 2^(k+1), j]
+        const uint32_t off = 1u << k;
+#pragma unroll
+        for (int i = 0; i < W; ++i) sv[i * kThreads + tid] = u[i];
+        __syncthreads();
+        if (tid >= off) {
+            double o[W];
+#pragma unroll
+            for (int i = 0; i < W; ++i) o[i] = sv[i * kThreads + tid - off];
+            op(k, o, u);
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int i = 0; i < W; ++i) sv[i * kThreads + tid] = u[i];
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < W; ++i) {
+        in[i] = tid ? sv[i * kThreads + tid - 1] : u_in[i];
+        last[i] = sv[i * kThreads + kThreads - 1];
+    }
+    __syncthreads();
+}
+// W words at p: pairs, or the one
+template <int W>
+TD_DEV void tile_load(const double* p, double (&t)[W]) {
+    static_assert(W == 1 || W % 2 == 0, "tile_load moves one word or pairs");
+    if (W == 1) { t[0] = gloadd(p); return; }
+#pragma unroll
+    for (int i = 0; i + 1 < W; i += 2) {
+        const d2v w = gload_d2(p + i);
+        t[i] = w.x; t[i + 1] = w.y;
+    }
+}
+// ... `in` to o and the W words at p, pair by pair (k_mb_carry keeps a wave more per SIMD than with all stores ahead of the loads)
+template <int W>
+TD_DEV void tile_store_load(double* o, const double (&in)[W], const double* p, double (&t)[W]) {
+    static_assert(W == 1 || W % 2 == 0, "tile_store_load moves one word or pairs");
+    if (W == 1) { gstored(o, in[0]); t[0] = gloadd(p); return; }
+#pragma unroll
+    for (int i = 0; i + 1 < W; i += 2) {
+        gstore_d2(o + i, in[i], in[i + 1]);
+        const d2v w = gload_d2(p + i);
+        t[i] = w.x; t[i + 1] = w.y;
+    }
+}
+// entry[r + 1] = A_tile entry[r] (+) total[r] over n tiles, entry[0] = init.  The buffers hold `per` chains of W words per tile:
+// tile r's total at agg[(r per + idx) W ..], its entry to carry[(r per + idx) W ..].  One workgroup: a lane folds `chunk`
+// consecutive tiles, the lanes are joined with the powers of A_tile^chunk, a second walk writes the entries.  A lane past the
+// last tile folds nothing.
+template <int W, class Op>
+TD_DEV void tile_carry(const Op& op, const double (&init)[W], const double* agg, double* carry, uint32_t idx, uint32_t per, uint32_t n,
+                       uint32_t chunk, double* sv) {
+    const uint32_t tid = threadIdx.x;
+    const uint32_t b = tid * chunk < n ? tid * chunk : n, e = b + chunk < n ? b + chunk : n;
+    double u[W], in[W], last[W], t[W];
+#pragma unroll
+    for (int i = 0; i < W; ++i) u[i] = tid ? 0.0 : init[i];
+    for (uint32_t r = b; r < e; ++r) {
+        tile_load(agg + ((size_t)r * per + idx) * W, t);
+        op.tile(u, t);
+#pragma unroll
+        for (int i = 0; i < W; ++i) u[i] = t[i];
+    }
+    lane_join(u, op, init, sv, in, last);
+    for (uint32_t r = b; r < e; ++r) {
+        tile_store_load(carry + ((size_t)r * per + idx) * W, in, agg + ((size_t)r * per + idx) * W, t);
+        op.tile(in, t);
+#pragma unroll
+        for (int i = 0; i < W; ++i) in[i] = t[i];
+    }
+}
+// scalar max: u <- max(u, p o) -- the releases (pw: a^(run 2^k), or a^(tile chunk 2^k) with a_tile among the tiles)
+struct JoinMax {
+    const double (&pw)[8];
+    double a_tile;
+    TD_DEV void operator()(uint32_t k, const double (&o)[1], double (&u)[1]) const { u[0] = fmax(u[0], pw[k] * o[0]); }
+    TD_DEV void tile(const double (&o)[1], double (&u)[1]) const { u[0] = fmax(u[0], a_tile * o[0]); }
+};
+// N chains that share one scalar factor: u <- u + p o -- the attacks' affine recurrences, the vocoder's followers
+template <int N>
+struct JoinAdd {
+    const double (&pw)[8];
+    double a_tile;
+    TD_DEV void operator()(uint32_t k, const double (&o)[N], double (&u)[N]) const {
+        const double p = pw[k];
+#pragma unroll
+        for (int i = 0; i < N; ++i) u[i] = u[i] + p * o[i];
+    }
+    TD_DEV void tile(const double (&o)[N], double (&u)[N]) const {
+#pragma unroll
+        for (int i = 0; i < N; ++i) u[i] = u[i] + a_tile * o[i];
+    }
+};
+// The scalar joins by name: the value entering the lane's run; *last: the tile's end value.
+template <bool ADD>
+TD_DEV double comp_lane_scan(double u, const double (&pw)[8], double u_in, double* sv, double* last) {
+    double v[1] = {u}, in[1], l[1];
+    const double v_in[1] = {u_in};
+    if (ADD) lane_join(v, JoinAdd<1>{pw, 0.0}, v_in, sv, in, l);
+    else lane_join(v, JoinMax{pw, 0.0}, v_in, sv, in, l);
+    *last = l[0];
+    return in[0];
+}
+// A release over one tile entered at cin: the lane's run y in, u[n] = max(y[n], a u[n - 1]) per frame out (lim, filt)
+template <uint32_t RUN>
+TD_DEV void scan_release(double (&y)[RUN], double a, const double (&pw)[8], double cin, double* sv) {
+    double u = threadIdx.x ? 0.0 : cin, last;
+#pragma unroll
+    for (uint32_t k = 0; k < RUN; ++k) u = fmax(y[k], a * u);
+    u = comp_lane_scan<false>(u, pw, cin, sv, &last);
+#pragma unroll
+    for (uint32_t k = 0; k < RUN; ++k) {
+        u = fmax(y[k], a * u);
+        y[k] = u;
+    }
+}
+// the reference's lerp (adsr.rs:42), f32
+TD_DEV float4 fx_mix4(float4 x, float4 p, float wet) {
+    return make_float4(x.x + wet * (p.x - x.x), x.y + wet * (p.y - x.y), x.z + wet * (p.z - x.z), x.w + wet * (p.w - x.w));
+}
+
+// ------------------------------------------------------------------------------------------------
 // k_master_*: loudness mastering (td_graph_master) -- a lookahead brickwall limiter at gain g under the
 // internal ceiling cp, every signal of a pass in ONE grid per kernel (blockIdx.y the signal), each signal's tiling its own.
 //   k_master_detect (once per call): q[n] = max over [n, n + W - 1] of p, p[n] = max(|x[n]|, the meter's interpolated
@@ -1764,25 +1907,11 @@ TD_DEV void mst_one_minus_h(const MasterDesc& d, int64_t t0, double (&omh)[kMast
 }
 // The release over the tile at t0 entering at u_in: returns the u entering the lane's run; *last (lane 255's end) the tile's end.
 TD_DEV double mst_release(const MasterDesc& d, const double (&omh)[kMasterRun], double u_in, double* sv, double* last) {
-    const uint32_t tid = threadIdx.x;
     const double a = d.a;
-    double u = tid ? 0.0 : u_in;
+    double u = threadIdx.x ? 0.0 : u_in;
 #pragma unroll
     for (uint32_t k = 0; k < kMasterRun; ++k) u = fmax(omh[k], a * u);
-#pragma unroll 1
-    for (uint32_t k = 0; k < 8; ++k) {   // inclusive scan over the lanes: (m, s) o x = max(m, s x), s = a^(run 2^k)
-        const uint32_t off = 1u << k;
-        sv[tid] = u;
-        __syncthreads();
-        if (tid >= off) u = fmax(u, d.pw[k] * sv[tid - off]);
-        __syncthreads();
-    }
-    sv[tid] = u;
-    __syncthreads();
-    const double in = tid ? sv[tid - 1] : u_in;
-    *last = sv[kThreads - 1];
-    __syncthreads();
-    return in;
+    return comp_lane_scan<false>(u, d.pw, u_in, sv, last);   // (m, s) o x = max(m, s x), s = a^(run 2^k)
 }
 __global__ __launch_bounds__(kThreads) void k_master_scan(const MasterDesc* __restrict__ descs) {
     const MasterDesc& d = descs[blockIdx.y];
@@ -1797,30 +1926,9 @@ __global__ __launch_bounds__(kThreads) void k_master_scan(const MasterDesc* __re
 __global__ __launch_bounds__(kThreads) void k_master_carry(const MasterDesc* __restrict__ descs) {
     const MasterDesc& d = descs[blockIdx.x];
     __shared__ double sv[kThreads];
-    const uint32_t tid = threadIdx.x, n = d.n_tiles, c = d.chunk;
-    const uint32_t b = tid * c, e = b + c < n ? b + c : n;
-    const bool add = d.op != 0u;
-    const double init = d.init ? *d.init : 0.0;
-    double u = tid ? 0.0 : init;
-    for (uint32_t r = b; r < e; ++r) u = add ? d.agg[r] + d.a_tile * u : fmax(d.agg[r], d.a_tile * u);
-#pragma unroll 1
-    for (uint32_t k = 0; k < 8; ++k) {
-        const uint32_t off = 1u << k;
-        sv[tid] = u;
-        __syncthreads();
-        if (tid >= off) {
-            const double o = d.pwc[k] * sv[tid - off];
-            u = add ? u + o : fmax(u, o);
-        }
-        __syncthreads();
-    }
-    sv[tid] = u;
-    __syncthreads();
-    u = tid ? sv[tid - 1] : init;
-    for (uint32_t r = b; r < e; ++r) {
-        d.carry[r] = u;
-        u = add ? d.agg[r] + d.a_tile * u : fmax(d.agg[r], d.a_tile * u);
-    }
+    const double init[1] = {d.init ? *d.init : 0.0};
+    if (d.op != 0u) tile_carry(JoinAdd<1>{d.pwc, d.a_tile}, init, d.agg, d.carry, 0u, 1u, d.n_tiles, d.chunk, sv);
+    else tile_carry(JoinMax{d.pwc, d.a_tile}, init, d.agg, d.carry, 0u, 1u, d.n_tiles, d.chunk, sv);
 }
 
 // One frame's word(s) at gain v = g G: saturate(trunc(w v)) on the integer word, (float)(x v) on f32
@@ -1980,9 +2088,6 @@ __global__ __launch_bounds__(kThreads) void k_master_apply(const MasterDesc* __r
 // k_comp_detect / k_comp_env / k_comp_apply: the compressor vertex (kernels.h CompDesc).  No reference
 // counterpart; the definition is the header's (td_graph_add_compressor), f64 from the level to the gain.
 // ------------------------------------------------------------------------------------------------
-typedef double d2v __attribute__((ext_vector_type(2)));
-TD_DEV d2v gload_d2(const double* p) { return *reinterpret_cast<const d2v TD_GLOBAL*>((const TD_GLOBAL char*)p); }
-TD_DEV void gstore_d2(double* p, double a, double b) { d2v w; w.x = a; w.y = b; *reinterpret_cast<d2v TD_GLOBAL*>((TD_GLOBAL char*)p) = w; }
 // steps 1 and 2: the wanted reduction in dB of one summed input frame
 TD_DEV double comp_want(const CompDesc& d, float l, float r) {
     const float al = fabsf(l), ar = fabsf(r);
@@ -1997,30 +2102,6 @@ TD_DEV double comp_want(const CompDesc& d, float l, float r) {
     }
     if (2.0 * o > W) return d.slope * o;
     return 0.0;
-}
-// The lanes' run-end values u (lane 0's run started from u_in) joined in lane order: Hillis-Steele with the host's powers
-// pw[k] = a^(kCompRun 2^k), operator max (the release) or + (the attack's affine recurrence: every lane's factor is the same
-// a^kCompRun).  Returns the value entering the lane's run; *last: the tile's end value.
-template <bool ADD>
-TD_DEV double comp_lane_scan(double u, const double (&pw)[8], double u_in, double* sv, double* last) {
-    const uint32_t tid = threadIdx.x;
-#pragma unroll 1
-    for (uint32_t k = 0; k < 8; ++k) {
-        const uint32_t off = 1u << k;
-        sv[tid] = u;
-        __syncthreads();
-        if (tid >= off) {
-            const double o = pw[k] * sv[tid - off];
-            u = ADD ? u + o : fmax(u, o);
-        }
-        __syncthreads();
-    }
-    sv[tid] = u;
-    __syncthreads();
-    const double in = tid ? sv[tid - 1] : u_in;
-    *last = sv[kThreads - 1];
-    __syncthreads();
-    return in;
 }
 // the lane's kCompRun values of dy (0 from `frames` on)
 TD_DEV void comp_load_run(const CompDesc& d, uint32_t f0, double (&y)[kCompRun]) {
@@ -2117,9 +2198,7 @@ __global__ __launch_bounds__(kThreads) void k_comp_apply(const CompDesc* __restr
         const double g1 = exp10((mk - yl) / 20.0);
         if (m + 2u == M) d.state->yL = yl;
         const float4 p = make_float4((float)((double)x.x * g0), (float)((double)x.y * g0), (float)((double)x.z * g1), (float)((double)x.w * g1));
-        // the reference's lerp (adsr.rs:42), f32
-        const float4 o = make_float4(x.x + wet * (p.x - x.x), x.y + wet * (p.y - x.y), x.z + wet * (p.z - x.z), x.w + wet * (p.w - x.w));
-        store_pair(d.out, m, M, epilogue4(o, d.pg));
+        store_pair(d.out, m, M, epilogue4(fx_mix4(x, p, wet), d.pg));
     }
 }
 
@@ -2143,34 +2222,17 @@ TD_DEV void eq_mac(double (&u)[4], const double (&P)[4], const double (&o)[4]) {
     u[2] += P[0] * o[2] + P[1] * o[3];
     u[3] += P[2] * o[2] + P[3] * o[3];
 }
-// The lanes' run-end states u (lane 0's run started from u_in, the others' from 0) joined in lane order: Hillis-Steele with
-// the host's matrices pw[k] = A^(run 2^k).  in: the state entering the lane's run; last: the state after the last lane's.
-// sv: 4 planes of kThreads doubles.
+// lane_join's operator: the 2x2 over both channels, pw[k] = A^(run 2^k) (EqDesc::pw in a tile, pwc among the tiles)
+struct JoinEq {
+    const double (&pw)[8][4];
+    const double (&a_tile)[4];
+    TD_DEV void operator()(uint32_t k, const double (&o)[4], double (&u)[4]) const { eq_mac(u, pw[k], o); }
+    TD_DEV void tile(const double (&o)[4], double (&u)[4]) const { eq_mac(u, a_tile, o); }
+};
+// The join inside a tile, by name (no tile step there: a_tile is any four words).  A function of its own with pw its one table:
+// joined straight from the kernels, k_eq_local's term loop compiles to other instructions.
 TD_DEV void eq_lane_scan(double (&u)[4], const double (&pw)[8][4], const double (&u_in)[4], double* sv, double (&in)[4], double (&last)[4]) {
-    const uint32_t tid = threadIdx.x;
-#pragma unroll 1
-    for (uint32_t k = 0; k < 8; ++k) {
-        const uint32_t off = 1u << k;
-#pragma unroll
-        for (uint32_t i = 0; i < 4; ++i) sv[i * kThreads + tid] = u[i];
-        __syncthreads();
-        if (tid >= off) {
-            double o[4];
-#pragma unroll
-            for (uint32_t i = 0; i < 4; ++i) o[i] = sv[i * kThreads + tid - off];
-            eq_mac(u, pw[k], o);
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (uint32_t i = 0; i < 4; ++i) sv[i * kThreads + tid] = u[i];
-    __syncthreads();
-#pragma unroll
-    for (uint32_t i = 0; i < 4; ++i) {
-        in[i] = tid ? sv[i * kThreads + tid - 1] : u_in[i];
-        last[i] = sv[i * kThreads + kThreads - 1];
-    }
-    __syncthreads();
+    lane_join(u, JoinEq{pw, pw[0]}, u_in, sv, in, last);
 }
 __global__ __launch_bounds__(kThreads) void k_eq_local(const EqDesc* __restrict__ descs) {
     const EqDesc& d = descs[blockIdx.y];
@@ -2198,40 +2260,15 @@ __global__ __launch_bounds__(kThreads) void k_eq_local(const EqDesc* __restrict_
         gstore_d2(d.agg + 4u * blockIdx.x + 2u, last[2], last[3]);
     }
 }
-// entry[t + 1] = A^kEqTile entry[t] + total[t], entry[0] = *init: k_master_carry's shape (a lane folds `chunk` consecutive
-// tiles, Hillis-Steele over the lanes, a second walk writes the entries) with a 2x2 operator and both channels.  A kernel of
-// its own: k_master_carry and its two users stay as they are.
+// entry[t + 1] = A^kEqTile entry[t] + total[t], entry[0] = *init: tile_carry with the 2x2 operator and both channels.  A kernel
+// of its own: k_master_carry and its two users stay as they are.
 __global__ __launch_bounds__(kThreads) void k_eq_carry(const EqDesc* __restrict__ descs) {
     const EqDesc& d = descs[blockIdx.x];
     __shared__ double sv[4 * kThreads];
-    const uint32_t tid = threadIdx.x, n = d.n_tiles, c = d.chunk;
-    const uint32_t b = tid * c, e = b + c < n ? b + c : n;
     double init[4] = {0.0, 0.0, 0.0, 0.0};
-    if (d.init) {
-        const d2v l = gload_d2(&d.init->s1l), r = gload_d2(&d.init->s1r);
-        init[0] = l.x; init[1] = l.y; init[2] = r.x; init[3] = r.y;
-    }
-    double u[4];
-#pragma unroll
-    for (uint32_t i = 0; i < 4; ++i) u[i] = tid ? 0.0 : init[i];
-    for (uint32_t r = b; r < e; ++r) {
-        const d2v l = gload_d2(d.agg + 4u * r), rr = gload_d2(d.agg + 4u * r + 2u);
-        double t[4] = {l.x, l.y, rr.x, rr.y};
-        eq_mac(t, d.a_tile, u);
-#pragma unroll
-        for (uint32_t i = 0; i < 4; ++i) u[i] = t[i];
-    }
-    double in[4], last[4];
-    eq_lane_scan(u, d.pwc, init, sv, in, last);
-    for (uint32_t r = b; r < e; ++r) {
-        gstore_d2(d.carry + 4u * r, in[0], in[1]);
-        gstore_d2(d.carry + 4u * r + 2u, in[2], in[3]);
-        const d2v l = gload_d2(d.agg + 4u * r), rr = gload_d2(d.agg + 4u * r + 2u);
-        double t[4] = {l.x, l.y, rr.x, rr.y};
-        eq_mac(t, d.a_tile, in);
-#pragma unroll
-        for (uint32_t i = 0; i < 4; ++i) in[i] = t[i];
-    }
+    static_assert(sizeof(EqState) == 4 * sizeof(double) && offsetof(EqState, s1r) == 2 * sizeof(double), "init is EqState's four words in order");
+    if (d.init) tile_load(&d.init->s1l, init);
+    tile_carry(JoinEq{d.pwc, d.a_tile}, init, d.agg, d.carry, 0u, 1u, d.n_tiles, d.chunk, sv);
 }
 // one frame of the definition, one channel: y = b0 x + s1;  s1 = (b1 x - a1 y) + s2;  s2 = b2 x - a2 y;  p = (float)y -- a
 // non-finite x enters as 0 and comes out as itself
@@ -2275,9 +2312,7 @@ __global__ __launch_bounds__(kThreads) void k_eq_apply(const EqDesc* __restrict_
         p.z = eq_frame(d, x[j].z, z[0], z[1]);
         p.w = eq_frame(d, x[j].w, z[2], z[3]);
         if (m + 2u == M) { d.state->s1l = z[0]; d.state->s2l = z[1]; d.state->s1r = z[2]; d.state->s2r = z[3]; }
-        // the reference's lerp (adsr.rs:42), f32
-        const float4 o = make_float4(x[j].x + wet * (p.x - x[j].x), x[j].y + wet * (p.y - x[j].y), x[j].z + wet * (p.z - x[j].z), x[j].w + wet * (p.w - x[j].w));
-        store_pair(d.out, m, M, epilogue4(o, d.pg));
+        store_pair(d.out, m, M, epilogue4(fx_mix4(x[j], p, wet), d.pg));
     }
 }
 
@@ -2686,8 +2721,6 @@ __global__ __launch_bounds__(kThreads) void k_chorus(const ChorusDesc* __restric
 // the header's (td_graph_add_reverb): 8 damped feedback combs per channel summed from 0.0 in ascending order, 4 series all-pass
 // sections, cross-mix, wet lerp, pan and gain -- f64 on the f32 summed input.
 // ------------------------------------------------------------------------------------------------
-TD_DEV double gloadd(const double* p) { return *reinterpret_cast<const double TD_GLOBAL*>((const TD_GLOBAL char*)p); }
-TD_DEV void gstored(double* p, double v) { *reinterpret_cast<double TD_GLOBAL*>((TD_GLOBAL char*)p) = v; }
 // the summed input, materialised once: k_sum's frame mapping, identity epilogue
 __global__ __launch_bounds__(kThreads) void k_reverb_sum(const ReverbDesc* __restrict__ descs) { fx_sum(descs); }
 constexpr uint32_t kReverbRow = 256;   // doubles per (comb, channel) row of the window's delayed reads in LDS
@@ -6334,9 +6367,7 @@ __global__ __launch_bounds__(kThreads) void k_gate_apply(const GateDesc* __restr
         }
         const float4 v = x[j];
         const float4 p = make_float4((float)((double)v.x * g0), (float)((double)v.y * g0), (float)((double)v.z * g1), (float)((double)v.w * g1));
-        // the reference's lerp (adsr.rs:42), f32
-        const float4 o = make_float4(v.x + wet * (p.x - v.x), v.y + wet * (p.y - v.y), v.z + wet * (p.z - v.z), v.w + wet * (p.w - v.w));
-        store_pair(d.out, m, M, epilogue4(o, d.pg));
+        store_pair(d.out, m, M, epilogue4(fx_mix4(v, p, wet), d.pg));
     }
 }
 
@@ -6597,10 +6628,33 @@ TD_DEV double voc_frame(double b0, double b1, double b2, double a1, double a2, d
     s2 = b2 * x - a2 * y;
     return y;
 }
-// The lanes' run-end states joined in lane order, NB bands of NV two-vectors each (band j's vectors share its matrices:
-// TILES ? pwc : pw), eq_lane_scan's arithmetic.  u: lane 0's run started from u_in, the others' from 0.  in: the state entering
-// the lane's run; last: the state after the last lane's.  sv: 2 NV NB planes.
+// lane_join's operator: NB bands of NV two-vectors each, band j's vectors sharing its matrices (TILES ? pwc : pw; a_tile one
+// tile on), JoinEq's arithmetic.  The followers' NB scalar chains are JoinAdd<NB>.
 template <int NB, int NV, bool TILES>
+struct JoinVoc {
+    const VocBand* bd;
+    TD_DEV static void mac(const double* P, const double (&o)[2 * NV * NB], double (&u)[2 * NV * NB], int j) {
+        const double p0 = gloadd(P), p1 = gloadd(P + 1), p2 = gloadd(P + 2), p3 = gloadd(P + 3);
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+            const int i = 2 * (NV * j + v);
+            const double n0 = u[i] + (p0 * o[i] + p1 * o[i + 1]), n1 = u[i + 1] + (p2 * o[i] + p3 * o[i + 1]);
+            u[i] = n0; u[i + 1] = n1;
+        }
+    }
+    TD_DEV void operator()(uint32_t k, const double (&o)[2 * NV * NB], double (&u)[2 * NV * NB]) const {
+#pragma unroll
+        for (int j = 0; j < NB; ++j) mac(TILES ? bd[j].pwc[k] : bd[j].pw[k], o, u, j);
+    }
+    TD_DEV void tile(const double (&o)[2 * NV * NB], double (&u)[2 * NV * NB]) const {
+#pragma unroll
+        for (int j = 0; j < NB; ++j) mac(bd[j].a_tile, o, u, j);
+    }
+};
+// k_voc_apply's two joins keep the bodies they had (JoinVoc's and JoinAdd's arithmetic, the matrices loaded ahead of the LDS
+// words): joined through lane_join its 4-band form at 64 vertices measured 1.3 % slower in both rounds of
+// profiles/scan_share_time.txt.  NB bands of NV two-vectors each; sv: 2 NV NB planes.
+template <int NB, int NV>
 TD_DEV void voc_lane_scan(double (&u)[2 * NV * NB], const VocBand* bd, const double (&u_in)[2 * NV * NB], double* sv, double (&in)[2 * NV * NB],
                           double (&last)[2 * NV * NB]) {
     constexpr int W = 2 * NV * NB;
@@ -6614,7 +6668,7 @@ TD_DEV void voc_lane_scan(double (&u)[2 * NV * NB], const VocBand* bd, const dou
         if (tid >= off) {
 #pragma unroll
             for (int j = 0; j < NB; ++j) {
-                const double* P = TILES ? bd[j].pwc[k] : bd[j].pw[k];
+                const double* P = bd[j].pw[k];
                 const double p0 = gloadd(P), p1 = gloadd(P + 1), p2 = gloadd(P + 2), p3 = gloadd(P + 3);
 #pragma unroll
                 for (int v = 0; v < NV; ++v) {
@@ -6637,7 +6691,6 @@ TD_DEV void voc_lane_scan(double (&u)[2 * NV * NB], const VocBand* bd, const dou
     }
     __syncthreads();
 }
-// ... and NB scalar chains that share the factors pw[k] (comp_lane_scan<true>'s arithmetic)
 template <int NB>
 TD_DEV void voc_env_scan(double (&e)[NB], const double (&pw)[8], const double (&e_in)[NB], double* sv, double (&in)[NB], double (&last)[NB]) {
     const uint32_t tid = threadIdx.x;
@@ -6735,7 +6788,7 @@ __global__ __launch_bounds__(kThreads) void k_voc_local(const VocDesc* __restric
                 voc_zstep(c0, c1, a1, a2, u[6 * jb + 4], u[6 * jb + 5], xm[j]);
             }
         }
-        voc_lane_scan<J, 3, false>(u, bd, zero, sv, in, last);
+        lane_join(u, JoinVoc<J, 3, false>{bd}, zero, sv, in, last);
         if (tid == 0) {
             double* a = d.agg + ((size_t)blockIdx.x * B + g * J) * 6u;
 #pragma unroll
@@ -6743,60 +6796,22 @@ __global__ __launch_bounds__(kThreads) void k_voc_local(const VocDesc* __restric
         }
     }
 }
-// MODE 0: entry[t + 1] = A_b^kVocTile entry[t] + total[t] for band b's three two-vectors, entry[0] the line's (k_eq_carry's
-// shape: a lane folds `chunk` consecutive tiles, Hillis-Steele over the lanes, a second walk writes the entries).  MODE 1: the
-// scalar affine carry of e_b with a^kVocTile.  One workgroup per band and vertex: grid (B, n_desc).
+// MODE 0: entry[t + 1] = A_b^kVocTile entry[t] + total[t] for band b's three two-vectors, entry[0] the line's (tile_carry).
+// MODE 1: the scalar affine carry of e_b with a^kVocTile.  One workgroup per band and vertex: grid (B, n_desc).
 template <int MODE>
 __global__ __launch_bounds__(kThreads) void k_voc_carry(const VocDesc* __restrict__ descs) {
     const VocDesc& d = descs[blockIdx.y];
     const uint32_t band = blockIdx.x, B = d.bands;
     if (band >= B) return;
     __shared__ double sv[6 * kThreads];
-    const uint32_t tid = threadIdx.x, n = d.n_tiles, c = d.chunk;
-    const uint32_t b = tid * c < n ? tid * c : n, e = b + c < n ? b + c : n;
     if (MODE == 0) {
-        const VocBand* bd = d.band + band;
-        double P[4];
+        double init[6];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) P[i] = gloadd(&bd->a_tile[i]);
-        double init[6], u[6], in[6], last[6];
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            init[i] = d.init ? gloadd(d.init + kVocState * band + i) : 0.0;
-            u[i] = tid ? 0.0 : init[i];
-        }
-        for (uint32_t r = b; r < e; ++r) {
-            const double* a = d.agg + ((size_t)r * B + band) * 6u;
-#pragma unroll
-            for (int v = 0; v < 3; ++v) {
-                const d2v t = gload_d2(a + 2 * v);
-                const double n0 = t.x + (P[0] * u[2 * v] + P[1] * u[2 * v + 1]), n1 = t.y + (P[2] * u[2 * v] + P[3] * u[2 * v + 1]);
-                u[2 * v] = n0; u[2 * v + 1] = n1;
-            }
-        }
-        voc_lane_scan<1, 3, true>(u, bd, init, sv, in, last);
-        for (uint32_t r = b; r < e; ++r) {
-            const double* a = d.agg + ((size_t)r * B + band) * 6u;
-            double* o = d.carry + ((size_t)r * B + band) * 6u;
-#pragma unroll
-            for (int v = 0; v < 3; ++v) {
-                gstore_d2(o + 2 * v, in[2 * v], in[2 * v + 1]);
-                const d2v t = gload_d2(a + 2 * v);
-                const double n0 = t.x + (P[0] * in[2 * v] + P[1] * in[2 * v + 1]), n1 = t.y + (P[2] * in[2 * v] + P[3] * in[2 * v + 1]);
-                in[2 * v] = n0; in[2 * v + 1] = n1;
-            }
-        }
+        for (int i = 0; i < 6; ++i) init[i] = d.init ? gloadd(d.init + kVocState * band + i) : 0.0;
+        tile_carry(JoinVoc<1, 3, true>{d.band + band}, init, d.agg, d.carry, band, B, d.n_tiles, d.chunk, sv);
     } else {
-        const double at = d.a_tile;
-        double init[1], u[1], in[1], last[1];
-        init[0] = d.init ? gloadd(d.init + kVocState * band + 6u) : 0.0;
-        u[0] = tid ? 0.0 : init[0];
-        for (uint32_t r = b; r < e; ++r) u[0] = gloadd(d.agge + (size_t)r * B + band) + at * u[0];
-        voc_env_scan<1>(u, d.pwac, init, sv, in, last);
-        for (uint32_t r = b; r < e; ++r) {
-            gstored(d.carrye + (size_t)r * B + band, in[0]);
-            in[0] = gloadd(d.agge + (size_t)r * B + band) + at * in[0];
-        }
+        const double init[1] = {d.init ? gloadd(d.init + kVocState * band + 6u) : 0.0};
+        tile_carry(JoinAdd<1>{d.pwac, d.a_tile}, init, d.agge, d.carrye, band, B, d.n_tiles, d.chunk, sv);
     }
 }
 template <int B>
@@ -6823,7 +6838,7 @@ __global__ __launch_bounds__(kThreads) void k_voc_env(const VocDesc* __restrict_
 #pragma unroll
             for (uint32_t j = 0; j < kVocRun; ++j) voc_zstep(c0, c1, a1, a2, u[2 * jb], u[2 * jb + 1], xm[j]);
         }
-        voc_lane_scan<J, 1, false>(u, bd, cin, sv, z, last);
+        lane_join(u, JoinVoc<J, 1, false>{bd}, cin, sv, z, last);
         double e[J], ezero[J], ein[J], elast[J];
 #pragma unroll
         for (int jb = 0; jb < J; ++jb) {
@@ -6832,7 +6847,7 @@ __global__ __launch_bounds__(kThreads) void k_voc_env(const VocDesc* __restrict_
 #pragma unroll
             for (uint32_t j = 0; j < kVocRun; ++j) e[jb] = fa * e[jb] + oa * fabs(voc_frame(b0, b1, b2, a1, a2, z[2 * jb], z[2 * jb + 1], xm[j]));
         }
-        voc_env_scan<J>(e, d.pwa, ezero, sv, ein, elast);
+        lane_join(e, JoinAdd<J>{d.pwa, 0.0}, ezero, sv, ein, elast);
         if (tid < (uint32_t)J) {
             double w = elast[0];
 #pragma unroll
@@ -6902,7 +6917,7 @@ __global__ __launch_bounds__(kThreads) void k_voc_apply(const VocDesc* __restric
                     voc_zstep(c0, c1, a1, a2, u[6 * jb + 4], u[6 * jb + 5], xm[j]);
                 }
             }
-            voc_lane_scan<J, 3, false>(u, bd, cin, sv, z, last);
+            voc_lane_scan<J, 3>(u, bd, cin, sv, z, last);
         }
         // the follower entering the lane's run: its zero-start run-end value from a copy of the modulator's state, joined
         double ein[J];
@@ -6948,9 +6963,7 @@ __global__ __launch_bounds__(kThreads) void k_voc_apply(const VocDesc* __restric
         if (m >= M) break;
         const float4 x = make_float4(xl[2 * j], xr[2 * j], xl[2 * j + 1], xr[2 * j + 1]);
         const float4 p = make_float4((float)(gn * accl[2 * j]), (float)(gn * accr[2 * j]), (float)(gn * accl[2 * j + 1]), (float)(gn * accr[2 * j + 1]));
-        // the reference's lerp (adsr.rs:42), f32
-        const float4 o = make_float4(x.x + wet * (p.x - x.x), x.y + wet * (p.y - x.y), x.z + wet * (p.z - x.z), x.w + wet * (p.w - x.w));
-        store_pair(d.out, m, M, epilogue4(o, d.pg));
+        store_pair(d.out, m, M, epilogue4(fx_mix4(x, p, wet), d.pg));
     }
 }
 
@@ -7108,20 +7121,7 @@ TD_DEV void filt_keep(double* p, const double (&y)[kFiltRun], uint32_t M, uint32
     for (uint32_t k = 0; k < kFiltRun; ++k)
         if (f0 + k + 1u == M) gstored(p, y[k]);
 }
-// the release: the lane's run of s from u (lane 0: the entering y1), joined; then y1 per frame, in place
-TD_DEV void filt_release(const FiltDesc& d, double (&y)[kFiltRun], double cin, double* sv) {
-    const double aR = d.aR;
-    double u = threadIdx.x ? 0.0 : cin, last;
-#pragma unroll
-    for (uint32_t k = 0; k < kFiltRun; ++k) u = fmax(y[k], aR * u);
-    u = comp_lane_scan<false>(u, d.pwR, cin, sv, &last);
-#pragma unroll
-    for (uint32_t k = 0; k < kFiltRun; ++k) {
-        u = fmax(y[k], aR * u);
-        y[k] = u;
-    }
-}
-// the attack: e per frame from y1, in place, entered with cin
+// the attack: e per frame from y1, in place, entered with cin (the release before it, y1 from s, is scan_release)
 TD_DEV void filt_attack(const FiltDesc& d, double (&y)[kFiltRun], double cin, double* sv) {
     const double aA = d.aA, oA = d.oA;
     double b = threadIdx.x ? 0.0 : cin, last;
@@ -7164,7 +7164,7 @@ __global__ __launch_bounds__(kThreads) void k_filt_env(const FiltDesc* __restric
     const double aA = d.aA, oA = d.oA;
     double y[kFiltRun], last;
     filt_load_run(d.lv, M, f0, y);
-    filt_release(d, y, d.carry1[blockIdx.x], sv);
+    scan_release(y, d.aR, d.pwR, d.carry1[blockIdx.x], sv);
     filt_keep(&d.state->y1, y, M, f0);
     filt_store_run(d.lv, M, f0, y);
     double b = 0.0;
@@ -7248,7 +7248,7 @@ __global__ __launch_bounds__(kThreads) void k_filt_apply(const FiltDesc* __restr
 #pragma unroll
                 for (uint32_t k = 0; k < kFiltRun; ++k) e[k] = filt_level(x[k].x, x[k].y);
             }
-            filt_release(d, e, d.init ? gloadd(&d.init->y1) : 0.0, sv);
+            scan_release(e, d.aR, d.pwR, d.init ? gloadd(&d.init->y1) : 0.0, sv);
             filt_keep(&d.state->y1, e, M, f0);
             filt_attack(d, e, d.init ? gloadd(&d.init->e) : 0.0, sv);
             filt_keep(&d.state->e, e, M, f0);
@@ -7374,19 +7374,6 @@ TD_DEV void lim_load_q(const float* q, uint32_t M, uint32_t f0, float (&Q)[kLimR
     } else {
 #pragma unroll
         for (uint32_t k = 0; k < kLimRun; ++k) Q[k] = f0 + k < M ? gload1(q + f0 + k) : 0.f;
-    }
-}
-// the release over one tile entered at cin: 1 - h of the lane's run in, u per frame out
-TD_DEV void lim_release(const LimDesc& d, double (&y)[kLimRun], double cin, double* sv) {
-    const double a = d.a;
-    double u = threadIdx.x ? 0.0 : cin, last;
-#pragma unroll
-    for (uint32_t k = 0; k < kLimRun; ++k) u = fmax(y[k], a * u);
-    u = comp_lane_scan<false>(u, d.pw, cin, sv, &last);
-#pragma unroll
-    for (uint32_t k = 0; k < kLimRun; ++k) {
-        u = fmax(y[k], a * u);
-        y[k] = u;
     }
 }
 // PS[j] = sum of e over (s0, j] for the lane's run from frame fa on, a round behind `running`: the lane's own sums, the lanes'
@@ -7538,7 +7525,7 @@ __global__ __launch_bounds__(kThreads) void k_lim_apply(const LimDesc* __restric
             lim_load_q(d.q, M, (uint32_t)fa, Qa);
 #pragma unroll
             for (uint32_t k = 0; k < kLimRun; ++k) y[k] = lim_omh(d, Qa[k]);
-            lim_release(d, y, d.carry[tile - 1u], sv);
+            scan_release(y, d.a, d.pw, d.carry[tile - 1u], sv);   // 1 - h of the lane's run in, u per frame out
 #pragma unroll
             for (uint32_t k = 0; k < kLimRun; ++k) {
                 y[k] = 1.0 - y[k];
@@ -7550,7 +7537,7 @@ __global__ __launch_bounds__(kThreads) void k_lim_apply(const LimDesc* __restric
     }
 #pragma unroll
     for (uint32_t k = 0; k < kLimRun; ++k) y[k] = f0 + k < M ? lim_omh(d, Q[k]) : 0.0;
-    lim_release(d, y, SINGLE ? (fresh ? 0.0 : gloadd(lr)) : d.carry[tile], sv);
+    scan_release(y, d.a, d.pw, SINGLE ? (fresh ? 0.0 : gloadd(lr)) : d.carry[tile], sv);
 #pragma unroll
     for (uint32_t k = 0; k < kLimRun; ++k) {
         if (f0 + k + 1u == M) gstored(lw, y[k]);   // the chunk's last frame: the u the next chunk / block pull enters with
@@ -7576,9 +7563,7 @@ __global__ __launch_bounds__(kThreads) void k_lim_apply(const LimDesc* __restric
         }
         const float4 p = make_float4((float)(((double)xd[0].x * gin) * G[0]), (float)(((double)xd[0].y * gin) * G[0]),
                                      (float)(((double)xd[1].x * gin) * G[1]), (float)(((double)xd[1].y * gin) * G[1]));
-        // the reference's lerp (adsr.rs:42), f32
-        const float4 o = make_float4(xd[0].x + wet * (p.x - xd[0].x), xd[0].y + wet * (p.y - xd[0].y), xd[1].x + wet * (p.z - xd[1].x),
-                                     xd[1].y + wet * (p.w - xd[1].y));
+        const float4 o = fx_mix4(make_float4(xd[0].x, xd[0].y, xd[1].x, xd[1].y), p, wet);
         store_pair(d.out, m, M, zero_tail(epilogue4(o, d.pg), m, M));
     }
 }
@@ -7629,36 +7614,13 @@ TD_DEV void mb_matvec_add(const double* P, const double (&o)[kMbWords], double (
     TD_MB_BLOCKS(TD_MB_X)
 #undef TD_MB_X
 }
-// The lanes' run-end states of one channel joined in lane order (eq_lane_scan's shape over 18 planes): TILES ? pwc : pw.  u: lane
-// 0's run started from u_in, the others' from 0.  in: the state entering the lane's run; last: the state after the last lane's.
+// lane_join's operator over one channel's 18 words: the block list of TILES ? pwc : pw (a_tile one tile on)
 template <bool TILES>
-TD_DEV void mb_lane_scan(double (&u)[kMbWords], const MbPowers* pw, const double (&u_in)[kMbWords], double* sv, double (&in)[kMbWords],
-                         double (&last)[kMbWords]) {
-    const uint32_t tid = threadIdx.x;
-#pragma unroll 1
-    for (uint32_t k = 0; k < 8; ++k) {
-        const uint32_t off = 1u << k;
-#pragma unroll
-        for (uint32_t i = 0; i < kMbWords; ++i) sv[i * kThreads + tid] = u[i];
-        __syncthreads();
-        if (tid >= off) {
-            double o[kMbWords];
-#pragma unroll
-            for (uint32_t i = 0; i < kMbWords; ++i) o[i] = sv[i * kThreads + tid - off];
-            mb_matvec_add(TILES ? pw->pwc[k] : pw->pw[k], o, u);
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (uint32_t i = 0; i < kMbWords; ++i) sv[i * kThreads + tid] = u[i];
-    __syncthreads();
-#pragma unroll
-    for (uint32_t i = 0; i < kMbWords; ++i) {
-        in[i] = tid ? sv[i * kThreads + tid - 1] : u_in[i];
-        last[i] = sv[i * kThreads + kThreads - 1];
-    }
-    __syncthreads();
-}
+struct JoinMb {
+    const MbPowers* pw;
+    TD_DEV void operator()(uint32_t k, const double (&o)[kMbWords], double (&u)[kMbWords]) const { mb_matvec_add(TILES ? pw->pwc[k] : pw->pw[k], o, u); }
+    TD_DEV void tile(const double (&o)[kMbWords], double (&u)[kMbWords]) const { mb_matvec_add(pw->a_tile, o, u); }
+};
 // steps 1 and 2 of the compressor on one band's f64 frame (comp_want's order)
 TD_DEV double mb_want(double thr, double slope, double W, double l, double r) {
     const double al = fabs(l), ar = fabs(r);
@@ -7718,10 +7680,10 @@ TD_DEV void mb_start(const double* cy, double (&cl)[kMbWords], double (&cr)[kMbW
 TD_DEV void mb_join(const MbPowers* pw, const double (&cl)[kMbWords], const double (&cr)[kMbWords], double* sv, double (&zl)[kMbWords],
                     double (&zr)[kMbWords]) {
     double in[kMbWords], last[kMbWords];
-    mb_lane_scan<false>(zl, pw, cl, sv, in, last);
+    lane_join(zl, JoinMb<false>{pw}, cl, sv, in, last);
 #pragma unroll
     for (uint32_t i = 0; i < kMbWords; ++i) zl[i] = in[i];
-    mb_lane_scan<false>(zr, pw, cr, sv, in, last);
+    lane_join(zr, JoinMb<false>{pw}, cr, sv, in, last);
 #pragma unroll
     for (uint32_t i = 0; i < kMbWords; ++i) zr[i] = in[i];
 }
@@ -7737,27 +7699,27 @@ __global__ __launch_bounds__(kThreads) void k_mb_local(const MbDesc* __restrict_
     for (uint32_t i = 0; i < kMbWords; ++i) { zero[i] = 0.0; zl[i] = 0.0; zr[i] = 0.0; }
     mb_run_terms(d, c, f0, zl, zr);
     double* a = d.agg + (size_t)blockIdx.x * 2u * kMbWords;
-    mb_lane_scan<false>(zl, d.pow, zero, sv, in, last);
+    lane_join(zl, JoinMb<false>{d.pow}, zero, sv, in, last);
     if (tid == 0) {
 #pragma unroll
         for (uint32_t i = 0; i < kMbWords; i += 2) gstore_d2(a + i, last[i], last[i + 1]);
     }
-    mb_lane_scan<false>(zr, d.pow, zero, sv, in, last);
+    lane_join(zr, JoinMb<false>{d.pow}, zero, sv, in, last);
     if (tid == 0) {
 #pragma unroll
         for (uint32_t i = 0; i < kMbWords; i += 2) gstore_d2(a + kMbWords + i, last[i], last[i + 1]);
     }
 }
-// entry[t + 1] = A^kMbTile entry[t] + total[t] for one channel's 18 words, entry[0] the line's (k_eq_carry's shape: a lane folds
-// `chunk` consecutive tiles, Hillis-Steele over the lanes, a second walk writes the entries).  One workgroup per channel and
-// vertex: grid (2, n_desc).
+// entry[t + 1] = A^kMbTile entry[t] + total[t] for one channel's 18 words, entry[0] the line's.  One workgroup per channel and
+// vertex: grid (2, n_desc).  tile_carry's steps from tile_carry's pieces, written out: the kernel sits at the SGPR limit with 168
+// spills to lanes, and through tile_carry it compiles to 172 and more.
 __global__ __launch_bounds__(kThreads) void k_mb_carry(const MbDesc* __restrict__ descs) {
     const MbDesc& d = descs[blockIdx.y];
     const uint32_t ch = blockIdx.x;
     __shared__ double sv[kMbWords * kThreads];
     const uint32_t tid = threadIdx.x, n = d.n_tiles, c = d.chunk;
     const uint32_t b = tid * c < n ? tid * c : n, e = b + c < n ? b + c : n;
-    const double* P = d.pow->a_tile;
+    const JoinMb<true> op{d.pow};
     double init[kMbWords], u[kMbWords], in[kMbWords], last[kMbWords];
 #pragma unroll
     for (uint32_t i = 0; i < kMbWords; ++i) {
@@ -7765,29 +7727,17 @@ __global__ __launch_bounds__(kThreads) void k_mb_carry(const MbDesc* __restrict_
         u[i] = tid ? 0.0 : init[i];
     }
     for (uint32_t r = b; r < e; ++r) {
-        const double* a = d.agg + ((size_t)r * 2u + ch) * kMbWords;
         double t[kMbWords];
-#pragma unroll
-        for (uint32_t i = 0; i < kMbWords; i += 2) {
-            const d2v w = gload_d2(a + i);
-            t[i] = w.x; t[i + 1] = w.y;
-        }
-        mb_matvec_add(P, u, t);
+        tile_load(d.agg + ((size_t)r * 2u + ch) * kMbWords, t);
+        op.tile(u, t);
 #pragma unroll
         for (uint32_t i = 0; i < kMbWords; ++i) u[i] = t[i];
     }
-    mb_lane_scan<true>(u, d.pow, init, sv, in, last);
+    lane_join(u, op, init, sv, in, last);
     for (uint32_t r = b; r < e; ++r) {
-        const double* a = d.agg + ((size_t)r * 2u + ch) * kMbWords;
-        double* o = d.carry + ((size_t)r * 2u + ch) * kMbWords;
         double t[kMbWords];
-#pragma unroll
-        for (uint32_t i = 0; i < kMbWords; i += 2) {
-            gstore_d2(o + i, in[i], in[i + 1]);
-            const d2v w = gload_d2(a + i);
-            t[i] = w.x; t[i + 1] = w.y;
-        }
-        mb_matvec_add(P, in, t);
+        tile_store_load(d.carry + ((size_t)r * 2u + ch) * kMbWords, in, d.agg + ((size_t)r * 2u + ch) * kMbWords, t);
+        op.tile(in, t);
 #pragma unroll
         for (uint32_t i = 0; i < kMbWords; ++i) in[i] = t[i];
     }
@@ -7940,9 +7890,7 @@ __global__ __launch_bounds__(kThreads) void k_mb_apply(const MbDesc* __restrict_
             }
         }
         const float4 p = make_float4(pl[0], pr[0], pl[1], pr[1]);
-        // the reference's lerp (adsr.rs:42), f32
-        const float4 o = make_float4(x.x + wet * (p.x - x.x), x.y + wet * (p.y - x.y), x.z + wet * (p.z - x.z), x.w + wet * (p.w - x.w));
-        store_pair(d.out, m, M, epilogue4(o, d.pg));
+        store_pair(d.out, m, M, epilogue4(fx_mix4(x, p, wet), d.pg));
     }
 }
 
