@@ -769,6 +769,11 @@ int td_graph_sync(td_graph* g);
  * ran k_norm_fix before returning.  The results are the same either way; nothing in the library traps or waits without
  * bound on work that may not be running.  0 in normal operation. */
 size_t td_graph_norm_fix_runs(const td_graph* g);
+/* (tests, tuning) How many reference blocks the single-pass Normalize launches of this graph (or of the batch it belongs to)
+ * stored a SECOND time since the last call: a tile of the wide sum kernel may scale and store with the earlier tiles' peaks it
+ * can see before it waits for the rest, and stores a block again where the running peak came out differently.  Counted only
+ * while engine option debug.norm has bit 2 or bit 4 set (the launch carries no atomic otherwise); waits for the stream. */
+size_t td_graph_norm_respec(td_graph* g);
 /* HIP-event timing of the launches of the last render, per kernel family (ms).  names/ms are parallel
  * arrays of capacity cap; returns the number of entries. Enabled by td_graph_set_profiling(g, n): n = 1
  * times every render, n > 1 every n-th render only (the events themselves cost a few us per launch), 0 off. */
@@ -830,7 +835,11 @@ size_t td_cached_memory_bytes(void);
  * Test hooks, "debug.<name>" -- not part of the supported surface: each selects an older or alternative form of a launch, or moves
  * a speculation parameter whose outcome the device verifies; value-neutral by construction, and each pinned by the test named:
  *   debug.norm n (bit 0: every single-pass Normalize tile gives up its wait at once -> the check kernel redoes the vertex;
- *     tests/test_gpu_bench_form.py) / debug.spec_normalize 0|1 / debug.single_pass_normalize 0|1 / debug.fuse_normalize 0|1
+ *     tests/test_gpu_bench_form.py; bit 1, timing only, WRONG peaks: the earlier tiles' words are not read at all;
+ *     bit 2: a tile's one look at the earlier tiles' words sees nothing -- it stores with its own peaks and again after the
+ *     wait wherever the running peak came out differently; bit 3: the OTHER order of store and wait than the default -- the
+ *     default order is what the read-only option debug.norm_early_store reports (1: store first; kSpecEpilogueDefault); bit 4: count the
+ *     blocks stored twice, td_graph_norm_respec, as bit 2 does; tests/test_gpu_sum_spec_epilogue.py) / debug.spec_normalize 0|1 / debug.single_pass_normalize 0|1 / debug.fuse_normalize 0|1
  *     (the two-launch Normalize forms; tests/test_gpu_spec_normalize.py, test_gpu_band_scan.py) /
  *   debug.sum_groups n (0: automatic; n: the wide packed sum in its ragged form on a grid of n workgroups, each carrying 4 .. 16
  *     quads of 256 frames -- a render whose timeline n cannot carry that way fails; tests/test_gpu_sum_ragged.py) /

@@ -125,6 +125,7 @@ SIGNATURES = {
     "td_graph_render_all_async": (_sz, [_vp, _vp, _vp, _sz, _i32]),
     "td_graph_sync": (_i32, [_vp]),
     "td_graph_norm_fix_runs": (_sz, [_vp]),
+    "td_graph_norm_respec": (_sz, [_vp]),
     "td_graph_set_profiling": (None, [_vp, _i32]),
     "td_graph_host_times": (_sz, [_vp, C.POINTER(C.c_double), _i32]),
     "td_graph_last_kernel_times": (_sz, [_vp, C.POINTER(_cp), _fp, C.POINTER(_sz), _sz]),
@@ -233,6 +234,8 @@ def lib():
             raise TermdawError("%s is missing; there is no CPU fallback" % (_LIB_OVERRIDE or LIB_PATH))
         L = C.CDLL(_LIB_OVERRIDE or LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
+            if _LIB_OVERRIDE and name == "td_graph_norm_respec" and not hasattr(L, name):
+                continue   # (A/B runs against a library built before the counter existed)
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -828,6 +831,11 @@ class Graph:
     def norm_fix_runs(self):
         """How often a single-pass Normalize launch was redone by the check kernel after the fact (0 in normal operation)."""
         return lib().td_graph_norm_fix_runs(self.h)
+
+    def norm_respec(self):
+        """Blocks the single-pass Normalize launches stored a second time since the last call (counted only with engine option
+        debug.norm bit 2 or bit 4 set; include/termdaw_amd.h)."""
+        return lib().td_graph_norm_respec(self.h)
 
     def host_times(self, reset=True):
         """Host ms per phase since the last reset: compile, descriptors, upload, launches; and chunk count."""

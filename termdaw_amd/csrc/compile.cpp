@@ -1769,7 +1769,7 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                             if (!out_f32) x.out = nullptr;
                         }
                         x.term_mode = term_mode[vi];
-                        x.debug = (uint32_t)g->norm_debug;
+                        x.debug = ((uint32_t)g->norm_debug & 15u) ^ (g->norm_early_store ? 0u : 8u);   // (bit 3 of the option: the OTHER order of store and wait)
                         x.pg = presum ? PanGain{1.0f, 1.0f, 1.0f, 0u} : make_pg(v.gain, v.angle);
                         if (presum && band_plan[vi].Wq) {   // block responses for the warm-up guess
                             BandPlan& bp = band_plan[vi];
@@ -1803,6 +1803,7 @@ int compile_chunk(td_graph* g, const td_samplebank* sb, const td_flowwbank* fb,
                                 cb.esync_fix.push_back({o + offsetof(SumDesc, sync), cb.esync_bytes});
                                 cb.esync_bytes += (2 * nb * 8 + 63) & ~(size_t)63;
                                 cb.flag_fix.push_back(o + offsetof(SumDesc, host_flag));
+                                if (g->norm_debug & (4 | 16)) cb.respec_fix.push_back(o + offsetof(SumDesc, respec));
                             }
                             cb.scratch_field(o, offsetof(SumDesc, peaks), pk);
                             if (ragged_of.count(vs[i])) cb.scratch_field(o, offsetof(SumDesc, peaks2), pk + nb * sizeof(float));

@@ -693,6 +693,10 @@ static int ensure_arena(Arena& ar, size_t bytes, hipStream_t stream) {
         *ar.h_flag = 0u;
         TD_HIP(hipHostGetDevicePointer((void**)&ar.d_flag, ar.h_flag, 0));
     }
+    if (!ar.d_respec) {
+        TD_HIP(hipMalloc((void**)&ar.d_respec, 256));
+        TD_HIP(hipMemset(ar.d_respec, 0, 256));
+    }
     if (bytes <= ar.cap) return 1;
     const size_t cap = std::max<size_t>(bytes * 2, 1 << 20);
     if (stream && !settle_arena(ar, stream)) return 0;   // (a pending fix reads descriptors in the buffer about to go)
@@ -719,6 +723,7 @@ static void free_arena(Arena& ar) {
     if (ar.d) (void)hipFree(ar.d);
     if (ar.copied) (void)hipEventDestroy(ar.copied);
     if (ar.h_flag) (void)hipHostFree(ar.h_flag);
+    if (ar.d_respec) (void)hipFree(ar.d_respec);
     ar = Arena{};
 }
 
@@ -824,6 +829,10 @@ static int submit_chunk(Arena& ar, ChunkBuild& cb, hipStream_t stream, ProfCtx& 
     }
     for (size_t at : cb.flag_fix) {
         uint64_t p = (uint64_t)(uintptr_t)ar.d_flag;
+        memcpy(&st.b[at], &p, 8);
+    }
+    for (size_t at : cb.respec_fix) {
+        uint64_t p = (uint64_t)(uintptr_t)ar.d_respec;
         memcpy(&st.b[at], &p, 8);
     }
     for (auto& f : cb.table_fix) {
@@ -2378,6 +2387,17 @@ size_t td_graph_render_all_async(td_graph* g, const td_samplebank* sb, td_flowwb
     return n_blocks * g->bl;
 }
 int td_graph_sync(td_graph* g) { return drain(g); }
+size_t td_graph_norm_respec(td_graph* g) {
+    if (!g->stream || !drain(g)) return 0;
+    size_t n = 0;
+    for (Arena* ar : {&g->arena, g->batch ? &g->batch->arena : (Arena*)nullptr}) {
+        if (!ar || !ar->d_respec) continue;
+        uint32_t v = 0;
+        if (hipMemcpy(&v, ar->d_respec, 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemset(ar->d_respec, 0, 4) != hipSuccess) return 0;
+        n += v;
+    }
+    return n;
+}
 size_t td_graph_norm_fix_runs(const td_graph* g) { return g->arena.fix_runs + (g->batch ? g->batch->arena.fix_runs : 0); }
 size_t td_graph_render_all(td_graph* g, const td_samplebank* sb, td_flowwbank* fb, size_t n_blocks, int bits) {
     const size_t n = td_graph_render_all_async(g, sb, fb, n_blocks, bits);
@@ -3010,13 +3030,14 @@ static std::vector<OptionRef> option_table(td_graph* g) {
         {"debug.reverb_form", 2, &g->reverb_form}, {"debug.reverb_block", 2, &g->reverb_block},
         {"debug.band_quick", 2, &g->band_quick}, {"debug.band_short", 2, &g->band_short}, {"debug.band_medium", 2, &g->band_medium},
         {"debug.band_warmup", 2, &g->band_warmup}, {"debug.band_depth", 2, &g->band_depth},
-        {"debug.stem_taps", 2, &g->stem_taps},
+        {"debug.stem_taps", 2, &g->stem_taps}, {"debug.norm_early_store", 0, &g->norm_early_store},
     };
 }
 int td_graph_set_option(td_graph* g, const char* key, long value) {
     const std::string k = key ? key : "";
     // (keys with a rule of their own first)
     if (k == "debug.stem_taps") return fail("td_graph_set_option: debug.stem_taps is read-only");
+    if (k == "debug.norm_early_store") return fail("td_graph_set_option: debug.norm_early_store is read-only (debug.norm bit 3 selects the other order)");
     if (k == "band_mode") {   // 0: exact (default, the parity mode), 1: blocked affine scan (tolerance class), 2: the scan under the guard
         if (value != 0 && value != 1 && value != 2) return fail("band_mode must be 0 (exact), 1 (scan) or 2 (guarded scan)");
         if (g->guard.armed && !drain(g)) return 0;   // (a verdict still out belongs to the mode it was rendered in)

@@ -272,6 +272,7 @@ struct Arena {
     // its device address); settle_arena() looks at the word once the stream has drained and launches these then.
     uint32_t* h_flag = nullptr;
     uint32_t* d_flag = nullptr;
+    uint32_t* d_respec = nullptr;   // device word: blocks a single-pass Normalize launch stored twice (SumDesc::respec, td_graph_norm_respec)
     struct PendingFix { size_t off; int n; uint32_t M, bl; };
     std::vector<PendingFix> pending_fix;
     size_t fix_runs = 0;       // how often that happened (td_graph_norm_fix_runs)
@@ -329,6 +330,7 @@ struct ChunkBuild {
     size_t esync_bytes = 0;
     std::vector<Fix> esync_fix;
     std::vector<size_t> flag_fix;   // pointer fields -> the arena's host-visible word (SumDesc::host_flag)
+    std::vector<size_t> respec_fix; // pointer fields -> the arena's count of blocks stored twice (SumDesc::respec; debug.norm bits 2 / 4 only)
     std::vector<Launch> launches;
     size_t n_graphs = 0;
     bool one_grid_sources = true;   // every graph compiled in has engine option "one_grid_sources" set (submit_chunk: k_sources)
@@ -349,6 +351,7 @@ struct ChunkBuild {
         esync_bytes = 0;
         esync_fix.clear();
         flag_fix.clear();
+        respec_fix.clear();
         launches.clear();
         n_graphs = 0;
         one_grid_sources = true;
@@ -496,7 +499,8 @@ struct td_graph {
     bool fuse_normalize = true;                // band_mode 1: a Normalize vertex right behind a scan launch is evaluated by that launch (BandScanDesc::norm)
     bool single_pass_normalize = true;         // fresh renders of wide all-loop sums find the running peak inside the sum launch (SumDesc mode 4)
     unsigned sum_groups = 0;                   // (tests, A/B runs) debug.sum_groups: workgroups of the ragged packed sum's grid; 0 = automatic
-    int norm_debug = 0;                        // (tests) bit 0: every single-pass Normalize tile gives up its wait at once -> k_norm_fix
+    int norm_debug = 0;                        // (tests) bit 0: every single-pass Normalize tile gives up its wait at once -> k_norm_fix; bits 1 .. 4: SumDesc::debug, include/termdaw_amd.h
+    bool norm_early_store = tdk::kSpecEpilogueDefault;   // (read-only, "debug.norm_early_store") the wide sum's single-pass Normalize tiles store before they wait, unless debug.norm bit 3
     bool defer_fix = true;                     // (set per render) this render is one chunk: the output vertex' k_norm_fix may wait for settle()
     float band_live_thr = 1e-9f;               // energy from before the short window / energy inside it below which it is enough
     unsigned band_depth = 100;                 // the guess chains block responses until (1 - gamma)^(256 K) <= e^-band_depth

@@ -106,6 +106,10 @@ struct SumDesc {
     uint32_t term_mode;        // TermMode: lets the kernel pick a loop specialised for the term kinds
     uint32_t debug;            // (tests) bit 0: every wait for an earlier tile's granule gives up at once -> violated -> k_norm_fix;
                                // bit 1 (k_sum16w, timing experiments only -- WRONG results): the earlier tiles' words are not read at all
+                               // bit 2 (k_sum16w): a tile's one look at the earlier tiles' words sees nothing -- it stores with the running
+                               //    peak of its own blocks, waits, and stores again every block whose running peak came out differently
+                               // bit 3 (k_sum16w): a tile does NOT store before its wait (the engine sets it unless the early store is
+                               //    asked for: kSpecEpilogueDefault, engine option debug.norm bit 3)
     PanGain pg;
     // mode 2: a second copy of the raw sum, planar within every aligned 4-frame block --
     // {l0 l1 l2 l3}{r0 r1 r2 r3} instead of {l0 r0 l1 r1}{l2 r2 l3 r3} -- the form k_band_spec's warm-up
@@ -128,7 +132,14 @@ struct SumDesc {
     // where that is the same workgroup): complete in memory when the launch ends, whatever a wait did.  nullptr: every
     // other form (k_norm_fix folds the two where it is set).
     float* peaks2;
+    // modes 4 / 5, k_sum16w: a device word that counts the blocks stored a second time (the early store's running peak did not
+    // hold).  nullptr -- no atomic in the launch -- unless engine option debug.norm has bit 2 or bit 4 (td_graph_norm_respec).
+    uint32_t* respec;
 };
+// k_sum16w's modes 4 / 5: does a tile scale and store with the lower tiles' peaks it can see BEFORE it waits for the rest (and
+// again where that guess did not hold)?  Engine option debug.norm bit 3 selects the other order.  Measured on the headline
+// (docs/EXPERIMENTS.md 000000) -- the gain has to clear ten times the parent's run-to-run spread to become the default.
+constexpr bool kSpecEpilogueDefault = false;
 
 // Normalize pass B: running max over the block peaks (`*max = buf_max.max(*max)`), buf.scale(len, 1.0 / max)
 // (extensions.rs:323-328), epilogue, optional fused quantise.  Every workgroup derives the running max of

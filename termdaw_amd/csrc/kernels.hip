@@ -13,6 +13,7 @@
 #include "kernels.h"
 #include "sum_partition.h"
 #include "sum_index.h"
+#include "sum_runmax.h"
 
 #include <algorithm>
 
@@ -162,10 +163,11 @@ TD_DEV void raise_violated(NormState* st, uint32_t* host_flag) {
 // The granules of ALL tiles below `n`, a workgroup's threads striding over them: f(index, value) for each; false when one
 // did not show within `limit` polls.  Four loads per thread are in flight before the first is looked at -- a thread's
 // granules, one dependent round trip after the other, were 2 - 3 us of every launch that ends in such a gather.
+// (`first`: where the thread starts -- its own index, or what look_lower_granules returned: the words it has still to wait for)
 template <typename F>
-TD_DEV bool for_lower_granules(const unsigned long long* sync, uint32_t n, uint32_t limit, F f, uint32_t tag = 1u) {
+TD_DEV bool for_lower_granules_from(const unsigned long long* sync, uint32_t first, uint32_t n, uint32_t limit, F f, uint32_t tag) {
     bool ok = true;
-    for (uint32_t base = threadIdx.x; base < n; base += 4u * (uint32_t)kThreads) {
+    for (uint32_t base = first; base < n; base += 4u * (uint32_t)kThreads) {
         unsigned long long g[4];
 #pragma unroll
         for (uint32_t u = 0; u < 4u; ++u) {
@@ -185,6 +187,32 @@ TD_DEV bool for_lower_granules(const unsigned long long* sync, uint32_t n, uint3
         }
     }
     return ok;
+}
+template <typename F>
+TD_DEV bool for_lower_granules(const unsigned long long* sync, uint32_t n, uint32_t limit, F f, uint32_t tag = 1u) {
+    return for_lower_granules_from(sync, threadIdx.x, n, limit, f, tag);
+}
+// ONE look at the same words, no waiting: f(index, value) for every granule that is there.  Returns where the thread's first
+// missing word lies (for_lower_granules_from's `first`: the wait begins there), 0xFFFFFFFF when it saw all of them.
+template <typename F>
+TD_DEV uint32_t look_lower_granules(const unsigned long long* sync, uint32_t n, F f, uint32_t tag) {
+    uint32_t first_missing = 0xFFFFFFFFu;
+    for (uint32_t base = threadIdx.x; base < n; base += 4u * (uint32_t)kThreads) {
+        unsigned long long g[4];
+#pragma unroll
+        for (uint32_t u = 0; u < 4u; ++u) {
+            const uint32_t idx = base + u * (uint32_t)kThreads;
+            g[u] = idx < n ? granule_load(sync + idx) : 0ull;
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < 4u; ++u) {
+            const uint32_t idx = base + u * (uint32_t)kThreads;
+            if (idx >= n) continue;
+            if ((uint32_t)(g[u] >> 32) == tag) f(idx, (uint32_t)g[u]);
+            else first_missing = min(first_missing, base);
+        }
+    }
+    return first_missing;
 }
 
 // ... the same over two granule arrays at once: f(index, value_a, value_b)
@@ -796,6 +824,16 @@ __global__ __launch_bounds__(kThreads) void k_sum16w(const SumDesc* __restrict__
 #pragma unroll
     for (int q = 0; q < 2 * NQ; ++q) if (pair_frame<SH>(m, q) < M) pk = absmax4(pk, a[q]);
     float spec_init = 0.0f;
+    // (modes 3 / 4 / 5 store out of the registers, below: with which scale, whether now, and whether a wait is still to come)
+    constexpr uint32_t wpb = 4 / NQ;   // waves per reference block
+    const uint32_t wave = threadIdx.x >> 6, my_block = wave / wpb;
+    __shared__ float wm4[kThreads / 64], pm4[kThreads / 64], pm4f[kThreads / 64];
+    __shared__ uint32_t bad4, miss4;
+    float pb[NQ], pm = 0.0f, r_store = 0.0f, run_stored = 0.0f;
+    uint32_t first_missing = 0xFFFFFFFFu;
+    bool forced = false, store_now = false, pending = false;
+#pragma unroll
+    for (int b = 0; b < NQ; ++b) pb[b] = 0.0f;
     if (d.mode >= 4) {
         // Single-pass RUNNING-PEAK normalize (fresh renders: `*max = buf_max.max(*max)` block by block, extensions.rs:321-329)
         // for a grid that is resident at once: the tile's block peaks first, the tile's maximum published as one granule,
@@ -808,15 +846,11 @@ __global__ __launch_bounds__(kThreads) void k_sum16w(const SumDesc* __restrict__
         // right behind this one where anything in the submission reads the vertex' output, and otherwise only when the
         // host-visible word says so (settle(), engine.cpp): nothing in here can trap or hang.
         const float init = spec_init_early;
-        __shared__ float wm4[kThreads / 64], pm4[kThreads / 64];
-        __shared__ uint32_t bad4;
-        const uint32_t wave = threadIdx.x >> 6;
         const float pw = wave_max(pk);
         if ((threadIdx.x & 63) == 0) wm4[wave] = pw;
-        if (threadIdx.x == 0) bad4 = 0u;
+        if (threadIdx.x == 0) { bad4 = 0u; miss4 = 0u; }
         __syncthreads();
-        constexpr uint32_t wpb = 4 / NQ;   // waves per reference block
-        float pb[NQ], T = 0.0f;
+        float T = 0.0f;
 #pragma unroll
         for (int b = 0; b < NQ; ++b) {
             float p = wm4[b * wpb];
@@ -833,64 +867,96 @@ __global__ __launch_bounds__(kThreads) void k_sum16w(const SumDesc* __restrict__
             asm volatile("" ::"v"(init));   // (the carried max has been READ before this tile counts as published: the last tile replaces it)
             granule_store(sync + blockIdx.x, __float_as_uint(T), tag);
         }
-        float pm = 0.0f;
-        const bool forced = (d.debug & 1u) != 0u && blockIdx.x != 0u;   // (tests: every wait gives up at once)
-        const bool ok = (d.debug & 2u) ? true : !forced && for_lower_granules(sync, blockIdx.x, kScanSpinLimitSum,
-                                                      [&pm](uint32_t, uint32_t v) { pm = fmaxf(pm, __uint_as_float(v)); }, tag);
-        pm = wave_max(pm);
-        if ((threadIdx.x & 63) == 0) pm4[wave] = pm;
-        if (!ok) bad4 = 1u;
+        // The tile does not wait before it acts (debug bit 3 clear).  Block b is scaled by 1 / run_b, and run_b changes only if a
+        // lower tile that has NOT yet published is louder than everything the tile can already see: ONE look at the lower
+        // words, the fold from what is there, and the tile scales, quantises and stores with that -- from copies, a[] stays the
+        // raw sum.  Only then does it wait (bounded, as before) for the words that were missing; a block whose final running
+        // peak is the float it was stored with has the reference's bytes in memory already, any other is scaled and stored
+        // again by the lanes that stored it.  The wait leaves the critical path of every tile whose guess held; a tile that
+        // gives up leaves whatever it stored to k_norm_fix, which overwrites it.
+        // (debug bit 2: the look sees nothing -- every tile guesses from its own peaks; bit 1, timing only: no word is read at all)
+        forced = (d.debug & 1u) != 0u && blockIdx.x != 0u;   // (tests: every wait gives up at once)
+        const bool nospec = (d.debug & 8u) != 0u;
+        if (!(d.debug & (2u | 4u | 8u)))
+            first_missing = look_lower_granules(sync, blockIdx.x, [&pm](uint32_t, uint32_t v) { pm = fmaxf(pm, __uint_as_float(v)); }, tag);
+        else if (!(d.debug & 2u)) first_missing = threadIdx.x;   // (nothing seen: the wait covers every lower word)
+        const float pms = wave_max(pm);
+        if ((threadIdx.x & 63) == 0) pm4[wave] = pms;
+        if (first_missing < blockIdx.x) miss4 = 1u;
         __syncthreads();
-        float run = fmaxf(fmaxf(fmaxf(pm4[0], pm4[1]), fmaxf(pm4[2], pm4[3])), init);   // max_{b-1} entering the tile
-        float r_mine = 0.0f;
-        const uint32_t my_block = wave / wpb;
-#pragma unroll
-        for (int b = 0; b < NQ; ++b) {
-            run = fmaxf(pb[b], run);   // *max = buf_max.max(*max)
-            if ((uint32_t)b == my_block) r_mine = 1.0f / run;
-        }
-        if (threadIdx.x == 0) {
+        pending = miss4 != 0u;   // (uniform over the workgroup)
+        float run_spec[NQ];
+        const float leaving = tdrm::fold<NQ>(tdrm::entering(init, fmaxf(fmaxf(pm4[0], pm4[1]), fmaxf(pm4[2], pm4[3]))), pb, run_spec);
+        run_stored = tdrm::of_block<NQ>(run_spec, my_block);
+        r_store = 1.0f / run_stored;
+        store_now = !(nospec && pending);
+        if (!pending && threadIdx.x == 0) {   // the look saw every lower tile: the guess is the result
             NormState* st = const_cast<NormState*>(d.state);
-            if (bad4) raise_violated(st, d.host_flag);
-            else if (blockIdx.x == gridDim.x - 1u) st->max = run;   // (every earlier tile has read the old value: see above)
+            if (forced) raise_violated(st, d.host_flag);
+            else if (blockIdx.x == gridDim.x - 1u) st->max = leaving;   // (every earlier tile has read the old value: see above)
         }
-        spec_init = -1.0f;   // (no speculation to check below)
-#pragma unroll
-        for (int q = 0; q < 2 * NQ; ++q) a[q] = epilogue4(make_float4(a[q].x * r_mine, a[q].y * r_mine, a[q].z * r_mine, a[q].w * r_mine), d.pg);
+        spec_init = -1.0f;   // (no speculation of mode 3's kind to check below)
     }
     if (d.mode == 3) {   // speculative single-pass normalize (see SumDesc): scaled, finished frames out of registers
         spec_init = d.use_init ? d.init_max : d.state->max;
-        const float r = 1.0f / spec_init;
-#pragma unroll
-        for (int q = 0; q < 2 * NQ; ++q) a[q] = epilogue4(make_float4(a[q].x * r, a[q].y * r, a[q].z * r, a[q].w * r), d.pg);
+        r_store = 1.0f / spec_init;
+        store_now = true;
     }
     if (d.mode >= 3) {
-        if (d.out) {   // (nullptr: nobody reads the f32 form of this output vertex -- engine option "output_f32" 0)
+        for (;;) {
+            if (store_now) {
+                // scale, pan / gain, quantise, store -- from copies of the raw sums
 #pragma unroll
-            for (int q = 0; q < 2 * NQ; ++q) store_pair(d.out, pair_frame<SH>(m, q), M, a[q]);
-        }
-        if (d.qmode == 1u) {
-            // int16 PCM: the lane's 4 * NQ frames are 16 * NQ contiguous bytes -> one 16-byte store per 4 frames
-            uint32_t* o = reinterpret_cast<uint32_t*>(d.pcm);
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) {
-                const uint32_t mm = quad_frame<SH>(m, q);
-                if (mm + 3u < M) {
-                    const float4 v0 = a[2 * q], v1 = a[2 * q + 1];
-                    u4v w;
-                    w.x = ((uint32_t)quant16(v0.x, d.amplitude) & 0xFFFFu) | ((uint32_t)quant16(v0.y, d.amplitude) << 16);
-                    w.y = ((uint32_t)quant16(v0.z, d.amplitude) & 0xFFFFu) | ((uint32_t)quant16(v0.w, d.amplitude) << 16);
-                    w.z = ((uint32_t)quant16(v1.x, d.amplitude) & 0xFFFFu) | ((uint32_t)quant16(v1.y, d.amplitude) << 16);
-                    w.w = ((uint32_t)quant16(v1.z, d.amplitude) & 0xFFFFu) | ((uint32_t)quant16(v1.w, d.amplitude) << 16);
-                    *reinterpret_cast<u4v TD_GLOBAL*>((TD_GLOBAL char*)(o + mm)) = w;
-                } else {
-                    store_quant_pair(d.pcm, 1u, mm, M, a[2 * q], d.amplitude);
-                    store_quant_pair(d.pcm, 1u, mm + 2u, M, a[2 * q + 1], d.amplitude);
+                for (int q = 0; q < NQ; ++q) {
+                    const float4 s0 = a[2 * q], s1 = a[2 * q + 1];
+                    const float4 v0 = epilogue4(make_float4(s0.x * r_store, s0.y * r_store, s0.z * r_store, s0.w * r_store), d.pg);
+                    const float4 v1 = epilogue4(make_float4(s1.x * r_store, s1.y * r_store, s1.z * r_store, s1.w * r_store), d.pg);
+                    const uint32_t mm = quad_frame<SH>(m, q);
+                    if (d.out) {   // (nullptr: nobody reads the f32 form of this output vertex -- engine option "output_f32" 0)
+                        store_pair(d.out, mm, M, v0);
+                        store_pair(d.out, mm + 2u, M, v1);
+                    }
+                    if (d.qmode == 1u && mm + 3u < M) {
+                        // int16 PCM: the lane's 4 frames are 16 contiguous bytes -> one 16-byte store
+                        uint32_t* o = reinterpret_cast<uint32_t*>(d.pcm);
+                        u4v w;
+                        w.x = ((uint32_t)quant16(v0.x, d.amplitude) & 0xFFFFu) | ((uint32_t)quant16(v0.y, d.amplitude) << 16);
+                        w.y = ((uint32_t)quant16(v0.z, d.amplitude) & 0xFFFFu) | ((uint32_t)quant16(v0.w, d.amplitude) << 16);
+                        w.z = ((uint32_t)quant16(v1.x, d.amplitude) & 0xFFFFu) | ((uint32_t)quant16(v1.y, d.amplitude) << 16);
+                        w.w = ((uint32_t)quant16(v1.z, d.amplitude) & 0xFFFFu) | ((uint32_t)quant16(v1.w, d.amplitude) << 16);
+                        *reinterpret_cast<u4v TD_GLOBAL*>((TD_GLOBAL char*)(o + mm)) = w;
+                    } else if (d.qmode) {
+                        store_quant_pair(d.pcm, d.qmode, mm, M, v0, d.amplitude);
+                        store_quant_pair(d.pcm, d.qmode, mm + 2u, M, v1, d.amplitude);
+                    }
                 }
             }
-        } else if (d.qmode) {
-#pragma unroll
-            for (int q = 0; q < 2 * NQ; ++q) store_quant_pair(d.pcm, d.qmode, pair_frame<SH>(m, q), M, a[q], d.amplitude);
+            if (!pending) break;
+            // ---- the bounded wait for the lower words the look did not find, and the final fold
+            pending = false;
+            const bool ok = for_lower_granules_from(d.sync, first_missing, blockIdx.x, forced ? 0u : kScanSpinLimitSum,
+                                                    [&pm](uint32_t, uint32_t v) { pm = fmaxf(pm, __uint_as_float(v)); }, tag);
+            const float pmf = wave_max(pm);
+            if ((threadIdx.x & 63) == 0) pm4f[wave] = pmf;
+            if (!ok || forced) bad4 = 1u;
+            __syncthreads();
+            float run_final[NQ];
+            const float leaving = tdrm::fold<NQ>(tdrm::entering(spec_init_early, fmaxf(fmaxf(pm4f[0], pm4f[1]), fmaxf(pm4f[2], pm4f[3]))), pb, run_final);
+            if (threadIdx.x == 0) {
+                NormState* st = const_cast<NormState*>(d.state);
+                if (bad4) raise_violated(st, d.host_flag);
+                else if (blockIdx.x == gridDim.x - 1u) st->max = leaving;   // (every earlier tile has read the old value: see above)
+            }
+            const float run_mine = tdrm::of_block<NQ>(run_final, my_block);
+            const bool stored = store_now;   // (false: debug bit 3, nothing is in memory yet)
+            store_now = !stored || tdrm::differs(run_stored, run_mine);   // (uniform over the wave: its quads are one block's)
+            if (!store_now) break;
+            if (stored) {
+                // a lane rewrites only addresses it wrote itself: its first stores have landed before the second ones leave
+                __builtin_amdgcn_s_waitcnt(0);
+                if (d.respec && (threadIdx.x & (64u * wpb - 1u)) == 0u && (blockIdx.x * NQ + my_block) * kTileFrames < M) atomicAdd(d.respec, 1u);
+            }
+            r_store = 1.0f / run_mine;
         }
     } else {
 #pragma unroll
