@@ -29,6 +29,10 @@ inline void params(size_t sr, int /*voices*/, float delay_ms, float depth_ms, fl
     out[5] = kHch;
 }
 
+inline const char* const* shape_names() {   // (the script line's names of an LFO's shape, TD_CHORUS_* in order: the phaser's and the filter's too)
+    static const char* const n[2] = {"sine", "triangle"};
+    return n;
+}
 // nullptr, or what is wrong: the message names the parameter (a NaN fails every comparison)
 inline const char* check(size_t sr, int voices, float delay_ms, float depth_ms, float rate_hz, float stereo, int shape) {
     if (!(voices >= 1 && voices <= kMaxVoices)) return "voices must be 1 .. 4";

@@ -102,7 +102,10 @@ struct FxLevel {
 };
 
 // One row per effect kind (the table: compile_fx.cpp), in the order of their families in `Family` -- the order a level launches them
-// in.  Everything the compiler AND the engine know of a kind beyond its vertex' parameter fields (engine.cpp td_graph_add_*).
+// in.  Everything the compiler, the engine AND the project front end know of a kind: a new kind is a row, its parameter block
+// (fx_params.h) and its functions, and td_graph_add_* / td_*_params in the public header.  The row's second half is the kind as the
+// front ends see it: its script line `script`(name, gain, angle, wet, params ...), the parameters' schema in that order -- from
+// which project.cpp binds, checks and dumps the line -- and what adding a vertex does beyond storing the block (engine.cpp add_fx).
 constexpr double kNoStaticGain = -1.0;   // FxKind::through: no estimate is carried through this vertex
 struct FxKind {
     Kind kind;
@@ -124,7 +127,18 @@ struct FxKind {
     bool built;               // the weak launch_* entry points of the kind are linked
     bool keyed_built;         // ... and those of its keyed forms (true where there are none beyond `built`)
     const char* keyed_name;   // as in "this build has no keyed <keyed_name> kernels"
-    void (*rest)(const td_graph* g, const Vertex& v, StateSlot* run);   // the state at time 0 into the vertex' slots; nullptr: all-zero bytes
+    void (*rest)(const td_graph* g, const Vertex& v, StateSlot* run);   // the state at time 0 into the vertex' slots; nullptr: all-zero bytes (put at add too: the gate's, closed, depends on the parameters)
+    const char* script;       // the script line's function, "add_<kind>"
+    const char* script_prefix;   // in front of a reason at the script line: "add_<kind>: " (two kinds name themselves twice)
+    const FxParam* params;    // the line's arguments behind wet, in its order
+    int n_params;
+    // the parameters at rate sr: nullptr, or the reason without a prefix.  rate_free: only the ranges that do not depend on the rate
+    const char* (*check)(size_t sr, const FxParams& p, bool rate_free);
+    // what of `check` the script line is held to, where its number is known (the rest fails when the graph is built): the
+    // compressor's nothing, the EQ's and the delay's the rate-free ranges, every later kind's all of it at the project's rate
+    enum LineCheck { LINE_NONE, LINE_RATE_FREE, LINE_FULL } line_check;
+    bool starts_pending;      // a vertex is added with Vertex::first_pending set: its line, once it exists, is read only where the vertex itself has written it
+    void (*settle)(FxParams& p);   // the block as the vertex keeps it (the EQ's: no gain_db on a kind without gain); nullptr: as given
     int family_of(const Vertex& v) const { return family ? family(v) : first_family; }
     void put_rest(const td_graph* g, const Vertex& v, StateSlot* run) const {
         memset(run, 0, (size_t)state_slots * sizeof(StateSlot));
@@ -134,7 +148,11 @@ struct FxKind {
 const FxKind* fx_kind(Kind k);          // nullptr: not an effect kind
 const FxKind* fx_of_family(int fam);    // nullptr: not an effect kind's family (one array read: submit_chunk asks per launch)
 
-// ---- engine.cpp: the device memory the compiler hands out addresses of ----
+// ---- engine.cpp ----
+// An effect vertex of kind `k` with the block `p` (sample_index: a convolution's response): what every td_graph_add_<kind> and the
+// project's replay come down to.  0: `p` fails the kind's check, g_error names the kind and the parameter.
+int add_fx(td_graph* g, Kind k, const char* name, float gain, float angle, float wet, const FxParams& p, size_t sample_index = 0);
+// ... the device memory the compiler hands out addresses of
 int upload_tables(td_graph* g, TableCache& tc, const Staging& tmp);   // a vertex' event tables -> its device buffer (queued on the graph's stream)
 int ensure_buffers(td_graph* g, size_t frames);                      // the edge-buffer pool holds buffers of >= frames frames; all of them free
 void* take_line(td_graph* g, tde::Vertex& v, size_t bytes);   // the block a delay, saturator, chorus, reverb, vocoder, limiter or multiband vertex carries (Vertex::line), allocated on first use (nullptr: out of device memory)

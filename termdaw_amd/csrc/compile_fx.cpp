@@ -1,11 +1,14 @@
 // compile_fx.cpp -- the effect kinds of the host compiler (compile.h FxKind / FxLevel): compressor, EQ, delay, saturator,
 // chorus, reverb, gate, phaser, vocoder, filter, limiter, multiband, convolution.  One table row per kind -- its chunk limit, the family its launches start at, the factor the guard
 // carries an estimate through it at, the state slots it carries and their state at time 0, whether it takes a key, whether its
-// kernels are linked -- one function per kind that lowers a level's vertices of that kind to descriptors and launches, and right
+// kernels are linked; and the kind as the front ends see it: its script line, the schema of its parameters (fx_params.h), their
+// check, how much of the check the script line is held to and what adding a vertex does beyond storing the block -- one function per
+// kind that lowers a level's vertices of that kind to descriptors and launches, and right
 // behind it the one that decodes such a launch and calls the kernels' entry points (kernels.h launch_*: the only calls out of the
-// host compiler; no HIP call of its own, like compile.cpp).  compile_chunk and engine.cpp enumerate the kinds through the table
-// only.  Not an object of its own: compile.cpp includes this file at its end, so no build list changes with it.
+// host compiler; no HIP call of its own, like compile.cpp).  compile_chunk, engine.cpp and project.cpp enumerate the kinds through
+// the table only.  Not an object of its own: compile.cpp includes this file at its end, so no build list changes with it.
 #include "chorus_math.h"
+#include "comp_math.h"
 #include "compile.h"
 #include "conv_math.h"
 #include "delay_math.h"
@@ -66,12 +69,12 @@ static int lower_comp(FxLevel& L, std::vector<size_t>& vs) {
         if (L.key_off.count(vi)) L.key_fields(x, vi);
         x.state = &g->dstate[v.state_slot].comp;
         x.n_tiles = n_tiles;
-        x.thr = (double)v.threshold_db;
-        x.slope = 1.0 - 1.0 / (double)v.ratio;
-        x.knee = (double)v.knee_db;
-        x.makeup = (double)v.makeup_db;
-        x.aR = exp(-1.0 / ((double)v.release_ms * (double)sr / 1000.0));
-        x.aA = v.attack_ms > 0.0f ? exp(-1.0 / ((double)v.attack_ms * (double)sr / 1000.0)) : 0.0;
+        x.thr = (double)v.fx.comp.threshold_db;
+        x.slope = 1.0 - 1.0 / (double)v.fx.comp.ratio;
+        x.knee = (double)v.fx.comp.knee_db;
+        x.makeup = (double)v.fx.comp.makeup_db;
+        x.aR = exp(-1.0 / ((double)v.fx.comp.release_ms * (double)sr / 1000.0));
+        x.aA = v.fx.comp.attack_ms > 0.0f ? exp(-1.0 / ((double)v.fx.comp.attack_ms * (double)sr / 1000.0)) : 0.0;
         x.oA = 1.0 - x.aA;
         MasterDesc y1{}, yl{};
         y1.n_tiles = yl.n_tiles = n_tiles;
@@ -148,7 +151,7 @@ static int lower_eq(FxLevel& L, std::vector<size_t>& vs) {
         x.n_tiles = n_tiles;
         x.chunk = chunk;
         double c[5];
-        eq::coefficients(v.eq_kind, L.sr, v.eq_freq, v.eq_q, v.eq_gain_db, c);
+        eq::coefficients(v.fx.eq.kind, L.sr, v.fx.eq.freq_hz, v.fx.eq.q, v.fx.eq.gain_db, c);
         x.b0 = c[0]; x.b1 = c[1]; x.b2 = c[2]; x.a1 = c[3]; x.a2 = c[4];
         x.c0 = x.b1 - x.a1 * x.b0;
         x.c1 = x.b2 - x.a2 * x.b0;
@@ -185,7 +188,7 @@ static int lower_delay(FxLevel& L, std::vector<size_t>& vs) {
         const Vertex& v = g->vertices[vi];
         Plan p{};
         p.vi = vi;
-        delay::params(L.sr, v.delay_ms, v.delay_feedback, v.delay_cross, p.c);
+        delay::params(L.sr, v.fx.delay.time_ms, v.fx.delay.feedback, v.fx.delay.cross, p.c);
         p.D = (uint32_t)p.c[0];
         p.t = delay::tiling(M, p.D, T);
         if ((uint64_t)M + (uint64_t)(T + 4u) * p.D > 0xFFFF0000ull) return fail("delay: chunk too long");
@@ -260,13 +263,13 @@ static int lower_sat(FxLevel& L, std::vector<size_t>& vs) {
     const uint32_t F = g->sat_tile, n_tiles = (uint32_t)((M + F - 1) / F);
     const bool filtered = L.fam != F_SAT1, multi = filtered && M > (size_t)kSatInlineFrames;   // (multi: k_sat_sum first)
     std::vector<size_t> ord(vs.begin(), vs.end());   // one k_sat launch per oversampling factor
-    std::stable_sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return g->vertices[a].sat_oversample < g->vertices[b].sat_oversample; });
+    std::stable_sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return g->vertices[a].fx.sat.oversample < g->vertices[b].fx.sat.oversample; });
     std::vector<SatDesc> d;
     std::map<int, size_t> taps_off;
     for (size_t vi : ord) {
         Vertex& v = g->vertices[vi];
         double c[6];
-        sat::params(v.sat_kind, v.sat_oversample, v.sat_drive_db, v.sat_bias, v.sat_out_db, c);
+        sat::params(v.fx.sat.kind, v.fx.sat.oversample, v.fx.sat.drive_db, v.fx.sat.bias, v.fx.sat.out_db, c);
         SatDesc x{};
         if (multi && !(x.x = L.tmp_buffer())) return 0;
         L.head(x, vi);
@@ -275,15 +278,15 @@ static int lower_sat(FxLevel& L, std::vector<size_t>& vs) {
             if (!x.line) return fail("termdaw_amd: out of device memory for a saturator line");
             x.parity = v.line.parity;
             x.filled = (uint32_t)std::min<uint64_t>(enter_chunk(v, M, true), sat::kLine);
-            if (!taps_off.count(v.sat_oversample)) taps_off[v.sat_oversample] = L.cb.st->put(sat::taps(v.sat_oversample));
+            if (!taps_off.count(v.fx.sat.oversample)) taps_off[v.fx.sat.oversample] = L.cb.st->put(sat::taps(v.fx.sat.oversample));
         }
         v.first_pending = false;   // (R = 1 has no line: the set_time is consumed all the same)
         x.F = F;
         x.n_tiles = n_tiles;
-        x.kind = (uint32_t)v.sat_kind;
+        x.kind = (uint32_t)v.fx.sat.kind;
         x.g_in = c[0];
         x.g_out = c[1];
-        x.bias = (double)v.sat_bias;
+        x.bias = (double)v.fx.sat.bias;
         x.fb = c[2];
         d.push_back(x);
     }
@@ -293,12 +296,12 @@ static int lower_sat(FxLevel& L, std::vector<size_t>& vs) {
         return 1;
     }
     for (size_t i = 0; i < ord.size(); ++i)
-        L.cb.ptr_field(off + i * sizeof(SatDesc), offsetof(SatDesc, taps), taps_off[g->vertices[ord[i]].sat_oversample]);
+        L.cb.ptr_field(off + i * sizeof(SatDesc), offsetof(SatDesc, taps), taps_off[g->vertices[ord[i]].fx.sat.oversample]);
     if (multi) L.add_launch(F_SAT_SUM, off, (int)ord.size(), 0);
     for (size_t i = 0; i < ord.size();) {
-        const int R = g->vertices[ord[i]].sat_oversample;
+        const int R = g->vertices[ord[i]].fx.sat.oversample;
         size_t j = i;
-        while (j < ord.size() && g->vertices[ord[j]].sat_oversample == R) ++j;
+        while (j < ord.size() && g->vertices[ord[j]].fx.sat.oversample == R) ++j;
         L.add_launch(F_SAT, off + i * sizeof(SatDesc), (int)(j - i), sat_aux(n_tiles, F, (uint32_t)R, !multi));
         i = j;
     }
@@ -322,7 +325,7 @@ static int lower_chorus(FxLevel& L, std::vector<size_t>& vs) {
     for (size_t vi : vs) {
         Vertex& v = g->vertices[vi];
         double c[6];
-        chorus::params(L.sr, v.chorus_voices, v.chorus_delay_ms, v.chorus_depth_ms, v.chorus_rate_hz, v.chorus_stereo, v.chorus_shape, c);
+        chorus::params(L.sr, v.fx.chorus.voices, v.fx.chorus.delay_ms, v.fx.chorus.depth_ms, v.fx.chorus.rate_hz, v.fx.chorus.stereo, v.fx.chorus.shape, c);
         ChorusDesc x{};
         if (multi && !(x.x = L.tmp_buffer())) return 0;
         L.head(x, vi);
@@ -334,13 +337,13 @@ static int lower_chorus(FxLevel& L, std::vector<size_t>& vs) {
         x.t0 = L.t0;
         x.F = F;
         x.n_tiles = n_tiles;
-        x.voices = (uint32_t)v.chorus_voices;
-        x.shape = (uint32_t)v.chorus_shape;
+        x.voices = (uint32_t)v.fx.chorus.voices;
+        x.shape = (uint32_t)v.fx.chorus.shape;
         x.D0 = c[0];
         x.A = c[1];
         x.f = c[2];
-        x.stereo = (double)v.chorus_stereo;
-        x.inv_v = 1.0 / (double)v.chorus_voices;
+        x.stereo = (double)v.fx.chorus.stereo;
+        x.inv_v = 1.0 / (double)v.fx.chorus.voices;
         d.push_back(x);
     }
     const size_t off = L.put(d, vs);
@@ -360,7 +363,7 @@ static int lower_reverb(FxLevel& L, std::vector<size_t>& vs) {
     for (size_t vi : vs) {
         Vertex& v = g->vertices[vi];
         double c[reverb::kParams];
-        reverb::params(L.sr, v.reverb_room, v.reverb_damp, v.reverb_width, v.reverb_size, c);
+        reverb::params(L.sr, v.fx.reverb.room, v.fx.reverb.damp, v.fx.reverb.width, v.fx.reverb.size, c);
         ReverbDesc x{};
         x.x = L.tmp_buffer();
         if (!x.x) return 0;
@@ -420,7 +423,7 @@ static int lower_gate(FxLevel& L, std::vector<size_t>& vs) {
         x.n_tiles = n_tiles;
         x.chunk = chunk;
         double c[6];
-        gate::params(L.sr, v.gate_threshold_db, v.gate_hysteresis_db, v.gate_hold_ms, v.gate_attack_ms, v.gate_release_ms, v.gate_range_db, c);
+        gate::params(L.sr, v.fx.gate.threshold_db, v.fx.gate.hysteresis_db, v.fx.gate.hold_ms, v.fx.gate.attack_ms, v.fx.gate.release_ms, v.fx.gate.range_db, c);
         if (!(c[2] <= gate::kMaxHold)) return fail("gate: hold_ms is too many frames at this sample rate");
         x.To = c[0];
         x.Tc = c[1];
@@ -470,7 +473,7 @@ static void launch_gate(const Launch& L, const void* d, hipStream_t s) {
 // A gate vertex' state at time 0: closed, the hold run out -- (env, h, c) = (0, 0, H + 1)
 static void rest_gate(const td_graph* g, const Vertex& v, StateSlot* run) {
     double c[6];
-    gate::params(g->sr, v.gate_threshold_db, v.gate_hysteresis_db, v.gate_hold_ms, v.gate_attack_ms, v.gate_release_ms, v.gate_range_db, c);
+    gate::params(g->sr, v.fx.gate.threshold_db, v.fx.gate.hysteresis_db, v.fx.gate.hold_ms, v.fx.gate.attack_ms, v.fx.gate.release_ms, v.fx.gate.range_db, c);
     run->gate = {0.0, 0u, (uint32_t)std::min(c[2] + 1.0, gate::kMaxHold + 1.0), {0, 0, 0, 0}};
 }
 
@@ -480,7 +483,7 @@ static int lower_phaser(FxLevel& L, std::vector<size_t>& vs) {
     const uint32_t n_tiles = (uint32_t)((L.M + kPhaserTile - 1) / kPhaserTile);
     const bool multi = n_tiles > 1u;   // (multi: k_phaser_local and k_phaser_carry first)
     std::vector<size_t> ord(vs.begin(), vs.end());   // one launch per stage count: the kernels are templates on it
-    std::stable_sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return g->vertices[a].phaser_stages < g->vertices[b].phaser_stages; });
+    std::stable_sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return g->vertices[a].fx.phaser.stages < g->vertices[b].fx.phaser.stages; });
     std::vector<PhaserDesc> d;
     for (size_t vi : ord) {
         Vertex& v = g->vertices[vi];
@@ -494,14 +497,14 @@ static int lower_phaser(FxLevel& L, std::vector<size_t>& vs) {
         x.t0 = L.t0;
         x.n_tiles = n_tiles;
         double c[phaser::kParams];
-        phaser::params(L.sr, v.phaser_stages, v.phaser_lo_hz, v.phaser_hi_hz, v.phaser_rate_hz, v.phaser_feedback, v.phaser_stereo, v.phaser_shape, c);
-        x.stages = (uint32_t)v.phaser_stages;
-        x.shape = (uint32_t)v.phaser_shape;
+        phaser::params(L.sr, v.fx.phaser.stages, v.fx.phaser.lo_hz, v.fx.phaser.hi_hz, v.fx.phaser.rate_hz, v.fx.phaser.feedback, v.fx.phaser.stereo, v.fx.phaser.shape, c);
+        x.stages = (uint32_t)v.fx.phaser.stages;
+        x.shape = (uint32_t)v.fx.phaser.shape;
         x.am = c[3];
         x.ad = c[4];
         x.f = c[5];
         x.fb = c[6];
-        x.stereo = (double)v.phaser_stereo;
+        x.stereo = (double)v.fx.phaser.stereo;
         d.push_back(x);
     }
     const size_t off = L.put(d, ord);
@@ -541,7 +544,7 @@ static int lower_vocoder(FxLevel& L, std::vector<size_t>& vs) {
     // the keyed vertices behind the others (FxLevel::keyed_last), each group by band count: the kernels are templates on it
     std::vector<size_t> ord(vs.begin(), vs.end());
     const size_t n_plain = L.keyed_last(ord);
-    auto by_bands = [&](size_t a, size_t b) { return g->vertices[a].voc_bands < g->vertices[b].voc_bands; };
+    auto by_bands = [&](size_t a, size_t b) { return g->vertices[a].fx.vocoder.bands < g->vertices[b].fx.vocoder.bands; };
     std::stable_sort(ord.begin(), ord.begin() + (long)n_plain, by_bands);
     std::stable_sort(ord.begin() + (long)n_plain, ord.end(), by_bands);
     std::vector<VocDesc> d;
@@ -550,7 +553,7 @@ static int lower_vocoder(FxLevel& L, std::vector<size_t>& vs) {
         const size_t vi = ord[i];
         Vertex& v = g->vertices[vi];
         const bool keyed = i >= n_plain;
-        const int B = v.voc_bands;
+        const int B = v.fx.vocoder.bands;
         VocDesc x{};
         if (multi) {
             if (!(x.x = L.tmp_buffer())) return 0;
@@ -566,7 +569,7 @@ static int lower_vocoder(FxLevel& L, std::vector<size_t>& vs) {
         x.chunk = chunk;
         x.bands = (uint32_t)B;
         double c[vocoder::kMaxParams];
-        vocoder::params(L.sr, B, v.voc_lo_hz, v.voc_hi_hz, v.voc_q, v.voc_response_ms, v.voc_out_db, c);
+        vocoder::params(L.sr, B, v.fx.vocoder.lo_hz, v.fx.vocoder.hi_hz, v.fx.vocoder.q, v.fx.vocoder.response_ms, v.fx.vocoder.out_db, c);
         std::vector<VocBand> bands((size_t)B);
         for (int b = 0; b < B; ++b) {
             VocBand& y = bands[(size_t)b];
@@ -670,13 +673,13 @@ static int lower_filter(FxLevel& L, std::vector<size_t>& vs) {
         x.t0 = L.t0;
         x.n_tiles = n_tiles;
         double c[filter::kParams];
-        filter::params(L.sr, v.filt_kind, v.filt_freq_hz, v.filt_q, v.filt_lfo_oct, v.filt_rate_hz, v.filt_stereo, v.filt_shape,
-                       v.filt_env_oct, v.filt_sens_db, v.filt_attack_ms, v.filt_release_ms, c);
-        x.kind = (uint32_t)v.filt_kind;
-        x.shape = (uint32_t)v.filt_shape;
+        filter::params(L.sr, v.fx.filter.kind, v.fx.filter.freq_hz, v.fx.filter.q, v.fx.filter.lfo_oct, v.fx.filter.rate_hz, v.fx.filter.stereo, v.fx.filter.shape,
+                       v.fx.filter.env_oct, v.fx.filter.sens_db, v.fx.filter.attack_ms, v.fx.filter.release_ms, c);
+        x.kind = (uint32_t)v.fx.filter.kind;
+        x.shape = (uint32_t)v.fx.filter.shape;
         x.env = i >= n_still ? 1u : 0u;
         x.g0 = c[0]; x.kq = c[1]; x.gmin = c[2]; x.gmax = c[3]; x.cl = c[4]; x.ce = c[5]; x.f = c[6];
-        x.stereo = (double)v.filt_stereo;
+        x.stereo = (double)v.fx.filter.stereo;
         x.S = c[7]; x.aA = c[8]; x.oA = c[9]; x.aR = c[10];
         for (int j = 0; j < 8; ++j) {
             const double e = (double)(1u << j);
@@ -765,7 +768,7 @@ static int lower_limiter(FxLevel& L, std::vector<size_t>& vs) {
     for (size_t vi : vs) {
         Vertex& v = g->vertices[vi];
         double c[limiter::kParams];
-        limiter::params(L.sr, v.lim_ceiling_db, v.lim_lookahead_ms, v.lim_release_ms, v.lim_drive_db, c);
+        limiter::params(L.sr, v.fx.limiter.ceiling_db, v.fx.limiter.lookahead_ms, v.fx.limiter.release_ms, v.fx.limiter.drive_db, c);
         if (!(c[2] <= limiter::kMaxL)) return fail("limiter: lookahead_ms is too many frames at this sample rate");
         LimDesc x{};
         if (multi) {
@@ -843,7 +846,7 @@ static int lower_multiband(FxLevel& L, std::vector<size_t>& vs) {
         x.n_tiles = n_tiles;
         x.chunk = chunk;
         double c[multiband::kParams];
-        multiband::params(L.sr, v.mb_lo_hz, v.mb_hi_hz, v.mb_attack_ms, v.mb_release_ms, c);
+        multiband::params(L.sr, v.fx.mb.lo_hz, v.fx.mb.hi_hz, v.fx.mb.attack_ms, v.fx.mb.release_ms, c);
         for (int s = 0; s < 5; ++s)
             for (int i = 0; i < 5; ++i) x.co[s][i] = c[5 * s + i];
         std::vector<MbPowers> pw(1);
@@ -852,11 +855,11 @@ static int lower_multiband(FxLevel& L, std::vector<size_t>& vs) {
         x.aA = c[25];
         x.aR = c[26];
         x.oA = 1.0 - x.aA;
-        x.knee = (double)v.mb_knee_db;
+        x.knee = (double)v.fx.mb.knee_db;
         for (int b = 0; b < 3; ++b) {
-            x.thr[b] = (double)v.mb_threshold_db[b];
-            x.slope[b] = 1.0 - 1.0 / (double)v.mb_ratio[b];
-            x.makeup[b] = (double)v.mb_makeup_db[b];
+            x.thr[b] = (double)v.fx.mb.threshold_db[b];
+            x.slope[b] = 1.0 - 1.0 / (double)v.fx.mb.ratio[b];
+            x.makeup[b] = (double)v.fx.mb.makeup_db[b];
         }
         for (int j = 0; j < 8; ++j) {   // (the compressor's powers: k_comp_env runs over the bands)
             const double e = (double)(1u << j);
@@ -953,9 +956,9 @@ static int lower_convolution(FxLevel& L, std::vector<size_t>& vs) {
         Vertex& v = g->vertices[vi];
         if (!L.sb || v.sample_index >= L.sb->samples.size()) return fail("convolution: sample index out of range");
         const SampleEntry& smp = L.sb->samples[v.sample_index];
-        if (const char* why = conv::check_len(L.sr, smp.len, v.conv_length_ms)) return fail(std::string("convolution: ") + why);
+        if (const char* why = conv::check_len(L.sr, smp.len, v.fx.conv.length_ms)) return fail(std::string("convolution: ") + why);
         double c[conv::kParams];
-        conv::params(L.sr, smp.len, v.conv_length_ms, v.conv_predelay_ms, v.conv_out_db, c);
+        conv::params(L.sr, smp.len, v.fx.conv.length_ms, v.fx.conv.predelay_ms, v.fx.conv.out_db, c);
         ConvDesc x{};
         if (!(x.x = L.tmp_buffer())) return 0;
         L.head(x, vi);
@@ -965,7 +968,7 @@ static int lower_convolution(FxLevel& L, std::vector<size_t>& vs) {
         x.P = (uint32_t)c[3];
         x.hist = (uint32_t)c[4];
         x.n_tiles = n_tiles;
-        x.norm = (uint32_t)v.conv_norm;
+        x.norm = (uint32_t)v.fx.conv.norm;
         x.ir = smp.d;
         if (!(x.tw = take_twiddles(g))) return fail("termdaw_amd: out of device memory for the convolution vertices' twiddle table");
         const size_t line_bytes = std::max<size_t>(16, 2 * (size_t)x.hist * sizeof(float2));
@@ -1022,7 +1025,7 @@ static bool fits_mb(const td_graph*, const Vertex&, size_t M) { return M <= 0xFF
 // the windows of a chunk and the partitions in front of them stay a 32-bit grid, the frames a 32-bit index
 static bool fits_conv(const td_graph*, const Vertex&, size_t M) { return M <= 0xF0000000ull; }
 
-static int family_sat(const Vertex& v) { return v.sat_oversample == 1 ? F_SAT1 : F_SAT_SUM; }
+static int family_sat(const Vertex& v) { return v.fx.sat.oversample == 1 ? F_SAT1 : F_SAT_SUM; }
 
 // through: a dry vertex is the Sum it compiles to (factor 1); `lerp`: the estimate goes through (1 - wet) x + wet f(x) at
 // (1 - wet) + wet H, H the L2 gain (or Lipschitz bound) of f
@@ -1050,21 +1053,21 @@ static double through_convolution(const Vertex& v, size_t) { return dry(v) ? 1.0
 static double through_eq(const Vertex& v, size_t sr) {
     if (dry(v)) return 1.0;
     double c[5];
-    eq::coefficients(v.eq_kind, sr, v.eq_freq, v.eq_q, v.eq_gain_db, c);
+    eq::coefficients(v.fx.eq.kind, sr, v.fx.eq.freq_hz, v.fx.eq.q, v.fx.eq.gain_db, c);
     return lerp_gain(v, eq::hmax(c));
 }
 // a delay too: out = x + wet (echoes), the echo path's L2 gain is Hecho = 1 / (1 - feedback)
 static double through_delay(const Vertex& v, size_t sr) {
     if (dry(v)) return 1.0;
     double c[4];
-    delay::params(sr, v.delay_ms, v.delay_feedback, v.delay_cross, c);
+    delay::params(sr, v.fx.delay.time_ms, v.fx.delay.feedback, v.fx.delay.cross, c);
     return 1.0 + (double)v.wet * c[3];
 }
 // a saturator's shaper is Lipschitz: Hsat = g_out Hdown Lf g_in Hup
 static double through_sat(const Vertex& v, size_t) {
     if (dry(v)) return 1.0;
     double c[6];
-    sat::params(v.sat_kind, v.sat_oversample, v.sat_drive_db, v.sat_bias, v.sat_out_db, c);
+    sat::params(v.fx.sat.kind, v.fx.sat.oversample, v.fx.sat.drive_db, v.fx.sat.bias, v.fx.sat.out_db, c);
     return lerp_gain(v, c[5]);
 }
 // a chorus is linear (and time-varying): Hch, an L2 bound of the modulated four-point read
@@ -1073,8 +1076,44 @@ static double through_chorus(const Vertex& v, size_t) { return dry(v) ? 1.0 : le
 static double through_reverb(const Vertex& v, size_t sr) {
     if (dry(v)) return 1.0;
     double c[reverb::kParams];
-    reverb::params(sr, v.reverb_room, v.reverb_damp, v.reverb_width, v.reverb_size, c);
+    reverb::params(sr, v.fx.reverb.room, v.fx.reverb.damp, v.fx.reverb.width, v.fx.reverb.size, c);
     return lerp_gain(v, c[5]);
+}
+
+// check: the kind's block handed to its ranges (<kind>_math.h), field by field
+static const char* check_comp(size_t, const FxParams& p, bool) {
+    return comp::check(p.comp.threshold_db, p.comp.ratio, p.comp.attack_ms, p.comp.release_ms, p.comp.knee_db, p.comp.makeup_db);
+}
+static const char* check_eq(size_t sr, const FxParams& p, bool rate_free) { return eq::check(sr, p.eq.kind, p.eq.freq_hz, p.eq.q, p.eq.gain_db, rate_free); }
+static const char* check_delay(size_t sr, const FxParams& p, bool rate_free) { return delay::check(sr, p.delay.time_ms, p.delay.feedback, p.delay.cross, rate_free); }
+static const char* check_sat(size_t, const FxParams& p, bool) { return sat::check(p.sat.kind, p.sat.oversample, p.sat.drive_db, p.sat.bias, p.sat.out_db); }
+static const char* check_chorus(size_t sr, const FxParams& p, bool) {
+    return chorus::check(sr, p.chorus.voices, p.chorus.delay_ms, p.chorus.depth_ms, p.chorus.rate_hz, p.chorus.stereo, p.chorus.shape);
+}
+static const char* check_reverb(size_t sr, const FxParams& p, bool) { return reverb::check(sr, p.reverb.room, p.reverb.damp, p.reverb.width, p.reverb.size); }
+static const char* check_gate(size_t, const FxParams& p, bool) {
+    return gate::check(p.gate.threshold_db, p.gate.hysteresis_db, p.gate.hold_ms, p.gate.attack_ms, p.gate.release_ms, p.gate.range_db);
+}
+static const char* check_phaser(size_t sr, const FxParams& p, bool) {
+    return phaser::check(sr, p.phaser.stages, p.phaser.lo_hz, p.phaser.hi_hz, p.phaser.rate_hz, p.phaser.feedback, p.phaser.stereo, p.phaser.shape);
+}
+static const char* check_vocoder(size_t sr, const FxParams& p, bool) {
+    return vocoder::check(sr, p.vocoder.bands, p.vocoder.lo_hz, p.vocoder.hi_hz, p.vocoder.q, p.vocoder.response_ms, p.vocoder.out_db);
+}
+static const char* check_filter(size_t sr, const FxParams& p, bool) {
+    const FilterParams& f = p.filter;
+    return filter::check(sr, f.kind, f.freq_hz, f.q, f.lfo_oct, f.rate_hz, f.stereo, f.shape, f.env_oct, f.sens_db, f.attack_ms, f.release_ms);
+}
+static const char* check_limiter(size_t sr, const FxParams& p, bool) {
+    return limiter::check(sr, p.limiter.ceiling_db, p.limiter.lookahead_ms, p.limiter.release_ms, p.limiter.drive_db);
+}
+static const char* check_multiband(size_t sr, const FxParams& p, bool) {
+    return multiband::check(sr, p.mb.lo_hz, p.mb.hi_hz, p.mb.threshold_db, p.mb.ratio, p.mb.attack_ms, p.mb.release_ms, p.mb.knee_db, p.mb.makeup_db);
+}
+static const char* check_convolution(size_t sr, const FxParams& p, bool) { return conv::check(sr, p.conv.length_ms, p.conv.predelay_ms, p.conv.out_db, p.conv.norm); }
+// settle: an EQ kind without gain keeps none
+static void settle_eq(FxParams& p) {
+    if (!eq::kind_has_gain(p.eq.kind)) p.eq.gain_db = 0.0f;
 }
 
 // state_slots: a phaser vertex' 2 x (N + 1) doubles and a filter vertex' six take a run of slots
@@ -1092,20 +1131,66 @@ static_assert(F_COMP_DETECT < F_EQ_LOCAL && F_EQ_LOCAL < F_DELAY_LOCAL && F_DELA
               F_VOC_LOCAL < F_FILT_DETECT && F_FILT_DETECT < F_LIM_DETECT && F_LIM_DETECT < F_MB_LOCAL && F_MB_LOCAL < F_CONV_IR && F_CONV_IR < F_COUNT,
               "the rows of the effect kinds' table stand in the order of their families");
 static const FxKind* table() {
+    // the kinds' script lines behind (name, gain, angle, wet): the fields of their blocks in the order of the line
+    static const FxParam p_comp[] = {FX_F32(CompParams, threshold_db), FX_F32(CompParams, ratio), FX_F32(CompParams, attack_ms),
+                                     FX_F32(CompParams, release_ms), FX_F32(CompParams, knee_db), FX_F32(CompParams, makeup_db)};
+    static const FxParam p_eq[] = {FX_PARAM(EqParams, kind, NAME, eq::kind_names(), eq::kKinds, 0, nullptr), FX_F32(EqParams, freq_hz), FX_F32(EqParams, q),
+                                   FX_F32(EqParams, gain_db)};
+    static const FxParam p_delay[] = {FX_F32(DelayParams, time_ms), FX_F32(DelayParams, feedback), FX_F32(DelayParams, cross)};
+    static const FxParam p_sat[] = {FX_PARAM(SatParams, kind, NAME, sat::kind_names(), 3, 0, nullptr), FX_F32(SatParams, drive_db), FX_F32(SatParams, bias),
+                                    FX_F32(SatParams, out_db), FX_PARAM(SatParams, oversample, INT, nullptr, 0, 1u << 1 | 1u << 2 | 1u << 4 | 1u << 8, "1, 2, 4 or 8")};
+    static const FxParam p_chorus[] = {FX_PARAM(ChorusParams, voices, INT, nullptr, 0, 1u << 1 | 1u << 2 | 1u << 3 | 1u << 4, "1 .. 4"), FX_F32(ChorusParams, delay_ms),
+                                       FX_F32(ChorusParams, depth_ms), FX_F32(ChorusParams, rate_hz), FX_F32(ChorusParams, stereo),
+                                       FX_PARAM(ChorusParams, shape, NAME, chorus::shape_names(), 2, 0, nullptr)};
+    static const FxParam p_reverb[] = {FX_F32(ReverbParams, room), FX_F32(ReverbParams, damp), FX_F32(ReverbParams, width), FX_F32(ReverbParams, size)};
+    static const FxParam p_gate[] = {FX_F32(GateParams, threshold_db), FX_F32(GateParams, hysteresis_db), FX_F32(GateParams, hold_ms),
+                                     FX_F32(GateParams, attack_ms), FX_F32(GateParams, release_ms), FX_F32(GateParams, range_db)};
+    static const FxParam p_phaser[] = {FX_PARAM(PhaserParams, stages, INT, nullptr, 0, 1u << 2 | 1u << 4 | 1u << 6 | 1u << 8, "2, 4, 6 or 8"), FX_F32(PhaserParams, lo_hz),
+                                       FX_F32(PhaserParams, hi_hz), FX_F32(PhaserParams, rate_hz), FX_F32(PhaserParams, feedback), FX_F32(PhaserParams, stereo),
+                                       FX_PARAM(PhaserParams, shape, NAME, chorus::shape_names(), 2, 0, nullptr)};
+    static const FxParam p_vocoder[] = {FX_PARAM(VocoderParams, bands, INT, nullptr, 0, 1u << 4 | 1u << 8 | 1u << 16, "4, 8 or 16"), FX_F32(VocoderParams, lo_hz),
+                                        FX_F32(VocoderParams, hi_hz), FX_F32(VocoderParams, q), FX_F32(VocoderParams, response_ms), FX_F32(VocoderParams, out_db)};
+    static const FxParam p_filter[] = {FX_PARAM(FilterParams, kind, NAME, filter::kind_names(), 4, 0, nullptr), FX_F32(FilterParams, freq_hz), FX_F32(FilterParams, q),
+                                       FX_F32(FilterParams, lfo_oct), FX_F32(FilterParams, rate_hz), FX_F32(FilterParams, stereo),
+                                       FX_PARAM(FilterParams, shape, NAME, chorus::shape_names(), 2, 0, nullptr), FX_F32(FilterParams, env_oct),
+                                       FX_F32(FilterParams, sens_db), FX_F32(FilterParams, attack_ms), FX_F32(FilterParams, release_ms)};
+    static const FxParam p_limiter[] = {FX_F32(LimiterParams, ceiling_db), FX_F32(LimiterParams, lookahead_ms), FX_F32(LimiterParams, release_ms),
+                                        FX_F32(LimiterParams, drive_db)};
+    // (the per-band triples: the line is flat, the bands in the order low, mid, high)
+    static const FxParam p_mb[] = {FX_F32(MbParams, lo_hz), FX_F32(MbParams, hi_hz), FX_F32(MbParams, threshold_db[0]), FX_F32(MbParams, threshold_db[1]),
+                                   FX_F32(MbParams, threshold_db[2]), FX_F32(MbParams, ratio[0]), FX_F32(MbParams, ratio[1]), FX_F32(MbParams, ratio[2]),
+                                   FX_F32(MbParams, attack_ms), FX_F32(MbParams, release_ms), FX_F32(MbParams, knee_db), FX_F32(MbParams, makeup_db[0]),
+                                   FX_F32(MbParams, makeup_db[1]), FX_F32(MbParams, makeup_db[2])};
+    // (the response stands in front of the block's fields)
+    static const FxParam p_conv[] = {{"sample", FxParam::SAMPLE, 0, nullptr, 0, 0, nullptr}, FX_F32(ConvParams, length_ms), FX_F32(ConvParams, predelay_ms),
+                                     FX_F32(ConvParams, out_db), FX_PARAM(ConvParams, norm, INT, nullptr, 0, 1u << 0 | 1u << 1, "0 or 1")};
     static const FxKind rows[kFxKinds] = {
-        {K_COMPRESSOR, "compressor", "comp", F_COMP_DETECT, F_EQ_LOCAL - F_COMP_DETECT, sizeof(CompDesc), 1, true, fits_scan, nullptr, through_comp, lower_comp, launch_comp, launch_comp_detect && launch_comp_env && launch_comp_apply && launch_master_carry, launch_comp_detect_keyed != nullptr, "compressor / gate", nullptr},
-        {K_EQ, "eq", "eq", F_EQ_LOCAL, F_DELAY_LOCAL - F_EQ_LOCAL, sizeof(EqDesc), 1, false, fits_scan, nullptr, through_eq, lower_eq, launch_eq, launch_eq_local && launch_eq_carry && launch_eq_apply, true, nullptr, nullptr},
-        {K_DELAY, "delay", "delay", F_DELAY_LOCAL, F_SAT_SUM - F_DELAY_LOCAL, sizeof(DelayDesc), 0, false, fits_line, nullptr, through_delay, lower_delay, launch_delay, launch_delay_local && launch_delay_carry && launch_delay_apply, true, nullptr, nullptr},
-        {K_SATURATOR, "saturator", "sat", F_SAT_SUM, F_CHORUS_SUM - F_SAT_SUM, sizeof(SatDesc), 0, false, fits_sat, family_sat, through_sat, lower_sat, launch_sat_kind, launch_sat_sum && launch_sat && launch_sat1, true, nullptr, nullptr},
-        {K_CHORUS, "chorus", "chorus", F_CHORUS_SUM, F_REVERB_SUM - F_CHORUS_SUM, sizeof(ChorusDesc), 0, false, fits_chorus, nullptr, through_chorus, lower_chorus, launch_chorus_kind, launch_chorus_sum && launch_chorus, true, nullptr, nullptr},
-        {K_REVERB, "reverb", "reverb", F_REVERB_SUM, F_GATE_DETECT - F_REVERB_SUM, sizeof(ReverbDesc), 0, false, fits_line, nullptr, through_reverb, lower_reverb, launch_reverb_kind, launch_reverb_sum && launch_reverb, true, nullptr, nullptr},
-        {K_GATE, "gate", "gate", F_GATE_DETECT, F_PHASER_LOCAL - F_GATE_DETECT, sizeof(GateDesc), 1, true, fits_scan, nullptr, through_gate, lower_gate, launch_gate, launch_gate_detect && launch_gate_carry && launch_gate_env && launch_gate_apply, launch_gate_detect_keyed && launch_gate_env_keyed, "compressor / gate", rest_gate},
-        {K_PHASER, "phaser", "phaser", F_PHASER_LOCAL, F_VOC_LOCAL - F_PHASER_LOCAL, sizeof(PhaserDesc), kPhaserSlots, false, fits_scan, nullptr, through_phaser, lower_phaser, launch_phaser, launch_phaser_local && launch_phaser_carry && launch_phaser_apply, true, nullptr, nullptr},
-        {K_VOCODER, "vocoder", "voc", F_VOC_LOCAL, F_FILT_DETECT - F_VOC_LOCAL, sizeof(VocDesc), 0, true, fits_voc, nullptr, through_vocoder, lower_vocoder, launch_vocoder, launch_voc_local && launch_voc_carry && launch_voc_env && launch_voc_apply, launch_voc_local_keyed && launch_voc_apply_keyed, "vocoder", nullptr},
-        {K_FILTER, "filter", "filt", F_FILT_DETECT, F_LIM_DETECT - F_FILT_DETECT, sizeof(FiltDesc), kFiltSlots, true, fits_scan, nullptr, through_filter, lower_filter, launch_filter, launch_filt_detect && launch_filt_env && launch_filt_local && launch_filt_carry && launch_filt_apply && launch_master_carry, true, nullptr, nullptr},
-        {K_LIMITER, "limiter", "lim", F_LIM_DETECT, F_MB_LOCAL - F_LIM_DETECT, sizeof(LimDesc), 0, false, fits_scan, nullptr, through_limiter, lower_limiter, launch_limiter, launch_lim_detect && launch_lim_apply && launch_master_carry, true, nullptr, nullptr},
-        {K_MULTIBAND, "multiband", "mb", F_MB_LOCAL, F_CONV_IR - F_MB_LOCAL, sizeof(MbDesc), 0, false, fits_mb, nullptr, through_multiband, lower_multiband, launch_multiband, launch_mb_local && launch_mb_carry && launch_mb_detect && launch_mb_apply && launch_comp_env && launch_master_carry, true, nullptr, nullptr},
-        {K_CONVOLUTION, "convolution", "conv", F_CONV_IR, F_COUNT - F_CONV_IR, sizeof(ConvDesc), 0, false, fits_conv, nullptr, through_convolution, lower_convolution, launch_convolution, launch_conv_ir && launch_conv_fwd && launch_conv_mac && launch_conv_inv, true, nullptr, nullptr},
+        {K_COMPRESSOR, "compressor", "comp", F_COMP_DETECT, F_EQ_LOCAL - F_COMP_DETECT, sizeof(CompDesc), 1, true, fits_scan, nullptr, through_comp, lower_comp, launch_comp, launch_comp_detect && launch_comp_env && launch_comp_apply && launch_master_carry, launch_comp_detect_keyed != nullptr, "compressor / gate", nullptr,
+         "add_compressor", "add_compressor: ", FX_SCHEMA(p_comp), check_comp, FxKind::LINE_NONE, false, nullptr},
+        {K_EQ, "eq", "eq", F_EQ_LOCAL, F_DELAY_LOCAL - F_EQ_LOCAL, sizeof(EqDesc), 1, false, fits_scan, nullptr, through_eq, lower_eq, launch_eq, launch_eq_local && launch_eq_carry && launch_eq_apply, true, nullptr, nullptr,
+         "add_eq", "add_eq: ", FX_SCHEMA(p_eq), check_eq, FxKind::LINE_RATE_FREE, false, settle_eq},
+        {K_DELAY, "delay", "delay", F_DELAY_LOCAL, F_SAT_SUM - F_DELAY_LOCAL, sizeof(DelayDesc), 0, false, fits_line, nullptr, through_delay, lower_delay, launch_delay, launch_delay_local && launch_delay_carry && launch_delay_apply, true, nullptr, nullptr,
+         "add_delay", "add_delay: ", FX_SCHEMA(p_delay), check_delay, FxKind::LINE_RATE_FREE, true, nullptr},
+        {K_SATURATOR, "saturator", "sat", F_SAT_SUM, F_CHORUS_SUM - F_SAT_SUM, sizeof(SatDesc), 0, false, fits_sat, family_sat, through_sat, lower_sat, launch_sat_kind, launch_sat_sum && launch_sat && launch_sat1, true, nullptr, nullptr,
+         "add_saturator", "add_saturator: ", FX_SCHEMA(p_sat), check_sat, FxKind::LINE_FULL, true, nullptr},
+        {K_CHORUS, "chorus", "chorus", F_CHORUS_SUM, F_REVERB_SUM - F_CHORUS_SUM, sizeof(ChorusDesc), 0, false, fits_chorus, nullptr, through_chorus, lower_chorus, launch_chorus_kind, launch_chorus_sum && launch_chorus, true, nullptr, nullptr,
+         "add_chorus", "add_chorus: ", FX_SCHEMA(p_chorus), check_chorus, FxKind::LINE_FULL, true, nullptr},
+        {K_REVERB, "reverb", "reverb", F_REVERB_SUM, F_GATE_DETECT - F_REVERB_SUM, sizeof(ReverbDesc), 0, false, fits_line, nullptr, through_reverb, lower_reverb, launch_reverb_kind, launch_reverb_sum && launch_reverb, true, nullptr, nullptr,
+         "add_reverb", "add_reverb: ", FX_SCHEMA(p_reverb), check_reverb, FxKind::LINE_FULL, true, nullptr},
+        {K_GATE, "gate", "gate", F_GATE_DETECT, F_PHASER_LOCAL - F_GATE_DETECT, sizeof(GateDesc), 1, true, fits_scan, nullptr, through_gate, lower_gate, launch_gate, launch_gate_detect && launch_gate_carry && launch_gate_env && launch_gate_apply, launch_gate_detect_keyed && launch_gate_env_keyed, "compressor / gate", rest_gate,
+         "add_gate", "add_gate: ", FX_SCHEMA(p_gate), check_gate, FxKind::LINE_FULL, false, nullptr},
+        {K_PHASER, "phaser", "phaser", F_PHASER_LOCAL, F_VOC_LOCAL - F_PHASER_LOCAL, sizeof(PhaserDesc), kPhaserSlots, false, fits_scan, nullptr, through_phaser, lower_phaser, launch_phaser, launch_phaser_local && launch_phaser_carry && launch_phaser_apply, true, nullptr, nullptr,
+         "add_phaser", "add_phaser: ", FX_SCHEMA(p_phaser), check_phaser, FxKind::LINE_FULL, false, nullptr},
+        {K_VOCODER, "vocoder", "voc", F_VOC_LOCAL, F_FILT_DETECT - F_VOC_LOCAL, sizeof(VocDesc), 0, true, fits_voc, nullptr, through_vocoder, lower_vocoder, launch_vocoder, launch_voc_local && launch_voc_carry && launch_voc_env && launch_voc_apply, launch_voc_local_keyed && launch_voc_apply_keyed, "vocoder", nullptr,
+         "add_vocoder", "add_vocoder: ", FX_SCHEMA(p_vocoder), check_vocoder, FxKind::LINE_FULL, false, nullptr},
+        {K_FILTER, "filter", "filt", F_FILT_DETECT, F_LIM_DETECT - F_FILT_DETECT, sizeof(FiltDesc), kFiltSlots, true, fits_scan, nullptr, through_filter, lower_filter, launch_filter, launch_filt_detect && launch_filt_env && launch_filt_local && launch_filt_carry && launch_filt_apply && launch_master_carry, true, nullptr, nullptr,
+         "add_filter", "add_filter: ", FX_SCHEMA(p_filter), check_filter, FxKind::LINE_FULL, false, nullptr},
+        {K_LIMITER, "limiter", "lim", F_LIM_DETECT, F_MB_LOCAL - F_LIM_DETECT, sizeof(LimDesc), 0, false, fits_scan, nullptr, through_limiter, lower_limiter, launch_limiter, launch_lim_detect && launch_lim_apply && launch_master_carry, true, nullptr, nullptr,
+         "add_limiter", "add_limiter: ", FX_SCHEMA(p_limiter), check_limiter, FxKind::LINE_FULL, false, nullptr},
+        {K_MULTIBAND, "multiband", "mb", F_MB_LOCAL, F_CONV_IR - F_MB_LOCAL, sizeof(MbDesc), 0, false, fits_mb, nullptr, through_multiband, lower_multiband, launch_multiband, launch_mb_local && launch_mb_carry && launch_mb_detect && launch_mb_apply && launch_comp_env && launch_master_carry, true, nullptr, nullptr,
+         "add_multiband", "add_multiband: multiband: ", FX_SCHEMA(p_mb), check_multiband, FxKind::LINE_FULL, false, nullptr},
+        {K_CONVOLUTION, "convolution", "conv", F_CONV_IR, F_COUNT - F_CONV_IR, sizeof(ConvDesc), 0, false, fits_conv, nullptr, through_convolution, lower_convolution, launch_convolution, launch_conv_ir && launch_conv_fwd && launch_conv_mac && launch_conv_inv, true, nullptr, nullptr,
+         "add_convolution", "add_convolution: convolution: ", FX_SCHEMA(p_conv), check_convolution, FxKind::LINE_FULL, false, nullptr},
     };
     return rows;
 }

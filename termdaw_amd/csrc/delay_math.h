@@ -14,6 +14,16 @@ namespace delay {
 constexpr uint32_t kTileDefault = 16;   // steps per tile ("debug.delay_tile" 8 | 16 | 32 | 64)
 constexpr uint32_t kCarryFold = 16;     // k_delay_carry: tiles a thread folds serially before lanes get more threads
 
+// nullptr: fine, otherwise the reason.  rate_free: only the ranges that do not depend on the rate (a script line's: eq_math.h)
+inline const char* check(size_t sr, float time_ms, float feedback, float cross, bool rate_free = false) {
+    if (!rate_free && !sr) return "the sample rate must be positive";
+    if (!(time_ms >= 1.0f && time_ms <= 2000.0f)) return "time_ms must lie in [1, 2000] ms";
+    if (!(feedback >= 0.0f && feedback <= 0.98f)) return "feedback must lie in [0, 0.98]";
+    if (!(cross >= 0.0f && cross <= 1.0f)) return "cross must lie in [0, 1]";
+    if (!rate_free && (double)time_ms * (double)sr / 1000.0 > 268435456.0) return "time_ms is more than 2^28 frames at this sample rate";
+    return nullptr;
+}
+
 // (D, gs, gc, Hecho) in f64 from the f32 parameters, widened
 inline void params(size_t sr, float time_ms, float feedback, float cross, double out[4]) {
     const long long d = llround((double)time_ms * (double)sr / 1000.0);

@@ -1519,6 +1519,60 @@ static int batch_render_chunks(td_batch* b, size_t n_blocks, bool is_scan, int b
 
 }  // namespace tde
 
+// ---- what the C ABI's td_graph_add_* share: a vertex, a state slot, an effect vertex (add_fx: the project front end's too, compile.h) ----
+// A guarded render whose verdict is still out is settled before the graph it was rendered from changes shape (band_mode 2:
+// the render is done again from a snapshot of THIS graph's vertices).
+static void settle_guard_before_edit(td_graph* g) {
+    if (g->guard.armed && !g->guard.in_redo) (void)drain(g);
+}
+static Vertex& add_vertex(td_graph* g, const char* name, float gain, float angle, float wet, Kind kind) {
+    settle_guard_before_edit(g);
+    Vertex v;
+    v.kind = kind;
+    v.name = name;
+    v.gain = gain;
+    v.angle = fmaxf(fminf(angle, 90.0f), -90.0f);   // graph.rs:255
+    v.wet = fmaxf(fminf(wet, 1.0f), 0.0f);          // graph.rs:256
+    g->vertices.push_back(v);
+    g->edges.emplace_back();
+    g->key_edges.emplace_back();
+    g->name_map[name] = g->vertices.size() - 1;     // later duplicates overwrite (graph.rs:54)
+    g->plan_dirty = true;
+    return g->vertices.back();
+}
+static int new_slot(td_graph* g) {
+    // a freshly constructed slot makes the host mirror authoritative: fetch device values first
+    pull_state(g);
+    StateSlot s;
+    memset(&s, 0, sizeof s);
+    g->hstate.push_back(s);
+    g->state_host_dirty = true;
+    return (int)g->hstate.size() - 1;
+}
+// A kind's check of a block, by name: "<kind>: <reason>"
+static int fx_check(Kind k, size_t sr, const FxParams& p) {
+    const FxKind* fx = fx_kind(k);
+    if (const char* why = fx->check(sr, p, false)) return fail(std::string(fx->name) + ": " + why);
+    return 1;
+}
+// An effect vertex (compile.h): its kind's check, the state slots the kind carries (FxKind::state_slots), the vertex, the block as
+// the kind keeps it.  The slots first: new_slot pulls the state of the vertices that exist.  They are zeroed: every kind's state
+// at time 0 but the gate's, which needs the vertex' parameters (FxKind::rest).
+int tde::add_fx(td_graph* g, Kind k, const char* name, float gain, float angle, float wet, const FxParams& p, size_t sample_index) {
+    if (!fx_check(k, g->sr, p)) return 0;
+    const FxKind* fx = fx_kind(k);
+    const int n = fx->state_slots, slot = n ? new_slot(g) : -1;
+    for (int i = 1; i < n; ++i) new_slot(g);
+    Vertex& v = add_vertex(g, name, gain, angle, wet, k);
+    v.state_slot = slot;
+    v.sample_index = sample_index;
+    v.fx = p;
+    if (fx->settle) fx->settle(v.fx);
+    v.first_pending = fx->starts_pending;
+    if (fx->rest) fx->put_rest(g, v, &g->hstate[(size_t)v.state_slot]);
+    return 1;
+}
+
 // =================================================================================================
 // C ABI
 // =================================================================================================
@@ -1745,44 +1799,6 @@ void td_graph_reset(td_graph* g) {
     g->plan_dirty = true;
 }
 
-// A guarded render whose verdict is still out is settled before the graph it was rendered from changes shape (band_mode 2:
-// the render is done again from a snapshot of THIS graph's vertices).
-static void settle_guard_before_edit(td_graph* g) {
-    if (g->guard.armed && !g->guard.in_redo) (void)drain(g);
-}
-static Vertex& add_vertex(td_graph* g, const char* name, float gain, float angle, float wet, Kind kind) {
-    settle_guard_before_edit(g);
-    Vertex v;
-    v.kind = kind;
-    v.name = name;
-    v.gain = gain;
-    v.angle = fmaxf(fminf(angle, 90.0f), -90.0f);   // graph.rs:255
-    v.wet = fmaxf(fminf(wet, 1.0f), 0.0f);          // graph.rs:256
-    g->vertices.push_back(v);
-    g->edges.emplace_back();
-    g->key_edges.emplace_back();
-    g->name_map[name] = g->vertices.size() - 1;     // later duplicates overwrite (graph.rs:54)
-    g->plan_dirty = true;
-    return g->vertices.back();
-}
-static int new_slot(td_graph* g) {
-    // a freshly constructed slot makes the host mirror authoritative: fetch device values first
-    pull_state(g);
-    StateSlot s;
-    memset(&s, 0, sizeof s);
-    g->hstate.push_back(s);
-    g->state_host_dirty = true;
-    return (int)g->hstate.size() - 1;
-}
-// A vertex of an effect kind with the state slots its kind carries (FxKind::state_slots).  The slots first: new_slot pulls the state of
-// the vertices that exist.  They are zeroed: every kind's state at time 0 but the gate's, which needs the vertex' parameters (FxKind::rest).
-static Vertex& add_fx_vertex(td_graph* g, const char* name, float gain, float angle, float wet, Kind kind) {
-    const int n = fx_kind(kind)->state_slots, slot = n ? new_slot(g) : -1;
-    for (int i = 1; i < n; ++i) new_slot(g);
-    Vertex& v = add_vertex(g, name, gain, angle, wet, kind);
-    v.state_slot = slot;
-    return v;
-}
 static bool conf_from(const float* arr, int n, AdsrConfD* c) {   // adsr.rs:94-114
     if (n == 0) { *c = AdsrConfD{0, 0, 0, 0, 0, 0, 0, 0, 0}; return true; }
     if (n == 6) { *c = AdsrConfD{0.0f, arr[0], 1.0f, arr[1], arr[2], arr[3], arr[4], arr[5], 0.0f}; return true; }
@@ -1925,96 +1941,51 @@ int td_graph_add_bandpass(td_graph* g, const char* name, float gain, float angle
     g->hstate[slot].band = {0.f, 0.f, 0.f, 0.f, 1u, {0, 0, 0}};
     return 1;
 }
-// This engine's own dynamics vertex (no reference counterpart; the definition is in include/termdaw_amd.h).
+// This engine's own effect vertices (no reference counterpart; the definitions are in include/termdaw_amd.h): each packs its
+// arguments into its kind's block (fx_params.h) for add_fx; the td_<kind>_params beside them judge theirs by the same check.  The
+// state a kind carries beyond its slots is a line (Vertex::line; the convolution's response spectra beside it), allocated when the
+// vertex is first compiled into a submission.
 int td_graph_add_compressor(td_graph* g, const char* name, float gain, float angle, float wet, float threshold_db, float ratio,
                             float attack_ms, float release_ms, float knee_db, float makeup_db) {
-    if (!(threshold_db >= -80.0f && threshold_db <= 0.0f)) return fail("compressor: threshold_db must lie in [-80, 0] dB");
-    if (!(ratio >= 1.0f && ratio <= 1000.0f)) return fail("compressor: ratio must lie in [1, 1000]");
-    if (!(attack_ms >= 0.0f && attack_ms <= 1000.0f)) return fail("compressor: attack_ms must lie in [0, 1000] ms");
-    if (!(release_ms >= 1.0f && release_ms <= 10000.0f)) return fail("compressor: release_ms must lie in [1, 10000] ms");
-    if (!(knee_db >= 0.0f && knee_db <= 40.0f)) return fail("compressor: knee_db must lie in [0, 40] dB");
-    if (!(makeup_db >= -40.0f && makeup_db <= 40.0f)) return fail("compressor: makeup_db must lie in [-40, 40] dB");
-    Vertex& v = add_fx_vertex(g, name, gain, angle, wet, K_COMPRESSOR);
-    v.threshold_db = threshold_db;
-    v.ratio = ratio;
-    v.attack_ms = attack_ms;
-    v.release_ms = release_ms;
-    v.knee_db = knee_db;
-    v.makeup_db = makeup_db;
-    return 1;
+    FxParams p{};
+    p.comp = {threshold_db, ratio, attack_ms, release_ms, knee_db, makeup_db};
+    return add_fx(g, K_COMPRESSOR, name, gain, angle, wet, p);
 }
 
-// This engine's own filter vertex (no reference counterpart; the definition is in include/termdaw_amd.h).
-static int eq_check(int kind, size_t sr, float freq_hz, float q, float gain_db) {
-    if (!(kind >= 0 && kind < eq::kKinds)) return fail("eq: kind must be one of TD_EQ_LOWPASS .. TD_EQ_HIGHSHELF (0 .. 6)");
-    if (!sr) return fail("eq: the sample rate must be positive");
-    if (!(freq_hz >= 10.0f && 20.0 * (double)freq_hz <= 9.0 * (double)sr)) return fail("eq: freq_hz must lie in [10, 0.45 sr] Hz");
-    if (!(q >= 0.1f && q <= 20.0f)) return fail("eq: q must lie in [0.1, 20]");
-    if (eq::kind_has_gain(kind) && !(gain_db >= -24.0f && gain_db <= 24.0f)) return fail("eq: gain_db must lie in [-24, 24] dB");
-    return 1;
-}
 int td_graph_add_eq(td_graph* g, const char* name, float gain, float angle, float wet, int kind, float freq_hz, float q, float gain_db) {
-    if (!eq_check(kind, g->sr, freq_hz, q, gain_db)) return 0;
-    Vertex& v = add_fx_vertex(g, name, gain, angle, wet, K_EQ);
-    v.eq_kind = kind;
-    v.eq_freq = freq_hz;
-    v.eq_q = q;
-    v.eq_gain_db = eq::kind_has_gain(kind) ? gain_db : 0.0f;
-    return 1;
+    FxParams p{};
+    p.eq = {kind, freq_hz, q, gain_db};
+    return add_fx(g, K_EQ, name, gain, angle, wet, p);
 }
 int td_eq_coefficients(int kind, size_t sr, float freq_hz, float q, float gain_db, double out[6]) {
     if (!out) return fail("eq_coefficients: out is null");
-    if (!eq_check(kind, sr, freq_hz, q, gain_db)) return 0;
+    FxParams p{};
+    p.eq = {kind, freq_hz, q, gain_db};
+    if (!fx_check(K_EQ, sr, p)) return 0;
     eq::coefficients(kind, sr, freq_hz, q, gain_db, out);
     out[5] = eq::hmax(out);
     return 1;
 }
 
-// This engine's own echo vertex (no reference counterpart; the definition is in include/termdaw_amd.h).
-static int delay_check(size_t sr, float time_ms, float feedback, float cross) {
-    if (!sr) return fail("delay: the sample rate must be positive");
-    if (!(time_ms >= 1.0f && time_ms <= 2000.0f)) return fail("delay: time_ms must lie in [1, 2000] ms");
-    if (!(feedback >= 0.0f && feedback <= 0.98f)) return fail("delay: feedback must lie in [0, 0.98]");
-    if (!(cross >= 0.0f && cross <= 1.0f)) return fail("delay: cross must lie in [0, 1]");
-    if ((double)time_ms * (double)sr / 1000.0 > 268435456.0) return fail("delay: time_ms is more than 2^28 frames at this sample rate");
-    return 1;
-}
 int td_graph_add_delay(td_graph* g, const char* name, float gain, float angle, float wet, float time_ms, float feedback, float cross) {
-    if (!delay_check(g->sr, time_ms, feedback, cross)) return 0;
-    Vertex& v = add_fx_vertex(g, name, gain, angle, wet, K_DELAY);
-    v.delay_ms = time_ms;
-    v.delay_feedback = feedback;
-    v.delay_cross = cross;
-    v.first_pending = true;   // (the line, once it exists, is read from the first word the vertex itself has written)
-    return 1;
+    FxParams p{};
+    p.delay = {time_ms, feedback, cross};
+    return add_fx(g, K_DELAY, name, gain, angle, wet, p);
 }
 int td_delay_params(size_t sr, float time_ms, float feedback, float cross, double out[4]) {
     if (!out) return fail("delay_params: out is null");
-    if (!delay_check(sr, time_ms, feedback, cross)) return 0;
+    FxParams p{};
+    p.delay = {time_ms, feedback, cross};
+    if (!fx_check(K_DELAY, sr, p)) return 0;
     delay::params(sr, time_ms, feedback, cross, out);
     return 1;
 }
 
-// This engine's own waveshaper vertex (no reference counterpart; the definition is in include/termdaw_amd.h).
-static int sat_check(int kind, int oversample, float drive_db, float bias, float out_db) {
-    if (!(kind >= 0 && kind <= 2)) return fail("saturator: kind must be 0 (hard), 1 (cubic) or 2 (soft)");
-    if (!sat::oversample_ok(oversample)) return fail("saturator: oversample must be 1, 2, 4 or 8");
-    if (!(drive_db >= -24.0f && drive_db <= 48.0f)) return fail("saturator: drive_db must lie in [-24, 48] dB");
-    if (!(bias >= -1.0f && bias <= 1.0f)) return fail("saturator: bias must lie in [-1, 1]");
-    if (!(out_db >= -48.0f && out_db <= 24.0f)) return fail("saturator: out_db must lie in [-48, 24] dB");
-    return 1;
-}
 int td_graph_add_saturator(td_graph* g, const char* name, float gain, float angle, float wet, int kind, float drive_db, float bias,
                            float out_db, int oversample) {
-    if (!sat_check(kind, oversample, drive_db, bias, out_db)) return 0;
-    Vertex& v = add_fx_vertex(g, name, gain, angle, wet, K_SATURATOR);
-    v.sat_kind = kind;
-    v.sat_oversample = oversample;
-    v.sat_drive_db = drive_db;
-    v.sat_bias = bias;
-    v.sat_out_db = out_db;
-    v.first_pending = true;   // (the line, once it exists, is read from the first frame the vertex itself has written)
-    return 1;
+    FxParams p{};
+    p.sat = {kind, drive_db, bias, out_db, oversample};
+    return add_fx(g, K_SATURATOR, name, gain, angle, wet, p);
 }
 int td_saturator_taps(int oversample, double* taps, size_t cap) {
     if (!sat::oversample_ok(oversample)) return fail("saturator_taps: oversample must be 1, 2, 4 or 8");
@@ -2025,213 +1996,161 @@ int td_saturator_taps(int oversample, double* taps, size_t cap) {
 }
 int td_saturator_params(int kind, int oversample, float drive_db, float bias, float out_db, double out[6]) {
     if (!out) return fail("saturator_params: out is null");
-    if (!sat_check(kind, oversample, drive_db, bias, out_db)) return 0;
+    FxParams p{};
+    p.sat = {kind, drive_db, bias, out_db, oversample};
+    if (!fx_check(K_SATURATOR, 0, p)) return 0;   // (no range of it depends on the rate)
     sat::params(kind, oversample, drive_db, bias, out_db, out);
     return 1;
 }
 
-// This engine's own modulated-delay vertex (no reference counterpart; the definition is in include/termdaw_amd.h).
 int td_graph_add_chorus(td_graph* g, const char* name, float gain, float angle, float wet, int voices, float delay_ms, float depth_ms,
                         float rate_hz, float stereo, int shape) {
-    if (const char* why = chorus::check(g->sr, voices, delay_ms, depth_ms, rate_hz, stereo, shape)) return fail(std::string("chorus: ") + why);
-    Vertex& v = add_fx_vertex(g, name, gain, angle, wet, K_CHORUS);
-    v.chorus_voices = voices;
-    v.chorus_shape = shape;
-    v.chorus_delay_ms = delay_ms;
-    v.chorus_depth_ms = depth_ms;
-    v.chorus_rate_hz = rate_hz;
-    v.chorus_stereo = stereo;
-    v.first_pending = true;   // (the line, once it exists, is read from the first frame the vertex itself has written)
-    return 1;
+    FxParams p{};
+    p.chorus = {voices, delay_ms, depth_ms, rate_hz, stereo, shape};
+    return add_fx(g, K_CHORUS, name, gain, angle, wet, p);
 }
 int td_chorus_params(size_t sr, int voices, float delay_ms, float depth_ms, float rate_hz, float stereo, int shape, double out[6]) {
     if (!out) return fail("chorus_params: out is null");
-    if (const char* why = chorus::check(sr, voices, delay_ms, depth_ms, rate_hz, stereo, shape)) return fail(std::string("chorus: ") + why);
+    FxParams p{};
+    p.chorus = {voices, delay_ms, depth_ms, rate_hz, stereo, shape};
+    if (!fx_check(K_CHORUS, sr, p)) return 0;
     chorus::params(sr, voices, delay_ms, depth_ms, rate_hz, stereo, shape, out);
     return 1;
 }
 
-// This engine's own reverb vertex (no reference counterpart; the definition is in include/termdaw_amd.h).
 int td_graph_add_reverb(td_graph* g, const char* name, float gain, float angle, float wet, float room, float damp, float width, float size) {
-    if (const char* why = reverb::check(g->sr, room, damp, width, size)) return fail(std::string("reverb: ") + why);
-    Vertex& v = add_fx_vertex(g, name, gain, angle, wet, K_REVERB);
-    v.reverb_room = room;
-    v.reverb_damp = damp;
-    v.reverb_width = width;
-    v.reverb_size = size;
-    v.first_pending = true;   // (the state block, once it exists, is read only where the vertex itself has written it)
-    return 1;
+    FxParams p{};
+    p.reverb = {room, damp, width, size};
+    return add_fx(g, K_REVERB, name, gain, angle, wet, p);
 }
 int td_reverb_params(size_t sr, float room, float damp, float width, float size, double out[31]) {
     if (!out) return fail("reverb_params: out is null");
-    if (const char* why = reverb::check(sr, room, damp, width, size)) return fail(std::string("reverb: ") + why);
+    FxParams p{};
+    p.reverb = {room, damp, width, size};
+    if (!fx_check(K_REVERB, sr, p)) return 0;
     reverb::params(sr, room, damp, width, size, out);
     return 1;
 }
 
-// This engine's own noise gate vertex (no reference counterpart; the definition is in include/termdaw_amd.h).
 int td_graph_add_gate(td_graph* g, const char* name, float gain, float angle, float wet, float threshold_db, float hysteresis_db,
                       float hold_ms, float attack_ms, float release_ms, float range_db) {
-    if (const char* why = gate::check(threshold_db, hysteresis_db, hold_ms, attack_ms, release_ms, range_db)) return fail(std::string("gate: ") + why);
-    Vertex& v = add_fx_vertex(g, name, gain, angle, wet, K_GATE);
-    v.gate_threshold_db = threshold_db;
-    v.gate_hysteresis_db = hysteresis_db;
-    v.gate_hold_ms = hold_ms;
-    v.gate_attack_ms = attack_ms;
-    v.gate_release_ms = release_ms;
-    v.gate_range_db = range_db;
-    fx_kind(K_GATE)->put_rest(g, v, &g->hstate[(size_t)v.state_slot]);   // (closed: it depends on the parameters)
-    return 1;
+    FxParams p{};
+    p.gate = {threshold_db, hysteresis_db, hold_ms, attack_ms, release_ms, range_db};
+    return add_fx(g, K_GATE, name, gain, angle, wet, p);
 }
 int td_gate_params(size_t sr, float threshold_db, float hysteresis_db, float hold_ms, float attack_ms, float release_ms, float range_db,
                    double out[6]) {
     if (!out) return fail("gate_params: out is null");
-    if (const char* why = gate::check(threshold_db, hysteresis_db, hold_ms, attack_ms, release_ms, range_db)) return fail(std::string("gate: ") + why);
+    FxParams p{};
+    p.gate = {threshold_db, hysteresis_db, hold_ms, attack_ms, release_ms, range_db};
+    if (!fx_check(K_GATE, sr, p)) return 0;
     gate::params(sr, threshold_db, hysteresis_db, hold_ms, attack_ms, release_ms, range_db, out);
     return 1;
 }
 
-// (over the union of input and key edges: a key source is computed before the vertex it keys, like an input)
-// This engine's own phaser vertex (no reference counterpart; the definition is in include/termdaw_amd.h).
 int td_graph_add_phaser(td_graph* g, const char* name, float gain, float angle, float wet, int stages, float lo_hz, float hi_hz,
                         float rate_hz, float feedback, float stereo, int shape) {
-    if (const char* why = phaser::check(g->sr, stages, lo_hz, hi_hz, rate_hz, feedback, stereo, shape)) return fail(std::string("phaser: ") + why);
-    Vertex& v = add_fx_vertex(g, name, gain, angle, wet, K_PHASER);   // (its slots: a tdk::PhaserState)
-    v.phaser_stages = stages;
-    v.phaser_shape = shape;
-    v.phaser_lo_hz = lo_hz;
-    v.phaser_hi_hz = hi_hz;
-    v.phaser_rate_hz = rate_hz;
-    v.phaser_feedback = feedback;
-    v.phaser_stereo = stereo;
-    return 1;
+    FxParams p{};
+    p.phaser = {stages, lo_hz, hi_hz, rate_hz, feedback, stereo, shape};
+    return add_fx(g, K_PHASER, name, gain, angle, wet, p);
 }
 int td_phaser_params(size_t sr, int stages, float lo_hz, float hi_hz, float rate_hz, float feedback, float stereo, int shape, double out[7]) {
     if (!out) return fail("phaser_params: out is null");
-    if (const char* why = phaser::check(sr, stages, lo_hz, hi_hz, rate_hz, feedback, stereo, shape)) return fail(std::string("phaser: ") + why);
+    FxParams p{};
+    p.phaser = {stages, lo_hz, hi_hz, rate_hz, feedback, stereo, shape};
+    if (!fx_check(K_PHASER, sr, p)) return 0;
     phaser::params(sr, stages, lo_hz, hi_hz, rate_hz, feedback, stereo, shape, out);
     return 1;
 }
 
-// This engine's own vocoder vertex (no reference counterpart; the definition is in include/termdaw_amd.h).  Its state is a
-// carried line (7 doubles per band), allocated when the vertex is first compiled into a submission.
 int td_graph_add_vocoder(td_graph* g, const char* name, float gain, float angle, float wet, int bands, float lo_hz, float hi_hz, float q,
                          float response_ms, float out_db) {
-    if (const char* why = vocoder::check(g->sr, bands, lo_hz, hi_hz, q, response_ms, out_db)) return fail(std::string("vocoder: ") + why);
-    Vertex& v = add_fx_vertex(g, name, gain, angle, wet, K_VOCODER);
-    v.voc_bands = bands;
-    v.voc_lo_hz = lo_hz;
-    v.voc_hi_hz = hi_hz;
-    v.voc_q = q;
-    v.voc_response_ms = response_ms;
-    v.voc_out_db = out_db;
-    return 1;
+    FxParams p{};
+    p.vocoder = {bands, lo_hz, hi_hz, q, response_ms, out_db};
+    return add_fx(g, K_VOCODER, name, gain, angle, wet, p);
 }
 int td_vocoder_params(size_t sr, int bands, float lo_hz, float hi_hz, float q, float response_ms, float out_db, double* out, size_t cap) {
     if (!out) return fail("vocoder_params: out is null");
-    if (const char* why = vocoder::check(sr, bands, lo_hz, hi_hz, q, response_ms, out_db)) return fail(std::string("vocoder: ") + why);
+    FxParams p{};
+    p.vocoder = {bands, lo_hz, hi_hz, q, response_ms, out_db};
+    if (!fx_check(K_VOCODER, sr, p)) return 0;
     if (cap < vocoder::n_params(bands)) return fail("vocoder_params: out holds fewer than 6 bands + 2 doubles");
     vocoder::params(sr, bands, lo_hz, hi_hz, q, response_ms, out_db, out);
     return 1;
 }
 
-// This engine's own filter vertex (no reference counterpart; the definition is in include/termdaw_amd.h).
 int td_graph_add_filter(td_graph* g, const char* name, float gain, float angle, float wet, int kind, float freq_hz, float q,
                         float lfo_oct, float rate_hz, float stereo, int shape, float env_oct, float sens_db, float attack_ms, float release_ms) {
-    if (const char* why = filter::check(g->sr, kind, freq_hz, q, lfo_oct, rate_hz, stereo, shape, env_oct, sens_db, attack_ms, release_ms))
-        return fail(std::string("filter: ") + why);
-    Vertex& v = add_fx_vertex(g, name, gain, angle, wet, K_FILTER);   // (its slots: a tdk::FiltState)
-    v.filt_kind = kind;
-    v.filt_shape = shape;
-    v.filt_freq_hz = freq_hz;
-    v.filt_q = q;
-    v.filt_lfo_oct = lfo_oct;
-    v.filt_rate_hz = rate_hz;
-    v.filt_stereo = stereo;
-    v.filt_env_oct = env_oct;
-    v.filt_sens_db = sens_db;
-    v.filt_attack_ms = attack_ms;
-    v.filt_release_ms = release_ms;
-    return 1;
+    FxParams p{};
+    p.filter = {kind, freq_hz, q, lfo_oct, rate_hz, stereo, shape, env_oct, sens_db, attack_ms, release_ms};
+    return add_fx(g, K_FILTER, name, gain, angle, wet, p);
 }
 int td_filter_params(size_t sr, int kind, float freq_hz, float q, float lfo_oct, float rate_hz, float stereo, int shape, float env_oct,
                      float sens_db, float attack_ms, float release_ms, double* out, size_t cap) {
     if (!out) return fail("filter_params: out is null");
-    if (const char* why = filter::check(sr, kind, freq_hz, q, lfo_oct, rate_hz, stereo, shape, env_oct, sens_db, attack_ms, release_ms))
-        return fail(std::string("filter: ") + why);
+    FxParams p{};
+    p.filter = {kind, freq_hz, q, lfo_oct, rate_hz, stereo, shape, env_oct, sens_db, attack_ms, release_ms};
+    if (!fx_check(K_FILTER, sr, p)) return 0;
     if (cap < (size_t)filter::kParams) return fail("filter_params: out holds fewer than 11 doubles");
     filter::params(sr, kind, freq_hz, q, lfo_oct, rate_hz, stereo, shape, env_oct, sens_db, attack_ms, release_ms, out);
     return 1;
 }
 
-// This engine's own limiter vertex (no reference counterpart; the definition is in include/termdaw_amd.h).  Its state is a
-// carried line (u, and the e and the raw input of the last L - 1 frames), allocated when the vertex is first compiled into a submission.
 int td_graph_add_limiter(td_graph* g, const char* name, float gain, float angle, float wet, float ceiling_db, float lookahead_ms,
                          float release_ms, float drive_db) {
-    if (const char* why = limiter::check(g->sr, ceiling_db, lookahead_ms, release_ms, drive_db)) return fail(std::string("limiter: ") + why);
-    Vertex& v = add_fx_vertex(g, name, gain, angle, wet, K_LIMITER);
-    v.lim_ceiling_db = ceiling_db;
-    v.lim_lookahead_ms = lookahead_ms;
-    v.lim_release_ms = release_ms;
-    v.lim_drive_db = drive_db;
-    return 1;
+    FxParams p{};
+    p.limiter = {ceiling_db, lookahead_ms, release_ms, drive_db};
+    return add_fx(g, K_LIMITER, name, gain, angle, wet, p);
 }
 int td_limiter_params(size_t sr, float ceiling_db, float lookahead_ms, float release_ms, float drive_db, double out[5]) {
     if (!out) return fail("limiter_params: out is null");
-    if (const char* why = limiter::check(sr, ceiling_db, lookahead_ms, release_ms, drive_db)) return fail(std::string("limiter: ") + why);
+    FxParams p{};
+    p.limiter = {ceiling_db, lookahead_ms, release_ms, drive_db};
+    if (!fx_check(K_LIMITER, sr, p)) return 0;
     limiter::params(sr, ceiling_db, lookahead_ms, release_ms, drive_db, out);
     return 1;
 }
 
-// This engine's own multiband vertex (no reference counterpart; the definition is in include/termdaw_amd.h).  Its state is a
-// carried line (42 doubles), allocated when the vertex is first compiled into a submission.
+// (nullptr: the per-band pointers do not each point at three floats, g_error says so)
+static const MbParams* mb_block(MbParams* p, float lo_hz, float hi_hz, const float threshold_db[3], const float ratio[3], float attack_ms,
+                                float release_ms, float knee_db, const float makeup_db[3]) {
+    if (!threshold_db || !ratio || !makeup_db) {
+        fail("multiband: threshold_db, ratio and makeup_db must point at three floats each");
+        return nullptr;
+    }
+    *p = MbParams{lo_hz, hi_hz, {threshold_db[0], threshold_db[1], threshold_db[2]}, {ratio[0], ratio[1], ratio[2]}, attack_ms, release_ms, knee_db,
+                  {makeup_db[0], makeup_db[1], makeup_db[2]}};
+    return p;
+}
 int td_graph_add_multiband(td_graph* g, const char* name, float gain, float angle, float wet, float lo_hz, float hi_hz,
                            const float threshold_db[3], const float ratio[3], float attack_ms, float release_ms, float knee_db,
                            const float makeup_db[3]) {
-    if (!threshold_db || !ratio || !makeup_db) return fail("multiband: threshold_db, ratio and makeup_db must point at three floats each");
-    if (const char* why = multiband::check(g->sr, lo_hz, hi_hz, threshold_db, ratio, attack_ms, release_ms, knee_db, makeup_db))
-        return fail(std::string("multiband: ") + why);
-    Vertex& v = add_fx_vertex(g, name, gain, angle, wet, K_MULTIBAND);
-    v.mb_lo_hz = lo_hz;
-    v.mb_hi_hz = hi_hz;
-    v.mb_attack_ms = attack_ms;
-    v.mb_release_ms = release_ms;
-    v.mb_knee_db = knee_db;
-    for (int b = 0; b < 3; ++b) {
-        v.mb_threshold_db[b] = threshold_db[b];
-        v.mb_ratio[b] = ratio[b];
-        v.mb_makeup_db[b] = makeup_db[b];
-    }
-    return 1;
+    FxParams p{};
+    if (!mb_block(&p.mb, lo_hz, hi_hz, threshold_db, ratio, attack_ms, release_ms, knee_db, makeup_db)) return 0;
+    return add_fx(g, K_MULTIBAND, name, gain, angle, wet, p);
 }
 int td_multiband_params(size_t sr, float lo_hz, float hi_hz, const float threshold_db[3], const float ratio[3], float attack_ms,
                         float release_ms, float knee_db, const float makeup_db[3], double* out, size_t n) {
     if (!out) return fail("multiband_params: out is null");
-    if (!threshold_db || !ratio || !makeup_db) return fail("multiband: threshold_db, ratio and makeup_db must point at three floats each");
-    if (const char* why = multiband::check(sr, lo_hz, hi_hz, threshold_db, ratio, attack_ms, release_ms, knee_db, makeup_db))
-        return fail(std::string("multiband: ") + why);
+    FxParams p{};
+    if (!mb_block(&p.mb, lo_hz, hi_hz, threshold_db, ratio, attack_ms, release_ms, knee_db, makeup_db) || !fx_check(K_MULTIBAND, sr, p)) return 0;
     if (n < (size_t)multiband::kParams) return fail("multiband_params: out holds fewer than 27 doubles");
     multiband::params(sr, lo_hz, hi_hz, attack_ms, release_ms, out);
     return 1;
 }
 
-// This engine's own convolution vertex (no reference counterpart; the definition is in include/termdaw_amd.h).  Its state is a
-// carried line (the last D + Lh - 1 input frames) beside the response's partition spectra, both allocated when the vertex is first
-// compiled into a submission: the response is the bank's sample, which only a render brings.
+// (the response is the bank's sample, which only a render brings: its length is judged there, and where the bank is at hand)
 int td_graph_add_convolution(td_graph* g, const char* name, float gain, float angle, float wet, size_t sample_index, float length_ms,
                              float predelay_ms, float out_db, int norm) {
-    if (const char* why = conv::check(g->sr, length_ms, predelay_ms, out_db, norm)) return fail(std::string("convolution: ") + why);
-    Vertex& v = add_fx_vertex(g, name, gain, angle, wet, K_CONVOLUTION);
-    v.sample_index = sample_index;
-    v.conv_length_ms = length_ms;
-    v.conv_predelay_ms = predelay_ms;
-    v.conv_out_db = out_db;
-    v.conv_norm = norm;
-    return 1;
+    FxParams p{};
+    p.conv = {length_ms, predelay_ms, out_db, norm};
+    return add_fx(g, K_CONVOLUTION, name, gain, angle, wet, p, sample_index);
 }
 int td_convolution_params(size_t sr, size_t sample_len, float length_ms, float predelay_ms, float out_db, int norm, double out[6]) {
     if (!out) return fail("convolution_params: out is null");
-    if (const char* why = conv::check(sr, length_ms, predelay_ms, out_db, norm)) return fail(std::string("convolution: ") + why);
+    FxParams p{};
+    p.conv = {length_ms, predelay_ms, out_db, norm};
+    if (!fx_check(K_CONVOLUTION, sr, p)) return 0;
     if (const char* why = conv::check_len(sr, sample_len, length_ms)) return fail(std::string("convolution: ") + why);
     conv::params(sr, sample_len, length_ms, predelay_ms, out_db, out);
     return 1;

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/termdaw_amd.h"
+#include "fx_params.h"
 #include "kernels.h"
 
 namespace tde {
@@ -127,30 +128,9 @@ struct Vertex {
     bool exact_sin = false;   // (debug_sine, synth) the graph's "sine_mode" option at the last set_option / add: glibc's sinf on the device
     bool probe = false;       // (debug_sine, synth; set per chunk by compile_chunk) sine_mode 2: the fast form, its deviation measured by k_sine_probe
     float lgamma = 0, hgamma = 0;
-    float threshold_db = 0, ratio = 1, attack_ms = 0, release_ms = 1, knee_db = 0, makeup_db = 0;   // K_COMPRESSOR
-    int eq_kind = 0;   // K_EQ: TD_EQ_*
-    float eq_freq = 1000, eq_q = 1, eq_gain_db = 0;
-    float delay_ms = 1, delay_feedback = 0, delay_cross = 0;   // K_DELAY
-    int sat_kind = 0, sat_oversample = 1;   // K_SATURATOR: TD_SAT_*, R
-    float sat_drive_db = 0, sat_bias = 0, sat_out_db = 0;
-    int chorus_voices = 1, chorus_shape = 0;   // K_CHORUS: V, TD_CHORUS_*
-    float chorus_delay_ms = 1, chorus_depth_ms = 0, chorus_rate_hz = 1, chorus_stereo = 0;
-    float reverb_room = 0.5f, reverb_damp = 0.5f, reverb_width = 1.0f, reverb_size = 1.0f;   // K_REVERB
-    float gate_threshold_db = 0, gate_hysteresis_db = 0, gate_hold_ms = 0, gate_attack_ms = 0, gate_release_ms = 1, gate_range_db = 0;   // K_GATE
-    int phaser_stages = 2, phaser_shape = 0;   // K_PHASER: N, TD_CHORUS_*
-    float phaser_lo_hz = 20, phaser_hi_hz = 20, phaser_rate_hz = 1, phaser_feedback = 0, phaser_stereo = 0;
-    int voc_bands = 4;   // K_VOCODER: B
-    float voc_lo_hz = 40, voc_hi_hz = 80, voc_q = 1, voc_response_ms = 10, voc_out_db = 0;
-    int filt_kind = 0, filt_shape = 0;   // K_FILTER: TD_FILTER_*, TD_CHORUS_*
-    float filt_freq_hz = 1000, filt_q = 1, filt_lfo_oct = 0, filt_rate_hz = 1, filt_stereo = 0;
-    float filt_env_oct = 0, filt_sens_db = 0, filt_attack_ms = 0, filt_release_ms = 1;
-    float lim_ceiling_db = 0, lim_lookahead_ms = 0, lim_release_ms = 1, lim_drive_db = 0;   // K_LIMITER
-    float mb_lo_hz = 40, mb_hi_hz = 80, mb_attack_ms = 0, mb_release_ms = 1, mb_knee_db = 0;   // K_MULTIBAND
-    float mb_threshold_db[3] = {0, 0, 0}, mb_ratio[3] = {1, 1, 1}, mb_makeup_db[3] = {0, 0, 0};   // ... per band: low, mid, high
-    float conv_length_ms = 0, conv_predelay_ms = 0, conv_out_db = 0;   // K_CONVOLUTION (the response: sample_index)
-    int conv_norm = 0;
+    FxParams fx{};   // an effect kind: the block of its kind (fx_params.h)
     // a filter vertex whose follower runs: env_oct != 0 (otherwise y1, e stay as they are and key edges are ignored)
-    bool filt_follows() const { return filt_env_oct != 0.0f; }
+    bool filt_follows() const { return fx.filter.env_oct != 0.0f; }
     // a vertex with key edges reads them: it is not dry, and a filter's follower runs
     bool reads_key() const { return !(wet < 0.0001f) && (kind != K_FILTER || filt_follows()); }
     // The block of device memory a delay, saturator, chorus, reverb, vocoder, limiter or multiband vertex carries from chunk to chunk: allocated when the vertex

@@ -10,11 +10,21 @@ namespace tde {
 namespace eq {
 
 constexpr int kKinds = 7;   // TD_EQ_LOWPASS .. TD_EQ_HIGHSHELF
-inline const char* kind_name(int kind) {
+inline const char* const* kind_names() {   // (the script line's names, in the constants' order)
     static const char* const n[kKinds] = {"lowpass", "highpass", "bandpass", "notch", "peak", "lowshelf", "highshelf"};
-    return kind >= 0 && kind < kKinds ? n[kind] : "?";
+    return n;
 }
 inline bool kind_has_gain(int kind) { return kind >= 4; }
+// nullptr: fine, otherwise the reason.  rate_free: only the ranges that do not depend on the rate -- what a script line can be held
+// to, whose render rate comes with the graph (freq_hz's upper end fails when the graph is built)
+inline const char* check(size_t sr, int kind, float freq_hz, float q, float gain_db, bool rate_free = false) {
+    if (!(kind >= 0 && kind < kKinds)) return "kind must be one of TD_EQ_LOWPASS .. TD_EQ_HIGHSHELF (0 .. 6)";
+    if (!rate_free && !sr) return "the sample rate must be positive";
+    if (!(freq_hz >= 10.0f && (rate_free || 20.0 * (double)freq_hz <= 9.0 * (double)sr))) return "freq_hz must lie in [10, 0.45 sr] Hz";
+    if (!(q >= 0.1f && q <= 20.0f)) return "q must lie in [0.1, 20]";
+    if (kind_has_gain(kind) && !(gain_db >= -24.0f && gain_db <= 24.0f)) return "gain_db must lie in [-24, 24] dB";
+    return nullptr;
+}
 
 // (b0, b1, b2, a1, a2), normalised by a0.  f64 from the f32 parameters, widened; 1 - cos w0 as 2 sin^2(w0 / 2), which has no
 // cancellation at low frequencies.

@@ -53,6 +53,10 @@ inline void params(size_t sr, int /*kind*/, float freq_hz, float q, float lfo_oc
     out[10] = pole((double)release_ms, r);
 }
 
+inline const char* const* kind_names() {   // (the script line's names, TD_FILTER_* in order)
+    static const char* const n[4] = {"lowpass", "highpass", "bandpass", "notch"};
+    return n;
+}
 // nullptr, or what is wrong: the message names the parameter (a NaN fails every comparison, an infinity the far end)
 inline const char* check(size_t sr, int kind, float freq_hz, float q, float lfo_oct, float rate_hz, float stereo, int shape,
                          float env_oct, float sens_db, float attack_ms, float release_ms) {

@@ -16,19 +16,10 @@
 
 #include <hip/hip_runtime.h>
 
-#include "engine.h"
-#include "chorus_math.h"
-#include "devmem.h"
-#include "eq_math.h"
-#include "gate_math.h"
-#include "phaser_math.h"
-#include "vocoder_math.h"
-#include "filter_math.h"
-#include "limiter_math.h"
+#include "compile.h"
 #include "conv_math.h"
-#include "multiband_math.h"
+#include "devmem.h"
 #include "lua_subset.h"
-#include "reverb_math.h"
 #include "master.h"
 #include "wav.h"
 #include "midi.h"
@@ -113,19 +104,65 @@ struct SampsynCall { std::string name; float gain, angle; std::string floww; std
 struct Lv2fxCall { std::string name; float gain, angle, wet; std::string plugin; };
 struct AdsrCall { std::string name; float gain, angle, wet; std::string floww; bool use_off, use_max; int note; std::vector<float> conf; };
 struct BandCall { std::string name; float gain, angle, wet, lo, hi; bool pass; };
-struct CompCall { std::string name; float gain, angle, wet, threshold_db, ratio, attack_ms, release_ms, knee_db, makeup_db; };
-struct EqCall { std::string name; float gain, angle, wet; int kind; float freq_hz, q, gain_db; };
-struct DelayCall { std::string name; float gain, angle, wet, time_ms, feedback, cross; };
-struct ChorusCall { std::string name; float gain, angle, wet; int voices; float delay_ms, depth_ms, rate_hz, stereo; int shape; };
-struct ReverbCall { std::string name; float gain, angle, wet, room, damp, width, size; };
-struct PhaserCall { std::string name; float gain, angle, wet; int stages; float lo_hz, hi_hz, rate_hz, feedback, stereo; int shape; };
-struct VocoderCall { std::string name; float gain, angle, wet; int bands; float lo_hz, hi_hz, q, response_ms, out_db; };
-struct FilterCall { std::string name; float gain, angle, wet; int kind; float freq_hz, q, lfo_oct, rate_hz, stereo; int shape; float env_oct, sens_db, attack_ms, release_ms; };
-struct LimiterCall { std::string name; float gain, angle, wet, ceiling_db, lookahead_ms, release_ms, drive_db; };
-struct ConvolutionCall { std::string name; float gain, angle, wet; std::string sample; float length_ms, predelay_ms, out_db; int norm; };
-struct MultibandCall { std::string name; float gain, angle, wet, lo_hz, hi_hz, threshold_db[3], ratio[3], attack_ms, release_ms, knee_db, makeup_db[3]; };
-struct GateCall { std::string name; float gain, angle, wet, threshold_db, hysteresis_db, hold_ms, attack_ms, release_ms, range_db; };
-struct SatCall { std::string name; float gain, angle, wet; int kind; float drive_db, bias, out_db; int oversample; };
+// a line of an effect kind (compile.h FxKind::script): the block as the schema binds it; sample: a convolution's response, by name
+struct FxCall { Kind kind; std::string name; float gain, angle, wet; FxParams p; std::string sample; };
+// The groups of effect vertices in the order the graph is rebuilt in, each group in call order.  NOT the table's order: the
+// convolution vertices stand in front of the multiband ones (the table, and workloads.py's ProjectScript.build, have them the
+// other way round).  Vertex indices follow from this order, so it stays.
+const Kind kFxReplayOrder[] = {K_COMPRESSOR, K_EQ, K_DELAY, K_SATURATOR, K_CHORUS, K_REVERB, K_GATE, K_PHASER, K_VOCODER, K_FILTER, K_LIMITER,
+                               K_CONVOLUTION, K_MULTIBAND};
+
+// One line of an effect kind by the kind's schema: (name, gain, angle, wet), then the parameters in the schema's order.  Of several
+// faults a line names the first unknown name, then the first number that is none of an integer parameter's values, then what the
+// kind's check says -- as much of it as the line is held to (FxKind::line_check).  Every argument is converted first, so an
+// argument of the wrong type (a table where a number belongs) is named before any of those.  Appends the canonical line to `dump`.
+FxCall bind_fx(const FxKind& fx, const std::vector<Value>& a, size_t psr, std::string* dump) {
+    const char* f = fx.script;
+    FxCall c{fx.kind, to_str(f, a, 0), to_f32(f, a, 1), to_f32(f, a, 2), to_f32(f, a, 3), FxParams{}, ""};
+    std::vector<std::string> text((size_t)fx.n_params);
+    std::vector<float> num((size_t)fx.n_params);
+    for (int i = 0; i < fx.n_params; ++i) {
+        const FxParam& p = fx.params[i];
+        if (p.type == FxParam::NAME || p.type == FxParam::SAMPLE) text[(size_t)i] = to_str(f, a, 4 + (size_t)i);
+        else num[(size_t)i] = to_f32(f, a, 4 + (size_t)i);
+    }
+    auto field = [&](const FxParam& p) { return (char*)&c.p + p.offset; };
+    for (int i = 0; i < fx.n_params; ++i) {
+        const FxParam& p = fx.params[i];
+        if (p.type != FxParam::NAME) continue;
+        int k = 0;
+        while (k < p.n_names && text[(size_t)i] != p.names[k]) ++k;
+        if (k == p.n_names) {
+            std::string all;
+            for (int j = 0; j < p.n_names; ++j) all += std::string(j ? ", " : "") + p.names[j];
+            throw LuaError{std::string(fx.script_prefix) + "unknown " + p.name + " \"" + text[(size_t)i] + "\" (one of " + all + ")"};
+        }
+        memcpy(field(p), &k, sizeof k);
+    }
+    for (int i = 0; i < fx.n_params; ++i) {
+        const FxParam& p = fx.params[i];
+        if (p.type != FxParam::INT) continue;
+        const float x = num[(size_t)i];
+        if (!(x >= 0.0f && x < 32.0f && x == floorf(x) && (p.allowed >> (int)x & 1u))) throw LuaError{std::string(fx.script_prefix) + p.name + " must be " + p.domain};
+        const int k = (int)x;
+        memcpy(field(p), &k, sizeof k);
+    }
+    std::string line;   // (the arguments as the dump prints them: no spaces)
+    for (int i = 0; i < fx.n_params; ++i) {
+        const FxParam& p = fx.params[i];
+        const size_t u = (size_t)i;
+        switch (p.type) {
+            case FxParam::F32: memcpy(field(p), &num[u], sizeof(float)); line += "," + fnum(num[u]); break;
+            case FxParam::INT: line += "," + std::to_string((int)num[u]); break;
+            case FxParam::SAMPLE: c.sample = text[u]; [[fallthrough]];   // (printed like a name)
+            case FxParam::NAME: line += ",\"" + text[u] + "\""; break;
+        }
+    }
+    if (fx.line_check != FxKind::LINE_NONE)
+        if (const char* why = fx.check(psr, c.p, fx.line_check == FxKind::LINE_RATE_FREE)) throw LuaError{std::string(fx.script_prefix) + why};
+    *dump += std::string(f) + "(\"" + c.name + "\"," + fnum(c.gain) + "," + fnum(c.angle) + "," + fnum(c.wet) + line + ")\n";
+    return c;
+}
 
 using Triple = std::tuple<std::string, std::string, std::string>;
 
@@ -241,19 +278,7 @@ int do_refresh(td_state* s, const std::string& contents) {
     std::vector<Lv2fxCall> lv2fxs;
     std::vector<AdsrCall> adsrs;
     std::vector<BandCall> bandpasses;
-    std::vector<CompCall> compressors;
-    std::vector<EqCall> eqs;
-    std::vector<DelayCall> delays;
-    std::vector<SatCall> saturators;
-    std::vector<ChorusCall> choruses;
-    std::vector<ReverbCall> reverbs;
-    std::vector<GateCall> gates;
-    std::vector<PhaserCall> phasers;
-    std::vector<VocoderCall> vocoders;
-    std::vector<FilterCall> filters;
-    std::vector<LimiterCall> limiters;
-    std::vector<MultibandCall> multibands;
-    std::vector<ConvolutionCall> convolutions;
+    std::vector<FxCall> fx_calls;
     size_t cs = s->cs, render_sr = s->render_sr, bd = s->bd;
     // std::mem::take (state.rs:79-80): the locals start from the previous values, the State's own fields are left
     // EMPTY until the script has run (state.rs:169-170) -- so they stay empty when the script fails
@@ -398,190 +423,14 @@ int do_refresh(td_state* s, const std::string& contents) {
         dump += std::string(f) + "(\"" + c.name + "\"," + fnum(c.gain) + "," + fnum(c.angle) + "," + fnum(c.wet) + "," + fnum(c.lo) + "," + fnum(c.hi) + "," + (c.pass ? "true" : "false") + ")\n";
         return Value::nil();
     });
-    lua.set_function("add_compressor", [&](const std::vector<Value>& a) {   // this engine's own vertex (termdaw_amd.h td_graph_add_compressor)
-        const char* f = "add_compressor";
-        compressors.push_back({to_str(f, a, 0), to_f32(f, a, 1), to_f32(f, a, 2), to_f32(f, a, 3), to_f32(f, a, 4), to_f32(f, a, 5), to_f32(f, a, 6),
-                               to_f32(f, a, 7), to_f32(f, a, 8), to_f32(f, a, 9)});
-        auto& c = compressors.back();
-        dump += std::string(f) + "(\"" + c.name + "\"," + fnum(c.gain) + "," + fnum(c.angle) + "," + fnum(c.wet) + "," + fnum(c.threshold_db) + "," + fnum(c.ratio) + "," +
-                fnum(c.attack_ms) + "," + fnum(c.release_ms) + "," + fnum(c.knee_db) + "," + fnum(c.makeup_db) + ")\n";
-        return Value::nil();
-    });
-    lua.set_function("add_eq", [&](const std::vector<Value>& a) {   // this engine's own vertex (termdaw_amd.h td_graph_add_eq); kind by name
-        const char* f = "add_eq";
-        const std::string kind = to_str(f, a, 4);
-        int k = 0;
-        while (k < eq::kKinds && kind != eq::kind_name(k)) ++k;
-        if (k == eq::kKinds)
-            throw LuaError{"add_eq: unknown kind \"" + kind + "\" (one of lowpass, highpass, bandpass, notch, peak, lowshelf, highshelf)"};
-        eqs.push_back({to_str(f, a, 0), to_f32(f, a, 1), to_f32(f, a, 2), to_f32(f, a, 3), k, to_f32(f, a, 5), to_f32(f, a, 6), to_f32(f, a, 7)});
-        auto& c = eqs.back();
-        // the ranges that do not depend on the render rate are rejected here, where the line is known; freq_hz's upper end when
-        // the graph is built (td_graph_add_eq)
-        if (!(c.freq_hz >= 10.0f)) throw LuaError{"add_eq: freq_hz must lie in [10, 0.45 sr] Hz"};
-        if (!(c.q >= 0.1f && c.q <= 20.0f)) throw LuaError{"add_eq: q must lie in [0.1, 20]"};
-        if (eq::kind_has_gain(k) && !(c.gain_db >= -24.0f && c.gain_db <= 24.0f)) throw LuaError{"add_eq: gain_db must lie in [-24, 24] dB"};
-        dump += std::string(f) + "(\"" + c.name + "\"," + fnum(c.gain) + "," + fnum(c.angle) + "," + fnum(c.wet) + ",\"" + kind + "\"," + fnum(c.freq_hz) + "," +
-                fnum(c.q) + "," + fnum(c.gain_db) + ")\n";
-        return Value::nil();
-    });
-    lua.set_function("add_delay", [&](const std::vector<Value>& a) {   // this engine's own vertex (termdaw_amd.h td_graph_add_delay)
-        const char* f = "add_delay";
-        delays.push_back({to_str(f, a, 0), to_f32(f, a, 1), to_f32(f, a, 2), to_f32(f, a, 3), to_f32(f, a, 4), to_f32(f, a, 5), to_f32(f, a, 6)});
-        auto& c = delays.back();
-        // (out-of-range parameters are rejected here, where the line is known)
-        if (!(c.time_ms >= 1.0f && c.time_ms <= 2000.0f)) throw LuaError{"add_delay: time_ms must lie in [1, 2000] ms"};
-        if (!(c.feedback >= 0.0f && c.feedback <= 0.98f)) throw LuaError{"add_delay: feedback must lie in [0, 0.98]"};
-        if (!(c.cross >= 0.0f && c.cross <= 1.0f)) throw LuaError{"add_delay: cross must lie in [0, 1]"};
-        dump += std::string(f) + "(\"" + c.name + "\"," + fnum(c.gain) + "," + fnum(c.angle) + "," + fnum(c.wet) + "," + fnum(c.time_ms) + "," +
-                fnum(c.feedback) + "," + fnum(c.cross) + ")\n";
-        return Value::nil();
-    });
-    lua.set_function("add_saturator", [&](const std::vector<Value>& a) {   // this engine's own vertex (termdaw_amd.h td_graph_add_saturator); kind by name
-        const char* f = "add_saturator";
-        static const char* const kinds[3] = {"hard", "cubic", "soft"};
-        const std::string kind = to_str(f, a, 4);
-        int k = 0;
-        while (k < 3 && kind != kinds[k]) ++k;
-        if (k == 3) throw LuaError{"add_saturator: unknown kind \"" + kind + "\" (one of hard, cubic, soft)"};
-        const float over = to_f32(f, a, 8);
-        saturators.push_back({to_str(f, a, 0), to_f32(f, a, 1), to_f32(f, a, 2), to_f32(f, a, 3), k, to_f32(f, a, 5), to_f32(f, a, 6), to_f32(f, a, 7), (int)over});
-        auto& c = saturators.back();
-        // (out-of-range parameters are rejected here, where the line is known)
-        if (!(over == 1.0f || over == 2.0f || over == 4.0f || over == 8.0f)) throw LuaError{"add_saturator: oversample must be 1, 2, 4 or 8"};
-        if (!(c.drive_db >= -24.0f && c.drive_db <= 48.0f)) throw LuaError{"add_saturator: drive_db must lie in [-24, 48] dB"};
-        if (!(c.bias >= -1.0f && c.bias <= 1.0f)) throw LuaError{"add_saturator: bias must lie in [-1, 1]"};
-        if (!(c.out_db >= -48.0f && c.out_db <= 24.0f)) throw LuaError{"add_saturator: out_db must lie in [-48, 24] dB"};
-        dump += std::string(f) + "(\"" + c.name + "\"," + fnum(c.gain) + "," + fnum(c.angle) + "," + fnum(c.wet) + ",\"" + kind + "\"," + fnum(c.drive_db) + "," +
-                fnum(c.bias) + "," + fnum(c.out_db) + "," + std::to_string(c.oversample) + ")\n";
-        return Value::nil();
-    });
-    lua.set_function("add_chorus", [&](const std::vector<Value>& a) {   // this engine's own vertex (termdaw_amd.h td_graph_add_chorus); shape by name
-        const char* f = "add_chorus";
-        static const char* const shapes[2] = {"sine", "triangle"};
-        const std::string shape = to_str(f, a, 9);
-        int k = 0;
-        while (k < 2 && shape != shapes[k]) ++k;
-        if (k == 2) throw LuaError{"add_chorus: unknown shape \"" + shape + "\" (one of sine, triangle)"};
-        const float voices = to_f32(f, a, 4);
-        if (!(voices == 1.0f || voices == 2.0f || voices == 3.0f || voices == 4.0f)) throw LuaError{"add_chorus: voices must be 1 .. 4"};
-        choruses.push_back({to_str(f, a, 0), to_f32(f, a, 1), to_f32(f, a, 2), to_f32(f, a, 3), (int)voices, to_f32(f, a, 5), to_f32(f, a, 6), to_f32(f, a, 7), to_f32(f, a, 8), k});
-        auto& c = choruses.back();
-        // (out-of-range parameters are rejected here, where the line is known)
-        if (const char* why = tde::chorus::check(psr, c.voices, c.delay_ms, c.depth_ms, c.rate_hz, c.stereo, c.shape)) throw LuaError{std::string("add_chorus: ") + why};
-        dump += std::string(f) + "(\"" + c.name + "\"," + fnum(c.gain) + "," + fnum(c.angle) + "," + fnum(c.wet) + "," + std::to_string(c.voices) + "," + fnum(c.delay_ms) + "," +
-                fnum(c.depth_ms) + "," + fnum(c.rate_hz) + "," + fnum(c.stereo) + ",\"" + shape + "\")\n";
-        return Value::nil();
-    });
-    lua.set_function("add_reverb", [&](const std::vector<Value>& a) {   // this engine's own vertex (termdaw_amd.h td_graph_add_reverb)
-        const char* f = "add_reverb";
-        reverbs.push_back({to_str(f, a, 0), to_f32(f, a, 1), to_f32(f, a, 2), to_f32(f, a, 3), to_f32(f, a, 4), to_f32(f, a, 5), to_f32(f, a, 6), to_f32(f, a, 7)});
-        auto& c = reverbs.back();
-        // (out-of-range parameters are rejected here, where the line is known)
-        if (const char* why = tde::reverb::check(psr, c.room, c.damp, c.width, c.size)) throw LuaError{std::string("add_reverb: ") + why};
-        dump += std::string(f) + "(\"" + c.name + "\"," + fnum(c.gain) + "," + fnum(c.angle) + "," + fnum(c.wet) + "," + fnum(c.room) + "," + fnum(c.damp) + "," +
-                fnum(c.width) + "," + fnum(c.size) + ")\n";
-        return Value::nil();
-    });
-    lua.set_function("add_gate", [&](const std::vector<Value>& a) {   // this engine's own vertex (termdaw_amd.h td_graph_add_gate)
-        const char* f = "add_gate";
-        gates.push_back({to_str(f, a, 0), to_f32(f, a, 1), to_f32(f, a, 2), to_f32(f, a, 3), to_f32(f, a, 4), to_f32(f, a, 5), to_f32(f, a, 6),
-                         to_f32(f, a, 7), to_f32(f, a, 8), to_f32(f, a, 9)});
-        auto& c = gates.back();
-        // (out-of-range parameters are rejected here, where the line is known)
-        if (const char* why = tde::gate::check(c.threshold_db, c.hysteresis_db, c.hold_ms, c.attack_ms, c.release_ms, c.range_db)) throw LuaError{std::string("add_gate: ") + why};
-        dump += std::string(f) + "(\"" + c.name + "\"," + fnum(c.gain) + "," + fnum(c.angle) + "," + fnum(c.wet) + "," + fnum(c.threshold_db) + "," + fnum(c.hysteresis_db) + "," +
-                fnum(c.hold_ms) + "," + fnum(c.attack_ms) + "," + fnum(c.release_ms) + "," + fnum(c.range_db) + ")\n";
-        return Value::nil();
-    });
-    lua.set_function("add_phaser", [&](const std::vector<Value>& a) {   // this engine's own vertex (termdaw_amd.h td_graph_add_phaser); shape by name
-        const char* f = "add_phaser";
-        static const char* const shapes[2] = {"sine", "triangle"};
-        const std::string shape = to_str(f, a, 10);
-        int k = 0;
-        while (k < 2 && shape != shapes[k]) ++k;
-        if (k == 2) throw LuaError{"add_phaser: unknown shape \"" + shape + "\" (one of sine, triangle)"};
-        const float stages = to_f32(f, a, 4);
-        if (!(stages == 2.0f || stages == 4.0f || stages == 6.0f || stages == 8.0f)) throw LuaError{"add_phaser: stages must be 2, 4, 6 or 8"};
-        phasers.push_back({to_str(f, a, 0), to_f32(f, a, 1), to_f32(f, a, 2), to_f32(f, a, 3), (int)stages, to_f32(f, a, 5), to_f32(f, a, 6), to_f32(f, a, 7), to_f32(f, a, 8), to_f32(f, a, 9), k});
-        auto& c = phasers.back();
-        // (out-of-range parameters are rejected here, where the line is known)
-        if (const char* why = tde::phaser::check(psr, c.stages, c.lo_hz, c.hi_hz, c.rate_hz, c.feedback, c.stereo, c.shape)) throw LuaError{std::string("add_phaser: ") + why};
-        dump += std::string(f) + "(\"" + c.name + "\"," + fnum(c.gain) + "," + fnum(c.angle) + "," + fnum(c.wet) + "," + std::to_string(c.stages) + "," + fnum(c.lo_hz) + "," +
-                fnum(c.hi_hz) + "," + fnum(c.rate_hz) + "," + fnum(c.feedback) + "," + fnum(c.stereo) + ",\"" + shape + "\")\n";
-        return Value::nil();
-    });
-    lua.set_function("add_vocoder", [&](const std::vector<Value>& a) {   // this engine's own vertex (termdaw_amd.h td_graph_add_vocoder)
-        const char* f = "add_vocoder";
-        const float bands = to_f32(f, a, 4);
-        if (!(bands == 4.0f || bands == 8.0f || bands == 16.0f)) throw LuaError{"add_vocoder: bands must be 4, 8 or 16"};
-        vocoders.push_back({to_str(f, a, 0), to_f32(f, a, 1), to_f32(f, a, 2), to_f32(f, a, 3), (int)bands, to_f32(f, a, 5), to_f32(f, a, 6), to_f32(f, a, 7), to_f32(f, a, 8), to_f32(f, a, 9)});
-        auto& c = vocoders.back();
-        // (out-of-range parameters are rejected here, where the line is known)
-        if (const char* why = tde::vocoder::check(psr, c.bands, c.lo_hz, c.hi_hz, c.q, c.response_ms, c.out_db)) throw LuaError{std::string("add_vocoder: ") + why};
-        dump += std::string(f) + "(\"" + c.name + "\"," + fnum(c.gain) + "," + fnum(c.angle) + "," + fnum(c.wet) + "," + std::to_string(c.bands) + "," + fnum(c.lo_hz) + "," +
-                fnum(c.hi_hz) + "," + fnum(c.q) + "," + fnum(c.response_ms) + "," + fnum(c.out_db) + ")\n";
-        return Value::nil();
-    });
-    lua.set_function("add_filter", [&](const std::vector<Value>& a) {   // this engine's own vertex (termdaw_amd.h td_graph_add_filter); kind and shape by name
-        const char* f = "add_filter";
-        static const char* const kinds[4] = {"lowpass", "highpass", "bandpass", "notch"};
-        static const char* const shapes[2] = {"sine", "triangle"};
-        const std::string kind = to_str(f, a, 4), shape = to_str(f, a, 10);
-        int k = 0, sh = 0;
-        while (k < 4 && kind != kinds[k]) ++k;
-        if (k == 4) throw LuaError{"add_filter: unknown kind \"" + kind + "\" (one of lowpass, highpass, bandpass, notch)"};
-        while (sh < 2 && shape != shapes[sh]) ++sh;
-        if (sh == 2) throw LuaError{"add_filter: unknown shape \"" + shape + "\" (one of sine, triangle)"};
-        filters.push_back({to_str(f, a, 0), to_f32(f, a, 1), to_f32(f, a, 2), to_f32(f, a, 3), k, to_f32(f, a, 5), to_f32(f, a, 6), to_f32(f, a, 7), to_f32(f, a, 8),
-                           to_f32(f, a, 9), sh, to_f32(f, a, 11), to_f32(f, a, 12), to_f32(f, a, 13), to_f32(f, a, 14)});
-        auto& c = filters.back();
-        // (out-of-range parameters are rejected here, where the line is known)
-        if (const char* why = tde::filter::check(psr, c.kind, c.freq_hz, c.q, c.lfo_oct, c.rate_hz, c.stereo, c.shape, c.env_oct, c.sens_db, c.attack_ms, c.release_ms))
-            throw LuaError{std::string("add_filter: ") + why};
-        dump += std::string(f) + "(\"" + c.name + "\"," + fnum(c.gain) + "," + fnum(c.angle) + "," + fnum(c.wet) + ",\"" + kind + "\"," + fnum(c.freq_hz) + "," + fnum(c.q) + "," +
-                fnum(c.lfo_oct) + "," + fnum(c.rate_hz) + "," + fnum(c.stereo) + ",\"" + shape + "\"," + fnum(c.env_oct) + "," + fnum(c.sens_db) + "," + fnum(c.attack_ms) + "," +
-                fnum(c.release_ms) + ")\n";
-        return Value::nil();
-    });
-    lua.set_function("add_limiter", [&](const std::vector<Value>& a) {   // this engine's own vertex (termdaw_amd.h td_graph_add_limiter)
-        const char* f = "add_limiter";
-        limiters.push_back({to_str(f, a, 0), to_f32(f, a, 1), to_f32(f, a, 2), to_f32(f, a, 3), to_f32(f, a, 4), to_f32(f, a, 5), to_f32(f, a, 6), to_f32(f, a, 7)});
-        auto& c = limiters.back();
-        // (out-of-range parameters are rejected here, where the line is known)
-        if (const char* why = tde::limiter::check(psr, c.ceiling_db, c.lookahead_ms, c.release_ms, c.drive_db)) throw LuaError{std::string("add_limiter: ") + why};
-        dump += std::string(f) + "(\"" + c.name + "\"," + fnum(c.gain) + "," + fnum(c.angle) + "," + fnum(c.wet) + "," + fnum(c.ceiling_db) + "," + fnum(c.lookahead_ms) + "," +
-                fnum(c.release_ms) + "," + fnum(c.drive_db) + ")\n";
-        return Value::nil();
-    });
-    lua.set_function("add_multiband", [&](const std::vector<Value>& a) {   // this engine's own vertex (termdaw_amd.h td_graph_add_multiband)
-        const char* f = "add_multiband";   // (flat; the bands in the order low, mid, high)
-        multibands.push_back({to_str(f, a, 0), to_f32(f, a, 1), to_f32(f, a, 2), to_f32(f, a, 3), to_f32(f, a, 4), to_f32(f, a, 5),
-                              {to_f32(f, a, 6), to_f32(f, a, 7), to_f32(f, a, 8)}, {to_f32(f, a, 9), to_f32(f, a, 10), to_f32(f, a, 11)},
-                              to_f32(f, a, 12), to_f32(f, a, 13), to_f32(f, a, 14), {to_f32(f, a, 15), to_f32(f, a, 16), to_f32(f, a, 17)}});
-        auto& c = multibands.back();
-        // (out-of-range parameters are rejected here, where the line is known)
-        if (const char* why = tde::multiband::check(psr, c.lo_hz, c.hi_hz, c.threshold_db, c.ratio, c.attack_ms, c.release_ms, c.knee_db, c.makeup_db))
-            throw LuaError{std::string("add_multiband: multiband: ") + why};
-        dump += std::string(f) + "(\"" + c.name + "\"," + fnum(c.gain) + "," + fnum(c.angle) + "," + fnum(c.wet) + "," + fnum(c.lo_hz) + "," + fnum(c.hi_hz) + "," +
-                fnum(c.threshold_db[0]) + "," + fnum(c.threshold_db[1]) + "," + fnum(c.threshold_db[2]) + "," + fnum(c.ratio[0]) + "," + fnum(c.ratio[1]) + "," +
-                fnum(c.ratio[2]) + "," + fnum(c.attack_ms) + "," + fnum(c.release_ms) + "," + fnum(c.knee_db) + "," + fnum(c.makeup_db[0]) + "," +
-                fnum(c.makeup_db[1]) + "," + fnum(c.makeup_db[2]) + ")\n";
-        return Value::nil();
-    });
-    lua.set_function("add_convolution", [&](const std::vector<Value>& a) {   // this engine's own vertex (termdaw_amd.h td_graph_add_convolution)
-        const char* f = "add_convolution";
-        const float nf = to_f32(f, a, 8);
-        if (!(nf == 0.0f || nf == 1.0f)) throw LuaError{"add_convolution: convolution: norm must be 0 or 1"};
-        convolutions.push_back({to_str(f, a, 0), to_f32(f, a, 1), to_f32(f, a, 2), to_f32(f, a, 3), to_str(f, a, 4), to_f32(f, a, 5), to_f32(f, a, 6), to_f32(f, a, 7),
-                                nf == 1.0f ? 1 : 0});
-        auto& c = convolutions.back();
-        // (out-of-range parameters are rejected here, where the line is known; the response's length once the bank is loaded)
-        if (const char* why = tde::conv::check(psr, c.length_ms, c.predelay_ms, c.out_db, c.norm)) throw LuaError{std::string("add_convolution: convolution: ") + why};
-        dump += std::string(f) + "(\"" + c.name + "\"," + fnum(c.gain) + "," + fnum(c.angle) + "," + fnum(c.wet) + ",\"" + c.sample + "\"," + fnum(c.length_ms) + "," +
-                fnum(c.predelay_ms) + "," + fnum(c.out_db) + "," + (c.norm ? "1" : "0") + ")\n";
-        return Value::nil();
-    });
+    // this engine's own vertices, the effect kinds: one binder per row of the table (compile.h FxKind; termdaw_amd.h td_graph_add_<kind>)
+    for (Kind k : kFxReplayOrder) {
+        const FxKind* fx = fx_kind(k);
+        lua.set_function(fx->script, [&, fx](const std::vector<Value>& a) {
+            fx_calls.push_back(bind_fx(*fx, a, psr, &dump));
+            return Value::nil();
+        });
+    }
     lua.set_function("connect", [&](const std::vector<Value>& a) {
         edges.push_back({to_str("connect", a, 0), to_str("connect", a, 1)});
         dump += "connect(\"" + edges.back().first + "\",\"" + edges.back().second + "\")\n";
@@ -700,38 +549,17 @@ int do_refresh(td_state* s, const std::string& contents) {
             return 0;
     }
     for (auto& c : bandpasses) td_graph_add_bandpass(s->g, c.name.c_str(), c.gain, c.angle, c.wet, c.lo, c.hi, c.pass);
-    for (auto& c : compressors)
-        if (!td_graph_add_compressor(s->g, c.name.c_str(), c.gain, c.angle, c.wet, c.threshold_db, c.ratio, c.attack_ms, c.release_ms, c.knee_db, c.makeup_db))
-            return 0;
-    for (auto& c : eqs)
-        if (!td_graph_add_eq(s->g, c.name.c_str(), c.gain, c.angle, c.wet, c.kind, c.freq_hz, c.q, c.gain_db)) return 0;
-    for (auto& c : delays)
-        if (!td_graph_add_delay(s->g, c.name.c_str(), c.gain, c.angle, c.wet, c.time_ms, c.feedback, c.cross)) return 0;
-    for (auto& c : saturators)
-        if (!td_graph_add_saturator(s->g, c.name.c_str(), c.gain, c.angle, c.wet, c.kind, c.drive_db, c.bias, c.out_db, c.oversample)) return 0;
-    for (auto& c : choruses)
-        if (!td_graph_add_chorus(s->g, c.name.c_str(), c.gain, c.angle, c.wet, c.voices, c.delay_ms, c.depth_ms, c.rate_hz, c.stereo, c.shape)) return 0;
-    for (auto& c : reverbs)
-        if (!td_graph_add_reverb(s->g, c.name.c_str(), c.gain, c.angle, c.wet, c.room, c.damp, c.width, c.size)) return 0;
-    for (auto& c : gates)
-        if (!td_graph_add_gate(s->g, c.name.c_str(), c.gain, c.angle, c.wet, c.threshold_db, c.hysteresis_db, c.hold_ms, c.attack_ms, c.release_ms, c.range_db)) return 0;
-    for (auto& c : phasers)
-        if (!td_graph_add_phaser(s->g, c.name.c_str(), c.gain, c.angle, c.wet, c.stages, c.lo_hz, c.hi_hz, c.rate_hz, c.feedback, c.stereo, c.shape)) return 0;
-    for (auto& c : vocoders)
-        if (!td_graph_add_vocoder(s->g, c.name.c_str(), c.gain, c.angle, c.wet, c.bands, c.lo_hz, c.hi_hz, c.q, c.response_ms, c.out_db)) return 0;
-    for (auto& c : filters)
-        if (!td_graph_add_filter(s->g, c.name.c_str(), c.gain, c.angle, c.wet, c.kind, c.freq_hz, c.q, c.lfo_oct, c.rate_hz, c.stereo, c.shape, c.env_oct, c.sens_db,
-                                 c.attack_ms, c.release_ms)) return 0;
-    for (auto& c : limiters)
-        if (!td_graph_add_limiter(s->g, c.name.c_str(), c.gain, c.angle, c.wet, c.ceiling_db, c.lookahead_ms, c.release_ms, c.drive_db)) return 0;
-    for (auto& c : convolutions) {
-        if (!sample_index(c.sample, c.name, &si)) return 0;
-        // (the bank is loaded: a response over the cap fails here, by name, not at the first render)
-        if (const char* why = tde::conv::check_len(psr, s->sb->samples[si].len, c.length_ms)) return fail(std::string("add_convolution: convolution: ") + why);
-        if (!td_graph_add_convolution(s->g, c.name.c_str(), c.gain, c.angle, c.wet, si, c.length_ms, c.predelay_ms, c.out_db, c.norm)) return 0;
-    }
-    for (auto& c : multibands)
-        if (!td_graph_add_multiband(s->g, c.name.c_str(), c.gain, c.angle, c.wet, c.lo_hz, c.hi_hz, c.threshold_db, c.ratio, c.attack_ms, c.release_ms, c.knee_db, c.makeup_db)) return 0;
+    for (Kind k : kFxReplayOrder)
+        for (auto& c : fx_calls) {
+            if (c.kind != k) continue;
+            size_t response = 0;   // (a convolution's; every other kind keeps sample_index 0)
+            if (k == K_CONVOLUTION) {
+                if (!sample_index(c.sample, c.name, &response)) return 0;
+                // (the bank is loaded: a response over the cap fails here, by name, not at the first render)
+                if (const char* why = tde::conv::check_len(psr, s->sb->samples[response].len, c.p.conv.length_ms)) return fail(std::string(fx_kind(k)->script_prefix) + why);
+            }
+            if (!add_fx(s->g, k, c.name.c_str(), c.gain, c.angle, c.wet, c.p, response)) return 0;
+        }
     for (auto& e : edges) td_graph_connect(s->g, e.first.c_str(), e.second.c_str());   // failures only warn (state.rs:459)
     for (auto& e : key_edges) td_graph_connect_key(s->g, e.first.c_str(), e.second.c_str());   // (after the edges; failures only warn, like theirs)
     td_graph_set_output(s->g, s->output_vertex.c_str());

@@ -16,6 +16,19 @@ constexpr uint32_t kLine = 4 * kZ;      // raw input frames an output frame can 
 constexpr uint32_t kTileDefault = 256;  // output frames per workgroup (provisional; "debug.sat_tile" 128 | 256 | 384)
 
 inline bool oversample_ok(int R) { return R == 1 || R == 2 || R == 4 || R == 8; }
+inline const char* const* kind_names() {   // (the script line's names, TD_SAT_* in order)
+    static const char* const n[3] = {"hard", "cubic", "soft"};
+    return n;
+}
+// nullptr: fine, otherwise the reason
+inline const char* check(int kind, int oversample, float drive_db, float bias, float out_db) {
+    if (!(kind >= 0 && kind <= 2)) return "kind must be 0 (hard), 1 (cubic) or 2 (soft)";
+    if (!oversample_ok(oversample)) return "oversample must be 1, 2, 4 or 8";
+    if (!(drive_db >= -24.0f && drive_db <= 48.0f)) return "drive_db must lie in [-24, 48] dB";
+    if (!(bias >= -1.0f && bias <= 1.0f)) return "bias must lie in [-1, 1]";
+    if (!(out_db >= -48.0f && out_db <= 24.0f)) return "out_db must lie in [-48, 24] dB";
+    return nullptr;
+}
 inline uint32_t n_taps(int R) { return 2u * kZ * (uint32_t)R + 1u; }
 
 // h[0 .. 2ZR]: s w / sum(s w), every sum from 0.0 in ascending index

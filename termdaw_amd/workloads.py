@@ -365,32 +365,14 @@ class ProjectScript:
             g.add_adsr(name, gain, angle, wet, fidx(f, name), uo, um, note, conf)
         for name, gain, angle, wet, lo, hi, p in self.calls["add_bandpass"]:
             g.add_bandpass(name, gain, angle, wet, lo, hi, p)
-        for args in self.calls["add_compressor"]:
-            g.add_compressor(*args)
-        for args in self.calls["add_eq"]:
-            g.add_eq(*args)
-        for args in self.calls["add_delay"]:
-            g.add_delay(*args)
-        for args in self.calls["add_saturator"]:
-            g.add_saturator(*args)
-        for args in self.calls["add_chorus"]:
-            g.add_chorus(*args)
-        for args in self.calls["add_reverb"]:
-            g.add_reverb(*args)
-        for args in self.calls["add_gate"]:
-            g.add_gate(*args)
-        for args in self.calls["add_phaser"]:
-            g.add_phaser(*args)
-        for args in self.calls["add_vocoder"]:
-            g.add_vocoder(*args)
-        for args in self.calls["add_filter"]:
-            g.add_filter(*args)
-        for args in self.calls["add_limiter"]:
-            g.add_limiter(*args)
-        for args in self.calls["add_multiband"]:
-            g.add_multiband(*args)
-        for name, gain, angle, wet, smp, length_ms, predelay_ms, out_db, norm in self.calls.get("add_convolution", []):
-            g.add_convolution(name, gain, angle, wet, sidx(smp, name), length_ms, predelay_ms, out_db, norm)
+        # the effect kinds, in this order (the multiband vertices in front of the convolution ones: the front-end's replay has those
+        # two the other way round, project.cpp kFxReplayOrder; vertex indices follow from the order, so both stay)
+        for call in ("add_compressor", "add_eq", "add_delay", "add_saturator", "add_chorus", "add_reverb", "add_gate", "add_phaser",
+                     "add_vocoder", "add_filter", "add_limiter", "add_multiband", "add_convolution"):
+            for args in self.calls.get(call, []):
+                if call == "add_convolution":   # (the response by its load_sample name)
+                    args = args[:4] + (sidx(args[4], args[0]),) + args[5:]
+                getattr(g, call)(*args)
         for a, b in self.calls["connect"]:
             g.connect(a, b)
         for a, b in self.calls["connect_key"]:   # (after the connect calls, as the front-end applies them)
